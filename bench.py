@@ -18,8 +18,15 @@ zigp_comm_init).  With more than one rank the library exchange is additionally C
 with the torch.distributed sums, under a watchdog) and the outcome is part of the JSON line: `library_exchange_check`.
 `--gpus 1 --force-dist` runs this exact multi-rank code path (process group + communicator in one process) with one rank.
 
-The timed region runs with kernel event timing OFF and the side-stream overlap ON (the fast configuration); the per-kernel
-numbers behind `roofline` come from a separate short profiled pass after it (every launch timed, single stream).
+The timed region runs with kernel event timing OFF and the side-stream overlap ON (the fast configuration).
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps, writes the outputs of the last timed step
+when --dump-outputs DIR is given, and prints the JSON line.  Everything else is behind --full: the sustained-clock stamps, the
+separate short profiled pass behind `roofline` (every launch timed, single stream), the child rocprofv3 --pmc traffic passes, the
+library-exchange check of multi-rank runs, `other_configs` and the CPU baselines (the --no-* switches below still thin out a --full run).
+
+--dump-outputs DIR writes what the timed step returns to its caller, from the last timed step, as float64 DIR/<name>.npy:
+elbo.npy, elbo_data.npy, kl.npy and grad_<parameter>.npy for every trainable parameter (about 85 KB at M = 1024).
 """
 import argparse
 import hashlib
@@ -159,6 +166,16 @@ def headline(args, world, total_rows, dt):
     return {'metric': 'elbo_steps_per_sec', 'value': args.steps / dt * (total_rows / 1e6), 'unit': 'ELBO steps/s (value+gradient, 1e6-row steps, fp64)',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3,
             'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic'}
+
+
+def dump_outputs(d, out):
+    """--dump-outputs: what the timed step returned to its caller (out = (elbo_data, kl, gradient dict)) as float64 d/<name>.npy"""
+    os.makedirs(d, exist_ok=True)
+    elbo_data, kl, g = out
+    arrays = {'elbo': elbo_data - kl, 'elbo_data': elbo_data, 'kl': kl}
+    arrays.update({'grad_' + k: v for k, v in g.items()})
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + '.npy'), np.array(v, dtype=np.float64))
 
 
 def library_exchange_check(eng, dist, red_dev, p, jitter, scale, ref_out, rank, dt, args, world, total_rows, limit_s=150.0):
@@ -422,7 +439,14 @@ def main():
                     help="where the per-step all-reduce runs: torch.distributed on the packed vector (default) or ncclAllReduce inside libzigp.so")
     ap.add_argument('--force-dist', action='store_true', help='with --gpus 1: still initialise the process group and run the multi-rank code path with one rank')
     ap.add_argument('--no-library-check', action='store_true', help='skip the post-timing check of the library exchange against the torch.distributed sums')
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beyond the headline: clock stamps, profiled pass + roofline, PMC passes, library-exchange check, '
+                         'other configurations and CPU baselines')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step (ELBO, its data and KL terms, every gradient) as float64 DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         self_launch(args)              # before anything touches the GPU; never returns
@@ -491,24 +515,26 @@ def main():
     for _ in range(args.warmup):
         out = sh.elbo(p, jitter=jitter, scale=scale)
     barrier()
-    ck0 = eng.clock_stamp()
+    ck0 = eng.clock_stamp() if args.full else None
     t0 = time.time()
     for _ in range(args.steps):
         out = sh.elbo(p, jitter=jitter, scale=scale)
     barrier()
     dt = time.time() - t0
-    clock_timed = eng.clock_mhz(ck0, eng.clock_stamp())
+    clock_timed = eng.clock_mhz(ck0, eng.clock_stamp()) if args.full else None
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     elbo_data, kl = out[0], out[1]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
 
     # ---- the library exchange against the torch.distributed sums (all ranks; after the timed region, so that nothing it does can cost
     # the headline number).  Everything that can block has a time limit: zigp_comm_init gives up by itself, and a watchdog ends the
     # process (rank 0 prints the line it has, marked) if the check as a whole overruns.
     lib_check = None
-    if dist is not None and args.backend == 'nccl' and not sh.library_comm and not args.no_library_check:
+    if args.full and dist is not None and args.backend == 'nccl' and not sh.library_comm and not args.no_library_check:
         lib_check = library_exchange_check(eng, dist, red_dev, p, jitter, scale, out, rank, dt, args, world, total_rows)
     elif sh.library_comm:
         lib_check = {'status': 'the timed region itself ran on the library exchange'}
@@ -516,7 +542,7 @@ def main():
     # separate profiled pass (rank 0 only, its own shard, no all-reduce): every launch timed with HIP events on the stream
     # it runs on, single stream, so the per-kernel durations are those of kernels running alone
     prof, prof_wall_ms, clock_prof = None, None, None
-    if rank == 0 and args.profile_steps > 0:
+    if args.full and rank == 0 and args.profile_steps > 0:
         eng.set_overlap(False)
         eng.profile_sampling(1)
         eng.profile_enable(True)
@@ -549,9 +575,10 @@ def main():
                               if dist is not None else 'none'),
             'library_exchange_check': lib_check,
             'elbo': elbo_data - kl, 'elbo_data': elbo_data, 'kl': kl,
-            'sustained_clock_mhz': {'timed_region': clock_timed, 'profiled_pass': clock_prof,
-                                    'how': 's_memtime / s_memrealtime stamps on every XCD before and after the region (zigp_clock_stamp), median over XCDs; nominal 2400'},
         })
+        if args.full:
+            res['sustained_clock_mhz'] = {'timed_region': clock_timed, 'profiled_pass': clock_prof,
+                                          'how': 's_memtime / s_memrealtime stamps on every XCD before and after the region (zigp_clock_stamp), median over XCDs; nominal 2400'}
         if prof is not None:
             from zigp._lib import PROF_KERNELS
             gemm_classes = tuple(k for k in ('gemm_A1', 'gemm_A2', 'gemm_H', 'gemm_J', 'syrk') if prof[k]['launches'] > 0)   # (H: folded into J' since round 4)
@@ -626,7 +653,7 @@ def main():
                                     'kernel_ms_per_step': {k: v for k, v in kms.items() if k != 'mxm_stage'},
                                     'mxm_stage_ms_both_streams': kms.get('mxm_stage', 0.0),
                                     'chunk_loop_ms_sum': sum(v for k, v in kms.items() if k != 'mxm_stage')}
-        if not args.no_other_configs and world == 1:
+        if args.full and not args.no_other_configs and world == 1:
             try:
                 ncpu_oc = len(os.sched_getaffinity(0))
             except Exception:
@@ -636,7 +663,7 @@ def main():
             s8 = res['other_configs'].get('strong_1of8')
             if s8:
                 res['projected_8gpu_speedup'] = ms_per_step / (s8['ms_per_step'] + s8['allreduce_us_assumed'] * 1e-3)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             srows = min(args.cpu_sample_rows, N)
             try:
                 ncpu = len(os.sched_getaffinity(0))

@@ -10,6 +10,10 @@ G4  g4_kron_oracle.npz : this repo's literal Kronecker restatements (on/off, Gau
     minibatch; like G2 it guards the oracle against drift, it does not pin it to the reference.
 G3  g3_utils_pptr.npz : outputs of the REFERENCE's own `preprocessing` class (onofftf/utils_pptr.py, NumPy/pandas only,
     imported in place) on a seeded synthetic station table: time filter, location/time scaling, kernel_params.
+G5  g5_two_latents_slice.npz : the data term of the row slice in tests/test_gpu_fullsize.py::
+    test_two_latents_in_one_launch_with_different_block_counts (Mf = 300, Mg = 520, jitter 1e-6), evaluated in 80-bit extended
+    precision.  At that conditioning an fp64 evaluation carries ~1e-9 relative error of its own, and the torch oracle's value moves by
+    that much with the BLAS thread count and CPU, so the GPU value is held against this one instead.
 """
 import os
 import sys
@@ -120,10 +124,76 @@ def g4():
     np.savez_compressed(os.path.join(OUT, 'g4_kron_oracle.npz'), **out)
 
 
+# ---- G5: extended-precision data term (np.longdouble: 64-bit significand on x86) ----------------------------------------------------
+LD = np.longdouble
+
+
+def _ld_rbf(A, B, ell, var):
+    A, B = A.astype(LD) / ell.astype(LD), B.astype(LD) / ell.astype(LD)
+    d = A[:, None, :] - B[None, :, :]
+    return LD(var) * np.exp(-np.sum(d * d, axis=2) / 2)
+
+
+def _ld_chol(K):
+    n = K.shape[0]
+    L = np.zeros_like(K)
+    for j in range(n):
+        L[j, j] = np.sqrt(K[j, j] - np.dot(L[j, :j], L[j, :j]))
+        L[j + 1:, j] = (K[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+    return L
+
+
+def _ld_solve(L, B, lower):
+    n = L.shape[0]
+    A = np.zeros_like(B)
+    for i in (range(n) if lower else range(n - 1, -1, -1)):
+        s = L[i, :i] @ A[:i] if lower else L[i, i + 1:] @ A[i + 1:]
+        A[i] = (B[i] - s) / L[i, i]
+    return A
+
+
+def _ld_conditional(X, Z, ell, var, q_mu, q_sqrt, jitter):
+    """oracle/zigp_oracle_torch.py::conditional in extended precision (exact differences instead of the expanded r^2)"""
+    M = Z.shape[0]
+    L = _ld_chol(_ld_rbf(Z, Z, ell, var) + np.eye(M, dtype=LD) * LD(jitter))
+    A = _ld_solve(L, _ld_rbf(Z, X, ell, var), True)
+    fvar = LD(var) - np.sum(A * A, 0)
+    A = _ld_solve(L.T.copy(), A, False)
+    fmean = A.T @ q_mu.astype(LD).reshape(M)
+    return fmean, fvar + np.sum((A * q_sqrt.astype(LD).reshape(M, 1)) ** 2, 0)
+
+
+def ld_data_term(X, Y, p, jitter):
+    """oracle/zigp_oracle_torch.py::data_term in extended precision; erf in fp64 (point-wise, well conditioned)"""
+    from scipy.special import erf
+    fm, fv = _ld_conditional(X, p['Zf'], p['ell_f'], p['var_f'], p['u_fm'], p['u_fs_sqrt'], jitter)
+    gm, gv = _ld_conditional(X, p['Zg'], p['ell_g'], p['var_g'], p['u_gm'], p['u_gs_sqrt'], jitter)
+    z, a = gm / np.sqrt(1 + gv), 1 / np.sqrt(1 + 2 * gv)
+    cdfz = LD(0.5) * (1 + erf((z / np.sqrt(LD(2))).astype(np.float64)).astype(LD)) * (1 - LD(2e-3)) + LD(1e-3)
+    tz = np.arctan(a) / (2 * LD(np.pi)) * np.exp(-(z * z * (a * a + 1)) / 2)
+    e1, e2, ev = cdfz, cdfz - 2 * tz, cdfz - 2 * tz - cdfz * cdfz
+    e2, ev = (e2 + np.abs(e2)) / 2, (ev + np.abs(ev)) / 2
+    y, noise = Y.astype(LD).reshape(-1), LD(p['noise'])
+    ve = -np.log(2 * LD(np.pi)) / 2 - np.log(noise) / 2 - ((y - e1 * fm) ** 2 + e2 * fv + ev * fm * fm) / noise / 2
+    return np.sum(ve)
+
+
+def g5():
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), 'tests'))
+    from conftest import make_problem
+    N, Mf, Mg, seed, ell, jitter, rows = 38400, 300, 520, 31, 0.3, 1e-6, (12800, 38400)
+    X, Y, p = make_problem(N, Mf, 3, seed=seed, Mg=Mg, ell=ell)
+    Xs, Ys = X[rows[0]:rows[1]], Y[rows[0]:rows[1]]
+    d = ld_data_term(Xs, Ys, p, jitter)
+    np.savez_compressed(os.path.join(OUT, 'g5_two_latents_slice.npz'), N=N, Mf=Mf, Mg=Mg, seed=seed, ell=ell, jitter=jitter, rows=np.array(rows),
+                        X_sum=Xs.sum(), Y_sum=Ys.sum(), elbo_data=np.float64(d), elbo_data_repr=np.array(repr(d)))
+
+
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     g1()
     g2()
     g3()
     g4()
+    g5()
     print(os.listdir(OUT))

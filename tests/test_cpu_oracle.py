@@ -21,6 +21,31 @@ def test_rbf_matches_reference_kernse_np_golden():
         assert np.array_equal(o.rbf_Kdiag(X, var), g[tag + '_Kdiag'])
 
 
+def test_extended_precision_data_term_restates_the_oracle():
+    """oracle/make_golden.py::ld_data_term (the 80-bit evaluation behind G5) is the oracle's data term: on a well-conditioned problem
+    the two agree to fp64 rounding."""
+    import torch
+    import make_golden as mg
+    import zigp_oracle_torch as ot
+    X, Y, p = make_problem(600, 24, 3, seed=5, Mg=17, ell=0.3)
+    d_x = float(mg.ld_data_term(X, Y, p, 1e-2))
+    with torch.no_grad():
+        d = float(ot.data_term(ot._t(X), ot._t(Y).reshape(-1, 1), ot.make_leaves(p), 1e-2))
+    assert abs(d - d_x) <= 1e-13 * abs(d_x), (d, d_x)
+
+
+def test_g5_inputs_and_value_against_the_fp64_oracle():
+    """G5: the generator still produces the rows the extended-precision value was computed on, and the fp64 oracle lands within its own
+    rounding (~1e-9 at this conditioning, depending on the BLAS thread count and the CPU) of that value."""
+    import zigp_oracle_torch as ot
+    g = np.load(os.path.join(GOLD, 'g5_two_latents_slice.npz'))
+    X, Y, p = make_problem(int(g['N']), int(g['Mf']), 3, seed=int(g['seed']), Mg=int(g['Mg']), ell=float(g['ell']))
+    lo, hi = (int(r) for r in g['rows'])
+    assert abs(X[lo:hi].sum() - g['X_sum']) <= 1e-12 * abs(g['X_sum']) and abs(Y[lo:hi].sum() - g['Y_sum']) <= 1e-12 * abs(g['Y_sum'])
+    _, d_r, _, _ = ot.elbo_and_grad(X[lo:hi], Y[lo:hi], p, float(g['jitter']), include_kl=False, need_grad=False)
+    assert abs(d_r - float(g['elbo_data'])) <= 5e-9 * abs(float(g['elbo_data'])), (d_r, float(g['elbo_data']))
+
+
 def test_oracle_frozen_against_g2():
     """G2 freezes the restatement (values produced by this repo's oracle, not by the reference)."""
     import zigp_oracle as o

@@ -133,7 +133,7 @@ def test_bench_force_dist_runs_the_multi_rank_code_path_with_one_rank():
     of the packed vector, barriers, MAX of the times) with ONE rank, and after the timed region the library-exchange check: communicator
     through zigp_comm_init, one step through ncclAllReduce inside libzigp.so, compared with the torch.distributed sums."""
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--force-dist', '--rows', '65536', '--M', '256', '--steps', '2',
-           '--warmup', '1', '--no-cpu-baseline', '--no-other-configs', '--profile-steps', '0']
+           '--warmup', '1', '--full', '--no-cpu-baseline', '--no-other-configs', '--profile-steps', '0']
     env = dict(os.environ)
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(k, None)
@@ -159,7 +159,7 @@ def test_two_rank_rccl_exchange_matches_the_sum_of_the_shards(engine):
     sys.path.insert(0, ROOT)
     import bench
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'nccl', '--rows', '65536', '--M', '256', '--steps', '2',
-           '--warmup', '1', '--no-cpu-baseline', '--no-other-configs', '--profile-steps', '0']
+           '--warmup', '1', '--full', '--no-cpu-baseline', '--no-other-configs', '--profile-steps', '0']
     env = dict(os.environ)
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
@@ -177,3 +177,39 @@ def test_two_rank_rccl_exchange_matches_the_sum_of_the_shards(engine):
         tot += ed
         kl = k if rk == 0 else kl
     assert abs(res['elbo_data'] - tot) <= 1e-11 * abs(tot) and abs(res['kl'] - kl) <= 1e-12 * abs(kl)
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_the_last_step(engine, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: the headline line alone (no profiled pass, clock stamps,
+    other configurations or CPU baselines), and DIR holds the ELBO and the full gradient of the last timed step as float64 .npy files --
+    the same numbers as one call of the engine on the same seeded shard."""
+    sys.path.insert(0, ROOT)
+    import bench
+    out = tmp_path / 'outputs'
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--rows', '65536', '--M', '256', '--steps', '3', '--warmup', '1',
+           '--dump-outputs', str(out)]
+    env = dict(os.environ)
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
+        env.pop(k, None)
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res['metric'] == 'elbo_steps_per_sec' and res['steps'] == 3 and res['warmup'] == 1 and res['dtype'] == 'f64'
+    assert res['higher_is_better'] is True and res['ms_per_step'] > 0
+    assert abs(res['value'] - 1e3 / res['ms_per_step'] * 65536 / 1e6) <= 1e-9 * res['value']
+    for k in ('roofline', 'profiled_pass', 'sustained_clock_mhz', 'other_configs', 'cpu_baseline'):
+        assert k not in res, k
+    engine.set_chunk(0)              # the library's automatic rule, as in the bench run (other tests leave the shared engine pinned)
+    X, Y, p = bench.weak_shard(65536, 256, 3, 0, 1)
+    engine.set_data(X, Y)
+    ed, kl, g = engine.elbo(p, jitter=1e-6)
+    got = {f[:-4]: np.load(str(out / f)) for f in os.listdir(str(out))}
+    assert set(got) == {'elbo', 'elbo_data', 'kl'} | {'grad_' + k for k in g}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert float(got['elbo_data']) == res['elbo_data'] and float(got['kl']) == res['kl']
+    assert abs(float(got['elbo_data']) - ed) <= 1e-11 * abs(ed) and abs(float(got['kl']) - kl) <= 1e-12 * abs(kl)
+    for k in g:
+        a, b = got['grad_' + k].reshape(-1), np.asarray(g[k], dtype=np.float64).reshape(-1)
+        assert np.max(np.abs(a - b)) <= 1e-9 * max(np.max(np.abs(b)), 1e-300), k
