@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include <map>
+#include <memory>
 #include "../../include/zigp.h"
 #include "../../include/zigp_diag.h"
 #include "zigp_gemm.h"
@@ -17,6 +18,15 @@ struct DevBuf {
   double* p = nullptr;
   size_t cap = 0;  // doubles
   bool owned = true;   // false: p points into another buffer (alias)
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap), owned(o.owned) { o.p = nullptr; o.cap = 0; o.owned = true; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) { release(); p = o.p; cap = o.cap; owned = o.owned; o.p = nullptr; o.cap = 0; o.owned = true; }
+    return *this;
+  }
+  ~DevBuf() { release(); }
   int ensure(size_t n) {
     if (!owned) { p = nullptr; cap = 0; owned = true; }
     if (n <= cap) return 0;
@@ -33,10 +43,16 @@ struct DevBuf {
 
 enum ProfClass { PC_GEMM_A1 = 0, PC_GEMM_A2 = 1, PC_GEMM_H = 2, PC_GEMM_J = 3, PC_SYR2K = 4, PC_KUF = 5, PC_POINT = 6, PC_RED = 7, PC_MXM = 8, PC_OTHER = 9 };
 
-struct TileList {
+struct TileList {   // what a launch takes: a view of a device list that the tile cache owns (zigp_ctx::tiles)
   GemmTile* d = nullptr;
   int n = 0;     // list entries
   int per = 1;   // entries per workgroup (n is a multiple of it)
+};
+struct HipFree { void operator()(void* q) const { (void)hipFree(q); } };
+struct CachedTiles {   // an entry of the tile cache: owns the device copy of its list
+  std::unique_ptr<GemmTile, HipFree> d;
+  int n = 0, per = 1;
+  TileList view() const { return TileList{d.get(), n, per}; }
 };
 
 // Per-latent (f or g) device state of the dense path
@@ -73,6 +89,10 @@ struct KfState;     // fused Kronecker path (zigp_kronf.hip)
 struct PinnedArena {
   struct Block { char* p; size_t cap, used; };
   std::vector<Block> blocks;
+  PinnedArena() = default;
+  PinnedArena(const PinnedArena&) = delete;
+  PinnedArena& operator=(const PinnedArena&) = delete;
+  ~PinnedArena() { for (auto& b : blocks) (void)hipHostFree(b.p); }
   void reset() { for (auto& b : blocks) b.used = 0; }
   void* alloc(size_t bytes) {
     bytes = (bytes + 63) & ~(size_t)63;
@@ -83,18 +103,39 @@ struct PinnedArena {
     blocks.push_back(nb);
     return nb.p;
   }
-  void release() { for (auto& b : blocks) (void)hipHostFree(b.p); blocks.clear(); }
 };
 
-}  // namespace zigp
-
-struct zigp_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;    // stream every launch helper enqueues on (swapped to stream2 inside a TwoStream section)
+// The context's streams, events and Cholesky status word.  zigp_ctx derives from this and base classes are destroyed after the
+// members, so every buffer of the context (its DevBufs, the tile cache, the Kronecker states) is freed before the streams go.
+struct CtxHandles {
+  hipStream_t stream = nullptr;    // stream every launch helper enqueues on (switched for a scope by OnStream)
   hipStream_t stream_main = nullptr, stream2 = nullptr;
   hipStream_t stream3 = nullptr;   // dense path: buffers, zeroed accumulators and the first chunk's Kuf panels, under the M x M forward of both latents
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   hipEvent_t ev_prep_fork = nullptr, ev_prep = nullptr;
+  int* d_info = nullptr;
+  struct PendingEv { hipEvent_t a, b; int cls; };
+  std::vector<PendingEv> pending;       // profiling event pairs not yet read (prof_collect)
+  std::vector<hipEvent_t> ev_pool;
+  CtxHandles() = default;
+  CtxHandles(const CtxHandles&) = delete;
+  CtxHandles& operator=(const CtxHandles&) = delete;
+  ~CtxHandles() {
+    if (d_info) (void)hipFree(d_info);
+    for (auto& e : pending) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
+    for (auto e : ev_pool) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {ev_fork, ev_join, ev_prep_fork, ev_prep})
+      if (e) (void)hipEventDestroy(e);
+    for (hipStream_t s : {stream3, stream2, stream_main})
+      if (s) (void)hipStreamDestroy(s);
+  }
+};
+
+}  // namespace zigp
+
+struct zigp_ctx : zigp::CtxHandles {
+  ~zigp_ctx();                          // zigp_kron.hip, where KronState and KfState are complete
+  int device = 0;
   std::string err;
   int info = 0;
   int64_t fit_steps_applied = 0;       // zigp_kron_fit_steps: updates applied by the LAST call (all of them, or the ones before a failing step)
@@ -118,15 +159,12 @@ struct zigp_ctx {
   double mean_a[8] = {0}, mean_b = 0.0, mean_da[8] = {0}, mean_db = 0.0;   // 8 = zigp::MAXD (zigp_kernels.h)
   zigp::DevBuf out9;                    // predict outputs (9,Nc)
   zigp::DevBuf scratch, scratch2;       // misc
-  int* d_info = nullptr;
   zigp::PinnedArena pinned;             // host staging of the per-step transfers
-  zigp::KronState* kron = nullptr;
-  void (*kron_free)(zigp::KronState*) = nullptr;
-  zigp::KfState* kronf = nullptr;
-  void (*kronf_free)(zigp::KfState*) = nullptr;
+  std::unique_ptr<zigp::KronState> kron;
+  std::unique_ptr<zigp::KfState> kronf;
   bool kron_panels = false;             // zigp_set_kron_panels: force the panel (GEMM-core) Kronecker path
   int kron_range_tiles = 1024;          // larger-grid fused backward: rows go through in ranges of this many 16-point tiles (bounded operand spill; zigp_set_kron_range_tiles)
-  std::map<std::string, zigp::TileList> tiles;
+  std::map<std::string, zigp::CachedTiles> tiles;   // tile lists by key (get_tiles, zigp_host.h)
   // data-parallel exchange (zigp_comm_init): RCCL communicator, one rank per context / GPU
   void* comm = nullptr; int comm_rank = 0, comm_nranks = 1; int64_t comm_calls = 0;
   double comm_timeout_s = 120.0;         // zigp_comm_set_timeout: how long zigp_comm_init waits for its peers
@@ -141,9 +179,6 @@ struct zigp_ctx {
   double prof_ms[ZIGP_NCLASS] = {0};
   int64_t prof_n[ZIGP_NCLASS] = {0};
   double prof_flops[ZIGP_NCLASS] = {0};
-  struct PendingEv { hipEvent_t a, b; int cls; };
-  std::vector<PendingEv> pending;
-  std::vector<hipEvent_t> ev_pool;
 };
 
 namespace zigp {
@@ -175,27 +210,28 @@ namespace zigp {
 
 inline int fail_arg(zigp_ctx* c, const char* msg) { c->err = msg; return ZIGP_EARG; }
 
-// Two independent launch chains (the MxM stages of latents f and g) on two HIP streams: fork() after the work both
-// depend on, second() switches the helpers to stream2, join() makes the main stream wait for it.  The destructor
-// restores the main stream on every exit path.
-struct TwoStream {
+// The stream the launch helpers enqueue on (c->stream), switched for one scope: restored on every exit path.
+struct OnStream {
   zigp_ctx* c;
-  explicit TwoStream(zigp_ctx* c_) : c(c_) {}
-  ~TwoStream() { c->stream = c->stream_main; }
-  int fork() {
-    ZIGP_HIP(c, hipEventRecord(c->ev_fork, c->stream_main));
-    ZIGP_HIP(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-    return 0;
-  }
-  void second() { c->stream = c->stream2; }
-  void first() { c->stream = c->stream_main; }
-  int join() {
-    c->stream = c->stream_main;
-    ZIGP_HIP(c, hipEventRecord(c->ev_join, c->stream2));
-    ZIGP_HIP(c, hipStreamWaitEvent(c->stream_main, c->ev_join, 0));
-    return 0;
-  }
+  hipStream_t saved;
+  OnStream(zigp_ctx* c_, hipStream_t s) : c(c_), saved(c_->stream) { c->stream = s; }
+  ~OnStream() { c->stream = saved; }
+  OnStream(const OnStream&) = delete;
+  OnStream& operator=(const OnStream&) = delete;
 };
+
+// Fork: `side` waits for what the main stream has enqueued so far (ev is recorded on the main stream).
+inline int fork_side(zigp_ctx* c, hipEvent_t ev, hipStream_t side) {
+  ZIGP_HIP(c, hipEventRecord(ev, c->stream_main));
+  ZIGP_HIP(c, hipStreamWaitEvent(side, ev, 0));
+  return 0;
+}
+// Join: the main stream waits for what `side` has enqueued so far (ev is recorded on `side`).
+inline int join_side(zigp_ctx* c, hipEvent_t ev, hipStream_t side) {
+  ZIGP_HIP(c, hipEventRecord(ev, side));
+  ZIGP_HIP(c, hipStreamWaitEvent(c->stream_main, ev, 0));
+  return 0;
+}
 
 // RAII-less profiling bracket: call prof_begin before and prof_end after a group of launches.
 struct ProfScope {

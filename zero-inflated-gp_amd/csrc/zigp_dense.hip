@@ -96,11 +96,10 @@ int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D) {
 // from the start (see potrf_trtri_jobs).
 int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter, bool with_kl, bool need_grad) {
   const hipStream_t st[2] = {c->stream_main, c->stream2};
-  struct Restore { zigp_ctx* c; ~Restore() { c->stream = c->stream_main; } } restore{c};
   for (int h = 0; h < 2; ++h) {
     Latent& lt = c->lat[h];
     const int Mp = lt.Mp;
-    c->stream = st[h];
+    OnStream on(c, st[h]);
     KernHyp hyp = make_hyp(hl[h].ell, hl[h].var, D);
     hipLaunchKernelGGL(k_kuu_setup, dim3(ceil_div((int64_t)Mp * Mp, 256)), dim3(256), 0, c->stream, lt.Z.p, (int64_t)hl[h].M, hyp, jitter, lt.Kuu.p,
                        lt.L.p, lt.W.p, lt.s.p, lt.s2.p, (int64_t)Mp);
@@ -118,7 +117,7 @@ int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter
     for (int h = 0; h < 2; ++h) {
       Latent& lt = c->lat[h];
       const int Mp = lt.Mp;
-      c->stream = st[h];
+      OnStream on(c, st[h]);
       if (step == 0) lt.P_ready = false;
       double* v = lt.vec.p; double* alpha = v + Mp; double* dkinv = v + 2 * Mp; double* klv = v + 3 * Mp;
       switch (step) {
@@ -405,11 +404,9 @@ int dense_mxm_forward(zigp_ctx* c, DenseCall& k) {
   // The call's buffers, its zeroed accumulators and the first chunk's Kuf panels need the uploaded parameters only: third stream, under
   // the two factorisation chains (which are dependent launches of <= 36 workgroups).  Not while kernels are being timed (they run alone).
   k.prep_side = c->overlap == 1 && !c->prof_on;
-  if (k.prep_side) {
-    struct Guard { zigp_ctx* c; ~Guard() { c->stream = c->stream_main; } } guard{c};
-    ZIGP_HIP(c, hipEventRecord(c->ev_prep_fork, c->stream_main));
-    ZIGP_HIP(c, hipStreamWaitEvent(c->stream3, c->ev_prep_fork, 0));
-    c->stream = c->stream3;
+  if (k.prep_side) {     // the main stream waits for ev_prep before the chunk loop (run_dense)
+    ZIGP_TRY(fork_side(c, c->ev_prep_fork, c->stream3));
+    OnStream on(c, c->stream3);
     ZIGP_TRY(dense_prepare_buffers(c, k));
     if (k.has_rows)
       for (int h = 0; h < 2; ++h)
@@ -418,10 +415,9 @@ int dense_mxm_forward(zigp_ctx* c, DenseCall& k) {
   }
   {
     ProfScope ps(c, PC_MXM);     // wall time of the two concurrent chains: both events on the main stream, the second after the join
-    TwoStream ts(c);
-    ZIGP_TRY(ts.fork());
+    ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
     ZIGP_TRY(latents_forward(c, k.hl, k.D, k.jitter, true, k.need_grad));
-    ZIGP_TRY(ts.join());
+    ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   }
   return request_info(c, &k.hinfo);   // read after the final synchronisation
 }
@@ -525,22 +521,40 @@ int dense_chunk_loop(zigp_ctx* c, const DenseCall& k) {
     if (c->prof_every <= 1 || row_end - row_begin <= Nc_full) return true;   // every launch, the partial last chunk included
     return chunk_rows(n0) == Nc_full && (((n0 - row_begin) / Nc_full) % c->prof_every) == 0;
   };
-  struct SideGuard { zigp_ctx* c; ~SideGuard() { c->stream = c->stream_main; c->prof_skip = false; } } side_guard{c};
+  auto kuf = [&](int64_t n0) -> int {     // Kuf panels of both latents for the chunk at row n0
+    for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_kuf(c, c->lat[h], k.dX, k.Nrows, n0, chunk_rows(n0), D, k.ell_h[h]));
+    return 0;
+  };
+  auto kgrad = [&](int64_t n0, int64_t Nc) -> int {
+    for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_kgrad(c, c->lat[h], k.dX, k.Nrows, n0, Nc, D, k.ell_h[h]));
+    return 0;
+  };
+  // Side-stream section: stream2 forks from the main stream, runs `work` and records ev_join, which the main stream waits on
+  // (wait_side) before the next A1 -- or before panels it builds itself, or at the end of the loop.
   bool side_busy = false;
+  auto on_side = [&](auto work) -> int {
+    ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
+    OnStream on(c, c->stream2);
+    ZIGP_TRY(work());
+    ZIGP_HIP(c, hipEventRecord(c->ev_join, c->stream2));
+    side_busy = true;
+    return 0;
+  };
+  auto wait_side = [&]() -> int {
+    if (side_busy) ZIGP_HIP(c, hipStreamWaitEvent(c->stream_main, c->ev_join, 0));
+    side_busy = false;
+    return 0;
+  };
   c->prof_skip = c->prof_on && !sampled(row_begin);
-  if (!k.prep_side)     // (otherwise built on the third stream under the M x M forward: dense_mxm_forward)
-    for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_kuf(c, c->lat[h], k.dX, k.Nrows, row_begin, chunk_rows(row_begin), D, k.ell_h[h]));
+  if (!k.prep_side) ZIGP_TRY(kuf(row_begin));     // (otherwise built on the third stream under the M x M forward: dense_mxm_forward)
   for (int64_t n0 = row_begin; n0 < row_end; n0 += Nc_full) {
     const int64_t Nc = chunk_rows(n0);   // the last (partial) chunk shrinks to the next multiple of 1024 rows
     const int64_t n1 = n0 + Nc_full;
     const bool has_next = n1 < row_end;
     const bool timed = sampled(n0), timed_next = has_next && sampled(n1);
     c->prof_skip = c->prof_on && !timed;
-    if (side_busy) {
-      // A1 of this chunk needs the Kuf panels the side stream built behind the previous chunk's kgrads (which read J' and gm)
-      ZIGP_HIP(c, hipStreamWaitEvent(c->stream_main, c->ev_join, 0));
-      side_busy = false;
-    }
+    // A1 of this chunk needs the Kuf panels the side stream built behind the previous chunk's kgrads (which read J' and gm)
+    ZIGP_TRY(wait_side());
     // gradient steps with zigp_set_overlap(1): the point-wise stage rides in the J' launch (run_gemm_j_pw: cfg3 -0.4 % same-box,
     // profiles/r05t_ab_fuse_pointwise.log); timed chunks and overlap 0 keep every kernel on its own, as for the side stream
     bool pw_fused = false;
@@ -550,51 +564,30 @@ int dense_chunk_loop(zigp_ctx* c, const DenseCall& k) {
     // (cfg3 value-only: the 4 ms of panel building per pass were serial on the main stream)
     const bool kuf_fwd_side = c->overlap == 1 && c->fwd_kuf_side && !k.need_grad && has_next && !timed && !timed_next;
     std::function<int()> after_a1;
-    if (kuf_fwd_side)
-      after_a1 = [&]() -> int {
-        ZIGP_HIP(c, hipEventRecord(c->ev_fork, c->stream_main));
-        ZIGP_HIP(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-        c->stream = c->stream2;
-        int rc = 0;
-        for (int h = 0; h < 2 && !rc; ++h) rc = latent_chunk_kuf(c, c->lat[h], k.dX, k.Nrows, n1, chunk_rows(n1), D, k.ell_h[h]);
-        c->stream = c->stream_main;
-        if (rc) return rc;
-        ZIGP_HIP(c, hipEventRecord(c->ev_join, c->stream2));
-        side_busy = true;
-        return 0;
-      };
+    if (kuf_fwd_side) after_a1 = [&] { return on_side([&] { return kuf(n1); }); };
     ZIGP_TRY(chunk_forward(c, Nc, k.need_grad, (c->overlap == 1 && k.need_grad && !k.predict && !timed) ? &pwa : nullptr, &pw_fused, after_a1));
     if (!pw_fused) ZIGP_TRY(dense_pointwise(c, k, n0, Nc));
     // side work of this chunk: its kgrads and the next chunk's Kuf panels (gradient mode only: without the SYRKs there is
     // nothing on the main stream to hide them under)
     const bool kgrad_side = c->overlap == 1 && k.need_grad && !timed;
     const bool kuf_side = kgrad_side && has_next && !timed_next;
-    if (kgrad_side) {
-      ZIGP_HIP(c, hipEventRecord(c->ev_fork, c->stream_main));
-      ZIGP_HIP(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-      c->stream = c->stream2;
-      // (the next chunk's panels BEFORE this chunk's kgrads was measured and dropped: cfg2 +0.1 ms, HISTORY.md section 5 r4)
-      for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_kgrad(c, c->lat[h], k.dX, k.Nrows, n0, Nc, D, k.ell_h[h]));
-      if (kuf_side)
-        for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_kuf(c, c->lat[h], k.dX, k.Nrows, n1, chunk_rows(n1), D, k.ell_h[h]));
-      ZIGP_HIP(c, hipEventRecord(c->ev_join, c->stream2));
-      side_busy = true;
-      c->stream = c->stream_main;
-    }
+    if (kgrad_side)
+      ZIGP_TRY(on_side([&]() -> int {
+        // (the next chunk's panels BEFORE this chunk's kgrads was measured and dropped: cfg2 +0.1 ms, HISTORY.md section 5 r4)
+        ZIGP_TRY(kgrad(n0, Nc));
+        return kuf_side ? kuf(n1) : 0;
+      }));
     if (k.need_grad) {
-      if (!kgrad_side)
-        for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_kgrad(c, c->lat[h], k.dX, k.Nrows, n0, Nc, D, k.ell_h[h]));
+      if (!kgrad_side) ZIGP_TRY(kgrad(n0, Nc));
       for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_syrk(c, c->lat[h], Nc));
     }
     if (has_next && !kuf_side && !kuf_fwd_side) {   // a timed next chunk gets its panels from the main stream, with the side stream drained
-      if (side_busy) { ZIGP_HIP(c, hipStreamWaitEvent(c->stream_main, c->ev_join, 0)); side_busy = false; }
+      ZIGP_TRY(wait_side());
       c->prof_skip = c->prof_on && !timed_next;
-      for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_kuf(c, c->lat[h], k.dX, k.Nrows, n1, chunk_rows(n1), D, k.ell_h[h]));
+      ZIGP_TRY(kuf(n1));
     }
   }
-  if (side_busy) { ZIGP_HIP(c, hipStreamWaitEvent(c->stream_main, c->ev_join, 0)); side_busy = false; }
-  c->prof_skip = false;
-  return 0;
+  return wait_side();
 }
 
 // The call's result vector (layout: k_dense_pack) is assembled on the device, summed over the ranks of a data-parallel run where it
@@ -660,17 +653,18 @@ int run_dense(zigp_ctx* c, const zigp_params* p, const double* dX, const double*
   ZIGP_TRY(dense_mxm_forward(c, k));
   if (k.prep_side) ZIGP_HIP(c, hipStreamWaitEvent(c->stream_main, c->ev_prep, 0));
   else ZIGP_TRY(dense_prepare_buffers(c, k));
-  ZIGP_TRY(dense_chunk_loop(c, k));
+  const int rc = dense_chunk_loop(c, k);
+  c->prof_skip = false;   // the loop sets it for the chunks it does not time; cleared on every exit path
+  ZIGP_TRY(rc);
   if (predict) { ZIGP_HIP(c, hipStreamSynchronize(c->stream)); prof_collect(c); return info_result(c, k.hinfo, "Kuu"); }
   if (k.need_grad) {
     ProfScope ps(c, PC_MXM);     // wall time of the two concurrent chains, as in the forward: both events on the main stream, the second after the join
-    TwoStream ts(c);
-    ZIGP_TRY(ts.fork());
+    ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
     for (int h = 0; h < 2; ++h) {
-      if (h == 1) ts.second();
+      OnStream on(c, h == 0 ? c->stream_main : c->stream2);
       ZIGP_TRY(latent_mxm_backward(c, c->lat[h], D, jitter, k.has_rows, include_kl != 0));
     }
-    ZIGP_TRY(ts.join());
+    ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   }
   return dense_gather(c, k, elbo_data, kl, grads);
 }
@@ -710,6 +704,7 @@ int zigp_create(zigp_ctx** out, int device_id) {
   return ZIGP_OK;
 }
 
+// The context's destructor frees its buffers, then its events and streams (zigp_ctx.h); what must come first stays here.
 int zigp_destroy(zigp_ctx* c) {
   if (!c) return ZIGP_EARG;
   (void)hipSetDevice(c->device);
@@ -717,27 +712,6 @@ int zigp_destroy(zigp_ctx* c) {
   (void)hipStreamSynchronize(c->stream2);
   if (c->stream3) (void)hipStreamSynchronize(c->stream3);
   if (c->comm) { RcclApi* api = rccl_api(nullptr); if (api) (void)api->CommDestroy(static_cast<ncclComm_t>(c->comm)); c->comm = nullptr; }
-  for (int h = 0; h < 2; ++h) {
-    Latent& l = c->lat[h];
-    DevBuf* bs[] = {&l.Z, &l.ell, &l.u, &l.s, &l.s2, &l.Kuu, &l.L, &l.W, &l.K, &l.A1, &l.Jp, &l.Wp, &l.Wt, &l.Wpt, &l.P, &l.Qt, &l.Rt, &l.a1gm, &l.part, &l.gm, &l.gv, &l.du, &l.dsq, &l.krow,
-                    &l.dLpart, &l.T1, &l.T2, &l.T3, &l.G, &l.vec, &l.sk};
-    for (DevBuf* b : bs) b->release();
-  }
-  DevBuf* bs[] = {&c->ownX, &c->ownY, &c->pw_part, &c->out9, &c->scratch, &c->scratch2, &c->packed, &c->parm, &c->selX, &c->selY, &c->selIdx};
-  for (DevBuf* b : bs) b->release();
-  if (c->kron && c->kron_free) c->kron_free(c->kron);
-  if (c->kronf && c->kronf_free) c->kronf_free(c->kronf);
-  for (auto& kv : c->tiles) if (kv.second.d) (void)hipFree(kv.second.d);
-  for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-  if (c->d_info) (void)hipFree(c->d_info);
-  c->pinned.release();
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-  if (c->ev_prep_fork) (void)hipEventDestroy(c->ev_prep_fork);
-  if (c->ev_prep) (void)hipEventDestroy(c->ev_prep);
-  if (c->stream3) (void)hipStreamDestroy(c->stream3);
-  if (c->stream2) (void)hipStreamDestroy(c->stream2);
-  if (c->stream_main) (void)hipStreamDestroy(c->stream_main);
   delete c;
   return ZIGP_OK;
 }
@@ -904,12 +878,9 @@ int zigp_prior_kl(zigp_ctx* c, const zigp_params* p, double jitter, double* kl2)
   ZIGP_TRY(begin_staged_call(c));
   ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
   ZIGP_TRY(latents_upload(c, hl, p->D));
-  {
-    TwoStream ts(c);
-    ZIGP_TRY(ts.fork());
-    ZIGP_TRY(latents_forward(c, hl, p->D, jitter, true, false));
-    ZIGP_TRY(ts.join());
-  }
+  ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
+  ZIGP_TRY(latents_forward(c, hl, p->D, jitter, true, false));
+  ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   double klh[2] = {0.0, 0.0};
   for (int h = 0; h < 2; ++h)
     ZIGP_HIP(c, hipMemcpyAsync(&klh[h], c->lat[h].vec.p + 3 * c->lat[h].Mp, sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1000,23 +971,17 @@ int zigp_test_kuf(zigp_ctx* c, int64_t N, int32_t M, int32_t D, const double* X,
   for (int m = 0; m < M; ++m)
     for (int d = 0; d < D; ++d) zs[(size_t)m * D + d] = Z[(size_t)m * D + d] * kh.scale[d];
   DevBuf dx, dz, dk;
-  auto body = [&]() -> int {
-    ZIGP_ENSURE(c, dx, (size_t)N * D); ZIGP_ENSURE(c, dz, zs.size()); ZIGP_ENSURE(c, dk, hk.size());
-    ZIGP_HIP(c, hipMemcpyAsync(dx.p, X, sizeof(double) * N * D, hipMemcpyHostToDevice, c->stream));
-    ZIGP_HIP(c, hipMemcpyAsync(dz.p, zs.data(), sizeof(double) * zs.size(), hipMemcpyHostToDevice, c->stream));
-    const dim3 grid((unsigned)(Nc / 512), Mp / 16), block(256);
+  ZIGP_ENSURE(c, dx, (size_t)N * D); ZIGP_ENSURE(c, dz, zs.size()); ZIGP_ENSURE(c, dk, hk.size());
+  ZIGP_HIP(c, hipMemcpyAsync(dx.p, X, sizeof(double) * N * D, hipMemcpyHostToDevice, c->stream));
+  ZIGP_HIP(c, hipMemcpyAsync(dz.p, zs.data(), sizeof(double) * zs.size(), hipMemcpyHostToDevice, c->stream));
+  const dim3 grid((unsigned)(Nc / 512), Mp / 16), block(256);
 #define ZIGP_KUF(DD) \
   case DD: hipLaunchKernelGGL(k_kuf_build<DD>, grid, block, 0, c->stream, dx.p, N, (int64_t)0, dz.p, M, kh, dk.p, Nc); break;
-    switch (D) { ZIGP_KUF(1) ZIGP_KUF(2) ZIGP_KUF(3) ZIGP_KUF(4) ZIGP_KUF(5) ZIGP_KUF(6) ZIGP_KUF(7) ZIGP_KUF(8) }
+  switch (D) { ZIGP_KUF(1) ZIGP_KUF(2) ZIGP_KUF(3) ZIGP_KUF(4) ZIGP_KUF(5) ZIGP_KUF(6) ZIGP_KUF(7) ZIGP_KUF(8) }
 #undef ZIGP_KUF
-    ZIGP_HIP(c, hipGetLastError());
-    ZIGP_HIP(c, hipMemcpyAsync(hk.data(), dk.p, sizeof(double) * hk.size(), hipMemcpyDeviceToHost, c->stream));
-    ZIGP_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
-  };
-  const int rc = body();
-  dx.release(); dz.release(); dk.release();
-  if (rc) return rc;
+  ZIGP_HIP(c, hipGetLastError());
+  ZIGP_HIP(c, hipMemcpyAsync(hk.data(), dk.p, sizeof(double) * hk.size(), hipMemcpyDeviceToHost, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
   for (int m = 0; m < M; ++m) memcpy(K + (size_t)m * N, &hk[(size_t)m * Nc], sizeof(double) * N);
   return ZIGP_OK;
 }
@@ -1068,25 +1033,18 @@ int zigp_test_gemm(zigp_ctx* c, int32_t transA, int32_t transB, int64_t m, int64
   for (int64_t i = 0; i < ar0; ++i) memcpy(&ha[i * ac], &A[i * ac0], sizeof(double) * ac0);
   for (int64_t i = 0; i < br0; ++i) memcpy(&hb[i * bc], &B[i * bc0], sizeof(double) * bc0);
   DevBuf da, db, dc;
-  int rc = 0;
-  auto body = [&]() -> int {
-    ZIGP_ENSURE(c, da, ha.size()); ZIGP_ENSURE(c, db, hb.size()); ZIGP_ENSURE(c, dc, hc.size());
-    ZIGP_HIP(c, hipMemcpyAsync(da.p, ha.data(), sizeof(double) * ha.size(), hipMemcpyHostToDevice, c->stream));
-    ZIGP_HIP(c, hipMemcpyAsync(db.p, hb.data(), sizeof(double) * hb.size(), hipMemcpyHostToDevice, c->stream));
-    TileList tl;
-    ZIGP_TRY(tiles_full(c, (int)(mp / BM), (int)(np / BN), (int)(kp / BK), tl));
-    GemmArgs g = mk_args(da.p, ac, db.p, bc, dc.p, np);
-    if (!transA && !transB) ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_MNCONTIG, false>(c, tl, g, EpiStore())));
-    if (transA && !transB) ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false>(c, tl, g, EpiStore())));
-    if (!transA && transB) ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_KCONTIG, false>(c, tl, g, EpiStore())));
-    if (transA && transB) ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_KCONTIG, false>(c, tl, g, EpiStore())));
-    ZIGP_HIP(c, hipMemcpyAsync(hc.data(), dc.p, sizeof(double) * hc.size(), hipMemcpyDeviceToHost, c->stream));
-    ZIGP_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
-  };
-  rc = body();
-  da.release(); db.release(); dc.release();
-  if (rc) return rc;
+  ZIGP_ENSURE(c, da, ha.size()); ZIGP_ENSURE(c, db, hb.size()); ZIGP_ENSURE(c, dc, hc.size());
+  ZIGP_HIP(c, hipMemcpyAsync(da.p, ha.data(), sizeof(double) * ha.size(), hipMemcpyHostToDevice, c->stream));
+  ZIGP_HIP(c, hipMemcpyAsync(db.p, hb.data(), sizeof(double) * hb.size(), hipMemcpyHostToDevice, c->stream));
+  TileList tl;
+  ZIGP_TRY(tiles_full(c, (int)(mp / BM), (int)(np / BN), (int)(kp / BK), tl));
+  GemmArgs g = mk_args(da.p, ac, db.p, bc, dc.p, np);
+  if (!transA && !transB) ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_MNCONTIG, false>(c, tl, g, EpiStore())));
+  if (transA && !transB) ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false>(c, tl, g, EpiStore())));
+  if (!transA && transB) ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_KCONTIG, false>(c, tl, g, EpiStore())));
+  if (transA && transB) ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_KCONTIG, false>(c, tl, g, EpiStore())));
+  ZIGP_HIP(c, hipMemcpyAsync(hc.data(), dc.p, sizeof(double) * hc.size(), hipMemcpyDeviceToHost, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
   for (int64_t i = 0; i < m; ++i) memcpy(&C[i * n], &hc[i * np], sizeof(double) * n);
   return ZIGP_OK;
 }
@@ -1102,32 +1060,27 @@ int zigp_test_potrf_trtri(zigp_ctx* c, int64_t n, const double* A, double* L, do
     else ha[i * Mp + i] = 1.0;
   }
   DevBuf dl, dw, dt, dplanes;
-  auto body = [&]() -> int {
-    ZIGP_ENSURE(c, dl, ha.size()); ZIGP_ENSURE(c, dw, ha.size()); ZIGP_ENSURE(c, dt, ha.size());
-    ZIGP_HIP(c, hipMemcpyAsync(dl.p, ha.data(), sizeof(double) * ha.size(), hipMemcpyHostToDevice, c->stream));
-    ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
-    if (split_k) {     // the chain as the dense M x M forward runs it: every block product cut into k slices (run_gemm_sk_tiles)
-      const PotrfJob job = {dl.p, dw.p, dt.p, Mp, true, (int)n, 0.0, false, &dplanes};
-      const hipStream_t st = c->stream;
-      ZIGP_TRY(potrf_trtri_jobs(c, 1, &job, &st));
-    } else ZIGP_TRY(potrf_trtri(c, dl.p, dw.p, dt.p, Mp, true, (int)n));
-    ZIGP_TRY(check_info(c, "A"));
-    std::vector<double> ho(ha.size());
-    if (L) {
-      ZIGP_HIP(c, hipMemcpyAsync(ho.data(), dl.p, sizeof(double) * ho.size(), hipMemcpyDeviceToHost, c->stream));
-      ZIGP_HIP(c, hipStreamSynchronize(c->stream));
-      for (int64_t i = 0; i < n; ++i) memcpy(&L[i * n], &ho[i * Mp], sizeof(double) * n);
-    }
-    if (W) {
-      ZIGP_HIP(c, hipMemcpyAsync(ho.data(), dw.p, sizeof(double) * ho.size(), hipMemcpyDeviceToHost, c->stream));
-      ZIGP_HIP(c, hipStreamSynchronize(c->stream));
-      for (int64_t i = 0; i < n; ++i) memcpy(&W[i * n], &ho[i * Mp], sizeof(double) * n);
-    }
-    return 0;
-  };
-  int rc = body();
-  dl.release(); dw.release(); dt.release(); dplanes.release();
-  return rc;
+  ZIGP_ENSURE(c, dl, ha.size()); ZIGP_ENSURE(c, dw, ha.size()); ZIGP_ENSURE(c, dt, ha.size());
+  ZIGP_HIP(c, hipMemcpyAsync(dl.p, ha.data(), sizeof(double) * ha.size(), hipMemcpyHostToDevice, c->stream));
+  ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
+  if (split_k) {     // the chain as the dense M x M forward runs it: every block product cut into k slices (run_gemm_sk_tiles)
+    const PotrfJob job = {dl.p, dw.p, dt.p, Mp, true, (int)n, 0.0, false, &dplanes};
+    const hipStream_t st = c->stream;
+    ZIGP_TRY(potrf_trtri_jobs(c, 1, &job, &st));
+  } else ZIGP_TRY(potrf_trtri(c, dl.p, dw.p, dt.p, Mp, true, (int)n));
+  ZIGP_TRY(check_info(c, "A"));
+  std::vector<double> ho(ha.size());
+  if (L) {
+    ZIGP_HIP(c, hipMemcpyAsync(ho.data(), dl.p, sizeof(double) * ho.size(), hipMemcpyDeviceToHost, c->stream));
+    ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+    for (int64_t i = 0; i < n; ++i) memcpy(&L[i * n], &ho[i * Mp], sizeof(double) * n);
+  }
+  if (W) {
+    ZIGP_HIP(c, hipMemcpyAsync(ho.data(), dw.p, sizeof(double) * ho.size(), hipMemcpyDeviceToHost, c->stream));
+    ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+    for (int64_t i = 0; i < n; ++i) memcpy(&W[i * n], &ho[i * Mp], sizeof(double) * n);
+  }
+  return 0;
 }
 
 }  // extern "C"

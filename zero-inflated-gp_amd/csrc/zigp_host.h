@@ -19,21 +19,26 @@ struct EpiPhi {  // Phi: keep strictly-lower, halve the diagonal, zero above
 static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 
+// Device copy of a tile list into the context's cache under `key` (the cache entry owns it)
+static int put_tiles(zigp_ctx* c, const std::string& key, const std::vector<GemmTile>& v, int per, TileList& out) {
+  CachedTiles t;
+  t.n = (int)v.size(); t.per = per;
+  if (t.n > 0) {
+    GemmTile* d = nullptr;
+    ZIGP_HIP(c, hipMalloc((void**)&d, sizeof(GemmTile) * v.size()));
+    t.d.reset(d);
+    ZIGP_HIP(c, hipMemcpy(d, v.data(), sizeof(GemmTile) * v.size(), hipMemcpyHostToDevice));
+  }
+  out = c->tiles.emplace(key, std::move(t)).first->second.view();
+  return 0;
+}
 template <class F>
-static int get_tiles(zigp_ctx* c, const std::string& key, F build, TileList& out, int per = 1) {
+static int get_tiles(zigp_ctx* c, const std::string& key, F build, TileList& out) {
   auto it = c->tiles.find(key);
-  if (it != c->tiles.end()) { out = it->second; return 0; }
+  if (it != c->tiles.end()) { out = it->second.view(); return 0; }
   std::vector<GemmTile> v;
   build(v);
-  TileList tl;
-  tl.n = (int)v.size(); tl.per = per;
-  if (tl.n > 0) {
-    ZIGP_HIP(c, hipMalloc((void**)&tl.d, sizeof(GemmTile) * v.size()));
-    ZIGP_HIP(c, hipMemcpy(tl.d, v.data(), sizeof(GemmTile) * v.size(), hipMemcpyHostToDevice));
-  }
-  c->tiles[key] = tl;
-  out = tl;
-  return 0;
+  return put_tiles(c, key, v, 1, out);
 }
 
 static inline GemmTile mk_tile(int bi, int bj, int kbeg, int kend, int slice = 0) {
@@ -234,10 +239,10 @@ static int tiles_trmm(zigp_ctx* c, bool lower, int nbm, int nbn, bool paired, Ti
   const std::string key = std::string(lower ? "trl:" : "tru:") + std::to_string(nbm) + ":" + std::to_string(nbn) + (paired ? ":p" : ":l") +
                           (tail_units > 0 ? ":t" + std::to_string(tail_units) + ":" + std::to_string(tail_bins) : std::string());
   auto it = c->tiles.find(key);
-  if (it != c->tiles.end()) { tl = it->second; return 0; }
+  if (it != c->tiles.end()) { tl = it->second.view(); return 0; }
   std::vector<GemmTile> list;
   const int per = build_trmm_list(lower, nbm, nbn, paired, tail_units, tail_bins, list);
-  return get_tiles(c, key, [&](std::vector<GemmTile>& v) { v = list; }, tl, per);
+  return put_tiles(c, key, list, per, tl);
 }
 // The paired order has nbn * ceil(nbm / 2) units of EQUAL length per latent: it pays (2.2x fewer bytes, +6 % on the triangular
 // products) where the units of BOTH latents, launched together (run_gemm2), fill whole waves of the 512 resident workgroups --
@@ -434,8 +439,6 @@ static int run_gemm_sk_tiles(zigp_ctx* c, DevBuf& planes, const std::string& key
 // the split-K block products of the inverse (nullptr: plain launches, one workgroup per tile)
 struct PotrfJob { double* L; double* W; double* T; int Mp; bool want_W; int Mreal; double piv_tol; bool prepared; DevBuf* planes; };
 static int potrf_trtri_jobs(zigp_ctx* c, int njobs, const PotrfJob* jobs, const hipStream_t* streams) {
-  hipStream_t const saved = c->stream;
-  struct Restore { zigp_ctx* c; hipStream_t s; ~Restore() { c->stream = s; } } restore{c, saved};
   const int kb = BM / BK;  // k-steps per block
   const size_t shm = sizeof(double) * PB * PBLD;
   int nbmax = 0;
@@ -443,7 +446,7 @@ static int potrf_trtri_jobs(zigp_ctx* c, int njobs, const PotrfJob* jobs, const 
   // c->d_info is cleared by the caller (several factorizations may share one check_info)
   for (int q = 0; q < njobs; ++q) {
     if (jobs[q].prepared) continue;
-    c->stream = streams[q];
+    OnStream on(c, streams[q]);
     ZIGP_HIP(c, hipMemsetAsync(jobs[q].W, 0, sizeof(double) * jobs[q].Mp * jobs[q].Mp, c->stream));
   }
   for (int j = 0; j < nbmax; ++j) {
@@ -452,7 +455,7 @@ static int potrf_trtri_jobs(zigp_ctx* c, int njobs, const PotrfJob* jobs, const 
         const PotrfJob& J = jobs[q];
         const int Mp = J.Mp, nb = Mp / BM, Mreal = (J.Mreal < 0 || J.Mreal > Mp) ? Mp : J.Mreal;
         if (j >= nb) continue;
-        c->stream = streams[q];
+        OnStream on(c, streams[q]);
         double* Lb = J.L; double* Wb = J.W;
         if (step == 0) {
           double* Ajj = Lb + (int64_t)j * BM * Mp + (int64_t)j * BM;
@@ -489,7 +492,7 @@ static int potrf_trtri_jobs(zigp_ctx* c, int njobs, const PotrfJob* jobs, const 
     for (int q = 0; q < njobs; ++q) {
       const int Mp = jobs[q].Mp, nb = Mp / BM;
       if (bi + 1 >= nb || jobs[q].prepared) continue;
-      c->stream = streams[q];
+      OnStream on(c, streams[q]);
       ZIGP_HIP(c, hipMemset2DAsync(jobs[q].L + (int64_t)bi * BM * Mp + (int64_t)(bi + 1) * BM, sizeof(double) * Mp, 0,
                                    sizeof(double) * (size_t)(Mp - (bi + 1) * BM), BM, c->stream));
     }
@@ -500,7 +503,7 @@ static int potrf_trtri_jobs(zigp_ctx* c, int njobs, const PotrfJob* jobs, const 
         const PotrfJob& J = jobs[q];
         const int Mp = J.Mp, nb = Mp / BM;
         if (!J.want_W || b >= nb) continue;
-        c->stream = streams[q];
+        OnStream on(c, streams[q]);
         auto gen1 = [&](std::vector<GemmTile>& v) {
           for (int lo = 0; lo < nb; lo += 2 * b) {
             const int mid = lo + b, hi = std::min(lo + 2 * b, nb);

@@ -40,22 +40,6 @@ struct KronState {
   DevBuf X, Y, acc, out9;
 };
 
-static void kron_free(KronState* k) {
-  for (int h = 0; h < 2; ++h) {
-    KronLatent& l = k->lat[h];
-    for (int p = 0; p < 2; ++p) {
-      KronFactor& f = l.f[p];
-      DevBuf* bs[] = {&f.Z, &f.K, &f.L, &f.W, &f.P, &f.T, &f.dP, &f.G, &f.krow, &f.Kp, &f.Ap, &f.Asq, &f.dA, &f.E, &f.PdA, &f.Bx, &f.Cx};
-      for (DevBuf* b : bs) b->release();
-    }
-    DevBuf* bs[] = {&l.U, &l.S, &l.S2, &l.Al, &l.T0, &l.T1, &l.dAl, &l.dS2, &l.dU, &l.part, &l.gm, &l.gv, &l.dq0, &l.dq1, &l.planes, &l.vec};
-    for (DevBuf* b : bs) b->release();
-  }
-  DevBuf* bs[] = {&k->X, &k->Y, &k->acc, &k->out9};
-  for (DevBuf* b : bs) b->release();
-  delete k;
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------------------------------
@@ -532,6 +516,10 @@ int latent_backward(zigp_ctx* c, KronLatent& lt, const double* dX, int64_t N, in
 
 #include "zigp_kronf.hip"
 
+// Defined here, where KronState and KfState are complete.  The members go in reverse order of declaration, then the streams and
+// events of the base (zigp_ctx.h).
+zigp_ctx::~zigp_ctx() = default;
+
 namespace {
 
 int kron_run_panels(zigp_ctx* c, const zigp_kron_params* p, const double* X, const double* Y, int64_t N, double jitter, double scale,
@@ -598,7 +586,7 @@ int kron_run_panels(zigp_ctx* c, const zigp_kron_params* p, const double* X, con
                     double g_offset, double f_mu, int include_kl, bool predict, double* out9, double* elbo_data, double* kl, zigp_kron_grads* grads,
                     int lik, double* d_offset, bool dev_xy) {
   const int nlat = (lik == ZIGP_LIK_ONOFF) ? 2 : 1;   // single-latent heads use the f latent only
-  if (!c->kron) { c->kron = new (std::nothrow) KronState(); c->kron_free = kron_free; if (!c->kron) { c->err = "out of memory"; return ZIGP_EHIP; } }
+  if (!c->kron) { c->kron.reset(new (std::nothrow) KronState()); if (!c->kron) { c->err = "out of memory"; return ZIGP_EHIP; } }
   KronState& ks = *c->kron;
   ZIGP_TRY(begin_staged_call(c));
   const bool need_grad = grads != nullptr && !predict;
@@ -616,15 +604,13 @@ int kron_run_panels(zigp_ctx* c, const zigp_kron_params* p, const double* X, con
                           {{p->M0g, p->M1g}, {p->Z0g, p->Z1g}, {p->ell0g, p->ell1g}, {p->var0g, p->var1g}, p->u_gm, p->u_gs_sqrt}};
   if (nlat == 1) hl[1] = hl[0];
   ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
-  {
-    TwoStream ts(c);   // the two latents are independent launch chains of small kernels: f on the main stream, g on stream2
-    ZIGP_TRY(ts.fork());
-    for (int h = 0; h < nlat; ++h) {
-      if (h == 1) ts.second();
-      ZIGP_TRY(latent_setup(c, ks.lat[h], hl[h], D0, D1, jitter));
-    }
-    ZIGP_TRY(ts.join());
+  // the two latents are independent launch chains of small kernels: f on the main stream, g on stream2
+  ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
+  for (int h = 0; h < nlat; ++h) {
+    OnStream on(c, h == 0 ? c->stream_main : c->stream2);
+    ZIGP_TRY(latent_setup(c, ks.lat[h], hl[h], D0, D1, jitter));
   }
+  ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   int* hinfo = nullptr;
   ZIGP_TRY(request_info(c, &hinfo));   // read after the final synchronisation
   // KL scalars (value) -- before the backward pass overwrites nothing it needs
@@ -638,17 +624,14 @@ int kron_run_panels(zigp_ctx* c, const zigp_kron_params* p, const double* X, con
       ZIGP_TRY(download(c, lt.vec.p + Mq0 + Mq1, 8, &hkl[h]));
     }
   }
-  {
-    TwoStream ts(c);
-    ZIGP_TRY(ts.fork());
-    for (int h = 0; h < nlat; ++h) {
-      if (h == 1) ts.second();
-      KronLatent& lt = ks.lat[h];
-      ZIGP_TRY(latent_forward_panels(c, lt, ks.X.p, N, Nc, ldx));
-      ZIGP_ENSURE(c, lt.gm, Nc); ZIGP_ENSURE(c, lt.gv, Nc); ZIGP_ENSURE(c, lt.dq0, Nc); ZIGP_ENSURE(c, lt.dq1, Nc);
-    }
-    ZIGP_TRY(ts.join());
+  ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
+  for (int h = 0; h < nlat; ++h) {
+    OnStream on(c, h == 0 ? c->stream_main : c->stream2);
+    KronLatent& lt = ks.lat[h];
+    ZIGP_TRY(latent_forward_panels(c, lt, ks.X.p, N, Nc, ldx));
+    ZIGP_ENSURE(c, lt.gm, Nc); ZIGP_ENSURE(c, lt.gv, Nc); ZIGP_ENSURE(c, lt.dq0, Nc); ZIGP_ENSURE(c, lt.dq1, Nc);
   }
+  ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   const int blocks = (int)(Nc / PW_THREADS);
   ZIGP_ENSURE(c, ks.acc, (size_t)blocks * KPW_ACC);
   KronPwArgs a;
@@ -677,10 +660,9 @@ int kron_run_panels(zigp_ctx* c, const zigp_kron_params* p, const double* X, con
 
   double *hkrow[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, *hgu[2] = {nullptr, nullptr}, *hgs[2] = {nullptr, nullptr};
   if (need_grad) {
-    TwoStream ts(c);
-    ZIGP_TRY(ts.fork());
+    ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
     for (int h = 0; h < nlat; ++h) {
-      if (h == 1) ts.second();
+      OnStream on(c, h == 0 ? c->stream_main : c->stream2);
       KronLatent& lt = ks.lat[h];
       ZIGP_TRY(latent_backward(c, lt, ks.X.p, N, Nc, ldx, include_kl != 0));
       const int M0 = lt.f[0].M, M1 = lt.f[1].M, Mq0 = lt.f[0].Mq, Mq1 = lt.f[1].Mq;
@@ -701,7 +683,7 @@ int kron_run_panels(zigp_ctx* c, const zigp_kron_params* p, const double* X, con
       ZIGP_TRY(download(c, lt.T0.p, (size_t)M0 * M1, &hgu[h]));
       ZIGP_TRY(download(c, lt.T1.p, (size_t)M0 * M1, &hgs[h]));
     }
-    ZIGP_TRY(ts.join());
+    ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   }
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));
   ZIGP_TRY(info_result(c, hinfo, "a Kronecker factor of Kuu"));

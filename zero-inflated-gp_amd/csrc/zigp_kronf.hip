@@ -1091,11 +1091,6 @@ constexpr size_t KF_BWD_LDS = sizeof(double) * (KF_WAVES * 4 * 16 * KF_NBMAX * K
 struct KfState {
   DevBuf in, mat, pts, acc, res, out, spill, fit;
 };
-static void kf_free(KfState* k) {
-  DevBuf* bs[] = {&k->in, &k->mat, &k->pts, &k->acc, &k->res, &k->out, &k->spill, &k->fit};
-  for (DevBuf* b : bs) b->release();
-  delete k;
-}
 
 // Variants of the point-stage kernels by capacity (16-row blocks per factor):
 //   small  <2, 2>  accumulators in registers (grids up to 32 x 32: BASELINE cfg5)
@@ -1342,7 +1337,7 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
   // dev_xy: X / Y are DEVICE pointers into the resident data set (zigp_set_data): nothing but the parameters is staged
   const int nlat = (lik == ZIGP_LIK_ONOFF) ? 2 : 1;
   const KfPlan pl = kf_plan(p, nlat);
-  if (!c->kronf) { c->kronf = new (std::nothrow) KfState(); c->kronf_free = kf_free; if (!c->kronf) { c->err = "out of memory"; return ZIGP_EHIP; } }
+  if (!c->kronf) { c->kronf.reset(new (std::nothrow) KfState()); if (!c->kronf) { c->err = "out of memory"; return ZIGP_EHIP; } }
   KfState& ks = *c->kronf;
   ZIGP_TRY(begin_staged_call(c));
   const bool need_grad = (grads != nullptr || fit != nullptr) && !predict;
