@@ -2,8 +2,11 @@
 //
 // Per ELBO step (value + gradient), for each latent h in {f, g}:
 //   MxM stage   Kuu = k(Z,Z)+jitter I ; L = chol(Kuu) ; W = L^-1                    (OnOffSVGP.py:96-97, main.py:267-268)
-//   per chunk   K = k(Z, Xc) ; A1 = W K ; A2 = W^T A1 ; column sums -> mean, var      (main.py:266-303; A2 lives in accumulators only)
-//               H = (W diag(s^2)) A2 ; J' = W^T H - A2 = Q A2 = (Q W^T) A1            (gradient panels, independent of the cotangents)
+//   per chunk   K = k(Z, Xc) ; A1 = W K ; column sums -> mean                          (main.py:266-303)
+//               value-only / predict: A2 = W^T A1 (accumulators only) ; var = var0 - sum A1^2 + sum s^2 A2^2
+//               gradient step:  H = (W diag(s^2)) A2 ; J' = W^T H - A2 = Q A2 = (Q W^T) A1   (gradient panel, independent of the cotangents)
+//                               var = var0 + sum_m K J'  (k^T J' = k^T P S P k - k^T P k, P = Kuu^-1, S = diag(s^2)): no A2 product,
+//                               8 M^2 N flops per step (A1, J', rank-N update) instead of 10
 //               point-wise probit / likelihood / reverse pass -> gm, gv               (OnOffSVGP.py:168-204, OnOffLikelihood.py:30-32)
 //               reverse of the two triangular solves, with G = diag(gv), v = W u, alpha = W^T v:
 //                 E = W dA2 = v gm^T + 2 H G ;  F = dK = W^T(E - 2 A1 G) = alpha gm^T + 2 J' G
@@ -185,14 +188,16 @@ bool chunk_trmm_plan(int Mp0, int Mp1, int nbn, bool tail_on, TrmmTail& tail) {
   return paired;
 }
 
-// Forward panels of both latents for one chunk: A1, A2 (+ J' when a gradient is wanted), column partials.
+// Forward panels of both latents for one chunk and their column partials: A1 and A2 (value-only ELBO, predict) or A1 and J' (gradient step).
+// A gradient step launches no A2 product: the variance's  sum s^2 A2^2 - sum A1^2  is  sum_m K J'  (EpiStorePanelKColsum), reduced in the
+// epilogue of the J' product the reverse pass needs anyway -- 8 M^2 N flops per step instead of 10.
 // Where the triangular products run the paired order (trmm_paired_pays: cfg3, cfg2), each product class is ONE launch for both latents
 // (run_gemm2: latent g's workgroups fill the tail of latent f's, three launch boundaries fewer per chunk; cfg3 -0.4 ... -0.8 % same-box,
-// profiles/r05l_ab_merge_fg.log, r05s_ab_milestones.log).  In the LPT regime the products stay per latent, in the order A1 A2 J' (f), A1 A2 J' (g) (merged there:
+// profiles/r05l_ab_merge_fg.log, r05s_ab_milestones.log).  In the LPT regime the products stay per latent, in the order A1 A2 / A1 J' (f), then (g) (merged there:
 // cfg2 +1.2 %), and so does the rank-N update everywhere (its 512-workgroup split-K plan fills the chip exactly; merged +0.2 %).
-int chunk_forward(zigp_ctx* c, int64_t Nc, bool need_grad, const PwArgs* fuse_pw = nullptr, bool* fused = nullptr, const std::function<int()>& after_a1 = nullptr) {
+int chunk_forward(zigp_ctx* c, int64_t Nc, bool need_grad, const std::function<int()>& after_a1 = nullptr) {
   const int nbn = (int)(Nc / BN);
-  struct Set { TileList tl, tu, tf; double fl; GemmArgs a1, a2, j; EpiStoreColsum e1; EpiColsum e2; } q[2];
+  struct Set { TileList tl, tu, tf; double fl; GemmArgs a1, a2, j; EpiStoreColsum e1; EpiColsum e2; EpiStorePanelKColsum ej; } q[2];
   TrmmTail tail;
   const bool paired = chunk_trmm_plan(c->lat[0].Mp, c->lat[1].Mp, nbn, c->trmm_tail, tail), merge = paired;
   for (int h = 0; h < 2; ++h) {
@@ -200,8 +205,8 @@ int chunk_forward(zigp_ctx* c, int64_t Nc, bool need_grad, const PwArgs* fuse_pw
     const int Mp = lt.Mp, nbm = Mp / BM;
     const int np = Mp / 32;   // allocated partial rows per fused column sum (a kernel writes one per wave tile: 64 or 32 rows)
     ZIGP_TRY(tiles_trmm_lower(c, nbm, nbn, q[h].tl, paired, tail.units[h], tail.bins[h]));
-    ZIGP_TRY(tiles_trmm_upper(c, nbm, nbn, q[h].tu, paired, tail.units[h], tail.bins[h]));
     if (need_grad) ZIGP_TRY(tiles_full_xcd(c, nbm, nbn, nbm * (BM / BK), q[h].tf));
+    else ZIGP_TRY(tiles_trmm_upper(c, nbm, nbn, q[h].tu, paired, tail.units[h], tail.bins[h]));
     q[h].fl = (double)lt.M * lt.M * (double)Nc;
     // A1 = W K ; partial column sums  v^T A1 (= mean, since A2^T u = A1^T W u)  and  sum A1^2
     q[h].a1 = mk_args(lt.Wt.p, Mp, lt.K.p, Nc, lt.A1.p, Nc);
@@ -211,10 +216,11 @@ int chunk_forward(zigp_ctx* c, int64_t Nc, bool need_grad, const PwArgs* fuse_pw
     q[h].e2 = EpiColsum{nullptr, lt.s2.p, nullptr, lt.part.p + (size_t)2 * np * Nc};
     // J' = Q A2 = (Q W^T) A1, Q = Kuu^-1 diag(s^2) - I (M x M, dense): the two triangular products H = W diag(s^2) A2, J' = W^T H - A2 of the
     // reverse pass as ONE full product of the same flop count -- every tile the full k range (no triangular padding, half as many prologues and
-    // epilogues per flop), no H panel written and read back, no operand tile in the epilogue (r4: J' 61.9 -> 70.2 TFLOP/s, step -3.8 %,
-    // profiles/r04ak_ab_qform.log; the two-product form is in tools/r4_experiment_arms.patch).  r6: with R = Q W^T formed once per step in the
-    // M x M stage (latents_forward) the product reads the A1 panel, not A2.
+    // epilogues per flop), no H panel written and read back (r4: J' 61.9 -> 70.2 TFLOP/s, step -3.8 %, profiles/r04ak_ab_qform.log; the
+    // two-product form is in tools/r4_experiment_arms.patch).  r6: with R = Q W^T formed once per step in the M x M stage (latents_forward)
+    // the product reads the A1 panel, not A2.  Its epilogue also reduces sum_m K J' into plane 2 (in place of the A2 product's sums).
     q[h].j = mk_args(lt.Rt.p, Mp, lt.A1.p, Nc, lt.Jp.p, Nc);
+    q[h].ej = EpiStorePanelKColsum{lt.K.p, lt.part.p + (size_t)2 * np * Nc};
   }
   if (merge) {
     {
@@ -222,17 +228,12 @@ int chunk_forward(zigp_ctx* c, int64_t Nc, bool need_grad, const PwArgs* fuse_pw
       ZIGP_TRY((run_gemm2<LAY_MNCONTIG, LAY_MNCONTIG, false, TRI_A_LOWER>(c, q[0].tl, q[0].a1, q[0].e1, q[1].tl, q[1].a1, q[1].e1)));
     }
     if (after_a1) ZIGP_TRY(after_a1());     // the Kuf panels have had their only reader of a value-only / predict pass
-    {
-      ProfScope ps(c, PC_GEMM_A2, q[0].fl + q[1].fl);
-      ZIGP_TRY((run_gemm2<LAY_MNCONTIG, LAY_MNCONTIG, false, TRI_A_UPPER>(c, q[0].tu, q[0].a2, q[0].e2, q[1].tu, q[1].a2, q[1].e2)));
-    }
     if (need_grad) {
       ProfScope ps(c, PC_GEMM_J, 2.0 * (q[0].fl + q[1].fl));
-      if (fuse_pw && (Nc / PW_PTS) % 16 == 0) {
-        ZIGP_TRY(run_gemm_j_pw(c, q[0].tf, q[0].j, q[1].tf, q[1].j, *fuse_pw, (int)(Nc / PW_PTS)));
-        if (fused) *fused = true;
-      } else
-        ZIGP_TRY((run_gemm2<LAY_MNCONTIG, LAY_MNCONTIG, false>(c, q[0].tf, q[0].j, EpiStorePanel(), q[1].tf, q[1].j, EpiStorePanel())));
+      ZIGP_TRY((run_gemm2<LAY_MNCONTIG, LAY_MNCONTIG, false>(c, q[0].tf, q[0].j, q[0].ej, q[1].tf, q[1].j, q[1].ej)));
+    } else {
+      ProfScope ps(c, PC_GEMM_A2, q[0].fl + q[1].fl);
+      ZIGP_TRY((run_gemm2<LAY_MNCONTIG, LAY_MNCONTIG, false, TRI_A_UPPER>(c, q[0].tu, q[0].a2, q[0].e2, q[1].tu, q[1].a2, q[1].e2)));
     }
     return 0;
   }
@@ -242,13 +243,12 @@ int chunk_forward(zigp_ctx* c, int64_t Nc, bool need_grad, const PwArgs* fuse_pw
       ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false, TRI_A_LOWER>(c, q[h].tl, q[h].a1, q[h].e1)));
     }
     if (h == 1 && after_a1) ZIGP_TRY(after_a1());
-    {
-      ProfScope ps(c, PC_GEMM_A2, q[h].fl);
-      ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false, TRI_A_UPPER>(c, q[h].tu, q[h].a2, q[h].e2)));
-    }
     if (need_grad) {
       ProfScope ps(c, PC_GEMM_J, 2.0 * q[h].fl);
-      ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false>(c, q[h].tf, q[h].j, EpiStorePanel())));
+      ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false>(c, q[h].tf, q[h].j, q[h].ej)));
+    } else {
+      ProfScope ps(c, PC_GEMM_A2, q[h].fl);
+      ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false, TRI_A_UPPER>(c, q[h].tu, q[h].a2, q[h].e2)));
     }
   }
   return 0;
@@ -498,19 +498,21 @@ int dense_pointwise(zigp_ctx* c, const DenseCall& k, int64_t n0, int64_t Nc) {
   ProfScope ps(c, PC_POINT);
   const PwArgs a = dense_pointwise_args(c, k, n0, Nc);
   const int nblk = (int)(Nc / PW_PTS);
-  if (k.predict) hipLaunchKernelGGL(k_pointwise<true>, dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
-  else hipLaunchKernelGGL(k_pointwise<false>, dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
+  if (k.predict) hipLaunchKernelGGL((k_pointwise<true, false>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
+  else if (k.need_grad) hipLaunchKernelGGL((k_pointwise<false, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);   // variance from sum K J'
+  else hipLaunchKernelGGL((k_pointwise<false, false>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
   ZIGP_HIP(c, hipGetLastError());
   return 0;
 }
 
 // ---- chunk loop.  The MFMA-bound GEMMs stay on the main stream; with zigp_set_overlap(1) the HBM-bound kernels of a chunk -- the two
 // Kuf-cotangent reductions and the two Kuf panels of the NEXT chunk -- run on the side stream underneath the chunk's two SYRKs:
-//   main:  [wait side]  A1 (f|g)  A2 (f|g)  [point-wise +] J' (f|g)  (record)  SYRK f  SYRK g
+//   main:  [wait side]  A1 (f|g)  J' (f|g)  point-wise  (record)  SYRK f  SYRK g
 //   side:                                              (wait)    kgrad f  kgrad g  Kuf f'  Kuf g'  (record)
-// K is only read by A1 (and its rows' x, z by kgrad), J' / gm only by kgrad: the next chunk's GEMMs wait for the side stream, nothing
-// else is shared.  A chunk whose kernels are being timed (profiling samples every prof_every-th chunk) runs everything on the main
-// stream, so the per-kernel durations bench.py reports are those of kernels running alone.
+// K is read by A1 and by J''s epilogue (sum K J'), and by kgrad; the fork comes after both, so the next chunk's panels never overwrite a
+// K that J' still reads.  J' / gm are read only by kgrad: the next chunk's GEMMs wait for the side stream, nothing else is shared.
+// A chunk whose kernels are being timed (profiling samples every prof_every-th chunk) runs everything on the main stream, so the
+// per-kernel durations bench.py reports are those of kernels running alone.
 int dense_chunk_loop(zigp_ctx* c, const DenseCall& k) {
   if (!k.has_rows) return 0;
   const int64_t Nc_full = k.Nc, row_begin = k.row_begin, row_end = k.row_end;
@@ -555,18 +557,16 @@ int dense_chunk_loop(zigp_ctx* c, const DenseCall& k) {
     c->prof_skip = c->prof_on && !timed;
     // A1 of this chunk needs the Kuf panels the side stream built behind the previous chunk's kgrads (which read J' and gm)
     ZIGP_TRY(wait_side());
-    // gradient steps with zigp_set_overlap(1): the point-wise stage rides in the J' launch (run_gemm_j_pw: cfg3 -0.4 % same-box,
-    // profiles/r05t_ab_fuse_pointwise.log); timed chunks and overlap 0 keep every kernel on its own, as for the side stream
-    bool pw_fused = false;
-    const PwArgs pwa = dense_pointwise_args(c, k, n0, Nc);
     // value-only ELBO and predict (r6): there are no rank-N updates to hide the next chunk's Kuf panels under, but K has ONE reader there
     // -- A1 -- so the side stream builds the next panels right behind this chunk's A1, beside its A2 product and point-wise stage
     // (cfg3 value-only: the 4 ms of panel building per pass were serial on the main stream)
     const bool kuf_fwd_side = c->overlap == 1 && c->fwd_kuf_side && !k.need_grad && has_next && !timed && !timed_next;
     std::function<int()> after_a1;
     if (kuf_fwd_side) after_a1 = [&] { return on_side([&] { return kuf(n1); }); };
-    ZIGP_TRY(chunk_forward(c, Nc, k.need_grad, (c->overlap == 1 && k.need_grad && !k.predict && !timed) ? &pwa : nullptr, &pw_fused, after_a1));
-    if (!pw_fused) ZIGP_TRY(dense_pointwise(c, k, n0, Nc));
+    ZIGP_TRY(chunk_forward(c, Nc, k.need_grad, after_a1));
+    // the point-wise stage of a gradient step needs the J' launch's sums (it rode inside the J' launch while the variance came from A2:
+    // r5, profiles/r05t_ab_fuse_pointwise.log), so it is a launch of its own after it
+    ZIGP_TRY(dense_pointwise(c, k, n0, Nc));
     // side work of this chunk: its kgrads and the next chunk's Kuf panels (gradient mode only: without the SYRKs there is
     // nothing on the main stream to hide them under)
     const bool kgrad_side = c->overlap == 1 && k.need_grad && !timed;

@@ -109,7 +109,6 @@ struct EpiStore {   // C = alpha*acc
     epi_foreach(acc, e, [&](int64_t i, int64_t j, double v) { C[i * ld + j] = v; });
   }
 };
-struct EpiStorePanel : EpiStore {};   // same code under its own kernel name: the chunk loop's J' = Q A2 (profilers aggregate by name, and the M x M stage launches the plain one)
 struct EpiAccum {   // C += alpha*acc
   template <int TM, int TN>
   __device__ __forceinline__ void operator()(const double (&acc)[TM][TN][4], const EpiCtx& e) const {
@@ -171,6 +170,50 @@ struct EpiColsum {
   const double* __restrict__ w1; const double* __restrict__ w2; double* __restrict__ out1; double* __restrict__ out2;
   template <int TM, int TN>
   __device__ __forceinline__ void operator()(const double (&acc)[TM][TN][4], const EpiCtx& e) const { epi_colsum<false>(acc, e, w1, w2, out1, out2); }
+};
+// The chunk loop's J' = (Q W^T) A1 of a gradient step: store the panel and reduce  sum_m K[m,n] J'[m,n]  over this wave's 16 * TM rows into
+// partial row e.prow of `out` ([Mp / (16 TM)][ldc], as epi_colsum).  With J' = Q A2, Q = P S - I, A2 = P k (P = Kuu^-1, S = diag(s^2)):
+//   k^T J' = k^T P S P k - k^T P k = sum s^2 A2^2 - sum A1^2,
+// the whole data-dependent part of the latent variance, so a gradient step needs no A2 product.  K has J''s shape and row stride; its
+// rows m >= M are zero (k_kuf_build), so padded rows of J' add nothing.  The K loads of a 16-row sub-tile are issued before its stores,
+// so that their latency overlaps them (the whole wave tile's K at once spills: 64 accumulator + 64 K registers); the sum runs in the
+// fixed order of epi_colsum (bit-stable).
+struct EpiStorePanelKColsum {
+  const double* __restrict__ K; double* __restrict__ out;
+  template <int TM, int TN>
+  __device__ __forceinline__ void operator()(const double (&acc)[TM][TN][4], const EpiCtx& e) const {
+    double* __restrict__ C = e.C; const int64_t ld = e.ldc;
+    const int c_i = e.lane >> 4, c_j = e.lane & 15;
+    double s[TN];
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) s[tn] = 0.0;
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm) {   // per 16-row sub-tile: its K loads, then its stores, then the sums (one sub-tile of K in registers)
+      double kv[4][TN];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double* __restrict__ kr = K + (e.row0 + tm * e.tm_stride + 4 * r + c_i) * ld + e.col0 + c_j;
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) kv[r][tn] = kr[tn * 16];
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        double* __restrict__ cr = C + (e.row0 + tm * e.tm_stride + 4 * r + c_i) * ld + e.col0 + c_j;
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) cr[tn * 16] = e.alpha * acc[tm][tn][r];
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) s[tn] = fma(kv[r][tn], e.alpha * acc[tm][tn][r], s[tn]);
+    }
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) {   // fixed-order combine of the four 16-lane row groups
+      double a = s[tn];
+      a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
+      if (c_i == 0) out[e.prow * ld + e.col0 + tn * 16 + c_j] = a;
+    }
+  }
 };
 
 // k-contiguous image swizzle: granule position = (k>>1) ^ kswz(row).  kswz takes 8 distinct values on the even and on the odd rows of

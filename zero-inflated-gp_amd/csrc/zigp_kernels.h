@@ -166,9 +166,10 @@ k_kuf_build(const double* __restrict__ X, int64_t N, int64_t n0, const double* _
 // reverse pass to the cotangents of (fmean, fvar, gmean, gvar) and the noise variance.
 // ---------------------------------------------------------------------------------------------
 struct PwArgs {
-  const double* part_f; const double* part_g;    // per latent [3][NP][Nc]: sum v A1, sum A1^2, sum s2 A2^2 partial rows (EpiStoreColsum)
+  const double* part_f; const double* part_g;    // per latent [3][NP][Nc] partial rows: sum v A1, sum A1^2 (EpiStoreColsum), and plane 2:
+                                                  // sum s2 A2^2 (EpiColsum; value-only, predict) or sum K J' (EpiStorePanelKColsum; gradient step)
   int np_f, np_g;                                 // allocated partial rows per quantity (plane stride np * Nc)
-  int np1_f, np2_f, np1_g, np2_g;                 // rows actually written: np1 by the A1 kernel (quantities 0, 1), np2 by the A2 kernel
+  int np1_f, np2_f, np1_g, np2_g;                 // rows actually written: np1 by the A1 kernel (quantities 0, 1), np2 by the A2 / J' kernel
   const double* Y; int64_t n0, row_end, Nc;
   double var_f, var_g, noise, g_offset, scale;
   double* gm_f; double* gv_f; double* gm_g; double* gv_g;
@@ -228,21 +229,23 @@ __device__ __forceinline__ PwOut pointwise_eval(double fm, double fv, double gmn
 // Nc / PW_PTS = 512 blocks x 4 waves keep enough loads in flight to stream the partial-row planes), wave 0 adds the group sums
 // in group order (fixed order: bit-stable) and evaluates the point.
 constexpr int PW_PTS = 64, PW_GROUPS = PW_THREADS / PW_PTS;
-// (a device function: the gradient step runs it as the leading workgroups of the J' launch, two blocks per 512-thread workgroup)
-template <bool PREDICT>
+// GRADVAR (gradient steps): plane 2 holds sum_m K J' = sum s^2 A2^2 - sum A1^2 (EpiStorePanelKColsum), so the variance is
+// var + (plane 2) and plane 1 is not read.
+template <bool PREDICT, bool GRADVAR>
 __device__ __forceinline__ void pw_block(const PwArgs& p, int blk, int tid, double (*grp)[PW_GROUPS][PW_PTS]) {
+  static_assert(!(PREDICT && GRADVAR), "predict has no J' panel");
   const int lane = tid & (PW_PTS - 1), g = tid / PW_PTS;
   const int64_t n = (int64_t)blk * PW_PTS + lane;
   {
     double fm = 0.0, fsq = 0.0, fs2 = 0.0, gmn = 0.0, gsq = 0.0, gs2 = 0.0;
     for (int q = g; q < p.np1_f; q += PW_GROUPS) {
       fm += p.part_f[(int64_t)(0 * p.np_f + q) * p.Nc + n];
-      fsq += p.part_f[(int64_t)(1 * p.np_f + q) * p.Nc + n];
+      if (!GRADVAR) fsq += p.part_f[(int64_t)(1 * p.np_f + q) * p.Nc + n];
     }
     for (int q = g; q < p.np2_f; q += PW_GROUPS) fs2 += p.part_f[(int64_t)(2 * p.np_f + q) * p.Nc + n];
     for (int q = g; q < p.np1_g; q += PW_GROUPS) {
       gmn += p.part_g[(int64_t)(0 * p.np_g + q) * p.Nc + n];
-      gsq += p.part_g[(int64_t)(1 * p.np_g + q) * p.Nc + n];
+      if (!GRADVAR) gsq += p.part_g[(int64_t)(1 * p.np_g + q) * p.Nc + n];
     }
     for (int q = g; q < p.np2_g; q += PW_GROUPS) gs2 += p.part_g[(int64_t)(2 * p.np_g + q) * p.Nc + n];
     grp[0][g][lane] = fm; grp[1][g][lane] = fsq; grp[2][g][lane] = fs2;
@@ -259,7 +262,8 @@ __device__ __forceinline__ void pw_block(const PwArgs& p, int blk, int tid, doub
     tot[v] = a;
   }
   double fm = tot[0], gmn = tot[3];
-  const double fv = p.var_f - tot[1] + tot[2], gvr = p.var_g - tot[4] + tot[5];   // main.py:278,302
+  const double fv = GRADVAR ? p.var_f + tot[2] : p.var_f - tot[1] + tot[2];     // main.py:278,302
+  const double gvr = GRADVAR ? p.var_g + tot[5] : p.var_g - tot[4] + tot[5];
   gmn += p.g_offset;
   const bool valid = (p.n0 + n) < p.row_end;
   double xs[MAXD];
@@ -301,11 +305,11 @@ __device__ __forceinline__ void pw_block(const PwArgs& p, int blk, int tid, doub
     }
   }
 }
-template <bool PREDICT>
+template <bool PREDICT, bool GRADVAR>
 __global__ void __launch_bounds__(PW_THREADS)
 k_pointwise(PwArgs p) {
   __shared__ double grp[6][PW_GROUPS][PW_PTS];
-  pw_block<PREDICT>(p, blockIdx.x, threadIdx.x, grp);
+  pw_block<PREDICT, GRADVAR>(p, blockIdx.x, threadIdx.x, grp);
 }
 
 // ---------------------------------------------------------------------------------------------
