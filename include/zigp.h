@@ -63,13 +63,15 @@ int zigp_last_info(zigp_ctx* ctx);
 
 /* Tunables: chunk = number of data rows processed per pass through the fused pipeline (multiple of
  * 1024 and <= 1048576).  Default, until this is called: 32768 * 1024 / M rows, clamped to [32768, 131072]; a row range of up to 131072
- * rows goes through in one pass while its panels stay within 9 GB.  chunk_rows = 0 returns to that default rule. */
+ * rows goes through in one pass while 4 panels of 8 * M * rows bytes per latent stay within 9 GB (a pass holds 3: K, A1 and J'; the
+ * bound is deliberately conservative).  chunk_rows = 0 returns to that default rule. */
 int zigp_set_chunk(zigp_ctx* ctx, int64_t chunk_rows);
 /* The chunk (rows per pass) the dense path uses for M inducing points per latent on a long row range: the zigp_set_chunk value, else
  * the default rule. */
 int64_t zigp_get_chunk(zigp_ctx* ctx, int32_t M);
 /* Rows per pass the dense path actually uses for a row range of `span` rows: the range is cut into equal passes of at most the chunk above
- * (a multiple of 1024 rows each), and a range of up to 131072 rows goes through in ONE pass while its panels stay within 9 GB (M <= 1024). */
+ * (a multiple of 1024 rows each), and a range of up to 131072 rows goes through in ONE pass while 4 panels of 8 * M * rows bytes per latent
+ * (3 held: K, A1, J') stay within 9 GB (M <= 1024). */
 int64_t zigp_get_chunk_rows(zigp_ctx* ctx, int32_t M, int64_t span);
 /* Smallest Cholesky pivot accepted, as a multiple of eps * (kernel variance + jitter).  Default 8 (see ZIGP_ENOTPD above);
  * 0 reproduces tf.cholesky / LAPACK potrf, which fail on a non-positive pivot only (onofftf/main.py:200,268,355). */

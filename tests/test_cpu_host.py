@@ -716,9 +716,10 @@ def test_classifier_scores_match_sklearn():
 
 def test_triangular_tile_lists_are_partitions_with_and_without_the_lpt_tail():
     """The chunk loop's triangular products run host-built tile lists (paired units, both latents in one launch; since round 6 the last,
-    partly filled wave re-dealt longest-first -- zigp_host.h tiles_trmm / trmm_tail_plan).  zigp_test_trmm_list rebuilds them on the host,
-    as chunk_forward does, and checks that every (row block, column panel) tile occurs exactly once with the whole k range of its row
-    block -- for the bench configurations and a sweep of ragged shapes; no GPU involved."""
+    partly filled wave re-dealt longest-first -- zigp_host.h trmm_tiles / trmm_tail_plan).  zigp_test_trmm_list builds them on the host
+    through the planner run_dense uses (zigp_dense.hip chunk_plan) and checks that every (row block, column panel) tile occurs exactly
+    once with the whole k range of its row block -- for the bench configurations and a sweep of ragged shapes; no GPU involved.  The
+    benchmarked shapes are pinned: workgroups, entries per workgroup, tail units, worst tail load and paired, per latent."""
     import ctypes as C
     from zigp import _lib
     lib = _lib.load()
@@ -744,4 +745,10 @@ def test_triangular_tile_lists_are_partitions_with_and_without_the_lpt_tail():
             else:
                 assert lpt[:4] == plain[:4]
     assert tails >= 8                                              # the sweep does exercise the tail (cfg2 and the 125 952-row shard among them)
+    pinned = {(512, 512, 100352): [1568, 1504, 2, 3, 0, 576, 6, 1],  # cfg2: paired, LPT tail of 576 units in latent g's list
+              (1024, 1024, 32768): [1024, 1024, 2, 2, 0, 0, 0, 1],   # cfg3: paired, whole waves, no tail
+              (1024, 1024, 125952): [3936, 3744, 2, 3, 0, 704, 14, 1]}   # cfg3's 125 952-row shard: paired, tail of 704 units
+    for (Mf, Mg, Nc), want in pinned.items():
+        for lower in (1, 0):
+            assert lib.zigp_test_trmm_list(lower, Mf, Mg, Nc, 1, out) == 0 and list(out) == want, (Mf, Mg, Nc, lower, list(out))
     assert lib.zigp_test_trmm_list(1, 512, 512, 1000, 1, out) == _lib.ZIGP_EARG      # Nc must be a multiple of 128

@@ -494,14 +494,14 @@ def test_automatic_rule_takes_a_short_row_range_in_one_pass_with_the_same_result
 
 def test_M2048_sixteen_row_blocks_and_the_chunk_rule_beyond_its_one_pass_bound(engine):
     """M = 2048 (16 row blocks of 128; Mg = 1100: 9 blocks): the tile lists, the split-K plan of the rank-N update and the blocked
-    factorisation at twice cfg3's depth, against the oracle; then a row range beyond the one-pass bound of the chunk rule (4 panels of
-    8 Mp span bytes per latent <= 9 GB, include/zigp.h zigp_get_chunk_rows): 80 000 rows at M = 2048 go through in three passes of the
+    factorisation at twice cfg3's depth, against the oracle; then a row range beyond the one-pass bound of the chunk rule (3 panels of
+    8 Mp span bytes per latent -- K, A1, J' -- budgeted as 4 against 9 GB, include/zigp.h zigp_get_chunk_rows): 80 000 rows at M = 2048 go through in three passes of the
     M-scaled chunk -- same step as with a fixed small chunk, and a slice of it against the oracle."""
     import zigp_oracle as o
     import zigp_oracle_torch as ot
     engine.set_chunk(0)                                         # the automatic rule (earlier tests of the session fixed the chunk)
     assert engine.get_chunk(2048) == 32768
-    assert engine.get_chunk_rows(2048, 60000) == 60416          # 4 * 2 * 8 * 2048 * 60416 B = 7.9 GB: one pass
+    assert engine.get_chunk_rows(2048, 60000) == 60416          # bound 4 * 2 * 8 * 2048 * 60416 B = 7.9 GB (3 panels held, 4 budgeted): one pass
     assert engine.get_chunk_rows(2048, 80000) == 27648          # 10.6 GB: the rule falls back to ceil(80000 / 32768) = 3 equal passes
     X, Y, p = make_problem(80000, 2048, 3, seed=77, Mg=1100, ell=0.1)
     c = _cond(p, 1e-6)

@@ -236,7 +236,7 @@ def test_cfg1_toydata_M50_matches_oracle(engine):
 
 
 def test_two_latents_in_one_launch_with_different_block_counts(engine):
-    """The merged launches of the chunk loop (run_gemm2: A1, A2, J' of latent f and latent g as ONE grid each, paired tile order) with
+    """The merged launches of the chunk loop (run_gemm with two sets: A1, A2, J' of latent f and latent g as ONE grid each, paired tile order) with
     Mf = 300 (3 row blocks: a pair and a single middle tile per column panel) and Mg = 520 (5 row blocks): 304 column panels x (2 + 3)
     units = 1520 workgroups = 0.99 of three waves -> trmm_paired_pays.  Against the same step in 38 passes of 1024 rows, which takes the
     LPT order with one launch per latent (8 column panels x 5 units < 512), and against the oracle on a slice."""

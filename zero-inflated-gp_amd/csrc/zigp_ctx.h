@@ -66,7 +66,7 @@ struct Latent {
   DevBuf Kuu, L, W;                      // (Mp,Mp)
   DevBuf K, A1, Jp;                      // chunk panels [Mp][Nc]: Kuf, A1 = W K, J' = Q W^T A1 (A2 = W^T A1 is reduced to its column sums and never stored: r6)
   DevBuf Wp, a1gm;                       // W diag(s^2) (Mp,Mp); running sum of A1 gm [Mp]
-  DevBuf Wt, Wpt;                        // W^T, (W diag(s^2))^T (Mp,Mp): the m-contiguous images the lower-triangular products read
+  DevBuf Wt;                             // W^T (Mp,Mp): the m-contiguous image the lower-triangular product A1 = W K reads
   DevBuf P, Qt, Rt;                      // gradient steps: P = W^T W = Kuu^-1, Qt = diag(s^2) P - I = Q^T, Rt = W Qt = (Q W^T)^T: J' = Q A2 = (Q W^T) A1 (zigp_dense.hip, chunk_forward)
   bool P_ready = false;                  // P of THIS call's parameters is in `P` (the reverse M x M stage takes it from there)
   DevBuf part;                           // [3][Mp/32][Nc] partial rows of the fused column sums: v^T A1, sum A1^2, sum s^2 A2^2
@@ -153,7 +153,7 @@ struct zigp_ctx : zigp::CtxHandles {
   zigp::DevBuf pw_part;                 // pointwise block partials
   // mean function of f, m(x) = mean_b + mean_a . x (zigp_set_mean_function), and its gradient from the last zigp_elbo
   bool fwd_kuf_side = true;             // value-only / predict passes: the next chunk's Kuf panels on the side stream behind this chunk's A1 (env ZIGP_FWD_KUF_SIDE=0: off)
-  bool trmm_tail = true;                // merged triangular launches: re-deal the last, partly filled wave (tiles_trmm, zigp_host.h); env ZIGP_TRMM_TAIL=0 turns it off
+  bool trmm_tail = true;                // merged triangular launches: re-deal the last, partly filled wave (trmm_tiles, zigp_host.h); env ZIGP_TRMM_TAIL=0 turns it off
   int overlap = 1;                      // zigp_set_overlap: 1 (default) = HBM-bound side kernels of a chunk on stream2 under its SYRKs
   bool mean_on = false;
   double mean_a[8] = {0}, mean_b = 0.0, mean_da[8] = {0}, mean_db = 0.0;   // 8 = zigp::MAXD (zigp_kernels.h)
@@ -164,7 +164,7 @@ struct zigp_ctx : zigp::CtxHandles {
   std::unique_ptr<zigp::KfState> kronf;
   bool kron_panels = false;             // zigp_set_kron_panels: force the panel (GEMM-core) Kronecker path
   int kron_range_tiles = 1024;          // larger-grid fused backward: rows go through in ranges of this many 16-point tiles (bounded operand spill; zigp_set_kron_range_tiles)
-  std::map<std::string, zigp::CachedTiles> tiles;   // tile lists by key (get_tiles, zigp_host.h)
+  std::map<std::string, zigp::CachedTiles> tiles;   // tile lists by key (get_tiles, zigp_host.h); kept until zigp_destroy (bound: chunk_plan)
   // data-parallel exchange (zigp_comm_init): RCCL communicator, one rank per context / GPU
   void* comm = nullptr; int comm_rank = 0, comm_nranks = 1; int64_t comm_calls = 0;
   double comm_timeout_s = 120.0;         // zigp_comm_set_timeout: how long zigp_comm_init waits for its peers

@@ -87,13 +87,12 @@ int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D) {
     ZIGP_ENSURE(c, lt.vec, 4 * Mp + 8);
     ZIGP_ENSURE(c, lt.Wp, Mp * Mp);
     ZIGP_ENSURE(c, lt.Wt, Mp * Mp);
-    ZIGP_ENSURE(c, lt.Wpt, Mp * Mp);
     ZIGP_ENSURE(c, lt.P, Mp * Mp); ZIGP_ENSURE(c, lt.Qt, Mp * Mp); ZIGP_ENSURE(c, lt.Rt, Mp * Mp);
   }
   return 0;
 }
 
-// MxM forward of BOTH latents (kernels only): Kuu, L = chol, W = L^-1 (+ W^T, (W diag(s^2))^T), the KL pieces v = W u,
+// MxM forward of BOTH latents (kernels only): Kuu, L = chol, W = L^-1 (+ W^T), the KL pieces v = W u,
 // alpha = W^T v, dkinv = diag(K^-1), kl -> vec[3*Mp], and W' = W diag(s^2) for gradient steps.  Latent f runs on the main stream and g
 // on stream2 (the caller forks / joins); the launches ALTERNATE between the two chains step by step, so that both streams are fed
 // from the start (see potrf_trtri_jobs).
@@ -125,7 +124,7 @@ int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter
       double* v = lt.vec.p; double* alpha = v + Mp; double* dkinv = v + 2 * Mp; double* klv = v + 3 * Mp;
       switch (step) {
         case 0:   // W^T: the m-contiguous image of the factor that the lower-triangular product A1 = W K reads
-          hipLaunchKernelGGL(k_transpose_scale, dim3(Mp / 32, Mp / 32), dim3(32, 8), 0, c->stream, lt.W.p, lt.s2.p, (int64_t)Mp, lt.Wt.p, lt.Wpt.p);
+          hipLaunchKernelGGL(k_transpose, dim3(Mp / 32, Mp / 32), dim3(32, 8), 0, c->stream, lt.W.p, (int64_t)Mp, lt.Wt.p);
           break;
         // v = W u and alpha = W^T v are needed by the KL value, by the fused mean (v^T A1) and by the rank-1 parts of the data-term gradient
         case 1: if (with_kl) hipLaunchKernelGGL(k_gemv_rows, dim3(Mp), dim3(256), 0, c->stream, lt.W.p, lt.u.p, (int64_t)Mp, v); break;
@@ -177,78 +176,92 @@ int latent_chunk_kuf(zigp_ctx* c, Latent& lt, const double* dX, int64_t Nrows, i
   return 0;
 }
 
-// Tile order of the chunk's two triangular products: paired units + merged launch where both latents' units fill waves of the 512 slots
-// (trmm_paired_pays), and then the plan for a last wave that is not full (trmm_tail_plan; merged launch = [latent f's units | latent g's
-// units], unit counts multiples of 8).  Returns `paired`.
-bool chunk_trmm_plan(int Mp0, int Mp1, int nbn, bool tail_on, TrmmTail& tail) {
-  const int u0 = ((nbn + 7) / 8) * 8 * ((Mp0 / BM + 1) / 2), u1 = ((nbn + 7) / 8) * 8 * ((Mp1 / BM + 1) / 2);
-  const bool paired = trmm_paired_pays(nbn * ((Mp0 / BM + 1) / 2 + (Mp1 / BM + 1) / 2));
-  tail = TrmmTail{{0, 0}, {64, 64}};
-  if (paired && tail_on) tail = trmm_tail_plan(u0, Mp0 / BM, u1, Mp1 / BM);
-  return paired;
+// The launches of one chunk shape, decided on the host alone by chunk_plan (zigp_test_trmm_list checks these very lists): paired units +
+// merged launches where both latents' units fill waves of the 512 slots (trmm_paired_pays), then the plan for a last wave that is not full
+// (trmm_tail_plan; merged launch = [f's units | g's units], unit counts multiples of 8); per latent the lists of A1, of A2 (value-only ELBO,
+// predict) or J' (gradient step) and of the rank-N update, and the flop counts the ProfScopes report.  run_dense plans and uploads
+// (upload_plan) every chunk shape of a call before it enqueues anything: no hipMalloc or synchronous copy falls inside the chunk loop.  The
+// tile cache keeps its lists until zigp_destroy; they follow from (Mp_f, Mp_g, Nc): at most 128 chunk sizes per M pair under the automatic
+// rule, 1024 with zigp_set_chunk (multiples of 1024 rows up to 131072 / 2^20).
+struct ChunkPlan {
+  int64_t Nc = 0;
+  bool paired = false;   // and merged: each forward product is ONE launch for both latents
+  TrmmTail tail = {{0, 0}, {64, 64}};
+  struct Lat { TileSpec a1_spec, a2j_spec, syr_spec; TileList a1, a2j, syr; double fl = 0.0; } lat[2];   // a2j: A2 or J'; fl = M^2 Nc
+};
+ChunkPlan chunk_plan(const int (&M)[2], int64_t Nc, bool need_grad, bool tail_on) {
+  ChunkPlan pl;
+  const int nbm[2] = {ceil_div(M[0], BM), ceil_div(M[1], BM)}, nbn = (int)(Nc / BN);
+  pl.Nc = Nc;
+  pl.paired = trmm_paired_pays(nbn * ((nbm[0] + 1) / 2 + (nbm[1] + 1) / 2));
+  if (pl.paired && tail_on)
+    pl.tail = trmm_tail_plan((nbn + 7) / 8 * 8 * ((nbm[0] + 1) / 2), nbm[0], (nbn + 7) / 8 * 8 * ((nbm[1] + 1) / 2), nbm[1]);
+  for (int h = 0; h < 2; ++h) {
+    ChunkPlan::Lat& L = pl.lat[h];
+    L.a1_spec = trmm_tiles(true, nbm[h], nbn, pl.paired, pl.tail.units[h], pl.tail.bins[h]);
+    if (need_grad) {
+      L.a2j_spec = full_xcd_tiles(nbm[h], nbn, nbm[h] * (BM / BK));
+      L.syr_spec = syr2k_tiles(nbm[h], (int)(Nc / BK), syr_plan(nbm[h]));
+    } else L.a2j_spec = trmm_tiles(false, nbm[h], nbn, pl.paired, pl.tail.units[h], pl.tail.bins[h]);
+    L.fl = (double)M[h] * M[h] * (double)Nc;
+  }
+  return pl;
+}
+int upload_plan(zigp_ctx* c, ChunkPlan& pl) {
+  for (ChunkPlan::Lat& L : pl.lat) {
+    ZIGP_TRY(get_tiles(c, L.a1_spec, L.a1));
+    ZIGP_TRY(get_tiles(c, L.a2j_spec, L.a2j));
+    if (L.syr_spec.build) ZIGP_TRY(get_tiles(c, L.syr_spec, L.syr));
+  }
+  return 0;
 }
 
 // Forward panels of both latents for one chunk and their column partials: A1 and A2 (value-only ELBO, predict) or A1 and J' (gradient step).
 // A gradient step launches no A2 product: the variance's  sum s^2 A2^2 - sum A1^2  is  sum_m K J'  (EpiStorePanelKColsum), reduced in the
 // epilogue of the J' product the reverse pass needs anyway -- 8 M^2 N flops per step instead of 10.
-// Where the triangular products run the paired order (trmm_paired_pays: cfg3, cfg2), each product class is ONE launch for both latents
-// (run_gemm2: latent g's workgroups fill the tail of latent f's, three launch boundaries fewer per chunk; cfg3 -0.4 ... -0.8 % same-box,
-// profiles/r05l_ab_merge_fg.log, r05s_ab_milestones.log).  In the LPT regime the products stay per latent, in the order A1 A2 / A1 J' (f), then (g) (merged there:
-// cfg2 +1.2 %), and so does the rank-N update everywhere (its 512-workgroup split-K plan fills the chip exactly; merged +0.2 %).
-int chunk_forward(zigp_ctx* c, int64_t Nc, bool need_grad, const std::function<int()>& after_a1 = nullptr) {
-  const int nbn = (int)(Nc / BN);
-  struct Set { TileList tl, tu, tf; double fl; GemmArgs a1, a2, j; EpiStoreColsum e1; EpiColsum e2; EpiStorePanelKColsum ej; } q[2];
-  TrmmTail tail;
-  const bool paired = chunk_trmm_plan(c->lat[0].Mp, c->lat[1].Mp, nbn, c->trmm_tail, tail), merge = paired;
+// Where the triangular products run the paired order (trmm_paired_pays: cfg3, cfg2), each product class is ONE launch for both latents (run_gemm
+// with two sets: g's workgroups fill the tail of f's, three launch boundaries fewer per chunk; cfg3 -0.4 ... -0.8 % same-box, profiles/r05l_ab_merge_fg.log,
+// r05s_ab_milestones.log).  In the LPT regime the products stay per latent, in the order A1 A2 / A1 J' (f), then (g) (merged there: cfg2 +1.2 %), and
+// so does the rank-N update everywhere (its 512-workgroup split-K plan fills the chip exactly; merged +0.2 %).
+int chunk_forward(zigp_ctx* c, const ChunkPlan& pl, bool need_grad, const std::function<int()>& after_a1 = nullptr) {
+  const int64_t Nc = pl.Nc;
+  struct Set { TileList t1, t2; double fl; GemmArgs a1, a2j; EpiStoreColsum e1; EpiColsum e2; EpiStorePanelKColsum ej; } q[3] = {};   // q[2]: none
   for (int h = 0; h < 2; ++h) {
     Latent& lt = c->lat[h];
-    const int Mp = lt.Mp, nbm = Mp / BM;
-    const int np = Mp / 32;   // allocated partial rows per fused column sum (a kernel writes one per wave tile: 64 or 32 rows)
-    ZIGP_TRY(tiles_trmm_lower(c, nbm, nbn, q[h].tl, paired, tail.units[h], tail.bins[h]));
-    if (need_grad) ZIGP_TRY(tiles_full_xcd(c, nbm, nbn, nbm * (BM / BK), q[h].tf));
-    else ZIGP_TRY(tiles_trmm_upper(c, nbm, nbn, q[h].tu, paired, tail.units[h], tail.bins[h]));
-    q[h].fl = (double)lt.M * lt.M * (double)Nc;
+    const int Mp = lt.Mp, np = Mp / 32;   // np: allocated partial rows per fused column sum (a kernel writes one per wave tile: 64 or 32 rows)
+    q[h].t1 = pl.lat[h].a1; q[h].t2 = pl.lat[h].a2j; q[h].fl = pl.lat[h].fl;
     // A1 = W K ; partial column sums  v^T A1 (= mean, since A2^T u = A1^T W u)  and  sum A1^2
     q[h].a1 = mk_args(lt.Wt.p, Mp, lt.K.p, Nc, lt.A1.p, Nc);
     q[h].e1 = EpiStoreColsum{lt.vec.p, nullptr, lt.part.p, lt.part.p + (size_t)np * Nc};
-    // A2 = W^T A1 ; partial column sums  sum s^2 A2^2 -- the sums only: the panel itself has no reader (EpiColsum; ldc = stride of the partial rows)
-    q[h].a2 = mk_args(lt.W.p, Mp, lt.A1.p, Nc, nullptr, Nc);
-    q[h].e2 = EpiColsum{nullptr, lt.s2.p, nullptr, lt.part.p + (size_t)2 * np * Nc};
-    // J' = Q A2 = (Q W^T) A1, Q = Kuu^-1 diag(s^2) - I (M x M, dense): the two triangular products H = W diag(s^2) A2, J' = W^T H - A2 of the
-    // reverse pass as ONE full product of the same flop count -- every tile the full k range (no triangular padding, half as many prologues and
-    // epilogues per flop), no H panel written and read back (r4: J' 61.9 -> 70.2 TFLOP/s, step -3.8 %, profiles/r04ak_ab_qform.log; the
-    // two-product form is in tools/r4_experiment_arms.patch).  r6: with R = Q W^T formed once per step in the M x M stage (latents_forward)
-    // the product reads the A1 panel, not A2.  Its epilogue also reduces sum_m K J' into plane 2 (in place of the A2 product's sums).
-    q[h].j = mk_args(lt.Rt.p, Mp, lt.A1.p, Nc, lt.Jp.p, Nc);
-    q[h].ej = EpiStorePanelKColsum{lt.K.p, lt.part.p + (size_t)2 * np * Nc};
-  }
-  if (merge) {
-    {
-      ProfScope ps(c, PC_GEMM_A1, q[0].fl + q[1].fl);
-      ZIGP_TRY((run_gemm2<LAY_MNCONTIG, LAY_MNCONTIG, false, TRI_A_LOWER>(c, q[0].tl, q[0].a1, q[0].e1, q[1].tl, q[1].a1, q[1].e1)));
-    }
-    if (after_a1) ZIGP_TRY(after_a1());     // the Kuf panels have had their only reader of a value-only / predict pass
     if (need_grad) {
-      ProfScope ps(c, PC_GEMM_J, 2.0 * (q[0].fl + q[1].fl));
-      ZIGP_TRY((run_gemm2<LAY_MNCONTIG, LAY_MNCONTIG, false>(c, q[0].tf, q[0].j, q[0].ej, q[1].tf, q[1].j, q[1].ej)));
+      // J' = Q A2 = (Q W^T) A1, Q = Kuu^-1 diag(s^2) - I (M x M, dense): the two triangular products H = W diag(s^2) A2, J' = W^T H - A2 of the
+      // reverse pass as ONE full product of the same flop count -- every tile the full k range (no triangular padding, half as many prologues and
+      // epilogues per flop), no H panel written and read back (r4: J' 61.9 -> 70.2 TFLOP/s, step -3.8 %, profiles/r04ak_ab_qform.log; the
+      // two-product form is in tools/r4_experiment_arms.patch).  r6: with R = Q W^T formed once per step in the M x M stage (latents_forward)
+      // the product reads the A1 panel, not A2.  Its epilogue also reduces sum_m K J' into plane 2 (in place of the A2 product's sums).
+      q[h].a2j = mk_args(lt.Rt.p, Mp, lt.A1.p, Nc, lt.Jp.p, Nc);
+      q[h].ej = EpiStorePanelKColsum{lt.K.p, lt.part.p + (size_t)2 * np * Nc};
     } else {
-      ProfScope ps(c, PC_GEMM_A2, q[0].fl + q[1].fl);
-      ZIGP_TRY((run_gemm2<LAY_MNCONTIG, LAY_MNCONTIG, false, TRI_A_UPPER>(c, q[0].tu, q[0].a2, q[0].e2, q[1].tu, q[1].a2, q[1].e2)));
+      // A2 = W^T A1 ; partial column sums  sum s^2 A2^2 -- the sums only: the panel has no reader (no C; ldc = stride of the partial rows)
+      q[h].a2j = mk_args(lt.W.p, Mp, lt.A1.p, Nc, nullptr, Nc);
+      q[h].e2 = EpiColsum{nullptr, lt.s2.p, nullptr, lt.part.p + (size_t)2 * np * Nc};
     }
-    return 0;
   }
-  for (int h = 0; h < 2; ++h) {
+  const int groups = pl.paired ? 1 : 2;      // launch groups: merged {f, g}; LPT {f} then {g}
+  for (int gi = 0; gi < groups; ++gi) {
+    const Set& x = q[gi];
+    const Set& y = q[pl.paired ? 1 : 2];
     {
-      ProfScope ps(c, PC_GEMM_A1, q[h].fl);
-      ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false, TRI_A_LOWER>(c, q[h].tl, q[h].a1, q[h].e1)));
+      ProfScope ps(c, PC_GEMM_A1, x.fl + y.fl);
+      ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false, TRI_A_LOWER>(c, x.t1, x.a1, x.e1, y.t1, y.a1, y.e1)));
     }
-    if (h == 1 && after_a1) ZIGP_TRY(after_a1());
+    if (gi == groups - 1 && after_a1) ZIGP_TRY(after_a1());     // the Kuf panels have had their only reader of a value-only / predict pass
     if (need_grad) {
-      ProfScope ps(c, PC_GEMM_J, 2.0 * q[h].fl);
-      ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false>(c, q[h].tf, q[h].j, q[h].ej)));
+      ProfScope ps(c, PC_GEMM_J, 2.0 * (x.fl + y.fl));
+      ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false>(c, x.t2, x.a2j, x.ej, y.t2, y.a2j, y.ej)));
     } else {
-      ProfScope ps(c, PC_GEMM_A2, q[h].fl);
-      ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false, TRI_A_UPPER>(c, q[h].tu, q[h].a2, q[h].e2)));
+      ProfScope ps(c, PC_GEMM_A2, x.fl + y.fl);
+      ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false, TRI_A_UPPER>(c, x.t2, x.a2j, x.e2, y.t2, y.a2j, y.e2)));
     }
   }
   return 0;
@@ -284,18 +297,14 @@ int latent_chunk_kgrad(zigp_ctx* c, Latent& lt, const double* dX, int64_t Nrows,
 }
 
 // Rank-N update of the lower-triangular cotangent of one latent and chunk
-int latent_chunk_syrk(zigp_ctx* c, Latent& lt, int64_t Nc) {
-  const int Mp = lt.Mp, nbm = Mp / BM;
-  TileList ts;
-  ZIGP_TRY(tiles_syr2k(c, nbm, (int)(Nc / BK), syr_plan(nbm), ts));
-  const double fl = (double)lt.M * lt.M * (double)Nc;
-  {
-    ProfScope ps(c, PC_SYR2K, fl);   // planes += tril(A1 G A1^T)   (G = diag(gv) applied as k-scale on the B operand)
-    GemmArgs g = mk_args(lt.A1.p, Nc, lt.A1.p, Nc, lt.dLpart.p, Mp);
-    g.slice_stride = (int64_t)Mp * Mp; g.kscale = lt.gv.p;
-    ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_KCONTIG, true, TRI_C_LOWER>(c, ts, g, EpiAccum())));
-  }
-  return 0;
+int latent_chunk_syrk(zigp_ctx* c, const ChunkPlan& pl, int h) {
+  Latent& lt = c->lat[h];
+  const int Mp = lt.Mp;
+  const int64_t Nc = pl.Nc;
+  ProfScope ps(c, PC_SYR2K, pl.lat[h].fl);   // planes += tril(A1 G A1^T)   (G = diag(gv) applied as k-scale on the B operand)
+  GemmArgs g = mk_args(lt.A1.p, Nc, lt.A1.p, Nc, lt.dLpart.p, Mp);
+  g.slice_stride = (int64_t)Mp * Mp; g.kscale = lt.gv.p;
+  return run_gemm<LAY_KCONTIG, LAY_KCONTIG, true, TRI_C_LOWER>(c, pl.lat[h].syr, g, EpiAccum());
 }
 
 // MxM backward: G = dELBO/dKuu (symmetric) -> krow accumulators.
@@ -389,6 +398,7 @@ struct DenseCall {
   bool need_grad, has_rows;
   HostLatent hl[2]; const double* ell_h[2];
   int64_t Nc = 0;         // rows per full chunk
+  ChunkPlan plan[2];      // the full chunk and, if smaller, the last one (run_dense)
   int pw_blocks = 0;
   int* hinfo = nullptr;   // Cholesky status, staged with the other results
   bool prep_side = false; // buffers / zeroed accumulators / first Kuf panels were issued on the third stream (dense_mxm_forward)
@@ -433,8 +443,9 @@ int64_t auto_chunk_for(bool chunk_auto, int64_t chunk_set, int64_t Mp) {
 // Rows per pass for a row range of `span` rows.  A range of up to 131072 rows goes through in ONE pass unless the caller fixed the chunk: no
 // chunk boundary (where the side stream's kgrads outlast the rank-N updates), one prologue / tail per product instead of two to four -- cfg2
 // (1e5 rows, M = 512) 5.98 -> 5.81 ms, the 125 000-row shard of cfg3 23.4 -> 23.0 ms (tools/chunk_sweep.py, profiles/r04ao_chunk_sweep.log).
-// The rule is bounded by the panels' bytes (4 panels of 8 Mp span bytes per latent: <= 9 GB, i.e. M <= 1024 at 131072 rows -- what was
-// measured); beyond that, and on long ranges, the M-scaled chunk applies (cfg3: 32768 rows 167.8 ms, 65536: 170.2, 131072: 169.2).
+// The rule is bounded by the panels' bytes: a call holds 3 panels of 8 Mp span bytes per latent (K, A1, J'), and the bound budgets 4 of
+// them against 9 GB -- deliberately conservative: one pass was measured only up to M = 1024 at 131072 rows.  Beyond that, and on long
+// ranges, the M-scaled chunk applies (cfg3: 32768 rows 167.8 ms, 65536: 170.2, 131072: 169.2).
 int64_t chunk_rows_for(bool chunk_auto, int64_t chunk_set, int64_t Mp, int64_t span) {
   int64_t chunk = auto_chunk_for(chunk_auto, chunk_set, Mp);
   if (chunk_auto && span > 0 && span <= 131072 && 4 * 2 * 8 * Mp * round_up(span, 1024) <= ((int64_t)9 << 30)) chunk = 131072;
@@ -443,8 +454,6 @@ int64_t chunk_rows_for(bool chunk_auto, int64_t chunk_set, int64_t Mp, int64_t s
   return std::max<int64_t>(1024, round_up((span + nchunks - 1) / nchunks, 1024));
 }
 int dense_prepare_buffers(zigp_ctx* c, DenseCall& k) {
-  const int64_t span = k.has_rows ? (k.row_end - k.row_begin) : 0;
-  k.Nc = chunk_rows_for(c->chunk_auto, c->chunk, std::max(c->lat[0].Mp, c->lat[1].Mp), span);
   const int64_t Nc = k.Nc;
   const int D = k.D;
   k.pw_blocks = (int)(Nc / PW_PTS);
@@ -563,7 +572,8 @@ int dense_chunk_loop(zigp_ctx* c, const DenseCall& k) {
     const bool kuf_fwd_side = c->overlap == 1 && c->fwd_kuf_side && !k.need_grad && has_next && !timed && !timed_next;
     std::function<int()> after_a1;
     if (kuf_fwd_side) after_a1 = [&] { return on_side([&] { return kuf(n1); }); };
-    ZIGP_TRY(chunk_forward(c, Nc, k.need_grad, after_a1));
+    const ChunkPlan& pl = k.plan[Nc == k.plan[0].Nc ? 0 : 1];
+    ZIGP_TRY(chunk_forward(c, pl, k.need_grad, after_a1));
     // the point-wise stage of a gradient step needs the J' launch's sums (it rode inside the J' launch while the variance came from A2:
     // r5, profiles/r05t_ab_fuse_pointwise.log), so it is a launch of its own after it
     ZIGP_TRY(dense_pointwise(c, k, n0, Nc));
@@ -579,7 +589,7 @@ int dense_chunk_loop(zigp_ctx* c, const DenseCall& k) {
       }));
     if (k.need_grad) {
       if (!kgrad_side) ZIGP_TRY(kgrad(n0, Nc));
-      for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_syrk(c, c->lat[h], Nc));
+      for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_syrk(c, pl, h));
     }
     if (has_next && !kuf_side && !kuf_fwd_side) {   // a timed next chunk gets its panels from the main stream, with the side stream drained
       ZIGP_TRY(wait_side());
@@ -650,6 +660,15 @@ int run_dense(zigp_ctx* c, const zigp_params* p, const double* dX, const double*
   k.hl[0] = HostLatent{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f};
   k.hl[1] = HostLatent{p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g};
   k.ell_h[0] = p->ell_f; k.ell_h[1] = p->ell_g;
+  const int64_t span = k.has_rows ? row_end - row_begin : 0;
+  k.Nc = chunk_rows_for(c->chunk_auto, c->chunk, round_up(std::max(p->Mf, p->Mg), BM), span);
+  if (k.has_rows) {     // every tile list of the chunk loop, uploaded before the call enqueues anything
+    const int M[2] = {p->Mf, p->Mg};
+    const int64_t last = std::min<int64_t>(k.Nc, round_up(span - (span - 1) / k.Nc * k.Nc, 1024));
+    k.plan[0] = chunk_plan(M, k.Nc, k.need_grad, c->trmm_tail);
+    ZIGP_TRY(upload_plan(c, k.plan[0]));
+    if (last != k.Nc) { k.plan[1] = chunk_plan(M, last, k.need_grad, c->trmm_tail); ZIGP_TRY(upload_plan(c, k.plan[1])); }
+  }
   ZIGP_TRY(dense_mxm_forward(c, k));
   if (k.prep_side) ZIGP_HIP(c, hipStreamWaitEvent(c->stream_main, c->ev_prep, 0));
   else ZIGP_TRY(dense_prepare_buffers(c, k));
@@ -730,7 +749,7 @@ int zigp_set_chunk(zigp_ctx* c, int64_t chunk_rows) {
   if (!c) return ZIGP_EARG;
   if (chunk_rows == 0) { c->chunk_auto = true; c->chunk = 32768; return ZIGP_OK; }   // back to the automatic rule
   if (chunk_rows < 1024 || chunk_rows % 1024 != 0) return fail_arg(c, "chunk must be a positive multiple of 1024 (or 0: automatic)");
-  if (chunk_rows > (1 << 20)) return fail_arg(c, "chunk must be <= 1048576 rows (32-bit staging offsets; 5 panels of 8*M*chunk bytes per latent)");
+  if (chunk_rows > (1 << 20)) return fail_arg(c, "chunk must be <= 1048576 rows (32-bit staging offsets; 3 panels (K, A1, J') of 8*M*chunk bytes per latent)");
   c->chunk = chunk_rows;
   c->chunk_auto = false;
   return ZIGP_OK;
@@ -987,16 +1006,15 @@ int zigp_test_kuf(zigp_ctx* c, int64_t N, int32_t M, int32_t D, const double* X,
 }
 
 int zigp_test_trmm_list(int32_t lower, int32_t Mf, int32_t Mg, int64_t Nc, int32_t tail_on, int64_t* out) {
-  // host only (no context, no GPU): the lists chunk_forward would launch for a chunk of Nc rows, checked tile by tile
+  // host only (no context, no GPU): the lists run_dense plans for A1 (lower) or A2 (upper) of a chunk of Nc rows, checked tile by tile
   if (Mf <= 0 || Mg <= 0 || Nc <= 0 || Nc % BN != 0 || !out) return ZIGP_EARG;
   const int Mp[2] = {(int)round_up(Mf, BM), (int)round_up(Mg, BM)}, nbn = (int)(Nc / BN), kb = BM / BK;
-  TrmmTail tail;
-  const bool paired = chunk_trmm_plan(Mp[0], Mp[1], nbn, tail_on != 0, tail);
+  const ChunkPlan pl = chunk_plan({Mf, Mg}, Nc, false, tail_on != 0);
   int64_t wgs[2], per[2], worst_tail = 0;
   for (int h = 0; h < 2; ++h) {
     const int nbm = Mp[h] / BM;
     std::vector<GemmTile> v;
-    per[h] = build_trmm_list(lower != 0, nbm, nbn, paired, tail.units[h], tail.bins[h], v);
+    per[h] = (lower ? pl.lat[h].a1_spec : pl.lat[h].a2j_spec).build(v);
     if (v.size() % (size_t)per[h]) return -10;
     wgs[h] = (int64_t)(v.size() / per[h]);
     std::vector<int> seen((size_t)nbm * nbn, 0);
@@ -1008,8 +1026,8 @@ int zigp_test_trmm_list(int32_t lower, int32_t Mf, int32_t Mg, int64_t Nc, int32
       seen[(size_t)t.bi * nbn + t.bj] += 1;
     }
     for (int q : seen) if (q != 1) return -13;                          // every tile exactly once
-    if (paired && tail.units[h] > 0) {                                  // workgroups behind the regular units: the LPT tail
-      const int64_t regular = wgs[h] - 8 * (int64_t)std::min(64, tail.bins[h]);
+    if (pl.paired && pl.tail.units[h] > 0) {                            // workgroups behind the regular units: the LPT tail
+      const int64_t regular = wgs[h] - 8 * (int64_t)std::min(64, pl.tail.bins[h]);
       for (int64_t w = std::max<int64_t>(regular, 0); w < wgs[h]; ++w) {
         int64_t load = 0;
         for (int e = 0; e < per[h]; ++e) { const GemmTile& t = v[(size_t)w * per[h] + e]; load += std::max(0, t.kend - t.kbeg) / kb; }
@@ -1017,7 +1035,7 @@ int zigp_test_trmm_list(int32_t lower, int32_t Mf, int32_t Mg, int64_t Nc, int32
       }
     }
   }
-  out[0] = wgs[0]; out[1] = wgs[1]; out[2] = per[0]; out[3] = per[1]; out[4] = tail.units[0]; out[5] = tail.units[1]; out[6] = worst_tail; out[7] = paired ? 1 : 0;
+  out[0] = wgs[0]; out[1] = wgs[1]; out[2] = per[0]; out[3] = per[1]; out[4] = pl.tail.units[0]; out[5] = pl.tail.units[1]; out[6] = worst_tail; out[7] = pl.paired ? 1 : 0;
   return ZIGP_OK;
 }
 

@@ -19,7 +19,7 @@
 //         M0 base with a 144-double stride (odd k rows land 128 B further round the banks).
 //     One s_barrier per BK step; counted vmcnt keeps NSTAGE-2 stages in flight across it.
 //   * a workgroup runs a host-built UNIT of list entries (GemmArgs::per consecutive tiles, each with its own k range and k
-//     direction); the lists are built in zigp_host.h (tiles_trmm / tiles_syr2k / tiles_full_xcd).
+//     direction); the lists are built in zigp_host.h (trmm_tiles / syr2k_tiles / full_xcd_tiles).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -82,7 +82,8 @@ struct GemmArgs {
 
 // ---- epilogues --------------------------------------------------------------------------------
 // acc[tm][tn][r] of lane l is C[row0 + wm*RW + tm*16 + 4r + l/16][col0 + wn*64 + tn*16 + l%16]  (RW = 64 or 32 rows per wave).
-// An epilogue is `template <int TM, int TN> void operator()(const double (&acc)[TM][TN][4], const EpiCtx&) const`.
+// An epilogue is `template <int TM, int TN> void operator()(const double (&acc)[TM][TN][4], const EpiCtx&) const` with
+// `static constexpr bool writes_c`: whether it stores through e.C (run_gemm refuses a NULL C for those; the others get e.C = nullptr).
 struct EpiCtx {
   double* C; int64_t ldc; double alpha;
   int64_t row0, col0;   // first row / column of this wave's sub-tile (tm = 0, tn = 0)
@@ -103,6 +104,7 @@ __device__ __forceinline__ void epi_foreach(const double (&acc)[TM][TN][4], cons
     }
 }
 struct EpiStore {   // C = alpha*acc
+  static constexpr bool writes_c = true;
   template <int TM, int TN>
   __device__ __forceinline__ void operator()(const double (&acc)[TM][TN][4], const EpiCtx& e) const {
     double* __restrict__ C = e.C; const int64_t ld = e.ldc;
@@ -110,6 +112,7 @@ struct EpiStore {   // C = alpha*acc
   }
 };
 struct EpiAccum {   // C += alpha*acc
+  static constexpr bool writes_c = true;
   template <int TM, int TN>
   __device__ __forceinline__ void operator()(const double (&acc)[TM][TN][4], const EpiCtx& e) const {
     double* C = e.C; const int64_t ld = e.ldc;
@@ -159,14 +162,16 @@ __device__ __forceinline__ void epi_colsum(const double (&acc)[TM][TN][4], const
   }
 }
 struct EpiStoreColsum {
+  static constexpr bool writes_c = true;
   const double* __restrict__ w1; const double* __restrict__ w2; double* __restrict__ out1; double* __restrict__ out2;
   template <int TM, int TN>
   __device__ __forceinline__ void operator()(const double (&acc)[TM][TN][4], const EpiCtx& e) const { epi_colsum<true>(acc, e, w1, w2, out1, out2); }
 };
 // The column sums WITHOUT the panel (round 6): A2 = W^T A1 is needed for  sum_m s^2 A2^2  only -- the reverse pass takes J' = (Q W^T) A1 from
 // A1 directly and A2 gm = W^T (A1 gm) is linear -- so the product's 8 Mp Nc bytes are never written: same accumulators, same sums, bit for bit.
-// e.ldc is still the row stride of the partial-row planes; e.C is not used.
+// e.ldc is still the row stride of the partial-row planes.
 struct EpiColsum {
+  static constexpr bool writes_c = false;
   const double* __restrict__ w1; const double* __restrict__ w2; double* __restrict__ out1; double* __restrict__ out2;
   template <int TM, int TN>
   __device__ __forceinline__ void operator()(const double (&acc)[TM][TN][4], const EpiCtx& e) const { epi_colsum<false>(acc, e, w1, w2, out1, out2); }
@@ -179,6 +184,7 @@ struct EpiColsum {
 // so that their latency overlaps them (the whole wave tile's K at once spills: 64 accumulator + 64 K registers); the sum runs in the
 // fixed order of epi_colsum (bit-stable).
 struct EpiStorePanelKColsum {
+  static constexpr bool writes_c = true;
   const double* __restrict__ K; double* __restrict__ out;
   template <int TM, int TN>
   __device__ __forceinline__ void operator()(const double (&acc)[TM][TN][4], const EpiCtx& e) const {
@@ -319,7 +325,7 @@ enum { TRI_NONE = 0,
 // A ring stage has room for two operand tiles, so a step of this path covers TWO BK slices (the second one in the B slot; the k-scale
 // slices ride in the spare 2 KB behind each image): half the barriers and staging waits per MFMA of the generic path, which is what
 // brings a diagonal tile down to ~0.6 of a full tile's time.  The host gives diagonal tiles k ranges twice as long as the others'
-// (tiles_syr2k): both kinds of workgroup then finish together, and every XCD's tiles stay inside one window of k.
+// (syr2k_tiles): both kinds of workgroup then finish together, and every XCD's tiles stay inside one window of k.
 template <int W, int NSTAGE, bool KSCALE, class Epi>
 __device__ __forceinline__ void syrk_diag_tile(const GemmArgs& g, const GemmTile& tl, double* lds, int wave, int lane, const Epi& epi) {
   constexpr int WAVES = 4, CHUNKS = Shape<WAVES>::CHUNKS;
@@ -402,7 +408,7 @@ __device__ __forceinline__ void syrk_diag_tile(const GemmArgs& g, const GemmTile
     if (2 * it + 1 < total) slice_mfma(As + TILE_DOUBLES);
   }
   EpiCtx e;
-  e.C = g.C + (int64_t)tl.slice * g.slice_stride; e.ldc = g.ldc; e.alpha = g.alpha; e.lane = lane; e.prow = 0;
+  e.C = Epi::writes_c ? g.C + (int64_t)tl.slice * g.slice_stride : nullptr; e.ldc = g.ldc; e.alpha = g.alpha; e.lane = lane; e.prow = 0;
   e.col0 = row0;
   e.row0 = row0 + R2 * 16; epi(acc2, e);
   e.row0 = row0 + R1 * 16; epi(acc1, e);
@@ -587,7 +593,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const GemmTile& tl,
   }
 
   EpiCtx e;
-  e.C = g.C + (int64_t)tl.slice * g.slice_stride; e.ldc = g.ldc; e.alpha = g.alpha;
+  e.C = Epi::writes_c ? g.C + (int64_t)tl.slice * g.slice_stride : nullptr; e.ldc = g.ldc; e.alpha = g.alpha;
   e.row0 = row0 + wrow; e.col0 = col0 + wn * WTN; e.lane = lane; e.prow = (int64_t)tl.bi * WMW + wm; e.tm_stride = tm_stride;
   epi(acc, e);
 }

@@ -5,40 +5,34 @@
 #include "zigp_kernels.h"
 #include <algorithm>
 #include <cmath>
+#include <functional>
 
 namespace zigp {
-
-struct EpiPhi {  // Phi: keep strictly-lower, halve the diagonal, zero above
-  template <int TM, int TN>
-  __device__ __forceinline__ void operator()(const double (&acc)[TM][TN][4], const EpiCtx& e) const {
-    double* __restrict__ C = e.C; const int64_t ld = e.ldc;
-    epi_foreach(acc, e, [&](int64_t i, int64_t j, double v) { C[i * ld + j] = (j < i) ? v : ((j == i) ? 0.5 * v : 0.0); });
-  }
-};
 
 static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 
-// Device copy of a tile list into the context's cache under `key` (the cache entry owns it)
-static int put_tiles(zigp_ctx* c, const std::string& key, const std::vector<GemmTile>& v, int per, TileList& out) {
+// A tile list by name: its key in the context's tile cache and the host-only step that builds it (returns the entries per workgroup)
+struct TileSpec { std::string key; std::function<int(std::vector<GemmTile>&)> build; };
+// The cached device copy of a list; a list the cache has not seen yet is built and uploaded (hipMalloc + a synchronous copy) first
+static int get_tiles(zigp_ctx* c, const TileSpec& s, TileList& out) {
+  auto it = c->tiles.find(s.key);
+  if (it != c->tiles.end()) { out = it->second.view(); return 0; }
+  std::vector<GemmTile> v;
   CachedTiles t;
-  t.n = (int)v.size(); t.per = per;
+  t.per = s.build(v); t.n = (int)v.size();
   if (t.n > 0) {
     GemmTile* d = nullptr;
     ZIGP_HIP(c, hipMalloc((void**)&d, sizeof(GemmTile) * v.size()));
     t.d.reset(d);
     ZIGP_HIP(c, hipMemcpy(d, v.data(), sizeof(GemmTile) * v.size(), hipMemcpyHostToDevice));
   }
-  out = c->tiles.emplace(key, std::move(t)).first->second.view();
+  out = c->tiles.emplace(s.key, std::move(t)).first->second.view();
   return 0;
 }
-template <class F>
+template <class F>   // build(v): a list of one entry per workgroup
 static int get_tiles(zigp_ctx* c, const std::string& key, F build, TileList& out) {
-  auto it = c->tiles.find(key);
-  if (it != c->tiles.end()) { out = it->second.view(); return 0; }
-  std::vector<GemmTile> v;
-  build(v);
-  return put_tiles(c, key, v, 1, out);
+  return get_tiles(c, TileSpec{key, [&](std::vector<GemmTile>& v) { build(v); return 1; }}, out);
 }
 
 static inline GemmTile mk_tile(int bi, int bj, int kbeg, int kend, int slice = 0) {
@@ -49,17 +43,21 @@ constexpr int NST = 2;   // LDS ring depth of the GEMM core (2 stages = 74 KB pe
 
 // Workgroup shape per operand-layout pair (see Shape<> in zigp_gemm.h): 8 waves where the kernel fits 128 VGPRs -- the m/n-contiguous
 // products, i.e. all of the chunk loop's but the rank-N update.  The lower-triangular products (A1 = W K) read their factor TRANSPOSED
-// (m-contiguous image W^T, written once per step by k_transpose_scale) so that they run that kernel too (r3: A1 56-57 -> 60-61 TFLOP/s,
+// (m-contiguous image W^T, written once per step by k_transpose) so that they run that kernel too (r3: A1 56-57 -> 60-61 TFLOP/s,
 // profiles/r03c_ab_tail.log).  The 8-wave shape for the rank-N update and the 4-wave shape for the triangular products were measured
 // again on the 16x16x4 core and lose (profiles/r04m_ab_shapes.log).
 template <int AL, int BL, bool KS> struct WavesFor { static constexpr int value = 4; };
 template <> struct WavesFor<LAY_MNCONTIG, LAY_MNCONTIG, false> { static constexpr int value = 8; };
 
+// One launch of the GEMM core over one argument set, or over two (latent f and latent g of one chunk): set 1's workgroups follow set
+// 0's in the dispatch order, so the tail of one product is filled by the head of the other and the forward products of a chunk are
+// three launches instead of six.  An empty set is left out.
 template <int AL, int BL, bool KS, int TRI = TRI_NONE, class EP>
-static int run_gemm(zigp_ctx* c, const TileList& tl, GemmArgs g, EP ep) {
+static int run_gemm(zigp_ctx* c, TileList tl0, GemmArgs g0, EP ep0, TileList tl1 = {}, GemmArgs g1 = {}, EP ep1 = {}) {
+  if (tl0.n == 0) { tl0 = tl1; g0 = g1; ep0 = ep1; tl1 = TileList(); }
+  if (tl0.n == 0) return 0;
+  if (EP::writes_c && (!g0.C || (tl1.n > 0 && !g1.C))) return fail_arg(c, "run_gemm: the epilogue stores C, and C is NULL");
   constexpr int WV = WavesFor<AL, BL, KS>::value;
-  if (tl.n == 0) return 0;
-  g.tiles = tl.d; g.per = tl.per;
   constexpr size_t shm = sizeof(double) * NST * STAGE_DOUBLES;
   static bool attr_set = false;   // per instantiation
   if (!attr_set) {
@@ -67,30 +65,12 @@ static int run_gemm(zigp_ctx* c, const TileList& tl, GemmArgs g, EP ep) {
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     attr_set = true;
   }
-  const int nwg = tl.n / tl.per;
-  hipLaunchKernelGGL((gemm_f64_kernel<AL, BL, NST, KS, TRI, WV, EP>), dim3(nwg), dim3(64 * WV), shm, c->stream, g, ep, g, ep, nwg);
-  ZIGP_HIP(c, hipGetLastError());
-  return 0;
-}
-// The same product for two argument sets (latent f and latent g of one chunk) in ONE launch: set 1's workgroups follow set 0's in the
-// dispatch order, so the tail of one product is filled by the head of the other and the forward products of a chunk are three
-// launches instead of six.
-template <int AL, int BL, bool KS, int TRI = TRI_NONE, class EP>
-static int run_gemm2(zigp_ctx* c, const TileList& tl0, GemmArgs g0, EP ep0, const TileList& tl1, GemmArgs g1, EP ep1) {
-  if (tl0.n == 0) return run_gemm<AL, BL, KS, TRI>(c, tl1, g1, ep1);
-  if (tl1.n == 0) return run_gemm<AL, BL, KS, TRI>(c, tl0, g0, ep0);
-  constexpr int WV = WavesFor<AL, BL, KS>::value;
-  g0.tiles = tl0.d; g0.per = tl0.per; g1.tiles = tl1.d; g1.per = tl1.per;
-  constexpr size_t shm = sizeof(double) * NST * STAGE_DOUBLES;
-  static bool attr_set = false;   // per instantiation
-  if (!attr_set) {
-    ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f64_kernel<AL, BL, NST, KS, TRI, WV, EP>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    attr_set = true;
-  }
-  const int n0 = tl0.n / tl0.per, n1 = tl1.n / tl1.per;
-  hipLaunchKernelGGL((gemm_f64_kernel<AL, BL, NST, KS, TRI, WV, EP>), dim3((unsigned)(round_up(n0, 8) + n1)), dim3(64 * WV), shm, c->stream,
-                     g0, ep0, g1, ep1, n0);
+  g0.tiles = tl0.d; g0.per = tl0.per;
+  const int n0 = tl0.n / tl0.per;
+  int64_t nwg = n0;
+  if (tl1.n > 0) { g1.tiles = tl1.d; g1.per = tl1.per; nwg = round_up(n0, 8) + tl1.n / tl1.per; }
+  else { g1 = g0; ep1 = ep0; }     // one set: workgroups [0, n0) are the whole grid
+  hipLaunchKernelGGL((gemm_f64_kernel<AL, BL, NST, KS, TRI, WV, EP>), dim3((unsigned)nwg), dim3(64 * WV), shm, c->stream, g0, ep0, g1, ep1, n0);
   ZIGP_HIP(c, hipGetLastError());
   return 0;
 }
@@ -204,17 +184,13 @@ static int build_trmm_list(bool lower, int nbm, int nbn, bool paired, int tail_u
   }
   return per;
 }
-static int tiles_trmm(zigp_ctx* c, bool lower, int nbm, int nbn, bool paired, TileList& tl, int tail_units = 0, int tail_bins = 64) {
-  const std::string key = std::string(lower ? "trl:" : "tru:") + std::to_string(nbm) + ":" + std::to_string(nbn) + (paired ? ":p" : ":l") +
-                          (tail_units > 0 ? ":t" + std::to_string(tail_units) + ":" + std::to_string(tail_bins) : std::string());
-  auto it = c->tiles.find(key);
-  if (it != c->tiles.end()) { tl = it->second.view(); return 0; }
-  std::vector<GemmTile> list;
-  const int per = build_trmm_list(lower, nbm, nbn, paired, tail_units, tail_bins, list);
-  return put_tiles(c, key, list, per, tl);
+static TileSpec trmm_tiles(bool lower, int nbm, int nbn, bool paired, int tail_units, int tail_bins) {
+  return {std::string(lower ? "trl:" : "tru:") + std::to_string(nbm) + ":" + std::to_string(nbn) + (paired ? ":p" : ":l") +
+              (tail_units > 0 ? ":t" + std::to_string(tail_units) + ":" + std::to_string(tail_bins) : std::string()),
+          [=](std::vector<GemmTile>& v) { return build_trmm_list(lower, nbm, nbn, paired, tail_units, tail_bins, v); }};
 }
 // The paired order has nbn * ceil(nbm / 2) units of EQUAL length per latent: it pays (2.2x fewer bytes, +6 % on the triangular
-// products) where the units of BOTH latents, launched together (run_gemm2), fill whole waves of the 512 resident workgroups --
+// products) where the units of BOTH latents, launched together (run_gemm with two sets), fill whole waves of the 512 resident workgroups --
 // cfg3: 2 x 256 panels x 4 units = 4 waves exactly; cfg2: 2 x 784 x 2 = 3136 units = 6.1 waves, 0.875 full, still -1.3 % against LPT
 // (profiles/r05l_ab_merge_fg.log); launched per latent the same units are 3.06 waves and lose (+1.6 %).  Otherwise LPT, one launch
 // per latent, whose tiles of mixed length pack the tail.
@@ -222,8 +198,6 @@ static inline bool trmm_paired_pays(int units_both_latents) {
   const int slots = 512, waves = (units_both_latents + slots - 1) / slots;
   return units_both_latents >= slots && (double)units_both_latents / ((double)waves * slots) >= 0.85;
 }
-static int tiles_trmm_lower(zigp_ctx* c, int nbm, int nbn, TileList& tl, bool paired, int tail_units = 0, int tail_bins = 64) { return tiles_trmm(c, true, nbm, nbn, paired, tl, tail_units, tail_bins); }
-static int tiles_trmm_upper(zigp_ctx* c, int nbm, int nbn, TileList& tl, bool paired, int tail_units = 0, int tail_bins = 64) { return tiles_trmm(c, false, nbm, nbn, paired, tl, tail_units, tail_bins); }
 // Tail plan of a merged launch [set 0's units | set 1's units] (unit counts multiples of 8, nbm + 1 k blocks per unit) over 512 slots:
 // with a remainder r the last r + 512 units -- the end of set 1 and, where set 1 is shorter than that, the end of set 0 as well -- become
 // ONE wave of 512 LPT workgroups (64 per XCD, shared between the two sets in proportion to their tails' work) whenever that wave is
@@ -267,8 +241,8 @@ static inline SyrPlan syr_plan(int nbm) {
 // Lower-triangular output tiles x split-K slices over nk k-steps.  Launch position p runs on XCD p % 8 (observed round-robin dispatch;
 // speed only): XCD x is handed the tiles whose k range lies in the x-th eighth of the k range (both slice counts multiples of 8), else
 // -- no diagonal path -- a contiguous run of the k-major tile order.
-static int tiles_syr2k(zigp_ctx* c, int nbm, int nk, SyrPlan sp, TileList& tl) {
-  return get_tiles(c, "syr:" + std::to_string(nbm) + ":" + std::to_string(nk) + ":" + std::to_string(sp.So) + ":" + std::to_string(sp.Sd), [&](std::vector<GemmTile>& v) {
+static TileSpec syr2k_tiles(int nbm, int nk, SyrPlan sp) {
+  return {"syr:" + std::to_string(nbm) + ":" + std::to_string(nk) + ":" + std::to_string(sp.So) + ":" + std::to_string(sp.Sd), [=](std::vector<GemmTile>& v) {
     auto entry = [&](int bi, int bj, int s, int S) { return mk_tile(bi, bj, (int)((int64_t)nk * s / S), (int)((int64_t)nk * (s + 1) / S), s); };
     if (sp.So % 8 == 0 && sp.Sd % 8 == 0) {
       std::vector<GemmTile> q[8];
@@ -281,7 +255,7 @@ static int tiles_syr2k(zigp_ctx* c, int nbm, int nk, SyrPlan sp, TileList& tl) {
       }
       for (size_t e = 0; e < q[0].size(); ++e)          // all eight queues have the same length
         for (int x = 0; x < 8; ++x) v.push_back(q[x][e]);
-      return;
+      return 1;
     }
     std::vector<GemmTile> t;
     for (int bi = 0; bi < nbm; ++bi)
@@ -296,13 +270,14 @@ static int tiles_syr2k(zigp_ctx* c, int nbm, int nk, SyrPlan sp, TileList& tl) {
       const int idx = per * (p % 8) + p / 8;
       if (p / 8 < per && idx < n) v.push_back(t[idx]);
     }
-  }, tl);
+    return 1;
+  }};
 }
 // Full product over column panels, for the chunk loop: panel bj goes to XCD bj % 8 (launch position p runs on XCD p % 8), its nbm row
 // blocks are consecutive entries of that XCD's queue -- they start together and walk the panel's k range in lockstep, so a panel's
 // slab is fetched into that L2 once.  All tiles have the same length: nbm * nbn tiles over the 512 resident workgroups.
-static int tiles_full_xcd(zigp_ctx* c, int nbm, int nbn, int nk, TileList& tl) {
-  return get_tiles(c, "fullx:" + std::to_string(nbm) + ":" + std::to_string(nbn) + ":" + std::to_string(nk), [&](std::vector<GemmTile>& v) {
+static TileSpec full_xcd_tiles(int nbm, int nbn, int nk) {
+  return {"fullx:" + std::to_string(nbm) + ":" + std::to_string(nbn) + ":" + std::to_string(nk), [=](std::vector<GemmTile>& v) {
     std::vector<GemmTile> q[8];
     for (int bj = 0; bj < nbn; ++bj)
       for (int bi = 0; bi < nbm; ++bi) q[bj % 8].push_back(mk_tile(bi, bj, 0, nk));
@@ -310,7 +285,8 @@ static int tiles_full_xcd(zigp_ctx* c, int nbm, int nbn, int nk, TileList& tl) {
     for (int x = 0; x < 8; ++x) longest = std::max(longest, q[x].size());
     for (size_t e = 0; e < longest; ++e)
       for (int x = 0; x < 8; ++x) v.push_back(e < q[x].size() ? q[x][e] : mk_tile(0, 0, 0, 0));
-  }, tl);
+    return 1;
+  }};
 }
 static int tiles_full(zigp_ctx* c, int nbm, int nbn, int nk, TileList& tl) {
   return get_tiles(c, "full:" + std::to_string(nbm) + ":" + std::to_string(nbn) + ":" + std::to_string(nk), [&](std::vector<GemmTile>& v) {

@@ -724,11 +724,10 @@ __global__ void k_colscale(const double* __restrict__ W, const double* __restric
   if (idx >= Mp * Mp) return;
   out[idx] = s2[idx % Mp] * W[idx];
 }
-// Wt = W^T and (optionally) Wpt = (W diag(s2))^T = diag(s2) W^T, through a 32 x 33 LDS tile (coalesced reads and writes).
-// The lower-triangular products A1 = W K and H = W diag(s^2) A2 then read their triangular factor m-contiguous, like the W^T products:
-// all four run the 8-wave kernel shape (zigp_host.h, WavesFor).  Launch with dim3(Mp / 32, Mp / 32), dim3(32, 8).
+// Wt = W^T through a 32 x 33 LDS tile (coalesced reads and writes).  The lower-triangular product A1 = W K then reads its triangular
+// factor m-contiguous, like the W^T product A2, and runs the 8-wave kernel shape (zigp_host.h, WavesFor).  Launch with dim3(Mp / 32, Mp / 32), dim3(32, 8).
 __global__ void __launch_bounds__(256)
-k_transpose_scale(const double* __restrict__ W, const double* __restrict__ s2, int64_t Mp, double* __restrict__ Wt, double* __restrict__ Wpt) {
+k_transpose(const double* __restrict__ W, int64_t Mp, double* __restrict__ Wt) {
   __shared__ double tile[32][33];
   const int bx = blockIdx.x * 32, by = blockIdx.y * 32;
   for (int j = threadIdx.y; j < 32; j += 8) tile[j][threadIdx.x] = W[(int64_t)(by + j) * Mp + bx + threadIdx.x];   // W[i = by + j][k = bx + x]
@@ -737,7 +736,6 @@ k_transpose_scale(const double* __restrict__ W, const double* __restrict__ s2, i
     const double v = tile[threadIdx.x][j];                       // W[i = by + x][k = bx + j]
     const int64_t o = (int64_t)(bx + j) * Mp + by + threadIdx.x;   // Wt[k][i]
     Wt[o] = v;
-    if (Wpt) Wpt[o] = v * s2[bx + j];
   }
 }
 // Qt[k][i] = s2[k] * P[k][i] - (k == i):  Q^T for Q = P diag(s^2) - I (P symmetric)
