@@ -61,6 +61,63 @@ int zigp_test_potrf_trtri(zigp_ctx* ctx, int64_t n, const double* A, double* L, 
  * Kuf panel (kern.K(X, Xnew), onofftf/main.py:266; its exponential is hand-written, see csrc/zigp_kernels.h).  X (N,D), Z (M,D), ell (D). */
 int zigp_test_kuf(zigp_ctx* ctx, int64_t N, int32_t M, int32_t D, const double* X, const double* Z, const double* ell, double var, double* K);
 
+/* ---- stage diagnostics: ONE chunk's stage of the dense chunk loop on caller-supplied operands, through the functions the loop itself
+ * runs (chunk_plan -> upload_plan -> chunk_forward, the point-wise launch, latent_chunk_kgrad, latent_chunk_syrk + the plane reduction of
+ * the M x M reverse stage).  Host arrays in, host arrays out; every call synchronises and leaves the context usable for zigp_elbo. ---- */
+/* Device buffers the diagnostics fill before a launch hold this byte in every position (the double ZIGP_STAGE_SENTINEL_BYTE x 8 is
+ * 1.38e306): an output element that still holds it was not written. */
+#define ZIGP_STAGE_SENTINEL_BYTE 0x7f
+typedef struct zigp_stage_latent {
+  int32_t M, reserved;
+  const double* W;    /* (M,M) lower triangular; padded to Mp with the identity, as the factorisation leaves it; W^T by k_transpose */
+  const double* v;    /* (M)   weights of the fused sum v A1 (the mean) */
+  const double* s2;   /* (M)   weights of sum s^2 A2^2 (value mode) */
+  const double* K;    /* (M,Nc) Kuf panel; rows >= M are zero on the device */
+  const double* Rt;   /* (M,M) gradient mode: what the J' launch reads as its factor, (Q W^T)^T; padded with -I (Q = -I where s^2 = 0) */
+  double* A1;         /* out (M,Nc) */
+  double* Jp;         /* out (M,Nc), gradient mode */
+  double* part;       /* out [3][Mp/32][Nc]: the RAW partial-row planes; rows nothing wrote hold the sentinel */
+} zigp_stage_latent;
+/* Forward products of one chunk of Nc rows (a multiple of 1024) for both latents: A1 and the A2 sums (need_grad = 0) or A1 and J'
+ * (need_grad = 1).  only = -1: both latents as the loop launches them; 0 / 1: the plan of the pair, that latent's lists alone (the other
+ * latent's operands may then be NULL).  facts[12] = {paired, tail units f, tail units g, Mp_f, Mp_g, allocated partial rows per plane
+ * f, g, then the counts the point-wise stage is told: np1_f, np2_f, np1_g, np2_g, 0}. */
+int zigp_test_chunk_forward(zigp_ctx* ctx, int64_t Nc, int32_t need_grad, int32_t only, const zigp_stage_latent* lat /*[2]*/, int64_t* facts /*[12]*/);
+
+/* What the M x M forward of a call leaves for the chunk loop, downloaded: out_f / out_g [4] = {W (M,M), v = W u (M), alpha = W^T v (M),
+ * Rt = (Q W^T)^T (M,M; need_grad only)}, any of them NULL.  Runs the upload and the two factorisation chains as zigp_prior_kl does. */
+int zigp_test_latents_forward(zigp_ctx* ctx, const zigp_params* p, double jitter, int32_t need_grad, double* const* out_f, double* const* out_g);
+
+typedef struct zigp_stage_pointwise {
+  int32_t mode;       /* 0 value-only ELBO, 1 gradient step, 2 predict */
+  int32_t repeat;     /* launches (>= 1): acc keeps accumulating */
+  int32_t np_f, np1_f, np2_f, np_g, np1_g, np2_g;   /* allocated rows per plane, rows of planes 0 / 1 and of plane 2 to add */
+  int32_t D, mean_on;
+  const double* part_f;   /* [3][np_f][Nc] */
+  const double* part_g;   /* [3][np_g][Nc] */
+  const double* Y;        /* [Nrows] (NULL: predict) */
+  const double* X;        /* [Nrows][D] */
+  int64_t Nrows, n0, row_end, Nc;
+  double var_f, var_g, noise, g_offset, scale;
+  double mean_a[8], mean_b;
+  double *gm_f, *gv_f, *gm_g, *gv_g;   /* out [Nc] each (gradient step) */
+  double* acc;            /* in / out [Nc/64][13]: the per-block accumulators */
+  double* out9;           /* out [9][row_end] (predict) */
+} zigp_stage_pointwise;
+int zigp_test_pointwise(zigp_ctx* ctx, const zigp_stage_pointwise* a);
+
+/* Kuf cotangent reductions of one chunk: krow [4][M][2+2D] (the KG_SPLIT slabs; in: initial values, out: accumulated).  X (Nrows,D),
+ * Z (M,D), Jp / K (M,Nc), alpha (M), gm / gv (Nc).  exact = 0 / 1 forces the centred / the per-row form, -1 takes the host's rule (needs
+ * ell); centre = NULL: the mean inducing input, as the host computes it. */
+int zigp_test_kgrad(zigp_ctx* ctx, int32_t M, int32_t D, int64_t Nc, int64_t Nrows, int64_t n0, const double* Jp, const double* K,
+                    const double* alpha, const double* gm, const double* gv, const double* X, const double* Z, const double* ell,
+                    const double* centre, int32_t exact, double* krow);
+
+/* Rank-N update C1 = sum_chunks A1_i diag(gv_i) A1_i^T: the chunks' updates one after the other onto zeroed split-K planes, then the
+ * plane reduction.  A1[i] (M,Nc[i]), gv[i] (Nc[i]), Nc[i] multiples of 1024.  C1 (M,M) symmetric; plan[2] = {So, Sd}. */
+int zigp_test_rank_update(zigp_ctx* ctx, int32_t M, int32_t nchunks, const int64_t* Nc, const double* const* A1, const double* const* gv,
+                          double* C1, int64_t* plan /*[2]*/);
+
 #ifdef __cplusplus
 }
 #endif

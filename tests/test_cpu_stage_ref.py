@@ -1,0 +1,227 @@
+"""CPU suite: the host references of tests/stage_ref.py pinned to the oracle, so that a GPU-vs-stage_ref failure in test_gpu_stages.py
+means the kernel is wrong and not the test's idea of the operation.  Needs no GPU."""
+import numpy as np
+import pytest
+import scipy.linalg as sl
+import torch
+
+from conftest import make_problem, relerr
+import stage_ref as sr
+import zigp_oracle as zo
+import zigp_oracle_torch as ot
+
+JITTER = 1e-6
+
+
+def _latent(p, tag, X):
+    """The operands of the chunk loop for one latent, from the oracle's kernel and scipy.linalg's factorisation."""
+    Z, ell, var = p['Z' + tag], p['ell_' + tag], p['var_' + tag]
+    M = Z.shape[0]
+    Kuu = zo.rbf_K(Z, None, ell, var) + np.eye(M) * JITTER
+    L = sl.cholesky(Kuu, lower=True)
+    W = sl.solve_triangular(L, np.eye(M), lower=True)
+    u, s2 = p['u_%sm' % tag].reshape(-1), p['u_%ss_sqrt' % tag].reshape(-1) ** 2
+    K = zo.rbf_K(Z, X, ell, var)
+    P = W.T @ W
+    Rt = W @ (s2[:, None] * P - np.eye(M))          # Qt = diag(s^2) P - I, Rt = W Qt = (Q W^T)^T  (latents_forward)
+    return dict(M=M, W=W, v=W @ u, s2=s2, K=K, Rt=Rt, var=var, cond=np.linalg.cond(Kuu), alpha=W.T @ (W @ u))
+
+
+def _compose(X, Y, p, g_offset=0.0):
+    out = {}
+    for tag in 'fg':
+        q = _latent(p, tag, X)
+        a1 = sr.forward_a1(q['W'], q['v'], q['K'])
+        A1 = a1['A1'][0]
+        a2 = sr.forward_a2(q['W'], q['s2'], A1)
+        jp = sr.forward_jp(q['Rt'], q['K'], A1)
+        q.update(A1=A1, Jp=jp['Jp'][0], mean=a1['s_vA1'][0], sq1=a1['s_A1sq'][0], sq2=a2['s_s2A2sq'][0], kj=jp['s_KJ'][0])
+        q['var_value'] = q['var'] - q['sq1'] + q['sq2']
+        q['var_grad'] = q['var'] + q['kj']
+        out[tag] = q
+    fm = out['f']['mean'] + zo.mean_function(X, p).reshape(-1)
+    gm = out['g']['mean'] + g_offset
+    return out, fm, gm
+
+
+PROBLEMS = [dict(N=700, M=40, D=2, seed=3, Mg=None, mean=False), dict(N=900, M=33, D=3, seed=5, Mg=57, mean=True)]
+
+
+def _problem(c):
+    X, Y, p = make_problem(c['N'], c['M'], c['D'], seed=c['seed'], Mg=c['Mg'])
+    if c['mean']:
+        p = dict(p, mean_a=np.array([0.5, -0.25, 0.125]), mean_b=0.2)
+    return X, Y, p
+
+
+@pytest.mark.parametrize('c', PROBLEMS, ids=['square', 'ragged_mean'])
+def test_composed_references_reproduce_the_oracle(c):
+    """A1, the column sums and the point-wise formulas, composed, give build_predict's nine outputs and elbo's data term within the rule of
+    test_gpu_dense.py for the W-form against the oracle's triangular solves: max(1e-9, 1e-13 cond(Kuu)) relative."""
+    X, Y, p = _problem(c)
+    g_offset = -1.0 if c['mean'] else 0.0
+    lat, fm, gm = _compose(X, Y, p, g_offset)
+    cond = max(lat['f']['cond'], lat['g']['cond'])
+    tol = max(1e-9, 1e-13 * cond)
+    ref = zo.build_predict(X, p, JITTER, g_offset)
+    for variant in ('var_value', 'var_grad'):      # var - sum A1^2 + sum s^2 A2^2 and var + sum K J'
+        fv, gv = lat['f'][variant], lat['g'][variant]
+        o = sr.pointwise_np(fm, fv, gm, gv, Y.reshape(-1), p['noise'])
+        mine = (o['gfmean'], o['gfvar'], o['gfmeanu'], fm, fv, gm, gv, o['e1'], o['ev'])
+        for i, (a, b) in enumerate(zip(mine, ref)):
+            e = relerr(a, b.reshape(-1))
+            print('cond(Kuu)=%.2e %s out9[%d] relerr=%.2e' % (cond, variant, i, e))
+            assert e < tol, (variant, i, e)
+        data_ref = zo.elbo(X, Y, p, JITTER, g_offset=g_offset)[1]
+        e = abs(np.sum(o['ve']) - data_ref) / abs(data_ref)
+        print('cond(Kuu)=%.2e %s data term relerr=%.2e' % (cond, variant, e))
+        assert e < tol, (variant, e)
+
+
+@pytest.mark.parametrize('c', PROBLEMS, ids=['square', 'ragged_mean'])
+def test_sum_K_Jp_is_the_variance_term_to_the_rounding_bound(c):
+    """sum_m K J' = sum s^2 A2^2 - sum A1^2 holds for ANY W (pure algebra: J' = (W^T W S - I) W^T A1, A1 = W K), so the two sides are two
+    evaluations of one polynomial in (K, W, s^2) whose terms' magnitudes sum to  B = |K|^T |W^T| (S |W| |W^T| + I) |W| |K|  per column, at a
+    depth of at most 5 M + 16 roundings (K -> A1 -> A2 -> square -> sum, resp. W -> P -> Q^T -> R^T -> J' -> sum): |lhs - rhs| <= 2 gamma_(5M+16) B."""
+    X, Y, p = _problem(c)
+    lat, _, _ = _compose(X, Y, p)
+    for tag in 'fg':
+        q = lat[tag]
+        M = q['M']
+        aW, aK = np.abs(q['W']), np.abs(q['K'])
+        B = np.sum(aK * (aW.T @ ((q['s2'][:, None] * (aW @ aW.T) + np.eye(M)) @ (aW @ aK))), 0)
+        err = np.abs(q['kj'] - (q['sq2'] - q['sq1']))
+        r, k = sr.worst(err, 2 * sr.gamma(5 * M + 16) * B)
+        print('latent %s M=%d: identity error / bound = %.3g (column %d)' % (tag, M, r, k))
+        assert r <= 1.0
+
+
+def _rule(name, mine, other, truth, S):
+    """err(mine) <= 4 err(other) + 16 eps S, element-wise; returns the largest err(mine) / (eps S)."""
+    e_m, e_o = sr.mp_err(mine, truth), sr.mp_err(other, truth)
+    bad = e_m > 4 * e_o + 16 * sr.EPS * S
+    worst = float(np.max(e_m / (sr.EPS * S)))
+    print('%-7s largest err / (eps S): stage_ref %.3g, autograd %.3g' % (name, worst, float(np.max(e_o / (sr.EPS * S)))))
+    assert not bad.any(), (name, int(np.argmax(bad)), e_m[bad][:3], e_o[bad][:3])
+    return worst
+
+
+@pytest.mark.parametrize('c', PROBLEMS, ids=['square', 'ragged_mean'])
+def test_pointwise_cotangents_against_autograd_at_the_same_doubles(c):
+    """gm / gv of both latents and the noise derivative against torch autograd of the oracle's probit_expectations + variational_expectations
+    at the SAME float64 (fmean, fvar, gmean, gvar): no conditioning in between, so the rule is err <= 4 err_autograd + 16 eps S against
+    the 50-digit evaluation."""
+    X, Y, p = _problem(c)
+    lat, fm, gm = _compose(X, Y, p)
+    fv, gv = lat['f']['var_value'], lat['g']['var_value']
+    y = Y.reshape(-1)
+    n = 256                                              # points (mpmath is the slow side)
+    fm, fv, gm, gv, y = fm[:n], fv[:n], gm[:n], gv[:n], y[:n]
+    o = sr.pointwise_np(fm, fv, gm, gv, y, p['noise'])
+    t = [torch.tensor(a, dtype=torch.float64, requires_grad=True) for a in (fm, fv, gm, gv)]
+    noise = torch.tensor(float(p['noise']), dtype=torch.float64, requires_grad=True)
+    e1, e2, ev = ot.probit_expectations(t[2], t[3])
+    ve = ot.variational_expectations(e1 * t[0], e2 * t[1], ev * torch.square(t[0]), torch.tensor(y), noise)
+    # per-point noise derivative: one backward per output would be slow; d ve_n / d noise through a per-point copy of the noise
+    noise_n = torch.full((n,), float(p['noise']), dtype=torch.float64, requires_grad=True)
+    ve_n = ot.variational_expectations(e1 * t[0], e2 * t[1], ev * torch.square(t[0]), torch.tensor(y), noise_n)
+    torch.sum(ve_n).backward()
+    auto = dict(dfm=t[0].grad.numpy(), dfv=t[1].grad.numpy(), dgm=t[2].grad.numpy(), dgv=t[3].grad.numpy(), dnoise=noise_n.grad.numpy(),
+                ve=ve.detach().numpy())
+    truth = sr.pointwise_mp(fm, fv, gm, gv, y, p['noise'])
+    S = sr.pointwise_scales(fm, fv, gm, gv, y, p['noise'])
+    for k in ('ve', 'dfm', 'dfv', 'dgm', 'dgv', 'dnoise'):
+        _rule(k, o[k], auto[k], truth[k], S[k])
+
+
+def test_kuf_cotangent_sums_are_the_kernel_gradients():
+    """krow's columns are the reverse of KernSE.K: with Phi = sum_mn F_mn K_mn(Z, X, ell, var) and F held fixed, dPhi/dvar = sum_m krow[m,0] / var,
+    dPhi/dZ_md = krow[m,1+d] / ell_d^2, dPhi/dell_d = sum_m krow[m,1+D+d] / ell_d^3 (autograd through the oracle's kernel), and F itself is
+    dData/dK at fixed W: alpha gm^T + 2 J' diag(gv)."""
+    X, Y, p = make_problem(300, 21, 3, seed=11)
+    lat, fm, gmn = _compose(X, Y, p)
+    y = Y.reshape(-1)
+    o = sr.pointwise_np(fm, lat['f']['var_value'], gmn, lat['g']['var_value'], y, p['noise'])
+    for tag, gmk, gvk in (('f', 'dfm', 'dfv'), ('g', 'dgm', 'dgv')):
+        q = lat[tag]
+        Zt, ellt, vart = (torch.tensor(np.asarray(a, dtype=np.float64), requires_grad=True) for a in (p['Z' + tag], p['ell_' + tag], p['var_' + tag]))
+        Kt = ot.rbf_K(Zt, torch.tensor(X), ellt, vart)
+        # F = dData/dK at fixed W, u, s: autograd through the conditional written with W
+        Wt, ut, s2t = torch.tensor(q['W']), torch.tensor(p['u_%sm' % tag].reshape(-1)), torch.tensor(q['s2'])
+        Kl = Kt.detach().clone().requires_grad_(True)
+        A1 = Wt @ Kl
+        A2 = Wt.t() @ A1
+        mean = (Wt @ ut) @ A1
+        var = float(q['var']) - torch.sum(A1 * A1, 0) + s2t @ (A2 * A2)
+        other = lat['g' if tag == 'f' else 'f']
+        if tag == 'f':
+            e1, e2, ev = ot.probit_expectations(torch.tensor(gmn), torch.tensor(other['var_value']))
+            fmean, fvar = mean, var
+        else:
+            e1, e2, ev = ot.probit_expectations(mean, var)
+            fmean, fvar = torch.tensor(fm), torch.tensor(other['var_value'])
+        data = torch.sum(ot.variational_expectations(e1 * fmean, e2 * fvar, ev * torch.square(fmean), torch.tensor(y), torch.tensor(float(p['noise']), dtype=torch.float64)))
+        data.backward()
+        F = q['alpha'][:, None] * o[gmk][None, :] + 2 * q['Jp'] * o[gvk][None, :]
+        tol = max(1e-9, 1e-13 * q['cond'])
+        e = relerr(F, Kl.grad.numpy())
+        print('latent %s cond(Kuu)=%.2e F = dData/dK relerr %.2e' % (tag, q['cond'], e))
+        assert e < tol
+        krow, _ = sr.kgrad(q['Jp'], q['K'], q['alpha'], o[gmk], o[gvk], X, p['Z' + tag], 0)
+        torch.sum(torch.tensor(F) * Kt).backward()
+        ell = np.asarray(p['ell_' + tag])
+        D = X.shape[1]
+        assert relerr(np.sum(krow[:, 0]) / q['var'], float(vart.grad)) < 1e-11
+        assert relerr(krow[:, 1:1 + D] / ell ** 2, Zt.grad.numpy()) < 1e-11
+        assert relerr(np.sum(krow[:, 1 + D:1 + 2 * D], 0) / ell ** 3, ellt.grad.numpy()) < 1e-11
+        assert relerr(krow[:, 1 + 2 * D], q['K'] @ o[gmk]) < 1e-13
+        # the extended-precision reference and the centred bound are the same sums
+        kl, bnd = sr.kgrad(q['Jp'], q['K'], q['alpha'], o[gmk], o[gvk], X, p['Z' + tag], 0, centre=p['Z' + tag].mean(0), dtype=np.longdouble)
+        r, k = sr.worst(np.abs(np.asarray(kl, dtype=np.float64) - krow), 2 * bnd)
+        print('latent %s float64 kgrad reference against longdouble: error / bound %.3g' % (tag, r))
+        assert r <= 1.0
+        # a row range: n0 > 0 and fewer rows than columns
+        k2, _ = sr.kgrad(q['Jp'][:, :200], q['K'][:, :200], q['alpha'], o[gmk][:200], o[gvk][:200], X[:250], p['Z' + tag], 100)
+        k3, _ = sr.kgrad(q['Jp'][:, :150], q['K'][:, :150], q['alpha'], o[gmk][:150], o[gvk][:150], X[100:250], p['Z' + tag], 0)
+        assert np.array_equal(k2, k3)
+
+
+def test_rank_update_reference_and_plan_table():
+    rs = np.random.RandomState(0)
+    A, g = rs.randn(5, 48), rs.randn(48)
+    B, h = rs.randn(5, 16), rs.randn(16)
+    C, bnd = sr.rank_update([(A, g), (B, h)])
+    ref = np.zeros((5, 5))
+    for i in range(5):
+        for j in range(5):
+            ref[i, j] = sum(A[i, n] * g[n] * A[j, n] for n in range(48)) + sum(B[i, n] * h[n] * B[j, n] for n in range(16))
+    assert np.all(np.abs(C - ref) <= bnd) and np.all(np.abs(C - C.T) <= bnd)
+    # the plan table of the issue: nbm -> (So, Sd)
+    table = {1: (64, 32), 2: (64, 32), 3: (64, 32), 4: (64, 32), 5: (32, 16), 6: (16, 8), 7: (16, 8), 8: (16, 8), 9: (16, 8), 16: (16, 8)}
+    for nbm, plan in table.items():
+        assert sr.syr_plan(nbm) == plan, nbm
+    assert sr.slice_windows(64, 64)[:2] == [(0, 16), (16, 32)] and sr.slice_windows(64, 32)[-1] == (992, 1024)
+
+
+def test_plane_sum_order_and_bounds_reference_side():
+    """pw_plane_sum adds what the kernel adds; and the float64 BLAS side of the (B) comparisons stays inside its own half of the bound
+    against longdouble (the issue's CPU check, at a smaller size)."""
+    rs = np.random.RandomState(1)
+    plane = rs.randn(9, 64)
+    assert np.allclose(sr.pw_plane_sum(plane, 6), plane[:6].sum(0), rtol=0, atol=1e-14)
+    assert np.array_equal(sr.pw_plane_sum(plane, 1), plane[0]) and np.array_equal(sr.pw_plane_sum(plane, 0), np.zeros(64))
+    M, Nc = 150, 256
+    for spread in (False, True):
+        W, K = np.tril(rs.randn(M, M)), rs.randn(M, Nc)
+        if spread:
+            W = W * 10.0 ** rs.uniform(-8, 8, W.shape)
+            K = K * 10.0 ** rs.uniform(-8, 8, K.shape)
+        v = rs.randn(M)
+        a1 = sr.forward_a1(W, v, K)
+        Wl, Kl = W.astype(np.longdouble), K.astype(np.longdouble)
+        A1l = Wl @ Kl
+        for name, truth in (('A1', A1l), ('s_vA1', v.astype(np.longdouble) @ A1l), ('s_A1sq', np.sum(A1l * A1l, 0))):
+            val, bnd = a1[name]
+            r, _ = sr.worst(np.abs(np.asarray(val - truth, dtype=np.float64)), bnd / 2)
+            print('spread=%d %s: float64 reference error / its half of the bound = %.3g' % (spread, name, r))
+            assert r <= 1.0

@@ -36,6 +36,20 @@ struct HostLatent {
 // Parameters of both latents to the device (zero-padded to Mp): ONE staged image [Z | ell | u | s | Zs] x 2 and one copy -- the eight
 // separate copies of the first version were eight launches (~7 us apart) in front of a launch-bound M x M stage.  lt.Z / ell / u / s
 // are views into the context's parameter arena.
+// Centre of k_kgrad's moment sums (the mean inducing input) and the choice of its form, from the host copies of Z and ell
+// (latents_upload; zigp_test_kgrad's defaults)
+void kgrad_centre(Latent& lt, const double* Z, const double* ell, int M, int D) {
+  double spread = 0.0;
+  for (int d = 0; d < MAXD; ++d) {
+    double sum = 0.0;
+    if (d < D) for (int m = 0; m < M; ++m) sum += Z[(size_t)m * D + d];
+    lt.zc[d] = M > 0 ? sum / M : 0.0;
+    if (d < D) for (int m = 0; m < M; ++m) spread = std::max(spread, std::fabs(Z[(size_t)m * D + d] - lt.zc[d]) / ell[d]);
+  }
+  // inducing inputs further than KG_EXACT_SPREAD lengthscales from their mean (or not finite): per-row differences instead of the shift
+  lt.kg_exact = !(spread <= KG_EXACT_SPREAD);
+}
+
 int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D) {
   size_t off[2][6], total = 0;
   for (int h = 0; h < 2; ++h) {
@@ -61,15 +75,7 @@ int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D) {
     memcpy(img + off[h][2], q.u, sizeof(double) * q.M);
     memcpy(img + off[h][3], q.s, sizeof(double) * q.M);
     const KufHyp kh = make_kuf_hyp(q.ell, q.var, D);
-    double spread = 0.0;
-    for (int d = 0; d < MAXD; ++d) {      // centre of k_kgrad's moment sums: the mean inducing input
-      double sum = 0.0;
-      if (d < D) for (int m = 0; m < q.M; ++m) sum += q.Z[(size_t)m * D + d];
-      c->lat[h].zc[d] = q.M > 0 ? sum / q.M : 0.0;
-      if (d < D) for (int m = 0; m < q.M; ++m) spread = std::max(spread, std::fabs(q.Z[(size_t)m * D + d] - c->lat[h].zc[d]) / q.ell[d]);
-    }
-    // inducing inputs further than KG_EXACT_SPREAD lengthscales from their mean (or not finite): per-row differences instead of the shift
-    c->lat[h].kg_exact = !(spread <= KG_EXACT_SPREAD);
+    kgrad_centre(c->lat[h], q.Z, q.ell, q.M, D);
     for (int m = 0; m < q.M; ++m)
       for (int d = 0; d < D; ++d) img[off[h][4] + (size_t)m * D + d] = q.Z[(size_t)m * D + d] * kh.scale[d];
   }
@@ -307,6 +313,14 @@ int latent_chunk_syrk(zigp_ctx* c, const ChunkPlan& pl, int h) {
   return run_gemm<LAY_KCONTIG, LAY_KCONTIG, true, TRI_C_LOWER>(c, pl.lat[h].syr, g, EpiAccum());
 }
 
+// C1 = sym(sum_s planes) -> T1: the split-K planes of the chunks' rank-N updates, added in slice order
+void latent_sym_from_planes(zigp_ctx* c, Latent& lt) {
+  const int Mp = lt.Mp;
+  const SyrPlan sp = syr_plan(Mp / BM);
+  const int nt = Mp / 32;
+  hipLaunchKernelGGL(k_sym_from_planes, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, lt.dLpart.p, sp.So, sp.Sd, (int64_t)Mp, lt.T1.p);
+}
+
 // MxM backward: G = dELBO/dKuu (symmetric) -> krow accumulators.
 int latent_mxm_backward(zigp_ctx* c, Latent& lt, int D, double jitter, bool with_data, bool with_kl) {
   const int Mp = lt.Mp, nb = Mp / BM, kb = BM / BK;
@@ -324,12 +338,7 @@ int latent_mxm_backward(zigp_ctx* c, Latent& lt, int D, double jitter, bool with
       hipLaunchKernelGGL(k_gemv_rows, dim3(Mp), dim3(256), 0, c->stream, lt.W.p, kgm, (int64_t)Mp, lt.a1gm.p);
       hipLaunchKernelGGL(k_gemv_cols, dim3(Mp / 64), dim3(64, COL_LANES), 0, c->stream, lt.W.p, lt.a1gm.p, (int64_t)Mp, lt.du.p);
     }
-    // C1 = sym(sum_s planes) -> T1
-    {
-      const SyrPlan sp = syr_plan(nb);
-      const int nt = Mp / 32;
-      hipLaunchKernelGGL(k_sym_from_planes, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, lt.dLpart.p, sp.So, sp.Sd, (int64_t)Mp, lt.T1.p);
-    }
+    latent_sym_from_planes(c, lt);
     // dsq = diag(A2 G A2^T) = diag(W^T C1 W): Y = C1 W -> T3 ; dsq[m] = sum_k W[k][m] Y[k][m]
     ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "y", nb, [&](int bi, int bj, int& k0, int& k1) { k0 = bj * kb; k1 = nb * kb; },
                                                      lt.T1.p, lt.W.p, lt.T3.p, Mp, SK_STORE, 1.0, false)));
@@ -503,15 +512,17 @@ PwArgs dense_pointwise_args(zigp_ctx* c, const DenseCall& k, int64_t n0, int64_t
   a.acc = c->pw_part.p; a.out9 = k.d_out9 ? k.d_out9 - k.row_begin : nullptr; a.ld9 = k.row_end - k.row_begin;
   return a;
 }
-int dense_pointwise(zigp_ctx* c, const DenseCall& k, int64_t n0, int64_t Nc) {
+int dense_pointwise_launch(zigp_ctx* c, bool predict, bool need_grad, const PwArgs& a) {
   ProfScope ps(c, PC_POINT);
-  const PwArgs a = dense_pointwise_args(c, k, n0, Nc);
-  const int nblk = (int)(Nc / PW_PTS);
-  if (k.predict) hipLaunchKernelGGL((k_pointwise<true, false>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
-  else if (k.need_grad) hipLaunchKernelGGL((k_pointwise<false, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);   // variance from sum K J'
+  const int nblk = (int)(a.Nc / PW_PTS);
+  if (predict) hipLaunchKernelGGL((k_pointwise<true, false>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
+  else if (need_grad) hipLaunchKernelGGL((k_pointwise<false, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);   // variance from sum K J'
   else hipLaunchKernelGGL((k_pointwise<false, false>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
   ZIGP_HIP(c, hipGetLastError());
   return 0;
+}
+int dense_pointwise(zigp_ctx* c, const DenseCall& k, int64_t n0, int64_t Nc) {
+  return dense_pointwise_launch(c, k.predict, k.need_grad, dense_pointwise_args(c, k, n0, Nc));
 }
 
 // ---- chunk loop.  The MFMA-bound GEMMs stay on the main stream; with zigp_set_overlap(1) the HBM-bound kernels of a chunk -- the two
@@ -1099,6 +1110,255 @@ int zigp_test_potrf_trtri(zigp_ctx* c, int64_t n, const double* A, double* L, do
     for (int64_t i = 0; i < n; ++i) memcpy(&W[i * n], &ho[i * Mp], sizeof(double) * n);
   }
   return 0;
+}
+
+// ---- stage diagnostics (include/zigp_diag.h): one chunk's stage on caller-supplied operands, through the chunk loop's own functions ----
+namespace {
+// host (rows x cols, row-major) -> device [rows_p][cols] with zero rows behind it
+int stage_upload_rows(zigp_ctx* c, DevBuf& buf, const double* src, int64_t rows, int64_t rows_p, int64_t cols) {
+  ZIGP_ENSURE(c, buf, (size_t)rows_p * cols);
+  ZIGP_HIP(c, hipMemsetAsync(buf.p, 0, sizeof(double) * rows_p * cols, c->stream));
+  if (src) ZIGP_HIP(c, hipMemcpyAsync(buf.p, src, sizeof(double) * rows * cols, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+// host (M,M) -> device (Mp,Mp), `pad` on the diagonal behind it
+int stage_upload_square(zigp_ctx* c, DevBuf& buf, const double* src, int M, int Mp, double pad) {
+  std::vector<double> h((size_t)Mp * Mp, 0.0);
+  for (int i = 0; i < Mp; ++i) {
+    if (i < M) memcpy(&h[(size_t)i * Mp], src + (size_t)i * M, sizeof(double) * M);
+    else h[(size_t)i * Mp + i] = pad;
+  }
+  ZIGP_ENSURE(c, buf, h.size());
+  ZIGP_HIP(c, hipMemcpyAsync(buf.p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));     // h goes out of scope
+  return 0;
+}
+int stage_download_rows(zigp_ctx* c, const double* dev, double* dst, int64_t rows, int64_t cols) {
+  if (dst) ZIGP_HIP(c, hipMemcpyAsync(dst, dev, sizeof(double) * rows * cols, hipMemcpyDeviceToHost, c->stream));
+  return 0;
+}
+bool stage_chunk_ok(int64_t Nc) { return Nc >= 1024 && Nc % 1024 == 0 && Nc <= (1 << 20); }
+}  // namespace
+
+int zigp_test_chunk_forward(zigp_ctx* c, int64_t Nc, int32_t need_grad, int32_t only, const zigp_stage_latent* lat, int64_t* facts) {
+  if (!c) return ZIGP_EARG;
+  if (!lat || !facts || !stage_chunk_ok(Nc) || only < -1 || only > 1) return fail_arg(c, "zigp_test_chunk_forward: bad arguments");
+  for (int h = 0; h < 2; ++h) {
+    const zigp_stage_latent& q = lat[h];
+    if (q.M <= 0) return fail_arg(c, "zigp_test_chunk_forward: M must be positive");
+    if (only >= 0 && only != h) continue;
+    if (!q.W || !q.v || !q.s2 || !q.K || !q.A1 || !q.part || (need_grad && (!q.Rt || !q.Jp)))
+      return fail_arg(c, "zigp_test_chunk_forward: NULL operand of a latent that runs");
+  }
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  const bool grad = need_grad != 0;
+  for (int h = 0; h < 2; ++h) {
+    Latent& lt = c->lat[h];
+    const zigp_stage_latent& q = lat[h];
+    lt.M = q.M; lt.Mp = (int)round_up(q.M, BM);
+    const int Mp = lt.Mp;
+    const size_t np = Mp / 32;
+    ZIGP_ENSURE(c, lt.Wt, (size_t)Mp * Mp); ZIGP_ENSURE(c, lt.vec, 4 * (size_t)Mp + 8);
+    ZIGP_ENSURE(c, lt.A1, (size_t)Mp * Nc); ZIGP_ENSURE(c, lt.part, 3 * np * Nc);
+    if (grad) ZIGP_ENSURE(c, lt.Jp, (size_t)Mp * Nc);
+    if (only >= 0 && only != h) {      // planned, not launched: only the buffers chunk_forward takes addresses of
+      ZIGP_ENSURE(c, lt.W, (size_t)Mp * Mp); ZIGP_ENSURE(c, lt.s2, Mp); ZIGP_ENSURE(c, lt.K, (size_t)Mp * Nc); ZIGP_ENSURE(c, lt.Rt, (size_t)Mp * Mp);
+      continue;
+    }
+    ZIGP_TRY(stage_upload_square(c, lt.W, q.W, q.M, Mp, 1.0));
+    hipLaunchKernelGGL(k_transpose, dim3(Mp / 32, Mp / 32), dim3(32, 8), 0, c->stream, lt.W.p, (int64_t)Mp, lt.Wt.p);
+    ZIGP_HIP(c, hipGetLastError());
+    if (grad) ZIGP_TRY(stage_upload_square(c, lt.Rt, q.Rt, q.M, Mp, -1.0));
+    ZIGP_TRY(stage_upload_rows(c, lt.s2, q.s2, q.M, Mp, 1));
+    ZIGP_HIP(c, hipMemsetAsync(lt.vec.p, 0, sizeof(double) * (4 * (size_t)Mp + 8), c->stream));
+    ZIGP_HIP(c, hipMemcpyAsync(lt.vec.p, q.v, sizeof(double) * q.M, hipMemcpyHostToDevice, c->stream));
+    ZIGP_TRY(stage_upload_rows(c, lt.K, q.K, q.M, Mp, Nc));
+    ZIGP_HIP(c, hipMemsetAsync(lt.A1.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * Mp * Nc, c->stream));
+    if (grad) ZIGP_HIP(c, hipMemsetAsync(lt.Jp.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * Mp * Nc, c->stream));
+    ZIGP_HIP(c, hipMemsetAsync(lt.part.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * 3 * np * Nc, c->stream));
+  }
+  const int M[2] = {lat[0].M, lat[1].M};
+  ChunkPlan pl = chunk_plan(M, Nc, grad, c->trmm_tail);
+  ZIGP_TRY(upload_plan(c, pl));
+  if (only >= 0) { ChunkPlan::Lat& o = pl.lat[1 - only]; o.a1 = TileList(); o.a2j = TileList(); }
+  ZIGP_TRY(chunk_forward(c, pl, grad));
+  for (int h = 0; h < 2; ++h) {
+    if (only >= 0 && only != h) continue;
+    Latent& lt = c->lat[h];
+    ZIGP_TRY(stage_download_rows(c, lt.A1.p, lat[h].A1, lat[h].M, Nc));
+    if (grad) ZIGP_TRY(stage_download_rows(c, lt.Jp.p, lat[h].Jp, lat[h].M, Nc));
+    ZIGP_TRY(stage_download_rows(c, lt.part.p, lat[h].part, 3 * (int64_t)(lt.Mp / 32), Nc));
+  }
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  zigp_params pp;
+  memset(&pp, 0, sizeof(pp));
+  DenseCall k;
+  memset(static_cast<void*>(&k.hl), 0, sizeof(k.hl));
+  k.p = &pp; k.dX = nullptr; k.dY = nullptr; k.Nrows = Nc; k.D = 1; k.jitter = 0; k.scale = 1; k.g_offset = 0; k.row_begin = 0; k.row_end = Nc;
+  k.include_kl = 0; k.predict = false; k.d_out9 = nullptr; k.need_grad = grad; k.has_rows = true;
+  const PwArgs a = dense_pointwise_args(c, k, 0, Nc);     // the row counts the point-wise stage is told
+  facts[0] = pl.paired ? 1 : 0; facts[1] = pl.tail.units[0]; facts[2] = pl.tail.units[1]; facts[3] = c->lat[0].Mp; facts[4] = c->lat[1].Mp;
+  facts[5] = a.np_f; facts[6] = a.np_g; facts[7] = a.np1_f; facts[8] = a.np2_f; facts[9] = a.np1_g; facts[10] = a.np2_g; facts[11] = 0;
+  return ZIGP_OK;
+}
+
+int zigp_test_latents_forward(zigp_ctx* c, const zigp_params* p, double jitter, int32_t need_grad, double* const* out_f, double* const* out_g) {
+  if (!c) return ZIGP_EARG;
+  ZIGP_TRY(validate_params(c, p));
+  if (!out_f || !out_g || !(jitter >= 0)) return fail_arg(c, "zigp_test_latents_forward: bad arguments");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  HostLatent hl[2] = {{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f}, {p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g}};
+  ZIGP_TRY(begin_staged_call(c));
+  ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
+  ZIGP_TRY(latents_upload(c, hl, p->D));
+  ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
+  ZIGP_TRY(latents_forward(c, hl, p->D, jitter, true, need_grad != 0));
+  ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
+  ZIGP_TRY(check_info(c, "Kuu"));
+  double* const* outs[2] = {out_f, out_g};
+  for (int h = 0; h < 2; ++h) {
+    Latent& lt = c->lat[h];
+    const int M = lt.M, Mp = lt.Mp;
+    std::vector<double> hm((size_t)Mp * Mp);
+    const double* mats[2] = {lt.W.p, need_grad ? lt.Rt.p : nullptr};
+    double* dst[2] = {outs[h][0], outs[h][3]};
+    for (int q = 0; q < 2; ++q) {
+      if (!dst[q] || !mats[q]) continue;
+      ZIGP_HIP(c, hipMemcpyAsync(hm.data(), mats[q], sizeof(double) * hm.size(), hipMemcpyDeviceToHost, c->stream));
+      ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+      for (int i = 0; i < M; ++i) memcpy(dst[q] + (size_t)i * M, &hm[(size_t)i * Mp], sizeof(double) * M);
+    }
+    if (outs[h][1]) ZIGP_HIP(c, hipMemcpyAsync(outs[h][1], lt.vec.p, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
+    if (outs[h][2]) ZIGP_HIP(c, hipMemcpyAsync(outs[h][2], lt.vec.p + Mp, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
+    ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  prof_collect(c);
+  return ZIGP_OK;
+}
+
+int zigp_test_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s) {
+  if (!c) return ZIGP_EARG;
+  if (!s || s->mode < 0 || s->mode > 2 || s->repeat < 1 || !stage_chunk_ok(s->Nc) || !s->part_f || !s->part_g || !s->acc)
+    return fail_arg(c, "zigp_test_pointwise: bad arguments");
+  if (s->np_f < 1 || s->np_g < 1 || s->np1_f < 0 || s->np2_f < 0 || s->np1_g < 0 || s->np2_g < 0 || s->np1_f > s->np_f || s->np2_f > s->np_f ||
+      s->np1_g > s->np_g || s->np2_g > s->np_g)
+    return fail_arg(c, "zigp_test_pointwise: need 0 <= np1, np2 <= np");
+  if (s->D < 1 || s->D > MAXD || !s->X || s->Nrows <= 0 || s->n0 < 0 || s->row_end < s->n0 || s->row_end > s->Nrows || s->row_end > s->n0 + s->Nc)
+    return fail_arg(c, "zigp_test_pointwise: need X (Nrows,D), 1 <= D <= 8 and n0 <= row_end <= min(Nrows, n0 + Nc)");
+  if (s->mode == 1 && (!s->gm_f || !s->gv_f || !s->gm_g || !s->gv_g)) return fail_arg(c, "zigp_test_pointwise: gradient mode needs gm / gv outputs");
+  if (s->mode == 2 ? !s->out9 : !s->Y) return fail_arg(c, "zigp_test_pointwise: predict needs out9, the ELBO modes need Y");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  const int64_t Nc = s->Nc;
+  const size_t nacc = (size_t)(Nc / PW_PTS) * PW_ACC;
+  DevBuf dx, dy, pf, pg;
+  ZIGP_TRY(stage_upload_rows(c, dx, s->X, s->Nrows, s->Nrows, s->D));
+  if (s->Y) ZIGP_TRY(stage_upload_rows(c, dy, s->Y, s->Nrows, s->Nrows, 1));
+  ZIGP_TRY(stage_upload_rows(c, pf, s->part_f, 3 * (int64_t)s->np_f, 3 * (int64_t)s->np_f, Nc));
+  ZIGP_TRY(stage_upload_rows(c, pg, s->part_g, 3 * (int64_t)s->np_g, 3 * (int64_t)s->np_g, Nc));
+  ZIGP_TRY(stage_upload_rows(c, c->pw_part, s->acc, (int64_t)nacc, (int64_t)nacc, 1));
+  for (int h = 0; h < 2; ++h) { ZIGP_ENSURE(c, c->lat[h].gm, Nc); ZIGP_ENSURE(c, c->lat[h].gv, Nc); }
+  if (s->mode == 2) { ZIGP_ENSURE(c, c->out9, (size_t)9 * s->row_end + 1); ZIGP_HIP(c, hipMemsetAsync(c->out9.p, 0, sizeof(double) * (9 * s->row_end + 1), c->stream)); }
+  zigp_params pp;
+  memset(&pp, 0, sizeof(pp));
+  pp.var_f = s->var_f; pp.var_g = s->var_g; pp.noise = s->noise;
+  DenseCall k;
+  memset(static_cast<void*>(&k.hl), 0, sizeof(k.hl));
+  k.p = &pp; k.dX = dx.p; k.dY = s->Y ? dy.p : nullptr; k.Nrows = s->Nrows; k.D = s->D; k.jitter = 0; k.scale = s->scale; k.g_offset = s->g_offset;
+  k.row_begin = 0; k.row_end = s->row_end; k.include_kl = 0; k.predict = s->mode == 2; k.d_out9 = s->mode == 2 ? c->out9.p : nullptr;
+  k.need_grad = s->mode == 1; k.has_rows = true;
+  // the context's mean function for the duration of the call
+  const bool mean_on = c->mean_on; const double mean_b = c->mean_b; double mean_a[MAXD];
+  for (int d = 0; d < MAXD; ++d) { mean_a[d] = c->mean_a[d]; c->mean_a[d] = s->mean_a[d]; }
+  c->mean_on = s->mean_on != 0; c->mean_b = s->mean_b;
+  PwArgs a = dense_pointwise_args(c, k, s->n0, Nc);
+  c->mean_on = mean_on; c->mean_b = mean_b;
+  for (int d = 0; d < MAXD; ++d) c->mean_a[d] = mean_a[d];
+  a.part_f = pf.p; a.part_g = pg.p; a.np_f = s->np_f; a.np_g = s->np_g;
+  a.np1_f = s->np1_f; a.np2_f = s->np2_f; a.np1_g = s->np1_g; a.np2_g = s->np2_g;
+  for (int r = 0; r < s->repeat; ++r) ZIGP_TRY(dense_pointwise_launch(c, k.predict, k.need_grad, a));
+  if (s->mode == 1) {
+    ZIGP_TRY(stage_download_rows(c, c->lat[0].gm.p, s->gm_f, 1, Nc)); ZIGP_TRY(stage_download_rows(c, c->lat[0].gv.p, s->gv_f, 1, Nc));
+    ZIGP_TRY(stage_download_rows(c, c->lat[1].gm.p, s->gm_g, 1, Nc)); ZIGP_TRY(stage_download_rows(c, c->lat[1].gv.p, s->gv_g, 1, Nc));
+  }
+  if (s->mode == 2) ZIGP_TRY(stage_download_rows(c, c->out9.p, s->out9, 9, s->row_end));
+  else ZIGP_TRY(stage_download_rows(c, c->pw_part.p, s->acc, 1, (int64_t)nacc));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  return ZIGP_OK;
+}
+
+int zigp_test_kgrad(zigp_ctx* c, int32_t M, int32_t D, int64_t Nc, int64_t Nrows, int64_t n0, const double* Jp, const double* K, const double* alpha,
+                    const double* gm, const double* gv, const double* X, const double* Z, const double* ell, const double* centre, int32_t exact,
+                    double* krow) {
+  if (!c) return ZIGP_EARG;
+  if (M <= 0 || D < 1 || D > MAXD || !stage_chunk_ok(Nc) || Nrows <= 0 || n0 < 0 || n0 >= Nrows || !Jp || !K || !alpha || !gm || !gv || !X || !Z || !krow ||
+      exact < -1 || exact > 1 || (exact < 0 && !ell))
+    return fail_arg(c, "zigp_test_kgrad: bad arguments");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  Latent& lt = c->lat[0];
+  lt.M = M; lt.Mp = (int)round_up(M, BM);
+  const int Mp = lt.Mp, Wd = 2 + 2 * D;
+  if (exact < 0 || !centre) {
+    const double one[MAXD] = {1, 1, 1, 1, 1, 1, 1, 1};
+    kgrad_centre(lt, Z, ell ? ell : one, M, D);
+  }
+  if (exact >= 0) lt.kg_exact = exact != 0;
+  if (centre) for (int d = 0; d < MAXD; ++d) lt.zc[d] = d < D ? centre[d] : 0.0;
+  DevBuf dx;
+  ZIGP_TRY(stage_upload_rows(c, dx, X, Nrows, Nrows, D));
+  ZIGP_TRY(stage_upload_rows(c, lt.Z, Z, M, Mp, D));
+  ZIGP_TRY(stage_upload_rows(c, lt.K, K, M, Mp, Nc));
+  ZIGP_TRY(stage_upload_rows(c, lt.Jp, Jp, M, Mp, Nc));
+  ZIGP_TRY(stage_upload_rows(c, lt.gm, gm, 1, 1, Nc));
+  ZIGP_TRY(stage_upload_rows(c, lt.gv, gv, 1, 1, Nc));
+  ZIGP_ENSURE(c, lt.vec, 4 * (size_t)Mp + 8);
+  ZIGP_HIP(c, hipMemsetAsync(lt.vec.p, 0, sizeof(double) * (4 * (size_t)Mp + 8), c->stream));
+  ZIGP_HIP(c, hipMemcpyAsync(lt.vec.p + Mp, alpha, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+  ZIGP_ENSURE(c, lt.krow, (size_t)KG_SPLIT * Mp * Wd);
+  ZIGP_HIP(c, hipMemsetAsync(lt.krow.p, 0, sizeof(double) * KG_SPLIT * Mp * Wd, c->stream));
+  for (int sp = 0; sp < KG_SPLIT; ++sp)
+    ZIGP_HIP(c, hipMemcpyAsync(lt.krow.p + (size_t)sp * Mp * Wd, krow + (size_t)sp * M * Wd, sizeof(double) * M * Wd, hipMemcpyHostToDevice, c->stream));
+  ZIGP_TRY(latent_chunk_kgrad(c, lt, dx.p, Nrows, n0, Nc, D, ell));
+  for (int sp = 0; sp < KG_SPLIT; ++sp)
+    ZIGP_HIP(c, hipMemcpyAsync(krow + (size_t)sp * M * Wd, lt.krow.p + (size_t)sp * Mp * Wd, sizeof(double) * M * Wd, hipMemcpyDeviceToHost, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  return ZIGP_OK;
+}
+
+int zigp_test_rank_update(zigp_ctx* c, int32_t M, int32_t nchunks, const int64_t* Nc, const double* const* A1, const double* const* gv, double* C1,
+                          int64_t* plan) {
+  if (!c) return ZIGP_EARG;
+  if (M <= 0 || nchunks < 1 || !Nc || !A1 || !gv || !C1 || !plan) return fail_arg(c, "zigp_test_rank_update: bad arguments");
+  int64_t Nmax = 0;
+  for (int i = 0; i < nchunks; ++i) {
+    if (!stage_chunk_ok(Nc[i]) || !A1[i] || !gv[i]) return fail_arg(c, "zigp_test_rank_update: every chunk needs A1, gv and a multiple of 1024 rows");
+    Nmax = std::max(Nmax, Nc[i]);
+  }
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  Latent& lt = c->lat[0];
+  lt.M = M; lt.Mp = (int)round_up(M, BM);
+  const int Mp = lt.Mp;
+  const size_t mm = (size_t)Mp * Mp;
+  const SyrPlan sp = syr_plan(Mp / BM);
+  ZIGP_ENSURE(c, lt.dLpart, (size_t)sp.planes() * mm); ZIGP_ENSURE(c, lt.T1, mm);
+  ZIGP_ENSURE(c, lt.A1, (size_t)Mp * Nmax); ZIGP_ENSURE(c, lt.gv, Nmax);
+  ZIGP_HIP(c, hipMemsetAsync(lt.dLpart.p, 0, sizeof(double) * sp.planes() * mm, c->stream));
+  ZIGP_HIP(c, hipMemsetAsync(lt.T1.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * mm, c->stream));
+  const int Ms[2] = {M, M};
+  for (int i = 0; i < nchunks; ++i) {
+    ChunkPlan pl = chunk_plan(Ms, Nc[i], true, c->trmm_tail);
+    ZIGP_TRY(upload_plan(c, pl));
+    ZIGP_TRY(stage_upload_rows(c, lt.A1, A1[i], M, Mp, Nc[i]));
+    ZIGP_TRY(stage_upload_rows(c, lt.gv, gv[i], 1, 1, Nc[i]));
+    ZIGP_TRY(latent_chunk_syrk(c, pl, 0));
+  }
+  latent_sym_from_planes(c, lt);
+  ZIGP_HIP(c, hipGetLastError());
+  std::vector<double> hc(mm);
+  ZIGP_HIP(c, hipMemcpyAsync(hc.data(), lt.T1.p, sizeof(double) * mm, hipMemcpyDeviceToHost, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  for (int i = 0; i < M; ++i) memcpy(C1 + (size_t)i * M, &hc[(size_t)i * Mp], sizeof(double) * M);
+  plan[0] = sp.So; plan[1] = sp.Sd;
+  return ZIGP_OK;
 }
 
 }  // extern "C"

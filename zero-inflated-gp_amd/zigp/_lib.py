@@ -66,6 +66,25 @@ class zigp_kron_fit_opts(C.Structure):
                 ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double)]
 
 
+class zigp_stage_latent(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('M', C.c_int32), ('reserved', C.c_int32), ('W', dp), ('v', dp), ('s2', dp), ('K', dp), ('Rt', dp),
+                ('A1', dp), ('Jp', dp), ('part', dp)]
+
+
+class zigp_stage_pointwise(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('mode', C.c_int32), ('repeat', C.c_int32),
+                ('np_f', C.c_int32), ('np1_f', C.c_int32), ('np2_f', C.c_int32), ('np_g', C.c_int32), ('np1_g', C.c_int32), ('np2_g', C.c_int32),
+                ('D', C.c_int32), ('mean_on', C.c_int32),
+                ('part_f', dp), ('part_g', dp), ('Y', dp), ('X', dp),
+                ('Nrows', C.c_int64), ('n0', C.c_int64), ('row_end', C.c_int64), ('Nc', C.c_int64),
+                ('var_f', C.c_double), ('var_g', C.c_double), ('noise', C.c_double), ('g_offset', C.c_double), ('scale', C.c_double),
+                ('mean_a', C.c_double * 8), ('mean_b', C.c_double),
+                ('gm_f', dp), ('gv_f', dp), ('gm_g', dp), ('gv_g', dp), ('acc', dp), ('out9', dp)]
+
+
+STAGE_SENTINEL = float(np.frombuffer(bytes([0x7f]) * 8, dtype=np.float64)[0])   # ZIGP_STAGE_SENTINEL_BYTE in every byte: 1.38e306
+KG_SPLIT, PW_PTS, PW_ACC = 4, 64, 13   # csrc/zigp_kernels.h
+
 # name -> (restype, argtypes); mirrors include/zigp.h and include/zigp_diag.h exactly (tests check every declared symbol resolves)
 SIGNATURES = {
     'zigp_create': (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
@@ -118,6 +137,11 @@ SIGNATURES = {
     'zigp_test_gemm': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp]),
     'zigp_test_kuf': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, dp, dp, dp, C.c_double, dp]),
     'zigp_test_potrf_trtri': (C.c_int, [C.c_void_p, C.c_int64, dp, dp, dp, C.c_int32]),
+    'zigp_test_chunk_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(zigp_stage_latent), C.POINTER(C.c_int64)]),
+    'zigp_test_latents_forward': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_double, C.c_int32, C.POINTER(dp), C.POINTER(dp)]),
+    'zigp_test_pointwise': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_pointwise)]),
+    'zigp_test_kgrad': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int32, dp]),
+    'zigp_test_rank_update': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(dp), C.POINTER(dp), dp, C.POINTER(C.c_int64)]),
 }
 
 _lib = None

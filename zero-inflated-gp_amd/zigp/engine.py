@@ -644,6 +644,110 @@ class DenseEngine:
         return L, W
 
 
+    # ---- stage diagnostics (include/zigp_diag.h): one chunk's stage through the chunk loop's own functions ----
+    def test_chunk_forward(self, lat_f, lat_g, Nc, need_grad, only=None):
+        """Forward products of one chunk.  lat_*: dict(M=..., W=(M,M) lower, v=(M), s2=(M), K=(M,Nc), Rt=(M,M) in gradient mode); the latent
+        that does not run (only = 0 / 1) needs M alone.  Returns ([out_f, out_g], facts): out = dict(A1, Jp or None, part [3][Mp/32][Nc]
+        with rows nothing wrote at _lib.STAGE_SENTINEL) or None, facts = dict(paired, tail_f, tail_g, Mp, np, np1, np2)."""
+        Nc = int(Nc)
+        arr = (_lib.zigp_stage_latent * 2)()
+        keep, outs = [], []
+        for h, q in enumerate((lat_f, lat_g)):
+            M = int(q['M'])
+            arr[h].M = M
+            if only is not None and only != h:
+                outs.append(None)
+                continue
+            Mp = (M + 127) // 128 * 128
+            ins = dict(W=as_f64(q['W'], (M, M)), v=as_f64(q['v'], (M,)), s2=as_f64(q['s2'], (M,)), K=as_f64(q['K'], (M, Nc)))
+            if need_grad:
+                ins['Rt'] = as_f64(q['Rt'], (M, M))
+            out = dict(A1=np.zeros((M, Nc)), Jp=np.zeros((M, Nc)) if need_grad else None, part=np.zeros((3, Mp // 32, Nc)))
+            for k, a in list(ins.items()) + [(k, a) for k, a in out.items() if a is not None]:
+                setattr(arr[h], k, ptr(a))
+            keep.append(ins)
+            outs.append(out)
+        facts = (C.c_int64 * 12)()
+        _check(self.lib, self.ctx, self.lib.zigp_test_chunk_forward(self.ctx, Nc, int(bool(need_grad)), -1 if only is None else int(only), arr, facts))
+        f = list(facts)
+        return outs, dict(paired=f[0], tail_f=f[1], tail_g=f[2], Mp=(f[3], f[4]), np=(f[5], f[6]), np1=(f[7], f[9]), np2=(f[8], f[10]))
+
+    def test_latents_forward(self, p, jitter=1e-6, need_grad=True):
+        """What the M x M forward leaves for the chunk loop: [dict(W, v, alpha, Rt or None) for f, g]."""
+        pk = _Packed(p)
+        outs, arrs = [], []
+        for M in (pk.Mf, pk.Mg):
+            o = dict(W=np.zeros((M, M)), v=np.zeros(M), alpha=np.zeros(M), Rt=np.zeros((M, M)) if need_grad else None)
+            outs.append(o)
+            arrs.append((_lib.dp * 4)(ptr(o['W']), ptr(o['v']), ptr(o['alpha']), ptr(o['Rt']) if need_grad else None))
+        _check(self.lib, self.ctx, self.lib.zigp_test_latents_forward(self.ctx, C.byref(pk.struct), float(jitter), int(bool(need_grad)), arrs[0], arrs[1]))
+        return outs
+
+    def test_pointwise(self, mode, part_f, part_g, np1, np2, X, Y, n0, row_end, var_f, var_g, noise, g_offset=0.0, scale=1.0,
+                       mean=None, repeat=1, acc=None):
+        """The point-wise stage of one chunk.  mode 'value' / 'grad' / 'predict'; part_* [3][np][Nc]; np1 / np2 = (f, g) rows to add of planes
+        0, 1 / of plane 2; mean = None or (a (D), b).  Returns dict(gm_f, gv_f, gm_g, gv_g (grad), acc [Nc/64][PW_ACC], out9 (predict))."""
+        part_f, part_g = as_f64(part_f), as_f64(part_g)
+        X = as_f64(X)
+        if X.ndim == 1: X = X[:, None]
+        Nc = part_f.shape[2]
+        s = _lib.zigp_stage_pointwise()
+        s.mode = {'value': 0, 'grad': 1, 'predict': 2}[mode]
+        s.repeat = int(repeat)
+        s.np_f, s.np_g = part_f.shape[1], part_g.shape[1]
+        s.np1_f, s.np1_g = int(np1[0]), int(np1[1])
+        s.np2_f, s.np2_g = int(np2[0]), int(np2[1])
+        s.D, s.mean_on = X.shape[1], 0 if mean is None else 1
+        if mean is not None:
+            a = np.zeros(8)
+            a[:X.shape[1]] = np.asarray(mean[0], dtype=np.float64).reshape(-1)
+            s.mean_a = (C.c_double * 8)(*a)
+            s.mean_b = float(mean[1])
+        Yc = None if Y is None else as_f64(Y).reshape(-1)
+        s.part_f, s.part_g, s.X, s.Y = ptr(part_f), ptr(part_g), ptr(X), None if Yc is None else ptr(Yc)
+        s.Nrows, s.n0, s.row_end, s.Nc = X.shape[0], int(n0), int(row_end), Nc
+        s.var_f, s.var_g, s.noise, s.g_offset, s.scale = float(var_f), float(var_g), float(noise), float(g_offset), float(scale)
+        out = dict(acc=np.zeros((Nc // _lib.PW_PTS, _lib.PW_ACC)) if acc is None else np.array(as_f64(acc), copy=True))
+        s.acc = ptr(out['acc'])
+        if mode == 'grad':
+            for k in ('gm_f', 'gv_f', 'gm_g', 'gv_g'):
+                out[k] = np.zeros(Nc)
+                setattr(s, k, ptr(out[k]))
+        if mode == 'predict':
+            out['out9'] = np.zeros((9, int(row_end)))
+            s.out9 = ptr(out['out9'])
+        _check(self.lib, self.ctx, self.lib.zigp_test_pointwise(self.ctx, C.byref(s)))
+        return out
+
+    def test_kgrad(self, Jp, K, alpha, gm, gv, X, Z, n0=0, ell=None, centre=None, exact=None, krow=None):
+        """Kuf cotangent reductions of one chunk: the KG_SPLIT slabs [4][M][2+2D] (added onto `krow` if given)."""
+        X, Z = as_f64(X), as_f64(Z)
+        if X.ndim == 1: X = X[:, None]
+        if Z.ndim == 1: Z = Z[:, None]
+        M, D = Z.shape
+        K, Jp = as_f64(K), as_f64(Jp)
+        Nc = K.shape[1]
+        alpha, gm, gv = as_f64(alpha, (M,)), as_f64(gm, (Nc,)), as_f64(gv, (Nc,))
+        ell = None if ell is None else as_f64(np.broadcast_to(np.asarray(ell, dtype=np.float64), (D,)))
+        centre = None if centre is None else as_f64(centre, (D,))
+        out = np.zeros((_lib.KG_SPLIT, M, 2 + 2 * D)) if krow is None else np.array(as_f64(krow, (_lib.KG_SPLIT, M, 2 + 2 * D)), copy=True)
+        _check(self.lib, self.ctx, self.lib.zigp_test_kgrad(
+            self.ctx, M, D, Nc, X.shape[0], int(n0), ptr(as_f64(Jp, (M, Nc))), ptr(as_f64(K, (M, Nc))), ptr(alpha), ptr(gm), ptr(gv), ptr(X), ptr(Z),
+            None if ell is None else ptr(ell), None if centre is None else ptr(centre), -1 if exact is None else int(bool(exact)), ptr(out)))
+        return out
+
+    def test_rank_update(self, chunks):
+        """C1 = sum_i A1_i diag(gv_i) A1_i^T over chunks [(A1 (M,Nc_i), gv (Nc_i)), ...].  Returns (C1 (M,M), (So, Sd))."""
+        A = [as_f64(a) for a, _ in chunks]
+        g = [as_f64(v, (a.shape[1],)) for a, (_, v) in zip(A, chunks)]
+        M, n = A[0].shape[0], len(A)
+        Nc = (C.c_int64 * n)(*[a.shape[1] for a in A])
+        pa, pg = (_lib.dp * n)(*[ptr(a) for a in A]), (_lib.dp * n)(*[ptr(v) for v in g])
+        out, plan = np.zeros((M, M)), (C.c_int64 * 2)()
+        _check(self.lib, self.ctx, self.lib.zigp_test_rank_update(self.ctx, M, n, Nc, pa, pg, ptr(out), plan))
+        return out, (plan[0], plan[1])
+
+
 def reference_engine(device=0):
     """The engine of the reference look-alikes (onoffgpf.OnOffSVGP, onofftf.onoff / predict_onoff, the likelihood heads): results identical
     to the reference on the same inputs includes WHERE it fails -- tf.cholesky raises on a non-positive pivot only (onofftf/main.py:200,
