@@ -104,6 +104,50 @@ int zigp_elbo(zigp_ctx* ctx, const zigp_params* p, double jitter, double scale, 
               int64_t row_begin, int64_t row_end, int32_t include_kl,
               double* elbo_data, double* kl, zigp_grads* grads);
 
+/* ---- the dense fit loop on the device ---------------------------------------------------------------------------------------------
+ * Replaces the body of the dense model's minibatch training loop -- one sample of MinibatchData (onoffgpf/OnOffSVGP.py:42-47), one
+ * build_likelihood + gradient (:107-122, scaled by num_data / minibatch_size, :119-120) and one Adam update (the alternative to L-BFGS-B at
+ * zero-inflated-gpflow.ipynb:155) -- for n_steps consecutive iterations: gradient of cost = -(scale * sum var_exp - KL), chained through
+ * the Log1pe transform of the positive parameters (GPflow transforms.positive: OnOffSVGP.py:61,63, OnOffLikelihood.py:26), Adam with
+ * lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t), m / (sqrt(v) + eps).  As in zigp_kron_fit_steps the parameters live on the device for the
+ * whole call: every step's kernels read the parameter image and the hyperparameter block the previous step's update wrote, the steps are
+ * enqueued back to back and the host synchronises ONCE, at the end of the call.
+ *   shape        the model's sizes (Mf, Mg, D); its pointer and value fields are ignored
+ *   free_state   in/out [n_free]: the UNCONSTRAINED parameters in this block order (ZIGP_DENSE_FIT_BLOCKS = 11, the order of zigp_params):
+ *                Zf (Mf x D), Zg (Mg x D), u_fm (Mf), u_gm (Mg), u_fs_sqrt (Mf), u_gs_sqrt (Mg), ell_f, ell_g (ell_size_* entries each),
+ *                var_f, var_g, noise
+ *   adam_m, adam_v   in/out [n_free]: Adam moments (zeros at iteration 0)
+ *   t0           iterations done before this call (step i of the call is Adam's t = t0 + i + 1)
+ *   rows         [n_steps * batch] indices into the RESIDENT data set (zigp_set_data), repeats allowed, as for zigp_select_rows: step i
+ *                uses rows[i batch .. (i + 1) batch).  They are uploaded once per call and every step gathers its rows on the device into a
+ *                buffer of the call's own: the active selection of zigp_select_rows is left as found.  NULL: every step uses the ACTIVE
+ *                rows [0, N) (full-batch Adam; `batch` is ignored)
+ *   elbo_data, kl    out [n_steps] (nullable): scale * sum var_exp and KL of every step, evaluated at the parameters BEFORE its update
+ * opts: per block the learning rate, positive (1: value = log(1 + exp(x)) + 1e-6, Log1pe with lower 1e-6; 0: value = x) and trainable
+ * (0: the block's x, m and v stay untouched -- a fixed parameter, which zigp.optim.AdamGroups skips too; its value is the transform of
+ * its free-state entry).  ell_size_f / ell_size_g: D, or 1 for ONE lengthscale broadcast over the D columns, whose gradient is the sum
+ * of the D per-column gradients in column order.
+ * Every step runs the per-row form of the Kuf-cotangent reductions (the centred form of zigp_elbo needs a centre chosen on the host).
+ * A Cholesky failure in step k returns ZIGP_ENOTPD; free_state / adam_* then hold the state before the failing step -- the k updates
+ * before it HAVE been applied (zigp_fit_steps_applied returns k) -- the history entries from step k on are NaN, and zigp_last_error names
+ * the step and the latent.  The steps enqueued behind a failed one still run (at most n_steps - k wasted steps); their updates are skipped.
+ * ZIGP_EARG: NULL arguments or bad sizes, n_free not the model's, a row index out of range, more than 1 GiB of row indices, a mean
+ * function set on the context (its parameters stay with zigp_elbo and a host optimiser) or a communicator attached (zigp_comm_init). */
+#define ZIGP_DENSE_FIT_BLOCKS 11
+typedef struct {
+  double lr[ZIGP_DENSE_FIT_BLOCKS];          /* Adam learning rate of each block */
+  int32_t positive[ZIGP_DENSE_FIT_BLOCKS];   /* 1: Log1pe (lower 1e-6), 0: identity */
+  int32_t trainable[ZIGP_DENSE_FIT_BLOCKS];  /* 0: fixed */
+  int32_t ell_size_f, ell_size_g;            /* 1 or D */
+  double beta1, beta2, eps;                  /* TensorFlow's defaults: 0.9, 0.999, 1e-8 */
+} zigp_fit_opts;
+int zigp_fit_steps(zigp_ctx* ctx, const zigp_params* shape, const zigp_fit_opts* opts, double* free_state, double* adam_m,
+                   double* adam_v, int64_t n_free, int64_t t0, int32_t n_steps, const int64_t* rows, int64_t batch,
+                   double jitter, double scale, int32_t include_kl, double* elbo_data, double* kl);
+/* Updates applied by the LAST zigp_fit_steps call of this context: n_steps after a call that returned 0, the k steps before the failing
+ * one after ZIGP_ENOTPD, 0 when the call ended before its first step (bad argument, HIP error). */
+int64_t zigp_fit_steps_applied(zigp_ctx* ctx);
+
 /* Prediction.  Replaces OnOffSVGP.predict_onoffgp -> build_predict (onoffgpf/OnOffSVGP.py:124-152,160-162).
  * out9 is (9,N): gfmean, gfvar, gfmeanu, fmean, fvar, gmean, gvar, ephi_g, evar_phi_g (order of :152). */
 int zigp_predict(zigp_ctx* ctx, const zigp_params* p, const double* Xnew, int64_t N, double jitter,

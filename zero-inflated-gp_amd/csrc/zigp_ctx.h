@@ -148,6 +148,10 @@ struct zigp_ctx : zigp::CtxHandles {
   // zigp_select_rows: the active data (dX, dY, N) is a gathered batch of the resident set (fullX, fullY, fullN)
   const double* fullX = nullptr; const double* fullY = nullptr; int64_t fullN = 0;
   zigp::DevBuf selX, selY, selIdx;
+  // zigp_fit_steps: the call's own gathered batch and row indices (the selection above is left as found), its device state
+  // [x | m | v | history | failure record | hyperparameter block], and the updates its LAST call applied
+  zigp::DevBuf fitX, fitY, fitIdx, fit;
+  int64_t dense_fit_steps_applied = 0;
   // dense path state
   zigp::Latent lat[2];
   zigp::DevBuf pw_part;                 // pointwise block partials

@@ -50,13 +50,15 @@ void kgrad_centre(Latent& lt, const double* Z, const double* ell, int M, int D) 
   lt.kg_exact = !(spread <= KG_EXACT_SPREAD);
 }
 
-int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D) {
-  size_t off[2][6], total = 0;
+// Layout of the parameter image for the sizes M (sets lat[h].M / Mp, sizes c->parm) and, once the image is in place or on its way, the
+// views into it and the M x M buffers (latents_views).  latents_upload stages the image from host values; the fit loop
+// (zigp_fit_steps) has k_dense_fit_image write it from the free state.
+int latents_layout(zigp_ctx* c, const int (&M)[2], int D, size_t (&off)[2][6], size_t& total) {
+  total = 0;
   for (int h = 0; h < 2; ++h) {
     Latent& lt = c->lat[h];
-    lt.M = hl[h].M;
-    lt.Mp = (int)round_up(hl[h].M, BM);
-    lt.var = hl[h].var;
+    lt.M = M[h];
+    lt.Mp = (int)round_up(M[h], BM);
     const size_t Mp = lt.Mp;
     off[h][0] = total; total += Mp * D;      // Z
     off[h][1] = total; total += MAXD;        // ell
@@ -66,20 +68,9 @@ int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D) {
     off[h][5] = total;
   }
   ZIGP_ENSURE(c, c->parm, total);
-  ZIGP_PINNED(c, img, total);
-  memset(img, 0, sizeof(double) * total);
-  for (int h = 0; h < 2; ++h) {
-    const HostLatent& q = hl[h];
-    memcpy(img + off[h][0], q.Z, sizeof(double) * q.M * D);
-    memcpy(img + off[h][1], q.ell, sizeof(double) * D);
-    memcpy(img + off[h][2], q.u, sizeof(double) * q.M);
-    memcpy(img + off[h][3], q.s, sizeof(double) * q.M);
-    const KufHyp kh = make_kuf_hyp(q.ell, q.var, D);
-    kgrad_centre(c->lat[h], q.Z, q.ell, q.M, D);
-    for (int m = 0; m < q.M; ++m)
-      for (int d = 0; d < D; ++d) img[off[h][4] + (size_t)m * D + d] = q.Z[(size_t)m * D + d] * kh.scale[d];
-  }
-  ZIGP_HIP(c, hipMemcpyAsync(c->parm.p, img, sizeof(double) * total, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+int latents_views(zigp_ctx* c, const size_t (&off)[2][6], int D) {
   for (int h = 0; h < 2; ++h) {
     Latent& lt = c->lat[h];
     const size_t Mp = lt.Mp;
@@ -97,27 +88,58 @@ int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D) {
   }
   return 0;
 }
+int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D) {
+  size_t off[2][6], total = 0;
+  const int M[2] = {hl[0].M, hl[1].M};
+  ZIGP_TRY(latents_layout(c, M, D, off, total));
+  for (int h = 0; h < 2; ++h) c->lat[h].var = hl[h].var;
+  ZIGP_PINNED(c, img, total);
+  memset(img, 0, sizeof(double) * total);
+  for (int h = 0; h < 2; ++h) {
+    const HostLatent& q = hl[h];
+    memcpy(img + off[h][0], q.Z, sizeof(double) * q.M * D);
+    memcpy(img + off[h][1], q.ell, sizeof(double) * D);
+    memcpy(img + off[h][2], q.u, sizeof(double) * q.M);
+    memcpy(img + off[h][3], q.s, sizeof(double) * q.M);
+    const KufHyp kh = make_kuf_hyp(q.ell, q.var, D);
+    kgrad_centre(c->lat[h], q.Z, q.ell, q.M, D);
+    for (int m = 0; m < q.M; ++m)
+      for (int d = 0; d < D; ++d) img[off[h][4] + (size_t)m * D + d] = q.Z[(size_t)m * D + d] * kh.scale[d];
+  }
+  ZIGP_HIP(c, hipMemcpyAsync(c->parm.p, img, sizeof(double) * total, hipMemcpyHostToDevice, c->stream));
+  return latents_views(c, off, D);
+}
 
 // MxM forward of BOTH latents (kernels only): Kuu, L = chol, W = L^-1 (+ W^T), the KL pieces v = W u,
 // alpha = W^T v, dkinv = diag(K^-1), kl -> vec[3*Mp], and W' = W diag(s^2) for gradient steps.  Latent f runs on the main stream and g
 // on stream2 (the caller forks / joins); the launches ALTERNATE between the two chains step by step, so that both streams are fed
 // from the start (see potrf_trtri_jobs).
-int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter, bool with_kl, bool need_grad) {
+// d_hyp (fit loop, zigp_fit_steps): the hyperparameters and the pivot tolerances come from this device block (zigp_kernels.h, DH_*), hl
+// carries the sizes only, and latent h reports a failed factorisation in d_info2[h].
+int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter, bool with_kl, bool need_grad, const double* d_hyp = nullptr,
+                    int* d_info2 = nullptr) {
   const hipStream_t st[2] = {c->stream_main, c->stream2};
   for (int h = 0; h < 2; ++h) {
     Latent& lt = c->lat[h];
     const int Mp = lt.Mp;
     OnStream on(c, st[h]);
-    KernHyp hyp = make_hyp(hl[h].ell, hl[h].var, D);
-    hipLaunchKernelGGL(k_kuu_setup, dim3(ceil_div((int64_t)Mp * Mp, 256)), dim3(256), 0, c->stream, lt.Z.p, (int64_t)hl[h].M, hyp, jitter, lt.Kuu.p,
-                       lt.L.p, lt.W.p, lt.s.p, lt.s2.p, (int64_t)Mp);
+    const dim3 grid(ceil_div((int64_t)Mp * Mp, 256));
+    if (d_hyp)
+      hipLaunchKernelGGL(k_kuu_setup<LatHypDev>, grid, dim3(256), 0, c->stream, lt.Z.p, (int64_t)hl[h].M, LatHypDev{d_hyp + h * DH_LAT, D}, jitter, lt.Kuu.p,
+                         lt.L.p, lt.W.p, lt.s.p, lt.s2.p, (int64_t)Mp);
+    else {
+      KernHyp hyp = make_hyp(hl[h].ell, hl[h].var, D);
+      hipLaunchKernelGGL(k_kuu_setup<KernHyp>, grid, dim3(256), 0, c->stream, lt.Z.p, (int64_t)hl[h].M, hyp, jitter, lt.Kuu.p,
+                         lt.L.p, lt.W.p, lt.s.p, lt.s2.p, (int64_t)Mp);
+    }
     ZIGP_HIP(c, hipGetLastError());
   }
   {
     PotrfJob jobs[2];
     for (int h = 0; h < 2; ++h) {
       Latent& lt = c->lat[h];
-      jobs[h] = PotrfJob{lt.L.p, lt.W.p, lt.T1.p, lt.Mp, true, lt.M, pivot_tol(hl[h].var, jitter, c->pivot_rtol), true, &lt.sk};
+      jobs[h] = PotrfJob{lt.L.p, lt.W.p, lt.T1.p, lt.Mp, true, lt.M, d_hyp ? 0.0 : pivot_tol(hl[h].var, jitter, c->pivot_rtol), true, &lt.sk};
+      if (d_hyp) { jobs[h].tol_dev = d_hyp + h * DH_LAT + DH_PIVTOL; jobs[h].info = d_info2 + h; }
     }
     ZIGP_TRY(potrf_trtri_jobs(c, 2, jobs, st));
   }
@@ -166,13 +188,18 @@ int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter
 }
 
 // Kuf panel of one latent for the chunk starting at row n0 (HBM-write bound; runs on the side stream under the previous chunk's SYRKs)
-int latent_chunk_kuf(zigp_ctx* c, Latent& lt, const double* dX, int64_t Nrows, int64_t n0, int64_t Nc, int D, const double* ell_host) {
+// R (fit loop): the latent's record of the device hyperparameter block; ell_host is then not read
+int latent_chunk_kuf(zigp_ctx* c, Latent& lt, const double* dX, int64_t Nrows, int64_t n0, int64_t Nc, int D, const double* ell_host,
+                     const double* R = nullptr) {
   const int Mp = lt.Mp;
-  const KufHyp kh = make_kuf_hyp(ell_host, lt.var, D);
+  const KufHyp kh = R ? KufHyp() : make_kuf_hyp(ell_host, lt.var, D);
   ProfScope ps(c, PC_KUF);
   const dim3 grid((unsigned)(Nc / 512), Mp / 16), block(256);
-#define ZIGP_KUF(DD) \
-  case DD: hipLaunchKernelGGL(k_kuf_build<DD>, grid, block, 0, c->stream, dX, Nrows, n0, lt.Zs.p, lt.M, kh, lt.K.p, Nc); break;
+#define ZIGP_KUF(DD)                                                                                                                   \
+  case DD:                                                                                                                             \
+    if (R) hipLaunchKernelGGL((k_kuf_build<DD, LatHypDev>), grid, block, 0, c->stream, dX, Nrows, n0, lt.Zs.p, lt.M, LatHypDev{R, DD}, lt.K.p, Nc); \
+    else hipLaunchKernelGGL((k_kuf_build<DD, KufHyp>), grid, block, 0, c->stream, dX, Nrows, n0, lt.Zs.p, lt.M, kh, lt.K.p, Nc);               \
+    break;
   switch (D) {
     ZIGP_KUF(1) ZIGP_KUF(2) ZIGP_KUF(3) ZIGP_KUF(4) ZIGP_KUF(5) ZIGP_KUF(6) ZIGP_KUF(7) ZIGP_KUF(8)
     default: return fail_arg(c, "D out of range");
@@ -411,15 +438,22 @@ struct DenseCall {
   int pw_blocks = 0;
   int* hinfo = nullptr;   // Cholesky status, staged with the other results
   bool prep_side = false; // buffers / zeroed accumulators / first Kuf panels were issued on the third stream (dense_mxm_forward)
+  // a step of zigp_fit_steps: the parameter image and this hyperparameter block are on the device already (k_dense_fit_image), nothing is
+  // staged, and a failed factorisation of latent h is left in d_info2[h] for the update kernel (p and hl carry the sizes only)
+  const double* d_hyp = nullptr; int* d_info2 = nullptr;
+  const double* hyp_rec(int h) const { return d_hyp ? d_hyp + h * DH_LAT : nullptr; }
 };
 
 // Parameters to the device, then the MxM forward of f on the main stream and of g on stream2 (dozens of small dependent launches each)
 int dense_prepare_buffers(zigp_ctx* c, DenseCall& k);
 int64_t dense_first_chunk_rows(const DenseCall& k) { return std::min<int64_t>(k.Nc, round_up(k.row_end - k.row_begin, 1024)); }
 int dense_mxm_forward(zigp_ctx* c, DenseCall& k) {
-  ZIGP_TRY(begin_staged_call(c));
-  ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
-  ZIGP_TRY(latents_upload(c, k.hl, k.D));
+  if (k.d_hyp) ZIGP_HIP(c, hipMemsetAsync(k.d_info2, 0, 2 * sizeof(int), c->stream));
+  else {
+    ZIGP_TRY(begin_staged_call(c));
+    ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
+    ZIGP_TRY(latents_upload(c, k.hl, k.D));
+  }
   // The call's buffers, its zeroed accumulators and the first chunk's Kuf panels need the uploaded parameters only: third stream, under
   // the two factorisation chains (which are dependent launches of <= 36 workgroups).  Not while kernels are being timed (they run alone).
   k.prep_side = c->overlap == 1 && !c->prof_on;
@@ -429,16 +463,16 @@ int dense_mxm_forward(zigp_ctx* c, DenseCall& k) {
     ZIGP_TRY(dense_prepare_buffers(c, k));
     if (k.has_rows)
       for (int h = 0; h < 2; ++h)
-        ZIGP_TRY(latent_chunk_kuf(c, c->lat[h], k.dX, k.Nrows, k.row_begin, dense_first_chunk_rows(k), k.D, k.ell_h[h]));
+        ZIGP_TRY(latent_chunk_kuf(c, c->lat[h], k.dX, k.Nrows, k.row_begin, dense_first_chunk_rows(k), k.D, k.ell_h[h], k.hyp_rec(h)));
     ZIGP_HIP(c, hipEventRecord(c->ev_prep, c->stream3));
   }
   {
     ProfScope ps(c, PC_MXM);     // wall time of the two concurrent chains: both events on the main stream, the second after the join
     ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
-    ZIGP_TRY(latents_forward(c, k.hl, k.D, k.jitter, true, k.need_grad));
+    ZIGP_TRY(latents_forward(c, k.hl, k.D, k.jitter, true, k.need_grad, k.d_hyp, k.d_info2));
     ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   }
-  return request_info(c, &k.hinfo);   // read after the final synchronisation
+  return k.d_hyp ? 0 : request_info(c, &k.hinfo);   // read after the final synchronisation
 }
 
 // Chunk size and per-call buffers.  The row range is cut into ceil(span / chunk) chunks of (nearly) equal size, a multiple of 1024, so
@@ -512,17 +546,18 @@ PwArgs dense_pointwise_args(zigp_ctx* c, const DenseCall& k, int64_t n0, int64_t
   a.acc = c->pw_part.p; a.out9 = k.d_out9 ? k.d_out9 - k.row_begin : nullptr; a.ld9 = k.row_end - k.row_begin;
   return a;
 }
-int dense_pointwise_launch(zigp_ctx* c, bool predict, bool need_grad, const PwArgs& a) {
+int dense_pointwise_launch(zigp_ctx* c, bool predict, bool need_grad, const PwArgs& a, const double* d_hyp = nullptr) {
   ProfScope ps(c, PC_POINT);
   const int nblk = (int)(a.Nc / PW_PTS);
-  if (predict) hipLaunchKernelGGL((k_pointwise<true, false>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
+  if (d_hyp) hipLaunchKernelGGL((k_pointwise<false, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a, d_hyp);     // a gradient step of the fit loop
+  else if (predict) hipLaunchKernelGGL((k_pointwise<true, false>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
   else if (need_grad) hipLaunchKernelGGL((k_pointwise<false, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);   // variance from sum K J'
   else hipLaunchKernelGGL((k_pointwise<false, false>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
   ZIGP_HIP(c, hipGetLastError());
   return 0;
 }
 int dense_pointwise(zigp_ctx* c, const DenseCall& k, int64_t n0, int64_t Nc) {
-  return dense_pointwise_launch(c, k.predict, k.need_grad, dense_pointwise_args(c, k, n0, Nc));
+  return dense_pointwise_launch(c, k.predict, k.need_grad, dense_pointwise_args(c, k, n0, Nc), k.d_hyp);
 }
 
 // ---- chunk loop.  The MFMA-bound GEMMs stay on the main stream; with zigp_set_overlap(1) the HBM-bound kernels of a chunk -- the two
@@ -544,7 +579,7 @@ int dense_chunk_loop(zigp_ctx* c, const DenseCall& k) {
     return chunk_rows(n0) == Nc_full && (((n0 - row_begin) / Nc_full) % c->prof_every) == 0;
   };
   auto kuf = [&](int64_t n0) -> int {     // Kuf panels of both latents for the chunk at row n0
-    for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_kuf(c, c->lat[h], k.dX, k.Nrows, n0, chunk_rows(n0), D, k.ell_h[h]));
+    for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_kuf(c, c->lat[h], k.dX, k.Nrows, n0, chunk_rows(n0), D, k.ell_h[h], k.hyp_rec(h)));
     return 0;
   };
   auto kgrad = [&](int64_t n0, int64_t Nc) -> int {
@@ -613,10 +648,9 @@ int dense_chunk_loop(zigp_ctx* c, const DenseCall& k) {
 
 // The call's result vector (layout: k_dense_pack) is assembled on the device, summed over the ranks of a data-parallel run where it
 // lies (zigp_comm_init; no-op otherwise), downloaded once and unpacked: the call's single synchronisation.
-int dense_gather(zigp_ctx* c, DenseCall& k, double* elbo_data, double* kl, zigp_grads* grads) {
+int dense_pack(zigp_ctx* c, const DenseCall& k, DensePackArgs& a, size_t& n) {
   const int D = k.D;
-  size_t n = DP_HDR;
-  DensePackArgs a;
+  n = DP_HDR;
   memset(&a, 0, sizeof(a));
   for (int h = 0; h < 2; ++h) {
     Latent& lt = c->lat[h];
@@ -629,8 +663,16 @@ int dense_gather(zigp_ctx* c, DenseCall& k, double* elbo_data, double* kl, zigp_
   a.mean_on = c->mean_on ? 1 : 0;
   ZIGP_ENSURE(c, c->packed, n);
   a.out = c->packed.p;
-  hipLaunchKernelGGL(k_dense_pack, dim3(2), dim3(256), 0, c->stream, a);
+  if (k.d_hyp) hipLaunchKernelGGL(k_dense_pack<const double*>, dim3(2), dim3(256), 0, c->stream, a, k.d_hyp);
+  else hipLaunchKernelGGL(k_dense_pack<>, dim3(2), dim3(256), 0, c->stream, a);
   ZIGP_HIP(c, hipGetLastError());
+  return 0;
+}
+int dense_gather(zigp_ctx* c, DenseCall& k, double* elbo_data, double* kl, zigp_grads* grads) {
+  const int D = k.D;
+  size_t n = 0;
+  DensePackArgs a;
+  ZIGP_TRY(dense_pack(c, k, a, n));
   ZIGP_TRY(comm_allreduce(c, c->packed.p, n));
   double* hv = nullptr;
   ZIGP_TRY(download(c, c->packed.p, n, &hv));
@@ -659,6 +701,40 @@ int dense_gather(zigp_ctx* c, DenseCall& k, double* elbo_data, double* kl, zigp_
   return 0;
 }
 
+// Chunk size of the call and every tile list of its chunk loop, uploaded before the call enqueues anything
+int dense_plan(zigp_ctx* c, DenseCall& k) {
+  const int M[2] = {k.hl[0].M, k.hl[1].M};
+  const int64_t span = k.has_rows ? k.row_end - k.row_begin : 0;
+  k.Nc = chunk_rows_for(c->chunk_auto, c->chunk, round_up(std::max(M[0], M[1]), BM), span);
+  if (k.has_rows) {
+    const int64_t last = std::min<int64_t>(k.Nc, round_up(span - (span - 1) / k.Nc * k.Nc, 1024));
+    k.plan[0] = chunk_plan(M, k.Nc, k.need_grad, c->trmm_tail);
+    ZIGP_TRY(upload_plan(c, k.plan[0]));
+    if (last != k.Nc) { k.plan[1] = chunk_plan(M, last, k.need_grad, c->trmm_tail); ZIGP_TRY(upload_plan(c, k.plan[1])); }
+  }
+  return 0;
+}
+// The launches of one call up to its result vector: M x M forward, chunk loop, M x M backward (gradient steps).  zigp_elbo / zigp_predict
+// run it once (run_dense), zigp_fit_steps once per iteration, on the same streams and events.
+int dense_step(zigp_ctx* c, DenseCall& k) {
+  ZIGP_TRY(dense_mxm_forward(c, k));
+  if (k.prep_side) ZIGP_HIP(c, hipStreamWaitEvent(c->stream_main, c->ev_prep, 0));
+  else ZIGP_TRY(dense_prepare_buffers(c, k));
+  const int rc = dense_chunk_loop(c, k);
+  c->prof_skip = false;   // the loop sets it for the chunks it does not time; cleared on every exit path
+  ZIGP_TRY(rc);
+  if (k.need_grad) {
+    ProfScope ps(c, PC_MXM);     // wall time of the two concurrent chains, as in the forward: both events on the main stream, the second after the join
+    ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
+    for (int h = 0; h < 2; ++h) {
+      OnStream on(c, h == 0 ? c->stream_main : c->stream2);
+      ZIGP_TRY(latent_mxm_backward(c, c->lat[h], k.D, k.jitter, k.has_rows, k.include_kl != 0));
+    }
+    ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
+  }
+  return 0;
+}
+
 // shared driver for zigp_elbo / zigp_predict
 int run_dense(zigp_ctx* c, const zigp_params* p, const double* dX, const double* dY, int64_t Nrows, int D, double jitter,
               double scale, double g_offset, int64_t row_begin, int64_t row_end, int include_kl, bool predict, double* d_out9,
@@ -671,31 +747,9 @@ int run_dense(zigp_ctx* c, const zigp_params* p, const double* dX, const double*
   k.hl[0] = HostLatent{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f};
   k.hl[1] = HostLatent{p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g};
   k.ell_h[0] = p->ell_f; k.ell_h[1] = p->ell_g;
-  const int64_t span = k.has_rows ? row_end - row_begin : 0;
-  k.Nc = chunk_rows_for(c->chunk_auto, c->chunk, round_up(std::max(p->Mf, p->Mg), BM), span);
-  if (k.has_rows) {     // every tile list of the chunk loop, uploaded before the call enqueues anything
-    const int M[2] = {p->Mf, p->Mg};
-    const int64_t last = std::min<int64_t>(k.Nc, round_up(span - (span - 1) / k.Nc * k.Nc, 1024));
-    k.plan[0] = chunk_plan(M, k.Nc, k.need_grad, c->trmm_tail);
-    ZIGP_TRY(upload_plan(c, k.plan[0]));
-    if (last != k.Nc) { k.plan[1] = chunk_plan(M, last, k.need_grad, c->trmm_tail); ZIGP_TRY(upload_plan(c, k.plan[1])); }
-  }
-  ZIGP_TRY(dense_mxm_forward(c, k));
-  if (k.prep_side) ZIGP_HIP(c, hipStreamWaitEvent(c->stream_main, c->ev_prep, 0));
-  else ZIGP_TRY(dense_prepare_buffers(c, k));
-  const int rc = dense_chunk_loop(c, k);
-  c->prof_skip = false;   // the loop sets it for the chunks it does not time; cleared on every exit path
-  ZIGP_TRY(rc);
+  ZIGP_TRY(dense_plan(c, k));
+  ZIGP_TRY(dense_step(c, k));
   if (predict) { ZIGP_HIP(c, hipStreamSynchronize(c->stream)); prof_collect(c); return info_result(c, k.hinfo, "Kuu"); }
-  if (k.need_grad) {
-    ProfScope ps(c, PC_MXM);     // wall time of the two concurrent chains, as in the forward: both events on the main stream, the second after the join
-    ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
-    for (int h = 0; h < 2; ++h) {
-      OnStream on(c, h == 0 ? c->stream_main : c->stream2);
-      ZIGP_TRY(latent_mxm_backward(c, c->lat[h], D, jitter, k.has_rows, include_kl != 0));
-    }
-    ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
-  }
   return dense_gather(c, k, elbo_data, kl, grads);
 }
 
@@ -725,7 +779,9 @@ int zigp_create(zigp_ctx** out, int device_id) {
       hipEventCreateWithFlags(&c->ev_prep_fork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming) != hipSuccess) { delete c; return ZIGP_EHIP; }
   if (hipMalloc((void**)&c->d_info, sizeof(int)) != hipSuccess) { delete c; return ZIGP_EHIP; }
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_potrf_diag), hipFuncAttributeMaxDynamicSharedMemorySize,
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_potrf_diag<double>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)(sizeof(double) * PB * PBLD)) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_potrf_diag<const double*>), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)(sizeof(double) * PB * PBLD)) != hipSuccess) { delete c; return ZIGP_EHIP; }
   if (const char* e = getenv("ZIGP_FWD_KUF_SIDE")) c->fwd_kuf_side = atoi(e) != 0;   // A/B switch (tools/ab_envs.sh); default on
   if (const char* e = getenv("ZIGP_TRMM_TAIL")) c->trmm_tail = atoi(e) != 0;      // A/B switch of the LPT tail (tools/ab_envs.sh); default on
@@ -868,6 +924,152 @@ int zigp_elbo(zigp_ctx* c, const zigp_params* p, double jitter, double scale, do
                    grads);
 }
 
+// ---- the dense fit loop on the device (include/zigp.h) ----
+// Host side of one call: everything is planned, sized and uploaded before the first step is enqueued (tile lists: dense_plan; the state,
+// the moments and the row indices: one staged copy each); a step is k_gather_rows (minibatch) + dense_step + k_dense_pack +
+// k_dense_fit_update + k_dense_fit_image on the call's main stream, its side work forked from and joined into it exactly as in zigp_elbo.
+// The first step sizes the per-call buffers and fills the tile cache of the M x M stage; from the second step on nothing allocates, copies
+// synchronously or synchronises until the one download at the end.
+static_assert(DFIT_BLOCKS == ZIGP_DENSE_FIT_BLOCKS, "block order of include/zigp.h");
+int zigp_fit_steps(zigp_ctx* c, const zigp_params* shape, const zigp_fit_opts* o, double* free_state, double* adam_m, double* adam_v, int64_t n_free,
+                   int64_t t0, int32_t n_steps, const int64_t* rows, int64_t batch, double jitter, double scale, int32_t include_kl, double* elbo_data,
+                   double* kl) {
+  if (!c) return ZIGP_EARG;
+  c->dense_fit_steps_applied = 0;      // whatever ends this call early, no update of it has been applied
+  if (!shape || !o || !free_state || !adam_m || !adam_v) return fail_arg(c, "zigp_fit_steps: NULL argument");
+  if (shape->Mf <= 0 || shape->Mg <= 0 || shape->D <= 0 || shape->D > MAXD) return fail_arg(c, "zigp_fit_steps: need Mf, Mg > 0 and 1 <= D <= 8");
+  if (n_steps <= 0 || t0 < 0 || (rows && batch <= 0)) return fail_arg(c, "zigp_fit_steps: need n_steps > 0, t0 >= 0 and, with rows, batch > 0");
+  if (!(jitter >= 0)) return fail_arg(c, "zigp_fit_steps: jitter must be >= 0");
+  if (!(o->beta1 >= 0 && o->beta1 < 1 && o->beta2 >= 0 && o->beta2 < 1 && o->eps > 0)) return fail_arg(c, "zigp_fit_steps: bad Adam constants");
+  const int D = shape->D, M[2] = {shape->Mf, shape->Mg};
+  const int es[2] = {o->ell_size_f, o->ell_size_g};
+  for (int h = 0; h < 2; ++h)
+    if (es[h] != 1 && es[h] != D) return fail_arg(c, "zigp_fit_steps: ell_size must be 1 or D");
+  if (!c->dX) return fail_arg(c, "zigp_fit_steps: no data set (call zigp_set_data first)");
+  if (D != c->D) return fail_arg(c, "zigp_fit_steps: shape.D differs from the data's D");
+  if (c->mean_on) return fail_arg(c, "zigp_fit_steps: a mean function is set; its parameters stay with the host loop (zigp_elbo + a host optimiser)");
+  if (c->comm) return fail_arg(c, "zigp_fit_steps: a communicator is attached; the dense device loop is single-process");
+  if (rows) {
+    if ((int64_t)n_steps > ((int64_t)1 << 27) / batch) return fail_arg(c, "zigp_fit_steps: n_steps * batch row indices exceed 1 GiB");
+    for (int64_t i = 0; i < (int64_t)n_steps * batch; ++i)
+      if (rows[i] < 0 || rows[i] >= c->fullN) return fail_arg(c, "zigp_fit_steps: row index out of range");
+  } else if (c->N <= 0) return fail_arg(c, "zigp_fit_steps: no active rows");
+  DenseFitArgs fa;
+  memset(static_cast<void*>(&fa), 0, sizeof(fa));
+  DenseFitDesc& d = fa.d;
+  {
+    const int sizes[DFIT_BLOCKS] = {M[0] * D, M[1] * D, M[0], M[1], M[0], M[1], es[0], es[1], 1, 1, 1};
+    int off = 0;
+    for (int b = 0; b < DFIT_BLOCKS; ++b) {
+      d.off[b] = off; d.n[b] = sizes[b]; d.gn[b] = 1; off += sizes[b];
+      d.positive[b] = o->positive[b] != 0; d.trainable[b] = o->trainable[b] != 0; d.lr[b] = o->lr[b];
+    }
+    d.off[DFIT_BLOCKS] = off;
+    if ((int64_t)off != n_free) return fail_arg(c, "zigp_fit_steps: n_free does not match the model sizes");
+    // the packed result vector (k_dense_pack): header, then per latent dZ (M D), du (M), ds (M), dell (D)
+    int g = DP_HDR;
+    for (int h = 0; h < 2; ++h) {
+      d.goff[0 + h] = g; d.goff[2 + h] = g + M[h] * D; d.goff[4 + h] = g + M[h] * D + M[h]; d.goff[6 + h] = g + M[h] * D + 2 * M[h];
+      d.gn[6 + h] = es[h] == 1 ? D : 1;
+      g += M[h] * D + 2 * M[h] + D;
+    }
+    d.goff[8] = 2; d.goff[9] = 3; d.goff[10] = 4;
+  }
+  d.D = D; d.M[0] = M[0]; d.M[1] = M[1];
+  d.beta1 = o->beta1; d.beta2 = o->beta2; d.eps = o->eps; d.jitter = jitter; d.rtol_eps = c->pivot_rtol * 2.220446049250313e-16;
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  ZIGP_TRY(begin_staged_call(c));
+  // the call as the step driver sees it: a gradient step over its own gathered batch, or over the active rows
+  zigp_params sizes_only;
+  memset(&sizes_only, 0, sizeof(sizes_only));
+  sizes_only.Mf = M[0]; sizes_only.Mg = M[1]; sizes_only.D = D;
+  DenseCall k;
+  k.p = &sizes_only; k.D = D; k.jitter = jitter; k.scale = scale; k.g_offset = 0.0; k.include_kl = include_kl; k.predict = false; k.d_out9 = nullptr;
+  k.need_grad = true; k.has_rows = true; k.row_begin = 0;
+  k.hl[0] = HostLatent{M[0], nullptr, nullptr, nullptr, nullptr, 0.0}; k.hl[1] = HostLatent{M[1], nullptr, nullptr, nullptr, nullptr, 0.0};
+  k.ell_h[0] = k.ell_h[1] = nullptr;
+  const int64_t nidx = rows ? (int64_t)n_steps * batch : 0;
+  if (rows) {
+    ZIGP_ENSURE(c, c->fitX, (size_t)batch * D); ZIGP_ENSURE(c, c->fitY, (size_t)batch); ZIGP_ENSURE(c, c->fitIdx, (size_t)nidx);
+    k.dX = c->fitX.p; k.dY = c->fitY.p; k.Nrows = batch;
+  } else { k.dX = c->dX; k.dY = c->dY; k.Nrows = c->N; }
+  k.row_end = k.Nrows;
+  ZIGP_TRY(dense_plan(c, k));
+  // device state of the call: [x | m | v | history (2 per step) | failure record (4 ints) | Cholesky status (2 ints)], all downloaded
+  // together at the end, then -- on a 256-byte boundary -- the hyperparameter block
+  const size_t nf = (size_t)n_free, n_hist = (size_t)2 * n_steps, n_down = 3 * nf + n_hist + 3, off_hyp = (size_t)round_up((int64_t)n_down, 32);
+  ZIGP_ENSURE(c, c->fit, off_hyp + DH_SIZE);
+  fa.x = c->fit.p; fa.m = fa.x + nf; fa.v = fa.m + nf; fa.hist = fa.v + nf;
+  fa.fail = reinterpret_cast<int*>(fa.hist + n_hist);
+  k.d_info2 = fa.fail + 4; fa.info = k.d_info2;
+  double* H = c->fit.p + off_hyp;
+  k.d_hyp = H;
+  size_t off[2][6], total = 0;
+  ZIGP_TRY(latents_layout(c, M, D, off, total));
+  ZIGP_TRY(latents_views(c, off, D));
+  for (int h = 0; h < 2; ++h) {
+    Latent& lt = c->lat[h];
+    lt.var = 0.0;            // not read: the kernels take it from the block
+    lt.kg_exact = true;      // the per-row form of k_kgrad: the centred form needs a centre chosen from Z and ell, which move on the device
+    for (int q = 0; q < MAXD; ++q) lt.zc[q] = 0.0;
+    d.img_Z[h] = (int)off[h][0]; d.img_ell[h] = (int)off[h][1]; d.img_u[h] = (int)off[h][2]; d.img_s[h] = (int)off[h][3]; d.img_Zs[h] = (int)off[h][4];
+  }
+  {
+    ZIGP_PINNED(c, hst, n_down);
+    memcpy(hst, free_state, sizeof(double) * nf); memcpy(hst + nf, adam_m, sizeof(double) * nf); memcpy(hst + 2 * nf, adam_v, sizeof(double) * nf);
+    memset(hst + 3 * nf, 0, sizeof(double) * (n_hist + 3));
+    ZIGP_HIP(c, hipMemcpyAsync(c->fit.p, hst, sizeof(double) * n_down, hipMemcpyHostToDevice, c->stream));
+    ZIGP_HIP(c, hipMemsetAsync(H, 0, sizeof(double) * DH_SIZE, c->stream));
+    ZIGP_HIP(c, hipMemsetAsync(c->parm.p, 0, sizeof(double) * total, c->stream));     // the zero padding of Z, u, s, Zs up to Mp
+    if (rows) {
+      int64_t* hi = (int64_t*)c->pinned.alloc(sizeof(int64_t) * nidx);
+      if (!hi) { c->err = "hipHostMalloc failed for the staging arena"; return ZIGP_EHIP; }
+      memcpy(hi, rows, sizeof(int64_t) * nidx);
+      ZIGP_HIP(c, hipMemcpyAsync(c->fitIdx.p, hi, sizeof(int64_t) * nidx, hipMemcpyHostToDevice, c->stream));
+    }
+  }
+  const dim3 ugrid(ceil_div(n_free, DFIT_THREADS));
+  hipLaunchKernelGGL(k_dense_fit_image, ugrid, dim3(DFIT_THREADS), 0, c->stream, d, fa.x, c->parm.p, H);
+  ZIGP_HIP(c, hipGetLastError());
+  for (int i = 0; i < n_steps; ++i) {
+    if (rows) {
+      hipLaunchKernelGGL(k_gather_rows, dim3(ceil_div(batch * (D + 1), 256)), dim3(256), 0, c->stream, c->fullX, c->fullY,
+                         reinterpret_cast<const int64_t*>(c->fitIdx.p) + (int64_t)i * batch, batch, D, c->fitX.p, c->fitY.p);
+      ZIGP_HIP(c, hipGetLastError());
+    }
+    ZIGP_TRY(dense_step(c, k));
+    DensePackArgs pa; size_t npk = 0;
+    ZIGP_TRY(dense_pack(c, k, pa, npk));
+    // lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t), t counted from 1 (zigp/optim.py AdamGroups.step): the two t-dependent factors from the host
+    const double t = (double)(t0 + i + 1);
+    fa.packed = c->packed.p; fa.step = i; fa.lr_sq = std::sqrt(1.0 - std::pow(d.beta2, t)); fa.lr_den = 1.0 - std::pow(d.beta1, t);
+    hipLaunchKernelGGL(k_dense_fit_update, ugrid, dim3(DFIT_THREADS), 0, c->stream, fa);
+    hipLaunchKernelGGL(k_dense_fit_image, ugrid, dim3(DFIT_THREADS), 0, c->stream, d, fa.x, c->parm.p, H);
+    ZIGP_HIP(c, hipGetLastError());
+  }
+  double* hst = nullptr;
+  ZIGP_TRY(download(c, c->fit.p, n_down, &hst));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  prof_collect(c);
+  const int* hfail = reinterpret_cast<const int*>(hst + 3 * nf + n_hist);
+  memcpy(free_state, hst, sizeof(double) * nf); memcpy(adam_m, hst + nf, sizeof(double) * nf); memcpy(adam_v, hst + 2 * nf, sizeof(double) * nf);
+  const int done = hfail[0] ? hfail[0] - 1 : n_steps;       // steps whose update was applied
+  c->dense_fit_steps_applied = done;
+  for (int i = 0; i < n_steps; ++i) {
+    if (elbo_data) elbo_data[i] = i < done ? hst[3 * nf + 2 * i] : NAN;
+    if (kl) kl[i] = i < done ? hst[3 * nf + 2 * i + 1] : NAN;
+  }
+  if (hfail[0]) {
+    char b[256];
+    snprintf(b, sizeof(b), "Cholesky failed in step %d of this zigp_fit_steps call (iteration %lld): Kuu of latent %s not positive definite at pivot %d; "
+             "the state returned is the one before that step", hfail[0] - 1, (long long)(t0 + hfail[0] - 1), hfail[1] ? "g" : "f", hfail[2]);
+    c->err = b; c->info = hfail[2];
+    return ZIGP_ENOTPD;
+  }
+  return ZIGP_OK;
+}
+int64_t zigp_fit_steps_applied(zigp_ctx* c) { return c ? c->dense_fit_steps_applied : (int64_t)ZIGP_EARG; }
+
 int zigp_predict(zigp_ctx* c, const zigp_params* p, const double* Xnew, int64_t N, double jitter, double g_offset, double* out9) {
   if (!c) return ZIGP_EARG;
   ZIGP_TRY(validate_params(c, p));
@@ -1006,7 +1208,7 @@ int zigp_test_kuf(zigp_ctx* c, int64_t N, int32_t M, int32_t D, const double* X,
   ZIGP_HIP(c, hipMemcpyAsync(dz.p, zs.data(), sizeof(double) * zs.size(), hipMemcpyHostToDevice, c->stream));
   const dim3 grid((unsigned)(Nc / 512), Mp / 16), block(256);
 #define ZIGP_KUF(DD) \
-  case DD: hipLaunchKernelGGL(k_kuf_build<DD>, grid, block, 0, c->stream, dx.p, N, (int64_t)0, dz.p, M, kh, dk.p, Nc); break;
+  case DD: hipLaunchKernelGGL((k_kuf_build<DD, KufHyp>), grid, block, 0, c->stream, dx.p, N, (int64_t)0, dz.p, M, kh, dk.p, Nc); break;
   switch (D) { ZIGP_KUF(1) ZIGP_KUF(2) ZIGP_KUF(3) ZIGP_KUF(4) ZIGP_KUF(5) ZIGP_KUF(6) ZIGP_KUF(7) ZIGP_KUF(8) }
 #undef ZIGP_KUF
   ZIGP_HIP(c, hipGetLastError());

@@ -382,7 +382,9 @@ static int run_gemm_sk_tiles(zigp_ctx* c, DevBuf& planes, const std::string& key
 
 // prepared: the caller has zeroed W and the strictly-upper blocks of L already (k_kuu_setup writes both next to Kuu); planes: buffer for
 // the split-K block products of the inverse (nullptr: plain launches, one workgroup per tile)
-struct PotrfJob { double* L; double* W; double* T; int Mp; bool want_W; int Mreal; double piv_tol; bool prepared; DevBuf* planes; };
+// tol_dev (fit loop): the pivot tolerance is read from this device word instead of piv_tol; info: status word of this job (default: c->d_info)
+struct PotrfJob { double* L; double* W; double* T; int Mp; bool want_W; int Mreal; double piv_tol; bool prepared; DevBuf* planes;
+                  const double* tol_dev = nullptr; int* info = nullptr; };
 static int potrf_trtri_jobs(zigp_ctx* c, int njobs, const PotrfJob* jobs, const hipStream_t* streams) {
   const int kb = BM / BK;  // k-steps per block
   const size_t shm = sizeof(double) * PB * PBLD;
@@ -406,7 +408,9 @@ static int potrf_trtri_jobs(zigp_ctx* c, int njobs, const PotrfJob* jobs, const 
           double* Ajj = Lb + (int64_t)j * BM * Mp + (int64_t)j * BM;
           double* Wjj = Wb + (int64_t)j * BM * Mp + (int64_t)j * BM;
           const int nreal_j = std::max(0, std::min(BM, Mreal - j * BM));
-          hipLaunchKernelGGL(k_potrf_diag, dim3(1), dim3(1024), shm, c->stream, Ajj, Ajj, Wjj, (int64_t)Mp, j * BM, c->d_info, (nreal_j + PNB - 1) / PNB, J.piv_tol);
+          int* info = J.info ? J.info : c->d_info;
+          if (J.tol_dev) hipLaunchKernelGGL(k_potrf_diag<const double*>, dim3(1), dim3(1024), shm, c->stream, Ajj, Ajj, Wjj, (int64_t)Mp, j * BM, info, (nreal_j + PNB - 1) / PNB, J.tol_dev);
+          else hipLaunchKernelGGL(k_potrf_diag<double>, dim3(1), dim3(1024), shm, c->stream, Ajj, Ajj, Wjj, (int64_t)Mp, j * BM, info, (nreal_j + PNB - 1) / PNB, J.piv_tol);
           ZIGP_HIP(c, hipGetLastError());
         } else if (j + 1 < nb && step == 1) {
           auto genp = [&](std::vector<GemmTile>& v) {

@@ -24,6 +24,28 @@ constexpr int PW_THREADS = 256;
 
 struct KernHyp { double inv_ell[MAXD]; double var; int D; };
 
+// Hyperparameter block of the dense fit loop (zigp_fit_steps; k_dense_fit_image writes it, an EARLIER launch than any of its readers).
+// A plain zigp_elbo / zigp_predict hands its kernels the hyperparameters by value (KernHyp, KufHyp, PwArgs, DensePackLat::var, the pivot
+// tolerance); inside a fit call the parameters change on the device without the host seeing them, so the same kernel bodies read them
+// from here instead.  One source per kernel: each of the six (k_kuu_setup, k_potrf_diag, k_kuf_build, k_pointwise, k_dense_pack, and
+// k_kgrad through its per-row form, which needs no centre) is a template on WHERE its hyperparameters come from -- the by-value struct
+// or number it always took, or a pointer into this block -- and reads them through the overloaded accessors next to it (hyp_*, pw_*,
+// pack_var, potrf_tol).  The by-value instantiations are the ones zigp_elbo / zigp_predict launch, with the kernel arguments and the
+// machine code they had as plain kernels.  Layout in doubles: a record of DH_LAT per latent h at h DH_LAT --
+//   [DH_INV, +MAXD) 1 / ell_d    [DH_ELL, +MAXD) ell_d    [DH_SCALE, +MAXD) KUF_C (1 / ell_d) (make_kuf_hyp)    DH_VAR: var
+//   DH_PIVTOL: rtol eps (var + jitter) (pivot_tol)
+// -- then DH_NOISE: the likelihood variance.  Read through the constant address space, as the KH_* block above.
+constexpr int DH_INV = 0, DH_ELL = MAXD, DH_SCALE = 2 * MAXD, DH_VAR = 3 * MAXD, DH_PIVTOL = 3 * MAXD + 1, DH_LAT = 3 * MAXD + 2;
+constexpr int DH_NOISE = 2 * DH_LAT, DH_SIZE = DH_NOISE + 2;
+struct LatHypDev { const double* R; int D; };       // record of one latent in the device block (D: the input dimension, where a body asks for it)
+__device__ __forceinline__ int hyp_dim(const KernHyp& h) { return h.D; }
+__device__ __forceinline__ double hyp_inv_ell(const KernHyp& h, int d) { return h.inv_ell[d]; }
+__device__ __forceinline__ double hyp_var(const KernHyp& h) { return h.var; }
+__device__ __forceinline__ int hyp_dim(const LatHypDev& h) { return h.D; }
+__device__ __forceinline__ double hyp_inv_ell(const LatHypDev& h, int d) { return KF_CONST(h.R)[DH_INV + d]; }
+__device__ __forceinline__ double hyp_scale(const LatHypDev& h, int d) { return KF_CONST(h.R)[DH_SCALE + d]; }
+__device__ __forceinline__ double hyp_var(const LatHypDev& h) { return KF_CONST(h.R)[DH_VAR]; }
+
 // ---------------------------------------------------------------------------------------------
 // block-wide deterministic sum (fixed order: lanes by xor-shuffle tree, then waves 0..nw-1)
 // ---------------------------------------------------------------------------------------------
@@ -70,7 +92,9 @@ __global__ void k_rbf_matrix(const double* __restrict__ X1, int64_t n1, const do
 // Kuu of the M x M forward (k_rbf_matrix with X1 = X2 = Z, same expression) together with everything the factorisation chain wants next to
 // it, in ONE launch: the working copy L = Kuu with its strictly-upper 128-blocks zero (the chain factors in place and never reads them;
 // potrf_trtri_jobs otherwise clears them block row by block row afterwards: 7 memsets at M = 1024), W = 0, and s2 = s^2.
-__global__ void k_kuu_setup(const double* __restrict__ Z, int64_t M, KernHyp h, double jitter, double* __restrict__ Kuu, double* __restrict__ L,
+// H = KernHyp: by value (zigp_elbo, zigp_predict, zigp_prior_kl); H = LatHypDev: the latent's record of the device block (fit loop)
+template <class H>
+__global__ void k_kuu_setup(const double* __restrict__ Z, int64_t M, H h, double jitter, double* __restrict__ Kuu, double* __restrict__ L,
                             double* __restrict__ W, const double* __restrict__ s, double* __restrict__ s2, int64_t Mp) {
   int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= Mp * Mp) return;
@@ -79,11 +103,11 @@ __global__ void k_kuu_setup(const double* __restrict__ Z, int64_t M, KernHyp h, 
   double v;
   if (i < M && j < M) {
     double r2 = 0.0;
-    for (int d = 0; d < h.D; ++d) {
-      double t = (Z[i * h.D + d] - Z[j * h.D + d]) * h.inv_ell[d];
+    for (int d = 0; d < hyp_dim(h); ++d) {
+      double t = (Z[i * hyp_dim(h) + d] - Z[j * hyp_dim(h) + d]) * hyp_inv_ell(h, d);
       r2 = fma(t, t, r2);
     }
-    v = h.var * exp(-0.5 * r2) + ((i == j) ? jitter : 0.0);
+    v = hyp_var(h) * exp(-0.5 * r2) + ((i == j) ? jitter : 0.0);
   } else {
     v = (i == j) ? 1.0 : 0.0;
   }
@@ -128,12 +152,16 @@ __device__ __forceinline__ double kuf_exp2_32(double w, const double* T) {   // 
   const int n = (int)kn;
   return __builtin_amdgcn_ldexp(T[n & 31] * p, n >> 5);
 }
-template <int D>
+__device__ __forceinline__ double hyp_scale(const KufHyp& h, int d) { return h.scale[d]; }
+__device__ __forceinline__ double hyp_var(const KufHyp& h) { return h.var; }
+// H = KufHyp: scale and var by value (zigp_elbo, zigp_predict); H = LatHypDev: from the latent's record of the device block (fit loop; Zs was
+// scaled by the same doubles, k_dense_fit_image)
+template <int D, class H>
 __global__ void __launch_bounds__(256)
-k_kuf_build(const double* __restrict__ X, int64_t N, int64_t n0, const double* __restrict__ Zs, int M, KufHyp h,
+k_kuf_build(const double* __restrict__ X, int64_t N, int64_t n0, const double* __restrict__ Zs, int M, H h,
             double* __restrict__ K, int64_t Nc) {
   __shared__ double T[32];
-  if (threadIdx.x < 32) T[threadIdx.x] = h.var * KUF_T[threadIdx.x];
+  if (threadIdx.x < 32) T[threadIdx.x] = hyp_var(h) * KUF_T[threadIdx.x];
   const int64_t n = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;   // two adjacent columns: 16-byte stores
   const int m0 = blockIdx.y * 16;
   double xs[2][D];
@@ -141,7 +169,7 @@ k_kuf_build(const double* __restrict__ X, int64_t N, int64_t n0, const double* _
   for (int e = 0; e < 2; ++e) {
     const bool valid = (n0 + n + e) < N;
 #pragma unroll
-    for (int d = 0; d < D; ++d) xs[e][d] = valid ? X[(n0 + n + e) * D + d] * h.scale[d] : 0.0;
+    for (int d = 0; d < D; ++d) xs[e][d] = valid ? X[(n0 + n + e) * D + d] * hyp_scale(h, d) : 0.0;
   }
   __syncthreads();
 #pragma unroll 4
@@ -231,8 +259,18 @@ __device__ __forceinline__ PwOut pointwise_eval(double fm, double fv, double gmn
 constexpr int PW_PTS = 64, PW_GROUPS = PW_THREADS / PW_PTS;
 // GRADVAR (gradient steps): plane 2 holds sum_m K J' = sum s^2 A2^2 - sum A1^2 (EpiStorePanelKColsum), so the variance is
 // var + (plane 2) and plane 1 is not read.
-template <bool PREDICT, bool GRADVAR>
-__device__ __forceinline__ void pw_block(const PwArgs& p, int blk, int tid, double (*grp)[PW_GROUPS][PW_PTS]) {
+// var_f / var_g / noise: the three fields of PwArgs, or the device block `H` (PwArgs' fields are then not read)
+struct PwHypDev { const double* H; };
+__device__ __forceinline__ const PwArgs& pw_hyp(const PwArgs& p) { return p; }
+__device__ __forceinline__ PwHypDev pw_hyp(const PwArgs&, const double* H) { return PwHypDev{H}; }
+__device__ __forceinline__ double pw_var_f(const PwArgs& p) { return p.var_f; }
+__device__ __forceinline__ double pw_var_g(const PwArgs& p) { return p.var_g; }
+__device__ __forceinline__ double pw_noise(const PwArgs& p) { return p.noise; }
+__device__ __forceinline__ double pw_var_f(const PwHypDev& h) { return KF_CONST(h.H)[DH_VAR]; }
+__device__ __forceinline__ double pw_var_g(const PwHypDev& h) { return KF_CONST(h.H)[DH_LAT + DH_VAR]; }
+__device__ __forceinline__ double pw_noise(const PwHypDev& h) { return KF_CONST(h.H)[DH_NOISE]; }
+template <bool PREDICT, bool GRADVAR, class HS>
+__device__ __forceinline__ void pw_block(const PwArgs& p, const HS& hs, int blk, int tid, double (*grp)[PW_GROUPS][PW_PTS]) {
   static_assert(!(PREDICT && GRADVAR), "predict has no J' panel");
   const int lane = tid & (PW_PTS - 1), g = tid / PW_PTS;
   const int64_t n = (int64_t)blk * PW_PTS + lane;
@@ -262,8 +300,8 @@ __device__ __forceinline__ void pw_block(const PwArgs& p, int blk, int tid, doub
     tot[v] = a;
   }
   double fm = tot[0], gmn = tot[3];
-  const double fv = GRADVAR ? p.var_f + tot[2] : p.var_f - tot[1] + tot[2];     // main.py:278,302
-  const double gvr = GRADVAR ? p.var_g + tot[5] : p.var_g - tot[4] + tot[5];
+  const double fv = GRADVAR ? pw_var_f(hs) + tot[2] : pw_var_f(hs) - tot[1] + tot[2];     // main.py:278,302
+  const double gvr = GRADVAR ? pw_var_g(hs) + tot[5] : pw_var_g(hs) - tot[4] + tot[5];
   gmn += p.g_offset;
   const bool valid = (p.n0 + n) < p.row_end;
   double xs[MAXD];
@@ -277,7 +315,7 @@ __device__ __forceinline__ void pw_block(const PwArgs& p, int blk, int tid, doub
     fm += m;
   }
   const double y = (valid && p.Y) ? p.Y[p.n0 + n] : 0.0;
-  PwOut o = pointwise_eval(fm, fv, gmn, gvr, y, p.noise);
+  PwOut o = pointwise_eval(fm, fv, gmn, gvr, y, pw_noise(hs));
   if (PREDICT) {
     if (valid) {
       double* q = p.out9 + (p.n0 + n);
@@ -305,11 +343,13 @@ __device__ __forceinline__ void pw_block(const PwArgs& p, int blk, int tid, doub
     }
   }
 }
-template <bool PREDICT, bool GRADVAR>
+// k_pointwise<..>(p): var_f, var_g and the noise variance from p; k_pointwise<..>(p, H): from the device block (a step of the fit loop)
+template <bool PREDICT, bool GRADVAR, class... HB>
 __global__ void __launch_bounds__(PW_THREADS)
-k_pointwise(PwArgs p) {
+k_pointwise(PwArgs p, HB... hb) {
+  static_assert(sizeof...(HB) <= 1, "at most the hyperparameter block");
   __shared__ double grp[6][PW_GROUPS][PW_PTS];
-  pw_block<PREDICT, GRADVAR>(p, blockIdx.x, threadIdx.x, grp);
+  pw_block<PREDICT, GRADVAR>(p, pw_hyp(p, hb...), blockIdx.x, threadIdx.x, grp);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -641,8 +681,14 @@ struct DensePackArgs {
   const double* pw; int pw_blocks; int D; int need_grad, include_kl, mean_on;
   double* out;
 };
+// k_dense_pack<>(a): the kernel variances from DensePackLat::var (zigp_elbo); k_dense_pack<const double*>(a, H): from the device
+// hyperparameter block H (fit loop; DensePackLat::var is not read, ell is a device pointer already)
+__device__ __forceinline__ double pack_var(const DensePackArgs& a, int h) { return a.lat[h].var; }
+__device__ __forceinline__ double pack_var(const DensePackArgs&, int h, const double* H) { return KF_CONST(H)[h * DH_LAT + DH_VAR]; }
+template <class... HV>
 __global__ void __launch_bounds__(256)
-k_dense_pack(DensePackArgs a) {
+k_dense_pack(DensePackArgs a, HV... hv) {
+  static_assert(sizeof...(HV) <= 1, "at most the hyperparameter block");
   __shared__ double sh[4];
   const int h = blockIdx.x, t = threadIdx.x;
   const DensePackLat& L = a.lat[h];
@@ -700,9 +746,8 @@ k_dense_pack(DensePackArgs a) {
     v = block_sum<4>(v, sh);
     if (t == 0) { const double e = L.ell[d]; ol[d] = v / (e * e * e); }
   }
-  if (t == 0) a.out[2 + h] = dv / L.var + pws[2 + h];
+  if (t == 0) a.out[2 + h] = dv / pack_var(a, h, hv...) + pws[2 + h];
 }
-
 // rows `idx` of the resident (X, Y) gathered into a contiguous batch (MinibatchData's per-step sample, onoffgpf/OnOffSVGP.py:46-47)
 __global__ void k_gather_rows(const double* __restrict__ X, const double* __restrict__ Y, const int64_t* __restrict__ idx, int64_t n, int D,
                               double* __restrict__ Xb, double* __restrict__ Yb) {
@@ -711,6 +756,126 @@ __global__ void k_gather_rows(const double* __restrict__ X, const double* __rest
   const int64_t i = t / (D + 1); const int d = (int)(t - i * (D + 1));
   const int64_t r = idx[i];
   if (d < D) Xb[i * D + d] = X[r * D + d]; else Yb[i] = Y[r];
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device-resident fit loops (zigp_kron_fit_steps: k_fit_update, zigp_kronf.hip; zigp_fit_steps: the two kernels below).  Both chain
+// d ELBO / d (constrained value) through the Log1pe transform and apply one Adam step per element with the arithmetic of
+// zigp.optim.AdamGroups.step, operation for operation (contraction off): scripts/onoff.py:325-350, TF defaults.
+// ---------------------------------------------------------------------------------------------
+// np.logaddexp(0, x) + 1e-6 (zigp/transforms.py Log1pe.forward; GPflow transforms.positive), branch structure of numpy's logaddexp
+__device__ __forceinline__ double kfit_softplus(double x) {
+#pragma clang fp contract(off)
+  const double sp = x < 0.0 ? log1p(exp(x)) : (x == 0.0 ? 0.6931471805599453 : x + log1p(exp(-x)));
+  return sp + 1e-6;
+}
+struct KfitAdam { double beta1, beta2, eps, lr_sq, lr_den; };   // lr_sq = sqrt(1 - beta2^t), lr_den = 1 - beta1^t: from the host, per step
+// One element: gc = d ELBO / d (constrained value); cost = -ELBO; d value / d x = sigmoid(x) for Log1pe (zigp/transforms.py grad_free)
+__device__ __forceinline__ void kfit_adam(double gc, bool positive, double lr, const KfitAdam& o, double& x, double& m, double& v) {
+#pragma clang fp contract(off)
+  const double g = -(positive ? gc * (0.5 * (1.0 + tanh(0.5 * x))) : gc);
+  const double mnew = o.beta1 * m + (1.0 - o.beta1) * g;
+  const double vnew = o.beta2 * v + (1.0 - o.beta2) * g * g;
+  const double lr_t = lr * o.lr_sq / o.lr_den;
+  x = x - lr_t * mnew / (sqrt(vnew) + o.eps);
+  m = mnew; v = vnew;
+}
+
+// Dense fit loop.  Blocks of the flat free-state vector, in the order of OnOffSVGP._pset (include/zigp.h ZIGP_DENSE_FIT_BLOCKS):
+//   0 Zf  1 Zg  2 u_fm  3 u_gm  4 u_fs_sqrt  5 u_gs_sqrt  6 ell_f  7 ell_g  8 var_f  9 var_g  10 noise
+// off / n: place in the free vector (n[6], n[7] = 1: one lengthscale broadcast over D); goff / gn: where k_dense_pack leaves the block's
+// gradient in the packed result vector, gn entries per element (D for a scalar lengthscale: its gradient is their sum, in d order).
+constexpr int DFIT_BLOCKS = 11, DFIT_THREADS = 256;
+struct DenseFitDesc {
+  int off[DFIT_BLOCKS + 1], n[DFIT_BLOCKS], goff[DFIT_BLOCKS], gn[DFIT_BLOCKS], positive[DFIT_BLOCKS], trainable[DFIT_BLOCKS];
+  double lr[DFIT_BLOCKS];
+  int D, M[2];
+  int img_Z[2], img_ell[2], img_u[2], img_s[2], img_Zs[2];   // offsets of the parameter image (latents_layout, zigp_dense.hip)
+  double beta1, beta2, eps, jitter, rtol_eps;                // rtol_eps = pivot_rtol * DBL_EPSILON (pivot_tol, zigp_host.h)
+};
+__device__ __forceinline__ int dfit_block(const DenseFitDesc& d, int e) {
+  int b = 0;
+#pragma unroll
+  for (int q = 1; q < DFIT_BLOCKS; ++q) b += (e >= d.off[q]) ? 1 : 0;
+  return b;
+}
+__device__ __forceinline__ double dfit_value(const DenseFitDesc& d, int b, double x) { return d.positive[b] ? kfit_softplus(x) : x; }
+
+// Free state -> parameter image: Z, u, s (the padding up to Mp stays zero: the host cleared the image once per call), ell, and
+// Zs = Z (KUF_C (1 / ell_d)) -- the operation order of make_kuf_hyp / latents_upload -- and the hyperparameter block H: 1 / ell, ell, the Kuf
+// scale, var, the pivot tolerance rtol eps (var + jitter), noise.  One element of the image per thread; a Zs element evaluates its
+// lengthscale itself.  Plain vector stores.
+__global__ void __launch_bounds__(DFIT_THREADS)
+k_dense_fit_image(DenseFitDesc d, const double* __restrict__ x, double* __restrict__ img, double* __restrict__ H) {
+#pragma clang fp contract(off)
+  const int e = blockIdx.x * DFIT_THREADS + threadIdx.x;
+  if (e >= d.off[DFIT_BLOCKS]) return;
+  const int b = dfit_block(d, e), i = e - d.off[b];
+  const double val = dfit_value(d, b, x[e]);
+  const int h = b & 1, D = d.D;
+  if (b <= 1) {
+    const int dd = i % D, eb = 6 + h;
+    const double ell = dfit_value(d, eb, x[d.off[eb] + (d.n[eb] == 1 ? 0 : dd)]);
+    img[d.img_Z[h] + i] = val;
+    img[d.img_Zs[h] + i] = val * (KUF_C * (1.0 / ell));
+  } else if (b <= 3) img[d.img_u[h] + i] = val;
+  else if (b <= 5) img[d.img_s[h] + i] = val;
+  else if (b <= 7) {
+    double* R = H + h * DH_LAT;
+    for (int dd = (d.n[b] == 1 ? 0 : i); dd < (d.n[b] == 1 ? D : i + 1); ++dd) {
+      img[d.img_ell[h] + dd] = val;
+      R[DH_ELL + dd] = val; R[DH_INV + dd] = 1.0 / val; R[DH_SCALE + dd] = KUF_C * (1.0 / val);
+    }
+  } else if (b <= 9) {
+    double* R = H + h * DH_LAT;
+    R[DH_VAR] = val; R[DH_PIVTOL] = d.rtol_eps * (val + d.jitter);
+  } else H[DH_NOISE] = val;
+}
+
+// The update: element-wise.  packed = the result vector k_dense_pack assembled for this step (header: data term, KL, d var_f, d var_g,
+// d noise; then per latent dZ, du, ds, dell: gradients w.r.t. the constrained values); info[h] != 0: the Cholesky of latent h failed
+// at that pivot.  A failure in this or an earlier step of the call leaves x, m, v as they are (fail[0] = 1 + step, fail[1] = latent,
+// fail[2] = pivot, written once); blocks with trainable == 0 are left alone, as AdamGroups skips fixed parameters.  The first thread
+// also writes the history entry (the values BEFORE this update).
+struct DenseFitArgs {
+  DenseFitDesc d;
+  double *x, *m, *v;
+  const double* packed;
+  const int* info;     // [2]
+  double* hist;        // [n_steps][2]
+  int* fail;           // [4]
+  int step;
+  double lr_sq, lr_den;
+};
+__global__ void __launch_bounds__(DFIT_THREADS)
+k_dense_fit_update(DenseFitArgs a) {
+  const DenseFitDesc& d = a.d;
+  __shared__ int s_fail;
+  if (threadIdx.x == 0) {
+    int f = a.fail[0];
+    if (f == 0) {
+      const int i0 = a.info[0], i1 = a.info[1];
+      const int bad = i0 != 0 ? 0 : (i1 != 0 ? 1 : -1);
+      if (bad >= 0) { f = 1 + a.step; if (blockIdx.x == 0) { a.fail[1] = bad; a.fail[2] = bad == 0 ? i0 : i1; a.fail[0] = f; } }
+    }
+    s_fail = f;
+  }
+  const int e = blockIdx.x * DFIT_THREADS + threadIdx.x;
+  const bool live = e < d.off[DFIT_BLOCKS];
+  const int b = live ? dfit_block(d, e) : 0, i = live ? e - d.off[b] : 0;
+  double x = 0.0, m = 0.0, v = 0.0, gc = 0.0;
+  if (live && d.trainable[b]) {
+    x = a.x[e]; m = a.m[e]; v = a.v[e];
+    const double* g = a.packed + d.goff[b] + i * d.gn[b];
+    gc = g[0];
+    for (int j = 1; j < d.gn[b]; ++j) gc += g[j];
+  }
+  __syncthreads();
+  if (s_fail) return;
+  if (e == 0) { a.hist[2 * a.step] = a.packed[0]; a.hist[2 * a.step + 1] = a.packed[1]; }
+  if (!live || !d.trainable[b]) return;
+  kfit_adam(gc, d.positive[b] != 0, d.lr[b], KfitAdam{d.beta1, d.beta2, d.eps, a.lr_sq, a.lr_den}, x, m, v);
+  a.x[e] = x; a.m[e] = m; a.v[e] = v;
 }
 
 // s2 = s*s
@@ -1092,8 +1257,13 @@ __device__ __forceinline__ bool potrf_diag_lds(double* S, PotrfShared& psh, int 
   return true;
 }
 
+// TOL = double: the tolerance by value (zigp_elbo, zigp_predict, the diagnostics); const double*: read from the device hyperparameter block
+// (fit loop: it depends on the kernel variance of the step)
+__device__ __forceinline__ double potrf_tol(double tol) { return tol; }
+__device__ __forceinline__ double potrf_tol(const double* tol) { return KF_CONST(tol)[0]; }
+template <class TOL>
 __global__ void __launch_bounds__(1024)
-k_potrf_diag(const double* __restrict__ A, double* __restrict__ L, double* __restrict__ W, int64_t ld, int j0, int* info, int npan, double tol) {
+k_potrf_diag(const double* __restrict__ A, double* __restrict__ L, double* __restrict__ W, int64_t ld, int j0, int* info, int npan, TOL tol) {
   // npan = number of 32-column panels that hold real rows; the rest of the block is identity padding (L = W = I there)
   extern __shared__ double S[];   // [128][129]
   __shared__ PotrfShared psh;
@@ -1103,7 +1273,7 @@ k_potrf_diag(const double* __restrict__ A, double* __restrict__ L, double* __res
     S[i * PBLD + j] = (j <= i) ? A[(int64_t)i * ld + j] : 0.0;
   }
   __syncthreads();
-  if (!potrf_diag_lds(S, psh, j0, info, npan, W != nullptr, tol)) return;
+  if (!potrf_diag_lds(S, psh, j0, info, npan, W != nullptr, potrf_tol(tol))) return;
   if (L) {
     for (int idx = t; idx < PB * PB; idx += 1024) {
       const int i = idx >> 7, j = idx & 127;
@@ -1117,5 +1287,4 @@ k_potrf_diag(const double* __restrict__ A, double* __restrict__ L, double* __res
     }
   }
 }
-
 }  // namespace zigp

@@ -1179,12 +1179,7 @@ struct KfFitArgs {
   int update;                   // 0: only free state -> image (first launch of a call)
 };
 
-// np.logaddexp(0, x) + 1e-6 (zigp/transforms.py Log1pe.forward; GPflow transforms.positive), branch structure of numpy's logaddexp
-__device__ __forceinline__ double kfit_softplus(double x) {
-#pragma clang fp contract(off)
-  const double sp = x < 0.0 ? log1p(exp(x)) : (x == 0.0 ? 0.6931471805599453 : x + log1p(exp(-x)));
-  return sp + 1e-6;
-}
+// kfit_softplus (Log1pe forward) and kfit_adam (the Adam arithmetic) are shared with the dense fit loop: zigp_kernels.h
 __device__ __forceinline__ double kfit_value(const KfFitDesc& d, int b, double x) { return d.positive[b] ? kfit_softplus(x) : x; }
 
 // Thread -> element of the free vector.  Workgroups 0 .. G - 2 walk the big blocks (Z0, Z1, u, s of f, then of g) one element per thread;
@@ -1310,12 +1305,9 @@ k_fit_update(KfFitArgs a) {
     else if (kind <= 3 || kind == 8) gc = gnum;
     else if (kind <= 5) gc = s_dl[h][kind - 4][i] / (aux * aux * aux);
     else gc = s_dv[h][kind - 6] / aux + pws[2 + h] * Ho[(2 * h + 1 - (kind - 6)) * KH_FAC + KH_VAR];   // Knn = var0 var1 enters var_n directly (scripts/onoff.py:196-200)
-    // cost = -ELBO; chain through the transform: d value / d x = sigmoid(x) for Log1pe (zigp/transforms.py)
-    const double g = -(d.positive[b] ? gc * (0.5 * (1.0 + tanh(0.5 * x))) : gc);
-    const double mnew = d.beta1 * mv + (1.0 - d.beta1) * g;
-    const double vnew = d.beta2 * vv + (1.0 - d.beta2) * g * g;
-    const double lr_t = d.lr[b] * a.lr_sq / a.lr_den;
-    const double xnew = x - lr_t * mnew / (sqrt(vnew) + d.eps);
+    // cost = -ELBO, chained through the transform, one Adam step (kfit_adam, zigp_kernels.h)
+    double xnew = x, mnew = mv, vnew = vv;
+    kfit_adam(gc, d.positive[b] != 0, d.lr[b], KfitAdam{d.beta1, d.beta2, d.eps, a.lr_sq, a.lr_den}, xnew, mnew, vnew);
     a.m[e] = mnew; a.v[e] = vnew; a.x[e] = xnew;
     kfit_store_value(a, Hn, b, i, kfit_value(d, b, xnew));
   }

@@ -14,12 +14,13 @@ from collections import OrderedDict
 import numpy as np
 
 import zigp
-from zigp.optim import ParamSet, lbfgsb, AdamGroups
-from zigp.transforms import positive
+from zigp.optim import ParamSet, lbfgsb, AdamGroups, DenseDeviceFit
+from zigp.transforms import positive, Log1pe, Identity
 from .param import Param, DataHolder, Parameterized
 from .mean_functions import MeanFunction, Zero
 
 JITTER = 1e-6   # gpflow settings.numerics.jitter_level default (OnOffSVGP.py:96-97) [GPflow-recall]
+DEVICE_FIT_CALL = 200   # iterations per zigp_fit_steps call of optimize(method='adam'): one synchronisation each
 
 
 class OnOffSVGP(Parameterized):
@@ -79,23 +80,52 @@ class OnOffSVGP(Parameterized):
             out['mean_b'] = np.array([g['mean_b']])
         return out
 
-    def _load_batch(self):
-        """X and Y go to HBM once; a minibatch (MinibatchData, :46-47) is a row-index sample gathered on the device per step."""
-        if not self._resident:
-            self._engine.set_data(self.Xtrain.value, self.Ytrain.value)
-            self._resident = True
+    def _sample_rows(self):
+        """One step's row sample from self._rng (MinibatchData, :46-47), or None for the full batch."""
         if self.minibatch_size >= self.num_data:
-            self._engine.select_rows(None)       # back to the full resident set (a minibatch_size raised after a minibatch step must not leave its last sample active)
-            return 1.0
+            return None
         # GPflow 0.4 MinibatchData picks its index manager by the batch fraction [GPflow-recall; not in the reference tree, unverified]:
         # up to one half sampling WITH replacement (rng.randint), ABOVE one half a fresh permutation's head (without replacement) -- the
         # boundary case of exactly one half goes with randint, as the `fraction > 0.5` test of that recollection says
         if 2 * self.minibatch_size <= self.num_data:
-            idx = self._rng.randint(self.num_data, size=self.minibatch_size)
-        else:
-            idx = self._rng.permutation(self.num_data)[:self.minibatch_size]
+            return self._rng.randint(self.num_data, size=self.minibatch_size)
+        return self._rng.permutation(self.num_data)[:self.minibatch_size]
+
+    def _make_resident(self):
+        if not self._resident:
+            self._engine.set_data(self.Xtrain.value, self.Ytrain.value)
+            self._resident = True
+
+    def _load_batch(self):
+        """X and Y go to HBM once; a minibatch (MinibatchData, :46-47) is a row-index sample gathered on the device per step."""
+        self._make_resident()
+        idx = self._sample_rows()
+        if idx is None:
+            self._engine.select_rows(None)       # back to the full resident set (a minibatch_size raised after a minibatch step must not leave its last sample active)
+            return 1.0
         self._engine.select_rows(idx)
         return float(self.num_data) / float(self.minibatch_size)          # :119-120
+
+    def _device_fit_eligible(self, pset):
+        """the Adam loop can run on the device (zigp_fit_steps): Zero mean function, every transform Identity or Log1pe(1e-6)"""
+        return type(self.mean_function) is Zero and all(
+            type(q.transform) is Identity or (isinstance(q.transform, Log1pe) and q.transform._lower == 1e-6) for q in pset.params.values())
+
+    def _adam_on_device(self, pset, maxiter):
+        """maxiter Adam iterations in calls of at most DEVICE_FIT_CALL: the row samples are drawn from self._rng in the order and by the
+        rule of _load_batch (the run sees the minibatches the host loop would), uploaded once per call and gathered on the device."""
+        self._make_resident()
+        self._engine.select_rows(None)
+        fit = DenseDeviceFit(self._engine, pset)
+        done = 0
+        while done < maxiter:
+            n = min(DEVICE_FIT_CALL, maxiter - done)
+            if self.minibatch_size >= self.num_data:
+                fit.steps(None, 0, JITTER, 1.0, n_steps=n)
+            else:
+                rows = np.stack([self._sample_rows() for _ in range(n)])
+                fit.steps(rows, self.minibatch_size, JITTER, float(self.num_data) / float(self.minibatch_size))
+            done += n
 
     def _elbo(self, need_grad):
         scale = self._load_batch()
@@ -118,7 +148,9 @@ class OnOffSVGP(Parameterized):
 
     def optimize(self, method='L-BFGS-B', maxiter=1000, disp=False, callback=None, learning_rate=0.01, **kw):
         """GPflow Model.optimize: scipy L-BFGS-B on the free state (default), or Adam when method='adam'
-        (the commented alternative at zero-inflated-gpflow.ipynb:155)."""
+        (the commented alternative at zero-inflated-gpflow.ipynb:155).  Adam without a callback runs its loop on the device
+        (zigp_fit_steps, DEVICE_FIT_CALL iterations per call) when the mean function is Zero; with a callback, or a mean function, every
+        iteration is a host step (select_rows + elbo + AdamGroups) -- the same minibatches and, to rounding, the same trajectory."""
         pset = self._pset()
 
         def vg(_values):
@@ -129,6 +161,9 @@ class OnOffSVGP(Parameterized):
         if str(method).lower() == 'adam':
             for p in pset.params.values():
                 p.learning_rate = learning_rate
+            if callback is None and self._device_fit_eligible(pset):      # the whole loop on the device; a callback wants the host every step
+                self._adam_on_device(pset, maxiter)
+                return None
             opt = AdamGroups(pset)
             for it in range(maxiter):
                 elbo, g = self._elbo(True)

@@ -66,6 +66,14 @@ class zigp_kron_fit_opts(C.Structure):
                 ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double)]
 
 
+DENSE_FIT_BLOCKS = 11   # include/zigp.h ZIGP_DENSE_FIT_BLOCKS
+
+
+class zigp_fit_opts(C.Structure):
+    _fields_ = [('lr', C.c_double * DENSE_FIT_BLOCKS), ('positive', C.c_int32 * DENSE_FIT_BLOCKS), ('trainable', C.c_int32 * DENSE_FIT_BLOCKS),
+                ('ell_size_f', C.c_int32), ('ell_size_g', C.c_int32), ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double)]
+
+
 class zigp_stage_latent(C.Structure):   # include/zigp_diag.h
     _fields_ = [('M', C.c_int32), ('reserved', C.c_int32), ('W', dp), ('v', dp), ('s2', dp), ('K', dp), ('Rt', dp),
                 ('A1', dp), ('Jp', dp), ('part', dp)]
@@ -97,6 +105,9 @@ SIGNATURES = {
     'zigp_select_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     'zigp_elbo': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int64,
                             C.c_int32, dp, dp, C.POINTER(zigp_grads)]),
+    'zigp_fit_steps': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.POINTER(zigp_fit_opts), dp, dp, dp, C.c_int64, C.c_int64, C.c_int32,
+                                 C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int32, dp, dp]),
+    'zigp_fit_steps_applied': (C.c_int64, [C.c_void_p]),
     'zigp_predict': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), dp, C.c_int64, C.c_double, C.c_double, dp]),
     'zigp_predict_device': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p]),
     'zigp_prior_kl': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_double, dp]),

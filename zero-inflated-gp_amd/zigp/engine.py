@@ -291,6 +291,45 @@ class DenseEngine:
                 g['mean_a'], g['mean_b'] = da[:mean_D], db.value
         return ed.value, kl.value, g
 
+    def fit_steps(self, shape, x, m, v, lr, positive, trainable, ell_size, t0, n_steps, rows=None, batch=0, jitter=1e-6, scale=1.0,
+                  beta1=0.9, beta2=0.999, eps=1e-8, include_kl=True):
+        """n_steps Adam iterations of the dense on/off fit ON THE DEVICE (zigp_fit_steps; a minibatch step of OnOffSVGP, onoffgpf/
+        OnOffSVGP.py:42-47,107-122, and its Adam update): one synchronisation for the whole call.
+        shape: dict(Mf, Mg, D); x, m, v: float64 [n_free] free state and Adam moments, UPDATED IN PLACE, in the block order PARAM_KEYS
+        (include/zigp.h); lr, positive, trainable: 11 per-block learning rates / Log1pe flags / trainable flags; ell_size = (f, g): 1 (one
+        lengthscale for all columns) or D; t0: iterations done so far; rows: int64 [n_steps * batch] indices into the resident data set,
+        step i uses rows[i * batch : (i + 1) * batch] -- None: every step uses the active rows (full-batch Adam).
+        Returns (elbo_data[n_steps], kl[n_steps]) -- the history, each at the parameters before that step's update."""
+        s = _lib.zigp_params()
+        s.Mf, s.Mg, s.D = int(shape['Mf']), int(shape['Mg']), int(shape['D'])
+        o = _lib.zigp_fit_opts()
+        for b in range(_lib.DENSE_FIT_BLOCKS):
+            o.lr[b] = float(lr[b]); o.positive[b] = int(bool(positive[b])); o.trainable[b] = int(bool(trainable[b]))
+        o.ell_size_f, o.ell_size_g = int(ell_size[0]), int(ell_size[1])
+        o.beta1, o.beta2, o.eps = float(beta1), float(beta2), float(eps)
+        for a in (x, m, v):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.ndim == 1 and a.size == x.size):
+                raise ValueError('x, m, v must be contiguous float64 vectors of one length')
+        n = int(n_steps)
+        rp = None
+        if rows is not None:
+            rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64)).reshape(-1)
+            if int(batch) <= 0 or rows.size != n * int(batch):
+                raise ValueError('rows must hold n_steps * batch indices')
+            rp = rows.ctypes.data
+        ed, kl = np.zeros(max(n, 0)), np.zeros(max(n, 0))
+        rc = self.lib.zigp_fit_steps(self.ctx, C.byref(s), C.byref(o), ptr(x), ptr(m), ptr(v), x.size, int(t0), n, rp, int(batch), float(jitter),
+                                     float(scale), 1 if include_kl else 0, ptr(ed), ptr(kl))
+        try:
+            _check(self.lib, self.ctx, rc)
+        except ZigpError as e:
+            # as kron_fit_steps: x / m / v hold the state after the updates that WERE applied; the count comes from the library
+            done = max(0, min(n, int(self.lib.zigp_fit_steps_applied(self.ctx))))
+            e.steps_applied = done
+            e.elbo_data, e.kl = ed[:done].copy(), kl[:done].copy()
+            raise
+        return ed, kl
+
     def _set_mean_function(self, p, D):
         """p may carry the mean function of f, m(x) = mean_b + mean_a . x (OnOffSVGP.py:29,134): 'mean_b' alone is GPflow's
         Constant, 'mean_a' (+ 'mean_b') its Linear; neither is Zero.  Returns len(mean_a) when one is set, else None."""

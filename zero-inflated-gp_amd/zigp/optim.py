@@ -5,6 +5,8 @@
 * `lbfgsb` is GPflow 0.4.0 Model.optimize's default (scipy.optimize.minimize(method='L-BFGS-B', jac=True)).
 * `AdamGroups` reproduces scripts/onoff.py:325-350: one tf.train.AdamOptimizer per distinct learning
   rate (TF defaults beta1=0.9, beta2=0.999, eps=1e-8; update lr_t = lr*sqrt(1-b2^t)/(1-b1^t)).
+* `DenseDeviceFit` keeps the same Adam state in the layout of zigp_fit_steps and advances it on the device
+  (the dense counterpart of onofftf.model.KronDeviceFit); `AdamGroups` is its host-side checker.
 """
 import numpy as np
 
@@ -123,3 +125,106 @@ class AdamGroups:
             self.x[k] = x - lr_t * self.m[k] / (np.sqrt(self.v[k]) + self.eps)
             p.set_free(self.x[k])
             self._written[k] = p.value.copy()
+
+
+# block order of zigp_fit_steps' free-state vector (include/zigp.h): the order of OnOffSVGP._pset / zigp.engine.PARAM_KEYS
+DENSE_FIT_KEYS = ('Zf', 'Zg', 'u_fm', 'u_gm', 'u_fs_sqrt', 'u_gs_sqrt', 'ell_f', 'ell_g', 'var_f', 'var_g', 'noise')
+
+
+class DenseDeviceFit:
+    """The Adam state of the dense on/off fit in the layout of zigp_fit_steps, for a ParamSet with the keys DENSE_FIT_KEYS (the one
+    OnOffSVGP._pset builds for a Zero mean function): the flat free state x and the moments m, v live here between calls (the engine
+    updates them in place), `steps` advances them on the device and writes the constrained values back into the ParamSet.
+    A fixed parameter is a block with trainable = 0: the device leaves its x, m, v alone and its .value is never written back (on the
+    device it is the transform of its free value: for a fixed Log1pe parameter that is forward(backward(value)), equal to the value to
+    rounding).  A lengthscale Param with one entry is ONE lengthscale for all D columns (ell_size = 1).  AdamGroups on the same ParamSet
+    is the host-side checker."""
+
+    def __init__(self, engine, pset, beta1=0.9, beta2=0.999, eps=1e-8):
+        from .transforms import Log1pe
+        self.engine, self.pset = engine, pset
+        self.beta1, self.beta2, self.eps = beta1, beta2, eps
+        extra = [k for k in pset.params if k not in DENSE_FIT_KEYS]
+        if extra or any(k not in pset.params for k in DENSE_FIT_KEYS):
+            raise ValueError('the dense device fit loop trains exactly %s (got also / not: %s): mean-function parameters stay with the host loop'
+                             % (', '.join(DENSE_FIT_KEYS), ', '.join(extra) or 'a key is missing'))
+        ps = [pset.params[k] for k in DENSE_FIT_KEYS]
+        for q in ps:
+            if not isinstance(q.transform, Log1pe) and type(q.transform).__name__ != 'Identity':
+                raise ValueError('unsupported transform %r' % (q.transform,))
+            if isinstance(q.transform, Log1pe) and q.transform._lower != 1e-6:
+                raise ValueError('the device fit loop implements Log1pe with lower = 1e-6')
+        Zf, Zg = ps[0].value, ps[1].value
+        if Zf.ndim != 2 or Zg.ndim != 2 or Zf.shape[1] != Zg.shape[1]:
+            raise ValueError('Zf and Zg must be (M,D) with equal D')
+        D = Zf.shape[1]
+        self.shape = dict(Mf=Zf.shape[0], Mg=Zg.shape[0], D=D)
+        self.sizes = [q.value.size for q in ps]
+        want = [Zf.size, Zg.size, Zf.shape[0], Zg.shape[0], Zf.shape[0], Zg.shape[0], None, None, 1, 1, 1]
+        for k, n, w in zip(DENSE_FIT_KEYS, self.sizes, want):
+            if (w is None and n not in (1, D)) or (w is not None and n != w):
+                raise ValueError('%s has %d entries' % (k, n))
+        self.ell_size = (self.sizes[6], self.sizes[7])
+        self.positive = [isinstance(q.transform, Log1pe) for q in ps]
+        self.m, self.v = np.zeros(sum(self.sizes)), np.zeros(sum(self.sizes))
+        self.t = 0
+        self.resync()
+
+    def _blocks(self):
+        o = 0
+        for k, n in zip(DENSE_FIT_KEYS, self.sizes):
+            yield k, self.pset.params[k], slice(o, o + n)
+            o += n
+
+    def steps(self, rows, batch, jitter, scale, n_steps=None, include_kl=True):
+        """Iterations on the resident data set (engine.set_data): rows = int64 [n_steps, batch] row indices, one row of it per step, or None
+        for n_steps iterations over the active rows (full batch).  Returns (elbo_data, kl) per step; the ParamSet holds the constrained
+        values after the last one.  If the engine raises in step k (a Cholesky failure), x / m / v are the state after the k updates that
+        WERE applied, self.t has advanced by k, and the exception carries `steps_applied`, `elbo_data`, `kl` of those steps.  The ParamSet
+        is read again when something other than this object changed it since the last call (an assignment to .value, a parameter fixed
+        or un-fixed, a new learning rate): see resync()."""
+        if rows is not None:
+            rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64)).reshape(-1)
+            if int(batch) <= 0 or rows.size % int(batch) or (n_steps is not None and rows.size != int(n_steps) * int(batch)):
+                raise ValueError('rows must hold whole steps of `batch` indices')
+            n_steps = rows.size // int(batch)
+        elif n_steps is None:
+            raise ValueError('full-batch steps (rows=None) need n_steps')
+        if self._stale():
+            self.resync()
+        try:
+            out = self.engine.fit_steps(self.shape, self.x, self.m, self.v, self.lr, self.positive, self.trainable, self.ell_size, self.t, n_steps,
+                                        rows=rows, batch=batch, jitter=jitter, scale=scale, beta1=self.beta1, beta2=self.beta2, eps=self.eps,
+                                        include_kl=include_kl)
+            self.t += int(n_steps)
+        except Exception as e:
+            self.t += int(getattr(e, 'steps_applied', 0))
+            raise
+        finally:
+            self.sync_params()
+        return out
+
+    def _stale(self):
+        """did anyone else write the ParamSet since sync_params?  equal_nan: a parameter that HAS gone NaN is still the value this object
+        wrote (NaN != NaN must not turn every later call into a resync from free(NaN))"""
+        return (any(not np.array_equal(q.value, w, equal_nan=True) for (k, q, sl), w in zip(self._blocks(), self._written))
+                or [not q.fixed for k, q, sl in self._blocks()] != self.trainable
+                or [float(q.learning_rate) for k, q, sl in self._blocks()] != self.lr)
+
+    def resync(self, reset=False):
+        """Take the free state, the fixed flags and the learning rates from the ParamSet again.  Adam's moments and the iteration count
+        are kept unless reset=True (parameters unrelated to the ones trained so far)."""
+        self.x = np.concatenate([q.free() for k, q, sl in self._blocks()])
+        self.trainable = [not q.fixed for k, q, sl in self._blocks()]
+        self.lr = [float(q.learning_rate) for k, q, sl in self._blocks()]
+        if reset:
+            self.m[:] = 0.0
+            self.v[:] = 0.0
+            self.t = 0
+        self._written = [q.value.copy() for k, q, sl in self._blocks()]
+
+    def sync_params(self):
+        for (k, q, sl), tr in zip(self._blocks(), self.trainable):
+            if tr:
+                q.set_free(self.x[sl])
+        self._written = [q.value.copy() for k, q, sl in self._blocks()]
