@@ -132,7 +132,8 @@ int zigp_elbo(zigp_ctx* ctx, const zigp_params* p, double jitter, double scale, 
  * before it HAVE been applied (zigp_fit_steps_applied returns k) -- the history entries from step k on are NaN, and zigp_last_error names
  * the step and the latent.  The steps enqueued behind a failed one still run (at most n_steps - k wasted steps); their updates are skipped.
  * ZIGP_EARG: NULL arguments or bad sizes, n_free not the model's, a row index out of range, more than 1 GiB of row indices, a mean
- * function set on the context (its parameters stay with zigp_elbo and a host optimiser) or a communicator attached (zigp_comm_init). */
+ * function set on the context (its parameters stay with zigp_elbo and a host optimiser), whitening switched on (zigp_set_whiten) or a
+ * communicator attached (zigp_comm_init). */
 #define ZIGP_DENSE_FIT_BLOCKS 11
 typedef struct {
   double lr[ZIGP_DENSE_FIT_BLOCKS];          /* Adam learning rate of each block */
@@ -251,6 +252,21 @@ int64_t zigp_kron_fit_steps_applied(zigp_ctx* ctx);
  * sum under data-parallel use. */
 int zigp_set_mean_function(zigp_ctx* ctx, const double* a, int32_t D, double b);
 int zigp_get_mean_function_grad(zigp_ctx* ctx, double* da, int32_t D, double* db);
+
+/* Whitened variational parametrisation of the DENSE path (the reference's `whiten` switch: gauss_kl_white_diag in build_prior_KL,
+ * onoffgpf/OnOffSVGP.py:88-91; whiten=self.whiten into the conditional, :133,137; GPConditional(whiten=True) skips the second
+ * back-substitution, onofftf/main.py:282-284; GaussKL(q_mu, q_sqrt, K=None), :193-195,227-228,246).  With on = 1, u_*m and u_*s_sqrt in
+ * zigp_params, and the matching blocks of zigp_grads, are the whitened quantities: q(u) = N(L u_m, L diag(u_s_sqrt^2) L^T) with
+ * L = chol(Kuu + jitter I), so that
+ *   mean = A^T u_m (+ mean function for f),  var = k** + sum_m (u_s_sqrt_m^2 - 1) A_mn^2,  A = L^-1 Kuf,
+ *   KL   = 0.5 (sum u_m^2 + sum u_s_sqrt^2 - M - sum log u_s_sqrt^2)   per latent.
+ * zigp_elbo (value-only, gradient, include_kl 0 / 1, row ranges, zigp_select_rows), zigp_predict, zigp_predict_device and zigp_prior_kl
+ * follow the setting; mean functions, g_offset, scale, the chunk rule and the data-parallel exchange work as without it.  The setting
+ * persists in the context like zigp_set_mean_function and is off after zigp_create.  zigp_fit_steps returns ZIGP_EARG while it is on (the
+ * device loop fits the unwhitened parametrisation only); the Kronecker entry points ignore it (the reference raises NotImplementedError
+ * there, scripts/onoff.py:145-146).  zigp_get_whiten returns 0 / 1, or ZIGP_EARG for a NULL context. */
+int zigp_set_whiten(zigp_ctx* ctx, int32_t on);
+int zigp_get_whiten(zigp_ctx* ctx);
 
 /* Single-latent heads on the same Kronecker conditional -- the reference's baselines, which re-use kron_inf and
  * GaussKLkron with one latent f:

@@ -18,7 +18,10 @@ extern "C" {
  * 3 gemm_J   J' = Q A2 = (Q W^T) A1    gemm_f64_kernel<1,1,2,false,0,8,EpiStorePanelKColsum>  (one full product on the A1 panel; fused
  *                                      sum_m K J' = sum s^2 A2^2 - sum A1^2, the variance term of a gradient step)
  * 4 syrk     C1 += A1 G A1^T           gemm_f64_kernel<0,0,2,true,3,4,EpiAccum>
- * 5 kuf_build   6 pointwise   7 kgrad   8 MxM stage (all kernels)   9 everything else. */
+ * 5 kuf_build   6 pointwise   7 kgrad   8 MxM stage (all kernels)   9 everything else.
+ * Whitened calls (zigp_set_whiten) book their launches in the same classes: 0 gemm_A1  A = W K with the weights u and s^2 - 1
+ * (<1,1,2,false,1,8,EpiStoreColsum> in a gradient step, <1,1,2,false,1,8,EpiColsum> -- no panel stored -- otherwise), 3 gemm_J
+ * J' = (W^T D) A, gemm_f64_kernel<1,1,2,false,2,8,EpiStore>, with M^2 Nc flops per latent; class 1 is not launched. */
 #define ZIGP_NCLASS 10
 int zigp_profile_enable(zigp_ctx* ctx, int32_t on);
 int zigp_profile_get(zigp_ctx* ctx, double* ms /*[ZIGP_NCLASS]*/, int64_t* launches /*[ZIGP_NCLASS]*/,
@@ -117,6 +120,18 @@ int zigp_test_kgrad(zigp_ctx* ctx, int32_t M, int32_t D, int64_t Nc, int64_t Nro
  * plane reduction.  A1[i] (M,Nc[i]), gv[i] (Nc[i]), Nc[i] multiples of 1024.  C1 (M,M) symmetric; plan[2] = {So, Sd}. */
 int zigp_test_rank_update(zigp_ctx* ctx, int32_t M, int32_t nchunks, const int64_t* Nc, const double* const* A1, const double* const* gv,
                           double* C1, int64_t* plan /*[2]*/);
+
+/* ---- whitened parametrisation (zigp_set_whiten): the stages that differ, through chunk_forward_white and the point-wise launch of a
+ * whitened call.  The structs are the ones above, read as follows. ---- */
+/* Forward products of one whitened chunk.  zigp_stage_latent: W as above; v = the weights of the mean sum (u); s2 = the weights of the
+ * variance sum (s^2 - 1; any sign); K as above; Rt (M,M) = what the J' launch reads as its factor, the image D W (row k of W scaled by
+ * s_k^2 - 1), zero padded, so that J' = Rt^T A.  need_grad = 0: the launch A = W K alone, with the non-storing epilogue -- A1 is not
+ * written and may be NULL; need_grad = 1: A (stored to A1) and J' = (W^T D) A (stored to Jp).  part [3][Mp/32][Nc]: plane 0 = partial
+ * rows of sum_m v_m A_mn, plane 2 = of sum_m s2_m A_mn^2, plane 1 is not written (sentinel).  only and facts as zigp_test_chunk_forward. */
+int zigp_test_chunk_forward_white(zigp_ctx* ctx, int64_t Nc, int32_t need_grad, int32_t only, const zigp_stage_latent* lat /*[2]*/, int64_t* facts /*[12]*/);
+/* The point-wise stage as a whitened call launches it: in every mode mean = sum of plane 0 (np1 rows), var = var_* + sum of plane 2 (np2
+ * rows); plane 1 is not read.  Arguments as zigp_test_pointwise. */
+int zigp_test_pointwise_white(zigp_ctx* ctx, const zigp_stage_pointwise* a);
 
 #ifdef __cplusplus
 }

@@ -76,6 +76,7 @@ struct Latent {
   DevBuf T1, T2, T3, G;                  // MxM scratch
   DevBuf sk;                             // [S][Mp*Mp] split-K planes of the O(M^3) products of the reverse pass
   DevBuf vec;                            // small vectors: v=W u [Mp], alpha [Mp], dkinv [Mp], scal[8]
+  DevBuf wh;                             // whitened calls (k_kl_white): s^2 - 1 [Mp], u [Mp], 1 [Mp], KL -- vec's layout as k_dense_pack reads it
 };
 
 struct KronState;   // Kronecker-path buffers (zigp_kron.hip)
@@ -160,6 +161,7 @@ struct zigp_ctx : zigp::CtxHandles {
   bool trmm_tail = true;                // merged triangular launches: re-deal the last, partly filled wave (trmm_tiles, zigp_host.h); env ZIGP_TRMM_TAIL=0 turns it off
   int overlap = 1;                      // zigp_set_overlap: 1 (default) = HBM-bound side kernels of a chunk on stream2 under its SYRKs
   bool mean_on = false;
+  bool whiten = false;                  // zigp_set_whiten: u_*m / u_*s_sqrt are the whitened quantities, q(u) = N(L u, L diag(s^2) L^T)
   double mean_a[8] = {0}, mean_b = 0.0, mean_da[8] = {0}, mean_db = 0.0;   // 8 = zigp::MAXD (zigp_kernels.h)
   zigp::DevBuf out9;                    // predict outputs (9,Nc)
   zigp::DevBuf scratch, scratch2;       // misc

@@ -17,6 +17,17 @@
 //               gv-weighted symmetric rank-N update C1 (gv applied as a k-scale inside the GEMM core, split-K,
 //               fixed order) replaces the two rank-N updates of the literal reverse pass; the rest is O(M^3).
 //   MxM stage   Kuu-bar = sym(W^T Phi(L^T dL) W) - dKL/dKuu ; -> dZ, dell, dvar        (Cholesky reverse, Murray 2016 / TF CholeskyGrad)
+//
+// Whitened parametrisation (zigp_set_whiten; GPConditional(whiten=True) skips the second back-substitution, main.py:282-284, and the white
+// GaussKL has no Kuu, :193-195,227-228,246; OnOffSVGP.py:88-91,133,137).  q(u) = N(L u, L diag(s^2) L^T), D = diag(s^2 - 1), A = W K:
+//   per chunk   A = W K with column sums  mean = sum_m u A ,  var = var0 + sum_m (s^2 - 1) A^2 : ONE triangular product (2 M^2 N), whose
+//               panel has no reader in a value-only / predict pass (EpiColsum: never stored)
+//               point-wise stage (needs the A launch only)
+//               gradient step:  J' = (W^T D) A  (upper-triangular product, M^2 N) ;  F = dK = alpha gm^T + 2 J' G , alpha = W^T u  (k_kgrad
+//               as it is) ;  C1 = A G A^T (the rank-N update as it is): 6 M^2 N flops per step instead of 8
+//   MxM stage   du = W (K gm) - u ;  ds = 2 s diag(C1) - s + 1/s ;  dL = -tril(alpha (A gm)^T + 2 (W^T D) C1) ;  Kuu-bar = sym(W^T Phi(L^T dL) W)
+//               (no P, Q, R, T, U, V; the KL adds nothing to Kuu-bar)
+// The branch is taken on the host alone: an unwhitened call launches exactly what it launched before the mode existed.
 #include "zigp_ctx.h"
 #include "zigp_kernels.h"
 #include "zigp_host.h"
@@ -82,6 +93,7 @@ int latents_views(zigp_ctx* c, const size_t (&off)[2][6], int D) {
     ZIGP_ENSURE(c, lt.W, Mp * Mp);
     ZIGP_ENSURE(c, lt.T1, Mp * Mp);
     ZIGP_ENSURE(c, lt.vec, 4 * Mp + 8);
+    ZIGP_ENSURE(c, lt.wh, 4 * Mp + 8);
     ZIGP_ENSURE(c, lt.Wp, Mp * Mp);
     ZIGP_ENSURE(c, lt.Wt, Mp * Mp);
     ZIGP_ENSURE(c, lt.P, Mp * Mp); ZIGP_ENSURE(c, lt.Qt, Mp * Mp); ZIGP_ENSURE(c, lt.Rt, Mp * Mp);
@@ -116,8 +128,10 @@ int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D) {
 // from the start (see potrf_trtri_jobs).
 // d_hyp (fit loop, zigp_fit_steps): the hyperparameters and the pivot tolerances come from this device block (zigp_kernels.h, DH_*), hl
 // carries the sizes only, and latent h reports a failed factorisation in d_info2[h].
+// whiten: W^T, alpha = W^T u (gradient steps), the white KL and the call's whitened vectors (k_kl_white -> Latent::wh) and, for gradient
+// steps, D W = diag(s^2 - 1) W in `Wp`, the factor image of J' = (W^T D) A and of the reverse stage's (W^T D) C1; no v, P, Q or R.
 int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter, bool with_kl, bool need_grad, const double* d_hyp = nullptr,
-                    int* d_info2 = nullptr) {
+                    int* d_info2 = nullptr, bool whiten = false) {
   const hipStream_t st[2] = {c->stream_main, c->stream2};
   for (int h = 0; h < 2; ++h) {
     Latent& lt = c->lat[h];
@@ -150,6 +164,17 @@ int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter
       OnStream on(c, st[h]);
       if (step == 0) lt.P_ready = false;
       double* v = lt.vec.p; double* alpha = v + Mp; double* dkinv = v + 2 * Mp; double* klv = v + 3 * Mp;
+      if (whiten) {
+        switch (step) {
+          case 0: hipLaunchKernelGGL(k_transpose, dim3(Mp / 32, Mp / 32), dim3(32, 8), 0, c->stream, lt.W.p, (int64_t)Mp, lt.Wt.p); break;
+          case 1: hipLaunchKernelGGL(k_kl_white, dim3(1), dim3(256), 0, c->stream, lt.u.p, lt.s.p, lt.M, (int64_t)Mp, lt.wh.p); break;
+          case 2: if (need_grad) hipLaunchKernelGGL(k_gemv_cols, dim3(Mp / 64), dim3(64, COL_LANES), 0, c->stream, lt.W.p, lt.u.p, (int64_t)Mp, alpha); break;
+          case 3: if (need_grad) hipLaunchKernelGGL(k_rowscale, dim3(ceil_div((int64_t)Mp * Mp, 256)), dim3(256), 0, c->stream, lt.W.p, lt.wh.p, (int64_t)Mp, lt.Wp.p); break;
+          default: break;
+        }
+        ZIGP_HIP(c, hipGetLastError());
+        continue;
+      }
       switch (step) {
         case 0:   // W^T: the m-contiguous image of the factor that the lower-triangular product A1 = W K reads
           hipLaunchKernelGGL(k_transpose, dim3(Mp / 32, Mp / 32), dim3(32, 8), 0, c->stream, lt.W.p, (int64_t)Mp, lt.Wt.p);
@@ -222,7 +247,9 @@ struct ChunkPlan {
   TrmmTail tail = {{0, 0}, {64, 64}};
   struct Lat { TileSpec a1_spec, a2j_spec, syr_spec; TileList a1, a2j, syr; double fl = 0.0; } lat[2];   // a2j: A2 or J'; fl = M^2 Nc
 };
-ChunkPlan chunk_plan(const int (&M)[2], int64_t Nc, bool need_grad, bool tail_on) {
+// whiten: A = W K is the same lower-triangular list; a gradient step adds the UPPER-triangular J' = (W^T D) A (the paired / tail lists of
+// A2) and the rank-N update, a value-only or predict pass has no second product at all (a2j stays empty).
+ChunkPlan chunk_plan(const int (&M)[2], int64_t Nc, bool need_grad, bool tail_on, bool whiten = false) {
   ChunkPlan pl;
   const int nbm[2] = {ceil_div(M[0], BM), ceil_div(M[1], BM)}, nbn = (int)(Nc / BN);
   pl.Nc = Nc;
@@ -232,7 +259,12 @@ ChunkPlan chunk_plan(const int (&M)[2], int64_t Nc, bool need_grad, bool tail_on
   for (int h = 0; h < 2; ++h) {
     ChunkPlan::Lat& L = pl.lat[h];
     L.a1_spec = trmm_tiles(true, nbm[h], nbn, pl.paired, pl.tail.units[h], pl.tail.bins[h]);
-    if (need_grad) {
+    if (whiten) {
+      if (need_grad) {
+        L.a2j_spec = trmm_tiles(false, nbm[h], nbn, pl.paired, pl.tail.units[h], pl.tail.bins[h]);
+        L.syr_spec = syr2k_tiles(nbm[h], (int)(Nc / BK), syr_plan(nbm[h]));
+      }
+    } else if (need_grad) {
       L.a2j_spec = full_xcd_tiles(nbm[h], nbn, nbm[h] * (BM / BK));
       L.syr_spec = syr2k_tiles(nbm[h], (int)(Nc / BK), syr_plan(nbm[h]));
     } else L.a2j_spec = trmm_tiles(false, nbm[h], nbn, pl.paired, pl.tail.units[h], pl.tail.bins[h]);
@@ -243,7 +275,7 @@ ChunkPlan chunk_plan(const int (&M)[2], int64_t Nc, bool need_grad, bool tail_on
 int upload_plan(zigp_ctx* c, ChunkPlan& pl) {
   for (ChunkPlan::Lat& L : pl.lat) {
     ZIGP_TRY(get_tiles(c, L.a1_spec, L.a1));
-    ZIGP_TRY(get_tiles(c, L.a2j_spec, L.a2j));
+    if (L.a2j_spec.build) ZIGP_TRY(get_tiles(c, L.a2j_spec, L.a2j));
     if (L.syr_spec.build) ZIGP_TRY(get_tiles(c, L.syr_spec, L.syr));
   }
   return 0;
@@ -296,6 +328,47 @@ int chunk_forward(zigp_ctx* c, const ChunkPlan& pl, bool need_grad, const std::f
       ProfScope ps(c, PC_GEMM_A2, x.fl + y.fl);
       ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false, TRI_A_UPPER>(c, x.t2, x.a2j, x.e2, y.t2, y.a2j, y.e2)));
     }
+  }
+  return 0;
+}
+
+// Whitened forward products of one chunk, in two parts around the point-wise stage (which needs part A alone).
+// Part A: A = W K, the lower-triangular merged launch of the unwhitened path with the epilogue weights w1 = u, w2 = s^2 - 1 (Latent::wh; 0 for
+// rows m >= M): plane 0 = sum_m u A (the mean, A^T u: main.py:287 without the back-substitution of :284), plane 2 = sum_m (s^2 - 1) A^2 (the
+// variance's data-dependent part, :278 + :302) -- plane 2, not 1, so that the point-wise stage is k_pointwise's var = var0 + (plane 2) form.
+// A gradient step stores the panel (J', the rank-N update read it); a value-only or predict pass has no reader for it and instantiates the
+// same kernel with the non-storing EpiColsum: no A panel is written or even allocated there.
+// Part J (gradient steps): J' = (W^T D) A -- run_gemm<TRI_A_UPPER> on the paired / tail lists of A2, the factor image D W from the M x M
+// forward, a plain panel-storing epilogue (the variance needs nothing from it): M^2 Nc flops per latent, half of the unwhitened J'.
+int chunk_forward_white(zigp_ctx* c, const ChunkPlan& pl, bool need_grad, bool part_j, const std::function<int()>& after_a = nullptr) {
+  const int64_t Nc = pl.Nc;
+  struct Set { TileList t; double fl; GemmArgs g; EpiStoreColsum es; EpiColsum ec; } q[3] = {};   // q[2]: none
+  for (int h = 0; h < 2; ++h) {
+    Latent& lt = c->lat[h];
+    const int Mp = lt.Mp, np = Mp / 32;
+    double* p0 = lt.part.p; double* p2 = lt.part.p + (size_t)2 * np * Nc;
+    q[h].fl = pl.lat[h].fl;
+    if (part_j) { q[h].t = pl.lat[h].a2j; q[h].g = mk_args(lt.Wp.p, Mp, lt.A1.p, Nc, lt.Jp.p, Nc); continue; }
+    q[h].t = pl.lat[h].a1;
+    q[h].g = mk_args(lt.Wt.p, Mp, lt.K.p, Nc, need_grad ? lt.A1.p : nullptr, Nc);
+    q[h].es = EpiStoreColsum{lt.wh.p + Mp, lt.wh.p, p0, p2};
+    q[h].ec = EpiColsum{lt.wh.p + Mp, lt.wh.p, p0, p2};
+  }
+  const int groups = pl.paired ? 1 : 2;      // launch groups: merged {f, g}; LPT {f} then {g}
+  for (int gi = 0; gi < groups; ++gi) {
+    const Set& x = q[gi];
+    const Set& y = q[pl.paired ? 1 : 2];
+    if (part_j) {
+      ProfScope ps(c, PC_GEMM_J, x.fl + y.fl);
+      ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false, TRI_A_UPPER>(c, x.t, x.g, EpiStore(), y.t, y.g, EpiStore())));
+      continue;
+    }
+    {
+      ProfScope ps(c, PC_GEMM_A1, x.fl + y.fl);
+      if (need_grad) ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false, TRI_A_LOWER>(c, x.t, x.g, x.es, y.t, y.g, y.es)));
+      else ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false, TRI_A_LOWER>(c, x.t, x.g, x.ec, y.t, y.g, y.ec)));
+    }
+    if (gi == groups - 1 && after_a) ZIGP_TRY(after_a());     // the Kuf panels have had their only reader of a value-only / predict pass
   }
   return 0;
 }
@@ -411,6 +484,47 @@ int latent_mxm_backward(zigp_ctx* c, Latent& lt, int D, double jitter, bool with
   return 0;
 }
 
+// MxM backward of a whitened call.  The single triangular solve A = W K leaves  dL = -tril(W^T dA A^T)  with  dA = u gm^T + 2 D A G, i.e.
+//   dL = -tril(alpha (A gm)^T + 2 (W^T D) C1),   C1 = A G A^T (the summed planes of the rank-N updates),  alpha = W^T u,
+// so ONE split-K product (W^T D) C1 replaces the T / U / V / Y chain of the unwhitened stage; then the same Phi / T / S chain, and
+// k_sym_combine without a KL part (the white KL does not depend on Kuu).  du's data part is A gm = W (K gm), ds's is diag(C1);
+// k_dense_pack adds the KL parts from Latent::wh.
+int latent_mxm_backward_white(zigp_ctx* c, Latent& lt, int D, double jitter, bool with_data) {
+  const int Mp = lt.Mp, nb = Mp / BM, kb = BM / BK;
+  const size_t mm = (size_t)Mp * Mp;
+  ZIGP_ENSURE(c, lt.T1, mm); ZIGP_ENSURE(c, lt.T2, mm); ZIGP_ENSURE(c, lt.T3, mm);
+  const int gridmm = ceil_div((int64_t)mm, 256);
+  if (with_data) {
+    {
+      double* kgm = lt.vec.p + 3 * Mp + 8;
+      hipLaunchKernelGGL(k_gather, dim3(ceil_div(Mp, 256)), dim3(256), 0, c->stream, lt.krow.p, 2 + 2 * D, 1 + 2 * D, Mp, KG_SPLIT,
+                         (int64_t)Mp * (2 + 2 * D), kgm);
+      hipLaunchKernelGGL(k_gemv_rows, dim3(Mp), dim3(256), 0, c->stream, lt.W.p, kgm, (int64_t)Mp, lt.a1gm.p);
+    }
+    latent_sym_from_planes(c, lt);      // C1 -> T1
+    hipLaunchKernelGGL(k_diag, dim3(ceil_div(Mp, 256)), dim3(256), 0, c->stream, lt.T1.p, (int64_t)Mp, lt.dsq.p);
+    // R = (W^T D) C1 (lower part) -> T2 ; the factor image D W is in Wp (latents_forward)
+    auto lower_up = [&](int bi, int bj, int& k0, int& k1) { if (bj <= bi) { k0 = bi * kb; k1 = nb * kb; } else { k0 = 0; k1 = 0; } };
+    ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "r", nb, lower_up, lt.Wp.p, lt.T1.p, lt.T2.p, Mp, SK_STORE, 1.0, true)));
+    // dL = -tril(alpha (A gm)^T + 2 R) -> T1 ; the second rank-1 term of k_dl_assemble is switched off by the zero vector `du` (zeroed per
+    // call and never written in this mode)
+    hipLaunchKernelGGL(k_dl_assemble, dim3(gridmm), dim3(256), 0, c->stream, lt.T2.p, (int64_t)Mp, lt.vec.p + Mp, lt.a1gm.p, lt.du.p,
+                       lt.du.p, lt.T1.p);
+    // Q = Phi(L^T dL) -> T2 ; T = Q W -> T3 (lower) ; S = W^T T -> T1
+    ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "r", nb, lower_up, lt.L.p, lt.T1.p, lt.T2.p, Mp, SK_PHI, 1.0, true)));
+    ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "t", nb, [&](int bi, int bj, int& k0, int& k1) {
+      if (bj <= bi) { k0 = bj * kb; k1 = (bi + 1) * kb; } else { k0 = 0; k1 = 0; } }, lt.T2.p, lt.W.p, lt.T3.p, Mp, SK_STORE, 1.0, true)));
+    ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "s", nb, [&](int bi, int bj, int& k0, int& k1) { k0 = std::max(bi, bj) * kb; k1 = nb * kb; },
+                                                      lt.W.p, lt.T3.p, lt.T1.p, Mp, SK_STORE, 1.0, false)));
+  }
+  // G = sym(S) -> T3
+  hipLaunchKernelGGL(k_sym_combine, dim3(gridmm), dim3(256), 0, c->stream, lt.T1.p, lt.T1.p, lt.T1.p, lt.vec.p + Mp, with_data ? 1 : 0, 0,
+                     (int64_t)Mp, lt.T3.p);
+  hipLaunchKernelGGL(k_kuu_grad, dim3(Mp), dim3(256), 0, c->stream, lt.T3.p, lt.Kuu.p, jitter, lt.Z.p, lt.M, D, (int64_t)Mp, lt.krow.p);
+  ZIGP_HIP(c, hipGetLastError());
+  return 0;
+}
+
 int validate_params(zigp_ctx* c, const zigp_params* p) {
   if (!p) return fail_arg(c, "params is NULL");
   if (p->Mf <= 0 || p->Mg <= 0) return fail_arg(c, "Mf and Mg must be positive");
@@ -432,6 +546,7 @@ struct DenseCall {
   const zigp_params* p; const double* dX; const double* dY; int64_t Nrows; int D;
   double jitter, scale, g_offset; int64_t row_begin, row_end; int include_kl; bool predict; double* d_out9;
   bool need_grad, has_rows;
+  bool whiten = false;    // the context's zigp_set_whiten at the time of the call (run_dense)
   HostLatent hl[2]; const double* ell_h[2];
   int64_t Nc = 0;         // rows per full chunk
   ChunkPlan plan[2];      // the full chunk and, if smaller, the last one (run_dense)
@@ -469,7 +584,7 @@ int dense_mxm_forward(zigp_ctx* c, DenseCall& k) {
   {
     ProfScope ps(c, PC_MXM);     // wall time of the two concurrent chains: both events on the main stream, the second after the join
     ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
-    ZIGP_TRY(latents_forward(c, k.hl, k.D, k.jitter, true, k.need_grad, k.d_hyp, k.d_info2));
+    ZIGP_TRY(latents_forward(c, k.hl, k.D, k.jitter, true, k.need_grad, k.d_hyp, k.d_info2, k.whiten));
     ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   }
   return k.d_hyp ? 0 : request_info(c, &k.hinfo);   // read after the final synchronisation
@@ -511,7 +626,8 @@ int dense_prepare_buffers(zigp_ctx* c, DenseCall& k) {
     const int Mp = lt.Mp;
     ZIGP_ENSURE(c, lt.gm, Nc); ZIGP_ENSURE(c, lt.gv, Nc);
     if (k.has_rows) {
-      ZIGP_ENSURE(c, lt.K, (size_t)Mp * Nc); ZIGP_ENSURE(c, lt.A1, (size_t)Mp * Nc);
+      ZIGP_ENSURE(c, lt.K, (size_t)Mp * Nc);
+      if (!k.whiten || k.need_grad) ZIGP_ENSURE(c, lt.A1, (size_t)Mp * Nc);     // a whitened value-only / predict pass stores no panel but K
       ZIGP_ENSURE(c, lt.part, (size_t)3 * (Mp / 32) * Nc);
       if (k.need_grad) ZIGP_ENSURE(c, lt.Jp, (size_t)Mp * Nc);
     }
@@ -546,10 +662,13 @@ PwArgs dense_pointwise_args(zigp_ctx* c, const DenseCall& k, int64_t n0, int64_t
   a.acc = c->pw_part.p; a.out9 = k.d_out9 ? k.d_out9 - k.row_begin : nullptr; a.ld9 = k.row_end - k.row_begin;
   return a;
 }
-int dense_pointwise_launch(zigp_ctx* c, bool predict, bool need_grad, const PwArgs& a, const double* d_hyp = nullptr) {
+int dense_pointwise_launch(zigp_ctx* c, bool predict, bool need_grad, const PwArgs& a, const double* d_hyp = nullptr, bool whiten = false) {
   ProfScope ps(c, PC_POINT);
   const int nblk = (int)(a.Nc / PW_PTS);
-  if (d_hyp) hipLaunchKernelGGL((k_pointwise<false, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a, d_hyp);     // a gradient step of the fit loop
+  if (whiten) {     // var = var0 + (plane 2) in every mode (chunk_forward_white); a value-only pass has gm_f = NULL and writes no cotangents
+    if (predict) hipLaunchKernelGGL((k_pointwise<true, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
+    else hipLaunchKernelGGL((k_pointwise<false, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
+  } else if (d_hyp) hipLaunchKernelGGL((k_pointwise<false, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a, d_hyp);     // a gradient step of the fit loop
   else if (predict) hipLaunchKernelGGL((k_pointwise<true, false>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
   else if (need_grad) hipLaunchKernelGGL((k_pointwise<false, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);   // variance from sum K J'
   else hipLaunchKernelGGL((k_pointwise<false, false>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
@@ -557,7 +676,7 @@ int dense_pointwise_launch(zigp_ctx* c, bool predict, bool need_grad, const PwAr
   return 0;
 }
 int dense_pointwise(zigp_ctx* c, const DenseCall& k, int64_t n0, int64_t Nc) {
-  return dense_pointwise_launch(c, k.predict, k.need_grad, dense_pointwise_args(c, k, n0, Nc), k.d_hyp);
+  return dense_pointwise_launch(c, k.predict, k.need_grad, dense_pointwise_args(c, k, n0, Nc), k.d_hyp, k.whiten);
 }
 
 // ---- chunk loop.  The MFMA-bound GEMMs stay on the main stream; with zigp_set_overlap(1) the HBM-bound kernels of a chunk -- the two
@@ -619,10 +738,16 @@ int dense_chunk_loop(zigp_ctx* c, const DenseCall& k) {
     std::function<int()> after_a1;
     if (kuf_fwd_side) after_a1 = [&] { return on_side([&] { return kuf(n1); }); };
     const ChunkPlan& pl = k.plan[Nc == k.plan[0].Nc ? 0 : 1];
-    ZIGP_TRY(chunk_forward(c, pl, k.need_grad, after_a1));
-    // the point-wise stage of a gradient step needs the J' launch's sums (it rode inside the J' launch while the variance came from A2:
-    // r5, profiles/r05t_ab_fuse_pointwise.log), so it is a launch of its own after it
-    ZIGP_TRY(dense_pointwise(c, k, n0, Nc));
+    if (k.whiten) {     // A (f|g), point-wise (it needs the A launch only), then J' (f|g) of a gradient step
+      ZIGP_TRY(chunk_forward_white(c, pl, k.need_grad, false, after_a1));
+      ZIGP_TRY(dense_pointwise(c, k, n0, Nc));
+      if (k.need_grad) ZIGP_TRY(chunk_forward_white(c, pl, true, true));
+    } else {
+      ZIGP_TRY(chunk_forward(c, pl, k.need_grad, after_a1));
+      // the point-wise stage of a gradient step needs the J' launch's sums (it rode inside the J' launch while the variance came from A2:
+      // r5, profiles/r05t_ab_fuse_pointwise.log), so it is a launch of its own after it
+      ZIGP_TRY(dense_pointwise(c, k, n0, Nc));
+    }
     // side work of this chunk: its kgrads and the next chunk's Kuf panels (gradient mode only: without the SYRKs there is
     // nothing on the main stream to hide them under)
     const bool kgrad_side = c->overlap == 1 && k.need_grad && !timed;
@@ -656,6 +781,8 @@ int dense_pack(zigp_ctx* c, const DenseCall& k, DensePackArgs& a, size_t& n) {
     Latent& lt = c->lat[h];
     DensePackLat& L = a.lat[h];
     L.krow = lt.krow.p; L.du = lt.du.p; L.dsq = lt.dsq.p; L.vec = lt.vec.p; L.s = lt.s.p; L.ell = lt.ell.p;
+    // whitened: du's data part is A gm, the KL parts and the KL value come from the whitened vectors (k_kl_white keeps vec's layout)
+    if (k.whiten) { L.du = lt.a1gm.p; L.vec = lt.wh.p; }
     L.M = lt.M; L.Mp = lt.Mp; L.var = lt.var; L.out_off = (int64_t)n;
     if (k.need_grad) n += (size_t)lt.M * D + 2 * (size_t)lt.M + D;
   }
@@ -708,9 +835,9 @@ int dense_plan(zigp_ctx* c, DenseCall& k) {
   k.Nc = chunk_rows_for(c->chunk_auto, c->chunk, round_up(std::max(M[0], M[1]), BM), span);
   if (k.has_rows) {
     const int64_t last = std::min<int64_t>(k.Nc, round_up(span - (span - 1) / k.Nc * k.Nc, 1024));
-    k.plan[0] = chunk_plan(M, k.Nc, k.need_grad, c->trmm_tail);
+    k.plan[0] = chunk_plan(M, k.Nc, k.need_grad, c->trmm_tail, k.whiten);
     ZIGP_TRY(upload_plan(c, k.plan[0]));
-    if (last != k.Nc) { k.plan[1] = chunk_plan(M, last, k.need_grad, c->trmm_tail); ZIGP_TRY(upload_plan(c, k.plan[1])); }
+    if (last != k.Nc) { k.plan[1] = chunk_plan(M, last, k.need_grad, c->trmm_tail, k.whiten); ZIGP_TRY(upload_plan(c, k.plan[1])); }
   }
   return 0;
 }
@@ -728,7 +855,8 @@ int dense_step(zigp_ctx* c, DenseCall& k) {
     ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
     for (int h = 0; h < 2; ++h) {
       OnStream on(c, h == 0 ? c->stream_main : c->stream2);
-      ZIGP_TRY(latent_mxm_backward(c, c->lat[h], k.D, k.jitter, k.has_rows, k.include_kl != 0));
+      if (k.whiten) ZIGP_TRY(latent_mxm_backward_white(c, c->lat[h], k.D, k.jitter, k.has_rows));
+      else ZIGP_TRY(latent_mxm_backward(c, c->lat[h], k.D, k.jitter, k.has_rows, k.include_kl != 0));
     }
     ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   }
@@ -744,6 +872,7 @@ int run_dense(zigp_ctx* c, const zigp_params* p, const double* dX, const double*
   k.row_begin = row_begin; k.row_end = row_end; k.include_kl = include_kl; k.predict = predict; k.d_out9 = d_out9;
   k.need_grad = (grads != nullptr) && !predict;
   k.has_rows = row_end > row_begin;
+  k.whiten = c->whiten;
   k.hl[0] = HostLatent{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f};
   k.hl[1] = HostLatent{p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g};
   k.ell_h[0] = p->ell_f; k.ell_h[1] = p->ell_g;
@@ -858,6 +987,14 @@ int zigp_set_mean_function(zigp_ctx* c, const double* a, int32_t D, double b) {
   return ZIGP_OK;
 }
 
+int zigp_set_whiten(zigp_ctx* c, int32_t on) {
+  if (!c) return ZIGP_EARG;
+  if (on < 0 || on > 1) return fail_arg(c, "zigp_set_whiten: on must be 0 or 1");
+  c->whiten = on != 0;
+  return ZIGP_OK;
+}
+int zigp_get_whiten(zigp_ctx* c) { return c ? (c->whiten ? 1 : 0) : (int)ZIGP_EARG; }
+
 int zigp_get_mean_function_grad(zigp_ctx* c, double* da, int32_t D, double* db) {
   if (!c) return ZIGP_EARG;
   if (D < 0 || D > MAXD || (D > 0 && !da)) return fail_arg(c, "zigp_get_mean_function_grad: need 0 <= D <= 8 and da[D]");
@@ -947,6 +1084,7 @@ int zigp_fit_steps(zigp_ctx* c, const zigp_params* shape, const zigp_fit_opts* o
     if (es[h] != 1 && es[h] != D) return fail_arg(c, "zigp_fit_steps: ell_size must be 1 or D");
   if (!c->dX) return fail_arg(c, "zigp_fit_steps: no data set (call zigp_set_data first)");
   if (D != c->D) return fail_arg(c, "zigp_fit_steps: shape.D differs from the data's D");
+  if (c->whiten) return fail_arg(c, "zigp_fit_steps: whitening is on (zigp_set_whiten); the device loop fits the unwhitened parametrisation only (zigp_elbo + a host optimiser)");
   if (c->mean_on) return fail_arg(c, "zigp_fit_steps: a mean function is set; its parameters stay with the host loop (zigp_elbo + a host optimiser)");
   if (c->comm) return fail_arg(c, "zigp_fit_steps: a communicator is attached; the dense device loop is single-process");
   if (rows) {
@@ -1111,11 +1249,11 @@ int zigp_prior_kl(zigp_ctx* c, const zigp_params* p, double jitter, double* kl2)
   ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
   ZIGP_TRY(latents_upload(c, hl, p->D));
   ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
-  ZIGP_TRY(latents_forward(c, hl, p->D, jitter, true, false));
+  ZIGP_TRY(latents_forward(c, hl, p->D, jitter, true, false, nullptr, nullptr, c->whiten));
   ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   double klh[2] = {0.0, 0.0};
   for (int h = 0; h < 2; ++h)
-    ZIGP_HIP(c, hipMemcpyAsync(&klh[h], c->lat[h].vec.p + 3 * c->lat[h].Mp, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    ZIGP_HIP(c, hipMemcpyAsync(&klh[h], (c->whiten ? c->lat[h].wh.p : c->lat[h].vec.p) + 3 * c->lat[h].Mp, sizeof(double), hipMemcpyDeviceToHost, c->stream));
   ZIGP_TRY(check_info(c, "Kuu"));          // synchronises; on failure kl2 is left untouched
   kl2[0] = klh[0]; kl2[1] = klh[1];
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));
@@ -1342,14 +1480,15 @@ int stage_download_rows(zigp_ctx* c, const double* dev, double* dst, int64_t row
 bool stage_chunk_ok(int64_t Nc) { return Nc >= 1024 && Nc % 1024 == 0 && Nc <= (1 << 20); }
 }  // namespace
 
-int zigp_test_chunk_forward(zigp_ctx* c, int64_t Nc, int32_t need_grad, int32_t only, const zigp_stage_latent* lat, int64_t* facts) {
+namespace {
+int stage_chunk_forward(zigp_ctx* c, int64_t Nc, int32_t need_grad, int32_t only, const zigp_stage_latent* lat, int64_t* facts, bool whiten) {
   if (!c) return ZIGP_EARG;
   if (!lat || !facts || !stage_chunk_ok(Nc) || only < -1 || only > 1) return fail_arg(c, "zigp_test_chunk_forward: bad arguments");
   for (int h = 0; h < 2; ++h) {
     const zigp_stage_latent& q = lat[h];
     if (q.M <= 0) return fail_arg(c, "zigp_test_chunk_forward: M must be positive");
     if (only >= 0 && only != h) continue;
-    if (!q.W || !q.v || !q.s2 || !q.K || !q.A1 || !q.part || (need_grad && (!q.Rt || !q.Jp)))
+    if (!q.W || !q.v || !q.s2 || !q.K || (!q.A1 && !(whiten && !need_grad)) || !q.part || (need_grad && (!q.Rt || !q.Jp)))
       return fail_arg(c, "zigp_test_chunk_forward: NULL operand of a latent that runs");
   }
   ZIGP_HIP(c, hipSetDevice(c->device));
@@ -1360,34 +1499,47 @@ int zigp_test_chunk_forward(zigp_ctx* c, int64_t Nc, int32_t need_grad, int32_t 
     lt.M = q.M; lt.Mp = (int)round_up(q.M, BM);
     const int Mp = lt.Mp;
     const size_t np = Mp / 32;
-    ZIGP_ENSURE(c, lt.Wt, (size_t)Mp * Mp); ZIGP_ENSURE(c, lt.vec, 4 * (size_t)Mp + 8);
-    ZIGP_ENSURE(c, lt.A1, (size_t)Mp * Nc); ZIGP_ENSURE(c, lt.part, 3 * np * Nc);
+    const bool has_a1 = !whiten || grad;      // a whitened value-only / predict pass stores no A panel
+    ZIGP_ENSURE(c, lt.Wt, (size_t)Mp * Mp); ZIGP_ENSURE(c, lt.vec, 4 * (size_t)Mp + 8); ZIGP_ENSURE(c, lt.wh, 4 * (size_t)Mp + 8);
+    if (has_a1) ZIGP_ENSURE(c, lt.A1, (size_t)Mp * Nc);
+    ZIGP_ENSURE(c, lt.part, 3 * np * Nc);
     if (grad) ZIGP_ENSURE(c, lt.Jp, (size_t)Mp * Nc);
     if (only >= 0 && only != h) {      // planned, not launched: only the buffers chunk_forward takes addresses of
       ZIGP_ENSURE(c, lt.W, (size_t)Mp * Mp); ZIGP_ENSURE(c, lt.s2, Mp); ZIGP_ENSURE(c, lt.K, (size_t)Mp * Nc); ZIGP_ENSURE(c, lt.Rt, (size_t)Mp * Mp);
+      ZIGP_ENSURE(c, lt.Wp, (size_t)Mp * Mp);
       continue;
     }
     ZIGP_TRY(stage_upload_square(c, lt.W, q.W, q.M, Mp, 1.0));
     hipLaunchKernelGGL(k_transpose, dim3(Mp / 32, Mp / 32), dim3(32, 8), 0, c->stream, lt.W.p, (int64_t)Mp, lt.Wt.p);
     ZIGP_HIP(c, hipGetLastError());
-    if (grad) ZIGP_TRY(stage_upload_square(c, lt.Rt, q.Rt, q.M, Mp, -1.0));
-    ZIGP_TRY(stage_upload_rows(c, lt.s2, q.s2, q.M, Mp, 1));
-    ZIGP_HIP(c, hipMemsetAsync(lt.vec.p, 0, sizeof(double) * (4 * (size_t)Mp + 8), c->stream));
-    ZIGP_HIP(c, hipMemcpyAsync(lt.vec.p, q.v, sizeof(double) * q.M, hipMemcpyHostToDevice, c->stream));
+    if (whiten) {      // the epilogue weights (Latent::wh: s2 = s^2 - 1, then v = u) and the J' factor image D W, zero padded
+      if (grad) ZIGP_TRY(stage_upload_square(c, lt.Wp, q.Rt, q.M, Mp, 0.0));
+      ZIGP_HIP(c, hipMemsetAsync(lt.wh.p, 0, sizeof(double) * (4 * (size_t)Mp + 8), c->stream));
+      ZIGP_HIP(c, hipMemcpyAsync(lt.wh.p, q.s2, sizeof(double) * q.M, hipMemcpyHostToDevice, c->stream));
+      ZIGP_HIP(c, hipMemcpyAsync(lt.wh.p + Mp, q.v, sizeof(double) * q.M, hipMemcpyHostToDevice, c->stream));
+    } else {
+      if (grad) ZIGP_TRY(stage_upload_square(c, lt.Rt, q.Rt, q.M, Mp, -1.0));
+      ZIGP_TRY(stage_upload_rows(c, lt.s2, q.s2, q.M, Mp, 1));
+      ZIGP_HIP(c, hipMemsetAsync(lt.vec.p, 0, sizeof(double) * (4 * (size_t)Mp + 8), c->stream));
+      ZIGP_HIP(c, hipMemcpyAsync(lt.vec.p, q.v, sizeof(double) * q.M, hipMemcpyHostToDevice, c->stream));
+    }
     ZIGP_TRY(stage_upload_rows(c, lt.K, q.K, q.M, Mp, Nc));
-    ZIGP_HIP(c, hipMemsetAsync(lt.A1.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * Mp * Nc, c->stream));
+    if (has_a1) ZIGP_HIP(c, hipMemsetAsync(lt.A1.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * Mp * Nc, c->stream));
     if (grad) ZIGP_HIP(c, hipMemsetAsync(lt.Jp.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * Mp * Nc, c->stream));
     ZIGP_HIP(c, hipMemsetAsync(lt.part.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * 3 * np * Nc, c->stream));
   }
   const int M[2] = {lat[0].M, lat[1].M};
-  ChunkPlan pl = chunk_plan(M, Nc, grad, c->trmm_tail);
+  ChunkPlan pl = chunk_plan(M, Nc, grad, c->trmm_tail, whiten);
   ZIGP_TRY(upload_plan(c, pl));
   if (only >= 0) { ChunkPlan::Lat& o = pl.lat[1 - only]; o.a1 = TileList(); o.a2j = TileList(); }
-  ZIGP_TRY(chunk_forward(c, pl, grad));
+  if (whiten) {
+    ZIGP_TRY(chunk_forward_white(c, pl, grad, false));
+    if (grad) ZIGP_TRY(chunk_forward_white(c, pl, true, true));
+  } else ZIGP_TRY(chunk_forward(c, pl, grad));
   for (int h = 0; h < 2; ++h) {
     if (only >= 0 && only != h) continue;
     Latent& lt = c->lat[h];
-    ZIGP_TRY(stage_download_rows(c, lt.A1.p, lat[h].A1, lat[h].M, Nc));
+    if (!whiten || grad) ZIGP_TRY(stage_download_rows(c, lt.A1.p, lat[h].A1, lat[h].M, Nc));
     if (grad) ZIGP_TRY(stage_download_rows(c, lt.Jp.p, lat[h].Jp, lat[h].M, Nc));
     ZIGP_TRY(stage_download_rows(c, lt.part.p, lat[h].part, 3 * (int64_t)(lt.Mp / 32), Nc));
   }
@@ -1402,6 +1554,13 @@ int zigp_test_chunk_forward(zigp_ctx* c, int64_t Nc, int32_t need_grad, int32_t 
   facts[0] = pl.paired ? 1 : 0; facts[1] = pl.tail.units[0]; facts[2] = pl.tail.units[1]; facts[3] = c->lat[0].Mp; facts[4] = c->lat[1].Mp;
   facts[5] = a.np_f; facts[6] = a.np_g; facts[7] = a.np1_f; facts[8] = a.np2_f; facts[9] = a.np1_g; facts[10] = a.np2_g; facts[11] = 0;
   return ZIGP_OK;
+}
+}  // namespace
+int zigp_test_chunk_forward(zigp_ctx* c, int64_t Nc, int32_t need_grad, int32_t only, const zigp_stage_latent* lat, int64_t* facts) {
+  return stage_chunk_forward(c, Nc, need_grad, only, lat, facts, false);
+}
+int zigp_test_chunk_forward_white(zigp_ctx* c, int64_t Nc, int32_t need_grad, int32_t only, const zigp_stage_latent* lat, int64_t* facts) {
+  return stage_chunk_forward(c, Nc, need_grad, only, lat, facts, true);
 }
 
 int zigp_test_latents_forward(zigp_ctx* c, const zigp_params* p, double jitter, int32_t need_grad, double* const* out_f, double* const* out_g) {
@@ -1438,7 +1597,8 @@ int zigp_test_latents_forward(zigp_ctx* c, const zigp_params* p, double jitter, 
   return ZIGP_OK;
 }
 
-int zigp_test_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s) {
+namespace {
+int stage_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s, bool whiten) {
   if (!c) return ZIGP_EARG;
   if (!s || s->mode < 0 || s->mode > 2 || s->repeat < 1 || !stage_chunk_ok(s->Nc) || !s->part_f || !s->part_g || !s->acc)
     return fail_arg(c, "zigp_test_pointwise: bad arguments");
@@ -1477,7 +1637,7 @@ int zigp_test_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s) {
   for (int d = 0; d < MAXD; ++d) c->mean_a[d] = mean_a[d];
   a.part_f = pf.p; a.part_g = pg.p; a.np_f = s->np_f; a.np_g = s->np_g;
   a.np1_f = s->np1_f; a.np2_f = s->np2_f; a.np1_g = s->np1_g; a.np2_g = s->np2_g;
-  for (int r = 0; r < s->repeat; ++r) ZIGP_TRY(dense_pointwise_launch(c, k.predict, k.need_grad, a));
+  for (int r = 0; r < s->repeat; ++r) ZIGP_TRY(dense_pointwise_launch(c, k.predict, k.need_grad, a, nullptr, whiten));
   if (s->mode == 1) {
     ZIGP_TRY(stage_download_rows(c, c->lat[0].gm.p, s->gm_f, 1, Nc)); ZIGP_TRY(stage_download_rows(c, c->lat[0].gv.p, s->gv_f, 1, Nc));
     ZIGP_TRY(stage_download_rows(c, c->lat[1].gm.p, s->gm_g, 1, Nc)); ZIGP_TRY(stage_download_rows(c, c->lat[1].gv.p, s->gv_g, 1, Nc));
@@ -1487,6 +1647,9 @@ int zigp_test_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s) {
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));
   return ZIGP_OK;
 }
+}  // namespace
+int zigp_test_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s) { return stage_pointwise(c, s, false); }
+int zigp_test_pointwise_white(zigp_ctx* c, const zigp_stage_pointwise* s) { return stage_pointwise(c, s, true); }
 
 int zigp_test_kgrad(zigp_ctx* c, int32_t M, int32_t D, int64_t Nc, int64_t Nrows, int64_t n0, const double* Jp, const double* K, const double* alpha,
                     const double* gm, const double* gv, const double* X, const double* Z, const double* ell, const double* centre, int32_t exact,

@@ -258,7 +258,9 @@ __device__ __forceinline__ PwOut pointwise_eval(double fm, double fv, double gmn
 // in group order (fixed order: bit-stable) and evaluates the point.
 constexpr int PW_PTS = 64, PW_GROUPS = PW_THREADS / PW_PTS;
 // GRADVAR (gradient steps): plane 2 holds sum_m K J' = sum s^2 A2^2 - sum A1^2 (EpiStorePanelKColsum), so the variance is
-// var + (plane 2) and plane 1 is not read.
+// var + (plane 2) and plane 1 is not read.  The whitened passes (zigp_set_whiten) are this form in every mode, predict included: their
+// one triangular launch A = W K writes  sum_m u_m A_mn  into plane 0 and  sum_m (s_m^2 - 1) A_mn^2  into plane 2 (main.py:278,287,302
+// with whiten = True), so the stage needs that launch alone.
 // var_f / var_g / noise: the three fields of PwArgs, or the device block `H` (PwArgs' fields are then not read)
 struct PwHypDev { const double* H; };
 __device__ __forceinline__ const PwArgs& pw_hyp(const PwArgs& p) { return p; }
@@ -271,7 +273,6 @@ __device__ __forceinline__ double pw_var_g(const PwHypDev& h) { return KF_CONST(
 __device__ __forceinline__ double pw_noise(const PwHypDev& h) { return KF_CONST(h.H)[DH_NOISE]; }
 template <bool PREDICT, bool GRADVAR, class HS>
 __device__ __forceinline__ void pw_block(const PwArgs& p, const HS& hs, int blk, int tid, double (*grp)[PW_GROUPS][PW_PTS]) {
-  static_assert(!(PREDICT && GRADVAR), "predict has no J' panel");
   const int lane = tid & (PW_PTS - 1), g = tid / PW_PTS;
   const int64_t n = (int64_t)blk * PW_PTS + lane;
   {
@@ -661,6 +662,33 @@ k_kl_value(const double* __restrict__ v, const double* __restrict__ L, const dou
   }
   mah = block_sum<4>(mah, sh); lq = block_sum<4>(lq, sh); tr = block_sum<4>(tr, sh); lp = block_sum<4>(lp, sh);
   if (threadIdx.x == 0) out[0] = 0.5 * (mah - (double)M - lq + tr + lp);
+}
+// Whitened parametrisation (zigp_set_whiten): q(u) = N(L u, L diag(s^2) L^T), so the prior is N(0, I) and the KL does not see Kuu
+// (gauss_kl_white_diag, onoffgpf/OnOffSVGP.py:88-91; GaussKL with K = None, onofftf/main.py:193-195,227-228,246):
+//   KL = 0.5 (sum u^2 + sum s^2 - M - sum log s^2).
+// One block; it also writes the call's small whitened vectors, zero / one padded to Mp:
+//   wh[0 .. Mp)     d = s^2 - 1   weights of the variance sum  sum_m d_m A_mn^2  and row scale of the J' factor D W (0 for m >= M)
+//   wh[Mp .. 2Mp)   u             weights of the mean sum; what k_dense_pack subtracts from du as dKL/du
+//   wh[2Mp .. 3Mp)  1             k_dense_pack's dKL/ds = -1/s + (this) s
+//   wh[3Mp]         KL
+// i.e. the layout of Latent::vec as k_dense_pack reads it, so that kernel runs unchanged.
+__global__ void __launch_bounds__(256)
+k_kl_white(const double* __restrict__ u, const double* __restrict__ s, int M, int64_t Mp, double* __restrict__ wh) {
+  __shared__ double sh[4];
+  double mah = 0.0, lq = 0.0, tr = 0.0;
+  for (int i = threadIdx.x; i < Mp; i += 256) {
+    const bool real = i < M;
+    const double ui = real ? u[i] : 0.0, s2 = real ? s[i] * s[i] : 1.0;
+    wh[i] = s2 - 1.0; wh[Mp + i] = ui; wh[2 * Mp + i] = 1.0;
+    if (real) { mah = fma(ui, ui, mah); tr += s2; lq += log(s2); }
+  }
+  mah = block_sum<4>(mah, sh); lq = block_sum<4>(lq, sh); tr = block_sum<4>(tr, sh);
+  if (threadIdx.x == 0) wh[3 * Mp] = 0.5 * (mah - (double)M - lq + tr);
+}
+// d[i] = A[i][i]
+__global__ void k_diag(const double* __restrict__ A, int64_t Mp, double* __restrict__ d) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < Mp) d[i] = A[i * Mp + i];
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -4,7 +4,9 @@ Same constructor signature, attributes and methods the reference exposes / its n
   OnOffSVGP(X, Y, kernf, kerng, likelihood, Zf, Zg, mean_function=None, minibatch_size=None, name='model')
   .optimize(maxiter=...)  .compute_log_likelihood()  .predict_onoffgp(Xnew)  .compute_prior_KL()  .savemodel(fname)
   .Xtrain .Ytrain .Zf .Zg .u_fm .u_gm .u_fs_sqrt .u_gs_sqrt .kernf .kerng .likelihood.variance
-whiten=False and q_diag=True are hard-coded in the reference (:33-34).  mean_function (:29,134): onoffgpf.mean_functions.Zero
+q_diag=True is hard-coded in the reference (:33-34) and so is whiten=False there, although build_prior_KL and build_predict carry the
+whitened branch (:88-91,133,137): here `whiten` is a trailing keyword (default False) that switches the engine to the whitened
+parametrisation q(u) = N(L u_m, L diag(u_s_sqrt^2) L^T), L = chol(Kuu).  mean_function (:29,134): onoffgpf.mean_functions.Zero
 (default), Constant or Linear -- evaluated, and differentiated, inside the engine's point-wise kernel.
 """
 import pickle
@@ -25,7 +27,7 @@ DEVICE_FIT_CALL = 200   # iterations per zigp_fit_steps call of optimize(method=
 
 class OnOffSVGP(Parameterized):
     def __init__(self, X, Y, kernf, kerng, likelihood, Zf, Zg, mean_function=None, minibatch_size=None, name='model',
-                 device=0):
+                 device=0, whiten=False):
         self.mean_function = mean_function or Zero()                 # :29
         if not isinstance(self.mean_function, MeanFunction):
             raise TypeError('mean_function must be an onoffgpf.mean_functions.{Zero, Constant, Linear}')
@@ -34,7 +36,7 @@ class OnOffSVGP(Parameterized):
             raise ValueError('Y must be (N,1): num_latent is 1 (OnOffSVGP.py:45)')
         self.name = name
         self.kernf, self.kerng, self.likelihood = kernf, kerng, likelihood
-        self.whiten, self.q_diag = False, True                       # :33-34
+        self.whiten, self.q_diag = bool(whiten), True                # :33-34 (whiten: the branch of :88-91,133,137)
         self.Xtrain, self.Ytrain = DataHolder(X), DataHolder(Y)      # :37-39
         self.num_data = X.shape[0]
         self.num_latent = Y.shape[1]
@@ -62,6 +64,8 @@ class OnOffSVGP(Parameterized):
     def _values(self):
         a, b = self.mean_function.linear_form(self.Xtrain.value.shape[1])
         mf = {k: v for k, v in (('mean_a', a), ('mean_b', b)) if v is not None}
+        if self.whiten:
+            mf['whiten'] = True          # the engine sets its mode from this on every call
         return dict(mf, Zf=self.Zf.value, Zg=self.Zg.value, u_fm=self.u_fm.value, u_gm=self.u_gm.value,
                     u_fs_sqrt=self.u_fs_sqrt.value, u_gs_sqrt=self.u_gs_sqrt.value,
                     ell_f=self.kernf.ell_vector(), ell_g=self.kerng.ell_vector(),
@@ -107,8 +111,8 @@ class OnOffSVGP(Parameterized):
         return float(self.num_data) / float(self.minibatch_size)          # :119-120
 
     def _device_fit_eligible(self, pset):
-        """the Adam loop can run on the device (zigp_fit_steps): Zero mean function, every transform Identity or Log1pe(1e-6)"""
-        return type(self.mean_function) is Zero and all(
+        """the Adam loop can run on the device (zigp_fit_steps): unwhitened, Zero mean function, every transform Identity or Log1pe(1e-6)"""
+        return not self.whiten and type(self.mean_function) is Zero and all(
             type(q.transform) is Identity or (isinstance(q.transform, Log1pe) and q.transform._lower == 1e-6) for q in pset.params.values())
 
     def _adam_on_device(self, pset, maxiter):
@@ -149,7 +153,7 @@ class OnOffSVGP(Parameterized):
     def optimize(self, method='L-BFGS-B', maxiter=1000, disp=False, callback=None, learning_rate=0.01, **kw):
         """GPflow Model.optimize: scipy L-BFGS-B on the free state (default), or Adam when method='adam'
         (the commented alternative at zero-inflated-gpflow.ipynb:155).  Adam without a callback runs its loop on the device
-        (zigp_fit_steps, DEVICE_FIT_CALL iterations per call) when the mean function is Zero; with a callback, or a mean function, every
+        (zigp_fit_steps, DEVICE_FIT_CALL iterations per call) when the mean function is Zero and whiten is off; otherwise, or with a callback, every
         iteration is a host step (select_rows + elbo + AdamGroups) -- the same minibatches and, to rounding, the same trajectory."""
         pset = self._pset()
 
@@ -190,6 +194,7 @@ class OnOffSVGP(Parameterized):
     def __setstate__(self, d):
         self.__dict__.update(d)
         self.__dict__.setdefault('mean_function', Zero())
+        self.__dict__.setdefault('whiten', False)
         self.__dict__['_engine'] = zigp.reference_engine(self.__dict__.setdefault('_device', 0))   # the device it was fitted on
 
     @staticmethod

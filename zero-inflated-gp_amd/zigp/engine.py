@@ -267,9 +267,20 @@ class DenseEngine:
         _check(self.lib, self.ctx, self.lib.zigp_select_rows(self.ctx, idx.ctypes.data, idx.size))
         self.N = int(idx.size)
 
+    def set_whiten(self, on):
+        """Whitened parametrisation of the dense path (zigp_set_whiten; the reference's `whiten` switch, onoffgpf/OnOffSVGP.py:88-91,
+        133,137): u_*m / u_*s_sqrt are then the whitened mean and standard deviation, q(u) = N(L u_m, L diag(u_s_sqrt^2) L^T).  elbo,
+        predict, predict_device and prior_kl set it themselves on every call from p.get('whiten', False) -- like the mean function -- so
+        an engine shared between models does not carry the mode from one caller to the next."""
+        _check(self.lib, self.ctx, self.lib.zigp_set_whiten(self.ctx, 1 if on else 0))
+
+    def get_whiten(self):
+        return bool(self.lib.zigp_get_whiten(self.ctx))
+
     def elbo(self, p, jitter=1e-6, scale=1.0, g_offset=0.0, rows=None, include_kl=True, need_grad=True):
-        """Returns (elbo_data, kl, grads or None); ELBO = elbo_data - kl."""
+        """Returns (elbo_data, kl, grads or None); ELBO = elbo_data - kl.  p['whiten'] = True: the whitened parametrisation (set_whiten)."""
         pk = _Packed(p)
+        self.set_whiten(p.get('whiten', False))
         mean_D = self._set_mean_function(p, pk.D)
         r0, r1 = (0, self.N) if rows is None else rows
         ed, kl = C.c_double(0), C.c_double(0)
@@ -299,7 +310,9 @@ class DenseEngine:
         (include/zigp.h); lr, positive, trainable: 11 per-block learning rates / Log1pe flags / trainable flags; ell_size = (f, g): 1 (one
         lengthscale for all columns) or D; t0: iterations done so far; rows: int64 [n_steps * batch] indices into the resident data set,
         step i uses rows[i * batch : (i + 1) * batch] -- None: every step uses the active rows (full-batch Adam).
-        Returns (elbo_data[n_steps], kl[n_steps]) -- the history, each at the parameters before that step's update."""
+        Returns (elbo_data[n_steps], kl[n_steps]) -- the history, each at the parameters before that step's update.
+        shape['whiten'] = True raises ValueError: the device loop fits the unwhitened parametrisation only."""
+        self.set_whiten(shape.get('whiten', False))     # the library refuses the call while the mode is on (ZIGP_EARG)
         s = _lib.zigp_params()
         s.Mf, s.Mg, s.D = int(shape['Mf']), int(shape['Mg']), int(shape['D'])
         o = _lib.zigp_fit_opts()
@@ -348,6 +361,7 @@ class DenseEngine:
         """(9,N) array in the order of OnOffSVGP.build_predict (onoffgpf/OnOffSVGP.py:152)."""
         pk = _Packed(p)
         self._set_mean_function(p, pk.D)
+        self.set_whiten(p.get('whiten', False))
         Xnew = as_f64(Xnew)
         if Xnew.ndim != 2 or Xnew.shape[1] != pk.D:
             raise ValueError('Xnew must be (N,%d)' % pk.D)
@@ -362,6 +376,7 @@ class DenseEngine:
         import torch
         pk = _Packed(p)
         self._set_mean_function(p, pk.D)
+        self.set_whiten(p.get('whiten', False))
         if not (X_t.is_cuda and X_t.device.index == self.device and X_t.dtype == torch.float64 and X_t.is_contiguous() and X_t.dim() == 2 and X_t.shape[1] == pk.D):
             raise ValueError('predict_device: need a contiguous float64 (N,%d) tensor on cuda:%d' % (pk.D, self.device))
         N = int(X_t.shape[0])
@@ -377,6 +392,7 @@ class DenseEngine:
 
     def prior_kl(self, p, jitter=1e-6):
         pk = _Packed(p)
+        self.set_whiten(p.get('whiten', False))
         out = np.zeros(2)
         _check(self.lib, self.ctx, self.lib.zigp_prior_kl(self.ctx, C.byref(pk.struct), float(jitter), ptr(out)))
         return out
@@ -684,10 +700,12 @@ class DenseEngine:
 
 
     # ---- stage diagnostics (include/zigp_diag.h): one chunk's stage through the chunk loop's own functions ----
-    def test_chunk_forward(self, lat_f, lat_g, Nc, need_grad, only=None):
+    def test_chunk_forward(self, lat_f, lat_g, Nc, need_grad, only=None, whiten=False):
         """Forward products of one chunk.  lat_*: dict(M=..., W=(M,M) lower, v=(M), s2=(M), K=(M,Nc), Rt=(M,M) in gradient mode); the latent
         that does not run (only = 0 / 1) needs M alone.  Returns ([out_f, out_g], facts): out = dict(A1, Jp or None, part [3][Mp/32][Nc]
-        with rows nothing wrote at _lib.STAGE_SENTINEL) or None, facts = dict(paired, tail_f, tail_g, Mp, np, np1, np2)."""
+        with rows nothing wrote at _lib.STAGE_SENTINEL) or None, facts = dict(paired, tail_f, tail_g, Mp, np, np1, np2).
+        whiten: the launches of a whitened call (zigp_test_chunk_forward_white): v / s2 are the weights of the mean / variance sums (planes 0
+        and 2), Rt the factor image D W of J' = Rt^T A; without need_grad no A panel is stored (A1 is None)."""
         Nc = int(Nc)
         arr = (_lib.zigp_stage_latent * 2)()
         keep, outs = [], []
@@ -701,13 +719,15 @@ class DenseEngine:
             ins = dict(W=as_f64(q['W'], (M, M)), v=as_f64(q['v'], (M,)), s2=as_f64(q['s2'], (M,)), K=as_f64(q['K'], (M, Nc)))
             if need_grad:
                 ins['Rt'] = as_f64(q['Rt'], (M, M))
-            out = dict(A1=np.zeros((M, Nc)), Jp=np.zeros((M, Nc)) if need_grad else None, part=np.zeros((3, Mp // 32, Nc)))
+            out = dict(A1=np.zeros((M, Nc)) if need_grad or not whiten else None, Jp=np.zeros((M, Nc)) if need_grad else None,
+                       part=np.zeros((3, Mp // 32, Nc)))
             for k, a in list(ins.items()) + [(k, a) for k, a in out.items() if a is not None]:
                 setattr(arr[h], k, ptr(a))
             keep.append(ins)
             outs.append(out)
         facts = (C.c_int64 * 12)()
-        _check(self.lib, self.ctx, self.lib.zigp_test_chunk_forward(self.ctx, Nc, int(bool(need_grad)), -1 if only is None else int(only), arr, facts))
+        fn = self.lib.zigp_test_chunk_forward_white if whiten else self.lib.zigp_test_chunk_forward
+        _check(self.lib, self.ctx, fn(self.ctx, Nc, int(bool(need_grad)), -1 if only is None else int(only), arr, facts))
         f = list(facts)
         return outs, dict(paired=f[0], tail_f=f[1], tail_g=f[2], Mp=(f[3], f[4]), np=(f[5], f[6]), np1=(f[7], f[9]), np2=(f[8], f[10]))
 
@@ -723,9 +743,9 @@ class DenseEngine:
         return outs
 
     def test_pointwise(self, mode, part_f, part_g, np1, np2, X, Y, n0, row_end, var_f, var_g, noise, g_offset=0.0, scale=1.0,
-                       mean=None, repeat=1, acc=None):
+                       mean=None, repeat=1, acc=None, whiten=False):
         """The point-wise stage of one chunk.  mode 'value' / 'grad' / 'predict'; part_* [3][np][Nc]; np1 / np2 = (f, g) rows to add of planes
-        0, 1 / of plane 2; mean = None or (a (D), b).  Returns dict(gm_f, gv_f, gm_g, gv_g (grad), acc [Nc/64][PW_ACC], out9 (predict))."""
+        0, 1 / of plane 2; mean = None or (a (D), b); whiten: the launch of a whitened call (mean = plane 0, var = var_* + plane 2 in every mode).  Returns dict(gm_f, gv_f, gm_g, gv_g (grad), acc [Nc/64][PW_ACC], out9 (predict))."""
         part_f, part_g = as_f64(part_f), as_f64(part_g)
         X = as_f64(X)
         if X.ndim == 1: X = X[:, None]
@@ -755,7 +775,8 @@ class DenseEngine:
         if mode == 'predict':
             out['out9'] = np.zeros((9, int(row_end)))
             s.out9 = ptr(out['out9'])
-        _check(self.lib, self.ctx, self.lib.zigp_test_pointwise(self.ctx, C.byref(s)))
+        fn = self.lib.zigp_test_pointwise_white if whiten else self.lib.zigp_test_pointwise
+        _check(self.lib, self.ctx, fn(self.ctx, C.byref(s)))
         return out
 
     def test_kgrad(self, Jp, K, alpha, gm, gv, X, Z, n0=0, ell=None, centre=None, exact=None, krow=None):
