@@ -42,7 +42,7 @@ typedef struct {
   int32_t Mf, Mg, D, reserved;
   const double *Zf, *Zg;             /* (Mf,D), (Mg,D) inducing inputs */
   const double *u_fm, *u_gm;         /* (Mf), (Mg) variational means */
-  const double *u_fs_sqrt, *u_gs_sqrt; /* (Mf), (Mg) variational std-devs (> 0) */
+  const double *u_fs_sqrt, *u_gs_sqrt; /* (Mf), (Mg) variational std-devs (> 0); with zigp_set_q_full: (Mf,Mf), (Mg,Mg) lower-triangular factors */
   const double *ell_f, *ell_g;       /* (D), (D) */
   double var_f, var_g;               /* kernel variances */
   double noise;                      /* likelihood variance */
@@ -132,7 +132,7 @@ int zigp_elbo(zigp_ctx* ctx, const zigp_params* p, double jitter, double scale, 
  * before it HAVE been applied (zigp_fit_steps_applied returns k) -- the history entries from step k on are NaN, and zigp_last_error names
  * the step and the latent.  The steps enqueued behind a failed one still run (at most n_steps - k wasted steps); their updates are skipped.
  * ZIGP_EARG: NULL arguments or bad sizes, n_free not the model's, a row index out of range, more than 1 GiB of row indices, a mean
- * function set on the context (its parameters stay with zigp_elbo and a host optimiser), whitening switched on (zigp_set_whiten) or a
+ * function set on the context (its parameters stay with zigp_elbo and a host optimiser), whitening or the full-covariance q(u) switched on (zigp_set_whiten, zigp_set_q_full) or a
  * communicator attached (zigp_comm_init). */
 #define ZIGP_DENSE_FIT_BLOCKS 11
 typedef struct {
@@ -267,6 +267,23 @@ int zigp_get_mean_function_grad(zigp_ctx* ctx, double* da, int32_t D, double* db
  * there, scripts/onoff.py:145-146).  zigp_get_whiten returns 0 / 1, or ZIGP_EARG for a NULL context. */
 int zigp_set_whiten(zigp_ctx* ctx, int32_t on);
 int zigp_get_whiten(zigp_ctx* ctx);
+
+/* Full-covariance q(u) of the whitened DENSE model (the reference's `q_diag = False` switch, onoffgpf/OnOffSVGP.py:33-34: the
+ * (M, M, num_latent) q_sqrt with transforms.LowerTriangular, :59-71; gauss_kl_white in build_prior_KL, :88-104; the 3-d q_sqrt branches
+ * of GaussKL and GPConditional, onofftf/main.py:208-213 and :292-296).  With on = 1 -- and zigp_set_whiten on -- u_fs_sqrt / u_gs_sqrt
+ * in zigp_params point to (M, M) row-major arrays of which only the lower triangle Lq is read (band_part(q_sqrt, -1, 0), main.py:210,293:
+ * whatever lies above the diagonal is ignored), and q(u) = N(L u_m, L Lq Lq^T L^T) with L = chol(Kuu + jitter I), so that
+ *   mean = A^T u_m (+ mean function for f),  var = k** - sum_m A_mn^2 + sum_m (Lq^T A)_mn^2,  A = L^-1 Kuf   (main.py:278,287,293-296,302)
+ *   KL   = 0.5 (sum u_m^2 + sum_{i>=j} Lq_ij^2 - M - sum_i log Lq_ii^2)                                  (main.py:193-195,212-213,224,227-228,246).
+ * A negative diagonal entry is legal (the log of its square); a zero one is ZIGP_EARG.  The blocks of the same name in zigp_grads are
+ * (M, M) with an exactly zero strict upper triangle; the struct layouts do not change.  zigp_elbo (all its options), zigp_predict,
+ * zigp_predict_device and zigp_prior_kl follow the setting.  The call's result vector grows to 16 + sum_h (M D + M + M^2 + D) doubles
+ * and the parameter upload by M^2 per latent (8 MB each way and latent at M = 1024, through the page-locked arena).
+ * ZIGP_EARG, with nothing enqueued: any of those calls while this is on and whitening is off (the unwhitened full-covariance model,
+ * gauss_kl, OnOffSVGP.py:102-104, is not implemented), and zigp_fit_steps while it is on.  The setting persists in the context, is off
+ * after zigp_create, and the Kronecker entry points ignore it.  zigp_get_q_full returns 0 / 1, or ZIGP_EARG for a NULL context. */
+int zigp_set_q_full(zigp_ctx* ctx, int32_t on);
+int zigp_get_q_full(zigp_ctx* ctx);
 
 /* Single-latent heads on the same Kronecker conditional -- the reference's baselines, which re-use kron_inf and
  * GaussKLkron with one latent f:

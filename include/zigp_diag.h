@@ -133,6 +133,15 @@ int zigp_test_chunk_forward_white(zigp_ctx* ctx, int64_t Nc, int32_t need_grad, 
  * rows); plane 1 is not read.  Arguments as zigp_test_pointwise. */
 int zigp_test_pointwise_white(zigp_ctx* ctx, const zigp_stage_pointwise* a);
 
+/* ---- full-covariance q(u) (zigp_set_q_full): the M x M stage of one latent.  The chunk loop of such a call runs the unwhitened
+ * launches (zigp_test_chunk_forward with v = u, s2 = 1, W -> Lq for the second product, Rt = (T - I) W), so only this stage is new. ---- */
+/* Forward: W (M,M) lower triangular, Lq (M,M) as the caller of zigp_elbo passes it (the strict upper triangle is ignored, the diagonal
+ * must be non-zero), u (M).  Returns, each (M,M) row-major or NULL: TmI = tril(Lq) tril(Lq)^T - I; Rt = TmI W, the image the J' launch
+ * reads (J' = Rt^T A); and *kl = 0.5 (sum u^2 + sum_{i>=j} Lq_ij^2 - M - sum_i log Lq_ii^2). */
+int zigp_test_q_full_forward(zigp_ctx* ctx, int32_t M, const double* W, const double* Lq, const double* u, double* TmI, double* Rt, double* kl);
+/* Backward: dLq (M,M) = tril(2 C1 Lq) - [include_kl] (tril(Lq) - diag(1 / Lq_ii)) for a symmetric C1 (M,M); strict upper triangle 0. */
+int zigp_test_q_full_dlq(zigp_ctx* ctx, int32_t M, const double* C1, const double* Lq, int32_t include_kl, double* dLq);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,6 +77,8 @@ struct Latent {
   DevBuf sk;                             // [S][Mp*Mp] split-K planes of the O(M^3) products of the reverse pass
   DevBuf vec;                            // small vectors: v=W u [Mp], alpha [Mp], dkinv [Mp], scal[8]
   DevBuf wh;                             // whitened calls (k_kl_white): s^2 - 1 [Mp], u [Mp], 1 [Mp], KL -- vec's layout as k_dense_pack reads it
+  DevBuf Lraw, Lq, lqssq, dLq;           // full-covariance calls (zigp_set_q_full): the caller's (M,M) block, its masked padded image (Mp,Mp), k_lq_stage's
+                                         // block sums [Mp*Mp/256], the gradient block (Mp,Mp); T - I lives in `P`, its image R^T = (T - I) W in `Rt`
 };
 
 struct KronState;   // Kronecker-path buffers (zigp_kron.hip)
@@ -162,6 +164,7 @@ struct zigp_ctx : zigp::CtxHandles {
   int overlap = 1;                      // zigp_set_overlap: 1 (default) = HBM-bound side kernels of a chunk on stream2 under its SYRKs
   bool mean_on = false;
   bool whiten = false;                  // zigp_set_whiten: u_*m / u_*s_sqrt are the whitened quantities, q(u) = N(L u, L diag(s^2) L^T)
+  bool q_full = false;                  // zigp_set_q_full (needs whiten): u_*s_sqrt are (M,M) lower-triangular factors Lq, q(u) = N(L u, L Lq Lq^T L^T)
   double mean_a[8] = {0}, mean_b = 0.0, mean_da[8] = {0}, mean_db = 0.0;   // 8 = zigp::MAXD (zigp_kernels.h)
   zigp::DevBuf out9;                    // predict outputs (9,Nc)
   zigp::DevBuf scratch, scratch2;       // misc

@@ -28,6 +28,18 @@
 //   MxM stage   du = W (K gm) - u ;  ds = 2 s diag(C1) - s + 1/s ;  dL = -tril(alpha (A gm)^T + 2 (W^T D) C1) ;  Kuu-bar = sym(W^T Phi(L^T dL) W)
 //               (no P, Q, R, T, U, V; the KL adds nothing to Kuu-bar)
 // The branch is taken on the host alone: an unwhitened call launches exactly what it launched before the mode existed.
+//
+// Full-covariance q(u) on the whitened model (zigp_set_q_full; the 3-d q_sqrt branches, OnOffSVGP.py:59-71, main.py:208-213,292-296).
+// q(u) = N(L u, L Lq Lq^T L^T), Lq lower triangular (M x M), T = Lq Lq^T, R = W^T (T - I), A = W K:
+//   per chunk   A = W K with column sums  mean = sum_m u A  and  sum_m A^2  (the lower-triangular launch, panel stored)
+//               value-only / predict:  B = Lq^T A (upper-triangular product, accumulators only: the A2 launch with Lq where W sits and
+//               weights 1) ;  var = var0 - sum A^2 + sum B^2                                           4 M^2 N flops
+//               gradient step:  J' = R A (the full product of the unwhitened step, epilogue sum_m K J' = A^T (T - I) A) ;
+//               var = var0 + sum_m K J' ;  F = alpha gm^T + 2 J' G, alpha = W^T u ;  C1 = A G A^T          8 M^2 N flops
+//   MxM stage   forward: Lq masked and padded (k_lq_stage), KL (k_kl_white_full), T - I and R^T = (T - I) W (split-K, gradient steps)
+//               backward: du = W (K gm) - u ;  dLq = tril(2 C1 Lq) - (tril(Lq) - diag(1 / Lq_ii)) ;  dL = -tril(alpha (A gm)^T + 2 R C1),
+//               then the whitened chain.
+// Every chunk-loop launch is an instantiation the unwhitened path already runs; only operands differ.
 #include "zigp_ctx.h"
 #include "zigp_kernels.h"
 #include "zigp_host.h"
@@ -100,7 +112,9 @@ int latents_views(zigp_ctx* c, const size_t (&off)[2][6], int D) {
   }
   return 0;
 }
-int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D) {
+// q_full: hl[h].s is the (M, M) row-major block; the image's s slot gets its diagonal (k_kuu_setup squares it, nobody reads the result)
+// and the block itself goes to Latent::Lraw, for k_lq_stage (latents_forward) to mask and pad.
+int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D, bool q_full = false) {
   size_t off[2][6], total = 0;
   const int M[2] = {hl[0].M, hl[1].M};
   ZIGP_TRY(latents_layout(c, M, D, off, total));
@@ -112,14 +126,58 @@ int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D) {
     memcpy(img + off[h][0], q.Z, sizeof(double) * q.M * D);
     memcpy(img + off[h][1], q.ell, sizeof(double) * D);
     memcpy(img + off[h][2], q.u, sizeof(double) * q.M);
-    memcpy(img + off[h][3], q.s, sizeof(double) * q.M);
+    if (q_full) for (int m = 0; m < q.M; ++m) img[off[h][3] + m] = q.s[(size_t)m * q.M + m];
+    else memcpy(img + off[h][3], q.s, sizeof(double) * q.M);
     const KufHyp kh = make_kuf_hyp(q.ell, q.var, D);
     kgrad_centre(c->lat[h], q.Z, q.ell, q.M, D);
     for (int m = 0; m < q.M; ++m)
       for (int d = 0; d < D; ++d) img[off[h][4] + (size_t)m * D + d] = q.Z[(size_t)m * D + d] * kh.scale[d];
   }
   ZIGP_HIP(c, hipMemcpyAsync(c->parm.p, img, sizeof(double) * total, hipMemcpyHostToDevice, c->stream));
+  if (q_full)
+    for (int h = 0; h < 2; ++h) {
+      Latent& lt = c->lat[h];
+      const size_t mm = (size_t)hl[h].M * hl[h].M, mmp = (size_t)lt.Mp * lt.Mp;
+      ZIGP_ENSURE(c, lt.Lraw, mm); ZIGP_ENSURE(c, lt.Lq, mmp); ZIGP_ENSURE(c, lt.lqssq, mmp / 256);
+      ZIGP_PINNED(c, raw, mm);
+      memcpy(raw, hl[h].s, sizeof(double) * mm);
+      ZIGP_HIP(c, hipMemcpyAsync(lt.Lraw.p, raw, sizeof(double) * mm, hipMemcpyHostToDevice, c->stream));
+    }
   return latents_views(c, off, D);
+}
+
+// ---- M x M stage of a full-covariance call (zigp_set_q_full), per latent, on the stream the caller selected ----
+// Lraw -> the masked, padded image Lq and its block sums; then the KL and the call's small vectors (Latent::wh)
+int latent_qfull_stage(zigp_ctx* c, Latent& lt) {
+  const int Mp = lt.Mp, nblk = (int)((size_t)Mp * Mp / 256);
+  hipLaunchKernelGGL(k_lq_stage, dim3(nblk), dim3(256), 0, c->stream, lt.Lraw.p, lt.M, (int64_t)Mp, lt.Lq.p, lt.lqssq.p);
+  hipLaunchKernelGGL(k_kl_white_full, dim3(1), dim3(256), 0, c->stream, lt.u.p, lt.Lq.p, lt.lqssq.p, nblk, lt.M, (int64_t)Mp, lt.wh.p);
+  ZIGP_HIP(c, hipGetLastError());
+  return 0;
+}
+// T - I = Lq Lq^T - I -> P (both factors lower triangular: k <= min(i, j)), then R^T = (T - I) W -> Rt (W lower triangular: k >= j), the
+// image the J' launch reads and the left factor of R C1 in the reverse stage
+int latent_qfull_factors(zigp_ctx* c, Latent& lt) {
+  const int Mp = lt.Mp, nb = Mp / BM, kb = BM / BK;
+  ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_KCONTIG>(c, lt.sk, "tt", nb, [&](int bi, int bj, int& k0, int& k1) { k0 = 0; k1 = (std::min(bi, bj) + 1) * kb; },
+                                                  lt.Lq.p, lt.Lq.p, lt.P.p, Mp, SK_STORE, 1.0, false)));
+  hipLaunchKernelGGL(k_sub_eye, dim3(ceil_div(Mp, 256)), dim3(256), 0, c->stream, lt.P.p, lt.M, (int64_t)Mp);
+  ZIGP_HIP(c, hipGetLastError());
+  return run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "y", nb, [&](int, int bj, int& k0, int& k1) { k0 = bj * kb; k1 = nb * kb; },
+                                                lt.P.p, lt.W.p, lt.Rt.p, Mp, SK_STORE, 1.0, false);
+}
+// dLq = tril(2 C1 Lq) - [kl] (tril(Lq) - diag(1 / Lq_ii)) -> dLq ; C1 in T1 (with_data), Y = C1 Lq -> T3
+int latent_qfull_dlq(zigp_ctx* c, Latent& lt, bool with_data, bool with_kl) {
+  const int Mp = lt.Mp, nb = Mp / BM, kb = BM / BK;
+  const size_t mm = (size_t)Mp * Mp;
+  ZIGP_ENSURE(c, lt.T3, mm); ZIGP_ENSURE(c, lt.dLq, mm);
+  if (with_data)
+    ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "y", nb, [&](int, int bj, int& k0, int& k1) { k0 = bj * kb; k1 = nb * kb; },
+                                                     lt.T1.p, lt.Lq.p, lt.T3.p, Mp, SK_STORE, 1.0, false)));
+  hipLaunchKernelGGL(k_dlq_assemble, dim3(ceil_div((int64_t)mm, 256)), dim3(256), 0, c->stream, lt.T3.p, lt.Lq.p, with_data ? 1 : 0, with_kl ? 1 : 0,
+                     lt.M, (int64_t)Mp, lt.dLq.p);
+  ZIGP_HIP(c, hipGetLastError());
+  return 0;
 }
 
 // MxM forward of BOTH latents (kernels only): Kuu, L = chol, W = L^-1 (+ W^T), the KL pieces v = W u,
@@ -130,8 +188,9 @@ int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D) {
 // carries the sizes only, and latent h reports a failed factorisation in d_info2[h].
 // whiten: W^T, alpha = W^T u (gradient steps), the white KL and the call's whitened vectors (k_kl_white -> Latent::wh) and, for gradient
 // steps, D W = diag(s^2 - 1) W in `Wp`, the factor image of J' = (W^T D) A and of the reverse stage's (W^T D) C1; no v, P, Q or R.
+// q_full (with whiten): the staged factor and its KL in place of k_kl_white, and T - I, R^T in place of D W (latent_qfull_*).
 int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter, bool with_kl, bool need_grad, const double* d_hyp = nullptr,
-                    int* d_info2 = nullptr, bool whiten = false) {
+                    int* d_info2 = nullptr, bool whiten = false, bool q_full = false) {
   const hipStream_t st[2] = {c->stream_main, c->stream2};
   for (int h = 0; h < 2; ++h) {
     Latent& lt = c->lat[h];
@@ -167,9 +226,15 @@ int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter
       if (whiten) {
         switch (step) {
           case 0: hipLaunchKernelGGL(k_transpose, dim3(Mp / 32, Mp / 32), dim3(32, 8), 0, c->stream, lt.W.p, (int64_t)Mp, lt.Wt.p); break;
-          case 1: hipLaunchKernelGGL(k_kl_white, dim3(1), dim3(256), 0, c->stream, lt.u.p, lt.s.p, lt.M, (int64_t)Mp, lt.wh.p); break;
+          case 1:
+            if (q_full) ZIGP_TRY(latent_qfull_stage(c, lt));
+            else hipLaunchKernelGGL(k_kl_white, dim3(1), dim3(256), 0, c->stream, lt.u.p, lt.s.p, lt.M, (int64_t)Mp, lt.wh.p);
+            break;
           case 2: if (need_grad) hipLaunchKernelGGL(k_gemv_cols, dim3(Mp / 64), dim3(64, COL_LANES), 0, c->stream, lt.W.p, lt.u.p, (int64_t)Mp, alpha); break;
-          case 3: if (need_grad) hipLaunchKernelGGL(k_rowscale, dim3(ceil_div((int64_t)Mp * Mp, 256)), dim3(256), 0, c->stream, lt.W.p, lt.wh.p, (int64_t)Mp, lt.Wp.p); break;
+          case 3:
+            if (need_grad && q_full) ZIGP_TRY(latent_qfull_factors(c, lt));
+            else if (need_grad) hipLaunchKernelGGL(k_rowscale, dim3(ceil_div((int64_t)Mp * Mp, 256)), dim3(256), 0, c->stream, lt.W.p, lt.wh.p, (int64_t)Mp, lt.Wp.p);
+            break;
           default: break;
         }
         ZIGP_HIP(c, hipGetLastError());
@@ -249,7 +314,9 @@ struct ChunkPlan {
 };
 // whiten: A = W K is the same lower-triangular list; a gradient step adds the UPPER-triangular J' = (W^T D) A (the paired / tail lists of
 // A2) and the rank-N update, a value-only or predict pass has no second product at all (a2j stays empty).
-ChunkPlan chunk_plan(const int (&M)[2], int64_t Nc, bool need_grad, bool tail_on, bool whiten = false) {
+// q_full: the unwhitened lists in both modes -- A and B = Lq^T A are the A1 / A2 pair, J' = R A is the full product.
+ChunkPlan chunk_plan(const int (&M)[2], int64_t Nc, bool need_grad, bool tail_on, bool whiten = false, bool q_full = false) {
+  if (q_full) whiten = false;
   ChunkPlan pl;
   const int nbm[2] = {ceil_div(M[0], BM), ceil_div(M[1], BM)}, nbn = (int)(Nc / BN);
   pl.Nc = Nc;
@@ -288,7 +355,9 @@ int upload_plan(zigp_ctx* c, ChunkPlan& pl) {
 // with two sets: g's workgroups fill the tail of f's, three launch boundaries fewer per chunk; cfg3 -0.4 ... -0.8 % same-box, profiles/r05l_ab_merge_fg.log,
 // r05s_ab_milestones.log).  In the LPT regime the products stay per latent, in the order A1 A2 / A1 J' (f), then (g) (merged there: cfg2 +1.2 %), and
 // so does the rank-N update everywhere (its 512-workgroup split-K plan fills the chip exactly; merged +0.2 %).
-int chunk_forward(zigp_ctx* c, const ChunkPlan& pl, bool need_grad, const std::function<int()>& after_a1 = nullptr) {
+// q_full (zigp_set_q_full): the same launches on the full-covariance operands -- the mean weights are u (Latent::wh), the second product's
+// factor is Lq (B = Lq^T A, weights 1) or R^T = (T - I) W (J' = R A, latent_qfull_factors wrote it where Q W^T's image lies).
+int chunk_forward(zigp_ctx* c, const ChunkPlan& pl, bool need_grad, const std::function<int()>& after_a1 = nullptr, bool q_full = false) {
   const int64_t Nc = pl.Nc;
   struct Set { TileList t1, t2; double fl; GemmArgs a1, a2j; EpiStoreColsum e1; EpiColsum e2; EpiStorePanelKColsum ej; } q[3] = {};   // q[2]: none
   for (int h = 0; h < 2; ++h) {
@@ -297,7 +366,7 @@ int chunk_forward(zigp_ctx* c, const ChunkPlan& pl, bool need_grad, const std::f
     q[h].t1 = pl.lat[h].a1; q[h].t2 = pl.lat[h].a2j; q[h].fl = pl.lat[h].fl;
     // A1 = W K ; partial column sums  v^T A1 (= mean, since A2^T u = A1^T W u)  and  sum A1^2
     q[h].a1 = mk_args(lt.Wt.p, Mp, lt.K.p, Nc, lt.A1.p, Nc);
-    q[h].e1 = EpiStoreColsum{lt.vec.p, nullptr, lt.part.p, lt.part.p + (size_t)np * Nc};
+    q[h].e1 = EpiStoreColsum{q_full ? lt.wh.p + Mp : lt.vec.p, nullptr, lt.part.p, lt.part.p + (size_t)np * Nc};
     if (need_grad) {
       // J' = Q A2 = (Q W^T) A1, Q = Kuu^-1 diag(s^2) - I (M x M, dense): the two triangular products H = W diag(s^2) A2, J' = W^T H - A2 of the
       // reverse pass as ONE full product of the same flop count -- every tile the full k range (no triangular padding, half as many prologues and
@@ -308,8 +377,8 @@ int chunk_forward(zigp_ctx* c, const ChunkPlan& pl, bool need_grad, const std::f
       q[h].ej = EpiStorePanelKColsum{lt.K.p, lt.part.p + (size_t)2 * np * Nc};
     } else {
       // A2 = W^T A1 ; partial column sums  sum s^2 A2^2 -- the sums only: the panel has no reader (no C; ldc = stride of the partial rows)
-      q[h].a2j = mk_args(lt.W.p, Mp, lt.A1.p, Nc, nullptr, Nc);
-      q[h].e2 = EpiColsum{nullptr, lt.s2.p, nullptr, lt.part.p + (size_t)2 * np * Nc};
+      q[h].a2j = mk_args(q_full ? lt.Lq.p : lt.W.p, Mp, lt.A1.p, Nc, nullptr, Nc);
+      q[h].e2 = EpiColsum{nullptr, q_full ? nullptr : lt.s2.p, nullptr, lt.part.p + (size_t)2 * np * Nc};
     }
   }
   const int groups = pl.paired ? 1 : 2;      // launch groups: merged {f, g}; LPT {f} then {g}
@@ -489,7 +558,9 @@ int latent_mxm_backward(zigp_ctx* c, Latent& lt, int D, double jitter, bool with
 // so ONE split-K product (W^T D) C1 replaces the T / U / V / Y chain of the unwhitened stage; then the same Phi / T / S chain, and
 // k_sym_combine without a KL part (the white KL does not depend on Kuu).  du's data part is A gm = W (K gm), ds's is diag(C1);
 // k_dense_pack adds the KL parts from Latent::wh.
-int latent_mxm_backward_white(zigp_ctx* c, Latent& lt, int D, double jitter, bool with_data) {
+// q_full: ds becomes dLq (latent_qfull_dlq, which also carries the KL part, so it runs without rows too) and the product's left factor
+// is R = W^T (T - I), dense: its image R^T is in Rt and every k block contributes to the lower tiles.
+int latent_mxm_backward_white(zigp_ctx* c, Latent& lt, int D, double jitter, bool with_data, bool q_full = false, bool with_kl = false) {
   const int Mp = lt.Mp, nb = Mp / BM, kb = BM / BK;
   const size_t mm = (size_t)Mp * Mp;
   ZIGP_ENSURE(c, lt.T1, mm); ZIGP_ENSURE(c, lt.T2, mm); ZIGP_ENSURE(c, lt.T3, mm);
@@ -502,10 +573,13 @@ int latent_mxm_backward_white(zigp_ctx* c, Latent& lt, int D, double jitter, boo
       hipLaunchKernelGGL(k_gemv_rows, dim3(Mp), dim3(256), 0, c->stream, lt.W.p, kgm, (int64_t)Mp, lt.a1gm.p);
     }
     latent_sym_from_planes(c, lt);      // C1 -> T1
-    hipLaunchKernelGGL(k_diag, dim3(ceil_div(Mp, 256)), dim3(256), 0, c->stream, lt.T1.p, (int64_t)Mp, lt.dsq.p);
+    if (q_full) ZIGP_TRY(latent_qfull_dlq(c, lt, true, with_kl));
+    else hipLaunchKernelGGL(k_diag, dim3(ceil_div(Mp, 256)), dim3(256), 0, c->stream, lt.T1.p, (int64_t)Mp, lt.dsq.p);
     // R = (W^T D) C1 (lower part) -> T2 ; the factor image D W is in Wp (latents_forward)
     auto lower_up = [&](int bi, int bj, int& k0, int& k1) { if (bj <= bi) { k0 = bi * kb; k1 = nb * kb; } else { k0 = 0; k1 = 0; } };
-    ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "r", nb, lower_up, lt.Wp.p, lt.T1.p, lt.T2.p, Mp, SK_STORE, 1.0, true)));
+    auto lower_all = [&](int bi, int bj, int& k0, int& k1) { k0 = 0; k1 = bj <= bi ? nb * kb : 0; };
+    if (q_full) ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "rfull", nb, lower_all, lt.Rt.p, lt.T1.p, lt.T2.p, Mp, SK_STORE, 1.0, true)));
+    else ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "r", nb, lower_up, lt.Wp.p, lt.T1.p, lt.T2.p, Mp, SK_STORE, 1.0, true)));
     // dL = -tril(alpha (A gm)^T + 2 R) -> T1 ; the second rank-1 term of k_dl_assemble is switched off by the zero vector `du` (zeroed per
     // call and never written in this mode)
     hipLaunchKernelGGL(k_dl_assemble, dim3(gridmm), dim3(256), 0, c->stream, lt.T2.p, (int64_t)Mp, lt.vec.p + Mp, lt.a1gm.p, lt.du.p,
@@ -516,7 +590,7 @@ int latent_mxm_backward_white(zigp_ctx* c, Latent& lt, int D, double jitter, boo
       if (bj <= bi) { k0 = bj * kb; k1 = (bi + 1) * kb; } else { k0 = 0; k1 = 0; } }, lt.T2.p, lt.W.p, lt.T3.p, Mp, SK_STORE, 1.0, true)));
     ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "s", nb, [&](int bi, int bj, int& k0, int& k1) { k0 = std::max(bi, bj) * kb; k1 = nb * kb; },
                                                       lt.W.p, lt.T3.p, lt.T1.p, Mp, SK_STORE, 1.0, false)));
-  }
+  } else if (q_full) ZIGP_TRY(latent_qfull_dlq(c, lt, false, with_kl));
   // G = sym(S) -> T3
   hipLaunchKernelGGL(k_sym_combine, dim3(gridmm), dim3(256), 0, c->stream, lt.T1.p, lt.T1.p, lt.T1.p, lt.vec.p + Mp, with_data ? 1 : 0, 0,
                      (int64_t)Mp, lt.T3.p);
@@ -534,6 +608,14 @@ int validate_params(zigp_ctx* c, const zigp_params* p) {
   if (!(p->var_f > 0) || !(p->var_g > 0) || !(p->noise > 0)) return fail_arg(c, "variances must be positive");
   for (int d = 0; d < p->D; ++d)
     if (!(p->ell_f[d] > 0) || !(p->ell_g[d] > 0)) return fail_arg(c, "lengthscales must be positive");
+  if (c->q_full) {     // (M, M) lower-triangular factors; a negative diagonal entry is legal (the KL takes the log of the square), a zero one is not
+    if (!c->whiten) return fail_arg(c, "zigp_set_q_full is on while whitening is off: the full-covariance q(u) exists for the whitened model only (zigp_set_whiten)");
+    for (int m = 0; m < p->Mf; ++m)
+      if (!(p->u_fs_sqrt[(size_t)m * p->Mf + m] != 0)) return fail_arg(c, "u_fs_sqrt has a zero (or NaN) diagonal entry (full q_sqrt, zigp_set_q_full)");
+    for (int m = 0; m < p->Mg; ++m)
+      if (!(p->u_gs_sqrt[(size_t)m * p->Mg + m] != 0)) return fail_arg(c, "u_gs_sqrt has a zero (or NaN) diagonal entry (full q_sqrt, zigp_set_q_full)");
+    return 0;
+  }
   for (int m = 0; m < p->Mf; ++m)
     if (!(p->u_fs_sqrt[m] > 0)) return fail_arg(c, "u_fs_sqrt must be positive (diagonal q_sqrt, transforms.positive)");
   for (int m = 0; m < p->Mg; ++m)
@@ -547,6 +629,7 @@ struct DenseCall {
   double jitter, scale, g_offset; int64_t row_begin, row_end; int include_kl; bool predict; double* d_out9;
   bool need_grad, has_rows;
   bool whiten = false;    // the context's zigp_set_whiten at the time of the call (run_dense)
+  bool q_full = false;    // the context's zigp_set_q_full (validate_params: only with whiten)
   HostLatent hl[2]; const double* ell_h[2];
   int64_t Nc = 0;         // rows per full chunk
   ChunkPlan plan[2];      // the full chunk and, if smaller, the last one (run_dense)
@@ -567,7 +650,7 @@ int dense_mxm_forward(zigp_ctx* c, DenseCall& k) {
   else {
     ZIGP_TRY(begin_staged_call(c));
     ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
-    ZIGP_TRY(latents_upload(c, k.hl, k.D));
+    ZIGP_TRY(latents_upload(c, k.hl, k.D, k.q_full));
   }
   // The call's buffers, its zeroed accumulators and the first chunk's Kuf panels need the uploaded parameters only: third stream, under
   // the two factorisation chains (which are dependent launches of <= 36 workgroups).  Not while kernels are being timed (they run alone).
@@ -584,7 +667,7 @@ int dense_mxm_forward(zigp_ctx* c, DenseCall& k) {
   {
     ProfScope ps(c, PC_MXM);     // wall time of the two concurrent chains: both events on the main stream, the second after the join
     ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
-    ZIGP_TRY(latents_forward(c, k.hl, k.D, k.jitter, true, k.need_grad, k.d_hyp, k.d_info2, k.whiten));
+    ZIGP_TRY(latents_forward(c, k.hl, k.D, k.jitter, true, k.need_grad, k.d_hyp, k.d_info2, k.whiten, k.q_full));
     ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   }
   return k.d_hyp ? 0 : request_info(c, &k.hinfo);   // read after the final synchronisation
@@ -627,7 +710,7 @@ int dense_prepare_buffers(zigp_ctx* c, DenseCall& k) {
     ZIGP_ENSURE(c, lt.gm, Nc); ZIGP_ENSURE(c, lt.gv, Nc);
     if (k.has_rows) {
       ZIGP_ENSURE(c, lt.K, (size_t)Mp * Nc);
-      if (!k.whiten || k.need_grad) ZIGP_ENSURE(c, lt.A1, (size_t)Mp * Nc);     // a whitened value-only / predict pass stores no panel but K
+      if (!k.whiten || k.need_grad || k.q_full) ZIGP_ENSURE(c, lt.A1, (size_t)Mp * Nc);     // a whitened (diagonal) value-only / predict pass stores no panel but K
       ZIGP_ENSURE(c, lt.part, (size_t)3 * (Mp / 32) * Nc);
       if (k.need_grad) ZIGP_ENSURE(c, lt.Jp, (size_t)Mp * Nc);
     }
@@ -676,7 +759,8 @@ int dense_pointwise_launch(zigp_ctx* c, bool predict, bool need_grad, const PwAr
   return 0;
 }
 int dense_pointwise(zigp_ctx* c, const DenseCall& k, int64_t n0, int64_t Nc) {
-  return dense_pointwise_launch(c, k.predict, k.need_grad, dense_pointwise_args(c, k, n0, Nc), k.d_hyp, k.whiten);
+  // a full-covariance call is the unwhitened forms: var0 - plane 1 + plane 2 (value-only, predict), var0 + plane 2 (gradient step)
+  return dense_pointwise_launch(c, k.predict, k.need_grad, dense_pointwise_args(c, k, n0, Nc), k.d_hyp, k.whiten && !k.q_full);
 }
 
 // ---- chunk loop.  The MFMA-bound GEMMs stay on the main stream; with zigp_set_overlap(1) the HBM-bound kernels of a chunk -- the two
@@ -738,7 +822,10 @@ int dense_chunk_loop(zigp_ctx* c, const DenseCall& k) {
     std::function<int()> after_a1;
     if (kuf_fwd_side) after_a1 = [&] { return on_side([&] { return kuf(n1); }); };
     const ChunkPlan& pl = k.plan[Nc == k.plan[0].Nc ? 0 : 1];
-    if (k.whiten) {     // A (f|g), point-wise (it needs the A launch only), then J' (f|g) of a gradient step
+    if (k.q_full) {     // A (f|g), then B = Lq^T A (sums only) or J' = R A, then the point-wise stage: the unwhitened order
+      ZIGP_TRY(chunk_forward(c, pl, k.need_grad, after_a1, true));
+      ZIGP_TRY(dense_pointwise(c, k, n0, Nc));
+    } else if (k.whiten) {     // A (f|g), point-wise (it needs the A launch only), then J' (f|g) of a gradient step
       ZIGP_TRY(chunk_forward_white(c, pl, k.need_grad, false, after_a1));
       ZIGP_TRY(dense_pointwise(c, k, n0, Nc));
       if (k.need_grad) ZIGP_TRY(chunk_forward_white(c, pl, true, true));
@@ -783,8 +870,8 @@ int dense_pack(zigp_ctx* c, const DenseCall& k, DensePackArgs& a, size_t& n) {
     L.krow = lt.krow.p; L.du = lt.du.p; L.dsq = lt.dsq.p; L.vec = lt.vec.p; L.s = lt.s.p; L.ell = lt.ell.p;
     // whitened: du's data part is A gm, the KL parts and the KL value come from the whitened vectors (k_kl_white keeps vec's layout)
     if (k.whiten) { L.du = lt.a1gm.p; L.vec = lt.wh.p; }
-    L.M = lt.M; L.Mp = lt.Mp; L.var = lt.var; L.out_off = (int64_t)n;
-    if (k.need_grad) n += (size_t)lt.M * D + 2 * (size_t)lt.M + D;
+    L.M = lt.M; L.Mp = lt.Mp; L.var = lt.var; L.out_off = (int64_t)n; L.q_full = k.q_full ? 1 : 0;
+    if (k.need_grad) n += (size_t)lt.M * D + (size_t)lt.M + (k.q_full ? (size_t)lt.M * lt.M : (size_t)lt.M) + D;
   }
   a.pw = c->pw_part.p; a.pw_blocks = k.pw_blocks; a.D = D; a.need_grad = k.need_grad ? 1 : 0; a.include_kl = k.include_kl ? 1 : 0;
   a.mean_on = c->mean_on ? 1 : 0;
@@ -792,6 +879,12 @@ int dense_pack(zigp_ctx* c, const DenseCall& k, DensePackArgs& a, size_t& n) {
   a.out = c->packed.p;
   if (k.d_hyp) hipLaunchKernelGGL(k_dense_pack<const double*>, dim3(2), dim3(256), 0, c->stream, a, k.d_hyp);
   else hipLaunchKernelGGL(k_dense_pack<>, dim3(2), dim3(256), 0, c->stream, a);
+  if (k.need_grad && k.q_full)
+    for (int h = 0; h < 2; ++h) {     // the (M, M) blocks, behind du
+      const Latent& lt = c->lat[h];
+      hipLaunchKernelGGL(k_pack_square, dim3(ceil_div((int64_t)lt.M * lt.M, 256)), dim3(256), 0, c->stream, lt.dLq.p, lt.M, (int64_t)lt.Mp,
+                         a.out + a.lat[h].out_off + (int64_t)lt.M * D + lt.M);
+    }
   ZIGP_HIP(c, hipGetLastError());
   return 0;
 }
@@ -820,8 +913,9 @@ int dense_gather(zigp_ctx* c, DenseCall& k, double* elbo_data, double* kl, zigp_
       const double* o = hv + a.lat[h].out_off;
       if (gZ[h]) memcpy(gZ[h], o, sizeof(double) * M * D);
       if (gu[h]) memcpy(gu[h], o + M * D, sizeof(double) * M);
-      if (gs[h]) memcpy(gs[h], o + M * D + M, sizeof(double) * M);
-      if (gl[h]) memcpy(gl[h], o + M * D + 2 * M, sizeof(double) * D);
+      const size_t ns = k.q_full ? M * M : M;
+      if (gs[h]) memcpy(gs[h], o + M * D + M, sizeof(double) * ns);
+      if (gl[h]) memcpy(gl[h], o + M * D + M + ns, sizeof(double) * D);
     }
     grads->var_f = hv[2]; grads->var_g = hv[3]; grads->noise = hv[4];
   }
@@ -835,9 +929,9 @@ int dense_plan(zigp_ctx* c, DenseCall& k) {
   k.Nc = chunk_rows_for(c->chunk_auto, c->chunk, round_up(std::max(M[0], M[1]), BM), span);
   if (k.has_rows) {
     const int64_t last = std::min<int64_t>(k.Nc, round_up(span - (span - 1) / k.Nc * k.Nc, 1024));
-    k.plan[0] = chunk_plan(M, k.Nc, k.need_grad, c->trmm_tail, k.whiten);
+    k.plan[0] = chunk_plan(M, k.Nc, k.need_grad, c->trmm_tail, k.whiten, k.q_full);
     ZIGP_TRY(upload_plan(c, k.plan[0]));
-    if (last != k.Nc) { k.plan[1] = chunk_plan(M, last, k.need_grad, c->trmm_tail, k.whiten); ZIGP_TRY(upload_plan(c, k.plan[1])); }
+    if (last != k.Nc) { k.plan[1] = chunk_plan(M, last, k.need_grad, c->trmm_tail, k.whiten, k.q_full); ZIGP_TRY(upload_plan(c, k.plan[1])); }
   }
   return 0;
 }
@@ -855,7 +949,7 @@ int dense_step(zigp_ctx* c, DenseCall& k) {
     ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
     for (int h = 0; h < 2; ++h) {
       OnStream on(c, h == 0 ? c->stream_main : c->stream2);
-      if (k.whiten) ZIGP_TRY(latent_mxm_backward_white(c, c->lat[h], k.D, k.jitter, k.has_rows));
+      if (k.whiten) ZIGP_TRY(latent_mxm_backward_white(c, c->lat[h], k.D, k.jitter, k.has_rows, k.q_full, k.include_kl != 0));
       else ZIGP_TRY(latent_mxm_backward(c, c->lat[h], k.D, k.jitter, k.has_rows, k.include_kl != 0));
     }
     ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
@@ -872,7 +966,7 @@ int run_dense(zigp_ctx* c, const zigp_params* p, const double* dX, const double*
   k.row_begin = row_begin; k.row_end = row_end; k.include_kl = include_kl; k.predict = predict; k.d_out9 = d_out9;
   k.need_grad = (grads != nullptr) && !predict;
   k.has_rows = row_end > row_begin;
-  k.whiten = c->whiten;
+  k.whiten = c->whiten; k.q_full = c->q_full;
   k.hl[0] = HostLatent{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f};
   k.hl[1] = HostLatent{p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g};
   k.ell_h[0] = p->ell_f; k.ell_h[1] = p->ell_g;
@@ -995,6 +1089,14 @@ int zigp_set_whiten(zigp_ctx* c, int32_t on) {
 }
 int zigp_get_whiten(zigp_ctx* c) { return c ? (c->whiten ? 1 : 0) : (int)ZIGP_EARG; }
 
+int zigp_set_q_full(zigp_ctx* c, int32_t on) {
+  if (!c) return ZIGP_EARG;
+  if (on < 0 || on > 1) return fail_arg(c, "zigp_set_q_full: on must be 0 or 1");
+  c->q_full = on != 0;
+  return ZIGP_OK;
+}
+int zigp_get_q_full(zigp_ctx* c) { return c ? (c->q_full ? 1 : 0) : (int)ZIGP_EARG; }
+
 int zigp_get_mean_function_grad(zigp_ctx* c, double* da, int32_t D, double* db) {
   if (!c) return ZIGP_EARG;
   if (D < 0 || D > MAXD || (D > 0 && !da)) return fail_arg(c, "zigp_get_mean_function_grad: need 0 <= D <= 8 and da[D]");
@@ -1084,6 +1186,7 @@ int zigp_fit_steps(zigp_ctx* c, const zigp_params* shape, const zigp_fit_opts* o
     if (es[h] != 1 && es[h] != D) return fail_arg(c, "zigp_fit_steps: ell_size must be 1 or D");
   if (!c->dX) return fail_arg(c, "zigp_fit_steps: no data set (call zigp_set_data first)");
   if (D != c->D) return fail_arg(c, "zigp_fit_steps: shape.D differs from the data's D");
+  if (c->q_full) return fail_arg(c, "zigp_fit_steps: the full-covariance q(u) is on (zigp_set_q_full, q_diag=False); the device loop fits the diagonal unwhitened parametrisation only (zigp_elbo + a host optimiser)");
   if (c->whiten) return fail_arg(c, "zigp_fit_steps: whitening is on (zigp_set_whiten); the device loop fits the unwhitened parametrisation only (zigp_elbo + a host optimiser)");
   if (c->mean_on) return fail_arg(c, "zigp_fit_steps: a mean function is set; its parameters stay with the host loop (zigp_elbo + a host optimiser)");
   if (c->comm) return fail_arg(c, "zigp_fit_steps: a communicator is attached; the dense device loop is single-process");
@@ -1247,9 +1350,9 @@ int zigp_prior_kl(zigp_ctx* c, const zigp_params* p, double jitter, double* kl2)
   HostLatent hl[2] = {{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f}, {p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g}};
   ZIGP_TRY(begin_staged_call(c));
   ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
-  ZIGP_TRY(latents_upload(c, hl, p->D));
+  ZIGP_TRY(latents_upload(c, hl, p->D, c->q_full));
   ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
-  ZIGP_TRY(latents_forward(c, hl, p->D, jitter, true, false, nullptr, nullptr, c->whiten));
+  ZIGP_TRY(latents_forward(c, hl, p->D, jitter, true, false, nullptr, nullptr, c->whiten, c->q_full));
   ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   double klh[2] = {0.0, 0.0};
   for (int h = 0; h < 2; ++h)
@@ -1563,10 +1666,67 @@ int zigp_test_chunk_forward_white(zigp_ctx* c, int64_t Nc, int32_t need_grad, in
   return stage_chunk_forward(c, Nc, need_grad, only, lat, facts, true);
 }
 
+// ---- full-covariance M x M stage (zigp_set_q_full), one latent, through latent_qfull_stage / _factors / _dlq ----
+namespace {
+int stage_qfull_operands(zigp_ctx* c, Latent& lt, int M, const double* Lq, const double* u) {
+  lt.M = M; lt.Mp = (int)round_up(M, BM);
+  const size_t Mp = lt.Mp, mm = (size_t)M * M;
+  ZIGP_ENSURE(c, lt.Lraw, mm); ZIGP_ENSURE(c, lt.Lq, Mp * Mp); ZIGP_ENSURE(c, lt.lqssq, Mp * Mp / 256); ZIGP_ENSURE(c, lt.wh, 4 * Mp + 8);
+  ZIGP_HIP(c, hipMemcpyAsync(lt.Lraw.p, Lq, sizeof(double) * mm, hipMemcpyHostToDevice, c->stream));
+  ZIGP_TRY(stage_upload_rows(c, lt.u, u, M, (int64_t)Mp, 1));
+  return latent_qfull_stage(c, lt);
+}
+int stage_download_square(zigp_ctx* c, const double* dev, int M, int Mp, double* dst) {
+  if (!dst) return 0;
+  std::vector<double> h((size_t)Mp * Mp);
+  ZIGP_HIP(c, hipMemcpyAsync(h.data(), dev, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  for (int i = 0; i < M; ++i) memcpy(dst + (size_t)i * M, &h[(size_t)i * Mp], sizeof(double) * M);
+  return 0;
+}
+}  // namespace
+int zigp_test_q_full_forward(zigp_ctx* c, int32_t M, const double* W, const double* Lq, const double* u, double* TmI, double* Rt, double* kl) {
+  if (!c) return ZIGP_EARG;
+  if (M <= 0 || !W || !Lq || !u) return fail_arg(c, "zigp_test_q_full_forward: bad arguments");
+  for (int m = 0; m < M; ++m)
+    if (!(Lq[(size_t)m * M + m] != 0)) return fail_arg(c, "zigp_test_q_full_forward: zero diagonal entry of Lq");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  Latent& lt = c->lat[0];
+  ZIGP_TRY(stage_qfull_operands(c, lt, M, Lq, u));
+  const int Mp = lt.Mp;
+  ZIGP_TRY(stage_upload_square(c, lt.W, W, M, Mp, 1.0));
+  ZIGP_ENSURE(c, lt.P, (size_t)Mp * Mp); ZIGP_ENSURE(c, lt.Rt, (size_t)Mp * Mp);
+  ZIGP_HIP(c, hipMemsetAsync(lt.P.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * Mp * Mp, c->stream));
+  ZIGP_HIP(c, hipMemsetAsync(lt.Rt.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * Mp * Mp, c->stream));
+  ZIGP_TRY(latent_qfull_factors(c, lt));
+  ZIGP_TRY(stage_download_square(c, lt.P.p, M, Mp, TmI));
+  ZIGP_TRY(stage_download_square(c, lt.Rt.p, M, Mp, Rt));
+  if (kl) ZIGP_HIP(c, hipMemcpyAsync(kl, lt.wh.p + 3 * (size_t)Mp, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  return ZIGP_OK;
+}
+int zigp_test_q_full_dlq(zigp_ctx* c, int32_t M, const double* C1, const double* Lq, int32_t include_kl, double* dLq) {
+  if (!c) return ZIGP_EARG;
+  if (M <= 0 || !C1 || !Lq || !dLq) return fail_arg(c, "zigp_test_q_full_dlq: bad arguments");
+  for (int m = 0; m < M; ++m)
+    if (!(Lq[(size_t)m * M + m] != 0)) return fail_arg(c, "zigp_test_q_full_dlq: zero diagonal entry of Lq");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  Latent& lt = c->lat[0];
+  ZIGP_TRY(stage_qfull_operands(c, lt, M, Lq, nullptr));
+  const int Mp = lt.Mp;
+  ZIGP_TRY(stage_upload_square(c, lt.T1, C1, M, Mp, 0.0));
+  ZIGP_ENSURE(c, lt.dLq, (size_t)Mp * Mp);
+  ZIGP_HIP(c, hipMemsetAsync(lt.dLq.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * Mp * Mp, c->stream));
+  ZIGP_TRY(latent_qfull_dlq(c, lt, true, include_kl != 0));
+  ZIGP_TRY(stage_download_square(c, lt.dLq.p, M, Mp, dLq));
+  return ZIGP_OK;
+}
+
 int zigp_test_latents_forward(zigp_ctx* c, const zigp_params* p, double jitter, int32_t need_grad, double* const* out_f, double* const* out_g) {
   if (!c) return ZIGP_EARG;
   ZIGP_TRY(validate_params(c, p));
   if (!out_f || !out_g || !(jitter >= 0)) return fail_arg(c, "zigp_test_latents_forward: bad arguments");
+  if (c->q_full) return fail_arg(c, "zigp_test_latents_forward: the unwhitened stage only (zigp_set_q_full is on; see zigp_test_q_full_forward)");
   ZIGP_HIP(c, hipSetDevice(c->device));
   HostLatent hl[2] = {{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f}, {p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g}};
   ZIGP_TRY(begin_staged_call(c));

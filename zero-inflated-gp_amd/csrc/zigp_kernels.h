@@ -692,10 +692,75 @@ __global__ void k_diag(const double* __restrict__ A, int64_t Mp, double* __restr
 }
 
 // ---------------------------------------------------------------------------------------------
+// Full-covariance q(u) on the whitened model (zigp_set_q_full): q(u) = N(L u, L Lq Lq^T L^T), Lq = band_part(q_sqrt, -1, 0) per latent
+// (OnOffSVGP.py:59-71; the 3-d q_sqrt branches of GaussKL and GPConditional, onofftf/main.py:208-213, 292-296).
+// ---------------------------------------------------------------------------------------------
+// Staging: the (M, M) row-major block as the caller gave it -> the zero-padded (Mp, Mp) row-major image of its LOWER triangle (the strict
+// upper triangle of the input is ignored, main.py:210,293).  That one image is what all three products read: Lq^T as the m-contiguous left
+// factor of B = Lq^T A (value-only variance), both k-contiguous factors of T = Lq Lq^T, and the right factor of C1 Lq.  Padded rows and
+// columns are zero, so they add nothing to any of them.  ssq[block] = the block's sum of squares (fixed order), the KL's trace term.
+__global__ void __launch_bounds__(256)
+k_lq_stage(const double* __restrict__ raw, int M, int64_t Mp, double* __restrict__ Lq, double* __restrict__ ssq) {
+  __shared__ double sh[4];
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;     // the grid covers Mp * Mp exactly (Mp is a multiple of 128)
+  const int64_t i = idx / Mp, j = idx - i * Mp;
+  const double v = (i < M && j <= i) ? raw[i * M + j] : 0.0;
+  Lq[idx] = v;
+  const double s = block_sum<4>(v * v, sh);
+  if (threadIdx.x == 0) ssq[blockIdx.x] = s;
+}
+// A[i][i] -= 1 for the real rows i < M  (T - I; the padded diagonal stays 0)
+__global__ void k_sub_eye(double* __restrict__ A, int M, int64_t Mp) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < M) A[i * Mp + i] -= 1.0;
+}
+// White KL of a full factor (GaussKL with K = None and a 3-d q_sqrt, main.py:193-195, 212-213, 224, 227-228, 246):
+//   KL = 0.5 (sum u^2 + sum_{i>=j} Lq_ij^2 - M - sum_i log Lq_ii^2)      (a negative diagonal entry is legal: the log of the square).
+// One block; the trace term from k_lq_stage's block sums, added in block order.  It writes the call's small vectors in the layout of
+// k_kl_white (Latent::wh): wh[Mp .. 2Mp) = u (weights of the mean sum, and dKL/du for k_dense_pack), wh[3Mp] = KL; the other two are
+// not read in this mode and are cleared.
+__global__ void __launch_bounds__(256)
+k_kl_white_full(const double* __restrict__ u, const double* __restrict__ Lq, const double* __restrict__ ssq, int nssq, int M, int64_t Mp,
+                double* __restrict__ wh) {
+  __shared__ double sh[4];
+  double mah = 0.0, lq = 0.0, tr = 0.0;
+  for (int i = threadIdx.x; i < Mp; i += 256) {
+    const bool real = i < M;
+    const double ui = real ? u[i] : 0.0;
+    wh[i] = 0.0; wh[Mp + i] = ui; wh[2 * Mp + i] = 0.0;
+    if (real) { const double d = Lq[(int64_t)i * Mp + i]; mah = fma(ui, ui, mah); lq += log(d * d); }
+  }
+  for (int b = threadIdx.x; b < nssq; b += 256) tr += ssq[b];
+  mah = block_sum<4>(mah, sh); lq = block_sum<4>(lq, sh); tr = block_sum<4>(tr, sh);
+  if (threadIdx.x == 0) wh[3 * Mp] = 0.5 * (mah - (double)M - lq + tr);
+}
+// dLq = tril(2 Y) - [kl] (tril(Lq) - diag(1 / Lq_ii)),  Y = C1 Lq  (the data part only if with_data); 0 above the diagonal and in the padding
+__global__ void k_dlq_assemble(const double* __restrict__ Y, const double* __restrict__ Lq, int with_data, int with_kl, int M, int64_t Mp,
+                               double* __restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= Mp * Mp) return;
+  const int64_t i = idx / Mp, j = idx - i * Mp;
+  double v = 0.0;
+  if (i < M && j <= i) {
+    if (with_data) v = 2.0 * Y[idx];
+    if (with_kl) { const double l = Lq[idx]; v -= (i == j) ? l - 1.0 / l : l; }
+  }
+  out[idx] = v;
+}
+// the (M, M) block of the result vector from the padded (Mp, Mp) image
+__global__ void k_pack_square(const double* __restrict__ src, int M, int64_t Mp, double* __restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)M * M) return;
+  const int64_t i = idx / M, j = idx - i * M;
+  out[idx] = src[i * Mp + j];
+}
+
+// ---------------------------------------------------------------------------------------------
 // Result vector of one dense ELBO call, assembled on the device so that a data-parallel run can sum it over ranks where it
 // lies (ncclAllReduce on the library's stream, zigp_comm_init) and one download brings everything back:
 //   out[0] elbo_data  [1] kl  [2] d var_f  [3] d var_g  [4] d noise  [5] d mean_b  [6..13] d mean_a   (header: DP_HDR doubles)
 //   then per latent h = f, g (only when a gradient was asked for):  dZ (M_h x D)  du (M_h)  ds (M_h)  dell (D)
+//   (zigp_set_q_full: the ds block is dLq, M_h x M_h, written by k_pack_square; this kernel leaves it alone and puts dell behind it)
 // Block h assembles latent h; block 0 also writes the header scalars.  Every sum has a fixed order (strided partial per thread,
 // xor tree over lanes, waves in index order): bit-stable run to run.
 // ---------------------------------------------------------------------------------------------
@@ -703,6 +768,7 @@ constexpr int DP_HDR = 16;
 struct DensePackLat {
   const double* krow; const double* du; const double* dsq; const double* vec; const double* s; const double* ell;
   int M, Mp; double var; int64_t out_off;
+  int q_full;   // the latent's q_sqrt block is (M, M) and not this kernel's
 };
 struct DensePackArgs {
   DensePackLat lat[2];
@@ -755,7 +821,7 @@ k_dense_pack(DensePackArgs a, HV... hv) {
     const double e = L.ell[d];
     o[idx] = ksum(m, 1 + d) / (e * e);
   }
-  double* ou = o + (int64_t)M * D; double* os = ou + M; double* ol = os + M;
+  double* ou = o + (int64_t)M * D; double* os = ou + M; double* ol = os + (L.q_full ? (int64_t)M * M : (int64_t)M);
   for (int m = t; m < M; m += 256) {
     const double sm = L.s[m];
     double dum = L.du[m], dsm = 2.0 * sm * L.dsq[m];
@@ -763,7 +829,8 @@ k_dense_pack(DensePackArgs a, HV... hv) {
       dum -= L.vec[Mp + m];
       dsm -= (-1.0 / sm + L.vec[2 * Mp + m] * sm);
     }
-    ou[m] = dum; os[m] = dsm;
+    ou[m] = dum;
+    if (!L.q_full) os[m] = dsm;
   }
   double dv = 0.0;
   for (int m = t; m < M; m += 256) dv += ksum(m, 0);

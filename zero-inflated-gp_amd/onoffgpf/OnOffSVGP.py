@@ -6,7 +6,10 @@ Same constructor signature, attributes and methods the reference exposes / its n
   .Xtrain .Ytrain .Zf .Zg .u_fm .u_gm .u_fs_sqrt .u_gs_sqrt .kernf .kerng .likelihood.variance
 q_diag=True is hard-coded in the reference (:33-34) and so is whiten=False there, although build_prior_KL and build_predict carry the
 whitened branch (:88-91,133,137): here `whiten` is a trailing keyword (default False) that switches the engine to the whitened
-parametrisation q(u) = N(L u_m, L diag(u_s_sqrt^2) L^T), L = chol(Kuu).  mean_function (:29,134): onoffgpf.mean_functions.Zero
+parametrisation q(u) = N(L u_m, L diag(u_s_sqrt^2) L^T), L = chol(Kuu).  `q_diag` (trailing keyword, default True) opens the other
+switch for the whitened model: q_diag=False makes u_*s_sqrt (M, M, 1) lower-triangular factors (transforms.LowerTriangular, identity at
+the start, :65-71) and q(u) = N(L u_m, L Lq Lq^T L^T) (gauss_kl_white, :88-89; the 3-d q_sqrt branch of the conditional).  The
+unwhitened full-covariance model (gauss_kl, :102-104) is not implemented: q_diag=False with whiten=False raises NotImplementedError.  mean_function (:29,134): onoffgpf.mean_functions.Zero
 (default), Constant or Linear -- evaluated, and differentiated, inside the engine's point-wise kernel.
 """
 import pickle
@@ -17,7 +20,7 @@ import numpy as np
 
 import zigp
 from zigp.optim import ParamSet, lbfgsb, AdamGroups, DenseDeviceFit
-from zigp.transforms import positive, Log1pe, Identity
+from zigp.transforms import positive, Log1pe, Identity, LowerTriangular
 from .param import Param, DataHolder, Parameterized
 from .mean_functions import MeanFunction, Zero
 
@@ -27,7 +30,7 @@ DEVICE_FIT_CALL = 200   # iterations per zigp_fit_steps call of optimize(method=
 
 class OnOffSVGP(Parameterized):
     def __init__(self, X, Y, kernf, kerng, likelihood, Zf, Zg, mean_function=None, minibatch_size=None, name='model',
-                 device=0, whiten=False):
+                 device=0, whiten=False, q_diag=True):
         self.mean_function = mean_function or Zero()                 # :29
         if not isinstance(self.mean_function, MeanFunction):
             raise TypeError('mean_function must be an onoffgpf.mean_functions.{Zero, Constant, Linear}')
@@ -36,7 +39,10 @@ class OnOffSVGP(Parameterized):
             raise ValueError('Y must be (N,1): num_latent is 1 (OnOffSVGP.py:45)')
         self.name = name
         self.kernf, self.kerng, self.likelihood = kernf, kerng, likelihood
-        self.whiten, self.q_diag = bool(whiten), True                # :33-34 (whiten: the branch of :88-91,133,137)
+        self.whiten, self.q_diag = bool(whiten), bool(q_diag)        # :33-34 (whiten: the branch of :88-91,133,137; q_diag: :59-71,88-89)
+        if not self.q_diag and not self.whiten:
+            raise NotImplementedError('q_diag=False is implemented for the whitened model only (whiten=True); the unwhitened '
+                                      'full-covariance q(u) (gauss_kl, OnOffSVGP.py:102-104) is not')
         self.Xtrain, self.Ytrain = DataHolder(X), DataHolder(Y)      # :37-39
         self.num_data = X.shape[0]
         self.num_latent = Y.shape[1]
@@ -46,8 +52,12 @@ class OnOffSVGP(Parameterized):
         self.num_inducing_f, self.num_inducing_g = self.Zf.value.shape[0], self.Zg.value.shape[0]
         self.u_fm = Param(np.random.randn(self.num_inducing_f, self.num_latent) * 0.01)   # :56 (unseeded, as the reference)
         self.u_gm = Param(np.random.randn(self.num_inducing_g, self.num_latent) * 0.01)   # :57
-        self.u_fs_sqrt = Param(np.ones((self.num_inducing_f, self.num_latent)), positive)  # :60-61
-        self.u_gs_sqrt = Param(np.ones((self.num_inducing_g, self.num_latent)), positive)  # :62-63
+        if self.q_diag:
+            self.u_fs_sqrt = Param(np.ones((self.num_inducing_f, self.num_latent)), positive)  # :60-61
+            self.u_gs_sqrt = Param(np.ones((self.num_inducing_g, self.num_latent)), positive)  # :62-63
+        else:                                                                                  # :65-71 (num_latent = 1: one identity each)
+            self.u_fs_sqrt = Param(np.eye(self.num_inducing_f)[:, :, None], LowerTriangular(self.num_inducing_f))
+            self.u_gs_sqrt = Param(np.eye(self.num_inducing_g)[:, :, None], LowerTriangular(self.num_inducing_g))
         self._device = int(device)
         self._engine = zigp.reference_engine(self._device)  # raises if libzigp.so / GPU is missing: no CPU fallback; tf.cholesky's pivot rule
         self._resident = False
@@ -66,6 +76,8 @@ class OnOffSVGP(Parameterized):
         mf = {k: v for k, v in (('mean_a', a), ('mean_b', b)) if v is not None}
         if self.whiten:
             mf['whiten'] = True          # the engine sets its mode from this on every call
+        if not self.q_diag:
+            mf['q_diag'] = False         # likewise (full-covariance q(u): u_*s_sqrt are (M, M, 1))
         return dict(mf, Zf=self.Zf.value, Zg=self.Zg.value, u_fm=self.u_fm.value, u_gm=self.u_gm.value,
                     u_fs_sqrt=self.u_fs_sqrt.value, u_gs_sqrt=self.u_gs_sqrt.value,
                     ell_f=self.kernf.ell_vector(), ell_g=self.kerng.ell_vector(),
@@ -80,6 +92,9 @@ class OnOffSVGP(Parameterized):
                 out[k] = np.array([np.sum(g[k])])
         for k in ('var_f', 'var_g', 'noise'):
             out[k] = np.array([g[k]])
+        if not self.q_diag:              # (M, M) from the engine -> the Param's (M, M, 1)
+            for k in ('u_fs_sqrt', 'u_gs_sqrt'):
+                out[k] = np.asarray(g[k])[:, :, None]
         if 'mean_b' in g:
             out['mean_b'] = np.array([g['mean_b']])
         return out
@@ -111,8 +126,9 @@ class OnOffSVGP(Parameterized):
         return float(self.num_data) / float(self.minibatch_size)          # :119-120
 
     def _device_fit_eligible(self, pset):
-        """the Adam loop can run on the device (zigp_fit_steps): unwhitened, Zero mean function, every transform Identity or Log1pe(1e-6)"""
-        return not self.whiten and type(self.mean_function) is Zero and all(
+        """the Adam loop can run on the device (zigp_fit_steps): unwhitened, diagonal q(u), Zero mean function, every transform Identity or
+        Log1pe(1e-6)"""
+        return not self.whiten and self.q_diag and type(self.mean_function) is Zero and all(
             type(q.transform) is Identity or (isinstance(q.transform, Log1pe) and q.transform._lower == 1e-6) for q in pset.params.values())
 
     def _adam_on_device(self, pset, maxiter):
@@ -153,7 +169,7 @@ class OnOffSVGP(Parameterized):
     def optimize(self, method='L-BFGS-B', maxiter=1000, disp=False, callback=None, learning_rate=0.01, **kw):
         """GPflow Model.optimize: scipy L-BFGS-B on the free state (default), or Adam when method='adam'
         (the commented alternative at zero-inflated-gpflow.ipynb:155).  Adam without a callback runs its loop on the device
-        (zigp_fit_steps, DEVICE_FIT_CALL iterations per call) when the mean function is Zero and whiten is off; otherwise, or with a callback, every
+        (zigp_fit_steps, DEVICE_FIT_CALL iterations per call) when the mean function is Zero, whiten is off and q_diag is on; otherwise, or with a callback, every
         iteration is a host step (select_rows + elbo + AdamGroups) -- the same minibatches and, to rounding, the same trajectory."""
         pset = self._pset()
 
@@ -195,6 +211,7 @@ class OnOffSVGP(Parameterized):
         self.__dict__.update(d)
         self.__dict__.setdefault('mean_function', Zero())
         self.__dict__.setdefault('whiten', False)
+        self.__dict__.setdefault('q_diag', True)
         self.__dict__['_engine'] = zigp.reference_engine(self.__dict__.setdefault('_device', 0))   # the device it was fitted on
 
     @staticmethod

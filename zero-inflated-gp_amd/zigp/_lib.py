@@ -138,6 +138,8 @@ SIGNATURES = {
     'zigp_get_mean_function_grad': (C.c_int, [C.c_void_p, dp, C.c_int32, dp]),
     'zigp_set_whiten': (C.c_int, [C.c_void_p, C.c_int32]),
     'zigp_get_whiten': (C.c_int, [C.c_void_p]),
+    'zigp_set_q_full': (C.c_int, [C.c_void_p, C.c_int32]),
+    'zigp_get_q_full': (C.c_int, [C.c_void_p]),
     'zigp_kron_head_elbo': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_int32, dp, dp, C.c_int64, C.c_double, C.c_double,
                                       C.c_double, C.c_int32, dp, dp, C.POINTER(zigp_kron_grads), dp]),
     'zigp_kron_head_predict': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_int32, dp, C.c_int64, C.c_double, C.c_double, dp]),
@@ -155,6 +157,8 @@ SIGNATURES = {
     'zigp_test_pointwise': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_pointwise)]),
     'zigp_test_chunk_forward_white': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(zigp_stage_latent), C.POINTER(C.c_int64)]),
     'zigp_test_pointwise_white': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_pointwise)]),
+    'zigp_test_q_full_forward': (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp]),
+    'zigp_test_q_full_dlq': (C.c_int, [C.c_void_p, C.c_int32, dp, dp, C.c_int32, dp]),
     'zigp_test_kgrad': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int32, dp]),
     'zigp_test_rank_update': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(dp), C.POINTER(dp), dp, C.POINTER(C.c_int64)]),
 }

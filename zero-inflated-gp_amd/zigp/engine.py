@@ -44,11 +44,28 @@ class _Packed:
                 raise ValueError('lengthscales must be scalar or have D entries')
             return np.ascontiguousarray(v)
 
+        # p['q_diag'] = False: full-covariance q(u) on the whitened model (zigp_set_q_full); u_*s_sqrt is then the (M, M) or (M, M, 1)
+        # factor, of which the library reads the lower triangle
+        self.q_full = not p.get('q_diag', True)
+        if self.q_full and not p.get('whiten', False):
+            raise ValueError('q_diag=False needs whiten=True: the full-covariance q(u) exists for the whitened model only')
+
+        def q_sqrt(k, M):
+            a = as_f64(p[k])
+            if not self.q_full:
+                return a.reshape(-1)
+            if a.shape not in ((M, M), (M, M, 1)):
+                raise ValueError('%s must be (%d, %d) or (%d, %d, 1) with q_diag=False, not %s' % (k, M, M, M, M, a.shape))
+            a = a.reshape(M, M)
+            if not np.all(np.diagonal(a) != 0):
+                raise ValueError('%s has a zero diagonal entry (q_diag=False)' % k)
+            return a
+
         self.arr = dict(Zf=Zf, Zg=Zg, u_fm=as_f64(p['u_fm']).reshape(-1), u_gm=as_f64(p['u_gm']).reshape(-1),
-                        u_fs_sqrt=as_f64(p['u_fs_sqrt']).reshape(-1), u_gs_sqrt=as_f64(p['u_gs_sqrt']).reshape(-1),
+                        u_fs_sqrt=q_sqrt('u_fs_sqrt', self.Mf), u_gs_sqrt=q_sqrt('u_gs_sqrt', self.Mg),
                         ell_f=ell(p['ell_f']), ell_g=ell(p['ell_g']))
         for k, M in (('u_fm', self.Mf), ('u_fs_sqrt', self.Mf), ('u_gm', self.Mg), ('u_gs_sqrt', self.Mg)):
-            if self.arr[k].size != M:
+            if self.arr[k].size != (M * M if self.q_full and k.endswith('s_sqrt') else M):
                 raise ValueError('%s must have %d entries' % (k, M))
         s = _lib.zigp_params()
         s.Mf, s.Mg, s.D = self.Mf, self.Mg, D
@@ -277,17 +294,32 @@ class DenseEngine:
     def get_whiten(self):
         return bool(self.lib.zigp_get_whiten(self.ctx))
 
-    def elbo(self, p, jitter=1e-6, scale=1.0, g_offset=0.0, rows=None, include_kl=True, need_grad=True):
-        """Returns (elbo_data, kl, grads or None); ELBO = elbo_data - kl.  p['whiten'] = True: the whitened parametrisation (set_whiten)."""
-        pk = _Packed(p)
+    def set_q_full(self, on):
+        """Full-covariance q(u) of the whitened dense model (zigp_set_q_full; the reference's `q_diag = False`, onoffgpf/OnOffSVGP.py:
+        59-71, 88-104): u_*s_sqrt are then (M, M) lower-triangular factors Lq, q(u) = N(L u_m, L Lq Lq^T L^T).  Set on every call from
+        p.get('q_diag', True), like the whitening."""
+        _check(self.lib, self.ctx, self.lib.zigp_set_q_full(self.ctx, 1 if on else 0))
+
+    def get_q_full(self):
+        return bool(self.lib.zigp_get_q_full(self.ctx))
+
+    def _set_modes(self, p):
         self.set_whiten(p.get('whiten', False))
+        self.set_q_full(not p.get('q_diag', True))
+
+    def elbo(self, p, jitter=1e-6, scale=1.0, g_offset=0.0, rows=None, include_kl=True, need_grad=True):
+        """Returns (elbo_data, kl, grads or None); ELBO = elbo_data - kl.  p['whiten'] = True: the whitened parametrisation (set_whiten);
+        with it, p['q_diag'] = False: full-covariance q(u) (set_q_full) -- u_*s_sqrt (M, M) or (M, M, 1), their gradients (M, M)."""
+        pk = _Packed(p)
+        self._set_modes(p)
         mean_D = self._set_mean_function(p, pk.D)
         r0, r1 = (0, self.N) if rows is None else rows
         ed, kl = C.c_double(0), C.c_double(0)
         gs, g = None, None
         if need_grad:
             g = dict(Zf=np.zeros((pk.Mf, pk.D)), Zg=np.zeros((pk.Mg, pk.D)), u_fm=np.zeros(pk.Mf), u_gm=np.zeros(pk.Mg),
-                     u_fs_sqrt=np.zeros(pk.Mf), u_gs_sqrt=np.zeros(pk.Mg), ell_f=np.zeros(pk.D), ell_g=np.zeros(pk.D))
+                     u_fs_sqrt=np.zeros((pk.Mf, pk.Mf) if pk.q_full else pk.Mf), u_gs_sqrt=np.zeros((pk.Mg, pk.Mg) if pk.q_full else pk.Mg),
+                     ell_f=np.zeros(pk.D), ell_g=np.zeros(pk.D))
             gs = _lib.zigp_grads()
             for k, a in g.items():
                 setattr(gs, k, ptr(a))
@@ -311,8 +343,8 @@ class DenseEngine:
         lengthscale for all columns) or D; t0: iterations done so far; rows: int64 [n_steps * batch] indices into the resident data set,
         step i uses rows[i * batch : (i + 1) * batch] -- None: every step uses the active rows (full-batch Adam).
         Returns (elbo_data[n_steps], kl[n_steps]) -- the history, each at the parameters before that step's update.
-        shape['whiten'] = True raises ValueError: the device loop fits the unwhitened parametrisation only."""
-        self.set_whiten(shape.get('whiten', False))     # the library refuses the call while the mode is on (ZIGP_EARG)
+        shape['whiten'] = True or shape['q_diag'] = False raises ValueError: the device loop fits the diagonal unwhitened parametrisation only."""
+        self._set_modes(shape)     # the library refuses the call while either mode is on (ZIGP_EARG; the message names q_diag / whitening)
         s = _lib.zigp_params()
         s.Mf, s.Mg, s.D = int(shape['Mf']), int(shape['Mg']), int(shape['D'])
         o = _lib.zigp_fit_opts()
@@ -361,7 +393,7 @@ class DenseEngine:
         """(9,N) array in the order of OnOffSVGP.build_predict (onoffgpf/OnOffSVGP.py:152)."""
         pk = _Packed(p)
         self._set_mean_function(p, pk.D)
-        self.set_whiten(p.get('whiten', False))
+        self._set_modes(p)
         Xnew = as_f64(Xnew)
         if Xnew.ndim != 2 or Xnew.shape[1] != pk.D:
             raise ValueError('Xnew must be (N,%d)' % pk.D)
@@ -376,7 +408,7 @@ class DenseEngine:
         import torch
         pk = _Packed(p)
         self._set_mean_function(p, pk.D)
-        self.set_whiten(p.get('whiten', False))
+        self._set_modes(p)
         if not (X_t.is_cuda and X_t.device.index == self.device and X_t.dtype == torch.float64 and X_t.is_contiguous() and X_t.dim() == 2 and X_t.shape[1] == pk.D):
             raise ValueError('predict_device: need a contiguous float64 (N,%d) tensor on cuda:%d' % (pk.D, self.device))
         N = int(X_t.shape[0])
@@ -392,7 +424,7 @@ class DenseEngine:
 
     def prior_kl(self, p, jitter=1e-6):
         pk = _Packed(p)
-        self.set_whiten(p.get('whiten', False))
+        self._set_modes(p)
         out = np.zeros(2)
         _check(self.lib, self.ctx, self.lib.zigp_prior_kl(self.ctx, C.byref(pk.struct), float(jitter), ptr(out)))
         return out
@@ -777,6 +809,23 @@ class DenseEngine:
             s.out9 = ptr(out['out9'])
         fn = self.lib.zigp_test_pointwise_white if whiten else self.lib.zigp_test_pointwise
         _check(self.lib, self.ctx, fn(self.ctx, C.byref(s)))
+        return out
+
+    def test_q_full_forward(self, W, Lq, u):
+        """Forward M x M stage of a full-covariance call for one latent (zigp_test_q_full_forward): returns (T - I, R^T = (T - I) W, KL)
+        for T = tril(Lq) tril(Lq)^T."""
+        W, Lq, u = as_f64(W), as_f64(Lq), as_f64(u).reshape(-1)
+        M = W.shape[0]
+        TmI, Rt, kl = np.zeros((M, M)), np.zeros((M, M)), np.zeros(1)
+        _check(self.lib, self.ctx, self.lib.zigp_test_q_full_forward(self.ctx, M, ptr(W), ptr(Lq), ptr(u), ptr(TmI), ptr(Rt), ptr(kl)))
+        return TmI, Rt, float(kl[0])
+
+    def test_q_full_dlq(self, C1, Lq, include_kl=True):
+        """dLq = tril(2 C1 Lq) - [include_kl] (tril(Lq) - diag(1 / Lq_ii)) as the reverse M x M stage forms it (zigp_test_q_full_dlq)."""
+        C1, Lq = as_f64(C1), as_f64(Lq)
+        M = C1.shape[0]
+        out = np.zeros((M, M))
+        _check(self.lib, self.ctx, self.lib.zigp_test_q_full_dlq(self.ctx, M, ptr(C1), ptr(Lq), 1 if include_kl else 0, ptr(out)))
         return out
 
     def test_kgrad(self, Jp, K, alpha, gm, gv, X, Z, n0=0, ell=None, centre=None, exact=None, krow=None):

@@ -30,6 +30,11 @@ class P:
     def free(self):
         return np.asarray(self.transform.backward(self.value), dtype=np.float64).reshape(-1)
 
+    def free_size(self):
+        """entries of the free vector: the value's size unless the transform says otherwise (LowerTriangular: N(N+1)/2 for N x N)"""
+        fs = getattr(self.transform, 'free_size', None)
+        return int(fs()) if fs is not None else self.value.size
+
     def set_free(self, x):
         self.value = np.asarray(self.transform.forward(x), dtype=np.float64).reshape(self.value.shape)
 
@@ -50,7 +55,7 @@ class ParamSet:
         o = 0
         for k in self.names():
             p = self.params[k]
-            n = p.value.size
+            n = p.free_size()
             p.set_free(np.asarray(x[o:o + n]))
             o += n
 
@@ -91,8 +96,8 @@ class AdamGroups:
         self.pset = pset
         self.b1, self.b2, self.eps = beta1, beta2, eps
         self.t = 0
-        self.m = {k: np.zeros(pset.params[k].value.size) for k in pset.names()}
-        self.v = {k: np.zeros(pset.params[k].value.size) for k in pset.names()}
+        self.m = {k: np.zeros(pset.params[k].free_size()) for k in pset.names()}
+        self.v = {k: np.zeros(pset.params[k].free_size()) for k in pset.names()}
         self.resync()
 
     def resync(self, reset=False):
@@ -113,7 +118,7 @@ class AdamGroups:
         for k in self.pset.names():
             p = self.pset.params[k]
             if k not in self.m:                                    # un-fixed since construction: it joins with fresh moments
-                self.m[k], self.v[k] = np.zeros(p.value.size), np.zeros(p.value.size)
+                self.m[k], self.v[k] = np.zeros(p.free_size()), np.zeros(p.free_size())
                 self._written[k] = None
             if self._written[k] is None or not np.array_equal(p.value, self._written[k], equal_nan=True):   # changed behind our back: start from what the ParamSet holds now
                 self.x[k] = p.free().copy()

@@ -43,3 +43,38 @@ class Log1pe:
 
 
 positive = Log1pe()
+
+
+class LowerTriangular:
+    """GPflow 0.4.0 `transforms.LowerTriangular(N)` for one matrix (num_latent = 1; onoffgpf/OnOffSVGP.py:65-71): the free vector holds
+    the N(N+1)/2 entries of the lower triangle in row-major order -- the diagonal unconstrained, as in GPflow -- and the value is the
+    (N, N) matrix (or (N, N, 1): the trailing axis of length 1 does not change the order) with an exactly zero strict upper triangle.
+    The free size differs from the value's size: `free_size` tells ParamSet / AdamGroups.  [GPflow-recall; SURVEY.md a9]"""
+
+    def __init__(self, N):
+        self.N = int(N)
+        self._rows, self._cols = np.tril_indices(self.N)      # row-major order of the lower triangle
+
+    def free_size(self):
+        return self.N * (self.N + 1) // 2
+
+    def forward(self, x):
+        x = np.asarray(x, dtype=np.float64).reshape(-1)
+        if x.size != self.free_size():
+            raise ValueError('LowerTriangular(%d): the free vector has %d entries, not %d' % (self.N, self.free_size(), x.size))
+        y = np.zeros((self.N, self.N))
+        y[self._rows, self._cols] = x
+        return y
+
+    def backward(self, y):
+        y = np.asarray(y, dtype=np.float64)
+        if y.size != self.N * self.N:
+            raise ValueError('LowerTriangular(%d): the value must be (%d, %d)' % (self.N, self.N, self.N))
+        return y.reshape(self.N, self.N)[self._rows, self._cols]
+
+    def grad_free(self, x, dy):
+        """dL/dx given dL/dy: the lower-triangle entries of dy (whatever dy holds above the diagonal has no free variable)."""
+        return np.asarray(dy, dtype=np.float64).reshape(self.N, self.N)[self._rows, self._cols]
+
+    def __repr__(self):
+        return 'LowerTriangular(%d)' % self.N
