@@ -238,7 +238,7 @@ int zigp_kron_fit_steps(zigp_ctx* ctx, const zigp_kron_params* shape, const zigp
                         int64_t t0, int32_t n_steps, const int64_t* row_begin, int64_t batch,
                         const double* Xw, const double* Yw, double jitter, double scale, int32_t include_kl,
                         double* elbo_data, double* kl);
-/* Updates applied by the LAST zigp_kron_fit_steps call of this context: n_steps after a call that returned 0, the k steps before the failing
+/* Updates applied by the LAST zigp_kron_fit_steps or zigp_kron_head_fit_steps call of this context (one counter for both): n_steps after a call that returned 0, the k steps before the failing
  * one after ZIGP_ENOTPD, 0 when the call ended before its first step (bad argument, HIP error).  This -- not a scan of the history for
  * NaN: an applied step may itself have a non-finite ELBO -- is what the caller's iteration count and Adam's bias correction advance by. */
 int64_t zigp_kron_fit_steps_applied(zigp_ctx* ctx);
@@ -298,6 +298,41 @@ int zigp_get_q_full(zigp_ctx* ctx);
 int zigp_kron_head_elbo(zigp_ctx* ctx, const zigp_kron_params* p, int32_t lik, const double* X, const double* Y,
                         int64_t N, double jitter, double scale, double f_mu, int32_t include_kl,
                         double* elbo_data, double* kl, zigp_kron_grads* grads, double* d_f_mu);
+/* The same bound on rows [row_begin, row_end) of the RESIDENT data set (zigp_set_data / zigp_set_data_device, D = D0 + D1): the
+ * single-latent companion of zigp_kron_elbo_rows -- no minibatch upload, same numbers as zigp_kron_head_elbo on those rows; grids beyond
+ * the fused kernels take the panel path with a device-to-device copy of the rows, an empty range is a zero data term. */
+int zigp_kron_head_elbo_rows(zigp_ctx* ctx, const zigp_kron_params* p, int32_t lik, int64_t row_begin, int64_t row_end,
+                             double jitter, double scale, double f_mu, int32_t include_kl,
+                             double* elbo_data, double* kl, zigp_kron_grads* grads, double* d_f_mu);
+
+/* The Adam fit loop of the heads on the device: replaces the training loops of scripts/svgp.py:240-330, scripts/classifier.py:276-316 and
+ * the regression loop of scripts/hurdle.py (its classifier loop is classifier.py's) for n_steps consecutive iterations -- the gradient of
+ * cost = -(scale * sum var_exp - KL), the Log1pe chain and one Adam per learning rate run in kernels, the steps are enqueued back to back
+ * and the host synchronises once per call.  Call semantics are those of zigp_kron_fit_steps, word for word (shape: sizes M0f, M1f, D0, D1
+ * only; free_state / adam_m / adam_v in/out; t0; row_begin[i] >= 0 selects rows of the resident set, -(1 + k) host batch k of Xw / Yw;
+ * elbo_data / kl are the history, each entry taken BEFORE its step's update; a Cholesky failure in step k returns ZIGP_ENOTPD with the
+ * state before that step, NaN history from k on and k in zigp_kron_fit_steps_applied -- the two fit loops share that counter; a
+ * communicator is honoured as there).  Block order of free_state (ZIGP_HEAD_FIT_BLOCKS = 10, all always present, so n_free =
+ * M0 D0 + M1 D1 + 2 M0 M1 + D0 + D1 + 4): Z0 (M0 x D0), Z1 (M1 x D1), u_m (M0 M1), u_s_sqrt (M0 M1), ell0 (D0), ell1 (D1), var0, var1,
+ * noise (ignored by the Bernoulli head), f_mu (the constant of classifier.py:70-72,136-137).  A block with trainable = 0 keeps its x, m, v;
+ * its value is the transform of its free entry: an absent f_mu is an untrainable block with free value 0, the classifier's noise an
+ * untrainable block with any positive value.
+ * ZIGP_EARG, with nothing enqueued and the state untouched: lik neither ZIGP_LIK_GAUSSIAN nor ZIGP_LIK_BERNOULLI, a grid beyond the
+ * fused kernels (step it with zigp_kron_head_elbo_rows and a host optimiser), a wrong n_free, a row range outside the resident set, NULL
+ * arguments, bad Adam constants. */
+#define ZIGP_HEAD_FIT_BLOCKS 10
+typedef struct {
+  double lr[ZIGP_HEAD_FIT_BLOCKS];          /* Adam learning rate of each block */
+  int32_t positive[ZIGP_HEAD_FIT_BLOCKS];   /* 1: value = log(1 + exp(x)) + 1e-6 (Log1pe), 0: value = x */
+  int32_t trainable[ZIGP_HEAD_FIT_BLOCKS];  /* 0: the block is not updated */
+  double beta1, beta2, eps;                 /* TensorFlow's defaults: 0.9, 0.999, 1e-8 */
+} zigp_kron_head_fit_opts;
+int zigp_kron_head_fit_steps(zigp_ctx* ctx, const zigp_kron_params* shape, int32_t lik, const zigp_kron_head_fit_opts* opts,
+                             double* free_state, double* adam_m, double* adam_v, int64_t n_free,
+                             int64_t t0, int32_t n_steps, const int64_t* row_begin, int64_t batch,
+                             const double* Xw, const double* Yw, double jitter, double scale, int32_t include_kl,
+                             double* elbo_data, double* kl);
+
 /* Replaces predict_svgp / predict_scgp (onofftf/svgppred.py:15-203, onofftf/svcppred.py:15-224).  out4 = 4 x N rows:
  * fmean, fvar, pfmean, pfvar.  Bernoulli: pfmean = probit(fmean / sqrt(1 + fvar)), pfvar = pfmean - pfmean^2
  * (svcppred.py "pfmean"/"pfvar"); Gaussian: pfmean = fmean, pfvar = fvar + noise (svgppred.py returns rows 0-1). */
@@ -310,7 +345,7 @@ int zigp_kron_head_predict(zigp_ctx* ctx, const zigp_kron_params* p, int32_t lik
  * device, on the library's stream (RCCL over xGMI; ~82 KB at M = 1024, D = 3).  RCCL is bound at run time (librccl.so.1).
  *   rank 0:      zigp_comm_unique_id(id)  -> send the 128 bytes to the other ranks by any means (torch.distributed broadcast, MPI, a file)
  *   every rank:  zigp_comm_init(ctx, rank, nranks, id)       (collective: returns when all ranks have joined)
- * From then on zigp_elbo, zigp_kron_elbo, zigp_kron_elbo_rows and zigp_kron_head_elbo return the SUM over ranks of elbo_data, kl, grads
+ * From then on zigp_elbo, zigp_kron_elbo, zigp_kron_elbo_rows, zigp_kron_head_elbo and zigp_kron_head_elbo_rows return the SUM over ranks of elbo_data, kl, grads
  * (and d_f_mu, the mean-function gradient) on every rank: each rank passes its own rows and include_kl = (rank == 0), so that the KL
  * and its gradient are counted once.  Every rank must make the same calls in the same order with the same model sizes.  Prediction
  * entry points are unaffected.  A Cholesky failure is reported by every rank (their Kuu are identical), after the exchange. */

@@ -141,7 +141,7 @@ struct zigp_ctx : zigp::CtxHandles {
   int device = 0;
   std::string err;
   int info = 0;
-  int64_t fit_steps_applied = 0;       // zigp_kron_fit_steps: updates applied by the LAST call (all of them, or the ones before a failing step)
+  int64_t fit_steps_applied = 0;       // zigp_kron_fit_steps / zigp_kron_head_fit_steps: updates applied by the LAST call (all of them, or the ones before a failing step)
   int64_t chunk = 32768;
   bool chunk_auto = true;                // no zigp_set_chunk yet: the chunk follows M (32768 rows at M = 1024, more for smaller M)
   // data

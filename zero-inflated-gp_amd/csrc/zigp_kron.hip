@@ -146,21 +146,26 @@ k_kron_pointwise(KronPwArgs p) {
 // with fm = kron mean + f_mu (classifier.py:136-137).  acc[b] = {ve, d noise, sum gv, 0, sum gm (= d f_mu)}.
 // Predict rows (ld = N): fmean, fvar, pfmean, pfvar -- Gaussian: pfmean = fm, pfvar = fv + s2 (density of y);
 // Bernoulli: pfmean = p, pfvar = p - p^2 (classifier.py:140).
-template <bool PREDICT>
+// DEVHYP (the steps of a fit call, zigp_kron_head_fit_steps): Knn = var_0 var_1, the noise and f_mu come from the device hyperparameter
+// block the previous step's update wrote (KH_VAR of the two factor records, KH_NOISE, KH_FMU) instead of the by-value fields.
+template <bool PREDICT, bool DEVHYP>
 __global__ void __launch_bounds__(PW_THREADS)
 k_kron_head_pointwise(KronPwArgs p, int lik) {
   __shared__ double sh[4];
   const int64_t n = (int64_t)blockIdx.x * PW_THREADS + threadIdx.x;
+  const double knn_f = DEVHYP ? KF_CONST(p.hyp)[KH_VAR] * KF_CONST(p.hyp)[KH_FAC + KH_VAR] : p.knn_f;
+  const double noise = DEVHYP ? KF_CONST(p.hyp)[KH_NOISE] : p.noise;
+  const double f_offset = DEVHYP ? KF_CONST(p.hyp)[KH_FMU] : p.f_offset;
   const double q0 = p.part_f[n], q1 = p.part_f[p.Nc + n];
-  const double fm = p.part_f[2 * p.Nc + n] + p.f_offset, fv = p.knn_f - q0 * q1 + p.part_f[3 * p.Nc + n];
+  const double fm = p.part_f[2 * p.Nc + n] + f_offset, fv = knn_f - q0 * q1 + p.part_f[3 * p.Nc + n];
   const bool valid = n < p.N;
   const double y = (valid && p.Y) ? p.Y[n] : 0.0;
   double ve, dfm, dfv, dnoise = 0.0, pm, pv;
   if (lik == ZIGP_LIK_GAUSSIAN) {
-    const double inv = 1.0 / p.noise, res = y - fm, q = res * res + fv;
-    ve = -0.5 * 1.8378770664093454836 - 0.5 * log(p.noise) - 0.5 * q * inv;
+    const double inv = 1.0 / noise, res = y - fm, q = res * res + fv;
+    ve = -0.5 * 1.8378770664093454836 - 0.5 * log(noise) - 0.5 * q * inv;
     dfm = res * inv; dfv = -0.5 * inv; dnoise = -0.5 * inv + 0.5 * q * inv * inv;
-    pm = fm; pv = fv + p.noise;
+    pm = fm; pv = fv + noise;
   } else {
     const double c1 = 1.0 - 2.e-3, c0 = 1.e-3;
     const double r = 1.0 / sqrt(1.0 + fv), z = fm * r;
@@ -646,14 +651,14 @@ int kron_run_panels(zigp_ctx* c, const zigp_kron_params* p, const double* X, con
     ZIGP_ENSURE(c, ks.out9, (size_t)rows * N);
     a.out9 = ks.out9.p;
     if (nlat == 2) hipLaunchKernelGGL(k_kron_pointwise<true>, dim3(blocks), dim3(PW_THREADS), 0, c->stream, a);
-    else hipLaunchKernelGGL(k_kron_head_pointwise<true>, dim3(blocks), dim3(PW_THREADS), 0, c->stream, a, lik);
+    else hipLaunchKernelGGL((k_kron_head_pointwise<true, false>), dim3(blocks), dim3(PW_THREADS), 0, c->stream, a, lik);
     ZIGP_HIP(c, hipGetLastError());
     ZIGP_HIP(c, hipMemcpyAsync(out9, ks.out9.p, sizeof(double) * rows * N, hipMemcpyDeviceToHost, c->stream));
     ZIGP_HIP(c, hipStreamSynchronize(c->stream));
     return info_result(c, hinfo, "a Kronecker factor of Kuu");
   }
   if (nlat == 2) hipLaunchKernelGGL(k_kron_pointwise<false>, dim3(blocks), dim3(PW_THREADS), 0, c->stream, a);
-  else hipLaunchKernelGGL(k_kron_head_pointwise<false>, dim3(blocks), dim3(PW_THREADS), 0, c->stream, a, lik);
+  else hipLaunchKernelGGL((k_kron_head_pointwise<false, false>), dim3(blocks), dim3(PW_THREADS), 0, c->stream, a, lik);
   ZIGP_HIP(c, hipGetLastError());
   double* hacc = nullptr;
   ZIGP_TRY(download(c, ks.acc.p, (size_t)blocks * KPW_ACC, &hacc));
@@ -812,8 +817,38 @@ int zigp_kron_fit_steps(zigp_ctx* c, const zigp_kron_params* p, const zigp_kron_
     if (row_begin[i] >= 0 ? row_begin[i] + batch > c->N : (!Xw || !Yw)) return fail_arg(c, "zigp_kron_fit_steps: a row range leaves the resident data set (or a host batch without Xw / Yw)");
   }
   ZIGP_HIP(c, hipSetDevice(c->device));
-  KfFitCall fit = {opts, free_state, adam_m, adam_v, n_free, t0, (int)n_steps, row_begin, batch, Xw, Yw, elbo_data, kl};
+  KfFitCall fit = {"zigp_kron_fit_steps", false, opts->lr, opts->positive, nullptr, opts->beta1, opts->beta2, opts->eps,
+                   free_state, adam_m, adam_v, n_free, t0, (int)n_steps, row_begin, batch, Xw, Yw, elbo_data, kl};
   return kronf_run(c, p, c->dX, c->dY, batch, jitter, scale, 0.0, 0.0, include_kl, false, nullptr, nullptr, nullptr, nullptr, ZIGP_LIK_ONOFF, nullptr, true, &fit);
+}
+
+int zigp_kron_head_fit_steps(zigp_ctx* c, const zigp_kron_params* p, int32_t lik, const zigp_kron_head_fit_opts* opts, double* free_state,
+                             double* adam_m, double* adam_v, int64_t n_free, int64_t t0, int32_t n_steps, const int64_t* row_begin, int64_t batch,
+                             const double* Xw, const double* Yw, double jitter, double scale, int32_t include_kl, double* elbo_data, double* kl) {
+  if (!c) return ZIGP_EARG;
+  c->fit_steps_applied = 0;      // whatever ends this call early, no update of it has been applied
+  if (!p || !opts || !free_state || !adam_m || !adam_v || !row_begin) return fail_arg(c, "zigp_kron_head_fit_steps: NULL argument");
+  if (lik != ZIGP_LIK_GAUSSIAN && lik != ZIGP_LIK_BERNOULLI)
+    return fail_arg(c, "zigp_kron_head_fit_steps: the likelihood must be ZIGP_LIK_GAUSSIAN or ZIGP_LIK_BERNOULLI (the OnOff fit is zigp_kron_fit_steps)");
+  if (p->M0f <= 0 || p->M1f <= 0) return fail_arg(c, "inducing counts must be positive");
+  if (p->D0 <= 0 || p->D1 <= 0 || p->D0 > MAXD || p->D1 > MAXD) return fail_arg(c, "factor dimensions must be in [1, 8]");
+  if (n_steps <= 0 || batch <= 0 || t0 < 0) return fail_arg(c, "zigp_kron_head_fit_steps: need n_steps > 0, batch > 0, t0 >= 0");
+  if (!(jitter >= 0)) return fail_arg(c, "zigp_kron_head_fit_steps: jitter must be >= 0");
+  if (!(opts->beta1 >= 0 && opts->beta1 < 1 && opts->beta2 >= 0 && opts->beta2 < 1 && opts->eps > 0)) return fail_arg(c, "zigp_kron_head_fit_steps: bad Adam constants");
+  if (!c->dX) return fail_arg(c, "zigp_kron_head_fit_steps: no data set (call zigp_set_data first)");
+  if (p->D0 + p->D1 != c->D) return fail_arg(c, "zigp_kron_head_fit_steps: D0 + D1 differs from the data's D");
+  if (c->kron_panels || !kf_eligible(p, 1))
+    return fail_arg(c, "zigp_kron_head_fit_steps: this inducing grid is beyond the fused Kronecker kernels (<= 32 x <= 32 or <= 16 x <= 112 points): "
+                       "step it with zigp_kron_head_elbo_rows and a host optimiser");
+  if (n_free != (int64_t)p->M0f * p->D0 + (int64_t)p->M1f * p->D1 + 2 * (int64_t)p->M0f * p->M1f + p->D0 + p->D1 + 4)
+    return fail_arg(c, "zigp_kron_head_fit_steps: n_free does not match the model sizes");
+  for (int i = 0; i < n_steps; ++i) {
+    if (row_begin[i] >= 0 ? row_begin[i] + batch > c->N : (!Xw || !Yw)) return fail_arg(c, "zigp_kron_head_fit_steps: a row range leaves the resident data set (or a host batch without Xw / Yw)");
+  }
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  KfFitCall fit = {"zigp_kron_head_fit_steps", true, opts->lr, opts->positive, opts->trainable, opts->beta1, opts->beta2, opts->eps,
+                   free_state, adam_m, adam_v, n_free, t0, (int)n_steps, row_begin, batch, Xw, Yw, elbo_data, kl};
+  return kronf_run(c, p, c->dX, c->dY, batch, jitter, scale, 0.0, 0.0, include_kl, false, nullptr, nullptr, nullptr, nullptr, lik, nullptr, true, &fit);
 }
 
 int64_t zigp_kron_fit_steps_applied(zigp_ctx* c) { return c ? c->fit_steps_applied : (int64_t)ZIGP_EARG; }
@@ -837,6 +872,24 @@ int zigp_kron_head_elbo(zigp_ctx* c, const zigp_kron_params* p, int32_t lik, con
   ZIGP_HIP(c, hipSetDevice(c->device));
   if (N == 0) return kron_run(c, p, kron_no_rows, kron_no_rows, 1, jitter, 0.0, 0.0, f_mu, include_kl, false, nullptr, elbo_data, kl, grads, lik, d_f_mu);
   return kron_run(c, p, X, Y, N, jitter, scale, 0.0, f_mu, include_kl, false, nullptr, elbo_data, kl, grads, lik, d_f_mu);
+}
+
+int zigp_kron_head_elbo_rows(zigp_ctx* c, const zigp_kron_params* p, int32_t lik, int64_t row_begin, int64_t row_end, double jitter, double scale,
+                             double f_mu, int32_t include_kl, double* elbo_data, double* kl, zigp_kron_grads* grads, double* d_f_mu) {
+  if (!c) return ZIGP_EARG;
+  if (lik == ZIGP_LIK_ONOFF) return fail_arg(c, "zigp_kron_head_elbo_rows: use zigp_kron_elbo_rows for the OnOff likelihood");
+  ZIGP_TRY(validate_kron(c, p, lik));
+  if (!(jitter >= 0)) return fail_arg(c, "zigp_kron_head_elbo_rows: jitter must be >= 0");
+  if (row_begin == row_end && row_begin >= 0 && row_begin <= c->N) {     // an empty range (an empty shard of a data-parallel run): zero data term, same calls as its peers
+    ZIGP_HIP(c, hipSetDevice(c->device));
+    return kron_run(c, p, kron_no_rows, kron_no_rows, 1, jitter, 0.0, 0.0, f_mu, include_kl, false, nullptr, elbo_data, kl, grads, lik, d_f_mu);
+  }
+  if (!c->dX) return fail_arg(c, "zigp_kron_head_elbo_rows: no data set (call zigp_set_data first)");
+  if (p->D0 + p->D1 != c->D) return fail_arg(c, "zigp_kron_head_elbo_rows: D0 + D1 differs from the data's D");
+  if (row_begin < 0 || row_end > c->N || row_begin > row_end) return fail_arg(c, "zigp_kron_head_elbo_rows: bad row range");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  return kron_run(c, p, c->dX + row_begin * c->D, c->dY + row_begin, row_end - row_begin, jitter, scale, 0.0, f_mu, include_kl, false, nullptr,
+                  elbo_data, kl, grads, lik, d_f_mu, true);
 }
 
 int zigp_kron_head_predict(zigp_ctx* c, const zigp_kron_params* p, int32_t lik, const double* Xnew, int64_t N, double jitter, double f_mu,

@@ -1157,13 +1157,19 @@ k_kron_pw_reduce(const double* __restrict__ acc, int blocks, double kl_counted, 
 // the kernels read is produced ON THE DEVICE from the free state (k_fit_update), so n steps are enqueued back to back on one stream and
 // the host synchronises once per call.  Block order of the flat free-state vector (ZIGP_FIT_BLOCKS = 17): for latent f, then g:
 // Z0, Z1, u, s, ell0, ell1, var0, var1; then the likelihood variance.
+// The single-latent heads (zigp_kron_head_fit_steps; svgp.py:240-330, classifier.py:276-316, the regression loop of hurdle.py) run the same
+// steps with nlat = 1 and the HEAD instantiation of the update kernel: ZIGP_HEAD_FIT_BLOCKS = 10 blocks -- the eight of latent f, the
+// likelihood variance (-> KH_NOISE, gradient pws[1]) and f_mu (-> KH_FMU, gradient pws[4]) -- of which any may be untrainable.
 constexpr int KFIT_BLOCKS = ZIGP_FIT_BLOCKS;
+static_assert(ZIGP_HEAD_FIT_BLOCKS <= KFIT_BLOCKS, "the head layout uses the first blocks of the descriptor");
 struct KfFitDesc {
   int off[KFIT_BLOCKS], n[KFIT_BLOCKS], dst[KFIT_BLOCKS], positive[KFIT_BLOCKS];   // offset in the free vector, size, offset in the parameter image
+  int trainable[KFIT_BLOCKS];   // HEAD only: 0 = the block keeps its x, m, v (its value is still the transform of its free entry)
   double lr[KFIT_BLOCKS];
   int nlat, D0, D1, M[2][2], Mq[2][2];
   int off_z[2][2], off_hyp, off_hyp2;          // parameter image; the two hyperparameter blocks (step i reads block i % 2, its update writes the other)
   int big_blk[8], big_off[9], hyp_blk[9], hyp_off[10];   // thread -> element map of k_fit_update: the big blocks (Z, u, s) in order, then the hyperparameter blocks in a workgroup of their own
+                                                         // (a layout with fewer blocks repeats the total in the offsets it does not use)
   int res_size, res_krow0, res_krow1, res_gu, res_gs, res_pws, res_info;   // result block (doubles)
   double beta1, beta2, eps;
 };
@@ -1198,17 +1204,27 @@ __device__ __forceinline__ int kfit_element(const KfFitDesc& d, int& i) {
   return blk[k];
 }
 
+// kind of block b: 0 Z0, 1 Z1, 2 u, 3 s, 4 ell0, 5 ell1, 6 var0, 7 var1, 8 noise, 9 f_mu (HEAD only: there the block index is the kind)
+template <bool HEAD>
+__device__ __forceinline__ int kfit_kind(int b, int& h) {
+  if (HEAD) { h = 0; return b; }
+  h = b / 8;
+  return b == KFIT_BLOCKS - 1 ? 8 : b % 8;
+}
+
 // value of element (block b, index i) into the parameter image: plain blocks are copied, the hyperparameter blocks fill their records of
 // the hyper block Hn the NEXT step reads (the block the current step was evaluated at stays intact: two blocks, used in turn)
+template <bool HEAD>
 __device__ __forceinline__ void kfit_store_value(const KfFitArgs& a, double* Hn, int b, int i, double val) {
 #pragma clang fp contract(off)
   const KfFitDesc& d = a.d;
-  const int kind = b == KFIT_BLOCKS - 1 ? 8 : b % 8;      // 0 Z0, 1 Z1, 2 u, 3 s, 4 ell0, 5 ell1, 6 var0, 7 var1, 8 noise
-  const int h = b / 8;
+  int h;
+  const int kind = kfit_kind<HEAD>(b, h);
   if (kind <= 3) a.img[d.dst[b] + i] = val;
   else if (kind <= 5) { double* R = Hn + (2 * h + (kind - 4)) * KH_FAC; R[KH_ELL + i] = val; R[KH_INV + i] = 1.0 / val; }
   else if (kind <= 7) Hn[(2 * h + (kind - 6)) * KH_FAC + KH_VAR] = val;
-  else Hn[KH_NOISE] = val;
+  else if (kind == 8) Hn[KH_NOISE] = val;
+  else Hn[KH_FMU] = val;
 }
 
 // Grid: KFIT_THREADS-wide workgroups, one element of the free vector per thread (the update is ~300 fp64 instructions per element --
@@ -1217,6 +1233,10 @@ __device__ __forceinline__ void kfit_store_value(const KfFitArgs& a, double* Hn,
 // in the element order handled by the last workgroup, which also writes the history entry and the failure record.
 constexpr int KFIT_MROWS = 16 * 7;       // most inducing rows per factor on the fused path (kf_plan)
 constexpr int KFIT_THREADS = 256;
+// HEAD: the single-latent block layout (see KfFitDesc) -- the noise takes pws[1], f_mu takes pws[4] (the sum of the fmean cotangents), and a
+// block with trainable = 0 only re-derives its value (the hyperparameter block it lives in changes every step).  The on/off instantiation
+// (!HEAD) is the kernel as it was: same element map, same operations in the same order.
+template <bool HEAD>
 __global__ void __launch_bounds__(KFIT_THREADS)
 k_fit_update(KfFitArgs a) {
   const KfFitDesc& d = a.d;
@@ -1227,7 +1247,7 @@ k_fit_update(KfFitArgs a) {
   const int b = kfit_element(d, i);
   const int e = b >= 0 ? d.off[b] + i : 0;
   if (!a.update) {                       // first launch of a call: free state -> parameter image
-    if (b >= 0) kfit_store_value(a, Hn, b, i, kfit_value(d, b, a.x[e]));
+    if (b >= 0) kfit_store_value<HEAD>(a, Hn, b, i, kfit_value(d, b, a.x[e]));
     return;
   }
   __shared__ int s_fail;
@@ -1257,7 +1277,7 @@ k_fit_update(KfFitArgs a) {
   double x = 0.0, mv = 0.0, vv = 0.0, gnum = 0.0, aux = 1.0;
   const double* pws = a.res + d.res_pws;
   if (b >= 0) {
-    kind = b == KFIT_BLOCKS - 1 ? 8 : b % 8; h = b / 8;
+    kind = kfit_kind<HEAD>(b, h);
     const double* R = a.res + h * d.res_size;
     x = a.x[e]; mv = a.m[e]; vv = a.v[e];
     if (kind <= 1) {
@@ -1268,7 +1288,7 @@ k_fit_update(KfFitArgs a) {
     else if (kind == 3) gnum = R[d.res_gs + i];
     else if (kind <= 5) aux = Ho[(2 * h + (kind - 4)) * KH_FAC + KH_ELL + i];
     else if (kind <= 7) aux = Ho[(2 * h + (kind - 6)) * KH_FAC + KH_VAR];
-    else gnum = pws[1];
+    else gnum = pws[kind == 8 ? 1 : 4];      // d noise; HEAD: d f_mu = the sum of the fmean cotangents
   }
   __syncthreads();
   if (s_fail) return;             // a Cholesky failed in this or an earlier step of the call: the state stays as it was before that step
@@ -1302,19 +1322,24 @@ k_fit_update(KfFitArgs a) {
 #pragma clang fp contract(off)
     double gc;      // d ELBO / d (constrained value)
     if (kind <= 1) gc = gnum / (aux * aux);
-    else if (kind <= 3 || kind == 8) gc = gnum;
+    else if (kind <= 3 || kind >= 8) gc = gnum;
     else if (kind <= 5) gc = s_dl[h][kind - 4][i] / (aux * aux * aux);
     else gc = s_dv[h][kind - 6] / aux + pws[2 + h] * Ho[(2 * h + 1 - (kind - 6)) * KH_FAC + KH_VAR];   // Knn = var0 var1 enters var_n directly (scripts/onoff.py:196-200)
     // cost = -ELBO, chained through the transform, one Adam step (kfit_adam, zigp_kernels.h)
     double xnew = x, mnew = mv, vnew = vv;
-    kfit_adam(gc, d.positive[b] != 0, d.lr[b], KfitAdam{d.beta1, d.beta2, d.eps, a.lr_sq, a.lr_den}, xnew, mnew, vnew);
-    a.m[e] = mnew; a.v[e] = vnew; a.x[e] = xnew;
-    kfit_store_value(a, Hn, b, i, kfit_value(d, b, xnew));
+    if (!HEAD || d.trainable[b]) {
+      kfit_adam(gc, d.positive[b] != 0, d.lr[b], KfitAdam{d.beta1, d.beta2, d.eps, a.lr_sq, a.lr_den}, xnew, mnew, vnew);
+      a.m[e] = mnew; a.v[e] = vnew; a.x[e] = xnew;
+    }
+    kfit_store_value<HEAD>(a, Hn, b, i, kfit_value(d, b, xnew));
   }
 }
 
-struct KfFitCall {          // host side of one zigp_kron_fit_steps call
-  const zigp_kron_fit_opts* opts;
+struct KfFitCall {          // host side of one zigp_kron_fit_steps / zigp_kron_head_fit_steps call
+  const char* name;          // the entry point, for its messages
+  bool head;                 // single-latent block layout (ZIGP_HEAD_FIT_BLOCKS)
+  const double* lr; const int32_t* positive; const int32_t* trainable;   // per block; trainable: head only (nullptr = every block)
+  double beta1, beta2, eps;
   double *x, *m, *v; int64_t n_free;
   int64_t t0; int n_steps; const int64_t* row_begin; int64_t batch;
   const double *Xw, *Yw;     // host batches for steps with row_begin < 0 (batch -(1 + k) of them)
@@ -1510,7 +1535,7 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
     memset(&a, 0, sizeof(a));
     const int gl_ = nlat - 1;   // latent whose buffers stand in for g (unused by the single-latent kernels)
     a.part_f = pts(0); a.part_g = pts(gl_); a.Y = Yd; a.N = N; a.Nc = Npad;
-    a.hyp = d_hyp;              // knn_f, knn_g, noise: from the device block (the single-latent heads read the by-value fields below)
+    a.hyp = d_hyp;              // knn_f, knn_g, noise: from the device block (the single-latent heads outside a fit call read the by-value fields below)
     if (!fit) { a.knn_f = p->var0f * p->var1f; a.knn_g = p->var0g * p->var1g; a.noise = p->noise; }
     a.g_offset = g_offset; a.f_offset = f_mu; a.scale = scale;
     a.gm_f = need_grad ? pts(0) + 4 * Npad : nullptr; a.gv_f = pts(0) + 5 * Npad; a.gm_g = pts(gl_) + 4 * Npad; a.gv_g = pts(gl_) + 5 * Npad;
@@ -1521,12 +1546,13 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
       ZIGP_ENSURE(c, ks.out, (size_t)rows * N);
       a.out9 = ks.out.p;
       if (nlat == 2) hipLaunchKernelGGL(k_kron_pointwise<true>, dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a);
-      else hipLaunchKernelGGL(k_kron_head_pointwise<true>, dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a, lik);
+      else hipLaunchKernelGGL((k_kron_head_pointwise<true, false>), dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a, lik);
       ZIGP_HIP(c, hipGetLastError());
       return 0;
     }
     if (nlat == 2) hipLaunchKernelGGL(k_kron_pointwise<false>, dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a);
-    else hipLaunchKernelGGL(k_kron_head_pointwise<false>, dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a, lik);
+    else if (fit) hipLaunchKernelGGL((k_kron_head_pointwise<false, true>), dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a, lik);   // Knn, noise, f_mu: device block
+    else hipLaunchKernelGGL((k_kron_head_pointwise<false, false>), dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a, lik);
     if (!need_grad) hipLaunchKernelGGL(k_kron_pw_reduce, dim3(1), dim3(256), 0, c->stream, d_pwacc, pw_blocks, include_kl ? 1.0 : 0.0, ks.res.p + RES_PWS);
     ZIGP_HIP(c, hipGetLastError());
     if (need_grad) {
@@ -1635,34 +1661,37 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
     memset(&fa, 0, sizeof(fa));
     KfFitDesc& d = fa.d;
     d.nlat = nlat; d.D0 = D0; d.D1 = D1;
+    const bool head = fit->head;
+    const int nblocks = head ? ZIGP_HEAD_FIT_BLOCKS : KFIT_BLOCKS;
     size_t o = 0;
-    for (int h = 0; h < 2; ++h) {
+    auto block = [&](int b, int n, size_t dst) {
+      d.off[b] = (int)o; d.n[b] = n; d.dst[b] = (int)dst; d.positive[b] = fit->positive[b]; d.lr[b] = fit->lr[b];
+      d.trainable[b] = fit->trainable ? (fit->trainable[b] != 0) : 1;
+      o += n;
+    };
+    for (int h = 0; h < nlat; ++h) {
       const int M0 = hl[h].M[0], M1 = hl[h].M[1];
       const int sizes[8] = {M0 * D0, M1 * D1, M0 * M1, M0 * M1, D0, D1, 1, 1};
       const size_t dsts[8] = {off_z[h][0], off_z[h][1], off_u[h], off_s[h], 0, 0, 0, 0};
-      for (int k = 0; k < 8; ++k) {
-        const int b = 8 * h + k;
-        d.off[b] = (int)o; d.n[b] = sizes[k]; d.dst[b] = (int)dsts[k]; d.positive[b] = fit->opts->positive[b]; d.lr[b] = fit->opts->lr[b];
-        o += sizes[k];
-      }
+      for (int k = 0; k < 8; ++k) block(8 * h + k, sizes[k], dsts[k]);
       for (int q = 0; q < 2; ++q) { d.M[h][q] = hl[h].M[q]; d.Mq[h][q] = Mq[h][q]; d.off_z[h][q] = (int)off_z[h][q]; }
     }
-    d.off[16] = (int)o; d.n[16] = 1; d.dst[16] = 0; d.positive[16] = fit->opts->positive[16]; d.lr[16] = fit->opts->lr[16];
-    o += 1;
-    if ((int64_t)o != fit->n_free) { c->err = "zigp_kron_fit_steps: n_free does not match the model sizes"; return ZIGP_EARG; }
+    for (int b = 8 * nlat; b < nblocks; ++b) block(b, 1, 0);      // the likelihood variance (head: and f_mu)
+    if ((int64_t)o != fit->n_free) { c->err = std::string(fit->name) + ": n_free does not match the model sizes"; return ZIGP_EARG; }
     d.off_hyp = (int)off_hyp; d.off_hyp2 = (int)off_hyp2;
     {
       int nbig = 0, nhyp = 0, kb = 0, kh = 0;
-      for (int b = 0; b < KFIT_BLOCKS; ++b) {
-        const bool big = b != 16 && b % 8 <= 3;
+      for (int b = 0; b < nblocks; ++b) {
+        const bool big = b < 8 * nlat && b % 8 <= 3;
         if (big) { d.big_blk[kb] = b; d.big_off[kb++] = nbig; nbig += d.n[b]; }
         else { d.hyp_blk[kh] = b; d.hyp_off[kh++] = nhyp; nhyp += d.n[b]; }
       }
-      d.big_off[8] = nbig; d.hyp_off[9] = nhyp;
+      for (; kb <= 8; ++kb) d.big_off[kb] = nbig;      // kfit_element walks eight big and nine hyperparameter blocks: the ones a
+      for (; kh <= 9; ++kh) d.hyp_off[kh] = nhyp;      // layout does not have start at the total (no thread maps to them)
     }
     d.res_size = (int)RES_SIZE; d.res_krow0 = (int)RES_KROW0; d.res_krow1 = (int)RES_KROW1; d.res_gu = (int)RES_GU; d.res_gs = (int)RES_GS;
     d.res_pws = (int)RES_PWS; d.res_info = (int)RES_INFO;
-    d.beta1 = fit->opts->beta1; d.beta2 = fit->opts->beta2; d.eps = fit->opts->eps;
+    d.beta1 = fit->beta1; d.beta2 = fit->beta2; d.eps = fit->eps;
     const size_t nf = (size_t)fit->n_free, n_hist = (size_t)2 * fit->n_steps;
     const size_t n_state = 3 * nf + n_hist + 8;
     ZIGP_ENSURE(c, ks.fit, n_state);
@@ -1684,7 +1713,11 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
     ZIGP_HIP(c, hipMemsetAsync(ks.in.p + off_hyp, 0, sizeof(double) * 2 * KH_SIZE, c->stream));
     const dim3 ugrid((d.big_off[8] + KFIT_THREADS - 1) / KFIT_THREADS + 1);
     fa.update = 0; fa.step = 0;
-    hipLaunchKernelGGL(k_fit_update, ugrid, dim3(KFIT_THREADS), 0, c->stream, fa);       // free state -> parameter image (hyper block 0)
+    auto update = [&] {
+      if (head) hipLaunchKernelGGL(k_fit_update<true>, ugrid, dim3(KFIT_THREADS), 0, c->stream, fa);
+      else hipLaunchKernelGGL(k_fit_update<false>, ugrid, dim3(KFIT_THREADS), 0, c->stream, fa);
+    };
+    update();       // free state -> parameter image (hyper block 0)
     ZIGP_HIP(c, hipGetLastError());
     fa.update = 1;
     for (int i = 0; i < fit->n_steps; ++i) {
@@ -1696,7 +1729,7 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
       // lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t), t counted from 1 (zigp/optim.py AdamGroups.step): the two t-dependent factors from the host
       const double t = (double)(fit->t0 + i + 1);
       fa.step = i; fa.lr_sq = std::sqrt(1.0 - std::pow(d.beta2, t)); fa.lr_den = 1.0 - std::pow(d.beta1, t);
-      hipLaunchKernelGGL(k_fit_update, ugrid, dim3(KFIT_THREADS), 0, c->stream, fa);
+      update();
       ZIGP_HIP(c, hipGetLastError());
     }
     double* hst = nullptr;
@@ -1711,9 +1744,9 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
       if (fit->hist_kl) fit->hist_kl[i] = i < done ? hst[3 * nf + 2 * i + 1] : NAN;
     }
     if (hfail[0]) {
-      char b[256];
-      snprintf(b, sizeof(b), "Cholesky failed in step %d of this zigp_kron_fit_steps call (iteration %lld): %s not positive definite at pivot %d; "
-               "the state returned is the one before that step", hfail[0] - 1, (long long)(fit->t0 + hfail[0] - 1), fac_names[hfail[1] & 3], hfail[2]);
+      char b[288];
+      snprintf(b, sizeof(b), "Cholesky failed in step %d of this %s call (iteration %lld): %s not positive definite at pivot %d; "
+               "the state returned is the one before that step", hfail[0] - 1, fit->name, (long long)(fit->t0 + hfail[0] - 1), fac_names[hfail[1] & 3], hfail[2]);
       c->err = b; c->info = hfail[2];
       return ZIGP_ENOTPD;
     }

@@ -1,7 +1,9 @@
 """Single-latent Kronecker SVGP models shared by the reference's baselines: the parameter set that scripts/svgp.py:51-112,
 scripts/hurdle.py:64-124 and scripts/classifier.py:56-112 declare (TF scopes f_kern/, likelihood/, f_ind/), the Adam fit loop
 of svgp.py:240-330 and the restore-and-predict step of onofftf/svgppred.py / onofftf/svcppred.py -- on libzigp's
-zigp_kron_head_elbo / zigp_kron_head_predict (include/zigp.h)."""
+zigp_kron_head_fit_steps / zigp_kron_head_elbo / zigp_kron_head_predict (include/zigp.h).  The fit loop runs on the device
+(`HeadDeviceFit`, one host synchronisation per 100 iterations); `fit_head(..., device_loop=False)` steps it from the host with
+zigp.optim.AdamGroups, one call per iteration (the checker of the device loop)."""
 import logging
 import os
 import time
@@ -69,14 +71,171 @@ def named_head_grads(g):
     return out
 
 
-def fit_head(pset, lik, Xtrain, Ytrain, num_iter, num_minibatch, logger, ckpt=None, eng=None, save_every=10000, history=None):
+# block order of zigp_kron_head_fit_steps' free-state vector (include/zigp.h): Z0, Z1, u, s, ell0, ell1, var0, var1, noise, f_mu
+HEAD_FIT_BLOCK_NAMES = ('f_ind/z_0', 'f_ind/z_1', 'f_ind/value', 'f_ind/variance', 'f_kern/lengthscale_0', 'f_kern/lengthscale_1',
+                        'f_kern/variance_0', 'f_kern/variance_1', 'likelihood/variance', 'f_mu')
+LOG_EVERY = 100         # fit_head's log cadence (the reference's heads print every 100 iterations, svgp.py:300)
+
+
+class HeadDeviceFit:
+    """The Adam state of a single-latent head fit in the layout of zigp_kron_head_fit_steps, for a ParamSet made by init_head_params --
+    the single-latent twin of onofftf.model.KronDeviceFit: the flat free state x and the moments m, v live here between calls (the
+    engine updates them in place), `steps` advances them on the device and writes the constrained values back into the ParamSet.
+    A fixed parameter is a block with trainable = 0: the device leaves its x, m, v alone and its .value is never written back.  All ten
+    blocks are always there: a ParamSet without `f_mu` (include_f_mu=False) gets an untrainable block with free value 0, one without
+    `likelihood/variance` (the classifier) an untrainable noise of 1 that the Bernoulli head never reads.  zigp.optim.AdamGroups on the
+    same ParamSet is the host-side checker."""
+
+    def __init__(self, engine, pset, lik, beta1=0.9, beta2=0.999, eps=1e-8):
+        if lik not in ('gaussian', 'bernoulli'):
+            raise ValueError("lik must be 'gaussian' or 'bernoulli', not %r" % (lik,))
+        self.engine, self.pset, self.lik = engine, pset, lik
+        self.beta1, self.beta2, self.eps = beta1, beta2, eps
+        missing = [k for k in HEAD_FIT_BLOCK_NAMES[:8] if k not in pset.params]
+        extra = [k for k in pset.params if k not in HEAD_FIT_BLOCK_NAMES]
+        if missing or extra:
+            raise ValueError('the head device fit loop trains the parameters of init_head_params (missing: %s; unknown: %s)'
+                             % (', '.join(missing) or '-', ', '.join(extra) or '-'))
+        if lik == 'gaussian' and 'likelihood/variance' not in pset.params:
+            raise ValueError("the Gaussian head needs the parameter 'likelihood/variance'")
+        for k, q in self._present():
+            if not isinstance(q.transform, Log1pe) and type(q.transform).__name__ != 'Identity':
+                raise ValueError('unsupported transform %r of %s' % (q.transform, k))
+            if isinstance(q.transform, Log1pe) and q.transform._lower != 1e-6:
+                raise ValueError('the device fit loop implements Log1pe with lower = 1e-6')
+        v = pset.params
+        Z0, Z1 = v['f_ind/z_0'].value, v['f_ind/z_1'].value
+        self.shape = dict(M0f=Z0.shape[0], M1f=Z1.shape[0], D0=Z0.shape[1], D1=Z1.shape[1])
+        M = Z0.shape[0] * Z1.shape[0]
+        want = [Z0.size, Z1.size, M, M, Z0.shape[1], Z1.shape[1], 1, 1, 1, 1]
+        self.sizes = want
+        for (k, q), n in zip(self._blocks(), want):
+            if q is not None and q.value.size != n:
+                raise ValueError('%s has %d entries, not %d' % (k, q.value.size, n))
+        self.positive = [q is not None and isinstance(q.transform, Log1pe) for k, q in self._blocks()]
+        self.m, self.v = np.zeros(sum(want)), np.zeros(sum(want))
+        self.t = 0
+        self.resync()
+
+    def _blocks(self):
+        return [(k, self.pset.params.get(k)) for k in HEAD_FIT_BLOCK_NAMES]
+
+    def _present(self):
+        return [(k, q) for k, q in self._blocks() if q is not None]
+
+    def _slices(self):
+        o = 0
+        for (k, q), n in zip(self._blocks(), self.sizes):
+            yield k, q, slice(o, o + n)
+            o += n
+
+    def steps(self, row_begin, batch, jitter, scale, Xw=None, Yw=None, include_kl=True):
+        """len(row_begin) iterations on the resident data set (engine.set_data): returns (elbo_data, kl) per step; the ParamSet holds the
+        constrained values after the last one.  If the engine raises in step k (a Cholesky failure), x / m / v are the state after the k
+        updates that WERE applied, self.t has advanced by k, and the exception carries `steps_applied`, `elbo_data`, `kl` of those steps.
+        The ParamSet is read again when something other than this object changed it since the last call (load_checkpoint, an assignment
+        to .value, a parameter fixed or un-fixed, a new learning rate): see resync()."""
+        if self._stale():
+            self.resync()
+        try:
+            out = self.engine.kron_head_fit_steps(self.shape, self.lik, self.x, self.m, self.v, self.lr, self.positive, self.trainable, self.t,
+                                                  row_begin, batch, jitter=jitter, scale=scale, Xw=Xw, Yw=Yw, beta1=self.beta1, beta2=self.beta2,
+                                                  eps=self.eps, include_kl=include_kl)
+            self.t += len(row_begin)
+        except Exception as e:
+            self.t += int(getattr(e, 'steps_applied', 0))
+            raise
+        finally:
+            self.sync_params()
+        return out
+
+    def _stale(self):
+        """did anyone else write the ParamSet since sync_params?  equal_nan: a parameter that HAS gone NaN is still the value this object
+        wrote (NaN != NaN must not turn every later call into a resync from free(NaN))"""
+        return (any(not np.array_equal(q.value, w, equal_nan=True) for (k, q), w in zip(self._present(), self._written))
+                or [q is not None and not q.fixed for k, q in self._blocks()] != self.trainable
+                or [float(q.learning_rate) if q is not None else 0.0 for k, q in self._blocks()] != self.lr)
+
+    def resync(self, reset=False):
+        """Take the free state, the fixed flags and the learning rates from the ParamSet again (after load_checkpoint or a manual
+        assignment).  Adam's moments and the iteration count are kept unless reset=True (parameters unrelated to the ones trained so
+        far: load_checkpoint(..., fitter=...) of another run)."""
+        # an absent block: f_mu = 0 (classifier.py:136-137 adds nothing); a noise of 1 for the head that has none (never read)
+        self.x = np.concatenate([q.free() if q is not None else np.array([1.0 if k == 'likelihood/variance' else 0.0]) for k, q in self._blocks()])
+        self.trainable = [q is not None and not q.fixed for k, q in self._blocks()]
+        self.lr = [float(q.learning_rate) if q is not None else 0.0 for k, q in self._blocks()]
+        if reset:
+            self.m[:] = 0.0
+            self.v[:] = 0.0
+            self.t = 0
+        self._written = [q.value.copy() for k, q in self._present()]
+
+    def sync_params(self):
+        for (k, q, sl), tr in zip(self._slices(), self.trainable):
+            if tr:
+                q.set_free(self.x[sl])
+        self._written = [q.value.copy() for k, q in self._present()]
+
+
+def head_device_loop_covers(num_inducing_f, D0=2, D1=1):
+    """the grids of the fused Kronecker kernels (<= 32 x <= 32 or <= 16 x <= 112 points, <= 7 columns per factor): what
+    zigp_kron_head_fit_steps accepts"""
+    m0, m1 = int(num_inducing_f[0]), int(num_inducing_f[1])
+    return ((m0 <= 32 and m1 <= 32) or (m0 <= 16 and m1 <= 112)) and D0 <= 7 and D1 <= 7
+
+
+def _device_loop(eng, pset, lik, train_data, num_iter, num_minibatch, scale, save_every, ckpt, logger, history):
+    """svgp.py:289-330 / classifier.py:276-316 with the loop body on the device (zigp_kron_head_fit_steps), run as
+    onofftf/onoff.py:_device_loop runs the on/off fit: the iterations between two log lines are ONE call.  The batch sequence is
+    DataSet's (onofftf/main.py:98-133): the permuted epoch is resident, a call ends at the one wrap-around batch of an epoch (its rows
+    go down with the call), at a checkpoint iteration, or after LOG_EVERY steps."""
+    fitter = HeadDeviceFit(eng, pset, lik)
+    resident, i = None, 0
+    while i < num_iter:
+        n_target = min(num_iter - i, LOG_EVERY - (i % LOG_EVERY))
+        if ckpt and save_every:
+            n_target = min(n_target, save_every - (i % save_every) if i % save_every else 1)       # a checkpoint iteration ends its call
+        t0 = time.time()
+        rbs, wrap = [], None
+        while len(rbs) < n_target:
+            gen, lo, hi, wrap = train_data.next_span(num_minibatch)
+            if wrap is not None:
+                rbs.append(-1)
+                break
+            if gen != resident:              # only ever at the start of a call: a generation changes right after a wrap-around batch
+                eng.set_data(train_data.xtrain, train_data.ytrain)
+                resident = gen
+            rbs.append(lo)
+        ed, kl = fitter.steps(rbs, num_minibatch, TRAIN_JITTER, scale, *(wrap if wrap is not None else (None, None)))
+        if history is not None:
+            history.extend((-(ed - kl)).tolist())
+        per_it = (time.time() - t0) / len(rbs)
+        for j in range(i, i + len(rbs)):
+            if j % LOG_EVERY == 0:
+                logger.info('{:>16d}'.format(j) + '{:>6.3f}'.format(per_it / 60))
+            if ckpt and save_every and j % save_every == 0:
+                save_checkpoint(pset, ckpt)
+        i += len(rbs)
+
+
+def fit_head(pset, lik, Xtrain, Ytrain, num_iter, num_minibatch, logger, ckpt=None, eng=None, save_every=10000, history=None,
+             device_loop=True):
     """The optimisation loop of svgp.py:289-330 / classifier.py:276-316: Adam per learning-rate group on
-    cost = -(sum(var_exp) * num_data / num_minibatch - kl)."""
+    cost = -(sum(var_exp) * num_data / num_minibatch - kl).  device_loop: run it on the device (_device_loop) where the inducing grid
+    is within the fused kernels; False, or a larger grid, steps it from the host, one engine call per iteration."""
     train_data = DataSet(Xtrain, Ytrain)                                          # svgp.py:43
     scale = float(Xtrain.shape[0]) / float(num_minibatch)                         # :212
-    opt = AdamGroups(pset)                                                        # :225-252
     logger.info('*******  started optimization at ' + time.strftime('%Y%m%d-%H%M') + ' *******')
     logger.info('{:>16s}'.format('iteration') + '{:>6s}'.format('time'))
+    Z0, Z1 = pset.params['f_ind/z_0'].value, pset.params['f_ind/z_1'].value
+    if (device_loop and num_iter > 0 and head_device_loop_covers((Z0.shape[0], Z1.shape[0]), Z0.shape[1], Z1.shape[1])
+            and num_minibatch <= Xtrain.shape[0]):
+        try:
+            _device_loop(eng, pset, lik, train_data, num_iter, num_minibatch, scale, save_every, ckpt, logger, history)
+        except KeyboardInterrupt:
+            print('Stopping training')
+        num_iter = 0
+    opt = AdamGroups(pset) if num_iter else None                                  # :225-252
     for i in range(num_iter):
         t0 = time.time()
         xb, yb = train_data.next_batch(num_minibatch)

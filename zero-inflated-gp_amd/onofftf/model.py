@@ -146,7 +146,7 @@ def save_checkpoint(pset, path):
 
 
 def load_checkpoint(pset, path, fitter=None, reset=True):
-    """Restore the ParamSet from the .npz written by save_checkpoint.  fitter: a KronDeviceFit / zigp.optim.AdamGroups stepping this
+    """Restore the ParamSet from the .npz written by save_checkpoint.  fitter: a KronDeviceFit / onofftf.heads.HeadDeviceFit / zigp.optim.AdamGroups stepping this
     ParamSet -- it takes the loaded values as its state at once and, with reset=True (the default: a checkpoint holds parameters, not
     Adam moments -- tf.train.Saver restores them only if they were saved, onofftf/utils.py:61-73 saves all variables of the graph; ours
     does not keep them), restarts its moments and iteration count instead of carrying those of the parameters it replaced."""

@@ -21,7 +21,7 @@ def mad(predict, actual):
 
 
 def hurdle(Xtrain, Ytrain, Xtest, Ytest, cresults, dir, num_iter=50000, num_inducing_f=(10, 100), num_minibatch=1000, device=0,
-           engine=None, kmeans_seed=None, history=None):
+           engine=None, kmeans_seed=None, history=None, device_loop=True):
     os.makedirs(dir, exist_ok=True)
     logger, handler = open_logger(os.path.join(dir, 'modelsumm_hurdle.log'))
     train_on = np.where(cresults['pred_train']['pfmean'] > 0.5)[0]                               # :49-50
@@ -33,7 +33,7 @@ def hurdle(Xtrain, Ytrain, Xtest, Ytest, cresults, dir, num_iter=50000, num_indu
     pset = init_head_params(Xtrain, num_inducing_f, 'gaussian', kmeans_seed=kmeans_seed)
     eng = engine or zigp.reference_engine(device)      # tf.cholesky's acceptance rule (pivot > 0)
     ckpt = os.path.join(dir, 'model_hurdle.ckpt')
-    fit_head(pset, 'gaussian', Xtr, Ytr, num_iter, min(num_minibatch, Xtr.shape[0]), logger, ckpt=ckpt, eng=eng, history=history)
+    fit_head(pset, 'gaussian', Xtr, Ytr, num_iter, min(num_minibatch, Xtr.shape[0]), logger, ckpt=ckpt, eng=eng, history=history, device_loop=device_loop)
     log_kernel_summary(logger, pset)
     ptr, pte = predict_svgp(Xtrain=Xtr, Xtest=Xte, checkpointPath=ckpt, num_inducing_f=np.array(num_inducing_f), engine=eng)   # :346-348
     res = {'pred_train_hurdle_svgp': ptr, 'pred_test_hurdle_svgp': pte,

@@ -66,6 +66,14 @@ class zigp_kron_fit_opts(C.Structure):
                 ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double)]
 
 
+HEAD_FIT_BLOCKS = 10   # include/zigp.h ZIGP_HEAD_FIT_BLOCKS
+
+
+class zigp_kron_head_fit_opts(C.Structure):
+    _fields_ = [('lr', C.c_double * HEAD_FIT_BLOCKS), ('positive', C.c_int32 * HEAD_FIT_BLOCKS), ('trainable', C.c_int32 * HEAD_FIT_BLOCKS),
+                ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double)]
+
+
 DENSE_FIT_BLOCKS = 11   # include/zigp.h ZIGP_DENSE_FIT_BLOCKS
 
 
@@ -142,6 +150,10 @@ SIGNATURES = {
     'zigp_get_q_full': (C.c_int, [C.c_void_p]),
     'zigp_kron_head_elbo': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_int32, dp, dp, C.c_int64, C.c_double, C.c_double,
                                       C.c_double, C.c_int32, dp, dp, C.POINTER(zigp_kron_grads), dp]),
+    'zigp_kron_head_elbo_rows': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_double,
+                                           C.c_double, C.c_int32, dp, dp, C.POINTER(zigp_kron_grads), dp]),
+    'zigp_kron_head_fit_steps': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_int32, C.POINTER(zigp_kron_head_fit_opts), dp, dp, dp, C.c_int64,
+                                           C.c_int64, C.c_int32, C.c_void_p, C.c_int64, dp, dp, C.c_double, C.c_double, C.c_int32, dp, dp]),
     'zigp_kron_head_predict': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_int32, dp, C.c_int64, C.c_double, C.c_double, dp]),
     'zigp_profile_enable': (C.c_int, [C.c_void_p, C.c_int32]),
     'zigp_profile_get': (C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int64), dp]),

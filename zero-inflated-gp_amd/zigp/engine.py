@@ -602,17 +602,21 @@ class DenseEngine:
 
     LIK = {'gaussian': _lib.LIK_GAUSSIAN, 'bernoulli': _lib.LIK_BERNOULLI}
 
-    def kron_head_elbo(self, p, X, Y, lik, jitter=1e-5, scale=1.0, f_mu=0.0, include_kl=True, need_grad=True):
+    def kron_head_elbo(self, p, X=None, Y=None, lik=None, jitter=1e-5, scale=1.0, f_mu=0.0, include_kl=True, need_grad=True, rows=None):
         """Single-latent Kronecker SVGP bound with a 'gaussian' (scripts/svgp.py, hurdle.py) or 'bernoulli'
-        (scripts/classifier.py) head.  p holds the f fields only (Zf, ell_f, var_f, u_fm, u_fs_sqrt[, noise]).
+        (scripts/classifier.py) head.  p holds the f fields only (Zf, ell_f, var_f, u_fm, u_fs_sqrt[, noise]).  Either an explicit host
+        minibatch (X, Y) or rows=(lo, hi) of the resident data set (set_data / set_data_device; zigp_kron_head_elbo_rows).
         Returns (elbo_data, kl, grads or None); grads has the f keys, 'noise' and 'f_mu'."""
         s, keep, dims = self._pack_kron(p, tags=('f',))
-        X = as_f64(X)
-        if X.ndim != 2 or X.shape[1] != dims[0] + dims[1]:
-            raise ValueError('X must be (N,%d)' % (dims[0] + dims[1]))
-        Y = as_f64(Y).reshape(-1)
-        if Y.size != X.shape[0]:
-            raise ValueError('Y must have N entries')
+        if rows is None:
+            X = as_f64(X)
+            if X.ndim != 2 or X.shape[1] != dims[0] + dims[1]:
+                raise ValueError('X must be (N,%d)' % (dims[0] + dims[1]))
+            Y = as_f64(Y).reshape(-1)
+            if Y.size != X.shape[0]:
+                raise ValueError('Y must have N entries')
+        elif X is not None or Y is not None:
+            raise ValueError('pass either (X, Y) or rows=(lo, hi), not both')
         ed, kl, dmu = C.c_double(0), C.c_double(0), C.c_double(0)
         gs, a = None, None
         if need_grad:
@@ -622,15 +626,63 @@ class DenseEngine:
                      um=np.zeros_like(um), us=np.zeros_like(us))
             gs.Z0f, gs.Z1f, gs.ell0f, gs.ell1f = ptr(a['Z0']), ptr(a['Z1']), ptr(a['ell0']), ptr(a['ell1'])
             gs.u_fm, gs.u_fs_sqrt = ptr(a['um']), ptr(a['us'])
-        rc = self.lib.zigp_kron_head_elbo(self.ctx, C.byref(s), self.LIK[lik], ptr(X), ptr(Y), X.shape[0], float(jitter), float(scale),
-                                          float(f_mu), 1 if include_kl else 0, C.byref(ed), C.byref(kl),
-                                          C.byref(gs) if gs is not None else None, C.byref(dmu))
+        gref = C.byref(gs) if gs is not None else None
+        if rows is None:
+            rc = self.lib.zigp_kron_head_elbo(self.ctx, C.byref(s), self.LIK[lik], ptr(X), ptr(Y), X.shape[0], float(jitter), float(scale),
+                                              float(f_mu), 1 if include_kl else 0, C.byref(ed), C.byref(kl), gref, C.byref(dmu))
+        else:
+            rc = self.lib.zigp_kron_head_elbo_rows(self.ctx, C.byref(s), self.LIK[lik], int(rows[0]), int(rows[1]), float(jitter), float(scale),
+                                                   float(f_mu), 1 if include_kl else 0, C.byref(ed), C.byref(kl), gref, C.byref(dmu))
         _check(self.lib, self.ctx, rc)
         out = None
         if need_grad:
             out = dict(noise=gs.noise, f_mu=dmu.value, Zf=[a['Z0'], a['Z1']], ell_f=[a['ell0'], a['ell1']], var_f=[gs.var0f, gs.var1f],
                        u_fm=a['um'], u_fs_sqrt=a['us'])
         return ed.value, kl.value, out
+
+    def kron_head_fit_steps(self, shape, lik, x, m, v, lr, positive, trainable, t0, row_begin, batch, jitter=1e-5, scale=1.0, Xw=None, Yw=None,
+                            beta1=0.9, beta2=0.999, eps=1e-8, include_kl=True):
+        """n = len(row_begin) Adam steps of a single-latent head fit ON THE DEVICE (zigp_kron_head_fit_steps; the loop bodies of
+        scripts/svgp.py:289-330 and classifier.py:276-316): one synchronisation for the whole call.  The single-latent twin of
+        kron_fit_steps -- shape: dict(M0f, M1f, D0, D1); lik: 'gaussian' or 'bernoulli'; x, m, v: float64 [n_free], UPDATED IN PLACE, in
+        the block order Z0, Z1, u, s, ell0, ell1, var0, var1, noise, f_mu; lr, positive, trainable: 10 per-block learning rates / Log1pe
+        flags / 0 for a block that is not updated (an absent f_mu: free value 0; the classifier's noise).  row_begin, Xw, Yw and the
+        return value (elbo_data[n], kl[n]) as kron_fit_steps; so are the exceptions, and what NotPositiveDefiniteError carries."""
+        if lik not in self.LIK:
+            raise ValueError("kron_head_fit_steps: lik must be 'gaussian' or 'bernoulli', not %r (the on/off fit is kron_fit_steps)" % (lik,))
+        s = _lib.zigp_kron_params()
+        for k in ('M0f', 'M1f', 'D0', 'D1'):
+            setattr(s, k, int(shape[k]))
+        o = _lib.zigp_kron_head_fit_opts()
+        for b in range(_lib.HEAD_FIT_BLOCKS):
+            o.lr[b] = float(lr[b]); o.positive[b] = int(bool(positive[b])); o.trainable[b] = int(bool(trainable[b]))
+        o.beta1, o.beta2, o.eps = float(beta1), float(beta2), float(eps)
+        for a in (x, m, v):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.ndim == 1 and a.size == x.size):
+                raise ValueError('x, m, v must be contiguous float64 vectors of one length')
+        rb = np.ascontiguousarray(np.asarray(row_begin, dtype=np.int64))
+        n = rb.size
+        xw = yw = None
+        if Xw is not None:
+            xw, yw = as_f64(Xw), as_f64(Yw).reshape(-1)
+            if xw.ndim != 2 or xw.shape[0] % int(batch) or yw.size != xw.shape[0]:
+                raise ValueError('Xw must hold whole batches of `batch` rows, Yw one value per row')
+            if rb.min() < -(xw.shape[0] // int(batch)):
+                raise ValueError('row_begin refers to a host batch beyond Xw')
+        elif n and rb.min() < 0:
+            raise ValueError('negative row_begin needs Xw, Yw')
+        ed, kl = np.zeros(n), np.zeros(n)
+        rc = self.lib.zigp_kron_head_fit_steps(self.ctx, C.byref(s), self.LIK[lik], C.byref(o), ptr(x), ptr(m), ptr(v), x.size, int(t0), n,
+                                               rb.ctypes.data, int(batch), ptr(xw) if xw is not None else None, ptr(yw) if yw is not None else None,
+                                               float(jitter), float(scale), 1 if include_kl else 0, ptr(ed), ptr(kl))
+        try:
+            _check(self.lib, self.ctx, rc)
+        except ZigpError as e:      # as kron_fit_steps: the count of applied updates comes from the library (the two loops share the counter)
+            done = max(0, min(n, int(self.lib.zigp_kron_fit_steps_applied(self.ctx))))
+            e.steps_applied = done
+            e.elbo_data, e.kl = ed[:done].copy(), kl[:done].copy()
+            raise
+        return ed, kl
 
     def kron_head_predict(self, p, Xnew, lik, jitter=1e-6, f_mu=0.0):
         """(4,N): fmean, fvar, pfmean, pfvar (onofftf/svgppred.py:180-186, onofftf/svcppred.py 'pfmean'/'pfvar')."""
