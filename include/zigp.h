@@ -145,8 +145,30 @@ typedef struct {
 int zigp_fit_steps(zigp_ctx* ctx, const zigp_params* shape, const zigp_fit_opts* opts, double* free_state, double* adam_m,
                    double* adam_v, int64_t n_free, int64_t t0, int32_t n_steps, const int64_t* rows, int64_t batch,
                    double jitter, double scale, int32_t include_kl, double* elbo_data, double* kl);
-/* Updates applied by the LAST zigp_fit_steps call of this context: n_steps after a call that returned 0, the k steps before the failing
- * one after ZIGP_ENOTPD, 0 when the call ended before its first step (bad argument, HIP error). */
+/* The same loop for the whitened parametrisations.  `mode` is an argument of the CALL: it decides the model that is fitted and the layout
+ * of free_state; the context's zigp_set_whiten / zigp_set_q_full settings are neither read nor changed, and the calls that follow
+ * (zigp_elbo, zigp_predict, ...) behave as if this call had not happened.
+ *   ZIGP_FIT_DIAG        unwhitened, diagonal q(u): the code path of zigp_fit_steps, bit-identical state and history
+ *   ZIGP_FIT_WHITE       zigp_set_whiten's model, q(u) = N(L u, L diag(s^2) L^T); the 11 blocks of zigp_fit_steps
+ *   ZIGP_FIT_WHITE_FULL  zigp_set_q_full's model, q(u) = N(L u, L Lq Lq^T L^T).  Blocks 4 and 5 hold the M (M + 1) / 2 entries of the LOWER
+ *                        TRIANGLE of Lq in row-major order (entry (i, j), j <= i, at i (i + 1) / 2 + j: the free vector of
+ *                        zigp.transforms.LowerTriangular and of GPflow's transforms.LowerTriangular); the diagonal is unconstrained
+ *                        (a negative entry is legal), so positive[4] and positive[5] must be 0.  n_free follows from these sizes.
+ * Everything else is zigp_fit_steps, word for word: rows / batch / NULL rows, t0, the history taken before each update, one
+ * synchronisation per call, and the Cholesky-failure contract (ZIGP_ENOTPD, the state before the failing step, NaN history from step k on,
+ * k in zigp_fit_steps_applied -- the two calls share that counter).
+ * ZIGP_EARG (nothing enqueued, the state untouched): what zigp_fit_steps refuses except the context's whiten / q_full flags -- a mean
+ * function and a communicator included -- and an unknown mode, positive set on a full block, a diagonal entry of Lq that is exactly zero
+ * in the incoming free_state (its log is not finite).  A diagonal entry that an update lands on exactly zero gets no special handling:
+ * that step's KL is not finite and its history entry shows it (an applied step may have a non-finite ELBO). */
+#define ZIGP_FIT_DIAG 0
+#define ZIGP_FIT_WHITE 1
+#define ZIGP_FIT_WHITE_FULL 2
+int zigp_fit_steps_mode(zigp_ctx* ctx, int32_t mode, const zigp_params* shape, const zigp_fit_opts* opts, double* free_state,
+                        double* adam_m, double* adam_v, int64_t n_free, int64_t t0, int32_t n_steps, const int64_t* rows,
+                        int64_t batch, double jitter, double scale, int32_t include_kl, double* elbo_data, double* kl);
+/* Updates applied by the LAST zigp_fit_steps or zigp_fit_steps_mode call of this context: n_steps after a call that returned 0, the k steps
+ * before the failing one after ZIGP_ENOTPD, 0 when the call ended before its first step (bad argument, HIP error). */
 int64_t zigp_fit_steps_applied(zigp_ctx* ctx);
 
 /* Prediction.  Replaces OnOffSVGP.predict_onoffgp -> build_predict (onoffgpf/OnOffSVGP.py:124-152,160-162).
@@ -262,8 +284,9 @@ int zigp_get_mean_function_grad(zigp_ctx* ctx, double* da, int32_t D, double* db
  *   KL   = 0.5 (sum u_m^2 + sum u_s_sqrt^2 - M - sum log u_s_sqrt^2)   per latent.
  * zigp_elbo (value-only, gradient, include_kl 0 / 1, row ranges, zigp_select_rows), zigp_predict, zigp_predict_device and zigp_prior_kl
  * follow the setting; mean functions, g_offset, scale, the chunk rule and the data-parallel exchange work as without it.  The setting
- * persists in the context like zigp_set_mean_function and is off after zigp_create.  zigp_fit_steps returns ZIGP_EARG while it is on (the
- * device loop fits the unwhitened parametrisation only); the Kronecker entry points ignore it (the reference raises NotImplementedError
+ * persists in the context like zigp_set_mean_function and is off after zigp_create.  zigp_fit_steps returns ZIGP_EARG while it is on (that
+ * call fits the unwhitened parametrisation only; the device loop of this model is zigp_fit_steps_mode with ZIGP_FIT_WHITE, which takes
+ * the parametrisation as an argument and does not read this setting); the Kronecker entry points ignore it (the reference raises NotImplementedError
  * there, scripts/onoff.py:145-146).  zigp_get_whiten returns 0 / 1, or ZIGP_EARG for a NULL context. */
 int zigp_set_whiten(zigp_ctx* ctx, int32_t on);
 int zigp_get_whiten(zigp_ctx* ctx);
@@ -280,7 +303,8 @@ int zigp_get_whiten(zigp_ctx* ctx);
  * zigp_predict_device and zigp_prior_kl follow the setting.  The call's result vector grows to 16 + sum_h (M D + M + M^2 + D) doubles
  * and the parameter upload by M^2 per latent (8 MB each way and latent at M = 1024, through the page-locked arena).
  * ZIGP_EARG, with nothing enqueued: any of those calls while this is on and whitening is off (the unwhitened full-covariance model,
- * gauss_kl, OnOffSVGP.py:102-104, is not implemented), and zigp_fit_steps while it is on.  The setting persists in the context, is off
+ * gauss_kl, OnOffSVGP.py:102-104, is not implemented), and zigp_fit_steps while it is on (the device loop of
+ * this model is zigp_fit_steps_mode with ZIGP_FIT_WHITE_FULL, which does not read this setting).  The setting persists in the context, is off
  * after zigp_create, and the Kronecker entry points ignore it.  zigp_get_q_full returns 0 / 1, or ZIGP_EARG for a NULL context. */
 int zigp_set_q_full(zigp_ctx* ctx, int32_t on);
 int zigp_get_q_full(zigp_ctx* ctx);

@@ -630,6 +630,7 @@ struct DenseCall {
   bool need_grad, has_rows;
   bool whiten = false;    // the context's zigp_set_whiten at the time of the call (run_dense)
   bool q_full = false;    // the context's zigp_set_q_full (validate_params: only with whiten)
+  bool tri_pack = false;  // q_full in the fit loop: dLq leaves as its lower triangle, M (M + 1) / 2 entries (k_pack_tril), not as the (M, M) block
   HostLatent hl[2]; const double* ell_h[2];
   int64_t Nc = 0;         // rows per full chunk
   ChunkPlan plan[2];      // the full chunk and, if smaller, the last one (run_dense)
@@ -748,7 +749,8 @@ PwArgs dense_pointwise_args(zigp_ctx* c, const DenseCall& k, int64_t n0, int64_t
 int dense_pointwise_launch(zigp_ctx* c, bool predict, bool need_grad, const PwArgs& a, const double* d_hyp = nullptr, bool whiten = false) {
   ProfScope ps(c, PC_POINT);
   const int nblk = (int)(a.Nc / PW_PTS);
-  if (whiten) {     // var = var0 + (plane 2) in every mode (chunk_forward_white); a value-only pass has gm_f = NULL and writes no cotangents
+  if (whiten && d_hyp) hipLaunchKernelGGL((k_pointwise<false, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a, d_hyp);     // a whitened step of the fit loop
+  else if (whiten) {     // var = var0 + (plane 2) in every mode (chunk_forward_white); a value-only pass has gm_f = NULL and writes no cotangents
     if (predict) hipLaunchKernelGGL((k_pointwise<true, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
     else hipLaunchKernelGGL((k_pointwise<false, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
   } else if (d_hyp) hipLaunchKernelGGL((k_pointwise<false, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a, d_hyp);     // a gradient step of the fit loop
@@ -871,7 +873,8 @@ int dense_pack(zigp_ctx* c, const DenseCall& k, DensePackArgs& a, size_t& n) {
     // whitened: du's data part is A gm, the KL parts and the KL value come from the whitened vectors (k_kl_white keeps vec's layout)
     if (k.whiten) { L.du = lt.a1gm.p; L.vec = lt.wh.p; }
     L.M = lt.M; L.Mp = lt.Mp; L.var = lt.var; L.out_off = (int64_t)n; L.q_full = k.q_full ? 1 : 0;
-    if (k.need_grad) n += (size_t)lt.M * D + (size_t)lt.M + (k.q_full ? (size_t)lt.M * lt.M : (size_t)lt.M) + D;
+    L.ns = !k.q_full ? (int64_t)lt.M : k.tri_pack ? (int64_t)lt.M * (lt.M + 1) / 2 : (int64_t)lt.M * lt.M;
+    if (k.need_grad) n += (size_t)lt.M * D + (size_t)lt.M + (size_t)L.ns + D;
   }
   a.pw = c->pw_part.p; a.pw_blocks = k.pw_blocks; a.D = D; a.need_grad = k.need_grad ? 1 : 0; a.include_kl = k.include_kl ? 1 : 0;
   a.mean_on = c->mean_on ? 1 : 0;
@@ -882,8 +885,10 @@ int dense_pack(zigp_ctx* c, const DenseCall& k, DensePackArgs& a, size_t& n) {
   if (k.need_grad && k.q_full)
     for (int h = 0; h < 2; ++h) {     // the (M, M) blocks, behind du
       const Latent& lt = c->lat[h];
-      hipLaunchKernelGGL(k_pack_square, dim3(ceil_div((int64_t)lt.M * lt.M, 256)), dim3(256), 0, c->stream, lt.dLq.p, lt.M, (int64_t)lt.Mp,
-                         a.out + a.lat[h].out_off + (int64_t)lt.M * D + lt.M);
+      double* os = a.out + a.lat[h].out_off + (int64_t)lt.M * D + lt.M;
+      const dim3 grid(ceil_div((int64_t)lt.M * lt.M, 256));
+      if (k.tri_pack) hipLaunchKernelGGL(k_pack_tril, grid, dim3(256), 0, c->stream, lt.dLq.p, lt.M, (int64_t)lt.Mp, os);
+      else hipLaunchKernelGGL(k_pack_square, grid, dim3(256), 0, c->stream, lt.dLq.p, lt.M, (int64_t)lt.Mp, os);
     }
   ZIGP_HIP(c, hipGetLastError());
   return 0;
@@ -1170,52 +1175,74 @@ int zigp_elbo(zigp_ctx* c, const zigp_params* p, double jitter, double scale, do
 // The first step sizes the per-call buffers and fills the tile cache of the M x M stage; from the second step on nothing allocates, copies
 // synchronously or synchronises until the one download at the end.
 static_assert(DFIT_BLOCKS == ZIGP_DENSE_FIT_BLOCKS, "block order of include/zigp.h");
-int zigp_fit_steps(zigp_ctx* c, const zigp_params* shape, const zigp_fit_opts* o, double* free_state, double* adam_m, double* adam_v, int64_t n_free,
-                   int64_t t0, int32_t n_steps, const int64_t* rows, int64_t batch, double jitter, double scale, int32_t include_kl, double* elbo_data,
-                   double* kl) {
+}  // extern "C"
+namespace {
+// One loop for the three parametrisations (include/zigp.h ZIGP_FIT_*).  `mode` decides the layout of blocks 4 and 5, the image kernels and
+// DenseCall::whiten / q_full, i.e. which chunk lists dense_plan plans and which launches dense_step makes; `legacy` is zigp_fit_steps, which
+// refuses while the context's own whiten / q_full flags are on -- zigp_fit_steps_mode neither reads nor changes them.
+int dense_fit_steps(zigp_ctx* c, int32_t mode, bool legacy, const zigp_params* shape, const zigp_fit_opts* o, double* free_state, double* adam_m,
+                    double* adam_v, int64_t n_free, int64_t t0, int32_t n_steps, const int64_t* rows, int64_t batch, double jitter, double scale,
+                    int32_t include_kl, double* elbo_data, double* kl) {
   if (!c) return ZIGP_EARG;
+  const std::string who = legacy ? "zigp_fit_steps" : "zigp_fit_steps_mode";
+  auto bad = [&](const char* what) { return fail_arg(c, (who + ": " + what).c_str()); };
   c->dense_fit_steps_applied = 0;      // whatever ends this call early, no update of it has been applied
-  if (!shape || !o || !free_state || !adam_m || !adam_v) return fail_arg(c, "zigp_fit_steps: NULL argument");
-  if (shape->Mf <= 0 || shape->Mg <= 0 || shape->D <= 0 || shape->D > MAXD) return fail_arg(c, "zigp_fit_steps: need Mf, Mg > 0 and 1 <= D <= 8");
-  if (n_steps <= 0 || t0 < 0 || (rows && batch <= 0)) return fail_arg(c, "zigp_fit_steps: need n_steps > 0, t0 >= 0 and, with rows, batch > 0");
-  if (!(jitter >= 0)) return fail_arg(c, "zigp_fit_steps: jitter must be >= 0");
-  if (!(o->beta1 >= 0 && o->beta1 < 1 && o->beta2 >= 0 && o->beta2 < 1 && o->eps > 0)) return fail_arg(c, "zigp_fit_steps: bad Adam constants");
+  if (!shape || !o || !free_state || !adam_m || !adam_v) return bad("NULL argument");
+  if (mode != ZIGP_FIT_DIAG && mode != ZIGP_FIT_WHITE && mode != ZIGP_FIT_WHITE_FULL)
+    return bad("unknown mode (ZIGP_FIT_DIAG, ZIGP_FIT_WHITE, ZIGP_FIT_WHITE_FULL)");
+  const bool white = mode != ZIGP_FIT_DIAG, full = mode == ZIGP_FIT_WHITE_FULL;
+  if (shape->Mf <= 0 || shape->Mg <= 0 || shape->D <= 0 || shape->D > MAXD) return bad("need Mf, Mg > 0 and 1 <= D <= 8");
+  if (n_steps <= 0 || t0 < 0 || (rows && batch <= 0)) return bad("need n_steps > 0, t0 >= 0 and, with rows, batch > 0");
+  if (!(jitter >= 0)) return bad("jitter must be >= 0");
+  if (!(o->beta1 >= 0 && o->beta1 < 1 && o->beta2 >= 0 && o->beta2 < 1 && o->eps > 0)) return bad("bad Adam constants");
   const int D = shape->D, M[2] = {shape->Mf, shape->Mg};
   const int es[2] = {o->ell_size_f, o->ell_size_g};
   for (int h = 0; h < 2; ++h)
-    if (es[h] != 1 && es[h] != D) return fail_arg(c, "zigp_fit_steps: ell_size must be 1 or D");
-  if (!c->dX) return fail_arg(c, "zigp_fit_steps: no data set (call zigp_set_data first)");
-  if (D != c->D) return fail_arg(c, "zigp_fit_steps: shape.D differs from the data's D");
-  if (c->q_full) return fail_arg(c, "zigp_fit_steps: the full-covariance q(u) is on (zigp_set_q_full, q_diag=False); the device loop fits the diagonal unwhitened parametrisation only (zigp_elbo + a host optimiser)");
-  if (c->whiten) return fail_arg(c, "zigp_fit_steps: whitening is on (zigp_set_whiten); the device loop fits the unwhitened parametrisation only (zigp_elbo + a host optimiser)");
-  if (c->mean_on) return fail_arg(c, "zigp_fit_steps: a mean function is set; its parameters stay with the host loop (zigp_elbo + a host optimiser)");
-  if (c->comm) return fail_arg(c, "zigp_fit_steps: a communicator is attached; the dense device loop is single-process");
+    if (es[h] != 1 && es[h] != D) return bad("ell_size must be 1 or D");
+  if (!c->dX) return bad("no data set (call zigp_set_data first)");
+  if (D != c->D) return bad("shape.D differs from the data's D");
+  if (legacy && c->q_full) return bad("the full-covariance q(u) is on (zigp_set_q_full, q_diag=False); the device loop fits the diagonal unwhitened parametrisation only (zigp_elbo + a host optimiser)");
+  if (legacy && c->whiten) return bad("whitening is on (zigp_set_whiten); the device loop fits the unwhitened parametrisation only (zigp_elbo + a host optimiser)");
+  if (c->mean_on) return bad("a mean function is set; its parameters stay with the host loop (zigp_elbo + a host optimiser)");
+  if (c->comm) return bad("a communicator is attached; the dense device loop is single-process");
   if (rows) {
-    if ((int64_t)n_steps > ((int64_t)1 << 27) / batch) return fail_arg(c, "zigp_fit_steps: n_steps * batch row indices exceed 1 GiB");
+    if ((int64_t)n_steps > ((int64_t)1 << 27) / batch) return bad("n_steps * batch row indices exceed 1 GiB");
     for (int64_t i = 0; i < (int64_t)n_steps * batch; ++i)
-      if (rows[i] < 0 || rows[i] >= c->fullN) return fail_arg(c, "zigp_fit_steps: row index out of range");
-  } else if (c->N <= 0) return fail_arg(c, "zigp_fit_steps: no active rows");
+      if (rows[i] < 0 || rows[i] >= c->fullN) return bad("row index out of range");
+  } else if (c->N <= 0) return bad("no active rows");
   DenseFitArgs fa;
   memset(static_cast<void*>(&fa), 0, sizeof(fa));
   DenseFitDesc& d = fa.d;
   {
-    const int sizes[DFIT_BLOCKS] = {M[0] * D, M[1] * D, M[0], M[1], M[0], M[1], es[0], es[1], 1, 1, 1};
+    // blocks 4, 5: the diagonal's M entries, or the M (M + 1) / 2 of Lq's lower triangle in row-major order (identity transform)
+    const int64_t ns64[2] = {full ? (int64_t)M[0] * (M[0] + 1) / 2 : M[0], full ? (int64_t)M[1] * (M[1] + 1) / 2 : M[1]};
+    if ((int64_t)(M[0] + M[1]) * (D + 1) + ns64[0] + ns64[1] + 2 * D + 3 > ((int64_t)1 << 30)) return bad("the free state exceeds 2^30 entries");
+    const int ns[2] = {(int)ns64[0], (int)ns64[1]};
+    const int sizes[DFIT_BLOCKS] = {M[0] * D, M[1] * D, M[0], M[1], ns[0], ns[1], es[0], es[1], 1, 1, 1};
     int off = 0;
     for (int b = 0; b < DFIT_BLOCKS; ++b) {
       d.off[b] = off; d.n[b] = sizes[b]; d.gn[b] = 1; off += sizes[b];
       d.positive[b] = o->positive[b] != 0; d.trainable[b] = o->trainable[b] != 0; d.lr[b] = o->lr[b];
     }
     d.off[DFIT_BLOCKS] = off;
-    if ((int64_t)off != n_free) return fail_arg(c, "zigp_fit_steps: n_free does not match the model sizes");
-    // the packed result vector (k_dense_pack): header, then per latent dZ (M D), du (M), ds (M), dell (D)
+    if ((int64_t)off != n_free) return bad("n_free does not match the model sizes");
+    if (full && (o->positive[4] != 0 || o->positive[5] != 0))
+      return bad("positive[4] / positive[5] must be 0 for ZIGP_FIT_WHITE_FULL (the diagonal of a full factor is unconstrained)");
+    if (full)     // a zero diagonal entry: the KL's log is not finite
+      for (int h = 0; h < 2; ++h)
+        for (int64_t i = 0; i < M[h]; ++i)
+          if (free_state[d.off[4 + h] + i * (i + 1) / 2 + i] == 0.0)
+            return bad(h ? "the full factor of g has a zero diagonal entry" : "the full factor of f has a zero diagonal entry");
+    // the packed result vector (k_dense_pack): header, then per latent dZ (M D), du (M), ds (M; full: dLq's lower triangle), dell (D)
     int g = DP_HDR;
     for (int h = 0; h < 2; ++h) {
-      d.goff[0 + h] = g; d.goff[2 + h] = g + M[h] * D; d.goff[4 + h] = g + M[h] * D + M[h]; d.goff[6 + h] = g + M[h] * D + 2 * M[h];
+      d.goff[0 + h] = g; d.goff[2 + h] = g + M[h] * D; d.goff[4 + h] = g + M[h] * D + M[h]; d.goff[6 + h] = g + M[h] * D + M[h] + ns[h];
       d.gn[6 + h] = es[h] == 1 ? D : 1;
-      g += M[h] * D + 2 * M[h] + D;
+      g += M[h] * D + M[h] + ns[h] + D;
     }
     d.goff[8] = 2; d.goff[9] = 3; d.goff[10] = 4;
   }
+  d.tri = full ? 1 : 0;
   d.D = D; d.M[0] = M[0]; d.M[1] = M[1];
   d.beta1 = o->beta1; d.beta2 = o->beta2; d.eps = o->eps; d.jitter = jitter; d.rtol_eps = c->pivot_rtol * 2.220446049250313e-16;
   ZIGP_HIP(c, hipSetDevice(c->device));
@@ -1227,6 +1254,7 @@ int zigp_fit_steps(zigp_ctx* c, const zigp_params* shape, const zigp_fit_opts* o
   DenseCall k;
   k.p = &sizes_only; k.D = D; k.jitter = jitter; k.scale = scale; k.g_offset = 0.0; k.include_kl = include_kl; k.predict = false; k.d_out9 = nullptr;
   k.need_grad = true; k.has_rows = true; k.row_begin = 0;
+  k.whiten = white; k.q_full = full; k.tri_pack = full;
   k.hl[0] = HostLatent{M[0], nullptr, nullptr, nullptr, nullptr, 0.0}; k.hl[1] = HostLatent{M[1], nullptr, nullptr, nullptr, nullptr, 0.0};
   k.ell_h[0] = k.ell_h[1] = nullptr;
   const int64_t nidx = rows ? (int64_t)n_steps * batch : 0;
@@ -1253,6 +1281,10 @@ int zigp_fit_steps(zigp_ctx* c, const zigp_params* shape, const zigp_fit_opts* o
     lt.var = 0.0;            // not read: the kernels take it from the block
     lt.kg_exact = true;      // the per-row form of k_kgrad: the centred form needs a centre chosen from Z and ell, which move on the device
     for (int q = 0; q < MAXD; ++q) lt.zc[q] = 0.0;
+    if (full) {     // the M x M buffers of the full factor (latents_upload / latent_qfull_dlq size them for zigp_elbo): before the first step
+      const size_t mm = (size_t)M[h] * M[h], mmp = (size_t)lt.Mp * lt.Mp;
+      ZIGP_ENSURE(c, lt.Lraw, mm); ZIGP_ENSURE(c, lt.Lq, mmp); ZIGP_ENSURE(c, lt.lqssq, mmp / 256); ZIGP_ENSURE(c, lt.T3, mmp); ZIGP_ENSURE(c, lt.dLq, mmp);
+    }
     d.img_Z[h] = (int)off[h][0]; d.img_ell[h] = (int)off[h][1]; d.img_u[h] = (int)off[h][2]; d.img_s[h] = (int)off[h][3]; d.img_Zs[h] = (int)off[h][4];
   }
   {
@@ -1270,7 +1302,12 @@ int zigp_fit_steps(zigp_ctx* c, const zigp_params* shape, const zigp_fit_opts* o
     }
   }
   const dim3 ugrid(ceil_div(n_free, DFIT_THREADS));
-  hipLaunchKernelGGL(k_dense_fit_image, ugrid, dim3(DFIT_THREADS), 0, c->stream, d, fa.x, c->parm.p, H);
+  const dim3 tgrid(ceil_div((int64_t)std::max(M[0], M[1]) * std::max(M[0], M[1]), DFIT_THREADS), 2);
+  auto image = [&]() {     // free state -> parameter image, hyperparameter block and, for full factors, the two Lraw blocks
+    hipLaunchKernelGGL(k_dense_fit_image, ugrid, dim3(DFIT_THREADS), 0, c->stream, d, fa.x, c->parm.p, H);
+    if (full) hipLaunchKernelGGL(k_dense_fit_image_tri, tgrid, dim3(DFIT_THREADS), 0, c->stream, d, fa.x, c->parm.p, c->lat[0].Lraw.p, c->lat[1].Lraw.p);
+  };
+  image();
   ZIGP_HIP(c, hipGetLastError());
   for (int i = 0; i < n_steps; ++i) {
     if (rows) {
@@ -1285,7 +1322,7 @@ int zigp_fit_steps(zigp_ctx* c, const zigp_params* shape, const zigp_fit_opts* o
     const double t = (double)(t0 + i + 1);
     fa.packed = c->packed.p; fa.step = i; fa.lr_sq = std::sqrt(1.0 - std::pow(d.beta2, t)); fa.lr_den = 1.0 - std::pow(d.beta1, t);
     hipLaunchKernelGGL(k_dense_fit_update, ugrid, dim3(DFIT_THREADS), 0, c->stream, fa);
-    hipLaunchKernelGGL(k_dense_fit_image, ugrid, dim3(DFIT_THREADS), 0, c->stream, d, fa.x, c->parm.p, H);
+    image();
     ZIGP_HIP(c, hipGetLastError());
   }
   double* hst = nullptr;
@@ -1301,13 +1338,27 @@ int zigp_fit_steps(zigp_ctx* c, const zigp_params* shape, const zigp_fit_opts* o
     if (kl) kl[i] = i < done ? hst[3 * nf + 2 * i + 1] : NAN;
   }
   if (hfail[0]) {
-    char b[256];
-    snprintf(b, sizeof(b), "Cholesky failed in step %d of this zigp_fit_steps call (iteration %lld): Kuu of latent %s not positive definite at pivot %d; "
-             "the state returned is the one before that step", hfail[0] - 1, (long long)(t0 + hfail[0] - 1), hfail[1] ? "g" : "f", hfail[2]);
+    char b[320];
+    snprintf(b, sizeof(b), "Cholesky failed in step %d of this %s call (iteration %lld): Kuu of latent %s not positive definite at pivot %d; "
+             "the state returned is the one before that step", hfail[0] - 1, who.c_str(), (long long)(t0 + hfail[0] - 1), hfail[1] ? "g" : "f", hfail[2]);
     c->err = b; c->info = hfail[2];
     return ZIGP_ENOTPD;
   }
   return ZIGP_OK;
+}
+}  // namespace
+extern "C" {
+int zigp_fit_steps(zigp_ctx* c, const zigp_params* shape, const zigp_fit_opts* o, double* free_state, double* adam_m, double* adam_v, int64_t n_free,
+                   int64_t t0, int32_t n_steps, const int64_t* rows, int64_t batch, double jitter, double scale, int32_t include_kl, double* elbo_data,
+                   double* kl) {
+  return dense_fit_steps(c, ZIGP_FIT_DIAG, true, shape, o, free_state, adam_m, adam_v, n_free, t0, n_steps, rows, batch, jitter, scale, include_kl,
+                         elbo_data, kl);
+}
+int zigp_fit_steps_mode(zigp_ctx* c, int32_t mode, const zigp_params* shape, const zigp_fit_opts* o, double* free_state, double* adam_m,
+                        double* adam_v, int64_t n_free, int64_t t0, int32_t n_steps, const int64_t* rows, int64_t batch, double jitter,
+                        double scale, int32_t include_kl, double* elbo_data, double* kl) {
+  return dense_fit_steps(c, mode, false, shape, o, free_state, adam_m, adam_v, n_free, t0, n_steps, rows, batch, jitter, scale, include_kl,
+                         elbo_data, kl);
 }
 int64_t zigp_fit_steps_applied(zigp_ctx* c) { return c ? c->dense_fit_steps_applied : (int64_t)ZIGP_EARG; }
 

@@ -755,13 +755,22 @@ __global__ void k_pack_square(const double* __restrict__ src, int M, int64_t Mp,
   const int64_t i = idx / M, j = idx - i * M;
   out[idx] = src[i * Mp + j];
 }
+// the lower triangle of the padded (Mp, Mp) image in row-major triangular order, out[i (i + 1) / 2 + j] for j <= i: the gradient block of a
+// full factor as the fit loop's update kernel reads it (zigp_fit_steps_mode, ZIGP_FIT_WHITE_FULL).  One thread per (i, j) of the square.
+__global__ void k_pack_tril(const double* __restrict__ src, int M, int64_t Mp, double* __restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)M * M) return;
+  const int64_t i = idx / M, j = idx - i * M;
+  if (j <= i) out[i * (i + 1) / 2 + j] = src[i * Mp + j];
+}
 
 // ---------------------------------------------------------------------------------------------
 // Result vector of one dense ELBO call, assembled on the device so that a data-parallel run can sum it over ranks where it
 // lies (ncclAllReduce on the library's stream, zigp_comm_init) and one download brings everything back:
 //   out[0] elbo_data  [1] kl  [2] d var_f  [3] d var_g  [4] d noise  [5] d mean_b  [6..13] d mean_a   (header: DP_HDR doubles)
 //   then per latent h = f, g (only when a gradient was asked for):  dZ (M_h x D)  du (M_h)  ds (M_h)  dell (D)
-//   (zigp_set_q_full: the ds block is dLq, M_h x M_h, written by k_pack_square; this kernel leaves it alone and puts dell behind it)
+//   (zigp_set_q_full: the ds block is dLq, M_h x M_h, written by k_pack_square -- in the fit loop its lower triangle, M_h (M_h + 1) / 2 entries,
+//   written by k_pack_tril; this kernel leaves it alone and puts dell behind its DensePackLat::ns entries)
 // Block h assembles latent h; block 0 also writes the header scalars.  Every sum has a fixed order (strided partial per thread,
 // xor tree over lanes, waves in index order): bit-stable run to run.
 // ---------------------------------------------------------------------------------------------
@@ -770,6 +779,7 @@ struct DensePackLat {
   const double* krow; const double* du; const double* dsq; const double* vec; const double* s; const double* ell;
   int M, Mp; double var; int64_t out_off;
   int q_full;   // the latent's q_sqrt block is (M, M) and not this kernel's
+  int64_t ns;   // entries of the ds block: M, or with q_full M M (k_pack_square) / M (M + 1) / 2 (k_pack_tril, fit loop)
 };
 struct DensePackArgs {
   DensePackLat lat[2];
@@ -822,7 +832,7 @@ k_dense_pack(DensePackArgs a, HV... hv) {
     const double e = L.ell[d];
     o[idx] = ksum(m, 1 + d) / (e * e);
   }
-  double* ou = o + (int64_t)M * D; double* os = ou + M; double* ol = os + (L.q_full ? (int64_t)M * M : (int64_t)M);
+  double* ou = o + (int64_t)M * D; double* os = ou + M; double* ol = os + L.ns;
   for (int m = t; m < M; m += 256) {
     const double sm = L.s[m];
     double dum = L.du[m], dsm = 2.0 * sm * L.dsq[m];
@@ -886,6 +896,7 @@ struct DenseFitDesc {
   int off[DFIT_BLOCKS + 1], n[DFIT_BLOCKS], goff[DFIT_BLOCKS], gn[DFIT_BLOCKS], positive[DFIT_BLOCKS], trainable[DFIT_BLOCKS];
   double lr[DFIT_BLOCKS];
   int D, M[2];
+  int tri;                                                   // blocks 4, 5 are lower triangles of M (M + 1) / 2 entries (k_dense_fit_image_tri)
   int img_Z[2], img_ell[2], img_u[2], img_s[2], img_Zs[2];   // offsets of the parameter image (latents_layout, zigp_dense.hip)
   double beta1, beta2, eps, jitter, rtol_eps;                // rtol_eps = pivot_rtol * DBL_EPSILON (pivot_tol, zigp_host.h)
 };
@@ -915,7 +926,7 @@ k_dense_fit_image(DenseFitDesc d, const double* __restrict__ x, double* __restri
     img[d.img_Z[h] + i] = val;
     img[d.img_Zs[h] + i] = val * (KUF_C * (1.0 / ell));
   } else if (b <= 3) img[d.img_u[h] + i] = val;
-  else if (b <= 5) img[d.img_s[h] + i] = val;
+  else if (b <= 5) { if (!d.tri) img[d.img_s[h] + i] = val; }
   else if (b <= 7) {
     double* R = H + h * DH_LAT;
     for (int dd = (d.n[b] == 1 ? 0 : i); dd < (d.n[b] == 1 ? D : i + 1); ++dd) {
@@ -926,6 +937,22 @@ k_dense_fit_image(DenseFitDesc d, const double* __restrict__ x, double* __restri
     double* R = H + h * DH_LAT;
     R[DH_VAR] = val; R[DH_PIVTOL] = d.rtol_eps * (val + d.jitter);
   } else H[DH_NOISE] = val;
+}
+
+// Full factors (d.tri; ZIGP_FIT_WHITE_FULL): block 4 + h of the free state is the lower triangle of Lq_h in row-major triangular order,
+// identity transform.  One thread per (i, j) of the (M, M) row-major block Lraw_h = blockIdx.y's: the entry for j <= i, an exact zero
+// above the diagonal, and the diagonal into the image's s slot -- what latents_upload stages from host values.  k_lq_stage masks and
+// pads it as in zigp_elbo.  Launched beside k_dense_fit_image, which leaves these two blocks alone.
+__global__ void __launch_bounds__(DFIT_THREADS)
+k_dense_fit_image_tri(DenseFitDesc d, const double* __restrict__ x, double* __restrict__ img, double* __restrict__ Lraw_f,
+                      double* __restrict__ Lraw_g) {
+  const int h = blockIdx.y;
+  const int64_t M = d.M[h], idx = (int64_t)blockIdx.x * DFIT_THREADS + threadIdx.x;
+  if (idx >= M * M) return;
+  const int64_t i = idx / M, j = idx - i * M;
+  const double val = j <= i ? x[d.off[4 + h] + i * (i + 1) / 2 + j] : 0.0;
+  (h == 0 ? Lraw_f : Lraw_g)[idx] = val;
+  if (i == j) img[d.img_s[h] + i] = val;
 }
 
 // The update: element-wise.  packed = the result vector k_dense_pack assembled for this step (header: data term, KL, d var_f, d var_g,

@@ -19,13 +19,13 @@ from collections import OrderedDict
 import numpy as np
 
 import zigp
-from zigp.optim import ParamSet, lbfgsb, AdamGroups, DenseDeviceFit
+from zigp.optim import ParamSet, lbfgsb, AdamGroups, DenseDeviceFit, WhiteDeviceFit
 from zigp.transforms import positive, Log1pe, Identity, LowerTriangular
 from .param import Param, DataHolder, Parameterized
 from .mean_functions import MeanFunction, Zero
 
 JITTER = 1e-6   # gpflow settings.numerics.jitter_level default (OnOffSVGP.py:96-97) [GPflow-recall]
-DEVICE_FIT_CALL = 200   # iterations per zigp_fit_steps call of optimize(method='adam'): one synchronisation each
+DEVICE_FIT_CALL = 200   # iterations per zigp_fit_steps / zigp_fit_steps_mode call of optimize(method='adam'): one synchronisation each
 
 
 class OnOffSVGP(Parameterized):
@@ -133,10 +133,11 @@ class OnOffSVGP(Parameterized):
 
     def _adam_on_device(self, pset, maxiter):
         """maxiter Adam iterations in calls of at most DEVICE_FIT_CALL: the row samples are drawn from self._rng in the order and by the
-        rule of _load_batch (the run sees the minibatches the host loop would), uploaded once per call and gathered on the device."""
+        rule of _load_batch (the run sees the minibatches the host loop would), uploaded once per call and gathered on the device.
+        A whitened model (diagonal or full-covariance q(u)) goes through WhiteDeviceFit (zigp_fit_steps_mode)."""
         self._make_resident()
         self._engine.select_rows(None)
-        fit = DenseDeviceFit(self._engine, pset)
+        fit = (WhiteDeviceFit if self.whiten else DenseDeviceFit)(self._engine, pset)
         done = 0
         while done < maxiter:
             n = min(DEVICE_FIT_CALL, maxiter - done)
@@ -166,11 +167,14 @@ class OnOffSVGP(Parameterized):
         out = self._engine.predict(self._values(), np.asarray(Xnew, dtype=np.float64), jitter=JITTER)
         return tuple(out[i].reshape(-1, 1) for i in range(9))
 
-    def optimize(self, method='L-BFGS-B', maxiter=1000, disp=False, callback=None, learning_rate=0.01, **kw):
+    def optimize(self, method='L-BFGS-B', maxiter=1000, disp=False, callback=None, learning_rate=0.01, device_loop=None, **kw):
         """GPflow Model.optimize: scipy L-BFGS-B on the free state (default), or Adam when method='adam'
         (the commented alternative at zero-inflated-gpflow.ipynb:155).  Adam without a callback runs its loop on the device
         (zigp_fit_steps, DEVICE_FIT_CALL iterations per call) when the mean function is Zero, whiten is off and q_diag is on; otherwise, or with a callback, every
-        iteration is a host step (select_rows + elbo + AdamGroups) -- the same minibatches and, to rounding, the same trajectory."""
+        iteration is a host step (select_rows + elbo + AdamGroups) -- the same minibatches and, to rounding, the same trajectory.
+        device_loop (method='adam' only): None is that rule; True runs the loop on the device for the whitened models as well (whiten=True,
+        with q_diag True or False: zigp_fit_steps_mode) and raises ValueError where it cannot -- a callback, a mean function other than
+        Zero, an unsupported transform; False forces the host loop."""
         pset = self._pset()
 
         def vg(_values):
@@ -181,7 +185,14 @@ class OnOffSVGP(Parameterized):
         if str(method).lower() == 'adam':
             for p in pset.params.values():
                 p.learning_rate = learning_rate
-            if callback is None and self._device_fit_eligible(pset):      # the whole loop on the device; a callback wants the host every step
+            if device_loop:
+                if callback is not None:
+                    raise ValueError('device_loop=True: a callback wants the host every step (device_loop=False, or no callback)')
+                if type(self.mean_function) is not Zero:
+                    raise ValueError('device_loop=True: the device loop fits the Zero mean function only (mean-function parameters stay with the host loop)')
+                self._adam_on_device(pset, maxiter)      # DenseDeviceFit / WhiteDeviceFit raise ValueError for a transform they do not implement
+                return None
+            if device_loop is None and callback is None and self._device_fit_eligible(pset):      # the whole loop on the device; a callback wants the host every step
                 self._adam_on_device(pset, maxiter)
                 return None
             opt = AdamGroups(pset)

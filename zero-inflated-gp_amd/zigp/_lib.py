@@ -75,6 +75,7 @@ class zigp_kron_head_fit_opts(C.Structure):
 
 
 DENSE_FIT_BLOCKS = 11   # include/zigp.h ZIGP_DENSE_FIT_BLOCKS
+FIT_DIAG, FIT_WHITE, FIT_WHITE_FULL = 0, 1, 2   # include/zigp.h ZIGP_FIT_*: the `mode` of zigp_fit_steps_mode
 
 
 class zigp_fit_opts(C.Structure):
@@ -115,6 +116,8 @@ SIGNATURES = {
                             C.c_int32, dp, dp, C.POINTER(zigp_grads)]),
     'zigp_fit_steps': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.POINTER(zigp_fit_opts), dp, dp, dp, C.c_int64, C.c_int64, C.c_int32,
                                  C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int32, dp, dp]),
+    'zigp_fit_steps_mode': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(zigp_params), C.POINTER(zigp_fit_opts), dp, dp, dp, C.c_int64, C.c_int64,
+                                      C.c_int32, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int32, dp, dp]),
     'zigp_fit_steps_applied': (C.c_int64, [C.c_void_p]),
     'zigp_predict': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), dp, C.c_int64, C.c_double, C.c_double, dp]),
     'zigp_predict_device': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p]),

@@ -345,6 +345,23 @@ class DenseEngine:
         Returns (elbo_data[n_steps], kl[n_steps]) -- the history, each at the parameters before that step's update.
         shape['whiten'] = True or shape['q_diag'] = False raises ValueError: the device loop fits the diagonal unwhitened parametrisation only."""
         self._set_modes(shape)     # the library refuses the call while either mode is on (ZIGP_EARG; the message names q_diag / whitening)
+        return self._fit_call(None, shape, x, m, v, lr, positive, trainable, ell_size, t0, n_steps, rows, batch, jitter, scale, beta1, beta2, eps,
+                              include_kl)
+
+    def fit_steps_mode(self, mode, shape, x, m, v, lr, positive, trainable, ell_size, t0, n_steps, rows=None, batch=0, jitter=1e-6, scale=1.0,
+                       beta1=0.9, beta2=0.999, eps=1e-8, include_kl=True):
+        """fit_steps for the parametrisation `mode` names (zigp_fit_steps_mode): _lib.FIT_DIAG (what fit_steps fits, bit for bit),
+        _lib.FIT_WHITE (the whitened model, the same 11 blocks) or _lib.FIT_WHITE_FULL (full-covariance q(u): blocks 4 and 5 of x / m / v
+        hold the M (M + 1) / 2 lower-triangle entries of the factors in row-major order, transforms.LowerTriangular's free vector, and
+        positive[4], positive[5] must be False).  The mode belongs to the call: the engine's set_whiten / set_q_full settings are neither
+        read nor changed, and shape's 'whiten' / 'q_diag' entries are ignored.  Arguments, return value, exceptions and what a
+        NotPositiveDefiniteError carries (steps_applied, the elbo_data / kl prefix) are those of fit_steps."""
+        return self._fit_call(int(mode), shape, x, m, v, lr, positive, trainable, ell_size, t0, n_steps, rows, batch, jitter, scale, beta1, beta2,
+                              eps, include_kl)
+
+    def _fit_call(self, mode, shape, x, m, v, lr, positive, trainable, ell_size, t0, n_steps, rows, batch, jitter, scale, beta1, beta2, eps,
+                  include_kl):
+        """mode None: zigp_fit_steps; otherwise zigp_fit_steps_mode"""
         s = _lib.zigp_params()
         s.Mf, s.Mg, s.D = int(shape['Mf']), int(shape['Mg']), int(shape['D'])
         o = _lib.zigp_fit_opts()
@@ -363,8 +380,9 @@ class DenseEngine:
                 raise ValueError('rows must hold n_steps * batch indices')
             rp = rows.ctypes.data
         ed, kl = np.zeros(max(n, 0)), np.zeros(max(n, 0))
-        rc = self.lib.zigp_fit_steps(self.ctx, C.byref(s), C.byref(o), ptr(x), ptr(m), ptr(v), x.size, int(t0), n, rp, int(batch), float(jitter),
-                                     float(scale), 1 if include_kl else 0, ptr(ed), ptr(kl))
+        tail = (C.byref(s), C.byref(o), ptr(x), ptr(m), ptr(v), x.size, int(t0), n, rp, int(batch), float(jitter), float(scale),
+                1 if include_kl else 0, ptr(ed), ptr(kl))
+        rc = self.lib.zigp_fit_steps(self.ctx, *tail) if mode is None else self.lib.zigp_fit_steps_mode(self.ctx, mode, *tail)
         try:
             _check(self.lib, self.ctx, rc)
         except ZigpError as e:

@@ -6,7 +6,8 @@
 * `AdamGroups` reproduces scripts/onoff.py:325-350: one tf.train.AdamOptimizer per distinct learning
   rate (TF defaults beta1=0.9, beta2=0.999, eps=1e-8; update lr_t = lr*sqrt(1-b2^t)/(1-b1^t)).
 * `DenseDeviceFit` keeps the same Adam state in the layout of zigp_fit_steps and advances it on the device
-  (the dense counterpart of onofftf.model.KronDeviceFit); `AdamGroups` is its host-side checker.
+  (the dense counterpart of onofftf.model.KronDeviceFit); `AdamGroups` is its host-side checker.  `WhiteDeviceFit` is the same for the
+  whitened models, diagonal and full-covariance (zigp_fit_steps_mode).
 """
 import numpy as np
 
@@ -198,9 +199,8 @@ class DenseDeviceFit:
         if self._stale():
             self.resync()
         try:
-            out = self.engine.fit_steps(self.shape, self.x, self.m, self.v, self.lr, self.positive, self.trainable, self.ell_size, self.t, n_steps,
-                                        rows=rows, batch=batch, jitter=jitter, scale=scale, beta1=self.beta1, beta2=self.beta2, eps=self.eps,
-                                        include_kl=include_kl)
+            out = self._engine_call(n_steps, rows=rows, batch=batch, jitter=jitter, scale=scale, beta1=self.beta1, beta2=self.beta2, eps=self.eps,
+                                    include_kl=include_kl)
             self.t += int(n_steps)
         except Exception as e:
             self.t += int(getattr(e, 'steps_applied', 0))
@@ -208,6 +208,9 @@ class DenseDeviceFit:
         finally:
             self.sync_params()
         return out
+
+    def _engine_call(self, n_steps, **kw):
+        return self.engine.fit_steps(self.shape, self.x, self.m, self.v, self.lr, self.positive, self.trainable, self.ell_size, self.t, n_steps, **kw)
 
     def _stale(self):
         """did anyone else write the ParamSet since sync_params?  equal_nan: a parameter that HAS gone NaN is still the value this object
@@ -233,3 +236,65 @@ class DenseDeviceFit:
             if tr:
                 q.set_free(self.x[sl])
         self._written = [q.value.copy() for k, q, sl in self._blocks()]
+
+
+class WhiteDeviceFit(DenseDeviceFit):
+    """DenseDeviceFit for the whitened models (zigp_fit_steps_mode): a ParamSet with the keys DENSE_FIT_KEYS whose u_fs_sqrt / u_gs_sqrt are
+    BOTH Log1pe(1e-6) vectors -- the whitened diagonal q(u), ZIGP_FIT_WHITE, the 11 blocks of DenseDeviceFit -- or BOTH
+    transforms.LowerTriangular(M) matrices, values (M, M) or (M, M, 1) -- the full-covariance q(u), ZIGP_FIT_WHITE_FULL: their blocks of
+    x / m / v are the M (M + 1) / 2 lower-triangle entries in row-major order, LowerTriangular's free vector, and sync_params writes the
+    matrices back with an exactly zero strict upper triangle.  One latent full and the other diagonal is refused.  steps / resync /
+    sync_params / the detection of outside changes are DenseDeviceFit's; AdamGroups on the same ParamSet is the host-side checker.
+    The engine's own whiten / q_full settings are neither read nor changed."""
+
+    def __init__(self, engine, pset, beta1=0.9, beta2=0.999, eps=1e-8):
+        from . import _lib
+        from .transforms import Log1pe, LowerTriangular
+        self.engine, self.pset = engine, pset
+        self.beta1, self.beta2, self.eps = beta1, beta2, eps
+        extra = [k for k in pset.params if k not in DENSE_FIT_KEYS]
+        if extra or any(k not in pset.params for k in DENSE_FIT_KEYS):
+            raise ValueError('the dense device fit loop trains exactly %s (got also / not: %s): mean-function parameters stay with the host loop'
+                             % (', '.join(DENSE_FIT_KEYS), ', '.join(extra) or 'a key is missing'))
+        ps = [pset.params[k] for k in DENSE_FIT_KEYS]
+        tri = [isinstance(ps[b].transform, LowerTriangular) for b in (4, 5)]
+        if tri[0] != tri[1]:
+            raise ValueError('u_fs_sqrt and u_gs_sqrt must both be LowerTriangular matrices (full-covariance q(u)) or both Log1pe vectors '
+                             '(diagonal q(u)): got %r and %r' % (ps[4].transform, ps[5].transform))
+        self.full = tri[0]
+        self.mode = _lib.FIT_WHITE_FULL if self.full else _lib.FIT_WHITE
+        for b, q in enumerate(ps):
+            if self.full and b in (4, 5):
+                continue
+            if b in (4, 5) and not isinstance(q.transform, Log1pe):
+                raise ValueError('%s: the diagonal q(u) of the whitened model is a Log1pe(1e-6) vector, not %r' % (DENSE_FIT_KEYS[b], q.transform))
+            if not isinstance(q.transform, Log1pe) and type(q.transform).__name__ != 'Identity':
+                raise ValueError('unsupported transform %r' % (q.transform,))
+            if isinstance(q.transform, Log1pe) and q.transform._lower != 1e-6:
+                raise ValueError('the device fit loop implements Log1pe with lower = 1e-6')
+        Zf, Zg = ps[0].value, ps[1].value
+        if Zf.ndim != 2 or Zg.ndim != 2 or Zf.shape[1] != Zg.shape[1]:
+            raise ValueError('Zf and Zg must be (M,D) with equal D')
+        D, M = Zf.shape[1], (Zf.shape[0], Zg.shape[0])
+        self.shape = dict(Mf=M[0], Mg=M[1], D=D)
+        if self.full:
+            for b in (4, 5):
+                q, Mh = ps[b], M[b - 4]
+                if q.transform.N != Mh or q.value.shape not in ((Mh, Mh), (Mh, Mh, 1)):
+                    raise ValueError('%s must be a LowerTriangular(%d) matrix of shape (%d, %d) or (%d, %d, 1), not %r of shape %r'
+                                     % (DENSE_FIT_KEYS[b], Mh, Mh, Mh, Mh, Mh, q.transform, q.value.shape))
+        self.sizes = [q.free_size() for q in ps]       # entries of the FREE vectors: M (M + 1) / 2 for a full factor
+        ns = [Mh * (Mh + 1) // 2 if self.full else Mh for Mh in M]
+        want = [Zf.size, Zg.size, M[0], M[1], ns[0], ns[1], None, None, 1, 1, 1]
+        for k, n, w in zip(DENSE_FIT_KEYS, self.sizes, want):
+            if (w is None and n not in (1, D)) or (w is not None and n != w):
+                raise ValueError('%s has %d entries' % (k, n))
+        self.ell_size = (self.sizes[6], self.sizes[7])
+        self.positive = [isinstance(q.transform, Log1pe) for q in ps]
+        self.m, self.v = np.zeros(sum(self.sizes)), np.zeros(sum(self.sizes))
+        self.t = 0
+        self.resync()
+
+    def _engine_call(self, n_steps, **kw):
+        return self.engine.fit_steps_mode(self.mode, self.shape, self.x, self.m, self.v, self.lr, self.positive, self.trainable, self.ell_size,
+                                          self.t, n_steps, **kw)
