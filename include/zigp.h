@@ -32,11 +32,18 @@ extern "C" {
 
 typedef struct zigp_ctx zigp_ctx;
 
+/* Largest input dimension D of the dense entry points (zigp_elbo, zigp_predict, zigp_predict_device, zigp_prior_kl, zigp_rbf_K,
+ * zigp_set_data, zigp_set_data_device, zigp_select_rows; all three parametrisations).  D <= 8 runs the kernels specialised per
+ * dimension; 9 <= D <= ZIGP_MAX_D runs the run-time-D ("wide") kernels.  Narrower: the device fit loops (zigp_fit_steps,
+ * zigp_fit_steps_mode) and a Linear mean function (zigp_set_mean_function with D > 0) stay at D <= 8, and the Kronecker path has its
+ * own fixed factor dimensions.  A larger D is ZIGP_EARG. */
+#define ZIGP_MAX_D 64
+
 /* Constrained parameter values of the dense model.  Replaces the Param members created in
  * OnOffSVGP.__init__ (onoffgpf/OnOffSVGP.py:50-71), the two gpflow.kernels.RBF objects
  * (zero-inflated-gpflow.ipynb:98-104; twin KernSE onofftf/main.py:33-63) and
  * OnOffLikelihood.variance (onoffgpf/OnOffLikelihood.py:26).
- * ell_*: D lengthscales (ARD; broadcast a scalar on the host). u_*s_sqrt: diagonal q_sqrt (q_diag=True,
+ * 1 <= D <= ZIGP_MAX_D (64).  ell_*: D lengthscales (ARD; broadcast a scalar on the host). u_*s_sqrt: diagonal q_sqrt (q_diag=True,
  * OnOffSVGP.py:34). */
 typedef struct {
   int32_t Mf, Mg, D, reserved;
@@ -268,7 +275,8 @@ int64_t zigp_kron_fit_steps_applied(zigp_ctx* ctx);
 /* Mean function of the latent f: m(x) = b + a . x, added to fmean before the likelihood and in zigp_predict
  * (`fmean = fmean + self.mean_function(Xnew)`, onoffgpf/OnOffSVGP.py:29,134).  Covers GPflow's Zero (the reference default:
  * D = -1 -- the state after zigp_create; a and b are ignored), Constant (D = 0, b = c; enabled also when c == 0, so that the
- * parameter still receives its gradient) and Linear with one output (a[D], b).  The setting
+ * parameter still receives its gradient) and Linear with one output (a[D], b; D <= 8 -- Zero and Constant work at every input dimension,
+ * a Linear mean at more than 8 columns is ZIGP_EARG).  The setting
  * persists in the context.  zigp_get_mean_function_grad returns d(scale * sum var_exp)/d(a, b) of the LAST zigp_elbo
  * called with grads != NULL (zeros when the mean function is off); like the other gradients it is a per-shard partial
  * sum under data-parallel use. */

@@ -49,6 +49,11 @@ int zigp_set_kron_panels(zigp_ctx* ctx, int32_t on);
  * the whole k range of its row block.  out[8] = {workgroups of latent f's list, of latent g's, entries per workgroup f, g, tail units f, g,
  * largest tail workgroup in k blocks, paired order (0 / 1)}.  Returns 0, ZIGP_EARG, or -10 ... -13 for a list that is not a partition. */
 int zigp_test_trmm_list(int32_t lower, int32_t Mf, int32_t Mg, int64_t Nc, int32_t tail_on, int64_t* out);
+/* Host only (no context, no GPU): the tile list of the moments product of the wide Kuf gradient (input dimensions 9 .. ZIGP_MAX_D) as
+ * zigp_elbo plans it for M inducing points and a chunk of Nc rows (a multiple of 1024).  out[0] = split-K slices, out[1] = list entries
+ * per workgroup, out[2] = entries, then (bi, bj, kbeg, kend, slice) per entry (k in units of 16 rows), as many entries as fit `cap`
+ * int64 values.  Returns 0 or ZIGP_EARG. */
+int zigp_test_kgmom_list(int32_t M, int64_t Nc, int64_t cap, int64_t* out);
 /* The gradient step of the larger fused grids (<= 16 x <= 112 points) sends its rows through in ranges of `tiles` 16-point tiles
  * (default 1024 = 16 384 rows: the per-point operand records of a range stay within 128 MB).  Results do not depend on it, bit for bit;
  * the tests lower it to run many ranges on small inputs. */

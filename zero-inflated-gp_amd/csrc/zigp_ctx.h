@@ -59,7 +59,7 @@ struct CachedTiles {   // an entry of the tile cache: owns the device copy of it
 struct Latent {
   int M = 0, Mp = 0;
   DevBuf Z, ell, u, s, s2;              // Z (Mp,D) zero padded; u,s,s2 (Mp) zero padded
-  double zc[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // mean inducing input (host copy): centre of k_kgrad's moment sums
+  double zc[64] = {0};                       // [ZIGP_MAX_D] mean inducing input (host copy): centre of k_kgrad's moment sums
   bool kg_exact = false;                     // inducing inputs spread over > KG_EXACT_SPREAD lengthscales: k_kgrad forms x - z_m per row (no centre shift)
   DevBuf Zs;                            // Z scaled by KUF_C / ell_d (k_kuf_build's units), same padding
   double var = 1.0;
@@ -72,6 +72,7 @@ struct Latent {
   DevBuf part;                           // [3][Mp/32][Nc] partial rows of the fused column sums: v^T A1, sum A1^2, sum s^2 A2^2
   DevBuf gm, gv;                         // cotangents of mean / var per column [Nc]
   DevBuf du, dsq, krow;                  // row accumulators: du[Mp], dsq[Mp], krow[Mp][1+2D]
+  DevBuf xm, mom, ks0;                   // wide Kuf gradient (D > 8, centred form): operand XM [Nc][128], split-K planes [S][Mp][128], per-split sum T [KG_SPLIT][Mp]
   DevBuf dLpart;                         // [S][Mp*Mp] split-K partials of the rank-N updates
   DevBuf T1, T2, T3, G;                  // MxM scratch
   DevBuf sk;                             // [S][Mp*Mp] split-K planes of the O(M^3) products of the reverse pass

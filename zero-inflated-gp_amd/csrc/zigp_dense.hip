@@ -50,6 +50,11 @@
 
 using namespace zigp;
 
+static_assert(WIDE_MAXD == ZIGP_MAX_D, "the wide kernels' hyperparameter structs hold ZIGP_MAX_D entries");
+#define ZIGP_STR2(x) #x
+#define ZIGP_STR(x) ZIGP_STR2(x)
+#define ZIGP_MAX_D_STR ZIGP_STR(ZIGP_MAX_D)
+
 namespace {
 
 struct HostLatent {
@@ -63,7 +68,7 @@ struct HostLatent {
 // (latents_upload; zigp_test_kgrad's defaults)
 void kgrad_centre(Latent& lt, const double* Z, const double* ell, int M, int D) {
   double spread = 0.0;
-  for (int d = 0; d < MAXD; ++d) {
+  for (int d = 0; d < WIDE_MAXD; ++d) {
     double sum = 0.0;
     if (d < D) for (int m = 0; m < M; ++m) sum += Z[(size_t)m * D + d];
     lt.zc[d] = M > 0 ? sum / M : 0.0;
@@ -84,7 +89,7 @@ int latents_layout(zigp_ctx* c, const int (&M)[2], int D, size_t (&off)[2][6], s
     lt.Mp = (int)round_up(M[h], BM);
     const size_t Mp = lt.Mp;
     off[h][0] = total; total += Mp * D;      // Z
-    off[h][1] = total; total += MAXD;        // ell
+    off[h][1] = total; total += std::max(D, MAXD);   // ell: max(D, 8) doubles, so every offset is what it was for D <= 8
     off[h][2] = total; total += Mp;          // u
     off[h][3] = total; total += Mp;          // s
     off[h][4] = total; total += Mp * D;      // Zs = Z scaled to k_kuf_build's units (the same doubles the kernel multiplies into x)
@@ -97,7 +102,7 @@ int latents_views(zigp_ctx* c, const size_t (&off)[2][6], int D) {
   for (int h = 0; h < 2; ++h) {
     Latent& lt = c->lat[h];
     const size_t Mp = lt.Mp;
-    lt.Z.alias(c->parm.p + off[h][0], Mp * D); lt.ell.alias(c->parm.p + off[h][1], MAXD);
+    lt.Z.alias(c->parm.p + off[h][0], Mp * D); lt.ell.alias(c->parm.p + off[h][1], std::max(D, MAXD));
     lt.u.alias(c->parm.p + off[h][2], Mp); lt.s.alias(c->parm.p + off[h][3], Mp); lt.Zs.alias(c->parm.p + off[h][4], Mp * D);
     ZIGP_ENSURE(c, lt.s2, Mp);
     ZIGP_ENSURE(c, lt.Kuu, Mp * Mp);
@@ -128,7 +133,7 @@ int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D, bool q_full = 
     memcpy(img + off[h][2], q.u, sizeof(double) * q.M);
     if (q_full) for (int m = 0; m < q.M; ++m) img[off[h][3] + m] = q.s[(size_t)m * q.M + m];
     else memcpy(img + off[h][3], q.s, sizeof(double) * q.M);
-    const KufHyp kh = make_kuf_hyp(q.ell, q.var, D);
+    const KufHypWide kh = make_kuf_hyp_wide(q.ell, q.var, D);
     kgrad_centre(c->lat[h], q.Z, q.ell, q.M, D);
     for (int m = 0; m < q.M; ++m)
       for (int d = 0; d < D; ++d) img[off[h][4] + (size_t)m * D + d] = q.Z[(size_t)m * D + d] * kh.scale[d];
@@ -200,6 +205,9 @@ int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter
     if (d_hyp)
       hipLaunchKernelGGL(k_kuu_setup<LatHypDev>, grid, dim3(256), 0, c->stream, lt.Z.p, (int64_t)hl[h].M, LatHypDev{d_hyp + h * DH_LAT, D}, jitter, lt.Kuu.p,
                          lt.L.p, lt.W.p, lt.s.p, lt.s2.p, (int64_t)Mp);
+    else if (D > MAXD)
+      hipLaunchKernelGGL(k_kuu_setup<KernHypWide>, grid, dim3(256), 0, c->stream, lt.Z.p, (int64_t)hl[h].M, make_hyp_wide(hl[h].ell, hl[h].var, D), jitter,
+                         lt.Kuu.p, lt.L.p, lt.W.p, lt.s.p, lt.s2.p, (int64_t)Mp);
     else {
       KernHyp hyp = make_hyp(hl[h].ell, hl[h].var, D);
       hipLaunchKernelGGL(k_kuu_setup<KernHyp>, grid, dim3(256), 0, c->stream, lt.Z.p, (int64_t)hl[h].M, hyp, jitter, lt.Kuu.p,
@@ -282,7 +290,7 @@ int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter
 int latent_chunk_kuf(zigp_ctx* c, Latent& lt, const double* dX, int64_t Nrows, int64_t n0, int64_t Nc, int D, const double* ell_host,
                      const double* R = nullptr) {
   const int Mp = lt.Mp;
-  const KufHyp kh = R ? KufHyp() : make_kuf_hyp(ell_host, lt.var, D);
+  const KufHyp kh = (R || D > MAXD) ? KufHyp() : make_kuf_hyp(ell_host, lt.var, D);
   ProfScope ps(c, PC_KUF);
   const dim3 grid((unsigned)(Nc / 512), Mp / 16), block(256);
 #define ZIGP_KUF(DD)                                                                                                                   \
@@ -292,7 +300,10 @@ int latent_chunk_kuf(zigp_ctx* c, Latent& lt, const double* dX, int64_t Nrows, i
     break;
   switch (D) {
     ZIGP_KUF(1) ZIGP_KUF(2) ZIGP_KUF(3) ZIGP_KUF(4) ZIGP_KUF(5) ZIGP_KUF(6) ZIGP_KUF(7) ZIGP_KUF(8)
-    default: return fail_arg(c, "D out of range");
+    default:      // 9 .. ZIGP_MAX_D: the run-time-D kernel, hyperparameters by value (the fit loop's device block stops at MAXD)
+      if (D < 1 || D > WIDE_MAXD || R) return fail_arg(c, "D out of range");
+      hipLaunchKernelGGL(k_kuf_build_wide, grid, block, 0, c->stream, dX, Nrows, n0, lt.Zs.p, lt.M, D, make_kuf_hyp_wide(ell_host, lt.var, D), lt.K.p, Nc);
+      break;
   }
 #undef ZIGP_KUF
   ZIGP_HIP(c, hipGetLastError());
@@ -310,12 +321,13 @@ struct ChunkPlan {
   int64_t Nc = 0;
   bool paired = false;   // and merged: each forward product is ONE launch for both latents
   TrmmTail tail = {{0, 0}, {64, 64}};
-  struct Lat { TileSpec a1_spec, a2j_spec, syr_spec; TileList a1, a2j, syr; double fl = 0.0; } lat[2];   // a2j: A2 or J'; fl = M^2 Nc
+  struct Lat { TileSpec a1_spec, a2j_spec, syr_spec, mom_spec; TileList a1, a2j, syr, mom; double fl = 0.0; } lat[2];   // a2j: A2 or J'; fl = M^2 Nc;
+                                                                                             // mom: moments product of the wide Kuf gradient (D > MAXD)
 };
 // whiten: A = W K is the same lower-triangular list; a gradient step adds the UPPER-triangular J' = (W^T D) A (the paired / tail lists of
 // A2) and the rank-N update, a value-only or predict pass has no second product at all (a2j stays empty).
 // q_full: the unwhitened lists in both modes -- A and B = Lq^T A are the A1 / A2 pair, J' = R A is the full product.
-ChunkPlan chunk_plan(const int (&M)[2], int64_t Nc, bool need_grad, bool tail_on, bool whiten = false, bool q_full = false) {
+ChunkPlan chunk_plan(const int (&M)[2], int64_t Nc, bool need_grad, bool tail_on, bool whiten = false, bool q_full = false, bool wide = false) {
   if (q_full) whiten = false;
   ChunkPlan pl;
   const int nbm[2] = {ceil_div(M[0], BM), ceil_div(M[1], BM)}, nbn = (int)(Nc / BN);
@@ -335,6 +347,7 @@ ChunkPlan chunk_plan(const int (&M)[2], int64_t Nc, bool need_grad, bool tail_on
       L.a2j_spec = full_xcd_tiles(nbm[h], nbn, nbm[h] * (BM / BK));
       L.syr_spec = syr2k_tiles(nbm[h], (int)(Nc / BK), syr_plan(nbm[h]));
     } else L.a2j_spec = trmm_tiles(false, nbm[h], nbn, pl.paired, pl.tail.units[h], pl.tail.bins[h]);
+    if (need_grad && wide) L.mom_spec = kgmom_tiles(nbm[h], Nc);
     L.fl = (double)M[h] * M[h] * (double)Nc;
   }
   return pl;
@@ -344,6 +357,7 @@ int upload_plan(zigp_ctx* c, ChunkPlan& pl) {
     ZIGP_TRY(get_tiles(c, L.a1_spec, L.a1));
     if (L.a2j_spec.build) ZIGP_TRY(get_tiles(c, L.a2j_spec, L.a2j));
     if (L.syr_spec.build) ZIGP_TRY(get_tiles(c, L.syr_spec, L.syr));
+    if (L.mom_spec.build) ZIGP_TRY(get_tiles(c, L.mom_spec, L.mom));
   }
   return 0;
 }
@@ -442,10 +456,36 @@ int chunk_forward_white(zigp_ctx* c, const ChunkPlan& pl, bool need_grad, bool p
   return 0;
 }
 
-// Kuf-cotangent reductions of one latent and chunk (HBM-read bound; runs on the side stream under the chunk's SYRKs)
-int latent_chunk_kgrad(zigp_ctx* c, Latent& lt, const double* dX, int64_t Nrows, int64_t n0, int64_t Nc, int D, const double* ell_host) {
+// D > MAXD, centred form: T over J' and the operand XM (k_kgrad_wide_prep), the moments product on the GEMM core, the planes into krow.
+// `mom` is the chunk shape's planned list (ChunkPlan::Lat::mom); the buffers were sized before the loop (dense_prepare_buffers).
+int latent_chunk_kgrad_wide(zigp_ctx* c, Latent& lt, const double* dX, int64_t Nrows, int64_t n0, int64_t Nc, int D, const TileList& mom) {
+  const int Mp = lt.Mp, S = kgmom_slices(Mp / BM, Nc);
+  if (mom.n != S * (Mp / BM)) return fail_arg(c, "wide Kuf gradient: the moments product's tile list was not planned for this chunk shape");
+  KgCentreWide ctr;
+  for (int d = 0; d < WIDE_MAXD; ++d) ctr.c[d] = lt.zc[d];
+  hipLaunchKernelGGL(k_kgrad_wide_prep, dim3(Mp / KG_ROWS, KG_SPLIT), dim3(256), 0, c->stream, lt.Jp.p, lt.K.p, lt.vec.p + Mp, lt.gm.p, lt.gv.p, dX, Nrows,
+                     n0, lt.M, Mp, D, Nc, (int64_t)Mp * (2 + 2 * D), ctr, lt.krow.p, lt.ks0.p, lt.xm.p);
+  ZIGP_HIP(c, hipGetLastError());
+  GemmArgs g = mk_args(lt.Jp.p, Nc, lt.xm.p, WIDE_MOM_COLS, lt.mom.p, WIDE_MOM_COLS);
+  g.slice_stride = (int64_t)Mp * WIDE_MOM_COLS;
+  ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_MNCONTIG, false>(c, mom, g, EpiStore())));
+  hipLaunchKernelGGL(k_kgrad_wide_finish, dim3(Mp / 4), dim3(256), 0, c->stream, lt.mom.p, S, lt.ks0.p, lt.Z.p, lt.M, Mp, D, ctr, lt.krow.p);
+  ZIGP_HIP(c, hipGetLastError());
+  return 0;
+}
+int ensure_kgrad_wide(zigp_ctx* c, Latent& lt, int64_t Nc) {
   const int Mp = lt.Mp;
-  KgCentre hyp;
+  ZIGP_ENSURE(c, lt.xm, (size_t)Nc * WIDE_MOM_COLS);
+  ZIGP_ENSURE(c, lt.mom, (size_t)kgmom_slices(Mp / BM, Nc) * Mp * WIDE_MOM_COLS);
+  ZIGP_ENSURE(c, lt.ks0, (size_t)KG_SPLIT * Mp);
+  return 0;
+}
+
+// Kuf-cotangent reductions of one latent and chunk (HBM-read bound; runs on the side stream under the chunk's SYRKs)
+int latent_chunk_kgrad(zigp_ctx* c, Latent& lt, const double* dX, int64_t Nrows, int64_t n0, int64_t Nc, int D, const double* ell_host,
+                       const TileList& mom = TileList()) {
+  const int Mp = lt.Mp;
+  KgCentre hyp;     // (not read by the wide launches)
   for (int d = 0; d < MAXD; ++d) hyp.c[d] = lt.zc[d];
   double* alpha = lt.vec.p + Mp;
   {
@@ -463,7 +503,14 @@ int latent_chunk_kgrad(zigp_ctx* c, Latent& lt, const double* dX, int64_t Nrows,
     break;
     switch (D) {
       ZIGP_KGRAD(1) ZIGP_KGRAD(2) ZIGP_KGRAD(3) ZIGP_KGRAD(4) ZIGP_KGRAD(5) ZIGP_KGRAD(6) ZIGP_KGRAD(7) ZIGP_KGRAD(8)
-      default: return fail_arg(c, "D out of range");
+      default:      // 9 .. ZIGP_MAX_D: the centred moments on the GEMM core, or (lt.kg_exact) the per-row form over windows of WIDE_SLICE
+                    // dimensions, one launch each
+        if (D < 1 || D > WIDE_MAXD) return fail_arg(c, "D out of range");
+        if (!lt.kg_exact) { ZIGP_TRY(latent_chunk_kgrad_wide(c, lt, dX, Nrows, n0, Nc, D, mom)); break; }
+        for (int d0 = 0; d0 < D; d0 += WIDE_SLICE)
+          hipLaunchKernelGGL(k_kgrad_slice, gk, bk, 0, c->stream, lt.Jp.p, lt.K.p, alpha, lt.gm.p, lt.gv.p, dX, Nrows, n0, lt.Z.p, lt.M, D, d0, Nc,
+                             slab, lt.krow.p);
+        break;
     }
 #undef ZIGP_KGRAD
     ZIGP_HIP(c, hipGetLastError());
@@ -488,6 +535,15 @@ void latent_sym_from_planes(zigp_ctx* c, Latent& lt) {
   const SyrPlan sp = syr_plan(Mp / BM);
   const int nt = Mp / 32;
   hipLaunchKernelGGL(k_sym_from_planes, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, lt.dLpart.p, sp.So, sp.Sd, (int64_t)Mp, lt.T1.p);
+}
+
+// G (in T3) -> slab 0 of krow: k_kuu_grad, or for D > MAXD its windows of WIDE_SLICE dimensions
+void launch_kuu_grad(zigp_ctx* c, Latent& lt, int D, double jitter) {
+  const int Mp = lt.Mp;
+  if (D > MAXD)
+    hipLaunchKernelGGL(k_kuu_grad_wide, dim3(Mp, ceil_div(D, WIDE_SLICE)), dim3(256), 0, c->stream, lt.T3.p, lt.Kuu.p, jitter, lt.Z.p, lt.M, D, (int64_t)Mp,
+                       lt.krow.p);
+  else hipLaunchKernelGGL(k_kuu_grad, dim3(Mp), dim3(256), 0, c->stream, lt.T3.p, lt.Kuu.p, jitter, lt.Z.p, lt.M, D, (int64_t)Mp, lt.krow.p);
 }
 
 // MxM backward: G = dELBO/dKuu (symmetric) -> krow accumulators.
@@ -548,7 +604,7 @@ int latent_mxm_backward(zigp_ctx* c, Latent& lt, int D, double jitter, bool with
   // G = sym(S) - dKL/dKuu -> T3 (T3 free again)
   hipLaunchKernelGGL(k_sym_combine, dim3(gridmm), dim3(256), 0, c->stream, S, P, PSP, lt.vec.p + Mp, with_data ? 1 : 0, with_kl ? 1 : 0,
                      (int64_t)Mp, lt.T3.p);
-  hipLaunchKernelGGL(k_kuu_grad, dim3(Mp), dim3(256), 0, c->stream, lt.T3.p, lt.Kuu.p, jitter, lt.Z.p, lt.M, D, (int64_t)Mp, lt.krow.p);
+  launch_kuu_grad(c, lt, D, jitter);
   ZIGP_HIP(c, hipGetLastError());
   return 0;
 }
@@ -594,7 +650,7 @@ int latent_mxm_backward_white(zigp_ctx* c, Latent& lt, int D, double jitter, boo
   // G = sym(S) -> T3
   hipLaunchKernelGGL(k_sym_combine, dim3(gridmm), dim3(256), 0, c->stream, lt.T1.p, lt.T1.p, lt.T1.p, lt.vec.p + Mp, with_data ? 1 : 0, 0,
                      (int64_t)Mp, lt.T3.p);
-  hipLaunchKernelGGL(k_kuu_grad, dim3(Mp), dim3(256), 0, c->stream, lt.T3.p, lt.Kuu.p, jitter, lt.Z.p, lt.M, D, (int64_t)Mp, lt.krow.p);
+  launch_kuu_grad(c, lt, D, jitter);
   ZIGP_HIP(c, hipGetLastError());
   return 0;
 }
@@ -602,7 +658,10 @@ int latent_mxm_backward_white(zigp_ctx* c, Latent& lt, int D, double jitter, boo
 int validate_params(zigp_ctx* c, const zigp_params* p) {
   if (!p) return fail_arg(c, "params is NULL");
   if (p->Mf <= 0 || p->Mg <= 0) return fail_arg(c, "Mf and Mg must be positive");
-  if (p->D <= 0 || p->D > MAXD) return fail_arg(c, "D must be in [1, 8]");
+  if (p->D <= 0 || p->D > ZIGP_MAX_D) return fail_arg(c, "D must be in [1, " ZIGP_MAX_D_STR "] (ZIGP_MAX_D)");
+  if (p->D > MAXD && c->mean_on)
+    for (int d = 0; d < MAXD; ++d)
+      if (c->mean_a[d] != 0.0) return fail_arg(c, "a Linear mean function is set and D > 8: Linear covers D in [1, 8] (Zero and Constant work at every D)");
   if (!p->Zf || !p->Zg || !p->u_fm || !p->u_gm || !p->u_fs_sqrt || !p->u_gs_sqrt || !p->ell_f || !p->ell_g)
     return fail_arg(c, "NULL pointer in params");
   if (!(p->var_f > 0) || !(p->var_g > 0) || !(p->noise > 0)) return fail_arg(c, "variances must be positive");
@@ -714,6 +773,7 @@ int dense_prepare_buffers(zigp_ctx* c, DenseCall& k) {
       if (!k.whiten || k.need_grad || k.q_full) ZIGP_ENSURE(c, lt.A1, (size_t)Mp * Nc);     // a whitened (diagonal) value-only / predict pass stores no panel but K
       ZIGP_ENSURE(c, lt.part, (size_t)3 * (Mp / 32) * Nc);
       if (k.need_grad) ZIGP_ENSURE(c, lt.Jp, (size_t)Mp * Nc);
+      if (k.need_grad && D > MAXD && !lt.kg_exact) ZIGP_TRY(ensure_kgrad_wide(c, lt, Nc));
     }
     if (k.need_grad) {
       ZIGP_ENSURE(c, lt.du, Mp); ZIGP_ENSURE(c, lt.dsq, Mp); ZIGP_ENSURE(c, lt.krow, (size_t)KG_SPLIT * Mp * (2 + 2 * D));
@@ -788,7 +848,8 @@ int dense_chunk_loop(zigp_ctx* c, const DenseCall& k) {
     return 0;
   };
   auto kgrad = [&](int64_t n0, int64_t Nc) -> int {
-    for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_kgrad(c, c->lat[h], k.dX, k.Nrows, n0, Nc, D, k.ell_h[h]));
+    const ChunkPlan& pl = k.plan[Nc == k.plan[0].Nc ? 0 : 1];
+    for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_kgrad(c, c->lat[h], k.dX, k.Nrows, n0, Nc, D, k.ell_h[h], pl.lat[h].mom));
     return 0;
   };
   // Side-stream section: stream2 forks from the main stream, runs `work` and records ev_join, which the main stream waits on
@@ -934,9 +995,9 @@ int dense_plan(zigp_ctx* c, DenseCall& k) {
   k.Nc = chunk_rows_for(c->chunk_auto, c->chunk, round_up(std::max(M[0], M[1]), BM), span);
   if (k.has_rows) {
     const int64_t last = std::min<int64_t>(k.Nc, round_up(span - (span - 1) / k.Nc * k.Nc, 1024));
-    k.plan[0] = chunk_plan(M, k.Nc, k.need_grad, c->trmm_tail, k.whiten, k.q_full);
+    k.plan[0] = chunk_plan(M, k.Nc, k.need_grad, c->trmm_tail, k.whiten, k.q_full, k.D > MAXD);
     ZIGP_TRY(upload_plan(c, k.plan[0]));
-    if (last != k.Nc) { k.plan[1] = chunk_plan(M, last, k.need_grad, c->trmm_tail, k.whiten, k.q_full); ZIGP_TRY(upload_plan(c, k.plan[1])); }
+    if (last != k.Nc) { k.plan[1] = chunk_plan(M, last, k.need_grad, c->trmm_tail, k.whiten, k.q_full, k.D > MAXD); ZIGP_TRY(upload_plan(c, k.plan[1])); }
   }
   return 0;
 }
@@ -1071,7 +1132,7 @@ static_assert(MAXD == 8, "zigp_ctx::mean_a / mean_da hold MAXD entries");
 
 int zigp_set_mean_function(zigp_ctx* c, const double* a, int32_t D, double b) {
   if (!c) return ZIGP_EARG;
-  if (D < -1 || D > MAXD || (D > 0 && !a)) return fail_arg(c, "zigp_set_mean_function: need -1 <= D <= 8 and a[D]");
+  if (D < -1 || D > MAXD || (D > 0 && !a)) return fail_arg(c, "zigp_set_mean_function: need -1 <= D <= 8 and a[D] (a Linear mean function covers D in [1, 8]; Zero and Constant work at every D)");
   if (D < 0) {   // Zero: no mean function, nothing to differentiate
     for (int d = 0; d < MAXD; ++d) c->mean_a[d] = 0.0;
     c->mean_b = 0.0; c->mean_on = false;
@@ -1112,7 +1173,7 @@ int zigp_get_mean_function_grad(zigp_ctx* c, double* da, int32_t D, double* db) 
 
 int zigp_set_data(zigp_ctx* c, const double* X, const double* Y, int64_t N, int32_t D) {
   if (!c) return ZIGP_EARG;
-  if (!X || !Y || N <= 0 || D <= 0 || D > MAXD) return fail_arg(c, "zigp_set_data: bad arguments (need X, Y, N>0, 1<=D<=8)");
+  if (!X || !Y || N <= 0 || D <= 0 || D > ZIGP_MAX_D) return fail_arg(c, "zigp_set_data: bad arguments (need X, Y, N>0, 1<=D<=" ZIGP_MAX_D_STR ")");
   ZIGP_HIP(c, hipSetDevice(c->device));
   ZIGP_ENSURE(c, c->ownX, (size_t)N * D);
   ZIGP_ENSURE(c, c->ownY, (size_t)N);
@@ -1126,7 +1187,7 @@ int zigp_set_data(zigp_ctx* c, const double* X, const double* Y, int64_t N, int3
 
 int zigp_set_data_device(zigp_ctx* c, const double* dX, const double* dY, int64_t N, int32_t D) {
   if (!c) return ZIGP_EARG;
-  if (!dX || !dY || N <= 0 || D <= 0 || D > MAXD) return fail_arg(c, "zigp_set_data_device: bad arguments");
+  if (!dX || !dY || N <= 0 || D <= 0 || D > ZIGP_MAX_D) return fail_arg(c, "zigp_set_data_device: bad arguments (need dX, dY, N>0, 1<=D<=" ZIGP_MAX_D_STR ")");
   c->dX = dX; c->dY = dY; c->N = N; c->D = D;
   c->fullX = dX; c->fullY = dY; c->fullN = N;
   return ZIGP_OK;
@@ -1191,7 +1252,9 @@ int dense_fit_steps(zigp_ctx* c, int32_t mode, bool legacy, const zigp_params* s
   if (mode != ZIGP_FIT_DIAG && mode != ZIGP_FIT_WHITE && mode != ZIGP_FIT_WHITE_FULL)
     return bad("unknown mode (ZIGP_FIT_DIAG, ZIGP_FIT_WHITE, ZIGP_FIT_WHITE_FULL)");
   const bool white = mode != ZIGP_FIT_DIAG, full = mode == ZIGP_FIT_WHITE_FULL;
-  if (shape->Mf <= 0 || shape->Mg <= 0 || shape->D <= 0 || shape->D > MAXD) return bad("need Mf, Mg > 0 and 1 <= D <= 8");
+  if (shape->Mf <= 0 || shape->Mg <= 0 || shape->D <= 0) return bad("need Mf, Mg > 0 and D >= 1");
+  if (shape->D > MAXD)
+    return bad(("D = " + std::to_string(shape->D) + ": the device fit loop covers D in [1, 8] (zigp_elbo + a host optimiser fit every D up to " ZIGP_MAX_D_STR ")").c_str());
   if (n_steps <= 0 || t0 < 0 || (rows && batch <= 0)) return bad("need n_steps > 0, t0 >= 0 and, with rows, batch > 0");
   if (!(jitter >= 0)) return bad("jitter must be >= 0");
   if (!(o->beta1 >= 0 && o->beta1 < 1 && o->beta2 >= 0 && o->beta2 < 1 && o->eps > 0)) return bad("bad Adam constants");
@@ -1280,7 +1343,7 @@ int dense_fit_steps(zigp_ctx* c, int32_t mode, bool legacy, const zigp_params* s
     Latent& lt = c->lat[h];
     lt.var = 0.0;            // not read: the kernels take it from the block
     lt.kg_exact = true;      // the per-row form of k_kgrad: the centred form needs a centre chosen from Z and ell, which move on the device
-    for (int q = 0; q < MAXD; ++q) lt.zc[q] = 0.0;
+    for (int q = 0; q < WIDE_MAXD; ++q) lt.zc[q] = 0.0;
     if (full) {     // the M x M buffers of the full factor (latents_upload / latent_qfull_dlq size them for zigp_elbo): before the first step
       const size_t mm = (size_t)M[h] * M[h], mmp = (size_t)lt.Mp * lt.Mp;
       ZIGP_ENSURE(c, lt.Lraw, mm); ZIGP_ENSURE(c, lt.Lq, mmp); ZIGP_ENSURE(c, lt.lqssq, mmp / 256); ZIGP_ENSURE(c, lt.T3, mmp); ZIGP_ENSURE(c, lt.dLq, mmp);
@@ -1417,7 +1480,8 @@ int zigp_prior_kl(zigp_ctx* c, const zigp_params* p, double jitter, double* kl2)
 
 int zigp_rbf_K(zigp_ctx* c, const double* X1, int64_t n1, const double* X2, int64_t n2, int32_t D, const double* ell, double var, double* K) {
   if (!c) return ZIGP_EARG;
-  if (!X1 || n1 <= 0 || D <= 0 || D > MAXD || !ell || !K) return fail_arg(c, "zigp_rbf_K: bad arguments");
+  if (!X1 || n1 <= 0 || D <= 0 || !ell || !K) return fail_arg(c, "zigp_rbf_K: bad arguments");
+  if (D > ZIGP_MAX_D) return fail_arg(c, "zigp_rbf_K: D must be in [1, " ZIGP_MAX_D_STR "] (ZIGP_MAX_D)");
   if (!X2) n2 = n1;
   if (n2 <= 0) return fail_arg(c, "zigp_rbf_K: bad n2");
   ZIGP_HIP(c, hipSetDevice(c->device));
@@ -1426,8 +1490,13 @@ int zigp_rbf_K(zigp_ctx* c, const double* X1, int64_t n1, const double* X2, int6
   double* d1 = c->scratch.p; double* d2 = d1 + n1 * D;
   ZIGP_HIP(c, hipMemcpyAsync(d1, X1, sizeof(double) * n1 * D, hipMemcpyHostToDevice, c->stream));
   ZIGP_HIP(c, hipMemcpyAsync(d2, X2 ? X2 : X1, sizeof(double) * n2 * D, hipMemcpyHostToDevice, c->stream));
-  KernHyp h = make_hyp(ell, var, D);
-  hipLaunchKernelGGL(k_rbf_matrix, dim3(ceil_div(n1 * n2, 256)), dim3(256), 0, c->stream, d1, n1, d2, n2, h, 0.0, c->scratch2.p, n1, n2, n2);
+  if (D > MAXD)
+    hipLaunchKernelGGL(k_rbf_matrix_wide, dim3(ceil_div(n1 * n2, 256)), dim3(256), 0, c->stream, d1, n1, d2, n2, make_hyp_wide(ell, var, D), 0.0,
+                       c->scratch2.p, n1, n2, n2);
+  else {
+    KernHyp h = make_hyp(ell, var, D);
+    hipLaunchKernelGGL(k_rbf_matrix, dim3(ceil_div(n1 * n2, 256)), dim3(256), 0, c->stream, d1, n1, d2, n2, h, 0.0, c->scratch2.p, n1, n2, n2);
+  }
   ZIGP_HIP(c, hipGetLastError());
   ZIGP_HIP(c, hipMemcpyAsync(K, c->scratch2.p, sizeof(double) * n1 * n2, hipMemcpyDeviceToHost, c->stream));
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));
@@ -1486,14 +1555,17 @@ int zigp_clock_stamp(zigp_ctx* c, int64_t* out) {
 // ---- diagnostics -------------------------------------------------------------------------------
 int zigp_test_kuf(zigp_ctx* c, int64_t N, int32_t M, int32_t D, const double* X, const double* Z, const double* ell, double var, double* K) {
   if (!c) return ZIGP_EARG;
-  if (N <= 0 || M <= 0 || D < 1 || D > MAXD || !X || !Z || !ell || !K) return fail_arg(c, "zigp_test_kuf: bad arguments");
+  if (N <= 0 || M <= 0 || D < 1 || D > ZIGP_MAX_D || !X || !Z || !ell || !K) return fail_arg(c, "zigp_test_kuf: bad arguments");
   ZIGP_HIP(c, hipSetDevice(c->device));
   const int64_t Nc = round_up(N, 1024);
   const int Mp = (int)round_up(M, 16);
-  const KufHyp kh = make_kuf_hyp(ell, var, D);
+  const KufHypWide khw = make_kuf_hyp_wide(ell, var, D);
+  KufHyp kh;
+  for (int d = 0; d < MAXD; ++d) kh.scale[d] = khw.scale[d];
+  kh.var = var;
   std::vector<double> zs((size_t)Mp * D, 0.0), hk((size_t)Mp * Nc);
   for (int m = 0; m < M; ++m)
-    for (int d = 0; d < D; ++d) zs[(size_t)m * D + d] = Z[(size_t)m * D + d] * kh.scale[d];
+    for (int d = 0; d < D; ++d) zs[(size_t)m * D + d] = Z[(size_t)m * D + d] * khw.scale[d];
   DevBuf dx, dz, dk;
   ZIGP_ENSURE(c, dx, (size_t)N * D); ZIGP_ENSURE(c, dz, zs.size()); ZIGP_ENSURE(c, dk, hk.size());
   ZIGP_HIP(c, hipMemcpyAsync(dx.p, X, sizeof(double) * N * D, hipMemcpyHostToDevice, c->stream));
@@ -1501,12 +1573,29 @@ int zigp_test_kuf(zigp_ctx* c, int64_t N, int32_t M, int32_t D, const double* X,
   const dim3 grid((unsigned)(Nc / 512), Mp / 16), block(256);
 #define ZIGP_KUF(DD) \
   case DD: hipLaunchKernelGGL((k_kuf_build<DD, KufHyp>), grid, block, 0, c->stream, dx.p, N, (int64_t)0, dz.p, M, kh, dk.p, Nc); break;
-  switch (D) { ZIGP_KUF(1) ZIGP_KUF(2) ZIGP_KUF(3) ZIGP_KUF(4) ZIGP_KUF(5) ZIGP_KUF(6) ZIGP_KUF(7) ZIGP_KUF(8) }
+  switch (D) {
+    ZIGP_KUF(1) ZIGP_KUF(2) ZIGP_KUF(3) ZIGP_KUF(4) ZIGP_KUF(5) ZIGP_KUF(6) ZIGP_KUF(7) ZIGP_KUF(8)
+    default: hipLaunchKernelGGL(k_kuf_build_wide, grid, block, 0, c->stream, dx.p, N, (int64_t)0, dz.p, M, D, khw, dk.p, Nc); break;
+  }
 #undef ZIGP_KUF
   ZIGP_HIP(c, hipGetLastError());
   ZIGP_HIP(c, hipMemcpyAsync(hk.data(), dk.p, sizeof(double) * hk.size(), hipMemcpyDeviceToHost, c->stream));
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));
   for (int m = 0; m < M; ++m) memcpy(K + (size_t)m * N, &hk[(size_t)m * Nc], sizeof(double) * N);
+  return ZIGP_OK;
+}
+
+int zigp_test_kgmom_list(int32_t M, int64_t Nc, int64_t cap, int64_t* out) {
+  // host only: the list run_dense plans for the moments product of the wide Kuf gradient -- out[0] = slices, out[1] = entries per
+  // workgroup, out[2] = entries, then (bi, bj, kbeg, kend, slice) per entry, as many as fit `cap` int64
+  if (M <= 0 || Nc <= 0 || Nc % 1024 != 0 || !out || cap < 3) return ZIGP_EARG;
+  const int nbm = (int)(round_up(M, BM) / BM);
+  std::vector<GemmTile> v;
+  out[0] = kgmom_slices(nbm, Nc); out[1] = kgmom_tiles(nbm, Nc).build(v); out[2] = (int64_t)v.size();
+  for (size_t i = 0; i < v.size() && 3 + 5 * (int64_t)(i + 1) <= cap; ++i) {
+    int64_t* o = out + 3 + 5 * i;
+    o[0] = v[i].bi; o[1] = v[i].bj; o[2] = v[i].kbeg; o[3] = v[i].kend; o[4] = v[i].slice;
+  }
   return ZIGP_OK;
 }
 
@@ -1816,8 +1905,8 @@ int stage_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s, bool whiten) {
   if (s->np_f < 1 || s->np_g < 1 || s->np1_f < 0 || s->np2_f < 0 || s->np1_g < 0 || s->np2_g < 0 || s->np1_f > s->np_f || s->np2_f > s->np_f ||
       s->np1_g > s->np_g || s->np2_g > s->np_g)
     return fail_arg(c, "zigp_test_pointwise: need 0 <= np1, np2 <= np");
-  if (s->D < 1 || s->D > MAXD || !s->X || s->Nrows <= 0 || s->n0 < 0 || s->row_end < s->n0 || s->row_end > s->Nrows || s->row_end > s->n0 + s->Nc)
-    return fail_arg(c, "zigp_test_pointwise: need X (Nrows,D), 1 <= D <= 8 and n0 <= row_end <= min(Nrows, n0 + Nc)");
+  if (s->D < 1 || s->D > ZIGP_MAX_D || (s->D > MAXD && s->mean_on) || !s->X || s->Nrows <= 0 || s->n0 < 0 || s->row_end < s->n0 || s->row_end > s->Nrows || s->row_end > s->n0 + s->Nc)
+    return fail_arg(c, "zigp_test_pointwise: need X (Nrows,D), 1 <= D <= " ZIGP_MAX_D_STR " (a mean function: D <= 8) and n0 <= row_end <= min(Nrows, n0 + Nc)");
   if (s->mode == 1 && (!s->gm_f || !s->gv_f || !s->gm_g || !s->gv_g)) return fail_arg(c, "zigp_test_pointwise: gradient mode needs gm / gv outputs");
   if (s->mode == 2 ? !s->out9 : !s->Y) return fail_arg(c, "zigp_test_pointwise: predict needs out9, the ELBO modes need Y");
   ZIGP_HIP(c, hipSetDevice(c->device));
@@ -1866,7 +1955,7 @@ int zigp_test_kgrad(zigp_ctx* c, int32_t M, int32_t D, int64_t Nc, int64_t Nrows
                     const double* gm, const double* gv, const double* X, const double* Z, const double* ell, const double* centre, int32_t exact,
                     double* krow) {
   if (!c) return ZIGP_EARG;
-  if (M <= 0 || D < 1 || D > MAXD || !stage_chunk_ok(Nc) || Nrows <= 0 || n0 < 0 || n0 >= Nrows || !Jp || !K || !alpha || !gm || !gv || !X || !Z || !krow ||
+  if (M <= 0 || D < 1 || D > ZIGP_MAX_D || !stage_chunk_ok(Nc) || Nrows <= 0 || n0 < 0 || n0 >= Nrows || !Jp || !K || !alpha || !gm || !gv || !X || !Z || !krow ||
       exact < -1 || exact > 1 || (exact < 0 && !ell))
     return fail_arg(c, "zigp_test_kgrad: bad arguments");
   ZIGP_HIP(c, hipSetDevice(c->device));
@@ -1874,16 +1963,19 @@ int zigp_test_kgrad(zigp_ctx* c, int32_t M, int32_t D, int64_t Nc, int64_t Nrows
   lt.M = M; lt.Mp = (int)round_up(M, BM);
   const int Mp = lt.Mp, Wd = 2 + 2 * D;
   if (exact < 0 || !centre) {
-    const double one[MAXD] = {1, 1, 1, 1, 1, 1, 1, 1};
+    double one[WIDE_MAXD];
+    for (double& v : one) v = 1.0;
     kgrad_centre(lt, Z, ell ? ell : one, M, D);
   }
   if (exact >= 0) lt.kg_exact = exact != 0;
-  if (centre) for (int d = 0; d < MAXD; ++d) lt.zc[d] = d < D ? centre[d] : 0.0;
+  if (centre) for (int d = 0; d < WIDE_MAXD; ++d) lt.zc[d] = d < D ? centre[d] : 0.0;
   DevBuf dx;
   ZIGP_TRY(stage_upload_rows(c, dx, X, Nrows, Nrows, D));
   ZIGP_TRY(stage_upload_rows(c, lt.Z, Z, M, Mp, D));
   ZIGP_TRY(stage_upload_rows(c, lt.K, K, M, Mp, Nc));
   ZIGP_TRY(stage_upload_rows(c, lt.Jp, Jp, M, Mp, Nc));
+  if (D > MAXD && Mp > M)      // the wide forms must not read the padded rows of J': they hold the stage sentinel here
+    ZIGP_HIP(c, hipMemsetAsync(lt.Jp.p + (size_t)M * Nc, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * (size_t)(Mp - M) * Nc, c->stream));
   ZIGP_TRY(stage_upload_rows(c, lt.gm, gm, 1, 1, Nc));
   ZIGP_TRY(stage_upload_rows(c, lt.gv, gv, 1, 1, Nc));
   ZIGP_ENSURE(c, lt.vec, 4 * (size_t)Mp + 8);
@@ -1893,7 +1985,12 @@ int zigp_test_kgrad(zigp_ctx* c, int32_t M, int32_t D, int64_t Nc, int64_t Nrows
   ZIGP_HIP(c, hipMemsetAsync(lt.krow.p, 0, sizeof(double) * KG_SPLIT * Mp * Wd, c->stream));
   for (int sp = 0; sp < KG_SPLIT; ++sp)
     ZIGP_HIP(c, hipMemcpyAsync(lt.krow.p + (size_t)sp * Mp * Wd, krow + (size_t)sp * M * Wd, sizeof(double) * M * Wd, hipMemcpyHostToDevice, c->stream));
-  ZIGP_TRY(latent_chunk_kgrad(c, lt, dx.p, Nrows, n0, Nc, D, ell));
+  TileList mom;
+  if (D > MAXD && !lt.kg_exact) {
+    ZIGP_TRY(ensure_kgrad_wide(c, lt, Nc));
+    ZIGP_TRY(get_tiles(c, kgmom_tiles(Mp / BM, Nc), mom));
+  }
+  ZIGP_TRY(latent_chunk_kgrad(c, lt, dx.p, Nrows, n0, Nc, D, ell, mom));
   for (int sp = 0; sp < KG_SPLIT; ++sp)
     ZIGP_HIP(c, hipMemcpyAsync(krow + (size_t)sp * M * Wd, lt.krow.p + (size_t)sp * Mp * Wd, sizeof(double) * M * Wd, hipMemcpyDeviceToHost, c->stream));
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));

@@ -564,6 +564,39 @@ static inline KufHyp make_kuf_hyp(const double* ell, double var, int D) {
   return h;
 }
 
+// Moments product of the wide Kuf gradient (k_kgrad_wide_prep, zigp_kernels.h): Mom[Mp][128] = T[Mp][Nc] . XM[Nc][128], one column tile,
+// split-K over the chunk's columns into S planes.  S follows from (Mp, Nc) alone: slices of at least 16 BK steps (256 columns), about
+// the 512 resident workgroups over the nbm row tiles, at most 64 planes.  One entry per workgroup; slice s of every row tile covers the
+// BK steps [ks s / S, ks (s + 1) / S) of ks = Nc / BK.
+static inline int kgmom_slices(int nbm, int64_t Nc) {
+  const int64_t ks = Nc / BK;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(64, ks / 16), 512 / std::max(nbm, 1)));
+}
+static inline int build_kgmom_list(int nbm, int64_t Nc, std::vector<GemmTile>& v) {
+  const int S = kgmom_slices(nbm, Nc);
+  const int64_t ks = Nc / BK;
+  for (int s = 0; s < S; ++s)
+    for (int bi = 0; bi < nbm; ++bi) v.push_back(mk_tile(bi, 0, (int)(ks * s / S), (int)(ks * (s + 1) / S), s));
+  return 1;
+}
+static inline TileSpec kgmom_tiles(int nbm, int64_t Nc) {
+  return TileSpec{"kgmom:" + std::to_string(nbm) + ":" + std::to_string(Nc), [=](std::vector<GemmTile>& v) { return build_kgmom_list(nbm, Nc, v); }};
+}
+
+// D > MAXD (the wide kernels, zigp_kernels.h): the same doubles, WIDE_MAXD entries
+static inline KernHypWide make_hyp_wide(const double* ell, double var, int D) {
+  KernHypWide h;
+  for (int d = 0; d < WIDE_MAXD; ++d) h.inv_ell[d] = (d < D) ? 1.0 / ell[d] : 0.0;
+  h.var = var; h.D = D;
+  return h;
+}
+static inline KufHypWide make_kuf_hyp_wide(const double* ell, double var, int D) {
+  KufHypWide h;
+  for (int d = 0; d < WIDE_MAXD; ++d) h.scale[d] = (d < D) ? KUF_C * (1.0 / ell[d]) : 0.0;
+  h.var = var;
+  return h;
+}
+
 // ---- small transfers through the pinned arena (zigp_ctx.h) ----
 // Start of an API call that stages transfers: make sure nothing of an earlier call (one that returned an error before its
 // final synchronisation, say) is still reading or writing the arena, then rewind it.

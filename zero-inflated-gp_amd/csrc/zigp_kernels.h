@@ -117,6 +117,37 @@ __global__ void k_kuu_setup(const double* __restrict__ Z, int64_t M, H h, double
   W[idx] = 0.0;
 }
 
+// Input dimensions 9 .. WIDE_MAXD (= ZIGP_MAX_D, include/zigp.h): the "wide" kernels.  Everything up to MAXD keeps the structs, kernels
+// and kernel arguments above and below (compile-time D, MAXD-sized locals); beyond it the dimension is a run-time argument, taken in slices
+// of WIDE_SLICE = MAXD dimensions where a kernel holds per-dimension values in registers, and the hyperparameters come BY VALUE in structs
+// sized for WIDE_MAXD (KernHypWide: 528 bytes, KufHypWide: 520 of the 4 KiB kernel-argument space; read with wave-uniform scalar loads).
+// The host takes this branch for D > MAXD only (zigp_dense.hip).
+constexpr int WIDE_MAXD = 64, WIDE_SLICE = 8;
+static_assert(WIDE_SLICE == MAXD, "a slice of the wide kernels is the register footprint of the D = MAXD kernels");
+struct KernHypWide { double inv_ell[WIDE_MAXD]; double var; int D; };
+__device__ __forceinline__ int hyp_dim(const KernHypWide& h) { return h.D; }
+__device__ __forceinline__ double hyp_inv_ell(const KernHypWide& h, int d) { return h.inv_ell[d]; }
+__device__ __forceinline__ double hyp_var(const KernHypWide& h) { return h.var; }
+// k_rbf_matrix at a run-time dimension up to WIDE_MAXD (same expression, same order of the terms)
+__global__ void k_rbf_matrix_wide(const double* __restrict__ X1, int64_t n1, const double* __restrict__ X2, int64_t n2,
+                                  KernHypWide h, double jitter, double* __restrict__ out, int64_t r_pad, int64_t c_pad, int64_t ld) {
+  int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= r_pad * c_pad) return;
+  int64_t i = idx / c_pad, j = idx - i * c_pad;
+  double v;
+  if (i < n1 && j < n2) {
+    double r2 = 0.0;
+    for (int d = 0; d < h.D; ++d) {
+      double t = (X1[i * h.D + d] - X2[j * h.D + d]) * h.inv_ell[d];
+      r2 = fma(t, t, r2);
+    }
+    v = h.var * exp(-0.5 * r2) + ((i == j) ? jitter : 0.0);
+  } else {
+    v = (i == j) ? 1.0 : 0.0;
+  }
+  out[i * ld + j] = v;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Kuf panel for one chunk: K[m][n] = var*exp(-0.5*|(z_m - x_n)/ell|^2), m < M ; 0 for padded rows.
 // (kern.K(X, Xnew), onofftf/main.py:266.)  grid (Nc/512, Mp/16); thread = two adjacent columns, 16 rows.
@@ -186,6 +217,54 @@ k_kuf_build(const double* __restrict__ X, int64_t N, int64_t n0, const double* _
       w0 = d == 0 ? -t0 * t0 : fma(-t0, t0, w0); w1 = d == 0 ? -t1 * t1 : fma(-t1, t1, w1);
     }
     *out = make_double2(kuf_exp2_32(w0, T), kuf_exp2_32(w1, T));
+  }
+}
+
+// The panel for D > MAXD: the same direct-difference sum  w = -sum_d (zs_d - xs_d)^2  in ascending d, the same epilogue and table, the
+// same thread mapping (two adjacent columns, 16 rows, 16-byte stores) -- with a run-time D taken in slices of WIDE_SLICE dimensions.  The
+// 16 x 2 partial sums stay in registers across the slices; a slice loads xs[2][WIDE_SLICE] (scaled as above) and the rows' Zs entries as
+// wave-uniform scalar loads.  The tail of the last slice is ZERO-FILLED (xs = zs = 0: the term is an exact -0 * 0 added to w) instead of
+// branching per term: the selects sit on the loads, the 2 VALU instructions per element and dimension are unconditional.  No
+// |x|^2 + |z|^2 - 2 x.z form: the argument's error stays proportional to eps * y, with D additions of terms of one sign, so the result
+// keeps the class of k_kuf_build (within 2 ulp of exp at the computed argument).  Rows m >= M are written as zeros.
+struct KufHypWide { double scale[WIDE_MAXD]; double var; };   // scale[d] = KUF_C * (1 / ell_d), d < D
+__global__ void __launch_bounds__(256)
+k_kuf_build_wide(const double* __restrict__ X, int64_t N, int64_t n0, const double* __restrict__ Zs, int M, int D, KufHypWide h,
+                 double* __restrict__ K, int64_t Nc) {
+  __shared__ double T[32];
+  if (threadIdx.x < 32) T[threadIdx.x] = h.var * KUF_T[threadIdx.x];
+  const int64_t n = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;
+  const int m0 = blockIdx.y * 16;
+  const bool valid[2] = {(n0 + n) < N, (n0 + n + 1) < N};
+  double w[16][2];
+#pragma unroll
+  for (int mm = 0; mm < 16; ++mm) { w[mm][0] = 0.0; w[mm][1] = 0.0; }
+  for (int d0 = 0; d0 < D; d0 += WIDE_SLICE) {
+    double xs[2][WIDE_SLICE];
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int dd = 0; dd < WIDE_SLICE; ++dd)
+        xs[e][dd] = (valid[e] && d0 + dd < D) ? X[(n0 + n + e) * D + d0 + dd] * h.scale[d0 + dd] : 0.0;
+#pragma unroll
+    for (int mm = 0; mm < 16; ++mm) {
+      const int m = m0 + mm;
+      if (m >= M) continue;     // uniform over the block
+#pragma unroll
+      for (int dd = 0; dd < WIDE_SLICE; ++dd) {
+        const double zs = (d0 + dd < D) ? Zs[(int64_t)m * D + d0 + dd] : 0.0;      // uniform: a scalar load
+        const double t0 = zs - xs[0][dd], t1 = zs - xs[1][dd];
+        w[mm][0] = fma(-t0, t0, w[mm][0]); w[mm][1] = fma(-t1, t1, w[mm][1]);
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int mm = 0; mm < 16; ++mm) {
+    const int m = m0 + mm;
+    double2* out = reinterpret_cast<double2*>(K + (int64_t)m * Nc + n);
+    if (m >= M) *out = make_double2(0.0, 0.0);
+    else *out = make_double2(kuf_exp2_32(w[mm][0], T), kuf_exp2_32(w[mm][1], T));
   }
 }
 
@@ -339,7 +418,7 @@ __device__ __forceinline__ void pw_block(const PwArgs& p, const HS& hs, int blk,
     const double gmf = sc * o.dfm;
     const double sb = wave_sum(gmf);
     if (lane == 0) a[4] += sb;
-    for (int d = 0; d < p.D; ++d) {
+    for (int d = 0; d < min(p.D, MAXD); ++d) {     // (D > MAXD: Constant only, mean_a = 0 -- the host refuses a Linear mean there)
       const double sa = wave_sum(gmf * xs[d]);
       if (lane == 0) a[5 + d] += sa;
     }
@@ -461,6 +540,173 @@ k_kgrad(const double* __restrict__ Jp, const double* __restrict__ K, const doubl
   }
 }
 
+// D > MAXD, centred form: the 2 D moment sums of a row do not fit its registers, and re-reading the K and J' panels once per window of
+// dimensions multiplies the HBM traffic of an HBM-read-bound kernel by ceil(D / 8) -- so the centred moments are ONE skinny product on the
+// GEMM core,  Mom[Mp][128] = T[Mp][Nc] . XM[Nc][128],  T = F K (the element k_kgrad forms on the fly),  XM = [x - c | (x - c)^2]:
+//   k_kgrad_wide_prep    T over J' in place (J' has no later reader: k_kgrad is its only one in all three parametrisations), the chunk's
+//                        sum_n T per row and column split (ks0) and, into krow, the two dimension-independent columns; the operand XM
+//   run_gemm             split-K over the chunk's columns into planes (kgmom_tiles, zigp_host.h; the instantiation of run_gemm_sk)
+//   k_kgrad_wide_finish  planes added in slice order, moments moved from c to z_m (the !EXACT tail of k_kgrad), added into slab 0 of krow
+// 2 x 128 flops per panel element on the matrix pipe and one read of each panel, against ceil(D / 8) reads for the sliced form below.
+// WIDE_MOM_COLS = 2 WIDE_MAXD = one 128-column tile of the core: columns d and WIDE_MAXD + d; the others are zero.
+constexpr int WIDE_MOM_COLS = 2 * WIDE_MAXD;
+static_assert(WIDE_MOM_COLS == 128, "the moment operand is exactly one column tile of the GEMM core (BN)");
+struct KgCentreWide { double c[WIDE_MAXD]; };
+// grid (Mp / KG_ROWS, KG_SPLIT).  Rows m >= M of T are written as exact zeros and nothing of them is read (a stage hook fills the padded
+// rows of J' with its sentinel); so are the columns at or beyond the last valid row.  XM rows at or beyond the last valid row are zeros.
+__global__ void __launch_bounds__(256)
+k_kgrad_wide_prep(double* __restrict__ Jp, const double* __restrict__ K, const double* __restrict__ alpha, const double* __restrict__ gm,
+                  const double* __restrict__ gv, const double* __restrict__ X, int64_t N, int64_t n0, int M, int Mp, int D, int64_t Nc,
+                  int64_t slab, KgCentreWide ctr, double* __restrict__ krow, double* __restrict__ ks0, double* __restrict__ XM) {
+  __shared__ double sh[4][KG_ROWS * 2];
+  __shared__ double cs[WIDE_MAXD];
+  if (threadIdx.x < WIDE_MAXD) cs[threadIdx.x] = ctr.c[threadIdx.x];
+  const int m0 = blockIdx.x * KG_ROWS;
+  const int64_t nspan = Nc / KG_SPLIT, nbeg = (int64_t)blockIdx.y * nspan, nend = nbeg + nspan;
+  const int64_t nvalid = min(Nc, N - n0);               // valid columns of the chunk
+  double am[KG_ROWS], acc[KG_ROWS][2];
+#pragma unroll
+  for (int r = 0; r < KG_ROWS; ++r) { am[r] = (m0 + r < M) ? alpha[m0 + r] : 0.0; acc[r][0] = 0.0; acc[r][1] = 0.0; }
+  for (int64_t n = nbeg + threadIdx.x; n < nend; n += 256) {
+    const bool live = n < nvalid;
+    const double gmn = live ? gm[n] : 0.0, gv2 = live ? 2.0 * gv[n] : 0.0;
+#pragma unroll
+    for (int r = 0; r < KG_ROWS; ++r) {
+      const int64_t o = (int64_t)(m0 + r) * Nc + n;
+      double t = 0.0;
+      if (live && m0 + r < M) {
+        const double kk = K[o];
+        t = fma(gv2, Jp[o], am[r] * gmn) * kk;
+        acc[r][0] += t;
+        acc[r][1] = fma(kk, gmn, acc[r][1]);
+      }
+      Jp[o] = t;
+    }
+  }
+  // fixed-order block reduction: lanes by xor tree, then waves 0..3
+#pragma unroll
+  for (int r = 0; r < KG_ROWS; ++r)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const double v = wave_sum(acc[r][q]);
+      if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][r * 2 + q] = v;
+    }
+  __syncthreads();
+  if (threadIdx.x < KG_ROWS * 2) {
+    const int r = threadIdx.x >> 1, q = threadIdx.x & 1, W = 2 + 2 * D;
+    const double v = (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
+    if (m0 + r < M) krow[(int64_t)blockIdx.y * slab + (int64_t)(m0 + r) * W + (q ? 1 + 2 * D : 0)] += v;
+    if (q == 0) ks0[(int64_t)blockIdx.y * Mp + m0 + r] = (m0 + r < M) ? v : 0.0;
+  }
+  // the moment operand: 256-row pieces of this split's rows of XM, dealt round the blocks of the split
+  for (int64_t piece = blockIdx.x; piece < nspan / 256; piece += gridDim.x) {
+    const int64_t base = (nbeg + piece * 256) * WIDE_MOM_COLS;
+    for (int j = 0; j < WIDE_MOM_COLS; ++j) {
+      const int64_t e = (int64_t)j * 256 + threadIdx.x;          // consecutive lanes, consecutive addresses
+      const int64_t n = nbeg + piece * 256 + e / WIDE_MOM_COLS;
+      const int col = (int)(e % WIDE_MOM_COLS), d = col % WIDE_MAXD;
+      double v = 0.0;
+      if (d < D && n < nvalid) {
+        const double xc = X[(n0 + n) * D + d] - cs[d];
+        v = col < WIDE_MAXD ? xc : xc * xc;
+      }
+      XM[base + e] = v;
+    }
+  }
+}
+// grid (Mp / 4), 256 threads: thread = (row, dimension); S1 and S2 from the planes in slice order, S0 from the splits in split order
+__global__ void __launch_bounds__(256)
+k_kgrad_wide_finish(const double* __restrict__ planes, int S, const double* __restrict__ ks0, const double* __restrict__ Z, int M, int Mp, int D,
+                    KgCentreWide ctr, double* __restrict__ krow) {
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6), d = threadIdx.x & 63;
+  if (m >= M || d >= D) return;
+  double S0 = 0.0, S1 = 0.0, S2 = 0.0;
+  for (int sp = 0; sp < KG_SPLIT; ++sp) S0 += ks0[(int64_t)sp * Mp + m];
+  const int64_t plane = (int64_t)Mp * WIDE_MOM_COLS;
+  for (int s = 0; s < S; ++s) {
+    S1 += planes[s * plane + (int64_t)m * WIDE_MOM_COLS + d];
+    S2 += planes[s * plane + (int64_t)m * WIDE_MOM_COLS + WIDE_MAXD + d];
+  }
+  const double dz = Z[(int64_t)m * D + d] - ctr.c[d];
+  const int W = 2 + 2 * D;
+  krow[(int64_t)m * W + 1 + d] += fma(-dz, S0, S1);                              // moments about c -> about z_m
+  krow[(int64_t)m * W + 1 + D + d] += fma(dz, fma(dz, S0, -2.0 * S1), S2);
+}
+
+// D > MAXD: the per-row (EXACT) body above over a run-time window of dimensions [d0, min(d0 + WIDE_SLICE, D)), launched ceil(D / WIDE_SLICE)
+// times per latent and chunk.  krow rows have the call's width 2 + 2 D; a launch adds its window's columns 1 + d and 1 + D + d, and the
+// launch with d0 = 0 also the two dimension-independent columns (sum F K and K gm).  The fallback of the centred form above (inducing
+// inputs spread beyond KG_EXACT_SPREAD lengthscales, the rule of kgrad_centre) and its yardstick (zigp_test_kgrad with exact = 1).  The tail of the last window is zero-filled at the
+// loads (x = z = 0: the terms are exact zeros) and its columns are not written.  Each launch re-reads the K and J' panels.
+__global__ void __launch_bounds__(256)
+k_kgrad_slice(const double* __restrict__ Jp, const double* __restrict__ K, const double* __restrict__ alpha,
+              const double* __restrict__ gm, const double* __restrict__ gv, const double* __restrict__ X, int64_t N, int64_t n0,
+              const double* __restrict__ Z, int M, int D, int d0, int64_t Nc, int64_t slab, double* __restrict__ krow) {
+  constexpr int S = WIDE_SLICE, WS = 2 + 2 * S;
+  __shared__ double sh[4][KG_ROWS * WS];
+  __shared__ double tot[KG_ROWS * WS];
+  krow += (int64_t)blockIdx.y * slab;
+  const int m0 = blockIdx.x * KG_ROWS;
+  if (m0 >= M) return;
+  const int nd = min(S, D - d0);
+  const bool first = d0 == 0;
+  double am[KG_ROWS], acc[KG_ROWS][WS], zr[KG_ROWS][S];
+#pragma unroll
+  for (int r = 0; r < KG_ROWS; ++r) {
+    am[r] = alpha[min(m0 + r, M - 1)];
+#pragma unroll
+    for (int dd = 0; dd < S; ++dd) zr[r][dd] = dd < nd ? Z[(int64_t)min(m0 + r, M - 1) * D + d0 + dd] : 0.0;
+#pragma unroll
+    for (int q = 0; q < WS; ++q) acc[r][q] = 0.0;
+  }
+  const int64_t nspan = Nc / KG_SPLIT, nbeg = (int64_t)blockIdx.y * nspan;
+  const int64_t nmax = min(nbeg + nspan, N - n0);
+  for (int64_t n = nbeg + threadIdx.x; n < nmax; n += 256) {
+    const double gmn = gm[n], gv2 = 2.0 * gv[n];
+    double xc[S];
+#pragma unroll
+    for (int dd = 0; dd < S; ++dd) xc[dd] = dd < nd ? X[(n0 + n) * D + d0 + dd] : 0.0;
+#pragma unroll
+    for (int r = 0; r < KG_ROWS; ++r) {
+      const int64_t o = (int64_t)(m0 + r) * Nc + n;     // rows beyond M are zero-padded panels (inside the allocation)
+      const double kk = K[o];
+      const double t = fma(gv2, Jp[o], am[r] * gmn) * kk;
+      if (first) {
+        acc[r][0] += t;
+        acc[r][1 + 2 * S] = fma(kk, gmn, acc[r][1 + 2 * S]);
+      }
+#pragma unroll
+      for (int dd = 0; dd < S; ++dd) {
+        const double df = xc[dd] - zr[r][dd], td = t * df;
+        acc[r][1 + dd] += td;
+        acc[r][1 + S + dd] = fma(td, df, acc[r][1 + S + dd]);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < KG_ROWS; ++r)
+#pragma unroll
+    for (int q = 0; q < WS; ++q) {
+      const double v = wave_sum(acc[r][q]);
+      if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][r * WS + q] = v;
+    }
+  __syncthreads();
+  if (threadIdx.x < KG_ROWS * WS) tot[threadIdx.x] = (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
+  __syncthreads();
+  if (threadIdx.x < KG_ROWS * WS) {
+    const int r = threadIdx.x / WS, q = threadIdx.x - r * WS;
+    const int W = 2 + 2 * D;
+    int col = -1;
+    if (q == 0) col = first ? 0 : -1;
+    else if (q == 1 + 2 * S) col = first ? 1 + 2 * D : -1;
+    else {
+      const int dd = (q - 1) % S;
+      if (dd < nd) col = (q <= S) ? 1 + d0 + dd : 1 + D + d0 + dd;
+    }
+    if (col >= 0 && m0 + r < M) krow[(int64_t)(m0 + r) * W + col] += tot[r * WS + q];
+  }
+}
+
 // Kuu -> (Z, ell, var) cotangent reductions with a symmetric G = dELBO/dKuu, block per row i:
 //   krow[i][0] += sum_j G Kz ; krow[i][1+d] += sum_j 2 G Kz (z_jd - z_id) ; krow[i][1+D+d] += sum_j G Kz (z_id-z_jd)^2
 // where Kz = Kuu - jitter*I.
@@ -496,6 +742,45 @@ k_kuu_grad(const double* __restrict__ G, const double* __restrict__ Kuu, double 
     double a = block_sum<4>(s1[d], sh);
     double b = block_sum<4>(s2[d], sh);
     if (threadIdx.x == 0) { krow[(int64_t)i * W + 1 + d] += a; krow[(int64_t)i * W + 1 + D + d] += b; }
+  }
+}
+
+// D > MAXD: k_kuu_grad over the dimension window [d0, min(d0 + WIDE_SLICE, D)), d0 = blockIdx.y WIDE_SLICE -- grid (Mp, ceil(D / WIDE_SLICE));
+// the window d0 = 0 also adds column 0.  O(M^2 D), off the hot path.
+__global__ void __launch_bounds__(256)
+k_kuu_grad_wide(const double* __restrict__ G, const double* __restrict__ Kuu, double jitter, const double* __restrict__ Z,
+                int M, int D, int64_t ld, double* __restrict__ krow) {
+  __shared__ double sh[4];
+  const int i = blockIdx.x, d0 = blockIdx.y * WIDE_SLICE;
+  if (i >= M) return;
+  const int nd = min(WIDE_SLICE, D - d0);
+  double zz[WIDE_SLICE];
+#pragma unroll
+  for (int d = 0; d < WIDE_SLICE; ++d) zz[d] = (d < nd) ? Z[(int64_t)i * D + d0 + d] : 0.0;
+  double s0 = 0.0, s1[WIDE_SLICE], s2[WIDE_SLICE];
+#pragma unroll
+  for (int d = 0; d < WIDE_SLICE; ++d) { s1[d] = 0.0; s2[d] = 0.0; }
+  for (int j = threadIdx.x; j < M; j += 256) {
+    double kz = Kuu[(int64_t)i * ld + j] - ((i == j) ? jitter : 0.0);
+    const double t = G[(int64_t)i * ld + j] * kz;
+    s0 += t;
+#pragma unroll
+    for (int d = 0; d < WIDE_SLICE; ++d)
+      if (d < nd) {
+        const double df = Z[(int64_t)j * D + d0 + d] - zz[d];
+        const double td = t * df;
+        s1[d] = fma(2.0, td, s1[d]);
+        s2[d] = fma(td, df, s2[d]);
+      }
+  }
+  const int W = 2 + 2 * D;
+  s0 = block_sum<4>(s0, sh);
+  if (threadIdx.x == 0 && d0 == 0) krow[(int64_t)i * W] += s0;
+#pragma unroll
+  for (int d = 0; d < WIDE_SLICE; ++d) {
+    double a = block_sum<4>(s1[d], sh);
+    double b = block_sum<4>(s2[d], sh);
+    if (threadIdx.x == 0 && d < nd) { krow[(int64_t)i * W + 1 + d0 + d] += a; krow[(int64_t)i * W + 1 + D + d0 + d] += b; }
   }
 }
 

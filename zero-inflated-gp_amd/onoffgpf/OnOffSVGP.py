@@ -22,7 +22,8 @@ import zigp
 from zigp.optim import ParamSet, lbfgsb, AdamGroups, DenseDeviceFit, WhiteDeviceFit
 from zigp.transforms import positive, Log1pe, Identity, LowerTriangular
 from .param import Param, DataHolder, Parameterized
-from .mean_functions import MeanFunction, Zero
+from .mean_functions import MeanFunction, Zero, Linear
+from zigp._lib import MAX_D, DEVICE_FIT_MAX_D
 
 JITTER = 1e-6   # gpflow settings.numerics.jitter_level default (OnOffSVGP.py:96-97) [GPflow-recall]
 DEVICE_FIT_CALL = 200   # iterations per zigp_fit_steps / zigp_fit_steps_mode call of optimize(method='adam'): one synchronisation each
@@ -37,6 +38,11 @@ class OnOffSVGP(Parameterized):
         X, Y = np.asarray(X, dtype=np.float64), np.asarray(Y, dtype=np.float64)
         if Y.ndim != 2 or Y.shape[1] != 1:
             raise ValueError('Y must be (N,1): num_latent is 1 (OnOffSVGP.py:45)')
+        if X.ndim != 2 or not 1 <= X.shape[1] <= MAX_D:
+            raise ValueError('X must be (N, D) with 1 <= D <= %d, not %s' % (MAX_D, X.shape))
+        if X.shape[1] > DEVICE_FIT_MAX_D and type(self.mean_function) is Linear:
+            raise ValueError('a Linear mean function covers D <= %d input columns (D = %d); Zero and Constant work at every D'
+                             % (DEVICE_FIT_MAX_D, X.shape[1]))
         self.name = name
         self.kernf, self.kerng, self.likelihood = kernf, kerng, likelihood
         self.whiten, self.q_diag = bool(whiten), bool(q_diag)        # :33-34 (whiten: the branch of :88-91,133,137; q_diag: :59-71,88-89)
@@ -127,8 +133,8 @@ class OnOffSVGP(Parameterized):
 
     def _device_fit_eligible(self, pset):
         """the Adam loop can run on the device (zigp_fit_steps): unwhitened, diagonal q(u), Zero mean function, every transform Identity or
-        Log1pe(1e-6)"""
-        return not self.whiten and self.q_diag and type(self.mean_function) is Zero and all(
+        Log1pe(1e-6), at most DEVICE_FIT_MAX_D input columns"""
+        return self.Xtrain.value.shape[1] <= DEVICE_FIT_MAX_D and not self.whiten and self.q_diag and type(self.mean_function) is Zero and all(
             type(q.transform) is Identity or (isinstance(q.transform, Log1pe) and q.transform._lower == 1e-6) for q in pset.params.values())
 
     def _adam_on_device(self, pset, maxiter):
@@ -190,6 +196,9 @@ class OnOffSVGP(Parameterized):
                     raise ValueError('device_loop=True: a callback wants the host every step (device_loop=False, or no callback)')
                 if type(self.mean_function) is not Zero:
                     raise ValueError('device_loop=True: the device loop fits the Zero mean function only (mean-function parameters stay with the host loop)')
+                if self.Xtrain.value.shape[1] > DEVICE_FIT_MAX_D:
+                    raise ValueError('device_loop=True: the device loop covers D <= %d input columns (D = %d); device_loop=False or None '
+                                     'runs the host loop' % (DEVICE_FIT_MAX_D, self.Xtrain.value.shape[1]))
                 self._adam_on_device(pset, maxiter)      # DenseDeviceFit / WhiteDeviceFit raise ValueError for a transform they do not implement
                 return None
             if device_loop is None and callback is None and self._device_fit_eligible(pset):      # the whole loop on the device; a callback wants the host every step

@@ -23,6 +23,10 @@ PROF_KERNELS = {'gemm_A1': 'gemm_f64_kernel<1,1,2,false,1,8,EpiStoreColsum> (A1 
 dp = C.c_void_p
 
 
+MAX_D = 64           # ZIGP_MAX_D (include/zigp.h): input dimensions of the dense entry points
+DEVICE_FIT_MAX_D = 8   # the device fit loops (zigp_fit_steps, zigp_fit_steps_mode) and a Linear mean function stop here
+
+
 class ZigpError(RuntimeError):
     pass
 
@@ -131,6 +135,7 @@ SIGNATURES = {
                                       C.c_void_p, C.c_int64, dp, dp, C.c_double, C.c_double, C.c_int32, dp, dp]),
     'zigp_kron_fit_steps_applied': (C.c_int64, [C.c_void_p]),
     'zigp_test_trmm_list': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    'zigp_test_kgmom_list': (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     'zigp_kron_predict': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), dp, C.c_int64, C.c_double, C.c_double, C.c_double, dp]),
     'zigp_get_chunk': (C.c_int64, [C.c_void_p, C.c_int32]),
     'zigp_get_chunk_rows': (C.c_int64, [C.c_void_p, C.c_int32, C.c_int64]),

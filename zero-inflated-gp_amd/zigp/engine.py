@@ -34,6 +34,8 @@ class _Packed:
         if Zf.ndim != 2 or Zg.ndim != 2 or Zf.shape[1] != Zg.shape[1]:
             raise ValueError('Zf and Zg must be (M,D) with equal D')
         D = Zf.shape[1]
+        if not 1 <= D <= _lib.MAX_D:
+            raise ValueError('D = %d: the dense path takes input dimensions 1 .. %d (ZIGP_MAX_D)' % (D, _lib.MAX_D))
         self.D, self.Mf, self.Mg = D, Zf.shape[0], Zg.shape[0]
 
         def ell(v):
