@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import relerr
+from kron_nd import _factored_with_oracle_inverse
 
 pytestmark = pytest.mark.gpu
 
@@ -70,23 +71,6 @@ def _mp_kron_inf(X, Zl, ell, var, u, s, jitter, npts):
         mu.append(float(m))
         vv.append(float(knn - q0 * q1 + st))
     return np.array(mu), np.array(vv)
-
-
-def _factored_with_oracle_inverse(X, p, tag, jit):
-    """The FACTORED identities the engine evaluates, on the CPU with the oracle's own np.linalg.inv (LAPACK LU, as
-    tf.matrix_inverse scripts/onoff.py:192): its distance from the literal dense order is the floor that the op order alone
-    sets (tests/test_cpu_oracle.py::test_factored_kronecker_algebra_differs_...; tools/lu_vs_chol_experiment.py)."""
-    import zigp_oracle as o
-    Z, ell, var = p['Z' + tag], p['ell_' + tag], [float(np.squeeze(v)) for v in p['var_' + tag]]
-    P = [np.linalg.inv(o.rbf_K(Z[q], None, ell[q], var[q]) + jit * np.eye(Z[q].shape[0])) for q in range(2)]
-    d0 = Z[0].shape[1]
-    k0, k1 = o.rbf_K(Z[0], X[:, :d0], ell[0], var[0]), o.rbf_K(Z[1], X[:, d0:], ell[1], var[1])
-    M0, M1 = Z[0].shape[0], Z[1].shape[0]
-    U, S2 = p['u_%sm' % tag].reshape(M0, M1), np.square(p['u_%ss_sqrt' % tag]).reshape(M0, M1)
-    a0, a1 = P[0] @ k0, P[1] @ k1
-    mu = np.einsum('in,ij,jn->n', k0, P[0] @ U @ P[1], k1)
-    vv = var[0] * var[1] - (k0 * a0).sum(0) * (k1 * a1).sum(0) + np.einsum('in,ij,jn->n', a0 ** 2, S2, a1 ** 2)
-    return mu, vv
 
 
 @pytest.mark.parametrize('N,M0,M1,M0g,M1g,HARD', [c + (False,) for c in CASES] + [(700, 32, 32, None, None, True)])

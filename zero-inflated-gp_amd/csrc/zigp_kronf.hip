@@ -1096,6 +1096,7 @@ struct KfState {
 //   small  <2, 2>  accumulators in registers (grids up to 32 x 32: BASELINE cfg5)
 //   large  <1, 7>  operands spilled per tile, k_kfl_accum (the reference's [10, 100] grid, scripts/onoff.py:52-53)
 // anything else (and more than 7 input columns per factor: 1 + 2 D moment columns <= 16) takes the GEMM-panel path of zigp_kron.hip.
+// tests/test_gpu_kron_nd.py walks this table (every factor dimension 1 to 8, each instantiation, latents with different block counts).
 struct KfPlan { bool ok, large; int nb0c, nb1c; };
 static KfPlan kf_plan(const zigp_kron_params* p, int nlat) {
   KfPlan pl = {false, false, 0, 0};
