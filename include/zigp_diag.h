@@ -92,8 +92,26 @@ typedef struct zigp_stage_latent {
  * f, g, then the counts the point-wise stage is told: np1_f, np2_f, np1_g, np2_g, 0}. */
 int zigp_test_chunk_forward(zigp_ctx* ctx, int64_t Nc, int32_t need_grad, int32_t only, const zigp_stage_latent* lat /*[2]*/, int64_t* facts /*[12]*/);
 
-/* What the M x M forward of a call leaves for the chunk loop, downloaded: out_f / out_g [4] = {W (M,M), v = W u (M), alpha = W^T v (M),
- * Rt = (Q W^T)^T (M,M; need_grad only)}, any of them NULL.  Runs the upload and the two factorisation chains as zigp_prior_kl does. */
+/* What the M x M forward of a call leaves, downloaded: out_f / out_g [ZIGP_FWD_OUTS], indexed by ZIGP_FWD_*, any of them NULL.  Runs the
+ * upload and the two factorisation chains of the context's parametrisation as zigp_elbo does: unwhitened, or whitened with a diagonal q_sqrt
+ * (zigp_set_whiten); a full-covariance context is refused (zigp_test_q_full_forward has that stage).  An output the mode, or need_grad = 0,
+ * does not produce is left untouched. */
+enum {
+  ZIGP_FWD_W = 0,      /* (M,M) W = L^-1 */
+  ZIGP_FWD_V = 1,      /* (M)   v = W u                              unwhitened */
+  ZIGP_FWD_ALPHA = 2,  /* (M)   alpha = W^T v;  whitened: W^T u (need_grad) */
+  ZIGP_FWD_RT = 3,     /* (M,M) Rt = W Qt = (Q W^T)^T                unwhitened, need_grad */
+  ZIGP_FWD_DKINV = 4,  /* (M)   diag(Kuu^-1) = column sums of W^2    unwhitened */
+  ZIGP_FWD_KL = 5,     /* (1)   the latent's KL */
+  ZIGP_FWD_P = 6,      /* (M,M) P = W^T W                            unwhitened, need_grad */
+  ZIGP_FWD_QT = 7,     /* (M,M) Qt = diag(s^2) P - I                 unwhitened, need_grad */
+  ZIGP_FWD_WP = 8,     /* (M,M) W diag(s^2);  whitened: D W = diag(s^2 - 1) W      need_grad */
+  ZIGP_FWD_WT = 9,     /* (M,M) W^T */
+  ZIGP_FWD_WH = 10,    /* (3,M) whitened: the block k_kl_white leaves: s^2 - 1, u, 1 */
+  ZIGP_FWD_L = 11,     /* (M,M) L = chol(Kuu) */
+  ZIGP_FWD_KUU = 12,   /* (M,M) Kuu + jitter I as k_kuu_setup writes it */
+  ZIGP_FWD_OUTS = 13
+};
 int zigp_test_latents_forward(zigp_ctx* ctx, const zigp_params* p, double jitter, int32_t need_grad, double* const* out_f, double* const* out_g);
 
 typedef struct zigp_stage_pointwise {
@@ -146,6 +164,81 @@ int zigp_test_pointwise_white(zigp_ctx* ctx, const zigp_stage_pointwise* a);
 int zigp_test_q_full_forward(zigp_ctx* ctx, int32_t M, const double* W, const double* Lq, const double* u, double* TmI, double* Rt, double* kl);
 /* Backward: dLq (M,M) = tril(2 C1 Lq) - [include_kl] (tril(Lq) - diag(1 / Lq_ii)) for a symmetric C1 (M,M); strict upper triangle 0. */
 int zigp_test_q_full_dlq(zigp_ctx* ctx, int32_t M, const double* C1, const double* Lq, int32_t include_kl, double* dLq);
+
+/* ---- the M x M reverse stage of ONE latent on caller-supplied operands, through latent_mxm_backward / latent_mxm_backward_white themselves
+ * (the chain of split-K products, their finishers and the element-wise / reduction kernels between them, then k_kuu_grad[_wide]).  The
+ * call's accumulators are sized and zeroed by the step's own path (dense_prepare_buffers) before the operands go in: C1 as the rank-update
+ * planes (tril(C1) in plane 0, zeros in the others, so that k_sym_from_planes runs as in a step), krow as given.  The derived images come
+ * from the forward stage's kernels: W diag(s^2) (k_colscale), D W (k_kl_white + k_rowscale), or the staged factor, T - I and R^T
+ * (latent_qfull_stage / _factors).  The M x M scratch buffers hold the stage sentinel before the first launch. ---- */
+/* Taps: one (M,M) copy taken right after the launch that produces the value and before its buffer is reused. */
+enum {
+  ZIGP_MXM_TAP_C1 = 0,   /* C1 after the plane sum (k_sym_from_planes) */
+  ZIGP_MXM_TAP_Y = 1,    /* unwhitened: Y = C1 W ("y");  full covariance: Y = C1 Lq ("y", latent_qfull_dlq) */
+  ZIGP_MXM_TAP_T = 2,    /* T = (W diag(s^2)) W^T ("tt") */
+  ZIGP_MXM_TAP_U = 3,    /* U = T C1 ("full") */
+  ZIGP_MXM_TAP_V = 4,    /* V = U + U^T - C1 (k_uut_minus) */
+  ZIGP_MXM_TAP_R = 5,    /* R: W^T V, (W^T D) C1 ("r", lower_up) or (W^T (T - I)) C1 ("rfull", lower_all); lower tiles */
+  ZIGP_MXM_TAP_DL = 6,   /* dL (k_dl_assemble) */
+  ZIGP_MXM_TAP_Q = 7,    /* Q = Phi(L^T dL) ("r" + SK_PHI) */
+  ZIGP_MXM_TAP_QW = 8,   /* Q W ("t"); lower tiles */
+  ZIGP_MXM_TAP_S = 9,    /* S = W^T (Q W) ("s") */
+  ZIGP_MXM_TAP_P = 10,   /* P = W^T W, when the stage forms it (P == NULL, with_kl) */
+  ZIGP_MXM_TAP_PSP = 11, /* P diag(s^2) P ("full"), with_kl, unwhitened */
+  ZIGP_MXM_TAPS = 12
+};
+typedef struct zigp_stage_mxm {
+  int32_t M, D;
+  int32_t mode;        /* 0 unwhitened, 1 whitened with a diagonal q_sqrt, 2 whitened with a full-covariance q_sqrt */
+  int32_t with_data, with_kl;   /* as the step passes them: has rows / include_kl */
+  int32_t reserved;
+  double jitter;
+  double pad;          /* what the padding (index >= M) of Z, Kuu, s and plane 0 of C1 holds on the device; a step leaves 0 there */
+  const double* W;     /* (M,M) lower triangular; padded to Mp with the identity */
+  const double* L;     /* (M,M) lower triangular; padded to Mp with the identity */
+  const double* Kuu;   /* (M,M) */
+  const double* Z;     /* (M,D) */
+  const double* s;     /* modes 0, 1: (M), non-zero;  mode 2: Lq (M,M), non-zero diagonal (the strict upper triangle is ignored) */
+  const double* u;     /* (M) or NULL (zeros): modes 1, 2, for the whitened vectors (the stage itself does not read it) */
+  const double* v;     /* (M) mode 0: W u */
+  const double* alpha; /* (M): W^T v (mode 0), W^T u (modes 1, 2) */
+  const double* P;     /* (M,M) mode 0: W^T W as the forward stage leaves it, or NULL: P_ready is false and the stage forms it */
+  const double* C1;    /* (M,M) symmetric (with_data) */
+  double* krow;        /* in / out [4][Mp][2+2D]: the WHOLE device buffer, padded rows included.  In: initial values; sum_slabs of column
+                          1 + 2D is K gm.  Out: what the stage left (it adds to slab 0, rows < M) */
+  double* a1gm;        /* out (M): W (K gm) */
+  double* du;          /* out (M): W^T a1gm (mode 0; stays zero otherwise) */
+  double* dsq;         /* out (M): diag(W^T C1 W) (mode 0), diag(C1) (mode 1); as zeroed in mode 2 */
+  double* dLq;         /* out (M,M), mode 2 */
+  double* G;           /* out (M,M): what k_kuu_grad reads */
+  double* tap[ZIGP_MXM_TAPS];   /* out (M,M) each or NULL; a tap its mode does not pass is left untouched */
+} zigp_stage_mxm;
+/* Any out pointer may be NULL.  Returns ZIGP_EARG (context still usable) for M <= 0, D outside 1 .. ZIGP_MAX_D, a mode outside 0 .. 2, a
+ * missing operand of the mode, or a zero on the diagonal of s / Lq. */
+int zigp_test_mxm_backward(zigp_ctx* ctx, const zigp_stage_mxm* a);
+
+/* ---- the call's result vector from caller-supplied accumulators, through dense_pack (k_dense_pack, and k_pack_square for mode 2) ---- */
+typedef struct zigp_stage_pack_latent {
+  int32_t M, reserved;
+  const double* krow;     /* [4][M][2+2D]: all KG_SPLIT slabs */
+  const double* du;       /* (M) mode 0: du;  modes 1, 2: W (K gm), what a whitened call packs as du's data part */
+  const double* dsq;      /* (M) modes 0, 1 */
+  const double* s;        /* (M) modes 0, 1, non-zero */
+  const double* dLq;      /* (M,M) mode 2 */
+  const double* kl_vec1;  /* (M) dKL/du: alpha (mode 0), u (modes 1, 2) */
+  const double* kl_vec2;  /* (M) c of dKL/ds = -1/s + c s: diag(Kuu^-1) (mode 0), ones (mode 1); mode 2: not used, may be NULL */
+  const double* ell;      /* (D) */
+  double var, kl;         /* kernel variance; the latent's KL value */
+} zigp_stage_pack_latent;
+typedef struct zigp_stage_pack {
+  int32_t D, mode;        /* mode as zigp_stage_mxm */
+  int32_t need_grad, include_kl, mean_on, pw_blocks;
+  const double* pw;       /* [pw_blocks][13]: the point-wise stage's per-block accumulators */
+  zigp_stage_pack_latent lat[2];
+  double* out;            /* [n_out] the packed vector: 16 header doubles, then per latent dZ (M,D), du (M), ds (M; mode 2: dLq (M,M)), dell (D) */
+  int64_t n_out;          /* must be what the flags imply (16 without need_grad) */
+} zigp_stage_pack;
+int zigp_test_dense_pack(zigp_ctx* ctx, const zigp_stage_pack* a);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
-"""Host references of the dense chunk loop's stages, one plain numpy statement per stage, each with the rounding bound its GPU twin is
-held to (tests/test_gpu_stages.py).  Written from the formulas in the kernel comments (csrc/zigp_dense.hip header, csrc/zigp_gemm.h epilogues,
+"""Host references of the dense chunk loop's stages and of the M x M stage that opens and closes a step, one plain numpy statement per
+stage or launch, each with the rounding bound its GPU twin is held to (tests/test_gpu_stages.py, tests/test_gpu_mxm_stages.py).  Written from the formulas in the kernel comments (csrc/zigp_dense.hip header, csrc/zigp_gemm.h epilogues,
 csrc/zigp_kernels.h k_pointwise / k_kgrad / k_sym_from_planes) and the oracle (oracle/zigp_oracle.py); tests/test_cpu_stage_ref.py pins their
 composition to the oracle on the CPU, so a GPU-vs-stage_ref failure means the kernel is wrong and not the test's idea of the operation.
 
@@ -289,3 +289,319 @@ def worst(err, bound):
     r = np.where(np.isnan(r), np.inf, r)
     k = int(np.argmax(r))
     return float(r.reshape(-1)[k]), k
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# M x M reverse stage (latent_mxm_backward, latent_mxm_backward_white): a chain of split-K products (run_gemm_sk), each with a k range
+# per 128 x 128 output tile, the finishers SK_STORE (plain or lower tiles only) and SK_PHI, and element-wise / reduction kernels between
+# them; then k_kuu_grad[_wide] into slab 0 of krow and k_dense_pack.
+# ---------------------------------------------------------------------------------------------------------------------------------
+BM, BK, KB = 128, 16, 8          # tile edge, k step, k steps per tile edge
+KG_SPLIT = 4
+
+# The k range of tile (bi, bj) of each product in BK steps, nb row blocks (None: the tile is not computed), restated from the comments at
+# the launches (NOT read from the library).  Each range skips only blocks in which one factor is structurally zero.
+SK_RANGES = {
+    'y':     lambda bi, bj, nb: (bj * KB, nb * KB),                              # A W, W lower triangular: k >= j
+    'tt':    lambda bi, bj, nb: (0, (min(bi, bj) + 1) * KB),                     # A B^T, both lower triangular: k <= min(i, j)
+    'full':  lambda bi, bj, nb: (0, nb * KB),
+    'r':     lambda bi, bj, nb: (bi * KB, nb * KB) if bj <= bi else None,        # lower_up: A^T B, A lower triangular (k >= i), lower tiles
+    'rfull': lambda bi, bj, nb: (0, nb * KB) if bj <= bi else None,              # lower_all: dense A^T, lower tiles
+    't':     lambda bi, bj, nb: (bj * KB, (bi + 1) * KB) if bj <= bi else None,  # Q W: Q lower (k <= i), W lower (k >= j), lower tiles
+    's':     lambda bi, bj, nb: (max(bi, bj) * KB, nb * KB),                     # W^T B, B zero above the diagonal tiles: k >= max(i, j)
+    'rt':    lambda bi, bj, nb: (0, (bi + 1) * KB),                              # W B, W lower triangular: k <= i
+}
+
+
+def sk_slices(name, nb):
+    """run_gemm_sk's slice rule: S = max(1, min(8, shortest k range in BK steps, 512 // computed tiles)) slices per tile."""
+    rng = [SK_RANGES[name](bi, bj, nb) for bi in range(nb) for bj in range(nb)]
+    rng = [r for r in rng if r is not None and r[1] > r[0]]
+    return max(1, min(8, min(k1 - k0 for k0, k1 in rng), 512 // len(rng)))
+
+
+def sk_windows(name, nb, bi, bj):
+    """The k windows (in BK steps) of tile (bi, bj)'s slices, in plane order: k0 + len s // S .. k0 + len (s + 1) // S."""
+    r = SK_RANGES[name](bi, bj, nb)
+    if r is None:
+        return []
+    S, (k0, k1) = sk_slices(name, nb), r
+    return [(k0 + (k1 - k0) * s // S, k0 + (k1 - k0) * (s + 1) // S) for s in range(S)]
+
+
+def sk_terms(name, M):
+    """(M, M) array: the number of terms of the k range of the tile an element lies in (0: the tile is not computed)."""
+    nb = round_up(M, BM) // BM
+    t = np.zeros((nb, nb))
+    for bi in range(nb):
+        for bj in range(nb):
+            r = SK_RANGES[name](bi, bj, nb)
+            t[bi, bj] = 0 if r is None else BK * (r[1] - r[0])
+    return np.kron(t, np.ones((BM, BM)))[:M, :M]
+
+
+def lower_tiles(M):
+    """True where the 128 x 128 tile of an element is on or below the diagonal of tiles."""
+    b = np.arange(M) // BM
+    return b[:, None] >= b[None, :]
+
+
+def phi(X):
+    """Phi of the Cholesky reverse: the strict lower triangle plus half the diagonal."""
+    return np.tril(X, -1) + 0.5 * np.diag(np.diag(X))
+
+
+def sk_product(name, A, B, lower_only=False, post=None):
+    """One split-K product C = A B (A, B: the (M, M) factors AS MULTIPLIED, any transposition applied by the caller) of the reverse stage:
+    the whole sum -- a range that is right leaves out structural zeros only, so a range that is short shows as an error -- in the tiles
+    the launch computes, zero in the others (lower_only: SK_STORE / SK_PHI define them as zero); post = phi for SK_PHI.
+    Bound 2 gamma_(k+2) (|A||B|), k = the terms of the tile's own k range."""
+    M = A.shape[0]
+    C, Bd = A @ B, 2 * gamma(sk_terms(name, M) + 2) * (np.abs(A) @ np.abs(B))
+    if lower_only:
+        C, Bd = np.where(lower_tiles(M), C, 0.0), np.where(lower_tiles(M), Bd, 0.0)
+    if post is not None:
+        C, Bd = post(C), np.tril(Bd)
+    return C, Bd
+
+
+def kuu_grad(G, Kuu, jitter, Z):
+    """k_kuu_grad / k_kuu_grad_wide: with Kz = Kuu - jitter I and t_ij = G_ij Kz_ij, the row sums [sum_j t, sum_j 2 t (z_jd - z_id),
+    sum_j t (z_id - z_jd)^2, 0] (M, 2 + 2D).  Sums of M terms, each with at most 5 roundings: gamma_(M+5) sum_j |t| |dz|^p."""
+    M, D = Z.shape
+    Kz = Kuu - jitter * np.eye(M)
+    t, T = G * Kz, np.abs(G * Kz)
+    out, bnd = np.zeros((M, 2 + 2 * D)), np.zeros((M, 2 + 2 * D))
+    out[:, 0], bnd[:, 0] = t.sum(1), T.sum(1)
+    for d in range(D):
+        df = Z[None, :, d] - Z[:, None, d]
+        out[:, 1 + d], out[:, 1 + D + d] = (2 * t * df).sum(1), (t * df * df).sum(1)
+        bnd[:, 1 + d], bnd[:, 1 + D + d] = (2 * T * np.abs(df)).sum(1), (T * df * df).sum(1)
+    return out, 2 * gamma(M + 5) * bnd
+
+
+MXM_MODES = ('diag', 'white', 'white_full')
+# which k-range rule (SK_RANGES) the launch behind a tap runs, per parametrisation
+MXM_PRODUCTS = {'diag': dict(Y='y', T='tt', U='full', R='r', Q='r', QW='t', S='s', P='s', PSP='full'),
+                'white': dict(R='r', Q='r', QW='t', S='s'),
+                'white_full': dict(Y='y', R='rfull', Q='r', QW='t', S='s')}
+
+
+def mxm_backward(op, mode='diag', with_data=True, with_kl=True, given=None):
+    """The reverse stage of one latent, one numpy statement per launch, in launch order.  op: W, L (lower triangular), Kuu, Z, s ((M), or Lq
+    (M, M) for 'white_full'), alpha, v ('diag'), C1 (symmetric), krow [4][>= M][2 + 2D] (initial values; the slabs' column 1 + 2D sums
+    to K gm), jitter, P (optional, 'diag': W^T W from the forward stage; absent: the stage forms it).
+    given = None: the chain -- every launch reads what the statements before it produced.  given = {name: array} (the GPU's taps and
+    outputs): every launch reads the operands ITS kernel read, so each bound is that of one launch.
+    Returns {name: (value, bound)} in launch order.  The chain, written out:
+      diag:        a1gm = W (K gm), du = W^T a1gm, dsq = diag(W^T C1 W), T = W diag(s^2) W^T, V = T C1 + C1 T - C1,
+                   dL = -tril(alpha a1gm^T + du v^T + 2 W^T V), S = W^T Phi(L^T dL) W, G = sym(S) - [kl] 1/2 (P - alpha alpha^T - P diag(s^2) P)
+      white:       a1gm = W (K gm), dsq = diag(C1), dL = -tril(alpha a1gm^T + 2 (W^T D) C1), D = diag(s^2 - 1), G = sym(S)
+      white_full:  dLq = tril(2 C1 Lq) - [kl] (tril(Lq) - diag(1 / Lq_ii)), dL = -tril(alpha a1gm^T + 2 W^T (Lq Lq^T - I) C1), G = sym(S)
+      krow slab 0 += k_kuu_grad(G)."""
+    W, L, Kuu, Z, alpha = (np.asarray(op[k], dtype=np.float64) for k in ('W', 'L', 'Kuu', 'Z', 'alpha'))
+    M, D = Z.shape
+    r = {}
+
+    def get(name):
+        return given[name] if given is not None and name in given else r[name][0]
+
+    def put(name, val, bnd):
+        r[name] = (val, bnd)
+
+    krow0 = np.array(op['krow'], dtype=np.float64)
+    full = mode == 'white_full'
+    if full:
+        Lq = np.tril(op['s'])
+        TmI = Lq @ Lq.T - np.eye(M)
+    else:
+        s2 = np.asarray(op['s'], dtype=np.float64) ** 2
+    if with_data:
+        C1in = np.asarray(op['C1'], dtype=np.float64)
+        col = krow0[:, :M, 1 + 2 * D]
+        kgm = ((col[0] + col[1]) + col[2]) + col[3]                                      # k_gather, slab order
+        put('a1gm', np.tril(W) @ kgm, 2 * gamma(M + 2) * (np.abs(np.tril(W)) @ np.abs(kgm)) + gamma(3) * np.abs(W) @ np.abs(col).sum(0))
+        if mode == 'diag':
+            put('du', W.T @ get('a1gm'), 2 * gamma(M + 2) * (np.abs(W.T) @ np.abs(get('a1gm'))))  # k_gemv_cols
+        put('C1', C1in.copy(), np.zeros((M, M)))                                         # plane 0 + zeros: the sum keeps its bits
+        C1 = get('C1')
+        if mode == 'diag':
+            put('Y', *sk_product('y', C1, W))
+            put('dsq', np.sum(W * get('Y'), 0), 2 * gamma(M + 2) * np.sum(np.abs(W * get('Y')), 0))   # k_coldot
+            put('T', *sk_product('tt', W * s2[None, :], W.T))
+            put('U', *sk_product('full', get('T'), C1))
+            U = get('U')
+            put('V', U + U.T - C1, 2 * gamma(2) * (np.abs(U) + np.abs(U.T) + np.abs(C1)))              # k_uut_minus
+            put('R', *sk_product('r', W.T, get('V'), lower_only=True))
+            a1gm, du, v = get('a1gm'), get('du'), np.asarray(op['v'], dtype=np.float64)
+            R = get('R')
+            put('dL', -np.tril(2.0 * R + np.outer(alpha, a1gm) + np.outer(du, v)),
+                np.tril(2 * gamma(4) * (2 * np.abs(R) + np.abs(np.outer(alpha, a1gm)) + np.abs(np.outer(du, v)))))   # k_dl_assemble
+        else:
+            if full:
+                put('Y', *sk_product('y', C1, Lq))
+                kl = np.tril(Lq) - np.diag(1.0 / np.diag(Lq)) if with_kl else 0.0
+                put('dLq', np.tril(2.0 * get('Y')) - kl, gamma(3) * (np.abs(np.tril(2.0 * get('Y'))) + np.abs(kl)))  # k_dlq_assemble
+                Rt = op['Rt'] if 'Rt' in op else TmI @ W                               # the image R^T = (T - I) W of the forward stage
+                put('R', *sk_product('rfull', Rt.T, C1, lower_only=True))
+            else:
+                put('dsq', np.diag(C1).copy(), np.zeros(M))                              # k_diag
+                put('R', *sk_product('r', ((s2 - 1.0)[:, None] * W).T, C1, lower_only=True))
+            a1gm, R = get('a1gm'), get('R')
+            put('dL', -np.tril(2.0 * R + np.outer(alpha, a1gm)), np.tril(2 * gamma(3) * (2 * np.abs(R) + np.abs(np.outer(alpha, a1gm)))))
+        put('Q', *sk_product('r', L.T, get('dL'), lower_only=True, post=phi))
+        put('QW', *sk_product('t', get('Q'), W, lower_only=True))
+        put('S', *sk_product('s', W.T, get('QW')))
+    elif full:
+        kl = np.tril(Lq) - np.diag(1.0 / np.diag(Lq)) if with_kl else np.zeros((M, M))
+        put('dLq', -kl, gamma(2) * np.abs(kl))
+    G, Gb = np.zeros((M, M)), np.zeros((M, M))
+    if with_data:
+        S = get('S')
+        G, Gb = 0.5 * (S + S.T), gamma(2) * (np.abs(S) + np.abs(S.T))
+    if with_kl and mode == 'diag':
+        if op.get('P') is None:
+            put('P', *sk_product('s', W.T, W))
+            P = get('P')
+        else:
+            P = np.asarray(op['P'], dtype=np.float64)
+        put('PSP', *sk_product('full', P, s2[:, None] * P))
+        PSP = get('PSP')
+        kl = 0.5 * (0.5 * (P + P.T) - np.outer(alpha, alpha) - 0.5 * (PSP + PSP.T))
+        G = G - kl
+        Gb = Gb + gamma(8) * (np.abs(G) + 0.5 * (np.abs(P) + np.abs(P.T)) + np.abs(np.outer(alpha, alpha)) + 0.5 * (np.abs(PSP) + np.abs(PSP.T)))
+    put('G', G, 2 * Gb)                                                                # k_sym_combine
+    kg, kb = kuu_grad(get('G'), Kuu, op['jitter'], Z)                                  # k_kuu_grad[_wide]: adds to slab 0, rows < M
+    krow = krow0.copy()
+    krow[0, :M] += kg
+    bnd = np.zeros_like(krow)
+    bnd[0, :M] = kb + EPS * np.abs(krow[0, :M])
+    put('krow', krow, bnd)
+    return r
+
+
+def dense_pack(krow, du, dsq, s, ell, var, include_kl=True, dkl_du=None, dkl_ds_diag=None):
+    """k_dense_pack's gradient blocks of one latent from the reverse stage's results: dZ = sum_slabs krow[:, 1 + d] / ell_d^2,
+    du = du - [kl] dKL/du, ds = 2 s dsq - [kl] (-1 / s + c s), dell = sum_m sum_slabs krow[:, 1 + D + d] / ell_d^3, and the Kuf / Kuu part of
+    dvar = sum_m sum_slabs krow[:, 0] / var.  dkl_du: alpha (unwhitened) or u (whitened); c = dkl_ds_diag: diag(Kuu^-1) or 1.
+    s = None (full covariance): no ds block -- dLq is the reverse stage's own."""
+    M = du.shape[0]
+    D = (krow.shape[2] - 2) // 2
+    k = krow[:, :M].sum(0)
+    ell = np.broadcast_to(np.asarray(ell, dtype=np.float64), (D,))
+    out = dict(dZ=k[:, 1:1 + D] / ell ** 2, dell=k[:, 1 + D:1 + 2 * D].sum(0) / ell ** 3, dvar=k[:, 0].sum() / var)
+    out['du'] = du - (dkl_du if include_kl else 0.0)
+    if s is not None:
+        out['ds'] = 2.0 * s * dsq - ((-1.0 / s + dkl_ds_diag * s) if include_kl else 0.0)
+    return out
+
+
+def mxm_int_seed(M, D):
+    """The draw of mxm_int_operands the GPU exact tier uses at (M, D); the CPU pin of the exactness premise walks the same draws."""
+    return 1000 + M + D
+
+
+def mxm_int_operands(M, D, seed, mode='diag'):
+    """Operands on which the whole reverse stage is EXACT in float64: every tap is a multiple of 1/8 and every product's sum |a||b| stays far
+    below 2^50, so each partial sum is exact in any order, with or without fma, and a GPU result must equal the numpy chain bit for bit.
+    W, L: unit lower triangular with three further +-1 entries per row at random columns <= i; s^2 in {1, 2} -- passed as s^2's square root
+    would not be exact, so s in {1, 2}, s^2 in {1, 4}; C1 = A + A^T with two +-1 entries per row of A; K gm in {-1, 0, 1} spread over
+    the four slabs of krow; alpha, v in {-1, 1}; Kuu symmetric and Z with entries in {-2 .. 2}; jitter = 1/2.
+    'white_full': Lq lower triangular, diagonal in {1, 2, -1} (1 / Lq_ii exact), two further +-1 entries per row."""
+    rs = np.random.RandomState(seed)
+
+    def unit_lower(n_extra):
+        A = np.eye(M)
+        for i in range(M):
+            for j in rs.randint(0, i + 1, n_extra):
+                if j < i:
+                    A[i, j] = rs.choice([-1.0, 1.0])
+        return A
+
+    W, L = unit_lower(3), unit_lower(3)
+    A = np.zeros((M, M))
+    for i in range(M):
+        A[i, rs.randint(0, M, 2)] = rs.choice([-1.0, 1.0], 2)
+    Kuu = rs.randint(-2, 3, (M, M)).astype(np.float64)
+    Kuu = np.tril(Kuu) + np.tril(Kuu, -1).T
+    Mp = round_up(M, BM)
+    krow = np.zeros((KG_SPLIT, Mp, 2 + 2 * D))
+    krow[rs.randint(0, KG_SPLIT, M), np.arange(M), 1 + 2 * D] = rs.randint(-1, 2, M)
+    op = dict(W=W, L=L, Kuu=Kuu, Z=rs.randint(-2, 3, (M, D)).astype(np.float64), C1=A + A.T, krow=krow, jitter=0.5,
+              alpha=rs.choice([-1.0, 1.0], M), v=rs.choice([-1.0, 1.0], M), u=rs.choice([-1.0, 1.0], M))
+    if mode == 'white_full':
+        Lq = np.diag(rs.choice([1.0, 2.0, -1.0], M))
+        for i in range(M):
+            for j in rs.randint(0, i + 1, 2):
+                if j < i:
+                    Lq[i, j] = rs.choice([-1.0, 1.0])
+        op['s'] = Lq
+    else:
+        op['s'] = rs.choice([1.0, 2.0], M)
+    return op
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# M x M forward stage (latents_forward) behind the factorisation: what it leaves for the chunk loop and the reverse stage
+# ---------------------------------------------------------------------------------------------------------------------------------
+def mxm_forward(W, L, u, s, white=False, need_grad=True, given=None):
+    """One statement per launch, applied to the W and L the factorisation produced.  Unwhitened: v = W u (k_gemv_rows), alpha = W^T v and
+    dkinv = column sums of W^2 (k_kl_cols), KL = 1/2 (sum v^2 - M - sum log s^2 + sum dkinv s^2 + sum log L_ii^2) (k_kl_value: four M-term
+    sums), Wp = W diag(s^2) (k_colscale), P = W^T W ("s"), Qt = diag(s^2) P - I, Rt = W Qt ("rt"), Wt = W^T.  Whitened: the block wh =
+    (s^2 - 1, u, 1) and KL = 1/2 (sum u^2 + sum s^2 - M - sum log s^2) (k_kl_white), alpha = W^T u (k_gemv_cols), Wp = diag(s^2 - 1) W.
+    given: the GPU's outputs -- every launch is then checked on the operands its kernel read.  Returns {name: (value, bound)}."""
+    M = W.shape[0]
+    r = {}
+
+    def get(name):
+        return given[name] if given is not None and given.get(name) is not None else r[name][0]
+
+    s2 = s * s
+    r['Wt'] = (W.T.copy(), np.zeros((M, M)))
+    if white:
+        r['wh'] = (np.stack([s2 - 1.0, u, np.ones(M)]), np.stack([EPS * (s2 + 1.0), np.zeros(M), np.zeros(M)]))
+        terms = np.array([np.sum(u * u), np.sum(s2), np.sum(np.abs(np.log(s2)))])
+        r['kl'] = (0.5 * (np.sum(u * u) - M - np.sum(np.log(s2)) + np.sum(s2)), gamma(M + 4) * (terms.sum() + M))
+        if need_grad:
+            r['alpha'] = (W.T @ u, 2 * gamma(M + 2) * (np.abs(W.T) @ np.abs(u)))
+            r['Wp'] = (get('wh')[0][:, None] * W, 2 * EPS * np.abs(get('wh')[0][:, None] * W))
+        return r
+    r['v'] = (np.tril(W) @ u, 2 * gamma(M + 2) * (np.abs(np.tril(W)) @ np.abs(u)))
+    v = get('v')
+    r['alpha'] = (W.T @ v, 2 * gamma(M + 2) * (np.abs(W.T) @ np.abs(v)))
+    r['dkinv'] = (np.sum(W * W, 0), 2 * gamma(M + 2) * np.sum(W * W, 0))
+    dk, ld = get('dkinv'), np.log(np.diag(L) ** 2)
+    terms = np.sum(v * v) + np.sum(np.abs(np.log(s2))) + np.sum(dk * s2) + np.sum(np.abs(ld))
+    r['kl'] = (0.5 * (np.sum(v * v) - M - np.sum(np.log(s2)) + np.sum(dk * s2) + np.sum(ld)), gamma(M + 4) * (terms + M))
+    if need_grad:
+        r['Wp'] = (W * s2[None, :], 2 * EPS * np.abs(W * s2[None, :]))
+        r['P'] = sk_product('s', W.T, W)
+        P = get('P')
+        r['Qt'] = (s2[:, None] * P - np.eye(M), 2 * gamma(2) * (np.abs(s2[:, None] * P) + np.eye(M)))
+        r['Rt'] = sk_product('rt', W, get('Qt'))
+    return r
+
+
+def dense_pack_ref(lat_f, lat_g, pw, D, mode='diag', include_kl=True):
+    """k_dense_pack's result vector with bounds: {name: (value, bound)} for data, kl, noise, var_f / var_g and per latent tag + dZ, du, ds,
+    dell.  lat_*: krow [4][M][2+2D], du, dsq, s (or dLq), kl_vec1, kl_vec2, ell, var, kl; pw [blocks][13].  Sums over the blocks / the M rows
+    of the four slabs, each term with the roundings of its formula: gamma_(terms + 8) of the sum of magnitudes."""
+    nb = pw.shape[0]
+    r = dict(data=(pw[:, 0].sum(), gamma(nb + 2) * np.abs(pw[:, 0]).sum()), noise=(pw[:, 1].sum(), gamma(nb + 2) * np.abs(pw[:, 1]).sum()),
+             kl=((lat_f['kl'] + lat_g['kl']) if include_kl else 0.0, EPS * (abs(lat_f['kl']) + abs(lat_g['kl']))))
+    for h, (tag, q) in enumerate((('f', lat_f), ('g', lat_g))):
+        M = q['du'].shape[0]
+        k, ka = q['krow'][:, :M].sum(0), np.abs(q['krow'][:, :M]).sum(0)
+        ell = np.broadcast_to(np.asarray(q['ell'], dtype=np.float64), (D,))
+        r[tag + 'dZ'] = (k[:, 1:1 + D] / ell ** 2, gamma(8) * ka[:, 1:1 + D] / ell ** 2)
+        r[tag + 'dell'] = (k[:, 1 + D:1 + 2 * D].sum(0) / ell ** 3, gamma(M + 8) * ka[:, 1 + D:1 + 2 * D].sum(0) / ell ** 3)
+        gv = pw[:, 2 + h]
+        r['var_' + tag] = (k[:, 0].sum() / q['var'] + gv.sum(), gamma(M + nb + 8) * (ka[:, 0].sum() / q['var'] + np.abs(gv).sum()))
+        r[tag + 'du'] = (q['du'] - (q['kl_vec1'] if include_kl else 0.0), EPS * (np.abs(q['du']) + np.abs(q['kl_vec1'])))
+        if mode == 'white_full':
+            r[tag + 'ds'] = (q['dLq'], np.zeros_like(q['dLq']))
+        else:
+            s = q['s']
+            klp = (-1.0 / s + q['kl_vec2'] * s) if include_kl else np.zeros(M)
+            r[tag + 'ds'] = (2.0 * s * q['dsq'] - klp, gamma(6) * (np.abs(2.0 * s * q['dsq']) + (np.abs(1.0 / s) + np.abs(q['kl_vec2'] * s) if include_kl else 0.0)))
+    return r

@@ -225,3 +225,181 @@ def test_plane_sum_order_and_bounds_reference_side():
             r, _ = sr.worst(np.abs(np.asarray(val - truth, dtype=np.float64)), bnd / 2)
             print('spread=%d %s: float64 reference error / its half of the bound = %.3g' % (spread, name, r))
             assert r <= 1.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# M x M reverse stage: the slice rule, the exact-tier operands, and the whole gradient composed from the references
+# ---------------------------------------------------------------------------------------------------------------------------------
+def test_split_k_slice_rule_table():
+    """run_gemm_sk's S per product and row-block count, as the issue states it: 8 everywhere up to nb = 8; from nb = 9 the full products take
+    512 // nb^2 (6 at nb = 9, 3 at nb = 12) while the lower-tile products keep more (8 at nb = 9, 6 at nb = 12)."""
+    full, lower = ('y', 'tt', 'full', 's', 'rt'), ('r', 'rfull', 't')
+    for nb in range(1, 9):
+        assert {sr.sk_slices(n, nb) for n in full + lower} == {8}, nb
+    assert {sr.sk_slices(n, 9) for n in full} == {6} and {sr.sk_slices(n, 9) for n in lower} == {8}
+    assert {sr.sk_slices(n, 12) for n in full} == {3} and {sr.sk_slices(n, 12) for n in lower} == {6}
+    # an 8-step range in 6 slices splits unevenly; every window list tiles its range without gap or overlap
+    assert sr.sk_windows('y', 9, 0, 8) == [(64, 65), (65, 66), (66, 68), (68, 69), (69, 70), (70, 72)]
+    for name in sr.SK_RANGES:
+        for nb in (1, 2, 3, 9, 12):
+            for bi in range(nb):
+                for bj in range(nb):
+                    w, r = sr.sk_windows(name, nb, bi, bj), sr.SK_RANGES[name](bi, bj, nb)
+                    if r is None:
+                        assert w == []
+                        continue
+                    assert w[0][0] == r[0] and w[-1][1] == r[1] and all(a[1] == b[0] for a, b in zip(w, w[1:])) and all(b > a for a, b in w)
+
+
+# the draws of the GPU exact tier (tests/test_gpu_mxm_stages.py): every size at D = 3 in every mode, every D at M = 300 unwhitened
+EXACT_DRAWS = [(M, 3, mode) for M in (9, 127, 128, 129, 300, 1100, 1536) for mode in sr.MXM_MODES] + [(300, D, 'diag') for D in (1, 8, 9, 17, 64)]
+
+
+@pytest.mark.parametrize('M,D,mode', EXACT_DRAWS, ids=lambda v: str(v))
+def test_integer_operands_make_the_reverse_stage_exact(M, D, mode):
+    """What entitles test_gpu_mxm_stages.py to demand bit equality, on the very draws it uses (sr.mxm_int_seed): every value of the float64
+    numpy chain is a multiple of 1/8 (krow: of 1/16, one more halving by Kuu - jitter I) and, for every product, max (|A||B|) stays below
+    2^50 -- so every partial sum is exactly representable, in any order, with or without fma."""
+    op = sr.mxm_int_operands(M, D, seed=sr.mxm_int_seed(M, D), mode=mode)
+    for P in ((None, 'given') if mode == 'diag' else (None,)):
+        if P is not None:
+            op = dict(op, P=op['W'].T @ op['W'])
+        r = sr.mxm_backward(op, mode)
+        worst = 0.0
+        for name, (val, bnd) in r.items():
+            q = 16.0 if name == 'krow' else 8.0
+            assert np.array_equal(val * q, np.round(val * q)), (name, M, mode)
+            if name in sr.MXM_PRODUCTS[mode]:
+                k = sr.sk_terms(sr.MXM_PRODUCTS[mode][name], M)
+                mag = np.max(np.where(k > 0, bnd / (2 * sr.gamma(k + 2) + (k == 0)), 0.0))
+                worst = max(worst, mag)
+        print('M=%d D=%d %s P %s: largest (|A||B|) of a product 2^%.1f' % (M, D, mode, P, np.log2(max(worst, 1.0))))
+        assert worst < 2.0 ** 50
+        if M > 128:
+            assert np.count_nonzero(r['G'][0]) > 0.5 * M * M
+            if mode == 'diag':
+                far = r['S'][0][-(M % 128 or 128):, :128]                                  # the far lower tile holds something in most places
+                assert np.count_nonzero(far) > 0.5 * far.size, (np.count_nonzero(far), far.size)
+
+
+def _mxm_fixture(D, seed):
+    """Two latents, Mf != Mg, neither a multiple of 32, a few hundred rows; lengthscales short enough for cond(Kuu) <= 1e4."""
+    X, Y, p = make_problem(300, 21, D, seed=seed, Mg=13, ell=0.12 if D == 2 else 0.45)
+    return X, Y, p
+
+
+def _mxm_forward(X, Y, p, tag, mode, base=None):
+    """The chunk loop's operands of one latent: A = W K, the mean / variance the point-wise stage sees, the panel J' and alpha of the Kuf
+    cotangent F = alpha gm^T + 2 J' diag(gv).  Unwhitened: what _compose reached (base = its latent: W, v, alpha, K, A1, J', the mean and
+    the gradient step's variance), plus the factor L and diag(Kuu^-1); whitened: the same operands for the other two parametrisations."""
+    Z, ell, var = p['Z' + tag], p['ell_' + tag], p['var_' + tag]
+    M = Z.shape[0]
+    Kuu = zo.rbf_K(Z, None, ell, var) + np.eye(M) * JITTER
+    L = sl.cholesky(Kuu, lower=True)
+    u = p['u_%sm' % tag].reshape(-1)
+    if mode == 'diag':
+        W = base['W']
+        return dict(M=M, W=W, L=L, Kuu=Kuu, Z=Z, K=base['K'], A=base['A1'], u=u, var=var, ell=ell, cond=base['cond'],
+                    s=p['u_%ss_sqrt' % tag].reshape(-1), v=base['v'], alpha=base['alpha'], dkinv=np.sum(W * W, 0), Jp=base['Jp'], mean=base['mean'],
+                    varn=base['var_grad'])
+    W = sl.solve_triangular(L, np.eye(M), lower=True)
+    K = zo.rbf_K(Z, X, ell, var)
+    A = W @ K
+    q = dict(M=M, W=W, L=L, Kuu=Kuu, Z=Z, K=K, A=A, u=u, var=var, ell=ell, cond=np.linalg.cond(Kuu))
+    if mode == 'white':
+        s = p['u_%ss_sqrt' % tag].reshape(-1)
+        d = s * s - 1.0
+        q.update(s=s, alpha=W.T @ u, Jp=(d[:, None] * W).T @ A, mean=u @ A, varn=var + d @ (A * A))
+    else:
+        Lq = np.tril(np.asarray(p['u_%ss_sqrt' % tag]).reshape(M, M))
+        TmI = Lq @ Lq.T - np.eye(M)
+        q.update(s=Lq, alpha=W.T @ u, Jp=(TmI @ W).T @ A, mean=u @ A, varn=var + np.sum(A * (TmI @ A), 0))
+    return q
+
+
+def _mxm_gradient(X, Y, p, mode, include_kl=True, rows=True):
+    """The whole gradient from the stage references: forward operands, point-wise cotangents, rank-N update, Kuf cotangent sums, the M x M
+    reverse stage, the pack formulas."""
+    D = X.shape[1]
+    base = _compose(X, Y, p)[0] if mode == 'diag' else dict(f=None, g=None)      # the unwhitened forward is the existing composition
+    lat = {tag: _mxm_forward(X, Y, p, tag, mode, base[tag]) for tag in 'fg'}
+    g = {}
+    if rows:
+        o = sr.pointwise_np(lat['f']['mean'], lat['f']['varn'], lat['g']['mean'], lat['g']['varn'], Y.reshape(-1), p['noise'])
+        g['noise'] = np.sum(o['dnoise'])
+    else:
+        g['noise'] = 0.0
+    for tag, gmk, gvk in (('f', 'dfm', 'dfv'), ('g', 'dgm', 'dgv')):
+        q = lat[tag]
+        M = q['M']
+        krow = np.zeros((sr.KG_SPLIT, M, 2 + 2 * D))
+        op = dict(W=q['W'], L=q['L'], Kuu=q['Kuu'], Z=q['Z'], s=q['s'], alpha=q['alpha'], v=q.get('v'), jitter=JITTER, krow=krow)
+        if rows:
+            gm, gv = o[gmk], o[gvk]
+            op['C1'] = sr.rank_update([(q['A'], gv)])[0]
+            krow[0] = sr.kgrad(q['Jp'], q['K'], q['alpha'], gm, gv, X, q['Z'], 0)[0]
+        r = sr.mxm_backward(op, mode, with_data=rows, with_kl=include_kl)
+        q['G'] = r['G'][0]
+        zero = np.zeros(M)
+        du = r['du'][0] if 'du' in r else (r['a1gm'][0] if rows else zero)
+        dsq = r['dsq'][0] if 'dsq' in r else zero
+        if mode == 'diag':
+            pk = sr.dense_pack(r['krow'][0], du, dsq, q['s'], q['ell'], q['var'], include_kl, q['alpha'], q['dkinv'])
+        elif mode == 'white':
+            pk = sr.dense_pack(r['krow'][0], du, dsq, q['s'], q['ell'], q['var'], include_kl, q['u'], 1.0)
+        else:
+            pk = sr.dense_pack(r['krow'][0], du, dsq, None, q['ell'], q['var'], include_kl, q['u'], None)
+            pk['ds'] = r['dLq'][0]
+        g['Z' + tag], g['u_%sm' % tag], g['u_%ss_sqrt' % tag], g['ell_' + tag] = pk['dZ'], pk['du'], pk['ds'], pk['dell']
+        g['var_' + tag] = pk['dvar'] + (np.sum(o[gvk]) if rows else 0.0)
+    return g, lat
+
+
+# Largest relative difference per block (relative to the block's largest entry) between the composed references and the oracle's autograd,
+# measured on these fixtures (all modes, D = 2 and 5, with and without KL / rows): 1.37e-13 / 3.8e-14 (unwhitened, D = 2 / 5), 4.3e-14 /
+# 1.6e-14 (whitened), 1.51e-13 / 2.0e-14 (full covariance).  The assertion is ten times the largest, far under the cap 1e-9.
+MXM_PIN_MEASURED = 1.6e-13
+MXM_PIN_CAP = 1e-9
+
+
+def _mxm_oracle(mode):
+    import whiten_ref
+    import fullcov_ref
+    return {'diag': ot, 'white': whiten_ref, 'white_full': fullcov_ref}[mode]
+
+
+@pytest.mark.parametrize('D', [2, 5])
+@pytest.mark.parametrize('mode', sr.MXM_MODES)
+def test_composed_reverse_stage_is_the_oracle_gradient(mode, D):
+    """Every key of PARAM_KEYS from the stage references (forward operands -> point-wise cotangents -> C1 and krow -> sr.mxm_backward ->
+    sr.dense_pack) against elbo_and_grad of the oracle (unwhitened), tests/whiten_ref.py and tests/fullcov_ref.py, with the KL, without it,
+    and with no rows (then G = -dKL/dKuu, also asserted in closed form).  cond(Kuu) <= 1e4 for both latents, so the project's rule
+    1e-13 cond caps the difference at 1e-9 relative per block.  Measured: at most 1.51e-13 relative per block (full covariance, D = 2); the
+    assertion is ten times the measured floor, 1.6e-12 (MXM_PIN_MEASURED): two float64 evaluations in different summation orders."""
+    import fullcov_ref
+    X, Y, p = _mxm_fixture(D, seed=21 + D)
+    if mode == 'white_full':
+        p = fullcov_ref.make_lq(p, seed=D, negative=1)
+    worst = 0.0
+    for include_kl, rows in ((True, True), (False, True), (True, False)):
+        g, lat = _mxm_gradient(X, Y, p, mode, include_kl, rows)
+        assert max(lat['f']['cond'], lat['g']['cond']) <= 1e4, (lat['f']['cond'], lat['g']['cond'])
+        Xr, Yr = (X, Y) if rows else (X[:0], Y[:0])
+        ref = _mxm_oracle(mode).elbo_and_grad(Xr, Yr, p, JITTER, include_kl=include_kl)[3]
+        for k in ot.PARAM_KEYS:
+            a, b = np.asarray(g[k], dtype=np.float64).reshape(-1), np.asarray(ref[k], dtype=np.float64).reshape(-1)
+            scale = np.max(np.abs(b))
+            e = float(np.max(np.abs(a - b)) / scale) if scale > 0 else float(np.max(np.abs(a)))
+            worst = max(worst, e)
+            print('MXM-PIN %s D=%d kl=%d rows=%d %-10s cond %.1e / %.1e  rel diff %.2e' % (mode, D, include_kl, rows, k, lat['f']['cond'], lat['g']['cond'], e))
+            assert e <= MXM_PIN_CAP, (k, e)
+            assert e <= 10 * MXM_PIN_MEASURED, (k, e)
+        if not rows and mode == 'diag':      # G = -dKL/dKuu = -1/2 (Kuu^-1 - alpha alpha^T - Kuu^-1 diag(s^2) Kuu^-1)
+            for tag in 'fg':
+                q = lat[tag]
+                Ki = np.linalg.inv(q['Kuu'])
+                G = -0.5 * (Ki - np.outer(q['alpha'], q['alpha']) - Ki @ np.diag(q['s'] ** 2) @ Ki)
+                assert relerr(q['G'], G) <= 1e-13 * q['cond'] + 1e-12
+        if not rows and mode != 'diag':      # the whitened KL does not see Kuu
+            assert not lat['f']['G'].any() and not lat['g']['G'].any()
+    print('MXM-PIN %s D=%d largest rel diff over all blocks %.2e' % (mode, D, worst))

@@ -546,8 +546,13 @@ void launch_kuu_grad(zigp_ctx* c, Latent& lt, int D, double jitter) {
   else hipLaunchKernelGGL(k_kuu_grad, dim3(Mp), dim3(256), 0, c->stream, lt.T3.p, lt.Kuu.p, jitter, lt.Z.p, lt.M, D, (int64_t)Mp, lt.krow.p);
 }
 
+// Taps of the M x M reverse stage (zigp_test_mxm_backward): tap(id, buffer) is called right after the launch that produced the value, before
+// its buffer is reused; ids are ZIGP_MXM_TAP_* (include/zigp_diag.h).  A call of the library passes none: no launch is added or moved.
+using MxmTap = std::function<int(int, const double*)>;
+#define ZIGP_TAP(id, buf) do { if (tap) ZIGP_TRY(tap(id, buf)); } while (0)
+
 // MxM backward: G = dELBO/dKuu (symmetric) -> krow accumulators.
-int latent_mxm_backward(zigp_ctx* c, Latent& lt, int D, double jitter, bool with_data, bool with_kl) {
+int latent_mxm_backward(zigp_ctx* c, Latent& lt, int D, double jitter, bool with_data, bool with_kl, const MxmTap& tap = nullptr) {
   const int Mp = lt.Mp, nb = Mp / BM, kb = BM / BK;
   const size_t mm = (size_t)Mp * Mp;
   ZIGP_ENSURE(c, lt.T1, mm); ZIGP_ENSURE(c, lt.T2, mm); ZIGP_ENSURE(c, lt.T3, mm); ZIGP_ENSURE(c, lt.G, mm);
@@ -564,31 +569,41 @@ int latent_mxm_backward(zigp_ctx* c, Latent& lt, int D, double jitter, bool with
       hipLaunchKernelGGL(k_gemv_cols, dim3(Mp / 64), dim3(64, COL_LANES), 0, c->stream, lt.W.p, lt.a1gm.p, (int64_t)Mp, lt.du.p);
     }
     latent_sym_from_planes(c, lt);
+    ZIGP_TAP(ZIGP_MXM_TAP_C1, lt.T1.p);
     // dsq = diag(A2 G A2^T) = diag(W^T C1 W): Y = C1 W -> T3 ; dsq[m] = sum_k W[k][m] Y[k][m]
     ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "y", nb, [&](int bi, int bj, int& k0, int& k1) { k0 = bj * kb; k1 = nb * kb; },
                                                      lt.T1.p, lt.W.p, lt.T3.p, Mp, SK_STORE, 1.0, false)));
+    ZIGP_TAP(ZIGP_MXM_TAP_Y, lt.T3.p);
     hipLaunchKernelGGL(k_coldot, dim3(Mp / 64), dim3(64, COL_LANES), 0, c->stream, lt.W.p, lt.T3.p, (int64_t)Mp, lt.dsq.p);
     // T = (W diag(s^2)) W^T -> T2   (both factors lower triangular: k <= min(i,j))
     ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_KCONTIG>(c, lt.sk, "tt", nb, [&](int bi, int bj, int& k0, int& k1) { k0 = 0; k1 = (std::min(bi, bj) + 1) * kb; },
                                                     lt.Wp.p, lt.W.p, lt.T2.p, Mp, SK_STORE, 1.0, false)));
+    ZIGP_TAP(ZIGP_MXM_TAP_T, lt.T2.p);
     // U = T C1 -> T3 ; V = U + U^T - C1 -> G
     ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "full", nb, [&](int, int, int& k0, int& k1) { k0 = 0; k1 = nb * kb; },
                                                      lt.T2.p, lt.T1.p, lt.T3.p, Mp, SK_STORE, 1.0, false)));
+    ZIGP_TAP(ZIGP_MXM_TAP_U, lt.T3.p);
     hipLaunchKernelGGL(k_uut_minus, dim3(gridmm), dim3(256), 0, c->stream, lt.T3.p, lt.T1.p, (int64_t)Mp, lt.G.p);
+    ZIGP_TAP(ZIGP_MXM_TAP_V, lt.G.p);
     // R = W^T V (lower part) -> T2
     auto lower_up = [&](int bi, int bj, int& k0, int& k1) { if (bj <= bi) { k0 = bi * kb; k1 = nb * kb; } else { k0 = 0; k1 = 0; } };
     ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "r", nb, lower_up, lt.W.p, lt.G.p, lt.T2.p, Mp, SK_STORE, 1.0, true)));
+    ZIGP_TAP(ZIGP_MXM_TAP_R, lt.T2.p);
     // dL = -tril(alpha (A1 gm)^T + (A2 gm) v^T + 2 R) -> T1
     hipLaunchKernelGGL(k_dl_assemble, dim3(gridmm), dim3(256), 0, c->stream, lt.T2.p, (int64_t)Mp, lt.vec.p + Mp, lt.a1gm.p, lt.du.p,
                        lt.vec.p, lt.T1.p);
+    ZIGP_TAP(ZIGP_MXM_TAP_DL, lt.T1.p);
     // Q = Phi(L^T dL) -> T2  (upper tiles are not computed)
     ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "r", nb, lower_up, lt.L.p, lt.T1.p, lt.T2.p, Mp, SK_PHI, 1.0, true)));
+    ZIGP_TAP(ZIGP_MXM_TAP_Q, lt.T2.p);
     // T = Q W -> T3 (lower)
     ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "t", nb, [&](int bi, int bj, int& k0, int& k1) {
       if (bj <= bi) { k0 = bj * kb; k1 = (bi + 1) * kb; } else { k0 = 0; k1 = 0; } }, lt.T2.p, lt.W.p, lt.T3.p, Mp, SK_STORE, 1.0, true)));
+    ZIGP_TAP(ZIGP_MXM_TAP_QW, lt.T3.p);
     // S = W^T T -> T1
     ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "s", nb, [&](int bi, int bj, int& k0, int& k1) { k0 = std::max(bi, bj) * kb; k1 = nb * kb; },
                                                       lt.W.p, lt.T3.p, lt.T1.p, Mp, SK_STORE, 1.0, false)));
+    ZIGP_TAP(ZIGP_MXM_TAP_S, lt.T1.p);
   }
   double* P = lt.P_ready ? lt.P.p : lt.T2.p; double* PSP = lt.G.p;
   if (with_kl) {
@@ -596,10 +611,12 @@ int latent_mxm_backward(zigp_ctx* c, Latent& lt, int D, double jitter, bool with
     if (!lt.P_ready)
       ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "s", nb, [&](int bi, int bj, int& k0, int& k1) { k0 = std::max(bi, bj) * kb; k1 = nb * kb; },
                                                         lt.W.p, lt.W.p, lt.T2.p, Mp, SK_STORE, 1.0, false)));
+    if (!lt.P_ready) ZIGP_TAP(ZIGP_MXM_TAP_P, lt.T2.p);
     // Ps = diag(s2) P -> T3 ; PSP = P Ps -> G
     hipLaunchKernelGGL(k_rowscale, dim3(gridmm), dim3(256), 0, c->stream, P, lt.s2.p, (int64_t)Mp, lt.T3.p);
     ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "full", nb, [&](int, int, int& k0, int& k1) { k0 = 0; k1 = nb * kb; },
                                                      P, lt.T3.p, lt.G.p, Mp, SK_STORE, 1.0, false)));
+    ZIGP_TAP(ZIGP_MXM_TAP_PSP, lt.G.p);
   }
   // G = sym(S) - dKL/dKuu -> T3 (T3 free again)
   hipLaunchKernelGGL(k_sym_combine, dim3(gridmm), dim3(256), 0, c->stream, S, P, PSP, lt.vec.p + Mp, with_data ? 1 : 0, with_kl ? 1 : 0,
@@ -616,7 +633,8 @@ int latent_mxm_backward(zigp_ctx* c, Latent& lt, int D, double jitter, bool with
 // k_dense_pack adds the KL parts from Latent::wh.
 // q_full: ds becomes dLq (latent_qfull_dlq, which also carries the KL part, so it runs without rows too) and the product's left factor
 // is R = W^T (T - I), dense: its image R^T is in Rt and every k block contributes to the lower tiles.
-int latent_mxm_backward_white(zigp_ctx* c, Latent& lt, int D, double jitter, bool with_data, bool q_full = false, bool with_kl = false) {
+int latent_mxm_backward_white(zigp_ctx* c, Latent& lt, int D, double jitter, bool with_data, bool q_full = false, bool with_kl = false,
+                              const MxmTap& tap = nullptr) {
   const int Mp = lt.Mp, nb = Mp / BM, kb = BM / BK;
   const size_t mm = (size_t)Mp * Mp;
   ZIGP_ENSURE(c, lt.T1, mm); ZIGP_ENSURE(c, lt.T2, mm); ZIGP_ENSURE(c, lt.T3, mm);
@@ -629,23 +647,31 @@ int latent_mxm_backward_white(zigp_ctx* c, Latent& lt, int D, double jitter, boo
       hipLaunchKernelGGL(k_gemv_rows, dim3(Mp), dim3(256), 0, c->stream, lt.W.p, kgm, (int64_t)Mp, lt.a1gm.p);
     }
     latent_sym_from_planes(c, lt);      // C1 -> T1
-    if (q_full) ZIGP_TRY(latent_qfull_dlq(c, lt, true, with_kl));
-    else hipLaunchKernelGGL(k_diag, dim3(ceil_div(Mp, 256)), dim3(256), 0, c->stream, lt.T1.p, (int64_t)Mp, lt.dsq.p);
+    ZIGP_TAP(ZIGP_MXM_TAP_C1, lt.T1.p);
+    if (q_full) {
+      ZIGP_TRY(latent_qfull_dlq(c, lt, true, with_kl));
+      ZIGP_TAP(ZIGP_MXM_TAP_Y, lt.T3.p);      // Y = C1 Lq
+    } else hipLaunchKernelGGL(k_diag, dim3(ceil_div(Mp, 256)), dim3(256), 0, c->stream, lt.T1.p, (int64_t)Mp, lt.dsq.p);
     // R = (W^T D) C1 (lower part) -> T2 ; the factor image D W is in Wp (latents_forward)
     auto lower_up = [&](int bi, int bj, int& k0, int& k1) { if (bj <= bi) { k0 = bi * kb; k1 = nb * kb; } else { k0 = 0; k1 = 0; } };
     auto lower_all = [&](int bi, int bj, int& k0, int& k1) { k0 = 0; k1 = bj <= bi ? nb * kb : 0; };
     if (q_full) ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "rfull", nb, lower_all, lt.Rt.p, lt.T1.p, lt.T2.p, Mp, SK_STORE, 1.0, true)));
     else ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "r", nb, lower_up, lt.Wp.p, lt.T1.p, lt.T2.p, Mp, SK_STORE, 1.0, true)));
+    ZIGP_TAP(ZIGP_MXM_TAP_R, lt.T2.p);
     // dL = -tril(alpha (A gm)^T + 2 R) -> T1 ; the second rank-1 term of k_dl_assemble is switched off by the zero vector `du` (zeroed per
     // call and never written in this mode)
     hipLaunchKernelGGL(k_dl_assemble, dim3(gridmm), dim3(256), 0, c->stream, lt.T2.p, (int64_t)Mp, lt.vec.p + Mp, lt.a1gm.p, lt.du.p,
                        lt.du.p, lt.T1.p);
+    ZIGP_TAP(ZIGP_MXM_TAP_DL, lt.T1.p);
     // Q = Phi(L^T dL) -> T2 ; T = Q W -> T3 (lower) ; S = W^T T -> T1
     ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "r", nb, lower_up, lt.L.p, lt.T1.p, lt.T2.p, Mp, SK_PHI, 1.0, true)));
+    ZIGP_TAP(ZIGP_MXM_TAP_Q, lt.T2.p);
     ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "t", nb, [&](int bi, int bj, int& k0, int& k1) {
       if (bj <= bi) { k0 = bj * kb; k1 = (bi + 1) * kb; } else { k0 = 0; k1 = 0; } }, lt.T2.p, lt.W.p, lt.T3.p, Mp, SK_STORE, 1.0, true)));
+    ZIGP_TAP(ZIGP_MXM_TAP_QW, lt.T3.p);
     ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "s", nb, [&](int bi, int bj, int& k0, int& k1) { k0 = std::max(bi, bj) * kb; k1 = nb * kb; },
                                                       lt.W.p, lt.T3.p, lt.T1.p, Mp, SK_STORE, 1.0, false)));
+    ZIGP_TAP(ZIGP_MXM_TAP_S, lt.T1.p);
   } else if (q_full) ZIGP_TRY(latent_qfull_dlq(c, lt, false, with_kl));
   // G = sym(S) -> T3
   hipLaunchKernelGGL(k_sym_combine, dim3(gridmm), dim3(256), 0, c->stream, lt.T1.p, lt.T1.p, lt.T1.p, lt.vec.p + Mp, with_data ? 1 : 0, 0,
@@ -1866,31 +1892,41 @@ int zigp_test_latents_forward(zigp_ctx* c, const zigp_params* p, double jitter, 
   if (!c) return ZIGP_EARG;
   ZIGP_TRY(validate_params(c, p));
   if (!out_f || !out_g || !(jitter >= 0)) return fail_arg(c, "zigp_test_latents_forward: bad arguments");
-  if (c->q_full) return fail_arg(c, "zigp_test_latents_forward: the unwhitened stage only (zigp_set_q_full is on; see zigp_test_q_full_forward)");
+  if (c->q_full) return fail_arg(c, "zigp_test_latents_forward: the diagonal stages only (zigp_set_q_full is on; see zigp_test_q_full_forward)");
   ZIGP_HIP(c, hipSetDevice(c->device));
+  const bool white = c->whiten, grad = need_grad != 0;
   HostLatent hl[2] = {{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f}, {p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g}};
   ZIGP_TRY(begin_staged_call(c));
   ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
   ZIGP_TRY(latents_upload(c, hl, p->D));
   ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
-  ZIGP_TRY(latents_forward(c, hl, p->D, jitter, true, need_grad != 0));
+  ZIGP_TRY(latents_forward(c, hl, p->D, jitter, true, grad, nullptr, nullptr, white, false));
   ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   ZIGP_TRY(check_info(c, "Kuu"));
   double* const* outs[2] = {out_f, out_g};
   for (int h = 0; h < 2; ++h) {
     Latent& lt = c->lat[h];
     const int M = lt.M, Mp = lt.Mp;
-    std::vector<double> hm((size_t)Mp * Mp);
-    const double* mats[2] = {lt.W.p, need_grad ? lt.Rt.p : nullptr};
-    double* dst[2] = {outs[h][0], outs[h][3]};
-    for (int q = 0; q < 2; ++q) {
-      if (!dst[q] || !mats[q]) continue;
-      ZIGP_HIP(c, hipMemcpyAsync(hm.data(), mats[q], sizeof(double) * hm.size(), hipMemcpyDeviceToHost, c->stream));
-      ZIGP_HIP(c, hipStreamSynchronize(c->stream));
-      for (int i = 0; i < M; ++i) memcpy(dst[q] + (size_t)i * M, &hm[(size_t)i * Mp], sizeof(double) * M);
+    double* const* o = outs[h];
+    // (M,M) images; one the mode or need_grad does not produce is left untouched
+    const double* mats[ZIGP_FWD_OUTS] = {nullptr};
+    mats[ZIGP_FWD_W] = lt.W.p; mats[ZIGP_FWD_L] = lt.L.p; mats[ZIGP_FWD_KUU] = lt.Kuu.p; mats[ZIGP_FWD_WT] = lt.Wt.p;
+    if (grad) mats[ZIGP_FWD_WP] = lt.Wp.p;
+    if (grad && !white) { mats[ZIGP_FWD_RT] = lt.Rt.p; mats[ZIGP_FWD_P] = lt.P.p; mats[ZIGP_FWD_QT] = lt.Qt.p; }
+    for (int q = 0; q < ZIGP_FWD_OUTS; ++q)
+      if (mats[q]) ZIGP_TRY(stage_download_square(c, mats[q], M, Mp, o[q]));
+    const double* vec = lt.vec.p;
+    if (!white) {
+      ZIGP_TRY(stage_download_rows(c, vec, o[ZIGP_FWD_V], 1, M));
+      ZIGP_TRY(stage_download_rows(c, vec + Mp, o[ZIGP_FWD_ALPHA], 1, M));
+      ZIGP_TRY(stage_download_rows(c, vec + 2 * Mp, o[ZIGP_FWD_DKINV], 1, M));
+      ZIGP_TRY(stage_download_rows(c, vec + 3 * Mp, o[ZIGP_FWD_KL], 1, 1));
+    } else {
+      if (grad) ZIGP_TRY(stage_download_rows(c, vec + Mp, o[ZIGP_FWD_ALPHA], 1, M));
+      ZIGP_TRY(stage_download_rows(c, lt.wh.p + 3 * Mp, o[ZIGP_FWD_KL], 1, 1));
+      if (o[ZIGP_FWD_WH])
+        for (int q = 0; q < 3; ++q) ZIGP_TRY(stage_download_rows(c, lt.wh.p + (size_t)q * Mp, o[ZIGP_FWD_WH] + (size_t)q * M, 1, M));
     }
-    if (outs[h][1]) ZIGP_HIP(c, hipMemcpyAsync(outs[h][1], lt.vec.p, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
-    if (outs[h][2]) ZIGP_HIP(c, hipMemcpyAsync(outs[h][2], lt.vec.p + Mp, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
     ZIGP_HIP(c, hipStreamSynchronize(c->stream));
   }
   prof_collect(c);
@@ -2031,6 +2067,183 @@ int zigp_test_rank_update(zigp_ctx* c, int32_t M, int32_t nchunks, const int64_t
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));
   for (int i = 0; i < M; ++i) memcpy(C1 + (size_t)i * M, &hc[(size_t)i * Mp], sizeof(double) * M);
   plan[0] = sp.So; plan[1] = sp.Sd;
+  return ZIGP_OK;
+}
+
+// ---- M x M reverse stage of one latent (include/zigp_diag.h), through latent_mxm_backward / latent_mxm_backward_white ----
+namespace {
+// host (rows x cols) -> device (rows_p x cols_p), `pad` outside the real block; lower: entries above the diagonal are zero
+int stage_upload_padded(zigp_ctx* c, DevBuf& buf, const double* src, int rows, int cols, int rows_p, int cols_p, double pad, bool lower = false) {
+  std::vector<double> h((size_t)rows_p * cols_p, pad);
+  for (int i = 0; i < rows; ++i) memcpy(&h[(size_t)i * cols_p], src + (size_t)i * cols, sizeof(double) * cols);
+  if (lower)
+    for (int i = 0; i < rows_p; ++i)
+      for (int j = i + 1; j < cols_p; ++j) h[(size_t)i * cols_p + j] = 0.0;
+  ZIGP_ENSURE(c, buf, h.size());
+  ZIGP_HIP(c, hipMemcpyAsync(buf.p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));     // h goes out of scope
+  return 0;
+}
+}  // namespace
+int zigp_test_mxm_backward(zigp_ctx* c, const zigp_stage_mxm* a) {
+  if (!c) return ZIGP_EARG;
+  if (!a) return fail_arg(c, "zigp_test_mxm_backward: NULL arguments");
+  if (a->M <= 0) return fail_arg(c, "zigp_test_mxm_backward: M must be positive");
+  if (a->D < 1 || a->D > ZIGP_MAX_D) return fail_arg(c, "zigp_test_mxm_backward: D must be in [1, " ZIGP_MAX_D_STR "] (ZIGP_MAX_D)");
+  if (a->mode < 0 || a->mode > 2) return fail_arg(c, "zigp_test_mxm_backward: mode must be 0 (unwhitened), 1 (whitened diagonal) or 2 (whitened full covariance)");
+  if (!(a->jitter >= 0) || !(a->pad == a->pad)) return fail_arg(c, "zigp_test_mxm_backward: jitter must be >= 0 and pad a number");
+  if (!a->W || !a->L || !a->Kuu || !a->Z || !a->s || !a->alpha || !a->krow || (a->mode == 0 && !a->v) || (a->with_data && !a->C1))
+    return fail_arg(c, "zigp_test_mxm_backward: NULL operand of the mode");
+  const int M = a->M, D = a->D, Wd = 2 + 2 * D;
+  const bool white = a->mode != 0, q_full = a->mode == 2, with_data = a->with_data != 0, with_kl = a->with_kl != 0;
+  for (int m = 0; m < M; ++m)
+    if (!((q_full ? a->s[(size_t)m * M + m] : a->s[m]) != 0))
+      return fail_arg(c, q_full ? "zigp_test_mxm_backward: zero (or NaN) diagonal entry of Lq" : "zigp_test_mxm_backward: zero (or NaN) entry of s");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  Latent& lt = c->lat[0];
+  lt.M = M; lt.Mp = (int)round_up(M, BM);
+  if (c->lat[1].Mp <= 0) { c->lat[1].M = 1; c->lat[1].Mp = BM; }     // the zeroing path below walks both latents
+  const int Mp = lt.Mp;
+  const size_t mm = (size_t)Mp * Mp;
+  // the call's accumulators, as a gradient step sizes and zeroes them (a1gm, du, dsq, krow; the rank-update planes when there are rows)
+  {
+    zigp_params pp;
+    memset(&pp, 0, sizeof(pp));
+    DenseCall k;
+    memset(static_cast<void*>(&k.hl), 0, sizeof(k.hl));
+    k.p = &pp; k.dX = nullptr; k.dY = nullptr; k.Nrows = 1024; k.D = D; k.jitter = a->jitter; k.scale = 1; k.g_offset = 0; k.row_begin = 0;
+    k.row_end = with_data ? 1024 : 0; k.include_kl = with_kl ? 1 : 0; k.predict = false; k.d_out9 = nullptr; k.need_grad = true; k.has_rows = with_data;
+    k.whiten = white; k.q_full = q_full; k.Nc = 1024;
+    ZIGP_TRY(dense_prepare_buffers(c, k));
+  }
+  // operands
+  ZIGP_TRY(stage_upload_square(c, lt.W, a->W, M, Mp, 1.0));
+  ZIGP_TRY(stage_upload_square(c, lt.L, a->L, M, Mp, 1.0));
+  ZIGP_TRY(stage_upload_padded(c, lt.Kuu, a->Kuu, M, M, Mp, Mp, a->pad));
+  ZIGP_TRY(stage_upload_padded(c, lt.Z, a->Z, M, D, Mp, D, a->pad));
+  ZIGP_ENSURE(c, lt.vec, 4 * (size_t)Mp + 8);
+  ZIGP_HIP(c, hipMemsetAsync(lt.vec.p, 0, sizeof(double) * (4 * (size_t)Mp + 8), c->stream));
+  if (a->v) ZIGP_HIP(c, hipMemcpyAsync(lt.vec.p, a->v, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+  ZIGP_HIP(c, hipMemcpyAsync(lt.vec.p + Mp, a->alpha, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+  ZIGP_ENSURE(c, lt.Wp, mm);
+  const dim3 gridmm(ceil_div((int64_t)mm, 256));
+  lt.P_ready = false;
+  if (q_full) {          // the staged factor and its small vectors, then T - I -> P and R^T -> Rt
+    ZIGP_TRY(stage_qfull_operands(c, lt, M, a->s, a->u));
+    ZIGP_ENSURE(c, lt.P, mm); ZIGP_ENSURE(c, lt.Rt, mm);
+    ZIGP_TRY(latent_qfull_factors(c, lt));
+  } else if (white) {    // the whitened vectors (k_kl_white), then D W -> Wp
+    ZIGP_TRY(stage_upload_padded(c, lt.u, a->u, a->u ? M : 0, 1, Mp, 1, 0.0));
+    ZIGP_TRY(stage_upload_padded(c, lt.s, a->s, M, 1, Mp, 1, a->pad));
+    ZIGP_ENSURE(c, lt.wh, 4 * (size_t)Mp + 8);
+    hipLaunchKernelGGL(k_kl_white, dim3(1), dim3(256), 0, c->stream, lt.u.p, lt.s.p, lt.M, (int64_t)Mp, lt.wh.p);
+    hipLaunchKernelGGL(k_rowscale, gridmm, dim3(256), 0, c->stream, lt.W.p, lt.wh.p, (int64_t)Mp, lt.Wp.p);
+    ZIGP_HIP(c, hipGetLastError());
+  } else {               // s^2 (one multiplication per entry, k_kuu_setup's), then W diag(s^2) -> Wp
+    std::vector<double> s2(M);
+    for (int m = 0; m < M; ++m) s2[m] = a->s[m] * a->s[m];
+    ZIGP_TRY(stage_upload_padded(c, lt.s2, s2.data(), M, 1, Mp, 1, a->pad * a->pad));
+    hipLaunchKernelGGL(k_colscale, gridmm, dim3(256), 0, c->stream, lt.W.p, lt.s2.p, (int64_t)Mp, lt.Wp.p);
+    ZIGP_HIP(c, hipGetLastError());
+    if (a->P) { ZIGP_TRY(stage_upload_square(c, lt.P, a->P, M, Mp, 1.0)); lt.P_ready = true; }
+  }
+  if (with_data) ZIGP_TRY(stage_upload_padded(c, lt.dLpart, a->C1, M, M, Mp, Mp, a->pad, true));     // plane 0; the others keep the step's zeros
+  ZIGP_HIP(c, hipMemcpyAsync(lt.krow.p, a->krow, sizeof(double) * KG_SPLIT * Mp * Wd, hipMemcpyHostToDevice, c->stream));
+  // scratch: whatever a launch reads before the stage wrote it shows
+  ZIGP_ENSURE(c, lt.T1, mm); ZIGP_ENSURE(c, lt.T2, mm); ZIGP_ENSURE(c, lt.T3, mm);
+  if (!white) ZIGP_ENSURE(c, lt.G, mm);
+  for (double* q : {lt.T1.p, lt.T2.p, lt.T3.p, white ? (double*)nullptr : lt.G.p})
+    if (q) ZIGP_HIP(c, hipMemsetAsync(q, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * mm, c->stream));
+  if (q_full) {
+    ZIGP_ENSURE(c, lt.dLq, mm);
+    ZIGP_HIP(c, hipMemsetAsync(lt.dLq.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * mm, c->stream));
+  }
+  const MxmTap tap = [&](int id, const double* dev) -> int {
+    if (id < 0 || id >= ZIGP_MXM_TAPS || !a->tap[id]) return 0;
+    return stage_download_square(c, dev, M, Mp, a->tap[id]);
+  };
+  const int rc = white ? latent_mxm_backward_white(c, lt, D, a->jitter, with_data, q_full, with_kl, tap)
+                       : latent_mxm_backward(c, lt, D, a->jitter, with_data, with_kl, tap);
+  lt.P_ready = false;
+  ZIGP_TRY(rc);
+  ZIGP_TRY(stage_download_rows(c, lt.a1gm.p, a->a1gm, 1, M));
+  ZIGP_TRY(stage_download_rows(c, lt.du.p, a->du, 1, M));
+  ZIGP_TRY(stage_download_rows(c, lt.dsq.p, a->dsq, 1, M));
+  ZIGP_TRY(stage_download_rows(c, lt.krow.p, a->krow, (int64_t)KG_SPLIT * Mp, Wd));
+  ZIGP_TRY(stage_download_square(c, lt.T3.p, M, Mp, a->G));
+  if (q_full) ZIGP_TRY(stage_download_square(c, lt.dLq.p, M, Mp, a->dLq));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  return ZIGP_OK;
+}
+
+// ---- the result vector (k_dense_pack, k_pack_square) from caller-supplied accumulators, through dense_pack ----
+int zigp_test_dense_pack(zigp_ctx* c, const zigp_stage_pack* a) {
+  if (!c) return ZIGP_EARG;
+  if (!a || !a->out) return fail_arg(c, "zigp_test_dense_pack: NULL arguments");
+  if (a->D < 1 || a->D > ZIGP_MAX_D) return fail_arg(c, "zigp_test_dense_pack: D must be in [1, " ZIGP_MAX_D_STR "] (ZIGP_MAX_D)");
+  if (a->mode < 0 || a->mode > 2 || a->pw_blocks < 1 || !a->pw) return fail_arg(c, "zigp_test_dense_pack: need a mode in 0 .. 2 and pw [pw_blocks][13], pw_blocks >= 1");
+  if (a->mean_on && a->D > MAXD) return fail_arg(c, "zigp_test_dense_pack: the mean function's sums cover D <= 8");
+  const int D = a->D, Wd = 2 + 2 * D;
+  const bool grad = a->need_grad != 0, white = a->mode != 0, q_full = a->mode == 2;
+  size_t need = DP_HDR;
+  for (int h = 0; h < 2; ++h) {
+    const zigp_stage_pack_latent& q = a->lat[h];
+    if (q.M <= 0) return fail_arg(c, "zigp_test_dense_pack: M must be positive");
+    if (!q.kl_vec1 || (!q_full && !q.kl_vec2)) return fail_arg(c, "zigp_test_dense_pack: NULL operand");
+    if (grad && (!q.krow || !q.du || !q.ell || !(q.var > 0) || (q_full ? !q.dLq : (!q.dsq || !q.s))))
+      return fail_arg(c, "zigp_test_dense_pack: NULL operand of a gradient call (or var <= 0)");
+    if (grad && !q_full)
+      for (int m = 0; m < q.M; ++m)
+        if (!(q.s[m] != 0)) return fail_arg(c, "zigp_test_dense_pack: zero (or NaN) entry of s");
+    if (grad) need += (size_t)q.M * D + q.M + (q_full ? (size_t)q.M * q.M : (size_t)q.M) + D;
+  }
+  if (a->n_out != (int64_t)need) return fail_arg(c, "zigp_test_dense_pack: n_out must be 16 + sum over the latents of M D + M + (M or M M) + D (16 without need_grad)");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  const size_t nacc = (size_t)a->pw_blocks * PW_ACC;
+  ZIGP_TRY(stage_upload_rows(c, c->pw_part, a->pw, (int64_t)nacc, (int64_t)nacc, 1));
+  for (int h = 0; h < 2; ++h) {
+    Latent& lt = c->lat[h];
+    const zigp_stage_pack_latent& q = a->lat[h];
+    lt.M = q.M; lt.Mp = (int)round_up(q.M, BM); lt.var = q.var;
+    const int M = lt.M, Mp = lt.Mp;
+    // the small vectors in the layout k_dense_pack reads: [. | dKL/du | diagonal factor of dKL/ds | KL]
+    DevBuf& vec = white ? lt.wh : lt.vec;
+    ZIGP_ENSURE(c, vec, 4 * (size_t)Mp + 8);
+    ZIGP_HIP(c, hipMemsetAsync(vec.p, 0, sizeof(double) * (4 * (size_t)Mp + 8), c->stream));
+    ZIGP_HIP(c, hipMemcpyAsync(vec.p + Mp, q.kl_vec1, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+    if (q.kl_vec2) ZIGP_HIP(c, hipMemcpyAsync(vec.p + 2 * (size_t)Mp, q.kl_vec2, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+    ZIGP_HIP(c, hipMemcpyAsync(vec.p + 3 * (size_t)Mp, &q.kl, sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (!grad) continue;
+    ZIGP_ENSURE(c, lt.krow, (size_t)KG_SPLIT * Mp * Wd);
+    ZIGP_HIP(c, hipMemsetAsync(lt.krow.p, 0, sizeof(double) * KG_SPLIT * Mp * Wd, c->stream));
+    for (int sp = 0; sp < KG_SPLIT; ++sp)
+      ZIGP_HIP(c, hipMemcpyAsync(lt.krow.p + (size_t)sp * Mp * Wd, q.krow + (size_t)sp * M * Wd, sizeof(double) * M * Wd, hipMemcpyHostToDevice, c->stream));
+    ZIGP_TRY(stage_upload_rows(c, white ? lt.a1gm : lt.du, q.du, M, Mp, 1));
+    ZIGP_TRY(stage_upload_rows(c, lt.ell, q.ell, D, std::max(D, MAXD), 1));
+    if (q_full) ZIGP_TRY(stage_upload_square(c, lt.dLq, q.dLq, M, Mp, 0.0));
+    else { ZIGP_TRY(stage_upload_rows(c, lt.dsq, q.dsq, M, Mp, 1)); ZIGP_TRY(stage_upload_rows(c, lt.s, q.s, M, Mp, 1)); }
+    if (q_full) {     // k_dense_pack loads s[m] and dsq[m] before it looks at q_full and discards what it forms from them: zeros
+      ZIGP_TRY(stage_upload_rows(c, lt.dsq, nullptr, 0, Mp, 1));
+      ZIGP_TRY(stage_upload_rows(c, lt.s, nullptr, 0, Mp, 1));
+    }
+  }
+  zigp_params pp;
+  memset(&pp, 0, sizeof(pp));
+  DenseCall k;
+  memset(static_cast<void*>(&k.hl), 0, sizeof(k.hl));
+  k.p = &pp; k.dX = nullptr; k.dY = nullptr; k.Nrows = 0; k.D = D; k.jitter = 0; k.scale = 1; k.g_offset = 0; k.row_begin = 0; k.row_end = 0;
+  k.include_kl = a->include_kl ? 1 : 0; k.predict = false; k.d_out9 = nullptr; k.need_grad = grad; k.has_rows = true;
+  k.whiten = white; k.q_full = q_full; k.pw_blocks = a->pw_blocks;
+  const bool mean_on = c->mean_on;
+  c->mean_on = a->mean_on != 0;
+  DensePackArgs pa;
+  size_t n = 0;
+  const int rc = dense_pack(c, k, pa, n);
+  c->mean_on = mean_on;
+  ZIGP_TRY(rc);
+  if (n != need) return fail_arg(c, "zigp_test_dense_pack: the pack laid out another vector than the caller sized");
+  ZIGP_TRY(stage_download_rows(c, c->packed.p, a->out, 1, (int64_t)n));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
   return ZIGP_OK;
 }
 

@@ -103,6 +103,30 @@ class zigp_stage_pointwise(C.Structure):   # include/zigp_diag.h
                 ('gm_f', dp), ('gv_f', dp), ('gm_g', dp), ('gv_g', dp), ('acc', dp), ('out9', dp)]
 
 
+MXM_TAPS = ('C1', 'Y', 'T', 'U', 'V', 'R', 'dL', 'Q', 'QW', 'S', 'P', 'PSP')   # include/zigp_diag.h ZIGP_MXM_TAP_*
+MXM_MODES = ('diag', 'white', 'white_full')                                      # zigp_stage_mxm.mode
+
+
+class zigp_stage_mxm(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('M', C.c_int32), ('D', C.c_int32), ('mode', C.c_int32), ('with_data', C.c_int32), ('with_kl', C.c_int32), ('reserved', C.c_int32),
+                ('jitter', C.c_double), ('pad', C.c_double),
+                ('W', dp), ('L', dp), ('Kuu', dp), ('Z', dp), ('s', dp), ('u', dp), ('v', dp), ('alpha', dp), ('P', dp), ('C1', dp),
+                ('krow', dp), ('a1gm', dp), ('du', dp), ('dsq', dp), ('dLq', dp), ('G', dp), ('tap', dp * len(MXM_TAPS))]
+
+
+FWD_OUTS = ('W', 'v', 'alpha', 'Rt', 'dkinv', 'kl', 'P', 'Qt', 'Wp', 'Wt', 'wh', 'L', 'Kuu')   # include/zigp_diag.h ZIGP_FWD_*
+
+
+class zigp_stage_pack_latent(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('M', C.c_int32), ('reserved', C.c_int32), ('krow', dp), ('du', dp), ('dsq', dp), ('s', dp), ('dLq', dp), ('kl_vec1', dp),
+                ('kl_vec2', dp), ('ell', dp), ('var', C.c_double), ('kl', C.c_double)]
+
+
+class zigp_stage_pack(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('D', C.c_int32), ('mode', C.c_int32), ('need_grad', C.c_int32), ('include_kl', C.c_int32), ('mean_on', C.c_int32),
+                ('pw_blocks', C.c_int32), ('pw', dp), ('lat', zigp_stage_pack_latent * 2), ('out', dp), ('n_out', C.c_int64)]
+
+
 STAGE_SENTINEL = float(np.frombuffer(bytes([0x7f]) * 8, dtype=np.float64)[0])   # ZIGP_STAGE_SENTINEL_BYTE in every byte: 1.38e306
 KG_SPLIT, PW_PTS, PW_ACC = 4, 64, 13   # csrc/zigp_kernels.h
 
@@ -181,6 +205,8 @@ SIGNATURES = {
     'zigp_test_q_full_dlq': (C.c_int, [C.c_void_p, C.c_int32, dp, dp, C.c_int32, dp]),
     'zigp_test_kgrad': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int32, dp]),
     'zigp_test_rank_update': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(dp), C.POINTER(dp), dp, C.POINTER(C.c_int64)]),
+    'zigp_test_mxm_backward': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_mxm)]),
+    'zigp_test_dense_pack': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_pack)]),
 }
 
 _lib = None

@@ -836,15 +836,61 @@ class DenseEngine:
         return outs, dict(paired=f[0], tail_f=f[1], tail_g=f[2], Mp=(f[3], f[4]), np=(f[5], f[6]), np1=(f[7], f[9]), np2=(f[8], f[10]))
 
     def test_latents_forward(self, p, jitter=1e-6, need_grad=True):
-        """What the M x M forward leaves for the chunk loop: [dict(W, v, alpha, Rt or None) for f, g]."""
+        """What the M x M forward of the context's parametrisation leaves (p['whiten'] as in elbo; a full-covariance p is refused):
+        [dict for f, g] with the keys of _lib.FWD_OUTS -- W, L, Kuu, Wt, kl always; unwhitened: v, alpha, dkinv and with need_grad Rt, P, Qt,
+        Wp = W diag(s^2); whitened: wh (3, M) = (s^2 - 1, u, 1) and with need_grad alpha = W^T u, Wp = D W.  Anything else is None."""
+        self._set_modes(p)
         pk = _Packed(p)
+        white = bool(p.get('whiten', False))
+        made = {'W', 'L', 'Kuu', 'Wt', 'kl'} | ({'wh'} if white else {'v', 'alpha', 'dkinv'})
+        if need_grad:
+            made |= {'alpha', 'Wp'} if white else {'Rt', 'P', 'Qt', 'Wp'}
         outs, arrs = [], []
         for M in (pk.Mf, pk.Mg):
-            o = dict(W=np.zeros((M, M)), v=np.zeros(M), alpha=np.zeros(M), Rt=np.zeros((M, M)) if need_grad else None)
+            shape = dict(v=(M,), alpha=(M,), dkinv=(M,), kl=(1,), wh=(3, M))
+            o = {k: np.zeros(shape.get(k, (M, M))) if k in made else None for k in _lib.FWD_OUTS}
             outs.append(o)
-            arrs.append((_lib.dp * 4)(ptr(o['W']), ptr(o['v']), ptr(o['alpha']), ptr(o['Rt']) if need_grad else None))
+            arrs.append((_lib.dp * len(_lib.FWD_OUTS))(*[None if o[k] is None else ptr(o[k]) for k in _lib.FWD_OUTS]))
         _check(self.lib, self.ctx, self.lib.zigp_test_latents_forward(self.ctx, C.byref(pk.struct), float(jitter), int(bool(need_grad)), arrs[0], arrs[1]))
+        for o in outs:
+            o['kl'] = float(o['kl'][0])
         return outs
+
+    def test_dense_pack(self, lat_f, lat_g, pw, D, mode='diag', need_grad=True, include_kl=True, mean_on=False):
+        """The call's result vector from the stages' accumulators (zigp_test_dense_pack).  lat_*: dict(krow [4][M][2+2D], du (M), dsq (M), s (M)
+        -- mode 'white_full': dLq (M,M) instead of dsq and s --, kl_vec1 (M), kl_vec2 (M), ell (D), var, kl); pw [blocks][PW_ACC].
+        Returns dict(data, kl, var_f, var_g, noise, mean_b, mean_a (8), f = dict(dZ, du, ds, dell), g = ..., packed)."""
+        pw = as_f64(pw)
+        a = _lib.zigp_stage_pack()
+        a.D, a.mode, a.need_grad, a.include_kl, a.mean_on, a.pw_blocks = int(D), _lib.MXM_MODES.index(mode), int(bool(need_grad)), int(bool(include_kl)), int(bool(mean_on)), pw.shape[0]
+        a.pw = ptr(pw)
+        full = mode == 'white_full'
+        keep, n, Ms = [], 16, []
+        for h, q in enumerate((lat_f, lat_g)):
+            M = int(np.asarray(q['kl_vec1']).size)
+            Ms.append(M)
+            a.lat[h].M, a.lat[h].var, a.lat[h].kl = M, float(q.get('var', 1.0)), float(q.get('kl', 0.0))
+            shapes = dict(krow=(_lib.KG_SPLIT, M, 2 + 2 * D), du=(M,), dsq=(M,), s=(M,), dLq=(M, M), kl_vec1=(M,), kl_vec2=(M,), ell=(D,))
+            for k, shape in shapes.items():
+                if q.get(k) is not None:
+                    x = as_f64(q[k], shape)
+                    keep.append(x)
+                    setattr(a.lat[h], k, ptr(x))
+            if need_grad:
+                n += M * D + M + (M * M if full else M) + D
+        out = np.zeros(n)
+        a.out, a.n_out = ptr(out), n
+        _check(self.lib, self.ctx, self.lib.zigp_test_dense_pack(self.ctx, C.byref(a)))
+        res = dict(data=out[0], kl=out[1], var_f=out[2], var_g=out[3], noise=out[4], mean_b=out[5], mean_a=out[6:14].copy(), packed=out)
+        if need_grad:
+            off = 16
+            for tag, M in zip('fg', Ms):
+                ns = M * M if full else M
+                res[tag] = dict(dZ=out[off:off + M * D].reshape(M, D), du=out[off + M * D:off + M * D + M],
+                                ds=out[off + M * D + M:off + M * D + M + ns].reshape((M, M) if full else (M,)),
+                                dell=out[off + M * D + M + ns:off + M * D + M + ns + D])
+                off += M * D + M + ns + D
+        return res
 
     def test_pointwise(self, mode, part_f, part_g, np1, np2, X, Y, n0, row_end, var_f, var_g, noise, g_offset=0.0, scale=1.0,
                        mean=None, repeat=1, acc=None, whiten=False):
@@ -927,6 +973,47 @@ class DenseEngine:
         out, plan = np.zeros((M, M)), (C.c_int64 * 2)()
         _check(self.lib, self.ctx, self.lib.zigp_test_rank_update(self.ctx, M, n, Nc, pa, pg, ptr(out), plan))
         return out, (plan[0], plan[1])
+
+    def test_mxm_backward(self, W, L, Kuu, Z, s, alpha, C1=None, Kgm=None, v=None, u=None, P=None, mode='diag', with_data=True, with_kl=True,
+                          jitter=1e-6, krow=None, pad=0.0, taps=True):
+        """The M x M reverse stage of one latent through latent_mxm_backward[_white] (zigp_test_mxm_backward).  mode 'diag' (unwhitened),
+        'white' or 'white_full' (then s is Lq, (M,M)).  krow: the WHOLE device buffer [KG_SPLIT][Mp][2+2D], padded rows included (the sum of
+        column 1 + 2D over the slabs is K gm), or None: zeros with Kgm (M) in slab 0.  P = None: the stage forms W^T W itself.  pad: what
+        the padding of Z, Kuu, s and C1 holds on the device.  Returns dict(a1gm, du, dsq, G, dLq (white_full), krow (whole buffer),
+        taps = {name: (M,M)} of the taps this mode passes (_lib.MXM_TAPS))."""
+        W, L, Kuu, Z = as_f64(W), as_f64(L), as_f64(Kuu), as_f64(Z)
+        if Z.ndim == 1: Z = Z[:, None]
+        M, D = Z.shape
+        Mp, Wd = (M + 127) // 128 * 128, 2 + 2 * D
+        full = mode == 'white_full'
+        a = _lib.zigp_stage_mxm()
+        a.M, a.D, a.mode, a.with_data, a.with_kl = M, D, _lib.MXM_MODES.index(mode), int(bool(with_data)), int(bool(with_kl))
+        a.jitter, a.pad = float(jitter), float(pad)
+        ins = dict(W=as_f64(W, (M, M)), L=as_f64(L, (M, M)), Kuu=as_f64(Kuu, (M, M)), Z=Z, s=as_f64(s, (M, M) if full else (M,)),
+                   alpha=as_f64(alpha, (M,)))
+        for k, x, shape in (('u', u, (M,)), ('v', v, (M,)), ('P', P, (M, M)), ('C1', C1, (M, M))):
+            if x is not None:
+                ins[k] = as_f64(x, shape)
+        if krow is None:
+            krow = np.zeros((_lib.KG_SPLIT, Mp, Wd))
+            if Kgm is not None:
+                krow[0, :M, 1 + 2 * D] = as_f64(Kgm, (M,))
+        out = dict(krow=np.array(as_f64(krow, (_lib.KG_SPLIT, Mp, Wd)), copy=True), a1gm=np.zeros(M), du=np.zeros(M), dsq=np.zeros(M),
+                   G=np.zeros((M, M)))
+        if full:
+            out['dLq'] = np.zeros((M, M))
+        for k, x in list(ins.items()) + list(out.items()):
+            setattr(a, k, ptr(x))
+        if mode == 'diag':
+            names = [t for t in _lib.MXM_TAPS if (with_data or t in ('P', 'PSP')) and (with_kl or t not in ('P', 'PSP')) and (t != 'P' or P is None)]
+        else:
+            names = [t for t in ('C1', 'R', 'dL', 'Q', 'QW', 'S') + (('Y',) if full else ()) if with_data]
+        tp = {t: np.zeros((M, M)) for t in names} if taps else {}
+        for t, x in tp.items():
+            a.tap[_lib.MXM_TAPS.index(t)] = ptr(x)
+        _check(self.lib, self.ctx, self.lib.zigp_test_mxm_backward(self.ctx, C.byref(a)))
+        out['taps'] = tp
+        return out
 
 
 def reference_engine(device=0):
