@@ -54,6 +54,12 @@ int zigp_test_trmm_list(int32_t lower, int32_t Mf, int32_t Mg, int64_t Nc, int32
  * per workgroup, out[2] = entries, then (bi, bj, kbeg, kend, slice) per entry (k in units of 16 rows), as many entries as fit `cap`
  * int64 values.  Returns 0 or ZIGP_EARG. */
 int zigp_test_kgmom_list(int32_t M, int64_t Nc, int64_t cap, int64_t* out);
+/* Host only (no context, no GPU): the split-K tile list of one of the eight k-range rules of the dense M x M stages (SkRule, csrc/zigp_host.h:
+ * 0 "s", 1 "y", 2 "r", 3 "tt", 4 "full", 5 "t", 6 "rt", 7 "rfull") for an nb x nb block product, from the one builder the launcher uploads
+ * from.  out[0] = split-K slices, out[1] = whether the rule's finish pass is lower_only (tiles above the diagonal are not computed and are
+ * stored as zero), out[2] = entries, then (bi, bj, kbeg, kend, slice) per entry (k in units of 16), as many entries as fit `cap` int64
+ * values.  Returns 0, or ZIGP_EARG for an unknown rule, nb <= 0, out == NULL or cap < 3. */
+int zigp_test_sk_list(int32_t rule, int32_t nb, int64_t cap, int64_t* out);
 /* The gradient step of the larger fused grids (<= 16 x <= 112 points) sends its rows through in ranges of `tiles` 16-point tiles
  * (default 1024 = 16 384 rows: the per-point operand records of a range stay within 128 MB).  Results do not depend on it, bit for bit;
  * the tests lower it to run many ranges on small inputs. */
@@ -165,7 +171,7 @@ int zigp_test_q_full_forward(zigp_ctx* ctx, int32_t M, const double* W, const do
 /* Backward: dLq (M,M) = tril(2 C1 Lq) - [include_kl] (tril(Lq) - diag(1 / Lq_ii)) for a symmetric C1 (M,M); strict upper triangle 0. */
 int zigp_test_q_full_dlq(zigp_ctx* ctx, int32_t M, const double* C1, const double* Lq, int32_t include_kl, double* dLq);
 
-/* ---- the M x M reverse stage of ONE latent on caller-supplied operands, through latent_mxm_backward / latent_mxm_backward_white themselves
+/* ---- the M x M reverse stage of ONE latent on caller-supplied operands, through latent_mxm_backward itself
  * (the chain of split-K products, their finishers and the element-wise / reduction kernels between them, then k_kuu_grad[_wide]).  The
  * call's accumulators are sized and zeroed by the step's own path (dense_prepare_buffers) before the operands go in: C1 as the rank-update
  * planes (tril(C1) in plane 0, zeros in the others, so that k_sym_from_planes runs as in a step), krow as given.  The derived images come
@@ -178,7 +184,7 @@ enum {
   ZIGP_MXM_TAP_T = 2,    /* T = (W diag(s^2)) W^T ("tt") */
   ZIGP_MXM_TAP_U = 3,    /* U = T C1 ("full") */
   ZIGP_MXM_TAP_V = 4,    /* V = U + U^T - C1 (k_uut_minus) */
-  ZIGP_MXM_TAP_R = 5,    /* R: W^T V, (W^T D) C1 ("r", lower_up) or (W^T (T - I)) C1 ("rfull", lower_all); lower tiles */
+  ZIGP_MXM_TAP_R = 5,    /* R: W^T V, (W^T D) C1 ("r") or (W^T (T - I)) C1 ("rfull"); lower tiles */
   ZIGP_MXM_TAP_DL = 6,   /* dL (k_dl_assemble) */
   ZIGP_MXM_TAP_Q = 7,    /* Q = Phi(L^T dL) ("r" + SK_PHI) */
   ZIGP_MXM_TAP_QW = 8,   /* Q W ("t"); lower tiles */

@@ -752,3 +752,51 @@ def test_triangular_tile_lists_are_partitions_with_and_without_the_lpt_tail():
         for lower in (1, 0):
             assert lib.zigp_test_trmm_list(lower, Mf, Mg, Nc, 1, out) == 0 and list(out) == want, (Mf, Mg, Nc, lower, list(out))
     assert lib.zigp_test_trmm_list(1, 512, 512, 1000, 1, out) == _lib.ZIGP_EARG      # Nc must be a multiple of 128
+
+
+def test_split_k_rule_table_builds_the_lists_of_the_eight_k_range_rules():
+    """The O(M^3) products of the dense M x M stages run split-K tile lists named by a rule (zigp_host.h SkRule / sk_range / build_sk_list,
+    the only builder run_gemm_sk has).  zigp_test_sk_list returns a rule's slice count, its finish pass's lower_only flag and the list as it
+    is uploaded; here the eight rules are stated once more, independently, as (bi, bj) -> [k0, k1) in units of 16 columns with kb = 8 steps
+    per 128-block, and the whole lists are compared for nb = 1 .. 12 (every block count that M <= 1536 reaches).  No GPU involved."""
+    import ctypes as C
+    from zigp import _lib
+    lib = _lib.load()
+    kb = 8
+    none = (0, 0)
+    rules = [    # (cache key, lower_only, k range)
+        ('s', 0, lambda bi, bj, nb: (max(bi, bj) * kb, nb * kb)),                          # W^T (.) with a lower-triangular right factor or W itself
+        ('y', 0, lambda bi, bj, nb: (bj * kb, nb * kb)),                                   # (.) W, W lower triangular as the right factor: k >= j
+        ('r', 1, lambda bi, bj, nb: (bi * kb, nb * kb) if bj <= bi else none),             # W^T (.), lower tiles only: k >= i
+        ('tt', 0, lambda bi, bj, nb: (0, (min(bi, bj) + 1) * kb)),                         # both factors lower triangular: k <= min(i, j)
+        ('full', 0, lambda bi, bj, nb: (0, nb * kb)),                                      # two dense factors
+        ('t', 1, lambda bi, bj, nb: (bj * kb, (bi + 1) * kb) if bj <= bi else none),       # lower times lower, lower tiles only: j <= k <= i
+        ('rt', 0, lambda bi, bj, nb: (0, (bi + 1) * kb)),                                  # W (.), W lower triangular as the left factor: k <= i
+        ('rfull', 1, lambda bi, bj, nb: (0, nb * kb if bj <= bi else 0)),                  # dense factors, lower tiles only
+    ]
+    cap = 3 + 5 * 8 * 144
+    out = (C.c_int64 * cap)()
+    by_minlen = by_slots = 0
+    for rule, (key, lower_only, krange) in enumerate(rules):
+        for nb in range(1, 13):
+            live = [(bi, bj) + krange(bi, bj, nb) for bi in range(nb) for bj in range(nb)]
+            live = [t for t in live if t[3] > t[2]]
+            minlen = min(k1 - k0 for _, _, k0, k1 in live)
+            S = max(1, min(8, minlen, 512 // len(live)))
+            by_minlen += S == minlen
+            by_slots += S == 512 // len(live) < 8
+            want = [(bi, bj, k0 + (k1 - k0) * s // S, k0 + (k1 - k0) * (s + 1) // S, s) for s in range(S) for bi, bj, k0, k1 in live]
+            assert lib.zigp_test_sk_list(rule, nb, cap, out) == 0, (key, nb)
+            assert (out[0], out[1], out[2]) == (S, lower_only, len(want)), (key, nb, out[0], out[1], out[2])
+            got = [tuple(out[3 + 5 * i:8 + 5 * i]) for i in range(len(want))]
+            assert got == want, (key, nb)
+            if lower_only:      # the finish pass zeroes the tiles above the diagonal: the list must not compute any of them
+                assert all(bj <= bi for bi, bj, _, _, _ in got)
+    assert by_minlen > 0 and by_slots > 0      # both regimes of the slice count: the shortest k range (8 steps) and 512 slots / tiles < 8
+    for bad in (-1, len(rules)):
+        assert lib.zigp_test_sk_list(bad, 4, cap, out) == _lib.ZIGP_EARG
+    assert lib.zigp_test_sk_list(0, 0, cap, out) == _lib.ZIGP_EARG and lib.zigp_test_sk_list(0, 4, cap, None) == _lib.ZIGP_EARG
+    assert lib.zigp_test_sk_list(0, 4, 2, out) == _lib.ZIGP_EARG      # no room for the three header values
+    # a cap between the header and the whole list: the header and the entries that fit, as zigp_test_kgmom_list
+    small = (C.c_int64 * 8)(*([-7] * 8))
+    assert lib.zigp_test_sk_list(0, 4, 8, small) == 0 and small[2] == 8 * 16 and tuple(small[3:8]) == (0, 0, 0, 4, 0)

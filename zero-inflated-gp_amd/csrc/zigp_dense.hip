@@ -57,6 +57,17 @@ static_assert(WIDE_MAXD == ZIGP_MAX_D, "the wide kernels' hyperparameter structs
 
 namespace {
 
+// The variational parametrisation of a call -- the three models of the header comment.  One value travels with the call (DenseCall::par)
+// and every host-side branch reads it; the pair "full covariance without whitening" does not exist (validate_params refuses it).
+enum class Param : int { Diag = 0, White = 1, WhiteFull = 2 };
+constexpr bool is_white(Param p) { return p != Param::Diag; }
+constexpr bool is_full(Param p) { return p == Param::WhiteFull; }
+// the `mode` of zigp_fit_steps_mode and of the stage diagnostics converts by cast, after its range check
+static_assert((int)Param::Diag == ZIGP_FIT_DIAG && (int)Param::White == ZIGP_FIT_WHITE && (int)Param::WhiteFull == ZIGP_FIT_WHITE_FULL,
+              "Param values are the ZIGP_FIT_* modes of include/zigp.h");
+// the context's two settable flags as a Param; validate_params refuses q_full without whiten before any caller gets here
+Param param_of(const zigp_ctx* c) { return !c->whiten ? Param::Diag : c->q_full ? Param::WhiteFull : Param::White; }
+
 struct HostLatent {
   int M; const double *Z, *u, *s, *ell; double var;
 };
@@ -117,9 +128,9 @@ int latents_views(zigp_ctx* c, const size_t (&off)[2][6], int D) {
   }
   return 0;
 }
-// q_full: hl[h].s is the (M, M) row-major block; the image's s slot gets its diagonal (k_kuu_setup squares it, nobody reads the result)
+// WhiteFull: hl[h].s is the (M, M) row-major block; the image's s slot gets its diagonal (k_kuu_setup squares it, nobody reads the result)
 // and the block itself goes to Latent::Lraw, for k_lq_stage (latents_forward) to mask and pad.
-int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D, bool q_full = false) {
+int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D, Param par) {
   size_t off[2][6], total = 0;
   const int M[2] = {hl[0].M, hl[1].M};
   ZIGP_TRY(latents_layout(c, M, D, off, total));
@@ -131,7 +142,7 @@ int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D, bool q_full = 
     memcpy(img + off[h][0], q.Z, sizeof(double) * q.M * D);
     memcpy(img + off[h][1], q.ell, sizeof(double) * D);
     memcpy(img + off[h][2], q.u, sizeof(double) * q.M);
-    if (q_full) for (int m = 0; m < q.M; ++m) img[off[h][3] + m] = q.s[(size_t)m * q.M + m];
+    if (is_full(par)) for (int m = 0; m < q.M; ++m) img[off[h][3] + m] = q.s[(size_t)m * q.M + m];
     else memcpy(img + off[h][3], q.s, sizeof(double) * q.M);
     const KufHypWide kh = make_kuf_hyp_wide(q.ell, q.var, D);
     kgrad_centre(c->lat[h], q.Z, q.ell, q.M, D);
@@ -139,7 +150,7 @@ int latents_upload(zigp_ctx* c, const HostLatent (&hl)[2], int D, bool q_full = 
       for (int d = 0; d < D; ++d) img[off[h][4] + (size_t)m * D + d] = q.Z[(size_t)m * D + d] * kh.scale[d];
   }
   ZIGP_HIP(c, hipMemcpyAsync(c->parm.p, img, sizeof(double) * total, hipMemcpyHostToDevice, c->stream));
-  if (q_full)
+  if (is_full(par))
     for (int h = 0; h < 2; ++h) {
       Latent& lt = c->lat[h];
       const size_t mm = (size_t)hl[h].M * hl[h].M, mmp = (size_t)lt.Mp * lt.Mp;
@@ -163,22 +174,19 @@ int latent_qfull_stage(zigp_ctx* c, Latent& lt) {
 // T - I = Lq Lq^T - I -> P (both factors lower triangular: k <= min(i, j)), then R^T = (T - I) W -> Rt (W lower triangular: k >= j), the
 // image the J' launch reads and the left factor of R C1 in the reverse stage
 int latent_qfull_factors(zigp_ctx* c, Latent& lt) {
-  const int Mp = lt.Mp, nb = Mp / BM, kb = BM / BK;
-  ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_KCONTIG>(c, lt.sk, "tt", nb, [&](int bi, int bj, int& k0, int& k1) { k0 = 0; k1 = (std::min(bi, bj) + 1) * kb; },
-                                                  lt.Lq.p, lt.Lq.p, lt.P.p, Mp, SK_STORE, 1.0, false)));
+  const int Mp = lt.Mp, nb = Mp / BM;
+  ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_KCONTIG>(c, lt.sk, SkRule::TT, nb, lt.Lq.p, lt.Lq.p, lt.P.p, Mp, SK_STORE, 1.0)));
   hipLaunchKernelGGL(k_sub_eye, dim3(ceil_div(Mp, 256)), dim3(256), 0, c->stream, lt.P.p, lt.M, (int64_t)Mp);
   ZIGP_HIP(c, hipGetLastError());
-  return run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "y", nb, [&](int, int bj, int& k0, int& k1) { k0 = bj * kb; k1 = nb * kb; },
-                                                lt.P.p, lt.W.p, lt.Rt.p, Mp, SK_STORE, 1.0, false);
+  return run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, SkRule::Y, nb, lt.P.p, lt.W.p, lt.Rt.p, Mp, SK_STORE, 1.0);
 }
 // dLq = tril(2 C1 Lq) - [kl] (tril(Lq) - diag(1 / Lq_ii)) -> dLq ; C1 in T1 (with_data), Y = C1 Lq -> T3
 int latent_qfull_dlq(zigp_ctx* c, Latent& lt, bool with_data, bool with_kl) {
-  const int Mp = lt.Mp, nb = Mp / BM, kb = BM / BK;
+  const int Mp = lt.Mp, nb = Mp / BM;
   const size_t mm = (size_t)Mp * Mp;
   ZIGP_ENSURE(c, lt.T3, mm); ZIGP_ENSURE(c, lt.dLq, mm);
   if (with_data)
-    ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "y", nb, [&](int, int bj, int& k0, int& k1) { k0 = bj * kb; k1 = nb * kb; },
-                                                     lt.T1.p, lt.Lq.p, lt.T3.p, Mp, SK_STORE, 1.0, false)));
+    ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, SkRule::Y, nb, lt.T1.p, lt.Lq.p, lt.T3.p, Mp, SK_STORE, 1.0)));
   hipLaunchKernelGGL(k_dlq_assemble, dim3(ceil_div((int64_t)mm, 256)), dim3(256), 0, c->stream, lt.T3.p, lt.Lq.p, with_data ? 1 : 0, with_kl ? 1 : 0,
                      lt.M, (int64_t)Mp, lt.dLq.p);
   ZIGP_HIP(c, hipGetLastError());
@@ -191,11 +199,11 @@ int latent_qfull_dlq(zigp_ctx* c, Latent& lt, bool with_data, bool with_kl) {
 // from the start (see potrf_trtri_jobs).
 // d_hyp (fit loop, zigp_fit_steps): the hyperparameters and the pivot tolerances come from this device block (zigp_kernels.h, DH_*), hl
 // carries the sizes only, and latent h reports a failed factorisation in d_info2[h].
-// whiten: W^T, alpha = W^T u (gradient steps), the white KL and the call's whitened vectors (k_kl_white -> Latent::wh) and, for gradient
+// White: W^T, alpha = W^T u (gradient steps), the white KL and the call's whitened vectors (k_kl_white -> Latent::wh) and, for gradient
 // steps, D W = diag(s^2 - 1) W in `Wp`, the factor image of J' = (W^T D) A and of the reverse stage's (W^T D) C1; no v, P, Q or R.
-// q_full (with whiten): the staged factor and its KL in place of k_kl_white, and T - I, R^T in place of D W (latent_qfull_*).
-int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter, bool with_kl, bool need_grad, const double* d_hyp = nullptr,
-                    int* d_info2 = nullptr, bool whiten = false, bool q_full = false) {
+// WhiteFull: the staged factor and its KL in place of k_kl_white, and T - I, R^T in place of D W (latent_qfull_*).
+int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter, Param par, bool with_kl, bool need_grad, const double* d_hyp,
+                    int* d_info2) {
   const hipStream_t st[2] = {c->stream_main, c->stream2};
   for (int h = 0; h < 2; ++h) {
     Latent& lt = c->lat[h];
@@ -231,16 +239,16 @@ int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter
       OnStream on(c, st[h]);
       if (step == 0) lt.P_ready = false;
       double* v = lt.vec.p; double* alpha = v + Mp; double* dkinv = v + 2 * Mp; double* klv = v + 3 * Mp;
-      if (whiten) {
+      if (is_white(par)) {
         switch (step) {
           case 0: hipLaunchKernelGGL(k_transpose, dim3(Mp / 32, Mp / 32), dim3(32, 8), 0, c->stream, lt.W.p, (int64_t)Mp, lt.Wt.p); break;
           case 1:
-            if (q_full) ZIGP_TRY(latent_qfull_stage(c, lt));
+            if (is_full(par)) ZIGP_TRY(latent_qfull_stage(c, lt));
             else hipLaunchKernelGGL(k_kl_white, dim3(1), dim3(256), 0, c->stream, lt.u.p, lt.s.p, lt.M, (int64_t)Mp, lt.wh.p);
             break;
           case 2: if (need_grad) hipLaunchKernelGGL(k_gemv_cols, dim3(Mp / 64), dim3(64, COL_LANES), 0, c->stream, lt.W.p, lt.u.p, (int64_t)Mp, alpha); break;
           case 3:
-            if (need_grad && q_full) ZIGP_TRY(latent_qfull_factors(c, lt));
+            if (need_grad && is_full(par)) ZIGP_TRY(latent_qfull_factors(c, lt));
             else if (need_grad) hipLaunchKernelGGL(k_rowscale, dim3(ceil_div((int64_t)Mp * Mp, 256)), dim3(256), 0, c->stream, lt.W.p, lt.wh.p, (int64_t)Mp, lt.Wp.p);
             break;
           default: break;
@@ -261,9 +269,7 @@ int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter
           break;
         case 5:   // P = W^T W = Kuu^-1 (the reverse M x M stage needs it anyway and takes it from here)
           if (need_grad) {
-            const int nb = Mp / BM, kb = BM / BK;
-            ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "s", nb, [&](int bi, int bj, int& k0, int& k1) { k0 = std::max(bi, bj) * kb; k1 = nb * kb; },
-                                                              lt.W.p, lt.W.p, lt.P.p, Mp, SK_STORE, 1.0, false)));
+            ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, SkRule::S, Mp / BM, lt.W.p, lt.W.p, lt.P.p, Mp, SK_STORE, 1.0)));
             lt.P_ready = true;
           }
           break;
@@ -272,11 +278,7 @@ int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter
           break;
         case 7:   // R^T = W Q^T (W lower triangular: k blocks 0 .. bi): J' = Q (W^T A1) = (Q W^T) A1 reads the A1 panel, so that the A2 panel
                   // has no reader left and is never written (r6; 8 Mp Nc bytes per latent and chunk, the A2 product 66 -> 69 TFLOP/s)
-          if (need_grad) {
-            const int nb = Mp / BM, kb = BM / BK;
-            ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "rt", nb, [&](int bi, int, int& k0, int& k1) { k0 = 0; k1 = (bi + 1) * kb; },
-                                                             lt.W.p, lt.Qt.p, lt.Rt.p, Mp, SK_STORE, 1.0, false)));
-          }
+          if (need_grad) ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, SkRule::RT, Mp / BM, lt.W.p, lt.Qt.p, lt.Rt.p, Mp, SK_STORE, 1.0)));
           break;
         default: break;
       }
@@ -324,11 +326,12 @@ struct ChunkPlan {
   struct Lat { TileSpec a1_spec, a2j_spec, syr_spec, mom_spec; TileList a1, a2j, syr, mom; double fl = 0.0; } lat[2];   // a2j: A2 or J'; fl = M^2 Nc;
                                                                                              // mom: moments product of the wide Kuf gradient (D > MAXD)
 };
-// whiten: A = W K is the same lower-triangular list; a gradient step adds the UPPER-triangular J' = (W^T D) A (the paired / tail lists of
-// A2) and the rank-N update, a value-only or predict pass has no second product at all (a2j stays empty).
-// q_full: the unwhitened lists in both modes -- A and B = Lq^T A are the A1 / A2 pair, J' = R A is the full product.
-ChunkPlan chunk_plan(const int (&M)[2], int64_t Nc, bool need_grad, bool tail_on, bool whiten = false, bool q_full = false, bool wide = false) {
-  if (q_full) whiten = false;
+// Every parametrisation runs A1 = W K on the same lower-triangular list; what follows it is written out per case:
+//   Diag       value-only / predict: A2 = W^T A1, upper-triangular (sums only);  gradient step: J' = (Q W^T) A1 as ONE full product + the rank-N update
+//   White      value-only / predict: no second product at all (a2j stays empty);  gradient step: J' = (W^T D) A, UPPER-triangular (the paired /
+//              tail lists of A2) + the rank-N update
+//   WhiteFull  the lists of Diag in both modes -- A and B = Lq^T A are the A1 / A2 pair, J' = R A is the full product
+ChunkPlan chunk_plan(const int (&M)[2], int64_t Nc, Param par, bool need_grad, bool tail_on, bool wide) {
   ChunkPlan pl;
   const int nbm[2] = {ceil_div(M[0], BM), ceil_div(M[1], BM)}, nbn = (int)(Nc / BN);
   pl.Nc = Nc;
@@ -337,16 +340,15 @@ ChunkPlan chunk_plan(const int (&M)[2], int64_t Nc, bool need_grad, bool tail_on
     pl.tail = trmm_tail_plan((nbn + 7) / 8 * 8 * ((nbm[0] + 1) / 2), nbm[0], (nbn + 7) / 8 * 8 * ((nbm[1] + 1) / 2), nbm[1]);
   for (int h = 0; h < 2; ++h) {
     ChunkPlan::Lat& L = pl.lat[h];
-    L.a1_spec = trmm_tiles(true, nbm[h], nbn, pl.paired, pl.tail.units[h], pl.tail.bins[h]);
-    if (whiten) {
-      if (need_grad) {
-        L.a2j_spec = trmm_tiles(false, nbm[h], nbn, pl.paired, pl.tail.units[h], pl.tail.bins[h]);
-        L.syr_spec = syr2k_tiles(nbm[h], (int)(Nc / BK), syr_plan(nbm[h]));
-      }
-    } else if (need_grad) {
-      L.a2j_spec = full_xcd_tiles(nbm[h], nbn, nbm[h] * (BM / BK));
-      L.syr_spec = syr2k_tiles(nbm[h], (int)(Nc / BK), syr_plan(nbm[h]));
-    } else L.a2j_spec = trmm_tiles(false, nbm[h], nbn, pl.paired, pl.tail.units[h], pl.tail.bins[h]);
+    auto tri = [&](bool lower) { return trmm_tiles(lower, nbm[h], nbn, pl.paired, pl.tail.units[h], pl.tail.bins[h]); };
+    auto full_product = [&] { return full_xcd_tiles(nbm[h], nbn, nbm[h] * (BM / BK)); };
+    L.a1_spec = tri(true);
+    switch (par) {
+      case Param::Diag: L.a2j_spec = need_grad ? full_product() : tri(false); break;
+      case Param::White: if (need_grad) L.a2j_spec = tri(false); break;
+      case Param::WhiteFull: L.a2j_spec = need_grad ? full_product() : tri(false); break;
+    }
+    if (need_grad) L.syr_spec = syr2k_tiles(nbm[h], (int)(Nc / BK), syr_plan(nbm[h]));
     if (need_grad && wide) L.mom_spec = kgmom_tiles(nbm[h], Nc);
     L.fl = (double)M[h] * M[h] * (double)Nc;
   }
@@ -369,9 +371,9 @@ int upload_plan(zigp_ctx* c, ChunkPlan& pl) {
 // with two sets: g's workgroups fill the tail of f's, three launch boundaries fewer per chunk; cfg3 -0.4 ... -0.8 % same-box, profiles/r05l_ab_merge_fg.log,
 // r05s_ab_milestones.log).  In the LPT regime the products stay per latent, in the order A1 A2 / A1 J' (f), then (g) (merged there: cfg2 +1.2 %), and
 // so does the rank-N update everywhere (its 512-workgroup split-K plan fills the chip exactly; merged +0.2 %).
-// q_full (zigp_set_q_full): the same launches on the full-covariance operands -- the mean weights are u (Latent::wh), the second product's
+// WhiteFull (zigp_set_q_full): the same launches on the full-covariance operands -- the mean weights are u (Latent::wh), the second product's
 // factor is Lq (B = Lq^T A, weights 1) or R^T = (T - I) W (J' = R A, latent_qfull_factors wrote it where Q W^T's image lies).
-int chunk_forward(zigp_ctx* c, const ChunkPlan& pl, bool need_grad, const std::function<int()>& after_a1 = nullptr, bool q_full = false) {
+int chunk_forward(zigp_ctx* c, const ChunkPlan& pl, Param par, bool need_grad, const std::function<int()>& after_a1 = nullptr) {
   const int64_t Nc = pl.Nc;
   struct Set { TileList t1, t2; double fl; GemmArgs a1, a2j; EpiStoreColsum e1; EpiColsum e2; EpiStorePanelKColsum ej; } q[3] = {};   // q[2]: none
   for (int h = 0; h < 2; ++h) {
@@ -380,7 +382,7 @@ int chunk_forward(zigp_ctx* c, const ChunkPlan& pl, bool need_grad, const std::f
     q[h].t1 = pl.lat[h].a1; q[h].t2 = pl.lat[h].a2j; q[h].fl = pl.lat[h].fl;
     // A1 = W K ; partial column sums  v^T A1 (= mean, since A2^T u = A1^T W u)  and  sum A1^2
     q[h].a1 = mk_args(lt.Wt.p, Mp, lt.K.p, Nc, lt.A1.p, Nc);
-    q[h].e1 = EpiStoreColsum{q_full ? lt.wh.p + Mp : lt.vec.p, nullptr, lt.part.p, lt.part.p + (size_t)np * Nc};
+    q[h].e1 = EpiStoreColsum{is_full(par) ? lt.wh.p + Mp : lt.vec.p, nullptr, lt.part.p, lt.part.p + (size_t)np * Nc};
     if (need_grad) {
       // J' = Q A2 = (Q W^T) A1, Q = Kuu^-1 diag(s^2) - I (M x M, dense): the two triangular products H = W diag(s^2) A2, J' = W^T H - A2 of the
       // reverse pass as ONE full product of the same flop count -- every tile the full k range (no triangular padding, half as many prologues and
@@ -391,8 +393,8 @@ int chunk_forward(zigp_ctx* c, const ChunkPlan& pl, bool need_grad, const std::f
       q[h].ej = EpiStorePanelKColsum{lt.K.p, lt.part.p + (size_t)2 * np * Nc};
     } else {
       // A2 = W^T A1 ; partial column sums  sum s^2 A2^2 -- the sums only: the panel has no reader (no C; ldc = stride of the partial rows)
-      q[h].a2j = mk_args(q_full ? lt.Lq.p : lt.W.p, Mp, lt.A1.p, Nc, nullptr, Nc);
-      q[h].e2 = EpiColsum{nullptr, q_full ? nullptr : lt.s2.p, nullptr, lt.part.p + (size_t)2 * np * Nc};
+      q[h].a2j = mk_args(is_full(par) ? lt.Lq.p : lt.W.p, Mp, lt.A1.p, Nc, nullptr, Nc);
+      q[h].e2 = EpiColsum{nullptr, is_full(par) ? nullptr : lt.s2.p, nullptr, lt.part.p + (size_t)2 * np * Nc};
     }
   }
   const int groups = pl.paired ? 1 : 2;      // launch groups: merged {f, g}; LPT {f} then {g}
@@ -551,131 +553,107 @@ void launch_kuu_grad(zigp_ctx* c, Latent& lt, int D, double jitter) {
 using MxmTap = std::function<int(int, const double*)>;
 #define ZIGP_TAP(id, buf) do { if (tap) ZIGP_TRY(tap(id, buf)); } while (0)
 
-// MxM backward: G = dELBO/dKuu (symmetric) -> krow accumulators.
-int latent_mxm_backward(zigp_ctx* c, Latent& lt, int D, double jitter, bool with_data, bool with_kl, const MxmTap& tap = nullptr) {
-  const int Mp = lt.Mp, nb = Mp / BM, kb = BM / BK;
-  const size_t mm = (size_t)Mp * Mp;
-  ZIGP_ENSURE(c, lt.T1, mm); ZIGP_ENSURE(c, lt.T2, mm); ZIGP_ENSURE(c, lt.T3, mm); ZIGP_ENSURE(c, lt.G, mm);
-  const int gridmm = ceil_div((int64_t)mm, 256);
-  double* S = lt.T1.p;
-  if (with_data) {
-    TileList ta, tb, tc, td;
-    // rank-1 seeds from K gm (accumulated by k_kgrad): A1 gm = W (K gm), A2 gm = du = W^T (A1 gm)
-    {
-      double* kgm = lt.vec.p + 3 * Mp + 8;
-      hipLaunchKernelGGL(k_gather, dim3(ceil_div(Mp, 256)), dim3(256), 0, c->stream, lt.krow.p, 2 + 2 * D, 1 + 2 * D, Mp, KG_SPLIT,
-                         (int64_t)Mp * (2 + 2 * D), kgm);
-      hipLaunchKernelGGL(k_gemv_rows, dim3(Mp), dim3(256), 0, c->stream, lt.W.p, kgm, (int64_t)Mp, lt.a1gm.p);
-      hipLaunchKernelGGL(k_gemv_cols, dim3(Mp / 64), dim3(64, COL_LANES), 0, c->stream, lt.W.p, lt.a1gm.p, (int64_t)Mp, lt.du.p);
-    }
-    latent_sym_from_planes(c, lt);
-    ZIGP_TAP(ZIGP_MXM_TAP_C1, lt.T1.p);
-    // dsq = diag(A2 G A2^T) = diag(W^T C1 W): Y = C1 W -> T3 ; dsq[m] = sum_k W[k][m] Y[k][m]
-    ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "y", nb, [&](int bi, int bj, int& k0, int& k1) { k0 = bj * kb; k1 = nb * kb; },
-                                                     lt.T1.p, lt.W.p, lt.T3.p, Mp, SK_STORE, 1.0, false)));
-    ZIGP_TAP(ZIGP_MXM_TAP_Y, lt.T3.p);
-    hipLaunchKernelGGL(k_coldot, dim3(Mp / 64), dim3(64, COL_LANES), 0, c->stream, lt.W.p, lt.T3.p, (int64_t)Mp, lt.dsq.p);
-    // T = (W diag(s^2)) W^T -> T2   (both factors lower triangular: k <= min(i,j))
-    ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_KCONTIG>(c, lt.sk, "tt", nb, [&](int bi, int bj, int& k0, int& k1) { k0 = 0; k1 = (std::min(bi, bj) + 1) * kb; },
-                                                    lt.Wp.p, lt.W.p, lt.T2.p, Mp, SK_STORE, 1.0, false)));
-    ZIGP_TAP(ZIGP_MXM_TAP_T, lt.T2.p);
-    // U = T C1 -> T3 ; V = U + U^T - C1 -> G
-    ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "full", nb, [&](int, int, int& k0, int& k1) { k0 = 0; k1 = nb * kb; },
-                                                     lt.T2.p, lt.T1.p, lt.T3.p, Mp, SK_STORE, 1.0, false)));
-    ZIGP_TAP(ZIGP_MXM_TAP_U, lt.T3.p);
-    hipLaunchKernelGGL(k_uut_minus, dim3(gridmm), dim3(256), 0, c->stream, lt.T3.p, lt.T1.p, (int64_t)Mp, lt.G.p);
-    ZIGP_TAP(ZIGP_MXM_TAP_V, lt.G.p);
-    // R = W^T V (lower part) -> T2
-    auto lower_up = [&](int bi, int bj, int& k0, int& k1) { if (bj <= bi) { k0 = bi * kb; k1 = nb * kb; } else { k0 = 0; k1 = 0; } };
-    ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "r", nb, lower_up, lt.W.p, lt.G.p, lt.T2.p, Mp, SK_STORE, 1.0, true)));
-    ZIGP_TAP(ZIGP_MXM_TAP_R, lt.T2.p);
-    // dL = -tril(alpha (A1 gm)^T + (A2 gm) v^T + 2 R) -> T1
-    hipLaunchKernelGGL(k_dl_assemble, dim3(gridmm), dim3(256), 0, c->stream, lt.T2.p, (int64_t)Mp, lt.vec.p + Mp, lt.a1gm.p, lt.du.p,
-                       lt.vec.p, lt.T1.p);
-    ZIGP_TAP(ZIGP_MXM_TAP_DL, lt.T1.p);
-    // Q = Phi(L^T dL) -> T2  (upper tiles are not computed)
-    ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "r", nb, lower_up, lt.L.p, lt.T1.p, lt.T2.p, Mp, SK_PHI, 1.0, true)));
-    ZIGP_TAP(ZIGP_MXM_TAP_Q, lt.T2.p);
-    // T = Q W -> T3 (lower)
-    ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "t", nb, [&](int bi, int bj, int& k0, int& k1) {
-      if (bj <= bi) { k0 = bj * kb; k1 = (bi + 1) * kb; } else { k0 = 0; k1 = 0; } }, lt.T2.p, lt.W.p, lt.T3.p, Mp, SK_STORE, 1.0, true)));
-    ZIGP_TAP(ZIGP_MXM_TAP_QW, lt.T3.p);
-    // S = W^T T -> T1
-    ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "s", nb, [&](int bi, int bj, int& k0, int& k1) { k0 = std::max(bi, bj) * kb; k1 = nb * kb; },
-                                                      lt.W.p, lt.T3.p, lt.T1.p, Mp, SK_STORE, 1.0, false)));
-    ZIGP_TAP(ZIGP_MXM_TAP_S, lt.T1.p);
-  }
-  double* P = lt.P_ready ? lt.P.p : lt.T2.p; double* PSP = lt.G.p;
-  if (with_kl) {
-    // P = W^T W -> T2   (a gradient step has it from the forward stage: latents_forward)
-    if (!lt.P_ready)
-      ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "s", nb, [&](int bi, int bj, int& k0, int& k1) { k0 = std::max(bi, bj) * kb; k1 = nb * kb; },
-                                                        lt.W.p, lt.W.p, lt.T2.p, Mp, SK_STORE, 1.0, false)));
-    if (!lt.P_ready) ZIGP_TAP(ZIGP_MXM_TAP_P, lt.T2.p);
-    // Ps = diag(s2) P -> T3 ; PSP = P Ps -> G
-    hipLaunchKernelGGL(k_rowscale, dim3(gridmm), dim3(256), 0, c->stream, P, lt.s2.p, (int64_t)Mp, lt.T3.p);
-    ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "full", nb, [&](int, int, int& k0, int& k1) { k0 = 0; k1 = nb * kb; },
-                                                     P, lt.T3.p, lt.G.p, Mp, SK_STORE, 1.0, false)));
-    ZIGP_TAP(ZIGP_MXM_TAP_PSP, lt.G.p);
-  }
-  // G = sym(S) - dKL/dKuu -> T3 (T3 free again)
-  hipLaunchKernelGGL(k_sym_combine, dim3(gridmm), dim3(256), 0, c->stream, S, P, PSP, lt.vec.p + Mp, with_data ? 1 : 0, with_kl ? 1 : 0,
-                     (int64_t)Mp, lt.T3.p);
-  launch_kuu_grad(c, lt, D, jitter);
-  ZIGP_HIP(c, hipGetLastError());
+// ---- M x M backward of one latent: G = dELBO/dKuu (symmetric) -> krow accumulators.  Every parametrisation runs the same head (the rank-1
+// seeds and C1) and the same tail (dL -> Phi -> Q W -> S = W^T (Q W)); between them each has its own way to R, the matrix part of dL. ----
+// Head: the rank-1 seeds from K gm (accumulated by k_kgrad): A1 gm = W (K gm) and, unwhitened, A2 gm = du = W^T (A1 gm); then C1 -> T1
+int mxm_backward_head(zigp_ctx* c, Latent& lt, int D, Param par, const MxmTap& tap) {
+  const int Mp = lt.Mp;
+  double* kgm = lt.vec.p + 3 * Mp + 8;
+  hipLaunchKernelGGL(k_gather, dim3(ceil_div(Mp, 256)), dim3(256), 0, c->stream, lt.krow.p, 2 + 2 * D, 1 + 2 * D, Mp, KG_SPLIT,
+                     (int64_t)Mp * (2 + 2 * D), kgm);
+  hipLaunchKernelGGL(k_gemv_rows, dim3(Mp), dim3(256), 0, c->stream, lt.W.p, kgm, (int64_t)Mp, lt.a1gm.p);
+  if (!is_white(par)) hipLaunchKernelGGL(k_gemv_cols, dim3(Mp / 64), dim3(64, COL_LANES), 0, c->stream, lt.W.p, lt.a1gm.p, (int64_t)Mp, lt.du.p);
+  latent_sym_from_planes(c, lt);
+  ZIGP_TAP(ZIGP_MXM_TAP_C1, lt.T1.p);
   return 0;
 }
-
-// MxM backward of a whitened call.  The single triangular solve A = W K leaves  dL = -tril(W^T dA A^T)  with  dA = u gm^T + 2 D A G, i.e.
-//   dL = -tril(alpha (A gm)^T + 2 (W^T D) C1),   C1 = A G A^T (the summed planes of the rank-N updates),  alpha = W^T u,
-// so ONE split-K product (W^T D) C1 replaces the T / U / V / Y chain of the unwhitened stage; then the same Phi / T / S chain, and
-// k_sym_combine without a KL part (the white KL does not depend on Kuu).  du's data part is A gm = W (K gm), ds's is diag(C1);
-// k_dense_pack adds the KL parts from Latent::wh.
-// q_full: ds becomes dLq (latent_qfull_dlq, which also carries the KL part, so it runs without rows too) and the product's left factor
-// is R = W^T (T - I), dense: its image R^T is in Rt and every k block contributes to the lower tiles.
-int latent_mxm_backward_white(zigp_ctx* c, Latent& lt, int D, double jitter, bool with_data, bool q_full = false, bool with_kl = false,
-                              const MxmTap& tap = nullptr) {
-  const int Mp = lt.Mp, nb = Mp / BM, kb = BM / BK;
+// Diag: R = W^T V (lower part) -> T2 with V = T C1 + C1 T - C1, T = (W diag(s^2)) W^T; on the way dsq = diag(A2 G A2^T) = diag(W^T C1 W)
+int mxm_backward_r_diag(zigp_ctx* c, Latent& lt, const MxmTap& tap) {
+  const int Mp = lt.Mp, nb = Mp / BM, gridmm = ceil_div((int64_t)Mp * Mp, 256);
+  // Y = C1 W -> T3 ; dsq[m] = sum_k W[k][m] Y[k][m]
+  ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, SkRule::Y, nb, lt.T1.p, lt.W.p, lt.T3.p, Mp, SK_STORE, 1.0)));
+  ZIGP_TAP(ZIGP_MXM_TAP_Y, lt.T3.p);
+  hipLaunchKernelGGL(k_coldot, dim3(Mp / 64), dim3(64, COL_LANES), 0, c->stream, lt.W.p, lt.T3.p, (int64_t)Mp, lt.dsq.p);
+  // T -> T2
+  ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_KCONTIG>(c, lt.sk, SkRule::TT, nb, lt.Wp.p, lt.W.p, lt.T2.p, Mp, SK_STORE, 1.0)));
+  ZIGP_TAP(ZIGP_MXM_TAP_T, lt.T2.p);
+  // U = T C1 -> T3 ; V = U + U^T - C1 -> G
+  ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, SkRule::FULL, nb, lt.T2.p, lt.T1.p, lt.T3.p, Mp, SK_STORE, 1.0)));
+  ZIGP_TAP(ZIGP_MXM_TAP_U, lt.T3.p);
+  hipLaunchKernelGGL(k_uut_minus, dim3(gridmm), dim3(256), 0, c->stream, lt.T3.p, lt.T1.p, (int64_t)Mp, lt.G.p);
+  ZIGP_TAP(ZIGP_MXM_TAP_V, lt.G.p);
+  ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, SkRule::R, nb, lt.W.p, lt.G.p, lt.T2.p, Mp, SK_STORE, 1.0)));
+  ZIGP_TAP(ZIGP_MXM_TAP_R, lt.T2.p);
+  return 0;
+}
+// White, WhiteFull.  The single triangular solve A = W K leaves  dL = -tril(W^T dA A^T)  with  dA = u gm^T + 2 D A G, i.e.
+//   dL = -tril(alpha (A gm)^T + 2 (W^T D) C1),   C1 = A G A^T,  alpha = W^T u,
+// so ONE split-K product R = (W^T D) C1 (lower part) -> T2 replaces the T / U / V / Y chain; the factor image D W is in Wp (latents_forward).
+// du's data part is A gm = W (K gm), ds's is diag(C1); k_dense_pack adds the KL parts from Latent::wh.
+// WhiteFull: ds becomes dLq (latent_qfull_dlq, which also carries the KL part) and the left factor is R = W^T (T - I), dense: its image
+// R^T is in Rt and every k block contributes to the lower tiles.
+int mxm_backward_r_white(zigp_ctx* c, Latent& lt, Param par, bool with_kl, const MxmTap& tap) {
+  const int Mp = lt.Mp, nb = Mp / BM;
+  if (is_full(par)) {
+    ZIGP_TRY(latent_qfull_dlq(c, lt, true, with_kl));
+    ZIGP_TAP(ZIGP_MXM_TAP_Y, lt.T3.p);      // Y = C1 Lq
+    ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, SkRule::RFULL, nb, lt.Rt.p, lt.T1.p, lt.T2.p, Mp, SK_STORE, 1.0)));
+  } else {
+    hipLaunchKernelGGL(k_diag, dim3(ceil_div(Mp, 256)), dim3(256), 0, c->stream, lt.T1.p, (int64_t)Mp, lt.dsq.p);
+    ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, SkRule::R, nb, lt.Wp.p, lt.T1.p, lt.T2.p, Mp, SK_STORE, 1.0)));
+  }
+  ZIGP_TAP(ZIGP_MXM_TAP_R, lt.T2.p);
+  return 0;
+}
+// Tail: dL = -tril(alpha (A1 gm)^T + r1 r2^T + 2 R) -> T1 ; Q = Phi(L^T dL) -> T2 (upper tiles are not computed) ; T = Q W -> T3 (lower) ;
+// S = W^T T -> T1.  r1, r2: the second rank-1 term, which differs by parametrisation (latent_mxm_backward).
+int mxm_backward_tail(zigp_ctx* c, Latent& lt, const double* r1, const double* r2, const MxmTap& tap) {
+  const int Mp = lt.Mp, nb = Mp / BM;
+  hipLaunchKernelGGL(k_dl_assemble, dim3(ceil_div((int64_t)Mp * Mp, 256)), dim3(256), 0, c->stream, lt.T2.p, (int64_t)Mp, lt.vec.p + Mp, lt.a1gm.p, r1,
+                     r2, lt.T1.p);
+  ZIGP_TAP(ZIGP_MXM_TAP_DL, lt.T1.p);
+  ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, SkRule::R, nb, lt.L.p, lt.T1.p, lt.T2.p, Mp, SK_PHI, 1.0)));
+  ZIGP_TAP(ZIGP_MXM_TAP_Q, lt.T2.p);
+  ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, SkRule::T, nb, lt.T2.p, lt.W.p, lt.T3.p, Mp, SK_STORE, 1.0)));
+  ZIGP_TAP(ZIGP_MXM_TAP_QW, lt.T3.p);
+  ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, SkRule::S, nb, lt.W.p, lt.T3.p, lt.T1.p, Mp, SK_STORE, 1.0)));
+  ZIGP_TAP(ZIGP_MXM_TAP_S, lt.T1.p);
+  return 0;
+}
+int latent_mxm_backward(zigp_ctx* c, Latent& lt, int D, double jitter, Param par, bool with_data, bool with_kl, const MxmTap& tap) {
+  const int Mp = lt.Mp, nb = Mp / BM;
   const size_t mm = (size_t)Mp * Mp;
   ZIGP_ENSURE(c, lt.T1, mm); ZIGP_ENSURE(c, lt.T2, mm); ZIGP_ENSURE(c, lt.T3, mm);
+  if (!is_white(par)) ZIGP_ENSURE(c, lt.G, mm);
   const int gridmm = ceil_div((int64_t)mm, 256);
   if (with_data) {
-    {
-      double* kgm = lt.vec.p + 3 * Mp + 8;
-      hipLaunchKernelGGL(k_gather, dim3(ceil_div(Mp, 256)), dim3(256), 0, c->stream, lt.krow.p, 2 + 2 * D, 1 + 2 * D, Mp, KG_SPLIT,
-                         (int64_t)Mp * (2 + 2 * D), kgm);
-      hipLaunchKernelGGL(k_gemv_rows, dim3(Mp), dim3(256), 0, c->stream, lt.W.p, kgm, (int64_t)Mp, lt.a1gm.p);
+    ZIGP_TRY(mxm_backward_head(c, lt, D, par, tap));
+    if (is_white(par)) ZIGP_TRY(mxm_backward_r_white(c, lt, par, with_kl, tap));
+    else ZIGP_TRY(mxm_backward_r_diag(c, lt, tap));
+    // unwhitened: (A2 gm) v^T; whitened: `du` is zeroed per call and never written, so du du^T switches the term off
+    ZIGP_TRY(mxm_backward_tail(c, lt, lt.du.p, is_white(par) ? lt.du.p : lt.vec.p, tap));
+  } else if (is_full(par)) ZIGP_TRY(latent_qfull_dlq(c, lt, false, with_kl));      // dLq's KL part needs no rows
+  if (is_white(par)) {
+    // G = sym(S) -> T3 : no KL part (the white KL does not depend on Kuu)
+    hipLaunchKernelGGL(k_sym_combine, dim3(gridmm), dim3(256), 0, c->stream, lt.T1.p, lt.T1.p, lt.T1.p, lt.vec.p + Mp, with_data ? 1 : 0, 0,
+                       (int64_t)Mp, lt.T3.p);
+  } else {
+    double* P = lt.P_ready ? lt.P.p : lt.T2.p; double* PSP = lt.G.p;
+    if (with_kl) {
+      // P = W^T W -> T2   (a gradient step has it from the forward stage: latents_forward)
+      if (!lt.P_ready) {
+        ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, SkRule::S, nb, lt.W.p, lt.W.p, lt.T2.p, Mp, SK_STORE, 1.0)));
+        ZIGP_TAP(ZIGP_MXM_TAP_P, lt.T2.p);
+      }
+      // Ps = diag(s2) P -> T3 ; PSP = P Ps -> G
+      hipLaunchKernelGGL(k_rowscale, dim3(gridmm), dim3(256), 0, c->stream, P, lt.s2.p, (int64_t)Mp, lt.T3.p);
+      ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, SkRule::FULL, nb, P, lt.T3.p, lt.G.p, Mp, SK_STORE, 1.0)));
+      ZIGP_TAP(ZIGP_MXM_TAP_PSP, lt.G.p);
     }
-    latent_sym_from_planes(c, lt);      // C1 -> T1
-    ZIGP_TAP(ZIGP_MXM_TAP_C1, lt.T1.p);
-    if (q_full) {
-      ZIGP_TRY(latent_qfull_dlq(c, lt, true, with_kl));
-      ZIGP_TAP(ZIGP_MXM_TAP_Y, lt.T3.p);      // Y = C1 Lq
-    } else hipLaunchKernelGGL(k_diag, dim3(ceil_div(Mp, 256)), dim3(256), 0, c->stream, lt.T1.p, (int64_t)Mp, lt.dsq.p);
-    // R = (W^T D) C1 (lower part) -> T2 ; the factor image D W is in Wp (latents_forward)
-    auto lower_up = [&](int bi, int bj, int& k0, int& k1) { if (bj <= bi) { k0 = bi * kb; k1 = nb * kb; } else { k0 = 0; k1 = 0; } };
-    auto lower_all = [&](int bi, int bj, int& k0, int& k1) { k0 = 0; k1 = bj <= bi ? nb * kb : 0; };
-    if (q_full) ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "rfull", nb, lower_all, lt.Rt.p, lt.T1.p, lt.T2.p, Mp, SK_STORE, 1.0, true)));
-    else ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "r", nb, lower_up, lt.Wp.p, lt.T1.p, lt.T2.p, Mp, SK_STORE, 1.0, true)));
-    ZIGP_TAP(ZIGP_MXM_TAP_R, lt.T2.p);
-    // dL = -tril(alpha (A gm)^T + 2 R) -> T1 ; the second rank-1 term of k_dl_assemble is switched off by the zero vector `du` (zeroed per
-    // call and never written in this mode)
-    hipLaunchKernelGGL(k_dl_assemble, dim3(gridmm), dim3(256), 0, c->stream, lt.T2.p, (int64_t)Mp, lt.vec.p + Mp, lt.a1gm.p, lt.du.p,
-                       lt.du.p, lt.T1.p);
-    ZIGP_TAP(ZIGP_MXM_TAP_DL, lt.T1.p);
-    // Q = Phi(L^T dL) -> T2 ; T = Q W -> T3 (lower) ; S = W^T T -> T1
-    ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "r", nb, lower_up, lt.L.p, lt.T1.p, lt.T2.p, Mp, SK_PHI, 1.0, true)));
-    ZIGP_TAP(ZIGP_MXM_TAP_Q, lt.T2.p);
-    ZIGP_TRY((run_gemm_sk<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.sk, "t", nb, [&](int bi, int bj, int& k0, int& k1) {
-      if (bj <= bi) { k0 = bj * kb; k1 = (bi + 1) * kb; } else { k0 = 0; k1 = 0; } }, lt.T2.p, lt.W.p, lt.T3.p, Mp, SK_STORE, 1.0, true)));
-    ZIGP_TAP(ZIGP_MXM_TAP_QW, lt.T3.p);
-    ZIGP_TRY((run_gemm_sk<LAY_MNCONTIG, LAY_MNCONTIG>(c, lt.sk, "s", nb, [&](int bi, int bj, int& k0, int& k1) { k0 = std::max(bi, bj) * kb; k1 = nb * kb; },
-                                                      lt.W.p, lt.T3.p, lt.T1.p, Mp, SK_STORE, 1.0, false)));
-    ZIGP_TAP(ZIGP_MXM_TAP_S, lt.T1.p);
-  } else if (q_full) ZIGP_TRY(latent_qfull_dlq(c, lt, false, with_kl));
-  // G = sym(S) -> T3
-  hipLaunchKernelGGL(k_sym_combine, dim3(gridmm), dim3(256), 0, c->stream, lt.T1.p, lt.T1.p, lt.T1.p, lt.vec.p + Mp, with_data ? 1 : 0, 0,
-                     (int64_t)Mp, lt.T3.p);
+    // G = sym(S) - dKL/dKuu -> T3 (T3 free again)
+    hipLaunchKernelGGL(k_sym_combine, dim3(gridmm), dim3(256), 0, c->stream, lt.T1.p, P, PSP, lt.vec.p + Mp, with_data ? 1 : 0, with_kl ? 1 : 0,
+                       (int64_t)Mp, lt.T3.p);
+  }
   launch_kuu_grad(c, lt, D, jitter);
   ZIGP_HIP(c, hipGetLastError());
   return 0;
@@ -713,9 +691,9 @@ struct DenseCall {
   const zigp_params* p; const double* dX; const double* dY; int64_t Nrows; int D;
   double jitter, scale, g_offset; int64_t row_begin, row_end; int include_kl; bool predict; double* d_out9;
   bool need_grad, has_rows;
-  bool whiten = false;    // the context's zigp_set_whiten at the time of the call (run_dense)
-  bool q_full = false;    // the context's zigp_set_q_full (validate_params: only with whiten)
-  bool tri_pack = false;  // q_full in the fit loop: dLq leaves as its lower triangle, M (M + 1) / 2 entries (k_pack_tril), not as the (M, M) block
+  Param par = Param::Diag;      // the context's zigp_set_whiten / zigp_set_q_full at the time of the call (run_dense), or the fit loop's mode
+  bool dlq_as_triangle = false; // packing choice of the fit loop, not a parametrisation: a WhiteFull step's dLq leaves as its lower triangle,
+                                // M (M + 1) / 2 entries (k_pack_tril), not as the (M, M) block zigp_elbo returns
   HostLatent hl[2]; const double* ell_h[2];
   int64_t Nc = 0;         // rows per full chunk
   ChunkPlan plan[2];      // the full chunk and, if smaller, the last one (run_dense)
@@ -736,7 +714,7 @@ int dense_mxm_forward(zigp_ctx* c, DenseCall& k) {
   else {
     ZIGP_TRY(begin_staged_call(c));
     ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
-    ZIGP_TRY(latents_upload(c, k.hl, k.D, k.q_full));
+    ZIGP_TRY(latents_upload(c, k.hl, k.D, k.par));
   }
   // The call's buffers, its zeroed accumulators and the first chunk's Kuf panels need the uploaded parameters only: third stream, under
   // the two factorisation chains (which are dependent launches of <= 36 workgroups).  Not while kernels are being timed (they run alone).
@@ -753,7 +731,7 @@ int dense_mxm_forward(zigp_ctx* c, DenseCall& k) {
   {
     ProfScope ps(c, PC_MXM);     // wall time of the two concurrent chains: both events on the main stream, the second after the join
     ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
-    ZIGP_TRY(latents_forward(c, k.hl, k.D, k.jitter, true, k.need_grad, k.d_hyp, k.d_info2, k.whiten, k.q_full));
+    ZIGP_TRY(latents_forward(c, k.hl, k.D, k.jitter, k.par, true, k.need_grad, k.d_hyp, k.d_info2));
     ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   }
   return k.d_hyp ? 0 : request_info(c, &k.hinfo);   // read after the final synchronisation
@@ -796,7 +774,7 @@ int dense_prepare_buffers(zigp_ctx* c, DenseCall& k) {
     ZIGP_ENSURE(c, lt.gm, Nc); ZIGP_ENSURE(c, lt.gv, Nc);
     if (k.has_rows) {
       ZIGP_ENSURE(c, lt.K, (size_t)Mp * Nc);
-      if (!k.whiten || k.need_grad || k.q_full) ZIGP_ENSURE(c, lt.A1, (size_t)Mp * Nc);     // a whitened (diagonal) value-only / predict pass stores no panel but K
+      if (k.par != Param::White || k.need_grad) ZIGP_ENSURE(c, lt.A1, (size_t)Mp * Nc);     // a whitened (diagonal) value-only / predict pass stores no panel but K
       ZIGP_ENSURE(c, lt.part, (size_t)3 * (Mp / 32) * Nc);
       if (k.need_grad) ZIGP_ENSURE(c, lt.Jp, (size_t)Mp * Nc);
       if (k.need_grad && D > MAXD && !lt.kg_exact) ZIGP_TRY(ensure_kgrad_wide(c, lt, Nc));
@@ -832,23 +810,25 @@ PwArgs dense_pointwise_args(zigp_ctx* c, const DenseCall& k, int64_t n0, int64_t
   a.acc = c->pw_part.p; a.out9 = k.d_out9 ? k.d_out9 - k.row_begin : nullptr; a.ld9 = k.row_end - k.row_begin;
   return a;
 }
-int dense_pointwise_launch(zigp_ctx* c, bool predict, bool need_grad, const PwArgs& a, const double* d_hyp = nullptr, bool whiten = false) {
+// k_pointwise<predict, plane-2 variance form>: the variance is var0 + (plane 2) instead of var0 - (plane 1) + (plane 2).  That form holds for
+//   a gradient step   -- Diag, WhiteFull: plane 2 = sum_m K J' (the J' epilogue); a predict pass is never one
+//   a fit-loop step   -- d_hyp: always a gradient step, through the overload that reads the device hyperparameter block
+//   a White call      -- plane 2 = sum (s^2 - 1) A^2 in every mode (chunk_forward_white); a value-only pass has gm_f = NULL and writes no cotangents
+// (a WhiteFull value-only / predict call is the unwhitened form: var0 - sum A^2 + sum B^2)
+int dense_pointwise_launch(zigp_ctx* c, Param par, bool predict, bool need_grad, const PwArgs& a, const double* d_hyp) {
   ProfScope ps(c, PC_POINT);
-  const int nblk = (int)(a.Nc / PW_PTS);
-  if (whiten && d_hyp) hipLaunchKernelGGL((k_pointwise<false, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a, d_hyp);     // a whitened step of the fit loop
-  else if (whiten) {     // var = var0 + (plane 2) in every mode (chunk_forward_white); a value-only pass has gm_f = NULL and writes no cotangents
-    if (predict) hipLaunchKernelGGL((k_pointwise<true, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
-    else hipLaunchKernelGGL((k_pointwise<false, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
-  } else if (d_hyp) hipLaunchKernelGGL((k_pointwise<false, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a, d_hyp);     // a gradient step of the fit loop
-  else if (predict) hipLaunchKernelGGL((k_pointwise<true, false>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
-  else if (need_grad) hipLaunchKernelGGL((k_pointwise<false, true>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);   // variance from sum K J'
-  else hipLaunchKernelGGL((k_pointwise<false, false>), dim3(nblk), dim3(PW_THREADS), 0, c->stream, a);
+  const dim3 grid((unsigned)(a.Nc / PW_PTS)), block(PW_THREADS);
+  const bool plane2 = need_grad || d_hyp || par == Param::White;
+  if (d_hyp) hipLaunchKernelGGL((k_pointwise<false, true>), grid, block, 0, c->stream, a, d_hyp);
+  else if (predict && plane2) hipLaunchKernelGGL((k_pointwise<true, true>), grid, block, 0, c->stream, a);
+  else if (predict) hipLaunchKernelGGL((k_pointwise<true, false>), grid, block, 0, c->stream, a);
+  else if (plane2) hipLaunchKernelGGL((k_pointwise<false, true>), grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL((k_pointwise<false, false>), grid, block, 0, c->stream, a);
   ZIGP_HIP(c, hipGetLastError());
   return 0;
 }
 int dense_pointwise(zigp_ctx* c, const DenseCall& k, int64_t n0, int64_t Nc) {
-  // a full-covariance call is the unwhitened forms: var0 - plane 1 + plane 2 (value-only, predict), var0 + plane 2 (gradient step)
-  return dense_pointwise_launch(c, k.predict, k.need_grad, dense_pointwise_args(c, k, n0, Nc), k.d_hyp, k.whiten && !k.q_full);
+  return dense_pointwise_launch(c, k.par, k.predict, k.need_grad, dense_pointwise_args(c, k, n0, Nc), k.d_hyp);
 }
 
 // ---- chunk loop.  The MFMA-bound GEMMs stay on the main stream; with zigp_set_overlap(1) the HBM-bound kernels of a chunk -- the two
@@ -911,15 +891,12 @@ int dense_chunk_loop(zigp_ctx* c, const DenseCall& k) {
     std::function<int()> after_a1;
     if (kuf_fwd_side) after_a1 = [&] { return on_side([&] { return kuf(n1); }); };
     const ChunkPlan& pl = k.plan[Nc == k.plan[0].Nc ? 0 : 1];
-    if (k.q_full) {     // A (f|g), then B = Lq^T A (sums only) or J' = R A, then the point-wise stage: the unwhitened order
-      ZIGP_TRY(chunk_forward(c, pl, k.need_grad, after_a1, true));
-      ZIGP_TRY(dense_pointwise(c, k, n0, Nc));
-    } else if (k.whiten) {     // A (f|g), point-wise (it needs the A launch only), then J' (f|g) of a gradient step
+    if (k.par == Param::White) {     // A (f|g), point-wise (it needs the A launch only), then J' (f|g) of a gradient step
       ZIGP_TRY(chunk_forward_white(c, pl, k.need_grad, false, after_a1));
       ZIGP_TRY(dense_pointwise(c, k, n0, Nc));
       if (k.need_grad) ZIGP_TRY(chunk_forward_white(c, pl, true, true));
-    } else {
-      ZIGP_TRY(chunk_forward(c, pl, k.need_grad, after_a1));
+    } else {     // Diag: A1 (f|g), then A2 (sums only) or J'; WhiteFull: the same order -- A, then B = Lq^T A (sums only) or J' = R A
+      ZIGP_TRY(chunk_forward(c, pl, k.par, k.need_grad, after_a1));
       // the point-wise stage of a gradient step needs the J' launch's sums (it rode inside the J' launch while the variance came from A2:
       // r5, profiles/r05t_ab_fuse_pointwise.log), so it is a launch of its own after it
       ZIGP_TRY(dense_pointwise(c, k, n0, Nc));
@@ -958,9 +935,9 @@ int dense_pack(zigp_ctx* c, const DenseCall& k, DensePackArgs& a, size_t& n) {
     DensePackLat& L = a.lat[h];
     L.krow = lt.krow.p; L.du = lt.du.p; L.dsq = lt.dsq.p; L.vec = lt.vec.p; L.s = lt.s.p; L.ell = lt.ell.p;
     // whitened: du's data part is A gm, the KL parts and the KL value come from the whitened vectors (k_kl_white keeps vec's layout)
-    if (k.whiten) { L.du = lt.a1gm.p; L.vec = lt.wh.p; }
-    L.M = lt.M; L.Mp = lt.Mp; L.var = lt.var; L.out_off = (int64_t)n; L.q_full = k.q_full ? 1 : 0;
-    L.ns = !k.q_full ? (int64_t)lt.M : k.tri_pack ? (int64_t)lt.M * (lt.M + 1) / 2 : (int64_t)lt.M * lt.M;
+    if (is_white(k.par)) { L.du = lt.a1gm.p; L.vec = lt.wh.p; }
+    L.M = lt.M; L.Mp = lt.Mp; L.var = lt.var; L.out_off = (int64_t)n; L.q_full = is_full(k.par) ? 1 : 0;
+    L.ns = !is_full(k.par) ? (int64_t)lt.M : k.dlq_as_triangle ? (int64_t)lt.M * (lt.M + 1) / 2 : (int64_t)lt.M * lt.M;
     if (k.need_grad) n += (size_t)lt.M * D + (size_t)lt.M + (size_t)L.ns + D;
   }
   a.pw = c->pw_part.p; a.pw_blocks = k.pw_blocks; a.D = D; a.need_grad = k.need_grad ? 1 : 0; a.include_kl = k.include_kl ? 1 : 0;
@@ -969,12 +946,12 @@ int dense_pack(zigp_ctx* c, const DenseCall& k, DensePackArgs& a, size_t& n) {
   a.out = c->packed.p;
   if (k.d_hyp) hipLaunchKernelGGL(k_dense_pack<const double*>, dim3(2), dim3(256), 0, c->stream, a, k.d_hyp);
   else hipLaunchKernelGGL(k_dense_pack<>, dim3(2), dim3(256), 0, c->stream, a);
-  if (k.need_grad && k.q_full)
+  if (k.need_grad && is_full(k.par))
     for (int h = 0; h < 2; ++h) {     // the (M, M) blocks, behind du
       const Latent& lt = c->lat[h];
       double* os = a.out + a.lat[h].out_off + (int64_t)lt.M * D + lt.M;
       const dim3 grid(ceil_div((int64_t)lt.M * lt.M, 256));
-      if (k.tri_pack) hipLaunchKernelGGL(k_pack_tril, grid, dim3(256), 0, c->stream, lt.dLq.p, lt.M, (int64_t)lt.Mp, os);
+      if (k.dlq_as_triangle) hipLaunchKernelGGL(k_pack_tril, grid, dim3(256), 0, c->stream, lt.dLq.p, lt.M, (int64_t)lt.Mp, os);
       else hipLaunchKernelGGL(k_pack_square, grid, dim3(256), 0, c->stream, lt.dLq.p, lt.M, (int64_t)lt.Mp, os);
     }
   ZIGP_HIP(c, hipGetLastError());
@@ -1005,7 +982,7 @@ int dense_gather(zigp_ctx* c, DenseCall& k, double* elbo_data, double* kl, zigp_
       const double* o = hv + a.lat[h].out_off;
       if (gZ[h]) memcpy(gZ[h], o, sizeof(double) * M * D);
       if (gu[h]) memcpy(gu[h], o + M * D, sizeof(double) * M);
-      const size_t ns = k.q_full ? M * M : M;
+      const size_t ns = is_full(k.par) ? M * M : M;
       if (gs[h]) memcpy(gs[h], o + M * D + M, sizeof(double) * ns);
       if (gl[h]) memcpy(gl[h], o + M * D + M + ns, sizeof(double) * D);
     }
@@ -1021,9 +998,9 @@ int dense_plan(zigp_ctx* c, DenseCall& k) {
   k.Nc = chunk_rows_for(c->chunk_auto, c->chunk, round_up(std::max(M[0], M[1]), BM), span);
   if (k.has_rows) {
     const int64_t last = std::min<int64_t>(k.Nc, round_up(span - (span - 1) / k.Nc * k.Nc, 1024));
-    k.plan[0] = chunk_plan(M, k.Nc, k.need_grad, c->trmm_tail, k.whiten, k.q_full, k.D > MAXD);
+    k.plan[0] = chunk_plan(M, k.Nc, k.par, k.need_grad, c->trmm_tail, k.D > MAXD);
     ZIGP_TRY(upload_plan(c, k.plan[0]));
-    if (last != k.Nc) { k.plan[1] = chunk_plan(M, last, k.need_grad, c->trmm_tail, k.whiten, k.q_full, k.D > MAXD); ZIGP_TRY(upload_plan(c, k.plan[1])); }
+    if (last != k.Nc) { k.plan[1] = chunk_plan(M, last, k.par, k.need_grad, c->trmm_tail, k.D > MAXD); ZIGP_TRY(upload_plan(c, k.plan[1])); }
   }
   return 0;
 }
@@ -1041,8 +1018,7 @@ int dense_step(zigp_ctx* c, DenseCall& k) {
     ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
     for (int h = 0; h < 2; ++h) {
       OnStream on(c, h == 0 ? c->stream_main : c->stream2);
-      if (k.whiten) ZIGP_TRY(latent_mxm_backward_white(c, c->lat[h], k.D, k.jitter, k.has_rows, k.q_full, k.include_kl != 0));
-      else ZIGP_TRY(latent_mxm_backward(c, c->lat[h], k.D, k.jitter, k.has_rows, k.include_kl != 0));
+      ZIGP_TRY(latent_mxm_backward(c, c->lat[h], k.D, k.jitter, k.par, k.has_rows, k.include_kl != 0, nullptr));
     }
     ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   }
@@ -1058,7 +1034,7 @@ int run_dense(zigp_ctx* c, const zigp_params* p, const double* dX, const double*
   k.row_begin = row_begin; k.row_end = row_end; k.include_kl = include_kl; k.predict = predict; k.d_out9 = d_out9;
   k.need_grad = (grads != nullptr) && !predict;
   k.has_rows = row_end > row_begin;
-  k.whiten = c->whiten; k.q_full = c->q_full;
+  k.par = param_of(c);
   k.hl[0] = HostLatent{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f};
   k.hl[1] = HostLatent{p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g};
   k.ell_h[0] = p->ell_f; k.ell_h[1] = p->ell_g;
@@ -1265,7 +1241,7 @@ static_assert(DFIT_BLOCKS == ZIGP_DENSE_FIT_BLOCKS, "block order of include/zigp
 }  // extern "C"
 namespace {
 // One loop for the three parametrisations (include/zigp.h ZIGP_FIT_*).  `mode` decides the layout of blocks 4 and 5, the image kernels and
-// DenseCall::whiten / q_full, i.e. which chunk lists dense_plan plans and which launches dense_step makes; `legacy` is zigp_fit_steps, which
+// DenseCall::par, i.e. which chunk lists dense_plan plans and which launches dense_step makes; `legacy` is zigp_fit_steps, which
 // refuses while the context's own whiten / q_full flags are on -- zigp_fit_steps_mode neither reads nor changes them.
 int dense_fit_steps(zigp_ctx* c, int32_t mode, bool legacy, const zigp_params* shape, const zigp_fit_opts* o, double* free_state, double* adam_m,
                     double* adam_v, int64_t n_free, int64_t t0, int32_t n_steps, const int64_t* rows, int64_t batch, double jitter, double scale,
@@ -1277,7 +1253,8 @@ int dense_fit_steps(zigp_ctx* c, int32_t mode, bool legacy, const zigp_params* s
   if (!shape || !o || !free_state || !adam_m || !adam_v) return bad("NULL argument");
   if (mode != ZIGP_FIT_DIAG && mode != ZIGP_FIT_WHITE && mode != ZIGP_FIT_WHITE_FULL)
     return bad("unknown mode (ZIGP_FIT_DIAG, ZIGP_FIT_WHITE, ZIGP_FIT_WHITE_FULL)");
-  const bool white = mode != ZIGP_FIT_DIAG, full = mode == ZIGP_FIT_WHITE_FULL;
+  const Param par = (Param)mode;
+  const bool tri = is_full(par);     // blocks 4, 5 and the packed dLq: the lower triangle of the factor
   if (shape->Mf <= 0 || shape->Mg <= 0 || shape->D <= 0) return bad("need Mf, Mg > 0 and D >= 1");
   if (shape->D > MAXD)
     return bad(("D = " + std::to_string(shape->D) + ": the device fit loop covers D in [1, 8] (zigp_elbo + a host optimiser fit every D up to " ZIGP_MAX_D_STR ")").c_str());
@@ -1304,7 +1281,7 @@ int dense_fit_steps(zigp_ctx* c, int32_t mode, bool legacy, const zigp_params* s
   DenseFitDesc& d = fa.d;
   {
     // blocks 4, 5: the diagonal's M entries, or the M (M + 1) / 2 of Lq's lower triangle in row-major order (identity transform)
-    const int64_t ns64[2] = {full ? (int64_t)M[0] * (M[0] + 1) / 2 : M[0], full ? (int64_t)M[1] * (M[1] + 1) / 2 : M[1]};
+    const int64_t ns64[2] = {tri ? (int64_t)M[0] * (M[0] + 1) / 2 : M[0], tri ? (int64_t)M[1] * (M[1] + 1) / 2 : M[1]};
     if ((int64_t)(M[0] + M[1]) * (D + 1) + ns64[0] + ns64[1] + 2 * D + 3 > ((int64_t)1 << 30)) return bad("the free state exceeds 2^30 entries");
     const int ns[2] = {(int)ns64[0], (int)ns64[1]};
     const int sizes[DFIT_BLOCKS] = {M[0] * D, M[1] * D, M[0], M[1], ns[0], ns[1], es[0], es[1], 1, 1, 1};
@@ -1315,9 +1292,9 @@ int dense_fit_steps(zigp_ctx* c, int32_t mode, bool legacy, const zigp_params* s
     }
     d.off[DFIT_BLOCKS] = off;
     if ((int64_t)off != n_free) return bad("n_free does not match the model sizes");
-    if (full && (o->positive[4] != 0 || o->positive[5] != 0))
+    if (tri && (o->positive[4] != 0 || o->positive[5] != 0))
       return bad("positive[4] / positive[5] must be 0 for ZIGP_FIT_WHITE_FULL (the diagonal of a full factor is unconstrained)");
-    if (full)     // a zero diagonal entry: the KL's log is not finite
+    if (tri)     // a zero diagonal entry: the KL's log is not finite
       for (int h = 0; h < 2; ++h)
         for (int64_t i = 0; i < M[h]; ++i)
           if (free_state[d.off[4 + h] + i * (i + 1) / 2 + i] == 0.0)
@@ -1331,7 +1308,7 @@ int dense_fit_steps(zigp_ctx* c, int32_t mode, bool legacy, const zigp_params* s
     }
     d.goff[8] = 2; d.goff[9] = 3; d.goff[10] = 4;
   }
-  d.tri = full ? 1 : 0;
+  d.tri = tri ? 1 : 0;
   d.D = D; d.M[0] = M[0]; d.M[1] = M[1];
   d.beta1 = o->beta1; d.beta2 = o->beta2; d.eps = o->eps; d.jitter = jitter; d.rtol_eps = c->pivot_rtol * 2.220446049250313e-16;
   ZIGP_HIP(c, hipSetDevice(c->device));
@@ -1343,7 +1320,7 @@ int dense_fit_steps(zigp_ctx* c, int32_t mode, bool legacy, const zigp_params* s
   DenseCall k;
   k.p = &sizes_only; k.D = D; k.jitter = jitter; k.scale = scale; k.g_offset = 0.0; k.include_kl = include_kl; k.predict = false; k.d_out9 = nullptr;
   k.need_grad = true; k.has_rows = true; k.row_begin = 0;
-  k.whiten = white; k.q_full = full; k.tri_pack = full;
+  k.par = par; k.dlq_as_triangle = tri;
   k.hl[0] = HostLatent{M[0], nullptr, nullptr, nullptr, nullptr, 0.0}; k.hl[1] = HostLatent{M[1], nullptr, nullptr, nullptr, nullptr, 0.0};
   k.ell_h[0] = k.ell_h[1] = nullptr;
   const int64_t nidx = rows ? (int64_t)n_steps * batch : 0;
@@ -1370,7 +1347,7 @@ int dense_fit_steps(zigp_ctx* c, int32_t mode, bool legacy, const zigp_params* s
     lt.var = 0.0;            // not read: the kernels take it from the block
     lt.kg_exact = true;      // the per-row form of k_kgrad: the centred form needs a centre chosen from Z and ell, which move on the device
     for (int q = 0; q < WIDE_MAXD; ++q) lt.zc[q] = 0.0;
-    if (full) {     // the M x M buffers of the full factor (latents_upload / latent_qfull_dlq size them for zigp_elbo): before the first step
+    if (tri) {     // the M x M buffers of the full factor (latents_upload / latent_qfull_dlq size them for zigp_elbo): before the first step
       const size_t mm = (size_t)M[h] * M[h], mmp = (size_t)lt.Mp * lt.Mp;
       ZIGP_ENSURE(c, lt.Lraw, mm); ZIGP_ENSURE(c, lt.Lq, mmp); ZIGP_ENSURE(c, lt.lqssq, mmp / 256); ZIGP_ENSURE(c, lt.T3, mmp); ZIGP_ENSURE(c, lt.dLq, mmp);
     }
@@ -1394,7 +1371,7 @@ int dense_fit_steps(zigp_ctx* c, int32_t mode, bool legacy, const zigp_params* s
   const dim3 tgrid(ceil_div((int64_t)std::max(M[0], M[1]) * std::max(M[0], M[1]), DFIT_THREADS), 2);
   auto image = [&]() {     // free state -> parameter image, hyperparameter block and, for full factors, the two Lraw blocks
     hipLaunchKernelGGL(k_dense_fit_image, ugrid, dim3(DFIT_THREADS), 0, c->stream, d, fa.x, c->parm.p, H);
-    if (full) hipLaunchKernelGGL(k_dense_fit_image_tri, tgrid, dim3(DFIT_THREADS), 0, c->stream, d, fa.x, c->parm.p, c->lat[0].Lraw.p, c->lat[1].Lraw.p);
+    if (tri) hipLaunchKernelGGL(k_dense_fit_image_tri, tgrid, dim3(DFIT_THREADS), 0, c->stream, d, fa.x, c->parm.p, c->lat[0].Lraw.p, c->lat[1].Lraw.p);
   };
   image();
   ZIGP_HIP(c, hipGetLastError());
@@ -1490,13 +1467,14 @@ int zigp_prior_kl(zigp_ctx* c, const zigp_params* p, double jitter, double* kl2)
   HostLatent hl[2] = {{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f}, {p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g}};
   ZIGP_TRY(begin_staged_call(c));
   ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
-  ZIGP_TRY(latents_upload(c, hl, p->D, c->q_full));
+  const Param par = param_of(c);
+  ZIGP_TRY(latents_upload(c, hl, p->D, par));
   ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
-  ZIGP_TRY(latents_forward(c, hl, p->D, jitter, true, false, nullptr, nullptr, c->whiten, c->q_full));
+  ZIGP_TRY(latents_forward(c, hl, p->D, jitter, par, true, false, nullptr, nullptr));
   ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   double klh[2] = {0.0, 0.0};
   for (int h = 0; h < 2; ++h)
-    ZIGP_HIP(c, hipMemcpyAsync(&klh[h], (c->whiten ? c->lat[h].wh.p : c->lat[h].vec.p) + 3 * c->lat[h].Mp, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    ZIGP_HIP(c, hipMemcpyAsync(&klh[h], (is_white(par) ? c->lat[h].wh.p : c->lat[h].vec.p) + 3 * c->lat[h].Mp, sizeof(double), hipMemcpyDeviceToHost, c->stream));
   ZIGP_TRY(check_info(c, "Kuu"));          // synchronises; on failure kl2 is left untouched
   kl2[0] = klh[0]; kl2[1] = klh[1];
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));
@@ -1625,11 +1603,25 @@ int zigp_test_kgmom_list(int32_t M, int64_t Nc, int64_t cap, int64_t* out) {
   return ZIGP_OK;
 }
 
+int zigp_test_sk_list(int32_t rule, int32_t nb, int64_t cap, int64_t* out) {
+  // host only: the split-K list of a k-range rule (zigp_host.h SkRule) at nb blocks, through run_gemm_sk's own builder -- out[0] = slices,
+  // out[1] = lower_only of the finish pass, out[2] = entries, then (bi, bj, kbeg, kend, slice) per entry, as many as fit `cap` int64
+  if (rule < 0 || rule >= (int)SkRule::COUNT || nb <= 0 || !out || cap < 3) return ZIGP_EARG;
+  std::vector<GemmTile> v;
+  build_sk_list((SkRule)rule, nb, v);
+  out[0] = sk_slices((SkRule)rule, nb); out[1] = SK_RULES[rule].lower_only ? 1 : 0; out[2] = (int64_t)v.size();
+  for (size_t i = 0; i < v.size() && 3 + 5 * (int64_t)(i + 1) <= cap; ++i) {
+    int64_t* o = out + 3 + 5 * i;
+    o[0] = v[i].bi; o[1] = v[i].bj; o[2] = v[i].kbeg; o[3] = v[i].kend; o[4] = v[i].slice;
+  }
+  return ZIGP_OK;
+}
+
 int zigp_test_trmm_list(int32_t lower, int32_t Mf, int32_t Mg, int64_t Nc, int32_t tail_on, int64_t* out) {
   // host only (no context, no GPU): the lists run_dense plans for A1 (lower) or A2 (upper) of a chunk of Nc rows, checked tile by tile
   if (Mf <= 0 || Mg <= 0 || Nc <= 0 || Nc % BN != 0 || !out) return ZIGP_EARG;
   const int Mp[2] = {(int)round_up(Mf, BM), (int)round_up(Mg, BM)}, nbn = (int)(Nc / BN), kb = BM / BK;
-  const ChunkPlan pl = chunk_plan({Mf, Mg}, Nc, false, tail_on != 0);
+  const ChunkPlan pl = chunk_plan({Mf, Mg}, Nc, Param::Diag, false, tail_on != 0, false);
   int64_t wgs[2], per[2], worst_tail = 0;
   for (int h = 0; h < 2; ++h) {
     const int nbm = Mp[h] / BM;
@@ -1750,25 +1742,25 @@ bool stage_chunk_ok(int64_t Nc) { return Nc >= 1024 && Nc % 1024 == 0 && Nc <= (
 }  // namespace
 
 namespace {
-int stage_chunk_forward(zigp_ctx* c, int64_t Nc, int32_t need_grad, int32_t only, const zigp_stage_latent* lat, int64_t* facts, bool whiten) {
+int stage_chunk_forward(zigp_ctx* c, int64_t Nc, int32_t need_grad, int32_t only, const zigp_stage_latent* lat, int64_t* facts, Param par) {
   if (!c) return ZIGP_EARG;
   if (!lat || !facts || !stage_chunk_ok(Nc) || only < -1 || only > 1) return fail_arg(c, "zigp_test_chunk_forward: bad arguments");
   for (int h = 0; h < 2; ++h) {
     const zigp_stage_latent& q = lat[h];
     if (q.M <= 0) return fail_arg(c, "zigp_test_chunk_forward: M must be positive");
     if (only >= 0 && only != h) continue;
-    if (!q.W || !q.v || !q.s2 || !q.K || (!q.A1 && !(whiten && !need_grad)) || !q.part || (need_grad && (!q.Rt || !q.Jp)))
+    if (!q.W || !q.v || !q.s2 || !q.K || (!q.A1 && !(is_white(par) && !need_grad)) || !q.part || (need_grad && (!q.Rt || !q.Jp)))
       return fail_arg(c, "zigp_test_chunk_forward: NULL operand of a latent that runs");
   }
   ZIGP_HIP(c, hipSetDevice(c->device));
-  const bool grad = need_grad != 0;
+  const bool grad = need_grad != 0, white = is_white(par);     // Diag or White: a WhiteFull chunk is Diag's launches (include/zigp_diag.h)
   for (int h = 0; h < 2; ++h) {
     Latent& lt = c->lat[h];
     const zigp_stage_latent& q = lat[h];
     lt.M = q.M; lt.Mp = (int)round_up(q.M, BM);
     const int Mp = lt.Mp;
     const size_t np = Mp / 32;
-    const bool has_a1 = !whiten || grad;      // a whitened value-only / predict pass stores no A panel
+    const bool has_a1 = !white || grad;      // a whitened value-only / predict pass stores no A panel
     ZIGP_ENSURE(c, lt.Wt, (size_t)Mp * Mp); ZIGP_ENSURE(c, lt.vec, 4 * (size_t)Mp + 8); ZIGP_ENSURE(c, lt.wh, 4 * (size_t)Mp + 8);
     if (has_a1) ZIGP_ENSURE(c, lt.A1, (size_t)Mp * Nc);
     ZIGP_ENSURE(c, lt.part, 3 * np * Nc);
@@ -1781,7 +1773,7 @@ int stage_chunk_forward(zigp_ctx* c, int64_t Nc, int32_t need_grad, int32_t only
     ZIGP_TRY(stage_upload_square(c, lt.W, q.W, q.M, Mp, 1.0));
     hipLaunchKernelGGL(k_transpose, dim3(Mp / 32, Mp / 32), dim3(32, 8), 0, c->stream, lt.W.p, (int64_t)Mp, lt.Wt.p);
     ZIGP_HIP(c, hipGetLastError());
-    if (whiten) {      // the epilogue weights (Latent::wh: s2 = s^2 - 1, then v = u) and the J' factor image D W, zero padded
+    if (white) {      // the epilogue weights (Latent::wh: s2 = s^2 - 1, then v = u) and the J' factor image D W, zero padded
       if (grad) ZIGP_TRY(stage_upload_square(c, lt.Wp, q.Rt, q.M, Mp, 0.0));
       ZIGP_HIP(c, hipMemsetAsync(lt.wh.p, 0, sizeof(double) * (4 * (size_t)Mp + 8), c->stream));
       ZIGP_HIP(c, hipMemcpyAsync(lt.wh.p, q.s2, sizeof(double) * q.M, hipMemcpyHostToDevice, c->stream));
@@ -1798,17 +1790,17 @@ int stage_chunk_forward(zigp_ctx* c, int64_t Nc, int32_t need_grad, int32_t only
     ZIGP_HIP(c, hipMemsetAsync(lt.part.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * 3 * np * Nc, c->stream));
   }
   const int M[2] = {lat[0].M, lat[1].M};
-  ChunkPlan pl = chunk_plan(M, Nc, grad, c->trmm_tail, whiten);
+  ChunkPlan pl = chunk_plan(M, Nc, par, grad, c->trmm_tail, false);
   ZIGP_TRY(upload_plan(c, pl));
   if (only >= 0) { ChunkPlan::Lat& o = pl.lat[1 - only]; o.a1 = TileList(); o.a2j = TileList(); }
-  if (whiten) {
+  if (white) {
     ZIGP_TRY(chunk_forward_white(c, pl, grad, false));
     if (grad) ZIGP_TRY(chunk_forward_white(c, pl, true, true));
-  } else ZIGP_TRY(chunk_forward(c, pl, grad));
+  } else ZIGP_TRY(chunk_forward(c, pl, par, grad));
   for (int h = 0; h < 2; ++h) {
     if (only >= 0 && only != h) continue;
     Latent& lt = c->lat[h];
-    if (!whiten || grad) ZIGP_TRY(stage_download_rows(c, lt.A1.p, lat[h].A1, lat[h].M, Nc));
+    if (!white || grad) ZIGP_TRY(stage_download_rows(c, lt.A1.p, lat[h].A1, lat[h].M, Nc));
     if (grad) ZIGP_TRY(stage_download_rows(c, lt.Jp.p, lat[h].Jp, lat[h].M, Nc));
     ZIGP_TRY(stage_download_rows(c, lt.part.p, lat[h].part, 3 * (int64_t)(lt.Mp / 32), Nc));
   }
@@ -1826,10 +1818,10 @@ int stage_chunk_forward(zigp_ctx* c, int64_t Nc, int32_t need_grad, int32_t only
 }
 }  // namespace
 int zigp_test_chunk_forward(zigp_ctx* c, int64_t Nc, int32_t need_grad, int32_t only, const zigp_stage_latent* lat, int64_t* facts) {
-  return stage_chunk_forward(c, Nc, need_grad, only, lat, facts, false);
+  return stage_chunk_forward(c, Nc, need_grad, only, lat, facts, Param::Diag);
 }
 int zigp_test_chunk_forward_white(zigp_ctx* c, int64_t Nc, int32_t need_grad, int32_t only, const zigp_stage_latent* lat, int64_t* facts) {
-  return stage_chunk_forward(c, Nc, need_grad, only, lat, facts, true);
+  return stage_chunk_forward(c, Nc, need_grad, only, lat, facts, Param::White);
 }
 
 // ---- full-covariance M x M stage (zigp_set_q_full), one latent, through latent_qfull_stage / _factors / _dlq ----
@@ -1894,13 +1886,14 @@ int zigp_test_latents_forward(zigp_ctx* c, const zigp_params* p, double jitter, 
   if (!out_f || !out_g || !(jitter >= 0)) return fail_arg(c, "zigp_test_latents_forward: bad arguments");
   if (c->q_full) return fail_arg(c, "zigp_test_latents_forward: the diagonal stages only (zigp_set_q_full is on; see zigp_test_q_full_forward)");
   ZIGP_HIP(c, hipSetDevice(c->device));
-  const bool white = c->whiten, grad = need_grad != 0;
+  const Param par = param_of(c);     // Diag or White: a full-covariance context was refused above
+  const bool white = is_white(par), grad = need_grad != 0;
   HostLatent hl[2] = {{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f}, {p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g}};
   ZIGP_TRY(begin_staged_call(c));
   ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
-  ZIGP_TRY(latents_upload(c, hl, p->D));
+  ZIGP_TRY(latents_upload(c, hl, p->D, par));
   ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
-  ZIGP_TRY(latents_forward(c, hl, p->D, jitter, true, grad, nullptr, nullptr, white, false));
+  ZIGP_TRY(latents_forward(c, hl, p->D, jitter, par, true, grad, nullptr, nullptr));
   ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   ZIGP_TRY(check_info(c, "Kuu"));
   double* const* outs[2] = {out_f, out_g};
@@ -1934,7 +1927,7 @@ int zigp_test_latents_forward(zigp_ctx* c, const zigp_params* p, double jitter, 
 }
 
 namespace {
-int stage_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s, bool whiten) {
+int stage_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s, Param par) {
   if (!c) return ZIGP_EARG;
   if (!s || s->mode < 0 || s->mode > 2 || s->repeat < 1 || !stage_chunk_ok(s->Nc) || !s->part_f || !s->part_g || !s->acc)
     return fail_arg(c, "zigp_test_pointwise: bad arguments");
@@ -1973,7 +1966,7 @@ int stage_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s, bool whiten) {
   for (int d = 0; d < MAXD; ++d) c->mean_a[d] = mean_a[d];
   a.part_f = pf.p; a.part_g = pg.p; a.np_f = s->np_f; a.np_g = s->np_g;
   a.np1_f = s->np1_f; a.np2_f = s->np2_f; a.np1_g = s->np1_g; a.np2_g = s->np2_g;
-  for (int r = 0; r < s->repeat; ++r) ZIGP_TRY(dense_pointwise_launch(c, k.predict, k.need_grad, a, nullptr, whiten));
+  for (int r = 0; r < s->repeat; ++r) ZIGP_TRY(dense_pointwise_launch(c, par, k.predict, k.need_grad, a, nullptr));
   if (s->mode == 1) {
     ZIGP_TRY(stage_download_rows(c, c->lat[0].gm.p, s->gm_f, 1, Nc)); ZIGP_TRY(stage_download_rows(c, c->lat[0].gv.p, s->gv_f, 1, Nc));
     ZIGP_TRY(stage_download_rows(c, c->lat[1].gm.p, s->gm_g, 1, Nc)); ZIGP_TRY(stage_download_rows(c, c->lat[1].gv.p, s->gv_g, 1, Nc));
@@ -1984,8 +1977,8 @@ int stage_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s, bool whiten) {
   return ZIGP_OK;
 }
 }  // namespace
-int zigp_test_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s) { return stage_pointwise(c, s, false); }
-int zigp_test_pointwise_white(zigp_ctx* c, const zigp_stage_pointwise* s) { return stage_pointwise(c, s, true); }
+int zigp_test_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s) { return stage_pointwise(c, s, Param::Diag); }
+int zigp_test_pointwise_white(zigp_ctx* c, const zigp_stage_pointwise* s) { return stage_pointwise(c, s, Param::White); }
 
 int zigp_test_kgrad(zigp_ctx* c, int32_t M, int32_t D, int64_t Nc, int64_t Nrows, int64_t n0, const double* Jp, const double* K, const double* alpha,
                     const double* gm, const double* gv, const double* X, const double* Z, const double* ell, const double* centre, int32_t exact,
@@ -2054,7 +2047,7 @@ int zigp_test_rank_update(zigp_ctx* c, int32_t M, int32_t nchunks, const int64_t
   ZIGP_HIP(c, hipMemsetAsync(lt.T1.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * mm, c->stream));
   const int Ms[2] = {M, M};
   for (int i = 0; i < nchunks; ++i) {
-    ChunkPlan pl = chunk_plan(Ms, Nc[i], true, c->trmm_tail);
+    ChunkPlan pl = chunk_plan(Ms, Nc[i], Param::Diag, true, c->trmm_tail, false);
     ZIGP_TRY(upload_plan(c, pl));
     ZIGP_TRY(stage_upload_rows(c, lt.A1, A1[i], M, Mp, Nc[i]));
     ZIGP_TRY(stage_upload_rows(c, lt.gv, gv[i], 1, 1, Nc[i]));
@@ -2070,7 +2063,7 @@ int zigp_test_rank_update(zigp_ctx* c, int32_t M, int32_t nchunks, const int64_t
   return ZIGP_OK;
 }
 
-// ---- M x M reverse stage of one latent (include/zigp_diag.h), through latent_mxm_backward / latent_mxm_backward_white ----
+// ---- M x M reverse stage of one latent (include/zigp_diag.h), through latent_mxm_backward ----
 namespace {
 // host (rows x cols) -> device (rows_p x cols_p), `pad` outside the real block; lower: entries above the diagonal are zero
 int stage_upload_padded(zigp_ctx* c, DevBuf& buf, const double* src, int rows, int cols, int rows_p, int cols_p, double pad, bool lower = false) {
@@ -2095,10 +2088,11 @@ int zigp_test_mxm_backward(zigp_ctx* c, const zigp_stage_mxm* a) {
   if (!a->W || !a->L || !a->Kuu || !a->Z || !a->s || !a->alpha || !a->krow || (a->mode == 0 && !a->v) || (a->with_data && !a->C1))
     return fail_arg(c, "zigp_test_mxm_backward: NULL operand of the mode");
   const int M = a->M, D = a->D, Wd = 2 + 2 * D;
-  const bool white = a->mode != 0, q_full = a->mode == 2, with_data = a->with_data != 0, with_kl = a->with_kl != 0;
+  const Param par = (Param)a->mode;
+  const bool white = is_white(par), with_data = a->with_data != 0, with_kl = a->with_kl != 0;
   for (int m = 0; m < M; ++m)
-    if (!((q_full ? a->s[(size_t)m * M + m] : a->s[m]) != 0))
-      return fail_arg(c, q_full ? "zigp_test_mxm_backward: zero (or NaN) diagonal entry of Lq" : "zigp_test_mxm_backward: zero (or NaN) entry of s");
+    if (!((is_full(par) ? a->s[(size_t)m * M + m] : a->s[m]) != 0))
+      return fail_arg(c, is_full(par) ? "zigp_test_mxm_backward: zero (or NaN) diagonal entry of Lq" : "zigp_test_mxm_backward: zero (or NaN) entry of s");
   ZIGP_HIP(c, hipSetDevice(c->device));
   Latent& lt = c->lat[0];
   lt.M = M; lt.Mp = (int)round_up(M, BM);
@@ -2113,7 +2107,7 @@ int zigp_test_mxm_backward(zigp_ctx* c, const zigp_stage_mxm* a) {
     memset(static_cast<void*>(&k.hl), 0, sizeof(k.hl));
     k.p = &pp; k.dX = nullptr; k.dY = nullptr; k.Nrows = 1024; k.D = D; k.jitter = a->jitter; k.scale = 1; k.g_offset = 0; k.row_begin = 0;
     k.row_end = with_data ? 1024 : 0; k.include_kl = with_kl ? 1 : 0; k.predict = false; k.d_out9 = nullptr; k.need_grad = true; k.has_rows = with_data;
-    k.whiten = white; k.q_full = q_full; k.Nc = 1024;
+    k.par = par; k.Nc = 1024;
     ZIGP_TRY(dense_prepare_buffers(c, k));
   }
   // operands
@@ -2128,7 +2122,7 @@ int zigp_test_mxm_backward(zigp_ctx* c, const zigp_stage_mxm* a) {
   ZIGP_ENSURE(c, lt.Wp, mm);
   const dim3 gridmm(ceil_div((int64_t)mm, 256));
   lt.P_ready = false;
-  if (q_full) {          // the staged factor and its small vectors, then T - I -> P and R^T -> Rt
+  if (is_full(par)) {          // the staged factor and its small vectors, then T - I -> P and R^T -> Rt
     ZIGP_TRY(stage_qfull_operands(c, lt, M, a->s, a->u));
     ZIGP_ENSURE(c, lt.P, mm); ZIGP_ENSURE(c, lt.Rt, mm);
     ZIGP_TRY(latent_qfull_factors(c, lt));
@@ -2154,7 +2148,7 @@ int zigp_test_mxm_backward(zigp_ctx* c, const zigp_stage_mxm* a) {
   if (!white) ZIGP_ENSURE(c, lt.G, mm);
   for (double* q : {lt.T1.p, lt.T2.p, lt.T3.p, white ? (double*)nullptr : lt.G.p})
     if (q) ZIGP_HIP(c, hipMemsetAsync(q, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * mm, c->stream));
-  if (q_full) {
+  if (is_full(par)) {
     ZIGP_ENSURE(c, lt.dLq, mm);
     ZIGP_HIP(c, hipMemsetAsync(lt.dLq.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * mm, c->stream));
   }
@@ -2162,8 +2156,7 @@ int zigp_test_mxm_backward(zigp_ctx* c, const zigp_stage_mxm* a) {
     if (id < 0 || id >= ZIGP_MXM_TAPS || !a->tap[id]) return 0;
     return stage_download_square(c, dev, M, Mp, a->tap[id]);
   };
-  const int rc = white ? latent_mxm_backward_white(c, lt, D, a->jitter, with_data, q_full, with_kl, tap)
-                       : latent_mxm_backward(c, lt, D, a->jitter, with_data, with_kl, tap);
+  const int rc = latent_mxm_backward(c, lt, D, a->jitter, par, with_data, with_kl, tap);
   lt.P_ready = false;
   ZIGP_TRY(rc);
   ZIGP_TRY(stage_download_rows(c, lt.a1gm.p, a->a1gm, 1, M));
@@ -2171,7 +2164,7 @@ int zigp_test_mxm_backward(zigp_ctx* c, const zigp_stage_mxm* a) {
   ZIGP_TRY(stage_download_rows(c, lt.dsq.p, a->dsq, 1, M));
   ZIGP_TRY(stage_download_rows(c, lt.krow.p, a->krow, (int64_t)KG_SPLIT * Mp, Wd));
   ZIGP_TRY(stage_download_square(c, lt.T3.p, M, Mp, a->G));
-  if (q_full) ZIGP_TRY(stage_download_square(c, lt.dLq.p, M, Mp, a->dLq));
+  if (is_full(par)) ZIGP_TRY(stage_download_square(c, lt.dLq.p, M, Mp, a->dLq));
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));
   return ZIGP_OK;
 }
@@ -2184,18 +2177,19 @@ int zigp_test_dense_pack(zigp_ctx* c, const zigp_stage_pack* a) {
   if (a->mode < 0 || a->mode > 2 || a->pw_blocks < 1 || !a->pw) return fail_arg(c, "zigp_test_dense_pack: need a mode in 0 .. 2 and pw [pw_blocks][13], pw_blocks >= 1");
   if (a->mean_on && a->D > MAXD) return fail_arg(c, "zigp_test_dense_pack: the mean function's sums cover D <= 8");
   const int D = a->D, Wd = 2 + 2 * D;
-  const bool grad = a->need_grad != 0, white = a->mode != 0, q_full = a->mode == 2;
+  const Param par = (Param)a->mode;
+  const bool grad = a->need_grad != 0, white = is_white(par), lq = is_full(par);     // lq: the latents carry a full factor (dLq, no dsq / s)
   size_t need = DP_HDR;
   for (int h = 0; h < 2; ++h) {
     const zigp_stage_pack_latent& q = a->lat[h];
     if (q.M <= 0) return fail_arg(c, "zigp_test_dense_pack: M must be positive");
-    if (!q.kl_vec1 || (!q_full && !q.kl_vec2)) return fail_arg(c, "zigp_test_dense_pack: NULL operand");
-    if (grad && (!q.krow || !q.du || !q.ell || !(q.var > 0) || (q_full ? !q.dLq : (!q.dsq || !q.s))))
+    if (!q.kl_vec1 || (!lq && !q.kl_vec2)) return fail_arg(c, "zigp_test_dense_pack: NULL operand");
+    if (grad && (!q.krow || !q.du || !q.ell || !(q.var > 0) || (lq ? !q.dLq : (!q.dsq || !q.s))))
       return fail_arg(c, "zigp_test_dense_pack: NULL operand of a gradient call (or var <= 0)");
-    if (grad && !q_full)
+    if (grad && !lq)
       for (int m = 0; m < q.M; ++m)
         if (!(q.s[m] != 0)) return fail_arg(c, "zigp_test_dense_pack: zero (or NaN) entry of s");
-    if (grad) need += (size_t)q.M * D + q.M + (q_full ? (size_t)q.M * q.M : (size_t)q.M) + D;
+    if (grad) need += (size_t)q.M * D + q.M + (lq ? (size_t)q.M * q.M : (size_t)q.M) + D;
   }
   if (a->n_out != (int64_t)need) return fail_arg(c, "zigp_test_dense_pack: n_out must be 16 + sum over the latents of M D + M + (M or M M) + D (16 without need_grad)");
   ZIGP_HIP(c, hipSetDevice(c->device));
@@ -2220,9 +2214,9 @@ int zigp_test_dense_pack(zigp_ctx* c, const zigp_stage_pack* a) {
       ZIGP_HIP(c, hipMemcpyAsync(lt.krow.p + (size_t)sp * Mp * Wd, q.krow + (size_t)sp * M * Wd, sizeof(double) * M * Wd, hipMemcpyHostToDevice, c->stream));
     ZIGP_TRY(stage_upload_rows(c, white ? lt.a1gm : lt.du, q.du, M, Mp, 1));
     ZIGP_TRY(stage_upload_rows(c, lt.ell, q.ell, D, std::max(D, MAXD), 1));
-    if (q_full) ZIGP_TRY(stage_upload_square(c, lt.dLq, q.dLq, M, Mp, 0.0));
+    if (lq) ZIGP_TRY(stage_upload_square(c, lt.dLq, q.dLq, M, Mp, 0.0));
     else { ZIGP_TRY(stage_upload_rows(c, lt.dsq, q.dsq, M, Mp, 1)); ZIGP_TRY(stage_upload_rows(c, lt.s, q.s, M, Mp, 1)); }
-    if (q_full) {     // k_dense_pack loads s[m] and dsq[m] before it looks at q_full and discards what it forms from them: zeros
+    if (lq) {     // k_dense_pack loads s[m] and dsq[m] before it looks at q_full and discards what it forms from them: zeros
       ZIGP_TRY(stage_upload_rows(c, lt.dsq, nullptr, 0, Mp, 1));
       ZIGP_TRY(stage_upload_rows(c, lt.s, nullptr, 0, Mp, 1));
     }
@@ -2233,7 +2227,7 @@ int zigp_test_dense_pack(zigp_ctx* c, const zigp_stage_pack* a) {
   memset(static_cast<void*>(&k.hl), 0, sizeof(k.hl));
   k.p = &pp; k.dX = nullptr; k.dY = nullptr; k.Nrows = 0; k.D = D; k.jitter = 0; k.scale = 1; k.g_offset = 0; k.row_begin = 0; k.row_end = 0;
   k.include_kl = a->include_kl ? 1 : 0; k.predict = false; k.d_out9 = nullptr; k.need_grad = grad; k.has_rows = true;
-  k.whiten = white; k.q_full = q_full; k.pw_blocks = a->pw_blocks;
+  k.par = par; k.pw_blocks = a->pw_blocks;
   const bool mean_on = c->mean_on;
   c->mean_on = a->mean_on != 0;
   DensePackArgs pa;

@@ -515,37 +515,76 @@ k_sk_finish(const double* __restrict__ planes, int S, int64_t Mp, double alpha, 
   else out[idx] = (j < i) ? v : ((j == i) ? 0.5 * v : 0.0);
 }
 
-// krange(bi, bj, &kbeg, &kend) in units of BK; kend <= kbeg: the tile is not computed
-template <int AL, int BL, class KRange>
-static int run_gemm_sk(zigp_ctx* c, DevBuf& planes, const std::string& key, int nb, KRange krange, const double* A, const double* B, double* C,
-                       int64_t Mp, int post, double alpha, bool lower_only) {
+// The k range of output tile (bi, bj) of an nb x nb block product, by rule: which k blocks can contribute follows from the triangular
+// structure of the factors, and a rule whose product is needed in its lower tiles only computes no tile above the diagonal.  The table gives
+// each rule its key in the tile cache, whether its finish pass is lower_only (k_sk_finish then DEFINES the tiles above the diagonal as zero)
+// and the product shape it serves; sk_range is the rule itself, in units of BK (kb = BM / BK steps per block; k1 <= k0: not computed).
+enum class SkRule : int { S = 0, Y, R, TT, FULL, T, RT, RFULL, COUNT };
+struct SkRuleInfo { const char* key; bool lower_only; };
+constexpr SkRuleInfo SK_RULES[(int)SkRule::COUNT] = {
+    {"s", false},      // W^T X, W and X lower triangular (X = W: P = W^T W; X = Q W: S = W^T X): k >= max(i, j)
+    {"y", false},      // X W, W lower triangular as the right factor: k >= j
+    {"r", true},       // W^T X (or L^T X), W lower triangular as the transposed left factor, lower tiles only: k >= i
+    {"tt", false},     // X Y^T, both factors lower triangular: k <= min(i, j)
+    {"full", false},   // two dense factors: every k
+    {"t", true},       // Q W, both factors lower triangular, lower tiles only: j <= k <= i
+    {"rt", false},     // W X, W lower triangular as the left factor: k <= i
+    {"rfull", true},   // two dense factors, lower tiles only: every k
+};
+static inline void sk_range(SkRule r, int bi, int bj, int nb, int kb, int& k0, int& k1) {
+  const bool lower = bj <= bi;
+  k0 = 0; k1 = 0;
+  switch (r) {
+    case SkRule::S: k0 = std::max(bi, bj) * kb; k1 = nb * kb; break;
+    case SkRule::Y: k0 = bj * kb; k1 = nb * kb; break;
+    case SkRule::R: if (lower) { k0 = bi * kb; k1 = nb * kb; } break;
+    case SkRule::TT: k1 = (std::min(bi, bj) + 1) * kb; break;
+    case SkRule::FULL: k1 = nb * kb; break;
+    case SkRule::T: if (lower) { k0 = bj * kb; k1 = (bi + 1) * kb; } break;
+    case SkRule::RT: k1 = (bi + 1) * kb; break;
+    case SkRule::RFULL: if (lower) k1 = nb * kb; break;
+    case SkRule::COUNT: break;
+  }
+}
+// Slices per tile of a rule at nb blocks: at most 8, at most the shortest k range, S * tiles within the 512 resident workgroups (0: no tile)
+static inline int sk_slices(SkRule r, int nb) {
   int count = 0, minlen = 1 << 30;
   for (int bi = 0; bi < nb; ++bi)
     for (int bj = 0; bj < nb; ++bj) {
-      int k0, k1; krange(bi, bj, k0, k1);
+      int k0, k1; sk_range(r, bi, bj, nb, BM / BK, k0, k1);
       if (k1 > k0) { ++count; minlen = std::min(minlen, k1 - k0); }
     }
-  if (count == 0) return 0;
-  const int S = std::max(1, std::min(std::min(8, minlen), 512 / count));
+  return count == 0 ? 0 : std::max(1, std::min(std::min(8, minlen), 512 / count));
+}
+// The list of a rule at nb blocks, slice-major: the only builder (run_gemm_sk uploads it, zigp_test_sk_list shows it to the CPU suite)
+static inline void build_sk_list(SkRule r, int nb, std::vector<GemmTile>& v) {
+  const int S = sk_slices(r, nb);
+  for (int s = 0; s < S; ++s)
+    for (int bi = 0; bi < nb; ++bi)
+      for (int bj = 0; bj < nb; ++bj) {
+        int k0, k1; sk_range(r, bi, bj, nb, BM / BK, k0, k1);
+        if (k1 <= k0) continue;
+        const int len = k1 - k0;
+        v.push_back(mk_tile(bi, bj, k0 + (int)((int64_t)len * s / S), k0 + (int)((int64_t)len * (s + 1) / S), s));
+      }
+}
+// C = finish(alpha * A B) over the tiles of rule r; post: SK_STORE / SK_ACCUM / SK_PHI
+template <int AL, int BL>
+static int run_gemm_sk(zigp_ctx* c, DevBuf& planes, SkRule r, int nb, const double* A, const double* B, double* C, int64_t Mp, int post, double alpha) {
+  const SkRuleInfo& info = SK_RULES[(int)r];
+  const int S = sk_slices(r, nb), lower_only = info.lower_only ? 1 : 0;
+  if (S == 0) return 0;
   TileList tl;
-  ZIGP_TRY(get_tiles(c, "sk:" + key + ":" + std::to_string(nb) + ":" + std::to_string(S), [&](std::vector<GemmTile>& v) {
-    for (int s = 0; s < S; ++s)
-      for (int bi = 0; bi < nb; ++bi)
-        for (int bj = 0; bj < nb; ++bj) {
-          int k0, k1; krange(bi, bj, k0, k1);
-          if (k1 <= k0) continue;
-          const int len = k1 - k0;
-          v.push_back(mk_tile(bi, bj, k0 + (int)((int64_t)len * s / S), k0 + (int)((int64_t)len * (s + 1) / S), s));
-        }
-  }, tl));
+  ZIGP_TRY(get_tiles(c, std::string("sk:") + info.key + ":" + std::to_string(nb) + ":" + std::to_string(S),
+                     [&](std::vector<GemmTile>& v) { build_sk_list(r, nb, v); }, tl));
   ZIGP_ENSURE(c, planes, (size_t)S * Mp * Mp);
   GemmArgs g = mk_args(A, Mp, B, Mp, planes.p, Mp);
   g.slice_stride = Mp * Mp;
   ZIGP_TRY((run_gemm<AL, BL, false>(c, tl, g, EpiStore())));
   const dim3 grid((unsigned)((Mp * Mp + 255) / 256));
-  if (post == SK_STORE) hipLaunchKernelGGL(k_sk_finish<SK_STORE>, grid, dim3(256), 0, c->stream, planes.p, S, Mp, alpha, lower_only ? 1 : 0, C);
-  else if (post == SK_ACCUM) hipLaunchKernelGGL(k_sk_finish<SK_ACCUM>, grid, dim3(256), 0, c->stream, planes.p, S, Mp, alpha, lower_only ? 1 : 0, C);
-  else hipLaunchKernelGGL(k_sk_finish<SK_PHI>, grid, dim3(256), 0, c->stream, planes.p, S, Mp, alpha, lower_only ? 1 : 0, C);
+  if (post == SK_STORE) hipLaunchKernelGGL(k_sk_finish<SK_STORE>, grid, dim3(256), 0, c->stream, planes.p, S, Mp, alpha, lower_only, C);
+  else if (post == SK_ACCUM) hipLaunchKernelGGL(k_sk_finish<SK_ACCUM>, grid, dim3(256), 0, c->stream, planes.p, S, Mp, alpha, lower_only, C);
+  else hipLaunchKernelGGL(k_sk_finish<SK_PHI>, grid, dim3(256), 0, c->stream, planes.p, S, Mp, alpha, lower_only, C);
   ZIGP_HIP(c, hipGetLastError());
   return 0;
 }
