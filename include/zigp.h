@@ -317,6 +317,35 @@ int zigp_get_whiten(zigp_ctx* ctx);
 int zigp_set_q_full(zigp_ctx* ctx, int32_t on);
 int zigp_get_q_full(zigp_ctx* ctx);
 
+/* Kernel family of the DENSE path, per latent.  Replaces the choice of kernel object handed to the model: "gpflow objects for function &
+ * gamma kernels" (onoffgpf/OnOffSVGP.py:22; gpflow.kernels.RBF at zero-inflated-gpflow.ipynb:98-104, for which GPflow 0.4.0's
+ * kernels.Matern32 / kernels.Matern52 are drop-in alternatives, each latent its own).  With r2 = sum_d ((x_d - z_d) / ell_d)^2 and
+ * r = sqrt(r2 + 1e-12) (Stationary.euclid_dist; the floor keeps coincident points differentiable):
+ *   ZIGP_KERN_RBF       k = var exp(-r2 / 2)                               (the state after zigp_create)
+ *   ZIGP_KERN_MATERN32  k = var (1 + sqrt3 r) exp(-sqrt3 r)
+ *   ZIGP_KERN_MATERN52  k = var (1 + sqrt5 r + (5/3) r^2) exp(-sqrt5 r)
+ * Kdiag is var for all three; the diagonal of K(Z, Z) is the formula at r = 1e-6 (plus jitter), as GPflow evaluates it.  latent: 0 = f,
+ * 1 = g; the two may differ.  zigp_elbo (value-only and gradient, include_kl 0 / 1, row ranges, zigp_select_rows), zigp_predict,
+ * zigp_predict_device and zigp_prior_kl follow the setting in all three parametrisations (zigp_set_whiten, zigp_set_q_full); mean
+ * functions, g_offset, scale, the chunk rule and the data-parallel exchange work as without it; zigp_params and zigp_grads keep their
+ * layouts (ell_*, var_* are the kernel's lengthscales and variance).  A gradient step keeps one more panel of 8 * M * rows bytes per
+ * Matern latent (the derivative factor K' = -dk / d(r2 / 2)), the fourth of the four the chunk rule budgets (zigp_set_chunk).  The
+ * setting persists in the context like zigp_set_whiten.
+ * ZIGP_EARG: a NULL context, a latent outside {0, 1}, an unknown kind.  While a latent is Matern these return ZIGP_EARG with nothing
+ * enqueued (the message names the kernel): the entry points above at D > 8 (the wide kernels are RBF only), and zigp_fit_steps /
+ * zigp_fit_steps_mode at every D (the device loops fit RBF latents; zigp_elbo + a host optimiser fits the others).  The Kronecker entry
+ * points ignore the setting.  zigp_get_kernel returns the kind, or ZIGP_EARG for a NULL context or a latent outside {0, 1}. */
+#define ZIGP_KERN_RBF 0
+#define ZIGP_KERN_MATERN32 1
+#define ZIGP_KERN_MATERN52 2
+int zigp_set_kernel(zigp_ctx* ctx, int32_t latent /* 0 f, 1 g */, int32_t kind);
+int zigp_get_kernel(zigp_ctx* ctx, int32_t latent);
+/* Kernel matrices of any of the three kinds (gpflow kernels.Stationary.K -> RBF.K / Matern32.K / Matern52.K; zigp_rbf_K is the RBF
+ * one and stays as it is): K (n1,n2) = k(X1, X2) as above, no jitter.  X2 == NULL -> X1 (the diagonal is then the formula at r = 1e-6
+ * for the Matern kinds).  Argument conventions of zigp_rbf_K; 1 <= D <= ZIGP_MAX_D for ZIGP_KERN_RBF, D <= 8 for the Matern kinds. */
+int zigp_kern_K(zigp_ctx* ctx, int32_t kind, const double* X1, int64_t n1, const double* X2, int64_t n2, int32_t D,
+                const double* ell, double var, double* K);
+
 /* Single-latent heads on the same Kronecker conditional -- the reference's baselines, which re-use kron_inf and
  * GaussKLkron with one latent f:
  *   ZIGP_LIK_GAUSSIAN   scripts/svgp.py:127-200,207-233 and scripts/hurdle.py:127-252 (regression; noise variance)

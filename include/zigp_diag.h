@@ -145,6 +145,21 @@ int zigp_test_kgrad(zigp_ctx* ctx, int32_t M, int32_t D, int64_t Nc, int64_t Nro
                     const double* alpha, const double* gm, const double* gv, const double* X, const double* Z, const double* ell,
                     const double* centre, int32_t exact, double* krow);
 
+/* The counterpart of zigp_test_kuf for a kernel kind (ZIGP_KERN_*, include/zigp.h): the Kuf panel as a call with that kind on the
+ * latent builds it (kernels.Matern32.K / Matern52.K of GPflow 0.4.0 in place of RBF.K at onofftf/main.py:266) and, when Kd != NULL,
+ * the derivative panel K' = -dk / d(r2 / 2) a gradient step writes in the same launch (K' = K for ZIGP_KERN_RBF, copied).  K and Kd
+ * are (Mp16, N) row-major with Mp16 = M rounded up to 16: the rows m >= M of the last 16-row group are returned too (zeros).
+ * D <= 8 for the Matern kinds. */
+int zigp_test_kuf_kind(zigp_ctx* ctx, int32_t kind, int64_t N, int32_t M, int32_t D, const double* X, const double* Z, const double* ell,
+                       double var, double* K, double* Kd);
+/* The counterpart of zigp_test_kgrad for a kernel kind: the Kuf cotangent reductions of one chunk as a gradient step with that kind on
+ * the latent launches them (the reverse of kernels.Matern32.K / Matern52.K; of KernSE.K, onofftf/main.py:41-57, for ZIGP_KERN_RBF,
+ * where Kd is not read and the per-row form of k_kgrad runs).  Kd (M,Nc): the derivative panel; the
+ * 2 D moment columns of krow are taken with F Kd, columns 0 and 1 + 2 D with K.  Other arguments as zigp_test_kgrad. */
+int zigp_test_kgrad_kind(zigp_ctx* ctx, int32_t kind, int32_t M, int32_t D, int64_t Nc, int64_t Nrows, int64_t n0, const double* Jp,
+                         const double* K, const double* Kd, const double* alpha, const double* gm, const double* gv, const double* X,
+                         const double* Z, double* krow);
+
 /* Rank-N update C1 = sum_chunks A1_i diag(gv_i) A1_i^T: the chunks' updates one after the other onto zeroed split-K planes, then the
  * plane reduction.  A1[i] (M,Nc[i]), gv[i] (Nc[i]), Nc[i] multiples of 1024.  C1 (M,M) symmetric; plan[2] = {So, Sd}. */
 int zigp_test_rank_update(zigp_ctx* ctx, int32_t M, int32_t nchunks, const int64_t* Nc, const double* const* A1, const double* const* gv,

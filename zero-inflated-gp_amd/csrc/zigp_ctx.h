@@ -65,6 +65,7 @@ struct Latent {
   double var = 1.0;
   DevBuf Kuu, L, W;                      // (Mp,Mp)
   DevBuf K, A1, Jp;                      // chunk panels [Mp][Nc]: Kuf, A1 = W K, J' = Q W^T A1 (A2 = W^T A1 is reduced to its column sums and never stored: r6)
+  DevBuf Kd;                             // chunk panel [Mp][Nc] of a Matern latent's gradient step: K' = -dk / d(r2 / 2) (k_kuf_build_matern); freed when the latent goes back to RBF
   DevBuf Wp, a1gm;                       // W diag(s^2) (Mp,Mp); running sum of A1 gm [Mp]
   DevBuf Wt;                             // W^T (Mp,Mp): the m-contiguous image the lower-triangular product A1 = W K reads
   DevBuf P, Qt, Rt;                      // gradient steps: P = W^T W = Kuu^-1, Qt = diag(s^2) P - I = Q^T, Rt = W Qt = (Q W^T)^T: J' = Q A2 = (Q W^T) A1 (zigp_dense.hip, chunk_forward)
@@ -165,6 +166,7 @@ struct zigp_ctx : zigp::CtxHandles {
   int overlap = 1;                      // zigp_set_overlap: 1 (default) = HBM-bound side kernels of a chunk on stream2 under its SYRKs
   bool mean_on = false;
   bool whiten = false;                  // zigp_set_whiten: u_*m / u_*s_sqrt are the whitened quantities, q(u) = N(L u, L diag(s^2) L^T)
+  int kern[2] = {0, 0};                 // zigp_set_kernel: ZIGP_KERN_* of latent f, g (dense path)
   bool q_full = false;                  // zigp_set_q_full (needs whiten): u_*s_sqrt are (M,M) lower-triangular factors Lq, q(u) = N(L u, L Lq Lq^T L^T)
   double mean_a[8] = {0}, mean_b = 0.0, mean_da[8] = {0}, mean_db = 0.0;   // 8 = zigp::MAXD (zigp_kernels.h)
   zigp::DevBuf out9;                    // predict outputs (9,Nc)

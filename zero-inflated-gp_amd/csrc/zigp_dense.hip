@@ -70,7 +70,18 @@ Param param_of(const zigp_ctx* c) { return !c->whiten ? Param::Diag : c->q_full 
 
 struct HostLatent {
   int M; const double *Z, *u, *s, *ell; double var;
+  int kind = ZIGP_KERN_RBF;     // kernel family of the latent (zigp_set_kernel), read once per call next to param_of: run_dense, zigp_prior_kl
 };
+static_assert(KERN_RBF == ZIGP_KERN_RBF && KERN_M32 == ZIGP_KERN_MATERN32 && KERN_M52 == ZIGP_KERN_MATERN52,
+              "the kernels' kind values are the ZIGP_KERN_* constants of include/zigp.h");
+constexpr bool is_matern(int kind) { return kind != ZIGP_KERN_RBF; }
+const char* kern_name(int kind) { return kind == ZIGP_KERN_MATERN32 ? "Matern32" : kind == ZIGP_KERN_MATERN52 ? "Matern52" : "RBF"; }
+// "... Matern52 kernel on latent g ..." for the refusals that name the kernel (nullptr: both latents RBF)
+const char* matern_latent(const zigp_ctx* c, std::string& who) {
+  for (int h = 0; h < 2; ++h)
+    if (is_matern(c->kern[h])) { who = std::string(kern_name(c->kern[h])) + " kernel on latent " + (h ? "g" : "f"); return who.c_str(); }
+  return nullptr;
+}
 
 // Parameters of both latents to the device (zero-padded to Mp): ONE staged image [Z | ell | u | s | Zs] x 2 and one copy -- the eight
 // separate copies of the first version were eight launches (~7 us apart) in front of a launch-bound M x M stage.  lt.Z / ell / u / s
@@ -210,7 +221,10 @@ int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter
     const int Mp = lt.Mp;
     OnStream on(c, st[h]);
     const dim3 grid(ceil_div((int64_t)Mp * Mp, 256));
-    if (d_hyp)
+    if (is_matern(hl[h].kind))     // D <= MAXD and no device block: validate_params and dense_fit_steps refuse the rest
+      hipLaunchKernelGGL(k_kuu_setup_matern, grid, dim3(256), 0, c->stream, lt.Z.p, (int64_t)hl[h].M, make_hyp(hl[h].ell, hl[h].var, D), hl[h].kind, jitter,
+                         lt.Kuu.p, lt.L.p, lt.W.p, lt.s.p, lt.s2.p, (int64_t)Mp);
+    else if (d_hyp)
       hipLaunchKernelGGL(k_kuu_setup<LatHypDev>, grid, dim3(256), 0, c->stream, lt.Z.p, (int64_t)hl[h].M, LatHypDev{d_hyp + h * DH_LAT, D}, jitter, lt.Kuu.p,
                          lt.L.p, lt.W.p, lt.s.p, lt.s2.p, (int64_t)Mp);
     else if (D > MAXD)
@@ -289,8 +303,31 @@ int latents_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter
 
 // Kuf panel of one latent for the chunk starting at row n0 (HBM-write bound; runs on the side stream under the previous chunk's SYRKs)
 // R (fit loop): the latent's record of the device hyperparameter block; ell_host is then not read
+// kind (a Matern latent; D <= MAXD, no device block): k_kuf_build_matern on the same grid; with_kd (its gradient steps): the launch also
+// writes the derivative panel K' into lt.Kd (sized by dense_prepare_buffers)
+int latent_chunk_kuf_matern(zigp_ctx* c, Latent& lt, const double* dX, int64_t Nrows, int64_t n0, int64_t Nc, int D, const double* ell_host, int kind,
+                            bool with_kd) {
+  if (D < 1 || D > MAXD || !ell_host) return fail_arg(c, "a Matern Kuf panel needs 1 <= D <= 8 and host lengthscales");
+  if (with_kd && lt.Kd.cap < (size_t)lt.Mp * Nc) return fail_arg(c, "a Matern gradient step's K' panel was not sized for this chunk");
+  const KufHyp kh = make_kuf_hyp(ell_host, lt.var, D);
+  ProfScope ps(c, PC_KUF);
+  const dim3 grid((unsigned)(Nc / 512), lt.Mp / 16), block(256);
+#define ZIGP_KUF_M(DD, KK, GG) \
+  hipLaunchKernelGGL((k_kuf_build_matern<DD, KK, GG>), grid, block, 0, c->stream, dX, Nrows, n0, lt.Zs.p, lt.M, kh, lt.K.p, GG ? lt.Kd.p : nullptr, Nc)
+#define ZIGP_KUF_MD(DD)                                                                    \
+  case DD:                                                                                 \
+    if (kind == ZIGP_KERN_MATERN32) { if (with_kd) ZIGP_KUF_M(DD, KERN_M32, true); else ZIGP_KUF_M(DD, KERN_M32, false); } \
+    else { if (with_kd) ZIGP_KUF_M(DD, KERN_M52, true); else ZIGP_KUF_M(DD, KERN_M52, false); }                            \
+    break;
+  switch (D) { ZIGP_KUF_MD(1) ZIGP_KUF_MD(2) ZIGP_KUF_MD(3) ZIGP_KUF_MD(4) ZIGP_KUF_MD(5) ZIGP_KUF_MD(6) ZIGP_KUF_MD(7) ZIGP_KUF_MD(8) }
+#undef ZIGP_KUF_MD
+#undef ZIGP_KUF_M
+  ZIGP_HIP(c, hipGetLastError());
+  return 0;
+}
 int latent_chunk_kuf(zigp_ctx* c, Latent& lt, const double* dX, int64_t Nrows, int64_t n0, int64_t Nc, int D, const double* ell_host,
-                     const double* R = nullptr) {
+                     const double* R = nullptr, int kind = ZIGP_KERN_RBF, bool with_kd = false) {
+  if (is_matern(kind)) return latent_chunk_kuf_matern(c, lt, dX, Nrows, n0, Nc, D, ell_host, kind, with_kd);
   const int Mp = lt.Mp;
   const KufHyp kh = (R || D > MAXD) ? KufHyp() : make_kuf_hyp(ell_host, lt.var, D);
   ProfScope ps(c, PC_KUF);
@@ -484,8 +521,28 @@ int ensure_kgrad_wide(zigp_ctx* c, Latent& lt, int64_t Nc) {
 }
 
 // Kuf-cotangent reductions of one latent and chunk (HBM-read bound; runs on the side stream under the chunk's SYRKs)
+// A Matern latent (D <= MAXD): k_kgrad_matern, the per-row form reading K and the derivative panel lt.Kd.  The centred form is not
+// needed here: it exists to save fp64 VALU instructions beside the rank-N updates, and the Matern reduction already reads a third panel.
+int latent_chunk_kgrad_matern(zigp_ctx* c, Latent& lt, const double* dX, int64_t Nrows, int64_t n0, int64_t Nc, int D) {
+  const int Mp = lt.Mp;
+  if (D < 1 || D > MAXD) return fail_arg(c, "a Matern Kuf gradient needs 1 <= D <= 8");
+  if (lt.Kd.cap < (size_t)Mp * Nc) return fail_arg(c, "a Matern gradient step's K' panel was not sized for this chunk");
+  ProfScope ps(c, PC_RED);
+  const dim3 gk((unsigned)ceil_div(lt.M, KG_ROWS), KG_SPLIT), bk(256);
+  const int64_t slab = (int64_t)Mp * (2 + 2 * D);
+#define ZIGP_KGRAD_M(DD)                                                                                                                         \
+  case DD:                                                                                                                                       \
+    hipLaunchKernelGGL((k_kgrad_matern<DD>), gk, bk, 0, c->stream, lt.Jp.p, lt.K.p, lt.Kd.p, lt.vec.p + Mp, lt.gm.p, lt.gv.p, dX, Nrows, n0, lt.Z.p, \
+                       lt.M, Nc, slab, lt.krow.p);                                                                                               \
+    break;
+  switch (D) { ZIGP_KGRAD_M(1) ZIGP_KGRAD_M(2) ZIGP_KGRAD_M(3) ZIGP_KGRAD_M(4) ZIGP_KGRAD_M(5) ZIGP_KGRAD_M(6) ZIGP_KGRAD_M(7) ZIGP_KGRAD_M(8) }
+#undef ZIGP_KGRAD_M
+  ZIGP_HIP(c, hipGetLastError());
+  return 0;
+}
 int latent_chunk_kgrad(zigp_ctx* c, Latent& lt, const double* dX, int64_t Nrows, int64_t n0, int64_t Nc, int D, const double* ell_host,
-                       const TileList& mom = TileList()) {
+                       const TileList& mom = TileList(), int kind = ZIGP_KERN_RBF) {
+  if (is_matern(kind)) return latent_chunk_kgrad_matern(c, lt, dX, Nrows, n0, Nc, D);
   const int Mp = lt.Mp;
   KgCentre hyp;     // (not read by the wide launches)
   for (int d = 0; d < MAXD; ++d) hyp.c[d] = lt.zc[d];
@@ -540,9 +597,13 @@ void latent_sym_from_planes(zigp_ctx* c, Latent& lt) {
 }
 
 // G (in T3) -> slab 0 of krow: k_kuu_grad, or for D > MAXD its windows of WIDE_SLICE dimensions
-void launch_kuu_grad(zigp_ctx* c, Latent& lt, int D, double jitter) {
+// hk (a Matern latent, D <= MAXD): k_kuu_grad_matern, which recomputes K' from Z with the call's host lengthscales and variance
+void launch_kuu_grad(zigp_ctx* c, Latent& lt, int D, double jitter, const HostLatent* hk = nullptr) {
   const int Mp = lt.Mp;
-  if (D > MAXD)
+  if (hk && is_matern(hk->kind))
+    hipLaunchKernelGGL(k_kuu_grad_matern, dim3(Mp), dim3(256), 0, c->stream, lt.T3.p, lt.Kuu.p, jitter, lt.Z.p, lt.M, make_hyp(hk->ell, hk->var, D), hk->kind,
+                       (int64_t)Mp, lt.krow.p);
+  else if (D > MAXD)
     hipLaunchKernelGGL(k_kuu_grad_wide, dim3(Mp, ceil_div(D, WIDE_SLICE)), dim3(256), 0, c->stream, lt.T3.p, lt.Kuu.p, jitter, lt.Z.p, lt.M, D, (int64_t)Mp,
                        lt.krow.p);
   else hipLaunchKernelGGL(k_kuu_grad, dim3(Mp), dim3(256), 0, c->stream, lt.T3.p, lt.Kuu.p, jitter, lt.Z.p, lt.M, D, (int64_t)Mp, lt.krow.p);
@@ -620,7 +681,8 @@ int mxm_backward_tail(zigp_ctx* c, Latent& lt, const double* r1, const double* r
   ZIGP_TAP(ZIGP_MXM_TAP_S, lt.T1.p);
   return 0;
 }
-int latent_mxm_backward(zigp_ctx* c, Latent& lt, int D, double jitter, Param par, bool with_data, bool with_kl, const MxmTap& tap) {
+int latent_mxm_backward(zigp_ctx* c, Latent& lt, int D, double jitter, Param par, bool with_data, bool with_kl, const MxmTap& tap,
+                        const HostLatent* hk = nullptr) {
   const int Mp = lt.Mp, nb = Mp / BM;
   const size_t mm = (size_t)Mp * Mp;
   ZIGP_ENSURE(c, lt.T1, mm); ZIGP_ENSURE(c, lt.T2, mm); ZIGP_ENSURE(c, lt.T3, mm);
@@ -654,7 +716,7 @@ int latent_mxm_backward(zigp_ctx* c, Latent& lt, int D, double jitter, Param par
     hipLaunchKernelGGL(k_sym_combine, dim3(gridmm), dim3(256), 0, c->stream, lt.T1.p, P, PSP, lt.vec.p + Mp, with_data ? 1 : 0, with_kl ? 1 : 0,
                        (int64_t)Mp, lt.T3.p);
   }
-  launch_kuu_grad(c, lt, D, jitter);
+  launch_kuu_grad(c, lt, D, jitter, hk);
   ZIGP_HIP(c, hipGetLastError());
   return 0;
 }
@@ -663,6 +725,11 @@ int validate_params(zigp_ctx* c, const zigp_params* p) {
   if (!p) return fail_arg(c, "params is NULL");
   if (p->Mf <= 0 || p->Mg <= 0) return fail_arg(c, "Mf and Mg must be positive");
   if (p->D <= 0 || p->D > ZIGP_MAX_D) return fail_arg(c, "D must be in [1, " ZIGP_MAX_D_STR "] (ZIGP_MAX_D)");
+  if (p->D > MAXD) {
+    std::string who;
+    if (matern_latent(c, who))
+      return fail_arg(c, ("a " + who + " (zigp_set_kernel) and D = " + std::to_string(p->D) + ": the Matern kernels cover D in [1, 8] (the wide kernels are RBF only)").c_str());
+  }
   if (p->D > MAXD && c->mean_on)
     for (int d = 0; d < MAXD; ++d)
       if (c->mean_a[d] != 0.0) return fail_arg(c, "a Linear mean function is set and D > 8: Linear covers D in [1, 8] (Zero and Constant work at every D)");
@@ -725,7 +792,8 @@ int dense_mxm_forward(zigp_ctx* c, DenseCall& k) {
     ZIGP_TRY(dense_prepare_buffers(c, k));
     if (k.has_rows)
       for (int h = 0; h < 2; ++h)
-        ZIGP_TRY(latent_chunk_kuf(c, c->lat[h], k.dX, k.Nrows, k.row_begin, dense_first_chunk_rows(k), k.D, k.ell_h[h], k.hyp_rec(h)));
+        ZIGP_TRY(latent_chunk_kuf(c, c->lat[h], k.dX, k.Nrows, k.row_begin, dense_first_chunk_rows(k), k.D, k.ell_h[h], k.hyp_rec(h), k.hl[h].kind,
+                                  k.need_grad));
     ZIGP_HIP(c, hipEventRecord(c->ev_prep, c->stream3));
   }
   {
@@ -777,6 +845,8 @@ int dense_prepare_buffers(zigp_ctx* c, DenseCall& k) {
       if (k.par != Param::White || k.need_grad) ZIGP_ENSURE(c, lt.A1, (size_t)Mp * Nc);     // a whitened (diagonal) value-only / predict pass stores no panel but K
       ZIGP_ENSURE(c, lt.part, (size_t)3 * (Mp / 32) * Nc);
       if (k.need_grad) ZIGP_ENSURE(c, lt.Jp, (size_t)Mp * Nc);
+      // a Matern latent's gradient step: the derivative panel K', the fourth of the four panels per latent chunk_rows_for budgets
+      if (k.need_grad && is_matern(k.hl[h].kind)) ZIGP_ENSURE(c, lt.Kd, (size_t)Mp * Nc);
       if (k.need_grad && D > MAXD && !lt.kg_exact) ZIGP_TRY(ensure_kgrad_wide(c, lt, Nc));
     }
     if (k.need_grad) {
@@ -850,12 +920,13 @@ int dense_chunk_loop(zigp_ctx* c, const DenseCall& k) {
     return chunk_rows(n0) == Nc_full && (((n0 - row_begin) / Nc_full) % c->prof_every) == 0;
   };
   auto kuf = [&](int64_t n0) -> int {     // Kuf panels of both latents for the chunk at row n0
-    for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_kuf(c, c->lat[h], k.dX, k.Nrows, n0, chunk_rows(n0), D, k.ell_h[h], k.hyp_rec(h)));
+    for (int h = 0; h < 2; ++h)
+      ZIGP_TRY(latent_chunk_kuf(c, c->lat[h], k.dX, k.Nrows, n0, chunk_rows(n0), D, k.ell_h[h], k.hyp_rec(h), k.hl[h].kind, k.need_grad));
     return 0;
   };
   auto kgrad = [&](int64_t n0, int64_t Nc) -> int {
     const ChunkPlan& pl = k.plan[Nc == k.plan[0].Nc ? 0 : 1];
-    for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_kgrad(c, c->lat[h], k.dX, k.Nrows, n0, Nc, D, k.ell_h[h], pl.lat[h].mom));
+    for (int h = 0; h < 2; ++h) ZIGP_TRY(latent_chunk_kgrad(c, c->lat[h], k.dX, k.Nrows, n0, Nc, D, k.ell_h[h], pl.lat[h].mom, k.hl[h].kind));
     return 0;
   };
   // Side-stream section: stream2 forks from the main stream, runs `work` and records ev_join, which the main stream waits on
@@ -1018,7 +1089,7 @@ int dense_step(zigp_ctx* c, DenseCall& k) {
     ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
     for (int h = 0; h < 2; ++h) {
       OnStream on(c, h == 0 ? c->stream_main : c->stream2);
-      ZIGP_TRY(latent_mxm_backward(c, c->lat[h], k.D, k.jitter, k.par, k.has_rows, k.include_kl != 0, nullptr));
+      ZIGP_TRY(latent_mxm_backward(c, c->lat[h], k.D, k.jitter, k.par, k.has_rows, k.include_kl != 0, nullptr, &k.hl[h]));
     }
     ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   }
@@ -1035,8 +1106,8 @@ int run_dense(zigp_ctx* c, const zigp_params* p, const double* dX, const double*
   k.need_grad = (grads != nullptr) && !predict;
   k.has_rows = row_end > row_begin;
   k.par = param_of(c);
-  k.hl[0] = HostLatent{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f};
-  k.hl[1] = HostLatent{p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g};
+  k.hl[0] = HostLatent{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f, c->kern[0]};
+  k.hl[1] = HostLatent{p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g, c->kern[1]};
   k.ell_h[0] = p->ell_f; k.ell_h[1] = p->ell_g;
   ZIGP_TRY(dense_plan(c, k));
   ZIGP_TRY(dense_step(c, k));
@@ -1165,6 +1236,20 @@ int zigp_set_q_full(zigp_ctx* c, int32_t on) {
 }
 int zigp_get_q_full(zigp_ctx* c) { return c ? (c->q_full ? 1 : 0) : (int)ZIGP_EARG; }
 
+int zigp_set_kernel(zigp_ctx* c, int32_t latent, int32_t kind) {
+  if (!c) return ZIGP_EARG;
+  if (latent < 0 || latent > 1) return fail_arg(c, "zigp_set_kernel: latent must be 0 (f) or 1 (g)");
+  if (kind != ZIGP_KERN_RBF && kind != ZIGP_KERN_MATERN32 && kind != ZIGP_KERN_MATERN52)
+    return fail_arg(c, "zigp_set_kernel: unknown kernel kind (ZIGP_KERN_RBF, ZIGP_KERN_MATERN32, ZIGP_KERN_MATERN52)");
+  c->kern[latent] = kind;
+  if (!is_matern(kind)) {     // the derivative panel exists only while the latent is Matern (every call ends synchronised: nothing reads it now)
+    (void)hipSetDevice(c->device);
+    c->lat[latent].Kd.release();
+  }
+  return ZIGP_OK;
+}
+int zigp_get_kernel(zigp_ctx* c, int32_t latent) { return (c && latent >= 0 && latent <= 1) ? c->kern[latent] : (int)ZIGP_EARG; }
+
 int zigp_get_mean_function_grad(zigp_ctx* c, double* da, int32_t D, double* db) {
   if (!c) return ZIGP_EARG;
   if (D < 0 || D > MAXD || (D > 0 && !da)) return fail_arg(c, "zigp_get_mean_function_grad: need 0 <= D <= 8 and da[D]");
@@ -1270,6 +1355,10 @@ int dense_fit_steps(zigp_ctx* c, int32_t mode, bool legacy, const zigp_params* s
   if (legacy && c->q_full) return bad("the full-covariance q(u) is on (zigp_set_q_full, q_diag=False); the device loop fits the diagonal unwhitened parametrisation only (zigp_elbo + a host optimiser)");
   if (legacy && c->whiten) return bad("whitening is on (zigp_set_whiten); the device loop fits the unwhitened parametrisation only (zigp_elbo + a host optimiser)");
   if (c->mean_on) return bad("a mean function is set; its parameters stay with the host loop (zigp_elbo + a host optimiser)");
+  {
+    std::string kw;
+    if (matern_latent(c, kw)) return bad(("a " + kw + " is set (zigp_set_kernel); the device loop fits RBF latents only (zigp_elbo + a host optimiser)").c_str());
+  }
   if (c->comm) return bad("a communicator is attached; the dense device loop is single-process");
   if (rows) {
     if ((int64_t)n_steps > ((int64_t)1 << 27) / batch) return bad("n_steps * batch row indices exceed 1 GiB");
@@ -1464,7 +1553,8 @@ int zigp_prior_kl(zigp_ctx* c, const zigp_params* p, double jitter, double* kl2)
   ZIGP_TRY(validate_params(c, p));
   if (!kl2) return fail_arg(c, "zigp_prior_kl: kl2 is NULL");
   ZIGP_HIP(c, hipSetDevice(c->device));
-  HostLatent hl[2] = {{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f}, {p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g}};
+  HostLatent hl[2] = {{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f, c->kern[0]},
+                      {p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g, c->kern[1]}};
   ZIGP_TRY(begin_staged_call(c));
   ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
   const Param par = param_of(c);
@@ -1501,6 +1591,29 @@ int zigp_rbf_K(zigp_ctx* c, const double* X1, int64_t n1, const double* X2, int6
     KernHyp h = make_hyp(ell, var, D);
     hipLaunchKernelGGL(k_rbf_matrix, dim3(ceil_div(n1 * n2, 256)), dim3(256), 0, c->stream, d1, n1, d2, n2, h, 0.0, c->scratch2.p, n1, n2, n2);
   }
+  ZIGP_HIP(c, hipGetLastError());
+  ZIGP_HIP(c, hipMemcpyAsync(K, c->scratch2.p, sizeof(double) * n1 * n2, hipMemcpyDeviceToHost, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  return ZIGP_OK;
+}
+
+int zigp_kern_K(zigp_ctx* c, int32_t kind, const double* X1, int64_t n1, const double* X2, int64_t n2, int32_t D, const double* ell, double var,
+                double* K) {
+  if (!c) return ZIGP_EARG;
+  if (kind == ZIGP_KERN_RBF) return zigp_rbf_K(c, X1, n1, X2, n2, D, ell, var, K);
+  if (kind != ZIGP_KERN_MATERN32 && kind != ZIGP_KERN_MATERN52)
+    return fail_arg(c, "zigp_kern_K: unknown kernel kind (ZIGP_KERN_RBF, ZIGP_KERN_MATERN32, ZIGP_KERN_MATERN52)");
+  if (!X1 || n1 <= 0 || D <= 0 || !ell || !K) return fail_arg(c, "zigp_kern_K: bad arguments");
+  if (D > MAXD) return fail_arg(c, (std::string("zigp_kern_K: the ") + kern_name(kind) + " kernel covers D in [1, 8]").c_str());
+  if (!X2) n2 = n1;
+  if (n2 <= 0) return fail_arg(c, "zigp_kern_K: bad n2");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  ZIGP_ENSURE(c, c->scratch, (size_t)(n1 + n2) * D);
+  ZIGP_ENSURE(c, c->scratch2, (size_t)n1 * n2);
+  double* d1 = c->scratch.p; double* d2 = d1 + n1 * D;
+  ZIGP_HIP(c, hipMemcpyAsync(d1, X1, sizeof(double) * n1 * D, hipMemcpyHostToDevice, c->stream));
+  ZIGP_HIP(c, hipMemcpyAsync(d2, X2 ? X2 : X1, sizeof(double) * n2 * D, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_matern_matrix, dim3(ceil_div(n1 * n2, 256)), dim3(256), 0, c->stream, d1, n1, d2, n2, make_hyp(ell, var, D), kind, c->scratch2.p);
   ZIGP_HIP(c, hipGetLastError());
   ZIGP_HIP(c, hipMemcpyAsync(K, c->scratch2.p, sizeof(double) * n1 * n2, hipMemcpyDeviceToHost, c->stream));
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));
@@ -1586,6 +1699,41 @@ int zigp_test_kuf(zigp_ctx* c, int64_t N, int32_t M, int32_t D, const double* X,
   ZIGP_HIP(c, hipMemcpyAsync(hk.data(), dk.p, sizeof(double) * hk.size(), hipMemcpyDeviceToHost, c->stream));
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));
   for (int m = 0; m < M; ++m) memcpy(K + (size_t)m * N, &hk[(size_t)m * Nc], sizeof(double) * N);
+  return ZIGP_OK;
+}
+
+int zigp_test_kuf_kind(zigp_ctx* c, int32_t kind, int64_t N, int32_t M, int32_t D, const double* X, const double* Z, const double* ell, double var,
+                       double* K, double* Kd) {
+  if (!c) return ZIGP_EARG;
+  if (kind != ZIGP_KERN_RBF && kind != ZIGP_KERN_MATERN32 && kind != ZIGP_KERN_MATERN52) return fail_arg(c, "zigp_test_kuf_kind: unknown kernel kind");
+  if (N <= 0 || M <= 0 || D < 1 || D > ZIGP_MAX_D || !X || !Z || !ell || !K) return fail_arg(c, "zigp_test_kuf_kind: bad arguments");
+  if (is_matern(kind) && D > MAXD) return fail_arg(c, (std::string("zigp_test_kuf_kind: the ") + kern_name(kind) + " kernel covers D in [1, 8]").c_str());
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  // the panel through the chunk loop's own launch helper, on a latent of this call's own
+  const int64_t Nc = round_up(N, 1024);
+  Latent lt;
+  lt.M = M; lt.Mp = (int)round_up(M, BM); lt.var = var;
+  const int Mp = lt.Mp, Mp16 = (int)round_up(M, 16);
+  const KufHypWide khw = make_kuf_hyp_wide(ell, var, D);
+  std::vector<double> zs((size_t)Mp * D, 0.0), hk((size_t)Mp16 * Nc);
+  for (int m = 0; m < M; ++m)
+    for (int d = 0; d < D; ++d) zs[(size_t)m * D + d] = Z[(size_t)m * D + d] * khw.scale[d];
+  DevBuf dx;
+  ZIGP_ENSURE(c, dx, (size_t)N * D); ZIGP_ENSURE(c, lt.Zs, zs.size()); ZIGP_ENSURE(c, lt.K, (size_t)Mp * Nc);
+  if (Kd && is_matern(kind)) ZIGP_ENSURE(c, lt.Kd, (size_t)Mp * Nc);
+  ZIGP_HIP(c, hipMemcpyAsync(dx.p, X, sizeof(double) * N * D, hipMemcpyHostToDevice, c->stream));
+  ZIGP_HIP(c, hipMemcpyAsync(lt.Zs.p, zs.data(), sizeof(double) * zs.size(), hipMemcpyHostToDevice, c->stream));
+  ZIGP_HIP(c, hipMemsetAsync(lt.K.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * (size_t)Mp * Nc, c->stream));
+  if (lt.Kd.p) ZIGP_HIP(c, hipMemsetAsync(lt.Kd.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * (size_t)Mp * Nc, c->stream));
+  ZIGP_TRY(latent_chunk_kuf(c, lt, dx.p, N, 0, Nc, D, ell, nullptr, kind, Kd != nullptr));
+  for (int pass = 0; pass < 2; ++pass) {
+    double* dst = pass ? Kd : K;
+    if (!dst) continue;
+    const double* src = (pass && is_matern(kind)) ? lt.Kd.p : lt.K.p;      // RBF: K' = K
+    ZIGP_HIP(c, hipMemcpyAsync(hk.data(), src, sizeof(double) * hk.size(), hipMemcpyDeviceToHost, c->stream));
+    ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+    for (int m = 0; m < Mp16; ++m) memcpy(dst + (size_t)m * N, &hk[(size_t)m * Nc], sizeof(double) * N);
+  }
   return ZIGP_OK;
 }
 
@@ -2020,6 +2168,39 @@ int zigp_test_kgrad(zigp_ctx* c, int32_t M, int32_t D, int64_t Nc, int64_t Nrows
     ZIGP_TRY(get_tiles(c, kgmom_tiles(Mp / BM, Nc), mom));
   }
   ZIGP_TRY(latent_chunk_kgrad(c, lt, dx.p, Nrows, n0, Nc, D, ell, mom));
+  for (int sp = 0; sp < KG_SPLIT; ++sp)
+    ZIGP_HIP(c, hipMemcpyAsync(krow + (size_t)sp * M * Wd, lt.krow.p + (size_t)sp * Mp * Wd, sizeof(double) * M * Wd, hipMemcpyDeviceToHost, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  return ZIGP_OK;
+}
+
+int zigp_test_kgrad_kind(zigp_ctx* c, int32_t kind, int32_t M, int32_t D, int64_t Nc, int64_t Nrows, int64_t n0, const double* Jp, const double* K,
+                         const double* Kd, const double* alpha, const double* gm, const double* gv, const double* X, const double* Z, double* krow) {
+  if (!c) return ZIGP_EARG;
+  if (kind == ZIGP_KERN_RBF) return zigp_test_kgrad(c, M, D, Nc, Nrows, n0, Jp, K, alpha, gm, gv, X, Z, nullptr, nullptr, 1, krow);
+  if (kind != ZIGP_KERN_MATERN32 && kind != ZIGP_KERN_MATERN52) return fail_arg(c, "zigp_test_kgrad_kind: unknown kernel kind");
+  if (M <= 0 || D < 1 || D > MAXD || !stage_chunk_ok(Nc) || Nrows <= 0 || n0 < 0 || n0 >= Nrows || !Jp || !K || !Kd || !alpha || !gm || !gv || !X || !Z || !krow)
+    return fail_arg(c, "zigp_test_kgrad_kind: bad arguments (a Matern kind needs 1 <= D <= 8 and the K' panel)");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  Latent lt;      // a latent of this call's own: the context's panels stay as they are
+  lt.M = M; lt.Mp = (int)round_up(M, BM);
+  const int Mp = lt.Mp, Wd = 2 + 2 * D;
+  DevBuf dx;
+  ZIGP_TRY(stage_upload_rows(c, dx, X, Nrows, Nrows, D));
+  ZIGP_TRY(stage_upload_rows(c, lt.Z, Z, M, Mp, D));
+  ZIGP_TRY(stage_upload_rows(c, lt.K, K, M, Mp, Nc));
+  ZIGP_TRY(stage_upload_rows(c, lt.Kd, Kd, M, Mp, Nc));
+  ZIGP_TRY(stage_upload_rows(c, lt.Jp, Jp, M, Mp, Nc));
+  ZIGP_TRY(stage_upload_rows(c, lt.gm, gm, 1, 1, Nc));
+  ZIGP_TRY(stage_upload_rows(c, lt.gv, gv, 1, 1, Nc));
+  ZIGP_ENSURE(c, lt.vec, 4 * (size_t)Mp + 8);
+  ZIGP_HIP(c, hipMemsetAsync(lt.vec.p, 0, sizeof(double) * (4 * (size_t)Mp + 8), c->stream));
+  ZIGP_HIP(c, hipMemcpyAsync(lt.vec.p + Mp, alpha, sizeof(double) * M, hipMemcpyHostToDevice, c->stream));
+  ZIGP_ENSURE(c, lt.krow, (size_t)KG_SPLIT * Mp * Wd);
+  ZIGP_HIP(c, hipMemsetAsync(lt.krow.p, 0, sizeof(double) * KG_SPLIT * Mp * Wd, c->stream));
+  for (int sp = 0; sp < KG_SPLIT; ++sp)
+    ZIGP_HIP(c, hipMemcpyAsync(lt.krow.p + (size_t)sp * Mp * Wd, krow + (size_t)sp * M * Wd, sizeof(double) * M * Wd, hipMemcpyHostToDevice, c->stream));
+  ZIGP_TRY(latent_chunk_kgrad(c, lt, dx.p, Nrows, n0, Nc, D, nullptr, TileList(), kind));
   for (int sp = 0; sp < KG_SPLIT; ++sp)
     ZIGP_HIP(c, hipMemcpyAsync(krow + (size_t)sp * M * Wd, lt.krow.p + (size_t)sp * Mp * Wd, sizeof(double) * M * Wd, hipMemcpyDeviceToHost, c->stream));
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));

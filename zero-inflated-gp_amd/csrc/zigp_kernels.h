@@ -784,7 +784,259 @@ k_kuu_grad_wide(const double* __restrict__ G, const double* __restrict__ Kuu, do
   }
 }
 
-// C1[i][j] = sum_s part[s][max(i,j)][min(i,j)]   (planes hold the lower triangle of A1 G A1^T; fixed summation order: s ascending)
+// ---------------------------------------------------------------------------------------------
+// Matern 3/2 and 5/2 (GPflow 0.4.0 kernels.Stationary / Matern32 / Matern52, the "gpflow objects for function & gamma kernels" of
+// onoffgpf/OnOffSVGP.py:22), D <= MAXD, per latent (zigp_set_kernel).  With r2 = sum_d ((x_d - z_d) / ell_d)^2 and the floored distance
+// r = sqrt(r2 + 1e-12) (Stationary.euclid_dist: the floor keeps coincident points differentiable),
+//   Matern32   k = var (1 + sqrt3 r) exp(-sqrt3 r)                     K' = 3 var exp(-sqrt3 r)
+//   Matern52   k = var (1 + sqrt5 r + (5/3) r^2) exp(-sqrt5 r)         K' = (5/3) var (1 + sqrt5 r) exp(-sqrt5 r)
+// K' = -dk / d(r2 / 2) is the one per-element quantity the reverse pass needs besides K (for the RBF kernel K' = K):
+//   dk/dz_d = K' (x_d - z_d) / ell_d^2,   dk/dell_d = K' (x_d - z_d)^2 / ell_d^3,   dk/dvar = K / var
+// so the krow layout, k_dense_pack and the host chain rule stay as they are; the 2 D moment columns are taken with F K' instead of F K.
+// Everything below stands BESIDE the RBF kernels: those keep their arguments and their machine code, and a call with both latents RBF
+// launches none of these.  Kind values are ZIGP_KERN_* (include/zigp.h).
+// ---------------------------------------------------------------------------------------------
+constexpr int KERN_RBF = 0, KERN_M32 = 1, KERN_M52 = 2;
+constexpr double MATERN_FLOOR = 1e-12;
+constexpr double MATERN_SQRT3 = 0x1.bb67ae8584caap+0, MATERN_SQRT5 = 0x1.1e3779b97f4a8p+1;
+// the two element functions in plain library arithmetic: the M x M stage (O(M^2 D), off the hot path) and zigp_kern_K
+__device__ __forceinline__ double matern_k(int kind, double var, double r2) {
+  const double r = sqrt(r2 + MATERN_FLOOR);
+  if (kind == KERN_M32) { const double t = MATERN_SQRT3 * r; return var * (1.0 + t) * exp(-t); }
+  const double t = MATERN_SQRT5 * r;
+  return var * (1.0 + t + (5.0 / 3.0) * (r * r)) * exp(-t);
+}
+__device__ __forceinline__ double matern_kd(int kind, double var, double r2) {
+  const double r = sqrt(r2 + MATERN_FLOOR);
+  if (kind == KERN_M32) return 3.0 * var * exp(-MATERN_SQRT3 * r);
+  const double t = MATERN_SQRT5 * r;
+  return (5.0 / 3.0) * var * (1.0 + t) * exp(-t);
+}
+
+// K (n1, n2) = k(X1, X2), no jitter, no padding: zigp_kern_K (gpflow kernels.Matern32.K / Matern52.K; k_rbf_matrix is the RBF one)
+__global__ void k_matern_matrix(const double* __restrict__ X1, int64_t n1, const double* __restrict__ X2, int64_t n2, KernHyp h, int kind,
+                                double* __restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n1 * n2) return;
+  const int64_t i = idx / n2, j = idx - i * n2;
+  double r2 = 0.0;
+  for (int d = 0; d < h.D; ++d) {
+    const double t = (X1[i * h.D + d] - X2[j * h.D + d]) * h.inv_ell[d];
+    r2 = fma(t, t, r2);
+  }
+  out[idx] = matern_k(kind, h.var, r2);
+}
+
+// k_kuu_setup for a Matern latent, with the same side duties: L = Kuu with its strictly-upper 128-blocks zero, W = 0, s2 = s^2.  The
+// diagonal is the formula at r = 1e-6 (GPflow evaluates K(Z, Z) through the floored distance) plus jitter.
+__global__ void k_kuu_setup_matern(const double* __restrict__ Z, int64_t M, KernHyp h, int kind, double jitter, double* __restrict__ Kuu,
+                                   double* __restrict__ L, double* __restrict__ W, const double* __restrict__ s, double* __restrict__ s2, int64_t Mp) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= Mp * Mp) return;
+  if (idx < Mp) s2[idx] = s[idx] * s[idx];
+  const int64_t i = idx / Mp, j = idx - i * Mp;
+  double v;
+  if (i < M && j < M) {
+    double r2 = 0.0;
+    for (int d = 0; d < h.D; ++d) {
+      const double t = (Z[i * h.D + d] - Z[j * h.D + d]) * h.inv_ell[d];
+      r2 = fma(t, t, r2);
+    }
+    v = matern_k(kind, h.var, r2) + ((i == j) ? jitter : 0.0);
+  } else {
+    v = (i == j) ? 1.0 : 0.0;
+  }
+  Kuu[idx] = v;
+  L[idx] = (j / 128 > i / 128) ? 0.0 : v;
+  W[idx] = 0.0;
+}
+
+// k_kuu_grad for a Matern latent: column 0 reads Kz = Kuu - jitter I as there; the moment columns take G K' with K' recomputed from Z
+// (O(M^2 D), off the hot path: no M x M panel of K' is kept).  On the diagonal the differences are zero, so K' there adds nothing.
+__global__ void __launch_bounds__(256)
+k_kuu_grad_matern(const double* __restrict__ G, const double* __restrict__ Kuu, double jitter, const double* __restrict__ Z,
+                  int M, KernHyp h, int kind, int64_t ld, double* __restrict__ krow) {
+  __shared__ double sh[4];
+  const int i = blockIdx.x, D = h.D;
+  if (i >= M) return;
+  double zz[MAXD];
+#pragma unroll
+  for (int d = 0; d < MAXD; ++d) zz[d] = (d < D) ? Z[i * D + d] : 0.0;
+  double s0 = 0.0, s1[MAXD], s2[MAXD];
+#pragma unroll
+  for (int d = 0; d < MAXD; ++d) { s1[d] = 0.0; s2[d] = 0.0; }
+  for (int j = threadIdx.x; j < M; j += 256) {
+    const double g = G[(int64_t)i * ld + j];
+    s0 = fma(g, Kuu[(int64_t)i * ld + j] - ((i == j) ? jitter : 0.0), s0);
+    double df[MAXD], r2 = 0.0;
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d) {
+      df[d] = (d < D) ? Z[j * D + d] - zz[d] : 0.0;
+      const double u = df[d] * h.inv_ell[d];
+      r2 = fma(u, u, r2);
+    }
+    const double t = g * matern_kd(kind, h.var, r2);
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d) {
+      const double td = t * df[d];
+      s1[d] = fma(2.0, td, s1[d]);
+      s2[d] = fma(td, df[d], s2[d]);
+    }
+  }
+  const int W = 2 + 2 * D;
+  s0 = block_sum<4>(s0, sh);
+  if (threadIdx.x == 0) krow[(int64_t)i * W] += s0;
+  for (int d = 0; d < D; ++d) {
+    double a = block_sum<4>(s1[d], sh);
+    double b = block_sum<4>(s2[d], sh);
+    if (threadIdx.x == 0) { krow[(int64_t)i * W + 1 + d] += a; krow[(int64_t)i * W + 1 + D + d] += b; }
+  }
+}
+
+// Kuf panel of a Matern latent: k_kuf_build's structure (two adjacent columns and 16 rows per thread, inputs pre-scaled by KUF_C / ell_d,
+// 16-byte stores, rows m >= M written as zeros) and its budget -- this kernel runs beside the triangular products, every VALU instruction
+// is paid in matrix-pipe time: no library exp(), sqrt() or pow(), no scratch.  From the direct-difference sum w = -(16 / ln 2) r2:
+//   g = sqrt(A (-w) + B) = (32 a / ln 2) r,   A = 64 a^2 / ln 2,  B = (32 a / ln 2)^2 1e-12,  a = sqrt3 or sqrt5
+//       (one fma, one clamp and kuf_sqrt: v_rsq_f64, good to 2^-23, one coupled Goldschmidt step for g ~ sqrt and h ~ 1 / (2 sqrt) -> 1.5 2^-46,
+//       one residual correction g += (s - g^2) h -> within 1 ulp; 8 instructions where the library's correctly rounded sqrt has 17);
+//   e = var exp(-a r) = T[j] 2^(-g / 32): kuf_exp2_32 as it is, same table, same polynomial;   t = a r = g ln 2 / 32;
+//   Matern32  K = e + e t,  K' = 3 e;    Matern52  K = e (1 + t (1 + t / 3))  (t^2 / 3 = (5/3) r^2),  K' = (5/3) (e + e t).
+// GRAD (a gradient step) also writes the derivative panel K' in the same launch: one or two more multiplies and one more store.
+// Coincident points: w = 0, g = sqrt(B), the r = 1e-6 value.  Far pairs: e underflows to an exact 0 through v_ldexp_f64 while t stays
+// finite (the clamp keeps g^2 below 2^997 whatever the inputs), so K = K' = 0 * finite = 0, never NaN.
+// Counted in the gfx950 ISA: 28.5 + 2 D (Matern32) / 30.5 + 2 D (Matern52) VALU instructions per element in a
+// value-only pass, 31 + 2 D / 34 + 2 D with GRAD, where k_kuf_build has 16 + 2 D; 30 to 58 VGPRs (D = 1 .. 8), no scratch.
+constexpr double KUF_LN2 = 0x1.62e42fefa39efp-1;
+template <int KIND> struct KufMatern {
+  static_assert(KIND == KERN_M32 || KIND == KERN_M52, "Matern 3/2 or 5/2");
+  static constexpr double a2 = KIND == KERN_M32 ? 3.0 : 5.0;
+  static constexpr double A = 64.0 * a2 / KUF_LN2;
+  static constexpr double B = 1024.0 * a2 / (KUF_LN2 * KUF_LN2) * MATERN_FLOOR;
+};
+__device__ __forceinline__ double kuf_sqrt(double s) {     // sqrt(s) within 1 ulp for s in [2^-1000, 2^1000] (here: [B, 2^996])
+  const double y = __builtin_amdgcn_rsq(s);
+  double g = s * y, h = 0.5 * y;
+  const double r = fma(-h, g, 0.5);
+  g = fma(g, r, g);
+  h = fma(h, r, h);
+  return fma(fma(-g, g, s), h, g);
+}
+template <int KIND, bool GRAD>
+__device__ __forceinline__ void kuf_matern(double w, const double* T, double& k, double& kd) {
+  const double g = kuf_sqrt(fmin(fma(-w, KufMatern<KIND>::A, KufMatern<KIND>::B), 0x1p+996));
+  const double t = g * (KUF_LN2 / 32.0);
+  const double e = kuf_exp2_32(-g, T);
+  if (KIND == KERN_M32) {
+    k = fma(e, t, e);
+    if (GRAD) kd = 3.0 * e;
+  } else {
+    k = e * fma(t, fma(t, 1.0 / 3.0, 1.0), 1.0);
+    if (GRAD) kd = (5.0 / 3.0) * fma(e, t, e);
+  }
+}
+template <int D, int KIND, bool GRAD>
+__global__ void __launch_bounds__(256)
+k_kuf_build_matern(const double* __restrict__ X, int64_t N, int64_t n0, const double* __restrict__ Zs, int M, KufHyp h,
+                   double* __restrict__ K, double* __restrict__ Kd, int64_t Nc) {
+  __shared__ double T[32];
+  if (threadIdx.x < 32) T[threadIdx.x] = hyp_var(h) * KUF_T[threadIdx.x];
+  const int64_t n = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;   // two adjacent columns: 16-byte stores
+  const int m0 = blockIdx.y * 16;
+  double xs[2][D];
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const bool valid = (n0 + n + e) < N;
+#pragma unroll
+    for (int d = 0; d < D; ++d) xs[e][d] = valid ? X[(n0 + n + e) * D + d] * hyp_scale(h, d) : 0.0;
+  }
+  __syncthreads();
+#pragma unroll 4
+  for (int mm = 0; mm < 16; ++mm) {
+    const int m = m0 + mm;
+    double2* out = reinterpret_cast<double2*>(K + (int64_t)m * Nc + n);
+    double2* outd = GRAD ? reinterpret_cast<double2*>(Kd + (int64_t)m * Nc + n) : nullptr;
+    if (m >= M) {     // uniform over the block
+      *out = make_double2(0.0, 0.0);
+      if (GRAD) *outd = make_double2(0.0, 0.0);
+      continue;
+    }
+    double w0, w1;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      const double zs = Zs[m * D + d];      // uniform: a scalar load
+      const double t0 = zs - xs[0][d], t1 = zs - xs[1][d];
+      w0 = d == 0 ? -t0 * t0 : fma(-t0, t0, w0); w1 = d == 0 ? -t1 * t1 : fma(-t1, t1, w1);
+    }
+    double k0, k1, kd0 = 0.0, kd1 = 0.0;
+    kuf_matern<KIND, GRAD>(w0, T, k0, kd0);
+    kuf_matern<KIND, GRAD>(w1, T, k1, kd1);
+    *out = make_double2(k0, k1);
+    if (GRAD) *outd = make_double2(kd0, kd1);
+  }
+}
+
+// Kuf cotangent of a Matern latent: the per-row (EXACT) form of k_kgrad -- same thread mapping, same fixed-order reduction -- which reads
+// K for columns 0 and 1 + 2 D and the derivative panel K' for the 2 D moment columns.  (No centred form: the shift saves two fused
+// multiply-adds per element and dimension and this kernel already pays a third panel read.)
+template <int D>
+__global__ void __launch_bounds__(256)
+k_kgrad_matern(const double* __restrict__ Jp, const double* __restrict__ K, const double* __restrict__ Kd, const double* __restrict__ alpha,
+               const double* __restrict__ gm, const double* __restrict__ gv, const double* __restrict__ X, int64_t N, int64_t n0,
+               const double* __restrict__ Z, int M, int64_t Nc, int64_t slab, double* __restrict__ krow) {
+  constexpr int W = 2 + 2 * D;
+  __shared__ double sh[4][KG_ROWS * W];
+  krow += (int64_t)blockIdx.y * slab;
+  const int m0 = blockIdx.x * KG_ROWS;
+  if (m0 >= M) return;
+  double am[KG_ROWS], acc[KG_ROWS][W], zr[KG_ROWS][D];
+#pragma unroll
+  for (int r = 0; r < KG_ROWS; ++r) {
+    am[r] = alpha[min(m0 + r, M - 1)];
+#pragma unroll
+    for (int d = 0; d < D; ++d) zr[r][d] = Z[min(m0 + r, M - 1) * D + d];
+#pragma unroll
+    for (int q = 0; q < W; ++q) acc[r][q] = 0.0;
+  }
+  const int64_t nspan = Nc / KG_SPLIT, nbeg = (int64_t)blockIdx.y * nspan;
+  const int64_t nmax = min(nbeg + nspan, N - n0);
+  for (int64_t n = nbeg + threadIdx.x; n < nmax; n += 256) {
+    const double gmn = gm[n], gv2 = 2.0 * gv[n];
+    double xc[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) xc[d] = X[(n0 + n) * D + d];
+#pragma unroll
+    for (int r = 0; r < KG_ROWS; ++r) {
+      const int64_t o = (int64_t)(m0 + r) * Nc + n;     // rows beyond M are zero-padded panels (inside the allocation)
+      const double kk = K[o];
+      const double f = fma(gv2, Jp[o], am[r] * gmn);
+      const double t = f * Kd[o];
+      acc[r][0] = fma(f, kk, acc[r][0]);
+      acc[r][1 + 2 * D] = fma(kk, gmn, acc[r][1 + 2 * D]);
+#pragma unroll
+      for (int d = 0; d < D; ++d) {
+        const double df = xc[d] - zr[r][d], td = t * df;
+        acc[r][1 + d] += td;
+        acc[r][1 + D + d] = fma(td, df, acc[r][1 + D + d]);
+      }
+    }
+  }
+  // fixed-order block reduction of the KG_ROWS*W partials: lanes by xor tree, then waves 0..3
+#pragma unroll
+  for (int r = 0; r < KG_ROWS; ++r)
+#pragma unroll
+    for (int q = 0; q < W; ++q) {
+      const double v = wave_sum(acc[r][q]);
+      if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][r * W + q] = v;
+    }
+  __syncthreads();
+  if (threadIdx.x < KG_ROWS * W) {
+    const int r = threadIdx.x / W, q = threadIdx.x - r * W;
+    if (m0 + r < M)
+      krow[(int64_t)(m0 + r) * W + q] += (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
+  }
+}
+
+// C1[i][j] = sum_s part[s][max(i,j)][min(i,j)]  (planes hold the lower triangle of A1 G A1^T; fixed summation order: s ascending)
 // One workgroup per 32 x 32 tile on or below the diagonal: the planes are read ONCE, along rows (the first version read the upper
 // half through transposed addresses, S strided loads per element: 118-150 us at M = 512 with 64 planes, a quarter of the M x M reverse
 // pass), the mirror image goes out through LDS.  Tiles inside a diagonal 128-block live in the first Sd planes only (the others hold

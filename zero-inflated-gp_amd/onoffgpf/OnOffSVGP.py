@@ -11,6 +11,8 @@ switch for the whitened model: q_diag=False makes u_*s_sqrt (M, M, 1) lower-tria
 the start, :65-71) and q(u) = N(L u_m, L Lq Lq^T L^T) (gauss_kl_white, :88-89; the 3-d q_sqrt branch of the conditional).  The
 unwhitened full-covariance model (gauss_kl, :102-104) is not implemented: q_diag=False with whiten=False raises NotImplementedError.  mean_function (:29,134): onoffgpf.mean_functions.Zero
 (default), Constant or Linear -- evaluated, and differentiated, inside the engine's point-wise kernel.
+kernf / kerng: onoffgpf.kernels.RBF, Matern32 or Matern52, each latent its own (:22); a Matern latent covers D <= 8 input columns and is
+fitted by L-BFGS-B or the host Adam loop (the device fit loops fit RBF latents).
 """
 import pickle
 import time
@@ -23,7 +25,7 @@ from zigp.optim import ParamSet, lbfgsb, AdamGroups, DenseDeviceFit, WhiteDevice
 from zigp.transforms import positive, Log1pe, Identity, LowerTriangular
 from .param import Param, DataHolder, Parameterized
 from .mean_functions import MeanFunction, Zero, Linear
-from zigp._lib import MAX_D, DEVICE_FIT_MAX_D
+from zigp._lib import MAX_D, DEVICE_FIT_MAX_D, KERNELS, MATERN_MAX_D
 
 JITTER = 1e-6   # gpflow settings.numerics.jitter_level default (OnOffSVGP.py:96-97) [GPflow-recall]
 DEVICE_FIT_CALL = 200   # iterations per zigp_fit_steps / zigp_fit_steps_mode call of optimize(method='adam'): one synchronisation each
@@ -43,6 +45,13 @@ class OnOffSVGP(Parameterized):
         if X.shape[1] > DEVICE_FIT_MAX_D and type(self.mean_function) is Linear:
             raise ValueError('a Linear mean function covers D <= %d input columns (D = %d); Zero and Constant work at every D'
                              % (DEVICE_FIT_MAX_D, X.shape[1]))
+        for tag, kern in (('kernf', kernf), ('kerng', kerng)):
+            kind = getattr(kern, 'kind', 'rbf')
+            if kind not in KERNELS:
+                raise ValueError("%s has the unknown kernel kind %r: onoffgpf.kernels has RBF, Matern32 and Matern52" % (tag, kind))
+            if kind != 'rbf' and X.shape[1] > MATERN_MAX_D:
+                raise ValueError('%s is a %s kernel and D = %d: the Matern kernels cover D <= %d input columns'
+                                 % (tag, type(kern).__name__, X.shape[1], MATERN_MAX_D))
         self.name = name
         self.kernf, self.kerng, self.likelihood = kernf, kerng, likelihood
         self.whiten, self.q_diag = bool(whiten), bool(q_diag)        # :33-34 (whiten: the branch of :88-91,133,137; q_diag: :59-71,88-89)
@@ -84,6 +93,9 @@ class OnOffSVGP(Parameterized):
             mf['whiten'] = True          # the engine sets its mode from this on every call
         if not self.q_diag:
             mf['q_diag'] = False         # likewise (full-covariance q(u): u_*s_sqrt are (M, M, 1))
+        for tag, kern in (('kern_f', self.kernf), ('kern_g', self.kerng)):
+            if getattr(kern, 'kind', 'rbf') != 'rbf':
+                mf[tag] = kern.kind      # likewise (Matern32 / Matern52; a kernel pickled before the kinds existed is an RBF)
         return dict(mf, Zf=self.Zf.value, Zg=self.Zg.value, u_fm=self.u_fm.value, u_gm=self.u_gm.value,
                     u_fs_sqrt=self.u_fs_sqrt.value, u_gs_sqrt=self.u_gs_sqrt.value,
                     ell_f=self.kernf.ell_vector(), ell_g=self.kerng.ell_vector(),
@@ -131,10 +143,17 @@ class OnOffSVGP(Parameterized):
         self._engine.select_rows(idx)
         return float(self.num_data) / float(self.minibatch_size)          # :119-120
 
+    def _matern_kernel(self):
+        """'kernf is a Matern52 kernel' for the first Matern latent, None when both are RBF"""
+        for tag, kern in (('kernf', self.kernf), ('kerng', self.kerng)):
+            if getattr(kern, 'kind', 'rbf') != 'rbf':
+                return '%s is a %s kernel' % (tag, type(kern).__name__)
+        return None
+
     def _device_fit_eligible(self, pset):
-        """the Adam loop can run on the device (zigp_fit_steps): unwhitened, diagonal q(u), Zero mean function, every transform Identity or
-        Log1pe(1e-6), at most DEVICE_FIT_MAX_D input columns"""
-        return self.Xtrain.value.shape[1] <= DEVICE_FIT_MAX_D and not self.whiten and self.q_diag and type(self.mean_function) is Zero and all(
+        """the Adam loop can run on the device (zigp_fit_steps): unwhitened, diagonal q(u), Zero mean function, RBF kernels, every transform
+        Identity or Log1pe(1e-6), at most DEVICE_FIT_MAX_D input columns"""
+        return self._matern_kernel() is None and self.Xtrain.value.shape[1] <= DEVICE_FIT_MAX_D and not self.whiten and self.q_diag and type(self.mean_function) is Zero and all(
             type(q.transform) is Identity or (isinstance(q.transform, Log1pe) and q.transform._lower == 1e-6) for q in pset.params.values())
 
     def _adam_on_device(self, pset, maxiter):
@@ -196,6 +215,9 @@ class OnOffSVGP(Parameterized):
                     raise ValueError('device_loop=True: a callback wants the host every step (device_loop=False, or no callback)')
                 if type(self.mean_function) is not Zero:
                     raise ValueError('device_loop=True: the device loop fits the Zero mean function only (mean-function parameters stay with the host loop)')
+                if self._matern_kernel() is not None:
+                    raise ValueError('device_loop=True: %s and the device loop fits RBF latents only; device_loop=False or None runs the '
+                                     'host loop' % self._matern_kernel())
                 if self.Xtrain.value.shape[1] > DEVICE_FIT_MAX_D:
                     raise ValueError('device_loop=True: the device loop covers D <= %d input columns (D = %d); device_loop=False or None '
                                      'runs the host loop' % (DEVICE_FIT_MAX_D, self.Xtrain.value.shape[1]))

@@ -11,6 +11,9 @@ ZIGP_OK, ZIGP_EARG, ZIGP_EHIP, ZIGP_ENOTPD, ZIGP_ECOMM = 0, -1, -2, -3, -4
 COMM_ID_BYTES = 128
 NCLASS = 10
 LIK_ONOFF, LIK_GAUSSIAN, LIK_BERNOULLI = 0, 1, 2   # include/zigp.h ZIGP_LIK_*
+KERN_RBF, KERN_MATERN32, KERN_MATERN52 = 0, 1, 2   # include/zigp.h ZIGP_KERN_*: kernel family of a dense latent (zigp_set_kernel)
+KERNELS = {'rbf': KERN_RBF, 'matern32': KERN_MATERN32, 'matern52': KERN_MATERN52}
+MATERN_MAX_D = 8     # the Matern kernels cover the input dimensions of the per-dimension kernels (csrc/zigp_kernels.h MAXD)
 PROF_CLASSES = ('gemm_A1', 'gemm_A2', 'gemm_H', 'gemm_J', 'syrk', 'kuf_build', 'pointwise', 'kgrad', 'mxm_stage', 'other')
 PROF_KERNELS = {'gemm_A1': 'gemm_f64_kernel<1,1,2,false,1,8,EpiStoreColsum> (A1 = W K, W read through W^T)',
                 'gemm_A2': 'gemm_f64_kernel<1,1,2,false,2,8,EpiColsum> (A2 = W^T A1, reduced to the column sums sum_m s^2 A2^2 in the epilogue; the panel is not stored; value-only ELBO and predict only)',
@@ -181,6 +184,9 @@ SIGNATURES = {
     'zigp_get_whiten': (C.c_int, [C.c_void_p]),
     'zigp_set_q_full': (C.c_int, [C.c_void_p, C.c_int32]),
     'zigp_get_q_full': (C.c_int, [C.c_void_p]),
+    'zigp_set_kernel': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    'zigp_get_kernel': (C.c_int, [C.c_void_p, C.c_int32]),
+    'zigp_kern_K': (C.c_int, [C.c_void_p, C.c_int32, dp, C.c_int64, dp, C.c_int64, C.c_int32, dp, C.c_double, dp]),
     'zigp_kron_head_elbo': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_int32, dp, dp, C.c_int64, C.c_double, C.c_double,
                                       C.c_double, C.c_int32, dp, dp, C.POINTER(zigp_kron_grads), dp]),
     'zigp_kron_head_elbo_rows': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_double,
@@ -205,6 +211,8 @@ SIGNATURES = {
     'zigp_test_q_full_forward': (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp]),
     'zigp_test_q_full_dlq': (C.c_int, [C.c_void_p, C.c_int32, dp, dp, C.c_int32, dp]),
     'zigp_test_kgrad': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int32, dp]),
+    'zigp_test_kuf_kind': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, dp, dp, dp, C.c_double, dp, dp]),
+    'zigp_test_kgrad_kind': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, dp, dp, dp, dp, dp]),
     'zigp_test_rank_update': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(dp), C.POINTER(dp), dp, C.POINTER(C.c_int64)]),
     'zigp_test_mxm_backward': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_mxm)]),
     'zigp_test_dense_pack': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_pack)]),

@@ -26,6 +26,21 @@ def _check(lib, ctx, rc):
     raise ZigpError('libzigp error %d: %s' % (rc, msg))
 
 
+def kernel_kinds(p, D=None):
+    """(kind of f, kind of g) from p.get('kern_f', 'rbf') / p.get('kern_g', 'rbf') -- 'rbf', 'matern32' or 'matern52' (_lib.KERNELS).
+    ValueError, before any device work, for an unknown name and for a Matern latent at D > 8."""
+    kinds = []
+    for tag in 'fg':
+        name = p.get('kern_' + tag, 'rbf')
+        if not isinstance(name, str) or name.lower() not in _lib.KERNELS:
+            raise ValueError("kern_%s = %r: the dense path knows the kernels 'rbf', 'matern32' and 'matern52'" % (tag, name))
+        kinds.append(_lib.KERNELS[name.lower()])
+        if D is not None and kinds[-1] != _lib.KERN_RBF and D > _lib.MATERN_MAX_D:
+            raise ValueError('kern_%s = %r and D = %d: the Matern kernels cover D in [1, %d] (the wide kernels are RBF only)'
+                             % (tag, name, D, _lib.MATERN_MAX_D))
+    return tuple(kinds)
+
+
 class _Packed:
     """Keeps the numpy arrays behind a zigp_params struct alive."""
 
@@ -37,6 +52,7 @@ class _Packed:
         if not 1 <= D <= _lib.MAX_D:
             raise ValueError('D = %d: the dense path takes input dimensions 1 .. %d (ZIGP_MAX_D)' % (D, _lib.MAX_D))
         self.D, self.Mf, self.Mg = D, Zf.shape[0], Zg.shape[0]
+        self.kinds = kernel_kinds(p, D)     # p['kern_f'] / p['kern_g']: the kernel family of each latent (zigp_set_kernel)
 
         def ell(v):
             v = as_f64(v).reshape(-1)
@@ -305,9 +321,26 @@ class DenseEngine:
     def get_q_full(self):
         return bool(self.lib.zigp_get_q_full(self.ctx))
 
+    def set_kernel(self, latent, name):
+        """Kernel family of a dense latent (zigp_set_kernel; the kernel object handed to the reference model, onoffgpf/OnOffSVGP.py:22):
+        latent 'f' / 0 or 'g' / 1; name 'rbf', 'matern32' or 'matern52' (GPflow 0.4.0 kernels.RBF / Matern32 / Matern52).  elbo, predict,
+        predict_device and prior_kl set both from p.get('kern_f', 'rbf') / p.get('kern_g', 'rbf') on every call, like the whitening."""
+        if not isinstance(name, str) or name.lower() not in _lib.KERNELS:
+            raise ValueError("kernel %r: the dense path knows 'rbf', 'matern32' and 'matern52'" % (name,))
+        _check(self.lib, self.ctx, self.lib.zigp_set_kernel(self.ctx, {'f': 0, 'g': 1}.get(latent, latent), _lib.KERNELS[name.lower()]))
+
+    def get_kernel(self, latent):
+        k = self.lib.zigp_get_kernel(self.ctx, {'f': 0, 'g': 1}.get(latent, latent))
+        if k < 0:
+            raise ValueError('zigp_get_kernel: latent must be f / 0 or g / 1')
+        return {v: n for n, v in _lib.KERNELS.items()}[k]
+
     def _set_modes(self, p):
+        kinds = kernel_kinds(p)          # an unknown name raises before anything is set
         self.set_whiten(p.get('whiten', False))
         self.set_q_full(not p.get('q_diag', True))
+        for h in (0, 1):
+            _check(self.lib, self.ctx, self.lib.zigp_set_kernel(self.ctx, h, kinds[h]))
 
     def elbo(self, p, jitter=1e-6, scale=1.0, g_offset=0.0, rows=None, include_kl=True, need_grad=True):
         """Returns (elbo_data, kl, grads or None); ELBO = elbo_data - kl.  p['whiten'] = True: the whitened parametrisation (set_whiten);
@@ -364,6 +397,12 @@ class DenseEngine:
     def _fit_call(self, mode, shape, x, m, v, lr, positive, trainable, ell_size, t0, n_steps, rows, batch, jitter, scale, beta1, beta2, eps,
                   include_kl):
         """mode None: zigp_fit_steps; otherwise zigp_fit_steps_mode"""
+        for tag, kind in zip('fg', kernel_kinds(shape)):      # the device loops fit RBF latents (the library refuses too: ZIGP_EARG)
+            if kind != _lib.KERN_RBF:
+                raise ValueError('kern_%s = %r: the device fit loops fit RBF latents only; a Matern model is fitted by elbo + a host '
+                                 'optimiser (OnOffSVGP.optimize runs its host loop)' % (tag, shape['kern_' + tag]))
+        for h in (0, 1):      # both RBF here; not left to whatever model used the engine before
+            _check(self.lib, self.ctx, self.lib.zigp_set_kernel(self.ctx, h, _lib.KERN_RBF))
         s = _lib.zigp_params()
         s.Mf, s.Mg, s.D = int(shape['Mf']), int(shape['Mg']), int(shape['D'])
         o = _lib.zigp_fit_opts()
@@ -459,6 +498,22 @@ class DenseEngine:
         out = np.zeros((X1.shape[0], X2a.shape[0]))
         _check(self.lib, self.ctx, self.lib.zigp_rbf_K(self.ctx, ptr(X1), X1.shape[0], None if X2 is None else ptr(X2a), X2a.shape[0], D,
                                                         ptr(ell), float(np.squeeze(var)), ptr(out)))
+        return out
+
+    def kern_K(self, kind, X1, X2, ell, var):
+        """K(X1, X2) of the kernel `kind` ('rbf', 'matern32', 'matern52'), no jitter (zigp_kern_K; gpflow kernels.Stationary.K);
+        X2 None: K(X1, X1), whose diagonal is the formula at r = 1e-6 for the Matern kinds."""
+        if not isinstance(kind, str) or kind.lower() not in _lib.KERNELS:
+            raise ValueError("kernel %r: the dense path knows 'rbf', 'matern32' and 'matern52'" % (kind,))
+        X1 = as_f64(X1)
+        D = X1.shape[1]
+        X2a = X1 if X2 is None else as_f64(X2)
+        ell = as_f64(ell).reshape(-1)
+        if ell.size == 1:
+            ell = np.full(D, float(ell[0]))
+        out = np.zeros((X1.shape[0], X2a.shape[0]))
+        _check(self.lib, self.ctx, self.lib.zigp_kern_K(self.ctx, _lib.KERNELS[kind.lower()], ptr(X1), X1.shape[0], None if X2 is None else ptr(X2a),
+                                                         X2a.shape[0], D, ptr(ell), float(np.squeeze(var)), ptr(out)))
         return out
 
     # ---- Kronecker (space x time) variant -------------------------------------------------------
@@ -793,6 +848,38 @@ class DenseEngine:
         ell = as_f64(np.broadcast_to(np.asarray(ell, dtype=np.float64), (D,)))
         out = np.zeros((M, N))
         _check(self.lib, self.ctx, self.lib.zigp_test_kuf(self.ctx, N, M, D, ptr(X), ptr(Z), ptr(ell), float(var), ptr(out)))
+        return out
+
+    def test_kuf_kind(self, kind, X, Z, ell, var, grad=True):
+        """(K, K') as a call with kernel `kind` on the latent builds its Kuf panel (zigp_test_kuf_kind): both (Mp16, N) with Mp16 = M
+        rounded up to 16, the padded rows included (zeros); K' = -dk / d(r2 / 2) is the derivative panel of a gradient step (None with
+        grad=False, where the launch is the value-only one)."""
+        X, Z = as_f64(X), as_f64(Z)
+        if X.ndim == 1: X = X[:, None]
+        if Z.ndim == 1: Z = Z[:, None]
+        N, D = X.shape
+        M = Z.shape[0]
+        Mp16 = (M + 15) // 16 * 16
+        ell = as_f64(np.broadcast_to(np.asarray(ell, dtype=np.float64), (D,)))
+        K = np.zeros((Mp16, N))
+        Kd = np.zeros((Mp16, N)) if grad else None
+        _check(self.lib, self.ctx, self.lib.zigp_test_kuf_kind(self.ctx, _lib.KERNELS[kind], N, M, D, ptr(X), ptr(Z), ptr(ell), float(var), ptr(K),
+                                                                None if Kd is None else ptr(Kd)))
+        return K, Kd
+
+    def test_kgrad_kind(self, kind, Jp, K, Kd, alpha, gm, gv, X, Z, n0=0, krow=None):
+        """test_kgrad for a kernel kind (zigp_test_kgrad_kind): the moment columns are taken with F Kd, columns 0 and 1 + 2D with K."""
+        X, Z = as_f64(X), as_f64(Z)
+        if X.ndim == 1: X = X[:, None]
+        if Z.ndim == 1: Z = Z[:, None]
+        M, D = Z.shape
+        K = as_f64(K)
+        Nc = K.shape[1]
+        K, Kd, Jp = as_f64(K, (M, Nc)), as_f64(Kd, (M, Nc)), as_f64(Jp, (M, Nc))
+        alpha, gm, gv = as_f64(alpha, (M,)), as_f64(gm, (Nc,)), as_f64(gv, (Nc,))
+        out = np.zeros((_lib.KG_SPLIT, M, 2 + 2 * D)) if krow is None else np.array(as_f64(krow, (_lib.KG_SPLIT, M, 2 + 2 * D)), copy=True)
+        _check(self.lib, self.ctx, self.lib.zigp_test_kgrad_kind(self.ctx, _lib.KERNELS[kind], M, D, Nc, X.shape[0], int(n0), ptr(Jp), ptr(K), ptr(Kd),
+                                                                  ptr(alpha), ptr(gm), ptr(gv), ptr(X), ptr(Z), ptr(out)))
         return out
 
     def test_potrf_trtri(self, A, split_k=False):
