@@ -261,6 +261,50 @@ typedef struct zigp_stage_pack {
 } zigp_stage_pack;
 int zigp_test_dense_pack(zigp_ctx* ctx, const zigp_stage_pack* a);
 
+/* ---- Kronecker path: ONE launch of a point-wise or per-point panel kernel (csrc/zigp_kron.hip) on caller-supplied operands, with the grid
+ * its production callers use.  Host arrays in, host arrays out; every call synchronises and leaves the context usable. ---- */
+/* The point-wise launch of a Kronecker call: k_kron_pointwise<PREDICT> (lik = ZIGP_LIK_ONOFF), k_kron_head_pointwise<PREDICT, false>, or, with
+ * dev_hyp = 1 on a head, k_kron_head_pointwise<false, true> (modes 0 and 1 only: no call launches the heads' predict kernel on the device
+ * block).  Grid Nc / 256 blocks of 256 points.  dev_hyp = 0: Knn = var0 var1 per latent, the noise and f_offset go in by value, as the
+ * panel path passes them.  dev_hyp = 1: they are read from a device hyperparameter block filled by the host code of the fused path (the
+ * factor records' variances, the noise; f_offset in the slot a device fit step keeps f_mu in -- the OnOff kernel takes f_offset by value in
+ * either case), and the by-value fields are zero. */
+typedef struct zigp_stage_kron_pointwise {
+  int32_t lik;            /* ZIGP_LIK_ONOFF / ZIGP_LIK_GAUSSIAN / ZIGP_LIK_BERNOULLI */
+  int32_t mode;           /* 0 value-only ELBO (the launch with gm_f == NULL), 1 gradient step, 2 predict */
+  int32_t dev_hyp;        /* 0 / 1 */
+  int32_t sentinel_out;   /* 1: every output buffer holds ZIGP_STAGE_SENTINEL_BYTE before the launch (0: zeros) */
+  int64_t N, Nc;          /* valid points; points launched: a multiple of 256, >= N */
+  int64_t ld_out;         /* predict: leading dimension of out, >= N (0: N, as the real calls) */
+  const double* part_f;   /* [4][Nc]: q0, q1, mean, st */
+  const double* part_g;   /* [4][Nc] (OnOff; the heads do not read it, may be NULL) */
+  const double* Y;        /* [N] (NULL: predict) */
+  double var0f, var1f, var0g, var1g, noise, g_offset, f_offset, scale;
+  double *gm_f, *gv_f, *dq0_f, *dq1_f, *gm_g, *gv_g, *dq0_g, *dq1_g;   /* out [Nc] each, modes 0 and 1, any of them NULL; the buffers as the
+                             launch left them -- mode 0 writes none of them, a head none of the g ones */
+  double* acc;            /* out [Nc / 256][5], modes 0 and 1: ve, d noise, sum gv_f, sum gv_g, sum gm_f per block */
+  double* out;            /* out [9 or 4][ld_out], predict */
+} zigp_stage_kron_pointwise;
+int zigp_test_kron_pointwise(zigp_ctx* ctx, const zigp_stage_kron_pointwise* a);
+
+/* The panel path's per-point kernels, one launch each with the grid of latent_forward_panels / latent_backward.  Nc: a multiple of 256; panels
+ * are row-major with Nc columns.  Output buffers hold the stage sentinel before the launch. */
+/* k_kron_kbuild: K (Mq, Nc), Mq = M rounded up to 128, = var exp(-0.5 |(z_m - x_n[col0 : col0 + D]) / ell|^2); X (N, ldx), Z (M, D), ell (D).
+ * The whole padded panel is returned: rows m >= M (zeros) and columns n >= N (the kernel at x = 0). */
+int zigp_test_kron_kbuild(zigp_ctx* ctx, int64_t N, int64_t Nc, int32_t ldx, int32_t col0, int32_t M, int32_t D, const double* X, const double* Z,
+                          const double* ell, double var, double* K);
+/* k_kron_colsum: part [4][Nc] = column sums of K0.A0, K1.A1, K0.B1 and A0sq.C1; K0, A0, B1, A0sq, C1 (M0, Nc), K1, A1 (M1, Nc). */
+int zigp_test_kron_colsum(zigp_ctx* ctx, int32_t M0, int32_t M1, int64_t Nc, const double* K0, const double* A0, const double* K1, const double* A1,
+                          const double* B1, const double* A0sq, const double* C1, double* part);
+/* k_kron_da: dA = 2 A gv C, E = dq K + dA over a panel of M rows (padded with zero rows to a multiple of 128 on the device, as the panels
+ * of a step are); A, C, K, dA, E (M, Nc), gv, dq (Nc). */
+int zigp_test_kron_da(zigp_ctx* ctx, int32_t M, int64_t Nc, const double* A, const double* C, const double* K, const double* gv, const double* dq,
+                      double* dA, double* E);
+/* k_kron_kgrad: krow (M, 2 + 2D), in: initial values, out: with the row's sums over the columns n < N added to columns 0 .. 2D (the last
+ * column is not touched); B, A, PdA, K (M, Nc), gm, dq (Nc), X (N, ldx), Z (M, D). */
+int zigp_test_kron_kgrad(zigp_ctx* ctx, int32_t M, int32_t D, int64_t N, int64_t Nc, int32_t ldx, int32_t col0, const double* B, const double* A,
+                         const double* PdA, const double* K, const double* gm, const double* dq, const double* X, const double* Z, double* krow);
+
 #ifdef __cplusplus
 }
 #endif

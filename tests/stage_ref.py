@@ -605,3 +605,196 @@ def dense_pack_ref(lat_f, lat_g, pw, D, mode='diag', include_kl=True):
             klp = (-1.0 / s + q['kl_vec2'] * s) if include_kl else np.zeros(M)
             r[tag + 'ds'] = (2.0 * s * q['dsq'] - klp, gamma(6) * (np.abs(2.0 * s * q['dsq']) + (np.abs(1.0 / s) + np.abs(q['kl_vec2'] * s) if include_kl else 0.0)))
     return r
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Kronecker path (csrc/zigp_kron.hip): the point-wise launches k_kron_pointwise / k_kron_head_pointwise and the panel path's per-point
+# kernels k_kron_kbuild, k_kron_colsum, k_kron_da, k_kron_kgrad (tests/test_gpu_kron_stages.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+KPW_THREADS, KPW_ACC = 256, 5
+TINY = 2.0 ** -960          # floor of every head scale: a result that underflows (exp(-z^2 / 2) at |z| ~ 38 ... 40) is not held to relative accuracy
+_MP_CACHE = {}
+
+
+def pointwise_mp_cached(fm, fv, gm, gv, y, noise):
+    """pointwise_mp, remembered per set of evaluation points: the dense and the Kronecker grid tests evaluate at the same doubles."""
+    key = tuple(np.ascontiguousarray(a, dtype=np.float64).tobytes() for a in (fm, fv, gm, gv, y)) + (float(noise),)
+    if key not in _MP_CACHE:
+        _MP_CACHE[key] = pointwise_mp(fm, fv, gm, gv, y, noise)
+    return _MP_CACHE[key]
+
+
+def kron_pw_inputs(part, knn, offset):
+    """(mean, var) as the Kronecker point-wise kernels form them from part [4][Nc] = q0, q1, mean, st: mean + offset and
+    knn - q0 q1 + st (scripts/onoff.py:209-211).  The kernel may contract knn - q0 q1 into one fma: callers that need bit-equality use
+    operands for which every association is exact."""
+    return part[2] + offset, knn - part[0] * part[1] + part[3]
+
+
+HEAD_OUTPUTS = ('ve', 'dfm', 'dfv', 'dnoise', 'pm', 'pv')
+
+
+def head_np(lik, fm, fv, y, noise):
+    """float64 numpy statement of the single-latent heads (k_kron_head_pointwise), operation by operation.
+    'gaussian' (scripts/svgp.py:198-200): ve = -1/2 log 2 pi - 1/2 log s2 - 1/2 ((y - fm)^2 + fv) / s2; predictive density of y: (fm, fv + s2).
+    'bernoulli' (scripts/classifier.py:139-140, 210-217): p = c0 + c1 Phi(fm / sqrt(1 + fv)), ve = log(p if y == 1 else 1 - p); (p, p - p^2)."""
+    from scipy.special import erf
+    fm, fv, y = (np.asarray(a, dtype=np.float64) for a in (fm, fv, y))
+    if lik == 'gaussian':
+        inv, res = 1.0 / noise, y - fm
+        q = res * res + fv
+        return dict(ve=-0.5 * LOG2PI - 0.5 * np.log(noise) - 0.5 * q * inv, dfm=res * inv, dfv=-0.5 * inv * np.ones_like(fm),
+                    dnoise=-0.5 * inv + 0.5 * q * inv * inv, pm=fm.copy(), pv=fv + noise)
+    r = 1.0 / np.sqrt(1.0 + fv)
+    z = fm * r
+    pr = 0.5 * (1.0 + erf(z * 0.70710678118654752440)) * C1 + C0
+    on = y == 1.0
+    w = np.where(on, pr, 1.0 - pr)
+    dp = np.where(on, 1.0, -1.0) / w
+    dz = dp * C1 * 0.39894228040143267794 * np.exp(-0.5 * z * z)
+    return dict(ve=np.log(w), dfm=dz * r, dfv=dz * (-0.5 * z / (1.0 + fv)), dnoise=np.zeros_like(fm), pm=pr, pv=pr - pr * pr)
+
+
+def head_mp(lik, fm, fv, y, noise, dps=50):
+    """The same formulas at 50 digits (mpmath), point by point, the clip p = c0 + c1 Phi(z) included; y == 1 exactly is 'on', anything
+    else 'off'.  Phi through mpmath's ncdf, which keeps its relative accuracy in the lower tail.  Returns dict of object arrays of mpf."""
+    import mpmath as mp
+    mp.mp.dps = dps
+    n = len(fm)
+    out = {k: np.empty(n, dtype=object) for k in HEAD_OUTPUTS}
+    c1, c0, one, half, two = mp.mpf(1) - mp.mpf('2e-3'), mp.mpf('1e-3'), mp.mpf(1), mp.mpf('0.5'), mp.mpf(2)
+    s2 = mp.mpf(float(noise))
+    for i in range(n):
+        f_, v_, y_ = (mp.mpf(float(x[i])) for x in (fm, fv, y))
+        if lik == 'gaussian':
+            res = y_ - f_
+            q = res * res + v_
+            vals = (-half * mp.log(two * mp.pi) - half * mp.log(s2) - half * q / s2, res / s2, -half / s2, -half / s2 + half * q / (s2 * s2), f_, v_ + s2)
+        else:
+            z = f_ / mp.sqrt(one + v_)
+            pr = c0 + c1 * mp.ncdf(z)
+            on = y_ == one
+            w = pr if on else one - pr
+            dz = (one if on else -one) / w * c1 * mp.npdf(z)
+            vals = (mp.log(w), dz / mp.sqrt(one + v_), dz * (-half * z / (one + v_)), mp.mpf(0), pr, pr - pr * pr)
+        for k, val in zip(HEAD_OUTPUTS, vals):
+            out[k][i] = val
+    return out
+
+
+def head_scales(lik, fm, fv, y, noise):
+    """S per output: the sum of the magnitudes it is formed from (as pointwise_scales), floored at TINY.
+    Gaussian, q = (y - fm)^2 + fv: ve: 1 + 1/2 |log s2| + 2 q / s2; dnoise: 1/2 / s2 + q / s2^2; dfm, dfv, pm, pv: the value's magnitude.
+    Bernoulli, z = fm / sqrt(1 + fv), S_w = 1 + phi(z) |z| (Phi is an O(1) quantity formed with absolute error; the argument's own
+    rounding moves it by phi |z| eps), w = p or 1 - p as y selects: ve = log w: |ve| + S_w / w; pm: S_w; pv = p - p^2: p + p^2 +
+    S_w |1 - 2 p|; dfm, dfv = +-c1 phi(z) / w times O(1) factors: |value| (4 + z^2 + S_w / w) -- the roundings of the factors, the z^2 of
+    exp(-z^2 / 2)'s argument, and w's relative error."""
+    r = head_np(lik, fm, fv, y, noise)
+    fm, fv, y = (np.asarray(a, dtype=np.float64) for a in (fm, fv, y))
+    if lik == 'gaussian':
+        q = (y - fm) ** 2 + fv
+        S = dict(ve=1.0 + 0.5 * abs(np.log(noise)) + 2.0 * q / noise, dnoise=0.5 / noise + q / noise ** 2, dfm=np.abs(r['dfm']), dfv=np.abs(r['dfv']),
+                 pm=np.abs(fm), pv=np.abs(r['pv']))
+    else:
+        z = fm / np.sqrt(1.0 + fv)
+        Sw = 1.0 + np.exp(-0.5 * z * z) / np.sqrt(2 * np.pi) * np.abs(z)
+        pr = r['pm']
+        w = np.where(y == 1.0, pr, 1.0 - pr)
+        f = 4.0 + z * z + Sw / w
+        S = dict(ve=np.abs(r['ve']) + Sw / w, pm=Sw, pv=pr + pr * pr + Sw * np.abs(1.0 - 2.0 * pr), dfm=np.abs(r['dfm']) * f, dfv=np.abs(r['dfv']) * f,
+                 dnoise=np.zeros_like(fm))
+    return {k: np.maximum(v, TINY) for k, v in S.items()}
+
+
+def kron_kbuild(X, col0, Z, ell, var, Nc, dtype=np.float64):
+    """k_kron_kbuild: K (M, Nc) = var exp(-1/2 |(z_m - x_n[col0 : col0 + D]) / ell|^2); the padding columns n >= N are the kernel at
+    x = 0.  Returns (K, y) with y = -log(K / var), the exponent the kuf tolerance is stated in."""
+    f = lambda a: np.asarray(a, dtype=dtype)
+    M, D = Z.shape
+    xs = np.zeros((Nc, D), dtype=dtype)
+    xs[:X.shape[0]] = f(X)[:, col0:col0 + D]
+    d = (f(Z)[:, None, :] - xs[None, :, :]) / f(ell)
+    y = dtype(0.5) * (d * d).sum(-1)
+    return dtype(var) * np.exp(-y), y
+
+
+def kron_colsum(K0, A0, K1, A1, B1, A0sq, C1, dtype=np.float64):
+    """k_kron_colsum: part [4][Nc] = sum_i K0 A0, sum_j K1 A1, sum_i K0 B1, sum_i A0sq C1.  Bound of the GPU side alone (the caller adds the
+    reference's own: the same again for float64, 2^-11 of it for longdouble): sums of M products, gamma_(M+2) sum |a b|."""
+    f = lambda a: np.asarray(a, dtype=dtype)
+    K0, A0, K1, A1, B1, A0sq, C1 = (f(a) for a in (K0, A0, K1, A1, B1, A0sq, C1))
+    prods = (K0 * A0, K1 * A1, K0 * B1, A0sq * C1)
+    out = np.stack([p.sum(0) for p in prods])
+    bnd = np.stack([gamma(p.shape[0] + 2) * np.abs(p).sum(0) for p in prods])
+    return out, np.asarray(bnd, dtype=np.float64)
+
+
+def kron_da(A, C, K, gv, dq, dtype=np.float64):
+    """k_kron_da: dA = 2 A gv C, E = dq K + dA.  Bounds: three roundings, gamma_3 |dA|; E one product and one sum more: gamma_4 (|dq K| + |dA|)."""
+    f = lambda a: np.asarray(a, dtype=dtype)
+    A, C, K, gv, dq = f(A), f(C), f(K), f(gv)[None, :], f(dq)[None, :]
+    dA = 2 * A * gv * C
+    E = dq * K + dA
+    return (dA, np.asarray(gamma(3) * np.abs(dA), dtype=np.float64)), (E, np.asarray(gamma(4) * (np.abs(dq * K) + np.abs(dA)), dtype=np.float64))
+
+
+def kron_kgrad(B, A, PdA, K, gm, dq, X, col0, Z, krow0=None, dtype=np.float64):
+    """k_kron_kgrad: dK = gm B + 2 dq A + PdA; krow[m] += [sum dK K, sum dK K (x_d - z_md), sum dK K (x_d - z_md)^2] over the N = len(X) valid
+    columns (x: the columns col0 : col0 + D of X); the last column of krow is not touched.  Returns (krow (M, 2 + 2D), bound).
+    Bound of the GPU side alone, as kgrad's: with T_mn = (|gm B| + 2 |dq A| + |PdA|) |K|, gamma_(N+9) (sum_n T |x - z|^p + |krow0|): the
+    sum of N terms, 8 spare roundings for dK (4), its product with K, x - z and the moment factors, one for the accumulation."""
+    f = lambda a: np.asarray(a, dtype=dtype)
+    M, D = Z.shape
+    N = X.shape[0]
+    B, A, PdA, K, gm, dq, Xc, Zc = f(B)[:, :N], f(A)[:, :N], f(PdA)[:, :N], f(K)[:, :N], f(gm)[None, :N], f(dq)[None, :N], f(X)[:, col0:col0 + D], f(Z)
+    t = (gm * B + 2 * dq * A + PdA) * K
+    T = (np.abs(gm * B) + 2 * np.abs(dq * A) + np.abs(PdA)) * np.abs(K)
+    out = np.zeros((M, 2 + 2 * D), dtype=dtype) if krow0 is None else f(krow0).copy()
+    bnd = np.abs(out)
+    bnd[:, 1 + 2 * D] = 0
+    out[:, 0] += t.sum(1)
+    bnd[:, 0] += T.sum(1)
+    for d in range(D):
+        df = Xc[None, :, d] - Zc[:, None, d]
+        out[:, 1 + d] += (t * df).sum(1)
+        out[:, 1 + D + d] += (t * df * df).sum(1)
+        bnd[:, 1 + d] += (T * np.abs(df)).sum(1)
+        bnd[:, 1 + D + d] += (T * df * df).sum(1)
+    return out, np.asarray(gamma(N + 9) * bnd, dtype=np.float64)
+
+
+def kron_dyadic_case(seed=0, Nc=1024):
+    """Operands of the Kronecker point-wise launch for which the evaluation point is EXACT: q0, q1, mean, st, the factor variances (and so
+    Knn = var0 var1) and the offsets are multiples of 2^-10 of magnitude <= 2^6, so q0 q1 is a multiple of 2^-20 below 2^12 and
+    Knn - q0 q1 + st, mean + offset need at most 33 bits in every association, with or without fma
+    (tests/test_cpu_stage_ref.py walks the associations in exact rationals).  Points 0 and 1 cancel terms of size 32 (latent f; 10 for
+    latent g) down to 2^-20.  Elsewhere the variance stays above 1."""
+    rs = np.random.RandomState(4000 + seed)
+    u = 2.0 ** -10
+    var_f, var_g = (8.0, 4.0), (2.0, 5.0)
+
+    def planes(a, b):          # cancelling points: (a + u)(b - u) = a b + (b - a) u - u^2, st = (b - a) u  ->  Knn - q0 q1 + st = u^2
+        q0, q1 = rs.randint(0, 3 * 1024, Nc) * u, rs.randint(0, 3 * 1024, Nc) * u
+        mean, st = rs.randint(-4 * 1024, 4 * 1024 + 1, Nc) * u, rs.randint(0, 8 * 1024, Nc) * u
+        q0[0], q1[0], st[0] = a + u, b - u, (b - a) * u
+        q0[1], q1[1], st[1] = -(a + u), -(b - u), (b - a) * u
+        return np.stack([q0, q1, mean, st])
+
+    return dict(part_f=planes(4.0, 8.0), part_g=planes(2.0, 5.0), var_f=var_f, var_g=var_g, f_offset=0.25, g_offset=-1.0, scale=2.5, noise=0.0625)
+
+
+def kron_panel_operands(kind, M, D, N, Nc, seed, M1=None, col0=2):
+    """Operands of the panel kernels.  kind 'int': integers in {-3 .. 3} -- every product and every sum of the four kernels is then an
+    integer far below 2^53 (the largest: 1000 terms of |dK K (x - z)^2| <= 30 * 3 * 36), so any order of evaluation, with or without fma,
+    gives the same double; 'normal': standard normal panels, K in (0, 1), inputs in (0, 1).  X is (N, ldx) with ldx = col0 + D + 1: the
+    factor reads the columns col0 : col0 + D."""
+    rs = np.random.RandomState(7000 + seed)
+    M1 = M if M1 is None else M1
+    ldx = col0 + D + 1
+    if kind == 'int':
+        draw = lambda *s: rs.randint(-3, 4, s).astype(np.float64)
+        pos = draw
+    else:
+        draw, pos = (lambda *s: rs.randn(*s)), (lambda *s: rs.rand(*s))
+    return dict(B=draw(M, Nc), A=draw(M, Nc), PdA=draw(M, Nc), K=pos(M, Nc), C=draw(M, Nc), Asq=pos(M, Nc), K1=pos(M1, Nc), A1=draw(M1, Nc),
+                gm=draw(Nc), gv=draw(Nc), dq=draw(Nc), X=pos(N, ldx), Z=pos(M, D), krow0=draw(M, 2 + 2 * D), col0=col0)

@@ -403,3 +403,99 @@ def test_composed_reverse_stage_is_the_oracle_gradient(mode, D):
         if not rows and mode != 'diag':      # the whitened KL does not see Kuu
             assert not lat['f']['G'].any() and not lat['g']['G'].any()
     print('MXM-PIN %s D=%d largest rel diff over all blocks %.2e' % (mode, D, worst))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Kronecker stage references (tests/test_gpu_kron_stages.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+HEAD_FM = [-40, -8, -3, -1, -1e-3, 0, 1e-3, 1, 3, 8, 40]
+HEAD_FV = [1e-10, 1e-3, 0.1, 1, 10, 1e3, 1e6]
+
+
+@pytest.mark.parametrize('lik,noise', [('bernoulli', 1.0), ('gaussian', 1e-4), ('gaussian', 1e-2), ('gaussian', 1.0)])
+def test_head_reference_alone_is_within_4_eps_S_of_the_truth(lik, noise):
+    """The premise of err_gpu <= 4 err_np + 16 eps S: head_np over the GPU test's grid, at the doubles 1 + (target - 1) the kernel is given,
+    stays below 4 eps S of the 50-digit head_mp on every output, nothing excluded (largest figure on this grid: 1.3)."""
+    ys = [0, 1, 0.5] if lik == 'bernoulli' else [0, 0.7, -3]
+    fm, fv, y = np.array(np.meshgrid(HEAD_FM, HEAD_FV, ys, indexing='ij'), dtype=np.float64).reshape(3, -1)
+    fv = 1.0 + (fv - 1.0)
+    ref, truth, S = sr.head_np(lik, fm, fv, y, noise), sr.head_mp(lik, fm, fv, y, noise), sr.head_scales(lik, fm, fv, y, noise)
+    for k in sr.HEAD_OUTPUTS:
+        r = sr.mp_err(ref[k], truth[k]) / (sr.EPS * S[k])
+        i = int(np.argmax(r))
+        print('head %-9s noise %-6g %-6s largest err_np / (eps S) = %.3g at fm %g fv %g y %g' % (lik, noise, k, r[i], fm[i], fv[i], y[i]))
+        assert r[i] < 4.0, (lik, noise, k, r[i])
+    if lik == 'bernoulli':       # y == 1 exactly is 'on'; 0.5 is 'off', as 0
+        on, off, half = y == 1.0, y == 0.0, y == 0.5
+        assert np.array_equal(ref['ve'][off], ref['ve'][half]) and not np.array_equal(ref['ve'][on], ref['ve'][off])
+        assert all(a == b for a, b in zip(truth['ve'][off], truth['ve'][half]))
+
+
+def test_dyadic_evaluation_points_are_exact_in_every_association():
+    """stage_ref.kron_dyadic_case in exact rationals: every partial result of Knn - q0 q1 + st in either association (and the product
+    itself, so also with the product fused into the subtraction) and of mean + offset is a double, so the float64 statement is THE value."""
+    from fractions import Fraction as F
+    c = sr.kron_dyadic_case()
+    exact = lambda x: F(float(x)) == x
+    for part, var, off in ((c['part_f'], c['var_f'], c['f_offset']), (c['part_g'], c['var_g'], c['g_offset'])):
+        knn = var[0] * var[1]
+        mean, fv = sr.kron_pw_inputs(part, knn, off)
+        assert F(knn) == F(var[0]) * F(var[1])
+        for n in range(part.shape[1]):
+            q0, q1, mu, st = (F(float(part[r, n])) for r in range(4))
+            for v in (q0, q1, mu, st):
+                assert (v * 1024).denominator == 1 and abs(v) <= 64
+            prod = q0 * q1
+            steps = (prod, F(knn) - prod, F(knn) - prod + st, F(knn) + st, st - prod, mu + F(off))
+            assert all(exact(s) for s in steps), n
+            assert F(float(fv[n])) == F(knn) - prod + st and F(float(mean[n])) == mu + F(off)
+        assert fv[0] == 2.0 ** -20 and fv[1] == 2.0 ** -20 and abs(part[0, 0] * part[1, 0]) >= var[0] * var[1]
+        assert np.all(fv[2:] > 1.0)
+
+
+@pytest.mark.parametrize('M,D,N', [(5, 1, 1), (16, 3, 257), (33, 8, 1000)])
+def test_kron_panel_restatements_float64_against_longdouble(M, D, N):
+    """float64 against the longdouble evaluation of the same statement, within the statement's own bound (+ 2^-11 of it for the reference)."""
+    Nc = 1024
+    o = sr.kron_panel_operands('normal', M, D, N, Nc, seed=M + D, M1=M + 3)
+    L = np.longdouble
+    a = (o['K'], o['A'], o['K1'], o['A1'], o['B'], o['Asq'], o['C'])
+    (r64, b), (rl, _) = sr.kron_colsum(*a), sr.kron_colsum(*a, dtype=L)
+    assert sr.worst(np.abs(r64 - rl), b * (1 + 2.0 ** -11))[0] <= 1.0
+    a = (o['A'], o['C'], o['K'], o['gv'], o['dq'])
+    for (r64, b), (rl, _) in zip(sr.kron_da(*a), sr.kron_da(*a, dtype=L)):
+        assert sr.worst(np.abs(r64 - rl), b * (1 + 2.0 ** -11))[0] <= 1.0
+    a = (o['B'], o['A'], o['PdA'], o['K'], o['gm'], o['dq'], o['X'], o['col0'], o['Z'])
+    (r64, b), (rl, _) = sr.kron_kgrad(*a, krow0=o['krow0']), sr.kron_kgrad(*a, krow0=o['krow0'], dtype=L)
+    ratio = sr.worst(np.abs(r64 - rl), b * (1 + 2.0 ** -11))[0]
+    print('kron_kgrad float64 / longdouble: largest error / bound %.3g' % ratio)
+    assert ratio <= 1.0
+    assert np.array_equal(r64[:, 1 + 2 * D], o['krow0'][:, 1 + 2 * D])
+    # the columns n >= N are not part of the statement
+    a2 = tuple(np.where(np.arange(Nc) < N, x, 1e300) if isinstance(x, np.ndarray) and x.shape[-1] == Nc else x for x in a)
+    assert np.array_equal(sr.kron_kgrad(*a2, krow0=o['krow0'])[0], r64)
+    K64, y = sr.kron_kbuild(o['X'], o['col0'], o['Z'], np.full(D, 0.7), 1.7, Nc)
+    Kl, yl = sr.kron_kbuild(o['X'], o['col0'], o['Z'], np.full(D, 0.7), 1.7, Nc, dtype=L)
+    assert np.all(np.abs(K64 - Kl) <= (4.0 + 8.0 * yl) * np.finfo(np.float64).eps * Kl + L(5e-324))
+    assert np.array_equal(K64[:, N:], np.repeat(K64[:, N:N + 1], Nc - N, 1)) and K64[:, N:].all()      # the kernel at x = 0, not zero
+
+
+@pytest.mark.parametrize('M,D,N', [(5, 1, 1), (16, 3, 257), (33, 8, 1000)])
+def test_kron_panel_integer_operands_are_exact(M, D, N):
+    """The premise of the bit-equal tier: integer operands, every magnitude sum far below 2^53, and the float64 statement equal to the
+    longdouble one."""
+    Nc = 1024
+    o = sr.kron_panel_operands('int', M, D, N, Nc, seed=M + D, M1=M + 3)
+    for k, v in o.items():
+        if isinstance(v, np.ndarray):
+            assert np.array_equal(v, np.round(v)) and np.max(np.abs(v)) <= 3, k
+    L = np.longdouble
+    a = (o['K'], o['A'], o['K1'], o['A1'], o['B'], o['Asq'], o['C'])
+    (r64, b), (rl, _) = sr.kron_colsum(*a), sr.kron_colsum(*a, dtype=L)
+    assert np.array_equal(r64, rl) and np.max(b) / sr.gamma(M + 2) < 2.0 ** 40
+    a = (o['A'], o['C'], o['K'], o['gv'], o['dq'])
+    for (r64, b), (rl, _) in zip(sr.kron_da(*a), sr.kron_da(*a, dtype=L)):
+        assert np.array_equal(r64, rl) and np.max(np.abs(r64)) <= 63
+    a = (o['B'], o['A'], o['PdA'], o['K'], o['gm'], o['dq'], o['X'], o['col0'], o['Z'])
+    (r64, b), (rl, _) = sr.kron_kgrad(*a, krow0=o['krow0']), sr.kron_kgrad(*a, krow0=o['krow0'], dtype=L)
+    assert np.array_equal(r64, rl) and np.array_equal(r64, np.round(r64)) and np.max(b) / sr.gamma(N + 9) < 2.0 ** 40

@@ -62,7 +62,11 @@ k_kron_kbuild(const double* __restrict__ X, int64_t N, int ldx, int col0, const 
 #pragma unroll
       for (int d = 0; d < MAXD; ++d)
         if (d < h.D) { double t = Z[m * h.D + d] * h.inv_ell[d] - xs[d]; r2 = fma(t, t, r2); }
-      v = h.var * exp(-0.5 * r2);
+      const double a = -0.5 * r2;
+      v = h.var * exp(a);
+      // A subnormal result: exp has already rounded to the subnormal grid and the product with var rounds again (up to 1.4 of the smallest
+      // subnormal off).  exp(a / 2) is normal there, so (var e) e rounds once.  Normal results keep the plain product.
+      if (v < 0x1p-1021) { const double e = exp(0.5 * a); v = (h.var * e) * e; }
     }
     K[(int64_t)m * Nc + n] = v;
   }
@@ -153,11 +157,14 @@ __global__ void __launch_bounds__(PW_THREADS)
 k_kron_head_pointwise(KronPwArgs p, int lik) {
   __shared__ double sh[4];
   const int64_t n = (int64_t)blockIdx.x * PW_THREADS + threadIdx.x;
-  const double knn_f = DEVHYP ? KF_CONST(p.hyp)[KH_VAR] * KF_CONST(p.hyp)[KH_FAC + KH_VAR] : p.knn_f;
+  // Knn as the ROUNDED product the by-value launches are handed, and the variance in one association for every variant: left to the
+  // compiler, the device-block variant fused var_0 var_1 into the subtraction and rounded q0 q1 on its own instead, an ulp of q0 q1 away
+  // from the other launches (what is left of a small predictive variance after the cancellation then differs in its leading digits).
+  const double knn_f = DEVHYP ? __dmul_rn(KF_CONST(p.hyp)[KH_VAR], KF_CONST(p.hyp)[KH_FAC + KH_VAR]) : p.knn_f;
   const double noise = DEVHYP ? KF_CONST(p.hyp)[KH_NOISE] : p.noise;
   const double f_offset = DEVHYP ? KF_CONST(p.hyp)[KH_FMU] : p.f_offset;
   const double q0 = p.part_f[n], q1 = p.part_f[p.Nc + n];
-  const double fm = p.part_f[2 * p.Nc + n] + f_offset, fv = knn_f - q0 * q1 + p.part_f[3 * p.Nc + n];
+  const double fm = p.part_f[2 * p.Nc + n] + f_offset, fv = fma(-q0, q1, knn_f) + p.part_f[3 * p.Nc + n];
   const bool valid = n < p.N;
   const double y = (valid && p.Y) ? p.Y[n] : 0.0;
   double ve, dfm, dfv, dnoise = 0.0, pm, pv;
@@ -914,6 +921,158 @@ int zigp_set_kron_range_tiles(zigp_ctx* c, int32_t tiles) {
 int zigp_set_kron_panels(zigp_ctx* c, int32_t on) {
   if (!c) return ZIGP_EARG;
   c->kron_panels = on != 0;
+  return ZIGP_OK;
+}
+
+}  // extern "C"
+
+// ---- stage diagnostics of the Kronecker path (include/zigp_diag.h): ONE launch of a point-wise or per-point panel kernel on
+// caller-supplied operands, with the grid its production callers use (kron_run_panels / kronf_run, latent_forward_panels, latent_backward) ----
+namespace {
+bool kron_stage_cols_ok(int64_t N, int64_t Nc) { return N >= 1 && Nc >= N && Nc % 256 == 0 && Nc <= (1 << 20); }
+// device buffer of n doubles holding the stage sentinel (fill != 0) or zeros
+int kron_stage_out(zigp_ctx* c, DevBuf& b, size_t n, bool sentinel) {
+  ZIGP_ENSURE(c, b, n);
+  ZIGP_HIP(c, hipMemsetAsync(b.p, sentinel ? ZIGP_STAGE_SENTINEL_BYTE : 0, sizeof(double) * n, c->stream));
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int zigp_test_kron_pointwise(zigp_ctx* c, const zigp_stage_kron_pointwise* s) {
+  if (!c) return ZIGP_EARG;
+  if (!s || (s->lik != ZIGP_LIK_ONOFF && s->lik != ZIGP_LIK_GAUSSIAN && s->lik != ZIGP_LIK_BERNOULLI) || s->mode < 0 || s->mode > 2 ||
+      (s->dev_hyp != 0 && s->dev_hyp != 1) || !kron_stage_cols_ok(s->N, s->Nc) || !s->part_f)
+    return fail_arg(c, "zigp_test_kron_pointwise: bad arguments");
+  const bool two = s->lik == ZIGP_LIK_ONOFF, predict = s->mode == 2, grad = s->mode == 1;
+  if (two && !s->part_g) return fail_arg(c, "zigp_test_kron_pointwise: the OnOff likelihood needs part_g");
+  if (!two && s->dev_hyp && predict) return fail_arg(c, "zigp_test_kron_pointwise: no step launches the heads' predict kernel on the device block");
+  const int64_t N = s->N, Nc = s->Nc, ld = predict ? (s->ld_out ? s->ld_out : N) : N;
+  if (predict ? (!s->out || ld < N) : (!s->Y || !s->acc)) return fail_arg(c, "zigp_test_kron_pointwise: predict needs out (ld_out >= N), the ELBO modes need Y and acc");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  const bool sent = s->sentinel_out != 0;
+  const int blocks = (int)(Nc / PW_THREADS), rows = two ? 9 : 4;
+  DevBuf pf, pg, dy, hyp, acc, out, pt[8];
+  ZIGP_TRY(stage_upload_rows(c, pf, s->part_f, 4, 4, Nc));
+  if (two) ZIGP_TRY(stage_upload_rows(c, pg, s->part_g, 4, 4, Nc));
+  if (s->Y) ZIGP_TRY(stage_upload_rows(c, dy, s->Y, N, N, 1));
+  for (DevBuf& b : pt) ZIGP_TRY(kron_stage_out(c, b, (size_t)Nc, sent));
+  ZIGP_TRY(kron_stage_out(c, acc, (size_t)blocks * KPW_ACC, sent));
+  if (predict) ZIGP_TRY(kron_stage_out(c, out, (size_t)rows * ld, sent));
+  KronPwArgs a;
+  memset(&a, 0, sizeof(a));
+  a.part_f = pf.p; a.part_g = two ? pg.p : pf.p; a.Y = s->Y ? dy.p : nullptr; a.N = N; a.Nc = Nc;
+  a.knn_f = s->var0f * s->var1f; a.knn_g = s->var0g * s->var1g; a.noise = s->noise;      // as kron_run_panels forms them
+  a.g_offset = s->g_offset; a.f_offset = s->f_offset; a.scale = s->scale;
+  a.gm_f = grad ? pt[0].p : nullptr; a.gv_f = pt[1].p; a.dq0_f = pt[2].p; a.dq1_f = pt[3].p;
+  a.gm_g = pt[4].p; a.gv_g = pt[5].p; a.dq0_g = pt[6].p; a.dq1_g = pt[7].p;
+  a.acc = acc.p; a.out9 = predict ? out.p : nullptr; a.ld9 = ld; a.hyp = nullptr;
+  if (s->dev_hyp) {
+    // the block kronf_run stages (kf_fill_hyp); the lengthscale slots are not read by these kernels
+    double H[KH_SIZE], one[MAXD];
+    for (double& v : one) v = 1.0;
+    const KfHostLatent hl[2] = {{{1, 1}, {nullptr, nullptr}, {one, one}, {s->var0f, s->var1f}, nullptr, nullptr},
+                                {{1, 1}, {nullptr, nullptr}, {one, one}, {s->var0g, s->var1g}, nullptr, nullptr}};
+    kf_fill_hyp(H, hl, two ? 2 : 1, 1, 1, s->noise);
+    H[KH_FMU] = s->f_offset;                    // the slot k_fit_update writes f_mu to
+    ZIGP_TRY(stage_upload_rows(c, hyp, H, 1, 1, KH_SIZE));
+    a.hyp = hyp.p;
+    a.knn_f = a.knn_g = a.noise = 0.0;          // a fit call leaves the by-value fields zero
+    if (!two) a.f_offset = 0.0;
+  }
+  if (two) {
+    if (predict) hipLaunchKernelGGL(k_kron_pointwise<true>, dim3(blocks), dim3(PW_THREADS), 0, c->stream, a);
+    else hipLaunchKernelGGL(k_kron_pointwise<false>, dim3(blocks), dim3(PW_THREADS), 0, c->stream, a);
+  } else if (predict) hipLaunchKernelGGL((k_kron_head_pointwise<true, false>), dim3(blocks), dim3(PW_THREADS), 0, c->stream, a, (int)s->lik);
+  else if (s->dev_hyp) hipLaunchKernelGGL((k_kron_head_pointwise<false, true>), dim3(blocks), dim3(PW_THREADS), 0, c->stream, a, (int)s->lik);
+  else hipLaunchKernelGGL((k_kron_head_pointwise<false, false>), dim3(blocks), dim3(PW_THREADS), 0, c->stream, a, (int)s->lik);
+  ZIGP_HIP(c, hipGetLastError());
+  if (predict) ZIGP_TRY(stage_download_rows(c, out.p, s->out, rows, ld));
+  else {
+    double* const host[8] = {s->gm_f, s->gv_f, s->dq0_f, s->dq1_f, s->gm_g, s->gv_g, s->dq0_g, s->dq1_g};
+    for (int i = 0; i < 8; ++i) ZIGP_TRY(stage_download_rows(c, pt[i].p, host[i], 1, Nc));
+    ZIGP_TRY(stage_download_rows(c, acc.p, s->acc, blocks, KPW_ACC));
+  }
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  return ZIGP_OK;
+}
+
+int zigp_test_kron_kbuild(zigp_ctx* c, int64_t N, int64_t Nc, int32_t ldx, int32_t col0, int32_t M, int32_t D, const double* X, const double* Z,
+                          const double* ell, double var, double* K) {
+  if (!c) return ZIGP_EARG;
+  if (!kron_stage_cols_ok(N, Nc) || M <= 0 || M > 4096 || D < 1 || D > MAXD || col0 < 0 || col0 + D > ldx || !X || !Z || !ell || !K)
+    return fail_arg(c, "zigp_test_kron_kbuild: bad arguments");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  const int Mq = (int)round_up(M, BM);
+  DevBuf dx, dz, dk;
+  ZIGP_TRY(stage_upload_rows(c, dx, X, N, N, ldx));
+  ZIGP_TRY(stage_upload_rows(c, dz, Z, M, Mq, D));
+  ZIGP_TRY(kron_stage_out(c, dk, (size_t)Mq * Nc, true));
+  hipLaunchKernelGGL(k_kron_kbuild, dim3((unsigned)(Nc / 256), Mq / 16), dim3(256), 0, c->stream, dx.p, N, (int)ldx, (int)col0, dz.p, (int)M,
+                     make_hyp(ell, var, D), dk.p, Nc);
+  ZIGP_HIP(c, hipGetLastError());
+  ZIGP_TRY(stage_download_rows(c, dk.p, K, Mq, Nc));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  return ZIGP_OK;
+}
+
+int zigp_test_kron_colsum(zigp_ctx* c, int32_t M0, int32_t M1, int64_t Nc, const double* K0, const double* A0, const double* K1, const double* A1,
+                          const double* B1, const double* A0sq, const double* C1, double* part) {
+  if (!c) return ZIGP_EARG;
+  if (!kron_stage_cols_ok(1, Nc) || M0 <= 0 || M1 <= 0 || M0 > 4096 || M1 > 4096 || !K0 || !A0 || !K1 || !A1 || !B1 || !A0sq || !C1 || !part)
+    return fail_arg(c, "zigp_test_kron_colsum: bad arguments");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  const double* host[7] = {K0, A0, K1, A1, B1, A0sq, C1};
+  const int rows[7] = {M0, M0, M1, M1, M0, M0, M0};
+  DevBuf d[7], dp;
+  for (int i = 0; i < 7; ++i) ZIGP_TRY(stage_upload_rows(c, d[i], host[i], rows[i], rows[i], Nc));
+  ZIGP_TRY(kron_stage_out(c, dp, (size_t)4 * Nc, true));
+  hipLaunchKernelGGL(k_kron_colsum, dim3((unsigned)(Nc / 256)), dim3(256), 0, c->stream, d[0].p, d[1].p, d[2].p, d[3].p, d[4].p, d[5].p, d[6].p,
+                     (int)M0, (int)M1, Nc, dp.p);
+  ZIGP_HIP(c, hipGetLastError());
+  ZIGP_TRY(stage_download_rows(c, dp.p, part, 4, Nc));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  return ZIGP_OK;
+}
+
+int zigp_test_kron_da(zigp_ctx* c, int32_t M, int64_t Nc, const double* A, const double* C, const double* K, const double* gv, const double* dq,
+                      double* dA, double* E) {
+  if (!c) return ZIGP_EARG;
+  if (!kron_stage_cols_ok(1, Nc) || M <= 0 || M > 4096 || !A || !C || !K || !gv || !dq || !dA || !E) return fail_arg(c, "zigp_test_kron_da: bad arguments");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  const int Mq = (int)round_up(M, BM);
+  const int64_t pn = (int64_t)Mq * Nc;
+  DevBuf da, dc, dk, dgv, ddq, oA, oE;
+  ZIGP_TRY(stage_upload_rows(c, da, A, M, Mq, Nc)); ZIGP_TRY(stage_upload_rows(c, dc, C, M, Mq, Nc)); ZIGP_TRY(stage_upload_rows(c, dk, K, M, Mq, Nc));
+  ZIGP_TRY(stage_upload_rows(c, dgv, gv, 1, 1, Nc)); ZIGP_TRY(stage_upload_rows(c, ddq, dq, 1, 1, Nc));
+  ZIGP_TRY(kron_stage_out(c, oA, (size_t)pn, true)); ZIGP_TRY(kron_stage_out(c, oE, (size_t)pn, true));
+  hipLaunchKernelGGL(k_kron_da, dim3(ceil_div(pn, 256)), dim3(256), 0, c->stream, da.p, dc.p, dk.p, dgv.p, ddq.p, Nc, pn, oA.p, oE.p);
+  ZIGP_HIP(c, hipGetLastError());
+  ZIGP_TRY(stage_download_rows(c, oA.p, dA, M, Nc)); ZIGP_TRY(stage_download_rows(c, oE.p, E, M, Nc));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  return ZIGP_OK;
+}
+
+int zigp_test_kron_kgrad(zigp_ctx* c, int32_t M, int32_t D, int64_t N, int64_t Nc, int32_t ldx, int32_t col0, const double* B, const double* A,
+                         const double* PdA, const double* K, const double* gm, const double* dq, const double* X, const double* Z, double* krow) {
+  if (!c) return ZIGP_EARG;
+  if (!kron_stage_cols_ok(N, Nc) || M <= 0 || M > 4096 || D < 1 || D > MAXD || col0 < 0 || col0 + D > ldx || !B || !A || !PdA || !K || !gm || !dq ||
+      !X || !Z || !krow)
+    return fail_arg(c, "zigp_test_kron_kgrad: bad arguments");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  const int Mq = (int)round_up(M, BM), Wd = 2 + 2 * D;
+  DevBuf db, da, dp, dk, dgm, ddq, dx, dz, dr;
+  ZIGP_TRY(stage_upload_rows(c, db, B, M, Mq, Nc)); ZIGP_TRY(stage_upload_rows(c, da, A, M, Mq, Nc)); ZIGP_TRY(stage_upload_rows(c, dp, PdA, M, Mq, Nc));
+  ZIGP_TRY(stage_upload_rows(c, dk, K, M, Mq, Nc));
+  ZIGP_TRY(stage_upload_rows(c, dgm, gm, 1, 1, Nc)); ZIGP_TRY(stage_upload_rows(c, ddq, dq, 1, 1, Nc));
+  ZIGP_TRY(stage_upload_rows(c, dx, X, N, N, ldx)); ZIGP_TRY(stage_upload_rows(c, dz, Z, M, Mq, D));
+  ZIGP_TRY(stage_upload_rows(c, dr, krow, M, Mq, Wd));
+  hipLaunchKernelGGL(k_kron_kgrad, dim3(Mq), dim3(256), 0, c->stream, db.p, da.p, dp.p, dk.p, dgm.p, ddq.p, dx.p, N, (int)ldx, (int)col0, dz.p, (int)M,
+                     (int)D, Nc, dr.p);
+  ZIGP_HIP(c, hipGetLastError());
+  ZIGP_TRY(stage_download_rows(c, dr.p, krow, M, Wd));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
   return ZIGP_OK;
 }
 

@@ -1347,6 +1347,24 @@ struct KfFitCall {          // host side of one zigp_kron_fit_steps / zigp_kron_
   double *hist_data, *hist_kl;
 };
 
+// Host image H [KH_SIZE] of the device hyperparameter block (KH_*, zigp_kernels.h) of a call that stages its parameters: one record per
+// (latent, factor) -- 1 / ell, ell, the variance; KH_ZC, the centre of the moment sums, is filled in by k_kf_factor -- and the noise.
+// KH_FMU stays 0: outside a fit call f_mu travels by value.
+static void kf_fill_hyp(double* H, const KfHostLatent* hl, int nlat, int D0, int D1, double noise) {
+  memset(H, 0, sizeof(double) * KH_SIZE);
+  for (int h = 0; h < nlat; ++h)
+    for (int q = 0; q < 2; ++q) {
+      const int D = q == 0 ? D0 : D1;
+      double* Rh = H + (2 * h + q) * KH_FAC;
+      for (int d = 0; d < MAXD; ++d) {
+        Rh[KH_INV + d] = d < D ? 1.0 / hl[h].ell[q][d] : 0.0;
+        Rh[KH_ELL + d] = d < D ? hl[h].ell[q][d] : 0.0;
+      }
+      Rh[KH_VAR] = hl[h].var[q];
+    }
+  H[KH_NOISE] = noise;
+}
+
 // One ELBO step (or prediction) of the fused Kronecker path.  fit != nullptr: n_steps gradient steps with the Adam update on the device
 // (p then carries the sizes only; X / Y are the resident data set).
 static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, const double* Y, int64_t N, double jitter, double scale,
@@ -1403,25 +1421,13 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
       memcpy(hin + off_x, X, sizeof(double) * N * ldx);
       if (Y) memcpy(hin + off_y, Y, sizeof(double) * N); else memset(hin + off_y, 0, sizeof(double) * N);
     }
-    double* H = hin + off_hyp;
-    memset(H, 0, sizeof(double) * KH_SIZE);
     for (int h = 0; h < nlat; ++h) {
       memcpy(hin + off_z[h][0], hl[h].Z[0], sizeof(double) * hl[h].M[0] * D0);
       memcpy(hin + off_z[h][1], hl[h].Z[1], sizeof(double) * hl[h].M[1] * D1);
       memcpy(hin + off_u[h], hl[h].u, sizeof(double) * hl[h].M[0] * hl[h].M[1]);
       memcpy(hin + off_s[h], hl[h].s, sizeof(double) * hl[h].M[0] * hl[h].M[1]);
-      for (int q = 0; q < 2; ++q) {
-        const int M = hl[h].M[q], D = q == 0 ? D0 : D1;
-        double* Rh = H + (2 * h + q) * KH_FAC;
-        for (int d = 0; d < MAXD; ++d) {      // (KH_ZC, the centre of the moment sums, is filled in by k_kf_factor)
-          Rh[KH_INV + d] = d < D ? 1.0 / hl[h].ell[q][d] : 0.0;
-          Rh[KH_ELL + d] = d < D ? hl[h].ell[q][d] : 0.0;
-        }
-        Rh[KH_VAR] = hl[h].var[q];
-        (void)M;
-      }
     }
-    H[KH_NOISE] = p->noise;
+    kf_fill_hyp(hin + off_hyp, hl, nlat, D0, D1, p->noise);
     ZIGP_HIP(c, hipMemcpyAsync(ks.in.p, hin, sizeof(double) * n_in, hipMemcpyHostToDevice, c->stream));
   }
   if (predict) ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));

@@ -130,6 +130,16 @@ class zigp_stage_pack(C.Structure):   # include/zigp_diag.h
                 ('pw_blocks', C.c_int32), ('pw', dp), ('lat', zigp_stage_pack_latent * 2), ('out', dp), ('n_out', C.c_int64)]
 
 
+class zigp_stage_kron_pointwise(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('lik', C.c_int32), ('mode', C.c_int32), ('dev_hyp', C.c_int32), ('sentinel_out', C.c_int32),
+                ('N', C.c_int64), ('Nc', C.c_int64), ('ld_out', C.c_int64), ('part_f', dp), ('part_g', dp), ('Y', dp),
+                ('var0f', C.c_double), ('var1f', C.c_double), ('var0g', C.c_double), ('var1g', C.c_double), ('noise', C.c_double),
+                ('g_offset', C.c_double), ('f_offset', C.c_double), ('scale', C.c_double),
+                ('gm_f', dp), ('gv_f', dp), ('dq0_f', dp), ('dq1_f', dp), ('gm_g', dp), ('gv_g', dp), ('dq0_g', dp), ('dq1_g', dp),
+                ('acc', dp), ('out', dp)]
+
+
+KPW_THREADS, KPW_ACC = 256, 5   # csrc/zigp_kron.hip: points per block and accumulators per block of the Kronecker point-wise kernels
 STAGE_SENTINEL = float(np.frombuffer(bytes([0x7f]) * 8, dtype=np.float64)[0])   # ZIGP_STAGE_SENTINEL_BYTE in every byte: 1.38e306
 KG_SPLIT, PW_PTS, PW_ACC = 4, 64, 13   # csrc/zigp_kernels.h
 
@@ -216,6 +226,11 @@ SIGNATURES = {
     'zigp_test_rank_update': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(dp), C.POINTER(dp), dp, C.POINTER(C.c_int64)]),
     'zigp_test_mxm_backward': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_mxm)]),
     'zigp_test_dense_pack': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_pack)]),
+    'zigp_test_kron_pointwise': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_kron_pointwise)]),
+    'zigp_test_kron_kbuild': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, C.c_double, dp]),
+    'zigp_test_kron_colsum': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, dp, dp, dp, dp, dp, dp, dp, dp]),
+    'zigp_test_kron_da': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, dp, dp, dp, dp, dp, dp, dp]),
+    'zigp_test_kron_kgrad': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp, dp]),
 }
 
 _lib = None

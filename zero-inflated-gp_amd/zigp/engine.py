@@ -1016,6 +1016,93 @@ class DenseEngine:
         _check(self.lib, self.ctx, fn(self.ctx, C.byref(s)))
         return out
 
+    # ---- Kronecker stage diagnostics (include/zigp_diag.h): one launch of a point-wise or per-point panel kernel ----
+    def test_kron_pointwise(self, lik, mode, part_f, part_g=None, Y=None, N=None, var_f=(1.0, 1.0), var_g=(1.0, 1.0), noise=1.0, g_offset=0.0,
+                            f_offset=0.0, scale=1.0, dev_hyp=False, sentinel_out=True, ld_out=None):
+        """The point-wise launch of a Kronecker call (zigp_test_kron_pointwise).  lik 'onoff' / 'gaussian' / 'bernoulli'; mode 'value' / 'grad' /
+        'predict'; part_* [4][Nc] = q0, q1, mean, st (Nc a multiple of 256; part_g: OnOff only); N valid points (default: len(Y)); var_* =
+        (var0, var1) of the latent's two factors.  dev_hyp: Knn, the noise and (heads) f_offset are read from the device hyperparameter block.
+        Returns, for 'value' / 'grad', dict(gm_f, gv_f, dq0_f, dq1_f, gm_g, gv_g, dq0_g, dq1_g [Nc] each, acc [Nc/256][5]) -- with
+        sentinel_out a buffer the launch did not write holds _lib.STAGE_SENTINEL --, for 'predict' dict(out [9 or 4][ld_out]), ld_out >= N
+        (default N, as the real calls)."""
+        part_f = as_f64(part_f)
+        Nc = part_f.shape[1]
+        part_f = as_f64(part_f, (4, Nc))
+        s = _lib.zigp_stage_kron_pointwise()
+        s.lik = {'onoff': _lib.LIK_ONOFF, 'gaussian': _lib.LIK_GAUSSIAN, 'bernoulli': _lib.LIK_BERNOULLI}[lik]
+        s.mode = {'value': 0, 'grad': 1, 'predict': 2}[mode]
+        s.dev_hyp, s.sentinel_out = int(bool(dev_hyp)), int(bool(sentinel_out))
+        Yc = None if Y is None else as_f64(Y).reshape(-1)
+        N = int(Yc.size if N is None else N)
+        s.N, s.Nc = N, Nc
+        s.part_f = ptr(part_f)
+        if part_g is not None:
+            part_g = as_f64(part_g, (4, Nc))
+            s.part_g = ptr(part_g)
+        s.Y = None if Yc is None else ptr(Yc)
+        s.var0f, s.var1f, s.var0g, s.var1g = float(var_f[0]), float(var_f[1]), float(var_g[0]), float(var_g[1])
+        s.noise, s.g_offset, s.f_offset, s.scale = float(noise), float(g_offset), float(f_offset), float(scale)
+        out = {}
+        if mode == 'predict':
+            ld = N if ld_out is None else int(ld_out)
+            s.ld_out = ld
+            out['out'] = np.zeros((9 if lik == 'onoff' else 4, ld))
+            s.out = ptr(out['out'])
+        else:
+            for k in ('gm_f', 'gv_f', 'dq0_f', 'dq1_f', 'gm_g', 'gv_g', 'dq0_g', 'dq1_g'):
+                out[k] = np.zeros(Nc)
+                setattr(s, k, ptr(out[k]))
+            out['acc'] = np.zeros((Nc // _lib.KPW_THREADS, _lib.KPW_ACC))
+            s.acc = ptr(out['acc'])
+        _check(self.lib, self.ctx, self.lib.zigp_test_kron_pointwise(self.ctx, C.byref(s)))
+        return out
+
+    def test_kron_panel_kbuild(self, X, col0, Z, ell, var, Nc):
+        """k_kron_kbuild (zigp_test_kron_kbuild): the WHOLE padded factor panel (Mq, Nc), Mq = M rounded up to 128, from the columns
+        col0 : col0 + D of X (N, ldx) and Z (M, D)."""
+        X, Z = as_f64(X), as_f64(Z)
+        if X.ndim == 1: X = X[:, None]
+        if Z.ndim == 1: Z = Z[:, None]
+        (N, ldx), (M, D) = X.shape, Z.shape
+        ell = as_f64(np.broadcast_to(np.asarray(ell, dtype=np.float64), (D,)))
+        out = np.zeros(((M + 127) // 128 * 128, int(Nc)))
+        _check(self.lib, self.ctx, self.lib.zigp_test_kron_kbuild(self.ctx, N, int(Nc), ldx, int(col0), M, D, ptr(X), ptr(Z), ptr(ell), float(var), ptr(out)))
+        return out
+
+    def test_kron_panel_colsum(self, K0, A0, K1, A1, B1, A0sq, C1):
+        """k_kron_colsum (zigp_test_kron_colsum): part [4][Nc] = column sums of K0.A0, K1.A1, K0.B1, A0sq.C1."""
+        K0, K1 = as_f64(K0), as_f64(K1)
+        (M0, Nc), M1 = K0.shape, K1.shape[0]
+        a = [as_f64(x, (m, Nc)) for x, m in ((K0, M0), (A0, M0), (K1, M1), (A1, M1), (B1, M0), (A0sq, M0), (C1, M0))]
+        out = np.zeros((4, Nc))
+        _check(self.lib, self.ctx, self.lib.zigp_test_kron_colsum(self.ctx, M0, M1, Nc, *[ptr(x) for x in a], ptr(out)))
+        return out
+
+    def test_kron_panel_da(self, A, Cx, K, gv, dq):
+        """k_kron_da (zigp_test_kron_da): (dA, E) = (2 A gv C, dq K + dA), (M, Nc) each."""
+        A = as_f64(A)
+        M, Nc = A.shape
+        Cx, K, gv, dq = as_f64(Cx, (M, Nc)), as_f64(K, (M, Nc)), as_f64(gv, (Nc,)), as_f64(dq, (Nc,))
+        dA, E = np.zeros((M, Nc)), np.zeros((M, Nc))
+        _check(self.lib, self.ctx, self.lib.zigp_test_kron_da(self.ctx, M, Nc, ptr(A), ptr(Cx), ptr(K), ptr(gv), ptr(dq), ptr(dA), ptr(E)))
+        return dA, E
+
+    def test_kron_panel_kgrad(self, B, A, PdA, K, gm, dq, X, col0, Z, krow=None):
+        """k_kron_kgrad (zigp_test_kron_kgrad): krow (M, 2 + 2D) with the sums over the N = len(X) valid columns added onto `krow` (zeros if
+        None); the factor's inputs are the columns col0 : col0 + D of X (N, ldx)."""
+        X, Z = as_f64(X), as_f64(Z)
+        if X.ndim == 1: X = X[:, None]
+        if Z.ndim == 1: Z = Z[:, None]
+        (N, ldx), (M, D) = X.shape, Z.shape
+        K = as_f64(K)
+        Nc = K.shape[1]
+        B, A, PdA, K = (as_f64(x, (M, Nc)) for x in (B, A, PdA, K))
+        gm, dq = as_f64(gm, (Nc,)), as_f64(dq, (Nc,))
+        out = np.zeros((M, 2 + 2 * D)) if krow is None else np.array(as_f64(krow, (M, 2 + 2 * D)), copy=True)
+        _check(self.lib, self.ctx, self.lib.zigp_test_kron_kgrad(self.ctx, M, D, N, Nc, ldx, int(col0), ptr(B), ptr(A), ptr(PdA), ptr(K), ptr(gm), ptr(dq),
+                                                                  ptr(X), ptr(Z), ptr(out)))
+        return out
+
     def test_q_full_forward(self, W, Lq, u):
         """Forward M x M stage of a full-covariance call for one latent (zigp_test_q_full_forward): returns (T - I, R^T = (T - I) W, KL)
         for T = tril(Lq) tril(Lq)^T."""
