@@ -400,6 +400,42 @@ int zigp_kron_head_fit_steps(zigp_ctx* ctx, const zigp_kron_params* shape, int32
 int zigp_kron_head_predict(zigp_ctx* ctx, const zigp_kron_params* p, int32_t lik, const double* Xnew, int64_t N,
                            double jitter, double f_mu, double* out4);
 
+/* ---- predictive density of held-out data and the moments of y (new: the reference's likelihood leaves them out -- "not implemented
+ * logp, conditional_mean and others", onoffgpf/OnOffLikelihood.py:28; GPflow's predict_density / predict_y) ----
+ * OnOff: at a test row f ~ N(fm, fv) and g ~ N(gm, gv) are independent under q (rows 3-6 of zigp_predict, mean
+ * function and g_offset applied) and y | f, g ~ N(Phi~(g) f, noise), Phi~(g) = 0.5 (1 + erf(g / sqrt 2)) (1 - 2e-3) + 1e-3
+ * (OnOffSVGP.py:178).  f integrates out in closed form, g by the caller's rule for the standard normal -- nodes x_i, weights w_i > 0
+ * with sum w_i = 1, n_quad <= ZIGP_DENSITY_MAX_QUAD of them:
+ *   Phi_i = Phi~(gm + sqrt(max(gv, 0)) x_i),   s_i = noise + Phi_i^2 max(fv, 0),
+ *   logp  = logsumexp_i [ log w_i - 0.5 log(2 pi s_i) - 0.5 (y - Phi_i fm)^2 / s_i ].
+ * This finite sum IS the result; how far it lies from the integral is a property of the rule (Gauss-Hermite with 64 nodes is the Python
+ * default; a row whose mass sits in the far tail of q(g) is beyond any rule centred on gm -- DESIGN.md section 10).
+ *   ymean = gfmean,  yvar = (gfvar + gfmeanu) + noise   (rows 0-2 of zigp_predict; the two additions in that order).
+ * Heads, closed form: ZIGP_LIK_GAUSSIAN  logp = log N(y; fm, fv + noise), ymean = fm, yvar = fv + noise;
+ *                     ZIGP_LIK_BERNOULLI p = pfmean of zigp_kron_head_predict (probit(fm / sqrt(1 + fv)) through the same link),
+ *                                        logp = log p for y == 1 and log1p(-p) otherwise, ymean = p, yvar = p (1 - p).
+ * out3 (nullable in all three calls) is (3, N): logp, ymean, yvar.  *sum receives sum_n logp_n, added in a fixed order (the same bits
+ * on every call).  N = 0 is ZIGP_OK with *sum = 0.
+ * ZIGP_EARG, with nothing enqueued, the outputs untouched and the context usable afterwards: a NULL context, an unknown lik, N < 0,
+ * noise not positive (the Bernoulli head ignores noise), a NULL sum or row pointer, and for OnOff n_quad outside
+ * [1, ZIGP_DENSITY_MAX_QUAD], NULL nodes or weights, a non-finite node, a weight that is not positive and finite. */
+#define ZIGP_DENSITY_MAX_QUAD 256
+/* Rows in HOST memory, for the Kronecker path and the heads: feed it the rows of zigp_kron_predict (3-6) or zigp_kron_head_predict
+ * (0-1).  gm, gv, nodes and weights are ignored for the heads and may be NULL there.  OnOff computes gfmean, gfvar and gfmeanu from
+ * the four rows as zigp_predict does. */
+int zigp_density_rows(zigp_ctx* ctx, int32_t lik, const double* fm, const double* fv, const double* gm, const double* gv,
+                      const double* y, int64_t N, double noise, const double* nodes, const double* weights, int32_t n_quad,
+                      double* out3, double* sum);
+/* Dense path: zigp_predict into the context's own (9, N) block, then the density kernel over it; only out3 and the sum come back.
+ * Every parametrisation, kernel kind, mean function and D that zigp_predict accepts (it consumes nothing but its rows), and
+ * zigp_predict's errors (ZIGP_ENOTPD included).  Xnew (N, D), Ynew (N), out3 (3, N) in host memory. */
+int zigp_predict_density(zigp_ctx* ctx, const zigp_params* p, const double* Xnew, const double* Ynew, int64_t N, double jitter,
+                         double g_offset, const double* nodes, const double* weights, int32_t n_quad, double* out3, double* sum);
+/* The same with Xnew, Ynew and out3 in DEVICE memory of the context's GPU (the companion of zigp_predict_device; anything else is
+ * ZIGP_EARG): nothing crosses PCIe but the parameters, the rule (host pointers) and the sum (a host double); complete on return. */
+int zigp_predict_density_device(zigp_ctx* ctx, const zigp_params* p, const double* dXnew, const double* dYnew, int64_t N, double jitter,
+                                double g_offset, const double* nodes, const double* weights, int32_t n_quad, double* d_out3, double* sum);
+
 /* ---- data-parallel exchange (new: the reference is single-process) ----
  * The ELBO data term is a sum over points (tf.reduce_sum(var_exp), onoffgpf/OnOffSVGP.py:122; scripts/onoff.py:307): one process per GPU
  * holds a row shard, and ONE ncclAllReduce(sum, f64) per step adds the packed [elbo_data, kl, gradient] vector of every rank, on the

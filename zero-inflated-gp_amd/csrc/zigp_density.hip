@@ -1,0 +1,243 @@
+// Held-out predictive density and the moments of y (include/zigp.h "predictive density").
+//
+// OnOff, per test row: under q, f ~ N(fm, fv) and g ~ N(gm, gv) are independent (rows 3-6 of zigp_predict, mean function and g_offset
+// applied) and y | f, g ~ N(Phi~(g) f, noise), Phi~ the link of pointwise_eval (zigp_kernels.h).  f integrates out in closed form, g by
+// the caller's rule for the standard normal (nodes x_i, weights w_i > 0, sum w_i = 1):
+//   Phi_i = Phi~(gm + sqrt(max(gv, 0)) x_i)
+//   s_i   = noise + Phi_i^2 max(fv, 0)
+//   logp  = logsumexp_i [ log w_i - 0.5 log(2 pi s_i) - 0.5 (y - Phi_i fm)^2 / s_i ]
+// That finite sum is the definition; its distance from the integral belongs to the rule (tools/density_accuracy.py).
+// Heads, closed form: Gaussian logp = log N(y; fm, fv + noise); Bernoulli p = the probability of k_kron_head_pointwise,
+// logp = log p (y == 1) or log1p(-p).
+#include "zigp_host.h"
+#include <cmath>
+
+using namespace zigp;
+
+namespace zigp {
+
+constexpr int DN_THREADS = 256;   // rows per block (one thread each); not tuned: tools/density_time.py is the measurement
+constexpr int DN_MAXQ = 256;      // ZIGP_DENSITY_MAX_QUAD
+static_assert(DN_MAXQ == ZIGP_DENSITY_MAX_QUAD, "include/zigp.h");
+
+struct DensityArgs {
+  const double* fm; const double* fv; const double* gm; const double* gv; const double* y;   // rows [N] (gm, gv: OnOff only)
+  const double* m0; const double* m1; const double* m2;   // OnOff: gfmean, gfvar, gfmeanu of a predict block; NULL: from the four rows
+  int64_t N;
+  double noise;
+  const double* rule;   // OnOff: x_i [n_quad], then log w_i [n_quad]
+  int n_quad;
+  double* out3;         // (3, ld3): logp, ymean, yvar (nullable)
+  int64_t ld3;
+  double* part;         // [gridDim.x] block sums of logp
+};
+
+constexpr double DN_LOG_2PI = 1.8378770664093454836;
+
+__device__ __forceinline__ double dn_link(double g) {   // OnOffSVGP.py:178, as pointwise_eval writes it
+  const double c1 = 1.0 - 2.e-3, c0 = 1.e-3;
+  return 0.5 * (1.0 + erf(g * 0.70710678118654752440)) * c1 + c0;
+}
+
+template <int LIK>
+__global__ void __launch_bounds__(DN_THREADS)
+k_density_rows(DensityArgs a) {
+  __shared__ double sx[LIK == ZIGP_LIK_ONOFF ? DN_MAXQ : 1], slw[LIK == ZIGP_LIK_ONOFF ? DN_MAXQ : 1];
+  __shared__ double sh[DN_THREADS / 64];
+  const int64_t n = (int64_t)blockIdx.x * DN_THREADS + threadIdx.x;
+  const bool valid = n < a.N;
+  const double fm = valid ? a.fm[n] : 0.0, fv = valid ? a.fv[n] : 0.0, y = valid ? a.y[n] : 0.0;
+  double logp, ymean, yvar;
+  if (LIK == ZIGP_LIK_ONOFF) {
+    for (int i = threadIdx.x; i < a.n_quad; i += DN_THREADS) { sx[i] = a.rule[i]; slw[i] = a.rule[a.n_quad + i]; }
+    __syncthreads();
+    const double gm = valid ? a.gm[n] : 0.0, gv = valid ? a.gv[n] : 0.0;
+    const double sg = sqrt(fmax(gv, 0.0)), fvp = fmax(fv, 0.0);
+    // online log-sum-exp: m = the largest term so far, acc = sum exp(term - m); the first node starts it, so that no -inf meets -inf
+    double m = 0.0, acc = 1.0;
+    for (int i = 0; i < a.n_quad; ++i) {
+      const double ph = dn_link(gm + sg * sx[i]);
+      const double s = a.noise + ph * ph * fvp, r = y - ph * fm;
+      const double l = slw[i] - 0.5 * (DN_LOG_2PI + log(s)) - 0.5 * (r * r) / s;
+      if (i == 0) { m = l; continue; }
+      const double d = l - m, e = exp(-fabs(d));
+      if (d > 0.0) { acc = fma(acc, e, 1.0); m = l; } else acc += e;
+    }
+    logp = m + log(acc);
+    if (a.m0) {   // a predict block: ymean = gfmean, yvar = (gfvar + gfmeanu) + noise, two additions in that order
+      ymean = valid ? a.m0[n] : 0.0;
+      yvar = __dadd_rn(__dadd_rn(valid ? a.m1[n] : 0.0, valid ? a.m2[n] : 0.0), a.noise);
+    } else {
+      const PwOut o = pointwise_eval(fm, fv, gm, gv, y, a.noise);
+      // the two products as the ROUNDED numbers zigp_predict stores (the empty statement pins them in registers): left to the compiler,
+      // one of them is fused into the addition and yvar is an ulp away from the sum of the stored rows
+      double gfvar = o.gfvar, gfmeanu = o.gfmeanu;
+      asm volatile("" : "+v"(gfvar), "+v"(gfmeanu));
+      ymean = o.gfmean;
+      yvar = __dadd_rn(__dadd_rn(gfvar, gfmeanu), a.noise);
+    }
+  } else if (LIK == ZIGP_LIK_GAUSSIAN) {
+    const double s = __dadd_rn(fv, a.noise), r = y - fm;
+    logp = -0.5 * (DN_LOG_2PI + log(s)) - 0.5 * (r * r) / s;
+    ymean = fm; yvar = s;
+  } else {
+    const double p = dn_link(fm * (1.0 / sqrt(1.0 + fv)));   // classifier.py:216-217, k_kron_head_pointwise
+    logp = (y == 1.0) ? log(p) : log1p(-p);
+    ymean = p; yvar = __dmul_rn(p, 1.0 - p);
+  }
+  if (valid && a.out3) { double* q = a.out3 + n; q[0] = logp; q[a.ld3] = ymean; q[2 * a.ld3] = yvar; }
+  const double sum = block_sum<DN_THREADS / 64>(valid ? logp : 0.0, sh);
+  if (threadIdx.x == 0) a.part[blockIdx.x] = sum;
+}
+
+// One block: thread t adds the partials t, t + DN_THREADS, ... in that order, then the threads' sums are added in thread order --
+// the same association on every call, so the sum is bit-stable.
+__global__ void __launch_bounds__(DN_THREADS)
+k_density_sum(const double* __restrict__ part, int nb, double* __restrict__ out) {
+  __shared__ double sh[DN_THREADS / 64];
+  double s = 0.0;
+  for (int b = threadIdx.x; b < nb; b += DN_THREADS) s += part[b];
+  s = block_sum<DN_THREADS / 64>(s, sh);
+  if (threadIdx.x == 0) out[0] = s;
+}
+
+}  // namespace zigp
+
+namespace {
+
+// Layout of scratch2 during a density call: the rule's table, the sum, the block partials, the three output rows
+constexpr size_t DN_OFF_SUM = 2 * DN_MAXQ, DN_OFF_PART = 2 * DN_MAXQ + 8;
+struct DensityBufs { double* rule; double* sum; double* part; double* out3; int nb; };
+
+int density_bufs(zigp_ctx* c, int64_t N, DensityBufs& b) {
+  b.nb = ceil_div(N, DN_THREADS);
+  const size_t off_out = (DN_OFF_PART + (size_t)b.nb + 7) & ~(size_t)7;
+  ZIGP_ENSURE(c, c->scratch2, off_out + (size_t)3 * N);
+  b.rule = c->scratch2.p; b.sum = c->scratch2.p + DN_OFF_SUM; b.part = c->scratch2.p + DN_OFF_PART; b.out3 = c->scratch2.p + off_out;
+  return 0;
+}
+
+// Everything a density call refuses that is not a pointer; touches nothing but the error text
+int density_check(zigp_ctx* c, const char* who, int lik, int64_t N, double noise, const double* nodes, const double* weights, int n_quad) {
+  const std::string w(who);
+  if (lik != ZIGP_LIK_ONOFF && lik != ZIGP_LIK_GAUSSIAN && lik != ZIGP_LIK_BERNOULLI) return fail_arg(c, (w + ": lik is not a ZIGP_LIK_* value").c_str());
+  if (N < 0) return fail_arg(c, (w + ": N is negative").c_str());
+  if (lik != ZIGP_LIK_BERNOULLI && !(noise > 0 && std::isfinite(noise))) return fail_arg(c, (w + ": noise must be positive and finite").c_str());
+  if (lik != ZIGP_LIK_ONOFF) return 0;
+  if (n_quad < 1 || n_quad > DN_MAXQ) return fail_arg(c, (w + ": n_quad must be in [1, 256] (ZIGP_DENSITY_MAX_QUAD)").c_str());
+  if (!nodes || !weights) return fail_arg(c, (w + ": nodes or weights is NULL").c_str());
+  for (int i = 0; i < n_quad; ++i) {
+    if (!std::isfinite(nodes[i])) return fail_arg(c, (w + ": nodes has a non-finite entry").c_str());
+    if (!(weights[i] > 0 && std::isfinite(weights[i]))) return fail_arg(c, (w + ": weights must be positive and finite").c_str());
+  }
+  return 0;
+}
+
+// The rule (nodes, then the logarithms of the weights, taken here) to the device, the rows kernel, the sum kernel; the caller
+// has synchronised whatever wrote the rows, and collects *sum with its own synchronisation
+int density_run(zigp_ctx* c, int lik, DensityArgs a, const DensityBufs& b, const double* nodes, const double* weights, double** hsum) {
+  if (lik == ZIGP_LIK_ONOFF) {
+    ZIGP_PINNED(c, h, 2 * (size_t)a.n_quad);
+    for (int i = 0; i < a.n_quad; ++i) { h[i] = nodes[i]; h[a.n_quad + i] = log(weights[i]); }
+    ZIGP_HIP(c, hipMemcpyAsync(b.rule, h, sizeof(double) * 2 * a.n_quad, hipMemcpyHostToDevice, c->stream));
+  }
+  a.rule = b.rule; a.part = b.part;
+  const dim3 grid(b.nb), block(DN_THREADS);
+  if (lik == ZIGP_LIK_ONOFF) hipLaunchKernelGGL(k_density_rows<ZIGP_LIK_ONOFF>, grid, block, 0, c->stream, a);
+  else if (lik == ZIGP_LIK_GAUSSIAN) hipLaunchKernelGGL(k_density_rows<ZIGP_LIK_GAUSSIAN>, grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL(k_density_rows<ZIGP_LIK_BERNOULLI>, grid, block, 0, c->stream, a);
+  ZIGP_HIP(c, hipGetLastError());
+  hipLaunchKernelGGL(k_density_sum, dim3(1), block, 0, c->stream, b.part, b.nb, b.sum);
+  ZIGP_HIP(c, hipGetLastError());
+  return download(c, b.sum, 1, hsum);
+}
+
+// zigp_predict_density / zigp_predict_density_device behind their argument checks: dX (N, D) and dY (N) are device memory
+int predict_density(zigp_ctx* c, const zigp_params* p, const double* dX, const double* dY, int64_t N, double jitter, double g_offset,
+                    const double* nodes, const double* weights, int n_quad, double* out3, bool out3_device, double* sum) {
+  DensityBufs b;
+  ZIGP_TRY(density_bufs(c, N, b));
+  ZIGP_ENSURE(c, c->out9, (size_t)9 * N);
+  ZIGP_TRY(run_dense(c, p, dX, nullptr, N, p->D, jitter, 1.0, g_offset, 0, N, 0, true, c->out9.p, nullptr, nullptr, nullptr));   // complete on return
+  const double* r = c->out9.p;
+  DensityArgs a{};
+  a.m0 = r; a.m1 = r + N; a.m2 = r + 2 * N; a.fm = r + 3 * N; a.fv = r + 4 * N; a.gm = r + 5 * N; a.gv = r + 6 * N; a.y = dY;
+  a.N = N; a.noise = p->noise; a.n_quad = n_quad; a.ld3 = N;
+  a.out3 = !out3 ? nullptr : out3_device ? out3 : b.out3;
+  double* hsum = nullptr;
+  ZIGP_TRY(density_run(c, ZIGP_LIK_ONOFF, a, b, nodes, weights, &hsum));
+  if (out3 && !out3_device) ZIGP_HIP(c, hipMemcpyAsync(out3, b.out3, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  *sum = hsum[0];
+  return ZIGP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int zigp_density_rows(zigp_ctx* c, int32_t lik, const double* fm, const double* fv, const double* gm, const double* gv, const double* y,
+                      int64_t N, double noise, const double* nodes, const double* weights, int32_t n_quad, double* out3, double* sum) {
+  if (!c) return ZIGP_EARG;
+  ZIGP_TRY(density_check(c, "zigp_density_rows", lik, N, noise, nodes, weights, n_quad));
+  if (!sum) return fail_arg(c, "zigp_density_rows: sum is NULL");
+  const bool onoff = lik == ZIGP_LIK_ONOFF;
+  if (N > 0 && (!fm || !fv || !y || (onoff && (!gm || !gv)))) return fail_arg(c, "zigp_density_rows: a row pointer (fm, fv, gm, gv, y) is NULL");
+  if (N == 0) { *sum = 0.0; return ZIGP_OK; }
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  ZIGP_TRY(begin_staged_call(c));
+  DensityBufs b;
+  ZIGP_TRY(density_bufs(c, N, b));
+  ZIGP_ENSURE(c, c->scratch, (size_t)5 * N);
+  double* d = c->scratch.p;
+  const double* src[5] = {fm, fv, y, gm, gv};
+  for (int k = 0; k < (onoff ? 5 : 3); ++k)
+    ZIGP_HIP(c, hipMemcpyAsync(d + k * N, src[k], sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
+  DensityArgs a{};
+  a.fm = d; a.fv = d + N; a.y = d + 2 * N; a.gm = onoff ? d + 3 * N : nullptr; a.gv = onoff ? d + 4 * N : nullptr;
+  a.N = N; a.noise = noise; a.n_quad = onoff ? n_quad : 0; a.out3 = out3 ? b.out3 : nullptr; a.ld3 = N;
+  double* hsum = nullptr;
+  ZIGP_TRY(density_run(c, lik, a, b, nodes, weights, &hsum));
+  if (out3) ZIGP_HIP(c, hipMemcpyAsync(out3, b.out3, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  *sum = hsum[0];
+  return ZIGP_OK;
+}
+
+int zigp_predict_density(zigp_ctx* c, const zigp_params* p, const double* Xnew, const double* Ynew, int64_t N, double jitter, double g_offset,
+                         const double* nodes, const double* weights, int32_t n_quad, double* out3, double* sum) {
+  if (!c) return ZIGP_EARG;
+  ZIGP_TRY(validate_params(c, p));
+  ZIGP_TRY(density_check(c, "zigp_predict_density", ZIGP_LIK_ONOFF, N, p->noise, nodes, weights, n_quad));
+  if (!sum) return fail_arg(c, "zigp_predict_density: sum is NULL");
+  if (N > 0 && (!Xnew || !Ynew)) return fail_arg(c, "zigp_predict_density: Xnew or Ynew is NULL");
+  if (N == 0) { *sum = 0.0; return ZIGP_OK; }
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  const size_t nx = ((size_t)N * p->D + 7) & ~(size_t)7;
+  ZIGP_ENSURE(c, c->scratch, nx + (size_t)N);
+  ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p, Xnew, sizeof(double) * N * p->D, hipMemcpyHostToDevice, c->stream));
+  ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p + nx, Ynew, sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
+  return predict_density(c, p, c->scratch.p, c->scratch.p + nx, N, jitter, g_offset, nodes, weights, n_quad, out3, false, sum);
+}
+
+int zigp_predict_density_device(zigp_ctx* c, const zigp_params* p, const double* dXnew, const double* dYnew, int64_t N, double jitter,
+                                double g_offset, const double* nodes, const double* weights, int32_t n_quad, double* d_out3, double* sum) {
+  if (!c) return ZIGP_EARG;
+  ZIGP_TRY(validate_params(c, p));
+  ZIGP_TRY(density_check(c, "zigp_predict_density_device", ZIGP_LIK_ONOFF, N, p->noise, nodes, weights, n_quad));
+  if (!sum) return fail_arg(c, "zigp_predict_density_device: sum is NULL");
+  if (N > 0 && (!dXnew || !dYnew)) return fail_arg(c, "zigp_predict_density_device: Xnew or Ynew is NULL");
+  if (N == 0) { *sum = 0.0; return ZIGP_OK; }
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  for (const double* q : {dXnew, dYnew, (const double*)d_out3}) {   // device memory of this context's GPU (a host pointer would fault inside a kernel)
+    hipPointerAttribute_t at;
+    if (!q) continue;
+    if (hipPointerGetAttributes(&at, q) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->device) {
+      (void)hipGetLastError();
+      return fail_arg(c, "zigp_predict_density_device: Xnew, Ynew and out3 must be device memory of the context's GPU");
+    }
+  }
+  return predict_density(c, p, dXnew, dYnew, N, jitter, g_offset, nodes, weights, n_quad, d_out3, true, sum);
+}
+
+}  // extern "C"

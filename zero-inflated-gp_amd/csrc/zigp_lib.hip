@@ -2,4 +2,5 @@
 // zigp_kernels.h (plain __global__ definitions), so they are compiled together.
 #include "zigp_dense.hip"
 #include "zigp_kron.hip"
+#include "zigp_density.hip"
 #include "zigp_comm.hip"

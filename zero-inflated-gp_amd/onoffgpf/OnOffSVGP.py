@@ -192,6 +192,21 @@ class OnOffSVGP(Parameterized):
         out = self._engine.predict(self._values(), np.asarray(Xnew, dtype=np.float64), jitter=JITTER)
         return tuple(out[i].reshape(-1, 1) for i in range(9))
 
+    def predict_y(self, Xnew):
+        """GPflow's predict_y: mean and variance of y at Xnew, each (N,1) -- ymean = gfmean, yvar = (gfvar + gfmeanu) + noise, from the
+        rows of build_predict (the reference's likelihood leaves conditional moments out, OnOffLikelihood.py:28)."""
+        out = self._engine.predict(self._values(), np.asarray(Xnew, dtype=np.float64), jitter=JITTER)
+        noise = float(self.likelihood.variance.value.reshape(-1)[0])
+        return out[0].reshape(-1, 1), ((out[1] + out[2]) + noise).reshape(-1, 1)
+
+    def predict_density(self, Xnew, Ynew, n_quad=64):
+        """GPflow's predict_density: log p(Ynew | Xnew) per row, (N,1) -- f integrated in closed form, g by Gauss-Hermite quadrature with
+        n_quad nodes on the device (zigp_predict_density); a row whose mass lies in the far tail of q(g) is beyond the rule (DESIGN.md
+        section 10)."""
+        out, _ = self._engine.predict_density(self._values(), np.asarray(Xnew, dtype=np.float64), np.asarray(Ynew, dtype=np.float64),
+                                              jitter=JITTER, n_quad=n_quad)
+        return out[0].reshape(-1, 1)
+
     def optimize(self, method='L-BFGS-B', maxiter=1000, disp=False, callback=None, learning_rate=0.01, device_loop=None, **kw):
         """GPflow Model.optimize: scipy L-BFGS-B on the free state (default), or Adam when method='adam'
         (the commented alternative at zero-inflated-gpflow.ipynb:155).  Adam without a callback runs its loop on the device

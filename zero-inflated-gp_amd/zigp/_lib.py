@@ -13,6 +13,7 @@ NCLASS = 10
 LIK_ONOFF, LIK_GAUSSIAN, LIK_BERNOULLI = 0, 1, 2   # include/zigp.h ZIGP_LIK_*
 KERN_RBF, KERN_MATERN32, KERN_MATERN52 = 0, 1, 2   # include/zigp.h ZIGP_KERN_*: kernel family of a dense latent (zigp_set_kernel)
 KERNELS = {'rbf': KERN_RBF, 'matern32': KERN_MATERN32, 'matern52': KERN_MATERN52}
+DENSITY_MAX_QUAD = 256   # include/zigp.h ZIGP_DENSITY_MAX_QUAD: nodes of the quadrature rule of the density calls
 MATERN_MAX_D = 8     # the Matern kernels cover the input dimensions of the per-dimension kernels (csrc/zigp_kernels.h MAXD)
 PROF_CLASSES = ('gemm_A1', 'gemm_A2', 'gemm_H', 'gemm_J', 'syrk', 'kuf_build', 'pointwise', 'kgrad', 'mxm_stage', 'other')
 PROF_KERNELS = {'gemm_A1': 'gemm_f64_kernel<1,1,2,false,1,8,EpiStoreColsum> (A1 = W K, W read through W^T)',
@@ -204,6 +205,10 @@ SIGNATURES = {
     'zigp_kron_head_fit_steps': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_int32, C.POINTER(zigp_kron_head_fit_opts), dp, dp, dp, C.c_int64,
                                            C.c_int64, C.c_int32, C.c_void_p, C.c_int64, dp, dp, C.c_double, C.c_double, C.c_int32, dp, dp]),
     'zigp_kron_head_predict': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_int32, dp, C.c_int64, C.c_double, C.c_double, dp]),
+    'zigp_density_rows': (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, C.c_int64, C.c_double, dp, dp, C.c_int32, dp, dp]),
+    'zigp_predict_density': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), dp, dp, C.c_int64, C.c_double, C.c_double, dp, dp, C.c_int32, dp, dp]),
+    'zigp_predict_density_device': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
+                                              dp, dp, C.c_int32, C.c_void_p, dp]),
     'zigp_profile_enable': (C.c_int, [C.c_void_p, C.c_int32]),
     'zigp_profile_get': (C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int64), dp]),
     'zigp_profile_reset': (C.c_int, [C.c_void_p]),

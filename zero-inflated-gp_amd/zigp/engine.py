@@ -481,6 +481,88 @@ class DenseEngine:
                                                                      float(g_offset), C.c_void_p(out.data_ptr())))
         return out
 
+    # ---- predictive density of held-out data (include/zigp.h "predictive density") ----
+    DENSITY_LIK = {'onoff': _lib.LIK_ONOFF, 'gaussian': _lib.LIK_GAUSSIAN, 'bernoulli': _lib.LIK_BERNOULLI}
+
+    @staticmethod
+    def _rule(n_quad, rule):
+        """(nodes, weights) as float64 arrays: `rule` when given, else Gauss-Hermite with n_quad nodes; the library checks the values"""
+        if rule is None:
+            from .quadrature import gauss_hermite
+            rule = gauss_hermite(n_quad)
+        x, w = as_f64(rule[0]).reshape(-1), as_f64(rule[1]).reshape(-1)
+        if x.size != w.size:
+            raise ValueError('rule: nodes and weights must have the same length')
+        return x, w
+
+    def density_rows(self, lik, fm, fv, gm, gv, y, noise, n_quad=64, rule=None, out=None):
+        """Log predictive density of y under rows of a predict call: returns ((3, N) array: logp, ymean, yvar; sum of logp).
+        lik 'onoff' (rows 3-6 of predict / kron_predict; g integrated by `rule` = (nodes, weights) for N(0, 1), default Gauss-Hermite
+        with n_quad nodes), 'gaussian' or 'bernoulli' (rows 0-1 of kron_head_predict, closed form; gm, gv and the rule are not read and
+        may be None).  out: a float64 buffer of at least 3 N entries to fill instead of a new array."""
+        lik = self.DENSITY_LIK[lik] if isinstance(lik, str) else int(lik)
+        onoff = lik == _lib.LIK_ONOFF
+        fm = as_f64(fm).reshape(-1)
+        N = fm.size
+        rows = [fm] + [None if a is None else as_f64(a).reshape(-1) for a in (fv, gm if onoff else None, gv if onoff else None, y)]
+        if any(a is not None and a.size != N for a in rows):
+            raise ValueError('density_rows: fm, fv, gm, gv and y must have the same length')
+        x, w = self._rule(n_quad, rule) if onoff else (None, None)
+        if out is None:
+            out = np.zeros(3 * N)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.size >= 3 * N):
+            raise ValueError('density_rows: out must be a C-contiguous float64 array of at least 3 N entries')
+        total = np.zeros(1)
+        _check(self.lib, self.ctx, self.lib.zigp_density_rows(self.ctx, lik, *[None if a is None else ptr(a) for a in rows], N, float(noise),
+                                                              None if x is None else ptr(x), None if w is None else ptr(w),
+                                                              0 if x is None else x.size, ptr(out), ptr(total)))
+        return out.reshape(-1)[:3 * N].reshape(3, N), float(total[0])
+
+    def predict_density(self, p, Xnew, Ynew, jitter=1e-6, g_offset=0.0, n_quad=64, rule=None, rows_out=True):
+        """Held-out log density of the dense OnOff model: predict at Xnew (N, D), then the density of Ynew (N) under its rows, on the device.
+        Returns ((3, N) array: logp, ymean, yvar; sum of logp); rows_out=False asks for the sum alone (None in place of the array)."""
+        pk = _Packed(p)
+        self._set_mean_function(p, pk.D)
+        self._set_modes(p)
+        Xnew, Ynew = as_f64(Xnew), as_f64(Ynew).reshape(-1)
+        if Xnew.ndim != 2 or Xnew.shape[1] != pk.D or Ynew.size != Xnew.shape[0]:
+            raise ValueError('Xnew must be (N,%d) and Ynew must have N entries' % pk.D)
+        x, w = self._rule(n_quad, rule)
+        N = Xnew.shape[0]
+        out = np.zeros((3, N)) if rows_out else None
+        total = np.zeros(1)
+        _check(self.lib, self.ctx, self.lib.zigp_predict_density(self.ctx, C.byref(pk.struct), ptr(Xnew), ptr(Ynew), N, float(jitter),
+                                                                 float(g_offset), ptr(x), ptr(w), x.size,
+                                                                 None if out is None else ptr(out), ptr(total)))
+        return out, float(total[0])
+
+    def predict_density_device(self, p, X_t, Y_t, jitter=1e-6, g_offset=0.0, n_quad=64, rule=None, out=None):
+        """predict_density on torch CUDA float64 tensors X_t (N, D) and Y_t (N) or (N, 1) of the engine's device; returns (a (3, N) CUDA
+        tensor, or `out` filled; the sum as a float) -- nothing but the parameters, the rule and the sum crosses PCIe."""
+        import torch
+        pk = _Packed(p)
+        self._set_mean_function(p, pk.D)
+        self._set_modes(p)
+
+        def ok(t):
+            return t.is_cuda and t.device.index == self.device and t.dtype == torch.float64 and t.is_contiguous()
+        if not (ok(X_t) and X_t.dim() == 2 and X_t.shape[1] == pk.D):
+            raise ValueError('predict_density_device: X needs a contiguous float64 (N,%d) tensor on cuda:%d' % (pk.D, self.device))
+        N = int(X_t.shape[0])
+        if not (ok(Y_t) and Y_t.numel() == N):
+            raise ValueError('predict_density_device: Y needs a contiguous float64 tensor of N entries on cuda:%d' % self.device)
+        if out is None:
+            out = torch.empty((3, N), dtype=torch.float64, device=X_t.device)
+        elif not (ok(out) and tuple(out.shape) == (3, N)):
+            raise ValueError('predict_density_device: out must be a contiguous float64 (3,N) tensor on the same device')
+        x, w = self._rule(n_quad, rule)
+        total = np.zeros(1)
+        torch.cuda.current_stream(self.device).synchronize()      # the engine's streams are not ordered after torch's
+        _check(self.lib, self.ctx, self.lib.zigp_predict_density_device(self.ctx, C.byref(pk.struct), C.c_void_p(X_t.data_ptr()),
+                                                                        C.c_void_p(Y_t.data_ptr()), N, float(jitter), float(g_offset),
+                                                                        ptr(x), ptr(w), x.size, C.c_void_p(out.data_ptr()), ptr(total)))
+        return out, float(total[0])
+
     def prior_kl(self, p, jitter=1e-6):
         pk = _Packed(p)
         self._set_modes(p)
