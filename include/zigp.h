@@ -435,6 +435,26 @@ int zigp_predict_density(zigp_ctx* ctx, const zigp_params* p, const double* Xnew
  * ZIGP_EARG): nothing crosses PCIe but the parameters, the rule (host pointers) and the sum (a host double); complete on return. */
 int zigp_predict_density_device(zigp_ctx* ctx, const zigp_params* p, const double* dXnew, const double* dYnew, int64_t N, double jitter,
                                 double g_offset, const double* nodes, const double* weights, int32_t n_quad, double* d_out3, double* sum);
+/* The same rule centred on each row's mode (OnOff only; DESIGN.md section 10, "centred").  A rule centred on gm cannot see mass that
+ * sits far from gm or in a spike between its nodes; these three calls shift and scale the caller's rule, per row, to a mode of the
+ * integrand.  With sg = sqrt(max(gv, 0)), z = (g - gm) / sg,
+ *   F(z) = -z^2 / 2 + l(Phi~(gm + sg z)),   l(u) = -0.5 log(2 pi s(u)) - 0.5 (y - u fm)^2 / s(u),   s(u) = noise + u^2 max(fv, 0):
+ *   zhat = a local maximiser of F: a safeguarded Newton search from z = 0 with analytic derivatives (every step at most one unit of g and
+ *          halved until F does not decrease; at most 60 iterations),  tau = 1 / sqrt(-F''(zhat)) clamped to (0, 1.5], 1 where -F'' <= 0;
+ *   z_i  = zhat + tau x_i,
+ *   logp = logsumexp_i [ log w_i + x_i^2 / 2 + log tau - z_i^2 / 2 + l(Phi~(gm + sg z_i)) ].
+ * Given (zhat, tau) that finite sum IS the result (one node: the Laplace approximation); gv <= 0 gives zhat = 0, tau = 1 exactly.
+ * centre2 (nullable) is (2, N): zhat, tau -- host memory, device memory in the _device call.  ymean, yvar, *sum, out3, the
+ * refusals and every other argument are those of the call without the suffix, bit for bit where they do not depend on the rule. */
+int zigp_density_rows_centred(zigp_ctx* ctx, const double* fm, const double* fv, const double* gm, const double* gv, const double* y,
+                              int64_t N, double noise, const double* nodes, const double* weights, int32_t n_quad, double* out3,
+                              double* sum, double* centre2);
+int zigp_predict_density_centred(zigp_ctx* ctx, const zigp_params* p, const double* Xnew, const double* Ynew, int64_t N, double jitter,
+                                 double g_offset, const double* nodes, const double* weights, int32_t n_quad, double* out3, double* sum,
+                                 double* centre2);
+int zigp_predict_density_centred_device(zigp_ctx* ctx, const zigp_params* p, const double* dXnew, const double* dYnew, int64_t N,
+                                        double jitter, double g_offset, const double* nodes, const double* weights, int32_t n_quad,
+                                        double* d_out3, double* sum, double* d_centre2);
 
 /* ---- data-parallel exchange (new: the reference is single-process) ----
  * The ELBO data term is a sum over points (tf.reduce_sum(var_exp), onoffgpf/OnOffSVGP.py:122; scripts/onoff.py:307): one process per GPU

@@ -7,6 +7,9 @@ with mpmath.quad at 30 digits over gm +- 12 sqrt(gv) in 64 panels.  Two row sets
           (oracle/zigp_oracle_torch.py, 10000 Adam steps in the unconstrained parameters) -- rows a user would actually score;
   stress  fm {0.5, 3, 10} x fv {1e-4, 0.1} x gm {-2, 0, 1.5} x gv {1e-3, 0.3, 9} x y {0, 0.4, 3} at noise 0.01 -- 162 rows, among them
           confident predictions scored against a far-away y, whose mass sits in the far tail of q(g).
+The window gm +- 12 sqrt(gv) TRUNCATES the truth: on ten stress rows (gv = 1e-3, fm = 10) mass lies outside it, and on five of them the
+reported "truth" is the window's edge, 114 to 1487 nats below the integral (fm = 10, gm = 1.5, gv = 1e-3, y = 0: -3814 here, -2327.6 over
+a range that holds the mass).  tools/density_centred_accuracy.py measures the same rows against that wider range.
 Appends the table to profiles/density_accuracy.log (or the file named by DENSITY_ACC_LOG).
 
   python tools/density_accuracy.py

@@ -9,6 +9,16 @@
 // That finite sum is the definition; its distance from the integral belongs to the rule (tools/density_accuracy.py).
 // Heads, closed form: Gaussian logp = log N(y; fm, fv + noise); Bernoulli p = the probability of k_kron_head_pointwise,
 // logp = log p (y == 1) or log1p(-p).
+//
+// Centred (OnOff only; k_density_rows_centred, the zigp_*_centred entry points): the same N(0, 1) rule, shifted and scaled per row to a
+// mode of the integrand.  With sg = sqrt(max(gv, 0)), z = (g - gm) / sg and l(u) = -0.5 log(2 pi s(u)) - 0.5 (y - u fm)^2 / s(u),
+// s(u) = noise + u^2 max(fv, 0):
+//   F(z)  = -z^2 / 2 + l(Phi~(gm + sg z))
+//   zhat  = a local maximiser of F, by a safeguarded Newton search from z = 0 (dc_search);  tau = 1 / sqrt(-F''(zhat)), at most DC_TAU_MAX
+//   z_i   = zhat + tau x_i
+//   logp  = logsumexp_i [ log w_i + x_i^2 / 2 + log tau - z_i^2 / 2 + l(Phi~(gm + sg z_i)) ]
+// (the change of variables z = zhat + tau x under the same rule; one node is the Laplace approximation).  Given (zhat, tau), which the
+// kernel returns, that finite sum is the definition.
 #include "zigp_host.h"
 #include <cmath>
 
@@ -86,6 +96,120 @@ k_density_rows(DensityArgs a) {
     ymean = p; yvar = __dmul_rn(p, 1.0 - p);
   }
   if (valid && a.out3) { double* q = a.out3 + n; q[0] = logp; q[a.ld3] = ymean; q[2 * a.ld3] = yvar; }
+  const double sum = block_sum<DN_THREADS / 64>(valid ? logp : 0.0, sh);
+  if (threadIdx.x == 0) a.part[blockIdx.x] = sum;
+}
+
+// ---- the rule centred on each row's mode ------------------------------------------------------------------------------------------
+constexpr int DC_MAX_ITER = 60;        // Newton iterations at most: a row can never spin
+constexpr int DC_MAX_HALVE = 30;       // halvings of one step at most
+constexpr double DC_TAU_MAX = 1.5;     // tau = 1 / sqrt(-F'') is clamped to (0, DC_TAU_MAX]
+constexpr double DC_SG_FLOOR = 1.e-3;  // a step is at most one unit of g: 1 / max(sg, DC_SG_FLOOR) in z
+constexpr double DC_FREE_STEP = 1.e-4; // in units of 1 / sqrt(-F''): a Newton step this small is taken unchecked (F cannot resolve it) ...
+constexpr double DC_STOP_STEP = 1.e-9; // ... and one this small ends the search
+constexpr double DC_INV_SQRT_2PI = 0.39894228040143267794;
+
+struct DensityCentredArgs {
+  DensityArgs a;      // rule: x_i [n_quad], log w_i [n_quad], x_i^2 / 2 [n_quad]
+  double* centre2;    // (2, ldc): zhat, tau (nullable)
+  int64_t ldc;
+};
+
+struct DcRow { double fm, fvp, gm, sg, y, noise; };
+struct DcVal { double F, F1, F2; };
+
+// F, F' and F'' at z:  F' = -z + sg l'(u) phi(g),  F'' = -1 + sg^2 [ l''(u) phi(g)^2 - g l'(u) phi(g) ],  phi(g) = (1 - 2e-3) N(g; 0, 1)
+__device__ __forceinline__ DcVal dc_eval(const DcRow& w, double z) {
+  const double g = w.gm + w.sg * z;
+  const double ph = dn_link(g);
+  const double dph = (1.0 - 2.e-3) * DC_INV_SQRT_2PI * exp(-0.5 * g * g);
+  const double s = w.noise + ph * ph * w.fvp, r = w.y - ph * w.fm, q = ph * w.fvp;
+  const double r2 = r * r, s2 = s * s;
+  DcVal v;
+  v.F = -0.5 * z * z + (-0.5 * (DN_LOG_2PI + log(s)) - 0.5 * r2 / s);
+  const double l1 = (r * w.fm - q) / s + r2 * q / s2;
+  const double l2 = -(w.fvp + w.fm * w.fm) / s + (2.0 * q * q - 4.0 * r * w.fm * q + r2 * w.fvp) / s2 - 4.0 * r2 * (q * q) / (s2 * s);
+  v.F1 = -z + w.sg * l1 * dph;
+  v.F2 = -1.0 + w.sg * w.sg * (l2 * dph * dph - g * l1 * dph);
+  return v;
+}
+
+// The search, in registers: Newton where -F'' > 0, else a capped step along sign(F'); every step capped at one unit of g and halved until
+// F does not decrease.  sg = 0 gives F' = 0 and F'' = -1 exactly: zhat = 0, tau = 1.
+__device__ __forceinline__ void dc_search(const DcRow& w, double& zhat, double& tau) {
+  const double cap = 1.0 / fmax(w.sg, DC_SG_FLOOR);
+  double z = 0.0;
+  DcVal v = dc_eval(w, z);
+  for (int it = 0; it < DC_MAX_ITER; ++it) {
+    const double h = -v.F2;
+    const bool newton = h > 0.0;
+    double step = newton ? v.F1 / h : (v.F1 > 0.0 ? cap : v.F1 < 0.0 ? -cap : 0.0);
+    step = step > cap ? cap : step < -cap ? -cap : step;
+    if (!(fabs(step) > 0.0)) break;   // zero or NaN
+    const double unit = newton ? 1.0 / sqrt(h) : 0.0;
+    const bool free_step = fabs(step) <= DC_FREE_STEP * unit, stop = fabs(step) <= DC_STOP_STEP * unit;
+    bool accepted = false;
+    double zn = z;
+    DcVal vn = v;
+    for (int k = 0; k <= DC_MAX_HALVE; ++k) {
+      zn = z + step;
+      vn = dc_eval(w, zn);
+      if (free_step || vn.F >= v.F) { accepted = true; break; }
+      step *= 0.5;
+    }
+    if (!accepted) break;
+    z = zn; v = vn;
+    if (stop) break;
+  }
+  const double h = -v.F2;
+  zhat = z;
+  tau = h > 0.0 ? fmin(1.0 / sqrt(h), DC_TAU_MAX) : 1.0;
+}
+
+__global__ void __launch_bounds__(DN_THREADS)
+k_density_rows_centred(DensityCentredArgs c) {
+  const DensityArgs& a = c.a;
+  __shared__ double sx[DN_MAXQ], slw[DN_MAXQ], shx[DN_MAXQ];
+  __shared__ double sh[DN_THREADS / 64];
+  const int64_t n = (int64_t)blockIdx.x * DN_THREADS + threadIdx.x;
+  const bool valid = n < a.N;
+  const double fm = valid ? a.fm[n] : 0.0, fv = valid ? a.fv[n] : 0.0, y = valid ? a.y[n] : 0.0;
+  for (int i = threadIdx.x; i < a.n_quad; i += DN_THREADS) { sx[i] = a.rule[i]; slw[i] = a.rule[a.n_quad + i]; shx[i] = a.rule[2 * a.n_quad + i]; }
+  __syncthreads();
+  const double gm = valid ? a.gm[n] : 0.0, gv = valid ? a.gv[n] : 0.0;
+  const double sg = sqrt(fmax(gv, 0.0)), fvp = fmax(fv, 0.0);
+  double zhat, tau;
+  {
+    DcRow w;
+    w.fm = fm; w.fvp = fvp; w.gm = gm; w.sg = sg; w.y = y; w.noise = a.noise;
+    dc_search(w, zhat, tau);
+  }
+  const double lt = log(tau);
+  // the online log-sum-exp of k_density_rows over the shifted and scaled nodes
+  double m = 0.0, acc = 1.0;
+  for (int i = 0; i < a.n_quad; ++i) {
+    const double z = zhat + tau * sx[i];
+    const double ph = dn_link(gm + sg * z);
+    const double s = a.noise + ph * ph * fvp, r = y - ph * fm;
+    const double l = ((slw[i] + shx[i]) + lt) - 0.5 * z * z + (-0.5 * (DN_LOG_2PI + log(s)) - 0.5 * (r * r) / s);
+    if (i == 0) { m = l; continue; }
+    const double d = l - m, e = exp(-fabs(d));
+    if (d > 0.0) { acc = fma(acc, e, 1.0); m = l; } else acc += e;
+  }
+  const double logp = m + log(acc);
+  double ymean, yvar;
+  if (a.m0) {   // as k_density_rows: the moments are not the rule's business
+    ymean = valid ? a.m0[n] : 0.0;
+    yvar = __dadd_rn(__dadd_rn(valid ? a.m1[n] : 0.0, valid ? a.m2[n] : 0.0), a.noise);
+  } else {
+    const PwOut o = pointwise_eval(fm, fv, gm, gv, y, a.noise);
+    double gfvar = o.gfvar, gfmeanu = o.gfmeanu;
+    asm volatile("" : "+v"(gfvar), "+v"(gfmeanu));
+    ymean = o.gfmean;
+    yvar = __dadd_rn(__dadd_rn(gfvar, gfmeanu), a.noise);
+  }
+  if (valid && a.out3) { double* q = a.out3 + n; q[0] = logp; q[a.ld3] = ymean; q[2 * a.ld3] = yvar; }
+  if (valid && c.centre2) { double* q = c.centre2 + n; q[0] = zhat; q[c.ldc] = tau; }
   const double sum = block_sum<DN_THREADS / 64>(valid ? logp : 0.0, sh);
   if (threadIdx.x == 0) a.part[blockIdx.x] = sum;
 }
@@ -172,6 +296,58 @@ int predict_density(zigp_ctx* c, const zigp_params* p, const double* dX, const d
   return ZIGP_OK;
 }
 
+// ---- centred: its own layout of scratch2 (the rule's table has three columns, and the (2, N) centre follows the three output rows) ----
+constexpr size_t DC_OFF_SUM = 3 * DN_MAXQ, DC_OFF_PART = 3 * DN_MAXQ + 8;
+struct DensityCentredBufs { DensityBufs b; double* centre2; };
+
+int density_centred_bufs(zigp_ctx* c, int64_t N, DensityCentredBufs& cb) {
+  DensityBufs& b = cb.b;
+  b.nb = ceil_div(N, DN_THREADS);
+  const size_t off_out = (DC_OFF_PART + (size_t)b.nb + 7) & ~(size_t)7;
+  ZIGP_ENSURE(c, c->scratch2, off_out + (size_t)5 * N);
+  b.rule = c->scratch2.p; b.sum = c->scratch2.p + DC_OFF_SUM; b.part = c->scratch2.p + DC_OFF_PART; b.out3 = c->scratch2.p + off_out;
+  cb.centre2 = b.out3 + (size_t)3 * N;
+  return 0;
+}
+
+// density_run for the centred kernel: the table is nodes, log weights, x^2 / 2 (both taken here); the block partials go to k_density_sum
+int density_centred_run(zigp_ctx* c, DensityCentredArgs ca, const DensityBufs& b, const double* nodes, const double* weights, double** hsum) {
+  const int nq = ca.a.n_quad;
+  ZIGP_PINNED(c, h, 3 * (size_t)nq);
+  for (int i = 0; i < nq; ++i) { h[i] = nodes[i]; h[nq + i] = log(weights[i]); h[2 * nq + i] = 0.5 * nodes[i] * nodes[i]; }
+  ZIGP_HIP(c, hipMemcpyAsync(b.rule, h, sizeof(double) * 3 * nq, hipMemcpyHostToDevice, c->stream));
+  ca.a.rule = b.rule; ca.a.part = b.part;
+  const dim3 grid(b.nb), block(DN_THREADS);
+  hipLaunchKernelGGL(k_density_rows_centred, grid, block, 0, c->stream, ca);
+  ZIGP_HIP(c, hipGetLastError());
+  hipLaunchKernelGGL(k_density_sum, dim3(1), block, 0, c->stream, b.part, b.nb, b.sum);
+  ZIGP_HIP(c, hipGetLastError());
+  return download(c, b.sum, 1, hsum);
+}
+
+// zigp_predict_density_centred / zigp_predict_density_centred_device behind their argument checks, as predict_density
+int predict_density_centred(zigp_ctx* c, const zigp_params* p, const double* dX, const double* dY, int64_t N, double jitter, double g_offset,
+                            const double* nodes, const double* weights, int n_quad, double* out3, double* centre2, bool on_device, double* sum) {
+  DensityCentredBufs cb;
+  ZIGP_TRY(density_centred_bufs(c, N, cb));
+  ZIGP_ENSURE(c, c->out9, (size_t)9 * N);
+  ZIGP_TRY(run_dense(c, p, dX, nullptr, N, p->D, jitter, 1.0, g_offset, 0, N, 0, true, c->out9.p, nullptr, nullptr, nullptr));   // complete on return
+  const double* r = c->out9.p;
+  DensityCentredArgs ca{};
+  DensityArgs& a = ca.a;
+  a.m0 = r; a.m1 = r + N; a.m2 = r + 2 * N; a.fm = r + 3 * N; a.fv = r + 4 * N; a.gm = r + 5 * N; a.gv = r + 6 * N; a.y = dY;
+  a.N = N; a.noise = p->noise; a.n_quad = n_quad; a.ld3 = N; ca.ldc = N;
+  a.out3 = !out3 ? nullptr : on_device ? out3 : cb.b.out3;
+  ca.centre2 = !centre2 ? nullptr : on_device ? centre2 : cb.centre2;
+  double* hsum = nullptr;
+  ZIGP_TRY(density_centred_run(c, ca, cb.b, nodes, weights, &hsum));
+  if (out3 && !on_device) ZIGP_HIP(c, hipMemcpyAsync(out3, cb.b.out3, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, c->stream));
+  if (centre2 && !on_device) ZIGP_HIP(c, hipMemcpyAsync(centre2, cb.centre2, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  *sum = hsum[0];
+  return ZIGP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -238,6 +414,74 @@ int zigp_predict_density_device(zigp_ctx* c, const zigp_params* p, const double*
     }
   }
   return predict_density(c, p, dXnew, dYnew, N, jitter, g_offset, nodes, weights, n_quad, d_out3, true, sum);
+}
+
+int zigp_density_rows_centred(zigp_ctx* c, const double* fm, const double* fv, const double* gm, const double* gv, const double* y, int64_t N,
+                              double noise, const double* nodes, const double* weights, int32_t n_quad, double* out3, double* sum,
+                              double* centre2) {
+  if (!c) return ZIGP_EARG;
+  ZIGP_TRY(density_check(c, "zigp_density_rows_centred", ZIGP_LIK_ONOFF, N, noise, nodes, weights, n_quad));
+  if (!sum) return fail_arg(c, "zigp_density_rows_centred: sum is NULL");
+  if (N > 0 && (!fm || !fv || !y || !gm || !gv)) return fail_arg(c, "zigp_density_rows_centred: a row pointer (fm, fv, gm, gv, y) is NULL");
+  if (N == 0) { *sum = 0.0; return ZIGP_OK; }
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  ZIGP_TRY(begin_staged_call(c));
+  DensityCentredBufs cb;
+  ZIGP_TRY(density_centred_bufs(c, N, cb));
+  ZIGP_ENSURE(c, c->scratch, (size_t)5 * N);
+  double* d = c->scratch.p;
+  const double* src[5] = {fm, fv, y, gm, gv};
+  for (int k = 0; k < 5; ++k) ZIGP_HIP(c, hipMemcpyAsync(d + k * N, src[k], sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
+  DensityCentredArgs ca{};
+  DensityArgs& a = ca.a;
+  a.fm = d; a.fv = d + N; a.y = d + 2 * N; a.gm = d + 3 * N; a.gv = d + 4 * N;
+  a.N = N; a.noise = noise; a.n_quad = n_quad; a.out3 = out3 ? cb.b.out3 : nullptr; a.ld3 = N;
+  ca.centre2 = centre2 ? cb.centre2 : nullptr; ca.ldc = N;
+  double* hsum = nullptr;
+  ZIGP_TRY(density_centred_run(c, ca, cb.b, nodes, weights, &hsum));
+  if (out3) ZIGP_HIP(c, hipMemcpyAsync(out3, cb.b.out3, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, c->stream));
+  if (centre2) ZIGP_HIP(c, hipMemcpyAsync(centre2, cb.centre2, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  *sum = hsum[0];
+  return ZIGP_OK;
+}
+
+int zigp_predict_density_centred(zigp_ctx* c, const zigp_params* p, const double* Xnew, const double* Ynew, int64_t N, double jitter,
+                                 double g_offset, const double* nodes, const double* weights, int32_t n_quad, double* out3, double* sum,
+                                 double* centre2) {
+  if (!c) return ZIGP_EARG;
+  ZIGP_TRY(validate_params(c, p));
+  ZIGP_TRY(density_check(c, "zigp_predict_density_centred", ZIGP_LIK_ONOFF, N, p->noise, nodes, weights, n_quad));
+  if (!sum) return fail_arg(c, "zigp_predict_density_centred: sum is NULL");
+  if (N > 0 && (!Xnew || !Ynew)) return fail_arg(c, "zigp_predict_density_centred: Xnew or Ynew is NULL");
+  if (N == 0) { *sum = 0.0; return ZIGP_OK; }
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  const size_t nx = ((size_t)N * p->D + 7) & ~(size_t)7;
+  ZIGP_ENSURE(c, c->scratch, nx + (size_t)N);
+  ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p, Xnew, sizeof(double) * N * p->D, hipMemcpyHostToDevice, c->stream));
+  ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p + nx, Ynew, sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
+  return predict_density_centred(c, p, c->scratch.p, c->scratch.p + nx, N, jitter, g_offset, nodes, weights, n_quad, out3, centre2, false, sum);
+}
+
+int zigp_predict_density_centred_device(zigp_ctx* c, const zigp_params* p, const double* dXnew, const double* dYnew, int64_t N, double jitter,
+                                        double g_offset, const double* nodes, const double* weights, int32_t n_quad, double* d_out3,
+                                        double* sum, double* d_centre2) {
+  if (!c) return ZIGP_EARG;
+  ZIGP_TRY(validate_params(c, p));
+  ZIGP_TRY(density_check(c, "zigp_predict_density_centred_device", ZIGP_LIK_ONOFF, N, p->noise, nodes, weights, n_quad));
+  if (!sum) return fail_arg(c, "zigp_predict_density_centred_device: sum is NULL");
+  if (N > 0 && (!dXnew || !dYnew)) return fail_arg(c, "zigp_predict_density_centred_device: Xnew or Ynew is NULL");
+  if (N == 0) { *sum = 0.0; return ZIGP_OK; }
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  for (const double* q : {dXnew, dYnew, (const double*)d_out3, (const double*)d_centre2}) {   // as zigp_predict_density_device
+    hipPointerAttribute_t at;
+    if (!q) continue;
+    if (hipPointerGetAttributes(&at, q) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->device) {
+      (void)hipGetLastError();
+      return fail_arg(c, "zigp_predict_density_centred_device: Xnew, Ynew, out3 and centre2 must be device memory of the context's GPU");
+    }
+  }
+  return predict_density_centred(c, p, dXnew, dYnew, N, jitter, g_offset, nodes, weights, n_quad, d_out3, d_centre2, true, sum);
 }
 
 }  // extern "C"

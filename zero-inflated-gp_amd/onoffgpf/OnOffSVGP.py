@@ -199,12 +199,14 @@ class OnOffSVGP(Parameterized):
         noise = float(self.likelihood.variance.value.reshape(-1)[0])
         return out[0].reshape(-1, 1), ((out[1] + out[2]) + noise).reshape(-1, 1)
 
-    def predict_density(self, Xnew, Ynew, n_quad=64):
+    def predict_density(self, Xnew, Ynew, n_quad=64, centre='mean'):
         """GPflow's predict_density: log p(Ynew | Xnew) per row, (N,1) -- f integrated in closed form, g by Gauss-Hermite quadrature with
-        n_quad nodes on the device (zigp_predict_density); a row whose mass lies in the far tail of q(g) is beyond the rule (DESIGN.md
-        section 10)."""
+        n_quad nodes on the device (zigp_predict_density).  centre='mean' centres the rule on gm: a row whose mass lies in the far tail
+        of q(g), or in a spike between two nodes, is beyond it; centre='mode' shifts and scales the rule to each row's mode
+        (zigp_predict_density_centred)."""
+        kw = {} if centre == 'mean' else {'centre': centre}
         out, _ = self._engine.predict_density(self._values(), np.asarray(Xnew, dtype=np.float64), np.asarray(Ynew, dtype=np.float64),
-                                              jitter=JITTER, n_quad=n_quad)
+                                              jitter=JITTER, n_quad=n_quad, **kw)
         return out[0].reshape(-1, 1)
 
     def optimize(self, method='L-BFGS-B', maxiter=1000, disp=False, callback=None, learning_rate=0.01, device_loop=None, **kw):

@@ -209,6 +209,11 @@ SIGNATURES = {
     'zigp_predict_density': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), dp, dp, C.c_int64, C.c_double, C.c_double, dp, dp, C.c_int32, dp, dp]),
     'zigp_predict_density_device': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
                                               dp, dp, C.c_int32, C.c_void_p, dp]),
+    'zigp_density_rows_centred': (C.c_int, [C.c_void_p, dp, dp, dp, dp, dp, C.c_int64, C.c_double, dp, dp, C.c_int32, dp, dp, dp]),
+    'zigp_predict_density_centred': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), dp, dp, C.c_int64, C.c_double, C.c_double, dp, dp, C.c_int32,
+                                               dp, dp, dp]),
+    'zigp_predict_density_centred_device': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
+                                                      dp, dp, C.c_int32, C.c_void_p, dp, C.c_void_p]),
     'zigp_profile_enable': (C.c_int, [C.c_void_p, C.c_int32]),
     'zigp_profile_get': (C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int64), dp]),
     'zigp_profile_reset': (C.c_int, [C.c_void_p]),

@@ -495,12 +495,24 @@ class DenseEngine:
             raise ValueError('rule: nodes and weights must have the same length')
         return x, w
 
-    def density_rows(self, lik, fm, fv, gm, gv, y, noise, n_quad=64, rule=None, out=None):
+    @staticmethod
+    def _centre(centre, lik=None):
+        """True for centre='mode', False for 'mean' (the rule centred on gm); the heads are closed form and have no rule to centre"""
+        if centre not in ('mean', 'mode'):
+            raise ValueError("centre must be 'mean' (the rule centred on gm) or 'mode' (centred on each row's mode), not %r" % (centre,))
+        if centre == 'mode' and lik is not None and lik != _lib.LIK_ONOFF:
+            raise ValueError("centre='mode' applies to the 'onoff' density only: the Gaussian and Bernoulli heads are closed form")
+        return centre == 'mode'
+
+    def density_rows(self, lik, fm, fv, gm, gv, y, noise, n_quad=64, rule=None, out=None, centre='mean', return_centre=False):
         """Log predictive density of y under rows of a predict call: returns ((3, N) array: logp, ymean, yvar; sum of logp).
         lik 'onoff' (rows 3-6 of predict / kron_predict; g integrated by `rule` = (nodes, weights) for N(0, 1), default Gauss-Hermite
         with n_quad nodes), 'gaussian' or 'bernoulli' (rows 0-1 of kron_head_predict, closed form; gm, gv and the rule are not read and
-        may be None).  out: a float64 buffer of at least 3 N entries to fill instead of a new array."""
+        may be None).  out: a float64 buffer of at least 3 N entries to fill instead of a new array.
+        centre='mode' ('onoff' only) shifts and scales the rule, per row, to a mode of the integrand (zigp_density_rows_centred);
+        return_centre=True appends the (2, N) array (zhat, tau) of that search to the result -- zeros and ones under centre='mean'."""
         lik = self.DENSITY_LIK[lik] if isinstance(lik, str) else int(lik)
+        mode = self._centre(centre, lik)
         onoff = lik == _lib.LIK_ONOFF
         fm = as_f64(fm).reshape(-1)
         N = fm.size
@@ -513,14 +525,24 @@ class DenseEngine:
         elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.size >= 3 * N):
             raise ValueError('density_rows: out must be a C-contiguous float64 array of at least 3 N entries')
         total = np.zeros(1)
-        _check(self.lib, self.ctx, self.lib.zigp_density_rows(self.ctx, lik, *[None if a is None else ptr(a) for a in rows], N, float(noise),
-                                                              None if x is None else ptr(x), None if w is None else ptr(w),
-                                                              0 if x is None else x.size, ptr(out), ptr(total)))
-        return out.reshape(-1)[:3 * N].reshape(3, N), float(total[0])
+        centre2 = np.vstack([np.zeros(N), np.ones(N)]) if return_centre else None
+        if mode:
+            if any(a is None for a in rows):
+                raise ValueError("density_rows: centre='mode' needs fm, fv, gm, gv and y")
+            _check(self.lib, self.ctx, self.lib.zigp_density_rows_centred(self.ctx, *[ptr(a) for a in rows], N, float(noise), ptr(x), ptr(w), x.size,
+                                                                          ptr(out), ptr(total), None if centre2 is None else ptr(centre2)))
+        else:
+            _check(self.lib, self.ctx, self.lib.zigp_density_rows(self.ctx, lik, *[None if a is None else ptr(a) for a in rows], N, float(noise),
+                                                                  None if x is None else ptr(x), None if w is None else ptr(w),
+                                                                  0 if x is None else x.size, ptr(out), ptr(total)))
+        res = out.reshape(-1)[:3 * N].reshape(3, N), float(total[0])
+        return res + (centre2,) if return_centre else res
 
-    def predict_density(self, p, Xnew, Ynew, jitter=1e-6, g_offset=0.0, n_quad=64, rule=None, rows_out=True):
+    def predict_density(self, p, Xnew, Ynew, jitter=1e-6, g_offset=0.0, n_quad=64, rule=None, rows_out=True, centre='mean', return_centre=False):
         """Held-out log density of the dense OnOff model: predict at Xnew (N, D), then the density of Ynew (N) under its rows, on the device.
-        Returns ((3, N) array: logp, ymean, yvar; sum of logp); rows_out=False asks for the sum alone (None in place of the array)."""
+        Returns ((3, N) array: logp, ymean, yvar; sum of logp); rows_out=False asks for the sum alone (None in place of the array).
+        centre and return_centre: as density_rows."""
+        mode = self._centre(centre)
         pk = _Packed(p)
         self._set_mean_function(p, pk.D)
         self._set_modes(p)
@@ -531,15 +553,25 @@ class DenseEngine:
         N = Xnew.shape[0]
         out = np.zeros((3, N)) if rows_out else None
         total = np.zeros(1)
-        _check(self.lib, self.ctx, self.lib.zigp_predict_density(self.ctx, C.byref(pk.struct), ptr(Xnew), ptr(Ynew), N, float(jitter),
-                                                                 float(g_offset), ptr(x), ptr(w), x.size,
-                                                                 None if out is None else ptr(out), ptr(total)))
-        return out, float(total[0])
+        centre2 = np.vstack([np.zeros(N), np.ones(N)]) if return_centre else None
+        if mode:
+            _check(self.lib, self.ctx, self.lib.zigp_predict_density_centred(self.ctx, C.byref(pk.struct), ptr(Xnew), ptr(Ynew), N, float(jitter),
+                                                                             float(g_offset), ptr(x), ptr(w), x.size,
+                                                                             None if out is None else ptr(out), ptr(total),
+                                                                             None if centre2 is None else ptr(centre2)))
+        else:
+            _check(self.lib, self.ctx, self.lib.zigp_predict_density(self.ctx, C.byref(pk.struct), ptr(Xnew), ptr(Ynew), N, float(jitter),
+                                                                     float(g_offset), ptr(x), ptr(w), x.size,
+                                                                     None if out is None else ptr(out), ptr(total)))
+        res = out, float(total[0])
+        return res + (centre2,) if return_centre else res
 
-    def predict_density_device(self, p, X_t, Y_t, jitter=1e-6, g_offset=0.0, n_quad=64, rule=None, out=None):
+    def predict_density_device(self, p, X_t, Y_t, jitter=1e-6, g_offset=0.0, n_quad=64, rule=None, out=None, centre='mean', return_centre=False):
         """predict_density on torch CUDA float64 tensors X_t (N, D) and Y_t (N) or (N, 1) of the engine's device; returns (a (3, N) CUDA
-        tensor, or `out` filled; the sum as a float) -- nothing but the parameters, the rule and the sum crosses PCIe."""
+        tensor, or `out` filled; the sum as a float) -- nothing but the parameters, the rule and the sum crosses PCIe.
+        centre and return_centre: as density_rows, the (2, N) centre a CUDA tensor."""
         import torch
+        mode = self._centre(centre)
         pk = _Packed(p)
         self._set_mean_function(p, pk.D)
         self._set_modes(p)
@@ -557,11 +589,20 @@ class DenseEngine:
             raise ValueError('predict_density_device: out must be a contiguous float64 (3,N) tensor on the same device')
         x, w = self._rule(n_quad, rule)
         total = np.zeros(1)
+        centre2 = None
+        if return_centre:
+            centre2 = torch.cat([torch.zeros((1, N), dtype=torch.float64, device=X_t.device), torch.ones((1, N), dtype=torch.float64, device=X_t.device)])
         torch.cuda.current_stream(self.device).synchronize()      # the engine's streams are not ordered after torch's
-        _check(self.lib, self.ctx, self.lib.zigp_predict_density_device(self.ctx, C.byref(pk.struct), C.c_void_p(X_t.data_ptr()),
-                                                                        C.c_void_p(Y_t.data_ptr()), N, float(jitter), float(g_offset),
-                                                                        ptr(x), ptr(w), x.size, C.c_void_p(out.data_ptr()), ptr(total)))
-        return out, float(total[0])
+        if mode:
+            _check(self.lib, self.ctx, self.lib.zigp_predict_density_centred_device(
+                self.ctx, C.byref(pk.struct), C.c_void_p(X_t.data_ptr()), C.c_void_p(Y_t.data_ptr()), N, float(jitter), float(g_offset),
+                ptr(x), ptr(w), x.size, C.c_void_p(out.data_ptr()), ptr(total), None if centre2 is None else C.c_void_p(centre2.data_ptr())))
+        else:
+            _check(self.lib, self.ctx, self.lib.zigp_predict_density_device(self.ctx, C.byref(pk.struct), C.c_void_p(X_t.data_ptr()),
+                                                                            C.c_void_p(Y_t.data_ptr()), N, float(jitter), float(g_offset),
+                                                                            ptr(x), ptr(w), x.size, C.c_void_p(out.data_ptr()), ptr(total)))
+        res = out, float(total[0])
+        return res + (centre2,) if return_centre else res
 
     def prior_kl(self, p, jitter=1e-6):
         pk = _Packed(p)
