@@ -4,7 +4,7 @@ test_cpu_density_centred.py, test_gpu_density_centred.py and tools/density_centr
 Per row, sg = sqrt(max(gv, 0)), z = (g - gm) / sg and
     F(z) = -z^2 / 2 + l(link(gm + sg z)),   l(u) = -0.5 log(2 pi s(u)) - 0.5 (y - u fm)^2 / s(u),   s(u) = noise + u^2 max(fv, 0).
 * `centre_np`         (zhat, tau): the safeguarded Newton search for a local maximiser of F from z = 0, the formulas in the order the
-                      kernel k_density_rows_centred writes them, and tau = 1 / sqrt(-F''(zhat)) clamped to TAU_MAX;
+                      kernel k_density_rows<ZIGP_LIK_ONOFF, true> writes them, and tau = 1 / sqrt(-F''(zhat)) clamped to TAU_MAX;
 * `logp_centred_np`   logsumexp_i [ log w_i + x_i^2 / 2 + log tau - z_i^2 / 2 + l(link(gm + sg z_i)) ],  z_i = zhat + tau x_i, in float64;
 * `logp_centred_mp`   the same finite sum on the same float64 inputs (zhat and tau included) at 50 digits;
 * `scales_centred`    density_ref.scales extended by the new terms: per node, on top of |l_i|, the link, the node g_i = gm + sg z_i and

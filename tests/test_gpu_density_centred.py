@@ -1,4 +1,4 @@
-"""GPU tests of the mode-centred predictive density (include/zigp.h "centred"; k_density_rows_centred in csrc/zigp_density.hip), in three
+"""GPU tests of the mode-centred predictive density (include/zigp.h "centred"; k_density_rows<ZIGP_LIK_ONOFF, true> in csrc/zigp_density.hip), in three
 tiers, each against tests/density_centred_ref.py:
   sum       at the kernel's OWN returned (zhat, tau) the finite sum is the definition: err_gpu <= 4 err_np + 16 eps S against the
             50-digit sum on the same float64 inputs (the project's rule for point-wise kernels, tests/test_gpu_density.py);
@@ -57,7 +57,8 @@ def _rows(N, seed=0):
 
 def test_sum_across_the_block_boundary(engine):
     """N = 1, 255, 256, 257: each call's rows, centres and sum; the 257-row call carries the 50-digit check, the shorter calls are its
-    prefixes bit for bit (a row's result does not depend on its neighbours), nothing is written past N, and the sum is the stable one"""
+    prefixes bit for bit (a row's result does not depend on its neighbours), nothing is written past N, and the sum is the stable one;
+    then the 257 rows at 256 nodes under both centres"""
     rows, ru = _rows(257, seed=7), Q.rule(20)
     out, total, c2 = engine.density_rows('onoff', *rows, Q.NOISE, rule=ru, centre='mode', return_centre=True)
     _sum_tier('centred block boundary', rows, ru, out, c2)
@@ -72,6 +73,27 @@ def test_sum_across_the_block_boundary(engine):
         o2, t2 = engine.density_rows('onoff', *[a[:N] for a in rows], Q.NOISE, rule=ru, centre='mode')
         assert t2 == tot[0] and np.array_equal(o2, out[:, :N])
         assert abs(tot[0] - np.sum(out[0, :N])) <= N * EPS * np.sum(np.abs(out[0, :N]))
+    # N = 257 at n_quad = 256: the one shape at which a full three-column table lies beside two block partials in the layout of scratch2
+    # that both centres share.  Each centre against its 50-digit sum; the centre='mean' call that follows the centre='mode' call is what
+    # an engine that never ran a centred call gives, bit for bit.
+    ru = Q.rule(256)
+    assert ru[0].size == 256
+    out, total, c2 = engine.density_rows('onoff', *rows, Q.NOISE, rule=ru, centre='mode', return_centre=True)
+    mean, mean_total = engine.density_rows('onoff', *rows, Q.NOISE, rule=ru)
+    _sum_tier('centred block boundary n_quad 256', rows, ru, out, c2)
+    truth = R.logp_mp(*rows, Q.NOISE, *ru)
+    err, err_np, S = R.err_to(truth, mean[0]), R.err_to(truth, R.logp_np(*rows, Q.NOISE, *ru)), R.scales(*rows, Q.NOISE, *ru)
+    print('gm-centred block boundary n_quad 256: %d rows, err_gpu / (eps S) max %.3f (NumPy %.3f)' % (len(S), (err / (EPS * S)).max(), (err_np / (EPS * S)).max()))
+    bad = np.nonzero(err > 4 * err_np + 16 * EPS * S)[0]
+    assert bad.size == 0, (bad[:5], err[bad[:5]] / (EPS * S[bad[:5]]))
+    assert abs(mean_total - np.sum(mean[0])) <= 257 * EPS * np.sum(np.abs(mean[0]))
+    import zigp
+    fresh = zigp.DenseEngine(0)
+    try:
+        fresh_mean, fresh_total = fresh.density_rows('onoff', *rows, Q.NOISE, rule=ru)
+    finally:
+        fresh.close()
+    assert np.array_equal(mean, fresh_mean) and mean_total == fresh_total
 
 
 # ---- 2. centre tier --------------------------------------------------------------------------------------------------------------

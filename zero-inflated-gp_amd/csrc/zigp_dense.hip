@@ -1538,12 +1538,7 @@ int zigp_predict_device(zigp_ctx* c, const zigp_params* p, const double* dXnew, 
   if (N < 0 || (N > 0 && (!dXnew || !d_out9))) return fail_arg(c, "zigp_predict_device: bad arguments");
   if (N == 0) return ZIGP_OK;
   ZIGP_HIP(c, hipSetDevice(c->device));
-  hipPointerAttribute_t ax, ao;     // both must be device memory of this context's GPU (a host pointer here would fault inside a kernel)
-  if (hipPointerGetAttributes(&ax, dXnew) != hipSuccess || hipPointerGetAttributes(&ao, d_out9) != hipSuccess ||
-      ax.type != hipMemoryTypeDevice || ao.type != hipMemoryTypeDevice || ax.device != c->device || ao.device != c->device) {
-    (void)hipGetLastError();
-    return fail_arg(c, "zigp_predict_device: Xnew and out9 must be device memory of the context's GPU");
-  }
+  ZIGP_TRY(require_device_ptrs(c, {dXnew, d_out9}, "zigp_predict_device: Xnew and out9 must be device memory of the context's GPU"));
   // rows in place: no copy in, no copy out; the call is complete on return (run_dense ends with the stream's synchronisation)
   return run_dense(c, p, dXnew, nullptr, N, p->D, jitter, 1.0, g_offset, 0, N, 0, true, d_out9, nullptr, nullptr, nullptr);
 }

@@ -10,8 +10,8 @@
 // Heads, closed form: Gaussian logp = log N(y; fm, fv + noise); Bernoulli p = the probability of k_kron_head_pointwise,
 // logp = log p (y == 1) or log1p(-p).
 //
-// Centred (OnOff only; k_density_rows_centred, the zigp_*_centred entry points): the same N(0, 1) rule, shifted and scaled per row to a
-// mode of the integrand.  With sg = sqrt(max(gv, 0)), z = (g - gm) / sg and l(u) = -0.5 log(2 pi s(u)) - 0.5 (y - u fm)^2 / s(u),
+// Centred (OnOff only; k_density_rows<ZIGP_LIK_ONOFF, true>, the zigp_*_centred entry points): the same N(0, 1) rule, shifted and scaled
+// per row to a mode of the integrand.  With sg = sqrt(max(gv, 0)), z = (g - gm) / sg and l(u) = -0.5 log(2 pi s(u)) - 0.5 (y - u fm)^2 / s(u),
 // s(u) = noise + u^2 max(fv, 0):
 //   F(z)  = -z^2 / 2 + l(Phi~(gm + sg z))
 //   zhat  = a local maximiser of F, by a safeguarded Newton search from z = 0 (dc_search);  tau = 1 / sqrt(-F''(zhat)), at most DC_TAU_MAX
@@ -19,6 +19,13 @@
 //   logp  = logsumexp_i [ log w_i + x_i^2 / 2 + log tau - z_i^2 / 2 + l(Phi~(gm + sg z_i)) ]
 // (the change of variables z = zhat + tau x under the same rule; one node is the Laplace approximation).  Given (zhat, tau), which the
 // kernel returns, that finite sum is the definition.
+//
+// One kernel template, k_density_rows<LIK, CENTRED>, in four instantiations (OnOff with either centre, the two heads), and one host path:
+// density_rows behind the two zigp_density_rows* entries, predict_density behind the four zigp_predict_density* entries.  The two OnOff
+// sums are written out side by side (dn_logsumexp): equal in exact arithmetic at zhat = 0, tau = 1, they differ in their rounding.
+// Both centres share one layout of scratch2 (stated at DN_OFF_SUM below).  Resources on gfx950 (-Rpass-analysis=kernel-resource-usage),
+// VGPRs / LDS bytes per block / waves per SIMD, no scratch anywhere: <ONOFF, false> 101 / 4128 / 4, <ONOFF, true> 130 / 6176 / 3,
+// <GAUSSIAN, false> 24 / 32 / 8, <BERNOULLI, false> 28 / 32 / 8.
 #include "zigp_host.h"
 #include <cmath>
 
@@ -35,10 +42,12 @@ struct DensityArgs {
   const double* m0; const double* m1; const double* m2;   // OnOff: gfmean, gfvar, gfmeanu of a predict block; NULL: from the four rows
   int64_t N;
   double noise;
-  const double* rule;   // OnOff: x_i [n_quad], then log w_i [n_quad]
+  const double* rule;   // OnOff: x_i [n_quad], then log w_i [n_quad]; centred: then x_i^2 / 2 [n_quad]
   int n_quad;
   double* out3;         // (3, ld3): logp, ymean, yvar (nullable)
   int64_t ld3;
+  double* centre2;      // centred: (2, ldc): zhat, tau (nullable)
+  int64_t ldc;
   double* part;         // [gridDim.x] block sums of logp
 };
 
@@ -47,57 +56,6 @@ constexpr double DN_LOG_2PI = 1.8378770664093454836;
 __device__ __forceinline__ double dn_link(double g) {   // OnOffSVGP.py:178, as pointwise_eval writes it
   const double c1 = 1.0 - 2.e-3, c0 = 1.e-3;
   return 0.5 * (1.0 + erf(g * 0.70710678118654752440)) * c1 + c0;
-}
-
-template <int LIK>
-__global__ void __launch_bounds__(DN_THREADS)
-k_density_rows(DensityArgs a) {
-  __shared__ double sx[LIK == ZIGP_LIK_ONOFF ? DN_MAXQ : 1], slw[LIK == ZIGP_LIK_ONOFF ? DN_MAXQ : 1];
-  __shared__ double sh[DN_THREADS / 64];
-  const int64_t n = (int64_t)blockIdx.x * DN_THREADS + threadIdx.x;
-  const bool valid = n < a.N;
-  const double fm = valid ? a.fm[n] : 0.0, fv = valid ? a.fv[n] : 0.0, y = valid ? a.y[n] : 0.0;
-  double logp, ymean, yvar;
-  if (LIK == ZIGP_LIK_ONOFF) {
-    for (int i = threadIdx.x; i < a.n_quad; i += DN_THREADS) { sx[i] = a.rule[i]; slw[i] = a.rule[a.n_quad + i]; }
-    __syncthreads();
-    const double gm = valid ? a.gm[n] : 0.0, gv = valid ? a.gv[n] : 0.0;
-    const double sg = sqrt(fmax(gv, 0.0)), fvp = fmax(fv, 0.0);
-    // online log-sum-exp: m = the largest term so far, acc = sum exp(term - m); the first node starts it, so that no -inf meets -inf
-    double m = 0.0, acc = 1.0;
-    for (int i = 0; i < a.n_quad; ++i) {
-      const double ph = dn_link(gm + sg * sx[i]);
-      const double s = a.noise + ph * ph * fvp, r = y - ph * fm;
-      const double l = slw[i] - 0.5 * (DN_LOG_2PI + log(s)) - 0.5 * (r * r) / s;
-      if (i == 0) { m = l; continue; }
-      const double d = l - m, e = exp(-fabs(d));
-      if (d > 0.0) { acc = fma(acc, e, 1.0); m = l; } else acc += e;
-    }
-    logp = m + log(acc);
-    if (a.m0) {   // a predict block: ymean = gfmean, yvar = (gfvar + gfmeanu) + noise, two additions in that order
-      ymean = valid ? a.m0[n] : 0.0;
-      yvar = __dadd_rn(__dadd_rn(valid ? a.m1[n] : 0.0, valid ? a.m2[n] : 0.0), a.noise);
-    } else {
-      const PwOut o = pointwise_eval(fm, fv, gm, gv, y, a.noise);
-      // the two products as the ROUNDED numbers zigp_predict stores (the empty statement pins them in registers): left to the compiler,
-      // one of them is fused into the addition and yvar is an ulp away from the sum of the stored rows
-      double gfvar = o.gfvar, gfmeanu = o.gfmeanu;
-      asm volatile("" : "+v"(gfvar), "+v"(gfmeanu));
-      ymean = o.gfmean;
-      yvar = __dadd_rn(__dadd_rn(gfvar, gfmeanu), a.noise);
-    }
-  } else if (LIK == ZIGP_LIK_GAUSSIAN) {
-    const double s = __dadd_rn(fv, a.noise), r = y - fm;
-    logp = -0.5 * (DN_LOG_2PI + log(s)) - 0.5 * (r * r) / s;
-    ymean = fm; yvar = s;
-  } else {
-    const double p = dn_link(fm * (1.0 / sqrt(1.0 + fv)));   // classifier.py:216-217, k_kron_head_pointwise
-    logp = (y == 1.0) ? log(p) : log1p(-p);
-    ymean = p; yvar = __dmul_rn(p, 1.0 - p);
-  }
-  if (valid && a.out3) { double* q = a.out3 + n; q[0] = logp; q[a.ld3] = ymean; q[2 * a.ld3] = yvar; }
-  const double sum = block_sum<DN_THREADS / 64>(valid ? logp : 0.0, sh);
-  if (threadIdx.x == 0) a.part[blockIdx.x] = sum;
 }
 
 // ---- the rule centred on each row's mode ------------------------------------------------------------------------------------------
@@ -109,13 +67,7 @@ constexpr double DC_FREE_STEP = 1.e-4; // in units of 1 / sqrt(-F''): a Newton s
 constexpr double DC_STOP_STEP = 1.e-9; // ... and one this small ends the search
 constexpr double DC_INV_SQRT_2PI = 0.39894228040143267794;
 
-struct DensityCentredArgs {
-  DensityArgs a;      // rule: x_i [n_quad], log w_i [n_quad], x_i^2 / 2 [n_quad]
-  double* centre2;    // (2, ldc): zhat, tau (nullable)
-  int64_t ldc;
-};
-
-struct DcRow { double fm, fvp, gm, sg, y, noise; };
+struct DcRow { double fm, fvp, gm, sg, y, noise; };   // an OnOff row as both sums read it: fvp = max(fv, 0), sg = sqrt(max(gv, 0))
 struct DcVal { double F, F1, F2; };
 
 // F, F' and F'' at z:  F' = -z + sg l'(u) phi(g),  F'' = -1 + sg^2 [ l''(u) phi(g)^2 - g l'(u) phi(g) ],  phi(g) = (1 - 2e-3) N(g; 0, 1)
@@ -166,52 +118,93 @@ __device__ __forceinline__ void dc_search(const DcRow& w, double& zhat, double& 
   tau = h > 0.0 ? fmin(1.0 / sqrt(h), DC_TAU_MAX) : 1.0;
 }
 
-__global__ void __launch_bounds__(DN_THREADS)
-k_density_rows_centred(DensityCentredArgs c) {
-  const DensityArgs& a = c.a;
-  __shared__ double sx[DN_MAXQ], slw[DN_MAXQ], shx[DN_MAXQ];
-  __shared__ double sh[DN_THREADS / 64];
-  const int64_t n = (int64_t)blockIdx.x * DN_THREADS + threadIdx.x;
-  const bool valid = n < a.N;
-  const double fm = valid ? a.fm[n] : 0.0, fv = valid ? a.fv[n] : 0.0, y = valid ? a.y[n] : 0.0;
-  for (int i = threadIdx.x; i < a.n_quad; i += DN_THREADS) { sx[i] = a.rule[i]; slw[i] = a.rule[a.n_quad + i]; shx[i] = a.rule[2 * a.n_quad + i]; }
+// ---- the pieces of k_density_rows -------------------------------------------------------------------------------------------------
+// The rule's table (COLS columns of n_quad entries) into LDS, once per block
+template <int COLS>
+__device__ __forceinline__ void dn_stage_rule(const DensityArgs& a, double (&tab)[COLS][DN_MAXQ]) {
+  for (int i = threadIdx.x; i < a.n_quad; i += DN_THREADS)
+    for (int k = 0; k < COLS; ++k) tab[k][i] = a.rule[k * a.n_quad + i];
   __syncthreads();
-  const double gm = valid ? a.gm[n] : 0.0, gv = valid ? a.gv[n] : 0.0;
-  const double sg = sqrt(fmax(gv, 0.0)), fvp = fmax(fv, 0.0);
-  double zhat, tau;
-  {
-    DcRow w;
-    w.fm = fm; w.fvp = fvp; w.gm = gm; w.sg = sg; w.y = y; w.noise = a.noise;
-    dc_search(w, zhat, tau);
-  }
-  const double lt = log(tau);
-  // the online log-sum-exp of k_density_rows over the shifted and scaled nodes
+}
+
+// The OnOff sum of one row over the staged rule (tab[0] = x_i, tab[1] = log w_i, centred: tab[2] = x_i^2 / 2, the nodes at zhat + tau x_i
+// and lt = log tau).  Online log-sum-exp: m = the largest term so far, acc = sum exp(term - m); the first node starts it, so that no -inf
+// meets -inf.
+template <bool CENTRED, int COLS>
+__device__ __forceinline__ double dn_logsumexp(const DcRow& w, const double (&tab)[COLS][DN_MAXQ], int n_quad, double zhat, double tau, double lt) {
+  static_assert(COLS == (CENTRED ? 3 : 2), "the centred table has a third column");
   double m = 0.0, acc = 1.0;
-  for (int i = 0; i < a.n_quad; ++i) {
-    const double z = zhat + tau * sx[i];
-    const double ph = dn_link(gm + sg * z);
-    const double s = a.noise + ph * ph * fvp, r = y - ph * fm;
-    const double l = ((slw[i] + shx[i]) + lt) - 0.5 * z * z + (-0.5 * (DN_LOG_2PI + log(s)) - 0.5 * (r * r) / s);
+  for (int i = 0; i < n_quad; ++i) {
+    double z = tab[0][i];
+    if constexpr (CENTRED) z = zhat + tau * tab[0][i];
+    const double ph = dn_link(w.gm + w.sg * z);
+    const double s = w.noise + ph * ph * w.fvp, r = w.y - ph * w.fm;
+    double l;   // the two sums keep their own association: they differ in bits where they agree in exact arithmetic
+    if constexpr (CENTRED) l = ((tab[1][i] + tab[2][i]) + lt) - 0.5 * z * z + (-0.5 * (DN_LOG_2PI + log(s)) - 0.5 * (r * r) / s);
+    else l = tab[1][i] - 0.5 * (DN_LOG_2PI + log(s)) - 0.5 * (r * r) / s;
     if (i == 0) { m = l; continue; }
     const double d = l - m, e = exp(-fabs(d));
     if (d > 0.0) { acc = fma(acc, e, 1.0); m = l; } else acc += e;
   }
-  const double logp = m + log(acc);
-  double ymean, yvar;
-  if (a.m0) {   // as k_density_rows: the moments are not the rule's business
+  return m + log(acc);
+}
+
+// ymean and yvar of an OnOff row: not the rule's business, so the same bits under either centre
+__device__ __forceinline__ void dn_moments(const DensityArgs& a, int64_t n, bool valid, double fm, double fv, double gm, double gv, double y,
+                                           double& ymean, double& yvar) {
+  if (a.m0) {   // a predict block: ymean = gfmean, yvar = (gfvar + gfmeanu) + noise, two additions in that order
     ymean = valid ? a.m0[n] : 0.0;
     yvar = __dadd_rn(__dadd_rn(valid ? a.m1[n] : 0.0, valid ? a.m2[n] : 0.0), a.noise);
   } else {
     const PwOut o = pointwise_eval(fm, fv, gm, gv, y, a.noise);
+    // the two products as the ROUNDED numbers zigp_predict stores (the empty statement pins them in registers): left to the compiler,
+    // one of them is fused into the addition and yvar is an ulp away from the sum of the stored rows
     double gfvar = o.gfvar, gfmeanu = o.gfmeanu;
     asm volatile("" : "+v"(gfvar), "+v"(gfmeanu));
     ymean = o.gfmean;
     yvar = __dadd_rn(__dadd_rn(gfvar, gfmeanu), a.noise);
   }
+}
+
+// The row's three results to out3, and the block's sum of logp to part (rows n >= N add zero and are written nowhere)
+__device__ __forceinline__ void dn_store(const DensityArgs& a, int64_t n, bool valid, double logp, double ymean, double yvar, double* sh) {
   if (valid && a.out3) { double* q = a.out3 + n; q[0] = logp; q[a.ld3] = ymean; q[2 * a.ld3] = yvar; }
-  if (valid && c.centre2) { double* q = c.centre2 + n; q[0] = zhat; q[c.ldc] = tau; }
   const double sum = block_sum<DN_THREADS / 64>(valid ? logp : 0.0, sh);
   if (threadIdx.x == 0) a.part[blockIdx.x] = sum;
+}
+
+template <int LIK, bool CENTRED>
+__global__ void __launch_bounds__(DN_THREADS)
+k_density_rows(DensityArgs a) {
+  static_assert(LIK == ZIGP_LIK_ONOFF || LIK == ZIGP_LIK_GAUSSIAN || LIK == ZIGP_LIK_BERNOULLI, "a ZIGP_LIK_* value");
+  static_assert(!CENTRED || LIK == ZIGP_LIK_ONOFF, "the heads are closed form: there is no rule to centre");
+  __shared__ double sh[DN_THREADS / 64];
+  const int64_t n = (int64_t)blockIdx.x * DN_THREADS + threadIdx.x;
+  const bool valid = n < a.N;
+  const double fm = valid ? a.fm[n] : 0.0, fv = valid ? a.fv[n] : 0.0, y = valid ? a.y[n] : 0.0;
+  double logp, ymean, yvar;
+  if constexpr (LIK == ZIGP_LIK_ONOFF) {
+    __shared__ double tab[CENTRED ? 3 : 2][DN_MAXQ];
+    dn_stage_rule(a, tab);
+    const double gm = valid ? a.gm[n] : 0.0, gv = valid ? a.gv[n] : 0.0;
+    DcRow w;
+    w.fm = fm; w.fvp = fmax(fv, 0.0); w.gm = gm; w.sg = sqrt(fmax(gv, 0.0)); w.y = y; w.noise = a.noise;
+    double zhat = 0.0, tau = 1.0, lt = 0.0;
+    if constexpr (CENTRED) { dc_search(w, zhat, tau); lt = log(tau); }
+    logp = dn_logsumexp<CENTRED>(w, tab, a.n_quad, zhat, tau, lt);
+    dn_moments(a, n, valid, fm, fv, gm, gv, y, ymean, yvar);
+    if constexpr (CENTRED)
+      if (valid && a.centre2) { double* q = a.centre2 + n; q[0] = zhat; q[a.ldc] = tau; }
+  } else if constexpr (LIK == ZIGP_LIK_GAUSSIAN) {
+    const double s = __dadd_rn(fv, a.noise), r = y - fm;
+    logp = -0.5 * (DN_LOG_2PI + log(s)) - 0.5 * (r * r) / s;
+    ymean = fm; yvar = s;
+  } else {
+    const double p = dn_link(fm * (1.0 / sqrt(1.0 + fv)));   // classifier.py:216-217, k_kron_head_pointwise
+    logp = (y == 1.0) ? log(p) : log1p(-p);
+    ymean = p; yvar = __dmul_rn(p, 1.0 - p);
+  }
+  dn_store(a, n, valid, logp, ymean, yvar, sh);
 }
 
 // One block: thread t adds the partials t, t + DN_THREADS, ... in that order, then the threads' sums are added in thread order --
@@ -229,15 +222,18 @@ k_density_sum(const double* __restrict__ part, int nb, double* __restrict__ out)
 
 namespace {
 
-// Layout of scratch2 during a density call: the rule's table, the sum, the block partials, the three output rows
-constexpr size_t DN_OFF_SUM = 2 * DN_MAXQ, DN_OFF_PART = 2 * DN_MAXQ + 8;
-struct DensityBufs { double* rule; double* sum; double* part; double* out3; int nb; };
+// Layout of scratch2 during a density call, in doubles, the same for either centre: the rule's table in [0, 3 DN_MAXQ) (two or three
+// columns of n_quad entries from its start), the sum at DN_OFF_SUM, the nb block partials from DN_OFF_PART, then, from the next
+// multiple of 8, the (3, N) output rows and -- a centred call -- the (2, N) centre behind them
+constexpr size_t DN_OFF_SUM = 3 * DN_MAXQ, DN_OFF_PART = DN_OFF_SUM + 8;
+struct DensityBufs { double* rule; double* sum; double* part; double* out3; double* centre2; int nb; };
 
-int density_bufs(zigp_ctx* c, int64_t N, DensityBufs& b) {
+int density_bufs(zigp_ctx* c, int64_t N, bool centred, DensityBufs& b) {
   b.nb = ceil_div(N, DN_THREADS);
   const size_t off_out = (DN_OFF_PART + (size_t)b.nb + 7) & ~(size_t)7;
-  ZIGP_ENSURE(c, c->scratch2, off_out + (size_t)3 * N);
+  ZIGP_ENSURE(c, c->scratch2, off_out + (size_t)(centred ? 5 : 3) * N);
   b.rule = c->scratch2.p; b.sum = c->scratch2.p + DN_OFF_SUM; b.part = c->scratch2.p + DN_OFF_PART; b.out3 = c->scratch2.p + off_out;
+  b.centre2 = centred ? b.out3 + (size_t)3 * N : nullptr;
   return 0;
 }
 
@@ -257,95 +253,102 @@ int density_check(zigp_ctx* c, const char* who, int lik, int64_t N, double noise
   return 0;
 }
 
-// The rule (nodes, then the logarithms of the weights, taken here) to the device, the rows kernel, the sum kernel; the caller
-// has synchronised whatever wrote the rows, and collects *sum with its own synchronisation
-int density_run(zigp_ctx* c, int lik, DensityArgs a, const DensityBufs& b, const double* nodes, const double* weights, double** hsum) {
+// The rule's table to the device (OnOff: nodes, the logarithms of the weights and -- centred -- x^2 / 2, all taken here), the rows
+// kernel, the sum kernel; the caller has synchronised whatever wrote the rows, and collects *hsum with its own synchronisation
+int density_run(zigp_ctx* c, int lik, bool centred, DensityArgs a, const DensityBufs& b, const double* nodes, const double* weights, double** hsum) {
   if (lik == ZIGP_LIK_ONOFF) {
-    ZIGP_PINNED(c, h, 2 * (size_t)a.n_quad);
-    for (int i = 0; i < a.n_quad; ++i) { h[i] = nodes[i]; h[a.n_quad + i] = log(weights[i]); }
-    ZIGP_HIP(c, hipMemcpyAsync(b.rule, h, sizeof(double) * 2 * a.n_quad, hipMemcpyHostToDevice, c->stream));
+    const int nq = a.n_quad, cols = centred ? 3 : 2;
+    ZIGP_PINNED(c, h, cols * (size_t)nq);
+    for (int i = 0; i < nq; ++i) {
+      h[i] = nodes[i]; h[nq + i] = log(weights[i]);
+      if (centred) h[2 * nq + i] = 0.5 * nodes[i] * nodes[i];
+    }
+    ZIGP_HIP(c, hipMemcpyAsync(b.rule, h, sizeof(double) * cols * nq, hipMemcpyHostToDevice, c->stream));
   }
   a.rule = b.rule; a.part = b.part;
   const dim3 grid(b.nb), block(DN_THREADS);
-  if (lik == ZIGP_LIK_ONOFF) hipLaunchKernelGGL(k_density_rows<ZIGP_LIK_ONOFF>, grid, block, 0, c->stream, a);
-  else if (lik == ZIGP_LIK_GAUSSIAN) hipLaunchKernelGGL(k_density_rows<ZIGP_LIK_GAUSSIAN>, grid, block, 0, c->stream, a);
-  else hipLaunchKernelGGL(k_density_rows<ZIGP_LIK_BERNOULLI>, grid, block, 0, c->stream, a);
+  if (lik == ZIGP_LIK_ONOFF && centred) hipLaunchKernelGGL((k_density_rows<ZIGP_LIK_ONOFF, true>), grid, block, 0, c->stream, a);
+  else if (lik == ZIGP_LIK_ONOFF) hipLaunchKernelGGL((k_density_rows<ZIGP_LIK_ONOFF, false>), grid, block, 0, c->stream, a);
+  else if (lik == ZIGP_LIK_GAUSSIAN) hipLaunchKernelGGL((k_density_rows<ZIGP_LIK_GAUSSIAN, false>), grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL((k_density_rows<ZIGP_LIK_BERNOULLI, false>), grid, block, 0, c->stream, a);
   ZIGP_HIP(c, hipGetLastError());
   hipLaunchKernelGGL(k_density_sum, dim3(1), block, 0, c->stream, b.part, b.nb, b.sum);
   ZIGP_HIP(c, hipGetLastError());
   return download(c, b.sum, 1, hsum);
 }
 
-// zigp_predict_density / zigp_predict_density_device behind their argument checks: dX (N, D) and dY (N) are device memory
-int predict_density(zigp_ctx* c, const zigp_params* p, const double* dX, const double* dY, int64_t N, double jitter, double g_offset,
-                    const double* nodes, const double* weights, int n_quad, double* out3, bool out3_device, double* sum) {
+// The end of every density call: the rows and the centre that were asked for on the host, the stream's synchronisation, the sum
+int density_finish(zigp_ctx* c, const DensityBufs& b, int64_t N, double* out3, double* centre2, const double* hsum, double* sum) {
+  if (out3) ZIGP_HIP(c, hipMemcpyAsync(out3, b.out3, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, c->stream));
+  if (centre2) ZIGP_HIP(c, hipMemcpyAsync(centre2, b.centre2, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  *sum = hsum[0];
+  return ZIGP_OK;
+}
+
+// zigp_density_rows and zigp_density_rows_centred (who: the entry's name for the messages; centred implies lik = ZIGP_LIK_ONOFF)
+int density_rows(zigp_ctx* c, const char* who, int lik, bool centred, const double* fm, const double* fv, const double* gm, const double* gv,
+                 const double* y, int64_t N, double noise, const double* nodes, const double* weights, int n_quad, double* out3, double* sum,
+                 double* centre2) {
+  if (!c) return ZIGP_EARG;
+  ZIGP_TRY(density_check(c, who, lik, N, noise, nodes, weights, n_quad));
+  if (!sum) return fail_arg(c, (std::string(who) + ": sum is NULL").c_str());
+  const bool onoff = lik == ZIGP_LIK_ONOFF;
+  if (N > 0 && (!fm || !fv || !y || (onoff && (!gm || !gv)))) return fail_arg(c, (std::string(who) + ": a row pointer (fm, fv, gm, gv, y) is NULL").c_str());
+  if (N == 0) { *sum = 0.0; return ZIGP_OK; }
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  ZIGP_TRY(begin_staged_call(c));
   DensityBufs b;
-  ZIGP_TRY(density_bufs(c, N, b));
+  ZIGP_TRY(density_bufs(c, N, centred, b));
+  ZIGP_ENSURE(c, c->scratch, (size_t)5 * N);
+  double* d = c->scratch.p;
+  const double* src[5] = {fm, fv, y, gm, gv};
+  for (int k = 0; k < (onoff ? 5 : 3); ++k)
+    ZIGP_HIP(c, hipMemcpyAsync(d + k * N, src[k], sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
+  DensityArgs a{};
+  a.fm = d; a.fv = d + N; a.y = d + 2 * N; a.gm = onoff ? d + 3 * N : nullptr; a.gv = onoff ? d + 4 * N : nullptr;
+  a.N = N; a.noise = noise; a.n_quad = onoff ? n_quad : 0; a.ld3 = N; a.ldc = N;
+  a.out3 = out3 ? b.out3 : nullptr; a.centre2 = centre2 ? b.centre2 : nullptr;
+  double* hsum = nullptr;
+  ZIGP_TRY(density_run(c, lik, centred, a, b, nodes, weights, &hsum));
+  return density_finish(c, b, N, out3, centre2, hsum, sum);
+}
+
+// The four zigp_predict_density* entries (who: the entry's name for the messages).  on_device: X (N, D), Y (N), out3 and centre2 are
+// device memory, read and written in place; else they are the host's, staged through scratch and scratch2.
+int predict_density(zigp_ctx* c, const char* who, const zigp_params* p, const double* X, const double* Y, int64_t N, double jitter,
+                    double g_offset, const double* nodes, const double* weights, int n_quad, double* out3, double* centre2, bool centred,
+                    bool on_device, double* sum) {
+  if (!c) return ZIGP_EARG;
+  ZIGP_TRY(validate_params(c, p));
+  ZIGP_TRY(density_check(c, who, ZIGP_LIK_ONOFF, N, p->noise, nodes, weights, n_quad));
+  if (!sum) return fail_arg(c, (std::string(who) + ": sum is NULL").c_str());
+  if (N > 0 && (!X || !Y)) return fail_arg(c, (std::string(who) + ": Xnew or Ynew is NULL").c_str());
+  if (N == 0) { *sum = 0.0; return ZIGP_OK; }
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  if (on_device) {
+    const std::string names = centred ? ": Xnew, Ynew, out3 and centre2" : ": Xnew, Ynew and out3";
+    ZIGP_TRY(require_device_ptrs(c, {X, Y, out3, centre2}, (who + names + " must be device memory of the context's GPU").c_str()));
+  } else {
+    const size_t nx = ((size_t)N * p->D + 7) & ~(size_t)7;
+    ZIGP_ENSURE(c, c->scratch, nx + (size_t)N);
+    ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p, X, sizeof(double) * N * p->D, hipMemcpyHostToDevice, c->stream));
+    ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p + nx, Y, sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
+    X = c->scratch.p; Y = c->scratch.p + nx;
+  }
+  DensityBufs b;
+  ZIGP_TRY(density_bufs(c, N, centred, b));
   ZIGP_ENSURE(c, c->out9, (size_t)9 * N);
-  ZIGP_TRY(run_dense(c, p, dX, nullptr, N, p->D, jitter, 1.0, g_offset, 0, N, 0, true, c->out9.p, nullptr, nullptr, nullptr));   // complete on return
+  ZIGP_TRY(run_dense(c, p, X, nullptr, N, p->D, jitter, 1.0, g_offset, 0, N, 0, true, c->out9.p, nullptr, nullptr, nullptr));   // complete on return
   const double* r = c->out9.p;
   DensityArgs a{};
-  a.m0 = r; a.m1 = r + N; a.m2 = r + 2 * N; a.fm = r + 3 * N; a.fv = r + 4 * N; a.gm = r + 5 * N; a.gv = r + 6 * N; a.y = dY;
-  a.N = N; a.noise = p->noise; a.n_quad = n_quad; a.ld3 = N;
-  a.out3 = !out3 ? nullptr : out3_device ? out3 : b.out3;
+  a.m0 = r; a.m1 = r + N; a.m2 = r + 2 * N; a.fm = r + 3 * N; a.fv = r + 4 * N; a.gm = r + 5 * N; a.gv = r + 6 * N; a.y = Y;
+  a.N = N; a.noise = p->noise; a.n_quad = n_quad; a.ld3 = N; a.ldc = N;
+  a.out3 = !out3 ? nullptr : on_device ? out3 : b.out3;
+  a.centre2 = !centre2 ? nullptr : on_device ? centre2 : b.centre2;
   double* hsum = nullptr;
-  ZIGP_TRY(density_run(c, ZIGP_LIK_ONOFF, a, b, nodes, weights, &hsum));
-  if (out3 && !out3_device) ZIGP_HIP(c, hipMemcpyAsync(out3, b.out3, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, c->stream));
-  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
-  *sum = hsum[0];
-  return ZIGP_OK;
-}
-
-// ---- centred: its own layout of scratch2 (the rule's table has three columns, and the (2, N) centre follows the three output rows) ----
-constexpr size_t DC_OFF_SUM = 3 * DN_MAXQ, DC_OFF_PART = 3 * DN_MAXQ + 8;
-struct DensityCentredBufs { DensityBufs b; double* centre2; };
-
-int density_centred_bufs(zigp_ctx* c, int64_t N, DensityCentredBufs& cb) {
-  DensityBufs& b = cb.b;
-  b.nb = ceil_div(N, DN_THREADS);
-  const size_t off_out = (DC_OFF_PART + (size_t)b.nb + 7) & ~(size_t)7;
-  ZIGP_ENSURE(c, c->scratch2, off_out + (size_t)5 * N);
-  b.rule = c->scratch2.p; b.sum = c->scratch2.p + DC_OFF_SUM; b.part = c->scratch2.p + DC_OFF_PART; b.out3 = c->scratch2.p + off_out;
-  cb.centre2 = b.out3 + (size_t)3 * N;
-  return 0;
-}
-
-// density_run for the centred kernel: the table is nodes, log weights, x^2 / 2 (both taken here); the block partials go to k_density_sum
-int density_centred_run(zigp_ctx* c, DensityCentredArgs ca, const DensityBufs& b, const double* nodes, const double* weights, double** hsum) {
-  const int nq = ca.a.n_quad;
-  ZIGP_PINNED(c, h, 3 * (size_t)nq);
-  for (int i = 0; i < nq; ++i) { h[i] = nodes[i]; h[nq + i] = log(weights[i]); h[2 * nq + i] = 0.5 * nodes[i] * nodes[i]; }
-  ZIGP_HIP(c, hipMemcpyAsync(b.rule, h, sizeof(double) * 3 * nq, hipMemcpyHostToDevice, c->stream));
-  ca.a.rule = b.rule; ca.a.part = b.part;
-  const dim3 grid(b.nb), block(DN_THREADS);
-  hipLaunchKernelGGL(k_density_rows_centred, grid, block, 0, c->stream, ca);
-  ZIGP_HIP(c, hipGetLastError());
-  hipLaunchKernelGGL(k_density_sum, dim3(1), block, 0, c->stream, b.part, b.nb, b.sum);
-  ZIGP_HIP(c, hipGetLastError());
-  return download(c, b.sum, 1, hsum);
-}
-
-// zigp_predict_density_centred / zigp_predict_density_centred_device behind their argument checks, as predict_density
-int predict_density_centred(zigp_ctx* c, const zigp_params* p, const double* dX, const double* dY, int64_t N, double jitter, double g_offset,
-                            const double* nodes, const double* weights, int n_quad, double* out3, double* centre2, bool on_device, double* sum) {
-  DensityCentredBufs cb;
-  ZIGP_TRY(density_centred_bufs(c, N, cb));
-  ZIGP_ENSURE(c, c->out9, (size_t)9 * N);
-  ZIGP_TRY(run_dense(c, p, dX, nullptr, N, p->D, jitter, 1.0, g_offset, 0, N, 0, true, c->out9.p, nullptr, nullptr, nullptr));   // complete on return
-  const double* r = c->out9.p;
-  DensityCentredArgs ca{};
-  DensityArgs& a = ca.a;
-  a.m0 = r; a.m1 = r + N; a.m2 = r + 2 * N; a.fm = r + 3 * N; a.fv = r + 4 * N; a.gm = r + 5 * N; a.gv = r + 6 * N; a.y = dY;
-  a.N = N; a.noise = p->noise; a.n_quad = n_quad; a.ld3 = N; ca.ldc = N;
-  a.out3 = !out3 ? nullptr : on_device ? out3 : cb.b.out3;
-  ca.centre2 = !centre2 ? nullptr : on_device ? centre2 : cb.centre2;
-  double* hsum = nullptr;
-  ZIGP_TRY(density_centred_run(c, ca, cb.b, nodes, weights, &hsum));
-  if (out3 && !on_device) ZIGP_HIP(c, hipMemcpyAsync(out3, cb.b.out3, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, c->stream));
-  if (centre2 && !on_device) ZIGP_HIP(c, hipMemcpyAsync(centre2, cb.centre2, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, c->stream));
-  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
-  *sum = hsum[0];
-  return ZIGP_OK;
+  ZIGP_TRY(density_run(c, ZIGP_LIK_ONOFF, centred, a, b, nodes, weights, &hsum));
+  return density_finish(c, b, N, on_device ? nullptr : out3, on_device ? nullptr : centre2, hsum, sum);
 }
 
 }  // namespace
@@ -354,134 +357,36 @@ extern "C" {
 
 int zigp_density_rows(zigp_ctx* c, int32_t lik, const double* fm, const double* fv, const double* gm, const double* gv, const double* y,
                       int64_t N, double noise, const double* nodes, const double* weights, int32_t n_quad, double* out3, double* sum) {
-  if (!c) return ZIGP_EARG;
-  ZIGP_TRY(density_check(c, "zigp_density_rows", lik, N, noise, nodes, weights, n_quad));
-  if (!sum) return fail_arg(c, "zigp_density_rows: sum is NULL");
-  const bool onoff = lik == ZIGP_LIK_ONOFF;
-  if (N > 0 && (!fm || !fv || !y || (onoff && (!gm || !gv)))) return fail_arg(c, "zigp_density_rows: a row pointer (fm, fv, gm, gv, y) is NULL");
-  if (N == 0) { *sum = 0.0; return ZIGP_OK; }
-  ZIGP_HIP(c, hipSetDevice(c->device));
-  ZIGP_TRY(begin_staged_call(c));
-  DensityBufs b;
-  ZIGP_TRY(density_bufs(c, N, b));
-  ZIGP_ENSURE(c, c->scratch, (size_t)5 * N);
-  double* d = c->scratch.p;
-  const double* src[5] = {fm, fv, y, gm, gv};
-  for (int k = 0; k < (onoff ? 5 : 3); ++k)
-    ZIGP_HIP(c, hipMemcpyAsync(d + k * N, src[k], sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
-  DensityArgs a{};
-  a.fm = d; a.fv = d + N; a.y = d + 2 * N; a.gm = onoff ? d + 3 * N : nullptr; a.gv = onoff ? d + 4 * N : nullptr;
-  a.N = N; a.noise = noise; a.n_quad = onoff ? n_quad : 0; a.out3 = out3 ? b.out3 : nullptr; a.ld3 = N;
-  double* hsum = nullptr;
-  ZIGP_TRY(density_run(c, lik, a, b, nodes, weights, &hsum));
-  if (out3) ZIGP_HIP(c, hipMemcpyAsync(out3, b.out3, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, c->stream));
-  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
-  *sum = hsum[0];
-  return ZIGP_OK;
+  return density_rows(c, "zigp_density_rows", lik, false, fm, fv, gm, gv, y, N, noise, nodes, weights, n_quad, out3, sum, nullptr);
 }
 
 int zigp_predict_density(zigp_ctx* c, const zigp_params* p, const double* Xnew, const double* Ynew, int64_t N, double jitter, double g_offset,
                          const double* nodes, const double* weights, int32_t n_quad, double* out3, double* sum) {
-  if (!c) return ZIGP_EARG;
-  ZIGP_TRY(validate_params(c, p));
-  ZIGP_TRY(density_check(c, "zigp_predict_density", ZIGP_LIK_ONOFF, N, p->noise, nodes, weights, n_quad));
-  if (!sum) return fail_arg(c, "zigp_predict_density: sum is NULL");
-  if (N > 0 && (!Xnew || !Ynew)) return fail_arg(c, "zigp_predict_density: Xnew or Ynew is NULL");
-  if (N == 0) { *sum = 0.0; return ZIGP_OK; }
-  ZIGP_HIP(c, hipSetDevice(c->device));
-  const size_t nx = ((size_t)N * p->D + 7) & ~(size_t)7;
-  ZIGP_ENSURE(c, c->scratch, nx + (size_t)N);
-  ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p, Xnew, sizeof(double) * N * p->D, hipMemcpyHostToDevice, c->stream));
-  ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p + nx, Ynew, sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
-  return predict_density(c, p, c->scratch.p, c->scratch.p + nx, N, jitter, g_offset, nodes, weights, n_quad, out3, false, sum);
+  return predict_density(c, "zigp_predict_density", p, Xnew, Ynew, N, jitter, g_offset, nodes, weights, n_quad, out3, nullptr, false, false, sum);
 }
 
 int zigp_predict_density_device(zigp_ctx* c, const zigp_params* p, const double* dXnew, const double* dYnew, int64_t N, double jitter,
                                 double g_offset, const double* nodes, const double* weights, int32_t n_quad, double* d_out3, double* sum) {
-  if (!c) return ZIGP_EARG;
-  ZIGP_TRY(validate_params(c, p));
-  ZIGP_TRY(density_check(c, "zigp_predict_density_device", ZIGP_LIK_ONOFF, N, p->noise, nodes, weights, n_quad));
-  if (!sum) return fail_arg(c, "zigp_predict_density_device: sum is NULL");
-  if (N > 0 && (!dXnew || !dYnew)) return fail_arg(c, "zigp_predict_density_device: Xnew or Ynew is NULL");
-  if (N == 0) { *sum = 0.0; return ZIGP_OK; }
-  ZIGP_HIP(c, hipSetDevice(c->device));
-  for (const double* q : {dXnew, dYnew, (const double*)d_out3}) {   // device memory of this context's GPU (a host pointer would fault inside a kernel)
-    hipPointerAttribute_t at;
-    if (!q) continue;
-    if (hipPointerGetAttributes(&at, q) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->device) {
-      (void)hipGetLastError();
-      return fail_arg(c, "zigp_predict_density_device: Xnew, Ynew and out3 must be device memory of the context's GPU");
-    }
-  }
-  return predict_density(c, p, dXnew, dYnew, N, jitter, g_offset, nodes, weights, n_quad, d_out3, true, sum);
+  return predict_density(c, "zigp_predict_density_device", p, dXnew, dYnew, N, jitter, g_offset, nodes, weights, n_quad, d_out3, nullptr, false, true, sum);
 }
 
 int zigp_density_rows_centred(zigp_ctx* c, const double* fm, const double* fv, const double* gm, const double* gv, const double* y, int64_t N,
                               double noise, const double* nodes, const double* weights, int32_t n_quad, double* out3, double* sum,
                               double* centre2) {
-  if (!c) return ZIGP_EARG;
-  ZIGP_TRY(density_check(c, "zigp_density_rows_centred", ZIGP_LIK_ONOFF, N, noise, nodes, weights, n_quad));
-  if (!sum) return fail_arg(c, "zigp_density_rows_centred: sum is NULL");
-  if (N > 0 && (!fm || !fv || !y || !gm || !gv)) return fail_arg(c, "zigp_density_rows_centred: a row pointer (fm, fv, gm, gv, y) is NULL");
-  if (N == 0) { *sum = 0.0; return ZIGP_OK; }
-  ZIGP_HIP(c, hipSetDevice(c->device));
-  ZIGP_TRY(begin_staged_call(c));
-  DensityCentredBufs cb;
-  ZIGP_TRY(density_centred_bufs(c, N, cb));
-  ZIGP_ENSURE(c, c->scratch, (size_t)5 * N);
-  double* d = c->scratch.p;
-  const double* src[5] = {fm, fv, y, gm, gv};
-  for (int k = 0; k < 5; ++k) ZIGP_HIP(c, hipMemcpyAsync(d + k * N, src[k], sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
-  DensityCentredArgs ca{};
-  DensityArgs& a = ca.a;
-  a.fm = d; a.fv = d + N; a.y = d + 2 * N; a.gm = d + 3 * N; a.gv = d + 4 * N;
-  a.N = N; a.noise = noise; a.n_quad = n_quad; a.out3 = out3 ? cb.b.out3 : nullptr; a.ld3 = N;
-  ca.centre2 = centre2 ? cb.centre2 : nullptr; ca.ldc = N;
-  double* hsum = nullptr;
-  ZIGP_TRY(density_centred_run(c, ca, cb.b, nodes, weights, &hsum));
-  if (out3) ZIGP_HIP(c, hipMemcpyAsync(out3, cb.b.out3, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, c->stream));
-  if (centre2) ZIGP_HIP(c, hipMemcpyAsync(centre2, cb.centre2, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, c->stream));
-  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
-  *sum = hsum[0];
-  return ZIGP_OK;
+  return density_rows(c, "zigp_density_rows_centred", ZIGP_LIK_ONOFF, true, fm, fv, gm, gv, y, N, noise, nodes, weights, n_quad, out3, sum, centre2);
 }
 
 int zigp_predict_density_centred(zigp_ctx* c, const zigp_params* p, const double* Xnew, const double* Ynew, int64_t N, double jitter,
                                  double g_offset, const double* nodes, const double* weights, int32_t n_quad, double* out3, double* sum,
                                  double* centre2) {
-  if (!c) return ZIGP_EARG;
-  ZIGP_TRY(validate_params(c, p));
-  ZIGP_TRY(density_check(c, "zigp_predict_density_centred", ZIGP_LIK_ONOFF, N, p->noise, nodes, weights, n_quad));
-  if (!sum) return fail_arg(c, "zigp_predict_density_centred: sum is NULL");
-  if (N > 0 && (!Xnew || !Ynew)) return fail_arg(c, "zigp_predict_density_centred: Xnew or Ynew is NULL");
-  if (N == 0) { *sum = 0.0; return ZIGP_OK; }
-  ZIGP_HIP(c, hipSetDevice(c->device));
-  const size_t nx = ((size_t)N * p->D + 7) & ~(size_t)7;
-  ZIGP_ENSURE(c, c->scratch, nx + (size_t)N);
-  ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p, Xnew, sizeof(double) * N * p->D, hipMemcpyHostToDevice, c->stream));
-  ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p + nx, Ynew, sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
-  return predict_density_centred(c, p, c->scratch.p, c->scratch.p + nx, N, jitter, g_offset, nodes, weights, n_quad, out3, centre2, false, sum);
+  return predict_density(c, "zigp_predict_density_centred", p, Xnew, Ynew, N, jitter, g_offset, nodes, weights, n_quad, out3, centre2, true, false, sum);
 }
 
 int zigp_predict_density_centred_device(zigp_ctx* c, const zigp_params* p, const double* dXnew, const double* dYnew, int64_t N, double jitter,
                                         double g_offset, const double* nodes, const double* weights, int32_t n_quad, double* d_out3,
                                         double* sum, double* d_centre2) {
-  if (!c) return ZIGP_EARG;
-  ZIGP_TRY(validate_params(c, p));
-  ZIGP_TRY(density_check(c, "zigp_predict_density_centred_device", ZIGP_LIK_ONOFF, N, p->noise, nodes, weights, n_quad));
-  if (!sum) return fail_arg(c, "zigp_predict_density_centred_device: sum is NULL");
-  if (N > 0 && (!dXnew || !dYnew)) return fail_arg(c, "zigp_predict_density_centred_device: Xnew or Ynew is NULL");
-  if (N == 0) { *sum = 0.0; return ZIGP_OK; }
-  ZIGP_HIP(c, hipSetDevice(c->device));
-  for (const double* q : {dXnew, dYnew, (const double*)d_out3, (const double*)d_centre2}) {   // as zigp_predict_density_device
-    hipPointerAttribute_t at;
-    if (!q) continue;
-    if (hipPointerGetAttributes(&at, q) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->device) {
-      (void)hipGetLastError();
-      return fail_arg(c, "zigp_predict_density_centred_device: Xnew, Ynew, out3 and centre2 must be device memory of the context's GPU");
-    }
-  }
-  return predict_density_centred(c, p, dXnew, dYnew, N, jitter, g_offset, nodes, weights, n_quad, d_out3, d_centre2, true, sum);
+  return predict_density(c, "zigp_predict_density_centred_device", p, dXnew, dYnew, N, jitter, g_offset, nodes, weights, n_quad, d_out3, d_centre2,
+                         true, true, sum);
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <functional>
+#include <initializer_list>
 
 namespace zigp {
 
@@ -667,5 +668,18 @@ static int download(zigp_ctx* c, const double* dev, size_t n, double** out) {
   return 0;
 }
 
+// What a *_device entry point is handed must be device memory of this context's GPU (a host pointer would fault inside a kernel): refuses
+// with `message` at the first pointer that is not, and clears the error the query left behind; NULL entries (optional outputs) are skipped
+static int require_device_ptrs(zigp_ctx* c, std::initializer_list<const void*> ptrs, const char* message) {
+  for (const void* q : ptrs) {
+    hipPointerAttribute_t at;
+    if (!q) continue;
+    if (hipPointerGetAttributes(&at, q) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->device) {
+      (void)hipGetLastError();
+      return fail_arg(c, message);
+    }
+  }
+  return 0;
+}
 
 }  // namespace zigp

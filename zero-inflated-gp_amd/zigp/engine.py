@@ -496,6 +496,11 @@ class DenseEngine:
         return x, w
 
     @staticmethod
+    def _opt(a):
+        """ptr(a), or None (a NULL pointer) for an array the call does not take"""
+        return None if a is None else ptr(a)
+
+    @staticmethod
     def _centre(centre, lik=None):
         """True for centre='mode', False for 'mean' (the rule centred on gm); the heads are closed form and have no rule to centre"""
         if centre not in ('mean', 'mode'):
@@ -526,15 +531,12 @@ class DenseEngine:
             raise ValueError('density_rows: out must be a C-contiguous float64 array of at least 3 N entries')
         total = np.zeros(1)
         centre2 = np.vstack([np.zeros(N), np.ones(N)]) if return_centre else None
-        if mode:
-            if any(a is None for a in rows):
-                raise ValueError("density_rows: centre='mode' needs fm, fv, gm, gv and y")
-            _check(self.lib, self.ctx, self.lib.zigp_density_rows_centred(self.ctx, *[ptr(a) for a in rows], N, float(noise), ptr(x), ptr(w), x.size,
-                                                                          ptr(out), ptr(total), None if centre2 is None else ptr(centre2)))
-        else:
-            _check(self.lib, self.ctx, self.lib.zigp_density_rows(self.ctx, lik, *[None if a is None else ptr(a) for a in rows], N, float(noise),
-                                                                  None if x is None else ptr(x), None if w is None else ptr(w),
-                                                                  0 if x is None else x.size, ptr(out), ptr(total)))
+        if mode and any(a is None for a in rows):
+            raise ValueError("density_rows: centre='mode' needs fm, fv, gm, gv and y")
+        # one call: the centred entry has no lik in front and takes the centre (or NULL) behind
+        fn, head, tail = (self.lib.zigp_density_rows_centred, (), (self._opt(centre2),)) if mode else (self.lib.zigp_density_rows, (lik,), ())
+        _check(self.lib, self.ctx, fn(self.ctx, *head, *[self._opt(a) for a in rows], N, float(noise), self._opt(x), self._opt(w), 0 if x is None else x.size,
+                                      ptr(out), ptr(total), *tail))
         res = out.reshape(-1)[:3 * N].reshape(3, N), float(total[0])
         return res + (centre2,) if return_centre else res
 
@@ -554,15 +556,9 @@ class DenseEngine:
         out = np.zeros((3, N)) if rows_out else None
         total = np.zeros(1)
         centre2 = np.vstack([np.zeros(N), np.ones(N)]) if return_centre else None
-        if mode:
-            _check(self.lib, self.ctx, self.lib.zigp_predict_density_centred(self.ctx, C.byref(pk.struct), ptr(Xnew), ptr(Ynew), N, float(jitter),
-                                                                             float(g_offset), ptr(x), ptr(w), x.size,
-                                                                             None if out is None else ptr(out), ptr(total),
-                                                                             None if centre2 is None else ptr(centre2)))
-        else:
-            _check(self.lib, self.ctx, self.lib.zigp_predict_density(self.ctx, C.byref(pk.struct), ptr(Xnew), ptr(Ynew), N, float(jitter),
-                                                                     float(g_offset), ptr(x), ptr(w), x.size,
-                                                                     None if out is None else ptr(out), ptr(total)))
+        fn, tail = (self.lib.zigp_predict_density_centred, (self._opt(centre2),)) if mode else (self.lib.zigp_predict_density, ())
+        _check(self.lib, self.ctx, fn(self.ctx, C.byref(pk.struct), ptr(Xnew), ptr(Ynew), N, float(jitter), float(g_offset), ptr(x), ptr(w), x.size,
+                                      self._opt(out), ptr(total), *tail))
         res = out, float(total[0])
         return res + (centre2,) if return_centre else res
 
@@ -593,14 +589,11 @@ class DenseEngine:
         if return_centre:
             centre2 = torch.cat([torch.zeros((1, N), dtype=torch.float64, device=X_t.device), torch.ones((1, N), dtype=torch.float64, device=X_t.device)])
         torch.cuda.current_stream(self.device).synchronize()      # the engine's streams are not ordered after torch's
+        fn, tail = self.lib.zigp_predict_density_device, ()
         if mode:
-            _check(self.lib, self.ctx, self.lib.zigp_predict_density_centred_device(
-                self.ctx, C.byref(pk.struct), C.c_void_p(X_t.data_ptr()), C.c_void_p(Y_t.data_ptr()), N, float(jitter), float(g_offset),
-                ptr(x), ptr(w), x.size, C.c_void_p(out.data_ptr()), ptr(total), None if centre2 is None else C.c_void_p(centre2.data_ptr())))
-        else:
-            _check(self.lib, self.ctx, self.lib.zigp_predict_density_device(self.ctx, C.byref(pk.struct), C.c_void_p(X_t.data_ptr()),
-                                                                            C.c_void_p(Y_t.data_ptr()), N, float(jitter), float(g_offset),
-                                                                            ptr(x), ptr(w), x.size, C.c_void_p(out.data_ptr()), ptr(total)))
+            fn, tail = self.lib.zigp_predict_density_centred_device, (None if centre2 is None else C.c_void_p(centre2.data_ptr()),)
+        _check(self.lib, self.ctx, fn(self.ctx, C.byref(pk.struct), C.c_void_p(X_t.data_ptr()), C.c_void_p(Y_t.data_ptr()), N, float(jitter),
+                                      float(g_offset), ptr(x), ptr(w), x.size, C.c_void_p(out.data_ptr()), ptr(total), *tail))
         res = out, float(total[0])
         return res + (centre2,) if return_centre else res
 
