@@ -456,6 +456,45 @@ int zigp_predict_density_centred_device(zigp_ctx* ctx, const zigp_params* p, con
                                         double jitter, double g_offset, const double* nodes, const double* weights, int32_t n_quad,
                                         double* d_out3, double* sum, double* d_centre2);
 
+/* ---- predictive scores: CDF, quantiles and CRPS of y (new) ----
+ * The predictive distribution of y at a test row is the finite Gaussian mixture of the density above (the rule centred on gm):
+ *   mu_k = Phi_k fm,   s_k = noise + Phi_k^2 max(fv, 0),   z_k(t) = (t - mu_k) / sqrt(s_k),   Phi_k as in zigp_density_rows;
+ *   F(t)  = sum_k w_k Phi(z_k(t)),   SF(t) = sum_k w_k Phi(-z_k(t)),   Phi(z) = erfc(-z / sqrt 2) / 2  -- each its own sum, never
+ *           1 - the other, so that the small tail keeps its relative accuracy;
+ *   quantile at p in (0, 1): the t with F(t) = p, found by a bracketed Newton search on F = p (p <= 1/2) or SF = 1 - p (p > 1/2) that
+ *           starts from [min_k, max_k] of mu_k + sqrt(s_k) Phi^-1(p) and ends on a bracket one ulp wide or a step that changes nothing;
+ *   CRPS  = sum_i w_i A(y - mu_i, s_i) - 1/2 sum_i sum_j w_i w_j A(mu_i - mu_j, s_i + s_j),
+ *           A(m, v) = 2 sqrt(v) phi(m / sqrt v) + m (2 Phi(m / sqrt v) - 1)     (the closed form for a Gaussian mixture).
+ * These finite sums ARE the results, as the density's sum is.  ZIGP_LIK_GAUSSIAN is the one-component case mu = fm, s = fv + noise:
+ * F = Phi(z), quantile = fm + sqrt(s) Phi^-1(p), CRPS = A(y - fm, s) - sqrt(s / pi).  ZIGP_LIK_BERNOULLI has no density and is refused
+ * by name: its CRPS is the Brier score (ymean - y)^2 of zigp_density_rows.
+ * The rule is the fixed one only: a rule that moves with y (the _centred calls) does not define one distribution per row.
+ * Outputs, each nullable and computed only when asked for: cdf2 (2, N): F(y), SF(y); quant (n_levels, N): one row per level, in the
+ * caller's order (any order, duplicates allowed); crps (N); *crps_sum = sum_n CRPS_n, added in a fixed order (the same bits on every
+ * call).  y (Ynew) may be NULL, and then cdf2, crps and crps_sum must be NULL; n_levels = 0 goes with NULL levels and quant.
+ * N = 0 is ZIGP_OK with *crps_sum = 0.
+ * ZIGP_EARG, with nothing enqueued, the outputs untouched and the context usable afterwards: a NULL context (before anything else is
+ * read), the Bernoulli head, what zigp_density_rows refuses of lik, N, noise, n_quad and the rule, n_levels outside
+ * [0, ZIGP_SCORE_MAX_LEVELS], a level that is not finite and strictly inside (0, 1), NULL levels or quant with n_levels > 0 (or
+ * either given with n_levels = 0), a NULL y with cdf2, crps or crps_sum given, a NULL row pointer. */
+#define ZIGP_SCORE_MAX_LEVELS 16
+/* Rows in HOST memory, for the Kronecker path and the Gaussian head: rows 3-6 of zigp_kron_predict or 0-1 of zigp_kron_head_predict.
+ * gm, gv, nodes and weights are ignored for the Gaussian head and may be NULL there. */
+int zigp_score_rows(zigp_ctx* ctx, int32_t lik, const double* fm, const double* fv, const double* gm, const double* gv,
+                    const double* y, int64_t N, double noise, const double* nodes, const double* weights, int32_t n_quad,
+                    const double* levels, int32_t n_levels, double* cdf2, double* quant, double* crps, double* crps_sum);
+/* Dense path: zigp_predict into the context's own (9, N) block, then the score kernel over its rows 3-6; only what was asked for comes
+ * back.  Every parametrisation, kernel kind, mean function and D that zigp_predict accepts, and zigp_predict's errors (ZIGP_ENOTPD
+ * included).  Xnew (N, D), Ynew (N) and the outputs in host memory. */
+int zigp_predict_scores(zigp_ctx* ctx, const zigp_params* p, const double* Xnew, const double* Ynew, int64_t N, double jitter,
+                        double g_offset, const double* nodes, const double* weights, int32_t n_quad, const double* levels,
+                        int32_t n_levels, double* cdf2, double* quant, double* crps, double* crps_sum);
+/* The same with Xnew, Ynew, cdf2, quant and crps in DEVICE memory of the context's GPU (anything else is ZIGP_EARG); the rule, the
+ * levels and crps_sum stay host pointers; complete on return. */
+int zigp_predict_scores_device(zigp_ctx* ctx, const zigp_params* p, const double* dXnew, const double* dYnew, int64_t N, double jitter,
+                               double g_offset, const double* nodes, const double* weights, int32_t n_quad, const double* levels,
+                               int32_t n_levels, double* d_cdf2, double* d_quant, double* d_crps, double* crps_sum);
+
 /* ---- data-parallel exchange (new: the reference is single-process) ----
  * The ELBO data term is a sum over points (tf.reduce_sum(var_exp), onoffgpf/OnOffSVGP.py:122; scripts/onoff.py:307): one process per GPU
  * holds a row shard, and ONE ncclAllReduce(sum, f64) per step adds the packed [elbo_data, kl, gradient] vector of every rank, on the

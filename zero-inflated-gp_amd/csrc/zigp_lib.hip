@@ -3,4 +3,5 @@
 #include "zigp_dense.hip"
 #include "zigp_kron.hip"
 #include "zigp_density.hip"
+#include "zigp_score.hip"
 #include "zigp_comm.hip"

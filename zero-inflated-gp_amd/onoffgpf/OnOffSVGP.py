@@ -209,6 +209,28 @@ class OnOffSVGP(Parameterized):
                                               jitter=JITTER, n_quad=n_quad, **kw)
         return out[0].reshape(-1, 1)
 
+    # Scores of the predictive distribution of y: the finite Gaussian mixture over the Gauss-Hermite rule centred on gm that predict_density
+    # (centre='mean') defines (zigp_predict_scores).  The fixed rule only: a rule that moves with y is not one
+    # distribution per row.
+    def predict_cdf(self, Xnew, Ynew, n_quad=64):
+        """(F, SF), each (N,1): P(y <= Ynew) and P(y > Ynew) per row, each its own sum (the small tail keeps its relative accuracy)"""
+        r = self._engine.predict_scores(self._values(), np.asarray(Xnew, dtype=np.float64), np.asarray(Ynew, dtype=np.float64), jitter=JITTER,
+                                        n_quad=n_quad, crps=False)
+        return r['cdf'].reshape(-1, 1), r['sf'].reshape(-1, 1)
+
+    def predict_quantiles(self, Xnew, levels, n_quad=64):
+        """(N, L): the quantiles of y at the L levels (each strictly inside (0, 1); at most 16 per call), in the caller's order"""
+        r = self._engine.predict_scores(self._values(), np.asarray(Xnew, dtype=np.float64), None, jitter=JITTER, n_quad=n_quad, levels=levels)
+        if r['quantiles'] is None:
+            return np.zeros((np.asarray(Xnew).shape[0], 0))
+        return np.ascontiguousarray(r['quantiles'].T)
+
+    def predict_crps(self, Xnew, Ynew, n_quad=64):
+        """(N,1): the continuous ranked probability score of Ynew under the predictive distribution, per row (closed form of the mixture)"""
+        r = self._engine.predict_scores(self._values(), np.asarray(Xnew, dtype=np.float64), np.asarray(Ynew, dtype=np.float64), jitter=JITTER,
+                                        n_quad=n_quad, cdf=False)
+        return r['crps'].reshape(-1, 1)
+
     def optimize(self, method='L-BFGS-B', maxiter=1000, disp=False, callback=None, learning_rate=0.01, device_loop=None, **kw):
         """GPflow Model.optimize: scipy L-BFGS-B on the free state (default), or Adam when method='adam'
         (the commented alternative at zero-inflated-gpflow.ipynb:155).  Adam without a callback runs its loop on the device

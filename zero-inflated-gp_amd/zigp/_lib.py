@@ -14,7 +14,8 @@ LIK_ONOFF, LIK_GAUSSIAN, LIK_BERNOULLI = 0, 1, 2   # include/zigp.h ZIGP_LIK_*
 KERN_RBF, KERN_MATERN32, KERN_MATERN52 = 0, 1, 2   # include/zigp.h ZIGP_KERN_*: kernel family of a dense latent (zigp_set_kernel)
 KERNELS = {'rbf': KERN_RBF, 'matern32': KERN_MATERN32, 'matern52': KERN_MATERN52}
 DENSITY_MAX_QUAD = 256   # include/zigp.h ZIGP_DENSITY_MAX_QUAD: nodes of the quadrature rule of the density calls
-MATERN_MAX_D = 8     # the Matern kernels cover the input dimensions of the per-dimension kernels (csrc/zigp_kernels.h MAXD)
+SCORE_MAX_LEVELS = 16    # include/zigp.h ZIGP_SCORE_MAX_LEVELS: quantile levels of one score call
+MATERN_MAX_D = 8    # the Matern kernels cover the input dimensions of the per-dimension kernels (csrc/zigp_kernels.h MAXD)
 PROF_CLASSES = ('gemm_A1', 'gemm_A2', 'gemm_H', 'gemm_J', 'syrk', 'kuf_build', 'pointwise', 'kgrad', 'mxm_stage', 'other')
 PROF_KERNELS = {'gemm_A1': 'gemm_f64_kernel<1,1,2,false,1,8,EpiStoreColsum> (A1 = W K, W read through W^T)',
                 'gemm_A2': 'gemm_f64_kernel<1,1,2,false,2,8,EpiColsum> (A2 = W^T A1, reduced to the column sums sum_m s^2 A2^2 in the epilogue; the panel is not stored; value-only ELBO and predict only)',
@@ -214,6 +215,11 @@ SIGNATURES = {
                                                dp, dp, dp]),
     'zigp_predict_density_centred_device': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
                                                       dp, dp, C.c_int32, C.c_void_p, dp, C.c_void_p]),
+    'zigp_score_rows': (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, C.c_int64, C.c_double, dp, dp, C.c_int32, dp, C.c_int32, dp, dp, dp, dp]),
+    'zigp_predict_scores': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), dp, dp, C.c_int64, C.c_double, C.c_double, dp, dp, C.c_int32, dp, C.c_int32,
+                                      dp, dp, dp, dp]),
+    'zigp_predict_scores_device': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
+                                             dp, dp, C.c_int32, dp, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, dp]),
     'zigp_profile_enable': (C.c_int, [C.c_void_p, C.c_int32]),
     'zigp_profile_get': (C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int64), dp]),
     'zigp_profile_reset': (C.c_int, [C.c_void_p]),

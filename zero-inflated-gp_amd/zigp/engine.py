@@ -597,6 +597,101 @@ class DenseEngine:
         res = out, float(total[0])
         return res + (centre2,) if return_centre else res
 
+    # ---- predictive scores: CDF, quantiles and CRPS of y (include/zigp.h "predictive scores") ----
+    @staticmethod
+    def _levels(levels):
+        """the quantile levels as a float64 array, or None for an empty set; the library checks the values"""
+        lv = as_f64(levels).reshape(-1)
+        if lv.size > _lib.SCORE_MAX_LEVELS:
+            raise ValueError('levels: at most %d levels per call (ZIGP_SCORE_MAX_LEVELS), not %d' % (_lib.SCORE_MAX_LEVELS, lv.size))
+        return lv if lv.size else None
+
+    @staticmethod
+    def _score_result(cdf2, quant, crps, total):
+        return {'cdf': None if cdf2 is None else cdf2[0], 'sf': None if cdf2 is None else cdf2[1], 'quantiles': quant, 'crps': crps,
+                'crps_sum': None if total is None else float(total[0])}
+
+    def score_rows(self, lik, fm, fv, gm, gv, y, noise, n_quad=64, rule=None, levels=(), cdf=True, crps=True):
+        """CDF pair, quantiles and CRPS of y under rows of a predict call, as a dict: 'cdf' and 'sf' (N) = F(y) and SF(y), each its own sum;
+        'quantiles' (L, N), one row per level of `levels` in the caller's order; 'crps' (N) and 'crps_sum'.  A key is None where that
+        output was not asked for: y=None leaves only the quantiles, levels=() leaves them out, cdf=False / crps=False drop those two.
+        lik 'onoff' (rows 3-6 of predict / kron_predict; the mixture over `rule` = (nodes, weights) for N(0, 1), default Gauss-Hermite with
+        n_quad nodes) or 'gaussian' (rows 0-1 of kron_head_predict, closed form; gm, gv and the rule are not read and may be None).
+        'bernoulli' is refused: it has no density, and its CRPS is the Brier score (ymean - y)^2 of density_rows.  The rule is the fixed
+        one only: a rule that moves with y (centre='mode') does not define one distribution per row."""
+        lik = self.DENSITY_LIK[lik] if isinstance(lik, str) else int(lik)
+        onoff = lik == _lib.LIK_ONOFF
+        fm = as_f64(fm).reshape(-1)
+        N = fm.size
+        rows = [fm] + [None if a is None else as_f64(a).reshape(-1) for a in (fv, gm if onoff else None, gv if onoff else None, y)]
+        if any(a is not None and a.size != N for a in rows):
+            raise ValueError('score_rows: fm, fv, gm, gv and y must have the same length')
+        x, w = self._rule(n_quad, rule) if onoff else (None, None)
+        lv = self._levels(levels)
+        have_y = rows[4] is not None
+        cdf2 = np.zeros((2, N)) if have_y and cdf else None
+        quant = None if lv is None else np.zeros((lv.size, N))
+        out = np.zeros(N) if have_y and crps else None
+        total = np.zeros(1) if have_y and crps else None
+        _check(self.lib, self.ctx, self.lib.zigp_score_rows(self.ctx, lik, *[self._opt(a) for a in rows], N, float(noise), self._opt(x), self._opt(w),
+                                                            0 if x is None else x.size, self._opt(lv), 0 if lv is None else lv.size,
+                                                            self._opt(cdf2), self._opt(quant), self._opt(out), self._opt(total)))
+        return self._score_result(cdf2, quant, out, total)
+
+    def predict_scores(self, p, Xnew, Ynew=None, jitter=1e-6, g_offset=0.0, n_quad=64, rule=None, levels=(), cdf=True, crps=True):
+        """Scores of the dense OnOff model: predict at Xnew (N, D), then score_rows' dict for Ynew (N, or None) under its rows, on the device."""
+        pk = _Packed(p)
+        self._set_mean_function(p, pk.D)
+        self._set_modes(p)
+        Xnew = as_f64(Xnew)
+        Ynew = None if Ynew is None else as_f64(Ynew).reshape(-1)
+        if Xnew.ndim != 2 or Xnew.shape[1] != pk.D or (Ynew is not None and Ynew.size != Xnew.shape[0]):
+            raise ValueError('Xnew must be (N,%d) and Ynew must have N entries' % pk.D)
+        x, w = self._rule(n_quad, rule)
+        lv = self._levels(levels)
+        N = Xnew.shape[0]
+        have_y = Ynew is not None
+        cdf2 = np.zeros((2, N)) if have_y and cdf else None
+        quant = None if lv is None else np.zeros((lv.size, N))
+        out = np.zeros(N) if have_y and crps else None
+        total = np.zeros(1) if have_y and crps else None
+        _check(self.lib, self.ctx, self.lib.zigp_predict_scores(self.ctx, C.byref(pk.struct), ptr(Xnew), self._opt(Ynew), N, float(jitter), float(g_offset),
+                                                                ptr(x), ptr(w), x.size, self._opt(lv), 0 if lv is None else lv.size,
+                                                                self._opt(cdf2), self._opt(quant), self._opt(out), self._opt(total)))
+        return self._score_result(cdf2, quant, out, total)
+
+    def predict_scores_device(self, p, X_t, Y_t=None, jitter=1e-6, g_offset=0.0, n_quad=64, rule=None, levels=(), cdf=True, crps=True):
+        """predict_scores on torch CUDA float64 tensors X_t (N, D) and Y_t (N) or (N, 1) (or None) of the engine's device; the dict's arrays
+        are CUDA tensors, 'crps_sum' a float -- nothing but the parameters, the rule, the levels and the sum crosses PCIe."""
+        import torch
+        pk = _Packed(p)
+        self._set_mean_function(p, pk.D)
+        self._set_modes(p)
+
+        def ok(t):
+            return t.is_cuda and t.device.index == self.device and t.dtype == torch.float64 and t.is_contiguous()
+        if not (ok(X_t) and X_t.dim() == 2 and X_t.shape[1] == pk.D):
+            raise ValueError('predict_scores_device: X needs a contiguous float64 (N,%d) tensor on cuda:%d' % (pk.D, self.device))
+        N = int(X_t.shape[0])
+        if Y_t is not None and not (ok(Y_t) and Y_t.numel() == N):
+            raise ValueError('predict_scores_device: Y needs a contiguous float64 tensor of N entries on cuda:%d' % self.device)
+        x, w = self._rule(n_quad, rule)
+        lv = self._levels(levels)
+        have_y = Y_t is not None
+
+        def new(*shape):
+            return torch.zeros(shape, dtype=torch.float64, device=X_t.device)
+        cdf2 = new(2, N) if have_y and cdf else None
+        quant = None if lv is None else new(lv.size, N)
+        out = new(N) if have_y and crps else None
+        total = np.zeros(1) if have_y and crps else None
+        D = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
+        torch.cuda.current_stream(self.device).synchronize()      # the engine's streams are not ordered after torch's
+        _check(self.lib, self.ctx, self.lib.zigp_predict_scores_device(self.ctx, C.byref(pk.struct), D(X_t), D(Y_t), N, float(jitter), float(g_offset),
+                                                                       ptr(x), ptr(w), x.size, self._opt(lv), 0 if lv is None else lv.size,
+                                                                       D(cdf2), D(quant), D(out), self._opt(total)))
+        return self._score_result(cdf2, quant, out, total)
+
     def prior_kl(self, p, jitter=1e-6):
         pk = _Packed(p)
         self._set_modes(p)
