@@ -495,6 +495,61 @@ int zigp_predict_scores_device(zigp_ctx* ctx, const zigp_params* p, const double
                                double g_offset, const double* nodes, const double* weights, int32_t n_quad, const double* levels,
                                int32_t n_levels, double* d_cdf2, double* d_quant, double* d_crps, double* crps_sum);
 
+/* ---- sample paths: joint posterior draws at test inputs by pathwise conditioning (new) ----
+ * Replaces GPflow 0.4.0's predict_f_samples for the model that OnOffSVGP mirrors, without a T x T covariance: a path is
+ *   f*(x) = f_prior(x) + k(x, Z) Kuu^-1 (u - f_prior(Z)),   u ~ q(u),   f_prior a random-feature draw of the prior (Wilson et al., 2020),
+ * so every test row is one finite sum given the draw.  Per latent h, row n and sample s, THE definition:
+ *   out[h][s][n] = shift_h + sum_d lin_h[d] x[n][d] + sum_{m<M} V_h[m][s] k_h(x_n, z_m)
+ *                + sum_{r<R} amp_h[r][s] cos( sum_d omega_h[r][d] x[n][d] + phase_h[r] )
+ * k_h the latent's ZIGP_KERN_* kind with the Kuf panel's own element function (the Matern kinds through the floored distance
+ * sqrt(r^2 + 1e-12)).  One summation order per element (kernel terms in groups of four in ascending m, then the cosines in ascending r,
+ * the mean part last): an element's bits do not depend on N, on the row's position, on S, on the sample's column, on the other latent
+ * or on the call.  1 <= D <= 8, 1 <= S <= ZIGP_PATH_MAX_S, M >= 1, R >= 0 (R = 0: the conditional-mean part alone).  The cosine is
+ * correct for every finite argument; beyond the library's fast range (|argument| of about 1e5 and more) it takes a slower path.
+ * ZIGP_EARG with a message that names the argument, nothing enqueued and the context usable afterwards: D > 8 (the message names D),
+ * S outside [1, 256], R < 0, M < 1, an unknown kind, a NULL table, a non-finite table entry, and a host pointer handed to a _device call.
+ * The Kronecker path, the heads and D > 8 have no sample paths. */
+#define ZIGP_PATH_MAX_S 256
+typedef struct {
+  int32_t kind, M, R, reserved;      /* ZIGP_KERN_*, inducing points, random features */
+  const double* Z;                   /* (M,D) */
+  const double* ell;                 /* (D) */
+  double var;
+  const double* V;                   /* (M,S) weights of the kernel terms */
+  const double* omega;               /* (R,D) frequencies */
+  const double* phase;               /* (R) */
+  const double* amp;                 /* (R,S) weights of the cosines */
+  const double* lin;                 /* (D) or NULL */
+  double shift;
+} zigp_path_latent;
+/* The sum above and nothing else.  lat: nlat (1 or 2) records, all arrays in host memory; X (N,D) and out (nlat,S,N) in host memory. */
+int zigp_path_rows(zigp_ctx* ctx, const zigp_path_latent* lat, int32_t nlat, int32_t D, int32_t S, const double* X, int64_t N, double* out);
+/* The same with X and out in DEVICE memory of the context's GPU (the tables stay host pointers); complete on return. */
+int zigp_path_rows_device(zigp_ctx* ctx, const zigp_path_latent* lat, int32_t nlat, int32_t D, int32_t S, const double* dX, int64_t N,
+                          double* d_out);
+/* A parameter-free draw of one latent: R random features and the standard normals behind u.  Handing the same draw to calls with other
+ * inputs or other hyperparameters gives the same paths there. */
+typedef struct {
+  int32_t R, reserved;
+  const double* omega0;              /* (R,D) frequencies for unit lengthscales: N(0, I) for RBF, Student-t with 2 nu degrees for Matern */
+  const double* phase;               /* (R) uniform on [0, 2 pi) */
+  const double* a;                   /* (R,S) standard normals */
+  const double* eps;                 /* (M,S) standard normals */
+} zigp_path_draw;
+/* Joint sample paths of the dense OnOff model.  Per latent: omega = omega0 / ell, amp = a sqrt(2 var / R); f_Z = the sum above at the
+ * rows Z with V = 0; V = W^T t with the W = L^-1 of the call's own M x M forward stage (Kuu + jitter I = L L^T) and
+ *   unwhitened: t = W (u_m + s o eps - f_Z), then one step of iterative refinement of V against Kuu;
+ *   whitened (zigp_set_whiten): t = u_m + s o eps - W f_Z;
+ *   whitened, full covariance (zigp_set_q_full): t = u_m + tril(L_q) eps - W f_Z;
+ * then the sum at Xnew, with the context's mean function (zigp_set_mean_function) as lin and shift of f and g_offset as the shift of g,
+ * as rows fmean and gmean of zigp_predict carry them.  Honours zigp_set_kernel.  out3 is (3,S,N): f, g, and gf = Phi~(g) f with the link
+ * of the predictive density.  zigp_predict's errors (ZIGP_ENOTPD included) and the refusals above. */
+int zigp_sample_paths(zigp_ctx* ctx, const zigp_params* p, const double* Xnew, int64_t N, double jitter, double g_offset,
+                      const zigp_path_draw* draw_f, const zigp_path_draw* draw_g, int32_t S, double* out3);
+/* The same with Xnew and out3 in DEVICE memory of the context's GPU; the draws stay host pointers; complete on return. */
+int zigp_sample_paths_device(zigp_ctx* ctx, const zigp_params* p, const double* dXnew, int64_t N, double jitter, double g_offset,
+                             const zigp_path_draw* draw_f, const zigp_path_draw* draw_g, int32_t S, double* d_out3);
+
 /* ---- data-parallel exchange (new: the reference is single-process) ----
  * The ELBO data term is a sum over points (tf.reduce_sum(var_exp), onoffgpf/OnOffSVGP.py:122; scripts/onoff.py:307): one process per GPU
  * holds a row shard, and ONE ncclAllReduce(sum, f64) per step adds the packed [elbo_data, kl, gradient] vector of every rank, on the

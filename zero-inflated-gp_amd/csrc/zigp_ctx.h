@@ -171,6 +171,7 @@ struct zigp_ctx : zigp::CtxHandles {
   double mean_a[8] = {0}, mean_b = 0.0, mean_da[8] = {0}, mean_db = 0.0;   // 8 = zigp::MAXD (zigp_kernels.h)
   zigp::DevBuf out9;                    // predict outputs (9,Nc)
   zigp::DevBuf scratch, scratch2;       // misc
+  zigp::DevBuf path_tab, path_out;      // sample paths (zigp_paths.hip): the call's tables and work matrices; the staged (nlat, S, N) result of a host call
   zigp::PinnedArena pinned;             // host staging of the per-step transfers
   std::unique_ptr<zigp::KronState> kron;
   std::unique_ptr<zigp::KfState> kronf;

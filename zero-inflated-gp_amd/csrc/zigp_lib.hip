@@ -4,4 +4,5 @@
 #include "zigp_kron.hip"
 #include "zigp_density.hip"
 #include "zigp_score.hip"
+#include "zigp_paths.hip"
 #include "zigp_comm.hip"

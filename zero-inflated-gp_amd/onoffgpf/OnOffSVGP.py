@@ -231,6 +231,14 @@ class OnOffSVGP(Parameterized):
                                         n_quad=n_quad, cdf=False)
         return r['crps'].reshape(-1, 1)
 
+    def predict_onoffgp_samples(self, Xnew, num_samples, n_features=1024, seed=None):
+        """GPflow's predict_f_samples for the three latent quantities: joint posterior sample paths (f, g, gf = Phi~(g) f) at Xnew, each
+        (num_samples, N, 1), by pathwise conditioning with n_features random features per latent (zigp_sample_paths; DESIGN.md section
+        10c): nothing of size N x N is formed.  The same seed gives the same arrays; at most 256 samples per call, D <= 8."""
+        r = self._engine.sample_paths(self._values(), np.asarray(Xnew, dtype=np.float64), n_samples=int(num_samples), n_features=int(n_features),
+                                      rng=np.random.RandomState(seed), jitter=JITTER)
+        return tuple(np.ascontiguousarray(r[k])[:, :, None] for k in ('f', 'g', 'gf'))
+
     def optimize(self, method='L-BFGS-B', maxiter=1000, disp=False, callback=None, learning_rate=0.01, device_loop=None, **kw):
         """GPflow Model.optimize: scipy L-BFGS-B on the free state (default), or Adam when method='adam'
         (the commented alternative at zero-inflated-gpflow.ipynb:155).  Adam without a callback runs its loop on the device

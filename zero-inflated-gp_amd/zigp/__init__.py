@@ -6,3 +6,4 @@ There is no CPU fallback: importing works anywhere, using an engine needs the bu
 from ._lib import ZigpError, NotPositiveDefiniteError  # noqa: F401
 from .engine import DenseEngine, PARAM_KEYS, reference_engine  # noqa: F401
 from . import quadrature  # noqa: F401
+from . import pathwise  # noqa: F401

@@ -67,6 +67,19 @@ class zigp_kron_grads(C.Structure):
                 ('u_fm', dp), ('u_gm', dp), ('u_fs_sqrt', dp), ('u_gs_sqrt', dp), ('noise', C.c_double)]
 
 
+PATH_MAX_S = 256   # include/zigp.h ZIGP_PATH_MAX_S: sample paths of one call
+PATH_MAX_D = 8     # the path kernel is specialised per input dimension (csrc/zigp_paths.hip)
+
+
+class zigp_path_latent(C.Structure):   # include/zigp.h "sample paths"
+    _fields_ = [('kind', C.c_int32), ('M', C.c_int32), ('R', C.c_int32), ('reserved', C.c_int32), ('Z', dp), ('ell', dp), ('var', C.c_double),
+                ('V', dp), ('omega', dp), ('phase', dp), ('amp', dp), ('lin', dp), ('shift', C.c_double)]
+
+
+class zigp_path_draw(C.Structure):   # include/zigp.h "sample paths"
+    _fields_ = [('R', C.c_int32), ('reserved', C.c_int32), ('omega0', dp), ('phase', dp), ('a', dp), ('eps', dp)]
+
+
 FIT_BLOCKS = 17   # include/zigp.h ZIGP_FIT_BLOCKS
 
 
@@ -220,6 +233,11 @@ SIGNATURES = {
                                       dp, dp, dp, dp]),
     'zigp_predict_scores_device': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
                                              dp, dp, C.c_int32, dp, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, dp]),
+    'zigp_path_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, dp, C.c_int64, dp]),
+    'zigp_path_rows_device': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'zigp_sample_paths': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), dp, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int32, dp]),
+    'zigp_sample_paths_device': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                           C.c_int32, C.c_void_p]),
     'zigp_profile_enable': (C.c_int, [C.c_void_p, C.c_int32]),
     'zigp_profile_get': (C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int64), dp]),
     'zigp_profile_reset': (C.c_int, [C.c_void_p]),

@@ -692,6 +692,144 @@ class DenseEngine:
                                                                        D(cdf2), D(quant), D(out), self._opt(total)))
         return self._score_result(cdf2, quant, out, total)
 
+    # ---- sample paths: joint posterior draws at test inputs (include/zigp.h "sample paths") ----
+    @staticmethod
+    def _path_latents(lats, D, S):
+        """The zigp_path_latent records of path_rows and the arrays behind them.  A latent is a dict: kind ('rbf' / 'matern32' /
+        'matern52' or a ZIGP_KERN_* value), Z (M, D), ell, var, V (M, S), omega (R, D), phase (R), amp (R, S) and, optional, lin (D)
+        and shift.  Sizes and shapes are checked here, before the library is touched."""
+        from . import pathwise
+        pathwise.check_sizes(D, S)
+        if len(lats) not in (1, 2):
+            raise ValueError('path_rows takes one or two latents, not %d' % len(lats))
+        recs, keep = (_lib.zigp_path_latent * len(lats))(), []
+        for h, q in enumerate(lats):
+            Z = as_f64(q['Z'])
+            if Z.ndim != 2 or Z.shape[1] != D or Z.shape[0] < 1:
+                raise ValueError('latent %d: Z must be (M,%d) with M >= 1' % (h, D))
+            M = Z.shape[0]
+            ell = as_f64(q['ell']).reshape(-1)
+            ell = np.full(D, float(ell[0])) if ell.size == 1 else np.ascontiguousarray(ell)
+            if ell.size != D:
+                raise ValueError('latent %d: ell must be scalar or have D entries' % h)
+            phase = as_f64(q['phase']).reshape(-1)
+            R = phase.size
+            arr = dict(Z=Z, ell=ell, V=as_f64(q['V']), omega=as_f64(q['omega']).reshape(R, -1) if R else np.zeros((0, D)), phase=phase,
+                       amp=as_f64(q['amp']).reshape(R, -1) if R else np.zeros((0, S)))
+            for k, shape in (('V', (M, S)), ('omega', (R, D)), ('amp', (R, S))):
+                if arr[k].shape != shape:
+                    raise ValueError('latent %d: %s must be %s, not %s' % (h, k, shape, arr[k].shape))
+            lin = q.get('lin')
+            if lin is not None:
+                lin = as_f64(lin).reshape(-1)
+                if lin.size != D:
+                    raise ValueError('latent %d: lin must have D entries' % h)
+                arr['lin'] = lin
+            r = recs[h]
+            r.kind, r.M, r.R = pathwise._kind(q.get('kind', 'rbf')), M, R
+            r.var, r.shift = float(np.squeeze(q['var'])), float(q.get('shift', 0.0))
+            for k, a in arr.items():
+                setattr(r, k, ptr(a) if a.size else None)
+            keep.append(arr)
+        return recs, keep
+
+    def path_rows(self, lats, X, S):
+        """The finite sum of zigp_path_rows: lats a list of one or two latent dicts (see _path_latents), X (N, D) host rows;
+        returns (nlat, S, N)."""
+        X = as_f64(X)
+        if X.ndim != 2:
+            raise ValueError('X must be (N, D)')
+        N, D = X.shape
+        recs, keep = self._path_latents(lats, D, int(S))
+        out = np.zeros((len(lats), int(S), N))
+        _check(self.lib, self.ctx, self.lib.zigp_path_rows(self.ctx, C.cast(recs, C.c_void_p), len(lats), D, int(S), ptr(X), N, ptr(out)))
+        return out
+
+    def path_rows_device(self, lats, X_t, S, out=None):
+        """path_rows on a torch CUDA float64 tensor (N, D) of the engine's device; returns (or fills `out`, whose first nlat S N
+        entries are the (nlat, S, N) result) a CUDA tensor."""
+        import torch
+
+        def ok(t):
+            return t.is_cuda and t.device.index == self.device and t.dtype == torch.float64 and t.is_contiguous()
+        if not (ok(X_t) and X_t.dim() == 2):
+            raise ValueError('path_rows_device: X needs a contiguous float64 (N, D) tensor on cuda:%d' % self.device)
+        N, D = int(X_t.shape[0]), int(X_t.shape[1])
+        recs, keep = self._path_latents(lats, D, int(S))
+        if out is None:
+            out = torch.empty((len(lats), int(S), N), dtype=torch.float64, device=X_t.device)
+        elif not (ok(out) and out.numel() >= len(lats) * int(S) * N):
+            raise ValueError('path_rows_device: out must be a contiguous float64 tensor of at least nlat S N entries on the same device')
+        torch.cuda.current_stream(self.device).synchronize()      # the engine's streams are not ordered after torch's
+        _check(self.lib, self.ctx, self.lib.zigp_path_rows_device(self.ctx, C.cast(recs, C.c_void_p), len(lats), D, int(S),
+                                                                   C.c_void_p(X_t.data_ptr()), N, C.c_void_p(out.data_ptr())))
+        return out
+
+    def _path_draws(self, pk, kinds, n_samples, n_features, rng, draws):
+        """(draws dict, the two zigp_path_draw records, the arrays behind them): new draws from rng unless `draws` is handed back"""
+        from . import pathwise
+        S = int(n_samples)
+        pathwise.check_sizes(pk.D, S)
+        if draws is None:
+            if rng is None:
+                rng = np.random.RandomState()
+            elif isinstance(rng, (int, np.integer)):
+                rng = np.random.RandomState(int(rng))
+            draws = {tag: pathwise.draw(kinds[h], int(n_features), pk.D, M, S, rng) for h, (tag, M) in enumerate((('f', pk.Mf), ('g', pk.Mg)))}
+        recs, keep = [], []
+        for tag, M in (('f', pk.Mf), ('g', pk.Mg)):
+            R, arr = pathwise.check_draw(draws[tag], tag, M, pk.D, S)
+            r = _lib.zigp_path_draw()
+            r.R = R
+            for k, a in arr.items():
+                setattr(r, k, ptr(a) if a.size else None)
+            recs.append(r)
+            keep.append(arr)
+        return draws, recs, keep
+
+    def sample_paths(self, p, Xnew, n_samples=16, n_features=1024, rng=None, draws=None, jitter=1e-6, g_offset=0.0):
+        """Joint posterior sample paths of the dense OnOff model at Xnew (N, D) by pathwise conditioning (zigp_sample_paths): returns
+        dict(f, g, gf: (S, N) each; draws).  rng: a numpy RandomState / Generator or a seed.  draws: the `draws` of an earlier call --
+        the same paths at other inputs or other hyperparameters (n_samples and the model's M must match them).  p is read as predict
+        reads it (whiten, q_diag, kern_f / kern_g, mean_a / mean_b).  D <= 8, 1 <= n_samples <= 256."""
+        pk = _Packed(p)
+        Xnew = as_f64(Xnew)
+        if Xnew.ndim != 2 or Xnew.shape[1] != pk.D:
+            raise ValueError('Xnew must be (N,%d)' % pk.D)
+        draws, recs, keep = self._path_draws(pk, pk.kinds, n_samples, n_features, rng, draws)
+        self._set_mean_function(p, pk.D)
+        self._set_modes(p)
+        S, N = int(n_samples), Xnew.shape[0]
+        out = np.zeros((3, S, N))
+        _check(self.lib, self.ctx, self.lib.zigp_sample_paths(self.ctx, C.byref(pk.struct), ptr(Xnew), N, float(jitter), float(g_offset),
+                                                               C.addressof(recs[0]), C.addressof(recs[1]), S, ptr(out)))
+        return dict(f=out[0], g=out[1], gf=out[2], draws=draws)
+
+    def sample_paths_device(self, p, X_t, n_samples=16, n_features=1024, rng=None, draws=None, jitter=1e-6, g_offset=0.0, out=None):
+        """sample_paths on a torch CUDA float64 tensor (N, D) of the engine's device: f, g, gf are views of one (3, S, N) CUDA tensor
+        (`out` when given) -- nothing but the parameters and the draws crosses PCIe."""
+        import torch
+        pk = _Packed(p)
+
+        def ok(t):
+            return t.is_cuda and t.device.index == self.device and t.dtype == torch.float64 and t.is_contiguous()
+        if not (ok(X_t) and X_t.dim() == 2 and X_t.shape[1] == pk.D):
+            raise ValueError('sample_paths_device: X needs a contiguous float64 (N,%d) tensor on cuda:%d' % (pk.D, self.device))
+        draws, recs, keep = self._path_draws(pk, pk.kinds, n_samples, n_features, rng, draws)
+        self._set_mean_function(p, pk.D)
+        self._set_modes(p)
+        S, N = int(n_samples), int(X_t.shape[0])
+        if out is None:
+            out = torch.empty((3, S, N), dtype=torch.float64, device=X_t.device)
+        elif not (ok(out) and tuple(out.shape) == (3, S, N)):
+            raise ValueError('sample_paths_device: out must be a contiguous float64 (3,S,N) tensor on the same device')
+        torch.cuda.current_stream(self.device).synchronize()      # the engine's streams are not ordered after torch's
+        if N:
+            _check(self.lib, self.ctx, self.lib.zigp_sample_paths_device(self.ctx, C.byref(pk.struct), C.c_void_p(X_t.data_ptr()), N, float(jitter),
+                                                                          float(g_offset), C.addressof(recs[0]), C.addressof(recs[1]), S,
+                                                                          C.c_void_p(out.data_ptr())))
+        return dict(f=out[0], g=out[1], gf=out[2], draws=draws)
+
     def prior_kl(self, p, jitter=1e-6):
         pk = _Packed(p)
         self._set_modes(p)
