@@ -550,6 +550,37 @@ int zigp_sample_paths(zigp_ctx* ctx, const zigp_params* p, const double* Xnew, i
 int zigp_sample_paths_device(zigp_ctx* ctx, const zigp_params* p, const double* dXnew, int64_t N, double jitter, double g_offset,
                              const zigp_path_draw* draw_f, const zigp_path_draw* draw_g, int32_t S, double* d_out3);
 
+/* ---- inducing inputs by k-means on the device: Lloyd iterations (new entry points) ----
+ * Replaces the host-side scipy.cluster.vq.kmeans call that picks the inducing inputs before the first ELBO step (scripts/onoff.py:67,
+ * scripts/svgp.py:64; the same call in onofftf/model.py init_params and onofftf/heads.py init_head_params) by its Lloyd iterations from a
+ * start the caller chooses; seeding, restarts and a tolerance stop stay with the caller.  THE definition -- X: N rows of stride ld doubles,
+ * of which the D columns from col0 are used; C (M, D) row-major, read and written.  Iteration t = 1, 2, ... with the current C:
+ *   d(i, j)   = sum_k (x_ik - c_jk)^2, k ascending, in the difference form (never |x|^2 - 2 x.c + |c|^2);
+ *   label_i   = the LOWEST j attaining min_j d(i, j);
+ *   c_j      <- (sum of the rows of label j) / count_j where count_j > 0; an empty cluster keeps its centroid;
+ *   inertia_t = sum_i d(i, label_i) against C before the update;  changed_t = rows whose label differs from iteration t - 1, changed_1 = N.
+ * The loop stops after the first t with changed_t = 0 (that iteration's update reproduces C bit for bit), or at t = max_iter.
+ * Outputs: C; labels int32 [N] of the last assignment; counts int64 [M]; history double [max_iter][2] = (inertia_t, changed_t), rows past
+ * *n_iter left as the caller passed them; *n_iter.  labels, counts and history may be NULL.  Every sum has one fixed order (no
+ * floating-point atomics): the same call gives the same bits every time, and the three forms below agree bit for bit on the same rows.
+ * Limits: 1 <= D <= ZIGP_MAX_D, 1 <= M <= min(N, ZIGP_KMEANS_MAX_M), N < 2^31, 1 <= max_iter <= 1048576.
+ * ZIGP_EARG with a message that names the argument, the outputs untouched and the context usable afterwards: a NULL context (before
+ * anything else is read), M < 1, M > N, M > ZIGP_KMEANS_MAX_M, D out of range, col0 < 0 or col0 + D > ld, max_iter out of range, a NULL
+ * X, C or n_iter, no resident data (the _resident form), a host pointer handed to the _device form (refused, not dereferenced), a
+ * non-finite entry of C (checked on the host: a NaN centroid never wins a row) and an inertia of iteration 1 that is not finite (X
+ * holds a non-finite value in the columns used). */
+#define ZIGP_KMEANS_MAX_M 4096
+/* X (N, ld), C and the outputs in HOST memory. */
+int zigp_kmeans(zigp_ctx* ctx, const double* X, int64_t N, int32_t ld, int32_t col0, int32_t D, int32_t M, double* C, int32_t max_iter,
+                int32_t* labels, int64_t* counts, double* history, int32_t* n_iter);
+/* The same with X in DEVICE memory of the context's GPU (e.g. a torch tensor); C and the outputs stay host pointers. */
+int zigp_kmeans_device(zigp_ctx* ctx, const double* dX, int64_t N, int32_t ld, int32_t col0, int32_t D, int32_t M, double* C,
+                       int32_t max_iter, int32_t* labels, int64_t* counts, double* history, int32_t* n_iter);
+/* The same on the WHOLE resident set of zigp_set_data / zigp_set_data_device (ld = its D): a selection made by zigp_select_rows is
+ * ignored and left as it was. */
+int zigp_kmeans_resident(zigp_ctx* ctx, int32_t col0, int32_t D, int32_t M, double* C, int32_t max_iter, int32_t* labels, int64_t* counts,
+                         double* history, int32_t* n_iter);
+
 /* ---- data-parallel exchange (new: the reference is single-process) ----
  * The ELBO data term is a sum over points (tf.reduce_sum(var_exp), onoffgpf/OnOffSVGP.py:122; scripts/onoff.py:307): one process per GPU
  * holds a row shard, and ONE ncclAllReduce(sum, f64) per step adds the packed [elbo_data, kl, gradient] vector of every rank, on the

@@ -22,10 +22,19 @@ PREDICT_JITTER = 1e-6   # onofftf/svgppred.py:13, onofftf/svcppred.py:13
 
 
 def init_head_params(Xtrain, num_inducing_f, lik, init_ell=(5., 5.), u_scale=0.01, init_noisevar=0.01, include_f_mu=False,
-                     kern_lr=1e-3, indp_lr=1e-3, rng=None, kmeans_seed=None):
+                     kern_lr=1e-3, indp_lr=1e-3, rng=None, kmeans_seed=None, kmeans='scipy', engine=None):
     """svgp.py:51-112 (ell [5,5],[5/1000]; var 20; noise 0.01; u 0.01*randn; s 1); the predictors rebuild the same set with
-    ell [8,8], u 0.1*randn, noise 0.001 before restoring (svgppred.py:21-37) -- those values are overwritten by the restore."""
-    from scipy.cluster.vq import kmeans
+    ell [8,8], u 0.1*randn, noise 0.001 before restoring (svgppred.py:21-37) -- those values are overwritten by the restore.
+    kmeans: 'scipy' (the reference's host call, svgp.py:64) or 'device' (onofftf.model.device_kmeans, on `engine`)."""
+    if kmeans not in ('scipy', 'device'):
+        raise ValueError("kmeans must be 'scipy' or 'device', not %r" % (kmeans,))
+    if kmeans == 'device':
+        from .model import device_kmeans
+
+        def kmeans(X2, M, seed=None):
+            return (device_kmeans(Xtrain, M, seed, engine),)
+    else:
+        from scipy.cluster.vq import kmeans
     rng = rng or np.random
     M0, M1 = int(num_inducing_f[0]), int(num_inducing_f[1])
     Zs = kmeans(Xtrain[:, 0:2], M0, seed=kmeans_seed)[0]                          # svgp.py:64

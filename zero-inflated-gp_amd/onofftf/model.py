@@ -10,9 +10,29 @@ from zigp.transforms import Log1pe, positive
 from .main import Param
 
 
-def init_params(Xtrain, num_inducing_f, num_inducing_g, init_noisevar=0.01, kern_lr=1e-3, indp_lr=1e-3, rng=None, kmeans_seed=None):
-    """scripts/onoff.py:51-137 (fit, noise 0.01) / onofftf/onoffpred.py:21-105 (predict, noise 0.001)."""
-    from scipy.cluster.vq import kmeans
+def device_kmeans(Xtrain, M, kmeans_seed, engine=None):
+    """The spatial centroids on the device: Lloyd iterations on Xtrain[:, 0:2] from the M rows zigp.inducing.sample_rows(N, M, kmeans_seed)
+    (DenseEngine.kmeans); always M centroids, an empty cluster keeps its start row.  engine None: one on device 0 for the call."""
+    import zigp
+    eng = engine if engine is not None else zigp.DenseEngine(0)
+    try:
+        return eng.kmeans(Xtrain, int(M), seed=kmeans_seed, cols=(0, 2))
+    finally:
+        if engine is None:
+            eng.close()
+
+
+def init_params(Xtrain, num_inducing_f, num_inducing_g, init_noisevar=0.01, kern_lr=1e-3, indp_lr=1e-3, rng=None, kmeans_seed=None,
+                kmeans='scipy', engine=None):
+    """scripts/onoff.py:51-137 (fit, noise 0.01) / onofftf/onoffpred.py:21-105 (predict, noise 0.001).
+    kmeans: 'scipy' (the reference's host call, :67) or 'device' (device_kmeans above, on `engine`)."""
+    if kmeans not in ('scipy', 'device'):
+        raise ValueError("kmeans must be 'scipy' or 'device', not %r" % (kmeans,))
+    if kmeans == 'device':
+        def kmeans(X2, M, seed=None):
+            return (device_kmeans(Xtrain, M, seed, engine),)
+    else:
+        from scipy.cluster.vq import kmeans
     rng = rng or np.random
     init_ell = [np.array([8., 8.]), np.array([5. / 1000])]                     # :57,60
     Zs = kmeans(Xtrain[:, 0:2], int(num_inducing_f[0]), seed=kmeans_seed)[0]      # :67 (unseeded in the reference)

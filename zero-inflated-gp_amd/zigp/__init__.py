@@ -7,3 +7,4 @@ from ._lib import ZigpError, NotPositiveDefiniteError  # noqa: F401
 from .engine import DenseEngine, PARAM_KEYS, reference_engine  # noqa: F401
 from . import quadrature  # noqa: F401
 from . import pathwise  # noqa: F401
+from . import inducing  # noqa: F401

@@ -238,6 +238,11 @@ SIGNATURES = {
     'zigp_sample_paths': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), dp, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int32, dp]),
     'zigp_sample_paths_device': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                            C.c_int32, C.c_void_p]),
+    'zigp_kmeans': (C.c_int, [C.c_void_p, dp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.c_int32, C.c_void_p, C.c_void_p, dp,
+                              C.POINTER(C.c_int32)]),
+    'zigp_kmeans_device': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.c_int32, C.c_void_p,
+                                     C.c_void_p, dp, C.POINTER(C.c_int32)]),
+    'zigp_kmeans_resident': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, dp, C.c_int32, C.c_void_p, C.c_void_p, dp, C.POINTER(C.c_int32)]),
     'zigp_profile_enable': (C.c_int, [C.c_void_p, C.c_int32]),
     'zigp_profile_get': (C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int64), dp]),
     'zigp_profile_reset': (C.c_int, [C.c_void_p]),

@@ -830,6 +830,73 @@ class DenseEngine:
                                                                           C.c_void_p(out.data_ptr())))
         return dict(f=out[0], g=out[1], gf=out[2], draws=draws)
 
+    # ---- inducing inputs by k-means on the device (include/zigp.h "inducing inputs"; zigp.inducing) ----
+    @staticmethod
+    def _kmeans_args(N, ld, M, init, seed, max_iter, cols, rows_of):
+        """(col0, D, C, outputs) of a k-means call, every refusal raised before the library is touched.  init None: the rows
+        zigp.inducing.sample_rows(N, M, seed), fetched by rows_of(idx) -> (M, ld)."""
+        from . import inducing
+        M, max_iter = int(M), int(max_iter)
+        col0, D = inducing.check_cols(cols, ld)
+        inducing.check_sizes(N, D, M, max_iter)
+        if init is None:
+            Cm = np.array(rows_of(inducing.sample_rows(N, M, seed))[:, col0:col0 + D], dtype=np.float64, order='C')
+        else:
+            Cm = inducing.check_init(init, M, D)
+        return col0, D, Cm, dict(labels=np.zeros(N, dtype=np.int32), counts=np.zeros(M, dtype=np.int64), history=np.zeros((max_iter, 2)))
+
+    @staticmethod
+    def _kmeans_result(Cm, out, n_iter, return_info):
+        if not return_info:
+            return Cm
+        h = out['history'][:n_iter]
+        return Cm, dict(labels=out['labels'], counts=out['counts'], inertia=h[:, 0].copy(), changed=h[:, 1].astype(np.int64), n_iter=n_iter,
+                        n_empty=int(np.count_nonzero(out['counts'] == 0)))
+
+    def kmeans(self, X, M, init=None, seed=None, max_iter=100, cols=None, return_info=False):
+        """Lloyd iterations on the device from a start the caller chooses (zigp_kmeans; the definition is zigp.inducing.kmeans_np).
+        X (N, ld) host rows, of which cols = (col0, D) are used (None: all); init None: the rows sample_rows(N, M, seed), else an
+        (M, D) array.  Returns the (M, D) centroids, with return_info also dict(labels, counts, inertia, changed, n_iter, n_empty)."""
+        X = as_f64(X)
+        if X.ndim != 2:
+            raise ValueError('X must be (N, ld)')
+        N, ld = X.shape
+        col0, D, Cm, out = self._kmeans_args(N, ld, M, init, seed, max_iter, cols, lambda idx: X[idx])
+        n = C.c_int32(0)
+        _check(self.lib, self.ctx, self.lib.zigp_kmeans(self.ctx, ptr(X), N, ld, col0, D, int(M), ptr(Cm), int(max_iter), out['labels'].ctypes.data,
+                                                        out['counts'].ctypes.data, ptr(out['history']), C.byref(n)))
+        return self._kmeans_result(Cm, out, n.value, return_info)
+
+    def kmeans_device(self, X_t, M, init=None, seed=None, max_iter=100, cols=None, return_info=False):
+        """kmeans on a torch CUDA float64 tensor (N, ld) of the engine's device (zigp_kmeans_device): the rows stay where they are, the
+        centroids and the info come back as host arrays."""
+        import torch
+        if not (X_t.is_cuda and X_t.device.index == self.device and X_t.dtype == torch.float64 and X_t.is_contiguous() and X_t.dim() == 2):
+            raise ValueError('kmeans_device: X needs a contiguous float64 (N, ld) tensor on cuda:%d' % self.device)
+        N, ld = int(X_t.shape[0]), int(X_t.shape[1])
+        col0, D, Cm, out = self._kmeans_args(N, ld, M, init, seed, max_iter, cols,
+                                             lambda idx: X_t[torch.as_tensor(idx, device=X_t.device)].cpu().numpy())
+        torch.cuda.current_stream(self.device).synchronize()      # the engine's streams are not ordered after torch's
+        n = C.c_int32(0)
+        _check(self.lib, self.ctx, self.lib.zigp_kmeans_device(self.ctx, C.c_void_p(X_t.data_ptr()), N, ld, col0, D, int(M), ptr(Cm), int(max_iter),
+                                                               out['labels'].ctypes.data, out['counts'].ctypes.data, ptr(out['history']), C.byref(n)))
+        return self._kmeans_result(Cm, out, n.value, return_info)
+
+    def kmeans_resident(self, M, init=None, max_iter=100, cols=None, return_info=False):
+        """kmeans on the WHOLE resident set of set_data / set_data_device (zigp_kmeans_resident): a selection made by select_rows is
+        ignored and left as it was.  init is an (M, D) start: the rows are on the device, so the caller picks it (e.g.
+        X[sample_rows(N, M, seed)] before set_data)."""
+        if self._full_N < 1:
+            raise ValueError('kmeans_resident: no resident data (call set_data first)')
+        if init is None:
+            raise ValueError('kmeans_resident: init must be an (M, D) array (the rows are on the device: nothing to sample from here)')
+        N, ld = int(self._full_N), int(self.D)
+        col0, D, Cm, out = self._kmeans_args(N, ld, M, init, None, max_iter, cols, None)
+        n = C.c_int32(0)
+        _check(self.lib, self.ctx, self.lib.zigp_kmeans_resident(self.ctx, col0, D, int(M), ptr(Cm), int(max_iter), out['labels'].ctypes.data,
+                                                                 out['counts'].ctypes.data, ptr(out['history']), C.byref(n)))
+        return self._kmeans_result(Cm, out, n.value, return_info)
+
     def prior_kl(self, p, jitter=1e-6):
         pk = _Packed(p)
         self._set_modes(p)
