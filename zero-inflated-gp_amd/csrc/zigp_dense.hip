@@ -43,6 +43,7 @@
 #include "zigp_ctx.h"
 #include "zigp_kernels.h"
 #include "zigp_host.h"
+#include "zigp_rows.h"
 #include "zigp_comm.h"
 #include <algorithm>
 #include <cmath>
@@ -1523,13 +1524,9 @@ int zigp_predict(zigp_ctx* c, const zigp_params* p, const double* Xnew, int64_t 
   if (N < 0 || (N > 0 && (!Xnew || !out9))) return fail_arg(c, "zigp_predict: bad arguments");
   if (N == 0) return ZIGP_OK;
   ZIGP_HIP(c, hipSetDevice(c->device));
-  ZIGP_ENSURE(c, c->scratch, (size_t)N * p->D);
-  ZIGP_ENSURE(c, c->out9, (size_t)9 * N);
-  ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p, Xnew, sizeof(double) * N * p->D, hipMemcpyHostToDevice, c->stream));
-  ZIGP_TRY(run_dense(c, p, c->scratch.p, nullptr, N, p->D, jitter, 1.0, g_offset, 0, N, 0, true, c->out9.p, nullptr, nullptr, nullptr));
-  ZIGP_HIP(c, hipMemcpyAsync(out9, c->out9.p, sizeof(double) * 9 * N, hipMemcpyDeviceToHost, c->stream));
-  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
-  return ZIGP_OK;
+  PredRows r;   // the block itself is the result: nine rows from its first, m0
+  ZIGP_TRY(rows_from_predict(c, p, Xnew, nullptr, N, jitter, g_offset, false, r));
+  return finish_copies(c, {{out9, r.m0, (size_t)9 * N}});
 }
 
 int zigp_predict_device(zigp_ctx* c, const zigp_params* p, const double* dXnew, int64_t N, double jitter, double g_offset, double* d_out9) {

@@ -20,13 +20,15 @@
 // (the change of variables z = zhat + tau x under the same rule; one node is the Laplace approximation).  Given (zhat, tau), which the
 // kernel returns, that finite sum is the definition.
 //
-// One kernel template, k_density_rows<LIK, CENTRED>, in four instantiations (OnOff with either centre, the two heads), and one host path:
-// density_rows behind the two zigp_density_rows* entries, predict_density behind the four zigp_predict_density* entries.  The two OnOff
-// sums are written out side by side (dn_logsumexp): equal in exact arithmetic at zhat = 0, tau = 1, they differ in their rounding.
-// Both centres share one layout of scratch2 (stated at DN_OFF_SUM below).  Resources on gfx950 (-Rpass-analysis=kernel-resource-usage),
+// One kernel template, k_density_rows<LIK, CENTRED>, in four instantiations (OnOff with either centre, the two heads), and one host path
+// on the row-call layer of zigp_rows.h: density_rows (rows_from_host) behind the two zigp_density_rows* entries, predict_density
+// (rows_from_predict) behind the four zigp_predict_density* entries, density_run behind both.  The two OnOff sums are written out side
+// by side (dn_logsumexp): equal in exact arithmetic at zhat = 0, tau = 1, they differ in their rounding.  The regions of scratch2, in
+// allocation order, each from a multiple of 8 doubles: the rule's table, the sum, the block partials, the (3, N) rows and -- centred --
+// the (2, N) centre.  Resources on gfx950 (-Rpass-analysis=kernel-resource-usage),
 // VGPRs / LDS bytes per block / waves per SIMD, no scratch anywhere: <ONOFF, false> 101 / 4128 / 4, <ONOFF, true> 130 / 6176 / 3,
 // <GAUSSIAN, false> 24 / 32 / 8, <BERNOULLI, false> 28 / 32 / 8.
-#include "zigp_host.h"
+#include "zigp_rows.h"
 #include <cmath>
 
 using namespace zigp;
@@ -207,81 +209,50 @@ k_density_rows(DensityArgs a) {
   dn_store(a, n, valid, logp, ymean, yvar, sh);
 }
 
-// One block: thread t adds the partials t, t + DN_THREADS, ... in that order, then the threads' sums are added in thread order --
-// the same association on every call, so the sum is bit-stable.
-__global__ void __launch_bounds__(DN_THREADS)
-k_density_sum(const double* __restrict__ part, int nb, double* __restrict__ out) {
-  __shared__ double sh[DN_THREADS / 64];
-  double s = 0.0;
-  for (int b = threadIdx.x; b < nb; b += DN_THREADS) s += part[b];
-  s = block_sum<DN_THREADS / 64>(s, sh);
-  if (threadIdx.x == 0) out[0] = s;
-}
-
 }  // namespace zigp
 
 namespace {
 
-// Layout of scratch2 during a density call, in doubles, the same for either centre: the rule's table in [0, 3 DN_MAXQ) (two or three
-// columns of n_quad entries from its start), the sum at DN_OFF_SUM, the nb block partials from DN_OFF_PART, then, from the next
-// multiple of 8, the (3, N) output rows and -- a centred call -- the (2, N) centre behind them
-constexpr size_t DN_OFF_SUM = 3 * DN_MAXQ, DN_OFF_PART = DN_OFF_SUM + 8;
-struct DensityBufs { double* rule; double* sum; double* part; double* out3; double* centre2; int nb; };
-
-int density_bufs(zigp_ctx* c, int64_t N, bool centred, DensityBufs& b) {
-  b.nb = ceil_div(N, DN_THREADS);
-  const size_t off_out = (DN_OFF_PART + (size_t)b.nb + 7) & ~(size_t)7;
-  ZIGP_ENSURE(c, c->scratch2, off_out + (size_t)(centred ? 5 : 3) * N);
-  b.rule = c->scratch2.p; b.sum = c->scratch2.p + DN_OFF_SUM; b.part = c->scratch2.p + DN_OFF_PART; b.out3 = c->scratch2.p + off_out;
-  b.centre2 = centred ? b.out3 + (size_t)3 * N : nullptr;
-  return 0;
-}
-
 // Everything a density call refuses that is not a pointer; touches nothing but the error text
 int density_check(zigp_ctx* c, const char* who, int lik, int64_t N, double noise, const double* nodes, const double* weights, int n_quad) {
-  const std::string w(who);
-  if (lik != ZIGP_LIK_ONOFF && lik != ZIGP_LIK_GAUSSIAN && lik != ZIGP_LIK_BERNOULLI) return fail_arg(c, (w + ": lik is not a ZIGP_LIK_* value").c_str());
-  if (N < 0) return fail_arg(c, (w + ": N is negative").c_str());
-  if (lik != ZIGP_LIK_BERNOULLI && !(noise > 0 && std::isfinite(noise))) return fail_arg(c, (w + ": noise must be positive and finite").c_str());
+  if (lik != ZIGP_LIK_ONOFF && lik != ZIGP_LIK_GAUSSIAN && lik != ZIGP_LIK_BERNOULLI) return refuse(c, who, "lik is not a ZIGP_LIK_* value");
+  if (N < 0) return refuse(c, who, "N is negative");
+  if (lik != ZIGP_LIK_BERNOULLI && !(noise > 0 && std::isfinite(noise))) return refuse(c, who, "noise must be positive and finite");
   if (lik != ZIGP_LIK_ONOFF) return 0;
-  if (n_quad < 1 || n_quad > DN_MAXQ) return fail_arg(c, (w + ": n_quad must be in [1, 256] (ZIGP_DENSITY_MAX_QUAD)").c_str());
-  if (!nodes || !weights) return fail_arg(c, (w + ": nodes or weights is NULL").c_str());
+  if (n_quad < 1 || n_quad > DN_MAXQ) return refuse(c, who, "n_quad must be in [1, 256] (ZIGP_DENSITY_MAX_QUAD)");
+  if (!nodes || !weights) return refuse(c, who, "nodes or weights is NULL");
   for (int i = 0; i < n_quad; ++i) {
-    if (!std::isfinite(nodes[i])) return fail_arg(c, (w + ": nodes has a non-finite entry").c_str());
-    if (!(weights[i] > 0 && std::isfinite(weights[i]))) return fail_arg(c, (w + ": weights must be positive and finite").c_str());
+    if (!std::isfinite(nodes[i])) return refuse(c, who, "nodes has a non-finite entry");
+    if (!(weights[i] > 0 && std::isfinite(weights[i]))) return refuse(c, who, "weights must be positive and finite");
   }
   return 0;
 }
 
-// The rule's table to the device (OnOff: nodes, the logarithms of the weights and -- centred -- x^2 / 2, all taken here), the rows
-// kernel, the sum kernel; the caller has synchronised whatever wrote the rows, and collects *hsum with its own synchronisation
-int density_run(zigp_ctx* c, int lik, bool centred, DensityArgs a, const DensityBufs& b, const double* nodes, const double* weights, double** hsum) {
-  if (lik == ZIGP_LIK_ONOFF) {
-    const int nq = a.n_quad, cols = centred ? 3 : 2;
-    ZIGP_PINNED(c, h, cols * (size_t)nq);
-    for (int i = 0; i < nq; ++i) {
-      h[i] = nodes[i]; h[nq + i] = log(weights[i]);
-      if (centred) h[2 * nq + i] = 0.5 * nodes[i] * nodes[i];
-    }
-    ZIGP_HIP(c, hipMemcpyAsync(b.rule, h, sizeof(double) * cols * nq, hipMemcpyHostToDevice, c->stream));
-  }
-  a.rule = b.rule; a.part = b.part;
-  const dim3 grid(b.nb), block(DN_THREADS);
-  if (lik == ZIGP_LIK_ONOFF && centred) hipLaunchKernelGGL((k_density_rows<ZIGP_LIK_ONOFF, true>), grid, block, 0, c->stream, a);
-  else if (lik == ZIGP_LIK_ONOFF) hipLaunchKernelGGL((k_density_rows<ZIGP_LIK_ONOFF, false>), grid, block, 0, c->stream, a);
+// The tail of every density call, behind either source of rows: the regions of scratch2, the rule's table (OnOff: nodes, the logarithms
+// of the weights and -- centred -- x^2 / 2), the rows kernel, the sum and the outputs.  on_device: out3 and centre2 are written in place.
+int density_run(zigp_ctx* c, int lik, bool centred, const PredRows& r, double noise, const double* nodes, const double* weights, int n_quad,
+                double* out3, double* centre2, bool on_device, double* sum) {
+  const bool onoff = lik == ZIGP_LIK_ONOFF;
+  const int64_t N = r.N;
+  const int nb = ceil_div(N, DN_THREADS);
+  RowArena ar(c->scratch2, "c->scratch2");
+  const size_t o_rule = ar.take(onoff ? (size_t)(centred ? 3 : 2) * n_quad : 0), o_sum = ar.take(1), o_part = ar.take(nb);
+  const size_t o_out = ar.take((size_t)3 * N), o_centre = ar.take(centred ? (size_t)2 * N : 0);
+  ZIGP_TRY(ar.commit(c));
+  if (onoff) ZIGP_TRY(upload_rule(c, ar.at(o_rule), nodes, weights, n_quad, centred ? RuleForm::X_LOGW_HALFX2 : RuleForm::X_LOGW));
+  DensityArgs a{};
+  a.fm = r.fm; a.fv = r.fv; a.gm = r.gm; a.gv = r.gv; a.y = r.y; a.m0 = r.m0; a.m1 = r.m1; a.m2 = r.m2;
+  a.N = N; a.noise = noise; a.rule = ar.at(o_rule); a.n_quad = onoff ? n_quad : 0; a.ld3 = N; a.ldc = N; a.part = ar.at(o_part);
+  a.out3 = out_target(out3, on_device, ar.at(o_out)); a.centre2 = out_target(centre2, on_device, ar.at(o_centre));
+  const dim3 grid(nb), block(DN_THREADS);
+  if (onoff && centred) hipLaunchKernelGGL((k_density_rows<ZIGP_LIK_ONOFF, true>), grid, block, 0, c->stream, a);
+  else if (onoff) hipLaunchKernelGGL((k_density_rows<ZIGP_LIK_ONOFF, false>), grid, block, 0, c->stream, a);
   else if (lik == ZIGP_LIK_GAUSSIAN) hipLaunchKernelGGL((k_density_rows<ZIGP_LIK_GAUSSIAN, false>), grid, block, 0, c->stream, a);
   else hipLaunchKernelGGL((k_density_rows<ZIGP_LIK_BERNOULLI, false>), grid, block, 0, c->stream, a);
   ZIGP_HIP(c, hipGetLastError());
-  hipLaunchKernelGGL(k_density_sum, dim3(1), block, 0, c->stream, b.part, b.nb, b.sum);
-  ZIGP_HIP(c, hipGetLastError());
-  return download(c, b.sum, 1, hsum);
-}
-
-// The end of every density call: the rows and the centre that were asked for on the host, the stream's synchronisation, the sum
-int density_finish(zigp_ctx* c, const DensityBufs& b, int64_t N, double* out3, double* centre2, const double* hsum, double* sum) {
-  if (out3) ZIGP_HIP(c, hipMemcpyAsync(out3, b.out3, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, c->stream));
-  if (centre2) ZIGP_HIP(c, hipMemcpyAsync(centre2, b.centre2, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, c->stream));
-  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  double* hsum = nullptr;
+  ZIGP_TRY(sum_partials(c, a.part, nb, ar.at(o_sum), &hsum));
+  ZIGP_TRY(finish_copies(c, {{on_device ? nullptr : out3, ar.at(o_out), (size_t)3 * N}, {on_device ? nullptr : centre2, ar.at(o_centre), (size_t)2 * N}}));
   *sum = hsum[0];
   return ZIGP_OK;
 }
@@ -292,26 +263,15 @@ int density_rows(zigp_ctx* c, const char* who, int lik, bool centred, const doub
                  double* centre2) {
   if (!c) return ZIGP_EARG;
   ZIGP_TRY(density_check(c, who, lik, N, noise, nodes, weights, n_quad));
-  if (!sum) return fail_arg(c, (std::string(who) + ": sum is NULL").c_str());
+  if (!sum) return refuse(c, who, "sum is NULL");
   const bool onoff = lik == ZIGP_LIK_ONOFF;
-  if (N > 0 && (!fm || !fv || !y || (onoff && (!gm || !gv)))) return fail_arg(c, (std::string(who) + ": a row pointer (fm, fv, gm, gv, y) is NULL").c_str());
+  if (N > 0 && (!fm || !fv || !y || (onoff && (!gm || !gv)))) return refuse(c, who, "a row pointer (fm, fv, gm, gv, y) is NULL");
   if (N == 0) { *sum = 0.0; return ZIGP_OK; }
   ZIGP_HIP(c, hipSetDevice(c->device));
   ZIGP_TRY(begin_staged_call(c));
-  DensityBufs b;
-  ZIGP_TRY(density_bufs(c, N, centred, b));
-  ZIGP_ENSURE(c, c->scratch, (size_t)5 * N);
-  double* d = c->scratch.p;
-  const double* src[5] = {fm, fv, y, gm, gv};
-  for (int k = 0; k < (onoff ? 5 : 3); ++k)
-    ZIGP_HIP(c, hipMemcpyAsync(d + k * N, src[k], sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
-  DensityArgs a{};
-  a.fm = d; a.fv = d + N; a.y = d + 2 * N; a.gm = onoff ? d + 3 * N : nullptr; a.gv = onoff ? d + 4 * N : nullptr;
-  a.N = N; a.noise = noise; a.n_quad = onoff ? n_quad : 0; a.ld3 = N; a.ldc = N;
-  a.out3 = out3 ? b.out3 : nullptr; a.centre2 = centre2 ? b.centre2 : nullptr;
-  double* hsum = nullptr;
-  ZIGP_TRY(density_run(c, lik, centred, a, b, nodes, weights, &hsum));
-  return density_finish(c, b, N, out3, centre2, hsum, sum);
+  PredRows r;
+  ZIGP_TRY(rows_from_host(c, onoff, fm, fv, gm, gv, y, N, r));
+  return density_run(c, lik, centred, r, noise, nodes, weights, n_quad, out3, centre2, false, sum);
 }
 
 // The four zigp_predict_density* entries (who: the entry's name for the messages).  on_device: X (N, D), Y (N), out3 and centre2 are
@@ -322,33 +282,16 @@ int predict_density(zigp_ctx* c, const char* who, const zigp_params* p, const do
   if (!c) return ZIGP_EARG;
   ZIGP_TRY(validate_params(c, p));
   ZIGP_TRY(density_check(c, who, ZIGP_LIK_ONOFF, N, p->noise, nodes, weights, n_quad));
-  if (!sum) return fail_arg(c, (std::string(who) + ": sum is NULL").c_str());
-  if (N > 0 && (!X || !Y)) return fail_arg(c, (std::string(who) + ": Xnew or Ynew is NULL").c_str());
+  if (!sum) return refuse(c, who, "sum is NULL");
+  if (N > 0 && (!X || !Y)) return refuse(c, who, "Xnew or Ynew is NULL");
   if (N == 0) { *sum = 0.0; return ZIGP_OK; }
   ZIGP_HIP(c, hipSetDevice(c->device));
-  if (on_device) {
-    const std::string names = centred ? ": Xnew, Ynew, out3 and centre2" : ": Xnew, Ynew and out3";
-    ZIGP_TRY(require_device_ptrs(c, {X, Y, out3, centre2}, (who + names + " must be device memory of the context's GPU").c_str()));
-  } else {
-    const size_t nx = ((size_t)N * p->D + 7) & ~(size_t)7;
-    ZIGP_ENSURE(c, c->scratch, nx + (size_t)N);
-    ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p, X, sizeof(double) * N * p->D, hipMemcpyHostToDevice, c->stream));
-    ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p + nx, Y, sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
-    X = c->scratch.p; Y = c->scratch.p + nx;
-  }
-  DensityBufs b;
-  ZIGP_TRY(density_bufs(c, N, centred, b));
-  ZIGP_ENSURE(c, c->out9, (size_t)9 * N);
-  ZIGP_TRY(run_dense(c, p, X, nullptr, N, p->D, jitter, 1.0, g_offset, 0, N, 0, true, c->out9.p, nullptr, nullptr, nullptr));   // complete on return
-  const double* r = c->out9.p;
-  DensityArgs a{};
-  a.m0 = r; a.m1 = r + N; a.m2 = r + 2 * N; a.fm = r + 3 * N; a.fv = r + 4 * N; a.gm = r + 5 * N; a.gv = r + 6 * N; a.y = Y;
-  a.N = N; a.noise = p->noise; a.n_quad = n_quad; a.ld3 = N; a.ldc = N;
-  a.out3 = !out3 ? nullptr : on_device ? out3 : b.out3;
-  a.centre2 = !centre2 ? nullptr : on_device ? centre2 : b.centre2;
-  double* hsum = nullptr;
-  ZIGP_TRY(density_run(c, ZIGP_LIK_ONOFF, centred, a, b, nodes, weights, &hsum));
-  return density_finish(c, b, N, on_device ? nullptr : out3, on_device ? nullptr : centre2, hsum, sum);
+  if (on_device)
+    ZIGP_TRY(require_device_ptrs(c, {X, Y, out3, centre2}, (std::string(who) + (centred ? ": Xnew, Ynew, out3 and centre2" : ": Xnew, Ynew and out3") +
+                                                            " must be device memory of the context's GPU").c_str()));
+  PredRows r;
+  ZIGP_TRY(rows_from_predict(c, p, X, Y, N, jitter, g_offset, on_device, r));
+  return density_run(c, ZIGP_LIK_ONOFF, centred, r, p->noise, nodes, weights, n_quad, out3, centre2, on_device, sum);
 }
 
 }  // namespace

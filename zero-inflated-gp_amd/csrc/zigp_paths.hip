@@ -38,7 +38,9 @@
 // on the GEMM core (M padded to 128 rows by the identity, S to 128 columns by zeros; the unwhitened V, whose right-hand side holds white
 // noise, takes one step of iterative refinement against Kuu: V += W^T W (rhs - Kuu V));  then the kernel on Xnew with the context's mean
 // function on f and g_offset on g, and the plane gf = dn_link(g) f (k_path_gf; dn_link of zigp_density.hip as it is).
-#include "zigp_host.h"
+// Host: path_rows and sample_paths keep their checks, tables and launches; the staging of X, the copy to the host, the call's one
+// synchronisation and the refusals' form are stage_inputs, finish_copies and refuse of zigp_rows.h.
+#include "zigp_rows.h"
 #include <cmath>
 #include <cstdlib>
 
@@ -252,17 +254,17 @@ bool path_all_finite(const double* p, size_t n) {
   return true;
 }
 int path_check_dims(zigp_ctx* c, const std::string& w, int D, int S, int64_t N) {
-  if (D < 1) return fail_arg(c, (w + ": D must be positive").c_str());
-  if (D > MAXD) return fail_arg(c, (w + ": D = " + std::to_string(D) + ": the path kernel covers D in [1, 8] (the wide path is not built)").c_str());
-  if (S < 1 || S > PT_MAXS) return fail_arg(c, (w + ": S = " + std::to_string(S) + " must be in [1, 256] (ZIGP_PATH_MAX_S)").c_str());
-  if (N < 0) return fail_arg(c, (w + ": N is negative").c_str());
+  if (D < 1) return refuse(c, w, "D must be positive");
+  if (D > MAXD) return refuse(c, w, "D = " + std::to_string(D) + ": the path kernel covers D in [1, 8] (the wide path is not built)");
+  if (S < 1 || S > PT_MAXS) return refuse(c, w, "S = " + std::to_string(S) + " must be in [1, 256] (ZIGP_PATH_MAX_S)");
+  if (N < 0) return refuse(c, w, "N is negative");
   return 0;
 }
 // a table: NULL or a non-finite entry is refused by the table's name
 int path_check_table(zigp_ctx* c, const std::string& w, const char* name, const double* p, size_t n) {
   if (n == 0) return 0;
-  if (!p) return fail_arg(c, (w + ": " + name + " is NULL").c_str());
-  if (!path_all_finite(p, n)) return fail_arg(c, (w + ": " + name + " has a non-finite entry").c_str());
+  if (!p) return refuse(c, w, std::string(name) + " is NULL");
+  if (!path_all_finite(p, n)) return refuse(c, w, std::string(name) + " has a non-finite entry");
   return 0;
 }
 
@@ -274,28 +276,28 @@ PathDims path_dims(int M, int R) { PathDims d; d.M4 = (int)round_up(M, 4); d.R4 
 int path_rows(zigp_ctx* c, const char* who, const zigp_path_latent* lat, int nlat, int D, int S, const double* X, int64_t N, double* out, bool on_device) {
   if (!c) return ZIGP_EARG;
   const std::string w(who);
-  if (!lat) return fail_arg(c, (w + ": lat is NULL").c_str());
-  if (nlat != 1 && nlat != 2) return fail_arg(c, (w + ": nlat must be 1 or 2").c_str());
+  if (!lat) return refuse(c, w, "lat is NULL");
+  if (nlat != 1 && nlat != 2) return refuse(c, w, "nlat must be 1 or 2");
   ZIGP_TRY(path_check_dims(c, w, D, S, N));
   for (int h = 0; h < nlat; ++h) {
     const zigp_path_latent& q = lat[h];
     if (q.kind != ZIGP_KERN_RBF && q.kind != ZIGP_KERN_MATERN32 && q.kind != ZIGP_KERN_MATERN52)
-      return fail_arg(c, (w + ": kind is not a ZIGP_KERN_* value").c_str());
-    if (q.M < 1) return fail_arg(c, (w + ": M must be positive").c_str());
-    if (q.R < 0) return fail_arg(c, (w + ": R is negative").c_str());
+      return refuse(c, w, "kind is not a ZIGP_KERN_* value");
+    if (q.M < 1) return refuse(c, w, "M must be positive");
+    if (q.R < 0) return refuse(c, w, "R is negative");
     ZIGP_TRY(path_check_table(c, w, "Z", q.Z, (size_t)q.M * D));
     ZIGP_TRY(path_check_table(c, w, "ell", q.ell, D));
     ZIGP_TRY(path_check_table(c, w, "V", q.V, (size_t)q.M * S));
     ZIGP_TRY(path_check_table(c, w, "omega", q.omega, (size_t)q.R * D));
     ZIGP_TRY(path_check_table(c, w, "phase", q.phase, q.R));
     ZIGP_TRY(path_check_table(c, w, "amp", q.amp, (size_t)q.R * S));
-    if (q.lin && !path_all_finite(q.lin, D)) return fail_arg(c, (w + ": lin has a non-finite entry").c_str());
-    if (!std::isfinite(q.shift)) return fail_arg(c, (w + ": shift is not finite").c_str());
-    if (!(q.var > 0 && std::isfinite(q.var))) return fail_arg(c, (w + ": var must be positive and finite").c_str());
+    if (q.lin && !path_all_finite(q.lin, D)) return refuse(c, w, "lin has a non-finite entry");
+    if (!std::isfinite(q.shift)) return refuse(c, w, "shift is not finite");
+    if (!(q.var > 0 && std::isfinite(q.var))) return refuse(c, w, "var must be positive and finite");
     for (int d = 0; d < D; ++d)
-      if (!(q.ell[d] > 0)) return fail_arg(c, (w + ": ell must be positive").c_str());
+      if (!(q.ell[d] > 0)) return refuse(c, w, "ell must be positive");
   }
-  if (N > 0 && (!X || !out)) return fail_arg(c, (w + ": X or out is NULL").c_str());
+  if (N > 0 && (!X || !out)) return refuse(c, w, "X or out is NULL");
   if (N == 0) return ZIGP_OK;
   ZIGP_HIP(c, hipSetDevice(c->device));
   if (on_device) ZIGP_TRY(require_device_ptrs(c, {X, out}, (w + ": X and out must be device memory of the context's GPU").c_str()));
@@ -339,25 +341,19 @@ int path_rows(zigp_ctx* c, const char* who, const zigp_path_latent* lat, int nla
     a.var = q.var; a.shift = q.shift;
   }
   ZIGP_HIP(c, hipMemcpyAsync(c->path_tab.p, img, sizeof(double) * total, hipMemcpyHostToDevice, c->stream));
-  const double* dX = X;
-  double* dout = out;
-  if (!on_device) {
-    ZIGP_ENSURE(c, c->scratch, (size_t)N * D);
-    ZIGP_ENSURE(c, c->path_out, (size_t)nlat * S * N);
-    ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p, X, sizeof(double) * N * D, hipMemcpyHostToDevice, c->stream));
-    dX = c->scratch.p; dout = c->path_out.p;
-  }
+  const double* dX = nullptr;
+  ZIGP_TRY(stage_inputs(c, X, N, D, on_device, &dX));
+  if (!on_device) ZIGP_ENSURE(c, c->path_out, (size_t)nlat * S * N);
+  double* dout = on_device ? out : c->path_out.p;
   for (int h = 0; h < nlat; ++h) { pa.lat[h].X = dX; pa.lat[h].out = dout + (size_t)h * S * N; }
   ZIGP_TRY(path_launch(c, D, pa, nlat, nst));
-  if (!on_device) ZIGP_HIP(c, hipMemcpyAsync(out, dout, sizeof(double) * nlat * S * N, hipMemcpyDeviceToHost, c->stream));
-  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
-  return ZIGP_OK;
+  return finish_copies(c, {{on_device ? nullptr : out, dout, (size_t)nlat * S * N}});
 }
 
 int path_check_draw(zigp_ctx* c, const std::string& w, const char* tag, const zigp_path_draw* dr, int M, int D, int S) {
   const std::string t(tag);
-  if (!dr) return fail_arg(c, (w + ": draw_" + t + " is NULL").c_str());
-  if (dr->R < 0) return fail_arg(c, (w + ": draw_" + t + ": R is negative").c_str());
+  if (!dr) return refuse(c, w, "draw_" + t + " is NULL");
+  if (dr->R < 0) return refuse(c, w, "draw_" + t + ": R is negative");
   ZIGP_TRY(path_check_table(c, w, ("draw_" + t + ".omega0").c_str(), dr->omega0, (size_t)dr->R * D));
   ZIGP_TRY(path_check_table(c, w, ("draw_" + t + ".phase").c_str(), dr->phase, dr->R));
   ZIGP_TRY(path_check_table(c, w, ("draw_" + t + ".a").c_str(), dr->a, (size_t)dr->R * S));
@@ -387,8 +383,8 @@ int sample_paths(zigp_ctx* c, const char* who, const zigp_params* p, const doubl
   ZIGP_TRY(path_check_dims(c, w, D, S, N));
   ZIGP_TRY(path_check_draw(c, w, "f", draw_f, p->Mf, D, S));
   ZIGP_TRY(path_check_draw(c, w, "g", draw_g, p->Mg, D, S));
-  if (!std::isfinite(g_offset)) return fail_arg(c, (w + ": g_offset is not finite").c_str());
-  if (N > 0 && (!X || !out3)) return fail_arg(c, (w + ": Xnew or out3 is NULL").c_str());
+  if (!std::isfinite(g_offset)) return refuse(c, w, "g_offset is not finite");
+  if (N > 0 && (!X || !out3)) return refuse(c, w, "Xnew or out3 is NULL");
   if (N == 0) return ZIGP_OK;
   ZIGP_HIP(c, hipSetDevice(c->device));
   if (on_device) ZIGP_TRY(require_device_ptrs(c, {X, out3}, (w + ": Xnew and out3 must be device memory of the context's GPU").c_str()));
@@ -502,14 +498,10 @@ int sample_paths(zigp_ctx* c, const char* who, const zigp_params* p, const doubl
   }
 
   // the paths at Xnew: the context's mean function on f, g_offset on g
-  const double* dX = X;
-  double* dout = out3;
-  if (!on_device) {
-    ZIGP_ENSURE(c, c->scratch, (size_t)N * D);
-    ZIGP_ENSURE(c, c->path_out, (size_t)3 * S * N);
-    ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p, X, sizeof(double) * N * D, hipMemcpyHostToDevice, c->stream));
-    dX = c->scratch.p; dout = c->path_out.p;
-  }
+  const double* dX = nullptr;
+  ZIGP_TRY(stage_inputs(c, X, N, D, on_device, &dX));
+  if (!on_device) ZIGP_ENSURE(c, c->path_out, (size_t)3 * S * N);
+  double* dout = on_device ? out3 : c->path_out.p;
   for (int h = 0; h < 2; ++h) {
     PathLat& a = pa.lat[h];
     a.X = dX; a.N = N; a.out = dout + (size_t)h * S * N; a.ldo = N;
@@ -523,8 +515,7 @@ int sample_paths(zigp_ctx* c, const char* who, const zigp_params* p, const doubl
   const int64_t SN = (int64_t)S * N;
   hipLaunchKernelGGL(k_path_gf, dim3((unsigned)ceil_div(SN, 256)), dim3(256), 0, c->stream, dout, dout + SN, dout + 2 * SN, SN);
   ZIGP_HIP(c, hipGetLastError());
-  if (!on_device) ZIGP_HIP(c, hipMemcpyAsync(out3, dout, sizeof(double) * 3 * SN, hipMemcpyDeviceToHost, c->stream));
-  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  ZIGP_TRY(finish_copies(c, {{on_device ? nullptr : out3, dout, (size_t)3 * SN}}));
   prof_collect(c);
   return info_result(c, hinfo, "Kuu");
 }

@@ -27,13 +27,13 @@
 //   * a lane adds its own nodes in the order l, l + G, ... (fma onto the running sum), its pairs in the order e = l, l + G, ...;
 //   * the row's lanes are added by the xor tree of sc_sum (offsets G / 2, ..., 1);
 //   * CRPS = [tree of the lanes' sum_k w_k A(y - mu_k, s_k)] - [tree of the lanes' (pairs + sum_k w_k^2 sqrt(s_k / pi))];
-//   * the block's sum of CRPS adds its rows in row order; k_density_sum adds the blocks (its own fixed order).
+//   * the block's sum of CRPS adds its rows in row order; k_sum_partials adds the blocks (its own fixed order).
 // Quantile search (sc_quantile): r(t) = F(t) - p or (1 - p) - SF(t), increasing, r' = the density; bracket [lo, hi] kept around the sign
 // change of r; a Newton step where it lands strictly inside and shrinks fast enough, else the midpoint; ends when the step no longer
 // changes t or the bracket is one ulp wide, after SC_MAX_ITER evaluations at the latest.  Phi^-1(p) comes from the host (sc_ndtri).
 // Resources on gfx950 (-Rpass-analysis=kernel-resource-usage), VGPRs / LDS bytes per block / waves per SIMD, no scratch:
 // <ONOFF, 64> 118 / 24608 / 4, <ONOFF, 32> 98 / 6208 / 4, <GAUSSIAN, 64> 30 / 32 / 8.
-#include "zigp_host.h"
+#include "zigp_rows.h"
 #include <cmath>
 #include <cstdlib>
 
@@ -220,30 +220,11 @@ k_score_rows(ScoreArgs a) {
 
 namespace {
 
-// Layout of scratch2 during a score call, in doubles.  It starts at score_base(N), where the region of a density call on the same N
-// rows ends (DN_OFF_SUM's layout with the centre: the two calls' regions are disjoint): the rule's table in [0, 2 DN_MAXQ) (x, then w),
-// the sum at SC_OFF_SUM, the nb block partials from SC_OFF_PART, then, from the next multiple of 8, the (2, N) CDF pair, the
-// (n_levels, N) quantiles and the N CRPS values.
-constexpr size_t SC_OFF_SUM = 2 * DN_MAXQ, SC_OFF_PART = SC_OFF_SUM + 8;
-struct ScoreBufs { double* rule; double* sum; double* part; double* cdf2; double* quant; double* crps; int nb; };
-
-size_t score_base(int64_t N) { return ((DN_OFF_PART + (size_t)ceil_div(N, DN_THREADS) + 7) & ~(size_t)7) + (size_t)5 * N; }
-
 // Lanes per OnOff row: half a wave for a rule of at most SC_HALF_MAXQ nodes, else a whole one.  ZIGP_SCORE_WAVE_PER_ROW=1 in the
 // environment gives every rule a whole wave: the other arm of tools/score_time.py.
 int score_group(int n_quad) {
   const char* e = getenv("ZIGP_SCORE_WAVE_PER_ROW");
   return n_quad <= SC_HALF_MAXQ && !(e && e[0] == '1') ? 32 : 64;
-}
-
-int score_bufs(zigp_ctx* c, int lik, int n_quad, int64_t N, int n_levels, ScoreBufs& b) {
-  b.nb = ceil_div(N, lik != ZIGP_LIK_ONOFF ? SC_THREADS : score_group(n_quad) == 32 ? ScGeom<32>::ROWS : ScGeom<64>::ROWS);
-  const size_t base = score_base(N), off_out = (base + SC_OFF_PART + (size_t)b.nb + 7) & ~(size_t)7;
-  ZIGP_ENSURE(c, c->scratch2, off_out + (size_t)(3 + n_levels) * N);
-  double* p = c->scratch2.p;
-  b.rule = p + base; b.sum = p + base + SC_OFF_SUM; b.part = p + base + SC_OFF_PART;
-  b.cdf2 = p + off_out; b.quant = b.cdf2 + (size_t)2 * N; b.crps = b.quant + (size_t)n_levels * N;
-  return 0;
 }
 
 // Phi^-1(q) for q in (0, 1/2]: Acklam's rational start (relative error 1.2e-9), then Halley steps on erfc, whose relative accuracy
@@ -272,52 +253,53 @@ double sc_ndtri_lower(double q) {
 // Everything a score call refuses that is not a row pointer; touches nothing but the error text
 int score_check(zigp_ctx* c, const char* who, int lik, int64_t N, double noise, const double* nodes, const double* weights, int n_quad,
                 const double* levels, int n_levels, bool have_y, const double* cdf2, const double* quant, const double* crps, const double* crps_sum) {
-  const std::string w(who);
   if (lik == ZIGP_LIK_BERNOULLI)
-    return fail_arg(c, (w + ": the Bernoulli head has no density, so no CDF, quantile or CRPS: its CRPS is the Brier score (ymean - y)^2 of zigp_density_rows").c_str());
+    return refuse(c, who, "the Bernoulli head has no density, so no CDF, quantile or CRPS: its CRPS is the Brier score (ymean - y)^2 of zigp_density_rows");
   ZIGP_TRY(density_check(c, who, lik, N, noise, nodes, weights, n_quad));
-  if (n_levels < 0 || n_levels > SC_MAXL) return fail_arg(c, (w + ": n_levels must be in [0, 16] (ZIGP_SCORE_MAX_LEVELS)").c_str());
-  if (n_levels == 0 && (levels || quant)) return fail_arg(c, (w + ": n_levels is 0, so levels and quant must be NULL").c_str());
-  if (n_levels > 0 && (!levels || !quant)) return fail_arg(c, (w + ": levels or quant is NULL").c_str());
+  if (n_levels < 0 || n_levels > SC_MAXL) return refuse(c, who, "n_levels must be in [0, 16] (ZIGP_SCORE_MAX_LEVELS)");
+  if (n_levels == 0 && (levels || quant)) return refuse(c, who, "n_levels is 0, so levels and quant must be NULL");
+  if (n_levels > 0 && (!levels || !quant)) return refuse(c, who, "levels or quant is NULL");
   for (int l = 0; l < n_levels; ++l)
-    if (!(levels[l] > 0.0 && levels[l] < 1.0)) return fail_arg(c, (w + ": levels must be finite and strictly inside (0, 1)").c_str());
-  if (!have_y && (cdf2 || crps || crps_sum)) return fail_arg(c, (w + ": y (Ynew) is NULL, so cdf2, crps and crps_sum must be NULL").c_str());
+    if (!(levels[l] > 0.0 && levels[l] < 1.0)) return refuse(c, who, "levels must be finite and strictly inside (0, 1)");
+  if (!have_y && (cdf2 || crps || crps_sum)) return refuse(c, who, "y (Ynew) is NULL, so cdf2, crps and crps_sum must be NULL");
   return 0;
 }
 
-// The rule's table to the device (OnOff), the levels into the arguments, the rows kernel and -- where the CRPS is asked for -- the sum
-// kernel; the caller has synchronised whatever wrote the rows, and collects *hsum (NULL without the CRPS) with its own synchronisation
-int score_run(zigp_ctx* c, int lik, ScoreArgs a, const ScoreBufs& b, const double* nodes, const double* weights, const double* levels, double** hsum) {
-  if (lik == ZIGP_LIK_ONOFF) {
-    const int nq = a.n_quad;
-    ZIGP_PINNED(c, h, 2 * (size_t)nq);
-    for (int i = 0; i < nq; ++i) { h[i] = nodes[i]; h[nq + i] = weights[i]; }
-    ZIGP_HIP(c, hipMemcpyAsync(b.rule, h, sizeof(double) * 2 * nq, hipMemcpyHostToDevice, c->stream));
-  }
-  for (int l = 0; l < a.n_levels; ++l) {
+// The tail of every score call, behind either source of rows (zigp_rows.h): the regions of scratch2, the rule's table (OnOff: nodes, then
+// weights), the levels into the arguments, the rows kernel, the sum where the CRPS is asked for, and the outputs.  on_device: cdf2, quant
+// and crps are written in place.  The regions, in allocation order, each from a multiple of 8 doubles: the rule's table, the sum, the block
+// partials, the (2, N) CDF pair, the (n_levels, N) quantiles, the N CRPS values -- from 0, like a density call's: neither outlives its call.
+int score_run(zigp_ctx* c, int lik, const PredRows& r, double noise, const double* nodes, const double* weights, int n_quad, const double* levels,
+              int n_levels, double* cdf2, double* quant, double* crps, bool on_device, double* crps_sum) {
+  const bool onoff = lik == ZIGP_LIK_ONOFF;
+  const int64_t N = r.N;
+  const int group = onoff ? score_group(n_quad) : 0;
+  const int nb = ceil_div(N, !onoff ? SC_THREADS : group == 32 ? ScGeom<32>::ROWS : ScGeom<64>::ROWS);
+  RowArena ar(c->scratch2, "c->scratch2");
+  const size_t o_rule = ar.take(onoff ? (size_t)2 * n_quad : 0), o_sum = ar.take(1), o_part = ar.take(nb);
+  const size_t o_cdf = ar.take((size_t)2 * N), o_quant = ar.take((size_t)n_levels * N), o_crps = ar.take(N);
+  ZIGP_TRY(ar.commit(c));
+  if (onoff) ZIGP_TRY(upload_rule(c, ar.at(o_rule), nodes, weights, n_quad, RuleForm::X_W));
+  ScoreArgs a{};
+  a.fm = r.fm; a.fv = r.fv; a.gm = r.gm; a.gv = r.gv; a.y = r.y;
+  a.N = N; a.noise = noise; a.rule = ar.at(o_rule); a.n_quad = onoff ? n_quad : 0; a.n_levels = n_levels; a.ld = N; a.part = ar.at(o_part);
+  for (int l = 0; l < n_levels; ++l) {
     const bool lower = levels[l] <= 0.5;
     const double q = lower ? levels[l] : 1.0 - levels[l], z = sc_ndtri_lower(q);   // 1 - p is exact for p > 1/2
     a.lev_q[l] = q; a.lev_z[l] = lower ? z : -z; a.lev_lower[l] = lower ? 1 : 0;
   }
-  a.rule = b.rule; a.part = b.part;
-  const dim3 grid(b.nb), block(SC_THREADS);
-  if (lik == ZIGP_LIK_ONOFF && score_group(a.n_quad) == 32) hipLaunchKernelGGL((k_score_rows<ZIGP_LIK_ONOFF, 32>), grid, block, 0, c->stream, a);
-  else if (lik == ZIGP_LIK_ONOFF) hipLaunchKernelGGL((k_score_rows<ZIGP_LIK_ONOFF, 64>), grid, block, 0, c->stream, a);
+  a.cdf2 = out_target(cdf2, on_device, ar.at(o_cdf)); a.quant = out_target(quant, on_device, ar.at(o_quant));
+  a.crps = out_target(crps, on_device, ar.at(o_crps));
+  a.want_crps = (crps || crps_sum) ? 1 : 0;
+  const dim3 grid(nb), block(SC_THREADS);
+  if (group == 32) hipLaunchKernelGGL((k_score_rows<ZIGP_LIK_ONOFF, 32>), grid, block, 0, c->stream, a);
+  else if (onoff) hipLaunchKernelGGL((k_score_rows<ZIGP_LIK_ONOFF, 64>), grid, block, 0, c->stream, a);
   else hipLaunchKernelGGL((k_score_rows<ZIGP_LIK_GAUSSIAN, 64>), grid, block, 0, c->stream, a);
   ZIGP_HIP(c, hipGetLastError());
-  *hsum = nullptr;
-  if (!a.want_crps) return 0;
-  hipLaunchKernelGGL(k_density_sum, dim3(1), dim3(DN_THREADS), 0, c->stream, b.part, b.nb, b.sum);
-  ZIGP_HIP(c, hipGetLastError());
-  return download(c, b.sum, 1, hsum);
-}
-
-// The end of every score call: the rows that were asked for on the host (NULL: nothing to copy), the stream's synchronisation, the sum
-int score_finish(zigp_ctx* c, const ScoreBufs& b, int64_t N, int n_levels, double* cdf2, double* quant, double* crps, const double* hsum, double* crps_sum) {
-  if (cdf2) ZIGP_HIP(c, hipMemcpyAsync(cdf2, b.cdf2, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, c->stream));
-  if (quant) ZIGP_HIP(c, hipMemcpyAsync(quant, b.quant, sizeof(double) * n_levels * N, hipMemcpyDeviceToHost, c->stream));
-  if (crps) ZIGP_HIP(c, hipMemcpyAsync(crps, b.crps, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
-  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  double* hsum = nullptr;
+  if (a.want_crps) ZIGP_TRY(sum_partials(c, a.part, nb, ar.at(o_sum), &hsum));
+  ZIGP_TRY(finish_copies(c, {{on_device ? nullptr : cdf2, ar.at(o_cdf), (size_t)2 * N}, {on_device ? nullptr : quant, ar.at(o_quant), (size_t)n_levels * N},
+                             {on_device ? nullptr : crps, ar.at(o_crps), (size_t)N}}));
   if (crps_sum) *crps_sum = hsum[0];
   return ZIGP_OK;
 }
@@ -328,26 +310,14 @@ int score_rows(zigp_ctx* c, const char* who, int lik, const double* fm, const do
   if (!c) return ZIGP_EARG;
   ZIGP_TRY(score_check(c, who, lik, N, noise, nodes, weights, n_quad, levels, n_levels, y != nullptr, cdf2, quant, crps, crps_sum));
   const bool onoff = lik == ZIGP_LIK_ONOFF;
-  if (N > 0 && (!fm || !fv || (onoff && (!gm || !gv)))) return fail_arg(c, (std::string(who) + ": a row pointer (fm, fv, gm, gv) is NULL").c_str());
+  if (N > 0 && (!fm || !fv || (onoff && (!gm || !gv)))) return refuse(c, who, "a row pointer (fm, fv, gm, gv) is NULL");
   if (N == 0) { if (crps_sum) *crps_sum = 0.0; return ZIGP_OK; }
   if (!cdf2 && !quant && !crps && !crps_sum) return ZIGP_OK;
   ZIGP_HIP(c, hipSetDevice(c->device));
   ZIGP_TRY(begin_staged_call(c));
-  ScoreBufs b;
-  ZIGP_TRY(score_bufs(c, lik, n_quad, N, n_levels, b));
-  ZIGP_ENSURE(c, c->scratch, (size_t)5 * N);
-  double* d = c->scratch.p;
-  const double* src[5] = {fm, fv, y, gm, gv};
-  for (int k = 0; k < (onoff ? 5 : 3); ++k)
-    if (src[k]) ZIGP_HIP(c, hipMemcpyAsync(d + k * N, src[k], sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
-  ScoreArgs a{};
-  a.fm = d; a.fv = d + N; a.y = y ? d + 2 * N : nullptr; a.gm = onoff ? d + 3 * N : nullptr; a.gv = onoff ? d + 4 * N : nullptr;
-  a.N = N; a.noise = noise; a.n_quad = onoff ? n_quad : 0; a.n_levels = n_levels; a.ld = N;
-  a.cdf2 = cdf2 ? b.cdf2 : nullptr; a.quant = quant ? b.quant : nullptr; a.crps = crps ? b.crps : nullptr;
-  a.want_crps = (crps || crps_sum) ? 1 : 0;
-  double* hsum = nullptr;
-  ZIGP_TRY(score_run(c, lik, a, b, nodes, weights, levels, &hsum));
-  return score_finish(c, b, N, n_levels, cdf2, quant, crps, hsum, crps_sum);
+  PredRows r;
+  ZIGP_TRY(rows_from_host(c, onoff, fm, fv, gm, gv, y, N, r));
+  return score_run(c, lik, r, noise, nodes, weights, n_quad, levels, n_levels, cdf2, quant, crps, false, crps_sum);
 }
 
 // The two zigp_predict_scores* entries.  on_device: X (N, D), Y (N) and the three outputs are device memory, read and written in place;
@@ -358,36 +328,16 @@ int predict_scores(zigp_ctx* c, const char* who, const zigp_params* p, const dou
   if (!c) return ZIGP_EARG;
   ZIGP_TRY(validate_params(c, p));
   ZIGP_TRY(score_check(c, who, ZIGP_LIK_ONOFF, N, p->noise, nodes, weights, n_quad, levels, n_levels, Y != nullptr, cdf2, quant, crps, crps_sum));
-  if (N > 0 && !X) return fail_arg(c, (std::string(who) + ": Xnew is NULL").c_str());
+  if (N > 0 && !X) return refuse(c, who, "Xnew is NULL");
   if (N == 0) { if (crps_sum) *crps_sum = 0.0; return ZIGP_OK; }
   if (!cdf2 && !quant && !crps && !crps_sum) return ZIGP_OK;
   ZIGP_HIP(c, hipSetDevice(c->device));
-  if (on_device) {
+  if (on_device)
     ZIGP_TRY(require_device_ptrs(c, {X, Y, cdf2, quant, crps},
                                  (std::string(who) + ": Xnew, Ynew, cdf2, quant and crps must be device memory of the context's GPU").c_str()));
-  } else {
-    const size_t nx = ((size_t)N * p->D + 7) & ~(size_t)7;
-    ZIGP_ENSURE(c, c->scratch, nx + (size_t)N);
-    ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p, X, sizeof(double) * N * p->D, hipMemcpyHostToDevice, c->stream));
-    if (Y) ZIGP_HIP(c, hipMemcpyAsync(c->scratch.p + nx, Y, sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
-    X = c->scratch.p;
-    if (Y) Y = c->scratch.p + nx;
-  }
-  ScoreBufs b;
-  ZIGP_TRY(score_bufs(c, ZIGP_LIK_ONOFF, n_quad, N, n_levels, b));
-  ZIGP_ENSURE(c, c->out9, (size_t)9 * N);
-  ZIGP_TRY(run_dense(c, p, X, nullptr, N, p->D, jitter, 1.0, g_offset, 0, N, 0, true, c->out9.p, nullptr, nullptr, nullptr));   // complete on return
-  const double* r = c->out9.p;
-  ScoreArgs a{};
-  a.fm = r + 3 * N; a.fv = r + 4 * N; a.gm = r + 5 * N; a.gv = r + 6 * N; a.y = Y;
-  a.N = N; a.noise = p->noise; a.n_quad = n_quad; a.n_levels = n_levels; a.ld = N;
-  a.cdf2 = !cdf2 ? nullptr : on_device ? cdf2 : b.cdf2;
-  a.quant = !quant ? nullptr : on_device ? quant : b.quant;
-  a.crps = !crps ? nullptr : on_device ? crps : b.crps;
-  a.want_crps = (crps || crps_sum) ? 1 : 0;
-  double* hsum = nullptr;
-  ZIGP_TRY(score_run(c, ZIGP_LIK_ONOFF, a, b, nodes, weights, levels, &hsum));
-  return score_finish(c, b, N, n_levels, on_device ? nullptr : cdf2, on_device ? nullptr : quant, on_device ? nullptr : crps, hsum, crps_sum);
+  PredRows r;
+  ZIGP_TRY(rows_from_predict(c, p, X, Y, N, jitter, g_offset, on_device, r));
+  return score_run(c, ZIGP_LIK_ONOFF, r, p->noise, nodes, weights, n_quad, levels, n_levels, cdf2, quant, crps, on_device, crps_sum);
 }
 
 }  // namespace

@@ -448,14 +448,41 @@ class DenseEngine:
                                                                     float(np.squeeze(0.0 if b is None else b))))
         return a.size
 
-    def predict(self, p, Xnew, jitter=1e-6, g_offset=0.0):
-        """(9,N) array in the order of OnOffSVGP.build_predict (onoffgpf/OnOffSVGP.py:152)."""
-        pk = _Packed(p)
+    # ---- what the predict-like calls share: predict, density, scores, sample paths ----
+    def _prepare(self, p, pk=None):
+        """the packed parameters of p (pk when the caller has packed them already), with the mean function and the modes set from p"""
+        pk = _Packed(p) if pk is None else pk
         self._set_mean_function(p, pk.D)
         self._set_modes(p)
+        return pk
+
+    def _device_f64(self, t):
+        """True for a contiguous float64 tensor on the engine's device"""
+        import torch
+        return t.is_cuda and t.device.index == self.device and t.dtype == torch.float64 and t.is_contiguous()
+
+    @staticmethod
+    def _host_xy(pk, Xnew, Ynew=None, with_y=False):
+        """Xnew as a float64 (N, D) array and Ynew as N entries (None stays None); with_y: the refusal names Ynew too"""
         Xnew = as_f64(Xnew)
-        if Xnew.ndim != 2 or Xnew.shape[1] != pk.D:
-            raise ValueError('Xnew must be (N,%d)' % pk.D)
+        Ynew = None if Ynew is None else as_f64(Ynew).reshape(-1)
+        if Xnew.ndim != 2 or Xnew.shape[1] != pk.D or (Ynew is not None and Ynew.size != Xnew.shape[0]):
+            raise ValueError('Xnew must be (N,%d)' % pk.D + (' and Ynew must have N entries' if with_y else ''))
+        return Xnew, Ynew
+
+    def _device_xy(self, who, pk, X_t, Y_t=None):
+        """N of the device rows X_t (N, D) and Y_t (N entries, or None), refused under the method's name `who`"""
+        if not (self._device_f64(X_t) and X_t.dim() == 2 and X_t.shape[1] == pk.D):
+            raise ValueError('%s: X needs a contiguous float64 (N,%d) tensor on cuda:%d' % (who, pk.D, self.device))
+        N = int(X_t.shape[0])
+        if Y_t is not None and not (self._device_f64(Y_t) and Y_t.numel() == N):
+            raise ValueError('%s: Y needs a contiguous float64 tensor of N entries on cuda:%d' % (who, self.device))
+        return N
+
+    def predict(self, p, Xnew, jitter=1e-6, g_offset=0.0):
+        """(9,N) array in the order of OnOffSVGP.build_predict (onoffgpf/OnOffSVGP.py:152)."""
+        pk = self._prepare(p)
+        Xnew, _ = self._host_xy(pk, Xnew)
         out = np.zeros((9, Xnew.shape[0]))
         _check(self.lib, self.ctx, self.lib.zigp_predict(self.ctx, C.byref(pk.struct), ptr(Xnew), Xnew.shape[0], float(jitter),
                                                           float(g_offset), ptr(out)))
@@ -465,15 +492,13 @@ class DenseEngine:
         """predict on a torch CUDA float64 tensor (N,D) of the engine's device; returns (or fills `out` with) a (9,N) CUDA tensor in the
         order of OnOffSVGP.build_predict -- nothing but the parameters crosses PCIe."""
         import torch
-        pk = _Packed(p)
-        self._set_mean_function(p, pk.D)
-        self._set_modes(p)
-        if not (X_t.is_cuda and X_t.device.index == self.device and X_t.dtype == torch.float64 and X_t.is_contiguous() and X_t.dim() == 2 and X_t.shape[1] == pk.D):
+        pk = self._prepare(p)
+        if not (self._device_f64(X_t) and X_t.dim() == 2 and X_t.shape[1] == pk.D):
             raise ValueError('predict_device: need a contiguous float64 (N,%d) tensor on cuda:%d' % (pk.D, self.device))
         N = int(X_t.shape[0])
         if out is None:
             out = torch.empty((9, N), dtype=torch.float64, device=X_t.device)
-        elif not (out.is_cuda and out.device.index == self.device and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (9, N)):
+        elif not (self._device_f64(out) and tuple(out.shape) == (9, N)):
             raise ValueError('predict_device: out must be a contiguous float64 (9,N) tensor on the same device')
         torch.cuda.current_stream(self.device).synchronize()      # the engine's streams are not ordered after torch's
         if N:
@@ -545,12 +570,8 @@ class DenseEngine:
         Returns ((3, N) array: logp, ymean, yvar; sum of logp); rows_out=False asks for the sum alone (None in place of the array).
         centre and return_centre: as density_rows."""
         mode = self._centre(centre)
-        pk = _Packed(p)
-        self._set_mean_function(p, pk.D)
-        self._set_modes(p)
-        Xnew, Ynew = as_f64(Xnew), as_f64(Ynew).reshape(-1)
-        if Xnew.ndim != 2 or Xnew.shape[1] != pk.D or Ynew.size != Xnew.shape[0]:
-            raise ValueError('Xnew must be (N,%d) and Ynew must have N entries' % pk.D)
+        pk = self._prepare(p)
+        Xnew, Ynew = self._host_xy(pk, Xnew, as_f64(Ynew), True)
         x, w = self._rule(n_quad, rule)
         N = Xnew.shape[0]
         out = np.zeros((3, N)) if rows_out else None
@@ -568,20 +589,11 @@ class DenseEngine:
         centre and return_centre: as density_rows, the (2, N) centre a CUDA tensor."""
         import torch
         mode = self._centre(centre)
-        pk = _Packed(p)
-        self._set_mean_function(p, pk.D)
-        self._set_modes(p)
-
-        def ok(t):
-            return t.is_cuda and t.device.index == self.device and t.dtype == torch.float64 and t.is_contiguous()
-        if not (ok(X_t) and X_t.dim() == 2 and X_t.shape[1] == pk.D):
-            raise ValueError('predict_density_device: X needs a contiguous float64 (N,%d) tensor on cuda:%d' % (pk.D, self.device))
-        N = int(X_t.shape[0])
-        if not (ok(Y_t) and Y_t.numel() == N):
-            raise ValueError('predict_density_device: Y needs a contiguous float64 tensor of N entries on cuda:%d' % self.device)
+        pk = self._prepare(p)
+        N = self._device_xy('predict_density_device', pk, X_t, Y_t)
         if out is None:
             out = torch.empty((3, N), dtype=torch.float64, device=X_t.device)
-        elif not (ok(out) and tuple(out.shape) == (3, N)):
+        elif not (self._device_f64(out) and tuple(out.shape) == (3, N)):
             raise ValueError('predict_density_device: out must be a contiguous float64 (3,N) tensor on the same device')
         x, w = self._rule(n_quad, rule)
         total = np.zeros(1)
@@ -611,6 +623,13 @@ class DenseEngine:
         return {'cdf': None if cdf2 is None else cdf2[0], 'sf': None if cdf2 is None else cdf2[1], 'quantiles': quant, 'crps': crps,
                 'crps_sum': None if total is None else float(total[0])}
 
+    @staticmethod
+    def _score_outputs(new, N, lv, have_y, cdf, crps):
+        """(cdf2, quant, crps, total) of a score call, None where the call does not ask for it; new(*shape): a zeroed array or tensor"""
+        want = have_y and crps
+        return (new(2, N) if have_y and cdf else None, None if lv is None else new(lv.size, N), new(N) if want else None,
+                np.zeros(1) if want else None)
+
     def score_rows(self, lik, fm, fv, gm, gv, y, noise, n_quad=64, rule=None, levels=(), cdf=True, crps=True):
         """CDF pair, quantiles and CRPS of y under rows of a predict call, as a dict: 'cdf' and 'sf' (N) = F(y) and SF(y), each its own sum;
         'quantiles' (L, N), one row per level of `levels` in the caller's order; 'crps' (N) and 'crps_sum'.  A key is None where that
@@ -628,11 +647,7 @@ class DenseEngine:
             raise ValueError('score_rows: fm, fv, gm, gv and y must have the same length')
         x, w = self._rule(n_quad, rule) if onoff else (None, None)
         lv = self._levels(levels)
-        have_y = rows[4] is not None
-        cdf2 = np.zeros((2, N)) if have_y and cdf else None
-        quant = None if lv is None else np.zeros((lv.size, N))
-        out = np.zeros(N) if have_y and crps else None
-        total = np.zeros(1) if have_y and crps else None
+        cdf2, quant, out, total = self._score_outputs(lambda *shape: np.zeros(shape), N, lv, rows[4] is not None, cdf, crps)
         _check(self.lib, self.ctx, self.lib.zigp_score_rows(self.ctx, lik, *[self._opt(a) for a in rows], N, float(noise), self._opt(x), self._opt(w),
                                                             0 if x is None else x.size, self._opt(lv), 0 if lv is None else lv.size,
                                                             self._opt(cdf2), self._opt(quant), self._opt(out), self._opt(total)))
@@ -640,21 +655,12 @@ class DenseEngine:
 
     def predict_scores(self, p, Xnew, Ynew=None, jitter=1e-6, g_offset=0.0, n_quad=64, rule=None, levels=(), cdf=True, crps=True):
         """Scores of the dense OnOff model: predict at Xnew (N, D), then score_rows' dict for Ynew (N, or None) under its rows, on the device."""
-        pk = _Packed(p)
-        self._set_mean_function(p, pk.D)
-        self._set_modes(p)
-        Xnew = as_f64(Xnew)
-        Ynew = None if Ynew is None else as_f64(Ynew).reshape(-1)
-        if Xnew.ndim != 2 or Xnew.shape[1] != pk.D or (Ynew is not None and Ynew.size != Xnew.shape[0]):
-            raise ValueError('Xnew must be (N,%d) and Ynew must have N entries' % pk.D)
+        pk = self._prepare(p)
+        Xnew, Ynew = self._host_xy(pk, Xnew, Ynew, True)
         x, w = self._rule(n_quad, rule)
         lv = self._levels(levels)
         N = Xnew.shape[0]
-        have_y = Ynew is not None
-        cdf2 = np.zeros((2, N)) if have_y and cdf else None
-        quant = None if lv is None else np.zeros((lv.size, N))
-        out = np.zeros(N) if have_y and crps else None
-        total = np.zeros(1) if have_y and crps else None
+        cdf2, quant, out, total = self._score_outputs(lambda *shape: np.zeros(shape), N, lv, Ynew is not None, cdf, crps)
         _check(self.lib, self.ctx, self.lib.zigp_predict_scores(self.ctx, C.byref(pk.struct), ptr(Xnew), self._opt(Ynew), N, float(jitter), float(g_offset),
                                                                 ptr(x), ptr(w), x.size, self._opt(lv), 0 if lv is None else lv.size,
                                                                 self._opt(cdf2), self._opt(quant), self._opt(out), self._opt(total)))
@@ -664,27 +670,12 @@ class DenseEngine:
         """predict_scores on torch CUDA float64 tensors X_t (N, D) and Y_t (N) or (N, 1) (or None) of the engine's device; the dict's arrays
         are CUDA tensors, 'crps_sum' a float -- nothing but the parameters, the rule, the levels and the sum crosses PCIe."""
         import torch
-        pk = _Packed(p)
-        self._set_mean_function(p, pk.D)
-        self._set_modes(p)
-
-        def ok(t):
-            return t.is_cuda and t.device.index == self.device and t.dtype == torch.float64 and t.is_contiguous()
-        if not (ok(X_t) and X_t.dim() == 2 and X_t.shape[1] == pk.D):
-            raise ValueError('predict_scores_device: X needs a contiguous float64 (N,%d) tensor on cuda:%d' % (pk.D, self.device))
-        N = int(X_t.shape[0])
-        if Y_t is not None and not (ok(Y_t) and Y_t.numel() == N):
-            raise ValueError('predict_scores_device: Y needs a contiguous float64 tensor of N entries on cuda:%d' % self.device)
+        pk = self._prepare(p)
+        N = self._device_xy('predict_scores_device', pk, X_t, Y_t)
         x, w = self._rule(n_quad, rule)
         lv = self._levels(levels)
-        have_y = Y_t is not None
-
-        def new(*shape):
-            return torch.zeros(shape, dtype=torch.float64, device=X_t.device)
-        cdf2 = new(2, N) if have_y and cdf else None
-        quant = None if lv is None else new(lv.size, N)
-        out = new(N) if have_y and crps else None
-        total = np.zeros(1) if have_y and crps else None
+        cdf2, quant, out, total = self._score_outputs(lambda *shape: torch.zeros(shape, dtype=torch.float64, device=X_t.device), N, lv,
+                                                      Y_t is not None, cdf, crps)
         D = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
         torch.cuda.current_stream(self.device).synchronize()      # the engine's streams are not ordered after torch's
         _check(self.lib, self.ctx, self.lib.zigp_predict_scores_device(self.ctx, C.byref(pk.struct), D(X_t), D(Y_t), N, float(jitter), float(g_offset),
@@ -749,16 +740,13 @@ class DenseEngine:
         """path_rows on a torch CUDA float64 tensor (N, D) of the engine's device; returns (or fills `out`, whose first nlat S N
         entries are the (nlat, S, N) result) a CUDA tensor."""
         import torch
-
-        def ok(t):
-            return t.is_cuda and t.device.index == self.device and t.dtype == torch.float64 and t.is_contiguous()
-        if not (ok(X_t) and X_t.dim() == 2):
+        if not (self._device_f64(X_t) and X_t.dim() == 2):
             raise ValueError('path_rows_device: X needs a contiguous float64 (N, D) tensor on cuda:%d' % self.device)
         N, D = int(X_t.shape[0]), int(X_t.shape[1])
         recs, keep = self._path_latents(lats, D, int(S))
         if out is None:
             out = torch.empty((len(lats), int(S), N), dtype=torch.float64, device=X_t.device)
-        elif not (ok(out) and out.numel() >= len(lats) * int(S) * N):
+        elif not (self._device_f64(out) and out.numel() >= len(lats) * int(S) * N):
             raise ValueError('path_rows_device: out must be a contiguous float64 tensor of at least nlat S N entries on the same device')
         torch.cuda.current_stream(self.device).synchronize()      # the engine's streams are not ordered after torch's
         _check(self.lib, self.ctx, self.lib.zigp_path_rows_device(self.ctx, C.cast(recs, C.c_void_p), len(lats), D, int(S),
@@ -793,12 +781,9 @@ class DenseEngine:
         the same paths at other inputs or other hyperparameters (n_samples and the model's M must match them).  p is read as predict
         reads it (whiten, q_diag, kern_f / kern_g, mean_a / mean_b).  D <= 8, 1 <= n_samples <= 256."""
         pk = _Packed(p)
-        Xnew = as_f64(Xnew)
-        if Xnew.ndim != 2 or Xnew.shape[1] != pk.D:
-            raise ValueError('Xnew must be (N,%d)' % pk.D)
+        Xnew, _ = self._host_xy(pk, Xnew)
         draws, recs, keep = self._path_draws(pk, pk.kinds, n_samples, n_features, rng, draws)
-        self._set_mean_function(p, pk.D)
-        self._set_modes(p)
+        self._prepare(p, pk)      # behind the draws' checks: a refused draw leaves the context's modes as they were
         S, N = int(n_samples), Xnew.shape[0]
         out = np.zeros((3, S, N))
         _check(self.lib, self.ctx, self.lib.zigp_sample_paths(self.ctx, C.byref(pk.struct), ptr(Xnew), N, float(jitter), float(g_offset),
@@ -810,18 +795,13 @@ class DenseEngine:
         (`out` when given) -- nothing but the parameters and the draws crosses PCIe."""
         import torch
         pk = _Packed(p)
-
-        def ok(t):
-            return t.is_cuda and t.device.index == self.device and t.dtype == torch.float64 and t.is_contiguous()
-        if not (ok(X_t) and X_t.dim() == 2 and X_t.shape[1] == pk.D):
-            raise ValueError('sample_paths_device: X needs a contiguous float64 (N,%d) tensor on cuda:%d' % (pk.D, self.device))
+        N = self._device_xy('sample_paths_device', pk, X_t)
         draws, recs, keep = self._path_draws(pk, pk.kinds, n_samples, n_features, rng, draws)
-        self._set_mean_function(p, pk.D)
-        self._set_modes(p)
-        S, N = int(n_samples), int(X_t.shape[0])
+        self._prepare(p, pk)
+        S = int(n_samples)
         if out is None:
             out = torch.empty((3, S, N), dtype=torch.float64, device=X_t.device)
-        elif not (ok(out) and tuple(out.shape) == (3, S, N)):
+        elif not (self._device_f64(out) and tuple(out.shape) == (3, S, N)):
             raise ValueError('sample_paths_device: out must be a contiguous float64 (3,S,N) tensor on the same device')
         torch.cuda.current_stream(self.device).synchronize()      # the engine's streams are not ordered after torch's
         if N:
@@ -871,7 +851,7 @@ class DenseEngine:
         """kmeans on a torch CUDA float64 tensor (N, ld) of the engine's device (zigp_kmeans_device): the rows stay where they are, the
         centroids and the info come back as host arrays."""
         import torch
-        if not (X_t.is_cuda and X_t.device.index == self.device and X_t.dtype == torch.float64 and X_t.is_contiguous() and X_t.dim() == 2):
+        if not (self._device_f64(X_t) and X_t.dim() == 2):
             raise ValueError('kmeans_device: X needs a contiguous float64 (N, ld) tensor on cuda:%d' % self.device)
         N, ld = int(X_t.shape[0]), int(X_t.shape[1])
         col0, D, Cm, out = self._kmeans_args(N, ld, M, init, seed, max_iter, cols,
