@@ -305,6 +305,62 @@ int zigp_test_kron_da(zigp_ctx* ctx, int32_t M, int64_t Nc, const double* A, con
 int zigp_test_kron_kgrad(zigp_ctx* ctx, int32_t M, int32_t D, int64_t N, int64_t Nc, int32_t ldx, int32_t col0, const double* B, const double* A,
                          const double* PdA, const double* K, const double* gm, const double* dq, const double* X, const double* Z, double* krow);
 
+/* ---- Fused Kronecker path (csrc/zigp_kronf.hip, zigp_kronl.h): ONE ordinary value-and-gradient step through the host code of
+ * zigp_kron_elbo / zigp_kron_head_elbo itself -- same plan, launches, grids and device buffers, zigp_set_kron_range_tiles honoured -- with
+ * device buffers snapshot around it.  Every tap is optional (NULL: not taken); a tap is a stream-ordered device-to-device copy enqueued
+ * right after the launch that produces the value, downloaded when the step has finished, so a later kernel that reuses the buffer cannot
+ * matter.  The caller sizes the host arrays: Mq_p = M_p rounded up to 16 (the latent's OWN padded sizes), nb_p = Mq_p / 16,
+ * Npad = max(1024, N rounded up to 1024); the capacity (nb0c, nb1c) is (2, 2) when every M_p <= 32, else (1, 7) (M0 <= 16, M1 <= 112).
+ * Returns ZIGP_EARG for a grid beyond the fused kernels, or one forced onto the panel path (zigp_set_kron_panels). ---- */
+typedef struct zigp_kronf_tap_factor {   /* after k_kf_factor */
+  double* K;      /* [128][128] K_p + jitter I; only the leading [R][R] part is written, R = M_p rounded up to 32, identity-padded beyond M_p */
+  double* P;      /* [Mq][Mq] row-major K_p^-1, zero rows / columns >= M_p */
+  double* PF;     /* [Mq * Mq] raw: P in A-fragment order, F[(rb * (Mq / 4) + ks) * 64 + lane] = P(16 rb + lane % 16, 4 ks + lane / 16) */
+  double* dvec;   /* [Mq + 1]: diag(P), then logdet K_p */
+  double* Zs;     /* [Mq][D_p] inducing inputs times 1 / ell, zero rows >= M_p */
+  double* zc;     /* [D_p] centre of the moment sums: the mid-range of the inducing inputs */
+} zigp_kronf_tap_factor;
+typedef struct zigp_kronf_tap_latent {
+  zigp_kronf_tap_factor fac[2];
+  double *U, *S2, *T0, *T1, *Al;       /* after k_kf_latent / k_kfl_latent: [Mq0][Mq1] row-major each, zero padded: u, s^2, U P1, P0 U, P0 U P1 */
+  double *AlF, *S2F, *AlTF, *S2TF;     /* [Mq0 * Mq1] raw fragment images of Al, S2 ([nb0][Mq1 / 4][64]) and of their transposes ([nb1][Mq0 / 4][64]) */
+  double* part;    /* after the forward kernel: [4][Npad] = q0, q1, mean, S-term */
+  double* cot;     /* after the point-wise kernel (before any injection): [4][Npad] = gm, gv, dq0, dq1 */
+  double* work;    /* after k_kf_reduce: the latent's whole work block, capacity rows and columns included.  With R_p = 16 nb_pc and
+                      ldw = max(R0, R1):  dAl [R0][ldw] | dS2 [R0][ldw] | dP0 [R0][ldw] | dP1 [R1][ldw] | Kr0 [R0][16] | Kr1 [R1][16]
+                      (sums over points, unsymmetrised dP_p = sum E_p K_p^T; Kr_p[m][j] = sum_n t_p[m, n] psi_j(x_n), psi = {1, x - zc, (x - zc)^2}) */
+  const double* inject;   /* in, optional: [4][N] copied over gm, gv, dq0, dq1 between the point-wise launch and the backward launch; rows >= N keep
+                             what the point-wise kernel wrote */
+} zigp_kronf_tap_latent;
+/* facts[] of zigp_test_kron_fused_step */
+enum { ZIGP_KFF_LARGE = 0,     /* 1: the larger-grid kernels (k_kfl_*), 0: the small-grid ones (k_kf_*) */
+       ZIGP_KFF_LARGE_EXACT,   /* 1: the larger-grid instantiation with compile-time block counts */
+       ZIGP_KFF_NB0C, ZIGP_KFF_NB1C,                                      /* capacity block counts */
+       ZIGP_KFF_NB0_F, ZIGP_KFF_NB1_F, ZIGP_KFF_NB0_G, ZIGP_KFF_NB1_G,    /* each latent's own block counts (a head: g = f) */
+       ZIGP_KFF_NPAD, ZIGP_KFF_NTILES,
+       ZIGP_KFF_TPW_FWD,       /* tiles per wave of the forward launch */
+       ZIGP_KFF_TPW_BWD,       /* tiles per wave of the backward launch (larger grids: of its first row range) */
+       ZIGP_KFF_NPARTS,        /* partial accumulators k_kf_reduce sums per latent */
+       ZIGP_KFF_TPS,           /* larger grids: tiles per part of k_kfl_accum (0: small grids) */
+       ZIGP_KFF_NRANGES,       /* larger grids: row ranges = backward + accumulate launch pairs (1: small grids) */
+       ZIGP_KFF_RANGE_TILES,   /* larger grids: tiles per range (0: small grids) */
+       ZIGP_KFF_ONE_LAUNCH,    /* 1: the point kernels took both latents (or the only one) in one launch */
+       ZIGP_KFF_COUNT };
+typedef struct zigp_stage_kron_fused {
+  int32_t lik;                  /* ZIGP_LIK_ONOFF (two latents) or a head (the f fields of everything) */
+  int32_t include_kl;
+  const zigp_kron_params* p;
+  const double *X, *Y;          /* host [N][D0 + D1], [N] */
+  int64_t N;                    /* >= 1 */
+  double jitter, scale, g_offset, f_mu;
+  zigp_kronf_tap_latent lat[2];
+  int64_t* facts;               /* out [ZIGP_KFF_COUNT], may be NULL */
+  double *elbo_data, *kl;       /* the step's ordinary outputs (of the injected cotangents, when there are any) */
+  zigp_kron_grads* grads;       /* required: the hook runs the gradient step */
+  double* d_f_mu;
+} zigp_stage_kron_fused;
+int zigp_test_kron_fused_step(zigp_ctx* ctx, const zigp_stage_kron_fused* a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -998,6 +998,26 @@ int zigp_test_kron_pointwise(zigp_ctx* c, const zigp_stage_kron_pointwise* s) {
   return ZIGP_OK;
 }
 
+// One value-and-gradient step of the fused path through kronf_run itself, with its device buffers snapshot (KfTap, zigp_kronf.hip)
+int zigp_test_kron_fused_step(zigp_ctx* c, const zigp_stage_kron_fused* s) {
+  if (!c) return ZIGP_EARG;
+  if (!s) return fail_arg(c, "zigp_test_kron_fused_step: bad arguments");
+  ZIGP_TRY(validate_kron(c, s->p, s->lik));
+  const int nlat = s->lik == ZIGP_LIK_ONOFF ? 2 : 1;
+  if (s->N < 1 || !s->X || !s->Y || !s->grads || !(s->jitter >= 0)) return fail_arg(c, "zigp_test_kron_fused_step: need N >= 1 rows X, Y, grads and jitter >= 0");
+  if (c->kron_panels || !kf_eligible(s->p, nlat))
+    return fail_arg(c, "zigp_test_kron_fused_step: this step does not run on the fused Kronecker kernels (grid beyond them, or zigp_set_kron_panels)");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  KfTap tap;
+  tap.s = s;
+  memset(tap.facts, 0, sizeof(tap.facts));
+  for (int h = 0; h < nlat; ++h)
+    if (s->lat[h].inject) ZIGP_TRY(stage_upload_rows(c, tap.inject[h], s->lat[h].inject, 4, 4, s->N));
+  ZIGP_TRY(kronf_run(c, s->p, s->X, s->Y, s->N, s->jitter, s->scale, s->g_offset, s->f_mu, s->include_kl, false, nullptr, s->elbo_data, s->kl, s->grads,
+                     s->lik, s->d_f_mu, false, nullptr, &tap));
+  return tap.flush(c);
+}
+
 int zigp_test_kron_kbuild(zigp_ctx* c, int64_t N, int64_t Nc, int32_t ldx, int32_t col0, int32_t M, int32_t D, const double* X, const double* Z,
                           const double* ell, double var, double* K) {
   if (!c) return ZIGP_EARG;

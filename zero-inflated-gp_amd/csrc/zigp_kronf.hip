@@ -1365,11 +1365,36 @@ static void kf_fill_hyp(double* H, const KfHostLatent* hl, int nlat, int D0, int
   H[KH_NOISE] = noise;
 }
 
+// Test hook of a step (zigp_test_kron_fused_step, include/zigp_diag.h).  Each tap is a device-to-device copy enqueued on the step's
+// stream right behind the launch that produces the value, into a buffer of its own; flush() downloads them once the step has finished.
+struct KfTap {
+  const zigp_stage_kron_fused* s;
+  struct Snap { double* host; DevBuf dev; size_t n; };
+  std::vector<Snap> snaps;
+  DevBuf inject[2];       // device copies of the injected cotangents [4][N], uploaded before the step
+  int64_t facts[ZIGP_KFF_COUNT];
+  int snap(zigp_ctx* c, double* host, const double* dev, size_t n) {
+    if (!host || n == 0) return 0;
+    snaps.emplace_back();
+    Snap& q = snaps.back();
+    q.host = host; q.n = n;
+    ZIGP_ENSURE(c, q.dev, n);
+    ZIGP_HIP(c, hipMemcpyAsync(q.dev.p, dev, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+  }
+  int flush(zigp_ctx* c) {      // the stream is idle
+    for (Snap& q : snaps) ZIGP_HIP(c, hipMemcpy(q.host, q.dev.p, sizeof(double) * q.n, hipMemcpyDeviceToHost));
+    if (s->facts) memcpy(s->facts, facts, sizeof(facts));
+    return 0;
+  }
+};
+
 // One ELBO step (or prediction) of the fused Kronecker path.  fit != nullptr: n_steps gradient steps with the Adam update on the device
-// (p then carries the sizes only; X / Y are the resident data set).
+// (p then carries the sizes only; X / Y are the resident data set).  tap != nullptr: the step of the stage tests, snapshots around its
+// launches (an ordinary step pays one pointer test for it: the tapped body is an instantiation of its own).
 static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, const double* Y, int64_t N, double jitter, double scale,
                      double g_offset, double f_mu, int include_kl, bool predict, double* out9, double* elbo_data, double* kl, zigp_kron_grads* grads,
-                     int lik, double* d_offset, bool dev_xy, const KfFitCall* fit = nullptr) {
+                     int lik, double* d_offset, bool dev_xy, const KfFitCall* fit = nullptr, KfTap* tap = nullptr) {
   // dev_xy: X / Y are DEVICE pointers into the resident data set (zigp_set_data): nothing but the parameters is staged
   const int nlat = (lik == ZIGP_LIK_ONOFF) ? 2 : 1;
   const KfPlan pl = kf_plan(p, nlat);
@@ -1469,7 +1494,8 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
   int* hinfo = nullptr;
 
   // ---- the launches of ONE step on rows (Xd, Yd) -- everything else it reads lives on the device (parameter image, hyper block)
-  auto enqueue = [&](const double* Xd, const double* Yd) -> int {
+  auto enqueue = [&](auto tapped, const double* Xd, const double* Yd) -> int {
+    constexpr bool TAP = decltype(tapped)::value;
     if (c->comm && !predict) ZIGP_HIP(c, hipMemsetAsync(ks.res.p, 0, sizeof(double) * RES_INFO, c->stream));   // parts a value-only / single-latent step leaves unwritten
     // ---- factor stage
     {
@@ -1487,6 +1513,16 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
       else { fa.info = reinterpret_cast<int*>(ks.res.p + RES_INFO); fa.own_slots = 1; }
       hipLaunchKernelGGL(k_kf_factor, dim3(2 * nlat), dim3(1024), sizeof(double) * PB * PBLD, c->stream, fa);
       ZIGP_HIP(c, hipGetLastError());
+      if constexpr (TAP) {
+        for (int h = 0; h < nlat; ++h)
+          for (int q = 0; q < 2; ++q) {
+            const zigp_kronf_tap_factor& tf = tap->s->lat[h].fac[q];
+            const KfFactorJob& jb = fa.job[2 * h + q];
+            const size_t mq = (size_t)jb.Mq;
+            ZIGP_TRY(tap->snap(c, tf.K, jb.K, (size_t)PB * PB)); ZIGP_TRY(tap->snap(c, tf.P, jb.P, mq * mq)); ZIGP_TRY(tap->snap(c, tf.PF, jb.PF, mq * mq));
+            ZIGP_TRY(tap->snap(c, tf.dvec, jb.dvec, mq + 1)); ZIGP_TRY(tap->snap(c, tf.Zs, jb.Zs, mq * jb.D)); ZIGP_TRY(tap->snap(c, tf.zc, jb.zc_out, (size_t)jb.D));
+          }
+      }
     }
     if (predict) ZIGP_TRY(request_info(c, &hinfo));   // value / gradient steps: the status slots come back with the result block
     {
@@ -1510,6 +1546,16 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
       }
       else hipLaunchKernelGGL(k_kf_latent, dim3(nlat), dim3(1024), 0, c->stream, la);
       ZIGP_HIP(c, hipGetLastError());
+      if constexpr (TAP) {
+        for (int h = 0; h < nlat; ++h) {
+          const zigp_kronf_tap_latent& tl = tap->s->lat[h];
+          const KfLatentJob& jb = la.job[h];
+          const size_t n01 = (size_t)jb.Mq0 * jb.Mq1;
+          double* const host[9] = {tl.U, tl.S2, tl.T0, tl.T1, tl.Al, tl.AlF, tl.S2F, tl.AlTF, tl.S2TF};
+          const double* const dev[9] = {jb.U, jb.S2, jb.T0, jb.T1, jb.Al, jb.AlF, jb.S2F, jb.AlTF, jb.S2TF};
+          for (int i = 0; i < 9; ++i) ZIGP_TRY(tap->snap(c, host[i], dev[i], n01));
+        }
+      }
     }
     // ---- point stage
     KfArgs ka;
@@ -1537,6 +1583,10 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
       else if (pl.large) hipLaunchKernelGGL((k_kfl_forward<1, 7, true, false>), grid, dim3(64 * KF_WAVES), lds_fwd, c->stream, ka);
       else ZIGP_TRY(kf_launch_small_latents(c, Mq, nlat, false, grid.x, ka));
       ZIGP_HIP(c, hipGetLastError());
+      if constexpr (TAP) {
+        tap->facts[ZIGP_KFF_TPW_FWD] = ka.tpw;
+        for (int h = 0; h < nlat; ++h) ZIGP_TRY(tap->snap(c, tap->s->lat[h].part, pts(h), (size_t)4 * Npad));
+      }
     }
     KronPwArgs a;
     memset(&a, 0, sizeof(a));
@@ -1562,6 +1612,14 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
     else hipLaunchKernelGGL((k_kron_head_pointwise<false, false>), dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a, lik);
     if (!need_grad) hipLaunchKernelGGL(k_kron_pw_reduce, dim3(1), dim3(256), 0, c->stream, d_pwacc, pw_blocks, include_kl ? 1.0 : 0.0, ks.res.p + RES_PWS);
     ZIGP_HIP(c, hipGetLastError());
+    if constexpr (TAP) {
+      for (int h = 0; h < nlat; ++h) {
+        ZIGP_TRY(tap->snap(c, tap->s->lat[h].cot, pts(h) + 4 * Npad, (size_t)4 * Npad));
+        if (tap->s->lat[h].inject)      // rows [4][N] over gm, gv, dq0, dq1 [Npad] each: the padding keeps the kernel's values
+          ZIGP_HIP(c, hipMemcpy2DAsync(pts(h) + 4 * Npad, sizeof(double) * Npad, tap->inject[h].p, sizeof(double) * N, sizeof(double) * N, 4,
+                                       hipMemcpyDeviceToDevice, c->stream));
+      }
+    }
     if (need_grad) {
       const int waves = std::min(ka.ntiles, 1024 / nlat);   // one wave per SIMD of the chip: the kernels hold ~400-500 registers per lane
       ka.tpw = (ka.ntiles + waves - 1) / waves;
@@ -1573,6 +1631,7 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
         ZIGP_ENSURE(c, ks.acc, (size_t)2 * nparts * nblk * 256);
         for (int h = 0; h < nlat; ++h) ka.lat[h].acc = ks.acc.p + (size_t)h * nparts * nblk * 256;
         ZIGP_TRY(kf_launch_small_latents(c, Mq, nlat, true, (unsigned)nwg, ka));
+        if constexpr (TAP) { tap->facts[ZIGP_KFF_TPW_BWD] = ka.tpw; tap->facts[ZIGP_KFF_NRANGES] = 1; }
       } else {
         // The backward kernel spills ~4 KB of operands per point and latent (at 10 x 100), which k_kfl_accum then sums over the points.  The
         // rows go through in RANGES of <= 1024 tiles (16 384 rows: <= 128 MB of records for both latents, Infinity-Cache resident), one
@@ -1612,12 +1671,18 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
           aa.tile0 = t0; aa.tile1 = t1; aa.part0 = t0 / tps;
           hipLaunchKernelGGL(k_kfl_accum, dim3((nblk + 3) / 4, (nt + tps - 1) / tps, nlat), dim3(256), 0, c->stream, aa);
           ZIGP_HIP(c, hipGetLastError());
+          if constexpr (TAP) { if (t0 == 0) tap->facts[ZIGP_KFF_TPW_BWD] = ka.tpw; ++tap->facts[ZIGP_KFF_NRANGES]; }
         }
+        if constexpr (TAP) { tap->facts[ZIGP_KFF_TPS] = tps; tap->facts[ZIGP_KFF_RANGE_TILES] = range_tiles; }
       }
       hipLaunchKernelGGL(k_kf_reduce, dim3(nblk * 256 / 16 + 1, nlat), dim3(256), 0, c->stream, ka.lat[0].acc, ka.lat[gl_].acc, nparts,
                          lat(0) + LAT_WORK, lat(gl_) + LAT_WORK, pl.nb0c, pl.nb1c, Mq[0][0] / 16, Mq[0][1] / 16, Mq[gl_][0] / 16, Mq[gl_][1] / 16,
                          d_pwacc, pw_blocks, include_kl ? 1.0 : 0.0, ks.res.p + RES_PWS);
       ZIGP_HIP(c, hipGetLastError());
+      if constexpr (TAP) {
+        tap->facts[ZIGP_KFF_NPARTS] = nparts;
+        for (int h = 0; h < nlat; ++h) ZIGP_TRY(tap->snap(c, tap->s->lat[h].work, lat(h) + LAT_WORK, (size_t)wl.total));
+      }
       KflFinishArgs fa;
       memset(&fa, 0, sizeof(fa));
       for (int h = 0; h < nlat; ++h) {
@@ -1732,7 +1797,7 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
       const double* Xd = rb >= 0 ? X + rb * ldx : d_wrap + (size_t)(-rb - 1) * N * ldx;
       const double* Yd = rb >= 0 ? Y + rb : d_wrap + n_wrap * (size_t)N * ldx + (size_t)(-rb - 1) * N;
       d_hyp = ks.in.p + ((i & 1) ? off_hyp2 : off_hyp);       // written by the previous step's update (step 0: by the launch above)
-      ZIGP_TRY(enqueue(Xd, Yd));
+      ZIGP_TRY(enqueue(std::false_type{}, Xd, Yd));
       // lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t), t counted from 1 (zigp/optim.py AdamGroups.step): the two t-dependent factors from the host
       const double t = (double)(fit->t0 + i + 1);
       fa.step = i; fa.lr_sq = std::sqrt(1.0 - std::pow(d.beta2, t)); fa.lr_den = 1.0 - std::pow(d.beta1, t);
@@ -1760,7 +1825,19 @@ static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, co
     return 0;
   }
 
-  ZIGP_TRY(enqueue(dev_xy ? X : ks.in.p + off_x, Y ? (dev_xy ? Y : ks.in.p + off_y) : nullptr));
+  {
+    const double* Xd = dev_xy ? X : ks.in.p + off_x;
+    const double* Yd = Y ? (dev_xy ? Y : ks.in.p + off_y) : nullptr;
+    if (tap) {
+      const int64_t f0[ZIGP_KFF_COUNT] = {pl.large, large_exact, pl.nb0c, pl.nb1c, Mq[0][0] / 16, Mq[0][1] / 16, Mq[nlat - 1][0] / 16, Mq[nlat - 1][1] / 16,
+                                          Npad, Npad / 16, 0, 0, 0, 0, 0, 0,
+                                          (pl.large || nlat == 1 || (Mq[0][0] == Mq[1][0] && Mq[0][1] == Mq[1][1])) ? 1 : 0};
+      memcpy(tap->facts, f0, sizeof(f0));
+      ZIGP_TRY(enqueue(std::true_type{}, Xd, Yd));
+    } else {
+      ZIGP_TRY(enqueue(std::false_type{}, Xd, Yd));
+    }
+  }
   if (predict) {
     const int rows = nlat == 2 ? 9 : 4;
     ZIGP_HIP(c, hipMemcpyAsync(out9, ks.out.p, sizeof(double) * rows * N, hipMemcpyDeviceToHost, c->stream));

@@ -154,6 +154,26 @@ class zigp_stage_kron_pointwise(C.Structure):   # include/zigp_diag.h
                 ('acc', dp), ('out', dp)]
 
 
+class zigp_kronf_tap_factor(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('K', dp), ('P', dp), ('PF', dp), ('dvec', dp), ('Zs', dp), ('zc', dp)]
+
+
+class zigp_kronf_tap_latent(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('fac', zigp_kronf_tap_factor * 2), ('U', dp), ('S2', dp), ('T0', dp), ('T1', dp), ('Al', dp),
+                ('AlF', dp), ('S2F', dp), ('AlTF', dp), ('S2TF', dp), ('part', dp), ('cot', dp), ('work', dp), ('inject', dp)]
+
+
+KFF_FACTS = ('large', 'large_exact', 'nb0c', 'nb1c', 'nb0_f', 'nb1_f', 'nb0_g', 'nb1_g', 'Npad', 'ntiles', 'tpw_fwd', 'tpw_bwd', 'nparts', 'tps',
+             'nranges', 'range_tiles', 'one_launch')   # include/zigp_diag.h ZIGP_KFF_*
+
+
+class zigp_stage_kron_fused(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('lik', C.c_int32), ('include_kl', C.c_int32), ('p', C.POINTER(zigp_kron_params)), ('X', dp), ('Y', dp), ('N', C.c_int64),
+                ('jitter', C.c_double), ('scale', C.c_double), ('g_offset', C.c_double), ('f_mu', C.c_double),
+                ('lat', zigp_kronf_tap_latent * 2), ('facts', C.POINTER(C.c_int64)), ('elbo_data', dp), ('kl', dp),
+                ('grads', C.POINTER(zigp_kron_grads)), ('d_f_mu', dp)]
+
+
 KPW_THREADS, KPW_ACC = 256, 5   # csrc/zigp_kron.hip: points per block and accumulators per block of the Kronecker point-wise kernels
 STAGE_SENTINEL = float(np.frombuffer(bytes([0x7f]) * 8, dtype=np.float64)[0])   # ZIGP_STAGE_SENTINEL_BYTE in every byte: 1.38e306
 KG_SPLIT, PW_PTS, PW_ACC = 4, 64, 13   # csrc/zigp_kernels.h
@@ -266,6 +286,7 @@ SIGNATURES = {
     'zigp_test_mxm_backward': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_mxm)]),
     'zigp_test_dense_pack': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_pack)]),
     'zigp_test_kron_pointwise': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_kron_pointwise)]),
+    'zigp_test_kron_fused_step': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_kron_fused)]),
     'zigp_test_kron_kbuild': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, C.c_double, dp]),
     'zigp_test_kron_colsum': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, dp, dp, dp, dp, dp, dp, dp, dp]),
     'zigp_test_kron_da': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, dp, dp, dp, dp, dp, dp, dp]),

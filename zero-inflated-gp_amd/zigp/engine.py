@@ -1453,6 +1453,83 @@ class DenseEngine:
         _check(self.lib, self.ctx, self.lib.zigp_test_kron_pointwise(self.ctx, C.byref(s)))
         return out
 
+    def test_kron_fused_step(self, p, X, Y, lik='onoff', jitter=1e-5, scale=1.0, g_offset=0.0, f_mu=0.0, include_kl=True, inject=None, taps=True):
+        """One value-and-gradient step of the fused Kronecker path with its device buffers snapshot around the launches
+        (zigp_test_kron_fused_step, include/zigp_diag.h, where every layout is written down).  p, X, Y as kron_elbo (lik 'onoff') or
+        kron_head_elbo ('gaussian' / 'bernoulli': the f fields only).  inject: None, or one entry per latent, each None or [4][N] = gm, gv,
+        dq0, dq1 copied over the point-wise kernel's cotangents before the backward launch.  taps=False: no snapshot at all.
+        Returns dict(elbo_data, kl, grads (as kron_elbo / kron_head_elbo), facts {name: int}, lat [per latent: dict(K, P, PF, dvec, Zs, zc --
+        lists over the two factors --, U, S2, T0, T1, Al, AlF, S2F, AlTF, S2TF, part, cot, work)])."""
+        two = lik == 'onoff'
+        tags = ('f', 'g') if two else ('f',)
+        sp, keep, dims = self._pack_kron(p, tags=tags)
+        X = as_f64(X)
+        if X.ndim != 2 or X.shape[1] != dims[0] + dims[1]:
+            raise ValueError('X must be (N,%d)' % (dims[0] + dims[1]))
+        Y = as_f64(Y).reshape(-1)
+        N = X.shape[0]
+        if Y.size != N:
+            raise ValueError('Y must have N entries')
+        s = _lib.zigp_stage_kron_fused()
+        s.lik = self.LIK[lik] if not two else _lib.LIK_ONOFF
+        s.include_kl = 1 if include_kl else 0
+        s.p = C.pointer(sp)
+        s.X, s.Y, s.N = ptr(X), ptr(Y), N
+        s.jitter, s.scale, s.g_offset, s.f_mu = float(jitter), float(scale), float(g_offset), float(f_mu)
+        Ms = [(keep[t][0].shape[0], keep[t][1].shape[0]) for t in tags]
+        small = all(m0 <= 32 and m1 <= 32 for m0, m1 in Ms)
+        R0, R1 = (32, 32) if small else (16, 112)                     # capacity rows (kf_plan)
+        ldw = max(R0, R1)
+        Npad = max(1024, -(-N // 1024) * 1024)
+        lat, hold = [], []
+        for h, (M0, M1) in enumerate(Ms):
+            Mq = (-(-M0 // 16) * 16, -(-M1 // 16) * 16)
+            d = {}
+            if taps:
+                d = dict(K=[np.zeros((128, 128)) for q in range(2)], P=[np.zeros((Mq[q], Mq[q])) for q in range(2)],
+                         PF=[np.zeros(Mq[q] * Mq[q]) for q in range(2)], dvec=[np.zeros(Mq[q] + 1) for q in range(2)],
+                         Zs=[np.zeros((Mq[q], dims[q])) for q in range(2)], zc=[np.zeros(dims[q]) for q in range(2)],
+                         part=np.zeros((4, Npad)), cot=np.zeros((4, Npad)), work=np.zeros(3 * R0 * ldw + R1 * ldw + 16 * (R0 + R1)))
+                for k in ('U', 'S2', 'T0', 'T1', 'Al'):
+                    d[k] = np.zeros(Mq)
+                for k in ('AlF', 'S2F', 'AlTF', 'S2TF'):
+                    d[k] = np.zeros(Mq[0] * Mq[1])
+                t = s.lat[h]
+                for q in range(2):
+                    for k in ('K', 'P', 'PF', 'dvec', 'Zs', 'zc'):
+                        setattr(t.fac[q], k, ptr(d[k][q]))
+                for k in ('U', 'S2', 'T0', 'T1', 'Al', 'AlF', 'S2F', 'AlTF', 'S2TF', 'part', 'cot', 'work'):
+                    setattr(t, k, ptr(d[k]))
+            if inject is not None and inject[h] is not None:
+                inj = as_f64(inject[h], (4, N))
+                hold.append(inj)
+                s.lat[h].inject = ptr(inj)
+            lat.append(d)
+        facts = (C.c_int64 * len(_lib.KFF_FACTS))()
+        s.facts = C.cast(facts, C.POINTER(C.c_int64))
+        sc = np.zeros(3)
+        s.elbo_data, s.kl, s.d_f_mu = sc.ctypes.data, sc.ctypes.data + 8, sc.ctypes.data + 16
+        gs = _lib.zigp_kron_grads()
+        g = {}
+        for tag in tags:
+            Z0, Z1, l0, l1, um, us = keep[tag]
+            a = dict(Z0=np.zeros_like(Z0), Z1=np.zeros_like(Z1), ell0=np.zeros_like(l0), ell1=np.zeros_like(l1), um=np.zeros_like(um), us=np.zeros_like(us))
+            g[tag] = a
+            setattr(gs, 'Z0' + tag, ptr(a['Z0'])); setattr(gs, 'Z1' + tag, ptr(a['Z1']))
+            setattr(gs, 'ell0' + tag, ptr(a['ell0'])); setattr(gs, 'ell1' + tag, ptr(a['ell1']))
+            setattr(gs, 'u_%sm' % tag, ptr(a['um'])); setattr(gs, 'u_%ss_sqrt' % tag, ptr(a['us']))
+        s.grads = C.pointer(gs)
+        _check(self.lib, self.ctx, self.lib.zigp_test_kron_fused_step(self.ctx, C.byref(s)))
+        out = dict(noise=gs.noise, f_mu=sc[2])
+        for tag in tags:
+            a = g[tag]
+            out['Z' + tag] = [a['Z0'], a['Z1']]
+            out['ell_' + tag] = [a['ell0'], a['ell1']]
+            out['var_' + tag] = [getattr(gs, 'var0' + tag), getattr(gs, 'var1' + tag)]
+            out['u_%sm' % tag] = a['um']
+            out['u_%ss_sqrt' % tag] = a['us']
+        return dict(elbo_data=float(sc[0]), kl=float(sc[1]), grads=out, facts={k: int(facts[i]) for i, k in enumerate(_lib.KFF_FACTS)}, lat=lat)
+
     def test_kron_panel_kbuild(self, X, col0, Z, ell, var, Nc):
         """k_kron_kbuild (zigp_test_kron_kbuild): the WHOLE padded factor panel (Mq, Nc), Mq = M rounded up to 128, from the columns
         col0 : col0 + D of X (N, ldx) and Z (M, D)."""
