@@ -26,6 +26,33 @@ def test_head_fit_symbols_exist_and_reject_a_null_context():
     assert lib.zigp_kron_head_elbo_rows(None, C.byref(s), _lib.LIK_GAUSSIAN, 0, 1, 1e-5, 1.0, 0.0, 1, None, None, None, None) == _lib.ZIGP_EARG
 
 
+def test_every_kron_entry_point_rejects_a_null_context():
+    """Each zigp_kron_* entry point is a wrapper over a shared function that starts with the context check: with a NULL context every one
+    returns ZIGP_EARG -- before it reads an argument, so the other pointers may be NULL too -- and zigp_kron_fit_steps_applied keeps its
+    own return for it (ZIGP_EARG as an int64)."""
+    from zigp import _lib
+    lib = _lib.load()
+    names = sorted(n for n in _lib.SIGNATURES if n.startswith('zigp_kron_'))
+    assert set(names) == {'zigp_kron_elbo', 'zigp_kron_elbo_rows', 'zigp_kron_fit_steps', 'zigp_kron_fit_steps_applied', 'zigp_kron_predict',
+                          'zigp_kron_head_elbo', 'zigp_kron_head_elbo_rows', 'zigp_kron_head_fit_steps', 'zigp_kron_head_predict'}
+    keep = []
+
+    def blank(t):
+        if t in (C.c_double,):
+            return 0.0
+        if t in (C.c_int32, C.c_int64, C.c_int):
+            return 0
+        if isinstance(t, type) and issubclass(t, C._Pointer):       # a struct the entry point would read: a zeroed one
+            keep.append(t._type_())
+            return C.byref(keep[-1])
+        return None
+    for n in names:
+        res, args = _lib.SIGNATURES[n]
+        assert args[0] is C.c_void_p, n
+        rc = getattr(lib, n)(None, *[blank(t) for t in args[1:]])
+        assert rc == _lib.ZIGP_EARG, (n, rc)
+
+
 @pytest.mark.parametrize('lik', ['gaussian', 'bernoulli'])
 def test_head_device_fit_equals_the_host_loop_on_the_oracle(lik):
     """20 steps at grid (6, 5) in calls of 7 + 7 + 6 with a host wrap-around batch mid-way: HeadDeviceFit over the oracle-backed stand-in ends

@@ -13,6 +13,7 @@
 // on the fp64 MFMA GEMM core (operands padded to 128); the reverse pass is hand-derived.
 #include "zigp_host.h"
 #include "zigp_comm.h"
+#include "zigp_kronc.h"
 
 using namespace zigp;
 
@@ -356,10 +357,6 @@ int nred(zigp_ctx* c, KronLatent& lt, const double* PA, const double* PB, const 
   return 0;
 }
 
-struct HostKronLatent {
-  int M[2]; const double* Z[2]; const double* ell[2]; double var[2]; const double* u; const double* s;
-};
-
 // lik != ZIGP_LIK_ONOFF: single latent, only the f fields (and, for the Gaussian head, noise) are read
 int validate_kron(zigp_ctx* c, const zigp_kron_params* p, int lik = ZIGP_LIK_ONOFF) {
   if (!p) return fail_arg(c, "kron params is NULL");
@@ -408,7 +405,7 @@ int upload_grid(zigp_ctx* c, DevBuf& b, const double* src, int M0, int M1, int M
   return 0;
 }
 
-int latent_setup(zigp_ctx* c, KronLatent& lt, const HostKronLatent& h, int D0, int D1, double jitter) {
+int latent_setup(zigp_ctx* c, KronLatent& lt, const KronHostLatent& h, int D0, int D1, double jitter) {
   ZIGP_TRY(factor_forward(c, lt.f[0], h.M[0], D0, 0, h.Z[0], h.ell[0], h.var[0], jitter));
   ZIGP_TRY(factor_forward(c, lt.f[1], h.M[1], D1, D0, h.Z[1], h.ell[1], h.var[1], jitter));
   const int M0 = h.M[0], M1 = h.M[1], Mq0 = lt.f[0].Mq, Mq1 = lt.f[1].Mq, nb0 = Mq0 / BM, nb1 = Mq1 / BM;
@@ -534,15 +531,17 @@ zigp_ctx::~zigp_ctx() = default;
 
 namespace {
 
-int kron_run_panels(zigp_ctx* c, const zigp_kron_params* p, const double* X, const double* Y, int64_t N, double jitter, double scale,
-                    double g_offset, double f_mu, int include_kl, bool predict, double* out9, double* elbo_data, double* kl, zigp_kron_grads* grads,
-                    int lik, double* d_offset, bool dev_xy);
+int kron_run_panels(zigp_ctx* c, const KronCall& k);
 
 // Data-parallel exchange of the PANEL path (grids beyond the fused kernels' capacity): its results reach the host piecewise, so with a
 // communicator (zigp_comm_init) the assembled outputs take one more round trip -- packed, summed over ranks on the device, unpacked.
 // (The fused path reduces its device result block in place before its single download.)
-int kron_exchange_host(zigp_ctx* c, const zigp_kron_params* p, int nlat, double* elbo_data, double* kl, zigp_kron_grads* g, double* d_offset) {
+int kron_exchange_host(zigp_ctx* c, const KronCall& k) {
   if (!c->comm) return 0;
+  const zigp_kron_params* p = k.p;
+  const int nlat = k.nlat;
+  double *elbo_data = k.elbo_data, *kl = k.kl, *d_offset = k.d_offset;
+  zigp_kron_grads* g = k.need_grad ? k.grads : nullptr;
   struct Piece { double* p; size_t n; };
   std::vector<Piece> pc;
   double scal[11] = {elbo_data ? *elbo_data : 0.0, kl ? *kl : 0.0, d_offset ? *d_offset : 0.0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -583,28 +582,24 @@ int kron_exchange_host(zigp_ctx* c, const zigp_kron_params* p, int nlat, double*
 }
 
 // small grids go through the fused register-resident kernels (zigp_kronf.hip); larger factors through the panel path below
-// g_offset: added to gmean before the probit moments (onofftf/onoffpred.py:141); f_mu: constant added to fmean (scripts/onoff.py:168-169,
-// classifier.py:136-137), its gradient (sum of the fmean cotangents) goes to *d_offset
-int kron_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, const double* Y, int64_t N, double jitter, double scale,
-             double g_offset, double f_mu, int include_kl, bool predict, double* out9, double* elbo_data, double* kl, zigp_kron_grads* grads,
-             int lik = ZIGP_LIK_ONOFF, double* d_offset = nullptr, bool dev_xy = false) {
-  const int nlat = (lik == ZIGP_LIK_ONOFF) ? 2 : 1;
-  if (!c->kron_panels && kf_eligible(p, nlat))
-    return kronf_run(c, p, X, Y, N, jitter, scale, g_offset, f_mu, include_kl, predict, out9, elbo_data, kl, grads, lik, d_offset, dev_xy);
-  return kron_run_panels(c, p, X, Y, N, jitter, scale, g_offset, f_mu, include_kl, predict, out9, elbo_data, kl, grads, lik, d_offset, dev_xy);
+int kron_run(zigp_ctx* c, const KronCall& k) {
+  if (!c->kron_panels && kf_eligible(k.p, k.nlat)) return kronf_run(c, k);
+  return kron_run_panels(c, k);
 }
 
-int kron_run_panels(zigp_ctx* c, const zigp_kron_params* p, const double* X, const double* Y, int64_t N, double jitter, double scale,
-                    double g_offset, double f_mu, int include_kl, bool predict, double* out9, double* elbo_data, double* kl, zigp_kron_grads* grads,
-                    int lik, double* d_offset, bool dev_xy) {
-  const int nlat = (lik == ZIGP_LIK_ONOFF) ? 2 : 1;   // single-latent heads use the f latent only
+int kron_run_panels(zigp_ctx* c, const KronCall& k) {
+  const zigp_kron_params* p = k.p;
+  const double *X = k.X, *Y = k.Y;
+  const int64_t N = k.N;
+  const int nlat = k.nlat, include_kl = k.include_kl;
+  const bool predict = k.predict, need_grad = k.need_grad;
+  const KronHostLatent* hl = k.hl;
   if (!c->kron) { c->kron.reset(new (std::nothrow) KronState()); if (!c->kron) { c->err = "out of memory"; return ZIGP_EHIP; } }
   KronState& ks = *c->kron;
   ZIGP_TRY(begin_staged_call(c));
-  const bool need_grad = grads != nullptr && !predict;
   const int D0 = p->D0, D1 = p->D1, ldx = D0 + D1;
   const int64_t Nc = std::max<int64_t>(1024, round_up(N, 1024));
-  if (dev_xy) {   // rows of the resident data set: device-to-device
+  if (k.dev_xy) {   // rows of the resident data set: device-to-device
     ZIGP_ENSURE(c, ks.X, (size_t)N * ldx); ZIGP_ENSURE(c, ks.Y, (size_t)N);
     ZIGP_HIP(c, hipMemcpyAsync(ks.X.p, X, sizeof(double) * N * ldx, hipMemcpyDeviceToDevice, c->stream));
     if (Y) ZIGP_HIP(c, hipMemcpyAsync(ks.Y.p, Y, sizeof(double) * N, hipMemcpyDeviceToDevice, c->stream));
@@ -612,15 +607,12 @@ int kron_run_panels(zigp_ctx* c, const zigp_kron_params* p, const double* X, con
     ZIGP_TRY(upload_padded(c, ks.X, X, (size_t)N * ldx, (size_t)N * ldx));   // the minibatch, staged like the parameters
     if (Y) ZIGP_TRY(upload_padded(c, ks.Y, Y, (size_t)N, (size_t)N));
   }
-  HostKronLatent hl[2] = {{{p->M0f, p->M1f}, {p->Z0f, p->Z1f}, {p->ell0f, p->ell1f}, {p->var0f, p->var1f}, p->u_fm, p->u_fs_sqrt},
-                          {{p->M0g, p->M1g}, {p->Z0g, p->Z1g}, {p->ell0g, p->ell1g}, {p->var0g, p->var1g}, p->u_gm, p->u_gs_sqrt}};
-  if (nlat == 1) hl[1] = hl[0];
   ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
   // the two latents are independent launch chains of small kernels: f on the main stream, g on stream2
   ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
   for (int h = 0; h < nlat; ++h) {
     OnStream on(c, h == 0 ? c->stream_main : c->stream2);
-    ZIGP_TRY(latent_setup(c, ks.lat[h], hl[h], D0, D1, jitter));
+    ZIGP_TRY(latent_setup(c, ks.lat[h], hl[h], D0, D1, k.jitter));
   }
   ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   int* hinfo = nullptr;
@@ -649,7 +641,7 @@ int kron_run_panels(zigp_ctx* c, const zigp_kron_params* p, const double* X, con
   KronPwArgs a;
   const int gl_ = nlat - 1;   // latent whose buffers stand in for g (unused by the single-latent kernels)
   a.part_f = ks.lat[0].part.p; a.part_g = ks.lat[gl_].part.p; a.Y = Y ? ks.Y.p : nullptr; a.N = N; a.Nc = Nc;
-  a.knn_f = p->var0f * p->var1f; a.knn_g = p->var0g * p->var1g; a.noise = p->noise; a.g_offset = g_offset; a.f_offset = f_mu; a.scale = scale;
+  a.knn_f = p->var0f * p->var1f; a.knn_g = p->var0g * p->var1g; a.noise = p->noise; a.g_offset = k.g_offset; a.f_offset = k.f_mu; a.scale = k.scale;
   a.gm_f = need_grad ? ks.lat[0].gm.p : nullptr; a.gv_f = ks.lat[0].gv.p; a.gm_g = ks.lat[gl_].gm.p; a.gv_g = ks.lat[gl_].gv.p;
   a.dq0_f = ks.lat[0].dq0.p; a.dq1_f = ks.lat[0].dq1.p; a.dq0_g = ks.lat[gl_].dq0.p; a.dq1_g = ks.lat[gl_].dq1.p;
   a.acc = ks.acc.p; a.out9 = nullptr; a.ld9 = N; a.hyp = nullptr;
@@ -658,14 +650,14 @@ int kron_run_panels(zigp_ctx* c, const zigp_kron_params* p, const double* X, con
     ZIGP_ENSURE(c, ks.out9, (size_t)rows * N);
     a.out9 = ks.out9.p;
     if (nlat == 2) hipLaunchKernelGGL(k_kron_pointwise<true>, dim3(blocks), dim3(PW_THREADS), 0, c->stream, a);
-    else hipLaunchKernelGGL((k_kron_head_pointwise<true, false>), dim3(blocks), dim3(PW_THREADS), 0, c->stream, a, lik);
+    else hipLaunchKernelGGL((k_kron_head_pointwise<true, false>), dim3(blocks), dim3(PW_THREADS), 0, c->stream, a, k.lik);
     ZIGP_HIP(c, hipGetLastError());
-    ZIGP_HIP(c, hipMemcpyAsync(out9, ks.out9.p, sizeof(double) * rows * N, hipMemcpyDeviceToHost, c->stream));
+    ZIGP_HIP(c, hipMemcpyAsync(k.out, ks.out9.p, sizeof(double) * rows * N, hipMemcpyDeviceToHost, c->stream));
     ZIGP_HIP(c, hipStreamSynchronize(c->stream));
-    return info_result(c, hinfo, "a Kronecker factor of Kuu");
+    return info_result(c, hinfo, kron_fac_any);
   }
   if (nlat == 2) hipLaunchKernelGGL(k_kron_pointwise<false>, dim3(blocks), dim3(PW_THREADS), 0, c->stream, a);
-  else hipLaunchKernelGGL((k_kron_head_pointwise<false, false>), dim3(blocks), dim3(PW_THREADS), 0, c->stream, a, lik);
+  else hipLaunchKernelGGL((k_kron_head_pointwise<false, false>), dim3(blocks), dim3(PW_THREADS), 0, c->stream, a, k.lik);
   ZIGP_HIP(c, hipGetLastError());
   double* hacc = nullptr;
   ZIGP_TRY(download(c, ks.acc.p, (size_t)blocks * KPW_ACC, &hacc));
@@ -684,7 +676,7 @@ int kron_run_panels(zigp_ctx* c, const zigp_kron_params* p, const double* X, con
         // G = -(P dP P) - kl*0.5*M_other*P  -> f.G ; then Kuu-style reductions into krow
         hipLaunchKernelGGL(k_kron_dk, dim3(ceil_div((int64_t)Mq * Mq, 256)), dim3(256), 0, c->stream, f.L.p, f.P.p,
                            include_kl ? 0.5 * (double)lt.f[1 - q].M : 0.0, (int64_t)Mq * Mq, f.G.p);
-        hipLaunchKernelGGL(k_kuu_grad, dim3(Mq), dim3(256), 0, c->stream, f.G.p, f.K.p, jitter, f.Z.p, f.M, f.D, (int64_t)Mq, f.krow.p);
+        hipLaunchKernelGGL(k_kuu_grad, dim3(Mq), dim3(256), 0, c->stream, f.G.p, f.K.p, k.jitter, f.Z.p, f.M, f.D, (int64_t)Mq, f.krow.p);
         ZIGP_HIP(c, hipGetLastError());
         ZIGP_TRY(download(c, f.krow.p, (size_t)Mq * (2 + 2 * f.D), &hkrow[h][q]));
       }
@@ -698,56 +690,17 @@ int kron_run_panels(zigp_ctx* c, const zigp_kron_params* p, const double* X, con
     ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   }
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));
-  ZIGP_TRY(info_result(c, hinfo, "a Kronecker factor of Kuu"));
+  ZIGP_TRY(info_result(c, hinfo, kron_fac_any));
   double s_ve = 0, s_dn = 0, s_gv[2] = {0, 0}, s_gm = 0;
   for (int b = 0; b < blocks; ++b) {
     const double* r = hacc + (size_t)KPW_ACC * b;
     s_ve += r[0]; s_dn += r[1]; s_gv[0] += r[2]; s_gv[1] += r[3]; s_gm += r[4];
   }
-  if (elbo_data) *elbo_data = s_ve;
-  if (d_offset) *d_offset = s_gm;
-  double klsum = 0.0;
-  if (include_kl) {
-    for (int h = 0; h < nlat; ++h) {
-      const int M0 = ks.lat[h].f[0].M, M1 = ks.lat[h].f[1].M;
-      klsum += 0.5 * (hkl[h][0] - (double)M0 * M1 - hkl[h][1] + hkl[h][2] + (double)M1 * hkl[h][3] + (double)M0 * hkl[h][4]);
-    }
-  }
-  if (kl) *kl = klsum;
-  if (need_grad) {
-    double* gZ[2][2] = {{grads->Z0f, grads->Z1f}, {grads->Z0g, grads->Z1g}};
-    double* gl[2][2] = {{grads->ell0f, grads->ell1f}, {grads->ell0g, grads->ell1g}};
-    double gvar[2][2];
-    double* gu[2] = {grads->u_fm, grads->u_gm};
-    double* gs[2] = {grads->u_fs_sqrt, grads->u_gs_sqrt};
-    for (int h = 0; h < nlat; ++h) {
-      for (int q = 0; q < 2; ++q) {
-        const KronFactor& f = ks.lat[h].f[q];
-        const int D = f.D, W = 2 + 2 * D;
-        double dv = 0.0;
-        std::vector<double> dl(D, 0.0);
-        for (int m = 0; m < f.M; ++m) {
-          const double* r = &hkrow[h][q][(size_t)m * W];
-          dv += r[0];
-          for (int d = 0; d < D; ++d) {
-            if (gZ[h][q]) gZ[h][q][m * D + d] = r[1 + d] / (f.ell[d] * f.ell[d]);
-            dl[d] += r[1 + D + d];
-          }
-        }
-        for (int d = 0; d < D; ++d)
-          if (gl[h][q]) gl[h][q][d] = dl[d] / (f.ell[d] * f.ell[d] * f.ell[d]);
-        // Knn = var0 * var1 enters var_n directly (scripts/onoff.py:196-200)
-        gvar[h][q] = dv / f.var + s_gv[h] * ks.lat[h].f[1 - q].var;
-      }
-      const size_t ng = (size_t)ks.lat[h].f[0].M * ks.lat[h].f[1].M;
-      if (gu[h]) memcpy(gu[h], hgu[h], sizeof(double) * ng);
-      if (gs[h]) memcpy(gs[h], hgs[h], sizeof(double) * ng);
-    }
-    grads->var0f = gvar[0][0]; grads->var1f = gvar[0][1];
-    grads->var0g = nlat == 2 ? gvar[1][0] : 0.0; grads->var1g = nlat == 2 ? gvar[1][1] : 0.0;
-    grads->noise = s_dn;
-  }
-  return kron_exchange_host(c, p, nlat, elbo_data, kl, need_grad ? grads : nullptr, d_offset);
+  if (k.elbo_data) *k.elbo_data = s_ve;
+  if (k.d_offset) *k.d_offset = s_gm;
+  if (k.kl) *k.kl = kron_kl(k, hkl, include_kl ? 1.0 : 0.0);
+  if (need_grad) kron_assemble_grads(k, hkrow, hgu, hgs, s_gv, s_dn);
+  return kron_exchange_host(c, k);
 }
 
 }  // namespace
@@ -756,159 +709,174 @@ namespace {
 // Prediction sets can be much larger than a training minibatch (predict_onoff runs over the full Xtrain / Xtest): rows go through
 // the path in chunks, so device panels and the pinned staging arena stay bounded; the factor stage is recomputed per chunk (microseconds).
 constexpr int64_t KRON_PREDICT_CHUNK = 131072;
-int kron_predict_chunked(zigp_ctx* c, const zigp_kron_params* p, const double* Xnew, int64_t N, double jitter, double g_offset, double f_mu,
-                         double* out, int lik, int rows) {
-  if (N <= KRON_PREDICT_CHUNK) return kron_run(c, p, Xnew, nullptr, N, jitter, 1.0, g_offset, f_mu, 0, true, out, nullptr, nullptr, nullptr, lik, nullptr);
-  const int ldx = p->D0 + p->D1;
+int kron_predict_chunked(zigp_ctx* c, const KronCall& k) {
+  if (k.N <= KRON_PREDICT_CHUNK) return kron_run(c, k);
+  const int ldx = k.p->D0 + k.p->D1, rows = k.nlat == 2 ? 9 : 4;
   std::vector<double> tmp((size_t)rows * KRON_PREDICT_CHUNK);
-  for (int64_t n0 = 0; n0 < N; n0 += KRON_PREDICT_CHUNK) {
-    const int64_t nc = std::min(KRON_PREDICT_CHUNK, N - n0);
-    ZIGP_TRY(kron_run(c, p, Xnew + n0 * ldx, nullptr, nc, jitter, 1.0, g_offset, f_mu, 0, true, tmp.data(), nullptr, nullptr, nullptr, lik, nullptr));
-    for (int r = 0; r < rows; ++r) memcpy(out + (size_t)r * N + n0, tmp.data() + (size_t)r * nc, sizeof(double) * nc);
+  KronCall kc = k;
+  kc.out = tmp.data();
+  for (int64_t n0 = 0; n0 < k.N; n0 += KRON_PREDICT_CHUNK) {
+    kc.X = k.X + n0 * ldx; kc.N = std::min(KRON_PREDICT_CHUNK, k.N - n0);
+    ZIGP_TRY(kron_run(c, kc));
+    for (int r = 0; r < rows; ++r) memcpy(k.out + (size_t)r * k.N + n0, tmp.data() + (size_t)r * kc.N, sizeof(double) * kc.N);
   }
   return ZIGP_OK;
 }
 // An EMPTY row set (a rank of a data-parallel run whose shard is empty) still has to make the same calls as its peers -- the exchange
 // inside the step is collective.  It is evaluated as ONE row at the origin with scale 0: the data term and every data-term gradient
 // are exactly zero, the KL part follows include_kl as usual.
-static const double kron_no_rows[2 * MAXD] = {0};
+const double kron_no_rows[2 * MAXD] = {0};
+
+// ---- the entry-point layer: each public function fills a KronCall with its arguments and names itself (`name`, for the messages) and,
+// for a single-latent head, its on/off counterpart (`twin`; nullptr for the on/off entry points) ----
+int kron_refuse(zigp_ctx* c, const char* name, const std::string& what) { c->err = std::string(name) + ": " + what; return ZIGP_EARG; }
+
+// zigp_kron[_head]_elbo (rows == nullptr: k.N host rows k.X, k.Y) and zigp_kron[_head]_elbo_rows (rows[0] .. rows[1] of the resident data set)
+int kron_elbo_entry(zigp_ctx* c, const char* name, const char* twin, KronCall k, const int64_t* rows) {
+  if (!c) return ZIGP_EARG;
+  if (twin && k.lik == ZIGP_LIK_ONOFF) return kron_refuse(c, name, std::string("use ") + twin + " for the OnOff likelihood");
+  ZIGP_TRY(validate_kron(c, k.p, k.lik));
+  if (!rows && (k.N < 0 || (k.N > 0 && (!k.X || !k.Y)))) return kron_refuse(c, name, "need X, Y for N > 0 rows");
+  if (!(k.jitter >= 0)) return kron_refuse(c, name, "jitter must be >= 0");
+  const bool empty = rows ? (rows[0] == rows[1] && rows[0] >= 0 && rows[0] <= c->N) : k.N == 0;
+  if (rows && !empty) {
+    if (!c->dX) return kron_refuse(c, name, "no data set (call zigp_set_data first)");
+    if (k.p->D0 + k.p->D1 != c->D) return kron_refuse(c, name, "D0 + D1 differs from the data's D");
+    if (rows[0] < 0 || rows[1] > c->N || rows[0] > rows[1]) return kron_refuse(c, name, "bad row range");
+    k.X = c->dX + rows[0] * c->D; k.Y = c->dY + rows[0]; k.N = rows[1] - rows[0]; k.dev_xy = true;
+  }
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  if (empty) { k.X = k.Y = kron_no_rows; k.N = 1; k.scale = 0.0; }      // zero data term, same calls as the peers of an empty shard
+  kron_call_derive(k);
+  return kron_run(c, k);
+}
+
+// zigp_kron[_head]_predict: k.N rows k.X -> k.out
+int kron_predict_entry(zigp_ctx* c, const char* name, const char* twin, KronCall k) {
+  if (!c) return ZIGP_EARG;
+  if (twin && k.lik == ZIGP_LIK_ONOFF) return kron_refuse(c, name, std::string("use ") + twin + " for the OnOff likelihood");
+  ZIGP_TRY(validate_kron(c, k.p, k.lik));
+  if (k.N < 0 || (k.N > 0 && (!k.X || !k.out))) return kron_refuse(c, name, "bad arguments");
+  if (k.N == 0) return ZIGP_OK;
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  k.scale = 1.0; k.predict = true;
+  kron_call_derive(k);
+  return kron_predict_chunked(c, k);
+}
+
+const int32_t* fit_trainable(const zigp_kron_fit_opts*) { return nullptr; }
+const int32_t* fit_trainable(const zigp_kron_head_fit_opts* o) { return o->trainable; }
+
+// zigp_kron_fit_steps / zigp_kron_head_fit_steps (Opts tells them apart).  fit: the caller's state, steps and batches; its per-block
+// options are taken from opts here, behind the NULL check.  rows_entry: the entry point a grid beyond the fused kernels is sent to.
+template <class Opts>
+int kron_fit_entry(zigp_ctx* c, const char* name, const char* rows_entry, const Opts* opts, KfFitCall fit, KronCall k) {
+  constexpr bool head = std::is_same<Opts, zigp_kron_head_fit_opts>::value;
+  const zigp_kron_params* p = k.p;
+  if (!c) return ZIGP_EARG;
+  c->fit_steps_applied = 0;      // whatever ends this call early, no update of it has been applied
+  if (!p || !opts || !fit.x || !fit.m || !fit.v || !fit.row_begin) return kron_refuse(c, name, "NULL argument");
+  if (head && k.lik != ZIGP_LIK_GAUSSIAN && k.lik != ZIGP_LIK_BERNOULLI)
+    return kron_refuse(c, name, "the likelihood must be ZIGP_LIK_GAUSSIAN or ZIGP_LIK_BERNOULLI (the OnOff fit is zigp_kron_fit_steps)");
+  if (p->M0f <= 0 || p->M1f <= 0 || (!head && (p->M0g <= 0 || p->M1g <= 0))) return fail_arg(c, "inducing counts must be positive");
+  if (p->D0 <= 0 || p->D1 <= 0 || p->D0 > MAXD || p->D1 > MAXD) return fail_arg(c, "factor dimensions must be in [1, 8]");
+  if (fit.n_steps <= 0 || fit.batch <= 0 || fit.t0 < 0) return kron_refuse(c, name, "need n_steps > 0, batch > 0, t0 >= 0");
+  if (!(k.jitter >= 0)) return kron_refuse(c, name, "jitter must be >= 0");
+  if (!(opts->beta1 >= 0 && opts->beta1 < 1 && opts->beta2 >= 0 && opts->beta2 < 1 && opts->eps > 0)) return kron_refuse(c, name, "bad Adam constants");
+  if (!c->dX) return kron_refuse(c, name, "no data set (call zigp_set_data first)");
+  if (p->D0 + p->D1 != c->D) return kron_refuse(c, name, "D0 + D1 differs from the data's D");
+  if (c->kron_panels || !kf_eligible(p, head ? 1 : 2))
+    return kron_refuse(c, name, std::string("this inducing grid is beyond the fused Kronecker kernels (<= 32 x <= 32 or <= 16 x <= 112 points): step it with ") +
+                                    rows_entry + " and a host optimiser");
+  if (head && fit.n_free != (int64_t)p->M0f * p->D0 + (int64_t)p->M1f * p->D1 + 2 * (int64_t)p->M0f * p->M1f + p->D0 + p->D1 + 4)
+    return kron_refuse(c, name, "n_free does not match the model sizes");
+  for (int i = 0; i < fit.n_steps; ++i) {
+    if (fit.row_begin[i] >= 0 ? fit.row_begin[i] + fit.batch > c->N : (!fit.Xw || !fit.Yw))
+      return kron_refuse(c, name, "a row range leaves the resident data set (or a host batch without Xw / Yw)");
+  }
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  fit.name = name; fit.head = head;
+  fit.lr = opts->lr; fit.positive = opts->positive; fit.trainable = fit_trainable(opts);
+  fit.beta1 = opts->beta1; fit.beta2 = opts->beta2; fit.eps = opts->eps;
+  k.X = c->dX; k.Y = c->dY; k.N = fit.batch; k.dev_xy = true;      // p carries the sizes only: the parameters come from the free state
+  kron_call_derive(k);
+  k.need_grad = true;
+  return kronf_run(c, k, &fit);
+}
 }  // namespace
 
 extern "C" {
 
 int zigp_kron_elbo(zigp_ctx* c, const zigp_kron_params* p, const double* X, const double* Y, int64_t N, double jitter, double scale,
                    double g_offset, double f_mu, int32_t include_kl, double* elbo_data, double* kl, zigp_kron_grads* grads, double* d_f_mu) {
-  if (!c) return ZIGP_EARG;
-  ZIGP_TRY(validate_kron(c, p));
-  if (N < 0 || (N > 0 && (!X || !Y))) return fail_arg(c, "zigp_kron_elbo: need X, Y for N > 0 rows");
-  if (!(jitter >= 0)) return fail_arg(c, "zigp_kron_elbo: jitter must be >= 0");
-  ZIGP_HIP(c, hipSetDevice(c->device));
-  if (N == 0) return kron_run(c, p, kron_no_rows, kron_no_rows, 1, jitter, 0.0, g_offset, f_mu, include_kl, false, nullptr, elbo_data, kl, grads, ZIGP_LIK_ONOFF, d_f_mu);
-  return kron_run(c, p, X, Y, N, jitter, scale, g_offset, f_mu, include_kl, false, nullptr, elbo_data, kl, grads, ZIGP_LIK_ONOFF, d_f_mu);
+  KronCall k = {};
+  k.p = p; k.lik = ZIGP_LIK_ONOFF; k.X = X; k.Y = Y; k.N = N; k.jitter = jitter; k.scale = scale; k.g_offset = g_offset; k.f_mu = f_mu;
+  k.include_kl = include_kl; k.elbo_data = elbo_data; k.kl = kl; k.grads = grads; k.d_offset = d_f_mu;
+  return kron_elbo_entry(c, "zigp_kron_elbo", nullptr, k, nullptr);
 }
 
 int zigp_kron_elbo_rows(zigp_ctx* c, const zigp_kron_params* p, int64_t row_begin, int64_t row_end, double jitter, double scale, double g_offset,
                         double f_mu, int32_t include_kl, double* elbo_data, double* kl, zigp_kron_grads* grads, double* d_f_mu) {
-  if (!c) return ZIGP_EARG;
-  ZIGP_TRY(validate_kron(c, p));
-  if (!(jitter >= 0)) return fail_arg(c, "zigp_kron_elbo_rows: jitter must be >= 0");
-  if (row_begin == row_end && row_begin >= 0 && row_begin <= c->N) {     // an empty range (an empty shard of a data-parallel run): zero data term, same calls as its peers
-    ZIGP_HIP(c, hipSetDevice(c->device));
-    return kron_run(c, p, kron_no_rows, kron_no_rows, 1, jitter, 0.0, g_offset, f_mu, include_kl, false, nullptr, elbo_data, kl, grads, ZIGP_LIK_ONOFF, d_f_mu);
-  }
-  if (!c->dX) return fail_arg(c, "zigp_kron_elbo_rows: no data set (call zigp_set_data first)");
-  if (p->D0 + p->D1 != c->D) return fail_arg(c, "zigp_kron_elbo_rows: D0 + D1 differs from the data's D");
-  if (row_begin < 0 || row_end > c->N || row_begin > row_end) return fail_arg(c, "zigp_kron_elbo_rows: bad row range");
-  ZIGP_HIP(c, hipSetDevice(c->device));
-  return kron_run(c, p, c->dX + row_begin * c->D, c->dY + row_begin, row_end - row_begin, jitter, scale, g_offset, f_mu, include_kl, false, nullptr,
-                  elbo_data, kl, grads, ZIGP_LIK_ONOFF, d_f_mu, true);
+  const int64_t rows[2] = {row_begin, row_end};
+  KronCall k = {};
+  k.p = p; k.lik = ZIGP_LIK_ONOFF; k.jitter = jitter; k.scale = scale; k.g_offset = g_offset; k.f_mu = f_mu;
+  k.include_kl = include_kl; k.elbo_data = elbo_data; k.kl = kl; k.grads = grads; k.d_offset = d_f_mu;
+  return kron_elbo_entry(c, "zigp_kron_elbo_rows", nullptr, k, rows);
+}
+
+int zigp_kron_head_elbo(zigp_ctx* c, const zigp_kron_params* p, int32_t lik, const double* X, const double* Y, int64_t N, double jitter,
+                        double scale, double f_mu, int32_t include_kl, double* elbo_data, double* kl, zigp_kron_grads* grads, double* d_f_mu) {
+  KronCall k = {};
+  k.p = p; k.lik = lik; k.X = X; k.Y = Y; k.N = N; k.jitter = jitter; k.scale = scale; k.f_mu = f_mu;
+  k.include_kl = include_kl; k.elbo_data = elbo_data; k.kl = kl; k.grads = grads; k.d_offset = d_f_mu;
+  return kron_elbo_entry(c, "zigp_kron_head_elbo", "zigp_kron_elbo", k, nullptr);
+}
+
+int zigp_kron_head_elbo_rows(zigp_ctx* c, const zigp_kron_params* p, int32_t lik, int64_t row_begin, int64_t row_end, double jitter, double scale,
+                             double f_mu, int32_t include_kl, double* elbo_data, double* kl, zigp_kron_grads* grads, double* d_f_mu) {
+  const int64_t rows[2] = {row_begin, row_end};
+  KronCall k = {};
+  k.p = p; k.lik = lik; k.jitter = jitter; k.scale = scale; k.f_mu = f_mu;
+  k.include_kl = include_kl; k.elbo_data = elbo_data; k.kl = kl; k.grads = grads; k.d_offset = d_f_mu;
+  return kron_elbo_entry(c, "zigp_kron_head_elbo_rows", "zigp_kron_elbo_rows", k, rows);
+}
+
+int zigp_kron_predict(zigp_ctx* c, const zigp_kron_params* p, const double* Xnew, int64_t N, double jitter, double g_offset, double f_mu, double* out9) {
+  KronCall k = {};
+  k.p = p; k.lik = ZIGP_LIK_ONOFF; k.X = Xnew; k.N = N; k.jitter = jitter; k.g_offset = g_offset; k.f_mu = f_mu; k.out = out9;
+  return kron_predict_entry(c, "zigp_kron_predict", nullptr, k);
+}
+
+int zigp_kron_head_predict(zigp_ctx* c, const zigp_kron_params* p, int32_t lik, const double* Xnew, int64_t N, double jitter, double f_mu,
+                           double* out4) {
+  KronCall k = {};
+  k.p = p; k.lik = lik; k.X = Xnew; k.N = N; k.jitter = jitter; k.f_mu = f_mu; k.out = out4;
+  return kron_predict_entry(c, "zigp_kron_head_predict", "zigp_kron_predict", k);
 }
 
 int zigp_kron_fit_steps(zigp_ctx* c, const zigp_kron_params* p, const zigp_kron_fit_opts* opts, double* free_state, double* adam_m, double* adam_v,
                         int64_t n_free, int64_t t0, int32_t n_steps, const int64_t* row_begin, int64_t batch, const double* Xw, const double* Yw,
                         double jitter, double scale, int32_t include_kl, double* elbo_data, double* kl) {
-  if (!c) return ZIGP_EARG;
-  c->fit_steps_applied = 0;      // whatever ends this call early, no update of it has been applied
-  if (!p || !opts || !free_state || !adam_m || !adam_v || !row_begin) return fail_arg(c, "zigp_kron_fit_steps: NULL argument");
-  if (p->M0f <= 0 || p->M1f <= 0 || p->M0g <= 0 || p->M1g <= 0) return fail_arg(c, "inducing counts must be positive");
-  if (p->D0 <= 0 || p->D1 <= 0 || p->D0 > MAXD || p->D1 > MAXD) return fail_arg(c, "factor dimensions must be in [1, 8]");
-  if (n_steps <= 0 || batch <= 0 || t0 < 0) return fail_arg(c, "zigp_kron_fit_steps: need n_steps > 0, batch > 0, t0 >= 0");
-  if (!(jitter >= 0)) return fail_arg(c, "zigp_kron_fit_steps: jitter must be >= 0");
-  if (!(opts->beta1 >= 0 && opts->beta1 < 1 && opts->beta2 >= 0 && opts->beta2 < 1 && opts->eps > 0)) return fail_arg(c, "zigp_kron_fit_steps: bad Adam constants");
-  if (!c->dX) return fail_arg(c, "zigp_kron_fit_steps: no data set (call zigp_set_data first)");
-  if (p->D0 + p->D1 != c->D) return fail_arg(c, "zigp_kron_fit_steps: D0 + D1 differs from the data's D");
-  if (c->kron_panels || !kf_eligible(p, 2))
-    return fail_arg(c, "zigp_kron_fit_steps: this inducing grid is beyond the fused Kronecker kernels (<= 32 x <= 32 or <= 16 x <= 112 points): "
-                       "step it with zigp_kron_elbo_rows and a host optimiser");
-  for (int i = 0; i < n_steps; ++i) {
-    if (row_begin[i] >= 0 ? row_begin[i] + batch > c->N : (!Xw || !Yw)) return fail_arg(c, "zigp_kron_fit_steps: a row range leaves the resident data set (or a host batch without Xw / Yw)");
-  }
-  ZIGP_HIP(c, hipSetDevice(c->device));
-  KfFitCall fit = {"zigp_kron_fit_steps", false, opts->lr, opts->positive, nullptr, opts->beta1, opts->beta2, opts->eps,
-                   free_state, adam_m, adam_v, n_free, t0, (int)n_steps, row_begin, batch, Xw, Yw, elbo_data, kl};
-  return kronf_run(c, p, c->dX, c->dY, batch, jitter, scale, 0.0, 0.0, include_kl, false, nullptr, nullptr, nullptr, nullptr, ZIGP_LIK_ONOFF, nullptr, true, &fit);
+  KfFitCall fit = {};
+  fit.x = free_state; fit.m = adam_m; fit.v = adam_v; fit.n_free = n_free; fit.t0 = t0; fit.n_steps = (int)n_steps; fit.row_begin = row_begin;
+  fit.batch = batch; fit.Xw = Xw; fit.Yw = Yw; fit.hist_data = elbo_data; fit.hist_kl = kl;
+  KronCall k = {};
+  k.p = p; k.lik = ZIGP_LIK_ONOFF; k.jitter = jitter; k.scale = scale; k.include_kl = include_kl;
+  return kron_fit_entry(c, "zigp_kron_fit_steps", "zigp_kron_elbo_rows", opts, fit, k);
 }
 
 int zigp_kron_head_fit_steps(zigp_ctx* c, const zigp_kron_params* p, int32_t lik, const zigp_kron_head_fit_opts* opts, double* free_state,
                              double* adam_m, double* adam_v, int64_t n_free, int64_t t0, int32_t n_steps, const int64_t* row_begin, int64_t batch,
                              const double* Xw, const double* Yw, double jitter, double scale, int32_t include_kl, double* elbo_data, double* kl) {
-  if (!c) return ZIGP_EARG;
-  c->fit_steps_applied = 0;      // whatever ends this call early, no update of it has been applied
-  if (!p || !opts || !free_state || !adam_m || !adam_v || !row_begin) return fail_arg(c, "zigp_kron_head_fit_steps: NULL argument");
-  if (lik != ZIGP_LIK_GAUSSIAN && lik != ZIGP_LIK_BERNOULLI)
-    return fail_arg(c, "zigp_kron_head_fit_steps: the likelihood must be ZIGP_LIK_GAUSSIAN or ZIGP_LIK_BERNOULLI (the OnOff fit is zigp_kron_fit_steps)");
-  if (p->M0f <= 0 || p->M1f <= 0) return fail_arg(c, "inducing counts must be positive");
-  if (p->D0 <= 0 || p->D1 <= 0 || p->D0 > MAXD || p->D1 > MAXD) return fail_arg(c, "factor dimensions must be in [1, 8]");
-  if (n_steps <= 0 || batch <= 0 || t0 < 0) return fail_arg(c, "zigp_kron_head_fit_steps: need n_steps > 0, batch > 0, t0 >= 0");
-  if (!(jitter >= 0)) return fail_arg(c, "zigp_kron_head_fit_steps: jitter must be >= 0");
-  if (!(opts->beta1 >= 0 && opts->beta1 < 1 && opts->beta2 >= 0 && opts->beta2 < 1 && opts->eps > 0)) return fail_arg(c, "zigp_kron_head_fit_steps: bad Adam constants");
-  if (!c->dX) return fail_arg(c, "zigp_kron_head_fit_steps: no data set (call zigp_set_data first)");
-  if (p->D0 + p->D1 != c->D) return fail_arg(c, "zigp_kron_head_fit_steps: D0 + D1 differs from the data's D");
-  if (c->kron_panels || !kf_eligible(p, 1))
-    return fail_arg(c, "zigp_kron_head_fit_steps: this inducing grid is beyond the fused Kronecker kernels (<= 32 x <= 32 or <= 16 x <= 112 points): "
-                       "step it with zigp_kron_head_elbo_rows and a host optimiser");
-  if (n_free != (int64_t)p->M0f * p->D0 + (int64_t)p->M1f * p->D1 + 2 * (int64_t)p->M0f * p->M1f + p->D0 + p->D1 + 4)
-    return fail_arg(c, "zigp_kron_head_fit_steps: n_free does not match the model sizes");
-  for (int i = 0; i < n_steps; ++i) {
-    if (row_begin[i] >= 0 ? row_begin[i] + batch > c->N : (!Xw || !Yw)) return fail_arg(c, "zigp_kron_head_fit_steps: a row range leaves the resident data set (or a host batch without Xw / Yw)");
-  }
-  ZIGP_HIP(c, hipSetDevice(c->device));
-  KfFitCall fit = {"zigp_kron_head_fit_steps", true, opts->lr, opts->positive, opts->trainable, opts->beta1, opts->beta2, opts->eps,
-                   free_state, adam_m, adam_v, n_free, t0, (int)n_steps, row_begin, batch, Xw, Yw, elbo_data, kl};
-  return kronf_run(c, p, c->dX, c->dY, batch, jitter, scale, 0.0, 0.0, include_kl, false, nullptr, nullptr, nullptr, nullptr, lik, nullptr, true, &fit);
+  KfFitCall fit = {};
+  fit.x = free_state; fit.m = adam_m; fit.v = adam_v; fit.n_free = n_free; fit.t0 = t0; fit.n_steps = (int)n_steps; fit.row_begin = row_begin;
+  fit.batch = batch; fit.Xw = Xw; fit.Yw = Yw; fit.hist_data = elbo_data; fit.hist_kl = kl;
+  KronCall k = {};
+  k.p = p; k.lik = lik; k.jitter = jitter; k.scale = scale; k.include_kl = include_kl;
+  return kron_fit_entry(c, "zigp_kron_head_fit_steps", "zigp_kron_head_elbo_rows", opts, fit, k);
 }
 
 int64_t zigp_kron_fit_steps_applied(zigp_ctx* c) { return c ? c->fit_steps_applied : (int64_t)ZIGP_EARG; }
-
-int zigp_kron_predict(zigp_ctx* c, const zigp_kron_params* p, const double* Xnew, int64_t N, double jitter, double g_offset, double f_mu, double* out9) {
-  if (!c) return ZIGP_EARG;
-  ZIGP_TRY(validate_kron(c, p));
-  if (N < 0 || (N > 0 && (!Xnew || !out9))) return fail_arg(c, "zigp_kron_predict: bad arguments");
-  if (N == 0) return ZIGP_OK;
-  ZIGP_HIP(c, hipSetDevice(c->device));
-  return kron_predict_chunked(c, p, Xnew, N, jitter, g_offset, f_mu, out9, ZIGP_LIK_ONOFF, 9);
-}
-
-int zigp_kron_head_elbo(zigp_ctx* c, const zigp_kron_params* p, int32_t lik, const double* X, const double* Y, int64_t N, double jitter,
-                        double scale, double f_mu, int32_t include_kl, double* elbo_data, double* kl, zigp_kron_grads* grads, double* d_f_mu) {
-  if (!c) return ZIGP_EARG;
-  if (lik == ZIGP_LIK_ONOFF) return fail_arg(c, "zigp_kron_head_elbo: use zigp_kron_elbo for the OnOff likelihood");
-  ZIGP_TRY(validate_kron(c, p, lik));
-  if (N < 0 || (N > 0 && (!X || !Y))) return fail_arg(c, "zigp_kron_head_elbo: need X, Y for N > 0 rows");
-  if (!(jitter >= 0)) return fail_arg(c, "zigp_kron_head_elbo: jitter must be >= 0");
-  ZIGP_HIP(c, hipSetDevice(c->device));
-  if (N == 0) return kron_run(c, p, kron_no_rows, kron_no_rows, 1, jitter, 0.0, 0.0, f_mu, include_kl, false, nullptr, elbo_data, kl, grads, lik, d_f_mu);
-  return kron_run(c, p, X, Y, N, jitter, scale, 0.0, f_mu, include_kl, false, nullptr, elbo_data, kl, grads, lik, d_f_mu);
-}
-
-int zigp_kron_head_elbo_rows(zigp_ctx* c, const zigp_kron_params* p, int32_t lik, int64_t row_begin, int64_t row_end, double jitter, double scale,
-                             double f_mu, int32_t include_kl, double* elbo_data, double* kl, zigp_kron_grads* grads, double* d_f_mu) {
-  if (!c) return ZIGP_EARG;
-  if (lik == ZIGP_LIK_ONOFF) return fail_arg(c, "zigp_kron_head_elbo_rows: use zigp_kron_elbo_rows for the OnOff likelihood");
-  ZIGP_TRY(validate_kron(c, p, lik));
-  if (!(jitter >= 0)) return fail_arg(c, "zigp_kron_head_elbo_rows: jitter must be >= 0");
-  if (row_begin == row_end && row_begin >= 0 && row_begin <= c->N) {     // an empty range (an empty shard of a data-parallel run): zero data term, same calls as its peers
-    ZIGP_HIP(c, hipSetDevice(c->device));
-    return kron_run(c, p, kron_no_rows, kron_no_rows, 1, jitter, 0.0, 0.0, f_mu, include_kl, false, nullptr, elbo_data, kl, grads, lik, d_f_mu);
-  }
-  if (!c->dX) return fail_arg(c, "zigp_kron_head_elbo_rows: no data set (call zigp_set_data first)");
-  if (p->D0 + p->D1 != c->D) return fail_arg(c, "zigp_kron_head_elbo_rows: D0 + D1 differs from the data's D");
-  if (row_begin < 0 || row_end > c->N || row_begin > row_end) return fail_arg(c, "zigp_kron_head_elbo_rows: bad row range");
-  ZIGP_HIP(c, hipSetDevice(c->device));
-  return kron_run(c, p, c->dX + row_begin * c->D, c->dY + row_begin, row_end - row_begin, jitter, scale, 0.0, f_mu, include_kl, false, nullptr,
-                  elbo_data, kl, grads, lik, d_f_mu, true);
-}
-
-int zigp_kron_head_predict(zigp_ctx* c, const zigp_kron_params* p, int32_t lik, const double* Xnew, int64_t N, double jitter, double f_mu,
-                           double* out4) {
-  if (!c) return ZIGP_EARG;
-  if (lik == ZIGP_LIK_ONOFF) return fail_arg(c, "zigp_kron_head_predict: use zigp_kron_predict for the OnOff likelihood");
-  ZIGP_TRY(validate_kron(c, p, lik));
-  if (N < 0 || (N > 0 && (!Xnew || !out4))) return fail_arg(c, "zigp_kron_head_predict: bad arguments");
-  if (N == 0) return ZIGP_OK;
-  ZIGP_HIP(c, hipSetDevice(c->device));
-  return kron_predict_chunked(c, p, Xnew, N, jitter, 0.0, f_mu, out4, lik, 4);
-}
 
 
 int zigp_set_kron_range_tiles(zigp_ctx* c, int32_t tiles) {
@@ -972,7 +940,7 @@ int zigp_test_kron_pointwise(zigp_ctx* c, const zigp_stage_kron_pointwise* s) {
     // the block kronf_run stages (kf_fill_hyp); the lengthscale slots are not read by these kernels
     double H[KH_SIZE], one[MAXD];
     for (double& v : one) v = 1.0;
-    const KfHostLatent hl[2] = {{{1, 1}, {nullptr, nullptr}, {one, one}, {s->var0f, s->var1f}, nullptr, nullptr},
+    const KronHostLatent hl[2] ={{{1, 1}, {nullptr, nullptr}, {one, one}, {s->var0f, s->var1f}, nullptr, nullptr},
                                 {{1, 1}, {nullptr, nullptr}, {one, one}, {s->var0g, s->var1g}, nullptr, nullptr}};
     kf_fill_hyp(H, hl, two ? 2 : 1, 1, 1, s->noise);
     H[KH_FMU] = s->f_offset;                    // the slot k_fit_update writes f_mu to
@@ -1013,8 +981,11 @@ int zigp_test_kron_fused_step(zigp_ctx* c, const zigp_stage_kron_fused* s) {
   memset(tap.facts, 0, sizeof(tap.facts));
   for (int h = 0; h < nlat; ++h)
     if (s->lat[h].inject) ZIGP_TRY(stage_upload_rows(c, tap.inject[h], s->lat[h].inject, 4, 4, s->N));
-  ZIGP_TRY(kronf_run(c, s->p, s->X, s->Y, s->N, s->jitter, s->scale, s->g_offset, s->f_mu, s->include_kl, false, nullptr, s->elbo_data, s->kl, s->grads,
-                     s->lik, s->d_f_mu, false, nullptr, &tap));
+  KronCall k = {};
+  k.p = s->p; k.lik = s->lik; k.X = s->X; k.Y = s->Y; k.N = s->N; k.jitter = s->jitter; k.scale = s->scale; k.g_offset = s->g_offset; k.f_mu = s->f_mu;
+  k.include_kl = s->include_kl; k.elbo_data = s->elbo_data; k.kl = s->kl; k.grads = s->grads; k.d_offset = s->d_f_mu;
+  kron_call_derive(k);
+  ZIGP_TRY(kronf_run(c, k, nullptr, &tap));
   return tap.flush(c);
 }
 

@@ -1139,7 +1139,6 @@ static int kf_launch_small_latents(zigp_ctx* c, const int (*Mq)[2], int nlat, bo
   return 0;
 }
 
-struct KfHostLatent { int M[2]; const double* Z[2]; const double* ell[2]; double var[2]; const double* u; const double* s; };
 constexpr int KF_KROW_W = 2 + 2 * MAXD;
 
 // Fixed-order sums of the point-wise block partials -> pws[0..KPW_ACC) (kf_pw_reduce, above): the result block of a step has a size
@@ -1350,7 +1349,7 @@ struct KfFitCall {          // host side of one zigp_kron_fit_steps / zigp_kron_
 // Host image H [KH_SIZE] of the device hyperparameter block (KH_*, zigp_kernels.h) of a call that stages its parameters: one record per
 // (latent, factor) -- 1 / ell, ell, the variance; KH_ZC, the centre of the moment sums, is filled in by k_kf_factor -- and the noise.
 // KH_FMU stays 0: outside a fit call f_mu travels by value.
-static void kf_fill_hyp(double* H, const KfHostLatent* hl, int nlat, int D0, int D1, double noise) {
+static void kf_fill_hyp(double* H, const KronHostLatent* hl, int nlat, int D0, int D1, double noise) {
   memset(H, 0, sizeof(double) * KH_SIZE);
   for (int h = 0; h < nlat; ++h)
     for (int q = 0; q < 2; ++q) {
@@ -1389,516 +1388,595 @@ struct KfTap {
   }
 };
 
-// One ELBO step (or prediction) of the fused Kronecker path.  fit != nullptr: n_steps gradient steps with the Adam update on the device
-// (p then carries the sizes only; X / Y are the resident data set).  tap != nullptr: the step of the stage tests, snapshots around its
-// launches (an ordinary step pays one pointer test for it: the tapped body is an instantiation of its own).
-static int kronf_run(zigp_ctx* c, const zigp_kron_params* p, const double* X, const double* Y, int64_t N, double jitter, double scale,
-                     double g_offset, double f_mu, int include_kl, bool predict, double* out9, double* elbo_data, double* kl, zigp_kron_grads* grads,
-                     int lik, double* d_offset, bool dev_xy, const KfFitCall* fit = nullptr, KfTap* tap = nullptr) {
-  // dev_xy: X / Y are DEVICE pointers into the resident data set (zigp_set_data): nothing but the parameters is staged
-  const int nlat = (lik == ZIGP_LIK_ONOFF) ? 2 : 1;
-  const KfPlan pl = kf_plan(p, nlat);
-  if (!c->kronf) { c->kronf.reset(new (std::nothrow) KfState()); if (!c->kronf) { c->err = "out of memory"; return ZIGP_EHIP; } }
-  KfState& ks = *c->kronf;
-  ZIGP_TRY(begin_staged_call(c));
-  const bool need_grad = (grads != nullptr || fit != nullptr) && !predict;
-  const int D0 = p->D0, D1 = p->D1, ldx = D0 + D1;
-  const int64_t Npad = std::max<int64_t>(1024, round_up(N, 1024));
-  KfHostLatent hl[2] = {{{p->M0f, p->M1f}, {p->Z0f, p->Z1f}, {p->ell0f, p->ell1f}, {p->var0f, p->var1f}, p->u_fm, p->u_fs_sqrt},
-                        {{p->M0g, p->M1g}, {p->Z0g, p->Z1g}, {p->ell0g, p->ell1g}, {p->var0g, p->var1g}, p->u_gm, p->u_gs_sqrt}};
-  if (nlat == 1) hl[1] = hl[0];
-  // ---- sizes of this variant
-  const int R0 = 16 * pl.nb0c, R1 = 16 * pl.nb1c;
-  const KfWork wl = kf_work_layout(pl.nb0c, pl.nb1c);
-  const int nblk = kf_nblocks(pl.nb0c, pl.nb1c);
-  const size_t r01 = (size_t)R0 * R1;
-  // per-factor region of KfState::mat: K [128][128] | P | PF | dvec ; per-latent: U S2 T0 T1 Al | AlF S2F AlTF S2TF | work | scratch
-  const size_t rmax = (size_t)wl.ldw * wl.ldw;
-  const size_t FAC_P = (size_t)PB * PB, FAC_PF = FAC_P + rmax, FAC_DV = FAC_PF + rmax, FAC_ZS = FAC_DV + wl.ldw + 8, FAC_SIZE = FAC_ZS + (size_t)wl.ldw * MAXD;
-  const size_t LAT_U = 0, LAT_S2 = r01, LAT_T0 = 2 * r01, LAT_T1 = 3 * r01, LAT_AL = 4 * r01, LAT_ALF = 5 * r01, LAT_S2F = 6 * r01, LAT_ALTF = 7 * r01,
-               LAT_S2TF = 8 * r01, LAT_WORK = 9 * r01, LAT_SCR = LAT_WORK + wl.total, SCR_SET = 3 * rmax + r01 + wl.ldw, LAT_SIZE = LAT_SCR + 2 * SCR_SET;
+// Per-call state of the fused path: the plan, the layout of its device buffers and everything else the launches of a step need that
+// does not change between the steps of a call.  kf_prepare builds it once; the fit loop runs kf_step on it up to hundreds of times (a step
+// is launch-bound) and moves d_hyp only.
+struct KfRun {
+  zigp_ctx* c;
+  const KronCall* k;
+  const KfFitCall* fit;       // nullptr outside a fit call
+  KfState* ks;
+  KfPlan pl;
+  KfWork wl;
+  int nlat, D0, D1, ldx, nblk, pw_blocks;
+  int64_t N, Npad;
+  bool need_grad;
+  int Mq[2][2];
+  bool large_exact;           // every latent has exactly the capacity's block counts: the instantiation with compile-time bounds
+  size_t lds_fwd, lds_bwd;    // LDS of the larger-grid point kernels: fragment images packed by the actual block counts (max over the latents)
+  // per-factor region of KfState::mat: K [128][128] | P | PF | dvec | Zs ; per-latent: U S2 T0 T1 Al | AlF S2F AlTF S2TF | work | scratch
+  size_t FAC_P, FAC_PF, FAC_DV, FAC_ZS, FAC_SIZE;
+  size_t LAT_U, LAT_S2, LAT_T0, LAT_T1, LAT_AL, LAT_ALF, LAT_S2F, LAT_ALTF, LAT_S2TF, LAT_WORK, LAT_SCR, SCR_SET, LAT_SIZE;
   // result block: [latent f][latent g][pws: 8 sums over points][4 Cholesky status slots (8 doubles)]; everything in front of the status
   // slots is summed over ranks in a data-parallel run; behind them, not downloaded: the point-wise block partials
-  const size_t RES_KLV = 0, RES_KROW0 = 8, RES_KROW1 = RES_KROW0 + (size_t)R0 * KF_KROW_W, RES_GU = RES_KROW1 + (size_t)R1 * KF_KROW_W,
-               RES_GS = RES_GU + r01, RES_SIZE = RES_GS + r01;
-  // ---- the staged image (one host -> device copy): the PARAMETER IMAGE -- per latent Z0, Z1, u, s, then the hyperparameter block (KH_*) --
-  // followed by X, Y of a host minibatch.  In a fit call the parameter image is written by k_fit_update instead.
+  size_t RES_KLV, RES_KROW0, RES_KROW1, RES_GU, RES_GS, RES_SIZE, RES_PWS, RES_INFO, n_res;
+  // the staged image (one host -> device copy): the PARAMETER IMAGE -- per latent Z0, Z1, u, s, then the hyperparameter block (KH_*) --
+  // followed by X, Y of a host minibatch.  In a fit call the parameter image is written by k_fit_update instead, and a second
+  // hyperparameter block follows the first: step i reads block i % 2, its update writes the other.
+  size_t off_z[2][2], off_u[2], off_s[2], off_hyp, off_hyp2, off_x, off_y, n_in;
+  size_t n_wrap;              // fit: host batches behind the image, [k][N][ldx], then their Y [k][N]
+  size_t pts_lat;             // per latent in KfState::pts: part[4], gm, gv, dq0, dq1
+  double* d_hyp;              // the hyperparameter block the next step's kernels read
+  double *d_wrap, *d_pwacc;
+  int* hinfo;                 // predict: the status word on its way to the host
+  double* fac(int h, int q) const { return ks->mat.p + (size_t)(2 * h + q) * FAC_SIZE; }
+  double* lat(int h) const { return ks->mat.p + (size_t)4 * FAC_SIZE + (size_t)h * LAT_SIZE; }
+  double* pts(int h) const { return ks->pts.p + (size_t)h * pts_lat; }
+  double* res(int h) const { return ks->res.p + (size_t)h * RES_SIZE; }
+};
+
+static int kf_prepare(zigp_ctx* c, const KronCall& k, const KfFitCall* fit, KfRun& s) {
+  memset(&s, 0, sizeof(s));
+  s.c = c; s.k = &k; s.fit = fit;
+  s.nlat = k.nlat; s.need_grad = k.need_grad; s.N = k.N;
+  const KfPlan pl = s.pl = kf_plan(k.p, k.nlat);
+  if (!c->kronf) { c->kronf.reset(new (std::nothrow) KfState()); if (!c->kronf) { c->err = "out of memory"; return ZIGP_EHIP; } }
+  KfState& ks = *c->kronf;
+  s.ks = &ks;
+  ZIGP_TRY(begin_staged_call(c));
+  const KronHostLatent* hl = k.hl;
+  const int nlat = s.nlat, D0 = s.D0 = k.p->D0, D1 = s.D1 = k.p->D1, ldx = s.ldx = D0 + D1;
+  const int64_t N = s.N;
+  s.Npad = std::max<int64_t>(1024, round_up(N, 1024));
+  // ---- sizes of this variant
+  const int R0 = 16 * pl.nb0c, R1 = 16 * pl.nb1c;
+  const KfWork wl = s.wl = kf_work_layout(pl.nb0c, pl.nb1c);
+  s.nblk = kf_nblocks(pl.nb0c, pl.nb1c);
+  const size_t r01 = (size_t)R0 * R1, rmax = (size_t)wl.ldw * wl.ldw;
+  s.FAC_P = (size_t)PB * PB; s.FAC_PF = s.FAC_P + rmax; s.FAC_DV = s.FAC_PF + rmax; s.FAC_ZS = s.FAC_DV + wl.ldw + 8; s.FAC_SIZE = s.FAC_ZS + (size_t)wl.ldw * MAXD;
+  s.LAT_U = 0; s.LAT_S2 = r01; s.LAT_T0 = 2 * r01; s.LAT_T1 = 3 * r01; s.LAT_AL = 4 * r01; s.LAT_ALF = 5 * r01; s.LAT_S2F = 6 * r01; s.LAT_ALTF = 7 * r01;
+  s.LAT_S2TF = 8 * r01; s.LAT_WORK = 9 * r01; s.LAT_SCR = s.LAT_WORK + wl.total; s.SCR_SET = 3 * rmax + r01 + wl.ldw; s.LAT_SIZE = s.LAT_SCR + 2 * s.SCR_SET;
+  s.RES_KLV = 0; s.RES_KROW0 = 8; s.RES_KROW1 = s.RES_KROW0 + (size_t)R0 * KF_KROW_W; s.RES_GU = s.RES_KROW1 + (size_t)R1 * KF_KROW_W;
+  s.RES_GS = s.RES_GU + r01; s.RES_SIZE = s.RES_GS + r01;
+  s.RES_PWS = (size_t)2 * s.RES_SIZE; s.RES_INFO = s.RES_PWS + 8; s.n_res = s.RES_INFO + 8;
   size_t off = 0;
-  size_t off_z[2][2], off_u[2], off_s[2];
   for (int h = 0; h < nlat; ++h) {
-    off_z[h][0] = off; off += (size_t)hl[h].M[0] * D0;
-    off_z[h][1] = off; off += (size_t)hl[h].M[1] * D1;
-    off_u[h] = off; off += (size_t)hl[h].M[0] * hl[h].M[1];
-    off_s[h] = off; off += (size_t)hl[h].M[0] * hl[h].M[1];
+    s.off_z[h][0] = off; off += (size_t)hl[h].M[0] * D0;
+    s.off_z[h][1] = off; off += (size_t)hl[h].M[1] * D1;
+    s.off_u[h] = off; off += (size_t)hl[h].M[0] * hl[h].M[1];
+    s.off_s[h] = off; off += (size_t)hl[h].M[0] * hl[h].M[1];
   }
-  const size_t off_hyp = off; off += KH_SIZE;
-  const size_t off_hyp2 = off; off += KH_SIZE;      // second hyperparameter block (fit calls: step i reads block i % 2, its update writes the other)
-  const size_t n_par = off;
-  const size_t off_x = n_par, off_y = dev_xy ? off_x : off_x + (size_t)N * ldx;
-  const size_t n_in = dev_xy ? n_par : off_y + (size_t)N;
-  const size_t n_wrap = fit ? [&] { size_t k = 0; for (int i = 0; i < fit->n_steps; ++i) if (fit->row_begin[i] < 0) k = std::max<size_t>(k, (size_t)(-fit->row_begin[i])); return k; }() : 0;
-  ZIGP_ENSURE(c, ks.in, n_in + n_wrap * (size_t)N * (ldx + 1));
-  double* d_hyp = ks.in.p + off_hyp;          // the hyperparameter block the next enqueue()'s kernels read
-  double* const d_wrap = ks.in.p + n_in;      // fit: host batches [k][N][ldx], then their Y [k][N]
-  if (!fit) {
-    ZIGP_PINNED(c, hin, n_in);
-    if (!dev_xy) {
-      memcpy(hin + off_x, X, sizeof(double) * N * ldx);
-      if (Y) memcpy(hin + off_y, Y, sizeof(double) * N); else memset(hin + off_y, 0, sizeof(double) * N);
-    }
-    for (int h = 0; h < nlat; ++h) {
-      memcpy(hin + off_z[h][0], hl[h].Z[0], sizeof(double) * hl[h].M[0] * D0);
-      memcpy(hin + off_z[h][1], hl[h].Z[1], sizeof(double) * hl[h].M[1] * D1);
-      memcpy(hin + off_u[h], hl[h].u, sizeof(double) * hl[h].M[0] * hl[h].M[1]);
-      memcpy(hin + off_s[h], hl[h].s, sizeof(double) * hl[h].M[0] * hl[h].M[1]);
-    }
-    kf_fill_hyp(hin + off_hyp, hl, nlat, D0, D1, p->noise);
-    ZIGP_HIP(c, hipMemcpyAsync(ks.in.p, hin, sizeof(double) * n_in, hipMemcpyHostToDevice, c->stream));
-  }
-  if (predict) ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
-  ZIGP_ENSURE(c, ks.mat, (size_t)4 * FAC_SIZE + 2 * LAT_SIZE);
-  const int pw_blocks = (int)(Npad / PW_THREADS);
-  const size_t pts_lat = (size_t)8 * Npad;   // part[4], gm, gv, dq0, dq1
-  ZIGP_ENSURE(c, ks.pts, 2 * pts_lat);
-  const size_t RES_PWS = (size_t)2 * RES_SIZE, RES_INFO = RES_PWS + 8, n_res = RES_INFO + 8;
-  ZIGP_ENSURE(c, ks.res, n_res + (size_t)pw_blocks * KPW_ACC);
-  auto fac = [&](int h, int q) { return ks.mat.p + (size_t)(2 * h + q) * FAC_SIZE; };
-  auto lat = [&](int h) { return ks.mat.p + (size_t)4 * FAC_SIZE + (size_t)h * LAT_SIZE; };
-  auto pts = [&](int h) { return ks.pts.p + (size_t)h * pts_lat; };
-  auto res = [&](int h) { return ks.res.p + (size_t)h * RES_SIZE; };
-  double* d_pwacc = ks.res.p + n_res;
-
-  int Mq[2][2];
+  s.off_hyp = off; off += KH_SIZE;
+  s.off_hyp2 = off; off += KH_SIZE;
+  s.off_x = off; s.off_y = k.dev_xy ? s.off_x : s.off_x + (size_t)N * ldx;
+  s.n_in = k.dev_xy ? off : s.off_y + (size_t)N;
+  if (fit)
+    for (int i = 0; i < fit->n_steps; ++i)
+      if (fit->row_begin[i] < 0) s.n_wrap = std::max<size_t>(s.n_wrap, (size_t)(-fit->row_begin[i]));
+  s.pw_blocks = (int)(s.Npad / PW_THREADS);
+  s.pts_lat = (size_t)8 * s.Npad;
+  ZIGP_ENSURE(c, ks.in, s.n_in + s.n_wrap * (size_t)N * (ldx + 1));
+  ZIGP_ENSURE(c, ks.mat, (size_t)4 * s.FAC_SIZE + 2 * s.LAT_SIZE);
+  ZIGP_ENSURE(c, ks.pts, 2 * s.pts_lat);
+  ZIGP_ENSURE(c, ks.res, s.n_res + (size_t)s.pw_blocks * KPW_ACC);
+  s.d_hyp = ks.in.p + s.off_hyp;
+  s.d_wrap = ks.in.p + s.n_in;
+  s.d_pwacc = ks.res.p + s.n_res;
   for (int h = 0; h < nlat; ++h)
-    for (int q = 0; q < 2; ++q) Mq[h][q] = (int)round_up(hl[h].M[q], 16);
-  bool large_exact = pl.large;   // every latent has exactly the capacity's block counts: the instantiation with compile-time bounds
-  for (int h = 0; h < nlat; ++h) large_exact = large_exact && Mq[h][0] == 16 * pl.nb0c && Mq[h][1] == 16 * pl.nb1c;
-  // LDS of the larger-grid point kernels: fragment images packed by the actual block counts (max over the latents)
-  size_t lds_fwd = 0, lds_bwd = 0;
+    for (int q = 0; q < 2; ++q) s.Mq[h][q] = (int)round_up(hl[h].M[q], 16);
+  s.large_exact = pl.large;
+  for (int h = 0; h < nlat; ++h) s.large_exact = s.large_exact && s.Mq[h][0] == 16 * pl.nb0c && s.Mq[h][1] == 16 * pl.nb1c;
   for (int h = 0; h < nlat; ++h) {
-    const size_t b0 = Mq[h][0] / 16, b1 = Mq[h][1] / 16;
-    lds_fwd = std::max(lds_fwd, sizeof(double) * 256 * (b0 * b0 + b1 * b1 + 2 * b0 * b1));
-    lds_bwd = std::max(lds_bwd, sizeof(double) * 256 * (b0 * b0 + b1 * b1 + 4 * b0 * b1));
-  }
-  static bool attr_set = false;
-  if (!attr_set) {
-    ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kf_factor), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * PB * PBLD)));
-    ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kf_finish), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KF_FIN_LDS));
-    ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_forward<1, 7, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_backward<1, 7, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_forward<1, 7, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_backward<1, 7, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_latent), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kfl_latent_lds(16 * 7)));
-    attr_set = true;
-  }
-  int* hinfo = nullptr;
-
-  // ---- the launches of ONE step on rows (Xd, Yd) -- everything else it reads lives on the device (parameter image, hyper block)
-  auto enqueue = [&](auto tapped, const double* Xd, const double* Yd) -> int {
-    constexpr bool TAP = decltype(tapped)::value;
-    if (c->comm && !predict) ZIGP_HIP(c, hipMemsetAsync(ks.res.p, 0, sizeof(double) * RES_INFO, c->stream));   // parts a value-only / single-latent step leaves unwritten
-    // ---- factor stage
-    {
-      KfFactorArgs fa;
-      memset(&fa, 0, sizeof(fa));
-      for (int h = 0; h < nlat; ++h)
-        for (int q = 0; q < 2; ++q) {
-          KfFactorJob& jb = fa.job[2 * h + q];
-          jb.Z = ks.in.p + off_z[h][q]; jb.M = hl[h].M[q]; jb.D = q == 0 ? D0 : D1; jb.Mq = Mq[h][q];
-          jb.hyp = d_hyp + (2 * h + q) * KH_FAC; jb.zc_out = d_hyp + (2 * h + q) * KH_FAC + KH_ZC;
-          jb.K = fac(h, q); jb.P = fac(h, q) + FAC_P; jb.PF = fac(h, q) + FAC_PF; jb.dvec = fac(h, q) + FAC_DV; jb.Zs = fac(h, q) + FAC_ZS;
-        }
-      fa.jitter = jitter; fa.piv_rtol = c->pivot_rtol;
-      if (predict) { fa.info = c->d_info; fa.own_slots = 0; }
-      else { fa.info = reinterpret_cast<int*>(ks.res.p + RES_INFO); fa.own_slots = 1; }
-      hipLaunchKernelGGL(k_kf_factor, dim3(2 * nlat), dim3(1024), sizeof(double) * PB * PBLD, c->stream, fa);
-      ZIGP_HIP(c, hipGetLastError());
-      if constexpr (TAP) {
-        for (int h = 0; h < nlat; ++h)
-          for (int q = 0; q < 2; ++q) {
-            const zigp_kronf_tap_factor& tf = tap->s->lat[h].fac[q];
-            const KfFactorJob& jb = fa.job[2 * h + q];
-            const size_t mq = (size_t)jb.Mq;
-            ZIGP_TRY(tap->snap(c, tf.K, jb.K, (size_t)PB * PB)); ZIGP_TRY(tap->snap(c, tf.P, jb.P, mq * mq)); ZIGP_TRY(tap->snap(c, tf.PF, jb.PF, mq * mq));
-            ZIGP_TRY(tap->snap(c, tf.dvec, jb.dvec, mq + 1)); ZIGP_TRY(tap->snap(c, tf.Zs, jb.Zs, mq * jb.D)); ZIGP_TRY(tap->snap(c, tf.zc, jb.zc_out, (size_t)jb.D));
-          }
-      }
-    }
-    if (predict) ZIGP_TRY(request_info(c, &hinfo));   // value / gradient steps: the status slots come back with the result block
-    {
-      KfLatentArgs la;
-      memset(&la, 0, sizeof(la));
-      for (int h = 0; h < nlat; ++h) {
-        KfLatentJob& jb = la.job[h];
-        jb.M0 = hl[h].M[0]; jb.M1 = hl[h].M[1]; jb.Mq0 = Mq[h][0]; jb.Mq1 = Mq[h][1];
-        jb.P0 = fac(h, 0) + FAC_P; jb.P1 = fac(h, 1) + FAC_P; jb.dvec0 = fac(h, 0) + FAC_DV; jb.dvec1 = fac(h, 1) + FAC_DV;
-        jb.PF0 = fac(h, 0) + FAC_PF; jb.PF1 = fac(h, 1) + FAC_PF;
-        jb.u = ks.in.p + off_u[h]; jb.s = ks.in.p + off_s[h];
-        double* L = lat(h);
-        jb.U = L + LAT_U; jb.S2 = L + LAT_S2; jb.T0 = L + LAT_T0; jb.T1 = L + LAT_T1; jb.Al = L + LAT_AL;
-        jb.AlF = L + LAT_ALF; jb.S2F = L + LAT_S2F; jb.AlTF = L + LAT_ALTF; jb.S2TF = L + LAT_S2TF;
-        jb.klv = res(h) + RES_KLV;
-      }
-      if (pl.large) {
-        int mq1 = 0;
-        for (int h = 0; h < nlat; ++h) mq1 = std::max(mq1, la.job[h].Mq1);
-        hipLaunchKernelGGL(k_kfl_latent, dim3(nlat), dim3(1024), kfl_latent_lds(mq1), c->stream, la);
-      }
-      else hipLaunchKernelGGL(k_kf_latent, dim3(nlat), dim3(1024), 0, c->stream, la);
-      ZIGP_HIP(c, hipGetLastError());
-      if constexpr (TAP) {
-        for (int h = 0; h < nlat; ++h) {
-          const zigp_kronf_tap_latent& tl = tap->s->lat[h];
-          const KfLatentJob& jb = la.job[h];
-          const size_t n01 = (size_t)jb.Mq0 * jb.Mq1;
-          double* const host[9] = {tl.U, tl.S2, tl.T0, tl.T1, tl.Al, tl.AlF, tl.S2F, tl.AlTF, tl.S2TF};
-          const double* const dev[9] = {jb.U, jb.S2, jb.T0, jb.T1, jb.Al, jb.AlF, jb.S2F, jb.AlTF, jb.S2TF};
-          for (int i = 0; i < 9; ++i) ZIGP_TRY(tap->snap(c, host[i], dev[i], n01));
-        }
-      }
-    }
-    // ---- point stage
-    KfArgs ka;
-    memset(&ka, 0, sizeof(ka));
-    ka.X = Xd; ka.N = N; ka.Npad = Npad; ka.ldx = ldx; ka.ntiles = (int)(Npad / 16);
-    for (int h = 0; h < nlat; ++h) {
-      KfLat& L = ka.lat[h];
-      for (int q = 0; q < 2; ++q) {
-        KfFac& f = L.f[q];
-        f.M = hl[h].M[q]; f.nb = Mq[h][q] / 16; f.D = q == 0 ? D0 : D1; f.col0 = q == 0 ? 0 : D0;
-        f.hyp = d_hyp + (2 * h + q) * KH_FAC;
-        f.Zs = fac(h, q) + FAC_ZS; f.PF = fac(h, q) + FAC_PF;
-      }
-      double* Lm = lat(h);
-      L.AlF = Lm + LAT_ALF; L.S2F = Lm + LAT_S2F; L.AlTF = Lm + LAT_ALTF; L.S2TF = Lm + LAT_S2TF;
-      double* P = pts(h);
-      L.part = P; L.gm = P + 4 * Npad; L.gv = P + 5 * Npad; L.dq0 = P + 6 * Npad; L.dq1 = P + 7 * Npad;
-    }
-    {
-      const int waves = std::min(ka.ntiles, pl.large ? 1024 / nlat : 2048);
-      ka.tpw = (ka.ntiles + waves - 1) / waves;
-      const int nw = (ka.ntiles + ka.tpw - 1) / ka.tpw;
-      const dim3 grid((nw + KF_WAVES - 1) / KF_WAVES, nlat);
-      if (pl.large && large_exact) hipLaunchKernelGGL((k_kfl_forward<1, 7, true, true>), grid, dim3(64 * KF_WAVES), lds_fwd, c->stream, ka);
-      else if (pl.large) hipLaunchKernelGGL((k_kfl_forward<1, 7, true, false>), grid, dim3(64 * KF_WAVES), lds_fwd, c->stream, ka);
-      else ZIGP_TRY(kf_launch_small_latents(c, Mq, nlat, false, grid.x, ka));
-      ZIGP_HIP(c, hipGetLastError());
-      if constexpr (TAP) {
-        tap->facts[ZIGP_KFF_TPW_FWD] = ka.tpw;
-        for (int h = 0; h < nlat; ++h) ZIGP_TRY(tap->snap(c, tap->s->lat[h].part, pts(h), (size_t)4 * Npad));
-      }
-    }
-    KronPwArgs a;
-    memset(&a, 0, sizeof(a));
-    const int gl_ = nlat - 1;   // latent whose buffers stand in for g (unused by the single-latent kernels)
-    a.part_f = pts(0); a.part_g = pts(gl_); a.Y = Yd; a.N = N; a.Nc = Npad;
-    a.hyp = d_hyp;              // knn_f, knn_g, noise: from the device block (the single-latent heads outside a fit call read the by-value fields below)
-    if (!fit) { a.knn_f = p->var0f * p->var1f; a.knn_g = p->var0g * p->var1g; a.noise = p->noise; }
-    a.g_offset = g_offset; a.f_offset = f_mu; a.scale = scale;
-    a.gm_f = need_grad ? pts(0) + 4 * Npad : nullptr; a.gv_f = pts(0) + 5 * Npad; a.gm_g = pts(gl_) + 4 * Npad; a.gv_g = pts(gl_) + 5 * Npad;
-    a.dq0_f = pts(0) + 6 * Npad; a.dq1_f = pts(0) + 7 * Npad; a.dq0_g = pts(gl_) + 6 * Npad; a.dq1_g = pts(gl_) + 7 * Npad;
-    a.acc = d_pwacc; a.out9 = nullptr; a.ld9 = N;
-    if (predict) {
-      const int rows = nlat == 2 ? 9 : 4;
-      ZIGP_ENSURE(c, ks.out, (size_t)rows * N);
-      a.out9 = ks.out.p;
-      if (nlat == 2) hipLaunchKernelGGL(k_kron_pointwise<true>, dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a);
-      else hipLaunchKernelGGL((k_kron_head_pointwise<true, false>), dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a, lik);
-      ZIGP_HIP(c, hipGetLastError());
-      return 0;
-    }
-    if (nlat == 2) hipLaunchKernelGGL(k_kron_pointwise<false>, dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a);
-    else if (fit) hipLaunchKernelGGL((k_kron_head_pointwise<false, true>), dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a, lik);   // Knn, noise, f_mu: device block
-    else hipLaunchKernelGGL((k_kron_head_pointwise<false, false>), dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a, lik);
-    if (!need_grad) hipLaunchKernelGGL(k_kron_pw_reduce, dim3(1), dim3(256), 0, c->stream, d_pwacc, pw_blocks, include_kl ? 1.0 : 0.0, ks.res.p + RES_PWS);
-    ZIGP_HIP(c, hipGetLastError());
-    if constexpr (TAP) {
-      for (int h = 0; h < nlat; ++h) {
-        ZIGP_TRY(tap->snap(c, tap->s->lat[h].cot, pts(h) + 4 * Npad, (size_t)4 * Npad));
-        if (tap->s->lat[h].inject)      // rows [4][N] over gm, gv, dq0, dq1 [Npad] each: the padding keeps the kernel's values
-          ZIGP_HIP(c, hipMemcpy2DAsync(pts(h) + 4 * Npad, sizeof(double) * Npad, tap->inject[h].p, sizeof(double) * N, sizeof(double) * N, 4,
-                                       hipMemcpyDeviceToDevice, c->stream));
-      }
-    }
-    if (need_grad) {
-      const int waves = std::min(ka.ntiles, 1024 / nlat);   // one wave per SIMD of the chip: the kernels hold ~400-500 registers per lane
-      ka.tpw = (ka.ntiles + waves - 1) / waves;
-      const int nw = (ka.ntiles + ka.tpw - 1) / ka.tpw;
-      const int nwg = (nw + KF_WAVES - 1) / KF_WAVES;
-      int nparts;
-      if (!pl.large) {
-        nparts = nwg * KF_WAVES;
-        ZIGP_ENSURE(c, ks.acc, (size_t)2 * nparts * nblk * 256);
-        for (int h = 0; h < nlat; ++h) ka.lat[h].acc = ks.acc.p + (size_t)h * nparts * nblk * 256;
-        ZIGP_TRY(kf_launch_small_latents(c, Mq, nlat, true, (unsigned)nwg, ka));
-        if constexpr (TAP) { tap->facts[ZIGP_KFF_TPW_BWD] = ka.tpw; tap->facts[ZIGP_KFF_NRANGES] = 1; }
-      } else {
-        // The backward kernel spills ~4 KB of operands per point and latent (at 10 x 100), which k_kfl_accum then sums over the points.  The
-        // rows go through in RANGES of <= 1024 tiles (16 384 rows: <= 128 MB of records for both latents, Infinity-Cache resident), one
-        // backward + one accumulate launch per range.  The split of the tiles into accumulation parts of tps tiles does not depend on the
-        // ranges (a range is a whole number of parts), so the partial sums -- and k_kf_reduce's fixed-order total -- are the same bits as
-        // with one range over everything; memory no longer grows with the row count (rounds 2-3: 0.86 GB for the pptr full batch, and a
-        // 64 GB cap with an error beyond it).
-        size_t rec[2] = {0, 0};
-        for (int h = 0; h < nlat; ++h) rec[h] = (size_t)64 * (Mq[h][0] + Mq[h][1]);
-        const int tps = std::max(4, std::min(64, ka.ntiles / 16));     // tiles per accumulation part (4 for a minibatch: the chain of dependent loads is short)
-        nparts = (ka.ntiles + tps - 1) / tps;
-        const int range_tiles = std::max(1, c->kron_range_tiles / tps) * tps;
-        const int spill_tiles = std::min(ka.ntiles, range_tiles);
-        ZIGP_ENSURE(c, ks.spill, (rec[0] + (nlat == 2 ? rec[1] : 0)) * spill_tiles);
-        ka.lat[0].spill = ks.spill.p;
-        if (nlat == 2) ka.lat[1].spill = ks.spill.p + rec[0] * spill_tiles;
-        ZIGP_ENSURE(c, ks.acc, (size_t)2 * nparts * nblk * 256);
-        KflAccArgs aa;
-        memset(&aa, 0, sizeof(aa));
-        aa.X = ka.X; aa.N = N; aa.ldx = ldx; aa.ntiles = ka.ntiles; aa.tps = tps; aa.nb0c = pl.nb0c; aa.nb1c = pl.nb1c;
-        for (int h = 0; h < nlat; ++h) {
-          KflAccLat& L = aa.lat[h];
-          L.spill = ka.lat[h].spill; L.gm = ka.lat[h].gm; L.gv = ka.lat[h].gv;
-          L.acc = ks.acc.p + (size_t)h * nparts * nblk * 256;
-          ka.lat[h].acc = L.acc;
-          L.nb0 = Mq[h][0] / 16; L.nb1 = Mq[h][1] / 16; L.D0 = D0; L.D1 = D1;
-          L.hyp0 = d_hyp + (2 * h) * KH_FAC; L.hyp1 = d_hyp + (2 * h + 1) * KH_FAC;
-        }
-        for (int t0 = 0; t0 < ka.ntiles; t0 += range_tiles) {
-          const int t1 = std::min(t0 + range_tiles, ka.ntiles), nt = t1 - t0;
-          const int rwaves = std::min(nt, 1024 / nlat);
-          ka.tile0 = t0; ka.tile1 = t1; ka.tpw = (nt + rwaves - 1) / rwaves;
-          const int rnw = (nt + ka.tpw - 1) / ka.tpw, rnwg = (rnw + KF_WAVES - 1) / KF_WAVES;
-          if (large_exact) hipLaunchKernelGGL((k_kfl_backward<1, 7, true, true>), dim3(rnwg, nlat), dim3(64 * KF_WAVES), lds_bwd, c->stream, ka);
-          else hipLaunchKernelGGL((k_kfl_backward<1, 7, true, false>), dim3(rnwg, nlat), dim3(64 * KF_WAVES), lds_bwd, c->stream, ka);
-          ZIGP_HIP(c, hipGetLastError());
-          aa.tile0 = t0; aa.tile1 = t1; aa.part0 = t0 / tps;
-          hipLaunchKernelGGL(k_kfl_accum, dim3((nblk + 3) / 4, (nt + tps - 1) / tps, nlat), dim3(256), 0, c->stream, aa);
-          ZIGP_HIP(c, hipGetLastError());
-          if constexpr (TAP) { if (t0 == 0) tap->facts[ZIGP_KFF_TPW_BWD] = ka.tpw; ++tap->facts[ZIGP_KFF_NRANGES]; }
-        }
-        if constexpr (TAP) { tap->facts[ZIGP_KFF_TPS] = tps; tap->facts[ZIGP_KFF_RANGE_TILES] = range_tiles; }
-      }
-      hipLaunchKernelGGL(k_kf_reduce, dim3(nblk * 256 / 16 + 1, nlat), dim3(256), 0, c->stream, ka.lat[0].acc, ka.lat[gl_].acc, nparts,
-                         lat(0) + LAT_WORK, lat(gl_) + LAT_WORK, pl.nb0c, pl.nb1c, Mq[0][0] / 16, Mq[0][1] / 16, Mq[gl_][0] / 16, Mq[gl_][1] / 16,
-                         d_pwacc, pw_blocks, include_kl ? 1.0 : 0.0, ks.res.p + RES_PWS);
-      ZIGP_HIP(c, hipGetLastError());
-      if constexpr (TAP) {
-        tap->facts[ZIGP_KFF_NPARTS] = nparts;
-        for (int h = 0; h < nlat; ++h) ZIGP_TRY(tap->snap(c, tap->s->lat[h].work, lat(h) + LAT_WORK, (size_t)wl.total));
-      }
-      KflFinishArgs fa;
-      memset(&fa, 0, sizeof(fa));
-      for (int h = 0; h < nlat; ++h) {
-        KfFinishJob& jb = fa.job[h];
-        jb.M0 = hl[h].M[0]; jb.M1 = hl[h].M[1]; jb.Mq0 = Mq[h][0]; jb.Mq1 = Mq[h][1]; jb.D0 = D0; jb.D1 = D1;
-        jb.P0 = fac(h, 0) + FAC_P; jb.P1 = fac(h, 1) + FAC_P; jb.dvec0 = fac(h, 0) + FAC_DV; jb.dvec1 = fac(h, 1) + FAC_DV;
-        jb.PF0 = fac(h, 0) + FAC_PF; jb.PF1 = fac(h, 1) + FAC_PF;
-        jb.K0 = fac(h, 0); jb.K1 = fac(h, 1); jb.Z0 = ks.in.p + off_z[h][0]; jb.Z1 = ks.in.p + off_z[h][1];
-        jb.hyp0 = d_hyp + (2 * h) * KH_FAC; jb.hyp1 = d_hyp + (2 * h + 1) * KH_FAC;
-        double* L = lat(h);
-        jb.U = L + LAT_U; jb.S2 = L + LAT_S2; jb.T0 = L + LAT_T0; jb.T1 = L + LAT_T1; jb.Al = L + LAT_AL; jb.s = ks.in.p + off_s[h];
-        jb.work = L + LAT_WORK;
-        jb.krow0 = res(h) + RES_KROW0; jb.krow1 = res(h) + RES_KROW1; jb.gu = res(h) + RES_GU; jb.gs = res(h) + RES_GS;
-      }
-      fa.jitter = jitter; fa.with_kl = include_kl ? 1 : 0;
-      fa.ldw = wl.ldw; fa.wS2 = wl.S2; fa.wP0 = wl.P0; fa.wP1 = wl.P1; fa.wK0 = wl.K0; fa.wK1 = wl.K1;
-      fa.scratch_off = (int64_t)wl.total; fa.scratch_set = (int64_t)SCR_SET;
-      if (pl.large) {
-        int nbmax = 1;
-        for (int h = 0; h < nlat; ++h) nbmax = std::max(nbmax, std::max(Mq[h][0], Mq[h][1]) / 16);
-        const dim3 grid(nbmax, 2, nlat);
-        hipLaunchKernelGGL(k_kfl_finish<1>, grid, dim3(KFL_FIN_THREADS), 0, c->stream, fa);
-        hipLaunchKernelGGL(k_kfl_finish<2>, grid, dim3(KFL_FIN_THREADS), 0, c->stream, fa);
-        hipLaunchKernelGGL(k_kfl_finish<3>, grid, dim3(KFL_FIN_THREADS), 0, c->stream, fa);
-      } else {
-        KfFinishArgs fs;
-        memset(&fs, 0, sizeof(fs));
-        fs.job[0] = fa.job[0]; fs.job[1] = fa.job[1]; fs.jitter = fa.jitter; fs.with_kl = fa.with_kl;
-        hipLaunchKernelGGL(k_kf_finish, dim3(2, nlat), dim3(1024), KF_FIN_LDS, c->stream, fs);
-      }
-      ZIGP_HIP(c, hipGetLastError());
-    }
-    if (c->comm) {   // data-parallel run: the block (cleared at the start of the step) is summed over ranks where it lies
-      // a rank that does not count the KL (include_kl = 0) must not add its scalars, which the latent kernel writes regardless
-      if (!include_kl) for (int h = 0; h < nlat; ++h) ZIGP_HIP(c, hipMemsetAsync(res(h) + RES_KLV, 0, sizeof(double) * 8, c->stream));
-      ZIGP_TRY(comm_allreduce(c, ks.res.p, RES_INFO));
-    }
-    return 0;
-  };
-
-  static const char* const fac_names[4] = {"Kronecker factor 0 of Kuu (latent f)", "Kronecker factor 1 of Kuu (latent f)",
-                                           "Kronecker factor 0 of Kuu (latent g)", "Kronecker factor 1 of Kuu (latent g)"};
-  // =========================================================================================================================
-  // fit call: n_steps steps back to back, parameters updated on the device, ONE synchronisation at the end
-  // =========================================================================================================================
-  if (fit) {
-    KfFitArgs fa;
-    memset(&fa, 0, sizeof(fa));
-    KfFitDesc& d = fa.d;
-    d.nlat = nlat; d.D0 = D0; d.D1 = D1;
-    const bool head = fit->head;
-    const int nblocks = head ? ZIGP_HEAD_FIT_BLOCKS : KFIT_BLOCKS;
-    size_t o = 0;
-    auto block = [&](int b, int n, size_t dst) {
-      d.off[b] = (int)o; d.n[b] = n; d.dst[b] = (int)dst; d.positive[b] = fit->positive[b]; d.lr[b] = fit->lr[b];
-      d.trainable[b] = fit->trainable ? (fit->trainable[b] != 0) : 1;
-      o += n;
-    };
-    for (int h = 0; h < nlat; ++h) {
-      const int M0 = hl[h].M[0], M1 = hl[h].M[1];
-      const int sizes[8] = {M0 * D0, M1 * D1, M0 * M1, M0 * M1, D0, D1, 1, 1};
-      const size_t dsts[8] = {off_z[h][0], off_z[h][1], off_u[h], off_s[h], 0, 0, 0, 0};
-      for (int k = 0; k < 8; ++k) block(8 * h + k, sizes[k], dsts[k]);
-      for (int q = 0; q < 2; ++q) { d.M[h][q] = hl[h].M[q]; d.Mq[h][q] = Mq[h][q]; d.off_z[h][q] = (int)off_z[h][q]; }
-    }
-    for (int b = 8 * nlat; b < nblocks; ++b) block(b, 1, 0);      // the likelihood variance (head: and f_mu)
-    if ((int64_t)o != fit->n_free) { c->err = std::string(fit->name) + ": n_free does not match the model sizes"; return ZIGP_EARG; }
-    d.off_hyp = (int)off_hyp; d.off_hyp2 = (int)off_hyp2;
-    {
-      int nbig = 0, nhyp = 0, kb = 0, kh = 0;
-      for (int b = 0; b < nblocks; ++b) {
-        const bool big = b < 8 * nlat && b % 8 <= 3;
-        if (big) { d.big_blk[kb] = b; d.big_off[kb++] = nbig; nbig += d.n[b]; }
-        else { d.hyp_blk[kh] = b; d.hyp_off[kh++] = nhyp; nhyp += d.n[b]; }
-      }
-      for (; kb <= 8; ++kb) d.big_off[kb] = nbig;      // kfit_element walks eight big and nine hyperparameter blocks: the ones a
-      for (; kh <= 9; ++kh) d.hyp_off[kh] = nhyp;      // layout does not have start at the total (no thread maps to them)
-    }
-    d.res_size = (int)RES_SIZE; d.res_krow0 = (int)RES_KROW0; d.res_krow1 = (int)RES_KROW1; d.res_gu = (int)RES_GU; d.res_gs = (int)RES_GS;
-    d.res_pws = (int)RES_PWS; d.res_info = (int)RES_INFO;
-    d.beta1 = fit->beta1; d.beta2 = fit->beta2; d.eps = fit->eps;
-    const size_t nf = (size_t)fit->n_free, n_hist = (size_t)2 * fit->n_steps;
-    const size_t n_state = 3 * nf + n_hist + 8;
-    ZIGP_ENSURE(c, ks.fit, n_state);
-    fa.x = ks.fit.p; fa.m = fa.x + nf; fa.v = fa.m + nf; fa.hist = fa.v + nf; fa.fail = reinterpret_cast<int*>(fa.hist + n_hist);
-    fa.img = ks.in.p; fa.res = ks.res.p;
-    {
-      ZIGP_PINNED(c, hst, n_state);
-      memcpy(hst, fit->x, sizeof(double) * nf); memcpy(hst + nf, fit->m, sizeof(double) * nf); memcpy(hst + 2 * nf, fit->v, sizeof(double) * nf);
-      memset(hst + 3 * nf, 0, sizeof(double) * (n_hist + 8));
-      ZIGP_HIP(c, hipMemcpyAsync(ks.fit.p, hst, sizeof(double) * n_state, hipMemcpyHostToDevice, c->stream));
-      if (n_wrap) {
-        const size_t nw = n_wrap * (size_t)N * (ldx + 1);
-        ZIGP_PINNED(c, hw, nw);
-        memcpy(hw, fit->Xw, sizeof(double) * n_wrap * N * ldx);
-        memcpy(hw + n_wrap * (size_t)N * ldx, fit->Yw, sizeof(double) * n_wrap * N);
-        ZIGP_HIP(c, hipMemcpyAsync(d_wrap, hw, sizeof(double) * nw, hipMemcpyHostToDevice, c->stream));
-      }
-    }
-    ZIGP_HIP(c, hipMemsetAsync(ks.in.p + off_hyp, 0, sizeof(double) * 2 * KH_SIZE, c->stream));
-    const dim3 ugrid((d.big_off[8] + KFIT_THREADS - 1) / KFIT_THREADS + 1);
-    fa.update = 0; fa.step = 0;
-    auto update = [&] {
-      if (head) hipLaunchKernelGGL(k_fit_update<true>, ugrid, dim3(KFIT_THREADS), 0, c->stream, fa);
-      else hipLaunchKernelGGL(k_fit_update<false>, ugrid, dim3(KFIT_THREADS), 0, c->stream, fa);
-    };
-    update();       // free state -> parameter image (hyper block 0)
-    ZIGP_HIP(c, hipGetLastError());
-    fa.update = 1;
-    for (int i = 0; i < fit->n_steps; ++i) {
-      const int64_t rb = fit->row_begin[i];
-      const double* Xd = rb >= 0 ? X + rb * ldx : d_wrap + (size_t)(-rb - 1) * N * ldx;
-      const double* Yd = rb >= 0 ? Y + rb : d_wrap + n_wrap * (size_t)N * ldx + (size_t)(-rb - 1) * N;
-      d_hyp = ks.in.p + ((i & 1) ? off_hyp2 : off_hyp);       // written by the previous step's update (step 0: by the launch above)
-      ZIGP_TRY(enqueue(std::false_type{}, Xd, Yd));
-      // lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t), t counted from 1 (zigp/optim.py AdamGroups.step): the two t-dependent factors from the host
-      const double t = (double)(fit->t0 + i + 1);
-      fa.step = i; fa.lr_sq = std::sqrt(1.0 - std::pow(d.beta2, t)); fa.lr_den = 1.0 - std::pow(d.beta1, t);
-      update();
-      ZIGP_HIP(c, hipGetLastError());
-    }
-    double* hst = nullptr;
-    ZIGP_TRY(download(c, ks.fit.p, n_state, &hst));
-    ZIGP_HIP(c, hipStreamSynchronize(c->stream));
-    const int* hfail = reinterpret_cast<const int*>(hst + 3 * nf + n_hist);
-    memcpy(fit->x, hst, sizeof(double) * nf); memcpy(fit->m, hst + nf, sizeof(double) * nf); memcpy(fit->v, hst + 2 * nf, sizeof(double) * nf);
-    const int done = hfail[0] ? hfail[0] - 1 : fit->n_steps;       // steps whose update was applied
-    c->fit_steps_applied = done;                                   // (zigp_kron_fit_steps_applied: the caller's iteration count advances by this)
-    for (int i = 0; i < fit->n_steps; ++i) {
-      if (fit->hist_data) fit->hist_data[i] = i < done ? hst[3 * nf + 2 * i] : NAN;
-      if (fit->hist_kl) fit->hist_kl[i] = i < done ? hst[3 * nf + 2 * i + 1] : NAN;
-    }
-    if (hfail[0]) {
-      char b[288];
-      snprintf(b, sizeof(b), "Cholesky failed in step %d of this %s call (iteration %lld): %s not positive definite at pivot %d; "
-               "the state returned is the one before that step", hfail[0] - 1, fit->name, (long long)(fit->t0 + hfail[0] - 1), fac_names[hfail[1] & 3], hfail[2]);
-      c->err = b; c->info = hfail[2];
-      return ZIGP_ENOTPD;
-    }
-    return 0;
-  }
-
-  {
-    const double* Xd = dev_xy ? X : ks.in.p + off_x;
-    const double* Yd = Y ? (dev_xy ? Y : ks.in.p + off_y) : nullptr;
-    if (tap) {
-      const int64_t f0[ZIGP_KFF_COUNT] = {pl.large, large_exact, pl.nb0c, pl.nb1c, Mq[0][0] / 16, Mq[0][1] / 16, Mq[nlat - 1][0] / 16, Mq[nlat - 1][1] / 16,
-                                          Npad, Npad / 16, 0, 0, 0, 0, 0, 0,
-                                          (pl.large || nlat == 1 || (Mq[0][0] == Mq[1][0] && Mq[0][1] == Mq[1][1])) ? 1 : 0};
-      memcpy(tap->facts, f0, sizeof(f0));
-      ZIGP_TRY(enqueue(std::true_type{}, Xd, Yd));
-    } else {
-      ZIGP_TRY(enqueue(std::false_type{}, Xd, Yd));
-    }
-  }
-  if (predict) {
-    const int rows = nlat == 2 ? 9 : 4;
-    ZIGP_HIP(c, hipMemcpyAsync(out9, ks.out.p, sizeof(double) * rows * N, hipMemcpyDeviceToHost, c->stream));
-    ZIGP_HIP(c, hipStreamSynchronize(c->stream));
-    return info_result(c, hinfo, "a Kronecker factor of Kuu");
-  }
-  double* hres = nullptr;
-  ZIGP_TRY(download(c, ks.res.p, n_res, &hres));
-  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
-  for (int j = 0; j < 2 * nlat; ++j) ZIGP_TRY(info_result(c, reinterpret_cast<const int*>(hres + RES_INFO) + 2 * j, fac_names[j]));
-  const double* pws = hres + RES_PWS;   // var_exp, d noise, sum gv_f, sum gv_g, sum gm_f (= d / d f_mu)
-  const double s_ve = pws[0], s_dn = pws[1], s_gv[2] = {pws[2], pws[3]};
-  if (elbo_data) *elbo_data = s_ve;
-  if (d_offset) *d_offset = pws[4];
-  // KL from its five scalars; in a data-parallel run they are the sums over the ranks that count it (pws[7] of them: one, by the
-  // contract of zigp_comm_init), and every rank returns the same value
-  double klsum = 0.0;
-  const double kl_ranks = pws[7];
-  if (kl_ranks > 0.0) {
-    for (int h = 0; h < nlat; ++h) {
-      const double* v = hres + (size_t)h * RES_SIZE + RES_KLV;
-      const int M0 = hl[h].M[0], M1 = hl[h].M[1];
-      klsum += 0.5 * (v[0] - kl_ranks * (double)M0 * M1 - v[1] + v[2] + (double)M1 * v[3] + (double)M0 * v[4]);
-    }
-  }
-  if (kl) *kl = klsum;
-  if (need_grad) {
-    double* gZ[2][2] = {{grads->Z0f, grads->Z1f}, {grads->Z0g, grads->Z1g}};
-    double* gl[2][2] = {{grads->ell0f, grads->ell1f}, {grads->ell0g, grads->ell1g}};
-    double gvar[2][2] = {{0, 0}, {0, 0}};
-    double* gu[2] = {grads->u_fm, grads->u_gm};
-    double* gs[2] = {grads->u_fs_sqrt, grads->u_gs_sqrt};
-    for (int h = 0; h < nlat; ++h) {
-      const double* R = hres + (size_t)h * RES_SIZE;
-      for (int q = 0; q < 2; ++q) {
-        const int D = q == 0 ? D0 : D1, W = 2 + 2 * D, M = hl[h].M[q];
-        const double* krow = R + (q == 0 ? RES_KROW0 : RES_KROW1);
-        const double* ell = hl[h].ell[q];
-        double dv = 0.0;
-        std::vector<double> dl(D, 0.0);
-        for (int m = 0; m < M; ++m) {
-          const double* r = &krow[(size_t)m * W];
-          dv += r[0];
-          for (int d = 0; d < D; ++d) {
-            if (gZ[h][q]) gZ[h][q][m * D + d] = r[1 + d] / (ell[d] * ell[d]);
-            dl[d] += r[1 + D + d];
-          }
-        }
-        for (int d = 0; d < D; ++d)
-          if (gl[h][q]) gl[h][q][d] = dl[d] / (ell[d] * ell[d] * ell[d]);
-        gvar[h][q] = dv / hl[h].var[q] + s_gv[h] * hl[h].var[1 - q];   // Knn = var0 * var1 enters var_n directly (scripts/onoff.py:196-200)
-      }
-      const size_t ng = (size_t)hl[h].M[0] * hl[h].M[1];
-      if (gu[h]) memcpy(gu[h], R + RES_GU, sizeof(double) * ng);
-      if (gs[h]) memcpy(gs[h], R + RES_GS, sizeof(double) * ng);
-    }
-    grads->var0f = gvar[0][0]; grads->var1f = gvar[0][1];
-    grads->var0g = nlat == 2 ? gvar[1][0] : 0.0; grads->var1g = nlat == 2 ? gvar[1][1] : 0.0;
-    grads->noise = s_dn;
+    const size_t b0 = s.Mq[h][0] / 16, b1 = s.Mq[h][1] / 16;
+    s.lds_fwd = std::max(s.lds_fwd, sizeof(double) * 256 * (b0 * b0 + b1 * b1 + 2 * b0 * b1));
+    s.lds_bwd = std::max(s.lds_bwd, sizeof(double) * 256 * (b0 * b0 + b1 * b1 + 4 * b0 * b1));
   }
   return 0;
+}
+
+// the dynamic-LDS limits of the kernels launched below, once per process (k_kf_backward's: kf_launch_small)
+static int kf_set_attributes(zigp_ctx* c) {
+  static bool attr_set = false;
+  if (attr_set) return 0;
+  ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kf_factor), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * PB * PBLD)));
+  ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kf_finish), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KF_FIN_LDS));
+  ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_forward<1, 7, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_backward<1, 7, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_forward<1, 7, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_backward<1, 7, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_latent), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kfl_latent_lds(16 * 7)));
+  attr_set = true;
+  return 0;
+}
+
+// the parameter image and, for a host minibatch, its rows: one staged copy (a fit call writes its image on the device: kf_fit_run)
+static int kf_stage_inputs(KfRun& s) {
+  zigp_ctx* c = s.c;
+  const KronCall& k = *s.k;
+  const KronHostLatent* hl = k.hl;
+  ZIGP_PINNED(c, hin, s.n_in);
+  if (!k.dev_xy) {
+    memcpy(hin + s.off_x, k.X, sizeof(double) * s.N * s.ldx);
+    if (k.Y) memcpy(hin + s.off_y, k.Y, sizeof(double) * s.N); else memset(hin + s.off_y, 0, sizeof(double) * s.N);
+  }
+  for (int h = 0; h < s.nlat; ++h) {
+    memcpy(hin + s.off_z[h][0], hl[h].Z[0], sizeof(double) * hl[h].M[0] * s.D0);
+    memcpy(hin + s.off_z[h][1], hl[h].Z[1], sizeof(double) * hl[h].M[1] * s.D1);
+    memcpy(hin + s.off_u[h], hl[h].u, sizeof(double) * hl[h].M[0] * hl[h].M[1]);
+    memcpy(hin + s.off_s[h], hl[h].s, sizeof(double) * hl[h].M[0] * hl[h].M[1]);
+  }
+  kf_fill_hyp(hin + s.off_hyp, hl, s.nlat, s.D0, s.D1, k.p->noise);
+  ZIGP_HIP(c, hipMemcpyAsync(s.ks->in.p, hin, sizeof(double) * s.n_in, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
+// ---- the stages of ONE step on rows (Xd, Yd), in launch order -- everything else a step reads lives on the device (parameter image,
+// hyper block).  TAP: the step of the stage tests, with a snapshot behind each launch; an ordinary step is the instantiation without them.
+template <bool TAP>
+static int kf_stage_factor(KfRun& s, KfTap* tap) {
+  zigp_ctx* c = s.c;
+  KfFactorArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  for (int h = 0; h < s.nlat; ++h)
+    for (int q = 0; q < 2; ++q) {
+      KfFactorJob& jb = fa.job[2 * h + q];
+      jb.Z = s.ks->in.p + s.off_z[h][q]; jb.M = s.k->hl[h].M[q]; jb.D = q == 0 ? s.D0 : s.D1; jb.Mq = s.Mq[h][q];
+      jb.hyp = s.d_hyp + (2 * h + q) * KH_FAC; jb.zc_out = s.d_hyp + (2 * h + q) * KH_FAC + KH_ZC;
+      jb.K = s.fac(h, q); jb.P = s.fac(h, q) + s.FAC_P; jb.PF = s.fac(h, q) + s.FAC_PF; jb.dvec = s.fac(h, q) + s.FAC_DV; jb.Zs = s.fac(h, q) + s.FAC_ZS;
+    }
+  fa.jitter = s.k->jitter; fa.piv_rtol = c->pivot_rtol;
+  if (s.k->predict) { fa.info = c->d_info; fa.own_slots = 0; }
+  else { fa.info = reinterpret_cast<int*>(s.ks->res.p + s.RES_INFO); fa.own_slots = 1; }
+  hipLaunchKernelGGL(k_kf_factor, dim3(2 * s.nlat), dim3(1024), sizeof(double) * PB * PBLD, c->stream, fa);
+  ZIGP_HIP(c, hipGetLastError());
+  if constexpr (TAP) {
+    for (int h = 0; h < s.nlat; ++h)
+      for (int q = 0; q < 2; ++q) {
+        const zigp_kronf_tap_factor& tf = tap->s->lat[h].fac[q];
+        const KfFactorJob& jb = fa.job[2 * h + q];
+        const size_t mq = (size_t)jb.Mq;
+        ZIGP_TRY(tap->snap(c, tf.K, jb.K, (size_t)PB * PB)); ZIGP_TRY(tap->snap(c, tf.P, jb.P, mq * mq)); ZIGP_TRY(tap->snap(c, tf.PF, jb.PF, mq * mq));
+        ZIGP_TRY(tap->snap(c, tf.dvec, jb.dvec, mq + 1)); ZIGP_TRY(tap->snap(c, tf.Zs, jb.Zs, mq * jb.D)); ZIGP_TRY(tap->snap(c, tf.zc, jb.zc_out, (size_t)jb.D));
+      }
+  }
+  return 0;
+}
+
+template <bool TAP>
+static int kf_stage_latent(KfRun& s, KfTap* tap) {
+  zigp_ctx* c = s.c;
+  KfLatentArgs la;
+  memset(&la, 0, sizeof(la));
+  for (int h = 0; h < s.nlat; ++h) {
+    KfLatentJob& jb = la.job[h];
+    jb.M0 = s.k->hl[h].M[0]; jb.M1 = s.k->hl[h].M[1]; jb.Mq0 = s.Mq[h][0]; jb.Mq1 = s.Mq[h][1];
+    jb.P0 = s.fac(h, 0) + s.FAC_P; jb.P1 = s.fac(h, 1) + s.FAC_P; jb.dvec0 = s.fac(h, 0) + s.FAC_DV; jb.dvec1 = s.fac(h, 1) + s.FAC_DV;
+    jb.PF0 = s.fac(h, 0) + s.FAC_PF; jb.PF1 = s.fac(h, 1) + s.FAC_PF;
+    jb.u = s.ks->in.p + s.off_u[h]; jb.s = s.ks->in.p + s.off_s[h];
+    double* L = s.lat(h);
+    jb.U = L + s.LAT_U; jb.S2 = L + s.LAT_S2; jb.T0 = L + s.LAT_T0; jb.T1 = L + s.LAT_T1; jb.Al = L + s.LAT_AL;
+    jb.AlF = L + s.LAT_ALF; jb.S2F = L + s.LAT_S2F; jb.AlTF = L + s.LAT_ALTF; jb.S2TF = L + s.LAT_S2TF;
+    jb.klv = s.res(h) + s.RES_KLV;
+  }
+  if (s.pl.large) {
+    int mq1 = 0;
+    for (int h = 0; h < s.nlat; ++h) mq1 = std::max(mq1, la.job[h].Mq1);
+    hipLaunchKernelGGL(k_kfl_latent, dim3(s.nlat), dim3(1024), kfl_latent_lds(mq1), c->stream, la);
+  }
+  else hipLaunchKernelGGL(k_kf_latent, dim3(s.nlat), dim3(1024), 0, c->stream, la);
+  ZIGP_HIP(c, hipGetLastError());
+  if constexpr (TAP) {
+    for (int h = 0; h < s.nlat; ++h) {
+      const zigp_kronf_tap_latent& tl = tap->s->lat[h];
+      const KfLatentJob& jb = la.job[h];
+      const size_t n01 = (size_t)jb.Mq0 * jb.Mq1;
+      double* const host[9] = {tl.U, tl.S2, tl.T0, tl.T1, tl.Al, tl.AlF, tl.S2F, tl.AlTF, tl.S2TF};
+      const double* const dev[9] = {jb.U, jb.S2, jb.T0, jb.T1, jb.Al, jb.AlF, jb.S2F, jb.AlTF, jb.S2TF};
+      for (int i = 0; i < 9; ++i) ZIGP_TRY(tap->snap(c, host[i], dev[i], n01));
+    }
+  }
+  return 0;
+}
+
+// fills ka, the arguments the point kernels of the step share (the backward stage adds its accumulators), and launches the forward ones
+template <bool TAP>
+static int kf_stage_point_forward(KfRun& s, KfTap* tap, const double* Xd, KfArgs& ka) {
+  zigp_ctx* c = s.c;
+  const int nlat = s.nlat;
+  const int64_t Npad = s.Npad;
+  memset(&ka, 0, sizeof(ka));
+  ka.X = Xd; ka.N = s.N; ka.Npad = Npad; ka.ldx = s.ldx; ka.ntiles = (int)(Npad / 16);
+  for (int h = 0; h < nlat; ++h) {
+    KfLat& L = ka.lat[h];
+    for (int q = 0; q < 2; ++q) {
+      KfFac& f = L.f[q];
+      f.M = s.k->hl[h].M[q]; f.nb = s.Mq[h][q] / 16; f.D = q == 0 ? s.D0 : s.D1; f.col0 = q == 0 ? 0 : s.D0;
+      f.hyp = s.d_hyp + (2 * h + q) * KH_FAC;
+      f.Zs = s.fac(h, q) + s.FAC_ZS; f.PF = s.fac(h, q) + s.FAC_PF;
+    }
+    double* Lm = s.lat(h);
+    L.AlF = Lm + s.LAT_ALF; L.S2F = Lm + s.LAT_S2F; L.AlTF = Lm + s.LAT_ALTF; L.S2TF = Lm + s.LAT_S2TF;
+    double* P = s.pts(h);
+    L.part = P; L.gm = P + 4 * Npad; L.gv = P + 5 * Npad; L.dq0 = P + 6 * Npad; L.dq1 = P + 7 * Npad;
+  }
+  const int waves = std::min(ka.ntiles, s.pl.large ? 1024 / nlat : 2048);
+  ka.tpw = (ka.ntiles + waves - 1) / waves;
+  const int nw = (ka.ntiles + ka.tpw - 1) / ka.tpw;
+  const dim3 grid((nw + KF_WAVES - 1) / KF_WAVES, nlat);
+  if (s.pl.large && s.large_exact) hipLaunchKernelGGL((k_kfl_forward<1, 7, true, true>), grid, dim3(64 * KF_WAVES), s.lds_fwd, c->stream, ka);
+  else if (s.pl.large) hipLaunchKernelGGL((k_kfl_forward<1, 7, true, false>), grid, dim3(64 * KF_WAVES), s.lds_fwd, c->stream, ka);
+  else ZIGP_TRY(kf_launch_small_latents(c, s.Mq, nlat, false, grid.x, ka));
+  ZIGP_HIP(c, hipGetLastError());
+  if constexpr (TAP) {
+    tap->facts[ZIGP_KFF_TPW_FWD] = ka.tpw;
+    for (int h = 0; h < nlat; ++h) ZIGP_TRY(tap->snap(c, tap->s->lat[h].part, s.pts(h), (size_t)4 * Npad));
+  }
+  return 0;
+}
+
+// the point-wise kernel: a prediction ends with it (rows -> KfState::out); a value-only step adds the sum of its block partials
+template <bool TAP>
+static int kf_stage_pointwise(KfRun& s, KfTap* tap, const double* Yd) {
+  zigp_ctx* c = s.c;
+  KfState& ks = *s.ks;
+  const KronCall& k = *s.k;
+  const int nlat = s.nlat, pw_blocks = s.pw_blocks;
+  const int64_t N = s.N, Npad = s.Npad;
+  KronPwArgs a;
+  memset(&a, 0, sizeof(a));
+  const int gl_ = nlat - 1;   // latent whose buffers stand in for g (unused by the single-latent kernels)
+  a.part_f = s.pts(0); a.part_g = s.pts(gl_); a.Y = Yd; a.N = N; a.Nc = Npad;
+  a.hyp = s.d_hyp;            // knn_f, knn_g, noise: from the device block (the single-latent heads outside a fit call read the by-value fields below)
+  if (!s.fit) { a.knn_f = k.p->var0f * k.p->var1f; a.knn_g = k.p->var0g * k.p->var1g; a.noise = k.p->noise; }
+  a.g_offset = k.g_offset; a.f_offset = k.f_mu; a.scale = k.scale;
+  a.gm_f = s.need_grad ? s.pts(0) + 4 * Npad : nullptr; a.gv_f = s.pts(0) + 5 * Npad; a.gm_g = s.pts(gl_) + 4 * Npad; a.gv_g = s.pts(gl_) + 5 * Npad;
+  a.dq0_f = s.pts(0) + 6 * Npad; a.dq1_f = s.pts(0) + 7 * Npad; a.dq0_g = s.pts(gl_) + 6 * Npad; a.dq1_g = s.pts(gl_) + 7 * Npad;
+  a.acc = s.d_pwacc; a.out9 = nullptr; a.ld9 = N;
+  if (k.predict) {
+    const int rows = nlat == 2 ? 9 : 4;
+    ZIGP_ENSURE(c, ks.out, (size_t)rows * N);
+    a.out9 = ks.out.p;
+    if (nlat == 2) hipLaunchKernelGGL(k_kron_pointwise<true>, dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a);
+    else hipLaunchKernelGGL((k_kron_head_pointwise<true, false>), dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a, k.lik);
+    ZIGP_HIP(c, hipGetLastError());
+    return 0;
+  }
+  if (nlat == 2) hipLaunchKernelGGL(k_kron_pointwise<false>, dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a);
+  else if (s.fit) hipLaunchKernelGGL((k_kron_head_pointwise<false, true>), dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a, k.lik);   // Knn, noise, f_mu: device block
+  else hipLaunchKernelGGL((k_kron_head_pointwise<false, false>), dim3(pw_blocks), dim3(PW_THREADS), 0, c->stream, a, k.lik);
+  if (!s.need_grad) hipLaunchKernelGGL(k_kron_pw_reduce, dim3(1), dim3(256), 0, c->stream, s.d_pwacc, pw_blocks, k.include_kl ? 1.0 : 0.0, ks.res.p + s.RES_PWS);
+  ZIGP_HIP(c, hipGetLastError());
+  if constexpr (TAP) {
+    for (int h = 0; h < nlat; ++h) {
+      ZIGP_TRY(tap->snap(c, tap->s->lat[h].cot, s.pts(h) + 4 * Npad, (size_t)4 * Npad));
+      if (tap->s->lat[h].inject)      // rows [4][N] over gm, gv, dq0, dq1 [Npad] each: the padding keeps the kernel's values
+        ZIGP_HIP(c, hipMemcpy2DAsync(s.pts(h) + 4 * Npad, sizeof(double) * Npad, tap->inject[h].p, sizeof(double) * N, sizeof(double) * N, 4,
+                                     hipMemcpyDeviceToDevice, c->stream));
+    }
+  }
+  return 0;
+}
+
+// small grid: the accumulators stay in registers, one partial per wave (nparts of them)
+template <bool TAP>
+static int kf_stage_backward_small(KfRun& s, KfTap* tap, KfArgs& ka, int& nparts) {
+  zigp_ctx* c = s.c;
+  KfState& ks = *s.ks;
+  const int waves = std::min(ka.ntiles, 1024 / s.nlat);   // one wave per SIMD of the chip: the kernels hold ~400-500 registers per lane
+  ka.tpw = (ka.ntiles + waves - 1) / waves;
+  const int nw = (ka.ntiles + ka.tpw - 1) / ka.tpw;
+  const int nwg = (nw + KF_WAVES - 1) / KF_WAVES;
+  nparts = nwg * KF_WAVES;
+  ZIGP_ENSURE(c, ks.acc, (size_t)2 * nparts * s.nblk * 256);
+  for (int h = 0; h < s.nlat; ++h) ka.lat[h].acc = ks.acc.p + (size_t)h * nparts * s.nblk * 256;
+  ZIGP_TRY(kf_launch_small_latents(c, s.Mq, s.nlat, true, (unsigned)nwg, ka));
+  if constexpr (TAP) { tap->facts[ZIGP_KFF_TPW_BWD] = ka.tpw; tap->facts[ZIGP_KFF_NRANGES] = 1; }
+  return 0;
+}
+
+// The larger-grid backward kernel spills ~4 KB of operands per point and latent (at 10 x 100), which k_kfl_accum then sums over the points.
+// The rows go through in RANGES of <= 1024 tiles (16 384 rows: <= 128 MB of records for both latents, Infinity-Cache resident), one
+// backward + one accumulate launch per range.  The split of the tiles into accumulation parts of tps tiles does not depend on the
+// ranges (a range is a whole number of parts), so the partial sums -- and k_kf_reduce's fixed-order total -- are the same bits as
+// with one range over everything; memory no longer grows with the row count (rounds 2-3: 0.86 GB for the pptr full batch, and a
+// 64 GB cap with an error beyond it).
+template <bool TAP>
+static int kf_stage_backward_large(KfRun& s, KfTap* tap, KfArgs& ka, int& nparts) {
+  zigp_ctx* c = s.c;
+  KfState& ks = *s.ks;
+  const int nlat = s.nlat, nblk = s.nblk;
+  size_t rec[2] = {0, 0};
+  for (int h = 0; h < nlat; ++h) rec[h] = (size_t)64 * (s.Mq[h][0] + s.Mq[h][1]);
+  const int tps = std::max(4, std::min(64, ka.ntiles / 16));     // tiles per accumulation part (4 for a minibatch: the chain of dependent loads is short)
+  nparts = (ka.ntiles + tps - 1) / tps;
+  const int range_tiles = std::max(1, c->kron_range_tiles / tps) * tps;
+  const int spill_tiles = std::min(ka.ntiles, range_tiles);
+  ZIGP_ENSURE(c, ks.spill, (rec[0] + (nlat == 2 ? rec[1] : 0)) * spill_tiles);
+  ka.lat[0].spill = ks.spill.p;
+  if (nlat == 2) ka.lat[1].spill = ks.spill.p + rec[0] * spill_tiles;
+  ZIGP_ENSURE(c, ks.acc, (size_t)2 * nparts * nblk * 256);
+  KflAccArgs aa;
+  memset(&aa, 0, sizeof(aa));
+  aa.X = ka.X; aa.N = s.N; aa.ldx = s.ldx; aa.ntiles = ka.ntiles; aa.tps = tps; aa.nb0c = s.pl.nb0c; aa.nb1c = s.pl.nb1c;
+  for (int h = 0; h < nlat; ++h) {
+    KflAccLat& L = aa.lat[h];
+    L.spill = ka.lat[h].spill; L.gm = ka.lat[h].gm; L.gv = ka.lat[h].gv;
+    L.acc = ks.acc.p + (size_t)h * nparts * nblk * 256;
+    ka.lat[h].acc = L.acc;
+    L.nb0 = s.Mq[h][0] / 16; L.nb1 = s.Mq[h][1] / 16; L.D0 = s.D0; L.D1 = s.D1;
+    L.hyp0 = s.d_hyp + (2 * h) * KH_FAC; L.hyp1 = s.d_hyp + (2 * h + 1) * KH_FAC;
+  }
+  for (int t0 = 0; t0 < ka.ntiles; t0 += range_tiles) {
+    const int t1 = std::min(t0 + range_tiles, ka.ntiles), nt = t1 - t0;
+    const int rwaves = std::min(nt, 1024 / nlat);   // one wave per SIMD of the chip: the kernels hold ~400-500 registers per lane
+    ka.tile0 = t0; ka.tile1 = t1; ka.tpw = (nt + rwaves - 1) / rwaves;
+    const int rnw = (nt + ka.tpw - 1) / ka.tpw, rnwg = (rnw + KF_WAVES - 1) / KF_WAVES;
+    if (s.large_exact) hipLaunchKernelGGL((k_kfl_backward<1, 7, true, true>), dim3(rnwg, nlat), dim3(64 * KF_WAVES), s.lds_bwd, c->stream, ka);
+    else hipLaunchKernelGGL((k_kfl_backward<1, 7, true, false>), dim3(rnwg, nlat), dim3(64 * KF_WAVES), s.lds_bwd, c->stream, ka);
+    ZIGP_HIP(c, hipGetLastError());
+    aa.tile0 = t0; aa.tile1 = t1; aa.part0 = t0 / tps;
+    hipLaunchKernelGGL(k_kfl_accum, dim3((nblk + 3) / 4, (nt + tps - 1) / tps, nlat), dim3(256), 0, c->stream, aa);
+    ZIGP_HIP(c, hipGetLastError());
+    if constexpr (TAP) { if (t0 == 0) tap->facts[ZIGP_KFF_TPW_BWD] = ka.tpw; ++tap->facts[ZIGP_KFF_NRANGES]; }
+  }
+  if constexpr (TAP) { tap->facts[ZIGP_KFF_TPS] = tps; tap->facts[ZIGP_KFF_RANGE_TILES] = range_tiles; }
+  return 0;
+}
+
+// fixed-order sum of the nparts partials into the work buffers; its extra workgroup sums the point-wise block partials (k_kron_pw_reduce)
+template <bool TAP>
+static int kf_stage_reduce(KfRun& s, KfTap* tap, const KfArgs& ka, int nparts) {
+  zigp_ctx* c = s.c;
+  const int nlat = s.nlat, gl_ = nlat - 1;
+  hipLaunchKernelGGL(k_kf_reduce, dim3(s.nblk * 256 / 16 + 1, nlat), dim3(256), 0, c->stream, ka.lat[0].acc, ka.lat[gl_].acc, nparts,
+                     s.lat(0) + s.LAT_WORK, s.lat(gl_) + s.LAT_WORK, s.pl.nb0c, s.pl.nb1c, s.Mq[0][0] / 16, s.Mq[0][1] / 16, s.Mq[gl_][0] / 16, s.Mq[gl_][1] / 16,
+                     s.d_pwacc, s.pw_blocks, s.k->include_kl ? 1.0 : 0.0, s.ks->res.p + s.RES_PWS);
+  ZIGP_HIP(c, hipGetLastError());
+  if constexpr (TAP) {
+    tap->facts[ZIGP_KFF_NPARTS] = nparts;
+    for (int h = 0; h < nlat; ++h) ZIGP_TRY(tap->snap(c, tap->s->lat[h].work, s.lat(h) + s.LAT_WORK, (size_t)s.wl.total));
+  }
+  return 0;
+}
+
+// work buffers -> the result block: krow of both factors, the gradients of u and s
+static int kf_stage_finish(KfRun& s) {
+  zigp_ctx* c = s.c;
+  const int nlat = s.nlat;
+  const KfWork& wl = s.wl;
+  KflFinishArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  for (int h = 0; h < nlat; ++h) {
+    KfFinishJob& jb = fa.job[h];
+    jb.M0 = s.k->hl[h].M[0]; jb.M1 = s.k->hl[h].M[1]; jb.Mq0 = s.Mq[h][0]; jb.Mq1 = s.Mq[h][1]; jb.D0 = s.D0; jb.D1 = s.D1;
+    jb.P0 = s.fac(h, 0) + s.FAC_P; jb.P1 = s.fac(h, 1) + s.FAC_P; jb.dvec0 = s.fac(h, 0) + s.FAC_DV; jb.dvec1 = s.fac(h, 1) + s.FAC_DV;
+    jb.PF0 = s.fac(h, 0) + s.FAC_PF; jb.PF1 = s.fac(h, 1) + s.FAC_PF;
+    jb.K0 = s.fac(h, 0); jb.K1 = s.fac(h, 1); jb.Z0 = s.ks->in.p + s.off_z[h][0]; jb.Z1 = s.ks->in.p + s.off_z[h][1];
+    jb.hyp0 = s.d_hyp + (2 * h) * KH_FAC; jb.hyp1 = s.d_hyp + (2 * h + 1) * KH_FAC;
+    double* L = s.lat(h);
+    jb.U = L + s.LAT_U; jb.S2 = L + s.LAT_S2; jb.T0 = L + s.LAT_T0; jb.T1 = L + s.LAT_T1; jb.Al = L + s.LAT_AL; jb.s = s.ks->in.p + s.off_s[h];
+    jb.work = L + s.LAT_WORK;
+    jb.krow0 = s.res(h) + s.RES_KROW0; jb.krow1 = s.res(h) + s.RES_KROW1; jb.gu = s.res(h) + s.RES_GU; jb.gs = s.res(h) + s.RES_GS;
+  }
+  fa.jitter = s.k->jitter; fa.with_kl = s.k->include_kl ? 1 : 0;
+  fa.ldw = wl.ldw; fa.wS2 = wl.S2; fa.wP0 = wl.P0; fa.wP1 = wl.P1; fa.wK0 = wl.K0; fa.wK1 = wl.K1;
+  fa.scratch_off = (int64_t)wl.total; fa.scratch_set = (int64_t)s.SCR_SET;
+  if (s.pl.large) {
+    int nbmax = 1;
+    for (int h = 0; h < nlat; ++h) nbmax = std::max(nbmax, std::max(s.Mq[h][0], s.Mq[h][1]) / 16);
+    const dim3 grid(nbmax, 2, nlat);
+    hipLaunchKernelGGL(k_kfl_finish<1>, grid, dim3(KFL_FIN_THREADS), 0, c->stream, fa);
+    hipLaunchKernelGGL(k_kfl_finish<2>, grid, dim3(KFL_FIN_THREADS), 0, c->stream, fa);
+    hipLaunchKernelGGL(k_kfl_finish<3>, grid, dim3(KFL_FIN_THREADS), 0, c->stream, fa);
+  } else {
+    KfFinishArgs fs;
+    memset(&fs, 0, sizeof(fs));
+    fs.job[0] = fa.job[0]; fs.job[1] = fa.job[1]; fs.jitter = fa.jitter; fs.with_kl = fa.with_kl;
+    hipLaunchKernelGGL(k_kf_finish, dim3(2, nlat), dim3(1024), KF_FIN_LDS, c->stream, fs);
+  }
+  ZIGP_HIP(c, hipGetLastError());
+  return 0;
+}
+
+template <bool TAP>
+static int kf_step(KfRun& s, KfTap* tap, const double* Xd, const double* Yd) {
+  zigp_ctx* c = s.c;
+  const bool predict = s.k->predict;
+  if (c->comm && !predict) ZIGP_HIP(c, hipMemsetAsync(s.ks->res.p, 0, sizeof(double) * s.RES_INFO, c->stream));   // parts a value-only / single-latent step leaves unwritten
+  ZIGP_TRY(kf_stage_factor<TAP>(s, tap));
+  if (predict) ZIGP_TRY(request_info(c, &s.hinfo));   // value / gradient steps: the status slots come back with the result block
+  ZIGP_TRY(kf_stage_latent<TAP>(s, tap));
+  KfArgs ka;
+  ZIGP_TRY(kf_stage_point_forward<TAP>(s, tap, Xd, ka));
+  ZIGP_TRY(kf_stage_pointwise<TAP>(s, tap, Yd));
+  if (predict) return 0;
+  if (s.need_grad) {
+    int nparts = 0;
+    if (s.pl.large) ZIGP_TRY(kf_stage_backward_large<TAP>(s, tap, ka, nparts));
+    else ZIGP_TRY(kf_stage_backward_small<TAP>(s, tap, ka, nparts));
+    ZIGP_TRY(kf_stage_reduce<TAP>(s, tap, ka, nparts));
+    ZIGP_TRY(kf_stage_finish(s));
+  }
+  if (c->comm) {   // data-parallel run: the block (cleared at the start of the step) is summed over ranks where it lies
+    // a rank that does not count the KL (include_kl = 0) must not add its scalars, which the latent kernel writes regardless
+    if (!s.k->include_kl) for (int h = 0; h < s.nlat; ++h) ZIGP_HIP(c, hipMemsetAsync(s.res(h) + s.RES_KLV, 0, sizeof(double) * 8, c->stream));
+    ZIGP_TRY(comm_allreduce(c, s.ks->res.p, s.RES_INFO));
+  }
+  return 0;
+}
+
+// the plan of the step as the stage tests read it (ZIGP_KFF_*); the stages fill in the launch facts
+static void kf_tap_plan(const KfRun& s, KfTap* tap) {
+  const int g = s.nlat - 1;
+  const int64_t f0[ZIGP_KFF_COUNT] = {s.pl.large, s.large_exact, s.pl.nb0c, s.pl.nb1c, s.Mq[0][0] / 16, s.Mq[0][1] / 16, s.Mq[g][0] / 16, s.Mq[g][1] / 16,
+                                      s.Npad, s.Npad / 16, 0, 0, 0, 0, 0, 0,
+                                      (s.pl.large || s.nlat == 1 || (s.Mq[0][0] == s.Mq[1][0] && s.Mq[0][1] == s.Mq[1][1])) ? 1 : 0};
+  memcpy(tap->facts, f0, sizeof(f0));
+}
+
+// ---- fit call: n_steps steps back to back, parameters updated on the device, ONE synchronisation at the end ----
+// the descriptor of k_fit_update: the blocks of the free vector, where their values go in the parameter image, the result block
+static int kf_fit_describe(const KfRun& s, KfFitDesc& d) {
+  const KfFitCall* fit = s.fit;
+  const int nlat = s.nlat;
+  d.nlat = nlat; d.D0 = s.D0; d.D1 = s.D1;
+  const int nblocks = fit->head ? ZIGP_HEAD_FIT_BLOCKS : KFIT_BLOCKS;
+  size_t o = 0;
+  auto block = [&](int b, int n, size_t dst) {
+    d.off[b] = (int)o; d.n[b] = n; d.dst[b] = (int)dst; d.positive[b] = fit->positive[b]; d.lr[b] = fit->lr[b];
+    d.trainable[b] = fit->trainable ? (fit->trainable[b] != 0) : 1;
+    o += n;
+  };
+  for (int h = 0; h < nlat; ++h) {
+    const int M0 = s.k->hl[h].M[0], M1 = s.k->hl[h].M[1];
+    const int sizes[8] = {M0 * s.D0, M1 * s.D1, M0 * M1, M0 * M1, s.D0, s.D1, 1, 1};
+    const size_t dsts[8] = {s.off_z[h][0], s.off_z[h][1], s.off_u[h], s.off_s[h], 0, 0, 0, 0};
+    for (int k = 0; k < 8; ++k) block(8 * h + k, sizes[k], dsts[k]);
+    for (int q = 0; q < 2; ++q) { d.M[h][q] = s.k->hl[h].M[q]; d.Mq[h][q] = s.Mq[h][q]; d.off_z[h][q] = (int)s.off_z[h][q]; }
+  }
+  for (int b = 8 * nlat; b < nblocks; ++b) block(b, 1, 0);      // the likelihood variance (head: and f_mu)
+  if ((int64_t)o != fit->n_free) { s.c->err = std::string(fit->name) + ": n_free does not match the model sizes"; return ZIGP_EARG; }
+  d.off_hyp = (int)s.off_hyp; d.off_hyp2 = (int)s.off_hyp2;
+  int nbig = 0, nhyp = 0, kb = 0, kh = 0;
+  for (int b = 0; b < nblocks; ++b) {
+    const bool big = b < 8 * nlat && b % 8 <= 3;
+    if (big) { d.big_blk[kb] = b; d.big_off[kb++] = nbig; nbig += d.n[b]; }
+    else { d.hyp_blk[kh] = b; d.hyp_off[kh++] = nhyp; nhyp += d.n[b]; }
+  }
+  for (; kb <= 8; ++kb) d.big_off[kb] = nbig;      // kfit_element walks eight big and nine hyperparameter blocks: the ones a
+  for (; kh <= 9; ++kh) d.hyp_off[kh] = nhyp;      // layout does not have start at the total (no thread maps to them)
+  d.res_size = (int)s.RES_SIZE; d.res_krow0 = (int)s.RES_KROW0; d.res_krow1 = (int)s.RES_KROW1; d.res_gu = (int)s.RES_GU; d.res_gs = (int)s.RES_GS;
+  d.res_pws = (int)s.RES_PWS; d.res_info = (int)s.RES_INFO;
+  d.beta1 = fit->beta1; d.beta2 = fit->beta2; d.eps = fit->eps;
+  return 0;
+}
+
+static int kf_fit_run(KfRun& s) {
+  zigp_ctx* c = s.c;
+  KfState& ks = *s.ks;
+  const KfFitCall* fit = s.fit;
+  const int64_t N = s.N;
+  const int ldx = s.ldx;
+  KfFitArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  ZIGP_TRY(kf_fit_describe(s, fa.d));
+  const KfFitDesc& d = fa.d;
+  const size_t nf = (size_t)fit->n_free, n_hist = (size_t)2 * fit->n_steps;
+  const size_t n_state = 3 * nf + n_hist + 8;
+  ZIGP_ENSURE(c, ks.fit, n_state);
+  fa.x = ks.fit.p; fa.m = fa.x + nf; fa.v = fa.m + nf; fa.hist = fa.v + nf; fa.fail = reinterpret_cast<int*>(fa.hist + n_hist);
+  fa.img = ks.in.p; fa.res = ks.res.p;
+  {
+    ZIGP_PINNED(c, hst, n_state);
+    memcpy(hst, fit->x, sizeof(double) * nf); memcpy(hst + nf, fit->m, sizeof(double) * nf); memcpy(hst + 2 * nf, fit->v, sizeof(double) * nf);
+    memset(hst + 3 * nf, 0, sizeof(double) * (n_hist + 8));
+    ZIGP_HIP(c, hipMemcpyAsync(ks.fit.p, hst, sizeof(double) * n_state, hipMemcpyHostToDevice, c->stream));
+    if (s.n_wrap) {
+      const size_t nw = s.n_wrap * (size_t)N * (ldx + 1);
+      ZIGP_PINNED(c, hw, nw);
+      memcpy(hw, fit->Xw, sizeof(double) * s.n_wrap * N * ldx);
+      memcpy(hw + s.n_wrap * (size_t)N * ldx, fit->Yw, sizeof(double) * s.n_wrap * N);
+      ZIGP_HIP(c, hipMemcpyAsync(s.d_wrap, hw, sizeof(double) * nw, hipMemcpyHostToDevice, c->stream));
+    }
+  }
+  ZIGP_HIP(c, hipMemsetAsync(ks.in.p + s.off_hyp, 0, sizeof(double) * 2 * KH_SIZE, c->stream));
+  const dim3 ugrid((d.big_off[8] + KFIT_THREADS - 1) / KFIT_THREADS + 1);
+  fa.update = 0; fa.step = 0;
+  auto update = [&] {
+    if (fit->head) hipLaunchKernelGGL(k_fit_update<true>, ugrid, dim3(KFIT_THREADS), 0, c->stream, fa);
+    else hipLaunchKernelGGL(k_fit_update<false>, ugrid, dim3(KFIT_THREADS), 0, c->stream, fa);
+  };
+  update();       // free state -> parameter image (hyper block 0)
+  ZIGP_HIP(c, hipGetLastError());
+  fa.update = 1;
+  const double *X = s.k->X, *Y = s.k->Y;      // the resident data set
+  for (int i = 0; i < fit->n_steps; ++i) {
+    const int64_t rb = fit->row_begin[i];
+    const double* Xd = rb >= 0 ? X + rb * ldx : s.d_wrap + (size_t)(-rb - 1) * N * ldx;
+    const double* Yd = rb >= 0 ? Y + rb : s.d_wrap + s.n_wrap * (size_t)N * ldx + (size_t)(-rb - 1) * N;
+    s.d_hyp = ks.in.p + ((i & 1) ? s.off_hyp2 : s.off_hyp);       // written by the previous step's update (step 0: by the launch above)
+    ZIGP_TRY(kf_step<false>(s, nullptr, Xd, Yd));
+    // lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t), t counted from 1 (zigp/optim.py AdamGroups.step): the two t-dependent factors from the host
+    const double t = (double)(fit->t0 + i + 1);
+    fa.step = i; fa.lr_sq = std::sqrt(1.0 - std::pow(d.beta2, t)); fa.lr_den = 1.0 - std::pow(d.beta1, t);
+    update();
+    ZIGP_HIP(c, hipGetLastError());
+  }
+  double* hst = nullptr;
+  ZIGP_TRY(download(c, ks.fit.p, n_state, &hst));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  const int* hfail = reinterpret_cast<const int*>(hst + 3 * nf + n_hist);
+  memcpy(fit->x, hst, sizeof(double) * nf); memcpy(fit->m, hst + nf, sizeof(double) * nf); memcpy(fit->v, hst + 2 * nf, sizeof(double) * nf);
+  const int done = hfail[0] ? hfail[0] - 1 : fit->n_steps;       // steps whose update was applied
+  c->fit_steps_applied = done;                                   // (zigp_kron_fit_steps_applied: the caller's iteration count advances by this)
+  for (int i = 0; i < fit->n_steps; ++i) {
+    if (fit->hist_data) fit->hist_data[i] = i < done ? hst[3 * nf + 2 * i] : NAN;
+    if (fit->hist_kl) fit->hist_kl[i] = i < done ? hst[3 * nf + 2 * i + 1] : NAN;
+  }
+  if (hfail[0]) {
+    char b[288];
+    snprintf(b, sizeof(b), "Cholesky failed in step %d of this %s call (iteration %lld): %s not positive definite at pivot %d; "
+             "the state returned is the one before that step", hfail[0] - 1, fit->name, (long long)(fit->t0 + hfail[0] - 1), kron_fac_names[hfail[1] & 3], hfail[2]);
+    c->err = b; c->info = hfail[2];
+    return ZIGP_ENOTPD;
+  }
+  return 0;
+}
+
+// the result block of a value / gradient step -> the outputs of the call
+static int kf_gather(KfRun& s) {
+  zigp_ctx* c = s.c;
+  const KronCall& k = *s.k;
+  double* hres = nullptr;
+  ZIGP_TRY(download(c, s.ks->res.p, s.n_res, &hres));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  for (int j = 0; j < 2 * s.nlat; ++j) ZIGP_TRY(info_result(c, reinterpret_cast<const int*>(hres + s.RES_INFO) + 2 * j, kron_fac_names[j]));
+  const double* pws = hres + s.RES_PWS;   // var_exp, d noise, sum gv_f, sum gv_g, sum gm_f (= d / d f_mu); [7]: the ranks that count the KL
+  if (k.elbo_data) *k.elbo_data = pws[0];
+  if (k.d_offset) *k.d_offset = pws[4];
+  double* R[2] = {hres, hres + s.RES_SIZE};
+  if (k.kl) { const double* klv[2] = {R[0] + s.RES_KLV, R[1] + s.RES_KLV}; *k.kl = kron_kl(k, klv, pws[7]); }
+  if (s.need_grad) {
+    double* krow[2][2] = {{R[0] + s.RES_KROW0, R[0] + s.RES_KROW1}, {R[1] + s.RES_KROW0, R[1] + s.RES_KROW1}};
+    double* gu[2] = {R[0] + s.RES_GU, R[1] + s.RES_GU};
+    double* gs[2] = {R[0] + s.RES_GS, R[1] + s.RES_GS};
+    kron_assemble_grads(k, krow, gu, gs, pws + 2, pws[1]);
+  }
+  return 0;
+}
+
+// One ELBO step (or prediction) of the fused Kronecker path.  fit != nullptr: n_steps gradient steps with the Adam update on the device
+// (k.p then carries the sizes only; k.X / k.Y are the resident data set).  tap != nullptr: the step of the stage tests
+// (zigp_test_kron_fused_step).
+static int kronf_run(zigp_ctx* c, const KronCall& k, const KfFitCall* fit = nullptr, KfTap* tap = nullptr) {
+  KfRun s;
+  ZIGP_TRY(kf_prepare(c, k, fit, s));
+  if (!fit) ZIGP_TRY(kf_stage_inputs(s));
+  if (k.predict) ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
+  ZIGP_TRY(kf_set_attributes(c));
+  if (fit) return kf_fit_run(s);
+  const double* Xd = k.dev_xy ? k.X : s.ks->in.p + s.off_x;
+  const double* Yd = k.Y ? (k.dev_xy ? k.Y : s.ks->in.p + s.off_y) : nullptr;
+  if (tap) {
+    kf_tap_plan(s, tap);
+    ZIGP_TRY(kf_step<true>(s, tap, Xd, Yd));
+  } else {
+    ZIGP_TRY(kf_step<false>(s, nullptr, Xd, Yd));
+  }
+  if (!k.predict) return kf_gather(s);
+  ZIGP_HIP(c, hipMemcpyAsync(k.out, s.ks->out.p, sizeof(double) * (k.nlat == 2 ? 9 : 4) * k.N, hipMemcpyDeviceToHost, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  return info_result(c, s.hinfo, kron_fac_any);
 }
 
 }  // namespace zigp

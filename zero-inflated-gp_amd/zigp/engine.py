@@ -952,20 +952,68 @@ class DenseEngine:
         s.noise = _scalar(p.get('noise', 1.0))
         return s, keep, dims
 
+    @staticmethod
+    def _kron_rows(X, dims, name='X'):
+        """the rows of a Kronecker call as float64 (N, D0 + D1)"""
+        X = as_f64(X)
+        if X.ndim != 2 or X.shape[1] != dims[0] + dims[1]:
+            raise ValueError('%s must be (N,%d)' % (name, dims[0] + dims[1]))
+        return X
+
+    @classmethod
+    def _kron_xy(cls, X, Y, rows, dims):
+        """(X, Y) of an explicit host minibatch, checked; (None, None) with rows=(lo, hi) of the resident data set -- not both"""
+        if rows is None:
+            X = cls._kron_rows(X, dims)
+            Y = as_f64(Y).reshape(-1)
+            if Y.size != X.shape[0]:
+                raise ValueError('Y must have N entries')
+            return X, Y
+        if X is not None or Y is not None:
+            raise ValueError('pass either (X, Y) or rows=(lo, hi), not both')
+        return None, None
+
+    def _kron_fit_call(self, fn, lead, x, m, v, t0, row_begin, batch, jitter, scale, Xw, Yw, include_kl):
+        """The part kron_fit_steps and kron_head_fit_steps share: fn is the library's entry point, lead its arguments between the
+        context and the free state (the shape and options structs, the head's likelihood)."""
+        for a in (x, m, v):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.ndim == 1 and a.size == x.size):
+                raise ValueError('x, m, v must be contiguous float64 vectors of one length')
+        rb = np.ascontiguousarray(np.asarray(row_begin, dtype=np.int64))
+        n = rb.size
+        xw = yw = None
+        if Xw is not None:
+            xw, yw = as_f64(Xw), as_f64(Yw).reshape(-1)
+            if xw.ndim != 2 or xw.shape[0] % int(batch) or yw.size != xw.shape[0]:
+                raise ValueError('Xw must hold whole batches of `batch` rows, Yw one value per row')
+            if rb.min() < -(xw.shape[0] // int(batch)):
+                raise ValueError('row_begin refers to a host batch beyond Xw')
+        elif n and rb.min() < 0:
+            raise ValueError('negative row_begin needs Xw, Yw')
+        ed, kl = np.zeros(n), np.zeros(n)
+        rc = fn(self.ctx, *lead, ptr(x), ptr(m), ptr(v), x.size, int(t0), n, rb.ctypes.data, int(batch),
+                ptr(xw) if xw is not None else None, ptr(yw) if yw is not None else None, float(jitter), float(scale),
+                1 if include_kl else 0, ptr(ed), ptr(kl))
+        try:
+            _check(self.lib, self.ctx, rc)
+        except ZigpError as e:
+            # include/zigp.h: after a failure x / m / v hold the state before the failing step and the history from that step on is NaN --
+            # the caller learns how many updates WERE applied (its iteration count and Adam's bias correction depend on it) and gets the
+            # history of those steps
+            # (the count comes from the library -- zigp_kron_fit_steps_applied, one counter for both loops; the first non-finite history
+            # entry is NOT it: an applied step can itself have a non-finite ELBO at extreme parameters, ADVICE r5)
+            done = max(0, min(n, int(self.lib.zigp_kron_fit_steps_applied(self.ctx))))
+            e.steps_applied = done
+            e.elbo_data, e.kl = ed[:done].copy(), kl[:done].copy()
+            raise
+        return ed, kl
+
     def kron_elbo(self, p, X=None, Y=None, jitter=1e-5, scale=1.0, g_offset=0.0, include_kl=True, need_grad=True, rows=None, f_mu=None):
         """One Kronecker ELBO (step); returns (elbo_data, kl, grads or None).  Either an explicit host minibatch (X, Y), as
         scripts/onoff.py:377-381 feeds it, or rows=(lo, hi) of the resident data set (set_data / set_data_device).
         f_mu: the optional constant added to fmean (scripts/onoff.py:161,168-169); when given, grads['f_mu'] is its gradient."""
         s, keep, dims = self._pack_kron(p)
-        if rows is None:
-            X = as_f64(X)
-            if X.ndim != 2 or X.shape[1] != dims[0] + dims[1]:
-                raise ValueError('X must be (N,%d)' % (dims[0] + dims[1]))
-            Y = as_f64(Y).reshape(-1)
-            if Y.size != X.shape[0]:
-                raise ValueError('Y must have N entries')
-        elif X is not None or Y is not None:
-            raise ValueError('pass either (X, Y) or rows=(lo, hi), not both')
+        X, Y = self._kron_xy(X, Y, rows, dims)
         ed, kl, dmu = C.c_double(0), C.c_double(0), C.c_double(0)
         fmu = 0.0 if f_mu is None else _scalar(f_mu)
         g, gs = None, None
@@ -1022,37 +1070,8 @@ class DenseEngine:
         for b in range(_lib.FIT_BLOCKS):
             o.lr[b] = float(lr[b]); o.positive[b] = int(bool(positive[b]))
         o.beta1, o.beta2, o.eps = float(beta1), float(beta2), float(eps)
-        for a in (x, m, v):
-            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.ndim == 1 and a.size == x.size):
-                raise ValueError('x, m, v must be contiguous float64 vectors of one length')
-        rb = np.ascontiguousarray(np.asarray(row_begin, dtype=np.int64))
-        n = rb.size
-        xw = yw = None
-        if Xw is not None:
-            xw, yw = as_f64(Xw), as_f64(Yw).reshape(-1)
-            if xw.ndim != 2 or xw.shape[0] % int(batch) or yw.size != xw.shape[0]:
-                raise ValueError('Xw must hold whole batches of `batch` rows, Yw one value per row')
-            if rb.min() < -(xw.shape[0] // int(batch)):
-                raise ValueError('row_begin refers to a host batch beyond Xw')
-        elif n and rb.min() < 0:
-            raise ValueError('negative row_begin needs Xw, Yw')
-        ed, kl = np.zeros(n), np.zeros(n)
-        rc = self.lib.zigp_kron_fit_steps(self.ctx, C.byref(s), C.byref(o), ptr(x), ptr(m), ptr(v), x.size, int(t0), n, rb.ctypes.data, int(batch),
-                                          ptr(xw) if xw is not None else None, ptr(yw) if yw is not None else None, float(jitter), float(scale),
-                                          1 if include_kl else 0, ptr(ed), ptr(kl))
-        try:
-            _check(self.lib, self.ctx, rc)
-        except ZigpError as e:
-            # include/zigp.h: after a failure x / m / v hold the state before the failing step and the history from that step on is NaN --
-            # the caller learns how many updates WERE applied (its iteration count and Adam's bias correction depend on it) and gets the
-            # history of those steps
-            # (the count comes from the library -- zigp_kron_fit_steps_applied; the first non-finite history entry is NOT it: an applied
-            # step can itself have a non-finite ELBO at extreme parameters)
-            done = max(0, min(n, int(self.lib.zigp_kron_fit_steps_applied(self.ctx))))
-            e.steps_applied = done
-            e.elbo_data, e.kl = ed[:done].copy(), kl[:done].copy()
-            raise
-        return ed, kl
+        return self._kron_fit_call(self.lib.zigp_kron_fit_steps, (C.byref(s), C.byref(o)), x, m, v, t0, row_begin, batch, jitter, scale, Xw, Yw,
+                                   include_kl)
 
     def kron_stepper(self, p):
         """A prepared Kronecker step for a FIXED model shape (the training loop: scripts/onoff.py:375-431 calls sess.run on one graph 50 000
@@ -1063,9 +1082,7 @@ class DenseEngine:
     def kron_predict(self, p, Xnew, jitter=1e-6, g_offset=0.0, f_mu=None):
         """(9,N) in the order of build_predict (scripts/onoff.py:184); onofftf/onoffpred.py uses jitter 1e-6, g_offset -1."""
         s, keep, dims = self._pack_kron(p)
-        Xnew = as_f64(Xnew)
-        if Xnew.ndim != 2 or Xnew.shape[1] != dims[0] + dims[1]:
-            raise ValueError('Xnew must be (N,%d)' % (dims[0] + dims[1]))
+        Xnew = self._kron_rows(Xnew, dims, 'Xnew')
         out = np.zeros((9, Xnew.shape[0]))
         _check(self.lib, self.ctx, self.lib.zigp_kron_predict(self.ctx, C.byref(s), ptr(Xnew), Xnew.shape[0], float(jitter),
                                                                float(g_offset), 0.0 if f_mu is None else _scalar(f_mu), ptr(out)))
@@ -1079,15 +1096,7 @@ class DenseEngine:
         minibatch (X, Y) or rows=(lo, hi) of the resident data set (set_data / set_data_device; zigp_kron_head_elbo_rows).
         Returns (elbo_data, kl, grads or None); grads has the f keys, 'noise' and 'f_mu'."""
         s, keep, dims = self._pack_kron(p, tags=('f',))
-        if rows is None:
-            X = as_f64(X)
-            if X.ndim != 2 or X.shape[1] != dims[0] + dims[1]:
-                raise ValueError('X must be (N,%d)' % (dims[0] + dims[1]))
-            Y = as_f64(Y).reshape(-1)
-            if Y.size != X.shape[0]:
-                raise ValueError('Y must have N entries')
-        elif X is not None or Y is not None:
-            raise ValueError('pass either (X, Y) or rows=(lo, hi), not both')
+        X, Y = self._kron_xy(X, Y, rows, dims)
         ed, kl, dmu = C.c_double(0), C.c_double(0), C.c_double(0)
         gs, a = None, None
         if need_grad:
@@ -1128,39 +1137,13 @@ class DenseEngine:
         for b in range(_lib.HEAD_FIT_BLOCKS):
             o.lr[b] = float(lr[b]); o.positive[b] = int(bool(positive[b])); o.trainable[b] = int(bool(trainable[b]))
         o.beta1, o.beta2, o.eps = float(beta1), float(beta2), float(eps)
-        for a in (x, m, v):
-            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.ndim == 1 and a.size == x.size):
-                raise ValueError('x, m, v must be contiguous float64 vectors of one length')
-        rb = np.ascontiguousarray(np.asarray(row_begin, dtype=np.int64))
-        n = rb.size
-        xw = yw = None
-        if Xw is not None:
-            xw, yw = as_f64(Xw), as_f64(Yw).reshape(-1)
-            if xw.ndim != 2 or xw.shape[0] % int(batch) or yw.size != xw.shape[0]:
-                raise ValueError('Xw must hold whole batches of `batch` rows, Yw one value per row')
-            if rb.min() < -(xw.shape[0] // int(batch)):
-                raise ValueError('row_begin refers to a host batch beyond Xw')
-        elif n and rb.min() < 0:
-            raise ValueError('negative row_begin needs Xw, Yw')
-        ed, kl = np.zeros(n), np.zeros(n)
-        rc = self.lib.zigp_kron_head_fit_steps(self.ctx, C.byref(s), self.LIK[lik], C.byref(o), ptr(x), ptr(m), ptr(v), x.size, int(t0), n,
-                                               rb.ctypes.data, int(batch), ptr(xw) if xw is not None else None, ptr(yw) if yw is not None else None,
-                                               float(jitter), float(scale), 1 if include_kl else 0, ptr(ed), ptr(kl))
-        try:
-            _check(self.lib, self.ctx, rc)
-        except ZigpError as e:      # as kron_fit_steps: the count of applied updates comes from the library (the two loops share the counter)
-            done = max(0, min(n, int(self.lib.zigp_kron_fit_steps_applied(self.ctx))))
-            e.steps_applied = done
-            e.elbo_data, e.kl = ed[:done].copy(), kl[:done].copy()
-            raise
-        return ed, kl
+        return self._kron_fit_call(self.lib.zigp_kron_head_fit_steps, (C.byref(s), self.LIK[lik], C.byref(o)), x, m, v, t0, row_begin, batch,
+                                   jitter, scale, Xw, Yw, include_kl)
 
     def kron_head_predict(self, p, Xnew, lik, jitter=1e-6, f_mu=0.0):
         """(4,N): fmean, fvar, pfmean, pfvar (onofftf/svgppred.py:180-186, onofftf/svcppred.py 'pfmean'/'pfvar')."""
         s, keep, dims = self._pack_kron(p, tags=('f',))
-        Xnew = as_f64(Xnew)
-        if Xnew.ndim != 2 or Xnew.shape[1] != dims[0] + dims[1]:
-            raise ValueError('Xnew must be (N,%d)' % (dims[0] + dims[1]))
+        Xnew = self._kron_rows(Xnew, dims, 'Xnew')
         out = np.zeros((4, Xnew.shape[0]))
         _check(self.lib, self.ctx, self.lib.zigp_kron_head_predict(self.ctx, C.byref(s), self.LIK[lik], ptr(Xnew), Xnew.shape[0],
                                                                     float(jitter), float(f_mu), ptr(out)))
