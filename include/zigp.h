@@ -508,7 +508,7 @@ int zigp_predict_scores_device(zigp_ctx* ctx, const zigp_params* p, const double
  * correct for every finite argument; beyond the library's fast range (|argument| of about 1e5 and more) it takes a slower path.
  * ZIGP_EARG with a message that names the argument, nothing enqueued and the context usable afterwards: D > 8 (the message names D),
  * S outside [1, 256], R < 0, M < 1, an unknown kind, a NULL table, a non-finite table entry, and a host pointer handed to a _device call.
- * The Kronecker path, the heads and D > 8 have no sample paths. */
+ * The Kronecker path and its heads draw their paths through the entry points of zigp_kronpaths.h; D > 8 has none. */
 #define ZIGP_PATH_MAX_S 256
 typedef struct {
   int32_t kind, M, R, reserved;      /* ZIGP_KERN_*, inducing points, random features */
@@ -549,6 +549,10 @@ int zigp_sample_paths(zigp_ctx* ctx, const zigp_params* p, const double* Xnew, i
 /* The same with Xnew and out3 in DEVICE memory of the context's GPU; the draws stay host pointers; complete on return. */
 int zigp_sample_paths_device(zigp_ctx* ctx, const zigp_params* p, const double* dXnew, int64_t N, double jitter, double g_offset,
                              const zigp_path_draw* draw_f, const zigp_path_draw* draw_g, int32_t S, double* d_out3);
+
+/* ---- Kronecker sample paths: the same draws for the Kronecker (space x time) model and its heads (new).
+ * Their record and entry points are declared in zigp_kronpaths.h, which is part of this boundary. */
+#include "zigp_kronpaths.h"
 
 /* ---- inducing inputs by k-means on the device: Lloyd iterations (new entry points) ----
  * Replaces the host-side scipy.cluster.vq.kmeans call that picks the inducing inputs before the first ELBO step (scripts/onoff.py:67,

@@ -5,5 +5,6 @@
 #include "zigp_density.hip"
 #include "zigp_score.hip"
 #include "zigp_paths.hip"
+#include "zigp_kronpaths.hip"
 #include "zigp_kmeans.hip"
 #include "zigp_comm.hip"

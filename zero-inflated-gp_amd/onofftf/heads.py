@@ -288,14 +288,19 @@ def close_logger(logger, handler):
     logger.removeHandler(handler)
 
 
-def restore_and_predict(lik, Xtrain, Xtest, checkpointPath, num_inducing_f, include_f_mu, rows, device=0, engine=None):
-    """svgppred.py:15-203 / svcppred.py:15-224: rebuild the parameter set, restore, evaluate with jitter 1e-6."""
+def _restore_head(lik, Xtrain, checkpointPath, num_inducing_f, include_f_mu, device, engine):
+    """svgppred.py:15-203 / svcppred.py:15-224: rebuild the parameter set and restore it; (engine, engine parameters, f_mu)"""
     pset = init_head_params(Xtrain, num_inducing_f, lik, init_ell=(8., 8.), u_scale=0.1, init_noisevar=0.001,
                             include_f_mu=include_f_mu, kern_lr=1e-4, indp_lr=1e-4)
     ck = os.path.join(checkpointPath, 'model') if os.path.isdir(checkpointPath) else checkpointPath
     load_checkpoint(pset, ck)
     eng = engine or zigp.reference_engine(device)      # tf.cholesky's acceptance rule (pivot > 0)
-    p, f_mu = head_engine_params(pset), head_f_mu(pset)
+    return eng, head_engine_params(pset), head_f_mu(pset)
+
+
+def restore_and_predict(lik, Xtrain, Xtest, checkpointPath, num_inducing_f, include_f_mu, rows, device=0, engine=None):
+    """Restore (_restore_head), then evaluate with jitter 1e-6."""
+    eng, p, f_mu = _restore_head(lik, Xtrain, checkpointPath, num_inducing_f, include_f_mu, device, engine)
 
     def run(X):
         o = eng.kron_head_predict(p, X, lik, jitter=PREDICT_JITTER, f_mu=f_mu)
@@ -305,3 +310,11 @@ def restore_and_predict(lik, Xtrain, Xtest, checkpointPath, num_inducing_f, incl
     if Xtest is not None:
         return pred_train, run(Xtest)
     return pred_train
+
+
+def restore_and_sample(lik, Xtrain, Xtest, checkpointPath, num_inducing_f, include_f_mu, num_samples, n_features=1024, seed=None, draws=None,
+                       device=0, engine=None):
+    """Restore (_restore_head), then joint sample paths of the head at Xtest (DenseEngine.kron_head_sample_paths, jitter 1e-6)."""
+    eng, p, f_mu = _restore_head(lik, Xtrain, checkpointPath, num_inducing_f, include_f_mu, device, engine)
+    return eng.kron_head_sample_paths(p, Xtest, lik, n_samples=int(num_samples), n_features=n_features, rng=seed, draws=draws,
+                                      jitter=PREDICT_JITTER, f_mu=f_mu)

@@ -29,3 +29,18 @@ def predict_onoff(Xtrain, Xtest, checkpointPath, num_inducing_f=np.array([10, 10
     if Xtest is not None:
         return pred_train, run(Xtest)
     return pred_train
+
+
+def sample_onoff(Xtrain, Xtest, checkpointPath, num_samples, num_inducing_f=np.array([10, 100]), num_inducing_g=np.array([10, 100]),
+                 n_features=1024, seed=None, draws=None, device=0, engine=None):
+    """Joint posterior sample paths of the restored model at Xtest, beside predict_onoff (same restore, jitter 1e-6, gmean shifted by
+    -1): {'f', 'g', 'gf'}, each (num_samples, N) -- a row is one draw of the whole field, so sums over rows (basin or weekly totals)
+    and sample maps come from it -- and 'draws', which gives the same paths at other inputs.  Xtrain only rebuilds the parameter set."""
+    pset = init_params(Xtrain, num_inducing_f, num_inducing_g, init_noisevar=0.001)
+    ck = checkpointPath
+    if os.path.isdir(ck):
+        ck = os.path.join(ck, 'model')
+    load_checkpoint(pset, ck)
+    eng = engine or zigp.reference_engine(device)
+    return eng.kron_sample_paths(engine_params(pset), Xtest, n_samples=int(num_samples), n_features=n_features, rng=seed, draws=draws,
+                                 jitter=jitter_level, g_offset=-1.0)

@@ -80,6 +80,14 @@ class zigp_path_draw(C.Structure):   # include/zigp.h "sample paths"
     _fields_ = [('R', C.c_int32), ('reserved', C.c_int32), ('omega0', dp), ('phase', dp), ('a', dp), ('eps', dp)]
 
 
+KRON_PATH_MAX_M = 128   # include/zigp_kronpaths.h: inducing points per factor (csrc/zigp_kronpaths.hip KP_MAXM)
+
+
+class zigp_kron_path_latent(C.Structure):   # include/zigp_kronpaths.h
+    _fields_ = [('M0', C.c_int32), ('M1', C.c_int32), ('R', C.c_int32), ('reserved', C.c_int32), ('Z0', dp), ('Z1', dp), ('ell0', dp), ('ell1', dp),
+                ('var0', C.c_double), ('var1', C.c_double), ('V', dp), ('omega', dp), ('phase', dp), ('amp', dp), ('shift', C.c_double)]
+
+
 FIT_BLOCKS = 17   # include/zigp.h ZIGP_FIT_BLOCKS
 
 
@@ -293,6 +301,20 @@ SIGNATURES = {
     'zigp_test_kron_kgrad': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp, dp]),
 }
 
+# include/zigp_kronpaths.h (the header zigp.h includes for the Kronecker sample paths): bound by load() like SIGNATURES
+KRON_PATH_SIGNATURES = {
+    'zigp_kron_path_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.c_int64, dp]),
+    'zigp_kron_path_rows_device': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'zigp_kron_sample_paths': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), dp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                                         C.c_void_p, C.c_int32, dp]),
+    'zigp_kron_sample_paths_device': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double,
+                                                C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    'zigp_kron_head_sample_paths': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_int32, dp, C.c_int64, C.c_double, C.c_double, C.c_void_p,
+                                              C.c_int32, dp]),
+    'zigp_kron_head_sample_paths_device': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_int32, C.c_void_p, C.c_int64, C.c_double, C.c_double,
+                                                     C.c_void_p, C.c_int32, C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -312,7 +334,7 @@ def load():
     except Exception:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(KRON_PATH_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -810,6 +810,182 @@ class DenseEngine:
                                                                           C.c_void_p(out.data_ptr())))
         return dict(f=out[0], g=out[1], gf=out[2], draws=draws)
 
+    # ---- Kronecker sample paths (include/zigp_kronpaths.h) ----
+    @staticmethod
+    def _kron_path_latents(lats, dims, S):
+        """The zigp_kron_path_latent records of kron_path_rows and the arrays behind them.  A latent is a dict: Z = [Z0 (M0, D0),
+        Z1 (M1, D1)], ell = [ell0, ell1], var = [var0, var1], V (M0 M1, S) factor-0-major, omega (R, D0 + D1), phase (R), amp (R, S)
+        and, optional, shift.  Sizes and shapes are checked here, before the library is touched."""
+        from . import pathwise
+        D0, D1 = dims
+        if len(lats) not in (1, 2):
+            raise ValueError('kron_path_rows takes one or two latents, not %d' % len(lats))
+        recs, keep = (_lib.zigp_kron_path_latent * len(lats))(), []
+        for h, q in enumerate(lats):
+            Z0, Z1 = as_f64(q['Z'][0]), as_f64(q['Z'][1])
+            if Z0.ndim != 2 or Z1.ndim != 2 or Z0.shape[1] != D0 or Z1.shape[1] != D1:
+                raise ValueError('latent %d: Z must be [(M0,%d), (M1,%d)]' % (h, D0, D1))
+            M0, M1 = Z0.shape[0], Z1.shape[0]
+            pathwise.check_kron_sizes(D0, D1, M0, M1, S)
+            ells = []
+            for k, Dq in ((0, D0), (1, D1)):
+                e = as_f64(q['ell'][k]).reshape(-1)
+                e = np.full(Dq, float(e[0])) if e.size == 1 else np.ascontiguousarray(e)
+                if e.size != Dq:
+                    raise ValueError('latent %d: ell[%d] must be scalar or have %d entries' % (h, k, Dq))
+                ells.append(e)
+            phase = as_f64(q['phase']).reshape(-1)
+            R, D, M = phase.size, D0 + D1, M0 * M1
+            arr = dict(Z0=Z0, Z1=Z1, ell0=ells[0], ell1=ells[1], V=as_f64(q['V']), omega=as_f64(q['omega']).reshape(R, -1) if R else np.zeros((0, D)),
+                       phase=phase, amp=as_f64(q['amp']).reshape(R, -1) if R else np.zeros((0, S)))
+            for k, shape in (('V', (M, S)), ('omega', (R, D)), ('amp', (R, S))):
+                if arr[k].shape != shape:
+                    raise ValueError('latent %d: %s must be %s, not %s' % (h, k, shape, arr[k].shape))
+            r = recs[h]
+            r.M0, r.M1, r.R = M0, M1, R
+            r.var0, r.var1, r.shift = _scalar(q['var'][0]), _scalar(q['var'][1]), float(q.get('shift', 0.0))
+            for k, a in arr.items():
+                setattr(r, k, ptr(a) if a.size else None)
+            keep.append(arr)
+        return recs, keep
+
+    def kron_path_rows(self, lats, X, S, dims):
+        """The finite sum of zigp_kron_path_rows: lats a list of one or two latent dicts (see _kron_path_latents), X (N, D0 + D1) host
+        rows, dims = (D0, D1); returns (nlat, S, N)."""
+        D0, D1 = int(dims[0]), int(dims[1])
+        X = self._kron_rows(X, (D0, D1))
+        recs, keep = self._kron_path_latents(lats, (D0, D1), int(S))
+        N = X.shape[0]
+        out = np.zeros((len(lats), int(S), N))
+        _check(self.lib, self.ctx, self.lib.zigp_kron_path_rows(self.ctx, C.cast(recs, C.c_void_p), len(lats), D0, D1, int(S), ptr(X), N, ptr(out)))
+        return out
+
+    def kron_path_rows_device(self, lats, X_t, S, dims, out=None):
+        """kron_path_rows on a torch CUDA float64 tensor (N, D0 + D1) of the engine's device; returns (or fills `out`, whose first
+        nlat S N entries are the (nlat, S, N) result) a CUDA tensor."""
+        import torch
+        D0, D1 = int(dims[0]), int(dims[1])
+        if not (self._device_f64(X_t) and X_t.dim() == 2 and int(X_t.shape[1]) == D0 + D1):
+            raise ValueError('kron_path_rows_device: X needs a contiguous float64 (N, %d) tensor on cuda:%d' % (D0 + D1, self.device))
+        N = int(X_t.shape[0])
+        recs, keep = self._kron_path_latents(lats, (D0, D1), int(S))
+        if out is None:
+            out = torch.empty((len(lats), int(S), N), dtype=torch.float64, device=X_t.device)
+        elif not (self._device_f64(out) and out.numel() >= len(lats) * int(S) * N):
+            raise ValueError('kron_path_rows_device: out must be a contiguous float64 tensor of at least nlat S N entries on the same device')
+        torch.cuda.current_stream(self.device).synchronize()      # the engine's streams are not ordered after torch's
+        _check(self.lib, self.ctx, self.lib.zigp_kron_path_rows_device(self.ctx, C.cast(recs, C.c_void_p), len(lats), D0, D1, int(S),
+                                                                        C.c_void_p(X_t.data_ptr()), N, C.c_void_p(out.data_ptr())))
+        return out
+
+    @staticmethod
+    def _kron_path_draws(s, dims, tags, n_samples, n_features, rng, draws):
+        """(draws dict, the zigp_path_draw records by tag, the arrays behind them) for the packed Kronecker parameters s"""
+        from . import pathwise
+        S, D = int(n_samples), dims[0] + dims[1]
+        grids = {t: (int(getattr(s, 'M0' + t)), int(getattr(s, 'M1' + t))) for t in tags}
+        for t in tags:
+            pathwise.check_kron_sizes(dims[0], dims[1], grids[t][0], grids[t][1], S)
+        if draws is None:
+            if rng is None:
+                rng = np.random.RandomState()
+            elif isinstance(rng, (int, np.integer)):
+                rng = np.random.RandomState(int(rng))
+            draws = {t: pathwise.draw('rbf', int(n_features), D, grids[t][0] * grids[t][1], S, rng) for t in tags}
+        recs, keep = {}, []
+        for t in tags:
+            R, arr = pathwise.check_draw(draws[t], t, grids[t][0] * grids[t][1], D, S)
+            r = _lib.zigp_path_draw()
+            r.R = R
+            for k, a in arr.items():
+                setattr(r, k, ptr(a) if a.size else None)
+            recs[t] = r
+            keep.append(arr)
+        return draws, recs, keep
+
+    def _kron_paths_out(self, who, X_t, planes, S, out):
+        import torch
+        N = int(X_t.shape[0])
+        if out is None:
+            out = torch.empty((planes, S, N), dtype=torch.float64, device=X_t.device)
+        elif not (self._device_f64(out) and tuple(out.shape) == (planes, S, N)):
+            raise ValueError('%s: out must be a contiguous float64 (%d,S,N) tensor on the same device' % (who, planes))
+        torch.cuda.current_stream(self.device).synchronize()      # the engine's streams are not ordered after torch's
+        return out
+
+    def _kron_device_rows(self, who, X_t, dims):
+        if not (self._device_f64(X_t) and X_t.dim() == 2 and int(X_t.shape[1]) == dims[0] + dims[1]):
+            raise ValueError('%s: Xnew needs a contiguous float64 (N, %d) tensor on cuda:%d' % (who, dims[0] + dims[1], self.device))
+        return int(X_t.shape[0])
+
+    def kron_sample_paths(self, p, Xnew, n_samples=16, n_features=1024, rng=None, draws=None, jitter=1e-6, g_offset=0.0, f_mu=None):
+        """Joint posterior sample paths of the Kronecker OnOff model at Xnew (N, D0 + D1) by pathwise conditioning
+        (zigp_kron_sample_paths): returns dict(f, g, gf: (S, N) each; draws).  p as kron_predict reads it; rng, draws as sample_paths
+        (a draw has omega0 (R, D0 + D1) and eps (M0 M1, S)).  D0 + D1 <= 8, grids of at most 128 x 128, 1 <= n_samples <= 256."""
+        s, keep, dims = self._pack_kron(p)
+        Xnew = self._kron_rows(Xnew, dims, 'Xnew')
+        draws, recs, keepd = self._kron_path_draws(s, dims, ('f', 'g'), n_samples, n_features, rng, draws)
+        S, N = int(n_samples), Xnew.shape[0]
+        out = np.zeros((3, S, N))
+        _check(self.lib, self.ctx, self.lib.zigp_kron_sample_paths(self.ctx, C.byref(s), ptr(Xnew), N, float(jitter), float(g_offset),
+                                                                    0.0 if f_mu is None else _scalar(f_mu), C.addressof(recs['f']),
+                                                                    C.addressof(recs['g']), S, ptr(out)))
+        return dict(f=out[0], g=out[1], gf=out[2], draws=draws)
+
+    def kron_sample_paths_device(self, p, X_t, n_samples=16, n_features=1024, rng=None, draws=None, jitter=1e-6, g_offset=0.0, f_mu=None,
+                                 out=None):
+        """kron_sample_paths on a torch CUDA float64 tensor (N, D0 + D1) of the engine's device: f, g, gf are views of one (3, S, N)
+        CUDA tensor (`out` when given)."""
+        s, keep, dims = self._pack_kron(p)
+        N = self._kron_device_rows('kron_sample_paths_device', X_t, dims)
+        draws, recs, keepd = self._kron_path_draws(s, dims, ('f', 'g'), n_samples, n_features, rng, draws)
+        S = int(n_samples)
+        out = self._kron_paths_out('kron_sample_paths_device', X_t, 3, S, out)
+        if N:
+            _check(self.lib, self.ctx, self.lib.zigp_kron_sample_paths_device(self.ctx, C.byref(s), C.c_void_p(X_t.data_ptr()), N, float(jitter),
+                                                                               float(g_offset), 0.0 if f_mu is None else _scalar(f_mu),
+                                                                               C.addressof(recs['f']), C.addressof(recs['g']), S,
+                                                                               C.c_void_p(out.data_ptr())))
+        return dict(f=out[0], g=out[1], gf=out[2], draws=draws)
+
+    def _head_lik(self, who, lik):
+        if lik not in self.LIK:
+            raise ValueError("%s: lik must be 'gaussian' or 'bernoulli', not %r (the on/off paths are kron_sample_paths)" % (who, lik))
+        return self.LIK[lik]
+
+    def kron_head_sample_paths(self, p, Xnew, lik, n_samples=16, n_features=1024, rng=None, draws=None, jitter=1e-6, f_mu=0.0):
+        """Sample paths of a single-latent head (zigp_kron_head_sample_paths): dict(f (S, N), draws) for 'gaussian', dict(f, p, draws)
+        for 'bernoulli' (p = the probit link of f with the reference's 1e-3 clamp).  p holds the f fields only; f already carries f_mu."""
+        code = self._head_lik('kron_head_sample_paths', lik)
+        s, keep, dims = self._pack_kron(p, tags=('f',))
+        Xnew = self._kron_rows(Xnew, dims, 'Xnew')
+        draws, recs, keepd = self._kron_path_draws(s, dims, ('f',), n_samples, n_features, rng, draws)
+        S, N, planes = int(n_samples), Xnew.shape[0], 2 if lik == 'bernoulli' else 1
+        out = np.zeros((planes, S, N))
+        _check(self.lib, self.ctx, self.lib.zigp_kron_head_sample_paths(self.ctx, C.byref(s), code, ptr(Xnew), N, float(jitter), _scalar(f_mu),
+                                                                         C.addressof(recs['f']), S, ptr(out)))
+        res = dict(f=out[0], draws=draws)
+        if planes == 2:
+            res['p'] = out[1]
+        return res
+
+    def kron_head_sample_paths_device(self, p, X_t, lik, n_samples=16, n_features=1024, rng=None, draws=None, jitter=1e-6, f_mu=0.0, out=None):
+        """kron_head_sample_paths on a torch CUDA float64 tensor of the engine's device: views of one (1 or 2, S, N) CUDA tensor."""
+        code = self._head_lik('kron_head_sample_paths_device', lik)
+        s, keep, dims = self._pack_kron(p, tags=('f',))
+        N = self._kron_device_rows('kron_head_sample_paths_device', X_t, dims)
+        draws, recs, keepd = self._kron_path_draws(s, dims, ('f',), n_samples, n_features, rng, draws)
+        S, planes = int(n_samples), 2 if lik == 'bernoulli' else 1
+        out = self._kron_paths_out('kron_head_sample_paths_device', X_t, planes, S, out)
+        if N:
+            _check(self.lib, self.ctx, self.lib.zigp_kron_head_sample_paths_device(self.ctx, C.byref(s), code, C.c_void_p(X_t.data_ptr()), N,
+                                                                                    float(jitter), _scalar(f_mu), C.addressof(recs['f']), S,
+                                                                                    C.c_void_p(out.data_ptr())))
+        res = dict(f=out[0], draws=draws)
+        if planes == 2:
+            res['p'] = out[1]
+        return res
+
     # ---- inducing inputs by k-means on the device (include/zigp.h "inducing inputs"; zigp.inducing) ----
     @staticmethod
     def _kmeans_args(N, ld, M, init, seed, max_iter, cols, rows_of):

@@ -95,3 +95,42 @@ def weights_np(Kuu, u_m, q_sqrt, eps, fZ, whiten=False, q_diag=True):
     else:
         t = u_m + np.tril(as_f64(q_sqrt).reshape(M, M)) @ eps - solve_triangular(L, fZ, lower=True)
     return solve_triangular(L.T, t, lower=False)
+
+
+# ---- the Kronecker (space x time) model and its heads (include/zigp_kronpaths.h) ----
+# draw() serves them with D = D0 + D1 and M = M0 M1: omega0 holds the frequencies of all the columns, eps the normals of the grid
+# (factor-0-major, as u_fm).  prior_np serves them with ell = [ell0 | ell1] and var = var0 var1.
+
+def check_kron_sizes(D0, D1, M0, M1, S):
+    """The sizes every Kronecker path call refuses, before the library is touched"""
+    if D0 < 1 or D1 < 1 or D0 + D1 > _lib.PATH_MAX_D:
+        raise ValueError('D0 = %d, D1 = %d: the Kronecker sample paths cover D0, D1 >= 1 with D0 + D1 <= %d' % (D0, D1, _lib.PATH_MAX_D))
+    if not (1 <= M0 <= _lib.KRON_PATH_MAX_M and 1 <= M1 <= _lib.KRON_PATH_MAX_M):
+        raise ValueError('M0 = %d, M1 = %d: the Kronecker sample paths cover 1 .. %d inducing points per factor' % (M0, M1, _lib.KRON_PATH_MAX_M))
+    if not 1 <= S <= _lib.PATH_MAX_S:
+        raise ValueError('S = %d: a call draws 1 .. %d sample paths (ZIGP_PATH_MAX_S)' % (S, _lib.PATH_MAX_S))
+
+
+def kron_weights_np(K0, K1, u_m, q_sqrt, eps, fZ):
+    """V (M0 M1, S), factor-0-major, with  (k0(x, Z0) (x) k1(x, Z1)) V = k(x, Z) (K0 (x) K1)^-1 (u - f_Z),  u = u_m + s o eps the draw of
+    q(u) behind eps:  V_s = K0^-1 (U + S o E_s - F_Z,s) K1^-1 as M0 x M1 matrices, by the Cholesky factor of each K_p (jitter included
+    by the caller) and triangular solves -- nothing of size M0 M1 x M0 M1 is formed.  fZ (M0 M1, S) = f_prior at the grid points."""
+    from scipy.linalg import solve_triangular
+    K0, K1, eps, fZ = as_f64(K0), as_f64(K1), as_f64(eps), as_f64(fZ)
+    M0, M1 = K0.shape[0], K1.shape[0]
+    M, S = M0 * M1, eps.shape[1]
+    if eps.shape != (M, S) or fZ.shape != (M, S):
+        raise ValueError('eps and fZ must be (M0 M1, S) = (%d, %d)' % (M, S))
+    rhs = as_f64(u_m).reshape(M, 1) + as_f64(q_sqrt).reshape(M, 1) * eps - fZ
+    L0, L1 = np.linalg.cholesky(K0), np.linalg.cholesky(K1)
+    R = rhs.reshape(M0, M1 * S)                                                     # K0^-1 from the left, every (j, s) column at once
+    R = solve_triangular(L0.T, solve_triangular(L0, R, lower=True), lower=False).reshape(M0, M1, S)
+    R = np.ascontiguousarray(R.transpose(1, 0, 2)).reshape(M1, M0 * S)              # K1^-1 from the right = from the left of the transpose
+    R = solve_triangular(L1.T, solve_triangular(L1, R, lower=True), lower=False).reshape(M1, M0, S)
+    return np.ascontiguousarray(R.transpose(1, 0, 2)).reshape(M, S)
+
+
+def kron_grid(Z0, Z1):
+    """The M0 M1 grid points (i, j) as rows [z0_i | z1_j], factor-0-major: (M0 M1, D0 + D1)"""
+    Z0, Z1 = as_f64(Z0), as_f64(Z1)
+    return np.hstack([np.repeat(Z0, Z1.shape[0], axis=0), np.tile(Z1, (Z0.shape[0], 1))])
