@@ -554,6 +554,10 @@ int zigp_sample_paths_device(zigp_ctx* ctx, const zigp_params* p, const double* 
  * Their record and entry points are declared in zigp_kronpaths.h, which is part of this boundary. */
 #include "zigp_kronpaths.h"
 
+/* ---- sample-path scores: group totals, energy and variogram scores of an ensemble (new).  Their options record
+ * and entry points are declared in zigp_ensemble.h, which is part of this boundary. */
+#include "zigp_ensemble.h"
+
 /* ---- inducing inputs by k-means on the device: Lloyd iterations (new entry points) ----
  * Replaces the host-side scipy.cluster.vq.kmeans call that picks the inducing inputs before the first ELBO step (scripts/onoff.py:67,
  * scripts/svgp.py:64; the same call in onofftf/model.py init_params and onofftf/heads.py init_head_params) by its Lloyd iterations from a

@@ -6,5 +6,6 @@
 #include "zigp_score.hip"
 #include "zigp_paths.hip"
 #include "zigp_kronpaths.hip"
+#include "zigp_ensemble.hip"
 #include "zigp_kmeans.hip"
 #include "zigp_comm.hip"

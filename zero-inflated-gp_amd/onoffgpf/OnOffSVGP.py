@@ -239,6 +239,24 @@ class OnOffSVGP(Parameterized):
                                       rng=np.random.RandomState(seed), jitter=JITTER)
         return tuple(np.ascontiguousarray(r[k])[:, :, None] for k in ('f', 'g', 'gf'))
 
+    def predict_path_scores(self, Xnew, Ynew, groups=None, num_samples=16, member='gf', noise_eps=None, weights=None, energy=True, totals=True,
+                            variogram=None, fair=False, n_features=1024, seed=None):
+        """Scores of joint posterior sample paths at Xnew against Ynew per group of rows (zigp_ensemble_scores_device; DESIGN.md section
+        10f): dict of NumPy arrays -- 'total' (num_samples, G) and 'total_obs' (G), the weighted group sums of every path and of Ynew;
+        'crps_total', the ensemble CRPS of the totals; 'energy', the energy score over the group's rows; 'variogram' (p = 0.5, 1 or 2), the
+        variogram score; 'offsets', 'labels'.  groups: None, G + 1 boundaries or N integer labels (a basin or week index).  The paths are
+        drawn and scored on the device; only the scores come back.  The members are the NOISE-FREE paths `member` ('f', 'g' or 'gf')
+        unless noise_eps, (num_samples, N) standard normals of the caller, is given: then gf + sqrt(noise variance) noise_eps."""
+        import torch
+        eng = self._engine
+        dev = torch.device('cuda', eng.device)
+        up = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)     # noqa: E731
+        r = eng.path_scores_device(self._values(), up(Xnew), up(np.asarray(Ynew, dtype=np.float64).reshape(-1)), groups=groups,
+                                   n_samples=int(num_samples), member=member, noise_eps=up(noise_eps), weights=up(weights), energy=energy,
+                                   totals=totals, variogram=variogram, fair=fair, n_features=int(n_features), rng=np.random.RandomState(seed),
+                                   jitter=JITTER)
+        return {k: v.cpu().numpy() if torch.is_tensor(v) else v for k, v in r.items() if k != 'draws'}
+
     def optimize(self, method='L-BFGS-B', maxiter=1000, disp=False, callback=None, learning_rate=0.01, device_loop=None, **kw):
         """GPflow Model.optimize: scipy L-BFGS-B on the free state (default), or Adam when method='adam'
         (the commented alternative at zero-inflated-gpflow.ipynb:155).  Adam without a callback runs its loop on the device

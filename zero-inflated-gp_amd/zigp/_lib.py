@@ -315,6 +315,22 @@ KRON_PATH_SIGNATURES = {
                                                      C.c_void_p, C.c_int32, C.c_void_p]),
 }
 
+# include/zigp_ensemble.h (the header zigp.h includes for the sample-path scores): bound by load() like SIGNATURES
+ENS_CHUNK = 64                # ZIGP_ENS_CHUNK
+ENS_VARIO_MAX_ROWS = 4096     # ZIGP_ENS_VARIO_MAX_ROWS
+
+
+class zigp_ens_opts(C.Structure):
+    _fields_ = [('fair', C.c_int32), ('vario_p', C.c_double)]
+
+
+_ENS_ARGS = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32,
+             C.POINTER(zigp_ens_opts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+ENSEMBLE_SIGNATURES = {
+    'zigp_ensemble_scores': (C.c_int, _ENS_ARGS),
+    'zigp_ensemble_scores_device': (C.c_int, _ENS_ARGS),
+}
+
 _lib = None
 
 
@@ -334,7 +350,7 @@ def load():
     except Exception:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(KRON_PATH_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(KRON_PATH_SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -986,6 +986,131 @@ class DenseEngine:
             res['p'] = out[1]
         return res
 
+    # ---- sample-path scores: totals, energy and variogram scores of an ensemble (include/zigp_ensemble.h) ----
+    ENS_KEYS = ('total', 'total_obs', 'crps_total', 'energy', 'variogram', 'dist')
+
+    @staticmethod
+    def _ens_outputs(new, S, G, energy, totals, variogram, return_dist):
+        """The six outputs of an ensemble call in the order of ENS_KEYS, None where the call does not ask; new(*shape): an array or tensor"""
+        return [new(S, G) if totals else None, new(G) if totals else None, new(G) if totals else None, new(G) if energy else None,
+                new(G) if variogram is not None else None, new(G, S + 1, S + 1) if return_dist else None]
+
+    def ensemble_scores(self, E, y, groups=None, weights=None, energy=True, totals=True, variogram=None, fair=False, return_dist=False):
+        """Scores of an ensemble E (S members, N rows) against the observation y (N) per group of rows (zigp_ensemble_scores), as a dict:
+        'total' (S, G) and 'total_obs' (G), the weighted group sums; 'crps_total' (G), the ensemble CRPS of the totals; 'energy' (G), the
+        energy score over the group's rows; 'variogram' (G), the variogram score of order p = variogram (0.5, 1 or 2); 'dist'
+        (G, S + 1, S + 1), the matrix of weighted distances between members, member S = y; 'offsets' (G + 1) and 'labels' (the distinct
+        labels in group order, or None).  A key is None where that output was not asked for (totals=False drops the first three).
+        groups: None (one group), G + 1 boundaries from 0 to N, or N integer labels -- labels that are not non-decreasing cost one stable
+        sort of the columns (np.take), and the groups come back in ascending label order.  weights: N row weights >= 0 (cell areas), default
+        1.  fair=True: c = 1 / (S (S - 1)) in place of 1 / S^2.  E may be a row-strided view (rows of stride >= N doubles)."""
+        from . import ensemble as ens
+        E = np.asarray(E, dtype=np.float64)
+        if E.ndim != 2:
+            raise ValueError('E must be (S, N)')
+        S, N = E.shape
+        y = as_f64(y).reshape(-1)
+        if y.size != N:
+            raise ValueError('y must have N = %d entries' % N)
+        w = None if weights is None else as_f64(weights).reshape(-1)
+        if w is not None and w.size != N:
+            raise ValueError('weights must have N = %d entries' % N)
+        off, order, labels = ens.plan_groups(groups, N)
+        opts = ens.check_args(S, N, off, w, variogram, fair)
+        if order is not None:
+            E, y, w = np.take(E, order, axis=1), np.take(y, order), None if w is None else np.take(w, order)
+        if S == 1 or not (E.strides[1] == 8 and E.strides[0] % 8 == 0 and E.strides[0] >= 8 * N):
+            E = np.ascontiguousarray(E)
+        ld = N if S == 1 else E.strides[0] // 8
+        G = off.size - 1
+        outs = self._ens_outputs(lambda *shape: np.zeros(shape), S, G, energy, totals, variogram, return_dist)
+        if any(o is not None for o in outs):
+            _check(self.lib, self.ctx, self.lib.zigp_ensemble_scores(self.ctx, E.ctypes.data, ld, S, N, ptr(y), self._opt(w),
+                                                                      off.ctypes.data_as(C.POINTER(C.c_int64)), G, C.byref(opts),
+                                                                      *[self._opt(o) for o in outs]))
+        return dict(zip(self.ENS_KEYS, outs), offsets=off, labels=labels)
+
+    def ensemble_scores_device(self, E_t, y_t, groups=None, weights=None, energy=True, totals=True, variogram=None, fair=False,
+                               return_dist=False):
+        """ensemble_scores on torch CUDA float64 tensors of the engine's device: E_t (S, N) with unit column stride and a row stride of
+        at least N -- a plane of a (3, S, N) paths block, or a row-strided view of one, is read where it is; y_t (N) or (N, 1); weights a
+        tensor of N entries (or None; not checked for sign).  The dict's outputs are CUDA tensors: nothing but the boundaries crosses PCIe.
+        Unsorted labels cost one index_select of the columns."""
+        import torch
+        from . import ensemble as ens
+        ok = lambda t: t.is_cuda and t.device.index == self.device and t.dtype == torch.float64     # noqa: E731
+        if not (ok(E_t) and E_t.dim() == 2 and (E_t.shape[1] == 0 or E_t.stride(1) == 1) and (E_t.shape[0] == 1 or E_t.stride(0) >= E_t.shape[1])):
+            raise ValueError('ensemble_scores_device: E needs a float64 (S, N) tensor on cuda:%d with unit column stride and a row stride >= N'
+                             % self.device)
+        S, N = int(E_t.shape[0]), int(E_t.shape[1])
+        if not (ok(y_t) and y_t.numel() == N and y_t.is_contiguous()):
+            raise ValueError('ensemble_scores_device: y needs a contiguous float64 tensor of N entries on cuda:%d' % self.device)
+        if weights is not None and not (ok(weights) and weights.numel() == N and weights.is_contiguous()):
+            raise ValueError('ensemble_scores_device: weights needs a contiguous float64 tensor of N entries on cuda:%d' % self.device)
+        off, order, labels = ens.plan_groups(groups, N)
+        opts = ens.check_args(S, N, off, None, variogram, fair)
+        y_t = y_t.reshape(-1)
+        w_t = None if weights is None else weights.reshape(-1)
+        if order is not None:
+            idx = torch.as_tensor(order, device=E_t.device)
+            E_t, y_t = E_t.index_select(1, idx), y_t.index_select(0, idx)
+            w_t = None if w_t is None else w_t.index_select(0, idx)
+        ld = N if S == 1 else int(E_t.stride(0))
+        G = off.size - 1
+        outs = self._ens_outputs(lambda *shape: torch.zeros(shape, dtype=torch.float64, device=E_t.device), S, G, energy, totals, variogram,
+                                 return_dist)
+        D = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
+        torch.cuda.current_stream(self.device).synchronize()      # the engine's streams are not ordered after torch's
+        if any(o is not None for o in outs):
+            _check(self.lib, self.ctx, self.lib.zigp_ensemble_scores_device(self.ctx, D(E_t), ld, S, N, D(y_t), D(w_t),
+                                                                             off.ctypes.data_as(C.POINTER(C.c_int64)), G, C.byref(opts),
+                                                                             *[D(o) for o in outs]))
+        return dict(zip(self.ENS_KEYS, outs), offsets=off, labels=labels)
+
+    def _score_paths(self, who, paths, noise, Y_t, member, noise_eps, score_args):
+        """ensemble_scores_device of one plane of a paths dict against Y_t; with noise_eps (S, N) the members get observation noise"""
+        from . import ensemble as ens
+        E_t = paths[ens.member_plane(member)]
+        if noise_eps is not None:
+            if not (self._device_f64(noise_eps) and tuple(noise_eps.shape) == tuple(E_t.shape)):
+                raise ValueError('%s: noise_eps needs a contiguous float64 (S, N) tensor of standard normals on cuda:%d' % (who, self.device))
+            E_t = E_t + float(np.sqrt(noise)) * noise_eps
+        res = self.ensemble_scores_device(E_t, Y_t, **score_args)
+        res['draws'] = paths['draws']
+        return res
+
+    def path_scores_device(self, p, X_t, Y_t, groups=None, n_samples=16, member='gf', noise_eps=None, weights=None, energy=True, totals=True,
+                           variogram=None, fair=False, return_dist=False, n_features=1024, rng=None, draws=None, jitter=1e-6, g_offset=0.0):
+        """Scores of the dense OnOff model's joint sample paths at X_t (N, D) against Y_t (N): sample_paths_device, then
+        ensemble_scores_device of the plane `member` ('f', 'g' or 'gf') where it lies -- only parameters, draws and scores cross PCIe.
+        Without noise_eps the members are the NOISE-FREE paths (the latent product gf, not draws of y); with noise_eps, a CUDA (S, N)
+        tensor of standard normals the caller drew, they are gf + sqrt(noise) noise_eps.  Returns ensemble_scores_device's dict plus
+        'draws' (hand them back to score the same paths again)."""
+        from . import ensemble as ens
+        ens.member_plane(member)
+        pk = _Packed(p)
+        N = self._device_xy('path_scores_device', pk, X_t, Y_t)
+        ens.check_args(int(n_samples), max(N, 1), ens.plan_groups(groups, N)[0], None, variogram, fair)
+        paths = self.sample_paths_device(p, X_t, n_samples=n_samples, n_features=n_features, rng=rng, draws=draws, jitter=jitter, g_offset=g_offset)
+        return self._score_paths('path_scores_device', paths, float(np.squeeze(p['noise'])), Y_t, member, noise_eps,
+                                 dict(groups=groups, weights=weights, energy=energy, totals=totals, variogram=variogram, fair=fair,
+                                      return_dist=return_dist))
+
+    def kron_path_scores_device(self, p, X_t, Y_t, groups=None, n_samples=16, member='gf', noise_eps=None, weights=None, energy=True,
+                                totals=True, variogram=None, fair=False, return_dist=False, n_features=1024, rng=None, draws=None, jitter=1e-6,
+                                g_offset=0.0, f_mu=None):
+        """path_scores_device for the Kronecker OnOff model: kron_sample_paths_device, then ensemble_scores_device of the plane `member`.
+        The members are noise-free unless noise_eps is given (p['noise'] is then the observation variance)."""
+        from . import ensemble as ens
+        ens.member_plane(member)
+        N = int(X_t.shape[0])
+        ens.check_args(int(n_samples), max(N, 1), ens.plan_groups(groups, N)[0], None, variogram, fair)
+        paths = self.kron_sample_paths_device(p, X_t, n_samples=n_samples, n_features=n_features, rng=rng, draws=draws, jitter=jitter,
+                                              g_offset=g_offset, f_mu=f_mu)
+        return self._score_paths('kron_path_scores_device', paths, float(np.squeeze(p['noise'])) if noise_eps is not None else 0.0, Y_t, member,
+                                 noise_eps, dict(groups=groups, weights=weights, energy=energy, totals=totals, variogram=variogram, fair=fair,
+                                                 return_dist=return_dist))
+
     # ---- inducing inputs by k-means on the device (include/zigp.h "inducing inputs"; zigp.inducing) ----
     @staticmethod
     def _kmeans_args(N, ld, M, init, seed, max_iter, cols, rows_of):
