@@ -334,12 +334,27 @@ int zigp_get_q_full(zigp_ctx* ctx);
  * ZIGP_EARG: a NULL context, a latent outside {0, 1}, an unknown kind.  While a latent is Matern these return ZIGP_EARG with nothing
  * enqueued (the message names the kernel): the entry points above at D > 8 (the wide kernels are RBF only), and zigp_fit_steps /
  * zigp_fit_steps_mode at every D (the device loops fit RBF latents; zigp_elbo + a host optimiser fits the others).  The Kronecker entry
- * points ignore the setting.  zigp_get_kernel returns the kind, or ZIGP_EARG for a NULL context or a latent outside {0, 1}. */
+ * points ignore the setting (theirs is zigp_set_kron_kernel, below).  zigp_get_kernel returns the kind, or ZIGP_EARG for a NULL context or a latent outside {0, 1}. */
 #define ZIGP_KERN_RBF 0
 #define ZIGP_KERN_MATERN32 1
 #define ZIGP_KERN_MATERN52 2
 int zigp_set_kernel(zigp_ctx* ctx, int32_t latent /* 0 f, 1 g */, int32_t kind);
 int zigp_get_kernel(zigp_ctx* ctx, int32_t latent);
+/* Kernel family of the KRONECKER path and its heads, per latent AND per factor: four independent settings (latent f / g x factor 0 / 1),
+ * all ZIGP_KERN_RBF after zigp_create, separate from zigp_set_kernel (which keeps meaning the dense latents only).  Per factor q, with
+ * r2 formed by fused multiply-adds from 0 in ascending d of (z_d / ell_d - x_d / ell_d) as the RBF factor panel forms it, k_q is the
+ * formula block above: r = sqrt(r2 + 1e-12); the diagonal of K_q(Z, Z) is the formula at r = 1e-6, plus jitter; Knn = var0 var1 for every
+ * kind.  zigp_kron_elbo[_rows] (value and gradient, include_kl 0 / 1, f_mu, g_offset, an empty row set, a communicator),
+ * zigp_kron_predict, zigp_kron_head_elbo[_rows] and zigp_kron_head_predict (the heads read the f kinds), and the sample paths of
+ * zigp_kronpaths.h follow the setting.  A call with any Matern factor runs on the GEMM-panel path whatever its grid (the fused
+ * register-resident kernels are RBF only; zigp_set_kron_panels is not needed); with all four factors RBF every call launches what it
+ * launched before this setting existed.  A gradient step keeps one more panel of 8 * M_q * rows bytes per Matern factor (K').
+ * ZIGP_EARG, naming the argument: a NULL context, a latent or factor outside {0, 1}, an unknown kind.  While a factor of a latent they fit
+ * is Matern, zigp_kron_fit_steps and zigp_kron_head_fit_steps return ZIGP_EARG with nothing enqueued and the context usable; the message
+ * names the kernel, the factor and the latent ("... Matern52 kernel on factor 1 of latent f ...").  Factor dimensions stay D0, D1 <= 8.
+ * zigp_get_kron_kernel returns the kind, or ZIGP_EARG. */
+int zigp_set_kron_kernel(zigp_ctx* ctx, int32_t latent /* 0 f, 1 g */, int32_t factor /* 0, 1 */, int32_t kind /* ZIGP_KERN_* */);
+int zigp_get_kron_kernel(zigp_ctx* ctx, int32_t latent, int32_t factor);
 /* Kernel matrices of any of the three kinds (gpflow kernels.Stationary.K -> RBF.K / Matern32.K / Matern52.K; zigp_rbf_K is the RBF
  * one and stays as it is): K (n1,n2) = k(X1, X2) as above, no jitter.  X2 == NULL -> X1 (the diagonal is then the formula at r = 1e-6
  * for the Matern kinds).  Argument conventions of zigp_rbf_K; 1 <= D <= ZIGP_MAX_D for ZIGP_KERN_RBF, D <= 8 for the Matern kinds. */

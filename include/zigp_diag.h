@@ -305,6 +305,17 @@ int zigp_test_kron_da(zigp_ctx* ctx, int32_t M, int64_t Nc, const double* A, con
 int zigp_test_kron_kgrad(zigp_ctx* ctx, int32_t M, int32_t D, int64_t N, int64_t Nc, int32_t ldx, int32_t col0, const double* B, const double* A,
                          const double* PdA, const double* K, const double* gm, const double* dq, const double* X, const double* Z, double* krow);
 
+/* The factor panel of any ZIGP_KERN_* kind, through the launch latent_forward_panels makes for that kind: K and (Kd != NULL: a gradient step)
+ * the derivative panel K' = -dk / d(r2 / 2), both (Mq, Nc) as zigp_test_kron_kbuild returns K.  ZIGP_KERN_RBF runs k_kron_kbuild (K' = K);
+ * a Matern kind k_kron_kbuild_matern<KIND, Kd != NULL>. */
+int zigp_test_kron_kbuild_kind(zigp_ctx* ctx, int32_t kind, int64_t N, int64_t Nc, int32_t ldx, int32_t col0, int32_t M, int32_t D, const double* X,
+                               const double* Z, const double* ell, double var, double* K, double* Kd);
+/* The factor cotangent of any kind: zigp_test_kron_kgrad's arguments plus Kd (M, Nc).  ZIGP_KERN_RBF runs k_kron_kgrad (Kd is not read); a Matern
+ * kind k_kron_kgrad_matern: column 0 takes dK K, the 2 D moment columns dK K'. */
+int zigp_test_kron_kgrad_kind(zigp_ctx* ctx, int32_t kind, int32_t M, int32_t D, int64_t N, int64_t Nc, int32_t ldx, int32_t col0, const double* B,
+                              const double* A, const double* PdA, const double* K, const double* Kd, const double* gm, const double* dq,
+                              const double* X, const double* Z, double* krow);
+
 /* ---- Fused Kronecker path (csrc/zigp_kronf.hip, zigp_kronl.h): ONE ordinary value-and-gradient step through the host code of
  * zigp_kron_elbo / zigp_kron_head_elbo itself -- same plan, launches, grids and device buffers, zigp_set_kron_range_tiles honoured -- with
  * device buffers snapshot around it.  Every tap is optional (NULL: not taken); a tap is a stream-ordered device-to-device copy enqueued

@@ -13,10 +13,16 @@
  * k0 k1 is rounded once; V is factor-0-major, as u_fm is.  One summation order per element (groups of four grid points with one i, ascending
  * j inside ascending i, M1 padded to a multiple of 4 by zero weights; then the cosines in ascending r; shift last): an element's bits do not
  * depend on N, on the row's position, on S, on the sample's column, on the other latent or on the call.
+ * Each factor has its own kernel family: the record's fourth word (it keeps its name, `reserved`) holds the kinds = kind0 + 4 * kind1 of two
+ * ZIGP_KERN_* values (0, what every caller has passed so far, is RBF x RBF as above).  A Matern factor evaluates k_q with the element function of its own factor panel (zigp_set_kron_kernel): the same
+ * r2 -- fused multiply-adds from 0 in ascending d of (z_d / ell_d - x_d / ell_d) -- then r = sqrt(r2 + 1e-12) and
+ *   ZIGP_KERN_MATERN32  k_q = var_q (1 + sqrt3 r) exp(-sqrt3 r),     ZIGP_KERN_MATERN52  k_q = var_q (1 + sqrt5 r + (5/3) r^2) exp(-sqrt5 r).
+ * The product of a Matern factor with any other is not a stationary kernel of one distance, but its spectral density is the product of
+ * the factors' densities: the frequencies of factor q's columns follow that factor's law (zigp.pathwise.kron_draw).
  * ZIGP_EARG with a message that names the argument, nothing enqueued and the context usable afterwards: D0 or D1 < 1, D0 + D1 > 8, M0 or M1
- * outside [1, 128], S outside [1, ZIGP_PATH_MAX_S], R < 0, a NULL table, a non-finite table entry, a host pointer handed to a _device call. */
+ * outside [1, 128], kinds outside the nine valid values, S outside [1, ZIGP_PATH_MAX_S], R < 0, a NULL table, a non-finite table entry, a host pointer handed to a _device call. */
 typedef struct {
-  int32_t M0, M1, R, reserved;       /* inducing points of factor 0 and 1, random features */
+  int32_t M0, M1, R, reserved;       /* inducing points of factor 0 and 1, random features; reserved carries the KINDS: kind0 + 4 * kind1 (0: RBF x RBF) */
   const double* Z0;                  /* (M0,D0) */
   const double* Z1;                  /* (M1,D1) */
   const double* ell0;                /* (D0) */
@@ -40,7 +46,8 @@ int zigp_kron_path_rows_device(zigp_ctx* ctx, const zigp_kron_path_latent* lat, 
  * rhs_s = U + S o E_s - F_Z,s as M0 x M1 matrices; V_s = K0^-1 rhs_s K1^-1, formed as W0^T (W0 rhs_s W1^T) W1 with the W_p = L_p^-1 of the
  * call's own factor forward stage (K_p + jitter I = L_p L_p^T, the one zigp_kron_predict runs); then the sum at Xnew with f_mu as the shift of f and g_offset as the shift of g, as rows fmean and gmean
  * of zigp_kron_predict carry them.  out3 is (3,S,N): f, g, and gf = Phi~(g) f with the link of the predictive density.
- * zigp_kron_predict's errors (ZIGP_ENOTPD names the factors) and the refusals above. */
+ * The factor kinds are the context's (zigp_set_kron_kernel; the heads follow the f kinds): the factor forward stage and the sum evaluate
+ * the same k_q.  zigp_kron_predict's errors (ZIGP_ENOTPD names the factors) and the refusals above. */
 int zigp_kron_sample_paths(zigp_ctx* ctx, const zigp_kron_params* p, const double* Xnew, int64_t N, double jitter, double g_offset, double f_mu,
                            const zigp_path_draw* draw_f, const zigp_path_draw* draw_g, int32_t S, double* out3);
 /* The same with Xnew and out3 in DEVICE memory of the context's GPU; the draws stay host pointers; complete on return. */

@@ -21,9 +21,11 @@ namespace zigp {
 
 struct KronFactor {
   int M = 0, Mq = 0, D = 0, col0 = 0;
+  int kind = ZIGP_KERN_RBF;                 // zigp_set_kron_kernel: the factor's kernel family
   double var = 1.0;
   std::vector<double> ell;
   DevBuf Z, K, L, W, P, T, dP, G, krow;
+  DevBuf Kd;                                // panel [Mq][Nc] of a Matern factor's gradient step: K' = -dk / d(r2 / 2) (k_kron_kbuild_matern)
   DevBuf Kp, Ap, Asq, dA, E, PdA, Bx, Cx;   // panels [Mq][Nc]: K_p, A_p, A_p^2, dA_p, E_p, P_p dA_p, (Alpha K_other), (S2 A_other^2)
 };
 
@@ -252,6 +254,120 @@ k_kron_kgrad(const double* __restrict__ B, const double* __restrict__ A, const d
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Matern 3/2 and 5/2 FACTORS (zigp_set_kron_kernel): each of the four factors (latent f / g x factor 0 / 1) has its own kind.  These
+// kernels stand beside the RBF ones above, which keep their arguments and their machine code; a call whose factors are all RBF
+// launches none of them.  Formulas, the floored distance and K' = -dk / d(r2 / 2): the Matern block of zigp_kernels.h.
+// ------------------------------------------------------------------------------------------------------------------
+// One element from its r2, in the plain library arithmetic of matern_k / matern_kd (same expressions; sqrt and exp are shared between
+// K and K').  r2 is clamped to 2^996 so that a far pair gives t finite, exp(-t) = +0 and K = K' = finite * 0 = +0, never inf * 0.
+// The dense panel's kuf_sqrt + table exponential (kuf_matern) is NOT used: its operand is the sum w = -(16 / ln 2) r2 of inputs
+// pre-scaled by KUF_C / ell on the host (Zs, hyp_scale), and its table carries var; this panel forms r2 from z / ell - x / ell as
+// k_kron_kbuild does, which is also the definition the path kernel (zigp_kronpaths.hip) shares.  The panel path is bound by its
+// GEMMs, not by this kernel.
+template <int KIND, bool GRAD>
+__device__ __forceinline__ void kron_matern_elem(double var, double r2, double& k, double& kd) {
+  static_assert(KIND == KERN_M32 || KIND == KERN_M52, "Matern 3/2 or 5/2");
+  const double r = sqrt(fmin(r2, 0x1p+996) + MATERN_FLOOR);
+  if (KIND == KERN_M32) {
+    const double t = MATERN_SQRT3 * r, e = exp(-t);
+    k = var * (1.0 + t) * e;
+    if (GRAD) kd = 3.0 * var * e;
+  } else {
+    const double t = MATERN_SQRT5 * r, e = exp(-t);
+    k = var * (1.0 + t + (5.0 / 3.0) * (r * r)) * e;
+    if (GRAD) kd = (5.0 / 3.0) * var * (1.0 + t) * e;
+  }
+}
+
+// k_kron_kbuild for a Matern factor: same grid and thread mapping (256 columns x 16 rows a block), rows m >= M zero, columns n >= N the
+// kernel at x = 0; GRAD (a gradient step) also writes the derivative panel K' in the same launch.
+template <int KIND, bool GRAD>
+__global__ void __launch_bounds__(256)
+k_kron_kbuild_matern(const double* __restrict__ X, int64_t N, int ldx, int col0, const double* __restrict__ Z, int M, KernHyp h,
+                     double* __restrict__ K, double* __restrict__ Kd, int64_t Nc) {
+  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int m0 = blockIdx.y * 16;
+  double xs[MAXD];
+  const bool valid = n < N;
+#pragma unroll
+  for (int d = 0; d < MAXD; ++d) xs[d] = (d < h.D && valid) ? X[n * ldx + col0 + d] * h.inv_ell[d] : 0.0;
+#pragma unroll 4
+  for (int mm = 0; mm < 16; ++mm) {
+    const int m = m0 + mm;
+    double v = 0.0, vd = 0.0;
+    if (m < M) {
+      double r2 = 0.0;
+#pragma unroll
+      for (int d = 0; d < MAXD; ++d)
+        if (d < h.D) { double t = Z[m * h.D + d] * h.inv_ell[d] - xs[d]; r2 = fma(t, t, r2); }
+      kron_matern_elem<KIND, GRAD>(h.var, r2, v, vd);
+    }
+    K[(int64_t)m * Nc + n] = v;
+    if (GRAD) Kd[(int64_t)m * Nc + n] = vd;
+  }
+}
+
+// k_kron_kgrad for a Matern factor: the same block-per-row mapping and fixed-order reduction; column 0 takes dK K, the 2 D moment
+// columns dK K' with K' read from the derivative panel of the build launch.
+__global__ void __launch_bounds__(256)
+k_kron_kgrad_matern(const double* __restrict__ B, const double* __restrict__ A, const double* __restrict__ PdA, const double* __restrict__ K,
+                    const double* __restrict__ Kd, const double* __restrict__ gm, const double* __restrict__ dq, const double* __restrict__ X,
+                    int64_t N, int ldx, int col0, const double* __restrict__ Z, int M, int D, int64_t Nc, double* __restrict__ krow) {
+  __shared__ double sh[4];
+  const int m = blockIdx.x;
+  if (m >= M) return;
+  double zz[MAXD];
+#pragma unroll
+  for (int d = 0; d < MAXD; ++d) zz[d] = (d < D) ? Z[m * D + d] : 0.0;
+  double s0 = 0.0, s1[MAXD], s2[MAXD];
+#pragma unroll
+  for (int d = 0; d < MAXD; ++d) { s1[d] = 0.0; s2[d] = 0.0; }
+  const int64_t r = (int64_t)m * Nc;
+  for (int64_t n = threadIdx.x; n < N; n += 256) {
+    const double dk = fma(gm[n], B[r + n], fma(2.0 * dq[n], A[r + n], PdA[r + n]));
+    const double t = dk * Kd[r + n];
+    s0 = fma(dk, K[r + n], s0);
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d)
+      if (d < D) {
+        const double df = X[n * ldx + col0 + d] - zz[d];
+        const double td = t * df;
+        s1[d] += td;
+        s2[d] = fma(td, df, s2[d]);
+      }
+  }
+  const int W = 2 + 2 * D;
+  s0 = block_sum<4>(s0, sh);
+  if (threadIdx.x == 0) krow[(int64_t)m * W] += s0;
+  for (int d = 0; d < D; ++d) {
+    double a = block_sum<4>(s1[d], sh);
+    double b = block_sum<4>(s2[d], sh);
+    if (threadIdx.x == 0) { krow[(int64_t)m * W + 1 + d] += a; krow[(int64_t)m * W + 1 + D + d] += b; }
+  }
+}
+
+// K_p (Mq, Mq) of a Matern factor: the padded, jittered sibling of k_rbf_matrix with X1 = X2 = Z -- identity in the padding, the
+// formula at r = 1e-6 (r2 = 0 through the floored distance) plus jitter on the diagonal.
+__global__ void k_kron_matern_matrix(const double* __restrict__ Z, int64_t M, KernHyp h, int kind, double jitter, double* __restrict__ out,
+                                     int64_t Mq) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= Mq * Mq) return;
+  const int64_t i = idx / Mq, j = idx - i * Mq;
+  double v;
+  if (i < M && j < M) {
+    double r2 = 0.0;
+    for (int d = 0; d < h.D; ++d) {
+      const double t = (Z[i * h.D + d] - Z[j * h.D + d]) * h.inv_ell[d];
+      r2 = fma(t, t, r2);
+    }
+    v = matern_k(kind, h.var, r2) + ((i == j) ? jitter : 0.0);
+  } else {
+    v = (i == j) ? 1.0 : 0.0;
+  }
+  out[idx] = v;
+}
+
 // out[idx] = sum_s planes[s][idx]
 __global__ void k_sum_planes(const double* __restrict__ planes, int S, int64_t n, double* __restrict__ out) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -372,16 +488,22 @@ int validate_kron(zigp_ctx* c, const zigp_kron_params* p, int lik = ZIGP_LIK_ONO
 }
 
 // factor MxM forward: K_p (+jitter), L_p, W_p, P_p = W^T W
-int factor_forward(zigp_ctx* c, KronFactor& f, int M, int D, int col0, const double* Z, const double* ell, double var, double jitter) {
-  f.M = M; f.Mq = (int)round_up(M, BM); f.D = D; f.col0 = col0; f.var = var;
+// kind: the factor's ZIGP_KERN_* (a Matern K_p: k_kron_matern_matrix in place of k_rbf_matrix; everything behind K_p is the same)
+int factor_forward(zigp_ctx* c, KronFactor& f, int M, int D, int col0, const double* Z, const double* ell, double var, double jitter,
+                   int kind = ZIGP_KERN_RBF) {
+  f.M = M; f.Mq = (int)round_up(M, BM); f.D = D; f.col0 = col0; f.var = var; f.kind = kind;
   f.ell.assign(ell, ell + D);
   const int Mq = f.Mq, nb = Mq / BM, kb = BM / BK;
   const size_t mm_ = (size_t)Mq * Mq;
   ZIGP_TRY(upload_padded(c, f.Z, Z, (size_t)M * D, (size_t)Mq * D));
   ZIGP_ENSURE(c, f.K, mm_); ZIGP_ENSURE(c, f.L, mm_); ZIGP_ENSURE(c, f.W, mm_); ZIGP_ENSURE(c, f.P, mm_); ZIGP_ENSURE(c, f.T, mm_);
   KernHyp hyp = make_hyp(ell, var, D);
-  hipLaunchKernelGGL(k_rbf_matrix, dim3(ceil_div((int64_t)mm_, 256)), dim3(256), 0, c->stream, f.Z.p, (int64_t)M, f.Z.p, (int64_t)M, hyp, jitter,
-                     f.K.p, (int64_t)Mq, (int64_t)Mq, (int64_t)Mq);
+  if (kind != ZIGP_KERN_RBF)
+    hipLaunchKernelGGL(k_kron_matern_matrix, dim3(ceil_div((int64_t)mm_, 256)), dim3(256), 0, c->stream, f.Z.p, (int64_t)M, hyp, kind, jitter, f.K.p,
+                       (int64_t)Mq);
+  else
+    hipLaunchKernelGGL(k_rbf_matrix, dim3(ceil_div((int64_t)mm_, 256)), dim3(256), 0, c->stream, f.Z.p, (int64_t)M, f.Z.p, (int64_t)M, hyp, jitter,
+                       f.K.p, (int64_t)Mq, (int64_t)Mq, (int64_t)Mq);
   ZIGP_HIP(c, hipGetLastError());
   ZIGP_HIP(c, hipMemcpyAsync(f.L.p, f.K.p, sizeof(double) * mm_, hipMemcpyDeviceToDevice, c->stream));
   ZIGP_TRY(potrf_trtri(c, f.L.p, f.W.p, f.T.p, Mq, true, M, pivot_tol(var, jitter, c->pivot_rtol)));
@@ -406,8 +528,8 @@ int upload_grid(zigp_ctx* c, DevBuf& b, const double* src, int M0, int M1, int M
 }
 
 int latent_setup(zigp_ctx* c, KronLatent& lt, const KronHostLatent& h, int D0, int D1, double jitter) {
-  ZIGP_TRY(factor_forward(c, lt.f[0], h.M[0], D0, 0, h.Z[0], h.ell[0], h.var[0], jitter));
-  ZIGP_TRY(factor_forward(c, lt.f[1], h.M[1], D1, D0, h.Z[1], h.ell[1], h.var[1], jitter));
+  ZIGP_TRY(factor_forward(c, lt.f[0], h.M[0], D0, 0, h.Z[0], h.ell[0], h.var[0], jitter, h.kind[0]));
+  ZIGP_TRY(factor_forward(c, lt.f[1], h.M[1], D1, D0, h.Z[1], h.ell[1], h.var[1], jitter, h.kind[1]));
   const int M0 = h.M[0], M1 = h.M[1], Mq0 = lt.f[0].Mq, Mq1 = lt.f[1].Mq, nb0 = Mq0 / BM, nb1 = Mq1 / BM;
   ZIGP_TRY(upload_grid(c, lt.U, h.u, M0, M1, Mq0, Mq1, false));
   ZIGP_TRY(upload_grid(c, lt.S, h.s, M0, M1, Mq0, Mq1, false));
@@ -424,17 +546,34 @@ int latent_setup(zigp_ctx* c, KronLatent& lt, const KronHostLatent& h, int D0, i
   return 0;
 }
 
-// forward panels + column sums for one latent
-int latent_forward_panels(zigp_ctx* c, KronLatent& lt, const double* dX, int64_t N, int64_t Nc, int ldx) {
+// K_p panel of a Matern factor (and, with_kd, its derivative panel K' for the gradient step) on k_kron_kbuild's grid
+int factor_kbuild_matern(zigp_ctx* c, KronFactor& f, const double* dX, int64_t N, int64_t Nc, int ldx, bool with_kd) {
+  const KernHyp hyp = make_hyp(f.ell.data(), f.var, f.D);
+  const dim3 grid((unsigned)(Nc / 256), f.Mq / 16), block(256);
+  if (with_kd) ZIGP_ENSURE(c, f.Kd, (size_t)f.Mq * Nc);
+#define ZIGP_KRON_KB(KK, GG) \
+  hipLaunchKernelGGL((k_kron_kbuild_matern<KK, GG>), grid, block, 0, c->stream, dX, N, ldx, f.col0, f.Z.p, f.M, hyp, f.Kp.p, GG ? f.Kd.p : nullptr, Nc)
+  if (f.kind == ZIGP_KERN_MATERN32) { if (with_kd) ZIGP_KRON_KB(KERN_M32, true); else ZIGP_KRON_KB(KERN_M32, false); }
+  else { if (with_kd) ZIGP_KRON_KB(KERN_M52, true); else ZIGP_KRON_KB(KERN_M52, false); }
+#undef ZIGP_KRON_KB
+  ZIGP_HIP(c, hipGetLastError());
+  return 0;
+}
+
+// forward panels + column sums for one latent; with_kd: a gradient step (a Matern factor also keeps its derivative panel)
+int latent_forward_panels(zigp_ctx* c, KronLatent& lt, const double* dX, int64_t N, int64_t Nc, int ldx, bool with_kd = false) {
   const int nbn = (int)(Nc / BN);
   for (int p = 0; p < 2; ++p) {
     KronFactor& f = lt.f[p];
     const size_t pn = (size_t)f.Mq * Nc;
     ZIGP_ENSURE(c, f.Kp, pn); ZIGP_ENSURE(c, f.Ap, pn); ZIGP_ENSURE(c, f.Asq, pn);
-    KernHyp hyp = make_hyp(f.ell.data(), f.var, f.D);
-    hipLaunchKernelGGL(k_kron_kbuild, dim3((unsigned)(Nc / 256), f.Mq / 16), dim3(256), 0, c->stream, dX, N, ldx, f.col0, f.Z.p, f.M, hyp,
-                       f.Kp.p, Nc);
-    ZIGP_HIP(c, hipGetLastError());
+    if (f.kind != ZIGP_KERN_RBF) ZIGP_TRY(factor_kbuild_matern(c, f, dX, N, Nc, ldx, with_kd));
+    else {
+      KernHyp hyp = make_hyp(f.ell.data(), f.var, f.D);
+      hipLaunchKernelGGL(k_kron_kbuild, dim3((unsigned)(Nc / 256), f.Mq / 16), dim3(256), 0, c->stream, dX, N, ldx, f.col0, f.Z.p, f.M, hyp,
+                         f.Kp.p, Nc);
+      ZIGP_HIP(c, hipGetLastError());
+    }
     // A_p = P_p K_p
     ZIGP_TRY((mm<LAY_KCONTIG, LAY_MNCONTIG>(c, f.P.p, f.Mq, f.Kp.p, Nc, f.Ap.p, Nc, f.Mq / BM, nbn, f.Mq / BM)));
     hipLaunchKernelGGL(k_square_panel, dim3(ceil_div((int64_t)pn, 256)), dim3(256), 0, c->stream, f.Ap.p, f.Asq.p, (int64_t)pn);
@@ -469,8 +608,12 @@ int latent_backward(zigp_ctx* c, KronLatent& lt, const double* dX, int64_t N, in
     hipLaunchKernelGGL(k_kron_da, dim3(ceil_div((int64_t)pn, 256)), dim3(256), 0, c->stream, f.Ap.p, f.Cx.p, f.Kp.p, lt.gv.p, dq[p], Nc,
                        (int64_t)pn, f.dA.p, f.E.p);
     ZIGP_TRY((mm<LAY_KCONTIG, LAY_MNCONTIG>(c, f.P.p, f.Mq, f.dA.p, Nc, f.PdA.p, Nc, f.Mq / BM, nbn, f.Mq / BM)));
-    hipLaunchKernelGGL(k_kron_kgrad, dim3(f.Mq), dim3(256), 0, c->stream, f.Bx.p, f.Ap.p, f.PdA.p, f.Kp.p, lt.gm.p, dq[p], dX, N, ldx, f.col0,
-                       f.Z.p, f.M, f.D, Nc, f.krow.p);
+    if (f.kind != ZIGP_KERN_RBF)
+      hipLaunchKernelGGL(k_kron_kgrad_matern, dim3(f.Mq), dim3(256), 0, c->stream, f.Bx.p, f.Ap.p, f.PdA.p, f.Kp.p, f.Kd.p, lt.gm.p, dq[p], dX, N, ldx,
+                         f.col0, f.Z.p, f.M, f.D, Nc, f.krow.p);
+    else
+      hipLaunchKernelGGL(k_kron_kgrad, dim3(f.Mq), dim3(256), 0, c->stream, f.Bx.p, f.Ap.p, f.PdA.p, f.Kp.p, lt.gm.p, dq[p], dX, N, ldx, f.col0,
+                         f.Z.p, f.M, f.D, Nc, f.krow.p);
     ZIGP_HIP(c, hipGetLastError());
     // dP_p (data) = E_p K_p^T
     ZIGP_ENSURE(c, f.dP, (size_t)f.Mq * f.Mq);
@@ -581,9 +724,10 @@ int kron_exchange_host(zigp_ctx* c, const KronCall& k) {
   return 0;
 }
 
-// small grids go through the fused register-resident kernels (zigp_kronf.hip); larger factors through the panel path below
+// small grids go through the fused register-resident kernels (zigp_kronf.hip); larger factors, and every call with a Matern factor
+// (zigp_set_kron_kernel: the fused kernels are RBF only), through the panel path below
 int kron_run(zigp_ctx* c, const KronCall& k) {
-  if (!c->kron_panels && kf_eligible(k.p, k.nlat)) return kronf_run(c, k);
+  if (!c->kron_panels && kf_eligible(k.p, k.nlat) && kron_matern_factor(k.hl, k.nlat).empty()) return kronf_run(c, k);
   return kron_run_panels(c, k);
 }
 
@@ -632,7 +776,7 @@ int kron_run_panels(zigp_ctx* c, const KronCall& k) {
   for (int h = 0; h < nlat; ++h) {
     OnStream on(c, h == 0 ? c->stream_main : c->stream2);
     KronLatent& lt = ks.lat[h];
-    ZIGP_TRY(latent_forward_panels(c, lt, ks.X.p, N, Nc, ldx));
+    ZIGP_TRY(latent_forward_panels(c, lt, ks.X.p, N, Nc, ldx, need_grad));
     ZIGP_ENSURE(c, lt.gm, Nc); ZIGP_ENSURE(c, lt.gv, Nc); ZIGP_ENSURE(c, lt.dq0, Nc); ZIGP_ENSURE(c, lt.dq1, Nc);
   }
   ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
@@ -676,7 +820,11 @@ int kron_run_panels(zigp_ctx* c, const KronCall& k) {
         // G = -(P dP P) - kl*0.5*M_other*P  -> f.G ; then Kuu-style reductions into krow
         hipLaunchKernelGGL(k_kron_dk, dim3(ceil_div((int64_t)Mq * Mq, 256)), dim3(256), 0, c->stream, f.L.p, f.P.p,
                            include_kl ? 0.5 * (double)lt.f[1 - q].M : 0.0, (int64_t)Mq * Mq, f.G.p);
-        hipLaunchKernelGGL(k_kuu_grad, dim3(Mq), dim3(256), 0, c->stream, f.G.p, f.K.p, k.jitter, f.Z.p, f.M, f.D, (int64_t)Mq, f.krow.p);
+        if (f.kind != ZIGP_KERN_RBF)
+          hipLaunchKernelGGL(k_kuu_grad_matern, dim3(Mq), dim3(256), 0, c->stream, f.G.p, f.K.p, k.jitter, f.Z.p, f.M,
+                             make_hyp(f.ell.data(), f.var, f.D), f.kind, (int64_t)Mq, f.krow.p);
+        else
+          hipLaunchKernelGGL(k_kuu_grad, dim3(Mq), dim3(256), 0, c->stream, f.G.p, f.K.p, k.jitter, f.Z.p, f.M, f.D, (int64_t)Mq, f.krow.p);
         ZIGP_HIP(c, hipGetLastError());
         ZIGP_TRY(download(c, f.krow.p, (size_t)Mq * (2 + 2 * f.D), &hkrow[h][q]));
       }
@@ -748,6 +896,7 @@ int kron_elbo_entry(zigp_ctx* c, const char* name, const char* twin, KronCall k,
   ZIGP_HIP(c, hipSetDevice(c->device));
   if (empty) { k.X = k.Y = kron_no_rows; k.N = 1; k.scale = 0.0; }      // zero data term, same calls as the peers of an empty shard
   kron_call_derive(k);
+  kron_set_kinds(c, k.hl, k.nlat);
   return kron_run(c, k);
 }
 
@@ -761,6 +910,7 @@ int kron_predict_entry(zigp_ctx* c, const char* name, const char* twin, KronCall
   ZIGP_HIP(c, hipSetDevice(c->device));
   k.scale = 1.0; k.predict = true;
   kron_call_derive(k);
+  kron_set_kinds(c, k.hl, k.nlat);
   return kron_predict_chunked(c, k);
 }
 
@@ -780,6 +930,14 @@ int kron_fit_entry(zigp_ctx* c, const char* name, const char* rows_entry, const 
     return kron_refuse(c, name, "the likelihood must be ZIGP_LIK_GAUSSIAN or ZIGP_LIK_BERNOULLI (the OnOff fit is zigp_kron_fit_steps)");
   if (p->M0f <= 0 || p->M1f <= 0 || (!head && (p->M0g <= 0 || p->M1g <= 0))) return fail_arg(c, "inducing counts must be positive");
   if (p->D0 <= 0 || p->D1 <= 0 || p->D0 > MAXD || p->D1 > MAXD) return fail_arg(c, "factor dimensions must be in [1, 8]");
+  {
+    KronHostLatent kinds[2] = {};
+    kron_set_kinds(c, kinds, head ? 1 : 2);
+    const std::string who = kron_matern_factor(kinds, head ? 1 : 2);
+    if (!who.empty())
+      return kron_refuse(c, name, "a " + who + " is set (zigp_set_kron_kernel); the device loop fits RBF factors only: step it with " + rows_entry +
+                                      " and a host optimiser");
+  }
   if (fit.n_steps <= 0 || fit.batch <= 0 || fit.t0 < 0) return kron_refuse(c, name, "need n_steps > 0, batch > 0, t0 >= 0");
   if (!(k.jitter >= 0)) return kron_refuse(c, name, "jitter must be >= 0");
   if (!(opts->beta1 >= 0 && opts->beta1 < 1 && opts->beta2 >= 0 && opts->beta2 < 1 && opts->eps > 0)) return kron_refuse(c, name, "bad Adam constants");
@@ -886,6 +1044,23 @@ int zigp_set_kron_range_tiles(zigp_ctx* c, int32_t tiles) {
   return ZIGP_OK;
 }
 
+int zigp_set_kron_kernel(zigp_ctx* c, int32_t latent, int32_t factor, int32_t kind) {
+  if (!c) return ZIGP_EARG;
+  if (latent != 0 && latent != 1) return fail_arg(c, "zigp_set_kron_kernel: latent must be 0 (f) or 1 (g)");
+  if (factor != 0 && factor != 1) return fail_arg(c, "zigp_set_kron_kernel: factor must be 0 or 1");
+  if (kind != ZIGP_KERN_RBF && kind != ZIGP_KERN_MATERN32 && kind != ZIGP_KERN_MATERN52)
+    return fail_arg(c, "zigp_set_kron_kernel: unknown kernel kind (ZIGP_KERN_RBF, ZIGP_KERN_MATERN32, ZIGP_KERN_MATERN52)");
+  c->kron_kern[latent][factor] = kind;
+  return ZIGP_OK;
+}
+
+int zigp_get_kron_kernel(zigp_ctx* c, int32_t latent, int32_t factor) {
+  if (!c) return ZIGP_EARG;
+  if (latent != 0 && latent != 1) return fail_arg(c, "zigp_get_kron_kernel: latent must be 0 (f) or 1 (g)");
+  if (factor != 0 && factor != 1) return fail_arg(c, "zigp_get_kron_kernel: factor must be 0 or 1");
+  return c->kron_kern[latent][factor];
+}
+
 int zigp_set_kron_panels(zigp_ctx* c, int32_t on) {
   if (!c) return ZIGP_EARG;
   c->kron_panels = on != 0;
@@ -973,7 +1148,9 @@ int zigp_test_kron_fused_step(zigp_ctx* c, const zigp_stage_kron_fused* s) {
   ZIGP_TRY(validate_kron(c, s->p, s->lik));
   const int nlat = s->lik == ZIGP_LIK_ONOFF ? 2 : 1;
   if (s->N < 1 || !s->X || !s->Y || !s->grads || !(s->jitter >= 0)) return fail_arg(c, "zigp_test_kron_fused_step: need N >= 1 rows X, Y, grads and jitter >= 0");
-  if (c->kron_panels || !kf_eligible(s->p, nlat))
+  KronHostLatent kinds[2] = {};
+  kron_set_kinds(c, kinds, nlat);
+  if (c->kron_panels || !kf_eligible(s->p, nlat) || !kron_matern_factor(kinds, nlat).empty())
     return fail_arg(c, "zigp_test_kron_fused_step: this step does not run on the fused Kronecker kernels (grid beyond them, or zigp_set_kron_panels)");
   ZIGP_HIP(c, hipSetDevice(c->device));
   KfTap tap;
@@ -1061,6 +1238,61 @@ int zigp_test_kron_kgrad(zigp_ctx* c, int32_t M, int32_t D, int64_t N, int64_t N
   ZIGP_TRY(stage_upload_rows(c, dr, krow, M, Mq, Wd));
   hipLaunchKernelGGL(k_kron_kgrad, dim3(Mq), dim3(256), 0, c->stream, db.p, da.p, dp.p, dk.p, dgm.p, ddq.p, dx.p, N, (int)ldx, (int)col0, dz.p, (int)M,
                      (int)D, Nc, dr.p);
+  ZIGP_HIP(c, hipGetLastError());
+  ZIGP_TRY(stage_download_rows(c, dr.p, krow, M, Wd));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  return ZIGP_OK;
+}
+
+// The factor panel of any kind through the launch latent_forward_panels makes for it: ZIGP_KERN_RBF is zigp_test_kron_kbuild (Kd, when
+// asked for, is a copy of K: K' = K), a Matern kind k_kron_kbuild_matern<KIND, Kd != NULL>.
+int zigp_test_kron_kbuild_kind(zigp_ctx* c, int32_t kind, int64_t N, int64_t Nc, int32_t ldx, int32_t col0, int32_t M, int32_t D, const double* X,
+                               const double* Z, const double* ell, double var, double* K, double* Kd) {
+  if (!c) return ZIGP_EARG;
+  if (kind != ZIGP_KERN_RBF && kind != ZIGP_KERN_MATERN32 && kind != ZIGP_KERN_MATERN52) return fail_arg(c, "zigp_test_kron_kbuild_kind: unknown kernel kind");
+  if (!kron_stage_cols_ok(N, Nc) || M <= 0 || M > 4096 || D < 1 || D > MAXD || col0 < 0 || col0 + D > ldx || !X || !Z || !ell || !K)
+    return fail_arg(c, "zigp_test_kron_kbuild_kind: bad arguments");
+  if (kind == ZIGP_KERN_RBF) {
+    ZIGP_TRY(zigp_test_kron_kbuild(c, N, Nc, ldx, col0, M, D, X, Z, ell, var, K));
+    if (Kd) memcpy(Kd, K, sizeof(double) * (size_t)round_up(M, BM) * Nc);
+    return ZIGP_OK;
+  }
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  KronFactor f;
+  f.M = M; f.Mq = (int)round_up(M, BM); f.D = D; f.col0 = col0; f.var = var; f.kind = kind;
+  f.ell.assign(ell, ell + D);
+  DevBuf dx;
+  ZIGP_TRY(stage_upload_rows(c, dx, X, N, N, ldx));
+  ZIGP_TRY(stage_upload_rows(c, f.Z, Z, M, f.Mq, D));
+  ZIGP_TRY(kron_stage_out(c, f.Kp, (size_t)f.Mq * Nc, true));
+  if (Kd) ZIGP_TRY(kron_stage_out(c, f.Kd, (size_t)f.Mq * Nc, true));
+  ZIGP_TRY(factor_kbuild_matern(c, f, dx.p, N, Nc, (int)ldx, Kd != nullptr));
+  ZIGP_TRY(stage_download_rows(c, f.Kp.p, K, f.Mq, Nc));
+  if (Kd) ZIGP_TRY(stage_download_rows(c, f.Kd.p, Kd, f.Mq, Nc));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));
+  return ZIGP_OK;
+}
+
+// The factor cotangent of any kind: ZIGP_KERN_RBF is zigp_test_kron_kgrad (Kd is not read), a Matern kind k_kron_kgrad_matern on K and K'.
+int zigp_test_kron_kgrad_kind(zigp_ctx* c, int32_t kind, int32_t M, int32_t D, int64_t N, int64_t Nc, int32_t ldx, int32_t col0, const double* B,
+                              const double* A, const double* PdA, const double* K, const double* Kd, const double* gm, const double* dq,
+                              const double* X, const double* Z, double* krow) {
+  if (!c) return ZIGP_EARG;
+  if (kind == ZIGP_KERN_RBF) return zigp_test_kron_kgrad(c, M, D, N, Nc, ldx, col0, B, A, PdA, K, gm, dq, X, Z, krow);
+  if (kind != ZIGP_KERN_MATERN32 && kind != ZIGP_KERN_MATERN52) return fail_arg(c, "zigp_test_kron_kgrad_kind: unknown kernel kind");
+  if (!kron_stage_cols_ok(N, Nc) || M <= 0 || M > 4096 || D < 1 || D > MAXD || col0 < 0 || col0 + D > ldx || !B || !A || !PdA || !K || !Kd || !gm ||
+      !dq || !X || !Z || !krow)
+    return fail_arg(c, "zigp_test_kron_kgrad_kind: bad arguments");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  const int Mq = (int)round_up(M, BM), Wd = 2 + 2 * D;
+  DevBuf db, da, dp, dk, dkd, dgm, ddq, dx, dz, dr;
+  ZIGP_TRY(stage_upload_rows(c, db, B, M, Mq, Nc)); ZIGP_TRY(stage_upload_rows(c, da, A, M, Mq, Nc)); ZIGP_TRY(stage_upload_rows(c, dp, PdA, M, Mq, Nc));
+  ZIGP_TRY(stage_upload_rows(c, dk, K, M, Mq, Nc)); ZIGP_TRY(stage_upload_rows(c, dkd, Kd, M, Mq, Nc));
+  ZIGP_TRY(stage_upload_rows(c, dgm, gm, 1, 1, Nc)); ZIGP_TRY(stage_upload_rows(c, ddq, dq, 1, 1, Nc));
+  ZIGP_TRY(stage_upload_rows(c, dx, X, N, N, ldx)); ZIGP_TRY(stage_upload_rows(c, dz, Z, M, Mq, D));
+  ZIGP_TRY(stage_upload_rows(c, dr, krow, M, Mq, Wd));
+  hipLaunchKernelGGL(k_kron_kgrad_matern, dim3(Mq), dim3(256), 0, c->stream, db.p, da.p, dp.p, dk.p, dkd.p, dgm.p, ddq.p, dx.p, N, (int)ldx, (int)col0,
+                     dz.p, (int)M, (int)D, Nc, dr.p);
   ZIGP_HIP(c, hipGetLastError());
   ZIGP_TRY(stage_download_rows(c, dr.p, krow, M, Wd));
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));

@@ -6,7 +6,8 @@
 namespace zigp {
 
 // one latent's parameters as the host holds them (zigp_kron_params, per factor q = 0, 1)
-struct KronHostLatent { int M[2]; const double* Z[2]; const double* ell[2]; double var[2]; const double* u; const double* s; };
+// kind[q]: the factor's ZIGP_KERN_* (zigp_set_kron_kernel; kron_set_kinds fills it from the context, 0 = RBF otherwise)
+struct KronHostLatent { int M[2]; const double* Z[2]; const double* ell[2]; double var[2]; const double* u; const double* s; int kind[2]; };
 
 // One ELBO step or prediction: filled by the entry points (zigp_kron.hip; fields they do not set are zero), read by kron_run,
 // kron_run_panels, kronf_run and kron_predict_chunked.
@@ -45,6 +46,22 @@ static void kron_call_derive(KronCall& k) {
   k.nlat = (k.lik == ZIGP_LIK_ONOFF) ? 2 : 1;
   k.need_grad = k.grads != nullptr && !k.predict;
   kron_host_latents(k.p, k.nlat, k.hl);
+}
+
+// The factor kinds of a call: context state (zigp_set_kron_kernel), read once per call next to kron_call_derive.  A head (nlat == 1)
+// follows the f kinds.
+static void kron_set_kinds(const zigp_ctx* c, KronHostLatent* hl, int nlat) {
+  for (int h = 0; h < 2; ++h)
+    for (int q = 0; q < 2; ++q) hl[h].kind[q] = c->kron_kern[nlat == 1 ? 0 : h][q];
+}
+static const char* kron_kern_name(int kind) { return kind == ZIGP_KERN_MATERN32 ? "Matern32" : kind == ZIGP_KERN_MATERN52 ? "Matern52" : "RBF"; }
+// "<kernel> kernel on factor <q> of latent <f|g>" of the first Matern factor of the call's latents, or empty: every factor is RBF
+static std::string kron_matern_factor(const KronHostLatent* hl, int nlat) {
+  for (int h = 0; h < nlat; ++h)
+    for (int q = 0; q < 2; ++q)
+      if (hl[h].kind[q] != ZIGP_KERN_RBF)
+        return std::string(kron_kern_name(hl[h].kind[q])) + " kernel on factor " + std::to_string(q) + " of latent " + (h ? "g" : "f");
+  return std::string();
 }
 
 // what a Cholesky failure names: one job of the fused factor kernel, or (predictions, the panel path) the factors as a whole

@@ -57,10 +57,13 @@ struct KpLat {
   const double* tab;                    // [sample tile][F][16] weights: grid points (i, j) at i M1p + j in [0, coff), cosines [coff, coff + R4)
   double* out; int64_t ldo;             // out[s * ldo + n]
   int M0, M1, M1p, R4, F, coff, S, D0, D1;
+  int kinds;                            // kind0 + 4 kind1 (ZIGP_KERN_*; 0: RBF x RBF), read by k_kron_path_rows_kinds alone.  It fills the padding
+                                        // behind the nine ints: the record's size and every other offset are what the RBF kernels were built with
   double inv_ell[MAXD];                 // 1 / ell0 (D0), then 1 / ell1 (D1)
   double var0, var1, shift;
 };
 struct KpArgs { KpLat lat[2]; int ntile; int wave_doubles; };   // ntile: sample tiles in the table, a multiple of NST; a wave's LDS region
+static_assert(sizeof(KpLat) == 200 && sizeof(KpArgs) == 408, "the kernel arguments of the RBF path kernels keep their layout");
 
 // the element of k_kron_kbuild from its r2: var exp(-r2 / 2), with that kernel's branch for subnormal results
 __device__ __forceinline__ double kp_value_of_r2(double r2, double var) {
@@ -94,6 +97,37 @@ __device__ __forceinline__ void kp_stage1(const double* __restrict__ xrow, const
   }
 }
 
+// kp_stage1 with the factor's kind (zigp_set_kron_kernel / zigp_kron_path_latent.kinds) as a run-time switch: RBF is kp_value_of_r2, a
+// Matern kind the element of k_kron_kbuild_matern (kron_matern_elem, zigp_kron.hip) from the same r2.  Stage 1 is M0 + M1 values a row,
+// off the MFMA loop.
+__device__ __forceinline__ double kp_value_of_kind(int kind, double r2, double var) {
+  double k, kd = 0.0;
+  if (kind == KERN_RBF) return kp_value_of_r2(r2, var);
+  if (kind == KERN_M32) kron_matern_elem<KERN_M32, false>(var, r2, k, kd);
+  else kron_matern_elem<KERN_M52, false>(var, r2, k, kd);
+  return k;
+}
+__device__ __forceinline__ void kp_stage1_kind(const double* __restrict__ xrow, const double* __restrict__ Z, const double* inv_ell, int Dq, double var,
+                                               int kind, int M, int Mp, double* dst, int g, int i16) {
+  for (int m0 = g; m0 < Mp; m0 += 16) {
+    double r2[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int d = 0; d < Dq; ++d) {
+      const double ie = inv_ell[d], xs = xrow[d] * ie;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int m = min(m0 + 4 * u, M - 1);      // a point behind M is read as the last one and not used
+        const double t = Z[(size_t)m * Dq + d] * ie - xs;
+        r2[u] = fma(t, t, r2[u]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int m = m0 + 4 * u;
+      if (m < Mp) dst[m * 16 + i16] = m < M ? kp_value_of_kind(kind, r2[u], var) : 0.0;
+    }
+  }
+}
+
 template <int D, int NST, int RT>
 __global__ void __launch_bounds__(256)
 k_kron_path_rows(KpArgs pa) {
@@ -123,6 +157,118 @@ k_kron_path_rows(KpArgs pa) {
       double* const k0 = region + (size_t)t * Mt * 16;
       kp_stage1(xrow, a.Z0, a.inv_ell, a.D0, a.var0, a.M0, a.M0, k0, g, i16);
       kp_stage1(xrow + a.D0, a.Z1, a.inv_ell + a.D0, a.D1, a.var1, a.M1, a.M1p, k0 + (size_t)a.M0 * 16, g, i16);
+    }
+  }
+  __syncthreads();      // every wave of the block arrives: none has left yet
+  if (row0 >= a.N) return;
+  const double* const k0s = region + i16;
+  const double* const k1s = region + (size_t)a.M0 * 16 + g * 16 + i16;
+  const int njg = a.M1p >> 2, ngroups = a.M0 * njg;      // groups of four grid points: group G holds (i, 4 jg + g), G = i njg + jg
+  for (int t0 = 0; t0 < pa.ntile; t0 += NST) {
+    potrf_d4 acc[RT][NST];
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+#pragma unroll
+      for (int j = 0; j < NST; ++j) acc[t][j] = potrf_d4{0.0, 0.0, 0.0, 0.0};
+    // stage 2: the groups in ascending j inside ascending i; the weights of the next U groups are read while these U run (a group
+    // behind the last is read as the last and not used)
+    if (ngroups > 0) {
+      const double* const wp = a.tab + ((int64_t)t0 * a.F + g) * 16 + i16;      // the lane's weight of group G and tile q: wp[(q F + 4 G) 16]
+      double cur[U][NST], nxt[U][NST];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int q = 0; q < NST; ++q) cur[u][q] = wp[((int64_t)q * a.F + 4 * min(u, ngroups - 1)) * 16];
+      int i = 0, jg = 0;
+      for (int G0 = 0; G0 < ngroups; G0 += U) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+          for (int q = 0; q < NST; ++q) nxt[u][q] = wp[((int64_t)q * a.F + 4 * min(G0 + U + u, ngroups - 1)) * 16];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (G0 + u < ngroups) {      // wave-uniform
+#pragma unroll
+            for (int t = 0; t < RT; ++t) {
+              const double v = __dmul_rn(k0s[((size_t)t * Mt + i) * 16], k1s[((size_t)t * Mt + 4 * jg) * 16]);
+#pragma unroll
+              for (int q = 0; q < NST; ++q) acc[t][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[u][q], v, acc[t][q], 0, 0, 0);
+            }
+            if (++jg == njg) { jg = 0; ++i; }
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+          for (int q = 0; q < NST; ++q) cur[u][q] = nxt[u][q];
+      }
+    }
+    // the cosine loop of k_path_rows, restated (that kernel's code is not touched)
+    for (int r = g; r < a.R4; r += 4) {      // R4 is a multiple of 4
+      double om[D], wt[NST];
+#pragma unroll
+      for (int d = 0; d < D; ++d) om[d] = a.omega[(int64_t)r * D + d];
+      const double ph = a.phase[r];
+#pragma unroll
+      for (int q = 0; q < NST; ++q) wt[q] = a.tab[((int64_t)(t0 + q) * a.F + a.coff + r) * 16 + i16];
+#pragma unroll
+      for (int t = 0; t < RT; ++t) {
+        double arg = om[0] * x[t][0];
+#pragma unroll
+        for (int d = 1; d < D; ++d) arg = fma(om[d], x[t][d], arg);
+        const double v = cos(arg + ph);
+#pragma unroll
+        for (int q = 0; q < NST; ++q) acc[t][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(wt[q], v, acc[t][q], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+      if (!valid[t]) continue;
+      const int64_t n = row0 + t * 16 + i16;
+#pragma unroll
+      for (int j = 0; j < NST; ++j)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int s = (t0 + j) * 16 + 4 * q + g;
+          if (s < a.S) a.out[(int64_t)s * a.ldo + n] = acc[t][j][q] + a.shift;
+        }
+    }
+  }
+}
+
+// k_kron_path_rows for a launch with a Matern factor on one of its latents: stage 1 is kp_stage1_kind with each factor's kind; stage 2,
+// the cosines and the stores -- and with them the one summation order -- are k_kron_path_rows restated.  (One shared body was built
+// first: inlined into k_kron_path_rows it changed that kernel's register allocation, and the RBF machine code is to stay what it was;
+// profiles/kron_matern_isa.log.)
+template <int D, int NST, int RT>
+__global__ void __launch_bounds__(256)
+k_kron_path_rows_kinds(KpArgs pa) {
+  extern __shared__ double kp_lds[];
+  constexpr int U = 8 / NST;                       // groups of four whose weights are read together: 8 reads of 512 bytes in flight
+  const KpLat& a = pa.lat[blockIdx.y];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, i16 = lane & 15;
+  const int waves = blockDim.x >> 6;
+  const int64_t row0 = ((int64_t)blockIdx.x * waves + wave) * (RT * 16);
+  const int Mt = a.M0 + a.M1p;                     // doubles / 16 of one row tile's region
+  double* const region = kp_lds + (size_t)wave * pa.wave_doubles;
+  double x[RT][D];
+  bool valid[RT];
+#pragma unroll
+  for (int t = 0; t < RT; ++t) {
+    const int64_t n = row0 + t * 16 + i16;
+    valid[t] = n < a.N;
+#pragma unroll
+    for (int d = 0; d < D; ++d) x[t][d] = valid[t] ? a.X[n * D + d] : 0.0;
+  }
+  // stage 1: the factor values of this wave's rows (a row behind N is read as the first row: finite values, never stored)
+  if (row0 < a.N) {
+#pragma unroll 1
+    for (int t = 0; t < RT; ++t) {
+      const int64_t n = row0 + t * 16 + i16;
+      const double* xrow = a.X + (n < a.N ? n : 0) * D;
+      double* const k0 = region + (size_t)t * Mt * 16;
+      kp_stage1_kind(xrow, a.Z0, a.inv_ell, a.D0, a.var0, a.kinds & 3, a.M0, a.M0, k0, g, i16);
+      kp_stage1_kind(xrow + a.D0, a.Z1, a.inv_ell + a.D0, a.D1, a.var1, a.kinds >> 2, a.M1, a.M1p, k0 + (size_t)a.M0 * 16, g, i16);
     }
   }
   __syncthreads();      // every wave of the block arrives: none has left yet
@@ -278,7 +424,13 @@ template <int D, int RT>
 int kp_launch_rt(zigp_ctx* c, const KpArgs& pa, int nlat, int nst, int64_t maxN, int waves) {
   const dim3 grid((unsigned)ceil_div(maxN, (int64_t)waves * RT * 16), (unsigned)nlat), block(64 * waves);
   const size_t shm = sizeof(double) * (size_t)pa.wave_doubles * waves;
-  if (nst == 4) hipLaunchKernelGGL((k_kron_path_rows<D, 4, RT>), grid, block, shm, c->stream, pa);
+  bool kinds = false;      // a Matern factor on a latent of this launch: the instantiations with the kind switch in stage 1
+  for (int h = 0; h < nlat; ++h) kinds = kinds || pa.lat[h].kinds != 0;
+  if (kinds) {
+    if (nst == 4) hipLaunchKernelGGL((k_kron_path_rows_kinds<D, 4, RT>), grid, block, shm, c->stream, pa);
+    else if (nst == 2) hipLaunchKernelGGL((k_kron_path_rows_kinds<D, 2, RT>), grid, block, shm, c->stream, pa);
+    else hipLaunchKernelGGL((k_kron_path_rows_kinds<D, 1, RT>), grid, block, shm, c->stream, pa);
+  } else if (nst == 4) hipLaunchKernelGGL((k_kron_path_rows<D, 4, RT>), grid, block, shm, c->stream, pa);
   else if (nst == 2) hipLaunchKernelGGL((k_kron_path_rows<D, 2, RT>), grid, block, shm, c->stream, pa);
   else hipLaunchKernelGGL((k_kron_path_rows<D, 1, RT>), grid, block, shm, c->stream, pa);
   ZIGP_HIP(c, hipGetLastError());
@@ -343,6 +495,8 @@ int kron_path_rows(zigp_ctx* c, const char* who, const zigp_kron_path_latent* la
     const zigp_kron_path_latent& q = lat[h];
     ZIGP_TRY(kp_check_grid(c, w, q.M0, q.M1));
     if (q.R < 0) return refuse(c, w, "R is negative");
+    if (q.reserved < 0 || q.reserved > 10 || (q.reserved & 3) == 3)      // the record's `reserved` word carries the kinds
+      return refuse(c, w, "kinds = " + std::to_string(q.reserved) + " is not kind0 + 4 kind1 of two ZIGP_KERN_* values");
     ZIGP_TRY(path_check_table(c, w, "Z0", q.Z0, (size_t)q.M0 * D0));
     ZIGP_TRY(path_check_table(c, w, "Z1", q.Z1, (size_t)q.M1 * D1));
     ZIGP_TRY(path_check_table(c, w, "ell0", q.ell0, D0));
@@ -402,6 +556,7 @@ int kron_path_rows(zigp_ctx* c, const char* who, const zigp_kron_path_latent* la
     a.ldo = N; a.M0 = q.M0; a.M1 = q.M1; a.M1p = dm[h].M1p; a.R4 = dm[h].R4; a.F = dm[h].F; a.coff = dm[h].coff; a.S = S; a.D0 = D0; a.D1 = D1;
     kp_inv_ell(a, q.ell0, q.ell1, D0, D1);
     a.var0 = q.var0; a.var1 = q.var1; a.shift = q.shift;
+    a.kinds = q.reserved;
   }
   ZIGP_HIP(c, hipMemcpyAsync(c->path_tab.p, img, sizeof(double) * total, hipMemcpyHostToDevice, c->stream));
   const double* dX = nullptr;
@@ -433,6 +588,7 @@ int kron_sample_paths(zigp_ctx* c, const char* who, const zigp_kron_params* p, i
   const int nlat = lik == ZIGP_LIK_ONOFF ? 2 : 1, D0 = p->D0, D1 = p->D1, D = D0 + D1;
   KronHostLatent hl[2];
   kron_host_latents(p, nlat, hl);
+  kron_set_kinds(c, hl, nlat);      // zigp_set_kron_kernel: the factor stage and the path kernel evaluate the same k_q
   const zigp_path_draw* dr[2] = {draw_f, draw_g};
   const char* tag[2] = {"f", "g"};
   for (int h = 0; h < nlat; ++h) {
@@ -464,8 +620,8 @@ int kron_sample_paths(zigp_ctx* c, const char* who, const zigp_kron_params* p, i
   // the call's own factor forward stage, as zigp_kron_predict's panel path runs it: K_p + jitter I, L_p, W_p = L_p^-1
   ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
   for (int h = 0; h < nlat; ++h) {
-    ZIGP_TRY(factor_forward(c, ks.lat[h].f[0], hl[h].M[0], D0, 0, hl[h].Z[0], hl[h].ell[0], hl[h].var[0], jitter));
-    ZIGP_TRY(factor_forward(c, ks.lat[h].f[1], hl[h].M[1], D1, D0, hl[h].Z[1], hl[h].ell[1], hl[h].var[1], jitter));
+    ZIGP_TRY(factor_forward(c, ks.lat[h].f[0], hl[h].M[0], D0, 0, hl[h].Z[0], hl[h].ell[0], hl[h].var[0], jitter, hl[h].kind[0]));
+    ZIGP_TRY(factor_forward(c, ks.lat[h].f[1], hl[h].M[1], D1, D0, hl[h].Z[1], hl[h].ell[1], hl[h].var[1], jitter, hl[h].kind[1]));
   }
   int* hinfo = nullptr;
   ZIGP_TRY(request_info(c, &hinfo));
@@ -526,6 +682,7 @@ int kron_sample_paths(zigp_ctx* c, const char* who, const zigp_kron_params* p, i
     a.M0 = M0; a.M1 = M1; a.M1p = dm[h].M1p; a.R4 = dm[h].R4; a.F = dm[h].F; a.coff = dm[h].coff; a.S = S; a.D0 = D0; a.D1 = D1;
     kp_inv_ell(a, hl[h].ell[0], hl[h].ell[1], D0, D1);
     a.var0 = hl[h].var[0]; a.var1 = hl[h].var[1]; a.shift = 0.0;
+    a.kinds = hl[h].kind[0] + 4 * hl[h].kind[1];
   }
   ZIGP_HIP(c, hipMemcpyAsync(base, img, sizeof(double) * staged, hipMemcpyHostToDevice, c->stream));
 

@@ -15,7 +15,7 @@ import zigp
 from zigp.optim import AdamGroups, ParamSet
 from zigp.transforms import Log1pe, positive
 from .main import DataSet, Param
-from .model import load_checkpoint, save_checkpoint
+from .model import get_kernels, has_matern, load_checkpoint, save_checkpoint, set_kernels
 
 TRAIN_JITTER = 1e-5     # scripts/svgp.py:18, classifier.py:19, hurdle.py:18
 PREDICT_JITTER = 1e-6   # onofftf/svgppred.py:13, onofftf/svcppred.py:13
@@ -63,6 +63,7 @@ def head_engine_params(pset):
                var_f=[v['f_kern/variance_0'], v['f_kern/variance_1']], u_fm=v['f_ind/value'], u_fs_sqrt=v['f_ind/variance'])
     if 'likelihood/variance' in v:
         out['noise'] = v['likelihood/variance']
+    out['kern_f'] = get_kernels(pset, ('f',))['f']
     return out
 
 
@@ -114,7 +115,8 @@ class HeadDeviceFit:
                 raise ValueError('the device fit loop implements Log1pe with lower = 1e-6')
         v = pset.params
         Z0, Z1 = v['f_ind/z_0'].value, v['f_ind/z_1'].value
-        self.shape = dict(M0f=Z0.shape[0], M1f=Z1.shape[0], D0=Z0.shape[1], D1=Z1.shape[1])
+        self.shape = dict(M0f=Z0.shape[0], M1f=Z1.shape[0], D0=Z0.shape[1], D1=Z1.shape[1],
+                          kern_f=get_kernels(pset, ('f',))['f'])      # a Matern factor: kron_head_fit_steps refuses by name
         M = Z0.shape[0] * Z1.shape[0]
         want = [Z0.size, Z1.size, M, M, Z0.shape[1], Z1.shape[1], 1, 1, 1, 1]
         self.sizes = want
@@ -228,10 +230,17 @@ def _device_loop(eng, pset, lik, train_data, num_iter, num_minibatch, scale, sav
 
 
 def fit_head(pset, lik, Xtrain, Ytrain, num_iter, num_minibatch, logger, ckpt=None, eng=None, save_every=10000, history=None,
-             device_loop=True):
+             device_loop=True, kernels=None):
     """The optimisation loop of svgp.py:289-330 / classifier.py:276-316: Adam per learning-rate group on
     cost = -(sum(var_exp) * num_data / num_minibatch - kl).  device_loop: run it on the device (_device_loop) where the inducing grid
-    is within the fused kernels; False, or a larger grid, steps it from the host, one engine call per iteration."""
+    is within the fused kernels; False, or a larger grid, steps it from the host, one engine call per iteration.
+    kernels: the factor kinds of f -- a name or a pair (space, time) of 'rbf', 'matern32', 'matern52' (None: what the parameter set
+    holds, RBF by default).  With a Matern factor the host loop runs also when device_loop=True (the device loop fits RBF factors)."""
+    if kernels is not None:
+        set_kernels(pset, kernels, ('f',))
+    if device_loop and num_iter > 0 and has_matern(pset, ('f',)):
+        logger.info('Matern factor kernel %s: the host Adam loop runs (the device loop fits RBF factors only)' % (get_kernels(pset, ('f',))['f'],))
+        device_loop = False
     train_data = DataSet(Xtrain, Ytrain)                                          # svgp.py:43
     scale = float(Xtrain.shape[0]) / float(num_minibatch)                         # :212
     logger.info('*******  started optimization at ' + time.strftime('%Y%m%d-%H%M') + ' *******')

@@ -46,6 +46,30 @@ class KernSE:
         return numpy.full(numpy.shape(X)[0], self._vals()[1])
 
 
+class _KernMatern(KernSE):
+    """A Matern kernel of one Kronecker factor: KernSE's interface; K goes through engine.kern_K (the floored distance
+    r = sqrt(r2 + 1e-12), so the diagonal of K(X) is the formula at r = 1e-6; Kdiag is the variance)."""
+    kind = None
+
+    def K(self, X, X2=None, engine=None):
+        from onoffgpf.kernels import _get_engine
+        l, v = self._vals()
+        return (engine or _get_engine()).kern_K(self.kind, X, X2, l, v)
+
+
+class KernMatern32(_KernMatern):
+    """k = var (1 + sqrt3 r) exp(-sqrt3 r) (GPflow kernels.Matern32) as a factor kernel: kernels=(..., 'matern32') of onoff() / fit_head()"""
+    kind = 'matern32'
+
+
+class KernMatern52(_KernMatern):
+    """k = var (1 + sqrt5 r + (5/3) r^2) exp(-sqrt5 r) (GPflow kernels.Matern52) as a factor kernel"""
+    kind = 'matern52'
+
+
+KERNEL_CLASSES = {'rbf': KernSE, 'matern32': KernMatern32, 'matern52': KernMatern52}
+
+
 class DataSet(object):
     """Minibatch iterator with the batch sequence of onofftf/main.py:66-133: numpy.random.seed(121) (random_seed.get_seed(121) -> op seed
     121, :70-73), one shuffle before the first batch, one at every epoch end, and a wrap-around batch made of the old epoch's tail plus the

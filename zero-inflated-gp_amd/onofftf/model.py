@@ -59,9 +59,57 @@ def init_params(Xtrain, num_inducing_f, num_inducing_g, init_noisevar=0.01, kern
     return ParamSet(p)
 
 
+KERNEL_NAMES = ('rbf', 'matern32', 'matern52')
+
+
+def kernel_kinds(kernels, tags=('f', 'g')):
+    """{tag: (space kind, time kind)} from the `kernels` argument of onoff() / fit_head(): None (RBF everywhere), a name (every factor), a
+    pair (space, time) for every latent, or a dict {'f': name or pair, 'g': ...} (a missing latent is RBF)."""
+    def pair(v):
+        p = (v, v) if isinstance(v, str) else tuple(v) if isinstance(v, (tuple, list)) and len(v) == 2 else None
+        if p is None or not all(isinstance(n, str) and n.lower() in KERNEL_NAMES for n in p):
+            raise ValueError("kernels: %r is not 'rbf', 'matern32' or 'matern52', or a pair (space, time) of them" % (v,))
+        return (p[0].lower(), p[1].lower())
+    if kernels is None:
+        kernels = 'rbf'
+    if isinstance(kernels, dict):
+        if set(kernels) - set(tags):
+            raise ValueError('kernels: latents %s are not in %s' % (sorted(set(kernels) - set(tags)), tags))
+        return {t: pair(kernels.get(t, 'rbf')) for t in tags}
+    return {t: pair(kernels) for t in tags}
+
+
+def kernel_options(argv):
+    """kernels=(space, time) from the command-line options --kernel-space NAME / --kernel-time NAME of the scripts (default rbf);
+    every latent of the script's model takes the pair."""
+    import argparse
+    ap = argparse.ArgumentParser(add_help=False)
+    ap.add_argument('--kernel-space', default='rbf', choices=KERNEL_NAMES)
+    ap.add_argument('--kernel-time', default='rbf', choices=KERNEL_NAMES)
+    a, _ = ap.parse_known_args(list(argv))
+    return (a.kernel_space, a.kernel_time)
+
+
+def set_kernels(pset, kernels, tags=('f', 'g')):
+    """Keep the factor kinds in the parameter set (pset.kernels): engine_params / head_engine_params pass them on as kern_f / kern_g,
+    save_checkpoint stores them, load_checkpoint restores them."""
+    pset.kernels = kernel_kinds(kernels, tags)
+    return pset
+
+
+def get_kernels(pset, tags=('f', 'g')):
+    k = getattr(pset, 'kernels', None) or {}
+    return {t: tuple(k.get(t, ('rbf', 'rbf'))) for t in tags}
+
+
+def has_matern(pset, tags=('f', 'g')):
+    return any(n != 'rbf' for pair in get_kernels(pset, tags).values() for n in pair)
+
+
 def engine_params(pset):
     v = {k: q.value for k, q in pset.params.items()}
-    return dict(Zf=[v['f_ind/z_0'], v['f_ind/z_1']], Zg=[v['g_ind/z_0'], v['g_ind/z_1']],
+    kern = get_kernels(pset)
+    return dict(kern_f=kern['f'], kern_g=kern['g'], Zf=[v['f_ind/z_0'], v['f_ind/z_1']], Zg=[v['g_ind/z_0'], v['g_ind/z_1']],
                 ell_f=[v['f_kern/lengthscale_0'], v['f_kern/lengthscale_1']], ell_g=[v['g_kern/lengthscale_0'], v['g_kern/lengthscale_1']],
                 var_f=[v['f_kern/variance_0'], v['f_kern/variance_1']], var_g=[v['g_kern/variance_0'], v['g_kern/variance_1']],
                 u_fm=v['f_ind/value'], u_gm=v['g_ind/value'], u_fs_sqrt=v['f_ind/variance'], u_gs_sqrt=v['g_ind/variance'],
@@ -114,6 +162,8 @@ class KronDeviceFit:
         v = pset.params
         self.shape = dict(M0f=v['f_ind/z_0'].value.shape[0], M1f=v['f_ind/z_1'].value.shape[0], M0g=v['g_ind/z_0'].value.shape[0],
                           M1g=v['g_ind/z_1'].value.shape[0], D0=v['f_ind/z_0'].value.shape[1], D1=v['f_ind/z_1'].value.shape[1])
+        kern = get_kernels(pset)      # a Matern factor: kron_fit_steps refuses by name (the device loop fits RBF factors)
+        self.shape.update(kern_f=kern['f'], kern_g=kern['g'])
 
     def steps(self, row_begin, batch, jitter, scale, Xw=None, Yw=None, include_kl=True):
         """len(row_begin) iterations on the resident data set (engine.set_data): returns (elbo_data, kl) per step; the ParamSet holds the
@@ -160,8 +210,13 @@ class KronDeviceFit:
         self._written = [self.pset.params[k].value.copy() for k in FIT_BLOCK_NAMES]
 
 
+CKPT_KERNELS = 'kernels'      # checkpoint entry with the factor kinds: names in the order f space, f time[, g space, g time]
+
+
 def save_checkpoint(pset, path):
-    np.savez(path, **{k.replace('/', '__'): q.value for k, q in pset.params.items()})
+    tags = ('f', 'g') if 'g_ind/value' in pset.params else ('f',)
+    kern = get_kernels(pset, tags)
+    np.savez(path, **{k.replace('/', '__'): q.value for k, q in pset.params.items()}, **{CKPT_KERNELS: np.array([n for t in tags for n in kern[t]])})
     return path if str(path).endswith('.npz') else str(path) + '.npz'
 
 
@@ -174,5 +229,8 @@ def load_checkpoint(pset, path, fitter=None, reset=True):
     d = np.load(path)
     for k, q in pset.params.items():
         q.value = np.asarray(d[k.replace('/', '__')], dtype=np.float64).reshape(q.value.shape)
+    # the factor kinds follow the checkpoint; one written before they existed holds none and loads as RBF
+    names = [str(n) for n in d[CKPT_KERNELS]] if CKPT_KERNELS in d.files else []
+    pset.kernels = {t: (names[2 * i], names[2 * i + 1]) if len(names) >= 2 * i + 2 else ('rbf', 'rbf') for i, t in enumerate(('f', 'g'))}
     if fitter is not None:
         fitter.resync(reset=reset)

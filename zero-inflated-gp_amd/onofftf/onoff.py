@@ -12,7 +12,7 @@ import numpy as np
 import zigp
 from zigp.optim import AdamGroups
 from .main import DataSet
-from .model import init_params, engine_params, named_grads, save_checkpoint
+from .model import init_params, engine_params, get_kernels, has_matern, named_grads, save_checkpoint, set_kernels
 
 jitter_level = 1e-5   # scripts/onoff.py:18
 
@@ -53,7 +53,11 @@ def _device_loop(eng, pset, train_data, num_iter, num_minibatch, scale, log_ever
 
 
 def onoff(Xtrain, Ytrain, Xtest, Ytest, dir, num_iter=50000, num_inducing_f=(10, 100), num_inducing_g=(10, 100),
-          num_minibatch=1000, log_every=200, save_every=10000, device=0, engine=None, kmeans_seed=None, history=None, device_loop=True):
+          num_minibatch=1000, log_every=200, save_every=10000, device=0, engine=None, kmeans_seed=None, history=None, device_loop=True,
+          kernels=None):
+    """kernels: the factor kinds -- None (RBF, the reference's KernSE), a name, a pair (space, time) for both latents, or
+    {'f': ..., 'g': ...} of 'rbf', 'matern32', 'matern52' (onofftf.model.kernel_kinds).  They are kept in the checkpoint, which the
+    predict / sample / score functions follow.  With a Matern factor the host Adam loop runs also when device_loop=True."""
     os.makedirs(dir, exist_ok=True) if dir else None
     logger = logging.getLogger('log')                                                # :35-40
     logger.setLevel(logging.DEBUG)
@@ -64,8 +68,12 @@ def onoff(Xtrain, Ytrain, Xtest, Ytest, dir, num_iter=50000, num_inducing_f=(10,
     train_data = DataSet(Xtrain, Ytrain)                                             # :43
     num_data = Xtrain.shape[0]                                                       # :54
     pset = init_params(Xtrain, num_inducing_f, num_inducing_g, init_noisevar=0.01, kmeans_seed=kmeans_seed)   # :51-137
+    set_kernels(pset, kernels)
     eng = engine or zigp.reference_engine(device)      # tf.cholesky's acceptance rule (pivot > 0)
     scale = float(num_data) / float(num_minibatch)                                   # :311
+    if device_loop and has_matern(pset):
+        logger.info('Matern factor kernels %s: the host Adam loop runs (the device loop fits RBF factors only)' % (get_kernels(pset),))
+        device_loop = False
     logger.info('*******  started optimization at ' + time.strftime('%Y%m%d-%H%M') + ' *******')
     # the device loop covers the grids of the fused kernels (<= 32 x <= 32, <= 16 x <= 112: the reference's [10, 100] and BASELINE's
     # 32 x 32); anything larger is stepped from the host, one call per iteration, as in rounds 1-3

@@ -31,7 +31,8 @@ def _scores(prob, actual):
 
 
 def classifier(Xtrain, Ytrain, Xtest, Ytest, dir, num_iter=500, num_inducing_f=(10, 100), num_minibatch=1000, include_f_mu=False,
-               device=0, engine=None, kmeans_seed=None, history=None, device_loop=True):
+               device=0, engine=None, kmeans_seed=None, history=None, device_loop=True, kernels=None):
+    """kernels: the factor kinds of f (fit_head); the command line takes --kernel-space / --kernel-time, default rbf"""
     os.makedirs(dir, exist_ok=True)
     Ytrain_c, Ytest_c = (Ytrain > 0) * 1.0, (Ytest > 0) * 1.0                                    # :43-47
     logger, handler = open_logger(os.path.join(dir, 'modelsumm_scgp.log'))
@@ -40,7 +41,8 @@ def classifier(Xtrain, Ytrain, Xtest, Ytest, dir, num_iter=500, num_inducing_f=(
     pset = init_head_params(Xtrain, num_inducing_f, 'bernoulli', include_f_mu=include_f_mu, kmeans_seed=kmeans_seed)   # :56-112
     eng = engine or zigp.reference_engine(device)      # tf.cholesky's acceptance rule (pivot > 0)
     ckpt = os.path.join(dir, 'model_scgp.ckpt')
-    fit_head(pset, 'bernoulli', Xtrain, Ytrain_c, num_iter, num_minibatch, logger, ckpt=ckpt, eng=eng, history=history, device_loop=device_loop)   # :276-321
+    fit_head(pset, 'bernoulli', Xtrain, Ytrain_c, num_iter, num_minibatch, logger, ckpt=ckpt, eng=eng, history=history, device_loop=device_loop,
+             kernels=kernels)   # :276-321
     log_kernel_summary(logger, pset)
     pred_train, pred_test = predict_scgp(Xtrain=Xtrain, Xtest=Xtest, checkpointPath=ckpt, num_inducing_f=np.array(num_inducing_f),
                                          include_f_mu=include_f_mu, engine=eng)                  # :352-354
@@ -64,4 +66,5 @@ def main(scriptPath, **kw):
 
 
 if __name__ == '__main__':
-    main(sys.argv[0])
+    from onofftf.model import kernel_options
+    main(sys.argv[0], kernels=kernel_options(sys.argv[1:]))      # --kernel-space NAME --kernel-time NAME, default rbf

@@ -21,7 +21,8 @@ def mad(predict, actual):
 
 
 def hurdle(Xtrain, Ytrain, Xtest, Ytest, cresults, dir, num_iter=50000, num_inducing_f=(10, 100), num_minibatch=1000, device=0,
-           engine=None, kmeans_seed=None, history=None, device_loop=True):
+           engine=None, kmeans_seed=None, history=None, device_loop=True, kernels=None):
+    """kernels: the factor kinds of the regression's f (fit_head); the command line takes --kernel-space / --kernel-time, default rbf"""
     os.makedirs(dir, exist_ok=True)
     logger, handler = open_logger(os.path.join(dir, 'modelsumm_hurdle.log'))
     train_on = np.where(cresults['pred_train']['pfmean'] > 0.5)[0]                               # :49-50
@@ -33,7 +34,8 @@ def hurdle(Xtrain, Ytrain, Xtest, Ytest, cresults, dir, num_iter=50000, num_indu
     pset = init_head_params(Xtrain, num_inducing_f, 'gaussian', kmeans_seed=kmeans_seed)
     eng = engine or zigp.reference_engine(device)      # tf.cholesky's acceptance rule (pivot > 0)
     ckpt = os.path.join(dir, 'model_hurdle.ckpt')
-    fit_head(pset, 'gaussian', Xtr, Ytr, num_iter, min(num_minibatch, Xtr.shape[0]), logger, ckpt=ckpt, eng=eng, history=history, device_loop=device_loop)
+    fit_head(pset, 'gaussian', Xtr, Ytr, num_iter, min(num_minibatch, Xtr.shape[0]), logger, ckpt=ckpt, eng=eng, history=history, device_loop=device_loop,
+             kernels=kernels)
     log_kernel_summary(logger, pset)
     ptr, pte = predict_svgp(Xtrain=Xtr, Xtest=Xte, checkpointPath=ckpt, num_inducing_f=np.array(num_inducing_f), engine=eng)   # :346-348
     res = {'pred_train_hurdle_svgp': ptr, 'pred_test_hurdle_svgp': pte,
@@ -67,4 +69,5 @@ def main(scriptPath, **kw):
 
 
 if __name__ == '__main__':
-    main(sys.argv[0])
+    from onofftf.model import kernel_options
+    main(sys.argv[0], kernels=kernel_options(sys.argv[1:]))      # --kernel-space NAME --kernel-time NAME, default rbf

@@ -13,7 +13,8 @@ jitter_level = TRAIN_JITTER   # scripts/svgp.py:18
 
 
 def svgp(Xtrain, Ytrain, Xtest, Ytest, dir, num_iter=50000, num_inducing_f=(10, 100), num_minibatch=1000, device=0, engine=None,
-         kmeans_seed=None, history=None, device_loop=True):
+         kmeans_seed=None, history=None, device_loop=True, kernels=None):
+    """kernels: the factor kinds of f, a name or a pair (space, time) of 'rbf', 'matern32', 'matern52' (fit_head); default RBF"""
     if dir:
         os.makedirs(dir, exist_ok=True)
     logger, handler = open_logger(os.path.join(dir, 'modelsumm.log') if dir else None)          # :30-39
@@ -23,7 +24,7 @@ def svgp(Xtrain, Ytrain, Xtest, Ytest, dir, num_iter=50000, num_inducing_f=(10, 
     pset = init_head_params(Xtrain, num_inducing_f, 'gaussian', kmeans_seed=kmeans_seed)       # :51-112
     eng = engine or zigp.reference_engine(device)      # tf.cholesky's acceptance rule (pivot > 0)
     fit_head(pset, 'gaussian', Xtrain, Ytrain, num_iter, num_minibatch, logger, ckpt=os.path.join(dir, 'model') if dir else None,
-             eng=eng, history=history, device_loop=device_loop)                                 # :289-334
+             eng=eng, history=history, device_loop=device_loop, kernels=kernels)                # :289-334
     log_kernel_summary(logger, pset)                                                            # :337-345
     # test predictions from the TRAINING graph (jitter 1e-5), clipped at 0  (:377-386)
     fmean = eng.kron_head_predict(head_engine_params(pset), Xtest, 'gaussian', jitter=jitter_level)[0].reshape(-1, 1)

@@ -11,7 +11,7 @@ ZIGP_OK, ZIGP_EARG, ZIGP_EHIP, ZIGP_ENOTPD, ZIGP_ECOMM = 0, -1, -2, -3, -4
 COMM_ID_BYTES = 128
 NCLASS = 10
 LIK_ONOFF, LIK_GAUSSIAN, LIK_BERNOULLI = 0, 1, 2   # include/zigp.h ZIGP_LIK_*
-KERN_RBF, KERN_MATERN32, KERN_MATERN52 = 0, 1, 2   # include/zigp.h ZIGP_KERN_*: kernel family of a dense latent (zigp_set_kernel)
+KERN_RBF, KERN_MATERN32, KERN_MATERN52 = 0, 1, 2   # include/zigp.h ZIGP_KERN_*: kernel family of a dense latent (zigp_set_kernel) or of a Kronecker factor (zigp_set_kron_kernel)
 KERNELS = {'rbf': KERN_RBF, 'matern32': KERN_MATERN32, 'matern52': KERN_MATERN52}
 DENSITY_MAX_QUAD = 256   # include/zigp.h ZIGP_DENSITY_MAX_QUAD: nodes of the quadrature rule of the density calls
 SCORE_MAX_LEVELS = 16    # include/zigp.h ZIGP_SCORE_MAX_LEVELS: quantile levels of one score call
@@ -239,6 +239,8 @@ SIGNATURES = {
     'zigp_get_q_full': (C.c_int, [C.c_void_p]),
     'zigp_set_kernel': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     'zigp_get_kernel': (C.c_int, [C.c_void_p, C.c_int32]),
+    'zigp_set_kron_kernel': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    'zigp_get_kron_kernel': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     'zigp_kern_K': (C.c_int, [C.c_void_p, C.c_int32, dp, C.c_int64, dp, C.c_int64, C.c_int32, dp, C.c_double, dp]),
     'zigp_kron_head_elbo': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_int32, dp, dp, C.c_int64, C.c_double, C.c_double,
                                       C.c_double, C.c_int32, dp, dp, C.POINTER(zigp_kron_grads), dp]),
@@ -299,6 +301,10 @@ SIGNATURES = {
     'zigp_test_kron_colsum': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, dp, dp, dp, dp, dp, dp, dp, dp]),
     'zigp_test_kron_da': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, dp, dp, dp, dp, dp, dp, dp]),
     'zigp_test_kron_kgrad': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp, dp]),
+    'zigp_test_kron_kbuild_kind': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp,
+                                             C.c_double, dp, dp]),
+    'zigp_test_kron_kgrad_kind': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, dp, dp, dp, dp, dp,
+                                            dp, dp, dp, dp, dp]),
 }
 
 # include/zigp_kronpaths.h (the header zigp.h includes for the Kronecker sample paths): bound by load() like SIGNATURES

@@ -41,6 +41,32 @@ def kernel_kinds(p, D=None):
     return tuple(kinds)
 
 
+def kron_kernel_kinds(p, tags=('f', 'g')):
+    """{tag: (kind of factor 0, kind of factor 1)} of a Kronecker parameter dict: p.get('kern_f', 'rbf') / p.get('kern_g', 'rbf') is a
+    name ('rbf', 'matern32', 'matern52': both factors) or a pair (kind0, kind1) of names.  ValueError, before any device work, for
+    anything else."""
+    out = {}
+    for tag in tags:
+        v = p.get('kern_' + tag, 'rbf')
+        pair = (v, v) if isinstance(v, str) else tuple(v) if isinstance(v, (tuple, list)) else None
+        if pair is None or len(pair) != 2 or not all(isinstance(n, str) and n.lower() in _lib.KERNELS for n in pair):
+            raise ValueError("kern_%s = %r: a Kronecker latent takes 'rbf', 'matern32' or 'matern52', or a pair (kind0, kind1) of them, "
+                             "one per factor" % (tag, v))
+        out[tag] = (_lib.KERNELS[pair[0].lower()], _lib.KERNELS[pair[1].lower()])
+    return out
+
+
+def kron_matern_factor(kinds):
+    """'<Kernel> kernel on factor <q> of latent <tag>' of the first Matern factor of kron_kernel_kinds' result, or None -- the naming
+    of the library's own refusals (zigp_kron_fit_steps)"""
+    names = {_lib.KERN_MATERN32: 'Matern32', _lib.KERN_MATERN52: 'Matern52'}
+    for tag in ('f', 'g'):
+        for q, k in enumerate(kinds.get(tag, ())):
+            if k in names:
+                return '%s kernel on factor %d of latent %s' % (names[k], q, tag)
+    return None
+
+
 class _Packed:
     """Keeps the numpy arrays behind a zigp_params struct alive."""
 
@@ -106,6 +132,7 @@ class KronStepper:
         self.eng = engine
         s, keep, dims = engine._pack_kron(p)            # private copies below: the caller's arrays may be views that change or go away
         self.dims = dims
+        self.kinds = kron_kernel_kinds(p)               # the factor kinds belong to the model shape: fixed here, set before every step
         self.par = {}
         self.s = _lib.zigp_kron_params()
         self.gs = _lib.zigp_kron_grads()
@@ -150,6 +177,7 @@ class KronStepper:
         s.noise = _scalar(p.get('noise', 1.0))
         fmu = 0.0 if f_mu is None else _scalar(f_mu)
         eng = self.eng
+        eng._apply_kron_kinds(self.kinds)
         if rows is None:
             X = as_f64(X)
             Y = as_f64(Y).reshape(-1)
@@ -334,6 +362,47 @@ class DenseEngine:
         if k < 0:
             raise ValueError('zigp_get_kernel: latent must be f / 0 or g / 1')
         return {v: n for n, v in _lib.KERNELS.items()}[k]
+
+    def set_kron_kernel(self, latent, factor, name):
+        """Kernel family of one factor of a Kronecker latent (zigp_set_kron_kernel): latent 'f' / 0 or 'g' / 1, factor 0 or 1, name 'rbf',
+        'matern32' or 'matern52'.  Every kron_* call sets all four from p.get('kern_f', 'rbf') / p.get('kern_g', 'rbf') first, so a
+        setting made here lasts until the next such call."""
+        if not isinstance(name, str) or name.lower() not in _lib.KERNELS:
+            raise ValueError("kernel %r: the Kronecker factors know 'rbf', 'matern32' and 'matern52'" % (name,))
+        self._kron_kinds_set = None
+        _check(self.lib, self.ctx, self.lib.zigp_set_kron_kernel(self.ctx, {'f': 0, 'g': 1}.get(latent, latent), int(factor),
+                                                                  _lib.KERNELS[name.lower()]))
+
+    def get_kron_kernel(self, latent, factor):
+        k = self.lib.zigp_get_kron_kernel(self.ctx, {'f': 0, 'g': 1}.get(latent, latent), int(factor))
+        if k < 0:
+            raise ValueError('zigp_get_kron_kernel: latent must be f / 0 or g / 1, factor 0 or 1')
+        return {v: n for n, v in _lib.KERNELS.items()}[k]
+
+    _kron_kinds_set = None      # the four kinds as this engine last set them (None: unknown), so a training loop sets them once
+
+    def _apply_kron_kinds(self, kinds):
+        """All four factor kinds of the context from kron_kernel_kinds' result (a latent that is absent: RBF) -- before every kron_* call,
+        so that a previous call's kinds never leak into this one."""
+        want = kinds.get('f', (0, 0)) + kinds.get('g', (0, 0))
+        if want == self._kron_kinds_set:
+            return
+        self._kron_kinds_set = None
+        for i, k in enumerate(want):
+            _check(self.lib, self.ctx, self.lib.zigp_set_kron_kernel(self.ctx, i >> 1, i & 1, int(k)))
+        self._kron_kinds_set = want
+
+    def _set_kron_kinds(self, p, tags=('f', 'g')):
+        self._apply_kron_kinds(kron_kernel_kinds(p, tags))
+
+    def _kron_fit_kinds(self, who, shape, tags):
+        """The device fit loops fit RBF factors: a Matern factor in shape raises before the library is touched, with the naming of the
+        library's own refusal; otherwise all four kinds go back to RBF."""
+        bad = kron_matern_factor(kron_kernel_kinds(shape, tags))
+        if bad:
+            raise ValueError('%s: a %s is set; the device loop fits RBF factors only: step the model with kron_%selbo(rows=...) and a host '
+                             'optimiser' % (who, bad, 'head_' if tags == ('f',) else ''))
+        self._apply_kron_kinds({})
 
     def _set_modes(self, p):
         kinds = kernel_kinds(p)          # an unknown name raises before anything is set
@@ -815,7 +884,7 @@ class DenseEngine:
     def _kron_path_latents(lats, dims, S):
         """The zigp_kron_path_latent records of kron_path_rows and the arrays behind them.  A latent is a dict: Z = [Z0 (M0, D0),
         Z1 (M1, D1)], ell = [ell0, ell1], var = [var0, var1], V (M0 M1, S) factor-0-major, omega (R, D0 + D1), phase (R), amp (R, S)
-        and, optional, shift.  Sizes and shapes are checked here, before the library is touched."""
+        and, optional, shift and kinds (a kernel name for both factors or a pair (kind0, kind1); default 'rbf').  Sizes and shapes are checked here, before the library is touched."""
         from . import pathwise
         D0, D1 = dims
         if len(lats) not in (1, 2):
@@ -843,6 +912,8 @@ class DenseEngine:
                     raise ValueError('latent %d: %s must be %s, not %s' % (h, k, shape, arr[k].shape))
             r = recs[h]
             r.M0, r.M1, r.R = M0, M1, R
+            k0, k1 = pathwise.kron_kinds(q.get('kinds', 'rbf'))      # the factor kinds of this latent's record: a name or a pair
+            r.reserved = k0 + 4 * k1                                    # the record's fourth word carries the kinds (include/zigp_kronpaths.h)
             r.var0, r.var1, r.shift = _scalar(q['var'][0]), _scalar(q['var'][1]), float(q.get('shift', 0.0))
             for k, a in arr.items():
                 setattr(r, k, ptr(a) if a.size else None)
@@ -879,8 +950,9 @@ class DenseEngine:
         return out
 
     @staticmethod
-    def _kron_path_draws(s, dims, tags, n_samples, n_features, rng, draws):
-        """(draws dict, the zigp_path_draw records by tag, the arrays behind them) for the packed Kronecker parameters s"""
+    def _kron_path_draws(s, dims, tags, n_samples, n_features, rng, draws, kinds=None):
+        """(draws dict, the zigp_path_draw records by tag, the arrays behind them) for the packed Kronecker parameters s; kinds: the
+        factor kinds by tag (kron_kernel_kinds), which decide the spectral law of each factor's frequencies"""
         from . import pathwise
         S, D = int(n_samples), dims[0] + dims[1]
         grids = {t: (int(getattr(s, 'M0' + t)), int(getattr(s, 'M1' + t))) for t in tags}
@@ -891,7 +963,8 @@ class DenseEngine:
                 rng = np.random.RandomState()
             elif isinstance(rng, (int, np.integer)):
                 rng = np.random.RandomState(int(rng))
-            draws = {t: pathwise.draw('rbf', int(n_features), D, grids[t][0] * grids[t][1], S, rng) for t in tags}
+            kinds = kinds or {}
+            draws = {t: pathwise.kron_draw(kinds.get(t, (0, 0)), int(n_features), dims[0], dims[1], grids[t][0], grids[t][1], S, rng) for t in tags}
         recs, keep = {}, []
         for t in tags:
             R, arr = pathwise.check_draw(draws[t], t, grids[t][0] * grids[t][1], D, S)
@@ -923,8 +996,9 @@ class DenseEngine:
         (zigp_kron_sample_paths): returns dict(f, g, gf: (S, N) each; draws).  p as kron_predict reads it; rng, draws as sample_paths
         (a draw has omega0 (R, D0 + D1) and eps (M0 M1, S)).  D0 + D1 <= 8, grids of at most 128 x 128, 1 <= n_samples <= 256."""
         s, keep, dims = self._pack_kron(p)
+        self._set_kron_kinds(p)
         Xnew = self._kron_rows(Xnew, dims, 'Xnew')
-        draws, recs, keepd = self._kron_path_draws(s, dims, ('f', 'g'), n_samples, n_features, rng, draws)
+        draws, recs, keepd = self._kron_path_draws(s, dims, ('f', 'g'), n_samples, n_features, rng, draws, kron_kernel_kinds(p, ('f', 'g')))
         S, N = int(n_samples), Xnew.shape[0]
         out = np.zeros((3, S, N))
         _check(self.lib, self.ctx, self.lib.zigp_kron_sample_paths(self.ctx, C.byref(s), ptr(Xnew), N, float(jitter), float(g_offset),
@@ -937,8 +1011,9 @@ class DenseEngine:
         """kron_sample_paths on a torch CUDA float64 tensor (N, D0 + D1) of the engine's device: f, g, gf are views of one (3, S, N)
         CUDA tensor (`out` when given)."""
         s, keep, dims = self._pack_kron(p)
+        self._set_kron_kinds(p)
         N = self._kron_device_rows('kron_sample_paths_device', X_t, dims)
-        draws, recs, keepd = self._kron_path_draws(s, dims, ('f', 'g'), n_samples, n_features, rng, draws)
+        draws, recs, keepd = self._kron_path_draws(s, dims, ('f', 'g'), n_samples, n_features, rng, draws, kron_kernel_kinds(p, ('f', 'g')))
         S = int(n_samples)
         out = self._kron_paths_out('kron_sample_paths_device', X_t, 3, S, out)
         if N:
@@ -958,8 +1033,9 @@ class DenseEngine:
         for 'bernoulli' (p = the probit link of f with the reference's 1e-3 clamp).  p holds the f fields only; f already carries f_mu."""
         code = self._head_lik('kron_head_sample_paths', lik)
         s, keep, dims = self._pack_kron(p, tags=('f',))
+        self._set_kron_kinds(p, ('f',))
         Xnew = self._kron_rows(Xnew, dims, 'Xnew')
-        draws, recs, keepd = self._kron_path_draws(s, dims, ('f',), n_samples, n_features, rng, draws)
+        draws, recs, keepd = self._kron_path_draws(s, dims, ('f',), n_samples, n_features, rng, draws, kron_kernel_kinds(p, ('f',)))
         S, N, planes = int(n_samples), Xnew.shape[0], 2 if lik == 'bernoulli' else 1
         out = np.zeros((planes, S, N))
         _check(self.lib, self.ctx, self.lib.zigp_kron_head_sample_paths(self.ctx, C.byref(s), code, ptr(Xnew), N, float(jitter), _scalar(f_mu),
@@ -973,8 +1049,9 @@ class DenseEngine:
         """kron_head_sample_paths on a torch CUDA float64 tensor of the engine's device: views of one (1 or 2, S, N) CUDA tensor."""
         code = self._head_lik('kron_head_sample_paths_device', lik)
         s, keep, dims = self._pack_kron(p, tags=('f',))
+        self._set_kron_kinds(p, ('f',))
         N = self._kron_device_rows('kron_head_sample_paths_device', X_t, dims)
-        draws, recs, keepd = self._kron_path_draws(s, dims, ('f',), n_samples, n_features, rng, draws)
+        draws, recs, keepd = self._kron_path_draws(s, dims, ('f',), n_samples, n_features, rng, draws, kron_kernel_kinds(p, ('f',)))
         S, planes = int(n_samples), 2 if lik == 'bernoulli' else 1
         out = self._kron_paths_out('kron_head_sample_paths_device', X_t, planes, S, out)
         if N:
@@ -1314,6 +1391,7 @@ class DenseEngine:
         scripts/onoff.py:377-381 feeds it, or rows=(lo, hi) of the resident data set (set_data / set_data_device).
         f_mu: the optional constant added to fmean (scripts/onoff.py:161,168-169); when given, grads['f_mu'] is its gradient."""
         s, keep, dims = self._pack_kron(p)
+        self._set_kron_kinds(p)
         X, Y = self._kron_xy(X, Y, rows, dims)
         ed, kl, dmu = C.c_double(0), C.c_double(0), C.c_double(0)
         fmu = 0.0 if f_mu is None else _scalar(f_mu)
@@ -1364,6 +1442,7 @@ class DenseEngine:
         order of include/zigp.h (per latent Z0, Z1, u, s, ell0, ell1, var0, var1; then the noise variance); lr, positive: 17 per-block
         learning rates / Log1pe flags; t0: iterations done so far; row_begin[i] >= 0: rows of the resident data set, -(1 + k): batch k of
         the host arrays (Xw, Yw).  Returns (elbo_data[n], kl[n]) -- the history, each at the parameters before that step's update."""
+        self._kron_fit_kinds('kron_fit_steps', shape, ('f', 'g'))
         s = _lib.zigp_kron_params()
         for k in ('M0f', 'M1f', 'M0g', 'M1g', 'D0', 'D1'):
             setattr(s, k, int(shape[k]))
@@ -1383,6 +1462,7 @@ class DenseEngine:
     def kron_predict(self, p, Xnew, jitter=1e-6, g_offset=0.0, f_mu=None):
         """(9,N) in the order of build_predict (scripts/onoff.py:184); onofftf/onoffpred.py uses jitter 1e-6, g_offset -1."""
         s, keep, dims = self._pack_kron(p)
+        self._set_kron_kinds(p)
         Xnew = self._kron_rows(Xnew, dims, 'Xnew')
         out = np.zeros((9, Xnew.shape[0]))
         _check(self.lib, self.ctx, self.lib.zigp_kron_predict(self.ctx, C.byref(s), ptr(Xnew), Xnew.shape[0], float(jitter),
@@ -1397,6 +1477,7 @@ class DenseEngine:
         minibatch (X, Y) or rows=(lo, hi) of the resident data set (set_data / set_data_device; zigp_kron_head_elbo_rows).
         Returns (elbo_data, kl, grads or None); grads has the f keys, 'noise' and 'f_mu'."""
         s, keep, dims = self._pack_kron(p, tags=('f',))
+        self._set_kron_kinds(p, ('f',))
         X, Y = self._kron_xy(X, Y, rows, dims)
         ed, kl, dmu = C.c_double(0), C.c_double(0), C.c_double(0)
         gs, a = None, None
@@ -1431,6 +1512,7 @@ class DenseEngine:
         return value (elbo_data[n], kl[n]) as kron_fit_steps; so are the exceptions, and what NotPositiveDefiniteError carries."""
         if lik not in self.LIK:
             raise ValueError("kron_head_fit_steps: lik must be 'gaussian' or 'bernoulli', not %r (the on/off fit is kron_fit_steps)" % (lik,))
+        self._kron_fit_kinds('kron_head_fit_steps', shape, ('f',))
         s = _lib.zigp_kron_params()
         for k in ('M0f', 'M1f', 'D0', 'D1'):
             setattr(s, k, int(shape[k]))
@@ -1444,6 +1526,7 @@ class DenseEngine:
     def kron_head_predict(self, p, Xnew, lik, jitter=1e-6, f_mu=0.0):
         """(4,N): fmean, fvar, pfmean, pfvar (onofftf/svgppred.py:180-186, onofftf/svcppred.py 'pfmean'/'pfvar')."""
         s, keep, dims = self._pack_kron(p, tags=('f',))
+        self._set_kron_kinds(p, ('f',))
         Xnew = self._kron_rows(Xnew, dims, 'Xnew')
         out = np.zeros((4, Xnew.shape[0]))
         _check(self.lib, self.ctx, self.lib.zigp_kron_head_predict(self.ctx, C.byref(s), self.LIK[lik], ptr(Xnew), Xnew.shape[0],
@@ -1824,6 +1907,35 @@ class DenseEngine:
         ell = as_f64(np.broadcast_to(np.asarray(ell, dtype=np.float64), (D,)))
         out = np.zeros(((M + 127) // 128 * 128, int(Nc)))
         _check(self.lib, self.ctx, self.lib.zigp_test_kron_kbuild(self.ctx, N, int(Nc), ldx, int(col0), M, D, ptr(X), ptr(Z), ptr(ell), float(var), ptr(out)))
+        return out
+
+    def test_kron_panel_kbuild_kind(self, kind, X, col0, Z, ell, var, Nc, grad=True):
+        """The factor panel of the kind 'rbf' / 'matern32' / 'matern52' (zigp_test_kron_kbuild_kind): (K, K') -- K' None with grad=False --
+        as test_kron_panel_kbuild returns K: the whole padded (Mq, Nc) panels."""
+        X, Z = as_f64(X), as_f64(Z)
+        if X.ndim == 1: X = X[:, None]
+        if Z.ndim == 1: Z = Z[:, None]
+        (N, ldx), (M, D) = X.shape, Z.shape
+        ell = as_f64(np.broadcast_to(np.asarray(ell, dtype=np.float64), (D,)))
+        Mq = (M + 127) // 128 * 128
+        K, Kd = np.zeros((Mq, int(Nc))), (np.zeros((Mq, int(Nc))) if grad else None)
+        _check(self.lib, self.ctx, self.lib.zigp_test_kron_kbuild_kind(self.ctx, _lib.KERNELS[kind], N, int(Nc), ldx, int(col0), M, D, ptr(X), ptr(Z),
+                                                                       ptr(ell), float(var), ptr(K), ptr(Kd) if grad else None))
+        return K, Kd
+
+    def test_kron_panel_kgrad_kind(self, kind, B, A, PdA, K, Kd, gm, dq, X, col0, Z, krow=None):
+        """The factor cotangent of the kind (zigp_test_kron_kgrad_kind): test_kron_panel_kgrad with the derivative panel Kd (M, Nc)."""
+        X, Z = as_f64(X), as_f64(Z)
+        if X.ndim == 1: X = X[:, None]
+        if Z.ndim == 1: Z = Z[:, None]
+        (N, ldx), (M, D) = X.shape, Z.shape
+        K = as_f64(K)
+        Nc = K.shape[1]
+        B, A, PdA, K, Kd = (as_f64(x, (M, Nc)) for x in (B, A, PdA, K, Kd))
+        gm, dq = as_f64(gm, (Nc,)), as_f64(dq, (Nc,))
+        out = np.zeros((M, 2 + 2 * D)) if krow is None else np.array(as_f64(krow, (M, 2 + 2 * D)), copy=True)
+        _check(self.lib, self.ctx, self.lib.zigp_test_kron_kgrad_kind(self.ctx, _lib.KERNELS[kind], M, D, N, Nc, ldx, int(col0), ptr(B), ptr(A),
+                                                                      ptr(PdA), ptr(K), ptr(Kd), ptr(gm), ptr(dq), ptr(X), ptr(Z), ptr(out)))
         return out
 
     def test_kron_panel_colsum(self, K0, A0, K1, A1, B1, A0sq, C1):

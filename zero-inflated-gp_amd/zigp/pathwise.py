@@ -111,6 +111,34 @@ def check_kron_sizes(D0, D1, M0, M1, S):
         raise ValueError('S = %d: a call draws 1 .. %d sample paths (ZIGP_PATH_MAX_S)' % (S, _lib.PATH_MAX_S))
 
 
+def kron_kinds(kinds):
+    """(kind0, kind1) as ZIGP_KERN_* values from a name or kind (both factors) or a pair of them"""
+    if isinstance(kinds, (str, int, np.integer)):
+        kinds = (kinds, kinds)
+    if len(kinds) != 2:
+        raise ValueError('the kinds of a Kronecker latent are a name or a pair (kind0, kind1), not %r' % (kinds,))
+    return _kind(kinds[0]), _kind(kinds[1])
+
+
+def kron_draw(kinds, R, D0, D1, M0, M1, S, rng):
+    """The draw of one Kronecker latent whose factors have the kinds (kind0, kind1): the dict of draw() with omega0 (R, D0 + D1) and
+    eps (M0 M1, S).  The spectral density of a product kernel is the product of the factors' densities, so the omega0 columns of factor
+    q follow that factor's law: z ~ N(0, I) for RBF, z sqrt(2 nu / chi2_{2 nu}) with ONE chi2 per feature and per Matern factor (factor
+    0 first).  With both kinds RBF the generator is consumed exactly as by draw('rbf', R, D0 + D1, M0 M1, S, rng)."""
+    k = kron_kinds(kinds)
+    check_kron_sizes(D0, D1, M0, M1, S)
+    if R < 0:
+        raise ValueError('R = %d must be >= 0' % R)
+    z = rng.standard_normal((R, D0 + D1))
+    for q, cols in ((0, slice(0, D0)), (1, slice(D0, D0 + D1))):
+        if k[q] in MATERN_NU:
+            nu = MATERN_NU[k[q]]
+            z[:, cols] *= np.sqrt(2.0 * nu / rng.chisquare(2.0 * nu, size=(R, 1)))
+    phase = rng.uniform(0.0, 2.0 * np.pi, size=R)
+    return dict(R=int(R), omega0=as_f64(z), phase=as_f64(phase), a=as_f64(rng.standard_normal((R, S))),
+                eps=as_f64(rng.standard_normal((M0 * M1, S))))
+
+
 def kron_weights_np(K0, K1, u_m, q_sqrt, eps, fZ):
     """V (M0 M1, S), factor-0-major, with  (k0(x, Z0) (x) k1(x, Z1)) V = k(x, Z) (K0 (x) K1)^-1 (u - f_Z),  u = u_m + s o eps the draw of
     q(u) behind eps:  V_s = K0^-1 (U + S o E_s - F_Z,s) K1^-1 as M0 x M1 matrices, by the Cholesky factor of each K_p (jitter included
