@@ -355,6 +355,16 @@ int zigp_get_kernel(zigp_ctx* ctx, int32_t latent);
  * zigp_get_kron_kernel returns the kind, or ZIGP_EARG. */
 int zigp_set_kron_kernel(zigp_ctx* ctx, int32_t latent /* 0 f, 1 g */, int32_t factor /* 0, 1 */, int32_t kind /* ZIGP_KERN_* */);
 int zigp_get_kron_kernel(zigp_ctx* ctx, int32_t latent, int32_t factor);
+/* Matern factors on the FUSED Kronecker kernels: opt-in context state, 0 after zigp_create.  With it off nothing changes: a call with a
+ * Matern factor runs on the GEMM panels, and the fit loops refuse it, as described above.  With it on, a call with a Matern factor goes to
+ * the fused register-resident kernels when zigp_set_kron_panels is off and its grid is one they cover (<= 32 x <= 32 or <= 16 x <= 112
+ * points, D0, D1 <= 7) -- the Matern instantiations of those kernels, launched only for such a call -- and zigp_kron_fit_steps /
+ * zigp_kron_head_fit_steps accept Matern factors (the kinds are fixed for the call).  Every other case routes as with the switch off:
+ * zigp_set_kron_panels(1) still wins, a grid beyond the fused kernels stays on the panels, and a call whose four factors are RBF launches
+ * what it always launched and returns the same bits.  ZIGP_EARG, naming the argument: a NULL context, on outside {0, 1}.
+ * zigp_get_kron_matern_fused returns the setting, or ZIGP_EARG for a NULL context. */
+int zigp_set_kron_matern_fused(zigp_ctx* ctx, int32_t on);
+int zigp_get_kron_matern_fused(zigp_ctx* ctx);
 /* Kernel matrices of any of the three kinds (gpflow kernels.Stationary.K -> RBF.K / Matern32.K / Matern52.K; zigp_rbf_K is the RBF
  * one and stays as it is): K (n1,n2) = k(X1, X2) as above, no jitter.  X2 == NULL -> X1 (the diagonal is then the formula at r = 1e-6
  * for the Matern kinds).  Argument conventions of zigp_rbf_K; 1 <= D <= ZIGP_MAX_D for ZIGP_KERN_RBF, D <= 8 for the Matern kinds. */

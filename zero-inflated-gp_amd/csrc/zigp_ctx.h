@@ -176,7 +176,8 @@ struct zigp_ctx : zigp::CtxHandles {
   std::unique_ptr<zigp::KronState> kron;
   std::unique_ptr<zigp::KfState> kronf;
   bool kron_panels = false;             // zigp_set_kron_panels: force the panel (GEMM-core) Kronecker path
-  int kron_kern[2][2] = {{0, 0}, {0, 0}};   // zigp_set_kron_kernel: ZIGP_KERN_* of [latent f, g][factor 0, 1]; any Matern factor routes a call to the panel path
+  int kron_kern[2][2] = {{0, 0}, {0, 0}};   // zigp_set_kron_kernel: ZIGP_KERN_* of [latent f, g][factor 0, 1]; any Matern factor routes a call to the panel path ...
+  bool kron_matern_fused = false;       // ... unless zigp_set_kron_matern_fused is on: then a fused-eligible grid runs the _kinds kernels of zigp_kronf.hip
   int kron_range_tiles = 1024;          // larger-grid fused backward: rows go through in ranges of this many 16-point tiles (bounded operand spill; zigp_set_kron_range_tiles)
   std::map<std::string, zigp::CachedTiles> tiles;   // tile lists by key (get_tiles, zigp_host.h); kept until zigp_destroy (bound: chunk_plan)
   // data-parallel exchange (zigp_comm_init): RCCL communicator, one rank per context / GPU

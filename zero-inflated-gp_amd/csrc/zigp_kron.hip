@@ -724,10 +724,15 @@ int kron_exchange_host(zigp_ctx* c, const KronCall& k) {
   return 0;
 }
 
-// small grids go through the fused register-resident kernels (zigp_kronf.hip); larger factors, and every call with a Matern factor
-// (zigp_set_kron_kernel: the fused kernels are RBF only), through the panel path below
+// Does a call with these factor kinds run on the fused kernels?  RBF factors: always (given the grid, and zigp_set_kron_panels off);
+// a Matern factor: only with zigp_set_kron_matern_fused on (the _kinds kernels of zigp_kronf.hip; off by default)
+static bool kron_kinds_fused(const zigp_ctx* c, const KronHostLatent* hl, int nlat) {
+  return c->kron_matern_fused || kron_matern_factor(hl, nlat).empty();
+}
+// small grids go through the fused register-resident kernels (zigp_kronf.hip); larger factors, and (unless zigp_set_kron_matern_fused
+// is on) every call with a Matern factor (zigp_set_kron_kernel), through the panel path below
 int kron_run(zigp_ctx* c, const KronCall& k) {
-  if (!c->kron_panels && kf_eligible(k.p, k.nlat) && kron_matern_factor(k.hl, k.nlat).empty()) return kronf_run(c, k);
+  if (!c->kron_panels && kf_eligible(k.p, k.nlat) && kron_kinds_fused(c, k.hl, k.nlat)) return kronf_run(c, k);
   return kron_run_panels(c, k);
 }
 
@@ -934,7 +939,7 @@ int kron_fit_entry(zigp_ctx* c, const char* name, const char* rows_entry, const 
     KronHostLatent kinds[2] = {};
     kron_set_kinds(c, kinds, head ? 1 : 2);
     const std::string who = kron_matern_factor(kinds, head ? 1 : 2);
-    if (!who.empty())
+    if (!who.empty() && !c->kron_matern_fused)
       return kron_refuse(c, name, "a " + who + " is set (zigp_set_kron_kernel); the device loop fits RBF factors only: step it with " + rows_entry +
                                       " and a host optimiser");
   }
@@ -958,6 +963,7 @@ int kron_fit_entry(zigp_ctx* c, const char* name, const char* rows_entry, const 
   fit.beta1 = opts->beta1; fit.beta2 = opts->beta2; fit.eps = opts->eps;
   k.X = c->dX; k.Y = c->dY; k.N = fit.batch; k.dev_xy = true;      // p carries the sizes only: the parameters come from the free state
   kron_call_derive(k);
+  kron_set_kinds(c, k.hl, k.nlat);      // Matern factors get here with zigp_set_kron_matern_fused only (refused above otherwise)
   k.need_grad = true;
   return kronf_run(c, k, &fit);
 }
@@ -1067,6 +1073,18 @@ int zigp_set_kron_panels(zigp_ctx* c, int32_t on) {
   return ZIGP_OK;
 }
 
+int zigp_set_kron_matern_fused(zigp_ctx* c, int32_t on) {
+  if (!c) return ZIGP_EARG;
+  if (on != 0 && on != 1) return fail_arg(c, "zigp_set_kron_matern_fused: on must be 0 or 1");
+  c->kron_matern_fused = on == 1;
+  return ZIGP_OK;
+}
+
+int zigp_get_kron_matern_fused(zigp_ctx* c) {
+  if (!c) return ZIGP_EARG;
+  return c->kron_matern_fused ? 1 : 0;
+}
+
 }  // extern "C"
 
 // ---- stage diagnostics of the Kronecker path (include/zigp_diag.h): ONE launch of a point-wise or per-point panel kernel on
@@ -1150,7 +1168,7 @@ int zigp_test_kron_fused_step(zigp_ctx* c, const zigp_stage_kron_fused* s) {
   if (s->N < 1 || !s->X || !s->Y || !s->grads || !(s->jitter >= 0)) return fail_arg(c, "zigp_test_kron_fused_step: need N >= 1 rows X, Y, grads and jitter >= 0");
   KronHostLatent kinds[2] = {};
   kron_set_kinds(c, kinds, nlat);
-  if (c->kron_panels || !kf_eligible(s->p, nlat) || !kron_matern_factor(kinds, nlat).empty())
+  if (c->kron_panels || !kf_eligible(s->p, nlat) || !kron_kinds_fused(c, kinds, nlat))
     return fail_arg(c, "zigp_test_kron_fused_step: this step does not run on the fused Kronecker kernels (grid beyond them, or zigp_set_kron_panels)");
   ZIGP_HIP(c, hipSetDevice(c->device));
   KfTap tap;
@@ -1162,6 +1180,7 @@ int zigp_test_kron_fused_step(zigp_ctx* c, const zigp_stage_kron_fused* s) {
   k.p = s->p; k.lik = s->lik; k.X = s->X; k.Y = s->Y; k.N = s->N; k.jitter = s->jitter; k.scale = s->scale; k.g_offset = s->g_offset; k.f_mu = s->f_mu;
   k.include_kl = s->include_kl; k.elbo_data = s->elbo_data; k.kl = s->kl; k.grads = s->grads; k.d_offset = s->d_f_mu;
   kron_call_derive(k);
+  kron_set_kinds(c, k.hl, nlat);
   ZIGP_TRY(kronf_run(c, k, nullptr, &tap));
   return tap.flush(c);
 }

@@ -209,6 +209,73 @@ __device__ __forceinline__ void kf_ktile(double (&K)[Q], const KfFac& f, int nb,
   }
 }
 
+// ---- Matern factors on the fused path (zigp_set_kron_matern_fused): the _kinds kernels ----------------------------------------------
+// The kernels whose names end in _kinds stand beside the RBF kernels and are launched only for a call that has a Matern factor.  Each
+// follows the RBF kernel it was taken from, as a *_kinds_body function, and is that kernel's text with the Matern pieces added.  The text
+// is kept twice on purpose: with the RBF kernels routed through a shared body (a template flag) they compiled to the same instruction
+// counts under another register allocation, and their machine code is pinned (tools/isa_compare.py).  A fix to an RBF point kernel has
+// to be made in its _kinds_body as well.  The _kinds kernels take one more argument, the kinds of the call's
+// four factors packed two bits each (bit 2 (2 h + q): ZIGP_KERN_* of factor q of latent h), so no argument of an RBF kernel moves; the
+// kind of a factor is wave-uniform and read at run time.
+__host__ __device__ inline int kf_kind_of(int kinds, int h, int q) { return (kinds >> (2 * (2 * h + q))) & 3; }
+
+// kf_ktile for a factor of any kind; GRAD also gives Kd = K' = -dk / d(r2 / 2) (K' = K for RBF).  r2 is formed by kf_r2_batch exactly as
+// for RBF (y = -r2 / 2, so -2 y is r2 again, exactly), then kron_matern_elem's arithmetic (zigp_kron.hip): r = sqrt(min(r2, 2^996) + 1e-12),
+// t = sqrt3 r or sqrt5 r, e = exp(-t) through kf_exp_neg, K = var (1 + t) e or var (1 + t + 5/3 r^2) e.  A far pair gives a finite
+// polynomial times e = +0.  An RBF factor takes kf_ktile itself: the same bits as in the RBF instantiation.
+template <int Q, bool SPEC, bool GRAD>
+__device__ __forceinline__ void kf_ktile_kinds(double (&K)[Q], double (&Kd)[Q], int kind, const KfFac& f, int nb, const double* zs,
+                                               const double* __restrict__ xrow, bool valid, int g) {
+  if (kind == KERN_RBF) {
+    kf_ktile<Q, SPEC>(K, f, nb, zs, xrow, valid, g);
+    if (GRAD) {
+#pragma unroll
+      for (int q = 0; q < Q; ++q) Kd[q] = K[q];
+    }
+    return;
+  }
+  double xs[MAXD];
+  const auto inv_ell = KF_CONST(f.hyp) + KH_INV;
+  const double var = KF_CONST(f.hyp)[KH_VAR];
+#pragma unroll
+  for (int d = 0; d < MAXD; ++d) xs[d] = (d < f.D) ? xrow[f.col0 + d] * inv_ell[d] : 0.0;
+  const bool m32 = kind == KERN_M32;
+  const double ca = m32 ? MATERN_SQRT3 : MATERN_SQRT5;
+  constexpr int B = Q < 8 ? Q : 8;
+  const int mlast = 16 * nb - 1;
+#pragma unroll
+  for (int q0 = 0; q0 < Q; q0 += B) {
+    double y[B], r[B], tt[B];
+    if (SPEC) {
+      switch (f.D) {
+        case 1: kf_r2_batch<1, B>(y, f, zs, xs, q0, g, mlast); break;
+        case 2: kf_r2_batch<2, B>(y, f, zs, xs, q0, g, mlast); break;
+        case 3: kf_r2_batch<3, B>(y, f, zs, xs, q0, g, mlast); break;
+        default: kf_r2_batch<0, B>(y, f, zs, xs, q0, g, mlast);
+      }
+    } else {
+      kf_r2_batch<0, B>(y, f, zs, xs, q0, g, mlast);
+    }
+#pragma unroll
+    for (int i = 0; i < B; ++i) {
+      r[i] = sqrt(fmin(-2.0 * y[i], 0x1p+996) + MATERN_FLOOR);
+      tt[i] = ca * r[i];
+      y[i] = -tt[i];
+    }
+    kf_exp_neg<B>(y);
+#pragma unroll
+    for (int i = 0; i < B; ++i)
+      if (q0 + i < Q) {
+        const int m = 4 * (q0 + i) + g;
+        const bool on = m < f.M && m <= mlast && valid;
+        const double p1 = 1.0 + tt[i];
+        const double poly = m32 ? p1 : p1 + (5.0 / 3.0) * (r[i] * r[i]);
+        K[q0 + i] = on ? var * poly * y[i] : 0.0;
+        if (GRAD) Kd[q0 + i] = on ? (m32 ? 3.0 * var * y[i] : (5.0 / 3.0) * var * p1 * y[i]) : 0.0;
+      }
+  }
+}
+
 // sum over the 4 row groups (lanes l, l^16, l^32, l^48): every lane ends with the column total, fixed order
 __device__ __forceinline__ double kf_colsum(double v) {
   v += __shfl_xor(v, 16, 64);
@@ -272,6 +339,15 @@ __device__ __forceinline__ void kf_forward_ktiles(KfTile<NB0, NB1>& t, const KfL
   const int nb0 = EXACT ? NB0 : f0.nb, nb1 = EXACT ? NB1 : f1.nb;
   kf_ktile<4 * NB0, EXACT>(t.K0, f0, nb0, Z0, xrow, valid, g);
   kf_ktile<4 * NB1, EXACT>(t.K1, f1, nb1, Z1, xrow, valid, g);
+}
+// kf_forward_ktiles for factors of any kind: lk = kind0 + 4 kind1 of this latent; GRAD: also the K' tiles
+template <int NB0, int NB1, bool EXACT, bool GRAD>
+__device__ __forceinline__ void kf_ktiles_any(KfTile<NB0, NB1>& t, double (&Kd0)[4 * NB0], double (&Kd1)[4 * NB1], int lk, const KfLat& L, const double* Z0,
+                                              const double* Z1, const double* __restrict__ xrow, bool valid, int g) {
+  const KfFac &f0 = L.f[0], &f1 = L.f[1];
+  const int nb0 = EXACT ? NB0 : f0.nb, nb1 = EXACT ? NB1 : f1.nb;
+  kf_ktile_kinds<4 * NB0, EXACT, GRAD>(t.K0, Kd0, lk & 3, f0, nb0, Z0, xrow, valid, g);
+  kf_ktile_kinds<4 * NB1, EXACT, GRAD>(t.K1, Kd1, lk >> 2, f1, nb1, Z1, xrow, valid, g);
 }
 template <int NB0, int NB1, bool EXACT>
 __device__ __forceinline__ void kf_forward_products(KfTile<NB0, NB1>& t, const KfLat& L, const KfFrags& F, int slot) {
@@ -339,6 +415,56 @@ k_kf_forward(KfArgs a) {
     q0 = kf_colsum(q0); q1 = kf_colsum(q1); mu = kf_colsum(mu); st = kf_colsum(st);
     if (g == 0) { L.part[pn] = q0; L.part[a.Npad + pn] = q1; L.part[2 * a.Npad + pn] = mu; L.part[3 * a.Npad + pn] = st; }
   }
+}
+template <int NB0, int NB1>
+__device__ __forceinline__ void kf_forward_kinds_body(const KfArgs& a, int kinds, double* sfr, double (*sz)[KF_MQ_ * MAXD]) {
+  const KfLat& L = a.lat[a.lat0 + blockIdx.y];
+  const int lk = (kinds >> (4 * (a.lat0 + blockIdx.y))) & 15;
+  double kd0[4 * NB0], kd1[4 * NB1];      // K' is not needed going forward (GRAD = false leaves them unwritten)
+  {
+    constexpr int n0 = NB0 * NB0 * 256, n1 = NB1 * NB1 * 256, n01 = NB0 * NB1 * 256;
+    // asynchronous copies (kf_stage_frag_async): the K tiles of the wave's first tile are computed underneath them, from the global
+    // copy of the scaled inducing inputs (the LDS copy becomes visible with the images, at kf_stage_wait)
+    kf_stage_frag_async(sfr, L.f[0].PF, n0); kf_stage_frag_async(sfr + KF_FRAG, L.f[1].PF, n1);
+    kf_stage_frag_async(sfr + 2 * KF_FRAG, L.AlF, n01); kf_stage_frag_async(sfr + 3 * KF_FRAG, L.S2F, n01);
+    kf_stage_z(sz[0], L.f[0]); kf_stage_z(sz[1], L.f[1]);
+  }
+  const KfFrags F = {sfr, sfr + KF_FRAG, sfr + 2 * KF_FRAG, sfr + 3 * KF_FRAG, nullptr, nullptr, sz[0], sz[1]};
+  const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15, slot = lane;      // slot: this lane's position in a fragment block
+  const int w = blockIdx.x * KF_WAVES + (threadIdx.x >> 6);
+  const int t1 = min((w + 1) * a.tpw, a.ntiles);
+  KfTile<NB0, NB1> t;
+  bool first = true;
+  if (w * a.tpw < t1) {
+    const int64_t pn = (int64_t)(w * a.tpw) * 16 + n;
+    kf_ktiles_any<NB0, NB1, true, false>(t, kd0, kd1, lk, L, L.f[0].Zs, L.f[1].Zs, a.X + (pn < a.N ? pn : 0) * a.ldx, pn < a.N, g);
+  }
+  kf_stage_wait();
+  for (int tile = w * a.tpw; tile < t1; ++tile) {
+    const int64_t pn = (int64_t)tile * 16 + n;
+    const bool valid = pn < a.N;
+    if (!first) kf_ktiles_any<NB0, NB1, true, false>(t, kd0, kd1, lk, L, F.Z0, F.Z1, a.X + (valid ? pn : 0) * a.ldx, valid, g);
+    first = false;
+    kf_forward_products<NB0, NB1, true>(t, L, F, slot);
+    double q0 = 0.0, q1 = 0.0, mu = 0.0, st = 0.0;
+#pragma unroll
+    for (int q = 0; q < 4 * NB0; ++q) {
+      q0 = fma(t.K0[q], t.A0[q], q0);
+      mu = fma(t.K0[q], t.B0[q], mu);
+      st = fma(t.A0[q] * t.A0[q], t.C0[q], st);
+    }
+#pragma unroll
+    for (int q = 0; q < 4 * NB1; ++q) q1 = fma(t.K1[q], t.A1[q], q1);
+    q0 = kf_colsum(q0); q1 = kf_colsum(q1); mu = kf_colsum(mu); st = kf_colsum(st);
+    if (g == 0) { L.part[pn] = q0; L.part[a.Npad + pn] = q1; L.part[2 * a.Npad + pn] = mu; L.part[3 * a.Npad + pn] = st; }
+  }
+}
+template <int NB0, int NB1>
+__global__ void __launch_bounds__(64 * KF_WAVES)
+k_kf_forward_kinds(KfArgs a, int kinds) {
+  __shared__ double sfr[4 * KF_FRAG];
+  __shared__ double sz[2][KF_MQ_ * MAXD];
+  kf_forward_kinds_body<NB0, NB1>(a, kinds, sfr, sz);
 }
 
 // tile in registers -> LDS image [row][KF_LD]
@@ -536,6 +662,222 @@ k_kf_backward(KfArgs a) {
 #pragma unroll
     for (int rb = 0; rb < NB1; ++rb) out[((KF_B_K1 + rb) * 4 + r) * 64 + lane] = accK1[rb][r];
   }
+}
+// k_kf_backward_kinds: the moment columns 1 .. 2 D of a Matern factor take t' = dK . K' in place of t = dK . K (column 0, the
+// variance, keeps t).  One MFMA chain has one A operand, so the moments are two chains per factor: t against Psi masked to the columns
+// that take K, then t' against Psi masked to the others; a column gets its products from one chain and exact zeros from the other, so an
+// RBF factor (every column in the first chain, t' = t) ends with the bits of the RBF instantiation.  The second chain of a Matern factor
+// also fills column 15 of its moment block with sum t' (Psi = 1; the column is free, D <= 7 on this path): the finish kernel re-centres
+// the t' moments with it, as it re-centres an RBF factor's with column 0.  K' waits in a lane-private LDS image
+// written with the K tile (kd[q * 64 + lane], 2 * KF_Q * 64 doubles per wave behind the fragment images): the accumulators and the tile
+// state leave no registers for it.
+template <int NB0, int NB1>
+__device__ __forceinline__ void kf_backward_kinds_body(const KfArgs& a, int kinds, double* lds) {
+  const KfLat& L = a.lat[a.lat0 + blockIdx.y];
+  const KfFac &f0 = L.f[0], &f1 = L.f[1];
+  const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15, slot = lane;      // slot: this lane's position in a fragment block
+  const int wib = threadIdx.x >> 6;
+  const int lk = (kinds >> (4 * (a.lat0 + blockIdx.y))) & 15;
+  const int w = blockIdx.x * KF_WAVES + wib;
+  constexpr int Q0 = 4 * NB0, Q1 = 4 * NB1;
+  constexpr int TILE = 16 * KF_NBMAX * KF_LD;
+  double* bK0 = lds + wib * 4 * TILE; double* bK1 = bK0 + TILE; double* c0 = bK1 + TILE; double* c1 = c0 + TILE;
+  double* sfr = lds + KF_WAVES * 4 * TILE;
+  {
+    constexpr int n0 = NB0 * NB0 * 256, n1 = NB1 * NB1 * 256, n01 = NB0 * NB1 * 256;
+    kf_stage_frag_async(sfr, f0.PF, n0); kf_stage_frag_async(sfr + KF_FRAG, f1.PF, n1);
+    kf_stage_frag_async(sfr + 2 * KF_FRAG, L.AlF, n01); kf_stage_frag_async(sfr + 3 * KF_FRAG, L.S2F, n01);
+    kf_stage_frag_async(sfr + 4 * KF_FRAG, L.AlTF, n01); kf_stage_frag_async(sfr + 5 * KF_FRAG, L.S2TF, n01);
+    kf_stage_z(sfr + 6 * KF_FRAG, f0); kf_stage_z(sfr + 6 * KF_FRAG + KF_MQ_ * MAXD, f1);
+  }
+  const KfFrags F = {sfr, sfr + KF_FRAG, sfr + 2 * KF_FRAG, sfr + 3 * KF_FRAG, sfr + 4 * KF_FRAG, sfr + 5 * KF_FRAG,
+                     sfr + 6 * KF_FRAG, sfr + 6 * KF_FRAG + KF_MQ_ * MAXD};
+  double accAl[NB0 * NB1][4], accS2[NB0 * NB1][4], accP0[NB0 * NB0][4], accP1[NB1 * NB1][4], accK0[NB0][4], accK1[NB1][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+#pragma unroll
+    for (int b = 0; b < NB0 * NB1; ++b) { accAl[b][r] = 0.0; accS2[b][r] = 0.0; }
+#pragma unroll
+    for (int b = 0; b < NB0 * NB0; ++b) accP0[b][r] = 0.0;
+#pragma unroll
+    for (int b = 0; b < NB1 * NB1; ++b) accP1[b][r] = 0.0;
+#pragma unroll
+    for (int b = 0; b < NB0; ++b) accK0[b][r] = 0.0;
+#pragma unroll
+    for (int b = 0; b < NB1; ++b) accK1[b][r] = 0.0;
+  }
+  const double one4[4] = {1.0, 1.0, 1.0, 1.0};
+  // column j = n of the moment matrix Psi_p: 0 -> 1, 1..D -> x_d - zc_d, D+1..2D -> (x_d - zc_d)^2, beyond -> 0   (fixed per lane)
+  int psi_kind[2], psi_col[2]; double psi_zc[2];
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const KfFac& f = L.f[p];
+    const int d = (n == 0) ? 0 : ((n <= f.D) ? n - 1 : ((n <= 2 * f.D) ? n - 1 - f.D : 0));
+    psi_kind[p] = (n == 0) ? 0 : ((n <= f.D) ? 1 : ((n <= 2 * f.D) ? 2 : 3));
+    // a Matern factor: column 15 (free: D <= 7 on this path) is the constant 1 again, in the SECOND chain -- sum t', which the finish
+    // kernel needs to re-centre the t' moments around z_m (column 0 is sum t)
+    if (n == 15 && ((lk >> (2 * p)) & 3) != KERN_RBF) psi_kind[p] = 0;
+    psi_col[p] = f.col0 + d; psi_zc[p] = KF_CONST(f.hyp)[KH_ZC + d];
+  }
+
+  const int t1 = min((w + 1) * a.tpw, a.ntiles);
+  KfTile<NB0, NB1> t;
+  // this lane's K' values of the tile, factor 0 then factor 1 (written and read by the same lane: no synchronisation)
+  double* const kdl = lds + KF_WAVES * 4 * TILE + 6 * KF_FRAG + 2 * KF_MQ_ * MAXD + wib * 2 * KF_Q * 64 + lane;
+  bool first = true;
+  if (w * a.tpw < t1) {          // K tiles of the first tile under the asynchronous staging copies (global copy of the inducing inputs)
+    const int64_t pn = (int64_t)(w * a.tpw) * 16 + n;
+    double kd0[Q0], kd1[Q1];
+    kf_ktiles_any<NB0, NB1, true, true>(t, kd0, kd1, lk, L, f0.Zs, f1.Zs, a.X + (pn < a.N ? pn : 0) * a.ldx, pn < a.N, g);
+    {
+#pragma unroll
+      for (int q = 0; q < Q0; ++q) kdl[q * 64] = kd0[q];
+#pragma unroll
+      for (int q = 0; q < Q1; ++q) kdl[(KF_Q + q) * 64] = kd1[q];
+    }
+  }
+  kf_stage_wait();
+  for (int tile = w * a.tpw; tile < t1; ++tile) {
+    const int64_t pn = (int64_t)tile * 16 + n;
+    const bool valid = pn < a.N;
+    const double* xrow = a.X + (valid ? pn : 0) * a.ldx;
+    if (!first) {
+      double kd0[Q0], kd1[Q1];
+      kf_ktiles_any<NB0, NB1, true, true>(t, kd0, kd1, lk, L, F.Z0, F.Z1, xrow, valid, g);
+      {
+#pragma unroll
+        for (int q = 0; q < Q0; ++q) kdl[q * 64] = kd0[q];
+#pragma unroll
+        for (int q = 0; q < Q1; ++q) kdl[(KF_Q + q) * 64] = kd1[q];
+      }
+    }
+    first = false;
+    kf_forward_products<NB0, NB1, true>(t, L, F, slot);
+    const double gmn = L.gm[pn], gvn = L.gv[pn], dq0n = L.dq0[pn], dq1n = L.dq1[pn];   // zero for padding points (scale 0 in the point-wise kernel)
+    double B1[Q1], C1[Q1], sq[Q0];
+#pragma unroll
+    for (int q = 0; q < Q1; ++q) { B1[q] = 0.0; C1[q] = 0.0; }
+#pragma unroll
+    for (int q = 0; q < Q0; ++q) sq[q] = t.A0[q] * t.A0[q];
+    kf_frag_mm<NB1, Q0>(B1, F.AlT, NB1, Q0, t.K0, slot);
+    kf_frag_mm<NB1, Q0>(C1, F.S2T, NB1, Q0, sq, slot);
+    double dA0[Q0], dA1[Q1], PdA0[Q0], PdA1[Q1];
+#pragma unroll
+    for (int q = 0; q < Q0; ++q) { dA0[q] = 2.0 * gvn * t.A0[q] * t.C0[q]; PdA0[q] = 0.0; }
+#pragma unroll
+    for (int q = 0; q < Q1; ++q) { dA1[q] = 2.0 * gvn * t.A1[q] * C1[q]; PdA1[q] = 0.0; }
+    kf_frag_mm<NB0, Q0>(PdA0, F.P0, NB0, Q0, dA0, slot);
+    kf_frag_mm<NB1, Q1>(PdA1, F.P1, NB1, Q1, dA1, slot);
+    // ---- LDS images for the sums over points (k index = point): K tiles, E tiles
+    kf_store_tile<Q0>(bK0, t.K0, g, n);
+    kf_store_tile<Q1>(bK1, t.K1, g, n);
+    {
+      double E0[Q0], E1[Q1];
+#pragma unroll
+      for (int q = 0; q < Q0; ++q) E0[q] = fma(dq0n, t.K0[q], dA0[q]);
+      kf_store_tile<Q0>(c0, E0, g, n);
+#pragma unroll
+      for (int q = 0; q < Q1; ++q) E1[q] = fma(dq1n, t.K1[q], dA1[q]);
+      kf_store_tile<Q1>(c1, E1, g, n);
+    }
+    kf_wave_sync();
+    double gmk[4], gvk[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) { gmk[ks] = __shfl(gmn, 4 * ks + g, 64); gvk[ks] = __shfl(gvn, 4 * ks + g, 64); }
+    kf_accum<NB0, NB1, 0, true>(accAl, bK0, bK1, gmk, lane);
+    kf_accum<NB0, NB0, 0, false>(accP0, c0, bK0, one4, lane);
+    kf_accum<NB1, NB1, 0, false>(accP1, c1, bK1, one4, lane);
+    kf_wave_sync();
+    // B operand of the moment products: lane (kk = g, column j = n) needs psi_j of point 4 ks + g -- loaded here (most of the tile state
+    // is dead by now), the round trip hides behind the dS2 products
+    double psi[2][4];
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        // selects, not branches: the eight loads go out back to back (one round trip, not eight)
+        const int64_t pt = (int64_t)tile * 16 + 4 * ks + g;
+        const double xv = a.X[(pt < a.N ? pt : 0) * a.ldx + psi_col[p]] - psi_zc[p];
+        const double v = psi_kind[p] == 0 ? 1.0 : (psi_kind[p] == 1 ? xv : (psi_kind[p] == 2 ? xv * xv : 0.0));
+        psi[p][ks] = (pt < a.N) ? v : 0.0;
+      }
+    kf_store_tile<Q0>(c0, t.A0, g, n);
+    kf_store_tile<Q1>(c1, t.A1, g, n);
+    kf_wave_sync();
+    kf_accum<NB0, NB1, 1, true>(accS2, c0, c1, gvk, lane);
+    kf_wave_sync();
+    {
+      double t0[Q0], t1v[Q1];
+#pragma unroll
+      for (int q = 0; q < Q0; ++q) t0[q] = fma(gmn, t.B0[q], fma(2.0 * dq0n, t.A0[q], PdA0[q])) * t.K0[q];
+      kf_store_tile<Q0>(c0, t0, g, n);
+#pragma unroll
+      for (int q = 0; q < Q1; ++q) t1v[q] = fma(gmn, B1[q], fma(2.0 * dq1n, t.A1[q], PdA1[q])) * t.K1[q];
+      kf_store_tile<Q1>(c1, t1v, g, n);
+    }
+    kf_wave_sync();
+    // moments: acc(rows of factor p, col j) += sum_n t_p[row, n] psi_j(x_n),  psi = {1, xc_d, xc_d^2}
+    // (the columns of this chain -- all of an RBF factor, column 0 of a Matern one)
+    const bool first0 = (lk & 3) == KERN_RBF || n == 0, first1 = (lk >> 2) == KERN_RBF || n == 0;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+#pragma unroll
+      for (int rb = 0; rb < NB0; ++rb) kf_mfma16(accK0[rb], c0[(16 * rb + n) * KF_LD + 4 * ks + g], first0 ? psi[0][ks] : 0.0);
+#pragma unroll
+      for (int rb = 0; rb < NB1; ++rb) kf_mfma16(accK1[rb], c1[(16 * rb + n) * KF_LD + 4 * ks + g], first1 ? psi[1][ks] : 0.0);
+    }
+    kf_wave_sync();
+    if (lk != 0) {      // the second chain: t' = dK . K' against the remaining columns (wave-uniform: the latent has a Matern factor)
+      {
+        double t0[Q0], t1v[Q1];
+#pragma unroll
+        for (int q = 0; q < Q0; ++q) t0[q] = fma(gmn, t.B0[q], fma(2.0 * dq0n, t.A0[q], PdA0[q])) * kdl[q * 64];
+        kf_store_tile<Q0>(c0, t0, g, n);
+#pragma unroll
+        for (int q = 0; q < Q1; ++q) t1v[q] = fma(gmn, B1[q], fma(2.0 * dq1n, t.A1[q], PdA1[q])) * kdl[(KF_Q + q) * 64];
+        kf_store_tile<Q1>(c1, t1v, g, n);
+      }
+      kf_wave_sync();
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+#pragma unroll
+        for (int rb = 0; rb < NB0; ++rb) kf_mfma16(accK0[rb], c0[(16 * rb + n) * KF_LD + 4 * ks + g], first0 ? 0.0 : psi[0][ks]);
+#pragma unroll
+        for (int rb = 0; rb < NB1; ++rb) kf_mfma16(accK1[rb], c1[(16 * rb + n) * KF_LD + 4 * ks + g], first1 ? 0.0 : psi[1][ks]);
+      }
+      kf_wave_sync();
+    }
+  }
+  // per-wave partials, [block][r][lane]; blocks numbered for the CAPACITY grid (KF_NBMAX x KF_NBMAX) that k_kf_reduce / k_kf_finish index
+  double* out = L.acc + (int64_t)w * KF_ACC_DOUBLES;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+#pragma unroll
+    for (int rb = 0; rb < NB0; ++rb)
+#pragma unroll
+      for (int cb = 0; cb < NB1; ++cb) {
+        out[((KF_B_AL + rb * KF_NBMAX + cb) * 4 + r) * 64 + lane] = accAl[rb * NB1 + cb][r];
+        out[((KF_B_S2 + rb * KF_NBMAX + cb) * 4 + r) * 64 + lane] = accS2[rb * NB1 + cb][r];
+      }
+#pragma unroll
+    for (int rb = 0; rb < NB0; ++rb)
+#pragma unroll
+      for (int cb = 0; cb < NB0; ++cb) out[((KF_B_P0 + rb * KF_NBMAX + cb) * 4 + r) * 64 + lane] = accP0[rb * NB0 + cb][r];
+#pragma unroll
+    for (int rb = 0; rb < NB1; ++rb)
+#pragma unroll
+      for (int cb = 0; cb < NB1; ++cb) out[((KF_B_P1 + rb * KF_NBMAX + cb) * 4 + r) * 64 + lane] = accP1[rb * NB1 + cb][r];
+#pragma unroll
+    for (int rb = 0; rb < NB0; ++rb) out[((KF_B_K0 + rb) * 4 + r) * 64 + lane] = accK0[rb][r];
+#pragma unroll
+    for (int rb = 0; rb < NB1; ++rb) out[((KF_B_K1 + rb) * 4 + r) * 64 + lane] = accK1[rb][r];
+  }
+}
+template <int NB0, int NB1>
+__global__ void __launch_bounds__(64 * KF_WAVES, 1)
+k_kf_backward_kinds(KfArgs a, int kinds) {
+  extern __shared__ double lds[];
+  kf_backward_kinds_body<NB0, NB1>(a, kinds, lds);
 }
 
 // ---- fixed-order sum of the partial accumulators; un-permutes the accumulator layout into row-major matrices ------------------
@@ -774,6 +1116,129 @@ k_kf_factor(KfFactorArgs a) {
       }
     }
   }
+}
+// k_kf_factor_kinds: a Matern factor's K_p as k_kron_matern_matrix builds it -- matern_k off the diagonal, the formula at r2 = 0
+// (r = 1e-6) plus jitter on it, identity in the padding; kinds: bit 2 j = the kind of job j.
+__device__ __forceinline__ void kf_factor_kinds_body(const KfFactorArgs& a, int kinds, double* S, PotrfShared& psh, double* red) {
+  const KfFactorJob& jb = a.job[blockIdx.x];
+  const int kind = (kinds >> (2 * blockIdx.x)) & 3;
+  const int t = threadIdx.x, M = jb.M, Mq = jb.Mq, D = jb.D;
+  const auto inv_ell = KF_CONST(jb.hyp) + KH_INV;
+  const double var = KF_CONST(jb.hyp)[KH_VAR];
+  int* const info = a.own_slots ? a.info + 2 * blockIdx.x : a.info;
+  if (a.own_slots && t == 0) { info[0] = 0; info[1] = 0; }       // ordered before the factorisation's atomicCAS by the barriers below
+  // inducing inputs into LDS first (the T tiles are idle until the factorisation): with Z read from global memory inside the loop
+  // every entry of K sat behind two dependent L2 round trips (in-kernel stamps: 23 k cycles for 16 entries per thread).  K is built
+  // for j <= i only and mirrored: rows i and nreal - 1 - i fold into one row of nreal + 1 entries.
+  double* zl = &psh.T[0][0][0];
+  for (int idx = t; idx < Mq * D; idx += 1024) {
+    const int m = idx / D, d = idx - m * D;
+    const double z = m < M ? jb.Z[idx] : 0.0;
+    zl[idx] = z;
+    jb.Zs[idx] = z * inv_ell[d];
+  }
+  __syncthreads();
+  if (t < 64) {        // zc_d = mid-range of the inducing inputs (min / max are exact: any order gives the same bits).  One wave, lanes over the
+                       // points: as a serial loop in MAXD lanes (100 dependent LDS reads) this held wave 0 back for ~10 k cycles before its share of K
+    for (int d = 0; d < MAXD; ++d) {
+      double zc = 0.0;
+      if (d < D) {
+        double lo = zl[d], hi = lo;                        // point 0: every lane starts from a real value
+        for (int m = t; m < M; m += 64) { const double z = zl[m * D + d]; lo = fmin(lo, z); hi = fmax(hi, z); }
+#pragma unroll
+        for (int sft = 32; sft >= 1; sft >>= 1) { lo = fmin(lo, __shfl_xor(lo, sft, 64)); hi = fmax(hi, __shfl_xor(hi, sft, 64)); }
+        zc = 0.5 * (lo + hi);
+      }
+      if (t == 0) jb.zc_out[d] = zc;
+    }
+  }
+  const int nreal = ((M + PNB - 1) / PNB) * PNB;   // the factorisation touches the 32-column panels that hold real rows only
+  for (int idx = t; idx < (nreal / 2) * (nreal + 1); idx += 1024) {
+    int i = idx / (nreal + 1), j = idx - i * (nreal + 1);
+    if (j > i) { j -= i + 1; i = nreal - 1 - i; }
+    double v;
+    if (i < M && j < M) {
+      double r2 = 0.0;
+      for (int d = 0; d < D; ++d) { const double q = (zl[i * D + d] - zl[j * D + d]) * inv_ell[d]; r2 = fma(q, q, r2); }
+      if (kind != KERN_RBF) v = matern_k(kind, var, r2) + ((i == j) ? a.jitter : 0.0);
+      else v = var * exp(-0.5 * r2) + ((i == j) ? a.jitter : 0.0);     // same expression as k_rbf_matrix
+    } else {
+      v = (i == j) ? 1.0 : 0.0;
+    }
+    jb.K[i * PB + j] = v;
+    S[i * PBLD + j] = v;
+    if (i != j) { jb.K[j * PB + i] = v; S[j * PBLD + i] = 0.0; }
+  }
+  __syncthreads();
+  if (!potrf_diag_lds(S, psh, 0, info, (M + PNB - 1) / PNB, true, a.piv_rtol * 2.220446049250313e-16 * (var + a.jitter))) return;   // info = plain 1-based pivot, as on the panel path; the slot says which factor
+  // logdet K = sum log L_ii^2 (fixed order: strided partials, then 16 wave sums in order)
+  {
+    double ld = 0.0;
+    for (int i = t; i < M; i += 1024) { const double l = S[i * PBLD + i]; ld += log(l * l); }
+    ld = wave_sum(ld);
+    if ((t & 63) == 0) red[t >> 6] = ld;
+    __syncthreads();
+    if (t == 0) { double q = 0.0; for (int w = 0; w < 16; ++w) q += red[w]; jb.dvec[Mq] = q; }
+  }
+  // P = W^T W on the MFMA pipe, operands straight from the LDS image: W[k][i] (k > i) is S[i][k], the diagonal is dinv, zero above.
+  // A(i, k) = W[k][i], B(k, j) = W[k][j].  P is symmetric: blocks rb >= cb only, which need k >= 16 rb; the first four k-steps of a
+  // block cross the diagonal of the A rows (and of the B rows when rb == cb) and take the select-guarded reads, the rest read S
+  // directly; four k-steps of loads go out together (in-kernel stamps at M = 100: 57 k cycles with one guarded k-step at a time,
+  // every LDS round trip exposed).  Dearest blocks first over the 16 waves.  Each lane ends with P(16 rb + 4 r + g, 16 cb + n),
+  // r = 0..3 -- one 32-byte granule of the fragment image PF -- and mirrors it into block (cb, rb).
+  {
+    // (r4: one 16 x 16 x 4 MFMA per k-step; the A operand of a lane is row 16 rb + n of the block -- the same read pattern as the B operand)
+    const int lane = t & 63, g = lane >> 4, n = lane & 15, wave = t >> 6;
+    const int nbq = Mq / 16, ksn = Mq / 4;
+    for (int blk = wave; blk < nbq * (nbq + 1) / 2; blk += 16) {
+      int rb = 0, cb = blk;
+      while (cb > rb) { cb -= rb + 1; ++rb; }
+      double acc[4] = {0.0, 0.0, 0.0, 0.0};
+      const int j = 16 * cb + n, i_a = 16 * rb + n;
+      const double* Sb = S + j * PBLD + g;
+      const double* Sa = S + i_a * PBLD + g;
+      {
+        double bv[4], av[4];
+        const double dj = psh.dinv[j], di = psh.dinv[i_a];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int k = 16 * rb + 4 * u + g;
+          const double sb = Sb[4 * (4 * rb + u)], sa = Sa[4 * (4 * rb + u)];
+          bv[u] = k > j ? sb : (k == j ? dj : 0.0);
+          av[u] = k > i_a ? sa : (k == i_a ? di : 0.0);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) kf_mfma16(acc, av[u], bv[u]);
+      }
+      for (int ks = 4 * rb + 4; ks < ksn; ks += 4) {
+        double bv[4], av[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { bv[u] = Sb[4 * (ks + u)]; av[u] = Sa[4 * (ks + u)]; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) kf_mfma16(acc, av[u], bv[u]);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = 16 * rb + 4 * r + g;
+        const double v = (i < M && j < M) ? acc[r] : 0.0;
+        jb.P[i * Mq + j] = v;
+        // fragment image (kf_write_frag): element (row R, column C) -> block (R / 16, C / 4), lane R % 16 + 16 (C % 4)
+        jb.PF[(int64_t)(rb * ksn + 4 * cb + (n >> 2)) * 64 + 4 * r + g + 16 * (n & 3)] = v;           // (row i, column j)
+        if (rb != cb) {
+          jb.P[j * Mq + i] = v;
+          jb.PF[(int64_t)(cb * ksn + 4 * rb + r) * 64 + n + 16 * g] = v;                              // (row j, column i): the mirror
+        }
+        if (i == j) jb.dvec[i] = v;
+      }
+    }
+  }
+}
+__global__ void __launch_bounds__(1024)
+k_kf_factor_kinds(KfFactorArgs a, int kinds) {
+  extern __shared__ double S[];   // [128][129]
+  __shared__ PotrfShared psh;
+  __shared__ double red[16];
+  kf_factor_kinds_body(a, kinds, S, psh, red);
 }
 
 // ---- small dense algebra of the M x M stages: every operand lives in LDS with row stride KF_SLD (odd: column walks are conflict free)
@@ -1077,6 +1542,67 @@ k_kf_finish(KfFinishArgs a) {
     }
   }
 }
+// ---- Matern factors, small grids: the krow rows of a Matern factor WITHOUT a Matern form of k_kf_finish ----
+// (A second instantiation of the finish body beside k_kf_finish changed the register allocation the compiler gives k_kf_finish itself,
+// and that kernel's machine code is pinned.)  What a Matern factor needs from the finish stage differs from the RBF form in two places
+// only: the moment columns 1 .. 2 D of krow take G . K'_p where RBF takes G . (K_p - jitter I), and their data moments are re-centred with
+// sum t' (column 15 of the moment block) where RBF uses sum t (column 0).  Both are INPUTS of k_kf_finish -- the K_p image it reads and the
+// moment block of its work buffer -- so the step runs k_kf_finish twice: once as always (gu, gs, column 0 of krow, and every column of an
+// RBF factor), and once on a copy of its inputs in which K_p is K'_p(Z_p, Z_p) and column 0 of the moment block holds column 15
+// (k_kf_kd_prepare), writing to scratch outputs; k_kf_krow_merge then takes the columns 1 .. 2 D of the Matern factors from the second run.
+// On the diagonal of K' the differences z_j - z_m are zero, so its value there (and the jitter k_kf_finish subtracts from it) adds nothing.
+// Per latent in KfState::spill (unused by the small grids otherwise):  Kd0 [32][PB] | Kd1 [32][PB] | work' | krow0' | krow1' | gu' | gs'
+constexpr int KF_KD_K = KF_MQ * PB, KF_KD_WORK = 2 * KF_KD_K, KF_KD_KROW0 = KF_KD_WORK + KF_W_TOTAL, KF_KD_KROW1 = KF_KD_KROW0 + KF_MQ * (2 + 2 * MAXD),
+              KF_KD_GU = KF_KD_KROW1 + KF_MQ * (2 + 2 * MAXD), KF_KD_GS = KF_KD_GU + KF_MQ * KF_MQ, KF_KD_TOTAL = KF_KD_GS + KF_MQ * KF_MQ;
+struct KfKdJob { int M0, M1, D0, D1; const double *Z0, *Z1, *hyp0, *hyp1; const double* work; double* buf; double *krow0, *krow1; };
+struct KfKdArgs { KfKdJob job[2]; };
+// grid (3, latents): workgroups 0 / 1 build K'_p of a Matern factor p, workgroup 2 copies the work block with sum t' in column 0 of the
+// moment block of every Matern factor
+__global__ void __launch_bounds__(256)
+k_kf_kd_prepare(KfKdArgs a, int kinds) {
+  const KfKdJob& jb = a.job[blockIdx.y];
+  const int t = threadIdx.x;
+  if (blockIdx.x == 2) {
+    double* w = jb.buf + KF_KD_WORK;
+    for (int idx = t; idx < KF_W_TOTAL; idx += 256) {
+      double v = jb.work[idx];
+      if (idx >= KF_W_K0) {
+        const int p = idx >= KF_W_K1 ? 1 : 0, e = idx - (p ? KF_W_K1 : KF_W_K0);
+        if ((e & 15) == 0 && kf_kind_of(kinds, blockIdx.y, p) != KERN_RBF) v = jb.work[idx + 15];
+      }
+      w[idx] = v;
+    }
+    return;
+  }
+  const int p = blockIdx.x, kind = kf_kind_of(kinds, blockIdx.y, p);
+  if (kind == KERN_RBF) return;      // its columns come from the first run
+  const int M = p == 0 ? jb.M0 : jb.M1, D = p == 0 ? jb.D0 : jb.D1;
+  const double* Z = p == 0 ? jb.Z0 : jb.Z1;
+  const auto hyp = KF_CONST(p == 0 ? jb.hyp0 : jb.hyp1);
+  const auto inv_ell = hyp + KH_INV;
+  const double var = hyp[KH_VAR];
+  double* Kd = jb.buf + p * KF_KD_K;
+  for (int idx = t; idx < M * M; idx += 256) {
+    const int i = idx / M, j = idx - i * M;
+    double r2 = 0.0;
+    for (int d = 0; d < D; ++d) { const double q = (Z[i * D + d] - Z[j * D + d]) * inv_ell[d]; r2 = fma(q, q, r2); }
+    Kd[i * PB + j] = matern_kd(kind, var, r2);
+  }
+}
+// grid (2, latents): columns 1 .. 2 D of the krow rows of a Matern factor from the second run
+__global__ void __launch_bounds__(256)
+k_kf_krow_merge(KfKdArgs a, int kinds) {
+  const KfKdJob& jb = a.job[blockIdx.y];
+  const int p = blockIdx.x;
+  if (kf_kind_of(kinds, blockIdx.y, p) == KERN_RBF) return;
+  const int M = p == 0 ? jb.M0 : jb.M1, D = p == 0 ? jb.D0 : jb.D1, W = 2 + 2 * D;
+  const double* src = jb.buf + (p == 0 ? KF_KD_KROW0 : KF_KD_KROW1);
+  double* dst = p == 0 ? jb.krow0 : jb.krow1;
+  for (int idx = threadIdx.x; idx < M * W; idx += 256) {
+    const int c = idx % W;
+    if (c >= 1 && c <= 2 * D) dst[idx] = src[idx];
+  }
+}
 
 }  // namespace zigp
 
@@ -1124,17 +1650,43 @@ static int kf_launch_small(zigp_ctx* c, bool backward, dim3 grid, const KfArgs& 
   ZIGP_HIP(c, hipGetLastError());
   return 0;
 }
-static int kf_launch_small(zigp_ctx* c, int nb0, int nb1, bool backward, dim3 grid, const KfArgs& ka) {
+// the _kinds instantiations (a call with a Matern factor): the packed kinds ride as an argument of their own; the backward kernel keeps
+// a lane-private K' image per wave behind the fragment images
+static_assert(sizeof(KfFac) == 40 && sizeof(KfLat) == 168 && sizeof(KfArgs) == 384, "the arguments of the RBF point kernels do not move");
+constexpr size_t KF_BWD_LDS_KINDS = KF_BWD_LDS + sizeof(double) * KF_WAVES * 2 * KF_Q * 64;
+static_assert(KF_BWD_LDS_KINDS <= 160 * 1024, "k_kf_backward_kinds: LDS of one workgroup");
+template <int NB0, int NB1>
+static int kf_launch_small_kinds(zigp_ctx* c, bool backward, dim3 grid, const KfArgs& ka, int kinds) {
+  if (backward) {
+    static bool attr = false;
+    if (!attr) {
+      ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kf_backward_kinds<NB0, NB1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KF_BWD_LDS_KINDS));
+      attr = true;
+    }
+    hipLaunchKernelGGL((k_kf_backward_kinds<NB0, NB1>), grid, dim3(64 * KF_WAVES), KF_BWD_LDS_KINDS, c->stream, ka, kinds);
+  } else {
+    hipLaunchKernelGGL((k_kf_forward_kinds<NB0, NB1>), grid, dim3(64 * KF_WAVES), 0, c->stream, ka, kinds);
+  }
+  ZIGP_HIP(c, hipGetLastError());
+  return 0;
+}
+static int kf_launch_small(zigp_ctx* c, int nb0, int nb1, bool backward, dim3 grid, const KfArgs& ka, int kinds) {
+  if (kinds) {
+    if (nb0 == 1 && nb1 == 1) return kf_launch_small_kinds<1, 1>(c, backward, grid, ka, kinds);
+    if (nb0 == 1 && nb1 == 2) return kf_launch_small_kinds<1, 2>(c, backward, grid, ka, kinds);
+    if (nb0 == 2 && nb1 == 1) return kf_launch_small_kinds<2, 1>(c, backward, grid, ka, kinds);
+    return kf_launch_small_kinds<2, 2>(c, backward, grid, ka, kinds);
+  }
   if (nb0 == 1 && nb1 == 1) return kf_launch_small<1, 1>(c, backward, grid, ka);
   if (nb0 == 1 && nb1 == 2) return kf_launch_small<1, 2>(c, backward, grid, ka);
   if (nb0 == 2 && nb1 == 1) return kf_launch_small<2, 1>(c, backward, grid, ka);
   return kf_launch_small<2, 2>(c, backward, grid, ka);
 }
 // one launch for both latents when their block counts agree, else one per latent (KfArgs::lat0 selects it)
-static int kf_launch_small_latents(zigp_ctx* c, const int (*Mq)[2], int nlat, bool backward, unsigned gx, KfArgs& ka) {
+static int kf_launch_small_latents(zigp_ctx* c, const int (*Mq)[2], int nlat, bool backward, unsigned gx, KfArgs& ka, int kinds) {
   const bool same = nlat == 1 || (Mq[0][0] == Mq[1][0] && Mq[0][1] == Mq[1][1]);
-  if (same) { ka.lat0 = 0; return kf_launch_small(c, Mq[0][0] / 16, Mq[0][1] / 16, backward, dim3(gx, nlat), ka); }
-  for (int h = 0; h < nlat; ++h) { ka.lat0 = h; ZIGP_TRY(kf_launch_small(c, Mq[h][0] / 16, Mq[h][1] / 16, backward, dim3(gx, 1), ka)); }
+  if (same) { ka.lat0 = 0; return kf_launch_small(c, Mq[0][0] / 16, Mq[0][1] / 16, backward, dim3(gx, nlat), ka, kinds); }
+  for (int h = 0; h < nlat; ++h) { ka.lat0 = h; ZIGP_TRY(kf_launch_small(c, Mq[h][0] / 16, Mq[h][1] / 16, backward, dim3(gx, 1), ka, kinds)); }
   ka.lat0 = 0;
   return 0;
 }
@@ -1401,6 +1953,7 @@ struct KfRun {
   int nlat, D0, D1, ldx, nblk, pw_blocks;
   int64_t N, Npad;
   bool need_grad;
+  int kinds;                  // the factor kinds of the call, packed (kf_kind_of); 0 = every factor RBF: the RBF kernels, else their _kinds forms
   int Mq[2][2];
   bool large_exact;           // every latent has exactly the capacity's block counts: the instantiation with compile-time bounds
   size_t lds_fwd, lds_bwd;    // LDS of the larger-grid point kernels: fragment images packed by the actual block counts (max over the latents)
@@ -1429,6 +1982,8 @@ static int kf_prepare(zigp_ctx* c, const KronCall& k, const KfFitCall* fit, KfRu
   memset(&s, 0, sizeof(s));
   s.c = c; s.k = &k; s.fit = fit;
   s.nlat = k.nlat; s.need_grad = k.need_grad; s.N = k.N;
+  for (int h = 0; h < k.nlat; ++h)
+    for (int q = 0; q < 2; ++q) s.kinds |= (k.hl[h].kind[q] & 3) << (2 * (2 * h + q));
   const KfPlan pl = s.pl = kf_plan(k.p, k.nlat);
   if (!c->kronf) { c->kronf.reset(new (std::nothrow) KfState()); if (!c->kronf) { c->err = "out of memory"; return ZIGP_EHIP; } }
   KfState& ks = *c->kronf;
@@ -1495,6 +2050,12 @@ static int kf_set_attributes(zigp_ctx* c) {
   ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_forward<1, 7, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_backward<1, 7, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_latent), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kfl_latent_lds(16 * 7)));
+  // the _kinds forms (Matern factors)
+  ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kf_factor_kinds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * PB * PBLD)));
+  ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_forward_kinds<1, 7, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_backward_kinds<1, 7, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_forward_kinds<1, 7, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  ZIGP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kfl_backward_kinds<1, 7, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   attr_set = true;
   return 0;
 }
@@ -1537,7 +2098,8 @@ static int kf_stage_factor(KfRun& s, KfTap* tap) {
   fa.jitter = s.k->jitter; fa.piv_rtol = c->pivot_rtol;
   if (s.k->predict) { fa.info = c->d_info; fa.own_slots = 0; }
   else { fa.info = reinterpret_cast<int*>(s.ks->res.p + s.RES_INFO); fa.own_slots = 1; }
-  hipLaunchKernelGGL(k_kf_factor, dim3(2 * s.nlat), dim3(1024), sizeof(double) * PB * PBLD, c->stream, fa);
+  if (s.kinds) hipLaunchKernelGGL(k_kf_factor_kinds, dim3(2 * s.nlat), dim3(1024), sizeof(double) * PB * PBLD, c->stream, fa, s.kinds);
+  else hipLaunchKernelGGL(k_kf_factor, dim3(2 * s.nlat), dim3(1024), sizeof(double) * PB * PBLD, c->stream, fa);
   ZIGP_HIP(c, hipGetLastError());
   if constexpr (TAP) {
     for (int h = 0; h < s.nlat; ++h)
@@ -1613,9 +2175,13 @@ static int kf_stage_point_forward(KfRun& s, KfTap* tap, const double* Xd, KfArgs
   ka.tpw = (ka.ntiles + waves - 1) / waves;
   const int nw = (ka.ntiles + ka.tpw - 1) / ka.tpw;
   const dim3 grid((nw + KF_WAVES - 1) / KF_WAVES, nlat);
-  if (s.pl.large && s.large_exact) hipLaunchKernelGGL((k_kfl_forward<1, 7, true, true>), grid, dim3(64 * KF_WAVES), s.lds_fwd, c->stream, ka);
+  if (s.pl.large && s.kinds) {
+    if (s.large_exact) hipLaunchKernelGGL((k_kfl_forward_kinds<1, 7, true, true>), grid, dim3(64 * KF_WAVES), s.lds_fwd, c->stream, ka, s.kinds);
+    else hipLaunchKernelGGL((k_kfl_forward_kinds<1, 7, true, false>), grid, dim3(64 * KF_WAVES), s.lds_fwd, c->stream, ka, s.kinds);
+  }
+  else if (s.pl.large && s.large_exact) hipLaunchKernelGGL((k_kfl_forward<1, 7, true, true>), grid, dim3(64 * KF_WAVES), s.lds_fwd, c->stream, ka);
   else if (s.pl.large) hipLaunchKernelGGL((k_kfl_forward<1, 7, true, false>), grid, dim3(64 * KF_WAVES), s.lds_fwd, c->stream, ka);
-  else ZIGP_TRY(kf_launch_small_latents(c, s.Mq, nlat, false, grid.x, ka));
+  else ZIGP_TRY(kf_launch_small_latents(c, s.Mq, nlat, false, grid.x, ka, s.kinds));
   ZIGP_HIP(c, hipGetLastError());
   if constexpr (TAP) {
     tap->facts[ZIGP_KFF_TPW_FWD] = ka.tpw;
@@ -1679,7 +2245,7 @@ static int kf_stage_backward_small(KfRun& s, KfTap* tap, KfArgs& ka, int& nparts
   nparts = nwg * KF_WAVES;
   ZIGP_ENSURE(c, ks.acc, (size_t)2 * nparts * s.nblk * 256);
   for (int h = 0; h < s.nlat; ++h) ka.lat[h].acc = ks.acc.p + (size_t)h * nparts * s.nblk * 256;
-  ZIGP_TRY(kf_launch_small_latents(c, s.Mq, s.nlat, true, (unsigned)nwg, ka));
+  ZIGP_TRY(kf_launch_small_latents(c, s.Mq, s.nlat, true, (unsigned)nwg, ka, s.kinds));
   if constexpr (TAP) { tap->facts[ZIGP_KFF_TPW_BWD] = ka.tpw; tap->facts[ZIGP_KFF_NRANGES] = 1; }
   return 0;
 }
@@ -1696,7 +2262,7 @@ static int kf_stage_backward_large(KfRun& s, KfTap* tap, KfArgs& ka, int& nparts
   KfState& ks = *s.ks;
   const int nlat = s.nlat, nblk = s.nblk;
   size_t rec[2] = {0, 0};
-  for (int h = 0; h < nlat; ++h) rec[h] = (size_t)64 * (s.Mq[h][0] + s.Mq[h][1]);
+  for (int h = 0; h < nlat; ++h) rec[h] = (size_t)(s.kinds ? 80 : 64) * (s.Mq[h][0] + s.Mq[h][1]);      // _kinds: t'_0 | t'_1 behind the eight images
   const int tps = std::max(4, std::min(64, ka.ntiles / 16));     // tiles per accumulation part (4 for a minibatch: the chain of dependent loads is short)
   nparts = (ka.ntiles + tps - 1) / tps;
   const int range_tiles = std::max(1, c->kron_range_tiles / tps) * tps;
@@ -1721,11 +2287,16 @@ static int kf_stage_backward_large(KfRun& s, KfTap* tap, KfArgs& ka, int& nparts
     const int rwaves = std::min(nt, 1024 / nlat);   // one wave per SIMD of the chip: the kernels hold ~400-500 registers per lane
     ka.tile0 = t0; ka.tile1 = t1; ka.tpw = (nt + rwaves - 1) / rwaves;
     const int rnw = (nt + ka.tpw - 1) / ka.tpw, rnwg = (rnw + KF_WAVES - 1) / KF_WAVES;
-    if (s.large_exact) hipLaunchKernelGGL((k_kfl_backward<1, 7, true, true>), dim3(rnwg, nlat), dim3(64 * KF_WAVES), s.lds_bwd, c->stream, ka);
+    if (s.kinds) {
+      if (s.large_exact) hipLaunchKernelGGL((k_kfl_backward_kinds<1, 7, true, true>), dim3(rnwg, nlat), dim3(64 * KF_WAVES), s.lds_bwd, c->stream, ka, s.kinds);
+      else hipLaunchKernelGGL((k_kfl_backward_kinds<1, 7, true, false>), dim3(rnwg, nlat), dim3(64 * KF_WAVES), s.lds_bwd, c->stream, ka, s.kinds);
+    }
+    else if (s.large_exact) hipLaunchKernelGGL((k_kfl_backward<1, 7, true, true>), dim3(rnwg, nlat), dim3(64 * KF_WAVES), s.lds_bwd, c->stream, ka);
     else hipLaunchKernelGGL((k_kfl_backward<1, 7, true, false>), dim3(rnwg, nlat), dim3(64 * KF_WAVES), s.lds_bwd, c->stream, ka);
     ZIGP_HIP(c, hipGetLastError());
     aa.tile0 = t0; aa.tile1 = t1; aa.part0 = t0 / tps;
-    hipLaunchKernelGGL(k_kfl_accum, dim3((nblk + 3) / 4, (nt + tps - 1) / tps, nlat), dim3(256), 0, c->stream, aa);
+    if (s.kinds) hipLaunchKernelGGL(k_kfl_accum_kinds, dim3((nblk + 3) / 4, (nt + tps - 1) / tps, nlat), dim3(256), 0, c->stream, aa, s.kinds);
+    else hipLaunchKernelGGL(k_kfl_accum, dim3((nblk + 3) / 4, (nt + tps - 1) / tps, nlat), dim3(256), 0, c->stream, aa);
     ZIGP_HIP(c, hipGetLastError());
     if constexpr (TAP) { if (t0 == 0) tap->facts[ZIGP_KFF_TPW_BWD] = ka.tpw; ++tap->facts[ZIGP_KFF_NRANGES]; }
   }
@@ -1778,11 +2349,33 @@ static int kf_stage_finish(KfRun& s) {
     hipLaunchKernelGGL(k_kfl_finish<1>, grid, dim3(KFL_FIN_THREADS), 0, c->stream, fa);
     hipLaunchKernelGGL(k_kfl_finish<2>, grid, dim3(KFL_FIN_THREADS), 0, c->stream, fa);
     hipLaunchKernelGGL(k_kfl_finish<3>, grid, dim3(KFL_FIN_THREADS), 0, c->stream, fa);
+    if (s.kinds) hipLaunchKernelGGL(k_kfl_krow_kinds, grid, dim3(KFL_FIN_THREADS), 0, c->stream, fa, s.kinds);      // the krow rows of the Matern factors
   } else {
     KfFinishArgs fs;
     memset(&fs, 0, sizeof(fs));
     fs.job[0] = fa.job[0]; fs.job[1] = fa.job[1]; fs.jitter = fa.jitter; fs.with_kl = fa.with_kl;
     hipLaunchKernelGGL(k_kf_finish, dim3(2, nlat), dim3(1024), KF_FIN_LDS, c->stream, fs);
+    if (s.kinds) {      // Matern factors: the second run on K' and sum t' (k_kf_kd_prepare), then the merge of its moment columns
+      ZIGP_HIP(c, hipGetLastError());
+      ZIGP_ENSURE(c, s.ks->spill, (size_t)2 * KF_KD_TOTAL);
+      KfKdArgs ka;
+      memset(&ka, 0, sizeof(ka));
+      KfFinishArgs f2 = fs;
+      for (int h = 0; h < nlat; ++h) {
+        const KfFinishJob& jb = fs.job[h];
+        KfKdJob& kj = ka.job[h];
+        double* buf = s.ks->spill.p + (size_t)h * KF_KD_TOTAL;
+        kj.M0 = jb.M0; kj.M1 = jb.M1; kj.D0 = jb.D0; kj.D1 = jb.D1; kj.Z0 = jb.Z0; kj.Z1 = jb.Z1; kj.hyp0 = jb.hyp0; kj.hyp1 = jb.hyp1;
+        kj.work = jb.work; kj.buf = buf; kj.krow0 = jb.krow0; kj.krow1 = jb.krow1;
+        KfFinishJob& j2 = f2.job[h];
+        if (kf_kind_of(s.kinds, h, 0) != KERN_RBF) j2.K0 = buf;
+        if (kf_kind_of(s.kinds, h, 1) != KERN_RBF) j2.K1 = buf + KF_KD_K;
+        j2.work = buf + KF_KD_WORK; j2.krow0 = buf + KF_KD_KROW0; j2.krow1 = buf + KF_KD_KROW1; j2.gu = buf + KF_KD_GU; j2.gs = buf + KF_KD_GS;
+      }
+      hipLaunchKernelGGL(k_kf_kd_prepare, dim3(3, nlat), dim3(256), 0, c->stream, ka, s.kinds);
+      hipLaunchKernelGGL(k_kf_finish, dim3(2, nlat), dim3(1024), KF_FIN_LDS, c->stream, f2);
+      hipLaunchKernelGGL(k_kf_krow_merge, dim3(2, nlat), dim3(256), 0, c->stream, ka, s.kinds);
+    }
   }
   ZIGP_HIP(c, hipGetLastError());
   return 0;

@@ -66,6 +66,48 @@ k_kfl_forward(KfArgs a) {
     if (g == 0) { L.part[pn] = q0; L.part[a.Npad + pn] = q1; L.part[2 * a.Npad + pn] = mu; L.part[3 * a.Npad + pn] = st; }
   }
 }
+// k_kfl_forward_kinds: the _kinds kernels of zigp_kronf.hip (Matern factors; kinds = the packed kinds of the call, an argument of those kernels alone)
+template <int NB0, int NB1, bool STAGE, bool EXACT>
+__device__ __forceinline__ void kfl_forward_kinds_body(const KfArgs& a, int kinds, double* lds) {
+  const KfLat& L = a.lat[a.lat0 + blockIdx.y];
+  const int lk = (kinds >> (4 * (a.lat0 + blockIdx.y))) & 15;
+  double kd0[4 * NB0], kd1[4 * NB1];      // K' is not needed going forward (GRAD = false leaves them unwritten)
+  const KfFrags F = kfl_stage_frags<STAGE>(lds, L, false);
+  const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15, slot = lane;      // slot: this lane's position in a fragment block
+  const int w = blockIdx.x * KF_WAVES + (threadIdx.x >> 6);
+  const int t1 = min((w + 1) * a.tpw, a.ntiles);
+  KfTile<NB0, NB1> t;
+  bool first = true;
+  if (w * a.tpw < t1) {          // K tiles of the first tile under the asynchronous staging copy
+    const int64_t pn = (int64_t)(w * a.tpw) * 16 + n;
+    kf_ktiles_any<NB0, NB1, EXACT, false>(t, kd0, kd1, lk, L, F.Z0, F.Z1, a.X + (pn < a.N ? pn : 0) * a.ldx, pn < a.N, g);
+  }
+  if (STAGE) kf_stage_wait();
+  for (int tile = w * a.tpw; tile < t1; ++tile) {
+    const int64_t pn = (int64_t)tile * 16 + n;
+    const bool valid = pn < a.N;
+    if (!first) kf_ktiles_any<NB0, NB1, EXACT, false>(t, kd0, kd1, lk, L, F.Z0, F.Z1, a.X + (valid ? pn : 0) * a.ldx, valid, g);
+    first = false;
+    kf_forward_products<NB0, NB1, EXACT>(t, L, F, slot);
+    double q0 = 0.0, q1 = 0.0, mu = 0.0, st = 0.0;
+#pragma unroll
+    for (int q = 0; q < 4 * NB0; ++q) {
+      q0 = fma(t.K0[q], t.A0[q], q0);
+      mu = fma(t.K0[q], t.B0[q], mu);
+      st = fma(t.A0[q] * t.A0[q], t.C0[q], st);
+    }
+#pragma unroll
+    for (int q = 0; q < 4 * NB1; ++q) q1 = fma(t.K1[q], t.A1[q], q1);
+    q0 = kf_colsum(q0); q1 = kf_colsum(q1); mu = kf_colsum(mu); st = kf_colsum(st);
+    if (g == 0) { L.part[pn] = q0; L.part[a.Npad + pn] = q1; L.part[2 * a.Npad + pn] = mu; L.part[3 * a.Npad + pn] = st; }
+  }
+}
+template <int NB0, int NB1, bool STAGE, bool EXACT>
+__global__ void __launch_bounds__(64 * KF_WAVES, 1)
+k_kfl_forward_kinds(KfArgs a, int kinds) {
+  extern __shared__ double lds[];
+  kfl_forward_kinds_body<NB0, NB1, STAGE, EXACT>(a, kinds, lds);
+}
 
 // Spill image of one tile quantity V (rows x 16 points), point-major with the rows of every 16-block permuted so that both operand
 // roles of k_kfl_accum read it coalesced:  element (row = 16 rb + 4 r + a, point n)  ->  base[n * Mq + 16 rb + 4 a + r]
@@ -147,6 +189,121 @@ k_kfl_backward(KfArgs a) {
     }
   }
 }
+// a lane's own values of a spill image back into registers (kfl_spill's addresses)
+template <int NB>
+__device__ __forceinline__ void kfl_unspill(double (&V)[4 * NB], const double* base, int nb, int Mq, int g, int n) {
+#pragma unroll
+  for (int rb = 0; rb < NB; ++rb) {
+    double4 v = make_double4(0.0, 0.0, 0.0, 0.0);
+    if (rb < nb) v = *reinterpret_cast<const double4*>(base + n * Mq + 16 * rb + 4 * g);
+    V[4 * rb] = v.x; V[4 * rb + 1] = v.y; V[4 * rb + 2] = v.z; V[4 * rb + 3] = v.w;
+  }
+}
+// k_kfl_backward_kinds: the record grows by t'_0 | t'_1 (16 Mq0 + 16 Mq1 doubles behind the eight images): t'_p = dK_p . K'_p, the
+// operand of the moment columns 1 .. 2 D of a Matern factor (k_kfl_accum_kinds).  K'_p waits in those two slots from the K tile to the
+// end of the tile -- written and read back by the same lane -- and is then overwritten by t'_p.
+template <int NB0, int NB1, bool STAGE, bool EXACT>
+__device__ __forceinline__ void kfl_backward_kinds_body(const KfArgs& a, int kinds, double* lds) {
+  const KfLat& L = a.lat[a.lat0 + blockIdx.y];
+  const KfFac &f0 = L.f[0], &f1 = L.f[1];
+  const int lk = (kinds >> (4 * (a.lat0 + blockIdx.y))) & 15;
+  const KfFrags F = kfl_stage_frags<STAGE>(lds, L, true);
+  const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15, slot = lane;      // slot: this lane's position in a fragment block
+  const int w = blockIdx.x * KF_WAVES + (threadIdx.x >> 6);
+  const int nb0 = EXACT ? NB0 : f0.nb, nb1 = EXACT ? NB1 : f1.nb;
+  const int Mq0 = 16 * nb0, Mq1 = 16 * nb1;
+  const int64_t rec = 80 * (int64_t)(Mq0 + Mq1);
+  const int tb = a.tile0 + w * a.tpw;                    // this launch covers tiles [tile0, tile1); its records are numbered from tile0
+  const int t1 = min(tb + a.tpw, a.tile1);
+  KfTile<NB0, NB1> t;
+  bool first = true;
+  if (tb < t1) {          // K tiles of the first tile under the asynchronous staging copy
+    const int64_t pn = (int64_t)tb * 16 + n;
+    double kd0[4 * NB0], kd1[4 * NB1];
+    kf_ktiles_any<NB0, NB1, EXACT, true>(t, kd0, kd1, lk, L, F.Z0, F.Z1, a.X + (pn < a.N ? pn : 0) * a.ldx, pn < a.N, g);
+    {
+      double* Rk = L.spill + (int64_t)(tb - a.tile0) * rec + 64 * (Mq0 + Mq1);
+      kfl_spill<NB0>(Rk, kd0, nb0, Mq0, g, n);
+      kfl_spill<NB1>(Rk + 16 * Mq0, kd1, nb1, Mq1, g, n);
+    }
+  }
+  if (STAGE) kf_stage_wait();
+  for (int tile = tb; tile < t1; ++tile) {
+    const int64_t pn = (int64_t)tile * 16 + n;
+    const bool valid = pn < a.N;
+    const double* xrow = a.X + (valid ? pn : 0) * a.ldx;
+    if (!first) {
+      double kd0[4 * NB0], kd1[4 * NB1];
+      kf_ktiles_any<NB0, NB1, EXACT, true>(t, kd0, kd1, lk, L, F.Z0, F.Z1, xrow, valid, g);
+      {
+        double* Rk = L.spill + (int64_t)(tile - a.tile0) * rec + 64 * (Mq0 + Mq1);
+        kfl_spill<NB0>(Rk, kd0, nb0, Mq0, g, n);
+        kfl_spill<NB1>(Rk + 16 * Mq0, kd1, nb1, Mq1, g, n);
+      }
+    }
+    first = false;
+    kf_forward_products<NB0, NB1, EXACT>(t, L, F, slot);
+    const double gmn = L.gm[pn], gvn = L.gv[pn], dq0n = L.dq0[pn], dq1n = L.dq1[pn];
+    double* R = L.spill + (int64_t)(tile - a.tile0) * rec;
+    double* R1 = R + 64 * Mq0;
+    kfl_spill<NB0>(R, t.K0, nb0, Mq0, g, n);
+    kfl_spill<NB1>(R1, t.K1, nb1, Mq1, g, n);
+    kfl_spill<NB0>(R + 32 * Mq0, t.A0, nb0, Mq0, g, n);
+    kfl_spill<NB1>(R1 + 32 * Mq1, t.A1, nb1, Mq1, g, n);
+    {   // factor 0: B0, C0 are part of the forward tile
+      double dA[4 * NB0], PdA[4 * NB0], E[4 * NB0];
+#pragma unroll
+      for (int q = 0; q < 4 * NB0; ++q) { dA[q] = 2.0 * gvn * t.A0[q] * t.C0[q]; PdA[q] = 0.0; E[q] = fma(dq0n, t.K0[q], dA[q]); }
+      kfl_spill<NB0>(R + 16 * Mq0, E, nb0, Mq0, g, n);
+      kf_frag_mm<NB0, 4 * NB0>(PdA, F.P0, nb0, 4 * nb0, dA, slot);
+#pragma unroll
+      for (int q = 0; q < 4 * NB0; ++q) E[q] = fma(gmn, t.B0[q], fma(2.0 * dq0n, t.A0[q], PdA[q])) * t.K0[q];
+      kfl_spill<NB0>(R + 48 * Mq0, E, nb0, Mq0, g, n);
+      {      // t'_0 over K'_0
+        double* Rk = R + 64 * (Mq0 + Mq1);
+        kfl_unspill<NB0>(E, Rk, nb0, Mq0, g, n);
+#pragma unroll
+        for (int q = 0; q < 4 * NB0; ++q) E[q] = fma(gmn, t.B0[q], fma(2.0 * dq0n, t.A0[q], PdA[q])) * E[q];
+        kfl_spill<NB0>(Rk, E, nb0, Mq0, g, n);
+      }
+    }
+    {   // factor 1: B1 = Alpha^T K0, C1 = S2^T A0^2
+      double B1[4 * NB1], C1[4 * NB1], sq[4 * NB0];
+#pragma unroll
+      for (int q = 0; q < 4 * NB1; ++q) { B1[q] = 0.0; C1[q] = 0.0; }
+#pragma unroll
+      for (int q = 0; q < 4 * NB0; ++q) sq[q] = t.A0[q] * t.A0[q];
+      kf_frag_mm<NB1, 4 * NB0>(B1, F.AlT, nb1, 4 * nb0, t.K0, slot);
+      kf_frag_mm<NB1, 4 * NB0>(C1, F.S2T, nb1, 4 * nb0, sq, slot);
+      double PdA[4 * NB1];
+#pragma unroll
+      for (int q = 0; q < 4 * NB1; ++q) { C1[q] = 2.0 * gvn * t.A1[q] * C1[q]; PdA[q] = 0.0; }       // C1 <- dA1
+      kf_frag_mm<NB1, 4 * NB1>(PdA, F.P1, nb1, 4 * nb1, C1, slot);
+#pragma unroll
+      for (int q = 0; q < 4 * NB1; ++q) {
+        const double dk = fma(gmn, B1[q], fma(2.0 * dq1n, t.A1[q], PdA[q]));
+        B1[q] = dk;                                                                         // B1 <- dK1 (kept for t'_1)
+        PdA[q] = dk * t.K1[q];                                                                         // PdA <- t1
+        C1[q] = fma(dq1n, t.K1[q], C1[q]);                                                             // C1 <- E1
+      }
+      kfl_spill<NB1>(R1 + 16 * Mq1, C1, nb1, Mq1, g, n);
+      kfl_spill<NB1>(R1 + 48 * Mq1, PdA, nb1, Mq1, g, n);
+      {      // t'_1 over K'_1
+        double* Rk = R + 64 * (Mq0 + Mq1) + 16 * Mq0;
+        kfl_unspill<NB1>(PdA, Rk, nb1, Mq1, g, n);
+#pragma unroll
+        for (int q = 0; q < 4 * NB1; ++q) PdA[q] = B1[q] * PdA[q];
+        kfl_spill<NB1>(Rk, PdA, nb1, Mq1, g, n);
+      }
+    }
+  }
+}
+template <int NB0, int NB1, bool STAGE, bool EXACT>
+__global__ void __launch_bounds__(64 * KF_WAVES, 1)
+k_kfl_backward_kinds(KfArgs a, int kinds) {
+  extern __shared__ double lds[];
+  kfl_backward_kinds_body<NB0, NB1, STAGE, EXACT>(a, kinds, lds);
+}
 
 struct KflAccLat { const double* spill; const double *gm, *gv; double* acc; int nb0, nb1, D0, D1; const double *hyp0, *hyp1; };   // hyp_p: factor records of the hyperparameter block (zc)
 struct KflAccArgs { KflAccLat lat[2]; const double* X; int64_t N; int ldx, ntiles, tps, nb0c, nb1c; int tile0, tile1, part0; };   // tile range of this launch, its first part
@@ -208,6 +365,73 @@ k_kfl_accum(KflAccArgs a) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) out[r * 64 + lane] = acc[r];
 }
+// k_kfl_accum_kinds: records of k_kfl_backward_kinds; the moment blocks of a Matern factor take a second product per k-step, t'_p
+// against the columns >= 1 (Psi masked to column 0 in the first): the two-chain form of k_kf_backward_kinds
+__device__ __forceinline__ void kfl_accum_kinds_body(const KflAccArgs& a, int kinds) {
+  const KflAccLat& L = a.lat[blockIdx.z];
+  const int lane = threadIdx.x & 63, kk = lane >> 4, bj = lane & 15;
+  const int nblk = kf_nblocks(a.nb0c, a.nb1c);
+  const int blk = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (blk >= nblk) return;
+  const KfBlock b = kf_block_decode(blk, a.nb0c, a.nb1c);
+  const int Mq0 = 16 * L.nb0, Mq1 = 16 * L.nb1;
+  const int64_t rec = 80 * (int64_t)(Mq0 + Mq1);
+  // moment blocks: this factor is Matern (wave-uniform) -> offA2: its t' image
+  const bool two = b.kind >= 4 && kf_kind_of(kinds, blockIdx.z, b.kind - 4) != KERN_RBF;
+  const int offA2 = 64 * (Mq0 + Mq1) + (b.kind == 4 ? 0 : 16 * Mq0);
+  // operand images inside a tile record, and the block counts that bound (rb, cb)
+  int offA, MqA, offB, MqB, nbr, nbc;
+  switch (b.kind) {
+    case 0: offA = 0; MqA = Mq0; offB = 64 * Mq0; MqB = Mq1; nbr = L.nb0; nbc = L.nb1; break;                         // K0 , K1 gm
+    case 1: offA = 32 * Mq0; MqA = Mq0; offB = 64 * Mq0 + 32 * Mq1; MqB = Mq1; nbr = L.nb0; nbc = L.nb1; break;       // A0^2 , A1^2 gv
+    case 2: offA = 16 * Mq0; MqA = Mq0; offB = 0; MqB = Mq0; nbr = L.nb0; nbc = L.nb0; break;                         // E0 , K0
+    case 3: offA = 64 * Mq0 + 16 * Mq1; MqA = Mq1; offB = 64 * Mq0; MqB = Mq1; nbr = L.nb1; nbc = L.nb1; break;       // E1 , K1
+    case 4: offA = 48 * Mq0; MqA = Mq0; offB = 0; MqB = 0; nbr = L.nb0; nbc = 1; break;                               // t0 , Psi_0
+    default: offA = 64 * Mq0 + 48 * Mq1; MqA = Mq1; offB = 0; MqB = 0; nbr = L.nb1; nbc = 1; break;                   // t1 , Psi_1
+  }
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  if (b.rb < nbr && b.cb < nbc) {
+    const int D = b.kind == 4 ? L.D0 : L.D1, col0 = b.kind == 4 ? 0 : L.D0;
+    const auto zc = KF_CONST(b.kind == 4 ? L.hyp0 : L.hyp1) + KH_ZC;
+    const int psi_d = (bj == 0) ? -1 : ((bj <= D) ? bj - 1 : ((bj <= 2 * D) ? bj - 1 - D : -2));   // -1: constant 1, -2: 0
+    const int t0 = a.tile0 + blockIdx.y * a.tps, t1 = min(t0 + a.tps, a.tile1);
+    const int oa = 16 * b.rb + 4 * (bj & 3) + (bj >> 2), ob = 16 * b.cb + 4 * (bj & 3) + (bj >> 2);     // both roles: row / column l % 16 of the block (permuted image, kfl_spill)
+#pragma unroll 2
+    for (int tile = t0; tile < t1; ++tile) {
+      const double* R = L.spill + (int64_t)(tile - a.tile0) * rec;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const int pt = 4 * ks + kk;
+        const int64_t pn = (int64_t)tile * 16 + pt;
+        double av = R[offA + pt * MqA + oa];          // A operand of v_mfma_f64_16x16x4: (row l % 16, point 4 ks + l / 16)
+        double bv;
+        if (b.kind <= 3) {
+          bv = R[offB + pt * MqB + ob];
+          if (b.kind == 0) bv *= L.gm[pn];
+          if (b.kind == 1) { bv = bv * bv * L.gv[pn]; av *= av; }
+        } else {
+          bv = 0.0;
+          if (pn < a.N) {
+            if (psi_d == -1) bv = 1.0;
+            else if (psi_d >= 0) { const double xv = a.X[pn * a.ldx + col0 + psi_d] - zc[psi_d]; bv = (bj <= D) ? xv : xv * xv; }
+          }
+        }
+        if (two) {      // column 15 (free: D <= 7) takes sum t', which re-centres the t' moments (k_kf_backward_kinds)
+          const double av2 = R[offA2 + pt * MqA + oa];
+          kf_mfma16(acc, av, bj == 0 ? bv : 0.0);
+          kf_mfma16(acc, av2, bj == 0 ? 0.0 : (bj == 15 ? (pn < a.N ? 1.0 : 0.0) : bv));
+        } else {
+          kf_mfma16(acc, av, bv);
+        }
+      }
+    }
+  }
+  double* out = L.acc + ((int64_t)(a.part0 + blockIdx.y) * nblk + blk) * 256;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) out[r * 64 + lane] = acc[r];
+}
+__global__ void __launch_bounds__(256)
+k_kfl_accum_kinds(KflAccArgs a, int kinds) { kfl_accum_kinds_body(a, kinds); }
 
 // ---- M x M stages with operands in global memory (L2 resident): the LDS-resident kernels of zigp_kronf.hip hold 32 x 32 matrices ----
 // C (m x n) [+]= op(A) (m x k) op(B) (k x n); m, k multiples of 4.  A thread owns a 4 x 1 micro-tile (rows i0..i0+3, column j) and
@@ -576,6 +800,68 @@ k_kfl_finish(KflFinishArgs a) {
         krow[m * W + 1 + D + d] = a2 + Kr[m * 16 + 1 + D + d] - 2.0 * dz * k1 + dz * dz * k0;
       }
     }
+    if (lane == 0) krow[m * W + 1 + 2 * D] = 0.0;
+  }
+}
+// Matern factors (zigp_set_kron_matern_fused): the krow rows of a Matern factor, launched BEHIND k_kfl_finish<3> on the same grid.  The three
+// stages do not see the kernel family until the last lines of stage 3, where the rows of G meet K_p; stage 3 leaves G in the factor's
+// scratch region (Gm), so this kernel redoes those last lines alone, as k_kuu_grad_matern forms them: column 0 takes G . (K_p - jitter I), the
+// moment columns G . K'_p with K' recomputed from Z (on the diagonal the differences are zero).  An RBF factor keeps what stage 3 wrote.
+// (Stage 3 itself is at its register limit: a Matern form of the whole kernel spilled.)
+__global__ void __launch_bounds__(KFL_FIN_THREADS)
+k_kfl_krow_kinds(KflFinishArgs a, int kinds) {
+  const KfFinishJob& jb = a.job[blockIdx.z];
+  const int p = blockIdx.y, rbk = blockIdx.x;
+  const int mkind = kf_kind_of(kinds, blockIdx.z, p);
+  if (mkind == KERN_RBF) return;
+  const int t = threadIdx.x, ldw = a.ldw;
+  const bool kl = a.with_kl != 0;
+  const int M = p == 0 ? jb.M0 : jb.M1, Mq = p == 0 ? jb.Mq0 : jb.Mq1, Mo = p == 0 ? jb.M1 : jb.M0, D = p == 0 ? jb.D0 : jb.D1;
+  if (rbk >= Mq / 16) return;
+  const double* Z = p == 0 ? jb.Z0 : jb.Z1;
+  const auto hyp = KF_CONST(p == 0 ? jb.hyp0 : jb.hyp1);
+  const auto zc = hyp + KH_ZC, inv_ell = hyp + KH_INV;
+  const double var = hyp[KH_VAR];
+  const double* P = p == 0 ? jb.P0 : jb.P1;
+  const double* Kuu = p == 0 ? jb.K0 : jb.K1;
+  const double* work = jb.work;
+  const double* Kr = work + (p == 0 ? a.wK0 : a.wK1);
+  double* krow = p == 0 ? jb.krow0 : jb.krow1;
+  const double* Gm = work + a.scratch_off + (int64_t)p * a.scratch_set + 2 * (int64_t)ldw * ldw;      // the Q region of the factor's scratch set: stage 3's G rows
+  const double coef = kl ? 0.5 * (double)Mo : 0.0;
+  const int R = 16 * rbk, W = 2 + 2 * D, lane = t & 63;
+  for (int m = R + (t >> 6); m < min(R + 16, M); m += KFL_FIN_THREADS / 64) {
+    double s0 = 0.0, s1[MAXD], s2[MAXD], zm[MAXD];
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d) { s1[d] = 0.0; s2[d] = 0.0; zm[d] = d < D ? Z[m * D + d] : 0.0; }
+    for (int j = lane; j < M; j += 64) {
+      const double kz = Kuu[m * PB + j] - ((m == j) ? a.jitter : 0.0);
+      const double gj = p == 0 ? Gm[m * ldw + j] : -Gm[m * ldw + j] - coef * P[m * Mq + j];
+      s0 += gj * kz;
+      double df[MAXD], r2 = 0.0;
+#pragma unroll
+      for (int d = 0; d < MAXD; ++d) {
+        df[d] = d < D ? Z[j * D + d] - zm[d] : 0.0;
+        const double u = df[d] * inv_ell[d];
+        r2 = fma(u, u, r2);
+      }
+      const double tm = gj * matern_kd(mkind, var, r2);
+#pragma unroll
+      for (int d = 0; d < MAXD; ++d) { s1[d] = fma(2.0 * tm, df[d], s1[d]); s2[d] = fma(tm * df[d], df[d], s2[d]); }
+    }
+    s0 = wave_sum(s0);
+    const double k0 = Kr[m * 16], kd = Kr[m * 16 + 15];      // sum t, sum t': the moments of t' are re-centred with the latter
+    if (lane == 0) krow[m * W] = s0 + k0;
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d)
+      if (d < D) {
+        const double a1 = wave_sum(s1[d]), a2 = wave_sum(s2[d]);
+        if (lane == 0) {
+          const double dz = zm[d] - zc[d], k1 = Kr[m * 16 + 1 + d];
+          krow[m * W + 1 + d] = a1 + k1 - dz * kd;
+          krow[m * W + 1 + D + d] = a2 + Kr[m * 16 + 1 + D + d] - 2.0 * dz * k1 + dz * dz * kd;
+        }
+      }
     if (lane == 0) krow[m * W + 1 + 2 * D] = 0.0;
   }
 }

@@ -15,7 +15,7 @@ import zigp
 from zigp.optim import AdamGroups, ParamSet
 from zigp.transforms import Log1pe, positive
 from .main import DataSet, Param
-from .model import get_kernels, has_matern, load_checkpoint, save_checkpoint, set_kernels
+from .model import fused_matern_scope, get_kernels, has_matern, load_checkpoint, save_checkpoint, set_kernels
 
 TRAIN_JITTER = 1e-5     # scripts/svgp.py:18, classifier.py:19, hurdle.py:18
 PREDICT_JITTER = 1e-6   # onofftf/svgppred.py:13, onofftf/svcppred.py:13
@@ -230,15 +230,25 @@ def _device_loop(eng, pset, lik, train_data, num_iter, num_minibatch, scale, sav
 
 
 def fit_head(pset, lik, Xtrain, Ytrain, num_iter, num_minibatch, logger, ckpt=None, eng=None, save_every=10000, history=None,
-             device_loop=True, kernels=None):
+             device_loop=True, kernels=None, fused_matern=False):
+    """fit_head's loop (_fit_head) under the fused Matern option: fused_matern=True runs Matern factors on the fused kernels for this
+    call (DenseEngine.set_kron_matern_fused; the engine's setting comes back afterwards), so that a Matern head takes the device_loop
+    branch an RBF head takes.  Not kept in the checkpoint."""
+    with fused_matern_scope(eng, fused_matern):
+        return _fit_head(pset, lik, Xtrain, Ytrain, num_iter, num_minibatch, logger, ckpt, eng, save_every, history, device_loop, kernels,
+                         fused_matern)
+
+
+def _fit_head(pset, lik, Xtrain, Ytrain, num_iter, num_minibatch, logger, ckpt, eng, save_every, history, device_loop, kernels, fused_matern):
     """The optimisation loop of svgp.py:289-330 / classifier.py:276-316: Adam per learning-rate group on
     cost = -(sum(var_exp) * num_data / num_minibatch - kl).  device_loop: run it on the device (_device_loop) where the inducing grid
     is within the fused kernels; False, or a larger grid, steps it from the host, one engine call per iteration.
     kernels: the factor kinds of f -- a name or a pair (space, time) of 'rbf', 'matern32', 'matern52' (None: what the parameter set
-    holds, RBF by default).  With a Matern factor the host loop runs also when device_loop=True (the device loop fits RBF factors)."""
+    holds, RBF by default).  With a Matern factor the host loop runs also when device_loop=True (the device loop fits RBF factors),
+    unless fused_matern."""
     if kernels is not None:
         set_kernels(pset, kernels, ('f',))
-    if device_loop and num_iter > 0 and has_matern(pset, ('f',)):
+    if device_loop and num_iter > 0 and has_matern(pset, ('f',)) and not fused_matern:
         logger.info('Matern factor kernel %s: the host Adam loop runs (the device loop fits RBF factors only)' % (get_kernels(pset, ('f',))['f'],))
         device_loop = False
     train_data = DataSet(Xtrain, Ytrain)                                          # svgp.py:43
@@ -307,18 +317,19 @@ def _restore_head(lik, Xtrain, checkpointPath, num_inducing_f, include_f_mu, dev
     return eng, head_engine_params(pset), head_f_mu(pset)
 
 
-def restore_and_predict(lik, Xtrain, Xtest, checkpointPath, num_inducing_f, include_f_mu, rows, device=0, engine=None):
-    """Restore (_restore_head), then evaluate with jitter 1e-6."""
+def restore_and_predict(lik, Xtrain, Xtest, checkpointPath, num_inducing_f, include_f_mu, rows, device=0, engine=None, fused_matern=False):
+    """Restore (_restore_head), then evaluate with jitter 1e-6.  fused_matern: Matern factors on the fused kernels for this call."""
     eng, p, f_mu = _restore_head(lik, Xtrain, checkpointPath, num_inducing_f, include_f_mu, device, engine)
 
     def run(X):
         o = eng.kron_head_predict(p, X, lik, jitter=PREDICT_JITTER, f_mu=f_mu)
         return {name: o[r].reshape(-1, 1) for name, r in rows}
 
-    pred_train = run(Xtrain)
-    if Xtest is not None:
-        return pred_train, run(Xtest)
-    return pred_train
+    with fused_matern_scope(eng, fused_matern):
+        pred_train = run(Xtrain)
+        if Xtest is not None:
+            return pred_train, run(Xtest)
+        return pred_train
 
 
 def restore_and_sample(lik, Xtrain, Xtest, checkpointPath, num_inducing_f, include_f_mu, num_samples, n_features=1024, seed=None, draws=None,

@@ -1,6 +1,7 @@
 """Parameter set of the Kronecker zero-inflated GP exactly as scripts/onoff.py:51-137 declares it
 (names follow the TF variable scopes f_kern/, g_kern/, likelihood/, f_ind/, g_ind/), + npz checkpoints in place of
 tf.train.Saver (onofftf/utils.py:61-73)."""
+import contextlib
 from collections import OrderedDict
 
 import numpy as np
@@ -88,6 +89,27 @@ def kernel_options(argv):
     ap.add_argument('--kernel-time', default='rbf', choices=KERNEL_NAMES)
     a, _ = ap.parse_known_args(list(argv))
     return (a.kernel_space, a.kernel_time)
+
+
+def fused_matern_option(argv):
+    """fused_matern=True from the command-line option --fused-matern of the scripts (default: off)"""
+    return '--fused-matern' in list(argv)
+
+
+@contextlib.contextmanager
+def fused_matern_scope(eng, on):
+    """The engine's fused Matern switch (DenseEngine.set_kron_matern_fused) for the length of one fit or predict call: on=True turns it on
+    and puts the engine's earlier setting back afterwards; on=False leaves the engine as it is.  The option belongs to the call, not to
+    the model: it is not kept in the checkpoint."""
+    if not on:
+        yield
+        return
+    was = eng.get_kron_matern_fused()
+    eng.set_kron_matern_fused(True)
+    try:
+        yield
+    finally:
+        eng.set_kron_matern_fused(was)
 
 
 def set_kernels(pset, kernels, tags=('f', 'g')):

@@ -12,7 +12,7 @@ import numpy as np
 import zigp
 from zigp.optim import AdamGroups
 from .main import DataSet
-from .model import init_params, engine_params, get_kernels, has_matern, named_grads, save_checkpoint, set_kernels
+from .model import init_params, engine_params, fused_matern_scope, get_kernels, has_matern, named_grads, save_checkpoint, set_kernels
 
 jitter_level = 1e-5   # scripts/onoff.py:18
 
@@ -54,10 +54,20 @@ def _device_loop(eng, pset, train_data, num_iter, num_minibatch, scale, log_ever
 
 def onoff(Xtrain, Ytrain, Xtest, Ytest, dir, num_iter=50000, num_inducing_f=(10, 100), num_inducing_g=(10, 100),
           num_minibatch=1000, log_every=200, save_every=10000, device=0, engine=None, kmeans_seed=None, history=None, device_loop=True,
-          kernels=None):
+          kernels=None, fused_matern=False):
     """kernels: the factor kinds -- None (RBF, the reference's KernSE), a name, a pair (space, time) for both latents, or
     {'f': ..., 'g': ...} of 'rbf', 'matern32', 'matern52' (onofftf.model.kernel_kinds).  They are kept in the checkpoint, which the
-    predict / sample / score functions follow.  With a Matern factor the host Adam loop runs also when device_loop=True."""
+    predict / sample / score functions follow.  With a Matern factor the host Adam loop runs also when device_loop=True, unless
+    fused_matern=True: then the engine runs Matern factors on the fused kernels for this call (DenseEngine.set_kron_matern_fused) and a
+    Matern model takes the device_loop branch an RBF model takes.  fused_matern is not kept in the checkpoint."""
+    eng = engine or zigp.reference_engine(device)      # tf.cholesky's acceptance rule (pivot > 0)
+    with fused_matern_scope(eng, fused_matern):
+        return _onoff(Xtrain, Ytrain, Xtest, Ytest, dir, num_iter, num_inducing_f, num_inducing_g, num_minibatch, log_every, save_every, eng,
+                      kmeans_seed, history, device_loop, kernels, fused_matern)
+
+
+def _onoff(Xtrain, Ytrain, Xtest, Ytest, dir, num_iter, num_inducing_f, num_inducing_g, num_minibatch, log_every, save_every, eng, kmeans_seed,
+           history, device_loop, kernels, fused_matern):
     os.makedirs(dir, exist_ok=True) if dir else None
     logger = logging.getLogger('log')                                                # :35-40
     logger.setLevel(logging.DEBUG)
@@ -69,9 +79,8 @@ def onoff(Xtrain, Ytrain, Xtest, Ytest, dir, num_iter=50000, num_inducing_f=(10,
     num_data = Xtrain.shape[0]                                                       # :54
     pset = init_params(Xtrain, num_inducing_f, num_inducing_g, init_noisevar=0.01, kmeans_seed=kmeans_seed)   # :51-137
     set_kernels(pset, kernels)
-    eng = engine or zigp.reference_engine(device)      # tf.cholesky's acceptance rule (pivot > 0)
     scale = float(num_data) / float(num_minibatch)                                   # :311
-    if device_loop and has_matern(pset):
+    if device_loop and has_matern(pset) and not fused_matern:
         logger.info('Matern factor kernels %s: the host Adam loop runs (the device loop fits RBF factors only)' % (get_kernels(pset),))
         device_loop = False
     logger.info('*******  started optimization at ' + time.strftime('%Y%m%d-%H%M') + ' *******')

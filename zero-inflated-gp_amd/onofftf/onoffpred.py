@@ -5,13 +5,14 @@ import os
 import numpy as np
 
 import zigp
-from .model import init_params, engine_params, load_checkpoint
+from .model import init_params, engine_params, fused_matern_scope, load_checkpoint
 
 jitter_level = 1e-6   # onofftf/onoffpred.py:13
 
 
 def predict_onoff(Xtrain, Xtest, checkpointPath, num_inducing_f=np.array([10, 100]), num_inducing_g=np.array([10, 100]),
-                  include_fmu=False, device=0, engine=None):
+                  include_fmu=False, device=0, engine=None, fused_matern=False):
+    # fused_matern: Matern factors of the restored model on the fused kernels for this call (DenseEngine.set_kron_matern_fused)
     # include_fmu has no effect in the reference either: its f_mu Param is commented out (onoffpred.py:27-28,89)
     pset = init_params(Xtrain, num_inducing_f, num_inducing_g, init_noisevar=0.001)
     ck = checkpointPath
@@ -25,10 +26,11 @@ def predict_onoff(Xtrain, Xtest, checkpointPath, num_inducing_f=np.array([10, 10
         o = eng.kron_predict(p, X, jitter=jitter_level, g_offset=-1.0)
         return {'gfmean': o[0].reshape(-1, 1), 'fmean': o[3].reshape(-1, 1), 'pgmean': o[7].reshape(-1, 1)}   # :273-280
 
-    pred_train = run(Xtrain)
-    if Xtest is not None:
-        return pred_train, run(Xtest)
-    return pred_train
+    with fused_matern_scope(eng, fused_matern):
+        pred_train = run(Xtrain)
+        if Xtest is not None:
+            return pred_train, run(Xtest)
+        return pred_train
 
 
 def sample_onoff(Xtrain, Xtest, checkpointPath, num_samples, num_inducing_f=np.array([10, 100]), num_inducing_g=np.array([10, 100]),

@@ -7,9 +7,10 @@ from .heads import restore_and_predict
 jitter_level = 1e-6   # onofftf/svcppred.py:13
 
 
-def predict_scgp(Xtrain, Xtest, checkpointPath, num_inducing_f=np.array([10, 100]), include_f_mu=False, device=0, engine=None):
+def predict_scgp(Xtrain, Xtest, checkpointPath, num_inducing_f=np.array([10, 100]), include_f_mu=False, device=0, engine=None,
+                 fused_matern=False):
     return restore_and_predict('bernoulli', Xtrain, Xtest, checkpointPath, num_inducing_f, include_f_mu,
-                               (('pfmean', 2), ('pfvar', 3)), device=device, engine=engine)
+                               (('pfmean', 2), ('pfvar', 3)), device=device, engine=engine, fused_matern=fused_matern)
 
 
 def sample_scgp(Xtrain, Xtest, checkpointPath, num_samples, num_inducing_f=np.array([10, 100]), include_f_mu=False, n_features=1024, seed=None,

@@ -7,10 +7,11 @@ from .heads import restore_and_predict
 jitter_level = 1e-6   # onofftf/svgppred.py:13
 
 
-def predict_svgp(Xtrain, Xtest, checkpointPath, num_inducing_f=np.array([10, 100]), include_fmu=False, device=0, engine=None):
+def predict_svgp(Xtrain, Xtest, checkpointPath, num_inducing_f=np.array([10, 100]), include_fmu=False, device=0, engine=None,
+                 fused_matern=False):
     # include_fmu only defines an unused initial value in the reference (svgppred.py:26-27)
     return restore_and_predict('gaussian', Xtrain, Xtest, checkpointPath, num_inducing_f, False,
-                               (('fmean', 0), ('fvar', 1)), device=device, engine=engine)       # :180-186
+                               (('fmean', 0), ('fvar', 1)), device=device, engine=engine, fused_matern=fused_matern)       # :180-186
 
 
 def sample_svgp(Xtrain, Xtest, checkpointPath, num_samples, num_inducing_f=np.array([10, 100]), n_features=1024, seed=None, draws=None,

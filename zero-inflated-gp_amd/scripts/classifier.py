@@ -31,8 +31,9 @@ def _scores(prob, actual):
 
 
 def classifier(Xtrain, Ytrain, Xtest, Ytest, dir, num_iter=500, num_inducing_f=(10, 100), num_minibatch=1000, include_f_mu=False,
-               device=0, engine=None, kmeans_seed=None, history=None, device_loop=True, kernels=None):
-    """kernels: the factor kinds of f (fit_head); the command line takes --kernel-space / --kernel-time, default rbf"""
+               device=0, engine=None, kmeans_seed=None, history=None, device_loop=True, kernels=None, fused_matern=False):
+    """kernels: the factor kinds of f (fit_head); the command line takes --kernel-space / --kernel-time, default rbf.
+    fused_matern (--fused-matern): Matern factors on the fused kernels and the device fit loop (fit_head, predict_scgp)"""
     os.makedirs(dir, exist_ok=True)
     Ytrain_c, Ytest_c = (Ytrain > 0) * 1.0, (Ytest > 0) * 1.0                                    # :43-47
     logger, handler = open_logger(os.path.join(dir, 'modelsumm_scgp.log'))
@@ -42,10 +43,10 @@ def classifier(Xtrain, Ytrain, Xtest, Ytest, dir, num_iter=500, num_inducing_f=(
     eng = engine or zigp.reference_engine(device)      # tf.cholesky's acceptance rule (pivot > 0)
     ckpt = os.path.join(dir, 'model_scgp.ckpt')
     fit_head(pset, 'bernoulli', Xtrain, Ytrain_c, num_iter, num_minibatch, logger, ckpt=ckpt, eng=eng, history=history, device_loop=device_loop,
-             kernels=kernels)   # :276-321
+             kernels=kernels, fused_matern=fused_matern)   # :276-321
     log_kernel_summary(logger, pset)
     pred_train, pred_test = predict_scgp(Xtrain=Xtrain, Xtest=Xtest, checkpointPath=ckpt, num_inducing_f=np.array(num_inducing_f),
-                                         include_f_mu=include_f_mu, engine=eng)                  # :352-354
+                                         include_f_mu=include_f_mu, engine=eng, fused_matern=fused_matern)   # :352-354
     results = {'pred_train': pred_train, 'pred_test': pred_test}
     for split, pred, truth in (('train', pred_train, Ytrain_c), ('test', pred_test, Ytest_c)):
         acc, prec, rec, auc = _scores(pred['pfmean'], truth)
@@ -66,5 +67,6 @@ def main(scriptPath, **kw):
 
 
 if __name__ == '__main__':
-    from onofftf.model import kernel_options
-    main(sys.argv[0], kernels=kernel_options(sys.argv[1:]))      # --kernel-space NAME --kernel-time NAME, default rbf
+    from onofftf.model import fused_matern_option, kernel_options
+    main(sys.argv[0], kernels=kernel_options(sys.argv[1:]),      # --kernel-space NAME --kernel-time NAME, default rbf
+         fused_matern=fused_matern_option(sys.argv[1:]))         # --fused-matern, default off

@@ -21,8 +21,9 @@ def mad(predict, actual):
 
 
 def hurdle(Xtrain, Ytrain, Xtest, Ytest, cresults, dir, num_iter=50000, num_inducing_f=(10, 100), num_minibatch=1000, device=0,
-           engine=None, kmeans_seed=None, history=None, device_loop=True, kernels=None):
-    """kernels: the factor kinds of the regression's f (fit_head); the command line takes --kernel-space / --kernel-time, default rbf"""
+           engine=None, kmeans_seed=None, history=None, device_loop=True, kernels=None, fused_matern=False):
+    """kernels: the factor kinds of the regression's f (fit_head); the command line takes --kernel-space / --kernel-time, default rbf.
+    fused_matern (--fused-matern): Matern factors on the fused kernels and the device fit loop (fit_head, predict_svgp)"""
     os.makedirs(dir, exist_ok=True)
     logger, handler = open_logger(os.path.join(dir, 'modelsumm_hurdle.log'))
     train_on = np.where(cresults['pred_train']['pfmean'] > 0.5)[0]                               # :49-50
@@ -35,9 +36,10 @@ def hurdle(Xtrain, Ytrain, Xtest, Ytest, cresults, dir, num_iter=50000, num_indu
     eng = engine or zigp.reference_engine(device)      # tf.cholesky's acceptance rule (pivot > 0)
     ckpt = os.path.join(dir, 'model_hurdle.ckpt')
     fit_head(pset, 'gaussian', Xtr, Ytr, num_iter, min(num_minibatch, Xtr.shape[0]), logger, ckpt=ckpt, eng=eng, history=history, device_loop=device_loop,
-             kernels=kernels)
+             kernels=kernels, fused_matern=fused_matern)
     log_kernel_summary(logger, pset)
-    ptr, pte = predict_svgp(Xtrain=Xtr, Xtest=Xte, checkpointPath=ckpt, num_inducing_f=np.array(num_inducing_f), engine=eng)   # :346-348
+    ptr, pte = predict_svgp(Xtrain=Xtr, Xtest=Xte, checkpointPath=ckpt, num_inducing_f=np.array(num_inducing_f), engine=eng,
+                            fused_matern=fused_matern)   # :346-348
     res = {'pred_train_hurdle_svgp': ptr, 'pred_test_hurdle_svgp': pte,
            'train_hurdle_reg_rmse': rmse(ptr['fmean'], Ytr), 'train_hurdle_reg_mae': mad(ptr['fmean'], Ytr),
            'test_hurdle_reg_rmse': rmse(pte['fmean'], Yte), 'test_hurdle_reg_mae': mad(pte['fmean'], Yte)}
@@ -69,5 +71,6 @@ def main(scriptPath, **kw):
 
 
 if __name__ == '__main__':
-    from onofftf.model import kernel_options
-    main(sys.argv[0], kernels=kernel_options(sys.argv[1:]))      # --kernel-space NAME --kernel-time NAME, default rbf
+    from onofftf.model import fused_matern_option, kernel_options
+    main(sys.argv[0], kernels=kernel_options(sys.argv[1:]),      # --kernel-space NAME --kernel-time NAME, default rbf
+         fused_matern=fused_matern_option(sys.argv[1:]))         # --fused-matern, default off

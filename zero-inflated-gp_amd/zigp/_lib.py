@@ -241,6 +241,8 @@ SIGNATURES = {
     'zigp_get_kernel': (C.c_int, [C.c_void_p, C.c_int32]),
     'zigp_set_kron_kernel': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     'zigp_get_kron_kernel': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    'zigp_set_kron_matern_fused': (C.c_int, [C.c_void_p, C.c_int32]),
+    'zigp_get_kron_matern_fused': (C.c_int, [C.c_void_p]),
     'zigp_kern_K': (C.c_int, [C.c_void_p, C.c_int32, dp, C.c_int64, dp, C.c_int64, C.c_int32, dp, C.c_double, dp]),
     'zigp_kron_head_elbo': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_int32, dp, dp, C.c_int64, C.c_double, C.c_double,
                                       C.c_double, C.c_int32, dp, dp, C.POINTER(zigp_kron_grads), dp]),

@@ -395,14 +395,32 @@ class DenseEngine:
     def _set_kron_kinds(self, p, tags=('f', 'g')):
         self._apply_kron_kinds(kron_kernel_kinds(p, tags))
 
+    # what set_kron_matern_fused last set.  The fit loops refuse a Matern factor BEFORE the library is touched (an engine without a library
+    # shows it: tests/test_cpu_kron_matern.py), so that refusal cannot ask the context; get_kron_matern_fused does.
+    _kron_matern_fused = False
+
+    def set_kron_matern_fused(self, on=True):
+        """Opt in to the fused Kronecker kernels for Matern factors (zigp_set_kron_matern_fused; off by default): with it on, a kron_* call
+        with a Matern factor on a grid the fused kernels cover runs their Matern instantiations instead of the GEMM panels, and
+        kron_fit_steps / kron_head_fit_steps accept Matern factors.  set_kron_panels(True) still wins."""
+        if on not in (True, False, 0, 1):
+            raise ValueError('set_kron_matern_fused: on must be True or False')
+        _check(self.lib, self.ctx, self.lib.zigp_set_kron_matern_fused(self.ctx, 1 if on else 0))
+        self._kron_matern_fused = bool(on)
+
+    def get_kron_matern_fused(self):
+        return bool(self.lib.zigp_get_kron_matern_fused(self.ctx))
+
     def _kron_fit_kinds(self, who, shape, tags):
-        """The device fit loops fit RBF factors: a Matern factor in shape raises before the library is touched, with the naming of the
-        library's own refusal; otherwise all four kinds go back to RBF."""
-        bad = kron_matern_factor(kron_kernel_kinds(shape, tags))
-        if bad:
+        """The device fit loops fit RBF factors unless set_kron_matern_fused is on: a Matern factor in shape then raises before the
+        library is touched, with the naming of the library's own refusal.  Otherwise the context gets the kinds of shape (all RBF with
+        the switch off)."""
+        kinds = kron_kernel_kinds(shape, tags)
+        bad = kron_matern_factor(kinds)
+        if bad and not self._kron_matern_fused:
             raise ValueError('%s: a %s is set; the device loop fits RBF factors only: step the model with kron_%selbo(rows=...) and a host '
                              'optimiser' % (who, bad, 'head_' if tags == ('f',) else ''))
-        self._apply_kron_kinds({})
+        self._apply_kron_kinds(kinds if bad else {})
 
     def _set_modes(self, p):
         kinds = kernel_kinds(p)          # an unknown name raises before anything is set
