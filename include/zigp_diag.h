@@ -342,6 +342,34 @@ typedef struct zigp_kronf_tap_latent {
                       (sums over points, unsymmetrised dP_p = sum E_p K_p^T; Kr_p[m][j] = sum_n t_p[m, n] psi_j(x_n), psi = {1, x - zc, (x - zc)^2}) */
   const double* inject;   /* in, optional: [4][N] copied over gm, gv, dq0, dq1 between the point-wise launch and the backward launch; rows >= N keep
                              what the point-wise kernel wrote */
+  /* ---- the finish stage (k_kf_finish; larger grids k_kfl_finish<1..3>; Matern factors: k_kf_kd_prepare / k_kf_krow_merge, k_kfl_krow_kinds).
+   * Capacity rows R_p = 16 nb_pc (32, 32 or 16, 112), ldw = max(R0, R1), W = 2 + 2 * 8 = 18 doubles per capacity row of a krow region.
+   * UNWRITTEN PARTS.  Every tap below is taken at the capacity size of its region.  When one of them is asked for, the hook fills the region
+   * with ZIGP_STAGE_SENTINEL_BYTE before the step's first launch that could write it -- the latents' result blocks (klv, krow, gu, gs,
+   * krow_first) at the start of the step, the scratch of the second small-grid run (Kd, krow2) before k_kf_kd_prepare, the G regions before
+   * k_kfl_finish<1> -- so an element the kernels never write comes back as the sentinel, and a kernel that wrote past its compact part shows.
+   * Nothing reads those elements (the step returns the bits of an ordinary call).  In a data-parallel context (zigp_comm_init) the step itself
+   * clears the result blocks, and their unwritten elements are +0 instead.  Padding the kernels DO write is exact zero: named per tap. */
+  double* klv;            /* after k_kf_latent / k_kfl_latent: [8] = sum U.Alpha, sum log s^2, sum d0 d1 s^2, logdet K0, logdet K1; [5..7] unwritten */
+  double* krow[2];        /* after the LAST launch of the stage: the region [R_p * W] of the result block.  The kernels write it COMPACTLY,
+                             [M_p][2 + 2 D_p] from its start (column 0: d var numerator, 1 .. D: d Z, D + 1 .. 2 D: d ell numerators, 1 + 2 D: exact 0);
+                             everything behind M_p (2 + 2 D_p) is unwritten */
+  double *gu, *gs;        /* after the last launch: [R0 * R1] regions of the result block, written compactly as [M0 * M1]; the rest is unwritten */
+  double* krow_first[2];  /* a step with a Matern factor: the krow regions (as `krow`) after the first k_kf_finish, before k_kf_krow_merge overwrites
+                             columns 1 .. 2 D of a Matern factor; larger grids: after k_kfl_finish<3>, before k_kfl_krow_kinds rewrites the rows of a
+                             Matern factor.  Not taken (the host array is left alone) by a step whose factors are all RBF */
+  double* Kd[2];          /* small grids with a Matern factor, after k_kf_kd_prepare: the [32][128] image K'_p(Z_p, Z_p) = -dk / d(r2 / 2) the second
+                             k_kf_finish reads in place of K_p.  The kernel writes the leading [M_p][M_p] entries of a Matern factor (row stride 128);
+                             everything else -- the whole image of an RBF factor included -- is unwritten */
+  double* work2;          /* same step, after k_kf_kd_prepare: the copy of the work block (layout of `work`, capacity (2, 2): 4 * 32 * 32 + 2 * 32 * 16
+                             doubles) with column 0 of the moment block of every Matern factor replaced by its column 15; every element is written */
+  double* krow2[2];       /* same step, after the second k_kf_finish (on Kd / work2): [32 * W] regions written compactly as `krow`; the rest is unwritten */
+  double* G[2];           /* larger grids, after k_kfl_finish<3> (before k_kfl_krow_kinds): the [ldw][ldw] region of the factor's scratch set the
+                             stage leaves its G rows in (row stride ldw = 112).  Factor 0: rows 0 .. Mq0 - 1, columns < Mq0 hold
+                             G = -P sym(dP') P - coef P itself (compensated, rounded once), rows 16 .. 16 + Mq0 - 1 the low words of Q2 = X P that
+                             stage 2 left there.  Factor 1: rows and columns < Mq1 hold the plain product P Q2 = P X P; the kernels form
+                             G = -that - coef P on the fly when they read it.  Rows / columns M_p .. Mq_p - 1 of G and P Q2 are written: exact
+                             (signed) zeros.  Everything else is unwritten */
 } zigp_kronf_tap_latent;
 /* facts[] of zigp_test_kron_fused_step */
 enum { ZIGP_KFF_LARGE = 0,     /* 1: the larger-grid kernels (k_kfl_*), 0: the small-grid ones (k_kf_*) */

@@ -96,6 +96,36 @@ SHIFT_CASE = 'd21-mix'
 SHIFT = 3.0               # the largest shift tried at which the oracle's own error is <= 1e-9: test_cpu_kron_nd.py::test_oracle_at_shifted_inputs
 
 
+# The finish-stage edge grids (tests/test_gpu_kronf_stages.py): N = 33 rows; the smallest grid the entry points accept is ONE point per factor
+# (validate_kron refuses M <= 0 only).  EDGE_C is the lengthscale constant c of these problems: tests/test_cpu_kronf_finish_ref.py shows on the
+# CPU that every deliberate mistake of the finish stage is caught on each of them at this c.
+EDGE_C = 0.5
+EDGE_GRIDS = [(1, 1), (15, 17), (16, 16), (17, 31), (32, 32), (16, 112), (9, 50), (10, 100), (1, 112)]
+EDGE_DS = [(1, 1), (7, 7)]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_problem(grid, D, g=None):
+    """(X, Y, p) of an edge grid at N = 33 (read-only); g: the g latent's grid when it differs"""
+    X, Y, p = make_kron_problem_nd(33, grid[0], grid[1], D[0], D[1], 4000 + 131 * grid[0] + grid[1] + 7 * D[0], M0g=g and g[0], M1g=g and g[1], c=EDGE_C)
+    _freeze(X, Y, p)
+    return X, Y, p
+
+
+def pptr_problem(grid):
+    """(Xtrain, Ytrain, x minibatch, y minibatch, p) of the precipitation data at the reference's initialisation on `grid` x `grid` inducing
+    points (the ill-conditioned init: cond(K_s) ~ 5e7 at 32 x 32) with a 1000-row minibatch as DataSet.next_batch hands it out"""
+    import os
+    from onofftf.model import init_params, engine_params
+    d = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'pptr.npz'))
+    Xtr, Ytr = d['Xtrain'].copy(), d['Ytrain']
+    Xtr[:, 2] /= 1000.0                                   # scripts/create_cvsplits.py:17
+    np.random.seed(7)
+    p = engine_params(init_params(Xtr, grid, grid, kmeans_seed=3))
+    idx = np.random.RandomState(11).permutation(Xtr.shape[0])[:1000]     # shuffled rows
+    return Xtr, Ytr, np.ascontiguousarray(Xtr[idx]), np.ascontiguousarray(Ytr[idx]), p
+
+
 def _seed(name):
     return 1000 + list(CASES).index(name)
 

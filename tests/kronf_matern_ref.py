@@ -156,6 +156,7 @@ NEW_KINDS = {
     'd77': (('matern52', 'matern32'), ('rbf', 'matern32')),
     'L51': (('rbf', 'matern32'), ('matern32', 'rbf')),
 }
+L77_KINDS = (('matern32', 'matern52'), ('matern52', 'rbf'))      # L77 is not in the table above: its kinds in the finish-stage tests
 PINNED = ('d11', 'd21-12', 'd21-mix', 'd31', 'd17', 'L32')      # held to floor <= 1e-8, cond <= 1e5 by tests/test_cpu_kron_matern.py
 
 
@@ -173,3 +174,25 @@ def fixture(name):
     X, Y, p = kron_nd.problem(name)
     kf, kg = fixture_kinds()[name]
     return X, Y, kmr.with_kinds(p, kf, kg)
+
+
+def zz_kd(kind, Z, ell, var, dtype=np.float64):
+    """(K', eK') (M, M) of a Matern factor at its own inducing inputs, as k_kf_kd_prepare / k_kfl_krow_kinds form it: the second pair of
+    ktile(..., grad=True) with Xp = Z"""
+    _, _, Kd, eKd = ktile(kind, Z, ell, var, Z, dtype, grad=True)
+    return Kd, eKd
+
+
+def finish(kinds, w, K0, K1, P0, P1, U, S2, T0, T1, Al, s, Z0, Z1, zc0, zc1, jitter, kl, ell, var, dtype=np.float64, Kd=(None, None), _mut=()):
+    """kronf_ref.finish with the factor kinds.  A Matern factor differs in the moment columns 1 .. 2 D of its krow only: tt = G . K'_p(Z_p, Z_p)
+    in place of G . (K_p - jitter I), and the re-centring with column 15 of its moment block (sum t') in place of column 0.  w['Kr%d' % p] is
+    the device block of the factor, 16 columns.  Kd[p]: (K', eK') to use for factor p (a stage test passes the tapped image with a zero
+    weight); None: formed here from Z_p, ell[p], var[p].  With every kind 'rbf' this IS kronf_ref.finish (same call, same bits)."""
+    mom = []
+    for p, (Z, Kr) in enumerate(((Z0, w['Kr0']), (Z1, w['Kr1']))):
+        if kinds[p] == 'rbf':
+            mom.append(None)
+            continue
+        kd = Kd[p] if Kd[p] is not None else zz_kd(kinds[p], Z, ell[p], var[p], dtype)
+        mom.append((kd[0], kd[1], np.asarray(Kr)[:, 15]))
+    return R.finish(w, K0, K1, P0, P1, U, S2, T0, T1, Al, s, Z0, Z1, zc0, zc1, jitter, kl, dtype, _mom=tuple(mom), _mut=_mut)

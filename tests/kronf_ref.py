@@ -4,6 +4,8 @@ Every function takes a `dtype` (np.float64 or np.longdouble) and returns, per ou
 values of the terms of the sums behind that output, each operand that is itself computed entering with its own error weight (below); the
 convention of tests/stage_ref.py: an evaluation of the same sums in any order is within a small multiple of eps S of the exact value.
 tests/test_cpu_kronf_ref.py pins them to torch autograd and to the oracle; tests/test_gpu_kronf_stages.py holds the kernels to them.
+The finish stage (kl_scalars, finish, krow_from_G, assemble at the end of this file: k_kf_finish, k_kfl_finish<1..3> and the host chain rule
+kron_assemble_grads) takes its inputs as given, so its S is the plain nested sum of absolute values; tests/test_cpu_kronf_finish_ref.py pins it.
 
 S is a first-order error weight, built with the computation: an input counts with its magnitude, a K tile with eK = |K| (2 + w), w the error weight
 of its exponent (ktile), a sum of products sum a_i b_i with sum (e(a_i) |b_i| + |a_i| e(b_i)), the
@@ -237,3 +239,139 @@ def exact_problem(grid_f, grid_g, D, N, jitter=0.0, seed=0):
                         Zs=[Z[q] / ell[q] for q in range(2)],
                         stage=(P[0], P[1], u / (c[0] * c[1]), s * s, Z[0], Z[1], ell[0], ell[1], var[0], var[1])))
     return dict(p=p, X=X, Y=Y, lat=lat, D=D, N=N, jitter=jitter)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the finish stage: k_kf_latent's KL scalars, the reverse M x M pass (k_kf_finish / k_kfl_finish<1..3>) and the host chain rule
+# ---------------------------------------------------------------------------------------------------------------------------------
+def kl_scalars(U, Al, s, d0, d1, dtype=np.float64):
+    """klv[0..2] of k_kf_latent / k_kfl_latent: sum U . Alpha, sum log s^2, sum d0_i d1_j s_ij^2 (d_p = diag P_p); klv[3], klv[4] are copies
+    of the factor kernel's logdets and need no restatement.  Returns dict name -> (value, S).  The logarithm turns the relative rounding of
+    s^2 into an absolute eps, and carries one of its own: each term of the second sum weighs |log s^2| + 2."""
+    U, Al, s, d0, d1 = _f(U, dtype), _f(Al, dtype), _f(s, dtype), _f(d0, dtype).reshape(-1), _f(d1, dtype).reshape(-1)
+    s2 = s * s
+    ls = np.log(s2)
+    dd = d0[:, None] * d1[None, :] * s2
+    return dict(uAl=((U * Al).sum(), (np.abs(U) * np.abs(Al)).sum()), logs2=(ls.sum(), (np.abs(ls) + 2).sum()), ds2=(dd.sum(), np.abs(dd).sum()))
+
+
+def krow_from_G(G, aG, K, Kr, Z, zc, jitter, dtype=np.float64, _mom=None, _mut=()):
+    """The last lines of the finish kernels for one factor: krow [M][2 + 2 D] from the rows of G (M, M) -- aG its error weight, |G| when G
+    is taken as given --, K = K_p + jitter I as tapped, the moment block Kr (M, >= 1 + 2 D) around zc, and Z (M, D):
+        kz = K - jitter I,  tt = G . kz,  df = z_jd - z_md,  dz = z_md - zc_d
+        krow[m][0] = sum_j tt + Kr[m][0];   krow[m][1 + d] = sum_j 2 tt df + Kr[m][1 + d] - dz Kr[m][0]
+        krow[m][1 + D + d] = sum_j tt df^2 + Kr[m][1 + D + d] - 2 dz Kr[m][1 + d] + dz^2 Kr[m][0];   krow[m][1 + 2 D] = 0
+    _mom = (Kd, eKd, kd): the Matern form (kronf_matern_ref.finish) -- the moment columns take tt' = G . Kd and are re-centred with kd
+    (column 15 of the device block) in place of Kr[:, 0].  _mut: the deliberate mistakes of tests/test_cpu_kronf_finish_ref.py.
+    Returns (value, S)."""
+    G, aG, K, Kr, Z, zc = _f(G, dtype), _f(aG, dtype), _f(K, dtype), _f(Kr, dtype), _f(Z, dtype), _f(zc, dtype).reshape(-1)
+    M, D = Z.shape
+    eye = np.eye(M, dtype=dtype)
+    kz, akz = K - dtype(jitter) * eye, np.abs(K) + dtype(jitter) * eye
+    tt, att = G * kz, aG * akz
+    if _mom is None:
+        tm, atm, c0 = tt, att, Kr[:, 0]
+    else:
+        Kd, eKd, kd = _f(_mom[0], dtype), _f(_mom[1], dtype), _f(_mom[2], dtype)
+        tm, atm, c0 = G * Kd, aG * np.abs(Kd) + np.abs(G) * eKd, kd
+    two = dtype(1) if 'no2' in _mut else dtype(2)
+    out, S = np.zeros((M, 2 + 2 * D), dtype=dtype), np.zeros((M, 2 + 2 * D), dtype=dtype)
+    out[:, 0], S[:, 0] = tt.sum(1) + Kr[:, 0], att.sum(1) + np.abs(Kr[:, 0])
+    for d in range(D):
+        df = Z[None, :, d] - Z[:, None, d]
+        dz = Z[:, d] - zc[d]
+        if 'dzsign' in _mut:
+            dz = -dz
+        k1, k2 = Kr[:, 1 + d], Kr[:, 1 + D + d]
+        out[:, 1 + d] = (two * tm * df).sum(1) + k1 - dz * c0
+        S[:, 1 + d] = (2 * atm * np.abs(df)).sum(1) + np.abs(k1) + np.abs(dz) * np.abs(c0)
+        out[:, 1 + D + d] = (tm * df * df).sum(1) + k2 - 2 * dz * k1 + dz * dz * c0
+        S[:, 1 + D + d] = (atm * df * df).sum(1) + np.abs(k2) + 2 * np.abs(dz) * np.abs(k1) + dz * dz * np.abs(c0)
+    return out, S
+
+
+def finish(w, K0, K1, P0, P1, U, S2, T0, T1, Al, s, Z0, Z1, zc0, zc1, jitter, kl, dtype=np.float64, _mom=(None, None), _mut=()):
+    """The reverse M x M pass, from the comment block above KfFinishJob (csrc/zigp_kronf.hip) and the kernel text.  w: the six matrices of
+    the work block trimmed to the latent's own grid (dAl, dS2 (M0, M1), dP_p (M_p, M_p), Kr_p (M_p, >= 1 + 2 D_p)); K_p as tapped (jitter
+    included), P_p, U, S2, T0, T1, Al (M0, M1) as tapped, s (M0, M1), kl: include_kl.  Per factor p, o the other one, d_p = diag P_p:
+        dP0' = dP0 + dAl T0^T, dP1' = dP1 + T1^T dAl;  Q0 = T0 U^T, Q1 = U^T T1;  w0_i = sum_j d1_j S2_ij, w1_j = sum_i d0_i S2_ij
+        X = sym(dP') - kl (1/4 (Q + Q^T) + 1/2 diag w);   PXP = P X P;   G = -PXP - kl 1/2 M_o P;   krow_p = krow_from_G(G, ...)
+        gu = P0 dAl P1 - kl Alpha;   gs = 2 s dS2 - kl (-1 / s + d0_i d1_j s)
+    Returns dict name -> (value, S) for krow0, krow1, gu, gs, G0, G1, PXP0, PXP1 (what k_kfl_finish<3> leaves for factor 1).  S: the nested sum
+    of absolute values; the inputs are the stage's own and enter with their magnitudes."""
+    P = (_f(P0, dtype), _f(P1, dtype))
+    K, Z, zc = (K0, K1), (Z0, Z1), (zc0, zc1)
+    U, S2, T0, T1, Al, s = (_f(a, dtype) for a in (U, S2, T0, T1, Al, s))
+    dAl, dS2 = _f(w['dAl'], dtype), _f(w['dS2'], dtype)
+    M = (P[0].shape[0], P[1].shape[0])
+    dv = (np.diag(P[0]), np.diag(P[1]))
+    klf = dtype(1 if kl else 0)
+    aU, adAl = np.abs(U), np.abs(dAl)
+    dP = (_f(w['dP0'], dtype) + dAl @ T0.T, _f(w['dP1'], dtype) + T1.T @ dAl)
+    adP = (np.abs(_f(w['dP0'], dtype)) + adAl @ np.abs(T0).T, np.abs(_f(w['dP1'], dtype)) + np.abs(T1).T @ adAl)
+    Q, aQ = (T0 @ U.T, U.T @ T1), (np.abs(T0) @ aU.T, aU.T @ np.abs(T1))
+    wv, awv = (S2 @ dv[1], S2.T @ dv[0]), (np.abs(S2) @ np.abs(dv[1]), np.abs(S2).T @ np.abs(dv[0]))
+    out = {}
+    for p in range(2):
+        aP = np.abs(P[p])
+        X = dP[p] if 'nosym' in _mut else (dP[p] + dP[p].T) / 2
+        aX = (adP[p] + adP[p].T) / 2
+        if kl:
+            if 'noQ' not in _mut:
+                X = X - (Q[p] + Q[p].T) / 4
+            X = X - np.diag(wv[p]) / 2
+            aX = aX + (aQ[p] + aQ[p].T) / 4 + np.diag(awv[p]) / 2
+        PXP, aPXP = P[p] @ X @ P[p], aP @ aX @ aP
+        coef = klf * dtype(M[p] if 'coefMp' in _mut else M[1 - p]) / 2
+        G, aG = -PXP - coef * P[p], aPXP + coef * aP
+        out['PXP%d' % p], out['G%d' % p] = (PXP, aPXP), (G, aG)
+        out['krow%d' % p] = krow_from_G(G, aG, K[p], w['Kr%d' % p], Z[p], zc[p], jitter, dtype, _mom[p], _mut)
+    out['gu'] = (P[0] @ dAl @ P[1] - klf * Al, np.abs(P[0]) @ adAl @ np.abs(P[1]) + klf * np.abs(Al))
+    dd = dv[0][:, None] * dv[1][None, :] * s
+    out['gs'] = (2 * s * dS2 - klf * (-1 / s + dd), 2 * np.abs(s * dS2) + klf * (1 / np.abs(s) + np.abs(dd)))
+    return out
+
+
+def assemble(krow, gu, gs, ell, var, s_gv, dtype=np.float64):
+    """kron_assemble_grads (csrc/zigp_kronc.h) for one latent: the host chain rule from krow_p (M_p, 2 + 2 D_p), gu, gs and s_gv, the sum of the
+    variance cotangents over the points:  dZ_p = krow[:, 1 : 1 + D] / ell^2;  d ell_p = sum_m krow[:, 1 + D : 1 + 2 D] / ell^3;
+    d var_p = sum_m krow[:, 0] / var_p + s_gv var_other;  d u = gu, d s = gs.  Returns dict name -> (value, S) with Z, ell, var lists over p."""
+    out = dict(Z=[], ell=[], var=[], u=(_f(gu, dtype), np.abs(_f(gu, dtype))), s=(_f(gs, dtype), np.abs(_f(gs, dtype))))
+    sg = _f(s_gv, dtype).reshape(())
+    for p in range(2):
+        kr, l, v = _f(krow[p], dtype), _f(ell[p], dtype).reshape(-1), _f(var[p], dtype).reshape(())
+        D = l.size
+        dZ = kr[:, 1:1 + D] / (l * l)
+        out['Z'].append((dZ, np.abs(dZ)))
+        out['ell'].append((kr[:, 1 + D:1 + 2 * D].sum(0) / (l * l * l), np.abs(kr[:, 1 + D:1 + 2 * D]).sum(0) / (l * l * l)))
+        vo = _f(var[1 - p], dtype).reshape(())
+        out['var'].append((kr[:, 0].sum() / v + sg * vo, np.abs(kr[:, 0]).sum() / v + np.abs(sg) * vo))
+    return out
+
+
+def moment_block16(Kr, Kd=None):
+    """the 16-column device moment block of a factor from backward()'s Kr (M, 1 + 2 D) and, for a Matern factor, Kd (M) in column 15"""
+    out = np.zeros((Kr.shape[0], 16))
+    out[:, :Kr.shape[1]] = Kr
+    if Kd is not None:
+        out[:, 15] = Kd
+    return out
+
+
+def exact_finish(L, D, jitter, kl, dtype=np.float64):
+    """finish() on the values an exact-tier step hands its finish stage (L: one latent of exact_problem): K_p + jitter I = c_p I,
+    P_p = I / c_p, T0 = U / c_1, T1 = U / c_0, Alpha = U / (c_0 c_1), the integer sums over points.  tests/test_cpu_kronf_finish_ref.py shows
+    which of its results are exact in float64 (all of them with kl off; with kl on all but gs where s = 3, see exact_gs_mask)."""
+    M, c = L['M'], L['c']
+    s = np.sqrt(L['S2'])
+    w = dict(L['sums'])
+    for q in range(2):
+        w['Kr%d' % q] = moment_block16(L['sums']['Kr%d' % q])
+    K = [c[q] * np.eye(M[q]) for q in range(2)]
+    return finish(w, K[0], K[1], L['P'][0], L['P'][1], L['U'], L['S2'], L['U'] / c[1], L['U'] / c[0], L['U'] / (c[0] * c[1]), s,
+                  L['Z'][0], L['Z'][1], L['zc'][0], L['zc'][1], jitter, kl, dtype=dtype)
+
+
+def exact_gs_mask(L):
+    """where gs is exact with kl on: -1 / s is a dyadic number for s in {1, 2} and not for s = 3"""
+    return np.sqrt(L['S2']) != 3.0

@@ -3,6 +3,9 @@ default): the _kinds kernels of csrc/zigp_kronf.hip and csrc/zigp_kronl.h agains
 with a kernel kind per factor) at the project's 1e-6, against the same call on the GEMM panels, and stage by stage against
 tests/kronf_matern_ref.py.  Fixtures: kronf_matern_ref.fixture_kinds() -- tests/test_cpu_kron_matern.py and
 tests/test_cpu_kron_matern_fused.py hold the reference's own floor on each at 1e-8 and cond(K_p + 1e-5 I) at 1e5.
+The finish stage of a step with Matern factors (k_kf_kd_prepare, the second k_kf_finish, k_kf_krow_merge; k_kfl_krow_kinds behind
+k_kfl_finish<3>) is held tap by tap in test_finish_stage_with_matern_factors (figures: profiles/kronf_finish_parity.log); its restatement,
+kronf_matern_ref.finish, is pinned by tests/test_cpu_kronf_finish_ref.py.
 
 On a build without the feature set_kron_matern_fused does not exist and every test here fails.  Every test prints its figures
 (pytest -s; profiles/kron_matern_fused_parity.log keeps a run's)."""
@@ -529,3 +532,144 @@ def test_onoff_and_fit_head_take_the_device_loop_with_fused_matern(engine, tmp_p
     for a, b in zip(pa, pb):
         for k in ('fmean', 'fvar'):
             assert relerr(b[k], a[k]) < TOL
+
+
+# ---- the finish stage with Matern factors ------------------------------------------------------------------------------------------------
+L77_KINDS = fm.L77_KINDS
+
+
+def _finish_fixture(name):
+    if name in TABLE:
+        return fm.fixture(name) + (kron_nd.CASES[name]['f'], kron_nd.CASES[name]['g'] or kron_nd.CASES[name]['f'], kron_nd.CASES[name]['D'])
+    if name == 'L77':
+        X, Y, p = kron_nd.problem(name)
+        k = kron_nd.CASES[name]
+        return X, Y, kmr.with_kinds(p, *L77_KINDS), k['f'], k['g'] or k['f'], k['D']
+    # a larger grid at D = (1, 1): k_kfl_krow_kinds multiplies by inv_ell[d] for d >= D, which is safe because the hyperparameter record is zero there
+    X, Y, p = kron_nd.edge_problem((10, 100), (1, 1))
+    return X, Y, kmr.with_kinds(p, ('matern52', 'matern32'), ('rbf', 'matern52')), (10, 100), (10, 100), (1, 1)
+
+
+def _bits(a, b):
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
+
+
+def _finish_kinds_latent(case, kinds, large, t, Z, ell, var, s, M, D, cap, jitter, kl):
+    """one latent of a tapped step with Matern factors: everything the finish stage leaves, against kronf_ref.finish / kronf_matern_ref.finish
+    in long double on the stage's own tapped inputs (test_gpu_kronf_stages._rule), and the bit-for-bit identities between its runs"""
+    import kronf_ref as kr
+    from test_gpu_kronf_stages import _rule, _log, finish_inputs, check_G_and_krow_from_G, assert_unwritten
+    from zigp import _lib
+    LD = np.longdouble
+    sfx = 'finish_kinds' + ('l' if large else '')
+    args = finish_inputs(t, Z, s, M, cap, jitter)
+    w, K = args[0], args[1:3]
+    mat = [k != 'rbf' for k in kinds]
+    assert_unwritten(case, t, M, D)
+    assert 'krow_first_cap' in t and (large or 'krow2_cap' in t)
+    cols = [slice(1, 1 + 2 * D[q]) for q in range(2)]
+    k64, kld = fm.finish(kinds, *args, kl, ell, var), fm.finish(kinds, *args, kl, ell, var, dtype=LD)
+    for q in range(2):
+        assert np.all(np.isfinite(t['krow'][q])), '%s: a non-finite krow entry' % case
+        assert not np.any(t['krow'][q][:, 1 + 2 * D[q]]), '%s: krow column 1 + 2 D' % case
+        _rule(sfx, case, 'krow%d' % q, t['krow'][q], k64['krow%d' % q][0], kld['krow%d' % q][0], k64['krow%d' % q][1])
+    for k in ('gu', 'gs'):       # written by the first run only
+        _rule(sfx, case, k, t[k], k64[k][0], kld[k][0], k64[k][1])
+    if large:
+        def krow_of(q, g, ag, dt):
+            mom = (fm.zz_kd(kinds[q], Z[q], ell[q], var[q], dt) + (w['Kr%d' % q][:, 15],)) if mat[q] else None
+            return kr.krow_from_G(g, ag, K[q], w['Kr%d' % q], Z[q], args[13 + q], jitter, dt, _mom=mom)
+        check_G_and_krow_from_G(sfx, case, t, args, kl, k64, kld, M, krow_of)
+        for q in range(2):
+            if not mat[q]:
+                assert _bits(t['krow'][q], t['krow_first'][q]), '%s: the rows of RBF factor %d are not what stage 3 wrote' % (case, q)
+            else:
+                # column 0: k_kfl_krow_kinds sums G . kz over the same lanes in the same order as stage 3, but as `s0 += gj * kz` where stage 3 has
+                # `tt = ... * kz; s0 += tt` with tt used again: whether either is contracted to an FMA is the compiler's choice, so the text does
+                # not guarantee the bits.  Column 0 is held by the rule (krow|G above); whether the bits agree is logged.
+                _log(sfx, case, 'krow%d column 0 %s stage 3\'s bits' % (q, 'keeps' if _bits(t['krow'][q][:, 0], t['krow_first'][q][:, 0]) else 'does NOT keep'))
+        return
+    # ---- small grids: k_kf_finish, k_kf_kd_prepare, k_kf_finish on (K', work'), k_kf_krow_merge
+    want = np.array(t['work'])
+    ws = kr.work_split(want, cap)
+    for q in range(2):
+        if mat[q]:
+            ws['Kr%d' % q][:, 0] = ws['Kr%d' % q][:, 15]
+    assert _bits(t['work2'], want), '%s: work2 is not work with column 0 <- column 15 in the moment blocks of the Matern factors' % case
+    K2 = list(K)
+    for q in range(2):
+        Kd = t['Kd'][q]
+        if not mat[q]:
+            assert np.all(Kd == _lib.STAGE_SENTINEL), '%s: the K\' image of RBF factor %d was written' % (case, q)
+            continue
+        rest = np.array(Kd)
+        rest[:M[q], :M[q]] = _lib.STAGE_SENTINEL
+        assert np.all(rest == _lib.STAGE_SENTINEL), '%s: K\'_%d written beyond [M][M]' % (case, q)
+        d64, dld = fm.zz_kd(kinds[q], Z[q], ell[q], var[q]), fm.zz_kd(kinds[q], Z[q], ell[q], var[q], LD)
+        _rule(sfx, case, 'Kd%d' % q, Kd[:M[q], :M[q]], d64[0], dld[0], d64[1])
+        K2[q] = Kd[:M[q], :M[q]]
+    f64, fld = kr.finish(*args, kl), kr.finish(*args, kl, dtype=LD)
+    w2 = kr.work_split(t['work2'], cap)
+    args2 = (dict(w, Kr0=w2['Kr0'][:M[0]], Kr1=w2['Kr1'][:M[1]]), K2[0], K2[1]) + args[3:]
+    g64, gld = kr.finish(*args2, kl), kr.finish(*args2, kl, dtype=LD)
+    for q in range(2):
+        _rule(sfx, case, 'first%d' % q, t['krow_first'][q], f64['krow%d' % q][0], fld['krow%d' % q][0], f64['krow%d' % q][1])
+        _rule(sfx, case, 'second%d' % q, t['krow2'][q], g64['krow%d' % q][0], gld['krow%d' % q][0], g64['krow%d' % q][1])
+        merged = np.array(t['krow_first'][q])
+        if mat[q]:
+            merged[:, cols[q]] = t['krow2'][q][:, cols[q]]
+        assert _bits(t['krow'][q], merged), '%s: krow%d is not krow2 in columns 1 .. 2 D of a Matern factor and the first run everywhere else' % (case, q)
+
+
+@pytest.mark.parametrize('name', ['d11', 'd21-21', 'd31', 'd17', 'd77', 'd21-mix2', 'L32', 'L51', 'L77', 'edgeL-D11'])
+def test_finish_stage_with_matern_factors(fused, name):
+    from test_gpu_kronf_stages import _check_facts, _unpack, check_assemble
+    X, Y, p, gf, gg, D = _finish_fixture(name)
+    N = X.shape[0]
+    try:
+        for kl in (True, False):
+            out = _hook(fused, p, X, Y, jitter=J, scale=7.0, include_kl=kl)
+            cap, nb = _check_facts(out['facts'], [gf, gg], N, 2)
+            for h, tag in enumerate('fg'):
+                Z, ell, var = _unpack(p, tag)
+                _finish_kinds_latent('%s/%s kl=%d' % (name, tag, kl), kmr.kinds_of(p)[h], cap == (1, 7), out['lat'][h], Z, ell, var, p['u_%ss_sqrt' % tag],
+                                     (gf, gg)[h], D, cap, J, kl)
+            if kl and name == 'd31':
+                check_assemble(name + ' matern', out, p, 'fg')
+    finally:      # the hook follows the kinds of the context: leave it as the tests behind this one expect it
+        for tag in 'fg':
+            for q in range(2):
+                fused.set_kron_kernel(tag, q, 'rbf')
+
+
+@pytest.mark.parametrize('name', ['d31', 'L32'])
+def test_hook_with_matern_factors_returns_the_bits_of_an_ordinary_call_and_repeats_its_taps(fused, name):
+    """The tapped step of a call with Matern factors -- which also fills the scratch of the second small-grid run, the G regions and the result
+    blocks with the stage sentinel -- returns the bits of the ordinary call; every tap, the Matern ones (krow_first, Kd, work2, krow2) and the
+    capacity arrays included, repeats between two tapped calls; a call with taps=False and an ordinary call afterwards are unchanged."""
+    from test_gpu_kronf_stages import _flat, _same, _rup
+    X, Y, p = fm.fixture(name)
+    kw = dict(jitter=J, scale=kron_nd.case_scale(name), f_mu=0.2, g_offset=0.1)
+    try:
+        ed0, kl0, g0 = fused.kron_elbo(p, X, Y, **kw)
+        t1 = _hook(fused, p, X, Y, **kw)
+        assert (t1['elbo_data'], t1['kl']) == (ed0, kl0) and _same(_flat(t1['grads']), _flat(g0)), 'the tapped step is not the ordinary step'
+        t2 = _hook(fused, p, X, Y, **kw)
+        small = 'Kd' in t1['lat'][0]
+        for h, lat in enumerate(t1['lat']):
+            assert 'krow_first' in lat and ('krow2' in lat and 'work2' in lat) == small and ('G' in lat) != small
+            for k, v in lat.items():
+                vs, ws = (v, t2['lat'][h][k]) if isinstance(v, list) else ([v], [t2['lat'][h][k]])
+                if k == 'K':                   # beyond the leading R x R part the buffer is never written
+                    Rs = [_rup(P.shape[0], 32) for P in lat['P']]
+                    vs, ws = [a[:R, :R] for a, R in zip(vs, Rs)], [a[:R, :R] for a, R in zip(ws, Rs)]
+                assert _same(vs, ws), 'tap %s of latent %d differs between two tapped calls' % (k, h)
+        t3 = _hook(fused, p, X, Y, taps=False, **kw)
+        assert (t3['elbo_data'], t3['kl']) == (ed0, kl0) and _same(_flat(t3['grads']), _flat(g0))
+        ed1, kl1, g1 = fused.kron_elbo(p, X, Y, **kw)
+        assert (ed1, kl1) == (ed0, kl0) and _same(_flat(g1), _flat(g0)), 'an ordinary call after the tapped ones changed'
+    finally:
+        for tag in 'fg':
+            for q in range(2):
+                fused.set_kron_kernel(tag, q, 'rbf')

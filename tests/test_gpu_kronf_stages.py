@@ -13,8 +13,18 @@ references are the NumPy restatements of tests/kronf_ref.py (pinned on the CPU b
 * hook hygiene: the tapped step returns the bits of an ordinary call, repeats its taps, leaves later calls unchanged, and refuses what
   does not run on the fused kernels.
 
-Every test prints STAGE-LOG lines (profiles/kronf_stage_parity.log keeps a run's).  The reverse M x M kernels (k_kf_finish, k_kfl_finish)
-and k_fit_update are not covered here."""
+* finish stage: the KL scalars of the latent kernels and everything the reverse M x M kernels (k_kf_finish, k_kfl_finish<1..3>) leave --
+  krow0, krow1, gu, gs; larger grids: the G rows of stage 3, and krow recomputed from those tapped rows -- against kronf_ref.finish /
+  kl_scalars in long double on the stage's own tapped inputs, with include_kl on and off: every bound-tier fixture, the heads, the pptr
+  init, the edge grids at N = 33 (one-point factors, every kf_lds_mm shape, the row-block bounds of k_kfl_finish, 15 moment columns), two
+  latents with different grids; bit for bit on the exact tier; and the gradients a step returns against the host chain rule
+  (kron_assemble_grads) of the tapped results.  tests/test_cpu_kronf_finish_ref.py pins that restatement to autograd and shows that the rule
+  catches each of eight deliberate mistakes on these fixtures.  The Matern additions of the stage (k_kf_kd_prepare, the second k_kf_finish,
+  k_kf_krow_merge, k_kfl_krow_kinds) are held in tests/test_gpu_kron_matern_fused.py.
+
+Every test prints STAGE-LOG lines (profiles/kronf_stage_parity.log and profiles/kronf_finish_parity.log keep a run's).  k_fit_update has no
+stage test: it stays covered only through the fit-loop tests (tests/test_gpu_kron_nd.py, test_gpu_head_fit.py, test_gpu_kron_matern_fused.py),
+which compare device steps with host-stepped ones."""
 import ctypes as C
 
 import numpy as np
@@ -123,6 +133,19 @@ def _assert_exact_taps(tag, t, L, D, N, cap):
     want = kr.work_image({k: (v, None) for k, v in L['sums'].items()}, M, D, cap)
     bad = np.flatnonzero(t['work'] != want)
     assert bad.size == 0, '%s: %d elements of the work block differ, first at %d: %r instead of %r' % (tag, bad.size, bad[0], t['work'][bad[0]], want[bad[0]])
+    # ---- the finish stage.  The steps of this tier count the KL; tests/test_cpu_kronf_finish_ref.py::test_exact_tier_finish_is_exact shows that
+    # on these inputs krow, gu and -- where s is 1 or 2 (-1 / s dyadic) -- gs are exact WITH the KL terms, so the comparison is `==`; gs at s = 3
+    # is rounded and stays out.
+    jitter = L['c'][0] - L['var'][0]
+    f = kr.exact_finish(L, D, jitter, True)
+    keep = kr.exact_gs_mask(L)
+    for q in range(2):
+        assert np.array_equal(t['krow'][q], f['krow%d' % q][0]), '%s: krow%d' % (tag, q)
+    assert np.array_equal(t['gu'], f['gu'][0]), '%s: gu' % tag
+    assert keep.any() and np.array_equal(t['gs'][keep], f['gs'][0][keep]), '%s: gs where 1 / s is exact' % tag
+    if 'G' in t:
+        assert np.array_equal(t['G'][0][:M[0], :M[0]], f['G0'][0]) and np.array_equal(t['G'][1][:M[1], :M[1]], f['PXP1'][0]), '%s: G rows of stage 3' % tag
+    assert_unwritten(tag, t, M, D)
 
 
 def _exact_step(engine, shape, D, N, lik, jitter=0.0):
@@ -333,6 +356,198 @@ def test_row_ranges_do_not_change_a_bit(engine, name, N, settings):
         engine.set_kron_range_tiles(1024)
     assert seen[0] == 1 and seen[1] == 2 and seen[2] >= 6, seen
     _log('ranges', '%s N=%d' % (name, N), 'bit-equal over %s ranges' % seen)
+
+
+# =====================================================================================================================================
+# the finish stage: k_kf_latent's KL scalars, k_kf_finish / k_kfl_finish<1..3> (Matern additions: tests/test_gpu_kron_matern_fused.py)
+# =====================================================================================================================================
+def finish_inputs(t, Z, s, M, cap, jitter):
+    """the arguments of kronf_ref.finish from the taps of one latent (the stage's own inputs: work, K, P, U, S2, T0, T1, Al, zc) and the
+    parameters Z, s"""
+    w = kr.work_split(t['work'], cap)
+    w = dict(dAl=w['dAl'][:M[0], :M[1]], dS2=w['dS2'][:M[0], :M[1]], dP0=w['dP0'][:M[0], :M[0]], dP1=w['dP1'][:M[1], :M[1]], Kr0=w['Kr0'][:M[0]], Kr1=w['Kr1'][:M[1]])
+    K = [t['K'][q][:M[q], :M[q]] for q in range(2)]
+    P = [t['P'][q][:M[q], :M[q]] for q in range(2)]
+    m = lambda k: t[k][:M[0], :M[1]]
+    return (w, K[0], K[1], P[0], P[1], m('U'), m('S2'), m('T0'), m('T1'), m('Al'), np.asarray(s, dtype=np.float64).reshape(M), Z[0], Z[1], t['zc'][0], t['zc'][1], jitter)
+
+
+def assert_unwritten(case, t, M, D):
+    """every finish-stage region at its capacity size: whatever lies outside the part the kernels write (include/zigp_diag.h) must come back
+    as the stage sentinel the hook put there -- a kernel that wrote with a wrong row stride, or past its compact part, would show"""
+    from zigp import _lib
+    SENT = _lib.STAGE_SENTINEL
+    Mq = (_rup(M[0], 16), _rup(M[1], 16))
+
+    def rest(name, a, written):
+        a = np.asarray(a)
+        mask = np.ones(a.shape, dtype=bool)
+        for sl in written:
+            mask[sl] = False
+        bad = a[mask] != SENT
+        assert not bad.any(), '%s: %d elements of %s outside what the kernels write were written' % (case, int(bad.sum()), name)
+        for sl in written:
+            assert not np.any(a[sl] == SENT), '%s: an element of %s the kernels write still holds the sentinel' % (case, name)
+
+    rest('klv', t['klv_cap'], [slice(0, 5)])
+    for k in ('gu', 'gs'):
+        rest(k, t[k + '_cap'], [slice(0, M[0] * M[1])])
+    for k in ('krow', 'krow_first', 'krow2'):
+        if k + '_cap' in t:
+            for q in range(2):
+                rest('%s[%d]' % (k, q), t[k + '_cap'][q], [slice(0, M[q] * (2 + 2 * D[q]))])
+    if 'G_cap' in t:
+        rest('G[0]', t['G_cap'][0], [(slice(0, Mq[0]), slice(0, Mq[0])), (slice(16, 16 + Mq[0]), slice(0, Mq[0]))])
+        rest('G[1]', t['G_cap'][1], [(slice(0, Mq[1]), slice(0, Mq[1]))])
+
+
+def check_G_and_krow_from_G(kernel, case, t, args, kl, f64, fld, M, krow_of=None):
+    """larger grids: the G rows k_kfl_finish<3> leaves (factor 0: G itself, factor 1: P Q2 = P X P) under the rule, their padding rows and
+    columns exact zeros, and krow recomputed from the TAPPED rows, so that stage 3's last lines are judged apart from the sandwich.
+    krow_of(q, G, aG, dtype) -> (value, S) overrides the RBF form of those lines (Matern factors)."""
+    w, K, P, Z, zc, jitter = args[0], args[1:3], args[3:5], args[11:13], args[13:15], args[15]
+    Mq = (_rup(M[0], 16), _rup(M[1], 16))
+    LD = np.longdouble
+    worst = {}
+    for q in range(2):
+        Gt = t['G'][q][:Mq[q]]
+        assert not np.any(Gt[M[q]:]) and not np.any(Gt[:, M[q]:]), '%s: rows / columns M .. Mq of the G region of factor %d' % (case, q)
+        key = 'G0' if q == 0 else 'PXP1'
+        worst[key] = _rule(kernel, case, key, Gt[:M[q], :M[q]], f64[key][0], fld[key][0], f64[key][1])
+        coef = (0.5 * M[1 - q]) if kl else 0.0
+        res = []
+        for dt in (np.float64, LD):
+            g = np.asarray(Gt[:M[q], :M[q]], dtype=dt)
+            if q == 1:
+                g = -g - dt(coef) * np.asarray(P[1], dtype=dt)
+            ag = np.abs(g) if q == 0 else np.abs(np.asarray(Gt[:M[q], :M[q]], dtype=dt)) + dt(coef) * np.abs(np.asarray(P[1], dtype=dt))
+            res.append(krow_of(q, g, ag, dt) if krow_of else kr.krow_from_G(g, ag, K[q], w['Kr%d' % q], Z[q], zc[q], jitter, dt))
+        worst['krow%d|G' % q] = _rule(kernel, case, 'krow%d|G' % q, t['krow'][q], res[0][0], res[1][0], res[0][1])
+    return worst
+
+
+def check_finish(case, large, t, Z, s, M, D, cap, jitter, kl):
+    """klv, krow0, krow1, gu, gs (larger grids: and G) of one latent of a tapped RBF step against kronf_ref in long double on the tapped inputs"""
+    sfx = 'l' if large else ''
+    Mq = (_rup(M[0], 16), _rup(M[1], 16))
+    args = finish_inputs(t, Z, s, M, cap, jitter)
+    d = [t['dvec'][q][:M[q]] for q in range(2)]
+    k64, kld = kr.kl_scalars(args[5], args[9], args[10], d[0], d[1]), kr.kl_scalars(args[5], args[9], args[10], d[0], d[1], dtype=np.longdouble)
+    worst = {}
+    for i, k in enumerate(('uAl', 'logs2', 'ds2')):
+        worst['klv%d' % i] = _rule('latent' + sfx, case, 'klv%d' % i, t['klv'][i:i + 1], np.reshape(k64[k][0], 1), np.reshape(kld[k][0], 1), np.reshape(k64[k][1], 1))
+    assert t['klv'][3] == t['dvec'][0][Mq[0]] and t['klv'][4] == t['dvec'][1][Mq[1]], '%s: klv[3], klv[4] are not the factor kernel\'s logdets' % case
+    f64, fld = kr.finish(*args, kl), kr.finish(*args, kl, dtype=np.longdouble)
+    for k in ('krow0', 'krow1', 'gu', 'gs'):
+        worst[k] = _rule('finish' + sfx, case, k, t[k[:4]][int(k[4])] if k.startswith('krow') else t[k], f64[k][0], fld[k][0], f64[k][1])
+    for q in range(2):
+        assert t['krow'][q].shape == (M[q], 2 + 2 * D[q]) and not np.any(t['krow'][q][:, 1 + 2 * D[q]]), '%s: krow column 1 + 2 D of factor %d is not exact 0' % (case, q)
+    if large:
+        worst.update(check_G_and_krow_from_G('finish' + sfx, case, t, args, kl, f64, fld, M))
+    else:
+        assert 'G' not in t
+    assert_unwritten(case, t, M, D)
+    return worst
+
+
+def _finish_case(engine, tag, p, X, Y, grids, D, lik='onoff', jitter=kron_nd.JITTER, scale=1.0, f_mu=0.0):
+    two = lik == 'onoff'
+    for kl in (True, False):
+        out = engine.test_kron_fused_step(p, X, Y, lik=lik, jitter=jitter, scale=scale, f_mu=f_mu, include_kl=kl)
+        cap, nb = _check_facts(out['facts'], grids, X.shape[0], len(grids))
+        assert out['kl'] == 0.0 or kl
+        for h, lt in enumerate('fg' if two else 'f'):
+            Z = p['Z' + lt]
+            check_finish('%s/%s kl=%d' % (tag, lt if two else lik, kl), cap == (1, 7), out['lat'][h], Z, p['u_%ss_sqrt' % lt], grids[h], D, cap, jitter, kl)
+
+
+@pytest.mark.parametrize('name', BOUND_CASES)
+def test_finish_bound_tier_on_the_fixtures_of_kron_nd(engine, name):
+    X, Y, p = kron_nd.problem(name)
+    k = kron_nd.CASES[name]
+    _finish_case(engine, name, p, X, Y, [k['f'], k['g'] or k['f']], k['D'], scale=kron_nd.case_scale(name))
+
+
+@pytest.mark.parametrize('name,lik', [('d31', 'gaussian'), ('d21-21', 'bernoulli'), ('L32', 'bernoulli')])
+def test_finish_bound_tier_heads(engine, name, lik):
+    X, Y, p = kron_nd.problem(name)
+    k = kron_nd.CASES[name]
+    y = Y if lik == 'gaussian' else (Y > 0).astype(np.float64)
+    _finish_case(engine, name, kron_nd.head_params(p), X, y, [k['f']], k['D'], lik=lik, scale=kron_nd.case_scale(name), f_mu=0.3)
+
+
+def test_finish_bound_tier_at_the_illconditioned_pptr_init(engine):
+    from test_gpu_pptr_params import _pptr_params
+    Xtr, Ytr, xb, yb, p = _pptr_params((32, 32))
+    D = (p['Zf'][0].shape[1], p['Zf'][1].shape[1])
+    _finish_case(engine, 'pptr32', p, xb, yb, [(32, 32), (32, 32)], D, jitter=1e-5, scale=Xtr.shape[0] / 1000.0)
+
+
+# ---- edges: N = 33; the smallest grid the entry point accepts is ONE point per factor (validate_kron refuses M <= 0 only), so (1, 1) and
+# (1, 112) stand where a refusal would have asked for 2.  The problems are kron_nd.edge_problem (lengthscale
+# constant kron_nd.EDGE_C); tests/test_cpu_kronf_finish_ref.py shows that every mutation of the stage is caught on these very problems.
+def _edge_cases():
+    return [(g, D) for g in kron_nd.EDGE_GRIDS for D in kron_nd.EDGE_DS]
+
+
+@pytest.mark.parametrize('grid,D', _edge_cases(), ids=lambda v: 'x'.join(map(str, v)))
+def test_finish_edges(engine, grid, D):
+    X, Y, p = kron_nd.edge_problem(grid, D)
+    _finish_case(engine, 'edge%dx%d D%d%d' % (grid + D), p, X, Y, [grid, grid], D, scale=7.0)
+
+
+@pytest.mark.parametrize('shape', ['mix', 'under', 'Lrmix'])
+def test_finish_edges_two_latents_with_different_grids_and_a_head(engine, shape):
+    gf, gg = SHAPES[shape]
+    for D in ((1, 1), (7, 7)):
+        X, Y, p = kron_nd.edge_problem(gf, D, gg)
+        _finish_case(engine, 'edge-%s D%d%d' % ((shape,) + D), p, X, Y, [gf, gg], D, scale=7.0)
+    _finish_case(engine, 'edge-%s head' % shape, kron_nd.head_params(p), X, Y, [gf], D, lik='gaussian', scale=7.0, f_mu=0.1)
+
+
+def test_a_grid_without_points_is_refused(engine):
+    X, Y, p = kron_nd.problem('d21-12')
+    q = dict(p)
+    q['Zf'] = [p['Zf'][0][:0], p['Zf'][1]]
+    q['u_fm'], q['u_fs_sqrt'] = p['u_fm'][:0], p['u_fs_sqrt'][:0]
+    with pytest.raises(ValueError):
+        engine.test_kron_fused_step(q, X, Y)
+
+
+@pytest.mark.parametrize('name', ['d31', 'd77', 'L32'])
+def test_returned_gradients_are_the_host_chain_rule_of_the_tapped_results(engine, name):
+    """kron_assemble_grads: the gradients a tapped step returns against kronf_ref.assemble of the tapped krow, gu, gs -- host double arithmetic,
+    a few operations per element: 16 eps S."""
+    X, Y, p = kron_nd.problem(name)
+    out = engine.test_kron_fused_step(p, X, Y, jitter=kron_nd.JITTER, scale=kron_nd.case_scale(name))
+    check_assemble(name, out, p, 'fg')
+
+
+def check_assemble(case, out, p, tags):
+    g = out['grads']
+    for h, tag in enumerate(tags):
+        t = out['lat'][h]
+        Z, ell, var = _unpack(p, tag)
+        s_gv = np.sum(np.asarray(t['cot'][1], dtype=np.longdouble))
+        a64 = kr.assemble(t['krow'], t['gu'], t['gs'], ell, var, float(s_gv))
+        ald = kr.assemble(t['krow'], t['gu'], t['gs'], ell, var, s_gv, dtype=np.longdouble)
+        pairs = [('u', g['u_%sm' % tag].reshape(t['gu'].shape), 0.0), ('s', g['u_%ss_sqrt' % tag].reshape(t['gs'].shape), 0.0)]
+        for q in range(2):
+            # the variance cotangents are summed over the points on the device in another order than here: their sum enters with the sum of
+            # their absolute values
+            sv = float(np.sum(np.abs(t['cot'][1]))) * var[1 - q]
+            pairs += [('Z%d' % q, g['Z' + tag][q], 0.0), ('ell%d' % q, g['ell_' + tag][q].reshape(-1), 0.0), ('var%d' % q, np.reshape(g['var_' + tag][q], 1), sv)]
+        worst = 0.0
+        for k, got, extra in pairs:
+            want, S = (ald[k[:-1]][int(k[-1])] if k[-1] in '01' else ald[k])
+            S64 = np.asarray(a64[k[:-1]][int(k[-1])][1] if k[-1] in '01' else a64[k][1], dtype=np.float64)
+            S64 = np.reshape(S64, np.shape(got)) + extra
+            err = np.asarray(np.abs(np.asarray(got, dtype=np.longdouble) - np.reshape(want, np.shape(got))), dtype=np.float64)
+            live = S64 > 0
+            r = float(np.max(err[live] / S64[live] / EPS)) if live.any() else 0.0
+            worst = max(worst, r)
+            assert np.all(err <= 16 * EPS * S64), '%s/%s: d %s is not the chain rule of the tapped results: err / (eps S) = %.2f' % (case, tag, k, r)
+        _log('assemble', '%s/%s' % (case, tag), 'max err / (eps S) = %.3f' % worst)
 
 
 # =====================================================================================================================================

@@ -22,15 +22,7 @@ GOLD = os.path.join(os.path.dirname(__file__), 'golden')
 NAMES = ('gfmean', 'gfvar', 'gfmeanu', 'fmean', 'fvar', 'gmean', 'gvar', 'ephi_g', 'evar_phi_g')
 
 
-def _pptr_params(grid):
-    from onofftf.model import init_params, engine_params
-    d = np.load(os.path.join(GOLD, 'pptr.npz'))
-    Xtr, Ytr = d['Xtrain'].copy(), d['Ytrain']
-    Xtr[:, 2] /= 1000.0                                   # scripts/create_cvsplits.py:17
-    np.random.seed(7)
-    p = engine_params(init_params(Xtr, grid, grid, kmeans_seed=3))
-    idx = np.random.RandomState(11).permutation(Xtr.shape[0])[:1000]     # a minibatch as DataSet.next_batch hands it out: shuffled rows
-    return Xtr, Ytr, np.ascontiguousarray(Xtr[idx]), np.ascontiguousarray(Ytr[idx]), p
+from kron_nd import pptr_problem as _pptr_params      # noqa: E402  (the fixture lives with the other Kronecker problems; the name is kept for its users)
 
 
 def _inv_compensated():

@@ -2145,6 +2145,7 @@ static int kf_stage_latent(KfRun& s, KfTap* tap) {
       double* const host[9] = {tl.U, tl.S2, tl.T0, tl.T1, tl.Al, tl.AlF, tl.S2F, tl.AlTF, tl.S2TF};
       const double* const dev[9] = {jb.U, jb.S2, jb.T0, jb.T1, jb.Al, jb.AlF, jb.S2F, jb.AlTF, jb.S2TF};
       for (int i = 0; i < 9; ++i) ZIGP_TRY(tap->snap(c, host[i], dev[i], n01));
+      ZIGP_TRY(tap->snap(c, tl.klv, jb.klv, 8));
     }
   }
   return 0;
@@ -2321,10 +2322,13 @@ static int kf_stage_reduce(KfRun& s, KfTap* tap, const KfArgs& ka, int nparts) {
 }
 
 // work buffers -> the result block: krow of both factors, the gradients of u and s
-static int kf_stage_finish(KfRun& s) {
+template <bool TAP>
+static int kf_stage_finish(KfRun& s, KfTap* tap) {
   zigp_ctx* c = s.c;
   const int nlat = s.nlat;
   const KfWork& wl = s.wl;
+  // the krow regions of the result block at their capacity sizes (kf_prepare: RES_KROW0 .. RES_GU)
+  const size_t n_krow[2] = {s.RES_KROW1 - s.RES_KROW0, s.RES_GU - s.RES_KROW1};
   KflFinishArgs fa;
   memset(&fa, 0, sizeof(fa));
   for (int h = 0; h < nlat; ++h) {
@@ -2346,9 +2350,26 @@ static int kf_stage_finish(KfRun& s) {
     int nbmax = 1;
     for (int h = 0; h < nlat; ++h) nbmax = std::max(nbmax, std::max(s.Mq[h][0], s.Mq[h][1]) / 16);
     const dim3 grid(nbmax, 2, nlat);
+    if constexpr (TAP) {      // the regions stage 3 leaves its G rows in hold the stage sentinel before stage 1: what comes back as the sentinel was never written
+      const size_t rmax = (size_t)wl.ldw * wl.ldw;
+      for (int h = 0; h < nlat; ++h)
+        for (int q = 0; q < 2; ++q)
+          if (tap->s->lat[h].G[q]) ZIGP_HIP(c, hipMemsetAsync(s.lat(h) + s.LAT_SCR + (size_t)q * s.SCR_SET + 2 * rmax, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * rmax, c->stream));
+    }
     hipLaunchKernelGGL(k_kfl_finish<1>, grid, dim3(KFL_FIN_THREADS), 0, c->stream, fa);
     hipLaunchKernelGGL(k_kfl_finish<2>, grid, dim3(KFL_FIN_THREADS), 0, c->stream, fa);
     hipLaunchKernelGGL(k_kfl_finish<3>, grid, dim3(KFL_FIN_THREADS), 0, c->stream, fa);
+    if constexpr (TAP) {      // stage 3's G rows (the Q region of the factor's scratch set), and the krow rows k_kfl_krow_kinds is about to rewrite
+      ZIGP_HIP(c, hipGetLastError());
+      const size_t rmax = (size_t)wl.ldw * wl.ldw;
+      for (int h = 0; h < nlat; ++h) {
+        const zigp_kronf_tap_latent& tl = tap->s->lat[h];
+        for (int q = 0; q < 2; ++q) {
+          ZIGP_TRY(tap->snap(c, tl.G[q], s.lat(h) + s.LAT_SCR + (size_t)q * s.SCR_SET + 2 * rmax, rmax));
+          if (s.kinds) ZIGP_TRY(tap->snap(c, tl.krow_first[q], q == 0 ? fa.job[h].krow0 : fa.job[h].krow1, n_krow[q]));
+        }
+      }
+    }
     if (s.kinds) hipLaunchKernelGGL(k_kfl_krow_kinds, grid, dim3(KFL_FIN_THREADS), 0, c->stream, fa, s.kinds);      // the krow rows of the Matern factors
   } else {
     KfFinishArgs fs;
@@ -2372,12 +2393,41 @@ static int kf_stage_finish(KfRun& s) {
         if (kf_kind_of(s.kinds, h, 1) != KERN_RBF) j2.K1 = buf + KF_KD_K;
         j2.work = buf + KF_KD_WORK; j2.krow0 = buf + KF_KD_KROW0; j2.krow1 = buf + KF_KD_KROW1; j2.gu = buf + KF_KD_GU; j2.gs = buf + KF_KD_GS;
       }
+      if constexpr (TAP) {    // the first run's krow; the second run's scratch (K' images, work', krow', gu', gs') holds the stage sentinel wherever its kernels do not write (nothing reads it there)
+        for (int h = 0; h < nlat; ++h) {
+          const zigp_kronf_tap_latent& tl = tap->s->lat[h];
+          ZIGP_TRY(tap->snap(c, tl.krow_first[0], fs.job[h].krow0, n_krow[0])); ZIGP_TRY(tap->snap(c, tl.krow_first[1], fs.job[h].krow1, n_krow[1]));
+          if (tl.Kd[0] || tl.Kd[1] || tl.krow2[0] || tl.krow2[1]) ZIGP_HIP(c, hipMemsetAsync(ka.job[h].buf, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * KF_KD_TOTAL, c->stream));
+        }
+      }
       hipLaunchKernelGGL(k_kf_kd_prepare, dim3(3, nlat), dim3(256), 0, c->stream, ka, s.kinds);
+      if constexpr (TAP) {
+        ZIGP_HIP(c, hipGetLastError());
+        for (int h = 0; h < nlat; ++h) {
+          const zigp_kronf_tap_latent& tl = tap->s->lat[h];
+          ZIGP_TRY(tap->snap(c, tl.Kd[0], ka.job[h].buf, (size_t)KF_KD_K)); ZIGP_TRY(tap->snap(c, tl.Kd[1], ka.job[h].buf + KF_KD_K, (size_t)KF_KD_K));
+          ZIGP_TRY(tap->snap(c, tl.work2, ka.job[h].buf + KF_KD_WORK, (size_t)KF_W_TOTAL));
+        }
+      }
       hipLaunchKernelGGL(k_kf_finish, dim3(2, nlat), dim3(1024), KF_FIN_LDS, c->stream, f2);
+      if constexpr (TAP) {
+        ZIGP_HIP(c, hipGetLastError());
+        for (int h = 0; h < nlat; ++h) {
+          const zigp_kronf_tap_latent& tl = tap->s->lat[h];
+          ZIGP_TRY(tap->snap(c, tl.krow2[0], f2.job[h].krow0, (size_t)KF_KD_KROW1 - KF_KD_KROW0)); ZIGP_TRY(tap->snap(c, tl.krow2[1], f2.job[h].krow1, (size_t)KF_KD_GU - KF_KD_KROW1));
+        }
+      }
       hipLaunchKernelGGL(k_kf_krow_merge, dim3(2, nlat), dim3(256), 0, c->stream, ka, s.kinds);
     }
   }
   ZIGP_HIP(c, hipGetLastError());
+  if constexpr (TAP) {        // what the LAST launch of the stage leaves in the result block
+    for (int h = 0; h < nlat; ++h) {
+      const zigp_kronf_tap_latent& tl = tap->s->lat[h];
+      ZIGP_TRY(tap->snap(c, tl.krow[0], fa.job[h].krow0, n_krow[0])); ZIGP_TRY(tap->snap(c, tl.krow[1], fa.job[h].krow1, n_krow[1]));
+      ZIGP_TRY(tap->snap(c, tl.gu, fa.job[h].gu, s.RES_GS - s.RES_GU)); ZIGP_TRY(tap->snap(c, tl.gs, fa.job[h].gs, s.RES_SIZE - s.RES_GS));
+    }
+  }
   return 0;
 }
 
@@ -2386,6 +2436,15 @@ static int kf_step(KfRun& s, KfTap* tap, const double* Xd, const double* Yd) {
   zigp_ctx* c = s.c;
   const bool predict = s.k->predict;
   if (c->comm && !predict) ZIGP_HIP(c, hipMemsetAsync(s.ks->res.p, 0, sizeof(double) * s.RES_INFO, c->stream));   // parts a value-only / single-latent step leaves unwritten
+  if constexpr (TAP) {      // the stage tests see what a step does NOT write: the latents' result blocks hold the stage sentinel first (nothing reads an
+    // unwritten part: kf_gather takes klv[0..4] and the compact krow, gu, gs).  A data-parallel step has just cleared the block instead: +0 there.
+    bool wanted = false;      // a step with none of these taps enqueues nothing
+    for (int h = 0; h < s.nlat; ++h) {
+      const zigp_kronf_tap_latent& tl = tap->s->lat[h];
+      wanted = wanted || tl.klv || tl.krow[0] || tl.krow[1] || tl.gu || tl.gs || tl.krow_first[0] || tl.krow_first[1];
+    }
+    if (wanted && !c->comm && !predict) ZIGP_HIP(c, hipMemsetAsync(s.ks->res.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * s.nlat * s.RES_SIZE, c->stream));
+  }
   ZIGP_TRY(kf_stage_factor<TAP>(s, tap));
   if (predict) ZIGP_TRY(request_info(c, &s.hinfo));   // value / gradient steps: the status slots come back with the result block
   ZIGP_TRY(kf_stage_latent<TAP>(s, tap));
@@ -2398,7 +2457,7 @@ static int kf_step(KfRun& s, KfTap* tap, const double* Xd, const double* Yd) {
     if (s.pl.large) ZIGP_TRY(kf_stage_backward_large<TAP>(s, tap, ka, nparts));
     else ZIGP_TRY(kf_stage_backward_small<TAP>(s, tap, ka, nparts));
     ZIGP_TRY(kf_stage_reduce<TAP>(s, tap, ka, nparts));
-    ZIGP_TRY(kf_stage_finish(s));
+    ZIGP_TRY(kf_stage_finish<TAP>(s, tap));
   }
   if (c->comm) {   // data-parallel run: the block (cleared at the start of the step) is summed over ranks where it lies
     // a rank that does not count the KL (include_kl = 0) must not add its scalars, which the latent kernel writes regardless

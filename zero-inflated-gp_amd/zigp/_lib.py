@@ -168,7 +168,9 @@ class zigp_kronf_tap_factor(C.Structure):   # include/zigp_diag.h
 
 class zigp_kronf_tap_latent(C.Structure):   # include/zigp_diag.h
     _fields_ = [('fac', zigp_kronf_tap_factor * 2), ('U', dp), ('S2', dp), ('T0', dp), ('T1', dp), ('Al', dp),
-                ('AlF', dp), ('S2F', dp), ('AlTF', dp), ('S2TF', dp), ('part', dp), ('cot', dp), ('work', dp), ('inject', dp)]
+                ('AlF', dp), ('S2F', dp), ('AlTF', dp), ('S2TF', dp), ('part', dp), ('cot', dp), ('work', dp), ('inject', dp),
+                ('klv', dp), ('krow', dp * 2), ('gu', dp), ('gs', dp), ('krow_first', dp * 2), ('Kd', dp * 2), ('work2', dp), ('krow2', dp * 2),
+                ('G', dp * 2)]
 
 
 KFF_FACTS = ('large', 'large_exact', 'nb0c', 'nb1c', 'nb0_f', 'nb1_f', 'nb0_g', 'nb1_g', 'Npad', 'ntiles', 'tpw_fwd', 'tpw_bwd', 'nparts', 'tps',

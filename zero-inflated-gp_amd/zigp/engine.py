@@ -1844,7 +1844,11 @@ class DenseEngine:
         kron_head_elbo ('gaussian' / 'bernoulli': the f fields only).  inject: None, or one entry per latent, each None or [4][N] = gm, gv,
         dq0, dq1 copied over the point-wise kernel's cotangents before the backward launch.  taps=False: no snapshot at all.
         Returns dict(elbo_data, kl, grads (as kron_elbo / kron_head_elbo), facts {name: int}, lat [per latent: dict(K, P, PF, dvec, Zs, zc --
-        lists over the two factors --, U, S2, T0, T1, Al, AlF, S2F, AlTF, S2TF, part, cot, work)])."""
+        lists over the two factors --, U, S2, T0, T1, Al, AlF, S2F, AlTF, S2TF, part, cot, work; of the finish stage, trimmed to what the kernels
+        write: klv (5), gu, gs (M0, M1), krow [2] (M_p, 2 + 2 D_p); a step with a Matern factor: krow_first [2] and, small grids, Kd [2] (32, 128),
+        work2, krow2 [2]; larger grids: G [2] -- (16 + Mq0, Mq0): G of factor 0 then the low words of Q2, and (Mq1, Mq1): P Q2 of factor 1; and
+        each of klv, gu, gs, krow, krow_first, krow2, G once more as '<name>_cap': the whole region at its capacity size, where an element no kernel
+        wrote holds _lib.STAGE_SENTINEL)])."""
         two = lik == 'onoff'
         tags = ('f', 'g') if two else ('f',)
         sp, keep, dims = self._pack_kron(p, tags=tags)
@@ -1864,6 +1868,8 @@ class DenseEngine:
         Ms = [(keep[t][0].shape[0], keep[t][1].shape[0]) for t in tags]
         small = all(m0 <= 32 and m1 <= 32 for m0, m1 in Ms)
         R0, R1 = (32, 32) if small else (16, 112)                     # capacity rows (kf_plan)
+        # the step follows the factor kinds of the CONTEXT: with a Matern factor it runs the Matern additions of the finish stage
+        matern = any(self.get_kron_kernel(0 if not two else h, q) != 'rbf' for h in range(len(tags)) for q in range(2))
         ldw = max(R0, R1)
         Npad = max(1024, -(-N // 1024) * 1024)
         lat, hold = [], []
@@ -1885,6 +1891,36 @@ class DenseEngine:
                         setattr(t.fac[q], k, ptr(d[k][q]))
                 for k in ('U', 'S2', 'T0', 'T1', 'Al', 'AlF', 'S2F', 'AlTF', 'S2TF', 'part', 'cot', 'work'):
                     setattr(t, k, ptr(d[k]))
+                # ---- the finish stage: regions at their capacity sizes (W = 2 + 2 * 8 doubles per capacity row of a krow region)
+                Rc, Wc, W = (R0, R1), 18, (2 + 2 * dims[0], 2 + 2 * dims[1])
+                raw = dict(klv=np.zeros(8), gu=np.zeros(R0 * R1), gs=np.zeros(R0 * R1), krow=[np.zeros(Rc[q] * Wc) for q in range(2)])
+                if matern:
+                    raw['krow_first'] = [np.zeros(Rc[q] * Wc) for q in range(2)]
+                    if small:
+                        raw.update(Kd=[np.zeros((32, 128)) for q in range(2)], work2=np.zeros(d['work'].size), krow2=[np.zeros(32 * Wc) for q in range(2)])
+                if not small:
+                    raw['G'] = [np.zeros((ldw, ldw)) for q in range(2)]
+                for k, v in raw.items():
+                    if isinstance(v, list):
+                        setattr(t, k, (_lib.dp * 2)(ptr(v[0]), ptr(v[1])))
+                    else:
+                        setattr(t, k, ptr(v))
+                hold.append(raw)
+                # every region whole under '<name>_cap' -- what the kernels do not write comes back as _lib.STAGE_SENTINEL (include/zigp_diag.h) --
+                # and, under the plain name, the part the kernels write (a view of it)
+                for k, v in raw.items():
+                    if k not in ('Kd', 'work2'):
+                        d[k + '_cap'] = v
+                Mh = (M0, M1)
+                d['klv'] = raw['klv'][:5]
+                d['gu'], d['gs'] = raw['gu'][:M0 * M1].reshape(M0, M1), raw['gs'][:M0 * M1].reshape(M0, M1)
+                for k in ('krow', 'krow_first', 'krow2'):
+                    if k in raw:
+                        d[k] = [raw[k][q][:Mh[q] * W[q]].reshape(Mh[q], W[q]) for q in range(2)]
+                if 'Kd' in raw:
+                    d['Kd'], d['work2'] = raw['Kd'], raw['work2']
+                if 'G' in raw:      # factor 0: G rows, then the low words of Q2 (rows 16 ..); factor 1: P Q2
+                    d['G'] = [raw['G'][0][:16 + Mq[0], :Mq[0]], raw['G'][1][:Mq[1], :Mq[1]]]
             if inject is not None and inject[h] is not None:
                 inj = as_f64(inject[h], (4, N))
                 hold.append(inj)
