@@ -400,6 +400,86 @@ typedef struct zigp_stage_kron_fused {
 } zigp_stage_kron_fused;
 int zigp_test_kron_fused_step(zigp_ctx* ctx, const zigp_stage_kron_fused* a);
 
+/* ---- The update kernels of the device fit loops, through the host loops themselves with the gradient step replaced by caller-supplied
+ * results.  Nothing but the update / image kernels is launched; no rows and (Kronecker) no resident data set are needed.  Snapshots are
+ * stream-ordered device-to-device copies behind the launches, downloaded after the loop's one synchronisation.  Both hooks return what the
+ * loop returns (ZIGP_OK, or ZIGP_ENOTPD for an injected Cholesky status: the snapshots and records are filled in either case) and leave
+ * the context usable. ---- */
+/* k_fit_update<false> (lik = ZIGP_LIK_ONOFF, the 17 blocks of zigp_kron_fit_steps) or k_fit_update<true> (a head, the 10 blocks of
+ * zigp_kron_head_fit_steps) through kf_fit_run: the production descriptor, grid, launches, lr_sq / lr_den, download and failure decoding.
+ * Step i copies res + i * n_res into the result block in place of running the step.  Result block (doubles, offsets in facts): per latent h
+ * at h * RES_SIZE: klv[5] at RES_KLV, krow of factor q at RES_KROW0 / RES_KROW1 written compactly as [M_q][2 + 2 D_q], gu / gs [M0 M1] at
+ * RES_GU / RES_GS; then pws[8] at RES_PWS (data term, d noise, sum gv_f, sum gv_g, sum gm_f, -, -, ranks that count the KL) and at
+ * RES_INFO four Cholesky status slots of 2 ints each (the first int of slot j is job j's pivot, 0 = fine).
+ * res == NULL: only facts is filled (the layout query the caller sizes res, snap_img with).
+ * Refused (ZIGP_EARG) like the fit calls: a grid beyond the fused kernels (a factor dimension above 7 included), zigp_set_kron_panels. */
+enum { ZIGP_KFU_RES_KLV = 0, ZIGP_KFU_RES_KROW0, ZIGP_KFU_RES_KROW1, ZIGP_KFU_RES_GU, ZIGP_KFU_RES_GS, ZIGP_KFU_RES_SIZE, ZIGP_KFU_RES_PWS,
+       ZIGP_KFU_RES_INFO, ZIGP_KFU_N_RES,
+       ZIGP_KFU_GRID,                 /* workgroups of every update launch: the big ones and the hyperparameter one */
+       ZIGP_KFU_BIG_OFF,              /* [9]: first element of each big block in the big workgroups' element order; [8] = their total */
+       ZIGP_KFU_HYP_OFF = ZIGP_KFU_BIG_OFF + 9,    /* [10]: the same for the hyperparameter workgroup */
+       ZIGP_KFU_N_IMG = ZIGP_KFU_HYP_OFF + 10,     /* doubles of the parameter image with both hyperparameter blocks */
+       ZIGP_KFU_OFF_HYP, ZIGP_KFU_OFF_HYP2,        /* the block step i reads is HYP for even i, HYP2 for odd i; its update writes the other */
+       ZIGP_KFU_OFF_Z,                /* [4]: image offset of Z of (latent, factor) = (0,0) (0,1) (1,0) (1,1) */
+       ZIGP_KFU_OFF_U = ZIGP_KFU_OFF_Z + 4, ZIGP_KFU_OFF_S = ZIGP_KFU_OFF_U + 2,   /* [2] each */
+       ZIGP_KFU_KH_SIZE = ZIGP_KFU_OFF_S + 2, ZIGP_KFU_KH_FAC, ZIGP_KFU_KH_INV, ZIGP_KFU_KH_ZC, ZIGP_KFU_KH_ELL, ZIGP_KFU_KH_VAR,
+       ZIGP_KFU_KH_NOISE, ZIGP_KFU_KH_FMU,         /* layout of a hyperparameter block: record (2 h + q) * KH_FAC, slots inside it */
+       ZIGP_KFU_COUNT };
+typedef struct zigp_stage_kron_fit_update {
+  int32_t lik;                  /* ZIGP_LIK_ONOFF, ZIGP_LIK_GAUSSIAN or ZIGP_LIK_BERNOULLI */
+  int32_t n_steps;
+  const zigp_kron_params* shape;   /* M0f, M1f, (M0g, M1g,) D0, D1; the pointers are not read */
+  const double* lr;             /* per block (17 or 10) */
+  const int32_t* positive;
+  const int32_t* trainable;     /* heads; NULL: every block.  Not read for ZIGP_LIK_ONOFF */
+  double beta1, beta2, eps;
+  int64_t t0, n_free;
+  double *x, *m, *v;            /* in / out [n_free], as the fit calls */
+  const double* res;            /* [n_steps][n_res] or NULL */
+  int64_t n_res, n_img;         /* must equal facts' (checked when res != NULL) */
+  double *snap_x, *snap_m, *snap_v;   /* out [1 + n_steps][n_free]: behind the initial image launch, then behind every update launch; any may be NULL */
+  double* snap_img;             /* out [1 + n_steps][n_img], may be NULL */
+  double* hist;                 /* out [n_steps][2]: the device history as downloaded (data term, KL); may be NULL */
+  int32_t* fail;                /* out [4]: the device failure record {1 + step, job, pivot, -}; may be NULL */
+  double *elbo_data, *kl;       /* out [n_steps]: the history as the entry points return it (NaN from a failing step on); may be NULL */
+  int64_t* steps_applied;       /* out, may be NULL */
+  int64_t* facts;               /* out [ZIGP_KFU_COUNT], may be NULL */
+} zigp_stage_kron_fit_update;
+int zigp_test_kron_fit_update(zigp_ctx* ctx, const zigp_stage_kron_fit_update* a);
+
+/* k_dense_fit_image, k_dense_fit_image_tri and k_dense_fit_update through dense_fit_steps (mode = ZIGP_FIT_*): its descriptor, grids, launches
+ * and download.  Step i takes packed + i * n_packed and info + 2 i in place of k_gather_rows + the step + k_dense_pack.  The packed vector has
+ * the layout of zigp_stage_pack::out: 16 header doubles (data term, KL, d var_f, d var_g, d noise, ...), then per latent dZ (M, D), du (M),
+ * ds (M; ZIGP_FIT_WHITE_FULL: the lower triangle of dLq in row-major order, M (M + 1) / 2), dell (D).  A data set must be resident
+ * (zigp_set_data; any rows of the shape's D): the loop plans its step although the hook does not run it.
+ * Snapshots behind every image launch (slot 0: the initial one, slot 1 + i: the one behind update i) and, for x / m / v, the same slots. */
+enum { ZIGP_DFU_IMG_Z = 0,            /* [2] each: f, g */
+       ZIGP_DFU_IMG_ELL = 2, ZIGP_DFU_IMG_U = 4, ZIGP_DFU_IMG_S = 6, ZIGP_DFU_IMG_ZS = 8, ZIGP_DFU_MP = 10,
+       ZIGP_DFU_N_IMG = 12, ZIGP_DFU_N_PACKED, ZIGP_DFU_GRID, ZIGP_DFU_TGRID,
+       ZIGP_DFU_DH_SIZE, ZIGP_DFU_DH_LAT, ZIGP_DFU_DH_INV, ZIGP_DFU_DH_ELL, ZIGP_DFU_DH_SCALE, ZIGP_DFU_DH_VAR, ZIGP_DFU_DH_PIVTOL, ZIGP_DFU_DH_NOISE,
+       ZIGP_DFU_COUNT };
+typedef struct zigp_stage_dense_fit_update {
+  int32_t mode, n_steps;
+  const zigp_params* shape;     /* Mf, Mg, D */
+  const zigp_fit_opts* opts;
+  int64_t t0, n_free;
+  double jitter;
+  double *x, *m, *v;            /* in / out [n_free] */
+  const double* packed;         /* [n_steps][n_packed] or NULL: only facts is filled */
+  const int32_t* info;          /* [n_steps][2] */
+  int64_t n_packed, n_img;      /* must equal facts' (checked when packed != NULL) */
+  double *snap_x, *snap_m, *snap_v;   /* out [1 + n_steps][n_free], any may be NULL */
+  double* snap_img;             /* out [1 + n_steps][n_img]: the parameter image at its padded size */
+  double* snap_H;               /* out [1 + n_steps][DH_SIZE] */
+  double* snap_Lraw[2];         /* out [1 + n_steps][M_h * M_h], ZIGP_FIT_WHITE_FULL only */
+  double* hist;                 /* out [n_steps][2] as downloaded */
+  int32_t* fail;                /* out [4] */
+  double *elbo_data, *kl;       /* out [n_steps] as the entry points return them */
+  int64_t* steps_applied;
+  int64_t* facts;               /* out [ZIGP_DFU_COUNT] */
+} zigp_stage_dense_fit_update;
+int zigp_test_dense_fit_update(zigp_ctx* ctx, const zigp_stage_dense_fit_update* a);
+
 #ifdef __cplusplus
 }
 #endif

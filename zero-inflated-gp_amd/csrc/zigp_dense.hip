@@ -1329,9 +1329,30 @@ namespace {
 // One loop for the three parametrisations (include/zigp.h ZIGP_FIT_*).  `mode` decides the layout of blocks 4 and 5, the image kernels and
 // DenseCall::par, i.e. which chunk lists dense_plan plans and which launches dense_step makes; `legacy` is zigp_fit_steps, which
 // refuses while the context's own whiten / q_full flags are on -- zigp_fit_steps_mode neither reads nor changes them.
+// State of the tapped loop: the caller's packed vectors and status ints on the device, and the snapshots x | m | v | image | H | Lraw_f |
+// Lraw_g, one slot behind every image launch.
+struct DenseFitTap {
+  DevBuf packed, info, snaps;
+  size_t n_packed, slot, n[5];
+  const double* src[5];
+  int taken;
+  int snap(zigp_ctx* c) {
+    double* q = snaps.p + (size_t)taken++ * slot;
+    for (int j = 0; j < 5; ++j) {
+      if (n[j]) ZIGP_HIP(c, hipMemcpyAsync(q, src[j], sizeof(double) * n[j], hipMemcpyDeviceToDevice, c->stream));
+      q += n[j];
+    }
+    return 0;
+  }
+};
+struct DenseFitNoTap {};
+// TAP (zigp_test_dense_fit_update, include/zigp_diag.h): step i's packed vector and Cholesky status come from the caller in place of
+// k_gather_rows + dense_step + dense_pack, and the state, the parameter image, the block H and the Lraw blocks are snapshot -- device to
+// device, on the loop's stream -- behind every image launch.
+template <bool TAP>
 int dense_fit_steps(zigp_ctx* c, int32_t mode, bool legacy, const zigp_params* shape, const zigp_fit_opts* o, double* free_state, double* adam_m,
                     double* adam_v, int64_t n_free, int64_t t0, int32_t n_steps, const int64_t* rows, int64_t batch, double jitter, double scale,
-                    int32_t include_kl, double* elbo_data, double* kl) {
+                    int32_t include_kl, double* elbo_data, double* kl, const zigp_stage_dense_fit_update* tap = nullptr) {
   if (!c) return ZIGP_EARG;
   const std::string who = legacy ? "zigp_fit_steps" : "zigp_fit_steps_mode";
   auto bad = [&](const char* what) { return fail_arg(c, (who + ": " + what).c_str()); };
@@ -1443,6 +1464,33 @@ int dense_fit_steps(zigp_ctx* c, int32_t mode, bool legacy, const zigp_params* s
     }
     d.img_Z[h] = (int)off[h][0]; d.img_ell[h] = (int)off[h][1]; d.img_u[h] = (int)off[h][2]; d.img_s[h] = (int)off[h][3]; d.img_Zs[h] = (int)off[h][4];
   }
+  const dim3 ugrid(ceil_div(n_free, DFIT_THREADS));
+  const dim3 tgrid(ceil_div((int64_t)std::max(M[0], M[1]) * std::max(M[0], M[1]), DFIT_THREADS), 2);
+  std::conditional_t<TAP, DenseFitTap, DenseFitNoTap> ts;      // the production loop carries nothing of the hook
+  if constexpr (TAP) {
+    const size_t n_packed = (size_t)d.goff[7] + D;
+    ts.n_packed = n_packed; ts.taken = 0;
+    const size_t sn[5] = {3 * nf, total, (size_t)DH_SIZE, tri ? (size_t)M[0] * M[0] : 0, tri ? (size_t)M[1] * M[1] : 0};
+    const double* const ssrc[5] = {c->fit.p, c->parm.p, H, c->lat[0].Lraw.p, c->lat[1].Lraw.p};
+    ts.slot = 0;
+    for (int j = 0; j < 5; ++j) { ts.n[j] = sn[j]; ts.src[j] = ssrc[j]; ts.slot += sn[j]; }
+    int64_t f[ZIGP_DFU_COUNT] = {0};
+    for (int h = 0; h < 2; ++h) {
+      f[ZIGP_DFU_IMG_Z + h] = d.img_Z[h]; f[ZIGP_DFU_IMG_ELL + h] = d.img_ell[h]; f[ZIGP_DFU_IMG_U + h] = d.img_u[h]; f[ZIGP_DFU_IMG_S + h] = d.img_s[h];
+      f[ZIGP_DFU_IMG_ZS + h] = d.img_Zs[h]; f[ZIGP_DFU_MP + h] = c->lat[h].Mp;
+    }
+    f[ZIGP_DFU_N_IMG] = (int64_t)total; f[ZIGP_DFU_N_PACKED] = (int64_t)n_packed; f[ZIGP_DFU_GRID] = ugrid.x; f[ZIGP_DFU_TGRID] = tri ? tgrid.x : 0;
+    const int64_t dh[8] = {DH_SIZE, DH_LAT, DH_INV, DH_ELL, DH_SCALE, DH_VAR, DH_PIVTOL, DH_NOISE};
+    memcpy(f + ZIGP_DFU_DH_SIZE, dh, sizeof(dh));
+    if (tap->facts) memcpy(tap->facts, f, sizeof(f));
+    if (!tap->packed) return ZIGP_OK;      // the layout query
+    if (!tap->info || tap->n_packed != (int64_t)n_packed || tap->n_img != (int64_t)total) return bad("info missing, or n_packed / n_img differ from the facts");
+    ZIGP_ENSURE(c, ts.packed, (size_t)n_steps * n_packed);
+    ZIGP_ENSURE(c, ts.info, (size_t)n_steps);      // two ints per step
+    ZIGP_ENSURE(c, ts.snaps, (size_t)(1 + n_steps) * ts.slot);
+    ZIGP_HIP(c, hipMemcpyAsync(ts.packed.p, tap->packed, sizeof(double) * n_steps * n_packed, hipMemcpyHostToDevice, c->stream));
+    ZIGP_HIP(c, hipMemcpyAsync(ts.info.p, tap->info, sizeof(int32_t) * 2 * n_steps, hipMemcpyHostToDevice, c->stream));
+  }
   {
     ZIGP_PINNED(c, hst, n_down);
     memcpy(hst, free_state, sizeof(double) * nf); memcpy(hst + nf, adam_m, sizeof(double) * nf); memcpy(hst + 2 * nf, adam_v, sizeof(double) * nf);
@@ -1457,35 +1505,56 @@ int dense_fit_steps(zigp_ctx* c, int32_t mode, bool legacy, const zigp_params* s
       ZIGP_HIP(c, hipMemcpyAsync(c->fitIdx.p, hi, sizeof(int64_t) * nidx, hipMemcpyHostToDevice, c->stream));
     }
   }
-  const dim3 ugrid(ceil_div(n_free, DFIT_THREADS));
-  const dim3 tgrid(ceil_div((int64_t)std::max(M[0], M[1]) * std::max(M[0], M[1]), DFIT_THREADS), 2);
   auto image = [&]() {     // free state -> parameter image, hyperparameter block and, for full factors, the two Lraw blocks
     hipLaunchKernelGGL(k_dense_fit_image, ugrid, dim3(DFIT_THREADS), 0, c->stream, d, fa.x, c->parm.p, H);
     if (tri) hipLaunchKernelGGL(k_dense_fit_image_tri, tgrid, dim3(DFIT_THREADS), 0, c->stream, d, fa.x, c->parm.p, c->lat[0].Lraw.p, c->lat[1].Lraw.p);
   };
   image();
   ZIGP_HIP(c, hipGetLastError());
+  if constexpr (TAP) ZIGP_TRY(ts.snap(c));
   for (int i = 0; i < n_steps; ++i) {
-    if (rows) {
-      hipLaunchKernelGGL(k_gather_rows, dim3(ceil_div(batch * (D + 1), 256)), dim3(256), 0, c->stream, c->fullX, c->fullY,
-                         reinterpret_cast<const int64_t*>(c->fitIdx.p) + (int64_t)i * batch, batch, D, c->fitX.p, c->fitY.p);
-      ZIGP_HIP(c, hipGetLastError());
+    if constexpr (TAP) {      // the caller's packed vector and status in place of the step
+      ZIGP_HIP(c, hipMemcpyAsync(k.d_info2, ts.info.p + i, sizeof(int) * 2, hipMemcpyDeviceToDevice, c->stream));
+      fa.packed = ts.packed.p + (size_t)i * ts.n_packed;
+    } else {
+      if (rows) {
+        hipLaunchKernelGGL(k_gather_rows, dim3(ceil_div(batch * (D + 1), 256)), dim3(256), 0, c->stream, c->fullX, c->fullY,
+                           reinterpret_cast<const int64_t*>(c->fitIdx.p) + (int64_t)i * batch, batch, D, c->fitX.p, c->fitY.p);
+        ZIGP_HIP(c, hipGetLastError());
+      }
+      ZIGP_TRY(dense_step(c, k));
+      DensePackArgs pa; size_t npk = 0;
+      ZIGP_TRY(dense_pack(c, k, pa, npk));
+      fa.packed = c->packed.p;
     }
-    ZIGP_TRY(dense_step(c, k));
-    DensePackArgs pa; size_t npk = 0;
-    ZIGP_TRY(dense_pack(c, k, pa, npk));
     // lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t), t counted from 1 (zigp/optim.py AdamGroups.step): the two t-dependent factors from the host
     const double t = (double)(t0 + i + 1);
-    fa.packed = c->packed.p; fa.step = i; fa.lr_sq = std::sqrt(1.0 - std::pow(d.beta2, t)); fa.lr_den = 1.0 - std::pow(d.beta1, t);
+    fa.step = i; fa.lr_sq = std::sqrt(1.0 - std::pow(d.beta2, t)); fa.lr_den = 1.0 - std::pow(d.beta1, t);
     hipLaunchKernelGGL(k_dense_fit_update, ugrid, dim3(DFIT_THREADS), 0, c->stream, fa);
     image();
     ZIGP_HIP(c, hipGetLastError());
+    if constexpr (TAP) ZIGP_TRY(ts.snap(c));
   }
   double* hst = nullptr;
   ZIGP_TRY(download(c, c->fit.p, n_down, &hst));
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));
   prof_collect(c);
   const int* hfail = reinterpret_cast<const int*>(hst + 3 * nf + n_hist);
+  if constexpr (TAP) {
+    if (tap->hist) memcpy(tap->hist, hst + 3 * nf, sizeof(double) * n_hist);
+    if (tap->fail) memcpy(tap->fail, hfail, sizeof(int) * 4);
+    std::vector<double> hs((size_t)ts.taken * ts.slot);
+    ZIGP_HIP(c, hipMemcpy(hs.data(), ts.snaps.p, sizeof(double) * hs.size(), hipMemcpyDeviceToHost));
+    double* const dst[7] = {tap->snap_x, tap->snap_m, tap->snap_v, tap->snap_img, tap->snap_H, tap->snap_Lraw[0], tap->snap_Lraw[1]};
+    const size_t n[7] = {nf, nf, nf, total, (size_t)DH_SIZE, ts.n[3], ts.n[4]};
+    for (int s = 0; s < ts.taken; ++s) {
+      const double* q = hs.data() + (size_t)s * ts.slot;
+      for (int j = 0; j < 7; ++j) {
+        if (dst[j] && n[j]) memcpy(dst[j] + (size_t)s * n[j], q, sizeof(double) * n[j]);
+        q += n[j];
+      }
+    }
+  }
   memcpy(free_state, hst, sizeof(double) * nf); memcpy(adam_m, hst + nf, sizeof(double) * nf); memcpy(adam_v, hst + 2 * nf, sizeof(double) * nf);
   const int done = hfail[0] ? hfail[0] - 1 : n_steps;       // steps whose update was applied
   c->dense_fit_steps_applied = done;
@@ -1507,16 +1576,27 @@ extern "C" {
 int zigp_fit_steps(zigp_ctx* c, const zigp_params* shape, const zigp_fit_opts* o, double* free_state, double* adam_m, double* adam_v, int64_t n_free,
                    int64_t t0, int32_t n_steps, const int64_t* rows, int64_t batch, double jitter, double scale, int32_t include_kl, double* elbo_data,
                    double* kl) {
-  return dense_fit_steps(c, ZIGP_FIT_DIAG, true, shape, o, free_state, adam_m, adam_v, n_free, t0, n_steps, rows, batch, jitter, scale, include_kl,
-                         elbo_data, kl);
+  return dense_fit_steps<false>(c, ZIGP_FIT_DIAG, true, shape, o, free_state, adam_m, adam_v, n_free, t0, n_steps, rows, batch, jitter, scale, include_kl,
+                                elbo_data, kl);
 }
 int zigp_fit_steps_mode(zigp_ctx* c, int32_t mode, const zigp_params* shape, const zigp_fit_opts* o, double* free_state, double* adam_m,
                         double* adam_v, int64_t n_free, int64_t t0, int32_t n_steps, const int64_t* rows, int64_t batch, double jitter,
                         double scale, int32_t include_kl, double* elbo_data, double* kl) {
-  return dense_fit_steps(c, mode, false, shape, o, free_state, adam_m, adam_v, n_free, t0, n_steps, rows, batch, jitter, scale, include_kl,
-                         elbo_data, kl);
+  return dense_fit_steps<false>(c, mode, false, shape, o, free_state, adam_m, adam_v, n_free, t0, n_steps, rows, batch, jitter, scale, include_kl,
+                                elbo_data, kl);
 }
 int64_t zigp_fit_steps_applied(zigp_ctx* c) { return c ? c->dense_fit_steps_applied : (int64_t)ZIGP_EARG; }
+
+// The image and update kernels of the dense fit loop through dense_fit_steps itself (include/zigp_diag.h): full-batch steps over the
+// active rows, none of which runs.
+int zigp_test_dense_fit_update(zigp_ctx* c, const zigp_stage_dense_fit_update* s) {
+  if (!c) return ZIGP_EARG;
+  if (!s || s->n_steps > 4096) return fail_arg(c, "zigp_test_dense_fit_update: bad arguments");
+  const int rc = dense_fit_steps<true>(c, s->mode, false, s->shape, s->opts, s->x, s->m, s->v, s->n_free, s->t0, s->n_steps, nullptr, 0, s->jitter, 1.0, 1,
+                                       s->elbo_data, s->kl, s);
+  if (s->steps_applied) *s->steps_applied = c->dense_fit_steps_applied;
+  return rc;
+}
 
 int zigp_predict(zigp_ctx* c, const zigp_params* p, const double* Xnew, int64_t N, double jitter, double g_offset, double* out9) {
   if (!c) return ZIGP_EARG;

@@ -1185,6 +1185,45 @@ int zigp_test_kron_fused_step(zigp_ctx* c, const zigp_stage_kron_fused* s) {
   return tap.flush(c);
 }
 
+// The update kernel of the Kronecker fit loops through kf_fit_run itself, each step replaced by the caller's result block (KfFitTap,
+// zigp_kronf.hip).  The checks are those of kron_fit_entry that do not concern rows or the data set.
+int zigp_test_kron_fit_update(zigp_ctx* c, const zigp_stage_kron_fit_update* s) {
+  const char* who = "zigp_test_kron_fit_update";
+  if (!c) return ZIGP_EARG;
+  c->fit_steps_applied = 0;
+  if (!s || !s->shape || !s->lr || !s->positive || !s->x || !s->m || !s->v) return kron_refuse(c, who, "NULL argument");
+  if (s->lik != ZIGP_LIK_ONOFF && s->lik != ZIGP_LIK_GAUSSIAN && s->lik != ZIGP_LIK_BERNOULLI) return kron_refuse(c, who, "unknown likelihood");
+  const bool head = s->lik != ZIGP_LIK_ONOFF;
+  const zigp_kron_params* p = s->shape;
+  if (p->M0f <= 0 || p->M1f <= 0 || (!head && (p->M0g <= 0 || p->M1g <= 0))) return fail_arg(c, "inducing counts must be positive");
+  if (p->D0 <= 0 || p->D1 <= 0 || p->D0 > MAXD || p->D1 > MAXD) return fail_arg(c, "factor dimensions must be in [1, 8]");
+  if (s->n_steps <= 0 || s->n_steps > 4096 || s->t0 < 0) return kron_refuse(c, who, "need 0 < n_steps <= 4096, t0 >= 0");
+  if (!(s->beta1 >= 0 && s->beta1 < 1 && s->beta2 >= 0 && s->beta2 < 1 && s->eps > 0)) return kron_refuse(c, who, "bad Adam constants");
+  if (c->kron_panels || !kf_eligible(p, head ? 1 : 2))
+    return kron_refuse(c, who, "this inducing grid is beyond the fused Kronecker kernels (<= 32 x <= 32 or <= 16 x <= 112 points, factor dimensions <= 7)");
+  if (head && s->n_free != (int64_t)p->M0f * p->D0 + (int64_t)p->M1f * p->D1 + 2 * (int64_t)p->M0f * p->M1f + p->D0 + p->D1 + 4)
+    return kron_refuse(c, who, "n_free does not match the model sizes");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  const std::vector<int64_t> rows((size_t)s->n_steps, 0);      // no step runs: nothing reads a row
+  KfFitCall fit = {};
+  fit.name = who; fit.head = head;
+  fit.lr = s->lr; fit.positive = s->positive; fit.trainable = head ? s->trainable : nullptr;
+  fit.beta1 = s->beta1; fit.beta2 = s->beta2; fit.eps = s->eps;
+  fit.x = s->x; fit.m = s->m; fit.v = s->v; fit.n_free = s->n_free; fit.t0 = s->t0; fit.n_steps = s->n_steps; fit.row_begin = rows.data();
+  fit.batch = 1; fit.hist_data = s->elbo_data; fit.hist_kl = s->kl;
+  KronCall k = {};
+  k.p = p; k.lik = s->lik; k.X = k.Y = kron_no_rows; k.N = 1; k.dev_xy = true; k.scale = 1.0; k.include_kl = 1;
+  kron_call_derive(k);
+  kron_set_kinds(c, k.hl, k.nlat);
+  k.need_grad = true;
+  KfFitTap tap;
+  tap.s = s; tap.nf = tap.n_img = 0; tap.taken = 0;
+  memset(tap.facts, 0, sizeof(tap.facts));
+  const int rc = kronf_run(c, k, &fit, nullptr, &tap);
+  if (s->steps_applied) *s->steps_applied = c->fit_steps_applied;
+  return rc;
+}
+
 int zigp_test_kron_kbuild(zigp_ctx* c, int64_t N, int64_t Nc, int32_t ldx, int32_t col0, int32_t M, int32_t D, const double* X, const double* Z,
                           const double* ell, double var, double* K) {
   if (!c) return ZIGP_EARG;

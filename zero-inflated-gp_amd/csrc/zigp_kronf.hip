@@ -2513,7 +2513,36 @@ static int kf_fit_describe(const KfRun& s, KfFitDesc& d) {
   return 0;
 }
 
-static int kf_fit_run(KfRun& s) {
+// Test hook of the loop (zigp_test_kron_fit_update, include/zigp_diag.h): step i's result block comes from the caller, and the state and the
+// parameter image are snapshot -- device-to-device, on the loop's stream -- behind the initial image launch and behind every update launch.
+struct KfFitTap {
+  const zigp_stage_kron_fit_update* s;
+  DevBuf res, snaps;          // the caller's result blocks [n_steps][n_res]; snapshots [1 + n_steps][3 n_free + n_img]
+  size_t nf, n_img;
+  int taken;
+  int64_t facts[ZIGP_KFU_COUNT];
+  int snap(zigp_ctx* c, const double* state, const double* img) {
+    double* q = snaps.p + (size_t)taken++ * (3 * nf + n_img);
+    ZIGP_HIP(c, hipMemcpyAsync(q, state, sizeof(double) * 3 * nf, hipMemcpyDeviceToDevice, c->stream));
+    ZIGP_HIP(c, hipMemcpyAsync(q + 3 * nf, img, sizeof(double) * n_img, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+  }
+  int flush(zigp_ctx* c) {      // the stream is idle
+    std::vector<double> h((size_t)taken * (3 * nf + n_img));
+    if (!h.empty()) ZIGP_HIP(c, hipMemcpy(h.data(), snaps.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+    double* const dst[3] = {s->snap_x, s->snap_m, s->snap_v};
+    for (int k = 0; k < taken; ++k) {
+      const double* q = h.data() + (size_t)k * (3 * nf + n_img);
+      for (int j = 0; j < 3; ++j)
+        if (dst[j]) memcpy(dst[j] + (size_t)k * nf, q + (size_t)j * nf, sizeof(double) * nf);
+      if (s->snap_img) memcpy(s->snap_img + (size_t)k * n_img, q + 3 * nf, sizeof(double) * n_img);
+    }
+    return 0;
+  }
+};
+
+template <bool TAP>
+static int kf_fit_run(KfRun& s, KfFitTap* tap) {
   zigp_ctx* c = s.c;
   KfState& ks = *s.ks;
   const KfFitCall* fit = s.fit;
@@ -2525,6 +2554,30 @@ static int kf_fit_run(KfRun& s) {
   const KfFitDesc& d = fa.d;
   const size_t nf = (size_t)fit->n_free, n_hist = (size_t)2 * fit->n_steps;
   const size_t n_state = 3 * nf + n_hist + 8;
+  if constexpr (TAP) {
+    const zigp_stage_kron_fit_update* ts = tap->s;
+    int64_t* f = tap->facts;
+    const int64_t res[9] = {(int64_t)s.RES_KLV, (int64_t)s.RES_KROW0, (int64_t)s.RES_KROW1, (int64_t)s.RES_GU, (int64_t)s.RES_GS, (int64_t)s.RES_SIZE,
+                            (int64_t)s.RES_PWS, (int64_t)s.RES_INFO, (int64_t)s.n_res};
+    memcpy(f + ZIGP_KFU_RES_KLV, res, sizeof(res));
+    f[ZIGP_KFU_GRID] = (d.big_off[8] + KFIT_THREADS - 1) / KFIT_THREADS + 1;
+    for (int k = 0; k < 9; ++k) f[ZIGP_KFU_BIG_OFF + k] = d.big_off[k];
+    for (int k = 0; k < 10; ++k) f[ZIGP_KFU_HYP_OFF + k] = d.hyp_off[k];
+    f[ZIGP_KFU_N_IMG] = (int64_t)(s.off_hyp2 + KH_SIZE); f[ZIGP_KFU_OFF_HYP] = (int64_t)s.off_hyp; f[ZIGP_KFU_OFF_HYP2] = (int64_t)s.off_hyp2;
+    for (int h = 0; h < 2; ++h) {
+      for (int q = 0; q < 2; ++q) f[ZIGP_KFU_OFF_Z + 2 * h + q] = h < s.nlat ? (int64_t)s.off_z[h][q] : -1;
+      f[ZIGP_KFU_OFF_U + h] = h < s.nlat ? (int64_t)s.off_u[h] : -1; f[ZIGP_KFU_OFF_S + h] = h < s.nlat ? (int64_t)s.off_s[h] : -1;
+    }
+    const int64_t kh[8] = {KH_SIZE, KH_FAC, KH_INV, KH_ZC, KH_ELL, KH_VAR, KH_NOISE, KH_FMU};
+    memcpy(f + ZIGP_KFU_KH_SIZE, kh, sizeof(kh));
+    if (ts->facts) memcpy(ts->facts, f, sizeof(tap->facts));
+    if (!ts->res) return 0;       // the layout query
+    if (ts->n_res != (int64_t)s.n_res || ts->n_img != f[ZIGP_KFU_N_IMG]) { c->err = "zigp_test_kron_fit_update: n_res / n_img differ from the facts"; return ZIGP_EARG; }
+    tap->nf = nf; tap->n_img = (size_t)ts->n_img; tap->taken = 0;
+    ZIGP_ENSURE(c, tap->res, (size_t)fit->n_steps * s.n_res);
+    ZIGP_ENSURE(c, tap->snaps, (size_t)(1 + fit->n_steps) * (3 * nf + tap->n_img));
+    ZIGP_HIP(c, hipMemcpyAsync(tap->res.p, ts->res, sizeof(double) * fit->n_steps * s.n_res, hipMemcpyHostToDevice, c->stream));
+  }
   ZIGP_ENSURE(c, ks.fit, n_state);
   fa.x = ks.fit.p; fa.m = fa.x + nf; fa.v = fa.m + nf; fa.hist = fa.v + nf; fa.fail = reinterpret_cast<int*>(fa.hist + n_hist);
   fa.img = ks.in.p; fa.res = ks.res.p;
@@ -2550,6 +2603,7 @@ static int kf_fit_run(KfRun& s) {
   };
   update();       // free state -> parameter image (hyper block 0)
   ZIGP_HIP(c, hipGetLastError());
+  if constexpr (TAP) ZIGP_TRY(tap->snap(c, ks.fit.p, ks.in.p));
   fa.update = 1;
   const double *X = s.k->X, *Y = s.k->Y;      // the resident data set
   for (int i = 0; i < fit->n_steps; ++i) {
@@ -2557,17 +2611,26 @@ static int kf_fit_run(KfRun& s) {
     const double* Xd = rb >= 0 ? X + rb * ldx : s.d_wrap + (size_t)(-rb - 1) * N * ldx;
     const double* Yd = rb >= 0 ? Y + rb : s.d_wrap + s.n_wrap * (size_t)N * ldx + (size_t)(-rb - 1) * N;
     s.d_hyp = ks.in.p + ((i & 1) ? s.off_hyp2 : s.off_hyp);       // written by the previous step's update (step 0: by the launch above)
-    ZIGP_TRY(kf_step<false>(s, nullptr, Xd, Yd));
+    if constexpr (TAP)      // the caller's result block in place of the step
+      ZIGP_HIP(c, hipMemcpyAsync(ks.res.p, tap->res.p + (size_t)i * s.n_res, sizeof(double) * s.n_res, hipMemcpyDeviceToDevice, c->stream));
+    else
+      ZIGP_TRY(kf_step<false>(s, nullptr, Xd, Yd));
     // lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t), t counted from 1 (zigp/optim.py AdamGroups.step): the two t-dependent factors from the host
     const double t = (double)(fit->t0 + i + 1);
     fa.step = i; fa.lr_sq = std::sqrt(1.0 - std::pow(d.beta2, t)); fa.lr_den = 1.0 - std::pow(d.beta1, t);
     update();
     ZIGP_HIP(c, hipGetLastError());
+    if constexpr (TAP) ZIGP_TRY(tap->snap(c, ks.fit.p, ks.in.p));
   }
   double* hst = nullptr;
   ZIGP_TRY(download(c, ks.fit.p, n_state, &hst));
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));
   const int* hfail = reinterpret_cast<const int*>(hst + 3 * nf + n_hist);
+  if constexpr (TAP) {
+    if (tap->s->hist) memcpy(tap->s->hist, hst + 3 * nf, sizeof(double) * n_hist);
+    if (tap->s->fail) memcpy(tap->s->fail, hfail, sizeof(int) * 4);
+    ZIGP_TRY(tap->flush(c));
+  }
   memcpy(fit->x, hst, sizeof(double) * nf); memcpy(fit->m, hst + nf, sizeof(double) * nf); memcpy(fit->v, hst + 2 * nf, sizeof(double) * nf);
   const int done = hfail[0] ? hfail[0] - 1 : fit->n_steps;       // steps whose update was applied
   c->fit_steps_applied = done;                                   // (zigp_kron_fit_steps_applied: the caller's iteration count advances by this)
@@ -2609,14 +2672,14 @@ static int kf_gather(KfRun& s) {
 
 // One ELBO step (or prediction) of the fused Kronecker path.  fit != nullptr: n_steps gradient steps with the Adam update on the device
 // (k.p then carries the sizes only; k.X / k.Y are the resident data set).  tap != nullptr: the step of the stage tests
-// (zigp_test_kron_fused_step).
-static int kronf_run(zigp_ctx* c, const KronCall& k, const KfFitCall* fit = nullptr, KfTap* tap = nullptr) {
+// (zigp_test_kron_fused_step).  fit_tap != nullptr: the fit loop of zigp_test_kron_fit_update.
+static int kronf_run(zigp_ctx* c, const KronCall& k, const KfFitCall* fit = nullptr, KfTap* tap = nullptr, KfFitTap* fit_tap = nullptr) {
   KfRun s;
   ZIGP_TRY(kf_prepare(c, k, fit, s));
   if (!fit) ZIGP_TRY(kf_stage_inputs(s));
   if (k.predict) ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
   ZIGP_TRY(kf_set_attributes(c));
-  if (fit) return kf_fit_run(s);
+  if (fit) return fit_tap ? kf_fit_run<true>(s, fit_tap) : kf_fit_run<false>(s, nullptr);
   const double* Xd = k.dev_xy ? k.X : s.ks->in.p + s.off_x;
   const double* Yd = k.Y ? (k.dev_xy ? k.Y : s.ks->in.p + s.off_y) : nullptr;
   if (tap) {

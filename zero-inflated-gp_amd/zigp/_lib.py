@@ -184,7 +184,44 @@ class zigp_stage_kron_fused(C.Structure):   # include/zigp_diag.h
                 ('grads', C.POINTER(zigp_kron_grads)), ('d_f_mu', dp)]
 
 
-KPW_THREADS, KPW_ACC = 256, 5   # csrc/zigp_kron.hip: points per block and accumulators per block of the Kronecker point-wise kernels
+KFU_FACTS = (('RES_KLV', 1), ('RES_KROW0', 1), ('RES_KROW1', 1), ('RES_GU', 1), ('RES_GS', 1), ('RES_SIZE', 1), ('RES_PWS', 1), ('RES_INFO', 1),
+             ('n_res', 1), ('grid', 1), ('big_off', 9), ('hyp_off', 10), ('n_img', 1), ('off_hyp', 1), ('off_hyp2', 1), ('off_z', 4), ('off_u', 2),
+             ('off_s', 2), ('KH_SIZE', 1), ('KH_FAC', 1), ('KH_INV', 1), ('KH_ZC', 1), ('KH_ELL', 1), ('KH_VAR', 1), ('KH_NOISE', 1),
+             ('KH_FMU', 1))   # include/zigp_diag.h ZIGP_KFU_*: (name, entries)
+KFU_COUNT = sum(n for _, n in KFU_FACTS)
+
+
+class zigp_stage_kron_fit_update(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('lik', C.c_int32), ('n_steps', C.c_int32), ('shape', C.POINTER(zigp_kron_params)), ('lr', dp), ('positive', dp), ('trainable', dp),
+                ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double), ('t0', C.c_int64), ('n_free', C.c_int64),
+                ('x', dp), ('m', dp), ('v', dp), ('res', dp), ('n_res', C.c_int64), ('n_img', C.c_int64),
+                ('snap_x', dp), ('snap_m', dp), ('snap_v', dp), ('snap_img', dp), ('hist', dp), ('fail', dp), ('elbo_data', dp), ('kl', dp),
+                ('steps_applied', dp), ('facts', dp)]
+
+
+DFU_FACTS = (('img_Z', 2), ('img_ell', 2), ('img_u', 2), ('img_s', 2), ('img_Zs', 2), ('Mp', 2), ('n_img', 1), ('n_packed', 1), ('grid', 1),
+             ('tgrid', 1), ('DH_SIZE', 1), ('DH_LAT', 1), ('DH_INV', 1), ('DH_ELL', 1), ('DH_SCALE', 1), ('DH_VAR', 1), ('DH_PIVTOL', 1),
+             ('DH_NOISE', 1))   # include/zigp_diag.h ZIGP_DFU_*
+DFU_COUNT = sum(n for _, n in DFU_FACTS)
+
+
+class zigp_stage_dense_fit_update(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('mode', C.c_int32), ('n_steps', C.c_int32), ('shape', C.POINTER(zigp_params)), ('opts', C.POINTER(zigp_fit_opts)),
+                ('t0', C.c_int64), ('n_free', C.c_int64), ('jitter', C.c_double), ('x', dp), ('m', dp), ('v', dp), ('packed', dp), ('info', dp),
+                ('n_packed', C.c_int64), ('n_img', C.c_int64), ('snap_x', dp), ('snap_m', dp), ('snap_v', dp), ('snap_img', dp), ('snap_H', dp),
+                ('snap_Lraw', dp * 2), ('hist', dp), ('fail', dp), ('elbo_data', dp), ('kl', dp), ('steps_applied', dp), ('facts', dp)]
+
+
+def unpack_facts(layout, arr):
+    """facts array -> dict (an entry with more than one value: a list)"""
+    out, o = {}, 0
+    for name, n in layout:
+        out[name] = int(arr[o]) if n == 1 else [int(a) for a in arr[o:o + n]]
+        o += n
+    return out
+
+
+KPW_THREADS, KPW_ACC = 256, 5  # csrc/zigp_kron.hip: points per block and accumulators per block of the Kronecker point-wise kernels
 STAGE_SENTINEL = float(np.frombuffer(bytes([0x7f]) * 8, dtype=np.float64)[0])   # ZIGP_STAGE_SENTINEL_BYTE in every byte: 1.38e306
 KG_SPLIT, PW_PTS, PW_ACC = 4, 64, 13   # csrc/zigp_kernels.h
 
@@ -301,6 +338,8 @@ SIGNATURES = {
     'zigp_test_dense_pack': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_pack)]),
     'zigp_test_kron_pointwise': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_kron_pointwise)]),
     'zigp_test_kron_fused_step': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_kron_fused)]),
+    'zigp_test_kron_fit_update': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_kron_fit_update)]),
+    'zigp_test_dense_fit_update': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_dense_fit_update)]),
     'zigp_test_kron_kbuild': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, C.c_double, dp]),
     'zigp_test_kron_colsum': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, dp, dp, dp, dp, dp, dp, dp, dp]),
     'zigp_test_kron_da': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, dp, dp, dp, dp, dp, dp, dp]),

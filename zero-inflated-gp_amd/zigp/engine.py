@@ -1951,6 +1951,163 @@ class DenseEngine:
             out['u_%ss_sqrt' % tag] = a['us']
         return dict(elbo_data=float(sc[0]), kl=float(sc[1]), grads=out, facts={k: int(facts[i]) for i, k in enumerate(_lib.KFF_FACTS)}, lat=lat)
 
+    @staticmethod
+    def kron_fit_sizes(shape, lik='onoff'):
+        """block sizes of the free vector of kron_fit_steps (lik 'onoff': 17 blocks) or kron_head_fit_steps (10 blocks)"""
+        D0, D1 = int(shape['D0']), int(shape['D1'])
+        out = []
+        for t in (('f', 'g') if lik == 'onoff' else ('f',)):
+            M0, M1 = int(shape['M0' + t]), int(shape['M1' + t])
+            out += [M0 * D0, M1 * D1, M0 * M1, M0 * M1, D0, D1, 1, 1]
+        return out + ([1] if lik == 'onoff' else [1, 1])
+
+    def _kron_fit_update_struct(self, shape, lik):
+        two = lik == 'onoff'
+        if not two and lik not in self.LIK:
+            raise ValueError("lik must be 'onoff', 'gaussian' or 'bernoulli'")
+        sp = _lib.zigp_kron_params()
+        for k in (('M0f', 'M1f', 'M0g', 'M1g', 'D0', 'D1') if two else ('M0f', 'M1f', 'D0', 'D1')):
+            setattr(sp, k, int(shape[k]))
+        s = _lib.zigp_stage_kron_fit_update()
+        s.lik = _lib.LIK_ONOFF if two else self.LIK[lik]
+        s.shape = C.pointer(sp)
+        facts = np.zeros(_lib.KFU_COUNT, dtype=np.int64)
+        s.facts = facts.ctypes.data
+        return s, sp, facts
+
+    def test_kron_fit_update_facts(self, shape, lik='onoff'):
+        """The layout a fit call of this shape uses (zigp_test_kron_fit_update with res = NULL): offsets of the result block, the grid and the
+        element map of the update launches, the parameter image (_lib.KFU_FACTS)."""
+        s, sp, facts = self._kron_fit_update_struct(shape, lik)
+        nb = _lib.FIT_BLOCKS if lik == 'onoff' else _lib.HEAD_FIT_BLOCKS
+        nf = sum(self.kron_fit_sizes(shape, lik))
+        z, lr, pos = np.zeros(nf), np.ones(nb), np.zeros(nb, dtype=np.int32)
+        s.n_steps, s.lr, s.positive, s.beta1, s.beta2, s.eps, s.n_free = 1, ptr(lr), pos.ctypes.data, 0.9, 0.999, 1e-8, nf
+        s.x, s.m, s.v = ptr(z), ptr(z), ptr(z)
+        _check(self.lib, self.ctx, self.lib.zigp_test_kron_fit_update(self.ctx, C.byref(s)))
+        return _lib.unpack_facts(_lib.KFU_FACTS, facts)
+
+    @staticmethod
+    def kron_result_block(facts, shape, lik, lats, pws, info=()):
+        """One raw result block [n_res] from compact arrays: lats = per latent dict(klv (5), krow [2] (M_q, 2 + 2 D_q), gu, gs (M0 M1)), pws (8),
+        info = the Cholesky status of factor job j (missing: 0).  Every other double -- and the second int of every status slot, and the slots
+        of jobs the model does not have -- holds _lib.STAGE_SENTINEL's bytes."""
+        blk = np.full(facts['n_res'], _lib.STAGE_SENTINEL)
+        for h, L in enumerate(lats):
+            o = h * facts['RES_SIZE']
+            blk[o + facts['RES_KLV']:o + facts['RES_KLV'] + 5] = as_f64(L['klv']).reshape(5)
+            for q, key in enumerate(('RES_KROW0', 'RES_KROW1')):
+                kr = as_f64(L['krow'][q]).reshape(-1)
+                blk[o + facts[key]:o + facts[key] + kr.size] = kr
+            for key, a in (('RES_GU', L['gu']), ('RES_GS', L['gs'])):
+                a = as_f64(a).reshape(-1)
+                blk[o + facts[key]:o + facts[key] + a.size] = a
+        blk[facts['RES_PWS']:facts['RES_PWS'] + 8] = as_f64(pws).reshape(8)
+        ints = blk[facts['RES_INFO']:facts['RES_INFO'] + 8].view(np.int32)
+        for j in range(2 * len(lats)):
+            ints[2 * j] = int(info[j]) if j < len(info) else 0
+        return blk
+
+    def test_kron_fit_update(self, shape, lik, x, m, v, lr, positive, trainable, t0, res, beta1=0.9, beta2=0.999, eps=1e-8):
+        """The update kernel of kron_fit_steps (lik 'onoff') / kron_head_fit_steps through the host loop itself, step i replaced by the raw
+        result block res[i] (zigp_test_kron_fit_update, include/zigp_diag.h; kron_result_block builds one).  x, m, v are updated in place as by
+        the fit calls.  An injected Cholesky failure does NOT raise: returns dict(rc, error, steps_applied, snap_x, snap_m, snap_v
+        [1 + n][n_free], snap_img [1 + n][n_img], hist [n][2], fail [4], elbo_data [n], kl [n], facts)."""
+        s, sp, facts = self._kron_fit_update_struct(shape, lik)
+        nb = _lib.FIT_BLOCKS if lik == 'onoff' else _lib.HEAD_FIT_BLOCKS
+        for a in (x, m, v):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.ndim == 1 and a.size == x.size):
+                raise ValueError('x, m, v must be contiguous float64 vectors of one length')
+        f0 = self.test_kron_fit_update_facts(shape, lik)
+        res = as_f64(res)
+        if res.ndim != 2 or res.shape[1] != f0['n_res']:
+            raise ValueError('res must be [n_steps][n_res = %d]' % f0['n_res'])
+        n, nf, n_img = res.shape[0], x.size, f0['n_img']
+        lr_a = as_f64(lr).reshape(nb)
+        pos = np.ascontiguousarray(np.asarray(positive, dtype=bool).reshape(nb), dtype=np.int32)
+        tr = None if trainable is None else np.ascontiguousarray(np.asarray(trainable, dtype=bool).reshape(nb), dtype=np.int32)
+        out = dict(snap_x=np.zeros((1 + n, nf)), snap_m=np.zeros((1 + n, nf)), snap_v=np.zeros((1 + n, nf)), snap_img=np.zeros((1 + n, n_img)),
+                   hist=np.zeros((n, 2)), fail=np.zeros(4, dtype=np.int32), elbo_data=np.zeros(n), kl=np.zeros(n))
+        applied = np.zeros(1, dtype=np.int64)
+        s.n_steps, s.lr, s.positive, s.trainable = n, ptr(lr_a), pos.ctypes.data, None if tr is None else tr.ctypes.data
+        s.beta1, s.beta2, s.eps, s.t0, s.n_free = float(beta1), float(beta2), float(eps), int(t0), nf
+        s.x, s.m, s.v, s.res, s.n_res, s.n_img = ptr(x), ptr(m), ptr(v), ptr(res), f0['n_res'], n_img
+        for k, a in out.items():
+            setattr(s, k, a.ctypes.data)
+        s.steps_applied = applied.ctypes.data
+        rc = self.lib.zigp_test_kron_fit_update(self.ctx, C.byref(s))
+        msg = ''
+        if rc != 0:
+            e = self.lib.zigp_last_error(self.ctx)
+            msg = e.decode() if e else ''
+            if rc != _lib.ZIGP_ENOTPD:
+                _check(self.lib, self.ctx, rc)
+        out.update(rc=rc, error=msg, steps_applied=int(applied[0]), facts=_lib.unpack_facts(_lib.KFU_FACTS, facts))
+        return out
+
+    @staticmethod
+    def dense_fit_sizes(mode, shape, ell_size):
+        """block sizes of the free vector of fit_steps / fit_steps_mode"""
+        Mf, Mg, D = int(shape['Mf']), int(shape['Mg']), int(shape['D'])
+        ns = [M * (M + 1) // 2 if mode == _lib.FIT_WHITE_FULL else M for M in (Mf, Mg)]
+        return [Mf * D, Mg * D, Mf, Mg, ns[0], ns[1], int(ell_size[0]), int(ell_size[1]), 1, 1, 1]
+
+    def test_dense_fit_update(self, mode, shape, x, m, v, lr, positive, trainable, ell_size, t0, packed, info=None, jitter=1e-6,
+                              beta1=0.9, beta2=0.999, eps=1e-8):
+        """The image and update kernels of fit_steps / fit_steps_mode through the host loop itself, step i's gradient step replaced by the
+        packed vector packed[i] (layout of test_dense_pack's output) and the Cholesky status info[i] = (f, g) (zigp_test_dense_fit_update,
+        include/zigp_diag.h).  A data set must be resident (set_data).  packed=None: the layout query, returns the facts dict
+        (_lib.DFU_FACTS).  Otherwise x, m, v are updated in place and an injected failure does NOT raise: returns dict(rc, error,
+        steps_applied, snap_x, snap_m, snap_v [1 + n][n_free], snap_img [1 + n][n_img], snap_H [1 + n][DH_SIZE], snap_Lraw [2] ([1 + n][M, M],
+        full mode), hist, fail, elbo_data, kl, facts)."""
+        mode = int(mode)
+        s = _lib.zigp_stage_dense_fit_update()
+        sp = _lib.zigp_params()
+        sp.Mf, sp.Mg, sp.D = int(shape['Mf']), int(shape['Mg']), int(shape['D'])
+        o = _lib.zigp_fit_opts()
+        for b in range(_lib.DENSE_FIT_BLOCKS):
+            o.lr[b] = float(lr[b]); o.positive[b] = int(bool(positive[b])); o.trainable[b] = int(bool(trainable[b]))
+        o.ell_size_f, o.ell_size_g = int(ell_size[0]), int(ell_size[1])
+        o.beta1, o.beta2, o.eps = float(beta1), float(beta2), float(eps)
+        for a in (x, m, v):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.ndim == 1 and a.size == x.size):
+                raise ValueError('x, m, v must be contiguous float64 vectors of one length')
+        facts = np.zeros(_lib.DFU_COUNT, dtype=np.int64)
+        s.mode, s.shape, s.opts, s.t0, s.n_free, s.jitter = mode, C.pointer(sp), C.pointer(o), int(t0), x.size, float(jitter)
+        s.x, s.m, s.v, s.facts = ptr(x), ptr(m), ptr(v), facts.ctypes.data
+        if packed is None:
+            s.n_steps = 1
+            _check(self.lib, self.ctx, self.lib.zigp_test_dense_fit_update(self.ctx, C.byref(s)))
+            return _lib.unpack_facts(_lib.DFU_FACTS, facts)
+        f0 = self.test_dense_fit_update(mode, shape, x, m, v, lr, positive, trainable, ell_size, t0, None, jitter=jitter, beta1=beta1, beta2=beta2,
+                                        eps=eps)
+        packed = as_f64(packed)
+        if packed.ndim != 2 or packed.shape[1] != f0['n_packed']:
+            raise ValueError('packed must be [n_steps][n_packed = %d]' % f0['n_packed'])
+        n, nf = packed.shape[0], x.size
+        info_a = np.zeros((n, 2), dtype=np.int32) if info is None else np.ascontiguousarray(np.asarray(info, dtype=np.int32).reshape(n, 2))
+        Ms = (sp.Mf, sp.Mg)
+        full = mode == _lib.FIT_WHITE_FULL
+        out = dict(snap_x=np.zeros((1 + n, nf)), snap_m=np.zeros((1 + n, nf)), snap_v=np.zeros((1 + n, nf)), snap_img=np.zeros((1 + n, f0['n_img'])),
+                   snap_H=np.zeros((1 + n, f0['DH_SIZE'])), hist=np.zeros((n, 2)), fail=np.zeros(4, dtype=np.int32), elbo_data=np.zeros(n), kl=np.zeros(n))
+        lraw = [np.zeros((1 + n, M, M)) for M in Ms] if full else None
+        applied = np.zeros(1, dtype=np.int64)
+        s.n_steps, s.packed, s.info, s.n_packed, s.n_img = n, ptr(packed), info_a.ctypes.data, f0['n_packed'], f0['n_img']
+        for k, a in out.items():
+            setattr(s, k, a.ctypes.data)
+        if full:
+            s.snap_Lraw = (_lib.dp * 2)(ptr(lraw[0]), ptr(lraw[1]))
+        s.steps_applied = applied.ctypes.data
+        rc = self.lib.zigp_test_dense_fit_update(self.ctx, C.byref(s))
+        msg = ''
+        if rc != 0:
+            e = self.lib.zigp_last_error(self.ctx)
+            msg = e.decode() if e else ''
+            if rc != _lib.ZIGP_ENOTPD:
+                _check(self.lib, self.ctx, rc)
+        out.update(rc=rc, error=msg, steps_applied=int(applied[0]), facts=_lib.unpack_facts(_lib.DFU_FACTS, facts), snap_Lraw=lraw)
+        return out
+
     def test_kron_panel_kbuild(self, X, col0, Z, ell, var, Nc):
         """k_kron_kbuild (zigp_test_kron_kbuild): the WHOLE padded factor panel (Mq, Nc), Mq = M rounded up to 128, from the columns
         col0 : col0 + D of X (N, ldx) and Z (M, D)."""
