@@ -400,6 +400,63 @@ typedef struct zigp_stage_kron_fused {
 } zigp_stage_kron_fused;
 int zigp_test_kron_fused_step(zigp_ctx* ctx, const zigp_stage_kron_fused* a);
 
+/* ---- One ordinary value-and-gradient step of the GEMM-PANEL path (kron_run_panels, csrc/zigp_kron.hip: grids beyond the fused kernels, D = 8,
+ * Matern factors without the opt-in, or zigp_set_kron_panels) through the production host code itself: the same launches, streams and
+ * buffers.  A tap is a stream-ordered device-to-device copy enqueued right behind the producing launch, on that latent's stream, into a
+ * buffer of its own, and downloaded after the step; a NULL tap is not taken.  The step returns the bits of an ordinary call (of the
+ * injected cotangents, when there are any).  Sizes: Mq_p = M_p rounded up to 128, Nc = max(1024, N rounded up to 1024); M x M taps are the
+ * whole padded [Mq][Mq] image (row stride Mq), grid taps [Mq0][Mq1] (row stride Mq1). ---- */
+typedef struct zigp_kronp_tap_factor {
+  double *K;        /* after the K_p launch: K_p + jitter I on [M][M], identity in the padding */
+  double *L, *W;    /* after potrf_trtri: the Cholesky factor (lower triangle; taken before the backward pass reuses the buffer) and its inverse */
+  double *P;        /* after P = W^T W: K_p^-1, identity in the padding */
+  double *krow_n;   /* [Mq][2 + 2 D] after k_kron_kgrad (the sums over points), before the Kuu-gradient kernel adds to it */
+  double *dP_red;   /* after the split-K reduction dP_p = sum_n E_p K_p^T */
+  double *dP_acc;   /* after the EpiAccum product: + dAl T0^T (p = 0), + (P0 U)^T dAl (p = 1) */
+  double *Q;        /* include_kl: the factor's G buffer after the KL product, Q0 = T0 U^T or Q1 = U^T (P0 U) */
+  double *dP_comb;  /* after k_kron_dp_combine */
+  double *T;        /* T = dP P */
+  double *PdPP;     /* P T, in the buffer L held */
+  double *G;        /* after k_kron_dk */
+  double *krow;     /* [Mq][2 + 2 D] after the Kuu-gradient kernel */
+} zigp_kronp_tap_factor;
+typedef struct zigp_kronp_tap_latent {
+  zigp_kronp_tap_factor f[2];
+  double *U, *S2, *T0, *Al;   /* after latent_setup's uploads and products: T0 = U P1, Al = P0 T0; zeros in the padding */
+  double *vec;                /* [Mq0 + Mq1]: diag(P0), diag(P1) */
+  double *klv;                /* include_kl: [5] = sum U.Alpha, sum log s^2, sum d0 d1 s^2, logdet K0, logdet K1 */
+  double *part;               /* [4][Nc] column sums after the forward panels */
+  const double* inject;       /* in, optional: [4][N] copied over gm, gv, dq0, dq1 behind the point-wise launch; columns >= N keep what it wrote */
+  double *cot;                /* [4][Nc]: gm, gv, dq0, dq1 as the backward pass reads them */
+  int32_t planes_of;          /* which split-K reduction `planes` is taken from: 0 dP0, 1 dP1, 2 dAl, 3 dS2 */
+  double *planes;             /* [S][nba 128][nbb 128] raw planes of that reduction, before k_sum_planes (S: facts) */
+  double *dAl, *dS2;          /* after their reductions */
+  double *T1_a, *dU;          /* T1 = dAl P1 ; dU = P0 T1 */
+  double *T1_b;               /* T1 = P0 U (its second use) */
+  double *gu, *gs;            /* [M0 M1], compact, after k_kron_us */
+} zigp_kronp_tap_latent;
+/* facts[] of zigp_test_kron_panel_step: ZIGP_KPF_NC, then per latent h at ZIGP_KPF_LAT + h * ZIGP_KPF_PER_LAT + ... */
+enum { ZIGP_KPF_NC = 0, ZIGP_KPF_NK, ZIGP_KPF_LAT,
+       ZIGP_KPF_MQ0 = 0, ZIGP_KPF_MQ1, ZIGP_KPF_NB0, ZIGP_KPF_NB1,
+       ZIGP_KPF_S_DP0, ZIGP_KPF_S_DP1, ZIGP_KPF_S_DAL, ZIGP_KPF_S_DS2,      /* split-K slices of each reduction, in planes_of order */
+       ZIGP_KPF_PER_LAT,
+       ZIGP_KPF_COUNT = ZIGP_KPF_LAT + 2 * ZIGP_KPF_PER_LAT };
+typedef struct zigp_stage_kron_panels {
+  int32_t lik;                  /* ZIGP_LIK_ONOFF (two latents) or a head (the f fields of everything) */
+  int32_t include_kl;
+  const zigp_kron_params* p;
+  const double *X, *Y;          /* host [N][D0 + D1], [N] */
+  int64_t N;                    /* >= 1 */
+  double jitter, scale, g_offset, f_mu;
+  zigp_kronp_tap_latent lat[2];
+  int64_t* facts;               /* out [ZIGP_KPF_COUNT], may be NULL */
+  double *elbo_data, *kl;       /* the step's ordinary outputs */
+  zigp_kron_grads* grads;       /* required: the hook runs the gradient step */
+  double* d_f_mu;
+} zigp_stage_kron_panels;
+/* Refuses (ZIGP_EARG) a step that an ordinary call would run on the fused kernels, unless zigp_set_kron_panels is on. */
+int zigp_test_kron_panel_step(zigp_ctx* ctx, const zigp_stage_kron_panels* a);
+
 /* ---- The update kernels of the device fit loops, through the host loops themselves with the gradient step replaced by caller-supplied
  * results.  Nothing but the update / image kernels is launched; no rows and (Kronecker) no resident data set are needed.  Snapshots are
  * stream-ordered device-to-device copies behind the launches, downloaded after the loop's one synchronisation.  Both hooks return what the

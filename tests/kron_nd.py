@@ -10,6 +10,8 @@
   every case; the GPU tolerances of test_gpu_kron_nd.py mean something only because of that.
 * `problem`, `oracle_predict`, `oracle_grad` cache a case's arrays and its oracle results: each is computed once per session, shared by
   the tests that need it and never written to.
+* `BLOCK_CASES` (with `block_problem`, `block_oracle_predict`, `block_oracle_grad`, `BLOCK_EDGE_GRIDS`) are the grids beyond one 128-row
+  block of the GEMM-panel path: test_cpu_kron_blocks.py pins them, test_gpu_kron_blocks.py and test_gpu_kron_panel_stages.py use them.
 """
 import functools
 from collections import OrderedDict
@@ -140,6 +142,96 @@ def problem(name, N=None, shift=0.0):
     return X, Y, p
 
 
+# Grids beyond ONE 128-row block of the GEMM-panel path (operands are padded to 128: every grid above has Mq0 = Mq1 = 128 and one block per
+# factor).  id -> as CASES; the comment is (block counts nb0, nb1) per latent and what the case is there for.  The c of each case is tuned on
+# the CPU (test_cpu_kron_blocks.py) to the same fixture conditions.  A table of its own: _seed indexes into CASES.
+BLOCK_CASES = OrderedDict([
+    ('b21', _case((2, 1), (130, 12), N=301, c=0.4)),                        # 2, 1: Mq0 = 256 != Mq1 = 128
+    ('b12', _case((1, 2), (9, 130), N=303, c=0.5)),                         # 1, 2: the transposed strides
+    ('bmix', _case((2, 1), (130, 12), (12, 130), N=305, c=0.5)),            # f 2, 1 and g 1, 2 in one step
+    ('b3', _case((1, 1), (257, 5), N=1031, c=0.5)),                         # 3, 1; Nc = 2048: nk = 128, dP0's split-K has S = 56 != nk
+    ('bedge', _case((3, 1), (129, 9), (128, 9), N=307, c=0.4)),             # f 2, 1 (one real row in the second block) beside g 1, 1 (no padding)
+    ('b22', _case((2, 1), (130, 129), N=309, c=0.35)),                       # 2, 2: four output tiles per split-K slice; literal form 16 770^2
+])
+# further grids of the stage tests (tests/test_gpu_kron_panel_stages.py), block_edge_problem(grid): one point in a factor beside two
+# blocks, a full block beside one row past it, a ragged second block beside three points
+BLOCK_EDGE_GRIDS = [(1, 130), (128, 129), (200, 3)]
+BLOCK_EDGE_C = 0.35
+
+
+@functools.lru_cache(maxsize=None)
+def block_edge_problem(grid):
+    """(X, Y, p) of a grid of BLOCK_EDGE_GRIDS at N = 33 rows and (D0, D1) = (1, 1) (read-only)"""
+    X, Y, p = make_kron_problem_nd(33, grid[0], grid[1], 1, 1, 6000 + 131 * grid[0] + grid[1], c=BLOCK_EDGE_C)
+    _freeze(X, Y, p)
+    return X, Y, p
+
+
+BLOCK_LITERAL = [k for k in BLOCK_CASES if k != 'b22']      # cases whose literal (dense) oracle is evaluated; b22: kronp_ref.factored_* only
+
+
+BLOCK_MATERN = ('b21', ('matern32', 'rbf'), ('matern52', 'matern52'))      # case, kinds of f, kinds of g: the Matern run of the block cases
+
+
+def block_matern_fixture():
+    """(X, Y, p) of the BLOCK_MATERN case with its kinds in p (arrays shared with block_problem's cache)"""
+    import kron_matern_ref as kmr
+    X, Y, p = block_problem(BLOCK_MATERN[0])
+    return X, Y, kmr.with_kinds(p, BLOCK_MATERN[1], BLOCK_MATERN[2])
+
+
+@functools.lru_cache(maxsize=None)
+def block_matern_oracle():
+    """(predict rows at g_offset 0, (elbo, data, kl, grads)) of the Matern fixture from tests/kron_matern_ref.py (literal order)"""
+    import kron_matern_ref as kmr
+    X, Y, p = block_matern_fixture()
+    return kmr.kron_build_predict(X, p, JITTER, 0.0), kmr.kron_elbo_and_grad(X, Y, p, JITTER, scale=block_scale(BLOCK_MATERN[0]))
+
+
+@functools.lru_cache(maxsize=None)
+def block_problem(name, N=None):
+    """(X, Y, p) of a case of BLOCK_CASES (read-only); N overrides the case's row count"""
+    k = BLOCK_CASES[name]
+    g = k['g'] or (None, None)
+    X, Y, p = make_kron_problem_nd(N or k['N'], k['f'][0], k['f'][1], k['D'][0], k['D'][1], 5000 + list(BLOCK_CASES).index(name), M0g=g[0], M1g=g[1],
+                                   c=k['c'])
+    _freeze(X, Y, p)
+    return X, Y, p
+
+
+def block_scale(name):
+    return 105280.0 / BLOCK_CASES[name]['N']
+
+
+def block_counts(name):
+    """((nb0, nb1) of f, (nb0, nb1) of g): 128-row blocks per factor"""
+    k = BLOCK_CASES[name]
+    return tuple(tuple(-(-m // 128) for m in grid) for grid in (k['f'], k['g'] or k['f']))
+
+
+@functools.lru_cache(maxsize=None)
+def block_oracle_predict(name, g_offset):
+    """the 9 prediction rows: the literal oracle, for b22 the factored restatement (pinned to the literal one in test_cpu_kron_blocks.py)"""
+    X, Y, p = block_problem(name)
+    if name in BLOCK_LITERAL:
+        import zigp_oracle as o
+        return tuple(np.asarray(r).reshape(-1) for r in o.kron_build_predict(X, p, JITTER, g_offset))
+    import kronp_ref
+    return tuple(kronp_ref.factored_predict(X, p, JITTER, g_offset))
+
+
+@functools.lru_cache(maxsize=None)
+def block_oracle_grad(name, include_kl=True, scale=None):
+    """(elbo, data, kl, grads) at jitter 1e-5 and the case's scale (or `scale`), from the same reference as block_oracle_predict"""
+    X, Y, p = block_problem(name)
+    scale = block_scale(name) if scale is None else scale
+    if name in BLOCK_LITERAL:
+        import zigp_oracle_torch as ot
+        return ot.kron_elbo_and_grad(X, Y, p, JITTER, scale=scale, include_kl=include_kl)
+    import kronp_ref
+    return kronp_ref.factored_elbo_and_grad(X, Y, p, JITTER, scale=scale, include_kl=include_kl)
+
+
 @functools.lru_cache(maxsize=None)
 def fit_problem(name):
     k = FIT_CASES[name]
@@ -215,6 +307,13 @@ def fixture_floor_and_cond(X, p, ref=None, jit=JITTER):
             K = o.rbf_K(Z, None, p['ell_' + tag][q], float(np.squeeze(p['var_' + tag][q]))) + jit * np.eye(Z.shape[0])
             cond = max(cond, float(np.linalg.cond(K)))
     return floor, cond
+
+
+def fixture_cond(p, jit=JITTER):
+    """max cond(K_p + jitter) over the four factors alone (a grid whose literal form is too large for the floor)"""
+    import zigp_oracle as o
+    return max(float(np.linalg.cond(o.rbf_K(p['Z' + tag][q], None, p['ell_' + tag][q], float(np.squeeze(p['var_' + tag][q])))
+                                    + jit * np.eye(p['Z' + tag][q].shape[0]))) for tag in 'fg' for q in range(2))
 
 
 def rbf_K_difference_form(X, X2, lengthscales, variance):

@@ -450,8 +450,42 @@ int mm(zigp_ctx* c, const double* A, int64_t lda, const double* B, int64_t ldb, 
   return run_gemm<AL, BL, false>(c, tl, mk_args(A, lda, B, ldb, C, ldc), EpiStore());
 }
 
+// Test hook of a panel step (zigp_test_kron_panel_step, include/zigp_diag.h).  Each tap is a device-to-device copy enqueued on the
+// current stream (the latent's own) right behind the launch that produces the value, into a buffer of its own; flush() downloads them
+// once the step has finished.  Host code only: an ordinary call passes no tap and enqueues exactly what it did before.
+struct KpTap {
+  const zigp_stage_kron_panels* s;
+  struct Snap { double* host; DevBuf dev; size_t n; };
+  std::vector<Snap> snaps;
+  DevBuf inject[2];       // device copies of the injected cotangents [4][N], uploaded before the step
+  int64_t facts[ZIGP_KPF_COUNT];
+  int snap(zigp_ctx* c, double* host, const double* dev, size_t n) {
+    if (!host || n == 0) return 0;
+    snaps.emplace_back();
+    Snap& q = snaps.back();
+    q.host = host; q.n = n;
+    ZIGP_ENSURE(c, q.dev, n);
+    ZIGP_HIP(c, hipMemcpyAsync(q.dev.p, dev, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+  }
+  int flush(zigp_ctx* c) {      // the streams are idle
+    for (Snap& q : snaps) ZIGP_HIP(c, hipMemcpy(q.host, q.dev.p, sizeof(double) * q.n, hipMemcpyDeviceToHost));
+    if (s->facts) memcpy(s->facts, facts, sizeof(facts));
+    return 0;
+  }
+};
+// the tap set of latent h (nullptr: an ordinary call); KP_SNAP(field, device pointer, count) is a no-op without one
+struct KpTapLat {
+  KpTap* tap; int h;
+  const zigp_kronp_tap_latent* t() const { return tap ? &tap->s->lat[h] : nullptr; }
+  int64_t* facts() const { return tap ? tap->facts + ZIGP_KPF_LAT + h * ZIGP_KPF_PER_LAT : nullptr; }
+};
+#define KP_SNAP(kp, field, dev, n) do { if ((kp).tap) ZIGP_TRY((kp).tap->snap(c, (kp).t()->field, (dev), (n))); } while (0)
+
 // out[Mqa x Mqb] = PA[Mqa][Nc] diag(scale) PB[Mqb][Nc]^T, split-K over S slices + plane sum
-int nred(zigp_ctx* c, KronLatent& lt, const double* PA, const double* PB, const double* scale, int nba, int nbb, int64_t Nc, double* out) {
+// which: the reduction's index in zigp_kronp_tap_latent::planes_of order (the hook's facts and raw planes)
+int nred(zigp_ctx* c, KronLatent& lt, const double* PA, const double* PB, const double* scale, int nba, int nbb, int64_t Nc, double* out,
+         KpTapLat kp = {nullptr, 0}, int which = 0) {
   const int nk = (int)(Nc / BK);
   int S = std::max(1, std::min(nk, 512 / std::max(1, nba * nbb)));
   TileList tl;
@@ -468,6 +502,10 @@ int nred(zigp_ctx* c, KronLatent& lt, const double* PA, const double* PB, const 
   g.slice_stride = plane; g.kscale = scale;
   if (scale) ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_KCONTIG, true>(c, tl, g, EpiStore())));
   else ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_KCONTIG, false>(c, tl, g, EpiStore())));
+  if (kp.tap) {
+    kp.facts()[ZIGP_KPF_S_DP0 + which] = S;
+    if (kp.t()->planes_of == which) KP_SNAP(kp, planes, lt.planes.p, (size_t)S * plane);
+  }
   hipLaunchKernelGGL(k_sum_planes, dim3(ceil_div(plane, 256)), dim3(256), 0, c->stream, lt.planes.p, S, plane, out);
   ZIGP_HIP(c, hipGetLastError());
   return 0;
@@ -490,7 +528,7 @@ int validate_kron(zigp_ctx* c, const zigp_kron_params* p, int lik = ZIGP_LIK_ONO
 // factor MxM forward: K_p (+jitter), L_p, W_p, P_p = W^T W
 // kind: the factor's ZIGP_KERN_* (a Matern K_p: k_kron_matern_matrix in place of k_rbf_matrix; everything behind K_p is the same)
 int factor_forward(zigp_ctx* c, KronFactor& f, int M, int D, int col0, const double* Z, const double* ell, double var, double jitter,
-                   int kind = ZIGP_KERN_RBF) {
+                   int kind = ZIGP_KERN_RBF, KpTapLat kp = {nullptr, 0}, int q = 0) {
   f.M = M; f.Mq = (int)round_up(M, BM); f.D = D; f.col0 = col0; f.var = var; f.kind = kind;
   f.ell.assign(ell, ell + D);
   const int Mq = f.Mq, nb = Mq / BM, kb = BM / BK;
@@ -505,14 +543,18 @@ int factor_forward(zigp_ctx* c, KronFactor& f, int M, int D, int col0, const dou
     hipLaunchKernelGGL(k_rbf_matrix, dim3(ceil_div((int64_t)mm_, 256)), dim3(256), 0, c->stream, f.Z.p, (int64_t)M, f.Z.p, (int64_t)M, hyp, jitter,
                        f.K.p, (int64_t)Mq, (int64_t)Mq, (int64_t)Mq);
   ZIGP_HIP(c, hipGetLastError());
+  KP_SNAP(kp, f[q].K, f.K.p, mm_);
   ZIGP_HIP(c, hipMemcpyAsync(f.L.p, f.K.p, sizeof(double) * mm_, hipMemcpyDeviceToDevice, c->stream));
   ZIGP_TRY(potrf_trtri(c, f.L.p, f.W.p, f.T.p, Mq, true, M, pivot_tol(var, jitter, c->pivot_rtol)));
+  KP_SNAP(kp, f[q].L, f.L.p, mm_);
+  KP_SNAP(kp, f[q].W, f.W.p, mm_);
   TileList t;
   ZIGP_TRY(get_tiles(c, "bw_s:" + std::to_string(nb), [&](std::vector<GemmTile>& v) {
     for (int bi = 0; bi < nb; ++bi)
       for (int bj = 0; bj < nb; ++bj) v.push_back(mk_tile(bi, bj, std::max(bi, bj) * kb, nb * kb));
   }, t));
   ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false>(c, t, mk_args(f.W.p, Mq, f.W.p, Mq, f.P.p, Mq), EpiStore())));
+  KP_SNAP(kp, f[q].P, f.P.p, mm_);
   return 0;
 }
 
@@ -527,9 +569,9 @@ int upload_grid(zigp_ctx* c, DevBuf& b, const double* src, int M0, int M1, int M
   return 0;
 }
 
-int latent_setup(zigp_ctx* c, KronLatent& lt, const KronHostLatent& h, int D0, int D1, double jitter) {
-  ZIGP_TRY(factor_forward(c, lt.f[0], h.M[0], D0, 0, h.Z[0], h.ell[0], h.var[0], jitter, h.kind[0]));
-  ZIGP_TRY(factor_forward(c, lt.f[1], h.M[1], D1, D0, h.Z[1], h.ell[1], h.var[1], jitter, h.kind[1]));
+int latent_setup(zigp_ctx* c, KronLatent& lt, const KronHostLatent& h, int D0, int D1, double jitter, KpTapLat kp = {nullptr, 0}) {
+  ZIGP_TRY(factor_forward(c, lt.f[0], h.M[0], D0, 0, h.Z[0], h.ell[0], h.var[0], jitter, h.kind[0], kp, 0));
+  ZIGP_TRY(factor_forward(c, lt.f[1], h.M[1], D1, D0, h.Z[1], h.ell[1], h.var[1], jitter, h.kind[1], kp, 1));
   const int M0 = h.M[0], M1 = h.M[1], Mq0 = lt.f[0].Mq, Mq1 = lt.f[1].Mq, nb0 = Mq0 / BM, nb1 = Mq1 / BM;
   ZIGP_TRY(upload_grid(c, lt.U, h.u, M0, M1, Mq0, Mq1, false));
   ZIGP_TRY(upload_grid(c, lt.S, h.s, M0, M1, Mq0, Mq1, false));
@@ -543,6 +585,12 @@ int latent_setup(zigp_ctx* c, KronLatent& lt, const KronHostLatent& h, int D0, i
   hipLaunchKernelGGL(k_diag, dim3(ceil_div(Mq0, 256)), dim3(256), 0, c->stream, lt.f[0].P.p, (int64_t)Mq0, Mq0, lt.vec.p);
   hipLaunchKernelGGL(k_diag, dim3(ceil_div(Mq1, 256)), dim3(256), 0, c->stream, lt.f[1].P.p, (int64_t)Mq1, Mq1, lt.vec.p + Mq0);
   ZIGP_HIP(c, hipGetLastError());
+  if (kp.tap) {
+    int64_t* fa = kp.facts();
+    fa[ZIGP_KPF_MQ0] = Mq0; fa[ZIGP_KPF_MQ1] = Mq1; fa[ZIGP_KPF_NB0] = nb0; fa[ZIGP_KPF_NB1] = nb1;
+    KP_SNAP(kp, U, lt.U.p, g); KP_SNAP(kp, S2, lt.S2.p, g); KP_SNAP(kp, T0, lt.T0.p, g); KP_SNAP(kp, Al, lt.Al.p, g);
+    KP_SNAP(kp, vec, lt.vec.p, (size_t)Mq0 + Mq1);
+  }
   return 0;
 }
 
@@ -590,7 +638,7 @@ int latent_forward_panels(zigp_ctx* c, KronLatent& lt, const double* dX, int64_t
   return 0;
 }
 
-int latent_backward(zigp_ctx* c, KronLatent& lt, const double* dX, int64_t N, int64_t Nc, int ldx, bool with_kl) {
+int latent_backward(zigp_ctx* c, KronLatent& lt, const double* dX, int64_t N, int64_t Nc, int ldx, bool with_kl, KpTapLat kp = {nullptr, 0}) {
   KronFactor &f0 = lt.f[0], &f1 = lt.f[1];
   const int nbn = (int)(Nc / BN), nb0 = f0.Mq / BM, nb1 = f1.Mq / BM;
   const int Mq0 = f0.Mq, Mq1 = f1.Mq;
@@ -615,29 +663,38 @@ int latent_backward(zigp_ctx* c, KronLatent& lt, const double* dX, int64_t N, in
       hipLaunchKernelGGL(k_kron_kgrad, dim3(f.Mq), dim3(256), 0, c->stream, f.Bx.p, f.Ap.p, f.PdA.p, f.Kp.p, lt.gm.p, dq[p], dX, N, ldx, f.col0,
                          f.Z.p, f.M, f.D, Nc, f.krow.p);
     ZIGP_HIP(c, hipGetLastError());
+    KP_SNAP(kp, f[p].krow_n, f.krow.p, (size_t)f.Mq * (2 + 2 * f.D));
     // dP_p (data) = E_p K_p^T
     ZIGP_ENSURE(c, f.dP, (size_t)f.Mq * f.Mq);
-    ZIGP_TRY(nred(c, lt, f.E.p, f.Kp.p, nullptr, f.Mq / BM, f.Mq / BM, Nc, f.dP.p));
+    ZIGP_TRY(nred(c, lt, f.E.p, f.Kp.p, nullptr, f.Mq / BM, f.Mq / BM, Nc, f.dP.p, kp, p));
+    KP_SNAP(kp, f[p].dP_red, f.dP.p, (size_t)f.Mq * f.Mq);
   }
   const size_t g = (size_t)Mq0 * Mq1;
   ZIGP_ENSURE(c, lt.dAl, g); ZIGP_ENSURE(c, lt.dS2, g); ZIGP_ENSURE(c, lt.dU, g);
   // dAlpha = K0 diag(gm) K1^T ; dS2 = A0^2 diag(gv) (A1^2)^T
-  ZIGP_TRY(nred(c, lt, f0.Kp.p, f1.Kp.p, lt.gm.p, nb0, nb1, Nc, lt.dAl.p));
-  ZIGP_TRY(nred(c, lt, f0.Asq.p, f1.Asq.p, lt.gv.p, nb0, nb1, Nc, lt.dS2.p));
+  ZIGP_TRY(nred(c, lt, f0.Kp.p, f1.Kp.p, lt.gm.p, nb0, nb1, Nc, lt.dAl.p, kp, 2));
+  KP_SNAP(kp, dAl, lt.dAl.p, g);
+  ZIGP_TRY(nred(c, lt, f0.Asq.p, f1.Asq.p, lt.gv.p, nb0, nb1, Nc, lt.dS2.p, kp, 3));
+  KP_SNAP(kp, dS2, lt.dS2.p, g);
   // ---- MxM: Alpha = P0 U P1 ----
   // dU = P0 dAl P1 : T1 = dAl P1 ; dU = P0 T1
   ZIGP_TRY((mm<LAY_KCONTIG, LAY_MNCONTIG>(c, lt.dAl.p, Mq1, f1.P.p, Mq1, lt.T1.p, Mq1, nb0, nb1, nb1)));
+  KP_SNAP(kp, T1_a, lt.T1.p, g);
   ZIGP_TRY((mm<LAY_KCONTIG, LAY_MNCONTIG>(c, f0.P.p, Mq0, lt.T1.p, Mq1, lt.dU.p, Mq1, nb0, nb1, nb0)));
+  KP_SNAP(kp, dU, lt.dU.p, g);
   // dP0 += dAl (U P1)^T = dAl T0^T  (T0 = U P1 from setup) ; dP1 += (P0 U)^T dAl
   {
     TileList t;
     ZIGP_TRY(tiles_full(c, nb0, nb0, nb1 * (BM / BK), t));
     ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_KCONTIG, false>(c, t, mk_args(lt.dAl.p, Mq1, lt.T0.p, Mq1, f0.dP.p, Mq0), EpiAccum())));
+    KP_SNAP(kp, f[0].dP_acc, f0.dP.p, (size_t)Mq0 * Mq0);
     // T1 = P0 U  ([Mq0][Mq1]) ; dP1 += T1^T dAl
     ZIGP_TRY((mm<LAY_KCONTIG, LAY_MNCONTIG>(c, f0.P.p, Mq0, lt.U.p, Mq1, lt.T1.p, Mq1, nb0, nb1, nb0)));
+    KP_SNAP(kp, T1_b, lt.T1.p, g);
     TileList t2;
     ZIGP_TRY(tiles_full(c, nb1, nb1, nb0 * (BM / BK), t2));
     ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false>(c, t2, mk_args(lt.T1.p, Mq1, lt.dAl.p, Mq1, f1.dP.p, Mq1), EpiAccum())));
+    KP_SNAP(kp, f[1].dP_acc, f1.dP.p, (size_t)Mq1 * Mq1);
   }
   // KL pieces on P: Q0 = U P1 U^T = T0 U^T ; Q1 = U^T P0 U = U^T T1(P0 U)
   for (int p = 0; p < 2; ++p) {
@@ -652,13 +709,18 @@ int latent_backward(zigp_ctx* c, KronLatent& lt, const double* dX, int64_t N, in
         TileList t; ZIGP_TRY(tiles_full(c, nb1, nb1, nb0 * (BM / BK), t));
         ZIGP_TRY((run_gemm<LAY_MNCONTIG, LAY_MNCONTIG, false>(c, t, mk_args(lt.U.p, Mq1, lt.T1.p, Mq1, f.G.p, Mq1), EpiStore())));
       }
+      KP_SNAP(kp, f[p].Q, f.G.p, (size_t)Mq * Mq);
     }
     const KronFactor& fo = lt.f[1 - p];
     hipLaunchKernelGGL(k_kron_dp_combine, dim3(ceil_div((int64_t)Mq * Mq, 256)), dim3(256), 0, c->stream, f.dP.p, f.G.p, lt.S2.p,
                        lt.vec.p + (p == 0 ? Mq0 : 0), p, Mq, fo.Mq, fo.M, (int64_t)Mq1, with_kl ? 1 : 0);
+    KP_SNAP(kp, f[p].dP_comb, f.dP.p, (size_t)Mq * Mq);
     // G = -(P dP P) - kl * 0.5 * M_other * P :  T = dP P ; Kt = P T
     ZIGP_TRY((mm<LAY_KCONTIG, LAY_MNCONTIG>(c, f.dP.p, Mq, f.P.p, Mq, f.T.p, Mq, nb, nb, nb)));
-    ZIGP_TRY((mm<LAY_KCONTIG, LAY_MNCONTIG>(c, f.P.p, Mq, f.T.p, Mq, f.L.p, Mq, nb, nb, nb)));   // L is free after setup? no: keep logdet source
+    KP_SNAP(kp, f[p].T, f.T.p, (size_t)Mq * Mq);
+    // P dP P goes into L: the KL scalars (k_kron_kl, which takes the log-determinants from L) are enqueued before the backward pass
+    ZIGP_TRY((mm<LAY_KCONTIG, LAY_MNCONTIG>(c, f.P.p, Mq, f.T.p, Mq, f.L.p, Mq, nb, nb, nb)));
+    KP_SNAP(kp, f[p].PdPP, f.L.p, (size_t)Mq * Mq);
     ZIGP_HIP(c, hipGetLastError());
   }
   return 0;
@@ -674,7 +736,7 @@ zigp_ctx::~zigp_ctx() = default;
 
 namespace {
 
-int kron_run_panels(zigp_ctx* c, const KronCall& k);
+int kron_run_panels(zigp_ctx* c, const KronCall& k, KpTap* tap = nullptr);
 
 // Data-parallel exchange of the PANEL path (grids beyond the fused kernels' capacity): its results reach the host piecewise, so with a
 // communicator (zigp_comm_init) the assembled outputs take one more round trip -- packed, summed over ranks on the device, unpacked.
@@ -736,7 +798,7 @@ int kron_run(zigp_ctx* c, const KronCall& k) {
   return kron_run_panels(c, k);
 }
 
-int kron_run_panels(zigp_ctx* c, const KronCall& k) {
+int kron_run_panels(zigp_ctx* c, const KronCall& k, KpTap* tap) {
   const zigp_kron_params* p = k.p;
   const double *X = k.X, *Y = k.Y;
   const int64_t N = k.N;
@@ -761,7 +823,7 @@ int kron_run_panels(zigp_ctx* c, const KronCall& k) {
   ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
   for (int h = 0; h < nlat; ++h) {
     OnStream on(c, h == 0 ? c->stream_main : c->stream2);
-    ZIGP_TRY(latent_setup(c, ks.lat[h], hl[h], D0, D1, k.jitter));
+    ZIGP_TRY(latent_setup(c, ks.lat[h], hl[h], D0, D1, k.jitter, KpTapLat{tap, h}));
   }
   ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
   int* hinfo = nullptr;
@@ -774,6 +836,7 @@ int kron_run_panels(zigp_ctx* c, const KronCall& k) {
       const int Mq0 = lt.f[0].Mq, Mq1 = lt.f[1].Mq;
       hipLaunchKernelGGL(k_kron_kl, dim3(1), dim3(256), 0, c->stream, lt.U.p, lt.Al.p, lt.S.p, lt.vec.p, lt.vec.p + Mq0, lt.f[0].L.p, lt.f[1].L.p,
                          lt.f[0].M, lt.f[1].M, Mq0, Mq1, lt.vec.p + Mq0 + Mq1);
+      KP_SNAP((KpTapLat{tap, h}), klv, lt.vec.p + Mq0 + Mq1, 5);
       ZIGP_TRY(download(c, lt.vec.p + Mq0 + Mq1, 8, &hkl[h]));
     }
   }
@@ -782,6 +845,7 @@ int kron_run_panels(zigp_ctx* c, const KronCall& k) {
     OnStream on(c, h == 0 ? c->stream_main : c->stream2);
     KronLatent& lt = ks.lat[h];
     ZIGP_TRY(latent_forward_panels(c, lt, ks.X.p, N, Nc, ldx, need_grad));
+    KP_SNAP((KpTapLat{tap, h}), part, lt.part.p, (size_t)4 * Nc);
     ZIGP_ENSURE(c, lt.gm, Nc); ZIGP_ENSURE(c, lt.gv, Nc); ZIGP_ENSURE(c, lt.dq0, Nc); ZIGP_ENSURE(c, lt.dq1, Nc);
   }
   ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
@@ -810,6 +874,18 @@ int kron_run_panels(zigp_ctx* c, const KronCall& k) {
   ZIGP_HIP(c, hipGetLastError());
   double* hacc = nullptr;
   ZIGP_TRY(download(c, ks.acc.p, (size_t)blocks * KPW_ACC, &hacc));
+  if (tap) {   // the hook: injected cotangents over what the point-wise launch wrote (columns < N), then the four vectors as the backward pass reads them
+    tap->facts[ZIGP_KPF_NC] = Nc; tap->facts[ZIGP_KPF_NK] = Nc / BK;
+    for (int h = 0; h < nlat; ++h) {
+      KronLatent& lt = ks.lat[h];
+      double* const v[4] = {lt.gm.p, lt.gv.p, lt.dq0.p, lt.dq1.p};
+      for (int i = 0; i < 4; ++i) {
+        if (tap->inject[h].p)
+          ZIGP_HIP(c, hipMemcpyAsync(v[i], tap->inject[h].p + (size_t)i * N, sizeof(double) * N, hipMemcpyDeviceToDevice, c->stream));
+        if (tap->s->lat[h].cot) ZIGP_TRY(tap->snap(c, tap->s->lat[h].cot + (size_t)i * Nc, v[i], (size_t)Nc));
+      }
+    }
+  }
 
   double *hkrow[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, *hgu[2] = {nullptr, nullptr}, *hgs[2] = {nullptr, nullptr};
   if (need_grad) {
@@ -817,7 +893,8 @@ int kron_run_panels(zigp_ctx* c, const KronCall& k) {
     for (int h = 0; h < nlat; ++h) {
       OnStream on(c, h == 0 ? c->stream_main : c->stream2);
       KronLatent& lt = ks.lat[h];
-      ZIGP_TRY(latent_backward(c, lt, ks.X.p, N, Nc, ldx, include_kl != 0));
+      const KpTapLat kp{tap, h};
+      ZIGP_TRY(latent_backward(c, lt, ks.X.p, N, Nc, ldx, include_kl != 0, kp));
       const int M0 = lt.f[0].M, M1 = lt.f[1].M, Mq0 = lt.f[0].Mq, Mq1 = lt.f[1].Mq;
       for (int q = 0; q < 2; ++q) {
         KronFactor& f = lt.f[q];
@@ -825,18 +902,21 @@ int kron_run_panels(zigp_ctx* c, const KronCall& k) {
         // G = -(P dP P) - kl*0.5*M_other*P  -> f.G ; then Kuu-style reductions into krow
         hipLaunchKernelGGL(k_kron_dk, dim3(ceil_div((int64_t)Mq * Mq, 256)), dim3(256), 0, c->stream, f.L.p, f.P.p,
                            include_kl ? 0.5 * (double)lt.f[1 - q].M : 0.0, (int64_t)Mq * Mq, f.G.p);
+        KP_SNAP(kp, f[q].G, f.G.p, (size_t)Mq * Mq);
         if (f.kind != ZIGP_KERN_RBF)
           hipLaunchKernelGGL(k_kuu_grad_matern, dim3(Mq), dim3(256), 0, c->stream, f.G.p, f.K.p, k.jitter, f.Z.p, f.M,
                              make_hyp(f.ell.data(), f.var, f.D), f.kind, (int64_t)Mq, f.krow.p);
         else
           hipLaunchKernelGGL(k_kuu_grad, dim3(Mq), dim3(256), 0, c->stream, f.G.p, f.K.p, k.jitter, f.Z.p, f.M, f.D, (int64_t)Mq, f.krow.p);
         ZIGP_HIP(c, hipGetLastError());
+        KP_SNAP(kp, f[q].krow, f.krow.p, (size_t)Mq * (2 + 2 * f.D));
         ZIGP_TRY(download(c, f.krow.p, (size_t)Mq * (2 + 2 * f.D), &hkrow[h][q]));
       }
       // u, s gradients (reuse T0 / T1 as outputs)
       hipLaunchKernelGGL(k_kron_us, dim3(ceil_div((int64_t)M0 * M1, 256)), dim3(256), 0, c->stream, lt.dU.p, lt.Al.p, lt.dS2.p, lt.S.p, lt.vec.p,
                          lt.vec.p + Mq0, M0, M1, Mq1, include_kl ? 1 : 0, lt.T0.p, lt.T1.p);
       ZIGP_HIP(c, hipGetLastError());
+      KP_SNAP(kp, gu, lt.T0.p, (size_t)M0 * M1); KP_SNAP(kp, gs, lt.T1.p, (size_t)M0 * M1);
       ZIGP_TRY(download(c, lt.T0.p, (size_t)M0 * M1, &hgu[h]));
       ZIGP_TRY(download(c, lt.T1.p, (size_t)M0 * M1, &hgs[h]));
     }
@@ -1182,6 +1262,34 @@ int zigp_test_kron_fused_step(zigp_ctx* c, const zigp_stage_kron_fused* s) {
   kron_call_derive(k);
   kron_set_kinds(c, k.hl, nlat);
   ZIGP_TRY(kronf_run(c, k, nullptr, &tap));
+  return tap.flush(c);
+}
+
+// One value-and-gradient step of the panel path through kron_run_panels itself, with its device buffers snapshot (KpTap)
+int zigp_test_kron_panel_step(zigp_ctx* c, const zigp_stage_kron_panels* s) {
+  if (!c) return ZIGP_EARG;
+  if (!s) return fail_arg(c, "zigp_test_kron_panel_step: bad arguments");
+  ZIGP_TRY(validate_kron(c, s->p, s->lik));
+  const int nlat = s->lik == ZIGP_LIK_ONOFF ? 2 : 1;
+  if (s->N < 1 || !s->X || !s->Y || !s->grads || !(s->jitter >= 0)) return fail_arg(c, "zigp_test_kron_panel_step: need N >= 1 rows X, Y, grads and jitter >= 0");
+  for (int h = 0; h < nlat; ++h)
+    if (s->lat[h].planes_of < 0 || s->lat[h].planes_of > 3) return fail_arg(c, "zigp_test_kron_panel_step: planes_of must be 0 .. 3");
+  KronHostLatent kinds[2] = {};
+  kron_set_kinds(c, kinds, nlat);
+  if (!c->kron_panels && kf_eligible(s->p, nlat) && kron_kinds_fused(c, kinds, nlat))
+    return fail_arg(c, "zigp_test_kron_panel_step: this step runs on the fused Kronecker kernels (force the panels with zigp_set_kron_panels)");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  KpTap tap;
+  tap.s = s;
+  memset(tap.facts, 0, sizeof(tap.facts));
+  for (int h = 0; h < nlat; ++h)
+    if (s->lat[h].inject) ZIGP_TRY(stage_upload_rows(c, tap.inject[h], s->lat[h].inject, 4, 4, s->N));
+  KronCall k = {};
+  k.p = s->p; k.lik = s->lik; k.X = s->X; k.Y = s->Y; k.N = s->N; k.jitter = s->jitter; k.scale = s->scale; k.g_offset = s->g_offset; k.f_mu = s->f_mu;
+  k.include_kl = s->include_kl; k.elbo_data = s->elbo_data; k.kl = s->kl; k.grads = s->grads; k.d_offset = s->d_f_mu;
+  kron_call_derive(k);
+  kron_set_kinds(c, k.hl, nlat);
+  ZIGP_TRY(kron_run_panels(c, k, &tap));
   return tap.flush(c);
 }
 

@@ -184,6 +184,31 @@ class zigp_stage_kron_fused(C.Structure):   # include/zigp_diag.h
                 ('grads', C.POINTER(zigp_kron_grads)), ('d_f_mu', dp)]
 
 
+KPT_FACTOR = ('K', 'L', 'W', 'P', 'krow_n', 'dP_red', 'dP_acc', 'Q', 'dP_comb', 'T', 'PdPP', 'G', 'krow')
+
+
+class zigp_kronp_tap_factor(C.Structure):   # include/zigp_diag.h
+    _fields_ = [(k, dp) for k in KPT_FACTOR]
+
+
+class zigp_kronp_tap_latent(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('f', zigp_kronp_tap_factor * 2), ('U', dp), ('S2', dp), ('T0', dp), ('Al', dp), ('vec', dp), ('klv', dp), ('part', dp),
+                ('inject', dp), ('cot', dp), ('planes_of', C.c_int32), ('planes', dp), ('dAl', dp), ('dS2', dp), ('T1_a', dp), ('dU', dp),
+                ('T1_b', dp), ('gu', dp), ('gs', dp)]
+
+
+KPF_LAT_FACTS = ('Mq0', 'Mq1', 'nb0', 'nb1', 'S_dP0', 'S_dP1', 'S_dAl', 'S_dS2')   # include/zigp_diag.h ZIGP_KPF_*: 'Nc', 'nk', then these per latent
+KPF_COUNT = 2 + 2 * len(KPF_LAT_FACTS)
+KP_REDUCTIONS = ('dP0', 'dP1', 'dAl', 'dS2')      # planes_of
+
+
+class zigp_stage_kron_panels(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('lik', C.c_int32), ('include_kl', C.c_int32), ('p', C.POINTER(zigp_kron_params)), ('X', dp), ('Y', dp), ('N', C.c_int64),
+                ('jitter', C.c_double), ('scale', C.c_double), ('g_offset', C.c_double), ('f_mu', C.c_double),
+                ('lat', zigp_kronp_tap_latent * 2), ('facts', C.POINTER(C.c_int64)), ('elbo_data', dp), ('kl', dp),
+                ('grads', C.POINTER(zigp_kron_grads)), ('d_f_mu', dp)]
+
+
 KFU_FACTS = (('RES_KLV', 1), ('RES_KROW0', 1), ('RES_KROW1', 1), ('RES_GU', 1), ('RES_GS', 1), ('RES_SIZE', 1), ('RES_PWS', 1), ('RES_INFO', 1),
              ('n_res', 1), ('grid', 1), ('big_off', 9), ('hyp_off', 10), ('n_img', 1), ('off_hyp', 1), ('off_hyp2', 1), ('off_z', 4), ('off_u', 2),
              ('off_s', 2), ('KH_SIZE', 1), ('KH_FAC', 1), ('KH_INV', 1), ('KH_ZC', 1), ('KH_ELL', 1), ('KH_VAR', 1), ('KH_NOISE', 1),
@@ -338,6 +363,7 @@ SIGNATURES = {
     'zigp_test_dense_pack': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_pack)]),
     'zigp_test_kron_pointwise': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_kron_pointwise)]),
     'zigp_test_kron_fused_step': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_kron_fused)]),
+    'zigp_test_kron_panel_step': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_kron_panels)]),
     'zigp_test_kron_fit_update': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_kron_fit_update)]),
     'zigp_test_dense_fit_update': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_dense_fit_update)]),
     'zigp_test_kron_kbuild': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, C.c_double, dp]),

@@ -1951,6 +1951,98 @@ class DenseEngine:
             out['u_%ss_sqrt' % tag] = a['us']
         return dict(elbo_data=float(sc[0]), kl=float(sc[1]), grads=out, facts={k: int(facts[i]) for i, k in enumerate(_lib.KFF_FACTS)}, lat=lat)
 
+    def test_kron_panel_step(self, p, X, Y, lik='onoff', jitter=1e-5, scale=1.0, g_offset=0.0, f_mu=0.0, include_kl=True, inject=None, taps=True,
+                             planes_of='dAl'):
+        """One value-and-gradient step of the GEMM-panel Kronecker path with its device buffers snapshot behind the launches
+        (zigp_test_kron_panel_step, include/zigp_diag.h, where every tap is written down).  Arguments as test_kron_fused_step; planes_of: the
+        split-K reduction whose raw planes are taken ('dP0', 'dP1', 'dAl', 'dS2').  Refused for a step an ordinary call runs on the fused
+        kernels (set_kron_panels forces the panels).
+        Returns dict(elbo_data, kl, grads, facts {Nc, nk, lat: [per latent {Mq0, Mq1, nb0, nb1, S_dP0, S_dP1, S_dAl, S_dS2}]}, lat [per latent:
+        dict(K, L, W, P, krow_n, dP_red, dP_acc, Q, dP_comb, T, PdPP, G, krow -- lists over the two factors, (Mq, Mq) or (Mq, 2 + 2 D); Q only
+        with include_kl --, U, S2, T0, Al, dAl, dS2, T1_a, dU, T1_b (Mq0, Mq1), vec (Mq0 + Mq1), klv (5, with include_kl), part, cot (4, Nc),
+        planes (S, nba 128, nbb 128), gu, gs (M0, M1))])."""
+        two = lik == 'onoff'
+        tags = ('f', 'g') if two else ('f',)
+        sp, keep, dims = self._pack_kron(p, tags=tags)
+        X = as_f64(X)
+        if X.ndim != 2 or X.shape[1] != dims[0] + dims[1]:
+            raise ValueError('X must be (N,%d)' % (dims[0] + dims[1]))
+        Y = as_f64(Y).reshape(-1)
+        N = X.shape[0]
+        if Y.size != N:
+            raise ValueError('Y must have N entries')
+        s = _lib.zigp_stage_kron_panels()
+        s.lik = self.LIK[lik] if not two else _lib.LIK_ONOFF
+        s.include_kl = 1 if include_kl else 0
+        s.p = C.pointer(sp)
+        s.X, s.Y, s.N = ptr(X), ptr(Y), N
+        s.jitter, s.scale, s.g_offset, s.f_mu = float(jitter), float(scale), float(g_offset), float(f_mu)
+        Nc = max(1024, -(-N // 1024) * 1024)
+        nk = Nc // 16
+        which = _lib.KP_REDUCTIONS.index(planes_of)
+        lat, hold = [], []
+        for h, tag in enumerate(tags):
+            M = (keep[tag][0].shape[0], keep[tag][1].shape[0])
+            Mq = tuple(-(-m // 128) * 128 for m in M)
+            t = s.lat[h]
+            t.planes_of = which
+            d = {}
+            if taps:
+                for k in _lib.KPT_FACTOR:
+                    if k == 'Q' and not include_kl:
+                        continue
+                    d[k] = [np.zeros((Mq[q], 2 + 2 * dims[q]) if k.startswith('krow') else (Mq[q], Mq[q])) for q in range(2)]
+                    for q in range(2):
+                        setattr(t.f[q], k, ptr(d[k][q]))
+                for k in ('U', 'S2', 'T0', 'Al', 'dAl', 'dS2', 'T1_a', 'dU', 'T1_b'):
+                    d[k] = np.zeros(Mq)
+                ba, bb = {'dP0': (Mq[0], Mq[0]), 'dP1': (Mq[1], Mq[1])}.get(planes_of, Mq)
+                S = max(1, min(nk, 512 // max(1, (ba // 128) * (bb // 128))))      # nred's rule; the step's own S comes back in facts
+                d.update(vec=np.zeros(Mq[0] + Mq[1]), part=np.zeros((4, Nc)), cot=np.zeros((4, Nc)), planes=np.zeros((S, ba, bb)),
+                         gu=np.zeros(M), gs=np.zeros(M))
+                if include_kl:
+                    d['klv'] = np.zeros(5)
+                for k, v in d.items():
+                    if not isinstance(v, list):
+                        setattr(t, k, ptr(v))
+            if inject is not None and inject[h] is not None:
+                inj = as_f64(inject[h], (4, N))
+                hold.append(inj)
+                t.inject = ptr(inj)
+            lat.append(d)
+        facts = (C.c_int64 * _lib.KPF_COUNT)()
+        s.facts = C.cast(facts, C.POINTER(C.c_int64))
+        sc = np.zeros(3)
+        s.elbo_data, s.kl, s.d_f_mu = sc.ctypes.data, sc.ctypes.data + 8, sc.ctypes.data + 16
+        gs = _lib.zigp_kron_grads()
+        g = {}
+        for tag in tags:
+            Z0, Z1, l0, l1, um, us = keep[tag]
+            a = dict(Z0=np.zeros_like(Z0), Z1=np.zeros_like(Z1), ell0=np.zeros_like(l0), ell1=np.zeros_like(l1), um=np.zeros_like(um), us=np.zeros_like(us))
+            g[tag] = a
+            setattr(gs, 'Z0' + tag, ptr(a['Z0'])); setattr(gs, 'Z1' + tag, ptr(a['Z1']))
+            setattr(gs, 'ell0' + tag, ptr(a['ell0'])); setattr(gs, 'ell1' + tag, ptr(a['ell1']))
+            setattr(gs, 'u_%sm' % tag, ptr(a['um'])); setattr(gs, 'u_%ss_sqrt' % tag, ptr(a['us']))
+        s.grads = C.pointer(gs)
+        _check(self.lib, self.ctx, self.lib.zigp_test_kron_panel_step(self.ctx, C.byref(s)))
+        out = dict(noise=gs.noise, f_mu=sc[2])
+        for tag in tags:
+            a = g[tag]
+            out['Z' + tag] = [a['Z0'], a['Z1']]
+            out['ell_' + tag] = [a['ell0'], a['ell1']]
+            out['var_' + tag] = [getattr(gs, 'var0' + tag), getattr(gs, 'var1' + tag)]
+            out['u_%sm' % tag] = a['um']
+            out['u_%ss_sqrt' % tag] = a['us']
+        nl = len(_lib.KPF_LAT_FACTS)
+        fd = dict(Nc=int(facts[0]), nk=int(facts[1]),
+                  lat=[{k: int(facts[2 + h * nl + i]) for i, k in enumerate(_lib.KPF_LAT_FACTS)} for h in range(len(tags))])
+        if taps:
+            for h, d in enumerate(lat):
+                if fd['lat'][h]['S_' + planes_of] != d['planes'].shape[0]:
+                    raise RuntimeError('test_kron_panel_step: the step split %s into %d slices, the binding sized its planes for %d'
+                                       % (planes_of, fd['lat'][h]['S_' + planes_of], d['planes'].shape[0]))
+        return dict(elbo_data=float(sc[0]), kl=float(sc[1]), grads=out, facts=fd, lat=lat)
+
     @staticmethod
     def kron_fit_sizes(shape, lik='onoff'):
         """block sizes of the free vector of kron_fit_steps (lik 'onoff': 17 blocks) or kron_head_fit_steps (10 blocks)"""
