@@ -537,6 +537,76 @@ typedef struct zigp_stage_dense_fit_update {
 } zigp_stage_dense_fit_update;
 int zigp_test_dense_fit_update(zigp_ctx* ctx, const zigp_stage_dense_fit_update* a);
 
+/* ---- The weight stage of the sample paths: what turns a draw of q(u) into the weight table the path kernels read, through the function the
+ * product entry points themselves call (path_weight_stage of csrc/zigp_paths.hip, kron_path_weight_stage of csrc/zigp_kronpaths.hip) behind the
+ * call's own M x M forward stage -- the same launches, grids and device buffers; the paths at Xnew are not run.  A tap is a stream-ordered
+ * device-to-device copy enqueued right behind the launch that produces the value, downloaded after the stage's synchronisation, so a later
+ * launch that reuses the buffer cannot matter; a NULL tap is not taken.  The work matrices a launch must write completely hold
+ * ZIGP_STAGE_SENTINEL_BYTE before the stage (an ordinary call clears them to 0): an element that still holds it was not written.  Both hooks
+ * synchronise, return what the entry point's factorisation check returns and leave the context usable. ---- */
+/* Dense model.  Mp = M rounded up to 128, Sp = S rounded up to 128, nst = sample tiles per pass (1, 2 or 4), ntile = ceil(S / 16) rounded up
+ * to nst, M4 / R4 = M / R rounded up to 4, F = M4 + R4.  "Diag" is the unwhitened parametrisation, "White" / "WhiteFull" the whitened ones. */
+typedef struct zigp_pathw_tap_latent {
+  double *Kuu, *W;      /* [Mp][Mp] as the call's latents_forward left them: Kuu + jitter I and W = L^-1, identity in the padding */
+  double *Lq;           /* WhiteFull: [Mp][Mp] the masked lower-triangular image of L_q, zero padding */
+  double *u, *s;        /* [Mp] as the device holds them, zero padding */
+  double *E;            /* [Mp][Sp] the staged eps, zero outside (M, S) */
+  double *FT;           /* [Sp][Mp] f_Z as the path kernel wrote it: FT[s][m], s < S, m < M; zero elsewhere */
+  double *rhs;          /* [Mp][Sp] after k_path_rhs (Diag: u + s o eps - f_Z; White / WhiteFull: t); exact zero outside (M, S) */
+  double *t;            /* Diag: [Mp][Sp] W rhs */
+  double *V0;           /* Diag: [Mp][Sp] W^T t, the weights BEFORE the refinement step */
+  double *KV;           /* Diag: Kuu V0 */
+  double *res;          /* Diag: rhs - Kuu V0 (k_path_axpy) */
+  double *t2, *cor;     /* Diag: W res and the correction W^T (W res) */
+  double *G, *H;        /* White / WhiteFull: G = W f_Z; WhiteFull: H = tril(L_q) E */
+  double *V;            /* [Mp][Sp] the final weights (Diag: V0 + cor by k_path_axpy) */
+  double *tab;          /* [ntile][F][16] the weight table after k_path_fill_v: rows < M4 from V, rows M4 .. F - 1 the cosine amplitudes as the host
+                           staged them.  The hook fills rows < M4 with the sentinel before k_path_fill_v */
+} zigp_pathw_tap_latent;
+enum { ZIGP_PWF_MODE = 0,      /* 0 Diag, 1 White, 2 WhiteFull */
+       ZIGP_PWF_SP, ZIGP_PWF_NST, ZIGP_PWF_NTILE,
+       ZIGP_PWF_MP,            /* [2] f, g; then M4 [2], R4 [2], F [2] */
+       ZIGP_PWF_M4 = ZIGP_PWF_MP + 2, ZIGP_PWF_R4 = ZIGP_PWF_M4 + 2, ZIGP_PWF_F = ZIGP_PWF_R4 + 2,
+       ZIGP_PWF_COUNT = ZIGP_PWF_F + 2 };
+typedef struct zigp_stage_path_weights {
+  const zigp_params* p;         /* read as zigp_sample_paths reads it (the context's parametrisation and kernels apply) */
+  double jitter;
+  const zigp_path_draw *draw_f, *draw_g;
+  int32_t S, reserved;
+  zigp_pathw_tap_latent lat[2];
+  int64_t* facts;               /* out [ZIGP_PWF_COUNT], may be NULL */
+} zigp_stage_path_weights;
+int zigp_test_path_weights(zigp_ctx* ctx, const zigp_stage_path_weights* a);
+
+/* Kronecker model and heads.  M = M0 M1, Mq_p = M_p rounded up to 128 (the row stride of K_p and W_p), M1p = M1 rounded up to 4,
+ * F = M0 M1p + R4.  The grid matrices are [S][M0][M1] (sample-major, factor-0-major inside a sample). */
+typedef struct zigp_kpathw_tap_latent {
+  double *K[2], *W[2];  /* [Mq_p][Mq_p] as factor_forward left them: K_p + jitter I, W_p = L_p^-1 */
+  double *E;            /* [M][S] eps as the draw holds it */
+  double *U, *Sq;       /* [M] */
+  double *FZ;           /* [S][M] f_Z as the path kernel wrote it */
+  double *rhs;          /* [S][M] after k_kp_rhs */
+  double *A1;           /* after k_kp_left:  W0 rhs_s */
+  double *B1;           /* after k_kp_right: (W0 rhs_s) W1^T */
+  double *A2;           /* after k_kp_left:  W0^T (..) */
+  double *V;            /* after k_kp_right: (..) W1, the weights */
+  double *tab;          /* [ntile][F][16] after k_kp_fill_v; the hook fills rows < M0 M1p with the sentinel before that launch */
+} zigp_kpathw_tap_latent;
+enum { ZIGP_KWF_NST = 0, ZIGP_KWF_NTILE,
+       ZIGP_KWF_MQ0,           /* [2] f, g; then Mq1 [2], M1p [2], R4 [2], F [2] */
+       ZIGP_KWF_MQ1 = ZIGP_KWF_MQ0 + 2, ZIGP_KWF_M1P = ZIGP_KWF_MQ1 + 2, ZIGP_KWF_R4 = ZIGP_KWF_M1P + 2, ZIGP_KWF_F = ZIGP_KWF_R4 + 2,
+       ZIGP_KWF_COUNT = ZIGP_KWF_F + 2 };
+typedef struct zigp_stage_kron_path_weights {
+  const zigp_kron_params* p;
+  int32_t lik;                  /* ZIGP_LIK_ONOFF (two latents) or a head (the f fields of everything) */
+  int32_t S;
+  double jitter;
+  const zigp_path_draw *draw_f, *draw_g;      /* draw_g: ZIGP_LIK_ONOFF only */
+  zigp_kpathw_tap_latent lat[2];
+  int64_t* facts;               /* out [ZIGP_KWF_COUNT], may be NULL */
+} zigp_stage_kron_path_weights;
+int zigp_test_kron_path_weights(zigp_ctx* ctx, const zigp_stage_kron_path_weights* a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -572,61 +572,22 @@ int kron_path_rows(zigp_ctx* c, const char* who, const zigp_kron_path_latent* la
 // product build: on the model fixtures (tools/kron_paths_parity.py, profiles/kron_paths_parity.log) a path is 7e-14 .. 3e-11 from the
 // restatement with the step and 3e-15 .. 2e-11 without it, under bounds of 2e-9 .. 1e-6 -- equally far inside.  Unlike the dense weights,
 // whose W^T W of one M x M factor of cond 4e8 needed the step, each W_p here belongs to one factor.  A build with
-// -DZIGP_KRON_PATH_REFINE (tools/build_variant.sh) compiles the step in, for that tool alone.
+// -DZIGP_KRON_PATH_REFINE (tools/build_variant.sh) compiles the step in, for that tool alone.  The claim is held by a test: the residual
+// rhs_s - K0 V_s K1 of the unrefined weights is within 4 res_np + 16 eps (|K0| |V_s| |K1| + |rhs_s|) per element on the model fixtures and the
+// 32 x 32 precipitation init (tests/test_gpu_path_weight_stages.py through zigp_test_kron_path_weights; measured <= 3.8 eps S_w).
 
 int kp_elementwise_grid(int64_t n) { return (int)ceil_div(n, (int64_t)256); }
 
-// zigp_kron_sample_paths[_device] (lik = ZIGP_LIK_ONOFF: out (3, S, N)) and zigp_kron_head_sample_paths[_device] (out (1 or 2, S, N))
-int kron_sample_paths(zigp_ctx* c, const char* who, const zigp_kron_params* p, int lik, const double* X, int64_t N, double jitter, double g_offset,
-                      double f_mu, const zigp_path_draw* draw_f, const zigp_path_draw* draw_g, int S, double* out, bool on_device) {
-  if (!c) return ZIGP_EARG;
-  const std::string w(who);
-  if (lik != ZIGP_LIK_ONOFF && lik != ZIGP_LIK_GAUSSIAN && lik != ZIGP_LIK_BERNOULLI)
-    return refuse(c, w, "lik must be ZIGP_LIK_GAUSSIAN or ZIGP_LIK_BERNOULLI");
-  if (p) ZIGP_TRY(kp_check_dims(c, w, p->D0, p->D1, S, N));      // names D0 + D1 before validate_kron speaks of the factor dimensions
-  ZIGP_TRY(validate_kron(c, p, lik));
-  const int nlat = lik == ZIGP_LIK_ONOFF ? 2 : 1, D0 = p->D0, D1 = p->D1, D = D0 + D1;
-  KronHostLatent hl[2];
-  kron_host_latents(p, nlat, hl);
-  kron_set_kinds(c, hl, nlat);      // zigp_set_kron_kernel: the factor stage and the path kernel evaluate the same k_q
-  const zigp_path_draw* dr[2] = {draw_f, draw_g};
-  const char* tag[2] = {"f", "g"};
-  for (int h = 0; h < nlat; ++h) {
-    ZIGP_TRY(kp_check_grid(c, w, hl[h].M[0], hl[h].M[1]));
-    ZIGP_TRY(path_check_draw(c, w, tag[h], dr[h], hl[h].M[0] * hl[h].M[1], D, S));
-    const size_t M = (size_t)hl[h].M[0] * hl[h].M[1];
-    ZIGP_TRY(path_check_table(c, w, h ? "u_gm" : "u_fm", hl[h].u, M));
-    ZIGP_TRY(path_check_table(c, w, h ? "u_gs_sqrt" : "u_fs_sqrt", hl[h].s, M));
-    for (int q = 0; q < 2; ++q) {
-      const int Dq = q ? D1 : D0;
-      ZIGP_TRY(path_check_table(c, w, q ? "Z1" : "Z0", hl[h].Z[q], (size_t)hl[h].M[q] * Dq));
-      ZIGP_TRY(path_check_table(c, w, q ? "ell1" : "ell0", hl[h].ell[q], Dq));
-      for (int d = 0; d < Dq; ++d)
-        if (!(hl[h].ell[q][d] > 0)) return refuse(c, w, "lengthscales must be positive");
-      if (!std::isfinite(hl[h].var[q])) return refuse(c, w, "variances must be finite");
-    }
-  }
-  if (!(jitter >= 0)) return refuse(c, w, "jitter must be >= 0");
-  if (!std::isfinite(g_offset)) return refuse(c, w, "g_offset is not finite");
-  if (!std::isfinite(f_mu)) return refuse(c, w, "f_mu is not finite");
-  if (N > 0 && (!X || !out)) return refuse(c, w, "Xnew or out is NULL");
-  if (N == 0) return ZIGP_OK;
-  ZIGP_HIP(c, hipSetDevice(c->device));
-  if (on_device) ZIGP_TRY(require_device_ptrs(c, {X, out}, (w + ": Xnew and out must be device memory of the context's GPU").c_str()));
-  if (!c->kron) { c->kron.reset(new (std::nothrow) KronState()); if (!c->kron) { c->err = "out of memory"; return ZIGP_EHIP; } }
-  KronState& ks = *c->kron;
-  ZIGP_TRY(begin_staged_call(c));
+struct KronPathTap : PathTap { const zigp_stage_kron_path_weights* s; int64_t facts[ZIGP_KWF_COUNT]; };
+// KW_SNAP(field, device pointer, count): latent h's tap of that name (zigp_test_kron_path_weights); a no-op without a sink
+#define KW_SNAP(field, dev, n) do { if (tap) ZIGP_TRY(tap->snap(c, tap->s->lat[h].field, (dev), (n))); } while (0)
 
-  // the call's own factor forward stage, as zigp_kron_predict's panel path runs it: K_p + jitter I, L_p, W_p = L_p^-1
-  ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
-  for (int h = 0; h < nlat; ++h) {
-    ZIGP_TRY(factor_forward(c, ks.lat[h].f[0], hl[h].M[0], D0, 0, hl[h].Z[0], hl[h].ell[0], hl[h].var[0], jitter, hl[h].kind[0]));
-    ZIGP_TRY(factor_forward(c, ks.lat[h].f[1], hl[h].M[1], D1, D0, hl[h].Z[1], hl[h].ell[1], hl[h].var[1], jitter, hl[h].kind[1]));
-  }
-  int* hinfo = nullptr;
-  ZIGP_TRY(request_info(c, &hinfo));
-
-  const int nst = path_tiles_per_pass(S), ntile = (int)round_up((S + 15) / 16, nst);
+// The weight stage of the Kronecker model calls behind the call's own factor forward stage: the device tables of the latents, f_Z by the
+// path kernel at the grid points, V_s = W0^T (W0 rhs_s W1^T) W1 and the grid points' part of the weight table.  pa comes back as the
+// argument record of the path launch at Xnew (X, N, out, ldo and shift are the caller's to set).
+int kron_path_weight_stage(zigp_ctx* c, KronState& ks, const KronHostLatent (&hl)[2], int nlat, const zigp_path_draw* const (&dr)[2], int D0, int D1,
+                           int S, int nst, KpArgs& pa, KronPathTap* tap) {
+  const int D = D0 + D1, ntile = (int)round_up((S + 15) / 16, nst);
   // device tables per latent: [omega | phase | table | E | U | Sq | grid rows] staged from the host, then [FZ | R | A | B | V] work matrices (S, M)
   size_t off[2][12], total = 0, staged = 0;
   KpDims dm[2];
@@ -650,7 +611,7 @@ int kron_sample_paths(zigp_ctx* c, const char* who, const zigp_kron_params* p, i
   double* base = c->path_tab.p;
   ZIGP_PINNED(c, img, staged);
   memset(img, 0, sizeof(double) * staged);
-  KpArgs pa{};
+  pa = KpArgs{};
   pa.ntile = ntile;
   for (int h = 0; h < nlat; ++h) {
     const int R = dr[h]->R, M0 = hl[h].M[0], M1 = hl[h].M[1];
@@ -685,6 +646,20 @@ int kron_sample_paths(zigp_ctx* c, const char* who, const zigp_kron_params* p, i
     a.kinds = hl[h].kind[0] + 4 * hl[h].kind[1];
   }
   ZIGP_HIP(c, hipMemcpyAsync(base, img, sizeof(double) * staged, hipMemcpyHostToDevice, c->stream));
+  if (tap) {      // the hook: every work matrix (S, M) is written completely by its launch
+    tap->facts[ZIGP_KWF_NST] = nst; tap->facts[ZIGP_KWF_NTILE] = ntile;
+    ZIGP_TRY(tap->sentinel(c, base + staged, total - staged));
+    for (int h = 0; h < nlat; ++h) {
+      const size_t M = (size_t)hl[h].M[0] * hl[h].M[1];
+      tap->facts[ZIGP_KWF_M1P + h] = dm[h].M1p; tap->facts[ZIGP_KWF_R4 + h] = dm[h].R4; tap->facts[ZIGP_KWF_F + h] = dm[h].F;
+      for (int q = 0; q < 2; ++q) {
+        const KronFactor& f = ks.lat[h].f[q];
+        tap->facts[(q ? ZIGP_KWF_MQ1 : ZIGP_KWF_MQ0) + h] = f.Mq;
+        KW_SNAP(K[q], f.K.p, (size_t)f.Mq * f.Mq); KW_SNAP(W[q], f.W.p, (size_t)f.Mq * f.Mq);
+      }
+      KW_SNAP(E, base + off[h][3], M * S); KW_SNAP(U, base + off[h][4], M); KW_SNAP(Sq, base + off[h][5], M);
+    }
+  }
 
   // f_Z: the cosines alone at the grid points (no grid group runs), written as (S, M)
   KpArgs pz = pa;
@@ -703,14 +678,20 @@ int kron_sample_paths(zigp_ctx* c, const char* who, const zigp_kron_params* p, i
     const int64_t n = (int64_t)M * S;
     const dim3 grid((unsigned)kp_elementwise_grid(n)), block(256);
     // dst = K0^-1 src K1^-1 through the explicit W_p: (W0^T (W0 src W1^T)) W1; A and B are the work matrices
-    auto solve = [&](const double* src, double* dst) {
+    auto solve = [&](const double* src, double* dst, bool taps) -> int {
       hipLaunchKernelGGL(k_kp_left, grid, block, 0, c->stream, f0.W.p, (int64_t)f0.Mq, 0, src, M0, M1, S, A);       // W0 src
+      if (taps) KW_SNAP(A1, A, (size_t)n);
       hipLaunchKernelGGL(k_kp_right, grid, block, 0, c->stream, A, f1.W.p, (int64_t)f1.Mq, 1, M0, M1, S, B);        // .. W1^T
+      if (taps) KW_SNAP(B1, B, (size_t)n);
       hipLaunchKernelGGL(k_kp_left, grid, block, 0, c->stream, f0.W.p, (int64_t)f0.Mq, 1, B, M0, M1, S, A);         // W0^T ..
+      if (taps) KW_SNAP(A2, A, (size_t)n);
       hipLaunchKernelGGL(k_kp_right, grid, block, 0, c->stream, A, f1.W.p, (int64_t)f1.Mq, 0, M0, M1, S, dst);      // .. W1
+      return 0;
     };
+    KW_SNAP(FZ, FZ, (size_t)n);
     hipLaunchKernelGGL(k_kp_rhs, grid, block, 0, c->stream, U, Sq, E, FZ, M, S, Rh);
-    solve(Rh, V);
+    KW_SNAP(rhs, Rh, (size_t)n);
+    ZIGP_TRY(solve(Rh, V, true));
 #ifdef ZIGP_KRON_PATH_REFINE
     {
       // What reaches a path is the residual of V (zigp_paths.hip, the dense refinement): V += K0^-1 (rhs - K0 V K1) K1^-1.  K_p is
@@ -718,14 +699,80 @@ int kron_sample_paths(zigp_ctx* c, const char* who, const zigp_kron_params* p, i
       hipLaunchKernelGGL(k_kp_left, grid, block, 0, c->stream, f0.K.p, (int64_t)f0.Mq, 0, V, M0, M1, S, A);         // K0 V
       hipLaunchKernelGGL(k_kp_right, grid, block, 0, c->stream, A, f1.K.p, (int64_t)f1.Mq, 0, M0, M1, S, B);        // .. K1
       hipLaunchKernelGGL(k_path_axpy, grid, block, 0, c->stream, Rh, -1.0, B, n, FZ);                                // residual
-      solve(FZ, FZ);
+      ZIGP_TRY(solve(FZ, FZ, false));
       hipLaunchKernelGGL(k_path_axpy, grid, block, 0, c->stream, V, 1.0, FZ, n, V);
     }
 #endif
+    KW_SNAP(V, V, (size_t)n);
+    if (tap)      // k_kp_fill_v writes every grid row of the table
+      for (int tile = 0; tile < ntile; ++tile) ZIGP_TRY(tap->sentinel(c, base + off[h][2] + (size_t)tile * dm[h].F * 16, (size_t)dm[h].coff * 16));
     const int64_t nfill = (int64_t)ntile * dm[h].coff * 16;
     hipLaunchKernelGGL(k_kp_fill_v, dim3((unsigned)kp_elementwise_grid(nfill)), block, 0, c->stream, V, M0, M1, dm[h].M1p, S, dm[h].F, ntile,
                        base + off[h][2]);
     ZIGP_HIP(c, hipGetLastError());
+    KW_SNAP(tab, base + off[h][2], (size_t)ntile * dm[h].F * 16);
+  }
+  return 0;
+}
+
+// zigp_kron_sample_paths[_device] (lik = ZIGP_LIK_ONOFF: out (3, S, N)) and zigp_kron_head_sample_paths[_device] (out (1 or 2, S, N))
+int kron_sample_paths(zigp_ctx* c, const char* who, const zigp_kron_params* p, int lik, const double* X, int64_t N, double jitter, double g_offset,
+                      double f_mu, const zigp_path_draw* draw_f, const zigp_path_draw* draw_g, int S, double* out, bool on_device,
+                      KronPathTap* tap = nullptr) {      // tap: zigp_test_kron_path_weights -- the weight stage alone, no rows
+  if (!c) return ZIGP_EARG;
+  const std::string w(who);
+  if (lik != ZIGP_LIK_ONOFF && lik != ZIGP_LIK_GAUSSIAN && lik != ZIGP_LIK_BERNOULLI)
+    return refuse(c, w, "lik must be ZIGP_LIK_GAUSSIAN or ZIGP_LIK_BERNOULLI");
+  if (p) ZIGP_TRY(kp_check_dims(c, w, p->D0, p->D1, S, N));      // names D0 + D1 before validate_kron speaks of the factor dimensions
+  ZIGP_TRY(validate_kron(c, p, lik));
+  const int nlat = lik == ZIGP_LIK_ONOFF ? 2 : 1, D0 = p->D0, D1 = p->D1, D = D0 + D1;
+  KronHostLatent hl[2];
+  kron_host_latents(p, nlat, hl);
+  kron_set_kinds(c, hl, nlat);      // zigp_set_kron_kernel: the factor stage and the path kernel evaluate the same k_q
+  const zigp_path_draw* dr[2] = {draw_f, draw_g};
+  const char* tag[2] = {"f", "g"};
+  for (int h = 0; h < nlat; ++h) {
+    ZIGP_TRY(kp_check_grid(c, w, hl[h].M[0], hl[h].M[1]));
+    ZIGP_TRY(path_check_draw(c, w, tag[h], dr[h], hl[h].M[0] * hl[h].M[1], D, S));
+    const size_t M = (size_t)hl[h].M[0] * hl[h].M[1];
+    ZIGP_TRY(path_check_table(c, w, h ? "u_gm" : "u_fm", hl[h].u, M));
+    ZIGP_TRY(path_check_table(c, w, h ? "u_gs_sqrt" : "u_fs_sqrt", hl[h].s, M));
+    for (int q = 0; q < 2; ++q) {
+      const int Dq = q ? D1 : D0;
+      ZIGP_TRY(path_check_table(c, w, q ? "Z1" : "Z0", hl[h].Z[q], (size_t)hl[h].M[q] * Dq));
+      ZIGP_TRY(path_check_table(c, w, q ? "ell1" : "ell0", hl[h].ell[q], Dq));
+      for (int d = 0; d < Dq; ++d)
+        if (!(hl[h].ell[q][d] > 0)) return refuse(c, w, "lengthscales must be positive");
+      if (!std::isfinite(hl[h].var[q])) return refuse(c, w, "variances must be finite");
+    }
+  }
+  if (!(jitter >= 0)) return refuse(c, w, "jitter must be >= 0");
+  if (!std::isfinite(g_offset)) return refuse(c, w, "g_offset is not finite");
+  if (!std::isfinite(f_mu)) return refuse(c, w, "f_mu is not finite");
+  if (!tap && N > 0 && (!X || !out)) return refuse(c, w, "Xnew or out is NULL");
+  if (!tap && N == 0) return ZIGP_OK;
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  if (on_device) ZIGP_TRY(require_device_ptrs(c, {X, out}, (w + ": Xnew and out must be device memory of the context's GPU").c_str()));
+  if (!c->kron) { c->kron.reset(new (std::nothrow) KronState()); if (!c->kron) { c->err = "out of memory"; return ZIGP_EHIP; } }
+  KronState& ks = *c->kron;
+  ZIGP_TRY(begin_staged_call(c));
+
+  // the call's own factor forward stage, as zigp_kron_predict's panel path runs it: K_p + jitter I, L_p, W_p = L_p^-1
+  ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
+  for (int h = 0; h < nlat; ++h) {
+    ZIGP_TRY(factor_forward(c, ks.lat[h].f[0], hl[h].M[0], D0, 0, hl[h].Z[0], hl[h].ell[0], hl[h].var[0], jitter, hl[h].kind[0]));
+    ZIGP_TRY(factor_forward(c, ks.lat[h].f[1], hl[h].M[1], D1, D0, hl[h].Z[1], hl[h].ell[1], hl[h].var[1], jitter, hl[h].kind[1]));
+  }
+  int* hinfo = nullptr;
+  ZIGP_TRY(request_info(c, &hinfo));
+
+  const int nst = path_tiles_per_pass(S);
+  KpArgs pa{};
+  ZIGP_TRY(kron_path_weight_stage(c, ks, hl, nlat, dr, D0, D1, S, nst, pa, tap));
+  if (tap) {
+    ZIGP_TRY(finish_copies(c, {}));
+    ZIGP_TRY(tap->flush(c));
+    return info_result(c, hinfo, kron_fac_any);
   }
 
   // the paths at Xnew: f_mu on f, g_offset on g
@@ -784,6 +831,20 @@ int zigp_kron_head_sample_paths_device(zigp_ctx* c, const zigp_kron_params* p, i
                                        double f_mu, const zigp_path_draw* draw_f, int32_t S, double* d_out) {
   if (c && lik == ZIGP_LIK_ONOFF) return refuse(c, "zigp_kron_head_sample_paths_device", "use zigp_kron_sample_paths_device for the OnOff likelihood");
   return kron_sample_paths(c, "zigp_kron_head_sample_paths_device", p, lik, dXnew, N, jitter, 0.0, f_mu, draw_f, nullptr, S, d_out, true);
+}
+
+// The weight stage of zigp_kron_sample_paths / zigp_kron_head_sample_paths through kron_sample_paths itself -- its checks, its factor
+// forward stage, kron_path_weight_stage -- with the device buffers snapshot (KronPathTap); the paths at Xnew are not run.
+int zigp_test_kron_path_weights(zigp_ctx* c, const zigp_stage_kron_path_weights* s) {
+  if (!c) return ZIGP_EARG;
+  if (!s) return refuse(c, "zigp_test_kron_path_weights", "the record is NULL");
+  KronPathTap tap;
+  tap.s = s;
+  memset(tap.facts, 0, sizeof(tap.facts));
+  ZIGP_TRY(kron_sample_paths(c, "zigp_test_kron_path_weights", s->p, s->lik, nullptr, 0, s->jitter, 0.0, 0.0, s->draw_f,
+                             s->lik == ZIGP_LIK_ONOFF ? s->draw_g : nullptr, s->S, nullptr, false, &tap));
+  if (s->facts) memcpy(s->facts, tap.facts, sizeof(tap.facts));
+  return ZIGP_OK;
 }
 
 }  // extern "C"

@@ -372,38 +372,40 @@ int path_gemm(zigp_ctx* c, bool at, bool bt, const double* A, const double* B, d
   return run_gemm<LAY_MNCONTIG, LAY_KCONTIG, false>(c, tl, g, EpiStore());
 }
 
-// zigp_sample_paths and zigp_sample_paths_device
-int sample_paths(zigp_ctx* c, const char* who, const zigp_params* p, const double* X, int64_t N, double jitter, double g_offset,
-                 const zigp_path_draw* draw_f, const zigp_path_draw* draw_g, int S, double* out3, bool on_device) {
-  if (!c) return ZIGP_EARG;
-  const std::string w(who);
-  if (p && p->D > MAXD && p->D <= ZIGP_MAX_D) ZIGP_TRY(path_check_dims(c, w, p->D, 1, 0));     // names D before validate_params speaks of the wide kernels
-  ZIGP_TRY(validate_params(c, p));
-  const int D = p->D;
-  ZIGP_TRY(path_check_dims(c, w, D, S, N));
-  ZIGP_TRY(path_check_draw(c, w, "f", draw_f, p->Mf, D, S));
-  ZIGP_TRY(path_check_draw(c, w, "g", draw_g, p->Mg, D, S));
-  if (!std::isfinite(g_offset)) return refuse(c, w, "g_offset is not finite");
-  if (N > 0 && (!X || !out3)) return refuse(c, w, "Xnew or out3 is NULL");
-  if (N == 0) return ZIGP_OK;
-  ZIGP_HIP(c, hipSetDevice(c->device));
-  if (on_device) ZIGP_TRY(require_device_ptrs(c, {X, out3}, (w + ": Xnew and out3 must be device memory of the context's GPU").c_str()));
+// The tap sink of the weight-stage hooks (zigp_test_path_weights, zigp_test_kron_path_weights; include/zigp_diag.h).  A tap is a
+// device-to-device copy enqueued on the call's stream right behind the launch that produces the value, into a buffer of its own; flush()
+// downloads them once the stream is idle.  Host code only: a product call passes no sink and enqueues exactly what it did before.
+struct PathTap {
+  struct Snap { double* host; DevBuf dev; size_t n; };
+  std::vector<Snap> snaps;
+  int snap(zigp_ctx* c, double* host, const double* dev, size_t n) {
+    if (!host || n == 0) return 0;
+    snaps.emplace_back();
+    Snap& q = snaps.back();
+    q.host = host; q.n = n;
+    ZIGP_ENSURE(c, q.dev, n);
+    ZIGP_HIP(c, hipMemcpyAsync(q.dev.p, dev, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+  }
+  int sentinel(zigp_ctx* c, double* dev, size_t n) {
+    ZIGP_HIP(c, hipMemsetAsync(dev, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * n, c->stream));
+    return 0;
+  }
+  int flush(zigp_ctx* c) {      // the stream is idle
+    for (Snap& q : snaps) ZIGP_HIP(c, hipMemcpy(q.host, q.dev.p, sizeof(double) * q.n, hipMemcpyDeviceToHost));
+    return 0;
+  }
+};
+struct DensePathTap : PathTap { const zigp_stage_path_weights* s; int64_t facts[ZIGP_PWF_COUNT]; };
+// PW_SNAP(field, device pointer, count): latent h's tap of that name; a no-op without a sink
+#define PW_SNAP(field, dev, n) do { if (tap) ZIGP_TRY(tap->snap(c, tap->s->lat[h].field, (dev), (n))); } while (0)
 
-  // the call's own M x M forward stage: Kuu, L, W = L^-1 (and the masked L_q of a full-covariance call)
-  const Param par = param_of(c);
-  HostLatent hl[2] = {{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f, c->kern[0]},
-                      {p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g, c->kern[1]}};
-  const zigp_path_draw* dr[2] = {draw_f, draw_g};
-  ZIGP_TRY(begin_staged_call(c));
-  ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
-  ZIGP_TRY(latents_upload(c, hl, D, par));
-  ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
-  ZIGP_TRY(latents_forward(c, hl, D, jitter, par, false, false, nullptr, nullptr));
-  ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
-  int* hinfo = nullptr;
-  ZIGP_TRY(request_info(c, &hinfo));
-
-  const int nst = path_tiles_per_pass(S), ntile = (int)round_up((S + 15) / 16, nst);
+// The weight stage of zigp_sample_paths behind the call's own M x M forward stage: the device tables of both latents, f_Z by the path
+// kernel on the rows Z, V = W^T t on the GEMM core and the kernel features' part of the weight table.  pa comes back as the argument record
+// of the path launch at Xnew (X, N, out, ldo, the mean part are the caller's to set).
+int path_weight_stage(zigp_ctx* c, Param par, const HostLatent (&hl)[2], const zigp_path_draw* const (&dr)[2], int D, int S, int nst, PathArgs& pa,
+                      DensePathTap* tap) {
+  const int ntile = (int)round_up((S + 15) / 16, nst);
   const int64_t Sp = round_up(S, BN);
   // device tables per latent: [omega | phase | table] staged from the host, then [E | FT | A | B | V] work matrices
   size_t off[2][8], total = 0, staged = 0;
@@ -428,7 +430,7 @@ int sample_paths(zigp_ctx* c, const char* who, const zigp_params* p, const doubl
   double* base = c->path_tab.p;
   ZIGP_PINNED(c, img, staged);
   memset(img, 0, sizeof(double) * staged);
-  PathArgs pa{};
+  pa = PathArgs{};
   pa.ntile = ntile;
   for (int h = 0; h < 2; ++h) {
     const int R = dr[h]->R, M = hl[h].M;
@@ -453,6 +455,20 @@ int sample_paths(zigp_ctx* c, const char* who, const zigp_params* p, const doubl
   }
   ZIGP_HIP(c, hipMemcpyAsync(base, img, sizeof(double) * staged, hipMemcpyHostToDevice, c->stream));
   ZIGP_HIP(c, hipMemsetAsync(base + staged, 0, sizeof(double) * (total - staged), c->stream));
+  if (tap) {      // the hook: A, B and V are written completely by their launches (FT is not: the path kernel writes (S, M) of it)
+    tap->facts[ZIGP_PWF_MODE] = par == Param::Diag ? 0 : is_full(par) ? 2 : 1;
+    tap->facts[ZIGP_PWF_SP] = Sp; tap->facts[ZIGP_PWF_NST] = nst; tap->facts[ZIGP_PWF_NTILE] = ntile;
+    for (int h = 0; h < 2; ++h) {
+      const size_t Mp = c->lat[h].Mp;
+      tap->facts[ZIGP_PWF_MP + h] = (int64_t)Mp; tap->facts[ZIGP_PWF_M4 + h] = dm[h].M4; tap->facts[ZIGP_PWF_R4 + h] = dm[h].R4;
+      tap->facts[ZIGP_PWF_F + h] = dm[h].F;
+      ZIGP_TRY(tap->sentinel(c, base + off[h][5], 3 * Mp * Sp));
+      PW_SNAP(Kuu, c->lat[h].Kuu.p, Mp * Mp); PW_SNAP(W, c->lat[h].W.p, Mp * Mp);
+      if (is_full(par)) PW_SNAP(Lq, c->lat[h].Lq.p, Mp * Mp);
+      PW_SNAP(u, c->lat[h].u.p, Mp); PW_SNAP(s, c->lat[h].s.p, Mp);
+      PW_SNAP(E, base + off[h][3], Mp * Sp);
+    }
+  }
 
   // f_Z: the cosine features alone on the rows Z (V = 0: no kernel group runs), written as (S, M) with row stride Mp
   PathArgs pz = pa;
@@ -466,36 +482,98 @@ int sample_paths(zigp_ctx* c, const char* who, const zigp_params* p, const doubl
   for (int h = 0; h < 2; ++h) {
     Latent& lt = c->lat[h];
     const int Mp = lt.Mp, M = hl[h].M;
+    const size_t ms = (size_t)Mp * Sp;
     double *E = base + off[h][3], *FT = base + off[h][4], *A = base + off[h][5], *B = base + off[h][6], *V = base + off[h][7];
     const dim3 grid((unsigned)ceil_div((int64_t)Mp * Sp, 256));
+    PW_SNAP(FT, FT, ms);
     if (par == Param::Diag) {
       hipLaunchKernelGGL(k_path_rhs, grid, dim3(256), 0, c->stream, 0, lt.u.p, lt.s.p, E, FT, nullptr, nullptr, M, S, (int64_t)Mp, Sp, A);
       ZIGP_HIP(c, hipGetLastError());
+      PW_SNAP(rhs, A, ms);
       ZIGP_TRY(path_gemm(c, false, false, lt.W.p, A, B, Mp, (int)Sp));      // t = W (u + s o eps - f_Z)
+      PW_SNAP(t, B, ms);
       ZIGP_TRY(path_gemm(c, true, false, lt.W.p, B, V, Mp, (int)Sp));       // V = W^T t
+      PW_SNAP(V0, V, ms);
       // One step of iterative refinement against Kuu itself.  The right-hand side holds the white noise s o eps, so V is of the size of
       // 1 / jitter, and a path is k(x, Z) V = (k(x, Z) Kuu^-1)(rhs - residual): what reaches the path is the RESIDUAL of V.  Through the
       // explicit W it is ~cond(L) eps |Kuu| |V| (measured 9.6e-7 of a path at cond(Kuu) 4e8, where the restatement's triangular solves
-      // are at 1.4e-8); after V += W^T W (rhs - Kuu V) it is that of a backward-stable solve.
+      // are at 1.4e-8); after V += W^T W (rhs - Kuu V) it is that of a backward-stable solve.  The step is held by the solve tier of
+      // tests/test_gpu_path_weight_stages.py: max |rhs - Kuu V| <= 8 x SciPy's Cholesky solve (65 x before the step, 0.98 x after it there).
       ZIGP_TRY(path_gemm(c, false, false, lt.Kuu.p, V, FT, Mp, (int)Sp));   // Kuu V  (f_Z has no reader left: its buffer as (Mp, Sp))
+      PW_SNAP(KV, FT, ms);
       hipLaunchKernelGGL(k_path_axpy, grid, dim3(256), 0, c->stream, A, -1.0, FT, (int64_t)Mp * Sp, A);       // residual
       ZIGP_HIP(c, hipGetLastError());
+      PW_SNAP(res, A, ms);
       ZIGP_TRY(path_gemm(c, false, false, lt.W.p, A, B, Mp, (int)Sp));
+      PW_SNAP(t2, B, ms);
       ZIGP_TRY(path_gemm(c, true, false, lt.W.p, B, FT, Mp, (int)Sp));      // the correction
+      PW_SNAP(cor, FT, ms);
       hipLaunchKernelGGL(k_path_axpy, grid, dim3(256), 0, c->stream, V, 1.0, FT, (int64_t)Mp * Sp, V);
       ZIGP_HIP(c, hipGetLastError());
     } else {
       ZIGP_TRY(path_gemm(c, false, true, lt.W.p, FT, A, Mp, (int)Sp));      // G = W f_Z
-      if (is_full(par)) ZIGP_TRY(path_gemm(c, false, false, lt.Lq.p, E, B, Mp, (int)Sp));   // H = tril(L_q) eps
+      PW_SNAP(G, A, ms);
+      if (is_full(par)) {
+        ZIGP_TRY(path_gemm(c, false, false, lt.Lq.p, E, B, Mp, (int)Sp));   // H = tril(L_q) eps
+        PW_SNAP(H, B, ms);
+      }
       hipLaunchKernelGGL(k_path_rhs, grid, dim3(256), 0, c->stream, is_full(par) ? 2 : 1, lt.u.p, lt.s.p, E, nullptr, A, B, M, S, (int64_t)Mp, Sp, FT);
       ZIGP_HIP(c, hipGetLastError());
+      PW_SNAP(rhs, FT, ms);
       ZIGP_TRY(path_gemm(c, true, false, lt.W.p, FT, V, Mp, (int)Sp));      // V = W^T t  (t overwrote f_Z, which has no reader left)
     }
+    PW_SNAP(V, V, ms);
+    if (tap)      // k_path_fill_v writes every kernel row of the table
+      for (int tile = 0; tile < ntile; ++tile) ZIGP_TRY(tap->sentinel(c, base + off[h][2] + (size_t)tile * dm[h].F * 16, (size_t)dm[h].M4 * 16));
     const int64_t nfill = (int64_t)ntile * dm[h].M4 * 16;
     hipLaunchKernelGGL(k_path_fill_v, dim3((unsigned)ceil_div(nfill, 256)), dim3(256), 0, c->stream, V, M, S, dm[h].M4, dm[h].F, ntile, Sp,
                        base + off[h][2]);
     ZIGP_HIP(c, hipGetLastError());
+    PW_SNAP(tab, base + off[h][2], (size_t)ntile * dm[h].F * 16);
   }
+  return 0;
+}
+
+// The call's own M x M forward stage: Kuu, L, W = L^-1 (and the masked L_q of a full-covariance call); *hinfo holds the factorisation's
+// status after the call's synchronisation
+int paths_forward(zigp_ctx* c, const HostLatent (&hl)[2], int D, double jitter, Param par, int** hinfo) {
+  ZIGP_TRY(begin_staged_call(c));
+  ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
+  ZIGP_TRY(latents_upload(c, hl, D, par));
+  ZIGP_TRY(fork_side(c, c->ev_fork, c->stream2));
+  ZIGP_TRY(latents_forward(c, hl, D, jitter, par, false, false, nullptr, nullptr));
+  ZIGP_TRY(join_side(c, c->ev_join, c->stream2));
+  return request_info(c, hinfo);
+}
+
+// zigp_sample_paths and zigp_sample_paths_device
+int sample_paths(zigp_ctx* c, const char* who, const zigp_params* p, const double* X, int64_t N, double jitter, double g_offset,
+                 const zigp_path_draw* draw_f, const zigp_path_draw* draw_g, int S, double* out3, bool on_device) {
+  if (!c) return ZIGP_EARG;
+  const std::string w(who);
+  if (p && p->D > MAXD && p->D <= ZIGP_MAX_D) ZIGP_TRY(path_check_dims(c, w, p->D, 1, 0));     // names D before validate_params speaks of the wide kernels
+  ZIGP_TRY(validate_params(c, p));
+  const int D = p->D;
+  ZIGP_TRY(path_check_dims(c, w, D, S, N));
+  ZIGP_TRY(path_check_draw(c, w, "f", draw_f, p->Mf, D, S));
+  ZIGP_TRY(path_check_draw(c, w, "g", draw_g, p->Mg, D, S));
+  if (!std::isfinite(g_offset)) return refuse(c, w, "g_offset is not finite");
+  if (N > 0 && (!X || !out3)) return refuse(c, w, "Xnew or out3 is NULL");
+  if (N == 0) return ZIGP_OK;
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  if (on_device) ZIGP_TRY(require_device_ptrs(c, {X, out3}, (w + ": Xnew and out3 must be device memory of the context's GPU").c_str()));
+
+  // the call's own M x M forward stage: Kuu, L, W = L^-1 (and the masked L_q of a full-covariance call)
+  const Param par = param_of(c);
+  HostLatent hl[2] = {{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f, c->kern[0]},
+                      {p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g, c->kern[1]}};
+  const zigp_path_draw* dr[2] = {draw_f, draw_g};
+  int* hinfo = nullptr;
+  ZIGP_TRY(paths_forward(c, hl, D, jitter, par, &hinfo));
+
+  const int nst = path_tiles_per_pass(S);
+  PathArgs pa{};
+  ZIGP_TRY(path_weight_stage(c, par, hl, dr, D, S, nst, pa, nullptr));
 
   // the paths at Xnew: the context's mean function on f, g_offset on g
   const double* dX = nullptr;
@@ -540,6 +618,38 @@ int zigp_sample_paths(zigp_ctx* c, const zigp_params* p, const double* Xnew, int
 int zigp_sample_paths_device(zigp_ctx* c, const zigp_params* p, const double* dXnew, int64_t N, double jitter, double g_offset,
                              const zigp_path_draw* draw_f, const zigp_path_draw* draw_g, int32_t S, double* d_out3) {
   return sample_paths(c, "zigp_sample_paths_device", p, dXnew, N, jitter, g_offset, draw_f, draw_g, S, d_out3, true);
+}
+
+// The weight stage of zigp_sample_paths through path_weight_stage itself, behind the call's own forward stage, with its device buffers
+// snapshot (DensePathTap); the paths at Xnew are not run.  The checks are those of sample_paths that do not concern rows.
+int zigp_test_path_weights(zigp_ctx* c, const zigp_stage_path_weights* s) {
+  if (!c) return ZIGP_EARG;
+  const std::string w("zigp_test_path_weights");
+  if (!s) return refuse(c, w, "the record is NULL");
+  const zigp_params* p = s->p;
+  if (p && p->D > MAXD && p->D <= ZIGP_MAX_D) ZIGP_TRY(path_check_dims(c, w, p->D, 1, 0));
+  ZIGP_TRY(validate_params(c, p));
+  const int D = p->D, S = s->S;
+  ZIGP_TRY(path_check_dims(c, w, D, S, 0));
+  ZIGP_TRY(path_check_draw(c, w, "f", s->draw_f, p->Mf, D, S));
+  ZIGP_TRY(path_check_draw(c, w, "g", s->draw_g, p->Mg, D, S));
+  if (!(s->jitter >= 0)) return refuse(c, w, "jitter must be >= 0");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  const Param par = param_of(c);
+  HostLatent hl[2] = {{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f, c->kern[0]},
+                      {p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g, c->kern[1]}};
+  const zigp_path_draw* dr[2] = {s->draw_f, s->draw_g};
+  int* hinfo = nullptr;
+  ZIGP_TRY(paths_forward(c, hl, D, s->jitter, par, &hinfo));
+  DensePathTap tap;
+  tap.s = s;
+  memset(tap.facts, 0, sizeof(tap.facts));
+  PathArgs pa{};
+  ZIGP_TRY(path_weight_stage(c, par, hl, dr, D, S, path_tiles_per_pass(S), pa, &tap));
+  ZIGP_TRY(finish_copies(c, {}));
+  ZIGP_TRY(tap.flush(c));
+  if (s->facts) memcpy(s->facts, tap.facts, sizeof(tap.facts));
+  return info_result(c, hinfo, "Kuu");
 }
 
 }  // extern "C"

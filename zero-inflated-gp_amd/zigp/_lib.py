@@ -237,6 +237,35 @@ class zigp_stage_dense_fit_update(C.Structure):   # include/zigp_diag.h
                 ('snap_Lraw', dp * 2), ('hist', dp), ('fail', dp), ('elbo_data', dp), ('kl', dp), ('steps_applied', dp), ('facts', dp)]
 
 
+PWT_FIELDS = ('Kuu', 'W', 'Lq', 'u', 's', 'E', 'FT', 'rhs', 't', 'V0', 'KV', 'res', 't2', 'cor', 'G', 'H', 'V', 'tab')
+PWF_FACTS = (('mode', 1), ('Sp', 1), ('nst', 1), ('ntile', 1), ('Mp', 2), ('M4', 2), ('R4', 2), ('F', 2))   # include/zigp_diag.h ZIGP_PWF_*
+PWF_COUNT = sum(n for _, n in PWF_FACTS)
+
+
+class zigp_pathw_tap_latent(C.Structure):   # include/zigp_diag.h
+    _fields_ = [(k, dp) for k in PWT_FIELDS]
+
+
+class zigp_stage_path_weights(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('p', C.POINTER(zigp_params)), ('jitter', C.c_double), ('draw_f', C.POINTER(zigp_path_draw)), ('draw_g', C.POINTER(zigp_path_draw)),
+                ('S', C.c_int32), ('reserved', C.c_int32), ('lat', zigp_pathw_tap_latent * 2), ('facts', C.POINTER(C.c_int64))]
+
+
+KWT_FIELDS = ('E', 'U', 'Sq', 'FZ', 'rhs', 'A1', 'B1', 'A2', 'V', 'tab')
+KWF_FACTS = (('nst', 1), ('ntile', 1), ('Mq0', 2), ('Mq1', 2), ('M1p', 2), ('R4', 2), ('F', 2))   # include/zigp_diag.h ZIGP_KWF_*
+KWF_COUNT = sum(n for _, n in KWF_FACTS)
+
+
+class zigp_kpathw_tap_latent(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('K', dp * 2), ('W', dp * 2)] + [(k, dp) for k in KWT_FIELDS]
+
+
+class zigp_stage_kron_path_weights(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('p', C.POINTER(zigp_kron_params)), ('lik', C.c_int32), ('S', C.c_int32), ('jitter', C.c_double),
+                ('draw_f', C.POINTER(zigp_path_draw)), ('draw_g', C.POINTER(zigp_path_draw)), ('lat', zigp_kpathw_tap_latent * 2),
+                ('facts', C.POINTER(C.c_int64))]
+
+
 def unpack_facts(layout, arr):
     """facts array -> dict (an entry with more than one value: a list)"""
     out, o = {}, 0
@@ -366,6 +395,8 @@ SIGNATURES = {
     'zigp_test_kron_panel_step': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_kron_panels)]),
     'zigp_test_kron_fit_update': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_kron_fit_update)]),
     'zigp_test_dense_fit_update': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_dense_fit_update)]),
+    'zigp_test_path_weights': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_path_weights)]),
+    'zigp_test_kron_path_weights': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_kron_path_weights)]),
     'zigp_test_kron_kbuild': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, C.c_double, dp]),
     'zigp_test_kron_colsum': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, dp, dp, dp, dp, dp, dp, dp, dp]),
     'zigp_test_kron_da': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, dp, dp, dp, dp, dp, dp, dp]),

@@ -2043,6 +2043,92 @@ class DenseEngine:
                                        % (planes_of, fd['lat'][h]['S_' + planes_of], d['planes'].shape[0]))
         return dict(elbo_data=float(sc[0]), kl=float(sc[1]), grads=out, facts=fd, lat=lat)
 
+    def test_path_weights(self, p, draws, n_samples, jitter=1e-6):
+        """The weight stage of sample_paths -- a draw of q(u) into the weight table the path kernel reads -- through the product's own
+        host function, with the device buffers snapshot behind every launch (zigp_test_path_weights, include/zigp_diag.h, where every
+        tap is written down).  p and draws as sample_paths reads them.  Returns dict(facts {mode, Sp, nst, ntile, Mp, M4, R4, F}, lat
+        [f, g: dict(Kuu, W (Mp, Mp), u, s (Mp), E, rhs, V (Mp, Sp), FT (Sp, Mp), tab (ntile, F, 16); unwhitened: t, V0, KV, res, t2, cor;
+        whitened: G; full covariance: Lq, H)]).  A work matrix element no launch wrote holds _lib.STAGE_SENTINEL."""
+        pk = _Packed(p)
+        S = int(n_samples)
+        draws, recs, keep = self._path_draws(pk, pk.kinds, S, 0, None, draws)
+        self._prepare(p, pk)
+        mode = 0 if not p.get('whiten', False) else 1 if p.get('q_diag', True) else 2
+        Sp, nt = -(-S // 128) * 128, -(-S // 16)
+        nst = 4 if nt >= 4 else 2 if nt >= 2 else 1
+        ntile = -(-nt // nst) * nst
+        s = _lib.zigp_stage_path_weights()
+        s.p, s.jitter, s.S = C.pointer(pk.struct), float(jitter), S
+        s.draw_f, s.draw_g = C.pointer(recs[0]), C.pointer(recs[1])
+        lat = []
+        for h, (M, tag) in enumerate(((pk.Mf, 'f'), (pk.Mg, 'g'))):
+            Mp, R = -(-M // 128) * 128, int(draws[tag]['R'])
+            F = -(-M // 4) * 4 + -(-R // 4) * 4
+            names = ['Kuu', 'W', 'u', 's', 'E', 'FT', 'rhs', 'V', 'tab'] + (['t', 'V0', 'KV', 'res', 't2', 'cor'] if mode == 0 else ['G']) + (
+                ['Lq', 'H'] if mode == 2 else [])
+            d = {}
+            for k in names:
+                shape = (Mp, Mp) if k in ('Kuu', 'W', 'Lq') else (Mp,) if k in ('u', 's') else (Sp, Mp) if k == 'FT' else (ntile, F, 16) if k == 'tab' else (Mp, Sp)
+                d[k] = np.full(shape, np.nan)
+                setattr(s.lat[h], k, ptr(d[k]))
+            lat.append(d)
+        facts = (C.c_int64 * _lib.PWF_COUNT)()
+        s.facts = C.cast(facts, C.POINTER(C.c_int64))
+        _check(self.lib, self.ctx, self.lib.zigp_test_path_weights(self.ctx, C.byref(s)))
+        fd = _lib.unpack_facts(_lib.PWF_FACTS, facts)
+        want = dict(mode=mode, Sp=Sp, nst=nst, ntile=ntile, Mp=[d['Kuu'].shape[0] for d in lat], F=[d['tab'].shape[1] for d in lat])
+        for k, v in want.items():
+            if fd[k] != v:
+                raise RuntimeError('test_path_weights: the stage ran with %s = %r, the binding sized its taps for %r' % (k, fd[k], v))
+        return dict(facts=fd, lat=lat)
+
+    def test_kron_path_weights(self, p, draws, n_samples, lik='onoff', jitter=1e-6):
+        """The weight stage of kron_sample_paths (lik 'onoff') or kron_head_sample_paths ('gaussian', 'bernoulli': the f fields alone)
+        through the product's own host function, with the device buffers snapshot behind every launch (zigp_test_kron_path_weights,
+        include/zigp_diag.h).  Returns dict(facts {nst, ntile, Mq0, Mq1, M1p, R4, F}, lat [per latent: dict(K, W: lists over the two factors,
+        (Mq, Mq); E (M, S); U, Sq (M); FZ, rhs, A1, B1, A2, V (S, M0, M1); tab (ntile, F, 16))])."""
+        two = lik == 'onoff'
+        tags = ('f', 'g') if two else ('f',)
+        code = _lib.LIK_ONOFF if two else self._head_lik('test_kron_path_weights', lik)
+        sp, keep, dims = self._pack_kron(p, tags=tags)
+        self._set_kron_kinds(p, tags)
+        S = int(n_samples)
+        draws, recs, keepd = self._kron_path_draws(sp, dims, tags, S, 0, None, draws, kron_kernel_kinds(p, tags))
+        nt = -(-S // 16)
+        nst = 4 if nt >= 4 else 2 if nt >= 2 else 1
+        ntile = -(-nt // nst) * nst
+        s = _lib.zigp_stage_kron_path_weights()
+        s.p, s.lik, s.S, s.jitter = C.pointer(sp), code, S, float(jitter)
+        s.draw_f = C.pointer(recs['f'])
+        if two:
+            s.draw_g = C.pointer(recs['g'])
+        lat = []
+        for h, tag in enumerate(tags):
+            M0, M1 = int(getattr(sp, 'M0' + tag)), int(getattr(sp, 'M1' + tag))
+            Mq, R = (-(-M0 // 128) * 128, -(-M1 // 128) * 128), int(draws[tag]['R'])
+            F = M0 * (-(-M1 // 4) * 4) + -(-R // 4) * 4
+            d = dict(K=[np.full((m, m), np.nan) for m in Mq], W=[np.full((m, m), np.nan) for m in Mq], E=np.full((M0 * M1, S), np.nan),
+                     U=np.full(M0 * M1, np.nan), Sq=np.full(M0 * M1, np.nan), tab=np.full((ntile, F, 16), np.nan))
+            for k in ('FZ', 'rhs', 'A1', 'B1', 'A2', 'V'):
+                d[k] = np.full((S, M0, M1), np.nan)
+            for k, v in d.items():
+                if isinstance(v, list):
+                    for q in range(2):
+                        getattr(s.lat[h], k)[q] = ptr(v[q])
+                else:
+                    setattr(s.lat[h], k, ptr(v))
+            lat.append(d)
+        facts = (C.c_int64 * _lib.KWF_COUNT)()
+        s.facts = C.cast(facts, C.POINTER(C.c_int64))
+        _check(self.lib, self.ctx, self.lib.zigp_test_kron_path_weights(self.ctx, C.byref(s)))
+        fd = _lib.unpack_facts(_lib.KWF_FACTS, facts)
+        for h, d in enumerate(lat):
+            got = (fd['nst'], fd['ntile'], fd['Mq0'][h], fd['Mq1'][h], fd['F'][h])
+            want = (nst, ntile, d['K'][0].shape[0], d['K'][1].shape[0], d['tab'].shape[1])
+            if got != want:
+                raise RuntimeError('test_kron_path_weights: the stage ran with (nst, ntile, Mq0, Mq1, F) = %r, the binding sized its taps for %r' % (got, want))
+        return dict(facts=fd, lat=lat)
+
     @staticmethod
     def kron_fit_sizes(shape, lik='onoff'):
         """block sizes of the free vector of kron_fit_steps (lik 'onoff': 17 blocks) or kron_head_fit_steps (10 blocks)"""
