@@ -425,6 +425,36 @@ int zigp_kron_head_fit_steps(zigp_ctx* ctx, const zigp_kron_params* shape, int32
 int zigp_kron_head_predict(zigp_ctx* ctx, const zigp_kron_params* p, int32_t lik, const double* Xnew, int64_t N,
                            double jitter, double f_mu, double* out4);
 
+/* ---- heads on the dense path: the same two baselines on the dense engine (scattered inputs, any D up to ZIGP_MAX_D, Matern kernels) ----
+ * GPflow 0.4.0's SVGP with likelihoods.Gaussian / likelihoods.Bernoulli: latent f alone under
+ *   ZIGP_LIK_GAUSSIAN   ve = -1/2 log 2pi - 1/2 log noise - 1/2 ((y - fm)^2 + fv) / noise            (scripts/svgp.py:198-200)
+ *   ZIGP_LIK_BERNOULLI  p = probit(fm / sqrt(1 + fv)) (1 - 2e-3) + 1e-3, ve = log(y == 1 ? p : 1 - p)   (scripts/classifier.py:139-140,210-217)
+ * in the arithmetic of the Kronecker heads' point-wise kernel.  lik belongs to the call: no context switch, no other call changes.
+ * Read: Mf, D, Zf, u_fm, u_fs_sqrt, ell_f, var_f and noise (Bernoulli ignores noise; its gradient comes back 0).  Mg and the g pointers are
+ * not read and may be 0 / NULL.  Written: the f fields and noise of grads (the g fields are left alone); *kl = KL_f, or 0 when include_kl is 0.
+ * Everything zigp_elbo / zigp_predict honour for latent f holds: the resident data, zigp_select_rows and row ranges, zigp_set_whiten and
+ * zigp_set_q_full (u_fs_sqrt and its gradient (Mf, Mf)), zigp_set_kernel(ctx, 0, kind), zigp_set_mean_function /
+ * zigp_get_mean_function_grad, D up to ZIGP_MAX_D under the same rules (Matern and Linear at D <= 8), zigp_set_chunk and zigp_set_overlap.
+ *
+ * HOW IT RUNS, AND WHAT THAT COSTS.  The chunk loop of the dense path is a two-latent schedule (paired tile lists, merged launches).  A head
+ * call runs that schedule as it is: the second latent is a library-owned PLACEHOLDER -- one inducing point at the origin, u = 0, s = 1
+ * (L_q = [1] with zigp_set_q_full), ell = 1 and var = 1 in every dimension, RBF whatever zigp_set_kernel(ctx, 1, ...) holds -- and only the
+ * point-wise launch differs (k_pointwise_head reads the planes of f and writes zero cotangents for the placeholder, so the placeholder's
+ * data gradient is exactly zero).  Its KL and its gradient blocks are dropped when the result is gathered.  The cost: the placeholder pads
+ * to one 128-row panel, so (128 / Mp)^2 of latent f's matrix work (Mp = Mf rounded up to 128) rides along, plus its launches -- about half
+ * an OnOff step with Mg = Mf, plus that share.  A one-latent schedule is a later change.
+ * ZIGP_EARG, naming the argument, with nothing enqueued and every output untouched: lik neither ZIGP_LIK_GAUSSIAN nor ZIGP_LIK_BERNOULLI;
+ * what zigp_elbo refuses for the f half of params; a communicator attached (zigp_comm_init: the heads are single-process).
+ * Not covered: zigp_fit_steps[_mode] (fit with zigp_head_elbo and a host optimiser), zigp_sample_paths, zigp_predict_density /
+ * zigp_predict_scores (zigp_density_rows / zigp_score_rows take rows 0-1 of zigp_head_predict with the same lik). */
+int zigp_head_elbo(zigp_ctx* ctx, const zigp_params* p, int32_t lik, double jitter, double scale, int64_t row_begin, int64_t row_end,
+                   int32_t include_kl, double* elbo_data, double* kl, zigp_grads* grads);
+/* out4 = 4 x N rows in the order of zigp_kron_head_predict: fmean, fvar, pfmean, pfvar (Gaussian: fmean, fvar + noise; Bernoulli: p,
+ * p - p^2).  The _device form takes and fills device memory of the context's GPU and is complete on return. */
+int zigp_head_predict(zigp_ctx* ctx, const zigp_params* p, int32_t lik, const double* Xnew, int64_t N, double jitter, double* out4);
+int zigp_head_predict_device(zigp_ctx* ctx, const zigp_params* p, int32_t lik, const double* dXnew, int64_t N, double jitter,
+                             double* d_out4);
+
 /* ---- predictive density of held-out data and the moments of y (new: the reference's likelihood leaves them out -- "not implemented
  * logp, conditional_mean and others", onoffgpf/OnOffLikelihood.py:28; GPflow's predict_density / predict_y) ----
  * OnOff: at a test row f ~ N(fm, fv) and g ~ N(gm, gv) are independent under q (rows 3-6 of zigp_predict, mean

@@ -176,6 +176,12 @@ int zigp_test_chunk_forward_white(zigp_ctx* ctx, int64_t Nc, int32_t need_grad, 
 /* The point-wise stage as a whitened call launches it: in every mode mean = sum of plane 0 (np1 rows), var = var_* + sum of plane 2 (np2
  * rows); plane 1 is not read.  Arguments as zigp_test_pointwise. */
 int zigp_test_pointwise_white(zigp_ctx* ctx, const zigp_stage_pointwise* a);
+/* One launch (a->repeat launches) of the head's point-wise kernel (zigp_head_elbo / zigp_head_predict, include/zigp.h) on caller-supplied
+ * partial planes of f: lik = ZIGP_LIK_GAUSSIAN or ZIGP_LIK_BERNOULLI; white = 0 reads the planes as zigp_test_pointwise does (mode 0 and 2:
+ * var = var_f - plane 1 + plane 2; mode 1: var_f + plane 2), white = 1 as zigp_test_pointwise_white (var_f + plane 2 in every mode).
+ * part_g, np*_g, var_g and g_offset are not read (part_g may be NULL); gm_g / gv_g come back as the zeros the kernel writes; out9 is the
+ * head's block, [4][row_end]: fmean, fvar, pfmean, pfvar; acc slot 3 is left as it was. */
+int zigp_test_pointwise_head(zigp_ctx* ctx, int32_t lik, int32_t white, const zigp_stage_pointwise* a);
 
 /* ---- full-covariance q(u) (zigp_set_q_full): the M x M stage of one latent.  The chunk loop of such a call runs the unwhitened
  * launches (zigp_test_chunk_forward with v = u, s2 = 1, W -> Lq for the second product, Rt = (T - I) W), so only this stage is new. ---- */

@@ -771,6 +771,9 @@ struct DenseCall {
   // a step of zigp_fit_steps: the parameter image and this hyperparameter block are on the device already (k_dense_fit_image), nothing is
   // staged, and a failed factorisation of latent h is left in d_info2[h] for the update kernel (p and hl carry the sizes only)
   const double* d_hyp = nullptr; int* d_info2 = nullptr;
+  // zigp_head_elbo / zigp_head_predict: ZIGP_LIK_GAUSSIAN or ZIGP_LIK_BERNOULLI -- the point-wise stage is k_pointwise_head, hl[1] is the
+  // library's placeholder latent (head_placeholder) and its KL and gradient blocks are left out of the result (dense_gather); 0: OnOff
+  int lik = 0;
   const double* hyp_rec(int h) const { return d_hyp ? d_hyp + h * DH_LAT : nullptr; }
 };
 
@@ -886,11 +889,22 @@ PwArgs dense_pointwise_args(zigp_ctx* c, const DenseCall& k, int64_t n0, int64_t
 //   a fit-loop step   -- d_hyp: always a gradient step, through the overload that reads the device hyperparameter block
 //   a White call      -- plane 2 = sum (s^2 - 1) A^2 in every mode (chunk_forward_white); a value-only pass has gm_f = NULL and writes no cotangents
 // (a WhiteFull value-only / predict call is the unwhitened form: var0 - sum A^2 + sum B^2)
-int dense_pointwise_launch(zigp_ctx* c, Param par, bool predict, bool need_grad, const PwArgs& a, const double* d_hyp) {
+// lik != 0 (DenseCall::lik): the head's kernel on the planes of f, in the same three forms; a head call has no device hyperparameter block
+static_assert(PWH_GAUSSIAN == ZIGP_LIK_GAUSSIAN && PWH_BERNOULLI == ZIGP_LIK_BERNOULLI, "the head kernel's LIK values are the ZIGP_LIK_* constants");
+template <int LIK>
+void pointwise_head_launch(zigp_ctx* c, const dim3& grid, const dim3& block, bool predict, bool plane2, const PwArgs& a) {
+  if (predict && plane2) hipLaunchKernelGGL((k_pointwise_head<LIK, true, true>), grid, block, 0, c->stream, a);
+  else if (predict) hipLaunchKernelGGL((k_pointwise_head<LIK, true, false>), grid, block, 0, c->stream, a);
+  else if (plane2) hipLaunchKernelGGL((k_pointwise_head<LIK, false, true>), grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL((k_pointwise_head<LIK, false, false>), grid, block, 0, c->stream, a);
+}
+int dense_pointwise_launch(zigp_ctx* c, Param par, bool predict, bool need_grad, const PwArgs& a, const double* d_hyp, int lik = 0) {
   ProfScope ps(c, PC_POINT);
   const dim3 grid((unsigned)(a.Nc / PW_PTS)), block(PW_THREADS);
   const bool plane2 = need_grad || d_hyp || par == Param::White;
-  if (d_hyp) hipLaunchKernelGGL((k_pointwise<false, true>), grid, block, 0, c->stream, a, d_hyp);
+  if (lik == ZIGP_LIK_GAUSSIAN) pointwise_head_launch<PWH_GAUSSIAN>(c, grid, block, predict, plane2, a);
+  else if (lik == ZIGP_LIK_BERNOULLI) pointwise_head_launch<PWH_BERNOULLI>(c, grid, block, predict, plane2, a);
+  else if (d_hyp) hipLaunchKernelGGL((k_pointwise<false, true>), grid, block, 0, c->stream, a, d_hyp);
   else if (predict && plane2) hipLaunchKernelGGL((k_pointwise<true, true>), grid, block, 0, c->stream, a);
   else if (predict) hipLaunchKernelGGL((k_pointwise<true, false>), grid, block, 0, c->stream, a);
   else if (plane2) hipLaunchKernelGGL((k_pointwise<false, true>), grid, block, 0, c->stream, a);
@@ -899,7 +913,7 @@ int dense_pointwise_launch(zigp_ctx* c, Param par, bool predict, bool need_grad,
   return 0;
 }
 int dense_pointwise(zigp_ctx* c, const DenseCall& k, int64_t n0, int64_t Nc) {
-  return dense_pointwise_launch(c, k.par, k.predict, k.need_grad, dense_pointwise_args(c, k, n0, Nc), k.d_hyp);
+  return dense_pointwise_launch(c, k.par, k.predict, k.need_grad, dense_pointwise_args(c, k, n0, Nc), k.d_hyp, k.lik);
 }
 
 // ---- chunk loop.  The MFMA-bound GEMMs stay on the main stream; with zigp_set_overlap(1) the HBM-bound kernels of a chunk -- the two
@@ -1037,11 +1051,14 @@ int dense_gather(zigp_ctx* c, DenseCall& k, double* elbo_data, double* kl, zigp_
   ZIGP_TRY(comm_allreduce(c, c->packed.p, n));
   double* hv = nullptr;
   ZIGP_TRY(download(c, c->packed.p, n, &hv));
+  // a head call: KL_f as the M x M forward left it (where k_dense_pack and zigp_prior_kl read it), not the packed sum with the placeholder's
+  double* hkl_f = nullptr;
+  if (k.lik) ZIGP_TRY(download(c, (is_white(k.par) ? c->lat[0].wh.p : c->lat[0].vec.p) + 3 * c->lat[0].Mp, 1, &hkl_f));
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));
   prof_collect(c);
   ZIGP_TRY(info_result(c, k.hinfo, "Kuu"));
   if (elbo_data) *elbo_data = hv[0];
-  if (kl) *kl = hv[1];
+  if (kl) *kl = !k.lik ? hv[1] : k.include_kl ? *hkl_f : 0.0;
   c->mean_db = hv[5];
   for (int d = 0; d < MAXD; ++d) c->mean_da[d] = hv[6 + d];
   if (k.need_grad) {
@@ -1049,7 +1066,7 @@ int dense_gather(zigp_ctx* c, DenseCall& k, double* elbo_data, double* kl, zigp_
     double* gu[2] = {grads->u_fm, grads->u_gm};
     double* gs[2] = {grads->u_fs_sqrt, grads->u_gs_sqrt};
     double* gl[2] = {grads->ell_f, grads->ell_g};
-    for (int h = 0; h < 2; ++h) {
+    for (int h = 0; h < (k.lik ? 1 : 2); ++h) {     // (a head call: the placeholder's blocks stay where they are)
       const size_t M = (size_t)c->lat[h].M;
       const double* o = hv + a.lat[h].out_off;
       if (gZ[h]) memcpy(gZ[h], o, sizeof(double) * M * D);
@@ -1058,7 +1075,8 @@ int dense_gather(zigp_ctx* c, DenseCall& k, double* elbo_data, double* kl, zigp_
       if (gs[h]) memcpy(gs[h], o + M * D + M, sizeof(double) * ns);
       if (gl[h]) memcpy(gl[h], o + M * D + M + ns, sizeof(double) * D);
     }
-    grads->var_f = hv[2]; grads->var_g = hv[3]; grads->noise = hv[4];
+    grads->var_f = hv[2]; grads->noise = hv[4];
+    if (!k.lik) grads->var_g = hv[3];
   }
   return 0;
 }
@@ -1098,17 +1116,35 @@ int dense_step(zigp_ctx* c, DenseCall& k) {
 }
 
 // shared driver for zigp_elbo / zigp_predict
+// The placeholder latent a head call puts in DenseCall::hl[1] (include/zigp.h "heads on the dense path"): one inducing point at the origin,
+// u = 0, s = 1 (the (1, 1) factor [1] of the full-covariance mode is the same double), ell = 1 in every dimension, var = 1, RBF
+struct HeadPlaceholder {
+  double Z[ZIGP_MAX_D], ell[ZIGP_MAX_D], u[1], s[1];
+  HeadPlaceholder() { for (int d = 0; d < ZIGP_MAX_D; ++d) { Z[d] = 0.0; ell[d] = 1.0; } u[0] = 0.0; s[0] = 1.0; }
+};
+const HeadPlaceholder& head_placeholder() { static const HeadPlaceholder h; return h; }
+
+int run_dense_lik(zigp_ctx* c, const zigp_params* p, int lik, const double* dX, const double* dY, int64_t Nrows, int D, double jitter,
+                  double scale, double g_offset, int64_t row_begin, int64_t row_end, int include_kl, bool predict, double* d_out9,
+                  double* elbo_data, double* kl, zigp_grads* grads);
 int run_dense(zigp_ctx* c, const zigp_params* p, const double* dX, const double* dY, int64_t Nrows, int D, double jitter,
               double scale, double g_offset, int64_t row_begin, int64_t row_end, int include_kl, bool predict, double* d_out9,
               double* elbo_data, double* kl, zigp_grads* grads) {
+  return run_dense_lik(c, p, 0, dX, dY, Nrows, D, jitter, scale, g_offset, row_begin, row_end, include_kl, predict, d_out9, elbo_data, kl, grads);
+}
+// lik != 0: a head call -- p is the library's copy of the caller's f half with the placeholder in the g fields (head_params)
+int run_dense_lik(zigp_ctx* c, const zigp_params* p, int lik, const double* dX, const double* dY, int64_t Nrows, int D, double jitter,
+                  double scale, double g_offset, int64_t row_begin, int64_t row_end, int include_kl, bool predict, double* d_out9,
+                  double* elbo_data, double* kl, zigp_grads* grads) {
   DenseCall k;
+  k.lik = lik;
   k.p = p; k.dX = dX; k.dY = dY; k.Nrows = Nrows; k.D = D; k.jitter = jitter; k.scale = scale; k.g_offset = g_offset;
   k.row_begin = row_begin; k.row_end = row_end; k.include_kl = include_kl; k.predict = predict; k.d_out9 = d_out9;
   k.need_grad = (grads != nullptr) && !predict;
   k.has_rows = row_end > row_begin;
   k.par = param_of(c);
   k.hl[0] = HostLatent{p->Mf, p->Zf, p->u_fm, p->u_fs_sqrt, p->ell_f, p->var_f, c->kern[0]};
-  k.hl[1] = HostLatent{p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g, c->kern[1]};
+  k.hl[1] = HostLatent{p->Mg, p->Zg, p->u_gm, p->u_gs_sqrt, p->ell_g, p->var_g, lik ? (int)ZIGP_KERN_RBF : c->kern[1]};
   k.ell_h[0] = p->ell_f; k.ell_h[1] = p->ell_g;
   ZIGP_TRY(dense_plan(c, k));
   ZIGP_TRY(dense_step(c, k));
@@ -1618,6 +1654,87 @@ int zigp_predict_device(zigp_ctx* c, const zigp_params* p, const double* dXnew, 
   ZIGP_TRY(require_device_ptrs(c, {dXnew, d_out9}, "zigp_predict_device: Xnew and out9 must be device memory of the context's GPU"));
   // rows in place: no copy in, no copy out; the call is complete on return (run_dense ends with the stream's synchronisation)
   return run_dense(c, p, dXnew, nullptr, N, p->D, jitter, 1.0, g_offset, 0, N, 0, true, d_out9, nullptr, nullptr, nullptr);
+}
+
+// ---- the heads on the dense path (include/zigp.h): latent f under a Gaussian or a Bernoulli likelihood ----
+}  // extern "C"
+namespace {
+// The refusals every head entry shares, then `q`: the caller's f half with the placeholder latent in the g fields.  validate_params' rules
+// for latent f alone: the g fields of `p` and the kernel of latent g (zigp_set_kernel(ctx, 1, ...)) are not read.
+int head_params(zigp_ctx* c, const char* who, const zigp_params* p, int32_t lik, zigp_params& q) {
+  const std::string w(who);
+  if (lik != ZIGP_LIK_GAUSSIAN && lik != ZIGP_LIK_BERNOULLI) return refuse(c, w, "lik must be ZIGP_LIK_GAUSSIAN or ZIGP_LIK_BERNOULLI");
+  if (c->comm) return refuse(c, w, "a communicator is attached (zigp_comm_init); the heads on the dense path are single-process");
+  if (!p) return refuse(c, w, "params is NULL");
+  if (p->Mf <= 0) return refuse(c, w, "params.Mf must be positive");
+  if (p->D <= 0 || p->D > ZIGP_MAX_D) return refuse(c, w, "params.D must be in [1, " ZIGP_MAX_D_STR "] (ZIGP_MAX_D)");
+  if (p->D > MAXD && is_matern(c->kern[0]))
+    return refuse(c, w, std::string("a ") + kern_name(c->kern[0]) + " kernel on latent f (zigp_set_kernel) and params.D = " + std::to_string(p->D) +
+                            ": the Matern kernels cover D in [1, 8] (the wide kernels are RBF only)");
+  if (p->D > MAXD && c->mean_on)
+    for (int d = 0; d < MAXD; ++d)
+      if (c->mean_a[d] != 0.0) return refuse(c, w, "a Linear mean function is set and params.D > 8: Linear covers D in [1, 8] (Zero and Constant work at every D)");
+  if (!p->Zf || !p->u_fm || !p->u_fs_sqrt || !p->ell_f) return refuse(c, w, "NULL pointer in params (Zf, u_fm, u_fs_sqrt, ell_f)");
+  if (!(p->var_f > 0)) return refuse(c, w, "params.var_f must be positive");
+  if (lik == ZIGP_LIK_GAUSSIAN && !(p->noise > 0)) return refuse(c, w, "params.noise must be positive (ZIGP_LIK_GAUSSIAN)");
+  for (int d = 0; d < p->D; ++d)
+    if (!(p->ell_f[d] > 0)) return refuse(c, w, "params.ell_f: lengthscales must be positive");
+  if (c->q_full) {
+    if (!c->whiten) return refuse(c, w, "zigp_set_q_full is on while whitening is off: the full-covariance q(u) exists for the whitened model only (zigp_set_whiten)");
+    for (int m = 0; m < p->Mf; ++m)
+      if (!(p->u_fs_sqrt[(size_t)m * p->Mf + m] != 0)) return refuse(c, w, "params.u_fs_sqrt has a zero (or NaN) diagonal entry (full q_sqrt, zigp_set_q_full)");
+  } else {
+    for (int m = 0; m < p->Mf; ++m)
+      if (!(p->u_fs_sqrt[m] > 0)) return refuse(c, w, "params.u_fs_sqrt must be positive (diagonal q_sqrt, transforms.positive)");
+  }
+  const HeadPlaceholder& h = head_placeholder();
+  q = *p;
+  q.Mg = 1; q.Zg = h.Z; q.u_gm = h.u; q.u_gs_sqrt = h.s; q.ell_g = h.ell; q.var_g = 1.0;
+  if (lik == ZIGP_LIK_BERNOULLI) q.noise = 1.0;     // not read by the Bernoulli head; its gradient comes back 0
+  return 0;
+}
+}  // namespace
+extern "C" {
+
+int zigp_head_elbo(zigp_ctx* c, const zigp_params* p, int32_t lik, double jitter, double scale, int64_t row_begin, int64_t row_end,
+                   int32_t include_kl, double* elbo_data, double* kl, zigp_grads* grads) {
+  if (!c) return ZIGP_EARG;
+  zigp_params q;
+  ZIGP_TRY(head_params(c, "zigp_head_elbo", p, lik, q));
+  if (!c->dX) return fail_arg(c, "zigp_head_elbo: no data set (call zigp_set_data first)");
+  if (p->D != c->D) return fail_arg(c, "zigp_head_elbo: params.D differs from the data's D");
+  if (row_begin < 0 || row_end > c->N || row_begin > row_end) return fail_arg(c, "zigp_head_elbo: bad row range");
+  if (!(jitter >= 0)) return fail_arg(c, "zigp_head_elbo: jitter must be >= 0");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  return run_dense_lik(c, &q, lik, c->dX, c->dY, c->N, c->D, jitter, scale, 0.0, row_begin, row_end, include_kl, false, nullptr, elbo_data, kl,
+                       grads);
+}
+
+int zigp_head_predict(zigp_ctx* c, const zigp_params* p, int32_t lik, const double* Xnew, int64_t N, double jitter, double* out4) {
+  if (!c) return ZIGP_EARG;
+  zigp_params q;
+  ZIGP_TRY(head_params(c, "zigp_head_predict", p, lik, q));
+  if (N < 0 || (N > 0 && (!Xnew || !out4))) return fail_arg(c, "zigp_head_predict: bad arguments (Xnew, N, out4)");
+  if (!(jitter >= 0)) return fail_arg(c, "zigp_head_predict: jitter must be >= 0");
+  if (N == 0) return ZIGP_OK;
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  const double* dX = nullptr;
+  ZIGP_TRY(stage_inputs(c, Xnew, N, q.D, false, &dX));
+  ZIGP_ENSURE(c, c->out9, (size_t)9 * N);     // the predict block of the row calls; a head fills its first four rows
+  ZIGP_TRY(run_dense_lik(c, &q, lik, dX, nullptr, N, q.D, jitter, 1.0, 0.0, 0, N, 0, true, c->out9.p, nullptr, nullptr, nullptr));
+  return finish_copies(c, {{out4, c->out9.p, (size_t)4 * N}});
+}
+
+int zigp_head_predict_device(zigp_ctx* c, const zigp_params* p, int32_t lik, const double* dXnew, int64_t N, double jitter, double* d_out4) {
+  if (!c) return ZIGP_EARG;
+  zigp_params q;
+  ZIGP_TRY(head_params(c, "zigp_head_predict_device", p, lik, q));
+  if (N < 0 || (N > 0 && (!dXnew || !d_out4))) return fail_arg(c, "zigp_head_predict_device: bad arguments (Xnew, N, out4)");
+  if (!(jitter >= 0)) return fail_arg(c, "zigp_head_predict_device: jitter must be >= 0");
+  if (N == 0) return ZIGP_OK;
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  ZIGP_TRY(require_device_ptrs(c, {dXnew, d_out4}, "zigp_head_predict_device: Xnew and out4 must be device memory of the context's GPU"));
+  return run_dense_lik(c, &q, lik, dXnew, nullptr, N, q.D, jitter, 1.0, 0.0, 0, N, 0, true, d_out4, nullptr, nullptr, nullptr);
 }
 
 int zigp_prior_kl(zigp_ctx* c, const zigp_params* p, double jitter, double* kl2) {
@@ -2147,12 +2264,15 @@ int zigp_test_latents_forward(zigp_ctx* c, const zigp_params* p, double jitter, 
 }
 
 namespace {
-int stage_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s, Param par) {
+// lik != 0: the head's kernel (zigp_test_pointwise_head) -- the g planes and their counts are not read, the predict block has four rows
+int stage_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s, Param par, int lik = 0) {
   if (!c) return ZIGP_EARG;
-  if (!s || s->mode < 0 || s->mode > 2 || s->repeat < 1 || !stage_chunk_ok(s->Nc) || !s->part_f || !s->part_g || !s->acc)
+  if (lik != 0 && lik != ZIGP_LIK_GAUSSIAN && lik != ZIGP_LIK_BERNOULLI)
+    return fail_arg(c, "zigp_test_pointwise_head: lik must be ZIGP_LIK_GAUSSIAN or ZIGP_LIK_BERNOULLI");
+  if (!s || s->mode < 0 || s->mode > 2 || s->repeat < 1 || !stage_chunk_ok(s->Nc) || !s->part_f || (!lik && !s->part_g) || !s->acc)
     return fail_arg(c, "zigp_test_pointwise: bad arguments");
-  if (s->np_f < 1 || s->np_g < 1 || s->np1_f < 0 || s->np2_f < 0 || s->np1_g < 0 || s->np2_g < 0 || s->np1_f > s->np_f || s->np2_f > s->np_f ||
-      s->np1_g > s->np_g || s->np2_g > s->np_g)
+  if (s->np_f < 1 || s->np1_f < 0 || s->np2_f < 0 || s->np1_f > s->np_f || s->np2_f > s->np_f ||
+      (!lik && (s->np_g < 1 || s->np1_g < 0 || s->np2_g < 0 || s->np1_g > s->np_g || s->np2_g > s->np_g)))
     return fail_arg(c, "zigp_test_pointwise: need 0 <= np1, np2 <= np");
   if (s->D < 1 || s->D > ZIGP_MAX_D || (s->D > MAXD && s->mean_on) || !s->X || s->Nrows <= 0 || s->n0 < 0 || s->row_end < s->n0 || s->row_end > s->Nrows || s->row_end > s->n0 + s->Nc)
     return fail_arg(c, "zigp_test_pointwise: need X (Nrows,D), 1 <= D <= " ZIGP_MAX_D_STR " (a mean function: D <= 8) and n0 <= row_end <= min(Nrows, n0 + Nc)");
@@ -2165,7 +2285,7 @@ int stage_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s, Param par) {
   ZIGP_TRY(stage_upload_rows(c, dx, s->X, s->Nrows, s->Nrows, s->D));
   if (s->Y) ZIGP_TRY(stage_upload_rows(c, dy, s->Y, s->Nrows, s->Nrows, 1));
   ZIGP_TRY(stage_upload_rows(c, pf, s->part_f, 3 * (int64_t)s->np_f, 3 * (int64_t)s->np_f, Nc));
-  ZIGP_TRY(stage_upload_rows(c, pg, s->part_g, 3 * (int64_t)s->np_g, 3 * (int64_t)s->np_g, Nc));
+  if (!lik) ZIGP_TRY(stage_upload_rows(c, pg, s->part_g, 3 * (int64_t)s->np_g, 3 * (int64_t)s->np_g, Nc));
   ZIGP_TRY(stage_upload_rows(c, c->pw_part, s->acc, (int64_t)nacc, (int64_t)nacc, 1));
   for (int h = 0; h < 2; ++h) { ZIGP_ENSURE(c, c->lat[h].gm, Nc); ZIGP_ENSURE(c, c->lat[h].gv, Nc); }
   if (s->mode == 2) { ZIGP_ENSURE(c, c->out9, (size_t)9 * s->row_end + 1); ZIGP_HIP(c, hipMemsetAsync(c->out9.p, 0, sizeof(double) * (9 * s->row_end + 1), c->stream)); }
@@ -2186,12 +2306,12 @@ int stage_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s, Param par) {
   for (int d = 0; d < MAXD; ++d) c->mean_a[d] = mean_a[d];
   a.part_f = pf.p; a.part_g = pg.p; a.np_f = s->np_f; a.np_g = s->np_g;
   a.np1_f = s->np1_f; a.np2_f = s->np2_f; a.np1_g = s->np1_g; a.np2_g = s->np2_g;
-  for (int r = 0; r < s->repeat; ++r) ZIGP_TRY(dense_pointwise_launch(c, par, k.predict, k.need_grad, a, nullptr));
+  for (int r = 0; r < s->repeat; ++r) ZIGP_TRY(dense_pointwise_launch(c, par, k.predict, k.need_grad, a, nullptr, lik));
   if (s->mode == 1) {
     ZIGP_TRY(stage_download_rows(c, c->lat[0].gm.p, s->gm_f, 1, Nc)); ZIGP_TRY(stage_download_rows(c, c->lat[0].gv.p, s->gv_f, 1, Nc));
     ZIGP_TRY(stage_download_rows(c, c->lat[1].gm.p, s->gm_g, 1, Nc)); ZIGP_TRY(stage_download_rows(c, c->lat[1].gv.p, s->gv_g, 1, Nc));
   }
-  if (s->mode == 2) ZIGP_TRY(stage_download_rows(c, c->out9.p, s->out9, 9, s->row_end));
+  if (s->mode == 2) ZIGP_TRY(stage_download_rows(c, c->out9.p, s->out9, lik ? 4 : 9, s->row_end));
   else ZIGP_TRY(stage_download_rows(c, c->pw_part.p, s->acc, 1, (int64_t)nacc));
   ZIGP_HIP(c, hipStreamSynchronize(c->stream));
   return ZIGP_OK;
@@ -2199,6 +2319,11 @@ int stage_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s, Param par) {
 }  // namespace
 int zigp_test_pointwise(zigp_ctx* c, const zigp_stage_pointwise* s) { return stage_pointwise(c, s, Param::Diag); }
 int zigp_test_pointwise_white(zigp_ctx* c, const zigp_stage_pointwise* s) { return stage_pointwise(c, s, Param::White); }
+int zigp_test_pointwise_head(zigp_ctx* c, int32_t lik, int32_t white, const zigp_stage_pointwise* s) {
+  if (!c) return ZIGP_EARG;
+  if (lik != ZIGP_LIK_GAUSSIAN && lik != ZIGP_LIK_BERNOULLI) return fail_arg(c, "zigp_test_pointwise_head: lik must be ZIGP_LIK_GAUSSIAN or ZIGP_LIK_BERNOULLI");
+  return stage_pointwise(c, s, white ? Param::White : Param::Diag, lik);
+}
 
 int zigp_test_kgrad(zigp_ctx* c, int32_t M, int32_t D, int64_t Nc, int64_t Nrows, int64_t n0, const double* Jp, const double* K, const double* alpha,
                     const double* gm, const double* gv, const double* X, const double* Z, const double* ell, const double* centre, int32_t exact,

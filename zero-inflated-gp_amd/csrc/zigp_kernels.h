@@ -434,6 +434,104 @@ k_pointwise(PwArgs p, HB... hb) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Point-wise stage of the single-latent heads on the dense path (zigp_head_elbo / zigp_head_predict): the SVGP baselines of the
+// reference on latent f alone,
+//   LIK = PWH_GAUSSIAN   (scripts/svgp.py:198-200):              ve = -1/2 log 2pi - 1/2 log s2 - 1/2 ((y - fm)^2 + fv) / s2
+//   LIK = PWH_BERNOULLI  (scripts/classifier.py:139-140,210-217): p = probit(fm / sqrt(1 + fv)), ve = log(y == 1 ? p : 1 - p)
+// in the arithmetic of k_kron_head_pointwise (zigp_kron.hip), expression for expression, so the two paths agree on equal (fm, fv).
+// A function of its own beside k_pointwise (whose code does not move): it reads the partial-row planes of f only -- the same planes, the
+// same summation order (wave g adds the rows g, g + PW_GROUPS, ...; wave 0 adds the groups in order) and the same mean function as
+// pw_block -- and PwArgs' part_g / np*_g / var_g / g_offset are not read.  The call's second latent is a placeholder whose cotangents
+// are zero: gm_g = gv_g = 0 for every point of the chunk.  acc[blk] += {ve, d noise, sum gv_f, (nothing), mean-function sums}: pw_block's
+// slots.  PREDICT: four rows at out9 (ld9 apart) in the order of zigp_kron_head_predict -- fmean, fvar, pfmean, pfvar (Gaussian: fm,
+// fv + s2; Bernoulli: p, p (1 - p)).
+// ---------------------------------------------------------------------------------------------
+constexpr int PWH_GAUSSIAN = 1, PWH_BERNOULLI = 2;   // ZIGP_LIK_GAUSSIAN, ZIGP_LIK_BERNOULLI (include/zigp.h; asserted in zigp_dense.hip)
+template <int LIK, bool PREDICT, bool GRADVAR>
+__global__ void __launch_bounds__(PW_THREADS)
+k_pointwise_head(PwArgs p) {
+  static_assert(LIK == PWH_GAUSSIAN || LIK == PWH_BERNOULLI, "a head is Gaussian or Bernoulli");
+  __shared__ double grp[3][PW_GROUPS][PW_PTS];
+  const int tid = threadIdx.x, blk = blockIdx.x;
+  const int lane = tid & (PW_PTS - 1), g = tid / PW_PTS;
+  const int64_t n = (int64_t)blk * PW_PTS + lane;
+  {
+    double fm = 0.0, fsq = 0.0, fs2 = 0.0;
+    for (int q = g; q < p.np1_f; q += PW_GROUPS) {
+      fm += p.part_f[(int64_t)(0 * p.np_f + q) * p.Nc + n];
+      if (!GRADVAR) fsq += p.part_f[(int64_t)(1 * p.np_f + q) * p.Nc + n];
+    }
+    for (int q = g; q < p.np2_f; q += PW_GROUPS) fs2 += p.part_f[(int64_t)(2 * p.np_f + q) * p.Nc + n];
+    grp[0][g][lane] = fm; grp[1][g][lane] = fsq; grp[2][g][lane] = fs2;
+  }
+  __syncthreads();
+  if (g != 0) return;
+  double tot[3];
+#pragma unroll
+  for (int v = 0; v < 3; ++v) {
+    double a = grp[v][0][lane];
+#pragma unroll
+    for (int w = 1; w < PW_GROUPS; ++w) a += grp[v][w][lane];
+    tot[v] = a;
+  }
+  double fm = tot[0];
+  const double fv = GRADVAR ? p.var_f + tot[2] : p.var_f - tot[1] + tot[2];
+  const bool valid = (p.n0 + n) < p.row_end;
+  double xs[MAXD];
+  if (p.mean_on) {
+    double m = p.mean_b;
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d) {
+      xs[d] = (d < p.D && valid) ? p.X[(p.n0 + n) * p.D + d] : 0.0;
+      m = fma(p.mean_a[d], xs[d], m);
+    }
+    fm += m;
+  }
+  const double y = (valid && p.Y) ? p.Y[p.n0 + n] : 0.0;
+  double ve, dfm, dfv, dnoise = 0.0, pm, pv;
+  if (LIK == PWH_GAUSSIAN) {
+    const double noise = p.noise;
+    const double inv = 1.0 / noise, res = y - fm, q = res * res + fv;
+    ve = -0.5 * 1.8378770664093454836 - 0.5 * log(noise) - 0.5 * q * inv;
+    dfm = res * inv; dfv = -0.5 * inv; dnoise = -0.5 * inv + 0.5 * q * inv * inv;
+    pm = fm; pv = fv + noise;
+  } else {
+    const double c1 = 1.0 - 2.e-3, c0 = 1.e-3;
+    const double r = 1.0 / sqrt(1.0 + fv), z = fm * r;
+    const double pr = 0.5 * (1.0 + erf(z * 0.70710678118654752440)) * c1 + c0;   // classifier.py:216-217
+    const bool on = (y == 1.0);                                                  // tf.equal(y, 1) :214
+    ve = log(on ? pr : 1.0 - pr);
+    const double dp = on ? 1.0 / pr : -1.0 / (1.0 - pr);
+    const double dz = dp * c1 * 0.39894228040143267794 * exp(-0.5 * z * z);
+    dfm = dz * r; dfv = dz * (-0.5 * z / (1.0 + fv));
+    // p - p^2 as the density kernel forms the variance of y (k_density_rows: p (1 - p), each operation rounded), so that rows 2 and 3 are
+    // zigp_density_rows' ymean and yvar at rows 0 and 1 bit for bit; within 2 ulp of k_kron_head_pointwise's pr - pr * pr
+    pm = pr; pv = __dmul_rn(pr, 1.0 - pr);
+  }
+  if (PREDICT) {
+    if (valid) {
+      double* q = p.out9 + (p.n0 + n);
+      q[0 * p.ld9] = fm; q[1 * p.ld9] = fv; q[2 * p.ld9] = pm; q[3 * p.ld9] = pv;
+    }
+    return;
+  }
+  // masked by selection, not by a product with 0: a point beyond row_end leaves exact zeros whatever its planes hold
+  const double gmf = valid ? p.scale * dfm : 0.0, gvf = valid ? p.scale * dfv : 0.0;
+  if (p.gm_f) { p.gm_f[n] = gmf; p.gv_f[n] = gvf; p.gm_g[n] = 0.0; p.gv_g[n] = 0.0; }
+  const double s0 = wave_sum(valid ? p.scale * ve : 0.0), s1 = wave_sum(valid ? p.scale * dnoise : 0.0), s2 = wave_sum(gvf);
+  double* a = p.acc + (int64_t)blk * PW_ACC;
+  if (lane == 0) { a[0] += s0; a[1] += s1; a[2] += s2; }
+  if (p.mean_on) {   // d/d mean_b = sum gm_f, d/d mean_a[d] = sum gm_f x_d
+    const double sb = wave_sum(gmf);
+    if (lane == 0) a[4] += sb;
+    for (int d = 0; d < min(p.D, MAXD); ++d) {
+      const double sa = wave_sum(gmf * xs[d]);
+      if (lane == 0) a[5 + d] += sa;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Kuf -> (Z, ell, var) cotangent reductions.  A block owns KG_ROWS rows of K / J' and sweeps the chunk's columns, so
 // gm, gv and the D coordinates of x_n are loaded once per column and reused for every row.  The Kuf cotangent is formed
 // on the fly, F[m,n] = dK = alpha[m] gm[n] + 2 gv[n] J'[m,n]:

@@ -2,7 +2,9 @@
 No GPflow, no TensorFlow: the graph is replaced by libzigp.so (include/zigp.h)."""
 from .OnOffSVGP import OnOffSVGP
 from .OnOffLikelihood import OnOffLikelihood
+from .svgp import SVGP
 from . import kernels
+from . import likelihoods
 from . import mean_functions
 
-__all__ = ['OnOffSVGP', 'OnOffLikelihood', 'kernels', 'mean_functions']
+__all__ = ['OnOffSVGP', 'OnOffLikelihood', 'SVGP', 'kernels', 'likelihoods', 'mean_functions']

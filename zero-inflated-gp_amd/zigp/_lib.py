@@ -344,6 +344,10 @@ SIGNATURES = {
     'zigp_kron_head_fit_steps': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_int32, C.POINTER(zigp_kron_head_fit_opts), dp, dp, dp, C.c_int64,
                                            C.c_int64, C.c_int32, C.c_void_p, C.c_int64, dp, dp, C.c_double, C.c_double, C.c_int32, dp, dp]),
     'zigp_kron_head_predict': (C.c_int, [C.c_void_p, C.POINTER(zigp_kron_params), C.c_int32, dp, C.c_int64, C.c_double, C.c_double, dp]),
+    'zigp_head_elbo': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_int32, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_int32, dp, dp,
+                                 C.POINTER(zigp_grads)]),
+    'zigp_head_predict': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_int32, dp, C.c_int64, C.c_double, dp]),
+    'zigp_head_predict_device': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_int32, C.c_void_p, C.c_int64, C.c_double, C.c_void_p]),
     'zigp_density_rows': (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, C.c_int64, C.c_double, dp, dp, C.c_int32, dp, dp]),
     'zigp_predict_density': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), dp, dp, C.c_int64, C.c_double, C.c_double, dp, dp, C.c_int32, dp, dp]),
     'zigp_predict_density_device': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
@@ -382,6 +386,7 @@ SIGNATURES = {
     'zigp_test_pointwise': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_pointwise)]),
     'zigp_test_chunk_forward_white': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(zigp_stage_latent), C.POINTER(C.c_int64)]),
     'zigp_test_pointwise_white': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_pointwise)]),
+    'zigp_test_pointwise_head': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(zigp_stage_pointwise)]),
     'zigp_test_q_full_forward': (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp]),
     'zigp_test_q_full_dlq': (C.c_int, [C.c_void_p, C.c_int32, dp, dp, C.c_int32, dp]),
     'zigp_test_kgrad': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int32, dp]),

@@ -119,6 +119,17 @@ class _Packed:
         self.struct = s
 
 
+HEAD_PARAM_KEYS = ('Zf', 'u_fm', 'u_fs_sqrt', 'ell_f', 'var_f', 'noise')     # what head_elbo reads of p, and the keys of its gradient
+
+
+def head_placeholder(D, q_full=False):
+    """The g fields of the placeholder latent a head call on the dense path runs beside latent f (include/zigp.h "heads on the dense
+    path"): one inducing point at the origin, u = 0, s = 1 (q_full: the (1, 1) factor [1]), ell = 1 and var = 1 in every dimension, RBF.
+    elbo / predict on dict(p, **head_placeholder(D)) enqueue the very launches head_elbo / head_predict do, point-wise stage apart."""
+    return dict(Zg=np.zeros((1, int(D))), u_gm=np.zeros(1), u_gs_sqrt=np.ones((1, 1)) if q_full else np.ones(1), ell_g=np.ones(int(D)),
+                var_g=1.0, kern_g='rbf')
+
+
 def _scalar(v):
     """float of a Python number or a size-1 array (np.squeeze on a plain float costs 1.5 us)"""
     return float(v) if isinstance(v, (float, int)) else float(np.asarray(v).reshape(-1)[0])
@@ -591,6 +602,74 @@ class DenseEngine:
         if N:
             _check(self.lib, self.ctx, self.lib.zigp_predict_device(self.ctx, C.byref(pk.struct), C.c_void_p(X_t.data_ptr()), N, float(jitter),
                                                                      float(g_offset), C.c_void_p(out.data_ptr())))
+        return out
+
+    # ---- heads on the dense path: latent f under a Gaussian or a Bernoulli likelihood (include/zigp.h "heads on the dense path") ----
+    def _prepare_head(self, who, p, lik):
+        """(packed parameters, ZIGP_LIK_*, len(mean_a) or None): p holds the f fields (HEAD_PARAM_KEYS; 'noise' may be left out for
+        'bernoulli') plus 'whiten', 'q_diag', 'kern_f' and the mean function as in elbo; whatever g fields it carries are not read"""
+        lik = self._head_lik(who, lik)
+        if 'Zf' not in p:
+            raise ValueError('%s: p needs Zf, u_fm, u_fs_sqrt, ell_f, var_f (and noise for the Gaussian head)' % who)
+        D = as_f64(p['Zf']).shape[-1]
+        q = dict(p, **head_placeholder(D, q_full=not p.get('q_diag', True)))
+        if lik == _lib.LIK_BERNOULLI:
+            q.setdefault('noise', 1.0)
+        pk = _Packed(q)
+        kinds = kernel_kinds(q)
+        mean_D = self._set_mean_function(p, pk.D)
+        self.set_whiten(p.get('whiten', False))
+        self.set_q_full(not p.get('q_diag', True))
+        _check(self.lib, self.ctx, self.lib.zigp_set_kernel(self.ctx, 0, kinds[0]))     # latent g's setting is not read by a head call
+        return pk, lik, mean_D
+
+    def head_elbo(self, p, lik, jitter=1e-6, scale=1.0, rows=None, include_kl=True, need_grad=True):
+        """The SVGP bound of latent f under lik = 'gaussian' or 'bernoulli' on the resident data (zigp_head_elbo): returns
+        (elbo_data, kl, grads or None), ELBO = elbo_data - kl, kl = KL_f.  grads has the keys HEAD_PARAM_KEYS (noise: 0 for 'bernoulli')
+        and, with a mean function, mean_a / mean_b.  rows = (begin, end) of the active rows, as in elbo."""
+        pk, lik, mean_D = self._prepare_head('head_elbo', p, lik)
+        r0, r1 = (0, self.N) if rows is None else rows
+        ed, kl = C.c_double(0), C.c_double(0)
+        gs, g = None, None
+        if need_grad:
+            g = dict(Zf=np.zeros((pk.Mf, pk.D)), u_fm=np.zeros(pk.Mf), u_fs_sqrt=np.zeros((pk.Mf, pk.Mf) if pk.q_full else pk.Mf),
+                     ell_f=np.zeros(pk.D))
+            gs = _lib.zigp_grads()
+            for k, a in g.items():
+                setattr(gs, k, ptr(a))
+        rc = self.lib.zigp_head_elbo(self.ctx, C.byref(pk.struct), lik, float(jitter), float(scale), int(r0), int(r1),
+                                     1 if include_kl else 0, C.byref(ed), C.byref(kl), C.byref(gs) if gs is not None else None)
+        _check(self.lib, self.ctx, rc)
+        if need_grad:
+            g['var_f'], g['noise'] = gs.var_f, gs.noise
+            if mean_D is not None:
+                da, db = np.zeros(max(mean_D, 1)), C.c_double(0)
+                _check(self.lib, self.ctx, self.lib.zigp_get_mean_function_grad(self.ctx, ptr(da), mean_D, C.byref(db)))
+                g['mean_a'], g['mean_b'] = da[:mean_D], db.value
+        return ed.value, kl.value, g
+
+    def head_predict(self, p, Xnew, lik, jitter=1e-6):
+        """(4, N): fmean, fvar, pfmean, pfvar in the order of kron_head_predict (zigp_head_predict) -- 'gaussian': fmean, fvar + noise;
+        'bernoulli': p = probit(fmean / sqrt(1 + fvar)) through the reference's clamp, p - p^2."""
+        pk, lik, _ = self._prepare_head('head_predict', p, lik)
+        Xnew, _ = self._host_xy(pk, Xnew)
+        out = np.zeros((4, Xnew.shape[0]))
+        _check(self.lib, self.ctx, self.lib.zigp_head_predict(self.ctx, C.byref(pk.struct), lik, ptr(Xnew), Xnew.shape[0], float(jitter), ptr(out)))
+        return out
+
+    def head_predict_device(self, p, X_t, lik, jitter=1e-6, out=None):
+        """head_predict on a torch CUDA float64 tensor (N, D) of the engine's device; returns (or fills `out` with) a (4, N) CUDA tensor."""
+        import torch
+        pk, lik, _ = self._prepare_head('head_predict_device', p, lik)
+        N = self._device_xy('head_predict_device', pk, X_t)
+        if out is None:
+            out = torch.empty((4, N), dtype=torch.float64, device=X_t.device)
+        elif not (self._device_f64(out) and tuple(out.shape) == (4, N)):
+            raise ValueError('head_predict_device: out must be a contiguous float64 (4,N) tensor on the same device')
+        torch.cuda.current_stream(self.device).synchronize()      # the engine's streams are not ordered after torch's
+        if N:
+            _check(self.lib, self.ctx, self.lib.zigp_head_predict_device(self.ctx, C.byref(pk.struct), lik, C.c_void_p(X_t.data_ptr()), N,
+                                                                          float(jitter), C.c_void_p(out.data_ptr())))
         return out
 
     # ---- predictive density of held-out data (include/zigp.h "predictive density") ----
@@ -1761,10 +1840,17 @@ class DenseEngine:
         return res
 
     def test_pointwise(self, mode, part_f, part_g, np1, np2, X, Y, n0, row_end, var_f, var_g, noise, g_offset=0.0, scale=1.0,
-                       mean=None, repeat=1, acc=None, whiten=False):
+                       mean=None, repeat=1, acc=None, whiten=False, head=None):
         """The point-wise stage of one chunk.  mode 'value' / 'grad' / 'predict'; part_* [3][np][Nc]; np1 / np2 = (f, g) rows to add of planes
-        0, 1 / of plane 2; mean = None or (a (D), b); whiten: the launch of a whitened call (mean = plane 0, var = var_* + plane 2 in every mode).  Returns dict(gm_f, gv_f, gm_g, gv_g (grad), acc [Nc/64][PW_ACC], out9 (predict))."""
-        part_f, part_g = as_f64(part_f), as_f64(part_g)
+        0, 1 / of plane 2; mean = None or (a (D), b); whiten: the launch of a whitened call (mean = plane 0, var = var_* + plane 2 in every mode).  Returns dict(gm_f, gv_f, gm_g, gv_g (grad), acc [Nc/64][PW_ACC], out9 (predict)).
+        head = 'gaussian' / 'bernoulli': the head's kernel instead (zigp_test_pointwise_head) -- part_g may be None, np1 / np2 are the f
+        counts (or pairs whose second entry is ignored), out9 is the head's (4, row_end) block."""
+        part_f = as_f64(part_f)
+        if head is not None:
+            lik = self._head_lik('test_pointwise', head)
+            part_g = np.zeros((3, 1, part_f.shape[2])) if part_g is None else part_g
+            np1, np2 = [(int(v), 0) if np.isscalar(v) else v for v in (np1, np2)]
+        part_g = as_f64(part_g)
         X = as_f64(X)
         if X.ndim == 1: X = X[:, None]
         Nc = part_f.shape[2]
@@ -1791,8 +1877,11 @@ class DenseEngine:
                 out[k] = np.zeros(Nc)
                 setattr(s, k, ptr(out[k]))
         if mode == 'predict':
-            out['out9'] = np.zeros((9, int(row_end)))
+            out['out9'] = np.zeros((4 if head is not None else 9, int(row_end)))
             s.out9 = ptr(out['out9'])
+        if head is not None:
+            _check(self.lib, self.ctx, self.lib.zigp_test_pointwise_head(self.ctx, lik, 1 if whiten else 0, C.byref(s)))
+            return out
         fn = self.lib.zigp_test_pointwise_white if whiten else self.lib.zigp_test_pointwise
         _check(self.lib, self.ctx, fn(self.ctx, C.byref(s)))
         return out
