@@ -70,6 +70,33 @@ int zigp_test_gemm(zigp_ctx* ctx, int32_t transA, int32_t transB, int64_t m, int
 /* L = chol(A) (lower), W = L^-1, A is (n,n) SPD; either output may be NULL.  split_k != 0: the blocked chain's products run as k slices +
  * an ordered reduction, as in the M x M forward of zigp_elbo (0: one workgroup per tile, as in the Kronecker panel path). */
 int zigp_test_potrf_trtri(zigp_ctx* ctx, int64_t n, const double* A, double* L, double* W, int32_t split_k);
+/* The same chain, tapped: ONE job of size n (1 .. 4096; padded to Mp = n rounded up to 128, nb = Mp / 128 block columns) through
+ * potrf_trtri_jobs itself (csrc/zigp_host.h) -- the launches of zigp_test_potrf_trtri, none more, none fewer.  L, W, T: the WHOLE padded
+ * [Mp][Mp] images as the chain leaves them (L, W: identity in the padding, exact zero above the diagonal; T, the scratch of the inverse:
+ * ZIGP_STAGE_SENTINEL_BYTE wherever no launch wrote).  snap: [snap_cap][Mp][Mp] images, one stream-ordered device-to-device copy right
+ * behind each launch, in launch order, downloaded after the call's one synchronisation: per block column j the diagonal kernel (two images:
+ * L, then W), the panel product (L) and the trailing update (L) -- the last two only for j < nb - 1 -- then per doubling distance
+ * b = 1, 2, 4 .. < nb the products tri1 (T) and tri2 (W).  The image behind one launch is the "before" image of the next (the panel product
+ * runs in place).  snap_cap >= launches + nb, with launches = nb + 2 (nb - 1) + 2 ceil(log2 nb).
+ * facts: ZIGP_PSF_REC header slots, then ZIGP_PSF_PER slots per launch: kind (ZIGP_PSL_*), j or b, output tiles, split-K slices S (0: one
+ * workgroup per tile, split_k = 0), npan of a diagonal launch (32-row panels it factors; the rest of the block is identity), index of the
+ * launch's first image (-1 without snap).  facts_cap >= ZIGP_PSF_REC + ZIGP_PSF_PER * launches.
+ * A failed factorisation returns ZIGP_ENOTPD with zigp_last_info = the 1-based pivot (also facts[ZIGP_PSF_INFO]); L, W, T, snap and facts
+ * are filled all the same (the failing diagonal kernel writes nothing, the launches behind it run on what is there).  Any out pointer may
+ * be NULL.  ZIGP_EARG (context still usable): n outside 1 .. 4096, A == NULL, a capacity too small. */
+enum { ZIGP_PSL_DIAG = 0, ZIGP_PSL_PANEL = 1, ZIGP_PSL_TRAIL = 2, ZIGP_PSL_TRI1 = 3, ZIGP_PSL_TRI2 = 4 };
+enum { ZIGP_PSF_MP = 0, ZIGP_PSF_NB, ZIGP_PSF_LAUNCHES, ZIGP_PSF_IMAGES, ZIGP_PSF_INFO, ZIGP_PSF_REC = 8, ZIGP_PSF_PER = 6 };
+typedef struct zigp_stage_potrf {
+  int64_t n;
+  int32_t split_k, reserved;
+  const double* A;        /* (n,n) symmetric; the lower triangle is read */
+  double *L, *W, *T;      /* out [Mp][Mp] */
+  double* snap;           /* out [snap_cap][Mp][Mp] */
+  int64_t snap_cap;
+  int64_t* facts;         /* out [facts_cap] */
+  int64_t facts_cap;
+} zigp_stage_potrf;
+int zigp_test_potrf_stages(zigp_ctx* ctx, const zigp_stage_potrf* a);
 
 /* The chunk loop's cross-covariance kernel on its own: K (M,N) row-major = var * exp(-0.5 |(z_m - x_n) / ell|^2) as k_kuf_build writes a
  * Kuf panel (kern.K(X, Xnew), onofftf/main.py:266; its exponential is hand-written, see csrc/zigp_kernels.h).  X (N,D), Z (M,D), ell (D). */

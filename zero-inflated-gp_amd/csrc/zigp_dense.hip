@@ -2050,6 +2050,58 @@ int zigp_test_potrf_trtri(zigp_ctx* c, int64_t n, const double* A, double* L, do
   return 0;
 }
 
+static_assert(PT_REC == ZIGP_PSF_PER && PT_DIAG == ZIGP_PSL_DIAG && PT_TRI2 == ZIGP_PSL_TRI2, "the tap's records are the hook's facts");
+int zigp_test_potrf_stages(zigp_ctx* c, const zigp_stage_potrf* a) {
+  if (!c) return ZIGP_EARG;
+  if (!a || a->n < 1 || a->n > 4096 || !a->A) return fail_arg(c, "zigp_test_potrf_stages: bad arguments");
+  const int n = (int)a->n, Mp = (int)round_up(n, BM), nb = Mp / BM;
+  int levels = 0;
+  for (int b = 1; b < nb; b *= 2) ++levels;
+  const int launches = nb + 2 * (nb - 1) + 2 * levels, images = launches + nb;
+  if (a->facts && a->facts_cap < ZIGP_PSF_REC + (int64_t)PT_REC * launches) return fail_arg(c, "zigp_test_potrf_stages: facts_cap too small");
+  if (a->snap && a->snap_cap < images) return fail_arg(c, "zigp_test_potrf_stages: snap_cap too small");
+  ZIGP_HIP(c, hipSetDevice(c->device));
+  const size_t mm = (size_t)Mp * Mp;
+  std::vector<double> ha(mm, 0.0);
+  for (int64_t i = 0; i < Mp; ++i) {
+    if (i < n) memcpy(&ha[i * Mp], &a->A[i * n], sizeof(double) * n);
+    else ha[i * Mp + i] = 1.0;
+  }
+  DevBuf dl, dw, dt, dplanes, dsnap;
+  ZIGP_ENSURE(c, dl, mm); ZIGP_ENSURE(c, dw, mm); ZIGP_ENSURE(c, dt, mm);
+  if (a->snap) ZIGP_ENSURE(c, dsnap, mm * images);
+  ZIGP_HIP(c, hipMemcpyAsync(dl.p, ha.data(), sizeof(double) * mm, hipMemcpyHostToDevice, c->stream));
+  ZIGP_HIP(c, hipMemsetAsync(dt.p, ZIGP_STAGE_SENTINEL_BYTE, sizeof(double) * mm, c->stream));   // T "as left": what no launch wrote holds the sentinel
+  ZIGP_HIP(c, hipMemsetAsync(c->d_info, 0, sizeof(int), c->stream));
+  PotrfTap tap;
+  tap.snap = a->snap ? dsnap.p : nullptr;
+  tap.cap = images;
+  const PotrfJob job = {dl.p, dw.p, dt.p, Mp, true, n, 0.0, false, a->split_k ? &dplanes : nullptr};
+  const hipStream_t st = c->stream;
+  ZIGP_TRY(potrf_trtri_jobs(c, 1, &job, &st, &tap));
+  int h = 0;
+  ZIGP_HIP(c, hipMemcpyAsync(&h, c->d_info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  ZIGP_HIP(c, hipStreamSynchronize(c->stream));     // the one synchronisation; everything below is a download
+  if (a->L) ZIGP_HIP(c, hipMemcpy(a->L, dl.p, sizeof(double) * mm, hipMemcpyDeviceToHost));
+  if (a->W) ZIGP_HIP(c, hipMemcpy(a->W, dw.p, sizeof(double) * mm, hipMemcpyDeviceToHost));
+  if (a->T) ZIGP_HIP(c, hipMemcpy(a->T, dt.p, sizeof(double) * mm, hipMemcpyDeviceToHost));
+  if (a->snap && tap.nsnap > 0) ZIGP_HIP(c, hipMemcpy(a->snap, dsnap.p, sizeof(double) * mm * tap.nsnap, hipMemcpyDeviceToHost));
+  if (a->facts) {
+    a->facts[ZIGP_PSF_MP] = Mp; a->facts[ZIGP_PSF_NB] = nb; a->facts[ZIGP_PSF_LAUNCHES] = (int64_t)tap.rec.size() / PT_REC;
+    a->facts[ZIGP_PSF_IMAGES] = tap.nsnap; a->facts[ZIGP_PSF_INFO] = h;
+    for (int k = ZIGP_PSF_INFO + 1; k < ZIGP_PSF_REC; ++k) a->facts[k] = 0;
+    std::copy(tap.rec.begin(), tap.rec.end(), a->facts + ZIGP_PSF_REC);
+  }
+  if (h != 0) {
+    c->info = h;
+    char b[256];
+    snprintf(b, sizeof(b), "Cholesky decomposition was not successful for A: the input might not be positive definite (pivot %d)", h);
+    c->err = b;
+    return ZIGP_ENOTPD;
+  }
+  return 0;
+}
+
 // ---- stage diagnostics (include/zigp_diag.h): one chunk's stage on caller-supplied operands, through the chunk loop's own functions ----
 namespace {
 // host (rows x cols, row-major) -> device [rows_p][cols] with zero rows behind it

@@ -357,13 +357,15 @@ k_sk_finish_tiles(const double* __restrict__ planes, const GemmTile* __restrict_
 }
 template <int AL, int BL, class Gen>
 static int run_gemm_sk_tiles(zigp_ctx* c, DevBuf& planes, const std::string& key, Gen gen, const double* A, const double* B, double* C, int64_t Mp, double alpha,
-                             bool accum = false) {
+                             bool accum = false, int* S_out = nullptr) {
   std::vector<GemmTile> base;
   gen(base);
+  if (S_out) *S_out = 0;
   if (base.empty()) return 0;
   int minlen = 1 << 30;
   for (const GemmTile& t : base) minlen = std::min(minlen, t.kend - t.kbeg);
   const int count = (int)base.size(), S = std::max(1, std::min(std::min(8, minlen), 512 / count));
+  if (S_out) *S_out = S;
   TileList tl;
   ZIGP_TRY(get_tiles(c, "skt:" + key + ":" + std::to_string(S), [&](std::vector<GemmTile>& v) {
     for (int s = 0; s < S; ++s)
@@ -386,11 +388,34 @@ static int run_gemm_sk_tiles(zigp_ctx* c, DevBuf& planes, const std::string& key
 // tol_dev (fit loop): the pivot tolerance is read from this device word instead of piv_tol; info: status word of this job (default: c->d_info)
 struct PotrfJob { double* L; double* W; double* T; int Mp; bool want_W; int Mreal; double piv_tol; bool prepared; DevBuf* planes;
                   const double* tol_dev = nullptr; int* info = nullptr; };
-static int potrf_trtri_jobs(zigp_ctx* c, int njobs, const PotrfJob* jobs, const hipStream_t* streams) {
+// Tap of job 0 (zigp_test_potrf_stages, include/zigp_diag.h): one record per launch -- kind, block column j or doubling distance b, output
+// tiles, split-K slices (0: one workgroup per tile), npan of a diagonal launch, index of its first image -- and, when `snap` is set, a
+// stream-ordered device-to-device copy of what the launch wrote (diagonal: L then W; panel / trailing: L; tri1: T; tri2: W) right behind
+// it.  nullptr (every production caller): nothing but the launches below is enqueued.
+enum { PT_DIAG = 0, PT_PANEL = 1, PT_TRAIL = 2, PT_TRI1 = 3, PT_TRI2 = 4, PT_REC = 6 };
+struct PotrfTap { double* snap = nullptr; int cap = 0, nsnap = 0; std::vector<int64_t> rec; };
+static int potrf_trtri_jobs(zigp_ctx* c, int njobs, const PotrfJob* jobs, const hipStream_t* streams, PotrfTap* tap = nullptr) {
   const int kb = BM / BK;  // k-steps per block
+  auto count_of = [](auto& gen) { std::vector<GemmTile> v; gen(v); return (int)v.size(); };
+  auto note = [&](int q, int kind, int idx, int tiles, int S, int npan, const double* a, const double* b) -> int {   // on job q's stream
+    if (!tap || q != 0) return 0;
+    const size_t mm = (size_t)jobs[0].Mp * jobs[0].Mp;
+    const int64_t r[PT_REC] = {kind, idx, tiles, S, npan, tap->snap ? tap->nsnap : -1};
+    tap->rec.insert(tap->rec.end(), r, r + PT_REC);
+    for (const double* src : {a, b}) {
+      if (!src || !tap->snap) continue;
+      if (tap->nsnap >= tap->cap) { c->err = "potrf tap: more images than the caller sized"; return ZIGP_EARG; }
+      ZIGP_HIP(c, hipMemcpyAsync(tap->snap + (size_t)tap->nsnap++ * mm, src, sizeof(double) * mm, hipMemcpyDeviceToDevice, c->stream));
+    }
+    return 0;
+  };
   const size_t shm = sizeof(double) * PB * PBLD;
   int nbmax = 0;
   for (int q = 0; q < njobs; ++q) nbmax = std::max(nbmax, jobs[q].Mp / BM);
+  // Every diagonal block must hold a real row: with npan = 0 the closing inverse of potrf_diag_lds would index LDS 32 rows below the block.
+  // Every caller pads with Mp = round_up(Mreal, 128), Mreal >= 1, so this refuses nothing that is passed today.
+  for (int q = 0; q < njobs; ++q)
+    if (jobs[q].Mreal >= 0 && jobs[q].Mreal <= jobs[q].Mp - BM) return fail_arg(c, "potrf_trtri_jobs: a diagonal block without a real row");
   // c->d_info is cleared by the caller (several factorizations may share one check_info)
   for (int q = 0; q < njobs; ++q) {
     if (jobs[q].prepared) continue;
@@ -413,16 +438,21 @@ static int potrf_trtri_jobs(zigp_ctx* c, int njobs, const PotrfJob* jobs, const 
           if (J.tol_dev) hipLaunchKernelGGL(k_potrf_diag<const double*>, dim3(1), dim3(1024), shm, c->stream, Ajj, Ajj, Wjj, (int64_t)Mp, j * BM, info, (nreal_j + PNB - 1) / PNB, J.tol_dev);
           else hipLaunchKernelGGL(k_potrf_diag<double>, dim3(1), dim3(1024), shm, c->stream, Ajj, Ajj, Wjj, (int64_t)Mp, j * BM, info, (nreal_j + PNB - 1) / PNB, J.piv_tol);
           ZIGP_HIP(c, hipGetLastError());
+          ZIGP_TRY(note(q, PT_DIAG, j, 1, 0, (nreal_j + PNB - 1) / PNB, Lb, J.want_W ? Wb : nullptr));
         } else if (j + 1 < nb && step == 1) {
           auto genp = [&](std::vector<GemmTile>& v) {
             for (int bi = j + 1; bi < nb; ++bi) v.push_back(mk_tile(bi, j, j * kb, (j + 1) * kb));
           };
           const std::string tag = "po_p:" + std::to_string(nb) + ":" + std::to_string(j);
           // L[bi][j] = A[bi][j] * W_jj^T   (in place: each tile reads only itself and W_jj)
-          if (J.planes) { ZIGP_TRY((run_gemm_sk_tiles<LAY_KCONTIG, LAY_KCONTIG>(c, *J.planes, tag, genp, Lb, Wb, Lb, Mp, 1.0))); continue; }
-          TileList tp;
-          ZIGP_TRY(get_tiles(c, tag, genp, tp));
-          ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_KCONTIG, false>(c, tp, mk_args(Lb, Mp, Wb, Mp, Lb, Mp), EpiStore())));
+          int S = 0;
+          if (J.planes) ZIGP_TRY((run_gemm_sk_tiles<LAY_KCONTIG, LAY_KCONTIG>(c, *J.planes, tag, genp, Lb, Wb, Lb, Mp, 1.0, false, &S)));
+          else {
+            TileList tp;
+            ZIGP_TRY(get_tiles(c, tag, genp, tp));
+            ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_KCONTIG, false>(c, tp, mk_args(Lb, Mp, Wb, Mp, Lb, Mp), EpiStore())));
+          }
+          if (tap) ZIGP_TRY(note(q, PT_PANEL, j, count_of(genp), S, 0, Lb, nullptr));
         } else if (j + 1 < nb && step == 2) {
           auto gens = [&](std::vector<GemmTile>& v) {
             for (int bi = j + 1; bi < nb; ++bi)
@@ -430,10 +460,14 @@ static int potrf_trtri_jobs(zigp_ctx* c, int njobs, const PotrfJob* jobs, const 
           };
           const std::string tag = "po_s:" + std::to_string(nb) + ":" + std::to_string(j);
           // A[bi][bj] -= L[bi][j] L[bj][j]^T
-          if (J.planes) { ZIGP_TRY((run_gemm_sk_tiles<LAY_KCONTIG, LAY_KCONTIG>(c, *J.planes, tag, gens, Lb, Lb, Lb, Mp, -1.0, true))); continue; }
-          TileList ts;
-          ZIGP_TRY(get_tiles(c, tag, gens, ts));
-          ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_KCONTIG, false>(c, ts, mk_args(Lb, Mp, Lb, Mp, Lb, Mp, -1.0), EpiAccum())));
+          int S = 0;
+          if (J.planes) ZIGP_TRY((run_gemm_sk_tiles<LAY_KCONTIG, LAY_KCONTIG>(c, *J.planes, tag, gens, Lb, Lb, Lb, Mp, -1.0, true, &S)));
+          else {
+            TileList ts;
+            ZIGP_TRY(get_tiles(c, tag, gens, ts));
+            ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_KCONTIG, false>(c, ts, mk_args(Lb, Mp, Lb, Mp, Lb, Mp, -1.0), EpiAccum())));
+          }
+          if (tap) ZIGP_TRY(note(q, PT_TRAIL, j, count_of(gens), S, 0, Lb, nullptr));
         }
       }
   }
@@ -472,15 +506,23 @@ static int potrf_trtri_jobs(zigp_ctx* c, int njobs, const PotrfJob* jobs, const 
         };
         const std::string tag = std::to_string(nb) + ":" + std::to_string(b);
         if (step == 0) {          // T = L21 W11
-          if (J.planes) { ZIGP_TRY((run_gemm_sk_tiles<LAY_KCONTIG, LAY_MNCONTIG>(c, *J.planes, "tri1:" + tag, gen1, J.L, J.W, J.T, Mp, 1.0))); continue; }
-          TileList t1;
-          ZIGP_TRY(get_tiles(c, "tri1:" + tag, gen1, t1));
-          ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_MNCONTIG, false>(c, t1, mk_args(J.L, Mp, J.W, Mp, J.T, Mp), EpiStore())));
+          int S = 0;
+          if (J.planes) ZIGP_TRY((run_gemm_sk_tiles<LAY_KCONTIG, LAY_MNCONTIG>(c, *J.planes, "tri1:" + tag, gen1, J.L, J.W, J.T, Mp, 1.0, false, &S)));
+          else {
+            TileList t1;
+            ZIGP_TRY(get_tiles(c, "tri1:" + tag, gen1, t1));
+            ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_MNCONTIG, false>(c, t1, mk_args(J.L, Mp, J.W, Mp, J.T, Mp), EpiStore())));
+          }
+          if (tap) ZIGP_TRY(note(q, PT_TRI1, b, count_of(gen1), S, 0, J.T, nullptr));
         } else {                  // W21 = -W22 T
-          if (J.planes) { ZIGP_TRY((run_gemm_sk_tiles<LAY_KCONTIG, LAY_MNCONTIG>(c, *J.planes, "tri2:" + tag, gen2, J.W, J.T, J.W, Mp, -1.0))); continue; }
-          TileList t2;
-          ZIGP_TRY(get_tiles(c, "tri2:" + tag, gen2, t2));
-          ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_MNCONTIG, false>(c, t2, mk_args(J.W, Mp, J.T, Mp, J.W, Mp, -1.0), EpiStore())));
+          int S = 0;
+          if (J.planes) ZIGP_TRY((run_gemm_sk_tiles<LAY_KCONTIG, LAY_MNCONTIG>(c, *J.planes, "tri2:" + tag, gen2, J.W, J.T, J.W, Mp, -1.0, false, &S)));
+          else {
+            TileList t2;
+            ZIGP_TRY(get_tiles(c, "tri2:" + tag, gen2, t2));
+            ZIGP_TRY((run_gemm<LAY_KCONTIG, LAY_MNCONTIG, false>(c, t2, mk_args(J.W, Mp, J.T, Mp, J.W, Mp, -1.0), EpiStore())));
+          }
+          if (tap) ZIGP_TRY(note(q, PT_TRI2, b, count_of(gen2), S, 0, J.W, nullptr));
         }
       }
   return 0;

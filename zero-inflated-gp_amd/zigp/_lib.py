@@ -266,6 +266,15 @@ class zigp_stage_kron_path_weights(C.Structure):   # include/zigp_diag.h
                 ('facts', C.POINTER(C.c_int64))]
 
 
+PSL_KINDS = ('diag', 'panel', 'trail', 'tri1', 'tri2')   # include/zigp_diag.h ZIGP_PSL_*
+PSF_REC, PSF_PER = 8, 6                                    # ZIGP_PSF_*: header slots (Mp, nb, launches, images, info), slots per launch
+
+
+class zigp_stage_potrf(C.Structure):   # include/zigp_diag.h
+    _fields_ = [('n', C.c_int64), ('split_k', C.c_int32), ('reserved', C.c_int32), ('A', dp), ('L', dp), ('W', dp), ('T', dp), ('snap', dp),
+                ('snap_cap', C.c_int64), ('facts', C.POINTER(C.c_int64)), ('facts_cap', C.c_int64)]
+
+
 def unpack_facts(layout, arr):
     """facts array -> dict (an entry with more than one value: a list)"""
     out, o = {}, 0
@@ -381,6 +390,7 @@ SIGNATURES = {
     'zigp_test_gemm': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp]),
     'zigp_test_kuf': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, dp, dp, dp, C.c_double, dp]),
     'zigp_test_potrf_trtri': (C.c_int, [C.c_void_p, C.c_int64, dp, dp, dp, C.c_int32]),
+    'zigp_test_potrf_stages': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_potrf)]),
     'zigp_test_chunk_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(zigp_stage_latent), C.POINTER(C.c_int64)]),
     'zigp_test_latents_forward': (C.c_int, [C.c_void_p, C.POINTER(zigp_params), C.c_double, C.c_int32, C.POINTER(dp), C.POINTER(dp)]),
     'zigp_test_pointwise': (C.c_int, [C.c_void_p, C.POINTER(zigp_stage_pointwise)]),

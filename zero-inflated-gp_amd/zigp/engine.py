@@ -1749,6 +1749,41 @@ class DenseEngine:
         _check(self.lib, self.ctx, self.lib.zigp_test_potrf_trtri(self.ctx, n, ptr(A), ptr(L), ptr(W), int(bool(split_k))))
         return L, W
 
+    def test_potrf_stages(self, A, split_k=False, snapshots=True):
+        """The blocked Cholesky + inverse of ONE (n,n) matrix through potrf_trtri_jobs itself, tapped (zigp_test_potrf_stages).  Returns
+        dict(L, W, T: the whole padded [Mp][Mp] images; T holds _lib.STAGE_SENTINEL where no launch wrote), Mp, nb, info (0 or the 1-based
+        failing pivot), launches: a list of dict(kind in _lib.PSL_KINDS, idx (block column j / doubling distance b), tiles, S (split-K slices;
+        0: one workgroup per tile), npan, snap: the [Mp][Mp] images copied right behind the launch -- diag: (L, W); panel, trail: (L,);
+        tri1: (T,); tri2: (W,) -- or () without snapshots).  A failed factorisation raises NotPositiveDefiniteError with this dict as
+        its `.stages` attribute (zigp_last_info holds the pivot)."""
+        A = as_f64(A)
+        if A.ndim != 2 or A.shape[0] != A.shape[1]:
+            raise ValueError('test_potrf_stages: A must be square')
+        n = A.shape[0]
+        Mp = max(1, (n + 127) // 128) * 128
+        nb = Mp // 128
+        launches = nb + 2 * (nb - 1) + 2 * max(0, (nb - 1).bit_length())
+        out = dict(L=np.zeros((Mp, Mp)), W=np.zeros((Mp, Mp)), T=np.zeros((Mp, Mp)))
+        snap = np.zeros((launches + nb, Mp, Mp)) if snapshots else None
+        facts = np.zeros(_lib.PSF_REC + _lib.PSF_PER * launches, dtype=np.int64)
+        a = _lib.zigp_stage_potrf(n=n, split_k=int(bool(split_k)), A=ptr(A), L=ptr(out['L']), W=ptr(out['W']), T=ptr(out['T']),
+                                  snap=None if snap is None else ptr(snap), snap_cap=0 if snap is None else snap.shape[0],
+                                  facts=facts.ctypes.data_as(C.POINTER(C.c_int64)), facts_cap=facts.size)
+        rc = self.lib.zigp_test_potrf_stages(self.ctx, C.byref(a))
+        if rc not in (0, _lib.ZIGP_ENOTPD):
+            _check(self.lib, self.ctx, rc)
+        out.update(Mp=int(facts[0]), nb=int(facts[1]), info=int(facts[4]), launches=[])
+        for k in range(int(facts[2])):
+            kind, idx, tiles, S, npan, first = (int(v) for v in facts[_lib.PSF_REC + _lib.PSF_PER * k:_lib.PSF_REC + _lib.PSF_PER * (k + 1)])
+            imgs = () if first < 0 else tuple(snap[first + i] for i in range(2 if kind == 0 else 1))
+            out['launches'].append(dict(kind=_lib.PSL_KINDS[kind], idx=idx, tiles=tiles, S=S, npan=npan, snap=imgs))
+        if rc != 0:
+            try:
+                _check(self.lib, self.ctx, rc)
+            except NotPositiveDefiniteError as e:
+                e.stages = out
+                raise
+        return out
 
     # ---- stage diagnostics (include/zigp_diag.h): one chunk's stage through the chunk loop's own functions ----
     def test_chunk_forward(self, lat_f, lat_g, Nc, need_grad, only=None, whiten=False):
